@@ -2,11 +2,16 @@
 loss + backward through all steps + Adam [+ RCCL gradient all-reduce]) on the RESISC45
 16-agent / 16-step configuration (BASELINE.json; SURVEY section 8d "C3"), synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver with torch.distributed.run, one rank per GPU; every rank
 works on its own batch shard (weak scaling), gradients are all-reduced over RCCL.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times K steps and prints the line (``roofline`` and
+``cpu_baseline`` are null).  ``--full`` adds what takes runs of its own: the per-class roofline
+sweep (one extra iteration per kernel class) and, for c3 on one GPU, the CPU baseline.
+``--dump-outputs DIR`` writes what the last timed step computed to DIR/<name>.npy (rank 0).
 
 The model is the product's own ``ModelsWrapper`` (reference init recipe), every random draw of
 the episode comes from the library's counter-based generator (no torch kernel in the timed
@@ -51,6 +56,7 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md "Peak BF16/FP16 MFMA" (den
 # fp32 products on the bf16 pipe (gemm_split.hip): six bf16 MFMA products per fp32 product
 PEAK_F32_VIA_BF16X6_TFLOPS = PEAK_BF16_MFMA_TFLOPS / 6.0
 PEAK_HBM_GBS = 8000.0         # MI355X_MICROARCH.md "HBM3E peak BW" (spec)
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: data bytes of all files together (.npy headers aside)
 
 # kernel classes of marl_profile_begin (include/marl_hip.h)
 CLASSES = {
@@ -207,6 +213,28 @@ def matrix_products_note(lib, cfg) -> str:
     return note
 
 
+def dump_outputs(path: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """Writes every tensor as path/<name>.npy: float32, integer outputs as float64 (which holds them
+    exactly).  If they do not fit in ``budget`` bytes together, the larger ones are cut to a fixed
+    sample of their flattened elements (sorted indices from numpy's default_rng(0), so the same
+    sizes give the same sample in every run); the smaller ones are written whole."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    host = {k: (v.detach().float() if v.is_floating_point() else v.detach().double()).cpu().numpy()
+            for k, v in arrays.items()}
+    names = sorted(host, key=lambda k: host[k].nbytes)
+    left = budget
+    for i, k in enumerate(names):
+        a = host[k]
+        keep = min(a.size, left // (len(names) - i) // a.itemsize)
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        left -= a.nbytes
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -223,7 +251,14 @@ def main() -> None:
                     help="draw positions / states / noise with torch kernels (round-1 behaviour)")
     ap.add_argument("--graph", action="store_true", help="replay the iteration as a captured hipGraph")
     ap.add_argument("--config", choices=["c3"] + sorted(OTHER), default="c3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-class roofline sweep and (c3, one GPU, unless --no-cpu-baseline) the CPU "
+                         "baseline; a plain run leaves roofline / cpu_baseline null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.graph and args.rollout_only:
         ap.error("--graph replays the whole training iteration: not with --rollout-only")
     global C3, NA, NS, IMG
@@ -333,12 +368,18 @@ def main() -> None:
         ok = ok and bool(th.isfinite(flat.params).all())
     if not ok:
         raise SystemExit("bench post-check failed: non-finite outputs or positions / actions out of range")
+    if args.dump_outputs and rank == 0:
+        arrays = {k: getattr(out, k) for k in ("step_preds", "step_log_probas", "step_values", "step_pos",
+                                                "step_actions")}
+        if state["scalars"] is not None:  # (training iteration: loss terms, updated weights, gradients)
+            arrays.update(scalars=state["scalars"], params=flat.params, grads=flat.grads)
+        dump_outputs(args.dump_outputs, arrays)
 
     # ---- rooflines ---------------------------------------------------------------------------
     # (1) whole iteration against both rooflines: algorithmic FLOPs / bytes of the
     #     timed work vs the fp32-MFMA and HBM peaks; (2) the dominant kernel class, found by a
     #     per-class HIP-event sweep (one extra iteration per class, events on the launch stream).
-    # Every rank runs the extra iterations (they contain the gradient all-reduce).
+    # Every rank runs the extra iterations (they contain the gradient all-reduce).  --full only.
     roofline = None
     cpu = None
     f_fwd, by_fwd, by_train, cls_train, cls_fwd = algorithmic_work(C3, IMG[0])
@@ -353,7 +394,7 @@ def main() -> None:
             return one_step()
         state["out"], state["scalars"] = fa.iteration(img, y, draw_episode_device(eng, rng_seed, 1 << 30))
 
-    for c in CLASSES:
+    for c in (CLASSES if args.full else ()):
         if c not in cls_flops:  # (rollout: no weight-gradient / CNN-backward launches)
             continue
         if rank == 0:
@@ -363,7 +404,7 @@ def main() -> None:
             tot, cnt = C.c_double(0), C.c_int(0)
             lib.marl_profile_end(C.byref(tot), C.byref(cnt))
             sweep[c] = (tot.value, cnt.value)
-    if rank == 0:
+    if rank == 0 and args.full:
         t_iter = dt / args.steps
         mult = 1.0 if args.rollout_only else 3.0
         flops_iter = mult * f_fwd * steps_per_iter_gpu
@@ -421,7 +462,7 @@ def main() -> None:
                                             "sources (sha256 differs)")
     if distributed:
         dist.barrier()
-    if rank == 0 and not args.no_cpu_baseline and args.gpus == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and args.gpus == 1:
         cpu = cpu_baseline()
 
     if rank == 0:

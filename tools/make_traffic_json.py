@@ -56,7 +56,7 @@ if lstm:
     out["per_iteration_2xfetch_plus_write_gb"] = round(out["whole_run_2xfetch_plus_write_gb"] / (lstm // 16), 3)
 out["src_sha256"] = csrc_sha256()
 out["source"] = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --kernel-trace (two separate passes) -- python3 "
-                 "bench.py --steps 2 --warmup 1 --no-cpu-baseline; per-launch averages per kernel class; summaries in "
+                 "bench.py --steps 2 --warmup 1 --full --no-cpu-baseline; per-launch averages per kernel class; summaries in "
                  f"profiles/{rnd}_bench_c3_pmc_*.csv")
 json.dump(out, open(f"profiles/{rnd}_traffic.json", "w"), indent=1)
 print(json.dumps(out, indent=1)[:1500])

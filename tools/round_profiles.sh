@@ -40,31 +40,31 @@ pmc() {  # pmc NAME "COUNTERS" [bench-args...] : one pass -> profiles/${R}_bench
   python3 tools/rocpd_pmc.py $DB $P/${R}_bench_${tag}_pmc_$name.csv > /dev/null
   if [ "$name" = sq_valu_mfma_busy_cycles ]; then python3 tools/rocpd_clock.py $DB $P/${R}_bench_${tag}_clock.csv 15 > /dev/null; fi
 }
-prof c3 --steps 20 --warmup 5
-pmc fetch_size FETCH_SIZE
-pmc write_size WRITE_SIZE
-pmc sq_valu_mfma_busy_cycles "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
-pmc sq_waits "SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY"
-pmc sq_lds "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS"
-pmc sq_insts "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_INSTS_SALU"
+prof c3 --full --steps 20 --warmup 5
+pmc fetch_size FETCH_SIZE c3 --full
+pmc write_size WRITE_SIZE c3 --full
+pmc sq_valu_mfma_busy_cycles "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" c3 --full
+pmc sq_waits "SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY" c3 --full
+pmc sq_lds "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS" c3 --full
+pmc sq_insts "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_INSTS_SALU" c3 --full
 rm -f $P/${R}_traffic.json
 python3 tools/make_traffic_json.py $R
-bench_line $P/${R}_bench_c3.json
-bench_line $P/${R}_bench_c3_rollout_only.json --rollout-only --no-cpu-baseline
+bench_line $P/${R}_bench_c3.json --full
+bench_line $P/${R}_bench_c3_rollout_only.json --rollout-only --full --no-cpu-baseline
 for c in c2 c4 c5; do
-  bench_line $P/${R}_bench_$c.json --config $c --no-cpu-baseline
-  prof $c --config $c --steps 10 --warmup 3
+  bench_line $P/${R}_bench_$c.json --config $c --full --no-cpu-baseline
+  prof $c --config $c --full --steps 10 --warmup 3
 done
-prof c3_rollout_only --rollout-only --steps 10 --warmup 3
+prof c3_rollout_only --rollout-only --full --steps 10 --warmup 3
 # the strong-scaling operating point of the C3 shapes (256 images over 8 GPUs = 32 per GPU)
-bench_line $P/${R}_bench_c3_b32.json --batch 32 --no-cpu-baseline
+bench_line $P/${R}_bench_c3_b32.json --batch 32 --full --no-cpu-baseline
 # BASELINE configs[3]'s weak-scaling variant: AID at 256 images per GPU
-bench_line $P/${R}_bench_c4_b256.json --config c4 --batch 256 --no-cpu-baseline --steps 30 --warmup 5
-prof c4_b256 --config c4 --batch 256 --steps 6 --warmup 2
+bench_line $P/${R}_bench_c4_b256.json --config c4 --batch 256 --full --no-cpu-baseline --steps 30 --warmup 5
+prof c4_b256 --config c4 --batch 256 --full --steps 6 --warmup 2
 for c in c4 c5; do
-  pmc fetch_size FETCH_SIZE $c --config $c
-  pmc write_size WRITE_SIZE $c --config $c
-  pmc sq_valu_mfma_busy_cycles "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" $c --config $c
+  pmc fetch_size FETCH_SIZE $c --config $c --full
+  pmc write_size WRITE_SIZE $c --config $c --full
+  pmc sq_valu_mfma_busy_cycles "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" $c --config $c --full
 done
 # the kernel-level lab records, regenerated from THIS tree (a stale one was cited as proof)
 rm -f $P/${R}_g3_lab.json gpurun_out/g3_lab.json
