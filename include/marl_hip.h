@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define MARL_ABI_VERSION 3
+#define MARL_ABI_VERSION 4
 
 #define MARL_OK 0
 #define MARL_EINVAL (-1)   /* bad configuration / null pointer          */
@@ -242,6 +242,39 @@ int marl_step_forward(const marl_config* cfg, const void* weights_ws, size_t wei
 /* (actions_out int64 [R], logp_out [R]: optional - when both are given the call also samples the
  * action and its log-probability, core/agent.py:53-61, from noise [R,nA] ~ Exp(1) if given, else
  * from the library's generator at (rng_seed, rng_offset).) */
+
+/* Autograd through ONE step (ABI 4): every ModelsWrapper.forward / MultiAgent.act call of the reference adds
+ * to the autograd graph (networks/models.py:78-138, core/agent.py:40-68); a user loop over act() - the
+ * reference's own EpisodeSampler is one (core/episode.py:32-82) - back-propagates through each of them.
+ *
+ * marl_step_forward_train: marl_step_forward with the same arguments and bit-identical outputs, which also
+ * keeps the activations marl_step_backward needs in a caller-owned STEP workspace: the training layout of one
+ * step, marl_workspace_sizes(cfg with nb_steps = 1, train = 1) (cfg->nb_steps is ignored by both calls).  One
+ * workspace per live step; it is free again after its backward. */
+int marl_step_forward_train(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                            void* step_ws, size_t step_ws_bytes,
+                            const float* obs, const float* msg, const float* norm_pos,
+                            const float* h, const float* c, const float* hc, const float* cc,
+                            float* probs, float* values, float* preds, float* new_msg,
+                            float* h_out, float* c_out, float* hc_out, float* cc_out,
+                            const float* noise, uint64_t rng_seed, uint64_t rng_offset,
+                            int64_t* actions_out, float* logp_out, void* stream);
+
+/* loss.backward() through the step of the matching marl_step_forward_train call (same weights: call it before
+ * the next marl_pack_weights).  obs is that call's observation [R,C,f,f] (the first convolution's weight
+ * gradient reads it).  Upstream gradients, each NULL = zero: g_probs [R,nA]; g_logp [R] = dL/d log p[a] of the
+ * action the forward SAMPLED (NULL unless the forward sampled); g_values [R]; g_preds [R,nC]; g_msg [R,n_m];
+ * g_h, g_c [R,n_b]; g_hc, g_cc [R,n_a] - of the step's outputs.  Writes dL/d(param) into grads_host[i] (tight
+ * reference shapes, OVERWRITTEN - accumulation over steps is the caller's, as in marl_episode_backward) and
+ * the input gradients d_msg [R,n_m] (through the message mean: networks/message.py:5-17), d_h, d_c [R,n_b],
+ * d_hc, d_cc [R,n_a] (tight; each NULL = not wanted).  No gradient w.r.t. obs / norm_pos (the reference's are
+ * crops of an image batch that does not require grad: core/environment.py:95-126). */
+int marl_step_backward(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
+                       void* step_ws, size_t step_ws_bytes, const float* obs,
+                       const float* g_probs, const float* g_logp, const float* g_values,
+                       const float* g_preds, const float* g_msg, const float* g_h, const float* g_c,
+                       const float* g_hc, const float* g_cc, float* const* grads_host,
+                       float* d_msg, float* d_h, float* d_c, float* d_hc, float* d_cc, void* stream);
 
 /* Environment.normalized_positions (core/environment.py:74-81): out[r,d] = pos[r,d] / size_d. */
 int marl_normalize_positions(const int64_t* pos, float* out, int rows, int h, int w, void* stream);

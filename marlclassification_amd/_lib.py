@@ -13,7 +13,7 @@ from typing import Optional
 
 MARL_MAX_CNN_LAYERS = 5
 MARL_MAX_ACTIONS = 16
-MARL_ABI_VERSION = 3
+MARL_ABI_VERSION = 4
 MARL_COUNTERS_BYTES = 32
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,7 +74,8 @@ EXPORTS = (
     "marl_counters_set marl_counters_tick marl_graph_begin marl_graph_end marl_graph_launch "
     "marl_graph_destroy marl_image_bytes marl_image_build marl_gemm_nt_images marl_gemm_nt_images_batch "
     "marl_lstm_images marl_gemm_tn_images marl_gemm_tn_images_scratch marl_plan_query "
-    "marl_gemm_tn_images_cell marl_gemm_tn_images_cell_scratch marl_backward_heads_event"
+    "marl_gemm_tn_images_cell marl_gemm_tn_images_cell_scratch marl_backward_heads_event "
+    "marl_step_forward_train marl_step_backward"
 ).split()
 
 _lib: Optional[C.CDLL] = None
@@ -109,6 +110,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_adam_step.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _f, _f, _f, _f, _f, _vp, _vp]
     lib.marl_step_forward.argtypes = ([_cfgp, _vp, _sz, _vp, _sz] + [_vp] * 15 + [_vp, _u64, _u64, _vp, _vp] +
                                       [_vp])
+    lib.marl_step_forward_train.argtypes = lib.marl_step_forward.argtypes
+    lib.marl_step_backward.argtypes = [_cfgp, _vp, _sz, _vp, _sz] + [_vp] * 10 + [C.POINTER(_vp)] + [_vp] * 6
     lib.marl_normalize_positions.argtypes = [_vp, _vp, _i, _i, _i, _vp]
     lib.marl_gemm_nt.argtypes = [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]
     lib.marl_gemm_nt_weights.argtypes = [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]

@@ -1,12 +1,14 @@
 """MultiAgent: recurrent state + policy sampling around ModelsWrapper (reference
 core/agent.py).  ``act`` is one ``marl_step_forward`` call that also samples
-(argmax(p / q), q ~ Exp(1): what th.multinomial(p, 1) computes) and returns log p[a]."""
+(argmax(p / q), q ~ Exp(1): what th.multinomial(p, 1) computes) and returns log p[a].
+With autograd enabled it is one autograd node (networks.models._StepFunction): log p[a],
+the predictions, the values and the carried state / message are differentiable."""
 
 from dataclasses import dataclass
 
 import torch as th
 
-from ..networks.models import ModelsWrapper, RecurrentOutput
+from ..networks.models import ModelsWrapper, RecurrentOutput, _StepFunction, step_needs_graph
 
 
 @dataclass
@@ -63,9 +65,16 @@ class MultiAgent:
             self.__calls += 1
         else:
             noise = th.empty(na, nb, model.nb_action, device=observation.device).exponential_(1.0)
-        probs, values, preds, msg, h, c, hc, cc, actions, logp = eng.step_forward(
-            observation, self.__last_msg, norm_pos, hid.h, hid.c, hid.h_caret, hid.c_caret, noise,
-            rng=rng)
+        state = (self.__last_msg, hid.h, hid.c, hid.h_caret, hid.c_caret)
+        if step_needs_graph(model, observation, norm_pos, *state):
+            named = list(model.named_parameters())
+            probs, values, preds, msg, h, c, hc, cc, actions, logp = _StepFunction.apply(
+                eng, observation, norm_pos, noise, rng, tuple(k for k, _ in named), *state,
+                *[p for _, p in named])
+        else:
+            probs, values, preds, msg, h, c, hc, cc, actions, logp = eng.step_forward(
+                observation, self.__last_msg, norm_pos, hid.h, hid.c, hid.h_caret, hid.c_caret, noise,
+                rng=rng)
         self.__hidden = RecurrentOutput(h, c, hc, cc)
         self.__last_msg = msg
         return AgentOutput(actions=actions, actions_log_probs=logp, predictions=preds, values=values)

@@ -518,6 +518,14 @@ int launch_i64_to_i32(const int64_t* src, int32_t* dst, int64_t n, hipStream_t s
 // dlogits[r][j] = dlogp[r] * (1[j == a_r] - p[r][j]) into [R, ld] (cols >= nA untouched)
 int launch_policy_dlogits(const float* dlogp, const float* probs, const int32_t* actions,
                           float* out, int ld, int64_t rows, int nA, hipStream_t st);
+// the same from a general dL/dprobs [rows, nA] (softmax backward) plus the dlogp term (nullable:
+// then actions are not read): dlogits[r][j] = p_j (g_j - sum_k p_k g_k) + dlogp[r] (1[j == a_r] - p_j)
+int launch_policy_dlogits_probs(const float* dlogp, const float* dprobs, const float* probs,
+                                const int32_t* actions, float* out, int ld, int64_t rows, int nA,
+                                hipStream_t st);
+// dst[r][c] += src[r][c] for c < cols (src null: nothing)
+int launch_acc2d(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t rows, int cols,
+                 hipStream_t st);
 // values[r] = dot(a[r,:n], w[:n]) + b
 int launch_rowdot(const float* a, int lda, const float* w, const float* b, float* out,
                   int64_t rows, int n, hipStream_t st);

@@ -1365,8 +1365,19 @@ static int gate_image_fallback(const Ctx& c, const PanelBwdProb& pd, int t) {
 // marl_backward_heads_event: recorded by episode_backward once the heads' parameter gradients are final
 static hipEvent_t g_heads_event = nullptr;
 
+// marl_step_backward: what one standalone step (nb_steps = 1) adds to the episode's backward
+struct StepBwd {
+    const float* obs = nullptr;      // [R, C, f, f]: the first convolution's input (there is no image batch)
+    const float* g_probs = nullptr;  // dL/dprobs [R, nA] (null: only the dlogp term)
+    // upstream gradients of the step's new message and state [R, n] tight (null = zero)
+    const float *g_msg = nullptr, *g_h = nullptr, *g_c = nullptr, *g_hc = nullptr, *g_cc = nullptr;
+    // gradients of the step's inputs [R, n] tight (null = not wanted)
+    float *d_msg = nullptr, *d_h = nullptr, *d_c = nullptr, *d_hc = nullptr, *d_cc = nullptr;
+};
+
 static int episode_backward(const Ctx& c0, const void* img, int img_u8, const float* g_preds,
-                            const float* g_logp, const float* g_values, float* const* grads) {
+                            const float* g_logp, const float* g_values, float* const* grads,
+                            const StepBwd* sb = nullptr) {
     Ctx c = c0;
     RedQueue rq;
     rq.reset(c.at(c.e.RED), c.e.red_floats, c.st);
@@ -1404,6 +1415,12 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
         q.flush();
         MARL_TRY(q.rc);
     }
+    if (sb) {  // the chain starts from the upstream dL/dc, dL/dc^ of the step's new cell states
+        MARL_TRY(launch_acc2d(c.at(c.e.DC), d.ld_nb, sb->g_c, d.n_b, d.R, d.n_b, st));
+        MARL_TRY(launch_acc2d(c.at(c.e.DCC), d.ld_na, sb->g_cc, d.n_a, d.R, d.n_a, st));
+        // patch positions of the first convolution's weight gradient: every patch at (0, 0) of its own image
+        MARL_TRY(launch_fill(reinterpret_cast<float*>(c.POSs(0)), d.R * 2, 0.f, st));
+    }
     MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.GPRED), d.ld_nC, c.wt(MARL_P_PRE_W1), p4(d.nC), d.nC,
                                 c.at(c.e.DAQ1), d.ld_nlb, (int)NR, d.nlb)));
     MARL_TRY(tn(c, c.at(c.e.GPRED), d.ld_nC, c.at(c.e.AQ1), d.ld_nlb, MARL_P_PRE_W1, d.nC, d.nlb, NR, grads[MARL_P_PRE_B1]));
@@ -1424,8 +1441,12 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
     }
     MARL_TRY(tn(c, c.at(c.e.DAC1), d.ld_nla, c.HCs(1), d.ld_na, MARL_P_CRI_W0, d.nla, d.n_a, NR, grads[MARL_P_CRI_B0]));
     // policy head: logp = log softmax(logits)[a]  (networks/policy.py:12-16, core/agent.py:57-61)
-    MARL_TRY(launch_policy_dlogits(g_logp, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG), d.ld_nA, NR,
-                                   d.nA, st));
+    if (sb && sb->g_probs)  // standalone step: dL/dprobs from the caller (+ the dlogp term)
+        MARL_TRY(launch_policy_dlogits_probs(g_logp, sb->g_probs, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG),
+                                             d.ld_nA, NR, d.nA, st));
+    else
+        MARL_TRY(launch_policy_dlogits(g_logp, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG), d.ld_nA, NR,
+                                       d.nA, st));
     MARL_TRY(tn(c, c.at(c.e.DLOG), d.ld_nA, c.at(c.e.AP1, 0), d.ld_nla, MARL_P_POL_W1, d.nA, d.nla, NR, grads[MARL_P_POL_B1]));
     if (d.nA <= 4 && d.nla <= 384) {
         MARL_TRY(ln_bwd_rank(c, c.at(c.e.DLOG), d.ld_nA, d.nA, MARL_P_POL_W1, c.at(c.e.ZP1, 0),
@@ -1447,10 +1468,14 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
         gemm_add_seg(pa, c.at(c.e.DAC1), d.ld_nla, c.wt(MARL_P_CRI_W0), d.ld_nla, d.nla);
         MARL_TRY(gemm2(c, ph, pa));
     }
+    if (sb) {  // + the upstream dL/dh, dL/dh^ of the step's new hidden states
+        MARL_TRY(launch_acc2d(c.DHs(ns), d.ld_nb, sb->g_h, d.n_b, d.R, d.n_b, st));
+        MARL_TRY(launch_acc2d(c.DHCs(ns), d.ld_na, sb->g_hc, d.n_a, d.R, d.n_a, st));
+    }
 
     // Data parallelism (parallel.py, BucketedGradAllReduce): every gradient of the three heads' parameters (POL_*,
     // CRI_*, PRE_*) is complete here, ahead of the ~1.4 ms reverse loop - flush what they queued and mark the point.
-    const bool heads_early = g_heads_event != nullptr;
+    const bool heads_early = g_heads_event != nullptr && !sb;
     if (heads_early) {
         if (c.tq) MARL_TRY(launch_tn_queue(tq, c.rq, st));
         MARL_TRY(rq.flush());
@@ -1468,6 +1493,24 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
         MARL_TRY(launch_tn_queue(tq, c.rq, st));  // (what the heads queued so far)
         c.rq = nullptr;
         c.tq = nullptr;
+    }
+    // In an episode the last step's message has no consumer.  A standalone step's new message may have one
+    // (the caller's next step, a loss): its encoder runs backward from dL/d(new message) here, ahead of the
+    // belief cell of that step, to which it adds dL/dh.
+    const bool enc_last = sb && sb->g_msg;
+    if (enc_last) {
+        const int t = ns - 1;
+        float* dze2 = c.at(c.e.DZE2) + (size_t)t * s_nm;
+        float* dae1 = c.at(c.e.DAE1) + (size_t)t * s_nm2;
+        MARL_TRY(launch_copy2d(sb->g_msg, d.n_m, dze2, d.ld_nm, d.R, d.n_m, st));
+        MARL_TRY(ln_bwd(c, dze2, d.ld_nm, c.at(c.e.ZE2, t), d.ld_nm, c.at(c.e.STE2, t), MARL_P_ENC_LN1W,
+                        MARL_P_ENC_LN1B, d.R, d.n_m, grads, 0));
+        MARL_TRY(gemm1(c, gemm_prob(dze2, d.ld_nm, c.wt(MARL_P_ENC_W1), p4(d.n_m), d.n_m, dae1, d.ld_nm2, R,
+                                    d.nm2)));
+        MARL_TRY(ln_bwd(c, dae1, d.ld_nm2, c.at(c.e.ZE1, t), d.ld_nm2, c.at(c.e.STE1, t), MARL_P_ENC_LN0W,
+                        MARL_P_ENC_LN0B, d.R, d.nm2, grads, 0));
+        MARL_TRY(gemm1(c, gemm_prob(dae1, d.ld_nm2, c.wt(MARL_P_ENC_W0), p4(d.nm2), d.nm2, c.DHs(ns), d.ld_nb, R,
+                                    d.n_b, nullptr, 1)));
     }
     // The action cell's backward of step t-1 only needs dh^_t, which is complete after step t's
     // W_hh product; it rides along (extra workgroups) with step t's decoder-panel launch, so
@@ -1662,6 +1705,9 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                                     d.ld_nm2, R, d.nm2)));
         MARL_TRY(ln_bwd(c, dad1, d.ld_nm2, c.at(c.e.ZD1, t), d.ld_nm2, c.at(c.e.STD1, t),
                         MARL_P_DEC_LN0W, MARL_P_DEC_LN0B, d.R, d.nm2, grads, !first));
+        if (t == 0 && sb && sb->d_msg)  // dL/d(mean message) of the step's input message
+            MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wt(MARL_P_DEC_W0), p4(d.nm2), d.nm2,
+                                        c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
         if (t > 0) {
             // through the message mean (self-adjoint) into the encoder of step t-1
             MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wt(MARL_P_DEC_W0), p4(d.nm2), d.nm2,
@@ -1681,6 +1727,18 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                                         c.DHs(t), d.ld_nb, R, d.n_b, nullptr, 1)));
         }
     }
+    if (sb) {  // gradients of the step's inputs: what the loop left for step -1
+        // (DMBAR = dL/d(mean message) of step 0; the mean is self-adjoint and may run in place: every thread
+        // owns one (batch, column) over all agents)
+        if (sb->d_msg) {
+            MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.n_m, st));
+            MARL_TRY(launch_copy2d(c.at(c.e.DMBAR), d.ld_nm, sb->d_msg, d.n_m, d.R, d.n_m, st));
+        }
+        if (sb->d_h) MARL_TRY(launch_copy2d(c.DHs(0), d.ld_nb, sb->d_h, d.n_b, d.R, d.n_b, st));
+        if (sb->d_c) MARL_TRY(launch_copy2d(c.at(c.e.DC), d.ld_nb, sb->d_c, d.n_b, d.R, d.n_b, st));
+        if (sb->d_hc) MARL_TRY(launch_copy2d(c.DHCs(0), d.ld_na, sb->d_hc, d.n_a, d.R, d.n_a, st));
+        if (sb->d_cc) MARL_TRY(launch_copy2d(c.at(c.e.DCC), d.ld_na, sb->d_cc, d.n_a, d.R, d.n_a, st));
+    }
     if (panels) {  // LayerNorm affine gradients of the in-loop layers: one reduction each
         const int64_t nblk = pln_blocks;
         MARL_TRY(launch_reduce_affine(c.at(c.e.PLN[0]), nblk * ns, d.n_mo, grads[MARL_P_DEC_LN1W],
@@ -1698,8 +1756,9 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
     // ---- weight gradients of the recurrent chain: one contraction over all steps -------
     MARL_TRY(tn(c, c.at(c.e.DDBAR), d.ld_dbl, c.at(c.e.AD1, 0), d.ld_nm2, MARL_P_DEC_W1, d.n_mo, d.nm2, NR, grads[MARL_P_DEC_B1]));
     MARL_TRY(tn(c, c.at(c.e.DAD1), d.ld_nm2, c.at(c.e.MBAR, 0), d.ld_nm, MARL_P_DEC_W0, d.nm2, d.n_m, NR, grads[MARL_P_DEC_B0]));
-    if (ns > 1) {
-        const int64_t er = (int64_t)(ns - 1) * d.R;  // the last step's message is never read
+    if (ns > 1 || enc_last) {
+        // the last step's message is never read in an episode; a standalone step's may be
+        const int64_t er = (int64_t)(enc_last ? ns : ns - 1) * d.R;
         MARL_TRY(tn(c, c.at(c.e.DZE2), d.ld_nm, c.at(c.e.AE1, 0), d.ld_nm2, MARL_P_ENC_W1, d.n_m, d.nm2, er, grads[MARL_P_ENC_B1]));
         MARL_TRY(tn(c, c.at(c.e.DAE1), d.ld_nm2, c.Hs(1), d.ld_nb, MARL_P_ENC_W0, d.nm2, d.n_b, er, grads[MARL_P_ENC_B0]));
     } else {
@@ -1792,6 +1851,13 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                     w.gst = c.at(c.e.GST[l - 1], 0);
                     w.gamma = c.wp(4 * (l - 1) + 2);
                     w.beta = c.wp(4 * (l - 1) + 3);
+                } else if (sb) {
+                    // standalone step: the caller's patches obs [R, C, f, f] are R one-patch images of
+                    // f x f at position 0 (POSs(0) zeroed above) - the gather reads exactly obs[r]
+                    w.img = sb->obs;
+                    w.img_u8 = 0;
+                    w.nb = (int)d.R;
+                    w.H = w.W = d.f;
                 } else if (!img) {
                     set_error("episode_backward: the image batch of the forward call is needed");
                     return MARL_EINVAL;
@@ -2211,15 +2277,19 @@ int marl_adam_step(float* params, const float* grads, float* exp_avg, float* exp
                        static_cast<hipStream_t>(stream), static_cast<const Counters*>(counters));
 }
 
-int marl_step_forward(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
-                      void* episode_ws, size_t episode_ws_bytes, const float* obs, const float* msg, const float* norm_pos, const float* h,
-                      const float* cc_, const float* hc, const float* cca, float* probs,
-                      float* values, float* preds, float* new_msg, float* h_out, float* c_out,
-                      float* hc_out, float* cc_out, const float* noise, uint64_t rng_seed,
-                      uint64_t rng_offset, int64_t* actions_out, float* logp_out, void* stream) {
+}  // extern "C"
+
+// marl_step_forward (train = 0) and marl_step_forward_train (train = 1: the activations stay in the
+// one-step training layout for marl_step_backward).  Same launches either way: the outputs are identical.
+static int step_forward(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes, void* episode_ws,
+                        size_t episode_ws_bytes, const float* obs, const float* msg, const float* norm_pos,
+                        const float* h, const float* cc_, const float* hc, const float* cca, float* probs,
+                        float* values, float* preds, float* new_msg, float* h_out, float* c_out, float* hc_out,
+                        float* cc_out, const float* noise, uint64_t rng_seed, uint64_t rng_offset,
+                        int64_t* actions_out, float* logp_out, int train, void* stream) {
     Ctx c;
     SplitRegistryScope reg_scope;
-    MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, 0, stream, c));
+    MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, train, stream, c));
     if (!obs || !msg || !norm_pos || !h || !cc_ || !hc || !cca || !probs || !values || !preds ||
         !new_msg || !h_out || !c_out || !hc_out || !cc_out) {
         set_error("step_forward: null argument");
@@ -2251,7 +2321,74 @@ int marl_step_forward(const marl_config* cfg, const void* weights_ws, size_t wei
     MARL_TRY(launch_copy2d(c.Cs(1), d.ld_nb, c_out, d.n_b, d.R, d.n_b, c.st));
     MARL_TRY(launch_copy2d(c.HCs(1), d.ld_na, hc_out, d.n_a, d.R, d.n_a, c.st));
     MARL_TRY(launch_copy2d(c.CCs(1), d.ld_na, cc_out, d.n_a, d.R, d.n_a, c.st));
+    if (train)  // the softmax backward reads the probabilities (the sampled action is in ACTs(0) already)
+        MARL_TRY(launch_copy2d(probs, d.nA, c.PROBSs(0), d.nA, d.R, d.nA, c.st));
     return MARL_OK;
+}
+
+extern "C" {
+
+int marl_step_forward(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                      void* episode_ws, size_t episode_ws_bytes, const float* obs, const float* msg, const float* norm_pos, const float* h,
+                      const float* cc_, const float* hc, const float* cca, float* probs,
+                      float* values, float* preds, float* new_msg, float* h_out, float* c_out,
+                      float* hc_out, float* cc_out, const float* noise, uint64_t rng_seed,
+                      uint64_t rng_offset, int64_t* actions_out, float* logp_out, void* stream) {
+    return step_forward(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, obs, msg, norm_pos, h, cc_,
+                        hc, cca, probs, values, preds, new_msg, h_out, c_out, hc_out, cc_out, noise, rng_seed,
+                        rng_offset, actions_out, logp_out, 0, stream);
+}
+
+int marl_step_forward_train(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                            void* step_ws, size_t step_ws_bytes, const float* obs, const float* msg,
+                            const float* norm_pos, const float* h, const float* c, const float* hc,
+                            const float* cc, float* probs, float* values, float* preds, float* new_msg,
+                            float* h_out, float* c_out, float* hc_out, float* cc_out, const float* noise,
+                            uint64_t rng_seed, uint64_t rng_offset, int64_t* actions_out, float* logp_out,
+                            void* stream) {
+    if (!cfg) {
+        set_error("step_forward_train: null configuration");
+        return MARL_EINVAL;
+    }
+    marl_config one = *cfg;  // the step workspace has the training layout of ONE step
+    one.nb_steps = 1;
+    return step_forward(&one, weights_ws, weights_ws_bytes, step_ws, step_ws_bytes, obs, msg, norm_pos, h, c, hc, cc,
+                        probs, values, preds, new_msg, h_out, c_out, hc_out, cc_out, noise, rng_seed, rng_offset,
+                        actions_out, logp_out, 1, stream);
+}
+
+int marl_step_backward(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes, void* step_ws,
+                       size_t step_ws_bytes, const float* obs, const float* g_probs, const float* g_logp,
+                       const float* g_values, const float* g_preds, const float* g_msg, const float* g_h,
+                       const float* g_c, const float* g_hc, const float* g_cc, float* const* grads_host,
+                       float* d_msg, float* d_h, float* d_c, float* d_hc, float* d_cc, void* stream) {
+    if (!cfg) {
+        set_error("step_backward: null configuration");
+        return MARL_EINVAL;
+    }
+    marl_config one = *cfg;
+    one.nb_steps = 1;
+    Ctx c;
+    SplitRegistryScope reg_scope;
+    MARL_TRY(make_ctx(&one, weights_ws, weights_ws_bytes, step_ws, step_ws_bytes, 1, stream, c));
+    if (!grads_host || !obs) {
+        set_error("step_backward: null gradient table or observation");
+        return MARL_EINVAL;
+    }
+    StepBwd sb;
+    sb.obs = obs;
+    sb.g_probs = g_probs;
+    sb.g_msg = g_msg;
+    sb.g_h = g_h;
+    sb.g_c = g_c;
+    sb.g_hc = g_hc;
+    sb.g_cc = g_cc;
+    sb.d_msg = d_msg;
+    sb.d_h = d_h;
+    sb.d_c = d_c;
+    sb.d_hc = d_hc;
+    sb.d_cc = d_cc;
+    return episode_backward(c, nullptr, 0, g_preds, g_logp, g_values, grads_host, &sb);
 }
 
 // test hook: where a named activation of step t lives inside episode_ws (float offset, ld)

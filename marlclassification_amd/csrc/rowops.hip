@@ -1446,6 +1446,52 @@ int launch_policy_dlogits(const float* dlogp, const float* probs, const int32_t*
     return MARL_OK;
 }
 
+// softmax backward from a general dL/dprobs plus the log-prob term of the sampled action, one row
+// per thread (nA <= MARL_MAX_ACTIONS): dz_j = p_j (g_j - sum_k p_k g_k) + gl (1[j == a] - p_j)
+__global__ void policy_dlogits_probs_kernel(const float* __restrict__ dlogp,
+                                            const float* __restrict__ dprobs,
+                                            const float* __restrict__ probs,
+                                            const int32_t* __restrict__ actions,
+                                            float* __restrict__ out, int ld, int64_t rows, int nA) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const float* p = probs + r * nA;
+    const float* g = dprobs + r * nA;
+    float s = 0.f;
+    for (int j = 0; j < nA; ++j) s = fmaf(p[j], g[j], s);
+    const float gl = dlogp ? dlogp[r] : 0.f;
+    const int a = dlogp ? actions[r] : -1;
+    for (int j = 0; j < nA; ++j)
+        out[r * ld + j] = p[j] * (g[j] - s) + gl * ((j == a ? 1.0f : 0.0f) - p[j]);
+}
+int launch_policy_dlogits_probs(const float* dlogp, const float* dprobs, const float* probs,
+                                const int32_t* actions, float* out, int ld, int64_t rows, int nA,
+                                hipStream_t st) {
+    if (rows <= 0) return MARL_OK;
+    hipLaunchKernelGGL(policy_dlogits_probs_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, st,
+                       dlogp, dprobs, probs, actions, out, ld, rows, nA);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
+// dst[r][c] += src[r][c] (an upstream gradient added into a padded buffer)
+__global__ void acc2d_kernel(float* __restrict__ dst, int64_t ldd, const float* __restrict__ src,
+                             int64_t lds, int64_t rows, int cols) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * cols) return;
+    const int64_t r = idx / cols;
+    const int c = (int)(idx % cols);
+    dst[r * ldd + c] += src[r * lds + c];
+}
+int launch_acc2d(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t rows, int cols,
+                 hipStream_t st) {
+    if (!src || rows <= 0 || cols <= 0) return MARL_OK;
+    hipLaunchKernelGGL(acc2d_kernel, dim3((unsigned)cdiv(rows * cols, 256)), dim3(256), 0, st, dst, ldd,
+                       src, lds, rows, cols);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
 __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ a, int lda,
                                                      const float* __restrict__ w,
                                                      const float* __restrict__ b,

@@ -451,11 +451,13 @@ class HipEngine:
     def step_forward(
         self, obs: th.Tensor, msg: th.Tensor, norm_pos: th.Tensor, h: th.Tensor, c: th.Tensor,
         hc: th.Tensor, cc: th.Tensor, noise: Optional[th.Tensor] = None,
-        rng: Optional[Tuple[int, int]] = None,
+        rng: Optional[Tuple[int, int]] = None, ws: Optional[th.Tensor] = None,
     ) -> Tuple[th.Tensor, ...]:
         """marl_step_forward: (probs, values, preds, new_msg, h, c, hc, cc) in [Na,Nb,..];
         with ``noise`` ([Na,Nb,nA] ~ Exp(1), parity mode) or ``rng=(seed, offset)`` (in-kernel
-        draws) also (actions int64, log-probs)."""
+        draws) also (actions int64, log-probs).  ``ws`` = a training workspace of the current
+        one-step configuration (``train_ws_acquire``): marl_step_forward_train, same outputs, the
+        activations stay in ``ws`` for ``step_backward``."""
         cfg = self.cfg
         assert cfg is not None
         na, nb = cfg.nb_agents, cfg.batch
@@ -477,12 +479,53 @@ class HipEngine:
             lp = th.empty(na, nb, device=dev)
             extra = (act, lp)
         seed, offset = rng if rng is not None else (0, 0)
-        wws, ews = self.packed_weights_ws(), self.episode_ws(False)
-        check(self.lib.marl_step_forward(
+        wws = self.packed_weights_ws()
+        if ws is not None:
+            if cfg.nb_steps != 1:
+                raise RuntimeError("step_forward(ws=...): configure the engine with nb_steps = 1")
+            self._check_ws(ws, "step_forward")
+            fn, ews = self.lib.marl_step_forward_train, ws
+        else:
+            fn, ews = self.lib.marl_step_forward, self.episode_ws(False)
+        check(fn(
             C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews),
             *[t.data_ptr() for t in ins], *[t.data_ptr() for t in outs], _ptr(nz), seed & _U64,
             offset & _U64, _ptr(act), _ptr(lp), _stream(dev)))
         return outs + extra
+
+    def _check_ws(self, ws: th.Tensor, what: str) -> None:
+        if getattr(ws, "_marl_key", None) != (self._cfg_key, _tune_epoch):
+            raise RuntimeError(
+                f"{what}: the engine was re-configured (other batch size / image shape / layout knob) since "
+                "this workspace was acquired - it no longer fits")
+
+    def step_backward(
+        self, ws: th.Tensor, obs: th.Tensor, grads: Dict[str, th.Tensor],
+        g_probs: Optional[th.Tensor] = None, g_logp: Optional[th.Tensor] = None,
+        g_values: Optional[th.Tensor] = None, g_preds: Optional[th.Tensor] = None,
+        g_msg: Optional[th.Tensor] = None, g_h: Optional[th.Tensor] = None,
+        g_c: Optional[th.Tensor] = None, g_hc: Optional[th.Tensor] = None,
+        g_cc: Optional[th.Tensor] = None, want: Sequence[bool] = (True,) * 5,
+    ) -> Tuple[Optional[th.Tensor], ...]:
+        """marl_step_backward of the step whose activations ``ws`` holds (``step_forward(ws=ws)``).
+        Upstream gradients may be None (zero); ``g_logp`` only if that forward sampled.  Writes the
+        parameter gradients into ``grads`` (overwritten) and returns the input gradients
+        (d_msg, d_h, d_c, d_hc, d_cc) in [Na,Nb,..], None where ``want`` is False."""
+        cfg = self.cfg
+        assert cfg is not None
+        self._check_ws(ws, "step_backward")
+        na, nb, dev = cfg.nb_agents, cfg.batch, self.device
+        obs = _need(obs, th.float32, "obs")
+        ups = [None if t is None else _need(t, th.float32, n) for t, n in (
+            (g_probs, "g_probs"), (g_logp, "g_logp"), (g_values, "g_values"), (g_preds, "g_preds"),
+            (g_msg, "g_msg"), (g_h, "g_h"), (g_c, "g_c"), (g_hc, "g_hc"), (g_cc, "g_cc"))]
+        widths = (cfg.n_m, cfg.n_b, cfg.n_b, cfg.n_a, cfg.n_a)
+        outs = tuple(th.empty(na, nb, n, device=dev) if w else None for n, w in zip(widths, want))
+        wws = self.packed_weights_ws()
+        check(self.lib.marl_step_backward(
+            C.byref(cfg), wws.data_ptr(), _nbytes(wws), ws.data_ptr(), _nbytes(ws), obs.data_ptr(),
+            *[_ptr(t) for t in ups], self._table(grads), *[_ptr(t) for t in outs], _stream(dev)))
+        return outs
 
     def draw_episode(self, seed: int, offset: int, with_noise: bool = False,
                      into: Optional[Tuple[th.Tensor, ...]] = None,

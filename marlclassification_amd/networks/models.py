@@ -6,7 +6,9 @@ drop-in ``nn.Module`` whose arithmetic is libmarl_hip.so.
 * parameters are views into one flat fp32 buffer (``flat_state``) so Adam and the
   data-parallel all-reduce are single kernels / collectives;
 * ``forward`` is the reference's per-step network (MultiAgent.act uses it); whole
-  episodes go through core.episode.EpisodeSampler (one call for all steps).
+  episodes go through core.episode.EpisodeSampler (one call for all steps).  With autograd
+  enabled a step is one autograd node (``_StepFunction``: marl_step_forward_train /
+  marl_step_backward), so user loops over single steps back-propagate as in the reference.
 """
 
 from dataclasses import dataclass
@@ -20,6 +22,87 @@ from ..fused import FlatParams
 from .blocks import LSTMCellWrapper, head, linear_ln_silu, mlp_two_norms
 from .init import init_layers
 from .vision import VisionCnnModule
+
+
+class _StepLease:
+    """One live step's training workspace: back to the engine's pool at backward, or when the
+    autograd graph holding the step is freed without a backward."""
+
+    def __init__(self, eng: HipEngine) -> None:
+        self.eng = eng
+        self.ws: Optional[th.Tensor] = eng.train_ws_acquire()
+
+    def release(self) -> None:
+        ws, self.ws = self.ws, None
+        if ws is not None:
+            self.eng.train_ws_release(ws)
+
+    def __del__(self) -> None:
+        try:
+            self.release()
+        except Exception:  # (interpreter shutdown)
+            pass
+
+
+def step_needs_graph(model: nn.Module, obs: th.Tensor, norm_pos: th.Tensor, *state: th.Tensor) -> bool:
+    """A step becomes an autograd node when grad mode is on and a parameter or an input of the
+    recurrent state (msg, h, c, h^, c^) requires grad; otherwise it is the plain marl_step_forward
+    call.  An observation / position that requires grad is refused rather than silently cut."""
+    if not th.is_grad_enabled():
+        return False
+    for t, n in ((obs, "observation"), (norm_pos, "norm_pos")):
+        if t.requires_grad:
+            raise RuntimeError(
+                f"the {n} requires grad: the HIP step has no gradient w.r.t. the observation or the "
+                "positions (the reference crops them from an image batch that does not require grad) - "
+                "pass it detached")
+    return any(p.requires_grad for p in model.parameters()) or any(t.requires_grad for t in state)
+
+
+class _StepFunction(th.autograd.Function):
+    """Autograd boundary around ONE step (ModelsWrapper.forward / MultiAgent.act): inputs msg, h, c,
+    h^, c^ and the model parameters; outputs probs, values, preds, msg, h, c, h^, c^ (+ the
+    non-differentiable actions and their log-probabilities when the step samples)."""
+
+    @staticmethod
+    def forward(ctx, eng: HipEngine, obs, norm_pos, noise, rng, names, msg, h, c, hc, cc, *params):
+        # every live step owns its saved activations (a one-step training workspace from the engine's
+        # pool): an unrolled loop keeps one per step until backward, as the reference's graph does
+        lease = _StepLease(eng)
+        outs = eng.step_forward(obs, msg, norm_pos, h, c, hc, cc, noise, rng=rng, ws=lease.ws)
+        ctx.eng, ctx.lease, ctx.obs = eng, lease, obs.contiguous()
+        ctx.cfg_key = eng._cfg_key
+        ctx.pack_generation = eng.pack_generation
+        ctx.names = names
+        ctx.sampled = len(outs) == 10
+        ctx.save_for_backward(*params)  # (an in-place update of a parameter before backward is an error)
+        ctx.set_materialize_grads(False)
+        if ctx.sampled:
+            ctx.mark_non_differentiable(outs[8])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_probs, g_values, g_preds, g_msg, g_h, g_c, g_hc, g_cc, *rest):
+        eng: HipEngine = ctx.eng
+        lease: _StepLease = ctx.lease
+        if lease.ws is None:
+            raise RuntimeError("this step's saved activations were already released by an earlier backward "
+                               "(run the step again instead of retain_graph)")
+        params = ctx.saved_tensors
+        if ctx.pack_generation != eng.pack_generation:
+            raise RuntimeError("the model's weights were modified (re-packed) after this step's forward: its "
+                               "backward needs the weights the forward used - call backward before the "
+                               "optimiser step")
+        if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
+            na, nb, ns, shape, u8 = ctx.cfg_key
+            eng.configure(na, nb, ns, shape, img_u8=u8)
+        g_logp = rest[1] if ctx.sampled else None
+        grads = {k: th.empty(p.shape, device=eng.device) for k, p in zip(ctx.names, params)}
+        want = ctx.needs_input_grad[6:11]
+        d_in = eng.step_backward(lease.ws, ctx.obs, grads, g_probs, g_logp, g_values, g_preds, g_msg, g_h,
+                                 g_c, g_hc, g_cc, want=want)
+        lease.release()
+        return (None,) * 6 + d_in + tuple(grads[k] for k in ctx.names)
 
 
 @dataclass
@@ -112,15 +195,23 @@ class ModelsWrapper(nn.Module):
         recurrent_hidden: RecurrentOutput,
     ) -> Tuple[ModelOutput, RecurrentOutput]:
         """One step of every network (reference models.py:78-138) through
-        ``marl_step_forward``.  Inference only: gradients flow through whole episodes
-        (EpisodeSampler), not through single steps."""
+        ``marl_step_forward``.  With grad enabled and a parameter (or msg / state) requiring
+        grad, the step is one autograd node (``_StepFunction``) whose backward is
+        ``marl_step_backward``: gradients reach the parameters and msg_t / the recurrent state."""
         na, nb = img_patch.shape[:2]
         eng = self.hip_engine(None)
         eng.configure(na, nb, 1, (img_patch.shape[2], img_patch.shape[3] + 1, img_patch.shape[4] + 1))
         self.ensure_packed(eng)
         rh = recurrent_hidden
-        probs, values, preds, msg, h, c, hc, cc = eng.step_forward(
-            img_patch, msg_t, norm_pos, rh.h, rh.c, rh.h_caret, rh.c_caret)
+        state = (msg_t, rh.h, rh.c, rh.h_caret, rh.c_caret)
+        if step_needs_graph(self, img_patch, norm_pos, *state):
+            named = list(self.named_parameters())
+            probs, values, preds, msg, h, c, hc, cc = _StepFunction.apply(
+                eng, img_patch, norm_pos, None, None, tuple(k for k, _ in named), *state,
+                *[p for _, p in named])
+        else:
+            probs, values, preds, msg, h, c, hc, cc = eng.step_forward(
+                img_patch, msg_t, norm_pos, rh.h, rh.c, rh.h_caret, rh.c_caret)
         return ModelOutput(probs, values, preds, msg), RecurrentOutput(h, c, hc, cc)
 
     # ---- HIP plumbing --------------------------------------------------------------------
