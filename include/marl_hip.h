@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define MARL_ABI_VERSION 4
+#define MARL_ABI_VERSION 5
 
 #define MARL_OK 0
 #define MARL_EINVAL (-1)   /* bad configuration / null pointer          */
@@ -197,6 +197,23 @@ int marl_episode_backward(const marl_config* cfg, void* weights_ws, size_t weigh
                           void* episode_ws, size_t episode_ws_bytes,
                           const void* img, const float* g_preds, const float* g_logp,
                           const float* g_values, float* const* grads_host, void* stream);
+
+/* The same backward pass that ALSO writes dL/d(img) (ABI 5).  The reference builds its autograd graph through the
+ * patch crop - Environment.__observation (core/environment.py:95-126) is a masked_select of the image batch - so
+ * img.requires_grad_(), run_episode, loss.backward() fills img.grad there (saliency maps, gradient-sign probes,
+ * input optimisation).  Same arguments and the same parameter gradients as the entry above; d_img [Nb,C,H,W] fp32
+ * (16-byte aligned) is OVERWRITTEN with the transposed first convolution (networks/vision.py:33-35) of dZ_0 summed
+ * over the crops of every agent and step at the positions the rollout saved: pos0 for step 0, the position after
+ * move t - 1 for step t; the crop after the last move is discarded by the episode (core/episode.py:72) and gets
+ * none.  Exactly 0 where no window looked and in channels the CNN does not read (MnistCnn: channel 0 only,
+ * networks/vision.py:63-65).  Every pixel has one owning workgroup and a fixed summation order: no atomics, the
+ * result is bit-reproducible.  No scratch beyond episode_ws.  cfg->img_u8 != 0 (an integer image has no gradient)
+ * or d_img == NULL: MARL_EINVAL, nothing enqueued. */
+int marl_episode_backward_img(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
+                              void* episode_ws, size_t episode_ws_bytes,
+                              const void* img, const float* g_preds, const float* g_logp,
+                              const float* g_values, float* const* grads_host, float* d_img,
+                              void* stream);
 
 /* Data-parallel overlap (no reference counterpart: training/trainer.py is single-device).  While an event
  * is installed (per-process state, NULL clears it), every marl_episode_backward records it on its stream at the

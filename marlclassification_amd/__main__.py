@@ -67,6 +67,8 @@ def build_parser() -> argparse.ArgumentParser:
     i.add_argument("--state-dict-path", type=str, required=True, dest="state_dict_path")
     i.add_argument("--class2idx", type=str, required=True, dest="class_to_idx")
     i.add_argument("-o", "--output-image-dir", type=str, required=True, dest="output_image_dir")
+    i.add_argument("--saliency", action="store_true", dest="saliency",
+                   help="also write saliency.png (|d logit / d pixel| of the predicted class) per image")
     t.add_argument("--exact-standardize", action="store_true", dest="exact_standardize",
                    help="multi-GPU: global advantage statistics (update == single-GPU big batch)")
     return p
@@ -107,7 +109,7 @@ def main(argv=None) -> None:
         os.makedirs(args.output_image_dir, exist_ok=True)
         infer_main(main_config, InferConfig(
             state_dict_path=args.state_dict_path, json_path=args.json_path, images_path=args.infer_images,
-            output_dir=args.output_image_dir, class_to_idx=args.class_to_idx))
+            output_dir=args.output_image_dir, class_to_idx=args.class_to_idx, saliency=args.saliency))
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ from typing import Optional
 
 MARL_MAX_CNN_LAYERS = 5
 MARL_MAX_ACTIONS = 16
-MARL_ABI_VERSION = 4
+MARL_ABI_VERSION = 5
 MARL_COUNTERS_BYTES = 32
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,7 +75,7 @@ EXPORTS = (
     "marl_graph_destroy marl_image_bytes marl_image_build marl_gemm_nt_images marl_gemm_nt_images_batch "
     "marl_lstm_images marl_gemm_tn_images marl_gemm_tn_images_scratch marl_plan_query "
     "marl_gemm_tn_images_cell marl_gemm_tn_images_cell_scratch marl_backward_heads_event "
-    "marl_step_forward_train marl_step_backward"
+    "marl_step_forward_train marl_step_backward marl_episode_backward_img"
 ).split()
 
 _lib: Optional[C.CDLL] = None
@@ -104,6 +104,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_graph_launch.argtypes = [_vp, _vp]
     lib.marl_graph_destroy.argtypes = [_vp]
     lib.marl_episode_backward.argtypes = [_cfgp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]
+    lib.marl_episode_backward_img.argtypes = ([_cfgp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp,
+                                               _vp])
     lib.marl_a2c_loss_fwd_bwd.argtypes = (
         [_cfgp, _vp, _sz, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]
     )

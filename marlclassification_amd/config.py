@@ -96,3 +96,4 @@ class InferConfig(BaseModel):
     images_path: List[str]
     output_dir: str
     class_to_idx: str
+    saliency: bool = False  # also write saliency.png (|d logit / d pixel|) next to the step frames

@@ -30,8 +30,8 @@ class EpisodeDetailedOutput:
 
 
 class _EpisodeFunction(th.autograd.Function):
-    """Autograd boundary around the fused episode: inputs are the model parameters, outputs
-    step_preds / step_log_probas / step_values (+ non-differentiable positions)."""
+    """Autograd boundary around the fused episode: inputs are the image batch and the model parameters,
+    outputs step_preds / step_log_probas / step_values (+ non-differentiable positions)."""
 
     @staticmethod
     def forward(ctx, eng: HipEngine, img: th.Tensor, draws: EpisodeDraws, names, *params):
@@ -63,10 +63,15 @@ class _EpisodeFunction(th.autograd.Function):
             na, nb, ns, shape, u8 = ctx.cfg_key
             eng.configure(na, nb, ns, shape, img_u8=u8)
         grads = {k: th.empty(s, device=eng.device) for k, s in zip(ctx.names, ctx.shapes)}
-        eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img)
+        # the image is a differentiable input (the reference's crop is a masked_select of it,
+        # core/environment.py:95-126): asked for, its gradient comes out of the same backward pass
+        d_img = th.empty(ctx.img.shape, device=eng.device) if ctx.needs_input_grad[1] else None
+        eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img)
         eng.train_ws_release(ctx.ws)
         ctx.ws = None
-        return (None, None, None, None) + tuple(grads[k] for k in ctx.names)
+        # (a frozen model: the parameter gradients are computed and dropped here)
+        return (None, d_img, None, None) + tuple(
+            grads[k] if need else None for k, need in zip(ctx.names, ctx.needs_input_grad[4:]))
 
 
 class EpisodeSampler:
@@ -143,7 +148,7 @@ class EpisodeSampler:
     def __episode_impl(self, img_batch: th.Tensor) -> EpisodeDetailedOutput:
         eng, img, draws = self.prepare(img_batch)
         model = self.__agents.model
-        if th.is_grad_enabled() and any(p.requires_grad for p in model.parameters()):
+        if th.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in model.parameters())):
             named = list(model.named_parameters())
             names = tuple(k for k, _ in named)
             preds, logp, values, pos, _ = _EpisodeFunction.apply(
@@ -166,7 +171,8 @@ class EpisodeSampler:
 
     def run_episode_raw(self, img_batch: th.Tensor, train: bool,
                         draws: Optional[EpisodeDraws] = None) -> Tuple[HipEngine, EpisodeTensors]:
-        """No autograd node: used by the fused Trainer (loss + backward are HIP calls)."""
+        """No autograd node: used by the fused Trainer (loss + backward are HIP calls).  An image that
+        requires grad is ignored here - the gradient w.r.t. the image exists on the ``run_episode`` path."""
         eng, img, d = self.prepare(img_batch)
         if draws is not None:
             d = draws

@@ -3180,4 +3180,136 @@ int launch_col2im(const float* dcols, int ldk, float* da, int64_t rows, int hin,
     return MARL_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Gradient w.r.t. the image batch (backward of the patch crop + the first convolution:
+// core/environment.py:95-126 is a masked_select of the image, so autograd scatters every patch's
+// gradient back into it; networks/vision.py:33-35 for Conv2d(k3, s2, p1)):
+//   d_obs[r, ci, y, x] = sum over co, taps (ky, kx) with oy = (y + 1 - ky) / 2 integral and in range
+//                        of dZ_0[r, (oy, ox), co] * W_0[co, ci, ky, kx]
+//   d_img[b, ci, p0 + y, p1 + x] += d_obs[(t, a, b), ci, y, x]
+// Windows of different agents and steps overlap.  No atomics: a workgroup OWNS one tile of one
+// image (kDimgTw columns x `th` lines, every channel), keeps it in LDS, walks that image's
+// Ns * Na crops in (t, a) order, and adds the part of each crop inside its tile - one thread per
+// pixel of the intersection, a barrier between crops - so every pixel has one owner and one
+// summation order.  The tile then goes out with one store per pixel, which is also the zero fill
+// (pixels no window covered, channels the CNN does not read).
+// ---------------------------------------------------------------------------
+constexpr int kDimgTw = 64;        // tile columns (256-byte line segments)
+constexpr int kDimgFloats = 6144;  // tile floats: cin * th * kDimgTw <= this (24 KiB)
+
+__global__ __launch_bounds__(256) void cnn_dimg_kernel(const CnnDimgArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float dimg_lds[];
+    const int tid = threadIdx.x;
+    const int cin = A.cin, cout = A.cout, th = A.th, hout = A.hout, f = A.f;
+    float* tile = dimg_lds;                     // [cin][th][kDimgTw]
+    float* wl = dimg_lds + cin * th * kDimgTw;  // [9 * cin][cout]  (k = tap * cin + ci)
+    for (int i = tid; i < cin * th * kDimgTw; i += 256) tile[i] = 0.f;
+    for (int i = tid; i < 9 * cin * cout; i += 256) wl[i] = A.wt0[(size_t)(i / cout) * A.ldwt + i % cout];
+    __syncthreads();
+    const int b = blockIdx.z;
+    const int y0 = blockIdx.y * th, x0 = blockIdx.x * kDimgTw;
+    const int y1 = y0 + th < A.H ? y0 + th : A.H;
+    const int x1 = x0 + kDimgTw < A.W ? x0 + kDimgTw : A.W;
+    const int64_t R = (int64_t)A.na * A.nb;
+    for (int t = 0; t < A.ns; ++t) {
+        for (int a = 0; a < A.na; ++a) {
+            const int64_t row = (int64_t)t * R + (int64_t)a * A.nb + b;
+            const int p0 = A.pos[row * 2], p1 = A.pos[row * 2 + 1];  // (workgroup-uniform)
+            const int ya = p0 > y0 ? p0 : y0, yb = p0 + f < y1 ? p0 + f : y1;
+            const int xa = p1 > x0 ? p1 : x0, xb = p1 + f < x1 ? p1 + f : x1;
+            if (ya >= yb || xa >= xb) continue;  // this crop misses the tile
+            const int ww = xb - xa, n = (yb - ya) * ww;
+            const float* dzr = A.dz0 + row * A.P * cout;
+            for (int e = tid; e < n; e += 256) {
+                const int Y = ya + e / ww, X = xa + e % ww;
+                const int y = Y - p0, x = X - p1;
+                float* dst = tile + (Y - y0) * kDimgTw + (X - x0);
+                for (int c0 = 0; c0 < cin; c0 += 4) {  // (one pass for cin <= 4)
+                    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ky = 0; ky < 3; ++ky) {
+                        const int ty = y + 1 - ky;
+                        if (ty < 0 || (ty & 1) || (ty >> 1) >= hout) continue;
+#pragma unroll
+                        for (int kx = 0; kx < 3; ++kx) {
+                            const int tx = x + 1 - kx;
+                            if (tx < 0 || (tx & 1) || (tx >> 1) >= hout) continue;
+                            const float* src = dzr + ((ty >> 1) * hout + (tx >> 1)) * cout;
+                            const float* w = wl + ((ky * 3 + kx) * cin + c0) * cout;
+                            for (int co = 0; co < cout; co += 4) {
+                                const float4 v = *reinterpret_cast<const float4*>(src + co);
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) {
+                                    if (c0 + j >= cin) break;
+                                    const float4 q = *reinterpret_cast<const float4*>(w + j * cout + co);
+                                    acc[j] = fmaf(v.w, q.w, fmaf(v.z, q.z, fmaf(v.y, q.y, fmaf(v.x, q.x, acc[j]))));
+                                }
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (c0 + j < cin) dst[(c0 + j) * th * kDimgTw] += acc[j];
+                }
+            }
+            __syncthreads();  // the next crop may cover the same pixels from other threads
+        }
+    }
+    // the tile -> d_img[b, :, y0:y1, x0:x1]; channels >= cin are zero
+    const int nrow = y1 - y0;
+    if ((A.W & 3) == 0) {
+        const int tot = A.c_img * nrow * (kDimgTw / 4);
+        for (int i = tid; i < tot; i += 256) {
+            const int x4 = i % (kDimgTw / 4), yy = (i / (kDimgTw / 4)) % nrow, ci = i / ((kDimgTw / 4) * nrow);
+            const int X = x0 + x4 * 4;
+            if (X >= A.W) continue;  // (W % 4 == 0: a float4 is wholly inside or outside)
+            const float4 v = ci < cin ? *reinterpret_cast<const float4*>(tile + (ci * th + yy) * kDimgTw + x4 * 4)
+                                      : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(A.d_img + (((int64_t)b * A.c_img + ci) * A.H + (y0 + yy)) * A.W + X) = v;
+        }
+    } else {
+        const int tot = A.c_img * nrow * kDimgTw;
+        for (int i = tid; i < tot; i += 256) {
+            const int xx = i % kDimgTw, yy = (i / kDimgTw) % nrow, ci = i / (kDimgTw * nrow);
+            if (x0 + xx >= A.W) continue;
+            A.d_img[(((int64_t)b * A.c_img + ci) * A.H + (y0 + yy)) * A.W + x0 + xx] =
+                ci < cin ? tile[(ci * th + yy) * kDimgTw + xx] : 0.f;
+        }
+    }
+}
+
+static int cnn_dimg_th(const CnnDimgArgs& a) {
+    int th = kDimgFloats / (a.cin * kDimgTw);
+    if (th > 32) th = 32;
+    if (th > a.H) th = a.H;
+    return th;
+}
+
+int cnn_dimg_supported(const CnnDimgArgs& a) {
+    if (a.cin < 1 || a.cin > a.c_img || (a.cout & 3) || a.ns < 1 || a.na < 1 || a.nb < 1 || a.nb > 65535) return 0;
+    if (cnn_dimg_th(a) < 1) return 0;
+    if (cdiv(a.H, cnn_dimg_th(a)) > 65535) return 0;
+    return (size_t)9 * a.cin * a.cout * sizeof(float) <= (size_t)32 * 1024;
+}
+
+int launch_cnn_dimg(CnnDimgArgs& a, hipStream_t st) {
+    if (!cnn_dimg_supported(a)) {
+        set_error("image gradient: shape outside the kernel's range (cin %d cout %d batch %d img %dx%d)", a.cin,
+                  a.cout, a.nb, a.H, a.W);
+        return MARL_ELIMIT;
+    }
+    if (!a.dz0 || !a.wt0 || !a.pos || !a.d_img || (reinterpret_cast<uintptr_t>(a.d_img) & 15)) {
+        set_error("image gradient: null or misaligned buffer (d_img must be 16-byte aligned)");
+        return MARL_EINVAL;
+    }
+    a.th = cnn_dimg_th(a);
+    const size_t lds = ((size_t)a.cin * a.th * kDimgTw + (size_t)9 * a.cin * a.cout) * sizeof(float);
+    prof_before(5, st);
+    hipLaunchKernelGGL(cnn_dimg_kernel, dim3((unsigned)cdiv(a.W, kDimgTw), (unsigned)cdiv(a.H, a.th), (unsigned)a.nb),
+                       dim3(256), lds, st, a);
+    prof_after(5, st);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
 }  // namespace marl

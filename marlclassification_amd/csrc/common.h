@@ -842,6 +842,22 @@ int launch_cnn_dgrad(CnnDgradArgs& a, hipStream_t st);
 int cnn_dgrad_w0_ok(const CnnDgradArgs& a, int cin0, int f0);  // (see w0_part)
 
 // ---------------------------------------------------------------------------
+// Gradient w.r.t. the image batch (cnn.hip): transposed first convolution of dZ_0 scattered back
+// through the patch crops of every step, one owner and one summation order per pixel (no atomics)
+// ---------------------------------------------------------------------------
+struct CnnDimgArgs {
+    const float* dz0;    // [ns * na * nb][P][cout]  gradient of layer 0's conv output, row (t, a, b)
+    const float* wt0;    // [9 * cin][ldwt]          layer 0's weight, transposed (k = tap * cin + ci)
+    const int32_t* pos;  // [ns * na * nb][2]        where row (t, a, b) was cropped
+    float* d_img;        // [nb][c_img][H][W]        out, overwritten (16-byte aligned)
+    int ns, na, nb, c_img, H, W;
+    int ldwt, cin, cout, f, hout, P;
+    int th;  // filled by the launcher: lines per tile
+};
+int cnn_dimg_supported(const CnnDimgArgs& a);
+int launch_cnn_dimg(CnnDimgArgs& a, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // Convolution weight gradient straight from the activations (cnn.hip): for every patch,
 //   dW_l[co][tap * cin + ci] += sum over output positions of dZ_l[pos][co] * A_{l-1}[in(pos, tap)][ci]
 // with A_{l-1} = SiLU(GroupNorm(Z_{l-1})) recomputed from the saved pre-norm output (or the raw

@@ -359,6 +359,22 @@ static CnnDgradArgs cnn_dgrad_shape(const Dims& d, int l) {
     return g;
 }
 
+static CnnDimgArgs cnn_dimg_shape(const Dims& d) {
+    CnnDimgArgs a{};
+    a.ns = d.ns;
+    a.na = d.na;
+    a.nb = d.nb;
+    a.c_img = d.c_img;
+    a.H = d.H;
+    a.W = d.W;
+    a.cin = d.ch[0];
+    a.cout = d.ch[1];
+    a.f = d.f;
+    a.hout = d.hw[1];
+    a.P = d.P[0];
+    return a;
+}
+
 static void make_elayout(const Dims& d, int train, ELayout& e) {
     Bump b;
     const size_t R = (size_t)d.R, NR = (size_t)d.NR, S1 = (size_t)d.ns + 1;
@@ -1377,7 +1393,7 @@ struct StepBwd {
 
 static int episode_backward(const Ctx& c0, const void* img, int img_u8, const float* g_preds,
                             const float* g_logp, const float* g_values, float* const* grads,
-                            const StepBwd* sb = nullptr) {
+                            const StepBwd* sb = nullptr, float* d_img = nullptr) {
     Ctx c = c0;
     RedQueue rq;
     rq.reset(c.at(c.e.RED), c.e.red_floats, c.st);
@@ -1892,6 +1908,7 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                 g.beta = c.wp(4 * (l - 1) + 3);
                 g.dzin = c.at(c.e.DZ[l - 1]);
                 if (g.w0 && !img) g.w0 = 0;  // (the step API has no image batch: layer 0 takes the separate launch)
+                if (d_img) g.w0 = 0;         // (the image gradient reads dZ_0 from the workspace)
                 if (c.e.dgrad_ok[l] &&
                     (size_t)cnn_dgrad_blocks(g) * 2 * d.ch[l] <= c.e.part_floats) {
                     RedQueue* q;
@@ -1937,6 +1954,15 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                 chw = 0;
             }
         }
+    }
+    if (d_img) {  // dL/d(img): dZ_0 (left in the workspace by the layer loop above) back through the crops of every step
+        CnnDimgArgs a = cnn_dimg_shape(d);
+        a.dz0 = c.at(c.e.DZ[0]);
+        a.wt0 = c.wt(0);
+        a.ldwt = c.w.ldt[0];
+        a.pos = c.POSs(0);
+        a.d_img = d_img;
+        MARL_TRY(launch_cnn_dimg(a, st));
     }
     if (c.tq) MARL_TRY(launch_tn_queue(tq, c.rq, st));  // the small weight gradients, one launch
     MARL_TRY(rq.flush());
@@ -2145,6 +2171,32 @@ int marl_episode_backward(const marl_config* cfg, void* weights_ws, size_t weigh
         return MARL_EINVAL;
     }
     return episode_backward(c, img, cfg->img_u8 != 0, g_preds, g_logp, g_values, grads_host);
+}
+
+int marl_episode_backward_img(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
+                              void* episode_ws, size_t episode_ws_bytes, const void* img, const float* g_preds,
+                              const float* g_logp, const float* g_values, float* const* grads_host, float* d_img,
+                              void* stream) {
+    Ctx c;
+    SplitRegistryScope reg_scope;
+    MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, 1, stream, c));
+    if (!grads_host) {
+        set_error("episode_backward_img: null gradient table");
+        return MARL_EINVAL;
+    }
+    if (cfg->img_u8 != 0) {
+        set_error("episode_backward_img: an integer (uint8) image batch has no gradient");
+        return MARL_EINVAL;
+    }
+    if (!d_img || !img) {
+        set_error("episode_backward_img: null %s", d_img ? "img" : "d_img");
+        return MARL_EINVAL;
+    }
+    if (!cnn_dimg_supported(cnn_dimg_shape(c.d))) {  // (before anything is enqueued)
+        set_error("episode_backward_img: shape outside the image-gradient kernel's range");
+        return MARL_ELIMIT;
+    }
+    return episode_backward(c, img, 0, g_preds, g_logp, g_values, grads_host, nullptr, d_img);
 }
 
 int marl_backward_heads_event(void* hip_event) {

@@ -373,12 +373,28 @@ class HipEngine:
         g_values: Optional[th.Tensor], grads: Dict[str, th.Tensor],
         generation: Optional[int] = None,
         ws: Optional[th.Tensor] = None, img: Optional[th.Tensor] = None,
+        d_img: Optional[th.Tensor] = None,
     ) -> None:
         """Backward of the LAST training rollout.  `generation` (the value of
         ``fwd_generation`` right after that rollout) makes a stale call fail loudly: the saved
-        activations live in the single training workspace, which a later rollout overwrites."""
+        activations live in the single training workspace, which a later rollout overwrites.
+        ``d_img`` ([Nb,C,H,W] fp32, overwritten): also the gradient w.r.t. the image batch
+        (marl_episode_backward_img); None: the plain entry, nothing extra is launched."""
         cfg = self.cfg
         assert cfg is not None
+        if d_img is not None:
+            d_img = _need(d_img, th.float32, "d_img")
+            if cfg.img_u8 or tuple(d_img.shape) != (cfg.batch, cfg.img_c, cfg.img_h, cfg.img_w):
+                raise RuntimeError("episode_backward: d_img needs a float image batch of the configured shape")
+
+        def run(ews: th.Tensor, image: th.Tensor, gp, gl, gv) -> None:
+            head = (C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews), image.data_ptr(),
+                    _ptr(gp), _ptr(gl), _ptr(gv), self._table(grads))
+            if d_img is None:
+                check(self.lib.marl_episode_backward(*head, _stream(self.device)))
+            else:
+                check(self.lib.marl_episode_backward_img(*head, d_img.data_ptr(), _stream(self.device)))
+
         if ws is not None:  # an episode that owns its workspace (autograd path)
             if getattr(ws, "_marl_key", None) != (self._cfg_key, _tune_epoch) or img is None:
                 raise RuntimeError(
@@ -388,9 +404,7 @@ class HipEngine:
             gl = None if g_logp is None else _need(g_logp, th.float32, "g_logp")
             gv = None if g_values is None else _need(g_values, th.float32, "g_values")
             wws = self.packed_weights_ws()
-            check(self.lib.marl_episode_backward(
-                C.byref(cfg), wws.data_ptr(), _nbytes(wws), ws.data_ptr(), _nbytes(ws), img.data_ptr(), _ptr(gp),
-                _ptr(gl), _ptr(gv), self._table(grads), _stream(self.device)))
+            run(ws, img, gp, gl, gv)
             return
         if self._fwd_img is None or self._fwd_key != self._cfg_key:
             raise RuntimeError(
@@ -406,10 +420,7 @@ class HipEngine:
         gl = None if g_logp is None else _need(g_logp, th.float32, "g_logp")
         gv = None if g_values is None else _need(g_values, th.float32, "g_values")
         wws, ews = self.packed_weights_ws(), self.episode_ws(True)
-        check(self.lib.marl_episode_backward(
-            C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews),
-            self._fwd_img.data_ptr(), _ptr(gp), _ptr(gl), _ptr(gv), self._table(grads),
-            _stream(self.device)))
+        run(ews, self._fwd_img, gp, gl, gv)
 
     def a2c_loss(
         self, out: EpisodeTensors, y: th.Tensor, gamma: float, phase: int = 0,

@@ -11,7 +11,7 @@ import torch as th
 
 from .config import InferConfig, MainConfig, ModelConfig
 from .core import EpisodeSampler
-from .visualization import visualize_steps
+from .visualization import saliency_maps, visualize_steps
 
 
 def load_image_u8(path: str) -> th.Tensor:
@@ -49,4 +49,12 @@ def infer_main(main_config: MainConfig, infer_config: InferConfig) -> int:
         with open(join(out_dir, "info.txt"), "w", encoding="utf-8") as info:
             info.write(f"{img_path}\n{infer_config.json_path}\n{infer_config.state_dict_path}\n")
         visualize_steps(sampler, x.to(device), x, marl_config.window_size, out_dir, class_to_idx)
+        if infer_config.saliency:
+            import matplotlib
+
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+
+            sal = saliency_maps(sampler, x.unsqueeze(0))[0].cpu()
+            plt.imsave(join(out_dir, "saliency.png"), (sal / sal.max().clamp_min(1e-30)).numpy(), cmap="inferno")
     return len(paths)

@@ -5,11 +5,33 @@ Consumer of the ``step_pos`` / ``step_preds`` layout of ``EpisodeSampler.run_epi
 reporting (matplotlib / PIL), nothing here is on the timed path."""
 
 from os.path import join
-from typing import Any, List, Mapping
+from typing import Any, List, Mapping, Optional, Union
 
 import torch as th
 
 from .core import EpisodeSampler
+
+
+def saliency_maps(episode_sampler: EpisodeSampler, img: th.Tensor,
+                  class_idx: Optional[Union[int, th.Tensor]] = None) -> th.Tensor:
+    """Per-pixel attribution of ONE episode: ``|d logit / d pixel|`` maxed over the channels, [Nb, H, W].
+    ``img`` [Nb, C, H, W] (fp32 in [0, 1], or uint8 - converted as ToTensor does) goes through the episode
+    requiring grad; the logit is the chosen class's (``class_idx``: an int or int64 [Nb]; default: the
+    predicted class) in the final agent-mean prediction.  Pixels no agent looked at are exactly 0.  The
+    model's parameter gradients are left untouched."""
+    device = episode_sampler.agents.device
+    x = img.detach().to(device)
+    x = (x.float() / 255.0 if x.dtype == th.uint8 else x.float().clone()).requires_grad_()
+    with th.enable_grad():
+        out = episode_sampler.run_episode(x)
+        logits = out.step_preds[-1].mean(dim=0)  # [Nb, nC]
+        if class_idx is None:
+            cls = logits.detach().argmax(dim=-1)
+        else:
+            cls = th.as_tensor(class_idx, dtype=th.int64, device=device).expand(logits.shape[0])
+        score = logits.gather(1, cls.unsqueeze(1)).sum()
+        (grad,) = th.autograd.grad(score, x)
+    return grad.abs().amax(dim=1)
 
 
 def visualize_steps(episode_sampler: EpisodeSampler, img: th.Tensor, img_ori: th.Tensor,
