@@ -215,6 +215,33 @@ int marl_episode_backward_img(const marl_config* cfg, void* weights_ws, size_t w
                               const float* g_values, float* const* grads_host, float* d_img,
                               void* stream);
 
+/* The action distributions of the fused episode (same ABI version: three added entries, nothing else moves).
+ *
+ * marl_episode_forward_probs: marl_episode_forward with the same arguments, train = 0 or 1, and bit-identical
+ * outputs, which ALSO delivers the distribution every step sampled its action from - softmax of the policy head
+ * (networks/policy.py:16, core/agent.py:51) - into step_probs [Ns,R,nA] (tight, not NULL): one copy launch more, out
+ * of the episode workspace where the sampling kernel keeps them for the backward pass. */
+int marl_episode_forward_probs(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                               void* episode_ws, size_t episode_ws_bytes,
+                               const void* img, const int64_t* pos0,
+                               const float* h0, const float* c0, const float* hc0, const float* cc0,
+                               const float* noise, const int64_t* forced_actions,
+                               uint64_t rng_seed, uint64_t rng_offset, const void* counters,
+                               float* step_preds, float* step_logp, float* step_values,
+                               int64_t* step_pos, int64_t* step_actions, float* step_probs,
+                               int train, void* stream);
+
+/* marl_episode_backward_img with d_img NULLABLE (NULL: parameter gradients only, a uint8 image is fine then) plus
+ * g_probs = dL/d(step_probs) [Ns,R,nA] (NULL = zero): the policy head's logit gradient of every row becomes
+ * p_j (g_j - sum_k p_k g_k) + g_logp (1[j = a] - p_j) - a loss may depend on the whole distribution (entropy bonus,
+ * KL penalty, distillation), not only on the log-probability of the sampled action.  No launch more than the entry
+ * above; with g_probs == NULL and d_img == NULL exactly what marl_episode_backward enqueues. */
+int marl_episode_backward_probs(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
+                                void* episode_ws, size_t episode_ws_bytes,
+                                const void* img, const float* g_preds, const float* g_logp,
+                                const float* g_values, float* const* grads_host, float* d_img,
+                                const float* g_probs, void* stream);
+
 /* Data-parallel overlap (no reference counterpart: training/trainer.py is single-device).  While an event
  * is installed (per-process state, NULL clears it), every marl_episode_backward records it on its stream at the
  * point where the gradients of the three heads' parameters (MARL_P_POL_* .. MARL_P_PRE_*: Policy / Critic /
@@ -235,6 +262,22 @@ int marl_a2c_loss_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episo
                           const float* step_values, const int64_t* y, float gamma,
                           float* g_preds, float* g_logp, float* g_values,
                           float* scalars_out, double* adv_stats, int phase, void* stream);
+
+/* The same loss with an entropy bonus: loss = L - entropy_coef * mean_{a,b} sum_t H(step_probs[t,a,b,:]) - the
+ * reference's reduction th.sum(., 0).mean() (training/trainer.py:111) applied to one more term.
+ * H = -sum_j p_j log p_j with 0 log 0 = 0: an exactly zero probability adds nothing to H and gets g_probs = 0
+ * (th.distributions.Categorical.entropy clamps instead and returns 1.19e-7 for [1,0,0,0]; the naive sum is NaN).
+ * step_probs [Ns,R,nA] (marl_episode_forward_probs); entropy_coef >= 0; g_probs [Ns,R,nA] receives
+ * entropy_coef / R * (log p_j + 1), to be handed to marl_episode_backward_probs; g_preds, g_logp, g_values as above.
+ * scalars_out[5] = {loss including the entropy term, path, error, critic, mean_{t,a,b} H}.  Phase 1 does not touch
+ * the entropy; phases 0 and 2 compute it, in the pass that writes g_logp / g_values: no launch more than the entry
+ * above, fixed-order fp64 partial sums (bit-reproducible). */
+int marl_a2c_loss_entropy_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
+                                  const float* step_preds, const float* step_logp,
+                                  const float* step_values, const int64_t* y, float gamma,
+                                  const float* step_probs, float entropy_coef,
+                                  float* g_preds, float* g_logp, float* g_values, float* g_probs,
+                                  float* scalars_out, double* adv_stats, int phase, void* stream);
 
 /* th.optim.Adam.step (training/trainer.py:33,116) on one flat buffer:
  * betas (0.9, 0.999), eps 1e-8, no weight decay; `step` is 1-based. grad_scale

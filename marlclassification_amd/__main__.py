@@ -71,6 +71,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also write saliency.png (|d logit / d pixel| of the predicted class) per image")
     t.add_argument("--exact-standardize", action="store_true", dest="exact_standardize",
                    help="multi-GPU: global advantage statistics (update == single-GPU big batch)")
+    t.add_argument("--entropy-coef", type=float, default=0.0, dest="entropy_coef",
+                   help="entropy bonus: loss - X * mean_{agents,batch} sum_t H(policy_t) (0: the reference's loss)")
     return p
 
 
@@ -90,7 +92,7 @@ def main(argv=None) -> None:
         train_config = TrainConfig(
             img_size=args.img_size, nb_epoch=args.nb_epoch, learning_rate=args.learning_rate,
             batch_size=args.batch_size, resources_dir=args.res_folder, output_dir=args.output_dir,
-            gamma=args.gamma,
+            gamma=args.gamma, entropy_coef=args.entropy_coef,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":

@@ -75,7 +75,8 @@ EXPORTS = (
     "marl_graph_destroy marl_image_bytes marl_image_build marl_gemm_nt_images marl_gemm_nt_images_batch "
     "marl_lstm_images marl_gemm_tn_images marl_gemm_tn_images_scratch marl_plan_query "
     "marl_gemm_tn_images_cell marl_gemm_tn_images_cell_scratch marl_backward_heads_event "
-    "marl_step_forward_train marl_step_backward marl_episode_backward_img"
+    "marl_step_forward_train marl_step_backward marl_episode_backward_img "
+    "marl_episode_forward_probs marl_episode_backward_probs marl_a2c_loss_entropy_fwd_bwd"
 ).split()
 
 _lib: Optional[C.CDLL] = None
@@ -96,6 +97,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_transition.argtypes = [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _vp]
     lib.marl_episode_forward.argtypes = ([_cfgp, _vp, _sz, _vp, _sz] + [_vp] * 8 + [_u64, _u64, _vp] + [_vp] * 5 +
                                          [_i, _vp])
+    lib.marl_episode_forward_probs.argtypes = ([_cfgp, _vp, _sz, _vp, _sz] + [_vp] * 8 + [_u64, _u64, _vp] +
+                                               [_vp] * 6 + [_i, _vp])
     lib.marl_draw_episode.argtypes = [_cfgp, _u64, _u64, _vp] + [_vp] * 7
     lib.marl_counters_set.argtypes = [_vp, _u64, _i64, _f, _f, _f, _vp]
     lib.marl_counters_tick.argtypes = [_vp, _f, _f, _f, _vp]
@@ -106,6 +109,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_episode_backward.argtypes = [_cfgp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]
     lib.marl_episode_backward_img.argtypes = ([_cfgp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp,
                                                _vp])
+    lib.marl_episode_backward_probs.argtypes = ([_cfgp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp,
+                                                 _vp, _vp])
+    lib.marl_a2c_loss_entropy_fwd_bwd.argtypes = (
+        [_cfgp, _vp, _sz, _vp, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]
+    )
     lib.marl_a2c_loss_fwd_bwd.argtypes = (
         [_cfgp, _vp, _sz, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]
     )

@@ -79,6 +79,8 @@ class TrainConfig(BaseModel):
     resources_dir: str
     output_dir: str
     gamma: float
+    # beta of the entropy bonus: loss - beta * mean_{a,b} sum_t H(pi_t) (0: the reference's plain A2C loss)
+    entropy_coef: float = 0.0
 
 
 class EvalConfig(BaseModel):

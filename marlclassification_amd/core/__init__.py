@@ -1,3 +1,3 @@
 from .agent import AgentOutput, MultiAgent
 from .environment import Environment
-from .episode import EpisodeDetailedOutput, EpisodeOutput, EpisodeSampler
+from .episode import EpisodeDetailedOutput, EpisodeOutput, EpisodeSampler, Trajectory

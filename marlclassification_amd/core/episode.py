@@ -27,30 +27,47 @@ class EpisodeDetailedOutput:
     step_log_probas: th.Tensor
     step_values: th.Tensor
     step_pos: th.Tensor
+    # beyond the reference's four fields: the distribution every step sampled from, [Ns,Na,Nb,nA] (only with
+    # ``EpisodeSampler.return_probs``; differentiable), and the sampled actions, int64 [Ns,Na,Nb]
+    step_probs: Optional[th.Tensor] = None
+    step_actions: Optional[th.Tensor] = None
+
+
+@dataclass
+class Trajectory:
+    """What ``run_episode(img, replay=...)`` needs to walk a stored episode again: its initial draws and the
+    actions it took (``EpisodeSampler.last_trajectory``)."""
+
+    draws: EpisodeDraws
+    actions: th.Tensor  # int64 [Ns,Na,Nb]
 
 
 class _EpisodeFunction(th.autograd.Function):
     """Autograd boundary around the fused episode: inputs are the image batch and the model parameters,
-    outputs step_preds / step_log_probas / step_values (+ non-differentiable positions)."""
+    outputs step_preds / step_log_probas / step_values (+ non-differentiable positions and actions) and, with
+    ``probs``, the differentiable step_probs as a sixth output.  ``forced`` (int64 [Ns,Na,Nb] or None) replaces
+    the sampling (trajectory replay)."""
 
     @staticmethod
-    def forward(ctx, eng: HipEngine, img: th.Tensor, draws: EpisodeDraws, names, *params):
+    def forward(ctx, eng: HipEngine, img: th.Tensor, draws: EpisodeDraws, names, probs: bool,
+                forced: Optional[th.Tensor], *params):
         # every episode owns its saved activations (a training workspace from the engine's pool), so
         # several rollouts of one model can be alive at once and (loss1 + loss2).backward() works as
         # with the reference's autograd graph (reference core/episode.py:84)
         ws = eng.train_ws_acquire()
         out = eng.episode_forward(img, draws.pos0, draws.h0, draws.c0, draws.hc0, draws.cc0,
-                                  draws.noise, None, True, rng=draws.rng, ws=ws)
+                                  draws.noise, forced, True, rng=draws.rng, ws=ws, probs=probs)
         ctx.eng, ctx.ws, ctx.img = eng, ws, img
         ctx.cfg_key = eng._cfg_key
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
         ctx.shapes = [p.shape for p in params]
         ctx.mark_non_differentiable(out.step_pos, out.step_actions)
-        return out.step_preds, out.step_log_probas, out.step_values, out.step_pos, out.step_actions
+        res = (out.step_preds, out.step_log_probas, out.step_values, out.step_pos, out.step_actions)
+        return res + (out.step_probs,) if probs else res
 
     @staticmethod
-    def backward(ctx, g_preds, g_logp, g_values, _g_pos, _g_act):
+    def backward(ctx, g_preds, g_logp, g_values, _g_pos, _g_act, g_probs=None):
         eng: HipEngine = ctx.eng
         if ctx.ws is None:
             raise RuntimeError("this episode's saved activations were already released by an earlier "
@@ -66,12 +83,13 @@ class _EpisodeFunction(th.autograd.Function):
         # the image is a differentiable input (the reference's crop is a masked_select of it,
         # core/environment.py:95-126): asked for, its gradient comes out of the same backward pass
         d_img = th.empty(ctx.img.shape, device=eng.device) if ctx.needs_input_grad[1] else None
-        eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img)
+        eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img,
+                             g_probs=g_probs)
         eng.train_ws_release(ctx.ws)
         ctx.ws = None
         # (a frozen model: the parameter gradients are computed and dropped here)
-        return (None, d_img, None, None) + tuple(
-            grads[k] if need else None for k, need in zip(ctx.names, ctx.needs_input_grad[4:]))
+        return (None, d_img, None, None, None, None) + tuple(
+            grads[k] if need else None for k, need in zip(ctx.names, ctx.needs_input_grad[6:]))
 
 
 class EpisodeSampler:
@@ -86,6 +104,11 @@ class EpisodeSampler:
         # by torch's seed (th.manual_seed keeps runs reproducible) and an episode counter.  False:
         # torch draws in the reference's order (positions, h, c, h^, c^, per-step Exp(1)).
         self.device_rng = True
+        # True: run_episode also returns ``step_probs`` (marl_episode_forward_probs: one copy launch more; under
+        # grad a differentiable output whose gradient reaches the policy head through marl_episode_backward_probs)
+        self.return_probs = False
+        # initial draws and actions of the latest episode: ``run_episode(img, replay=sampler.last_trajectory)``
+        self.last_trajectory: Optional[Trajectory] = None
         self.__episodes = 0
         self.__rng_seed: Optional[int] = None
         # every sampler is its own stream of the generator: the key mixes torch's seed with the
@@ -116,10 +139,11 @@ class EpisodeSampler:
         rank = int(os.environ.get("RANK", "0"))
         return (shard_seed(seed & 0xFFFFFFFFFFFF, rank) * 1_000_003 + self.__stream_id) & ((1 << 63) - 1)
 
-    def prepare(self, img_batch: th.Tensor) -> Tuple[HipEngine, th.Tensor, EpisodeDraws]:
+    def prepare(self, img_batch: th.Tensor,
+                draws: Optional[EpisodeDraws] = None) -> Tuple[HipEngine, th.Tensor, EpisodeDraws]:
         """Everything before the kernels: device transfer, engine configuration, weight
         packing, and the reference's random draws in the reference's order (positions,
-        h, c, h^, c^, per-step Exp(1) noise)."""
+        h, c, h^, c^, per-step Exp(1) noise).  ``draws``: these instead of new ones (a replay)."""
         agents, env = self.__agents, self.__env
         model = agents.model
         device = agents.device
@@ -129,6 +153,9 @@ class EpisodeSampler:
         # uint8 batches ([Nb,C,H,W], 0..255) stay uint8: ToTensor happens inside the gather kernel
         eng.configure(na, nb, ns, img.shape[1:], img_u8=img.dtype == th.uint8)
         model.ensure_packed(eng)
+        if draws is not None:
+            env.place(img, na, positions=draws.pos0)
+            return eng, img, draws
         if self.fixed_draws is not None:
             env.place(img, na, positions=self.fixed_draws.pos0)
             return eng, img, self.fixed_draws
@@ -145,24 +172,42 @@ class EpisodeSampler:
         noise = th.empty(ns, na, nb, env.nb_actions, device=device).exponential_(1.0)
         return eng, img, EpisodeDraws(pos0, st.h, st.c, st.h_caret, st.c_caret, noise)
 
-    def __episode_impl(self, img_batch: th.Tensor) -> EpisodeDetailedOutput:
-        eng, img, draws = self.prepare(img_batch)
+    def __check_replay(self, img_batch: th.Tensor, replay: Trajectory) -> None:
+        na, nb, ns = len(self.__agents), img_batch.shape[0], self.__nb_step
+        d = replay.draws
+        got = {"actions": (replay.actions, (ns, na, nb)), "pos0": (d.pos0, (na, nb, 2))}
+        got.update({k: (getattr(d, k), (na, nb)) for k in ("h0", "c0", "hc0", "cc0")})
+        for k, (t, shape) in got.items():
+            if tuple(t.shape[:len(shape)]) != shape or (k in ("actions", "pos0") and t.dim() != len(shape)):
+                raise ValueError(f"replay: {k} has shape {tuple(t.shape)}, this batch needs {shape} "
+                                 "([steps,] agents, batch first) - a trajectory replays on a batch of its own size")
+
+    def __episode_impl(self, img_batch: th.Tensor, replay: Optional[Trajectory] = None) -> EpisodeDetailedOutput:
+        if replay is not None:
+            self.__check_replay(img_batch, replay)  # (before anything is transferred or enqueued)
+        eng, img, draws = self.prepare(img_batch, None if replay is None else replay.draws)
+        forced = None if replay is None else replay.actions.to(img.device)
         model = self.__agents.model
+        want_probs = bool(self.return_probs)
         if th.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in model.parameters())):
             named = list(model.named_parameters())
             names = tuple(k for k, _ in named)
-            preds, logp, values, pos, _ = _EpisodeFunction.apply(
-                eng, img, draws, names, *[p for _, p in named])
+            res = _EpisodeFunction.apply(eng, img, draws, names, want_probs, forced, *[p for _, p in named])
+            preds, logp, values, pos, act = res[:5]
+            probs = res[5] if want_probs else None
         else:
             out = eng.episode_forward(img, draws.pos0, draws.h0, draws.c0, draws.hc0, draws.cc0,
-                                      draws.noise, None, False, rng=draws.rng)
-            preds, logp, values, pos = (out.step_preds, out.step_log_probas, out.step_values,
-                                        out.step_pos)
+                                      draws.noise, forced, False, rng=draws.rng, probs=want_probs)
+            preds, logp, values, pos, act, probs = (out.step_preds, out.step_log_probas, out.step_values,
+                                                    out.step_pos, out.step_actions, out.step_probs)
         self.__env._set_positions(pos[-1])
-        return EpisodeDetailedOutput(preds, logp, values, pos)
+        self.last_trajectory = Trajectory(draws, act)
+        return EpisodeDetailedOutput(preds, logp, values, pos, probs, act)
 
-    def run_episode(self, img_batch: th.Tensor) -> EpisodeDetailedOutput:
-        return self.__episode_impl(img_batch)
+    def run_episode(self, img_batch: th.Tensor, replay: Optional[Trajectory] = None) -> EpisodeDetailedOutput:
+        """``replay``: walk a stored trajectory again - its initial draws, its actions forced - under the
+        current weights (log pi_new(a) - log pi_old(a) on stored data; differentiable as usual)."""
+        return self.__episode_impl(img_batch, replay)
 
     def run_episode_get_last_step(self, img_batch: th.Tensor) -> EpisodeOutput:
         out = self.__episode_impl(img_batch)
@@ -170,13 +215,14 @@ class EpisodeSampler:
                              actions_log_probs=out.step_log_probas[-1])
 
     def run_episode_raw(self, img_batch: th.Tensor, train: bool,
-                        draws: Optional[EpisodeDraws] = None) -> Tuple[HipEngine, EpisodeTensors]:
+                        draws: Optional[EpisodeDraws] = None,
+                        probs: bool = False) -> Tuple[HipEngine, EpisodeTensors]:
         """No autograd node: used by the fused Trainer (loss + backward are HIP calls).  An image that
         requires grad is ignored here - the gradient w.r.t. the image exists on the ``run_episode`` path."""
         eng, img, d = self.prepare(img_batch)
         if draws is not None:
             d = draws
         out = eng.episode_forward(img, d.pos0, d.h0, d.c0, d.hc0, d.cc0, d.noise, None, train,
-                                  rng=d.rng)
+                                  rng=d.rng, probs=probs)
         self.__env._set_positions(out.step_pos[-1])
         return eng, out

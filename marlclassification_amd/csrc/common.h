@@ -927,6 +927,11 @@ struct LossArgs {
     int ns, na, nb, nc;
     float gamma;
     int phase;
+    // marl_a2c_loss_entropy_fwd_bwd (probs != nullptr): the entropy bonus, scalars is [5] then
+    const float* probs = nullptr;  // [Ns*R, nA] tight
+    float* g_probs = nullptr;      // [Ns*R, nA] tight
+    int n_act = 0;
+    float entropy_coef = 0.f;
 };
 size_t loss_scratch_floats(int ns, int na, int nb);
 int launch_loss(const LossArgs& a, hipStream_t st);

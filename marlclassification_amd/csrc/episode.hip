@@ -1393,7 +1393,8 @@ struct StepBwd {
 
 static int episode_backward(const Ctx& c0, const void* img, int img_u8, const float* g_preds,
                             const float* g_logp, const float* g_values, float* const* grads,
-                            const StepBwd* sb = nullptr, float* d_img = nullptr) {
+                            const StepBwd* sb = nullptr, float* d_img = nullptr,
+                            const float* g_probs = nullptr) {
     Ctx c = c0;
     RedQueue rq;
     rq.reset(c.at(c.e.RED), c.e.red_floats, c.st);
@@ -1457,8 +1458,9 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
     }
     MARL_TRY(tn(c, c.at(c.e.DAC1), d.ld_nla, c.HCs(1), d.ld_na, MARL_P_CRI_W0, d.nla, d.n_a, NR, grads[MARL_P_CRI_B0]));
     // policy head: logp = log softmax(logits)[a]  (networks/policy.py:12-16, core/agent.py:57-61)
-    if (sb && sb->g_probs)  // standalone step: dL/dprobs from the caller (+ the dlogp term)
-        MARL_TRY(launch_policy_dlogits_probs(g_logp, sb->g_probs, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG),
+    if (sb && sb->g_probs) g_probs = sb->g_probs;
+    if (g_probs)  // dL/dprobs from the caller (+ the dlogp term): a standalone step [R, nA] or all steps [Ns, R, nA]
+        MARL_TRY(launch_policy_dlogits_probs(g_logp, g_probs, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG),
                                              d.ld_nA, NR, d.nA, st));
     else
         MARL_TRY(launch_policy_dlogits(g_logp, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG), d.ld_nA, NR,
@@ -2071,13 +2073,15 @@ int marl_transition(const int64_t* pos_in, const int64_t* actions, int64_t* pos_
     return MARL_OK;
 }
 
-int marl_episode_forward(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
-                         void* episode_ws, size_t episode_ws_bytes, const void* img, const int64_t* pos0, const float* h0, const float* c0,
-                         const float* hc0, const float* cc0, const float* noise,
-                         const int64_t* forced_actions, uint64_t rng_seed, uint64_t rng_offset,
-                         const void* counters, float* step_preds, float* step_logp,
-                         float* step_values, int64_t* step_pos, int64_t* step_actions, int train,
-                         void* stream) {
+// marl_episode_forward (step_probs == nullptr) and marl_episode_forward_probs: the same launches, the latter plus
+// one copy of the workspace's PROBS [Ns][R][nA] (what every step's sampling kernel saved) into the caller's tensor
+static int episode_forward_all(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                               void* episode_ws, size_t episode_ws_bytes, const void* img, const int64_t* pos0,
+                               const float* h0, const float* c0, const float* hc0, const float* cc0,
+                               const float* noise, const int64_t* forced_actions, uint64_t rng_seed,
+                               uint64_t rng_offset, const void* counters, float* step_preds, float* step_logp,
+                               float* step_values, int64_t* step_pos, int64_t* step_actions, float* step_probs,
+                               int train, void* stream) {
     Ctx c;
     SplitRegistryScope reg_scope;
     MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, train, stream, c));
@@ -2157,7 +2161,37 @@ int marl_episode_forward(const marl_config* cfg, const void* weights_ws, size_t 
         if (chain || !decoded_ahead) MARL_TRY(launch_sample(a, c.st));
     }
     if (side) MARL_TRY(g_side.order(c2.st, c.st));  // join before the caller's stream continues
-    return heads_batched(c, 0, d.NR, step_values, step_preds);
+    MARL_TRY(heads_batched(c, 0, d.NR, step_values, step_preds));
+    if (step_probs) MARL_TRY(launch_copy2d(c.PROBSs(0), d.nA, step_probs, d.nA, d.NR, d.nA, c.st));
+    return MARL_OK;
+}
+
+int marl_episode_forward(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                         void* episode_ws, size_t episode_ws_bytes, const void* img, const int64_t* pos0, const float* h0, const float* c0,
+                         const float* hc0, const float* cc0, const float* noise,
+                         const int64_t* forced_actions, uint64_t rng_seed, uint64_t rng_offset,
+                         const void* counters, float* step_preds, float* step_logp,
+                         float* step_values, int64_t* step_pos, int64_t* step_actions, int train,
+                         void* stream) {
+    return episode_forward_all(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, img, pos0, h0, c0,
+                               hc0, cc0, noise, forced_actions, rng_seed, rng_offset, counters, step_preds,
+                               step_logp, step_values, step_pos, step_actions, nullptr, train, stream);
+}
+
+int marl_episode_forward_probs(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                               void* episode_ws, size_t episode_ws_bytes, const void* img, const int64_t* pos0,
+                               const float* h0, const float* c0, const float* hc0, const float* cc0,
+                               const float* noise, const int64_t* forced_actions, uint64_t rng_seed,
+                               uint64_t rng_offset, const void* counters, float* step_preds, float* step_logp,
+                               float* step_values, int64_t* step_pos, int64_t* step_actions, float* step_probs,
+                               int train, void* stream) {
+    if (!step_probs) {
+        set_error("episode_forward_probs: null step_probs");
+        return MARL_EINVAL;
+    }
+    return episode_forward_all(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, img, pos0, h0, c0,
+                               hc0, cc0, noise, forced_actions, rng_seed, rng_offset, counters, step_preds,
+                               step_logp, step_values, step_pos, step_actions, step_probs, train, stream);
 }
 
 int marl_episode_backward(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
@@ -2197,6 +2231,35 @@ int marl_episode_backward_img(const marl_config* cfg, void* weights_ws, size_t w
         return MARL_ELIMIT;
     }
     return episode_backward(c, img, 0, g_preds, g_logp, g_values, grads_host, nullptr, d_img);
+}
+
+int marl_episode_backward_probs(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
+                                void* episode_ws, size_t episode_ws_bytes, const void* img, const float* g_preds,
+                                const float* g_logp, const float* g_values, float* const* grads_host, float* d_img,
+                                const float* g_probs, void* stream) {
+    Ctx c;
+    SplitRegistryScope reg_scope;
+    MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, 1, stream, c));
+    if (!grads_host) {
+        set_error("episode_backward_probs: null gradient table");
+        return MARL_EINVAL;
+    }
+    if (d_img) {  // the checks of marl_episode_backward_img, before anything is enqueued
+        if (cfg->img_u8 != 0) {
+            set_error("episode_backward_probs: an integer (uint8) image batch has no gradient");
+            return MARL_EINVAL;
+        }
+        if (!img) {
+            set_error("episode_backward_probs: null img");
+            return MARL_EINVAL;
+        }
+        if (!cnn_dimg_supported(cnn_dimg_shape(c.d))) {
+            set_error("episode_backward_probs: shape outside the image-gradient kernel's range");
+            return MARL_ELIMIT;
+        }
+    }
+    return episode_backward(c, img, d_img ? 0 : cfg->img_u8 != 0, g_preds, g_logp, g_values, grads_host, nullptr,
+                            d_img, g_probs);
 }
 
 int marl_backward_heads_event(void* hip_event) {
@@ -2312,6 +2375,50 @@ int marl_a2c_loss_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episo
     a.nc = d.nC;
     a.gamma = gamma;
     a.phase = phase;
+    return launch_loss(a, static_cast<hipStream_t>(stream));
+}
+
+int marl_a2c_loss_entropy_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
+                                  const float* step_preds, const float* step_logp, const float* step_values,
+                                  const int64_t* y, float gamma, const float* step_probs, float entropy_coef,
+                                  float* g_preds, float* g_logp, float* g_values, float* g_probs,
+                                  float* scalars_out, double* adv_stats, int phase, void* stream) {
+    Dims d;
+    MARL_TRY(make_dims(cfg, d));
+    if (!episode_ws || !step_preds || !step_logp || !step_values || !y || !step_probs || !g_probs ||
+        !scalars_out || !adv_stats || phase < 0 || phase > 2 || !(entropy_coef >= 0.f)) {
+        set_error("a2c_loss_entropy: bad argument");
+        return MARL_EINVAL;
+    }
+    ELayout e;
+    make_elayout(d, 1, e);
+    if (episode_ws_bytes < e.total * sizeof(float)) {
+        set_error("a2c_loss_entropy: episode workspace too small (%zu of %zu bytes, training layout)",
+                  episode_ws_bytes, e.total * sizeof(float));
+        return MARL_ESIZE;
+    }
+    LossArgs a;
+    a.preds = step_preds;
+    a.logp = step_logp;
+    a.values = step_values;
+    a.y = y;
+    a.g_preds = g_preds;
+    a.ld_gp = d.nC;
+    a.g_logp = g_logp;
+    a.g_values = g_values;
+    a.scalars = scalars_out;
+    a.adv_stats = adv_stats;
+    a.scratch = static_cast<float*>(episode_ws) + e.LOSS;
+    a.ns = d.ns;
+    a.na = d.na;
+    a.nb = d.nb;
+    a.nc = d.nC;
+    a.gamma = gamma;
+    a.phase = phase;
+    a.probs = step_probs;
+    a.g_probs = g_probs;
+    a.n_act = d.nA;
+    a.entropy_coef = entropy_coef;
     return launch_loss(a, static_cast<hipStream_t>(stream));
 }
 

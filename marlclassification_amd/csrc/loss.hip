@@ -178,14 +178,21 @@ __global__ __launch_bounds__(256) void loss_stats_kernel(
     }
 }
 
+// ENT (marl_a2c_loss_entropy_fwd_bwd): the same pass also reads row i of the step distributions [NR][nA] and writes
+// H_i = -sum_j p_j log p_j into a third partial and g_probs[i][j] = beta / R * (log p_j + 1).  0 * log 0 = 0: an
+// exactly zero probability adds nothing to H and gets a zero gradient (nothing becomes NaN / Inf).  VEC: nA % 4 == 0
+// and 16-byte aligned tensors - a row moves as float4s.  ENT = false is the kernel of marl_a2c_loss_fwd_bwd.
+template <bool ENT, bool VEC>
 __global__ __launch_bounds__(256) void loss_grads_kernel(
     const float* __restrict__ logp, const float* __restrict__ values,
     const float* __restrict__ ret, const float* __restrict__ adv,
     const double* __restrict__ adv_stats, float* __restrict__ g_logp,
-    float* __restrict__ g_values, double* __restrict__ part, int64_t NR, int64_t R) {
-    __shared__ double sh[2][256];
+    float* __restrict__ g_values, double* __restrict__ part, int64_t NR, int64_t R,
+    const float* __restrict__ probs, float* __restrict__ g_probs, double* __restrict__ part_ent, int nA,
+    float beta) {
+    __shared__ double sh[ENT ? 3 : 2][256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
     if (i < NR) {
         const double n = adv_stats[0];
         const double mean_d = adv_stats[1] / n;
@@ -200,40 +207,74 @@ __global__ __launch_bounds__(256) void loss_grads_kernel(
         s2 = (double)(ad < 1.0f ? 0.5f * d * d : ad - 0.5f);
         if (g_logp) g_logp[i] = -advn * invR;
         if (g_values) g_values[i] = (ad < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f)) * invR;
+        if (ENT) {
+            const float scale = beta * invR;
+            float h = 0.f;
+            auto term = [&](float p) {  // adds p log p to h, returns the gradient
+                if (!(p > 0.f)) return 0.f;
+                const float lp = logf(p);
+                h = fmaf(p, lp, h);
+                return scale * (lp + 1.0f);
+            };
+            if (VEC) {
+                const float4* pv = reinterpret_cast<const float4*>(probs + i * nA);
+                float4* gv = reinterpret_cast<float4*>(g_probs + i * nA);
+                for (int k = 0; k < nA / 4; ++k) {
+                    const float4 p = pv[k];
+                    float4 g;
+                    g.x = term(p.x);
+                    g.y = term(p.y);
+                    g.z = term(p.z);
+                    g.w = term(p.w);
+                    gv[k] = g;
+                }
+            } else {
+                for (int j = 0; j < nA; ++j) g_probs[i * nA + j] = term(probs[i * nA + j]);
+            }
+            s3 = (double)(-h);
+        }
     }
     sh[0][threadIdx.x] = s1;
     sh[1][threadIdx.x] = s2;
+    if (ENT) sh[2][threadIdx.x] = s3;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (threadIdx.x < o) {
             sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
             sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+            if (ENT) sh[2][threadIdx.x] += sh[2][threadIdx.x + o];
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = sh[0][0];
         part[2 * blockIdx.x + 1] = sh[1][0];
+        if (ENT) part_ent[blockIdx.x] = sh[2][0];
     }
 }
 
-// scalars = {loss, path.sum(0).mean(), error.mean(), critic.sum(0).mean()} (trainer.py:111,119-122)
+// scalars = {loss, path.sum(0).mean(), error.mean(), critic.sum(0).mean()} (trainer.py:111,119-122);
+// ENT: loss -= beta * mean_{a,b} sum_t H and scalars[4] = mean_{t,a,b} H
+template <bool ENT>
 __global__ __launch_bounds__(256) void loss_final_kernel(
     const double* __restrict__ part, int nblocks, const double* __restrict__ part_err,
-    float* __restrict__ scalars, int ns, int nb, int64_t R) {
-    __shared__ double sh[2][256];
-    double p = 0.0, c = 0.0;
+    float* __restrict__ scalars, int ns, int nb, int64_t R, const double* __restrict__ part_ent, float beta) {
+    __shared__ double sh[ENT ? 3 : 2][256];
+    double p = 0.0, c = 0.0, h = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) {
         p += part[2 * i];
         c += part[2 * i + 1];
+        if (ENT) h += part_ent[i];
     }
     sh[0][threadIdx.x] = p;
     sh[1][threadIdx.x] = c;
+    if (ENT) sh[2][threadIdx.x] = h;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (threadIdx.x < o) {
             sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
             sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+            if (ENT) sh[2][threadIdx.x] += sh[2][threadIdx.x + o];
         }
         __syncthreads();
     }
@@ -242,7 +283,13 @@ __global__ __launch_bounds__(256) void loss_final_kernel(
         c = sh[1][0];
         const double path = p / (double)R, critic = c / (double)R;
         const double esum = part_err[0];
-        scalars[0] = (float)(path + esum / (double)nb + critic);
+        double loss = path + esum / (double)nb + critic;
+        if (ENT) {
+            h = sh[2][0];
+            loss -= (double)beta * (h / (double)R);
+            scalars[4] = (float)(h / ((double)R * ns));
+        }
+        scalars[0] = (float)loss;
         scalars[1] = (float)path;
         scalars[2] = (float)(esum / ((double)ns * nb));
         scalars[3] = (float)critic;
@@ -274,12 +321,36 @@ int launch_loss(const LossArgs& a, hipStream_t st) {
         MARL_LAUNCH_CHECK();
     }
     if (a.phase == 0 || a.phase == 2) {
-        hipLaunchKernelGGL(loss_grads_kernel, dim3((unsigned)L.blocksE), dim3(256), 0, st, a.logp,
-                           a.values, L.ret, L.adv, stats, a.g_logp, a.g_values, L.part_loss, NR, R);
-        MARL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, L.part_loss, L.blocksE,
-                           L.part_err, a.scalars, a.ns, a.nb, R);
-        MARL_LAUNCH_CHECK();
+        const dim3 grid((unsigned)L.blocksE), block(256);
+        if (!a.probs) {
+            hipLaunchKernelGGL((loss_grads_kernel<false, false>), grid, block, 0, st, a.logp, a.values, L.ret, L.adv,
+                               stats, a.g_logp, a.g_values, L.part_loss, NR, R, nullptr, nullptr, nullptr, 0, 0.f);
+            MARL_LAUNCH_CHECK();
+            hipLaunchKernelGGL(loss_final_kernel<false>, dim3(1), dim3(256), 0, st, L.part_loss, L.blocksE,
+                               L.part_err, a.scalars, a.ns, a.nb, R, nullptr, 0.f);
+            MARL_LAUNCH_CHECK();
+        } else {
+            // the entropy partials [blocksE] take the place of the rewards, dead since loss_returns_kernel (phases 0
+            // and 1); a single (t, r) row has no room there - the 16 spare floats behind `err` hold its one partial
+            double* part_ent =
+                NR >= 2 ? reinterpret_cast<double*>(L.rew)
+                        : reinterpret_cast<double*>(
+                              (reinterpret_cast<uintptr_t>(L.err + (int64_t)a.ns * a.nb) + 7) & ~(uintptr_t)7);
+            const bool vec = a.n_act % 4 == 0 && (reinterpret_cast<uintptr_t>(a.probs) & 15) == 0 &&
+                             (reinterpret_cast<uintptr_t>(a.g_probs) & 15) == 0;
+            if (vec)
+                hipLaunchKernelGGL((loss_grads_kernel<true, true>), grid, block, 0, st, a.logp, a.values, L.ret,
+                                   L.adv, stats, a.g_logp, a.g_values, L.part_loss, NR, R, a.probs, a.g_probs,
+                                   part_ent, a.n_act, a.entropy_coef);
+            else
+                hipLaunchKernelGGL((loss_grads_kernel<true, false>), grid, block, 0, st, a.logp, a.values, L.ret,
+                                   L.adv, stats, a.g_logp, a.g_values, L.part_loss, NR, R, a.probs, a.g_probs,
+                                   part_ent, a.n_act, a.entropy_coef);
+            MARL_LAUNCH_CHECK();
+            hipLaunchKernelGGL(loss_final_kernel<true>, dim3(1), dim3(256), 0, st, L.part_loss, L.blocksE,
+                               L.part_err, a.scalars, a.ns, a.nb, R, part_ent, a.entropy_coef);
+            MARL_LAUNCH_CHECK();
+        }
     }
     return MARL_OK;
 }

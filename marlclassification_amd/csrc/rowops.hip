@@ -1464,10 +1464,73 @@ __global__ void policy_dlogits_probs_kernel(const float* __restrict__ dlogp,
     for (int j = 0; j < nA; ++j)
         out[r * ld + j] = p[j] * (g[j] - s) + gl * ((j == a ? 1.0f : 0.0f) - p[j]);
 }
+// the same with nA = 4 * NV: a row's probabilities and upstream gradients arrive as NV 16-byte loads each and its
+// logit gradients leave as NV 16-byte stores (the fused episode runs this over Ns * R rows: three streams of
+// rows * nA floats, HBM-bound).  Same operations in the same order as the scalar kernel: same bits.
+template <int NV>
+__global__ __launch_bounds__(256) void policy_dlogits_probs_v4_kernel(const float* __restrict__ dlogp,
+                                                                      const float* __restrict__ dprobs,
+                                                                      const float* __restrict__ probs,
+                                                                      const int32_t* __restrict__ actions,
+                                                                      float* __restrict__ out, int ld, int64_t rows) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const float4* pv = reinterpret_cast<const float4*>(probs + r * (4 * NV));
+    const float4* gv = reinterpret_cast<const float4*>(dprobs + r * (4 * NV));
+    float p[4 * NV], g[4 * NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const float4 a = pv[k], b = gv[k];
+        p[4 * k] = a.x, p[4 * k + 1] = a.y, p[4 * k + 2] = a.z, p[4 * k + 3] = a.w;
+        g[4 * k] = b.x, g[4 * k + 1] = b.y, g[4 * k + 2] = b.z, g[4 * k + 3] = b.w;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4 * NV; ++j) s = fmaf(p[j], g[j], s);
+    const float gl = dlogp ? dlogp[r] : 0.f;
+    const int a = dlogp ? actions[r] : -1;
+    float4* ov = reinterpret_cast<float4*>(out + r * ld);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        float o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = 4 * k + q;
+            o[q] = p[j] * (g[j] - s) + gl * ((j == a ? 1.0f : 0.0f) - p[j]);
+        }
+        ov[k] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 int launch_policy_dlogits_probs(const float* dlogp, const float* dprobs, const float* probs,
                                 const int32_t* actions, float* out, int ld, int64_t rows, int nA,
                                 hipStream_t st) {
     if (rows <= 0) return MARL_OK;
+    if (nA % 4 == 0 && nA <= 16 && ld % 4 == 0 && aligned16(dprobs) && aligned16(probs) && aligned16(out)) {
+        const dim3 grid((unsigned)cdiv(rows, 256)), block(256);
+        switch (nA / 4) {
+        case 1:
+            hipLaunchKernelGGL(policy_dlogits_probs_v4_kernel<1>, grid, block, 0, st, dlogp, dprobs, probs, actions,
+                               out, ld, rows);
+            break;
+        case 2:
+            hipLaunchKernelGGL(policy_dlogits_probs_v4_kernel<2>, grid, block, 0, st, dlogp, dprobs, probs, actions,
+                               out, ld, rows);
+            break;
+        case 3:
+            hipLaunchKernelGGL(policy_dlogits_probs_v4_kernel<3>, grid, block, 0, st, dlogp, dprobs, probs, actions,
+                               out, ld, rows);
+            break;
+        default:
+            hipLaunchKernelGGL(policy_dlogits_probs_v4_kernel<4>, grid, block, 0, st, dlogp, dprobs, probs, actions,
+                               out, ld, rows);
+            break;
+        }
+        MARL_LAUNCH_CHECK();
+        return MARL_OK;
+    }
     hipLaunchKernelGGL(policy_dlogits_probs_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, st,
                        dlogp, dprobs, probs, actions, out, ld, rows, nA);
     MARL_LAUNCH_CHECK();

@@ -167,6 +167,8 @@ class EpisodeTensors:
     step_values: th.Tensor
     step_pos: th.Tensor
     step_actions: th.Tensor
+    # [Ns,Na,Nb,nA]: the distribution every step sampled from (episode_forward(probs=True)), else None
+    step_probs: Optional[th.Tensor] = None
 
 
 class HipEngine:
@@ -322,10 +324,11 @@ class HipEngine:
         cc0: th.Tensor, noise: Optional[th.Tensor], forced_actions: Optional[th.Tensor] = None,
         train: bool = True, rng: Optional[Tuple[int, int]] = None,
         out: Optional[EpisodeTensors] = None, counters: Optional[th.Tensor] = None,
-        ws: Optional[th.Tensor] = None,
+        ws: Optional[th.Tensor] = None, probs: bool = False,
     ) -> EpisodeTensors:
         """``noise`` = injected Exp(1) draws [Ns,Na,Nb,nA] (parity mode); ``noise=None`` with
-        ``rng=(seed, offset)`` draws them inside the sampling kernel (perf mode)."""
+        ``rng=(seed, offset)`` draws them inside the sampling kernel (perf mode).  ``probs``: also
+        ``step_probs`` (marl_episode_forward_probs; an ``out`` that already holds the tensor asks for it too)."""
         cfg = self.cfg
         assert cfg is not None
         na, nb, ns = cfg.nb_agents, cfg.batch, cfg.nb_steps
@@ -342,21 +345,26 @@ class HipEngine:
             raise ValueError("episode_forward needs noise, forced_actions or rng=(seed, offset)")
         seed, offset = rng if rng is not None else (0, 0)
         if out is None:  # (graph capture passes persistent output tensors: nothing may allocate)
-            out = self.new_outputs()
+            out = self.new_outputs(probs)
+        elif probs and out.step_probs is None:
+            raise ValueError("episode_forward(probs=True): `out` has no step_probs tensor (new_outputs(True))")
         wws, ews = self.packed_weights_ws(), (ws if ws is not None else self.episode_ws(train))
-        check(self.lib.marl_episode_forward(
-            C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews),
-            img.data_ptr(), pos0.data_ptr(), h0.data_ptr(), c0.data_ptr(), hc0.data_ptr(),
-            cc0.data_ptr(), _ptr(noise), _ptr(forced_actions), seed & _U64, offset & _U64,
-            _ptr(counters), out.step_preds.data_ptr(), out.step_log_probas.data_ptr(), out.step_values.data_ptr(),
-            out.step_pos.data_ptr(), out.step_actions.data_ptr(), int(train), _stream(dev)))
+        head = (C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews),
+                img.data_ptr(), pos0.data_ptr(), h0.data_ptr(), c0.data_ptr(), hc0.data_ptr(),
+                cc0.data_ptr(), _ptr(noise), _ptr(forced_actions), seed & _U64, offset & _U64,
+                _ptr(counters), out.step_preds.data_ptr(), out.step_log_probas.data_ptr(), out.step_values.data_ptr(),
+                out.step_pos.data_ptr(), out.step_actions.data_ptr())
+        if out.step_probs is None:
+            check(self.lib.marl_episode_forward(*head, int(train), _stream(dev)))
+        else:
+            check(self.lib.marl_episode_forward_probs(*head, out.step_probs.data_ptr(), int(train), _stream(dev)))
         if train and ws is None:  # (an episode with its own workspace does not touch the engine's)
             self.fwd_generation += 1
             self._fwd_img = img
             self._fwd_key = self._cfg_key
         return out
 
-    def new_outputs(self) -> EpisodeTensors:
+    def new_outputs(self, probs: bool = False) -> EpisodeTensors:
         cfg = self.cfg
         assert cfg is not None
         na, nb, ns, dev = cfg.nb_agents, cfg.batch, cfg.nb_steps, self.device
@@ -366,6 +374,7 @@ class HipEngine:
             th.empty(ns, na, nb, device=dev),
             th.empty(ns, na, nb, 2, dtype=th.int64, device=dev),
             th.empty(ns, na, nb, dtype=th.int64, device=dev),
+            th.empty(ns, na, nb, cfg.nb_action, device=dev) if probs else None,
         )
 
     def episode_backward(
@@ -373,15 +382,26 @@ class HipEngine:
         g_values: Optional[th.Tensor], grads: Dict[str, th.Tensor],
         generation: Optional[int] = None,
         ws: Optional[th.Tensor] = None, img: Optional[th.Tensor] = None,
-        d_img: Optional[th.Tensor] = None,
+        d_img: Optional[th.Tensor] = None, g_probs: Optional[th.Tensor] = None,
     ) -> None:
         """Backward of the LAST training rollout.  `generation` (the value of
         ``fwd_generation`` right after that rollout) makes a stale call fail loudly: the saved
         activations live in the single training workspace, which a later rollout overwrites.
         ``d_img`` ([Nb,C,H,W] fp32, overwritten): also the gradient w.r.t. the image batch
-        (marl_episode_backward_img); None: the plain entry, nothing extra is launched."""
+        (marl_episode_backward_img); None: the plain entry, nothing extra is launched.
+        ``g_probs`` ([Ns,Na,Nb,nA] fp32): dL/d(step_probs) (marl_episode_backward_probs, with or without ``d_img``);
+        None: the entries above, verbatim."""
         cfg = self.cfg
         assert cfg is not None
+        if g_probs is not None:
+            want = (cfg.nb_steps, cfg.nb_agents, cfg.batch, cfg.nb_action)
+            if not isinstance(g_probs, th.Tensor) or tuple(g_probs.shape) != want:
+                raise RuntimeError(f"episode_backward: g_probs must be a tensor of shape {want}, got "
+                                   f"{tuple(getattr(g_probs, 'shape', ()))}")
+            if g_probs.device != self.device:
+                raise RuntimeError(f"episode_backward: g_probs lives on {g_probs.device}, the episode on "
+                                   f"{self.device}")
+            g_probs = _need(g_probs, th.float32, "g_probs")
         if d_img is not None:
             d_img = _need(d_img, th.float32, "d_img")
             if cfg.img_u8 or tuple(d_img.shape) != (cfg.batch, cfg.img_c, cfg.img_h, cfg.img_w):
@@ -390,7 +410,10 @@ class HipEngine:
         def run(ews: th.Tensor, image: th.Tensor, gp, gl, gv) -> None:
             head = (C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews), image.data_ptr(),
                     _ptr(gp), _ptr(gl), _ptr(gv), self._table(grads))
-            if d_img is None:
+            if g_probs is not None:
+                check(self.lib.marl_episode_backward_probs(*head, _ptr(d_img), g_probs.data_ptr(),
+                                                           _stream(self.device)))
+            elif d_img is None:
                 check(self.lib.marl_episode_backward(*head, _stream(self.device)))
             else:
                 check(self.lib.marl_episode_backward_img(*head, d_img.data_ptr(), _stream(self.device)))
@@ -424,27 +447,52 @@ class HipEngine:
 
     def a2c_loss(
         self, out: EpisodeTensors, y: th.Tensor, gamma: float, phase: int = 0,
-        bufs: Optional[Tuple[th.Tensor, ...]] = None,
-    ) -> Tuple[th.Tensor, th.Tensor, th.Tensor, th.Tensor, th.Tensor]:
-        """Returns (g_preds, g_logp, g_values, scalars[4], adv_stats[3] float64)."""
+        bufs: Optional[Tuple[th.Tensor, ...]] = None, entropy_coef: float = 0.0,
+    ) -> Tuple[th.Tensor, ...]:
+        """Returns (g_preds, g_logp, g_values, scalars[4], adv_stats[3] float64).
+        ``entropy_coef`` > 0 (marl_a2c_loss_entropy_fwd_bwd; ``out.step_probs`` needed): the loss minus
+        ``entropy_coef * mean_{a,b} sum_t H``; returns (g_preds, g_logp, g_values, scalars[5], adv_stats, g_probs)
+        with scalars[4] = the mean entropy.  0: the plain entry, verbatim."""
         cfg = self.cfg
         assert cfg is not None
         dev = self.device
+        if not entropy_coef >= 0.0:
+            raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
         y = _need(y, th.int64, "y")
+        ent = entropy_coef > 0.0
+        if ent and out.step_probs is None:
+            raise ValueError("a2c_loss(entropy_coef > 0) needs the episode's step_probs: episode_forward(probs=True)")
         if bufs is None:
-            bufs = (
-                th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
-                th.empty_like(out.step_values), th.zeros(4, device=dev),
-                th.zeros(3, dtype=th.float64, device=dev),
-            )
-        gp, gl, gv, sc, st = bufs
+            bufs = self.new_loss_bufs(out, ent)
         ews = self.episode_ws(True)
-        check(self.lib.marl_a2c_loss_fwd_bwd(
+        if not ent:
+            gp, gl, gv, sc, st = bufs
+            check(self.lib.marl_a2c_loss_fwd_bwd(
+                C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(),
+                out.step_log_probas.data_ptr(), out.step_values.data_ptr(), y.data_ptr(),
+                C.c_float(gamma), gp.data_ptr(), gl.data_ptr(), gv.data_ptr(), sc.data_ptr(),
+                st.data_ptr(), phase, _stream(dev)))
+            return bufs
+        if len(bufs) != 6 or bufs[3].numel() != 5 or bufs[5].shape != out.step_probs.shape:
+            raise ValueError("a2c_loss(entropy_coef > 0): buffers from new_loss_bufs(out, True) needed")
+        gp, gl, gv, sc, st, gpr = bufs
+        check(self.lib.marl_a2c_loss_entropy_fwd_bwd(
             C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(),
             out.step_log_probas.data_ptr(), out.step_values.data_ptr(), y.data_ptr(),
-            C.c_float(gamma), gp.data_ptr(), gl.data_ptr(), gv.data_ptr(), sc.data_ptr(),
-            st.data_ptr(), phase, _stream(dev)))
+            C.c_float(gamma), _need(out.step_probs, th.float32, "step_probs").data_ptr(),
+            C.c_float(entropy_coef), gp.data_ptr(), gl.data_ptr(), gv.data_ptr(), gpr.data_ptr(),
+            sc.data_ptr(), st.data_ptr(), phase, _stream(dev)))
         return bufs
+
+    def new_loss_bufs(self, out: EpisodeTensors, entropy: bool = False) -> Tuple[th.Tensor, ...]:
+        """The output tensors of ``a2c_loss`` (persistent ones for a trainer / a captured graph)."""
+        dev = self.device
+        bufs = (
+            th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
+            th.empty_like(out.step_values), th.zeros(5 if entropy else 4, device=dev),
+            th.zeros(3, dtype=th.float64, device=dev),
+        )
+        return bufs + (th.empty_like(out.step_probs),) if entropy else bufs
 
     def adam(
         self, params: th.Tensor, grads: th.Tensor, exp_avg: th.Tensor, exp_avg_sq: th.Tensor,

@@ -106,9 +106,14 @@ class FusedA2C:
 
     def __init__(self, engine: HipEngine, flat: FlatParams, lr: float, gamma: float,
                  allreduce: Optional[Callable[[th.Tensor], float]] = None,
-                 use_graph: bool = False) -> None:
+                 use_graph: bool = False, entropy_coef: float = 0.0) -> None:
         if use_graph and allreduce is not None:
             raise ValueError("hipGraph replay covers the single-GPU iteration (no collective inside)")
+        if not entropy_coef >= 0.0:
+            raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
+        # beta of the entropy bonus (loss - beta * mean_{a,b} sum_t H); 0: the plain entries, verbatim.  May be
+        # changed between iterations (a captured graph is keyed by it)
+        self.entropy_coef = float(entropy_coef)
         self._graph = None  # (key, exec handle, stream, persistent tensors)
         self.engine = engine
         self.flat = flat
@@ -125,12 +130,12 @@ class FusedA2C:
         self._packed_gen = self.engine.weights_generation
 
     def rollout(self, img: th.Tensor, draws: EpisodeDraws, train: bool,
-                forced_actions: Optional[th.Tensor] = None) -> EpisodeTensors:
+                forced_actions: Optional[th.Tensor] = None, probs: bool = False) -> EpisodeTensors:
         if self._packed_gen != self.engine.weights_token():  # never packed, or the workspace was re-laid-out
             self.pack()
         return self.engine.episode_forward(img, draws.pos0, draws.h0, draws.c0, draws.hc0,
                                            draws.cc0, draws.noise, forced_actions, train,
-                                           rng=draws.rng)
+                                           rng=draws.rng, probs=probs)
 
     def iteration_graph(self, img: th.Tensor, y: th.Tensor, seed: int,
                         offset: int) -> Tuple[EpisodeTensors, th.Tensor]:
@@ -146,7 +151,8 @@ class FusedA2C:
 
         # (the tune epoch: after engine.tune() the workspaces baked into a captured graph are freed /
         # re-laid-out - the graph must be captured again)
-        key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch)
+        beta = self.entropy_coef
+        key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch, beta)
         if self._graph is None or self._graph[0] != key:
             if self._graph is not None:
                 eng.lib.marl_graph_destroy(self._graph[1])
@@ -155,7 +161,7 @@ class FusedA2C:
             eager = self.iteration(img, y, draw_episode_device(eng, seed, offset))
             offset += 1  # ... and the graph captured below starts at the NEXT iteration
             stream = th.cuda.Stream(device=eng.device)
-            out = eng.new_outputs()
+            out = eng.new_outputs(beta > 0)
             draws = eng.draw_episode(seed, 0)  # persistent draw tensors
             cnt = eng.new_counters()
             gviews = self._gviews
@@ -168,8 +174,9 @@ class FusedA2C:
                     eng.draw_episode(seed, 0, into=draws, counters=cnt)
                     eng.episode_forward(img, draws[0], draws[1], draws[2], draws[3], draws[4], None,
                                         None, True, rng=(seed, 0), out=out, counters=cnt)
-                    gp, gl, gv, scalars, _ = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs)
-                    eng.episode_backward(gp, gl, gv, gviews)
+                    bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
+                    gp, gl, gv, scalars = bufs[:4]
+                    eng.episode_backward(gp, gl, gv, gviews, g_probs=bufs[5] if beta > 0 else None)
                     eng.adam(self.flat.params, self.flat.grads, self.flat.exp_avg,
                              self.flat.exp_avg_sq, 1, self.lr, counters=cnt)
                     eng.pack(self._pviews)
@@ -206,22 +213,22 @@ class FusedA2C:
         return out, scalars
 
     def iteration(self, img: th.Tensor, y: th.Tensor, draws: EpisodeDraws) -> Tuple[EpisodeTensors, th.Tensor]:
-        """Returns the episode outputs and the device tensor {loss, path, error, critic}."""
+        """Returns the episode outputs and the device tensor {loss, path, error, critic} (with an entropy
+        bonus: the loss includes it and a fifth scalar holds the mean entropy)."""
         eng = self.engine
-        out = self.rollout(img, draws, True)
-        if self._loss_bufs is None or self._loss_bufs[0].shape != out.step_preds.shape:
-            dev = eng.device
-            self._loss_bufs = (
-                th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
-                th.empty_like(out.step_values), th.zeros(4, device=dev),
-                th.zeros(3, dtype=th.float64, device=dev),
-            )
-        gp, gl, gv, scalars, _ = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs)
+        beta = self.entropy_coef
+        out = self.rollout(img, draws, True, probs=beta > 0)
+        if (self._loss_bufs is None or self._loss_bufs[0].shape != out.step_preds.shape or
+                len(self._loss_bufs) != (6 if beta > 0 else 5)):
+            self._loss_bufs = eng.new_loss_bufs(out, beta > 0)
+        bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
+        gp, gl, gv, scalars = bufs[:4]
+        gpr = bufs[5] if beta > 0 else None
         bucketed = hasattr(self.allreduce, "before_backward")
         if bucketed:  # (two buckets: the heads' slice leaves while the reverse loop still runs)
             self.allreduce.before_backward(eng)
         try:
-            eng.episode_backward(gp, gl, gv, self._gviews)
+            eng.episode_backward(gp, gl, gv, self._gviews, g_probs=gpr)
         finally:
             if bucketed:
                 self.allreduce.after_backward(eng)

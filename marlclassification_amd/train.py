@@ -195,7 +195,8 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
                       allreduce=(BucketedGradAllReduce(world, None, nn_models.flat_state().offsets, nn_models.flat_state().numel,
                                                       device) if distributed else None),
                       exact_standardize_group=(dist.group.WORLD if distributed and world > 1 and
-                                               exact_standardize else None))
+                                               exact_standardize else None),
+                      entropy_coef=train_config.entropy_coef)
     for e in range(train_config.nb_epoch):
         for bs in samplers:
             bs.set_epoch(e)

@@ -31,7 +31,10 @@ class Trainer:
         meter_window_size: int = 64,
         allreduce: Optional[Callable[[th.Tensor], float]] = None,
         exact_standardize_group=None,
+        entropy_coef: float = 0.0,
     ) -> None:
+        if not entropy_coef >= 0.0:
+            raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
         self.__model = model
         self.__nb_class = nb_class
         self.__lr = learning_rate
@@ -40,11 +43,14 @@ class Trainer:
         self.__log_interval = log_interval
         self.__allreduce = allreduce
         self.__exact_group = exact_standardize_group
+        # beta of the entropy bonus (loss - beta * mean_{a,b} sum_t H): 0 = the reference's loss through the plain
+        # entries; > 0 = marl_episode_forward_probs / marl_a2c_loss_entropy_fwd_bwd / marl_episode_backward_probs
+        self.__entropy_coef = float(entropy_coef)
         self.__curr_step = 0
         self.__loss_bufs: Optional[Tuple[th.Tensor, ...]] = None
         self.__conf_meter = ConfusionMeter(nb_class, window_size=meter_window_size)
-        self.__meters = {k: LossMeter(window_size=meter_window_size)
-                         for k in ("loss", "path", "error", "critic")}
+        self.__meter_keys = ("loss", "path", "error", "critic") + (("entropy",) if entropy_coef > 0 else ())
+        self.__meters = {k: LossMeter(window_size=meter_window_size) for k in self.__meter_keys}
 
     @property
     def curr_step(self) -> int:
@@ -55,6 +61,8 @@ class Trainer:
         model = self.__model
         device = model.device
         y = y.to(device)
+        if self.__entropy_coef > 0:
+            return self.__train_step_entropy(x, y, sampler)
         eng, out = sampler.run_episode_raw(x, train=True)
         if self.__loss_bufs is None or self.__loss_bufs[0].shape != out.step_preds.shape:
             self.__loss_bufs = (
@@ -86,13 +94,46 @@ class Trainer:
         model.mark_updated(eng)
         return out, scalars
 
+    def __train_step_entropy(self, x: th.Tensor, y: th.Tensor,
+                             sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
+        """train_step with the entropy bonus: the same sequence through the three entries that carry the step
+        distributions (scalars[4] = the mean entropy)."""
+        model, beta, gamma = self.__model, self.__entropy_coef, self.__gamma
+        eng, out = sampler.run_episode_raw(x, train=True, probs=True)
+        if (self.__loss_bufs is None or len(self.__loss_bufs) != 6 or
+                self.__loss_bufs[5].shape != out.step_probs.shape or self.__loss_bufs[0].shape != out.step_preds.shape):
+            self.__loss_bufs = eng.new_loss_bufs(out, True)
+        if self.__exact_group is None:
+            gp, gl, gv, scalars, _, gpr = eng.a2c_loss(out, y, gamma, 0, self.__loss_bufs, entropy_coef=beta)
+        else:  # (phase 1 leaves the entropy alone: only the advantages have a batch-wide statistic)
+            from ..parallel import allreduce_adv_stats
+
+            stats = eng.a2c_loss(out, y, gamma, 1, self.__loss_bufs, entropy_coef=beta)[4]
+            allreduce_adv_stats(stats, self.__exact_group)
+            gp, gl, gv, scalars, _, gpr = eng.a2c_loss(out, y, gamma, 2, self.__loss_bufs, entropy_coef=beta)
+        flat = model.flat_state()
+        bucketed = hasattr(self.__allreduce, "before_backward")
+        if bucketed:
+            self.__allreduce.before_backward(eng)
+        try:
+            eng.episode_backward(gp, gl, gv, flat.grad_views(), g_probs=gpr)
+        finally:
+            if bucketed:
+                self.__allreduce.after_backward(eng)
+        scale = 1.0 if self.__allreduce is None else self.__allreduce(flat.grads)
+        flat.step += 1
+        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, self.__lr,
+                 grad_scale=scale)
+        model.mark_updated(eng)
+        return out, scalars
+
     def train_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler) -> None:
         self.__model.train()
         for x_train, y_train in dataloader:
             out, scalars = self.train_step(x_train, y_train, episode_sampler)
             # device-side meters, no sync (select last step, mean over agents: trainer.py:124-128)
             self.__conf_meter.add(out.step_preds[-1].mean(dim=0), y_train)
-            for i, k in enumerate(("loss", "path", "error", "critic")):
+            for i, k in enumerate(self.__meter_keys):
                 self.__meters[k].add(scalars[i].clone())
             if self.__metric_logger is not None and self.__curr_step % self.__log_interval == 0:
                 self.__metric_logger(self.__curr_step, self.metrics())
@@ -100,7 +141,7 @@ class Trainer:
 
     def metrics(self) -> Dict[str, float]:
         """Synchronises: windowed means of the loss terms + train precision / recall."""
-        return {
+        m = {
             "error": self.__meters["error"].loss(),
             "path_loss": self.__meters["path"].loss(),
             "loss": self.__meters["loss"].loss(),
@@ -108,6 +149,9 @@ class Trainer:
             "train_prec": self.__conf_meter.precision().mean().item(),
             "train_rec": self.__conf_meter.recall().mean().item(),
         }
+        if "entropy" in self.__meters:  # (only with an entropy bonus: the plain trainer never sees the distributions)
+            m["entropy"] = self.__meters["entropy"].loss()
+        return m
 
     def eval_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler) -> ConfusionMeter:
         self.__model.eval()
