@@ -279,6 +279,57 @@ int marl_a2c_loss_entropy_fwd_bwd(const marl_config* cfg, void* episode_ws, size
                                   float* g_preds, float* g_logp, float* g_values, float* g_probs,
                                   float* scalars_out, double* adv_stats, int phase, void* stream);
 
+/* PPO on the fused path (same ABI version: three added entries, nothing else moves).  The reference trains with one
+ * on-policy A2C step per rollout (training/trainer.py:66-116) and has no counterpart for any of them; each names the
+ * existing piece it extends.
+ *
+ * marl_advantages extends the advantage of the loss above (training/trainer.py:89-92: discounted returns - values,
+ * then training/functions.py:54-55) to GAE(lambda), as a call of its own whose results the caller keeps for several
+ * update epochs: rewards = classification_rewards (functions.py:7-32); delta_t = r_t + gamma V_{t+1} - V_t with
+ * V_Ns = 0 (the reference's returns have no bootstrap); A_t = delta_t + gamma lam A_{t+1}; ret_t = A_t + V_t (the
+ * critic target); advn = (A - mean) / (unbiased std + 1e-8) over all Ns * R entries.  0 <= lam <= 1; lam == 1 takes
+ * the arithmetic of discounted_returns (functions.py:35-51, flip-cumsum order): advn / ret then hold, bit for bit,
+ * what marl_a2c_loss_fwd_bwd uses internally.  advn, ret: caller-owned [Ns,R].  adv_stats[3] / phase as above:
+ * 0 = everything, 1 = up to the local (n, sum A, sum A^2), 2 = standardise with the (all-reduced) adv_stats.
+ * episode_ws: the TRAINING layout (scratch = its loss tail). */
+int marl_advantages(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
+                    const float* step_preds, const float* step_values, const int64_t* y,
+                    float gamma, float lam, float* advn, float* ret, double* adv_stats, int phase,
+                    void* stream);
+
+/* The clipped-surrogate loss in place of the path term of marl_a2c_loss_fwd_bwd (training/trainer.py:96-111), and its
+ * gradient w.r.t. the episode outputs:
+ *   rho = exp(step_logp - old_logp);  surr = -min(rho advn, clamp(rho, 1 - clip_eps, 1 + clip_eps) advn)
+ *   loss = mean_{a,b} sum_t [surr + smooth_l1(step_values, ret)] + vote cross-entropy (trainer.py:78-87, unchanged)
+ *          - entropy_coef * mean_{a,b} sum_t H(step_probs)        (only with step_probs, as in the entropy entry)
+ * old_logp, advn, ret [Ns,R]: the rollout's log-probabilities and the outputs of marl_advantages; clip_eps > 0.
+ * g_logp = -advn rho / R where the unclipped term is active, 0 where the clip is (advn > 0 and rho > 1 + clip_eps,
+ * or advn < 0 and rho < 1 - clip_eps); g_preds, g_values as in marl_a2c_loss_fwd_bwd; g_probs as in
+ * marl_a2c_loss_entropy_fwd_bwd.  step_probs and g_probs: both NULL (entropy_coef ignored) or both given.
+ * With old_logp == step_logp bit for bit and advn / ret from marl_advantages(lam = 1), g_preds, g_logp and g_values
+ * are bit-equal to marl_a2c_loss_fwd_bwd's.
+ * scalars_out[7] = {loss, surr.sum(0).mean(), error.mean(), critic.sum(0).mean(), mean_{t,a,b} H (0 without
+ * step_probs), approx_kl = mean(old_logp - step_logp), clip_frac = share of (t, r) where the clip is active}.
+ * Three launches, fixed-order fp64 partial sums (bit-reproducible), scratch = the loss tail of episode_ws. */
+int marl_ppo_loss_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
+                          const float* step_preds, const float* step_logp, const float* step_values,
+                          const int64_t* y, const float* old_logp, const float* advn, const float* ret,
+                          float clip_eps, const float* step_probs, float entropy_coef,
+                          float* g_preds, float* g_logp, float* g_values, float* g_probs,
+                          float* scalars_out, void* stream);
+
+/* th.nn.utils.clip_grad_norm_ (no call in the reference's trainer; it goes between loss.backward() and
+ * optimizer.step(), training/trainer.py:115-116) on the flat gradient buffer marl_adam_step reads:
+ * norm = sqrt(sum g^2) from fixed-order fp64 partials; g *= min(1, max_norm / (norm + 1e-6)) in place (a factor of
+ * exactly 1 leaves every bit); *norm_out (device) = norm.  grad_scale (> 0; 1 / world_size after an all-reduce sum,
+ * else 1) is applied FIRST - norm is that of grad_scale * g and the buffer ends up scaled by it too, so
+ * marl_adam_step then takes grad_scale = 1 and every rank clips the same averaged gradient.  Two launches, no host
+ * synchronisation.  scratch: caller-owned, >= MARL_GRAD_CLIP_SCRATCH_BYTES, 8-byte aligned; max_norm > 0; n >= 0. */
+#define MARL_GRAD_CLIP_BLOCKS 1024
+#define MARL_GRAD_CLIP_SCRATCH_BYTES (MARL_GRAD_CLIP_BLOCKS * 8)
+int marl_grad_clip(float* grads, int64_t n, float max_norm, float grad_scale, float* norm_out,
+                   void* scratch, size_t scratch_bytes, void* stream);
+
 /* th.optim.Adam.step (training/trainer.py:33,116) on one flat buffer:
  * betas (0.9, 0.999), eps 1e-8, no weight decay; `step` is 1-based. grad_scale
  * multiplies the gradient first (1/world_size after an all-reduce sum).  counters != NULL:

@@ -73,6 +73,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="multi-GPU: global advantage statistics (update == single-GPU big batch)")
     t.add_argument("--entropy-coef", type=float, default=0.0, dest="entropy_coef",
                    help="entropy bonus: loss - X * mean_{agents,batch} sum_t H(policy_t) (0: the reference's loss)")
+    t.add_argument("--ppo-epochs", type=int, default=1, dest="ppo_epochs",
+                   help="policy updates per rollout: epochs after the first replay the stored trajectory under the "
+                        "new weights on the clipped surrogate (1 with the other PPO flags at their defaults: plain A2C)")
+    t.add_argument("--ppo-clip", type=float, default=0.2, dest="ppo_clip",
+                   help="clip range of the probability ratio: clamp(ratio, 1 - X, 1 + X)")
+    t.add_argument("--gae-lambda", type=float, default=1.0, dest="gae_lambda",
+                   help="lambda of the generalised advantage estimate (1: the reference's full returns - values)")
+    t.add_argument("--max-grad-norm", type=float, default=None, dest="max_grad_norm",
+                   help="clip the global gradient norm to X before every Adam step (default: no clipping)")
     return p
 
 
@@ -92,7 +101,8 @@ def main(argv=None) -> None:
         train_config = TrainConfig(
             img_size=args.img_size, nb_epoch=args.nb_epoch, learning_rate=args.learning_rate,
             batch_size=args.batch_size, resources_dir=args.res_folder, output_dir=args.output_dir,
-            gamma=args.gamma, entropy_coef=args.entropy_coef,
+            gamma=args.gamma, entropy_coef=args.entropy_coef, ppo_epochs=args.ppo_epochs,
+            ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, max_grad_norm=args.max_grad_norm,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":

@@ -15,6 +15,7 @@ MARL_MAX_CNN_LAYERS = 5
 MARL_MAX_ACTIONS = 16
 MARL_ABI_VERSION = 5
 MARL_COUNTERS_BYTES = 32
+MARL_GRAD_CLIP_SCRATCH_BYTES = 1024 * 8
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MARL_LIB_PATH: another build of the SAME library (tools/build_variant.sh: timing / ablation builds, the previous
@@ -76,7 +77,8 @@ EXPORTS = (
     "marl_lstm_images marl_gemm_tn_images marl_gemm_tn_images_scratch marl_plan_query "
     "marl_gemm_tn_images_cell marl_gemm_tn_images_cell_scratch marl_backward_heads_event "
     "marl_step_forward_train marl_step_backward marl_episode_backward_img "
-    "marl_episode_forward_probs marl_episode_backward_probs marl_a2c_loss_entropy_fwd_bwd"
+    "marl_episode_forward_probs marl_episode_backward_probs marl_a2c_loss_entropy_fwd_bwd "
+    "marl_advantages marl_ppo_loss_fwd_bwd marl_grad_clip"
 ).split()
 
 _lib: Optional[C.CDLL] = None
@@ -117,6 +119,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_a2c_loss_fwd_bwd.argtypes = (
         [_cfgp, _vp, _sz, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]
     )
+    lib.marl_advantages.argtypes = [_cfgp, _vp, _sz, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _vp]
+    lib.marl_ppo_loss_fwd_bwd.argtypes = ([_cfgp, _vp, _sz] + [_vp] * 7 + [_f, _vp, _f] + [_vp] * 6)
+    lib.marl_grad_clip.argtypes = [_vp, _i64, _f, _f, _vp, _vp, _sz, _vp]
     lib.marl_adam_step.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _f, _f, _f, _f, _f, _vp, _vp]
     lib.marl_step_forward.argtypes = ([_cfgp, _vp, _sz, _vp, _sz] + [_vp] * 15 + [_vp, _u64, _u64, _vp, _vp] +
                                       [_vp])

@@ -4,7 +4,7 @@ side loads on the other.  ``build_marl`` is the constructor path for the hot-pat
 
 import json
 from os.path import exists, isfile
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 from pydantic import BaseModel
 
@@ -81,6 +81,12 @@ class TrainConfig(BaseModel):
     gamma: float
     # beta of the entropy bonus: loss - beta * mean_{a,b} sum_t H(pi_t) (0: the reference's plain A2C loss)
     entropy_coef: float = 0.0
+    # PPO on the fused path (all four at their defaults: the reference's one A2C step per rollout): update epochs per
+    # rollout, the clip range of the probability ratio, lambda of GAE, and the global gradient-norm bound (None: off)
+    ppo_epochs: int = 1
+    ppo_clip: float = 0.2
+    gae_lambda: float = 1.0
+    max_grad_norm: Optional[float] = None
 
 
 class EvalConfig(BaseModel):

@@ -216,13 +216,21 @@ class EpisodeSampler:
 
     def run_episode_raw(self, img_batch: th.Tensor, train: bool,
                         draws: Optional[EpisodeDraws] = None,
-                        probs: bool = False) -> Tuple[HipEngine, EpisodeTensors]:
+                        probs: bool = False,
+                        forced: Optional[th.Tensor] = None) -> Tuple[HipEngine, EpisodeTensors]:
         """No autograd node: used by the fused Trainer (loss + backward are HIP calls).  An image that
-        requires grad is ignored here - the gradient w.r.t. the image exists on the ``run_episode`` path."""
-        eng, img, d = self.prepare(img_batch)
-        if draws is not None:
-            d = draws
-        out = eng.episode_forward(img, d.pos0, d.h0, d.c0, d.hc0, d.cc0, d.noise, None, train,
+        requires grad is ignored here - the gradient w.r.t. the image exists on the ``run_episode`` path.
+        ``draws``: these instead of new ones - nothing is drawn, the sampler's episode counter stays (a replay
+        leaves the generator sequence of later rollouts where it was).  ``forced`` (int64 [Ns,Na,Nb]): these actions
+        replace the sampling (``draws`` + ``forced`` = the stored trajectory under the current weights)."""
+        if forced is not None:
+            if draws is None:
+                raise ValueError("replay: forced actions need the draws of the episode they were sampled in")
+            self.__check_replay(img_batch, Trajectory(draws, forced))  # (before anything is transferred or enqueued)
+        eng, img, d = self.prepare(img_batch, draws)
+        if forced is not None:
+            forced = forced.to(img.device)
+        out = eng.episode_forward(img, d.pos0, d.h0, d.c0, d.hc0, d.cc0, d.noise, forced, train,
                                   rng=d.rng, probs=probs)
         self.__env._set_positions(out.step_pos[-1])
         return eng, out

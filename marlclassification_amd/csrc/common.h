@@ -936,4 +936,47 @@ struct LossArgs {
 size_t loss_scratch_floats(int ns, int na, int nb);
 int launch_loss(const LossArgs& a, hipStream_t st);
 
+// marl_advantages: rewards -> GAE(lambda) -> standardise, into caller-owned advn / ret
+struct AdvArgs {
+    const float* preds;   // [Ns, Na, Nb, nC]
+    const float* values;  // [Ns, Na, Nb]
+    const int64_t* y;     // [Nb]
+    float* advn;          // [Ns*R] standardised advantage
+    float* ret;           // [Ns*R] critic target
+    double* adv_stats;    // [3]
+    float* scratch;       // the loss scratch (rewards, raw advantages, partials)
+    int ns, na, nb, nc;
+    float gamma, lam;
+    int phase;
+};
+int launch_advantages(const AdvArgs& a, hipStream_t st);
+
+// marl_ppo_loss_fwd_bwd: clipped surrogate + critic + vote error (- entropy bonus when probs != nullptr)
+struct PpoArgs {
+    const float* preds;
+    const float* logp;
+    const float* values;
+    const int64_t* y;
+    const float* old_logp;  // [Ns*R]
+    const float* advn;      // [Ns*R]
+    const float* ret;       // [Ns*R]
+    float clip_eps;
+    float* g_preds;
+    int ld_gp;
+    float* g_logp;
+    float* g_values;
+    float* scalars;  // [7]
+    float* scratch;
+    int ns, na, nb, nc;
+    const float* probs = nullptr;
+    float* g_probs = nullptr;
+    int n_act = 0;
+    float entropy_coef = 0.f;
+};
+int launch_ppo_loss(const PpoArgs& a, hipStream_t st);
+
+// marl_grad_clip; part: MARL_GRAD_CLIP_BLOCKS doubles
+int launch_grad_clip(float* g, int64_t n, float max_norm, float grad_scale, float* norm_out, double* part,
+                     hipStream_t st);
+
 }  // namespace marl

@@ -2422,6 +2422,102 @@ int marl_a2c_loss_entropy_fwd_bwd(const marl_config* cfg, void* episode_ws, size
     return launch_loss(a, static_cast<hipStream_t>(stream));
 }
 
+// the loss scratch (tail of the training layout) for the PPO entries; MARL_ESIZE when the workspace is too small
+static int loss_scratch_of(const Dims& d, void* episode_ws, size_t episode_ws_bytes, const char* who,
+                           float** scratch) {
+    ELayout e;
+    make_elayout(d, 1, e);
+    if (episode_ws_bytes < e.total * sizeof(float)) {
+        set_error("%s: episode workspace too small (%zu of %zu bytes, training layout)", who, episode_ws_bytes,
+                  e.total * sizeof(float));
+        return MARL_ESIZE;
+    }
+    *scratch = static_cast<float*>(episode_ws) + e.LOSS;
+    return MARL_OK;
+}
+
+int marl_advantages(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes, const float* step_preds,
+                    const float* step_values, const int64_t* y, float gamma, float lam, float* advn, float* ret,
+                    double* adv_stats, int phase, void* stream) {
+    Dims d;
+    MARL_TRY(make_dims(cfg, d));
+    if (!episode_ws || !step_preds || !step_values || !y || !advn || !ret || !adv_stats || phase < 0 ||
+        phase > 2 || !(lam >= 0.f && lam <= 1.f)) {
+        set_error("advantages: bad argument");
+        return MARL_EINVAL;
+    }
+    AdvArgs a;
+    MARL_TRY(loss_scratch_of(d, episode_ws, episode_ws_bytes, "advantages", &a.scratch));
+    a.preds = step_preds;
+    a.values = step_values;
+    a.y = y;
+    a.advn = advn;
+    a.ret = ret;
+    a.adv_stats = adv_stats;
+    a.ns = d.ns;
+    a.na = d.na;
+    a.nb = d.nb;
+    a.nc = d.nC;
+    a.gamma = gamma;
+    a.lam = lam;
+    a.phase = phase;
+    return launch_advantages(a, static_cast<hipStream_t>(stream));
+}
+
+int marl_ppo_loss_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
+                          const float* step_preds, const float* step_logp, const float* step_values,
+                          const int64_t* y, const float* old_logp, const float* advn, const float* ret,
+                          float clip_eps, const float* step_probs, float entropy_coef, float* g_preds, float* g_logp,
+                          float* g_values, float* g_probs, float* scalars_out, void* stream) {
+    Dims d;
+    MARL_TRY(make_dims(cfg, d));
+    if (!episode_ws || !step_preds || !step_logp || !step_values || !y || !old_logp || !advn || !ret ||
+        !scalars_out || !(clip_eps > 0.f) || (step_probs == nullptr) != (g_probs == nullptr) ||
+        (step_probs && !(entropy_coef >= 0.f))) {
+        set_error("ppo_loss: bad argument");
+        return MARL_EINVAL;
+    }
+    PpoArgs a;
+    MARL_TRY(loss_scratch_of(d, episode_ws, episode_ws_bytes, "ppo_loss", &a.scratch));
+    a.preds = step_preds;
+    a.logp = step_logp;
+    a.values = step_values;
+    a.y = y;
+    a.old_logp = old_logp;
+    a.advn = advn;
+    a.ret = ret;
+    a.clip_eps = clip_eps;
+    a.g_preds = g_preds;
+    a.ld_gp = d.nC;
+    a.g_logp = g_logp;
+    a.g_values = g_values;
+    a.scalars = scalars_out;
+    a.ns = d.ns;
+    a.na = d.na;
+    a.nb = d.nb;
+    a.nc = d.nC;
+    a.probs = step_probs;
+    a.g_probs = g_probs;
+    a.n_act = d.nA;
+    a.entropy_coef = entropy_coef;
+    return launch_ppo_loss(a, static_cast<hipStream_t>(stream));
+}
+
+int marl_grad_clip(float* grads, int64_t n, float max_norm, float grad_scale, float* norm_out, void* scratch,
+                   size_t scratch_bytes, void* stream) {
+    if (!grads || n < 0 || !(max_norm > 0.f) || !(grad_scale > 0.f) || !norm_out || !scratch ||
+        (reinterpret_cast<uintptr_t>(scratch) & 7) != 0) {
+        set_error("grad_clip: bad argument");
+        return MARL_EINVAL;
+    }
+    if (scratch_bytes < MARL_GRAD_CLIP_SCRATCH_BYTES) {
+        set_error("grad_clip: scratch too small (%zu of %d bytes)", scratch_bytes, MARL_GRAD_CLIP_SCRATCH_BYTES);
+        return MARL_ESIZE;
+    }
+    return launch_grad_clip(grads, n, max_norm, grad_scale, norm_out, static_cast<double*>(scratch),
+                            static_cast<hipStream_t>(stream));
+}
+
 int marl_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                    int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
                    const void* counters, void* stream) {

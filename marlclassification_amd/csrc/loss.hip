@@ -355,4 +355,315 @@ int launch_loss(const LossArgs& a, hipStream_t st) {
     return MARL_OK;
 }
 
+// ---------------------------------------------------------------------------
+// PPO on the fused path (marl_advantages, marl_ppo_loss_fwd_bwd, marl_grad_clip).  Nothing above moves: the A2C
+// entries launch what they launched.  Same conventions: fp64 partials, fixed-order trees, no float atomics.
+// ---------------------------------------------------------------------------
+
+// tree over K per-thread fp64 values; thread 0 ends up with the block sums in sh[k][0]
+template <int K>
+__device__ __forceinline__ void block_tree(double (*sh)[256], const double (&v)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+}
+
+// thread per row r, t from Ns - 1 down: delta_t = r_t + gamma V_{t+1} - V_t (V_Ns = 0: the reference's returns have no
+// bootstrap), A_t = delta_t + gamma lam A_{t+1}, ret_t = A_t + V_t; partials of sum A and sum A^2 as in
+// loss_returns_kernel (which stays the lam == 1 path: its flip-cumsum arithmetic is what the A2C loss standardises)
+__global__ __launch_bounds__(256) void loss_gae_kernel(const float* __restrict__ rew,
+                                                       const float* __restrict__ values,
+                                                       float* __restrict__ ret, float* __restrict__ adv,
+                                                       double* __restrict__ part, int ns, int64_t R,
+                                                       float gamma, float lam) {
+    __shared__ double sh[2][256];
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double s[2] = {0.0, 0.0};
+    if (r < R) {
+        const float gl = gamma * lam;
+        float A = 0.f, vnext = 0.f;
+        for (int t = ns - 1; t >= 0; --t) {
+            const int64_t i = (int64_t)t * R + r;
+            const float v = values[i];
+            const float delta = rew[i] + gamma * vnext - v;
+            A = delta + gl * A;
+            vnext = v;
+            ret[i] = A + v;
+            adv[i] = A;
+            s[0] += (double)A;
+            s[1] += (double)A * (double)A;
+        }
+    }
+    block_tree<2>(sh, s);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = sh[0][0];
+        part[2 * blockIdx.x + 1] = sh[1][0];
+    }
+}
+
+// advn = (adv - mean) / (std + 1e-8): functions.py:54-55, the expression of loss_grads_kernel
+__global__ __launch_bounds__(256) void loss_standardize_kernel(const float* __restrict__ adv,
+                                                               const double* __restrict__ adv_stats,
+                                                               float* __restrict__ advn, int64_t NR) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= NR) return;
+    const double n = adv_stats[0];
+    const double mean_d = adv_stats[1] / n;
+    const double var_d = (adv_stats[2] - adv_stats[1] * mean_d) / (n - 1.0);
+    const float mean = (float)mean_d;
+    const float sd = (float)sqrt(var_d > 0.0 ? var_d : 0.0);
+    advn[i] = (adv[i] - mean) / (sd + 1e-8f);
+}
+
+int launch_advantages(const AdvArgs& a, hipStream_t st) {
+    const int64_t R = (int64_t)a.na * a.nb, NR = R * a.ns;
+    LossLayout L = loss_layout(a.scratch, a.ns, a.na, a.nb);
+    double* stats = reinterpret_cast<double*>(a.adv_stats);
+    if (a.phase == 0 || a.phase == 1) {
+        const float rnd = (float)log((double)a.nc);
+        hipLaunchKernelGGL(loss_rewards_kernel, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st, a.preds, a.y, L.rew,
+                           NR, a.nb, a.nc, rnd);
+        MARL_LAUNCH_CHECK();
+        if (a.lam == 1.0f)
+            hipLaunchKernelGGL(loss_returns_kernel, dim3((unsigned)L.blocksC), dim3(256), 0, st, L.rew, a.values,
+                               a.ret, L.adv, L.part_adv, a.ns, R, a.gamma);
+        else
+            hipLaunchKernelGGL(loss_gae_kernel, dim3((unsigned)L.blocksC), dim3(256), 0, st, L.rew, a.values, a.ret,
+                               L.adv, L.part_adv, a.ns, R, a.gamma, a.lam);
+        MARL_LAUNCH_CHECK();
+        // (no vote error here: nerr = 0, the slot behind the loss partials receives a zero nobody reads)
+        hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(256), 0, st, L.part_adv, L.blocksC, L.err, (int64_t)0,
+                           L.part_err, stats, (double)NR);
+        MARL_LAUNCH_CHECK();
+    }
+    if (a.phase == 0 || a.phase == 2) {
+        hipLaunchKernelGGL(loss_standardize_kernel, dim3((unsigned)L.blocksE), dim3(256), 0, st, L.adv, stats,
+                           a.advn, NR);
+        MARL_LAUNCH_CHECK();
+    }
+    return MARL_OK;
+}
+
+// one thread per (t, r): rho = exp(logp - old_logp); surrogate -min(rho A, clamp(rho, 1 - eps, 1 + eps) A) and
+// g_logp = -A rho / R where the unclipped term is the active one, 0 where the clip is (A > 0 and rho > 1 + eps, or
+// A < 0 and rho < 1 - eps).  With old_logp == logp bit for bit rho is exactly 1 and (-A * rho) * (1 / R) is
+// loss_grads_kernel's -advn * invR, bit for bit; the critic term and g_values ARE that kernel's expressions.
+// part[2 i] / [2 i + 1] = surrogate / critic, extra[3 i ..] = entropy / old_logp - logp / clipped count.
+// ENT / VEC: as in loss_grads_kernel.
+template <bool ENT, bool VEC>
+__global__ __launch_bounds__(256) void ppo_grads_kernel(
+    const float* __restrict__ logp, const float* __restrict__ old_logp, const float* __restrict__ values,
+    const float* __restrict__ ret, const float* __restrict__ advn_in, float clip_eps, float* __restrict__ g_logp,
+    float* __restrict__ g_values, double* __restrict__ part, double* __restrict__ extra, int64_t NR, int64_t R,
+    const float* __restrict__ probs, float* __restrict__ g_probs, int nA, float beta) {
+    __shared__ double sh[5][256];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (i < NR) {
+        const float advn = advn_in[i];
+        const float invR = 1.0f / (float)R;
+        const float lp = logp[i], olp = old_logp[i];
+        const float rho = expf(lp - olp);
+        const float lo = 1.0f - clip_eps, hi = 1.0f + clip_eps;
+        const bool clipped = (advn > 0.f && rho > hi) || (advn < 0.f && rho < lo);
+        const float rc = fminf(fmaxf(rho, lo), hi);
+        s[0] = (double)(-(clipped ? rc : rho) * advn);
+        const float d = values[i] - ret[i];
+        const float ad = fabsf(d);
+        s[1] = (double)(ad < 1.0f ? 0.5f * d * d : ad - 0.5f);
+        s[3] = (double)(olp - lp);
+        s[4] = clipped ? 1.0 : 0.0;
+        if (g_logp) g_logp[i] = clipped ? 0.f : (-advn * rho) * invR;
+        if (g_values) g_values[i] = (ad < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f)) * invR;
+        if (ENT) {
+            const float scale = beta * invR;
+            float h = 0.f;
+            auto term = [&](float p) {  // adds p log p to h, returns the gradient
+                if (!(p > 0.f)) return 0.f;
+                const float l = logf(p);
+                h = fmaf(p, l, h);
+                return scale * (l + 1.0f);
+            };
+            if (VEC) {
+                const float4* pv = reinterpret_cast<const float4*>(probs + i * nA);
+                float4* gv = reinterpret_cast<float4*>(g_probs + i * nA);
+                for (int k = 0; k < nA / 4; ++k) {
+                    const float4 p = pv[k];
+                    float4 g;
+                    g.x = term(p.x);
+                    g.y = term(p.y);
+                    g.z = term(p.z);
+                    g.w = term(p.w);
+                    gv[k] = g;
+                }
+            } else {
+                for (int j = 0; j < nA; ++j) g_probs[i * nA + j] = term(probs[i * nA + j]);
+            }
+            s[2] = (double)(-h);
+        }
+    }
+    block_tree<5>(sh, s);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = sh[0][0];
+        part[2 * blockIdx.x + 1] = sh[1][0];
+        extra[3 * blockIdx.x] = sh[2][0];
+        extra[3 * blockIdx.x + 1] = sh[3][0];
+        extra[3 * blockIdx.x + 2] = sh[4][0];
+    }
+}
+
+// scalars = {loss, surrogate.sum(0).mean(), error.mean(), critic.sum(0).mean(), mean entropy (0 without a bonus),
+// approx_kl = mean(old_logp - logp), clip_frac}; the vote error [nerr] is summed here (strided, then the tree)
+__global__ __launch_bounds__(256) void ppo_final_kernel(const double* __restrict__ part,
+                                                        const double* __restrict__ extra, int nblocks,
+                                                        const float* __restrict__ err, int64_t nerr,
+                                                        float* __restrict__ scalars, int ns, int nb, int64_t R,
+                                                        float beta) {
+    __shared__ double sh[6][256];
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < nblocks; i += 256) {
+        s[0] += part[2 * i];
+        s[1] += part[2 * i + 1];
+        s[2] += extra[3 * i];
+        s[3] += extra[3 * i + 1];
+        s[4] += extra[3 * i + 2];
+    }
+    for (int64_t i = threadIdx.x; i < nerr; i += 256) s[5] += (double)err[i];
+    block_tree<6>(sh, s);
+    if (threadIdx.x == 0) {
+        const double NR = (double)R * ns;
+        const double surr = sh[0][0] / (double)R, critic = sh[1][0] / (double)R, h = sh[2][0];
+        const double esum = sh[5][0];
+        scalars[0] = (float)(surr + esum / (double)nb + critic - (double)beta * (h / (double)R));
+        scalars[1] = (float)surr;
+        scalars[2] = (float)(esum / ((double)ns * nb));
+        scalars[3] = (float)critic;
+        scalars[4] = (float)(h / NR);
+        scalars[5] = (float)(sh[3][0] / NR);
+        scalars[6] = (float)(sh[4][0] / NR);
+    }
+}
+
+int launch_ppo_loss(const PpoArgs& a, hipStream_t st) {
+    if (a.nc > 1024) {
+        set_error("nb_class %d > 1024 unsupported by the loss kernel", a.nc);
+        return MARL_ELIMIT;
+    }
+    const int64_t R = (int64_t)a.na * a.nb, NR = R * a.ns, nerr = (int64_t)a.ns * a.nb;
+    LossLayout L = loss_layout(a.scratch, a.ns, a.na, a.nb);
+    // three more partials per block than the A2C pass keeps: they take the place of the rewards (dead once
+    // marl_advantages returned; 6 floats per 256 rows); one block (NR <= 256): the 16 spare floats behind `err`
+    double* extra = L.blocksE > 1 ? reinterpret_cast<double*>(L.rew)
+                                  : reinterpret_cast<double*>(
+                                        (reinterpret_cast<uintptr_t>(L.err + nerr) + 7) & ~(uintptr_t)7);
+    hipLaunchKernelGGL(loss_error_kernel, dim3((unsigned)cdiv(nerr, 4)), dim3(256), 0, st, a.preds, a.y, L.err,
+                       a.g_preds, a.ld_gp, a.ns, a.na, a.nb, a.nc);
+    MARL_LAUNCH_CHECK();
+    const dim3 grid((unsigned)L.blocksE), block(256);
+    if (!a.probs) {
+        hipLaunchKernelGGL((ppo_grads_kernel<false, false>), grid, block, 0, st, a.logp, a.old_logp, a.values, a.ret,
+                           a.advn, a.clip_eps, a.g_logp, a.g_values, L.part_loss, extra, NR, R, nullptr, nullptr, 0,
+                           0.f);
+    } else {
+        const bool vec = a.n_act % 4 == 0 && (reinterpret_cast<uintptr_t>(a.probs) & 15) == 0 &&
+                         (reinterpret_cast<uintptr_t>(a.g_probs) & 15) == 0;
+        if (vec)
+            hipLaunchKernelGGL((ppo_grads_kernel<true, true>), grid, block, 0, st, a.logp, a.old_logp, a.values,
+                               a.ret, a.advn, a.clip_eps, a.g_logp, a.g_values, L.part_loss, extra, NR, R, a.probs,
+                               a.g_probs, a.n_act, a.entropy_coef);
+        else
+            hipLaunchKernelGGL((ppo_grads_kernel<true, false>), grid, block, 0, st, a.logp, a.old_logp, a.values,
+                               a.ret, a.advn, a.clip_eps, a.g_logp, a.g_values, L.part_loss, extra, NR, R, a.probs,
+                               a.g_probs, a.n_act, a.entropy_coef);
+    }
+    MARL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ppo_final_kernel, dim3(1), dim3(256), 0, st, L.part_loss, extra, L.blocksE, L.err, nerr,
+                       a.scalars, a.ns, a.nb, R, a.probs ? a.entropy_coef : 0.f);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// global-norm gradient clipping (th.nn.utils.clip_grad_norm_): partial sums of g^2, then finalise + scale
+// ---------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void clip_partials_kernel(const float* __restrict__ g, int64_t n,
+                                                            double* __restrict__ part) {
+    __shared__ double sh[1][256];
+    double s[1] = {0.0};
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        const float4* g4 = reinterpret_cast<const float4*>(g);
+        for (int64_t i = tid; i < n / 4; i += stride) {
+            const float4 v = g4[i];
+            s[0] += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += stride) s[0] += (double)g[i] * g[i];
+    }
+    block_tree<1>(sh, s);
+    if (threadIdx.x == 0) part[blockIdx.x] = sh[0][0];
+}
+
+// every block re-sums the (<= MARL_GRAD_CLIP_BLOCKS) partials in the same order, so all of them scale by the same
+// factor.  grad_scale (1 / world_size after an all-reduce sum) comes first: norm = || grad_scale g ||, and
+// g *= grad_scale * min(1, max_norm / (norm + 1e-6)); a factor of exactly 1 writes nothing: every bit stays
+template <bool VEC>
+__global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ g, int64_t n,
+                                                         const double* __restrict__ part, int nparts,
+                                                         float max_norm, float grad_scale,
+                                                         float* __restrict__ norm_out) {
+    __shared__ double sh[1][256];
+    double s[1] = {0.0};
+    for (int i = threadIdx.x; i < nparts; i += 256) s[0] += part[i];
+    block_tree<1>(sh, s);
+    const double norm = (double)grad_scale * sqrt(sh[0][0]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *norm_out = (float)norm;
+    const double cd = (double)max_norm / (norm + 1e-6);
+    const float coef = (float)((double)grad_scale * (cd < 1.0 ? cd : 1.0));
+    if (coef == 1.0f) return;
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        float4* g4 = reinterpret_cast<float4*>(g);
+        for (int64_t i = tid; i < n / 4; i += stride) {
+            float4 v = g4[i];
+            v.x *= coef;
+            v.y *= coef;
+            v.z *= coef;
+            v.w *= coef;
+            g4[i] = v;
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += stride) g[i] *= coef;
+    }
+}
+
+int launch_grad_clip(float* g, int64_t n, float max_norm, float grad_scale, float* norm_out, double* part,
+                     hipStream_t st) {
+    const bool vec = n % 4 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    int64_t gx = cdiv(vec ? n / 4 : n, 256);
+    if (gx > MARL_GRAD_CLIP_BLOCKS) gx = MARL_GRAD_CLIP_BLOCKS;
+    if (gx < 1) gx = 1;
+    if (vec) {
+        hipLaunchKernelGGL(clip_partials_kernel<true>, dim3((unsigned)gx), dim3(256), 0, st, g, n, part);
+        MARL_LAUNCH_CHECK();
+        hipLaunchKernelGGL(clip_scale_kernel<true>, dim3((unsigned)gx), dim3(256), 0, st, g, n, part, (int)gx,
+                           max_norm, grad_scale, norm_out);
+    } else {
+        hipLaunchKernelGGL(clip_partials_kernel<false>, dim3((unsigned)gx), dim3(256), 0, st, g, n, part);
+        MARL_LAUNCH_CHECK();
+        hipLaunchKernelGGL(clip_scale_kernel<false>, dim3((unsigned)gx), dim3(256), 0, st, g, n, part, (int)gx,
+                           max_norm, grad_scale, norm_out);
+    }
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
 }  // namespace marl

@@ -204,6 +204,7 @@ class HipEngine:
         self._ws_pool: Dict[tuple, list] = {}  # released per-episode training workspaces (autograd path)
         self._fwd_img: Optional[th.Tensor] = None
         self._fwd_key: Optional[Tuple] = None
+        self._clip_scratch: Optional[th.Tensor] = None  # partial sums + the norm of grad_clip
 
     # -- configuration / workspaces -------------------------------------------------
     def configure(self, nb_agents: int, batch: int, nb_steps: int, img_shape: Sequence[int],
@@ -493,6 +494,109 @@ class HipEngine:
             th.zeros(3, dtype=th.float64, device=dev),
         )
         return bufs + (th.empty_like(out.step_probs),) if entropy else bufs
+
+    # -- PPO: GAE(lambda) advantages, clipped surrogate, global-norm clipping ---------------------------------
+    def new_ppo_bufs(self, out: EpisodeTensors, entropy: bool = False) -> Tuple[th.Tensor, ...]:
+        """The tensors ``advantages`` and ``ppo_loss`` write (persistent ones for a trainer):
+        (g_preds, g_logp, g_values, scalars[7], adv_stats[3] float64, advn, ret) + (g_probs,) with ``entropy``."""
+        dev = self.device
+        if entropy and out.step_probs is None:
+            raise ValueError("new_ppo_bufs(entropy=True) needs the episode's step_probs: episode_forward(probs=True)")
+        bufs = (
+            th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
+            th.empty_like(out.step_values), th.zeros(7, device=dev),
+            th.zeros(3, dtype=th.float64, device=dev),
+            th.empty_like(out.step_values), th.empty_like(out.step_values),
+        )
+        return bufs + (th.empty_like(out.step_probs),) if entropy else bufs
+
+    def _check_ppo_bufs(self, out: EpisodeTensors, bufs: Tuple[th.Tensor, ...], what: str) -> None:
+        if (len(bufs) not in (7, 8) or bufs[3].numel() != 7 or bufs[5].shape != out.step_values.shape or
+                bufs[6].shape != out.step_values.shape):
+            raise ValueError(f"{what}: buffers from new_ppo_bufs(out, entropy) needed")
+
+    def advantages(
+        self, out: EpisodeTensors, y: th.Tensor, gamma: float, lam: float, phase: int = 0,
+        bufs: Optional[Tuple[th.Tensor, ...]] = None,
+    ) -> Tuple[th.Tensor, ...]:
+        """marl_advantages: rewards -> GAE(``lam``) -> standardise into ``bufs`` (``new_ppo_bufs``): advn = bufs[5],
+        ret = bufs[6], adv_stats = bufs[4].  ``lam`` = 1: the advantage and critic target of ``a2c_loss``, bit for
+        bit.  Phases as in ``a2c_loss``."""
+        cfg = self.cfg
+        assert cfg is not None
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"gae_lambda must lie in [0, 1], got {lam}")
+        if phase not in (0, 1, 2):
+            raise ValueError(f"phase must be 0, 1 or 2, got {phase}")
+        y = _need(y, th.int64, "y")
+        if bufs is None:
+            bufs = self.new_ppo_bufs(out, out.step_probs is not None)
+        self._check_ppo_bufs(out, bufs, "advantages")
+        ews = self.episode_ws(True)
+        check(self.lib.marl_advantages(
+            C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(), out.step_values.data_ptr(),
+            y.data_ptr(), C.c_float(gamma), C.c_float(lam), bufs[5].data_ptr(), bufs[6].data_ptr(),
+            bufs[4].data_ptr(), phase, _stream(self.device)))
+        return bufs
+
+    def ppo_loss(
+        self, out: EpisodeTensors, y: th.Tensor, old_logp: th.Tensor, advn: th.Tensor, ret: th.Tensor,
+        clip_eps: float, bufs: Optional[Tuple[th.Tensor, ...]] = None, entropy_coef: float = 0.0,
+    ) -> Tuple[th.Tensor, ...]:
+        """marl_ppo_loss_fwd_bwd: the clipped surrogate of ``out`` against ``old_logp`` with the standardised
+        advantage ``advn`` and the critic target ``ret`` (all [Ns,Na,Nb]; ``advantages``).  Writes g_preds, g_logp,
+        g_values = bufs[0:3], scalars[7] = bufs[3] = {loss, surrogate, error, critic, entropy, approx_kl, clip_frac}
+        and, with ``entropy_coef`` > 0 (``out.step_probs`` needed), g_probs = bufs[7]."""
+        cfg = self.cfg
+        assert cfg is not None
+        if not clip_eps > 0.0:
+            raise ValueError(f"ppo_clip must be > 0, got {clip_eps}")
+        if not entropy_coef >= 0.0:
+            raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
+        y = _need(y, th.int64, "y")
+        ent = entropy_coef > 0.0
+        if ent and out.step_probs is None:
+            raise ValueError("ppo_loss(entropy_coef > 0) needs the episode's step_probs: episode_forward(probs=True)")
+        want = tuple(out.step_log_probas.shape)
+        ins = []
+        for t, name in ((old_logp, "old_logp"), (advn, "advn"), (ret, "ret")):
+            if not isinstance(t, th.Tensor) or tuple(t.shape) != want:
+                raise ValueError(f"ppo_loss: {name} must be a tensor of shape {want}, got "
+                                 f"{tuple(getattr(t, 'shape', ()))}")
+            ins.append(_need(t, th.float32, name))
+        if bufs is None:
+            bufs = self.new_ppo_bufs(out, ent)
+        self._check_ppo_bufs(out, bufs, "ppo_loss")
+        if ent and (len(bufs) != 8 or bufs[7].shape != out.step_probs.shape):
+            raise ValueError("ppo_loss(entropy_coef > 0): buffers from new_ppo_bufs(out, True) needed")
+        probs = _need(out.step_probs, th.float32, "step_probs") if ent else None
+        ews = self.episode_ws(True)
+        check(self.lib.marl_ppo_loss_fwd_bwd(
+            C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(),
+            out.step_log_probas.data_ptr(), out.step_values.data_ptr(), y.data_ptr(), ins[0].data_ptr(),
+            ins[1].data_ptr(), ins[2].data_ptr(), C.c_float(clip_eps), _ptr(probs), C.c_float(entropy_coef),
+            bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[7].data_ptr() if ent else None,
+            bufs[3].data_ptr(), _stream(self.device)))
+        return bufs
+
+    def grad_clip(self, grads: th.Tensor, max_norm: float, grad_scale: float = 1.0) -> th.Tensor:
+        """marl_grad_clip: ``grads`` (flat fp32) *= min(1, max_norm / (norm + 1e-6)) in place; returns the device
+        scalar holding the norm before clipping (overwritten by the next call - clone to keep).  ``grad_scale``
+        (1 / world_size after an all-reduce sum) is applied first and stays in the buffer: Adam then takes 1."""
+        if not max_norm > 0.0:
+            raise ValueError(f"max_grad_norm must be > 0, got {max_norm}")
+        if not grad_scale > 0.0:
+            raise ValueError(f"grad_scale must be > 0, got {grad_scale}")
+        if not grads.is_cuda or grads.dtype != th.float32 or not grads.is_contiguous():
+            raise RuntimeError("grad_clip: the gradient buffer must be a contiguous fp32 GPU tensor")
+        if self._clip_scratch is None:
+            self._clip_scratch = th.zeros(_lib.MARL_GRAD_CLIP_SCRATCH_BYTES // 8 + 1, dtype=th.float64,
+                                          device=self.device)
+        sc = self._clip_scratch
+        check(self.lib.marl_grad_clip(grads.data_ptr(), grads.numel(), C.c_float(max_norm), C.c_float(grad_scale),
+                                      sc[-1:].data_ptr(),
+                                      sc.data_ptr(), _lib.MARL_GRAD_CLIP_SCRATCH_BYTES, _stream(self.device)))
+        return sc[-1:].view(th.float32)[0]
 
     def adam(
         self, params: th.Tensor, grads: th.Tensor, exp_avg: th.Tensor, exp_avg_sq: th.Tensor,

@@ -101,16 +101,93 @@ class FlatParams:
                 views[k].copy_(tensors[k])
 
 
+def check_ppo_options(ppo_epochs: int, ppo_clip: float, gae_lambda: float, max_grad_norm: Optional[float]) -> None:
+    """The constructor guards ``Trainer`` and ``FusedA2C`` share."""
+    if isinstance(ppo_epochs, bool) or not isinstance(ppo_epochs, int) or ppo_epochs < 1:
+        raise ValueError(f"ppo_epochs must be an integer >= 1, got {ppo_epochs!r}")
+    if not ppo_clip > 0.0:
+        raise ValueError(f"ppo_clip must be > 0, got {ppo_clip}")
+    if not 0.0 <= gae_lambda <= 1.0:
+        raise ValueError(f"gae_lambda must lie in [0, 1], got {gae_lambda}")
+    if max_grad_norm is not None and not max_grad_norm > 0.0:
+        raise ValueError(f"max_grad_norm must be > 0 or None, got {max_grad_norm}")
+
+
+def ppo_options_on(ppo_epochs: int, ppo_clip: float, gae_lambda: float, max_grad_norm: Optional[float]) -> bool:
+    """False = all four at their defaults: the A2C entries, verbatim."""
+    return ppo_epochs != 1 or ppo_clip != 0.2 or gae_lambda != 1.0 or max_grad_norm is not None
+
+
+def ppo_bufs_fit(bufs, out: EpisodeTensors, entropy: bool) -> bool:
+    """Do the persistent ``HipEngine.new_ppo_bufs`` tensors match this episode?"""
+    return (bufs is not None and len(bufs) == (8 if entropy else 7) and bufs[0].shape == out.step_preds.shape and
+            (not entropy or bufs[7].shape == out.step_probs.shape))
+
+
+def ppo_epochs_loop(eng: HipEngine, flat: "FlatParams", out: EpisodeTensors, y: th.Tensor, bufs, epochs: int,
+                    clip: float, beta: float, lr: float, allreduce, max_grad_norm: Optional[float], gviews,
+                    replay: Callable[[], EpisodeTensors], repack: Callable[[], None]) -> Optional[th.Tensor]:
+    """The K update epochs of one rollout ``out`` whose advantages already sit in ``bufs`` (``HipEngine.advantages``);
+    ``Trainer`` and ``FusedA2C`` both run this.  Epoch k > 0 starts with ``replay()``: the stored trajectory (same
+    draws, the rollout's actions forced) under the weights the last epoch packed.  Then ppo_loss -> backward (bucketed
+    hooks as in the A2C step) -> all-reduce -> [grad_clip, after the all-reduce and its scale: every rank clips the
+    same averaged gradient] -> Adam (``flat.step`` += 1) -> ``repack()``.  Returns the device scalar with the last
+    epoch's gradient norm (None without ``max_grad_norm``)."""
+    gp, gl, gv, _, _, advn, ret = bufs[:7]
+    gpr = bufs[7] if beta > 0 else None
+    # the old log-probabilities are the rollout's own output tensor: a replay writes fresh outputs, so epoch 0 has
+    # rho == 1 bit for bit and no copy is needed - as long as the replay really returns other storage
+    old_logp = out.step_log_probas
+    bucketed = hasattr(allreduce, "before_backward")  # parallel.BucketedGradAllReduce
+    cur, norm = out, None
+    for k in range(epochs):
+        if k > 0:
+            cur = replay()
+            if cur.step_log_probas.data_ptr() == old_logp.data_ptr():
+                raise RuntimeError("PPO replay wrote over the rollout's log-probabilities (persistent output "
+                                   "tensors?): the ratios would all be 1")
+        eng.ppo_loss(cur, y, old_logp, advn, ret, clip, bufs, entropy_coef=beta)
+        if bucketed:
+            allreduce.before_backward(eng)
+        try:
+            eng.episode_backward(gp, gl, gv, gviews, g_probs=gpr)
+        finally:
+            if bucketed:
+                allreduce.after_backward(eng)
+        scale = 1.0 if allreduce is None else allreduce(flat.grads)
+        if max_grad_norm is not None:
+            norm = eng.grad_clip(flat.grads, max_grad_norm, grad_scale=scale)
+            scale = 1.0
+        flat.step += 1
+        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, lr, grad_scale=scale)
+        repack()
+    return norm
+
+
 class FusedA2C:
     """rollout + loss + backward + Adam on one GPU; ``allreduce`` hooks in data parallelism."""
 
     def __init__(self, engine: HipEngine, flat: FlatParams, lr: float, gamma: float,
                  allreduce: Optional[Callable[[th.Tensor], float]] = None,
-                 use_graph: bool = False, entropy_coef: float = 0.0) -> None:
+                 use_graph: bool = False, entropy_coef: float = 0.0, ppo_epochs: int = 1,
+                 ppo_clip: float = 0.2, gae_lambda: float = 1.0,
+                 max_grad_norm: Optional[float] = None) -> None:
         if use_graph and allreduce is not None:
             raise ValueError("hipGraph replay covers the single-GPU iteration (no collective inside)")
         if not entropy_coef >= 0.0:
             raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
+        check_ppo_options(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
+        # K update epochs per rollout on the clipped surrogate (marl_advantages / marl_ppo_loss_fwd_bwd /
+        # marl_grad_clip); all four at their defaults: the A2C iteration below, verbatim
+        self.ppo_epochs, self.ppo_clip, self.gae_lambda = int(ppo_epochs), float(ppo_clip), float(gae_lambda)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._ppo = ppo_options_on(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
+        if use_graph and self._ppo:
+            # (K epochs in one capture: the counter block would have to tick K Adam steps per generator offset)
+            raise ValueError("hipGraph replay covers the one-update A2C iteration: ppo_epochs / ppo_clip / "
+                             "gae_lambda / max_grad_norm must stay at their defaults with use_graph")
+        self._ppo_bufs = None
+        self.last_grad_norm: Optional[th.Tensor] = None  # device scalar: the norm marl_grad_clip saw last
         # beta of the entropy bonus (loss - beta * mean_{a,b} sum_t H); 0: the plain entries, verbatim.  May be
         # changed between iterations (a captured graph is keyed by it)
         self.entropy_coef = float(entropy_coef)
@@ -147,6 +224,9 @@ class FusedA2C:
         read from the tensors of the capturing call (same storage every call, or re-capture).
         Outputs are persistent tensors, overwritten by every replay."""
         eng = self.engine
+        if self._ppo:
+            raise ValueError("iteration_graph captures the one-update A2C iteration: ppo_epochs / ppo_clip / "
+                             "gae_lambda / max_grad_norm must stay at their defaults")
         from . import engine as _engine_mod
 
         # (the tune epoch: after engine.tune() the workspaces baked into a captured graph are freed /
@@ -217,6 +297,8 @@ class FusedA2C:
         bonus: the loss includes it and a fifth scalar holds the mean entropy)."""
         eng = self.engine
         beta = self.entropy_coef
+        if self._ppo:
+            return self._iteration_ppo(img, y, draws)
         out = self.rollout(img, draws, True, probs=beta > 0)
         if (self._loss_bufs is None or self._loss_bufs[0].shape != out.step_preds.shape or
                 len(self._loss_bufs) != (6 if beta > 0 else 5)):
@@ -240,3 +322,22 @@ class FusedA2C:
                  self.flat.step, self.lr, grad_scale=scale)
         self.pack()
         return out, scalars
+
+    def _iteration_ppo(self, img: th.Tensor, y: th.Tensor, draws: EpisodeDraws) -> Tuple[EpisodeTensors, th.Tensor]:
+        """One rollout, ``ppo_epochs`` updates; returns the rollout's outputs and the last epoch's scalars
+        {loss, surrogate, error, critic, entropy, approx_kl, clip_frac}."""
+        eng, beta = self.engine, self.entropy_coef
+        ent = beta > 0
+        out = self.rollout(img, draws, True, probs=ent)
+        bufs = self._ppo_bufs
+        if not ppo_bufs_fit(bufs, out, ent):
+            bufs = self._ppo_bufs = eng.new_ppo_bufs(out, ent)
+        eng.advantages(out, y, self.gamma, self.gae_lambda, 0, bufs)
+        norm = ppo_epochs_loop(
+            eng, self.flat, out, y, bufs, self.ppo_epochs, self.ppo_clip, beta, self.lr, self.allreduce,
+            self.max_grad_norm, self._gviews,
+            replay=lambda: self.rollout(img, draws, True, forced_actions=out.step_actions, probs=ent),
+            repack=self.pack)
+        if norm is not None:
+            self.last_grad_norm = norm
+        return out, bufs[3]

@@ -196,7 +196,12 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
                                                       device) if distributed else None),
                       exact_standardize_group=(dist.group.WORLD if distributed and world > 1 and
                                                exact_standardize else None),
-                      entropy_coef=train_config.entropy_coef)
+                      entropy_coef=train_config.entropy_coef, ppo_epochs=train_config.ppo_epochs,
+                      ppo_clip=train_config.ppo_clip, gae_lambda=train_config.gae_lambda,
+                      max_grad_norm=train_config.max_grad_norm)
+    if rank == 0:
+        print("update: " + ", ".join(f"{k}={getattr(train_config, k)}" for k in (
+            "entropy_coef", "ppo_epochs", "ppo_clip", "gae_lambda", "max_grad_norm")), flush=True)
     for e in range(train_config.nb_epoch):
         for bs in samplers:
             bs.set_epoch(e)

@@ -4,6 +4,9 @@ One training iteration is: ``marl_episode_forward`` (all steps) -> ``marl_a2c_lo
 (loss + dL/d outputs) -> ``marl_episode_backward`` (BPTT, every parameter gradient) ->
 [one RCCL all-reduce of the flat gradient buffer] -> ``marl_adam_step`` -> re-pack.  No host
 synchronisation happens inside an iteration; meters are read every ``log_interval`` steps.
+With a PPO option off its default (``ppo_epochs``, ``ppo_clip``, ``gae_lambda``, ``max_grad_norm``) one rollout
+feeds K updates: ``marl_advantages`` once, then per epoch [replay forward] -> ``marl_ppo_loss_fwd_bwd`` -> backward
+-> [all-reduce] -> [``marl_grad_clip``] -> Adam -> re-pack.
 Same constructor and ``train_epoch`` / ``eval_epoch`` signatures as the reference.
 """
 
@@ -13,6 +16,7 @@ import torch as th
 
 from ..core import EpisodeSampler
 from ..engine import EpisodeTensors
+from ..fused import check_ppo_options, ppo_bufs_fit, ppo_epochs_loop, ppo_options_on
 from ..metrics import ConfusionMeter, LossMeter
 from ..networks import ModelsWrapper
 
@@ -32,9 +36,14 @@ class Trainer:
         allreduce: Optional[Callable[[th.Tensor], float]] = None,
         exact_standardize_group=None,
         entropy_coef: float = 0.0,
+        ppo_epochs: int = 1,
+        ppo_clip: float = 0.2,
+        gae_lambda: float = 1.0,
+        max_grad_norm: Optional[float] = None,
     ) -> None:
         if not entropy_coef >= 0.0:
             raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
+        check_ppo_options(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
         self.__model = model
         self.__nb_class = nb_class
         self.__lr = learning_rate
@@ -46,11 +55,26 @@ class Trainer:
         # beta of the entropy bonus (loss - beta * mean_{a,b} sum_t H): 0 = the reference's loss through the plain
         # entries; > 0 = marl_episode_forward_probs / marl_a2c_loss_entropy_fwd_bwd / marl_episode_backward_probs
         self.__entropy_coef = float(entropy_coef)
+        # PPO (marl_advantages / marl_ppo_loss_fwd_bwd / marl_grad_clip): K update epochs per rollout on the clipped
+        # surrogate with GAE(lambda) advantages, epochs 1 .. K-1 replaying the stored trajectory under the new
+        # weights.  All four at their defaults: the A2C step below, verbatim - nothing new is launched
+        self.__ppo_epochs, self.__ppo_clip, self.__gae_lambda = int(ppo_epochs), float(ppo_clip), float(gae_lambda)
+        self.__max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.__ppo = ppo_options_on(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
+        self.__ppo_bufs: Optional[Tuple[th.Tensor, ...]] = None
+        self.__grad_norm: Optional[th.Tensor] = None
         self.__curr_step = 0
         self.__loss_bufs: Optional[Tuple[th.Tensor, ...]] = None
         self.__conf_meter = ConfusionMeter(nb_class, window_size=meter_window_size)
         self.__meter_keys = ("loss", "path", "error", "critic") + (("entropy",) if entropy_coef > 0 else ())
+        # (scalars index of every meter: the PPO scalars keep the entropy slot, zero without a bonus)
+        self.__meter_idx = {k: i for i, k in enumerate(self.__meter_keys)}
+        if self.__ppo:
+            self.__meter_idx.update(approx_kl=5, clip_frac=6)
+            self.__meter_keys += ("approx_kl", "clip_frac")
         self.__meters = {k: LossMeter(window_size=meter_window_size) for k in self.__meter_keys}
+        if self.__max_grad_norm is not None:
+            self.__meters["grad_norm"] = LossMeter(window_size=meter_window_size)
 
     @property
     def curr_step(self) -> int:
@@ -61,6 +85,8 @@ class Trainer:
         model = self.__model
         device = model.device
         y = y.to(device)
+        if self.__ppo:
+            return self.__train_step_ppo(x, y, sampler)
         if self.__entropy_coef > 0:
             return self.__train_step_entropy(x, y, sampler)
         eng, out = sampler.run_episode_raw(x, train=True)
@@ -127,14 +153,48 @@ class Trainer:
         model.mark_updated(eng)
         return out, scalars
 
+    def __train_step_ppo(self, x: th.Tensor, y: th.Tensor,
+                         sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
+        """One rollout, K updates.  Returns the ROLLOUT's outputs (meters and confusion matrix stay on-policy) and
+        the last epoch's scalars {loss, surrogate, error, critic, entropy, approx_kl, clip_frac}."""
+        model, beta = self.__model, self.__entropy_coef
+        ent = beta > 0
+        # the draws of this rollout and the batch on the device: epochs 1 .. K-1 replay with them (nothing is drawn or
+        # uploaded again); run_episode_raw(draws=...) takes given draws as they are
+        _, img, draws = sampler.prepare(x)
+        eng, out = sampler.run_episode_raw(img, train=True, draws=draws, probs=ent)
+        if not ppo_bufs_fit(self.__ppo_bufs, out, ent):
+            self.__ppo_bufs = eng.new_ppo_bufs(out, ent)
+        bufs = self.__ppo_bufs
+        if self.__exact_group is None:
+            eng.advantages(out, y, self.__gamma, self.__gae_lambda, 0, bufs)
+        else:  # global mean / std of the advantages: one 3-double all-reduce between phases
+            from ..parallel import allreduce_adv_stats
+
+            eng.advantages(out, y, self.__gamma, self.__gae_lambda, 1, bufs)
+            allreduce_adv_stats(bufs[4], self.__exact_group)
+            eng.advantages(out, y, self.__gamma, self.__gae_lambda, 2, bufs)
+        flat = model.flat_state()
+        norm = ppo_epochs_loop(
+            eng, flat, out, y, bufs, self.__ppo_epochs, self.__ppo_clip, beta, self.__lr, self.__allreduce,
+            self.__max_grad_norm, flat.grad_views(),
+            replay=lambda: sampler.run_episode_raw(img, train=True, draws=draws, probs=ent,
+                                                   forced=out.step_actions)[1],
+            repack=lambda: model.mark_updated(eng))
+        if norm is not None:
+            self.__grad_norm = norm
+        return out, bufs[3]
+
     def train_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler) -> None:
         self.__model.train()
         for x_train, y_train in dataloader:
             out, scalars = self.train_step(x_train, y_train, episode_sampler)
             # device-side meters, no sync (select last step, mean over agents: trainer.py:124-128)
             self.__conf_meter.add(out.step_preds[-1].mean(dim=0), y_train)
-            for i, k in enumerate(self.__meter_keys):
-                self.__meters[k].add(scalars[i].clone())
+            for k in self.__meter_keys:
+                self.__meters[k].add(scalars[self.__meter_idx[k]].clone())
+            if self.__max_grad_norm is not None:  # (the norm before clipping, of the last epoch's gradient)
+                self.__meters["grad_norm"].add(self.__grad_norm.clone())
             if self.__metric_logger is not None and self.__curr_step % self.__log_interval == 0:
                 self.__metric_logger(self.__curr_step, self.metrics())
             self.__curr_step += 1
@@ -151,6 +211,9 @@ class Trainer:
         }
         if "entropy" in self.__meters:  # (only with an entropy bonus: the plain trainer never sees the distributions)
             m["entropy"] = self.__meters["entropy"].loss()
+        for k in ("approx_kl", "clip_frac", "grad_norm"):  # (only with the matching PPO option on)
+            if k in self.__meters:
+                m[k] = self.__meters[k].loss()
         return m
 
     def eval_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler) -> ConfusionMeter:
