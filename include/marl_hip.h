@@ -250,6 +250,25 @@ int marl_episode_backward_probs(const marl_config* cfg, void* weights_ws, size_t
  * while the rest of the backward pass runs (parallel.py, BucketedGradAllReduce). */
 int marl_backward_heads_event(void* hip_event);
 
+/* Communication graph of the message exchange (the method's aggregation over neighbours; the reference's
+ * networks/message.py:5-17 is the complete graph).  m_dev: caller-owned fp32 [nb_agents, nb_agents] on the device,
+ * row = receiver, column = sender; while it is installed (per-process state, NULL restores the mean over the other
+ * agents) every episode / step entry aggregates
+ *     mbar[a, b, :] = sum_a' M[a, a'] * m[a', b, :]
+ * in fp32 as one fmaf chain over a' ascending, and its backward uses M^T in the same fixed order (no atomics; no
+ * gradient with respect to M).  An entry that is exactly 0 is skipped, not multiplied: a non-neighbour's NaN / Inf
+ * does not leak through 0 * x.  Self-loops, asymmetric and negative weights are legal; the caller checks that the
+ * entries are finite.  The matrix is read when the kernels run, so it must stay alive and unchanged until the work
+ * enqueued under it has finished; a captured graph keeps the pointer.  Under a matrix the chained panel launches
+ * (encoder -> aggregate -> decoder, and their backward) mix inside the workgroup (the MIX instantiations of
+ * panel_fwd_kernel / panel_bwd_kernel, the matrix staged in LDS); the decoder of step 0, the unchained panel path, the
+ * GEMM + row-kernel path and the step entries aggregate with mix_msg_kernel in a launch of its own ahead of a plain
+ * launch.  marl_plan_query keys "comm" (a matrix is set), "comm_form" (0 / 1 / 2: the mean in the chained launch /
+ * while a panel stages / by agg_msg_kernel; 5 / 3 / 4: the matrix in the chained launch / by mix_msg_kernel ahead of
+ * a plain panel launch / ahead of the GEMM path) and "panel_chain" report the form.  Returns MARL_ELIMIT for nb_agents above 32; an entry whose configuration has
+ * another nb_agents returns MARL_EINVAL before anything is enqueued. */
+int marl_comm_matrix(const float* m_dev, int nb_agents);
+
 /* Loss of Trainer.train_epoch (training/trainer.py:76-111; training/functions.py:7-55)
  * and its gradient w.r.t. the episode outputs in one pass.
  * y int64 [Nb].  scalars_out[4] = {loss, path, error, critic} (trainer.py:111,119-122).

@@ -6,6 +6,7 @@ import argparse
 import re
 from os.path import abspath, dirname, join
 
+from .comm import check_spelling
 from .config import EvalConfig, InferConfig, MainConfig, ModelConfig, TrainConfig
 from .networks.vision import CNN_BY_NAME
 
@@ -82,7 +83,19 @@ def build_parser() -> argparse.ArgumentParser:
                    help="lambda of the generalised advantage estimate (1: the reference's full returns - values)")
     t.add_argument("--max-grad-norm", type=float, default=None, dest="max_grad_norm",
                    help="clip the global gradient norm to X before every Adam step (default: no clipping)")
+    for sp in (t, e, i):
+        sp.add_argument("--comm", type=_comm_arg, default=None, dest="comm", metavar="GRAPH",
+                        help="communication graph of the message exchange: full | none | ring[:k] | star[:hub] | "
+                             "grid:RxC | teams:a,b,... | FILE.npy ([Na,Na], row = receiver); default: the mean over "
+                             "the other agents (test / infer: what marl.json names)")
     return p
+
+
+def _comm_arg(text: str) -> str:
+    try:
+        return check_spelling(text)
+    except ValueError as err:
+        raise argparse.ArgumentTypeError(str(err))
 
 
 def main(argv=None) -> None:
@@ -97,6 +110,7 @@ def main(argv=None) -> None:
             hidden_size_msg_output=args.n_m_o, hidden_size_state=args.n_d, state_dim=args.dim,
             actions=parse_actions(args.action, args.dim), nb_class=args.nb_class,
             hidden_size_linear_belief=args.n_l_b, hidden_size_linear_action=args.n_l_a,
+            comm=args.comm,
         )
         train_config = TrainConfig(
             img_size=args.img_size, nb_epoch=args.nb_epoch, learning_rate=args.learning_rate,
@@ -110,7 +124,8 @@ def main(argv=None) -> None:
 
         eval_main(main_config, EvalConfig(
             img_size=args.img_size, state_dict_path=args.state_dict_path, batch_size=args.batch_size,
-            json_path=args.json_path, dataset_path=args.dataset_path, output_dir=args.output_dir))
+            json_path=args.json_path, dataset_path=args.dataset_path, output_dir=args.output_dir,
+            comm=args.comm))
     elif args.main_choice == "infer":
         import os
 
@@ -121,7 +136,8 @@ def main(argv=None) -> None:
         os.makedirs(args.output_image_dir, exist_ok=True)
         infer_main(main_config, InferConfig(
             state_dict_path=args.state_dict_path, json_path=args.json_path, images_path=args.infer_images,
-            output_dir=args.output_image_dir, class_to_idx=args.class_to_idx, saliency=args.saliency))
+            output_dir=args.output_image_dir, class_to_idx=args.class_to_idx, saliency=args.saliency,
+            comm=args.comm))
 
 
 if __name__ == "__main__":

@@ -78,7 +78,7 @@ EXPORTS = (
     "marl_gemm_tn_images_cell marl_gemm_tn_images_cell_scratch marl_backward_heads_event "
     "marl_step_forward_train marl_step_backward marl_episode_backward_img "
     "marl_episode_forward_probs marl_episode_backward_probs marl_a2c_loss_entropy_fwd_bwd "
-    "marl_advantages marl_ppo_loss_fwd_bwd marl_grad_clip"
+    "marl_advantages marl_ppo_loss_fwd_bwd marl_grad_clip marl_comm_matrix"
 ).split()
 
 _lib: Optional[C.CDLL] = None
@@ -160,6 +160,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_gemm_tn_images_cell.argtypes = [_vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]
     lib.marl_plan_query.argtypes = [_cfgp, _i, C.c_char_p, C.POINTER(_i)]
     lib.marl_backward_heads_event.argtypes = [_vp]
+    lib.marl_comm_matrix.argtypes = [_vp, _i]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("marl_abi_version", "marl_tune_get"):

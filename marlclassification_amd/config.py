@@ -39,17 +39,23 @@ class ModelConfig(BaseModel):
     nb_class: int
     hidden_size_linear_belief: int
     hidden_size_linear_action: int
+    # communication graph in the command-line spelling (comm.parse: full | none | ring[:k] | star[:hub] | grid:RxC |
+    # teams:a,b,... | FILE.npy); None: the reference's mean over the other agents - and the reference's marl.json
+    comm: Optional[str] = None
 
     def save_marl_config(self, out_json_path: str) -> None:
+        raw = {k: getattr(self, k) for k in _MODEL_KEYS}
+        if self.comm is not None:  # (only when one was given: a default run writes the reference's file)
+            raw["comm"] = self.comm
         with open(out_json_path, "w", encoding="utf-8") as f:
-            json.dump({k: getattr(self, k) for k in _MODEL_KEYS}, f)
+            json.dump(raw, f)
 
     @classmethod
     def load_marl_config(cls, json_path: str) -> "ModelConfig":
         assert exists(json_path) and isfile(json_path), f'"{json_path}" does not exist or is not a file'
         with open(json_path, "r", encoding="utf-8") as f:
             raw = json.load(f)
-        return cls(**{k: raw[k] for k in _MODEL_KEYS})
+        return cls(**{k: raw[k] for k in _MODEL_KEYS}, comm=raw.get("comm"))
 
     def build_networks(self) -> ModelsWrapper:
         assert self.ft_extr_str in CNN_BY_NAME, (
@@ -68,6 +74,10 @@ class ModelConfig(BaseModel):
 
     def build_marl(self, nb_agents: int) -> Tuple[ModelsWrapper, MultiAgent, Environment]:
         networks = self.build_networks()
+        if self.comm is not None:
+            from . import comm as _comm
+
+            networks.set_comm(_comm.parse(self.comm, nb_agents))  # (moves with networks.to(device))
         return networks, MultiAgent(nb_agents, networks), self.build_environment()
 
 
@@ -96,6 +106,7 @@ class EvalConfig(BaseModel):
     json_path: str
     dataset_path: str
     output_dir: str
+    comm: Optional[str] = None  # --comm: replaces the graph marl.json names (None: keep it)
 
 
 class InferConfig(BaseModel):
@@ -105,3 +116,4 @@ class InferConfig(BaseModel):
     output_dir: str
     class_to_idx: str
     saliency: bool = False  # also write saliency.png (|d logit / d pixel|) next to the step frames
+    comm: Optional[str] = None  # --comm: replaces the graph marl.json names (None: keep it)

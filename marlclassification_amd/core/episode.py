@@ -59,6 +59,7 @@ class _EpisodeFunction(th.autograd.Function):
                                   draws.noise, forced, True, rng=draws.rng, ws=ws, probs=probs)
         ctx.eng, ctx.ws, ctx.img = eng, ws, img
         ctx.cfg_key = eng._cfg_key
+        ctx.comm = eng.comm  # the backward goes through the transpose of THIS rollout's matrix, whatever is set by then
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
         ctx.shapes = [p.shape for p in params]
@@ -76,15 +77,19 @@ class _EpisodeFunction(th.autograd.Function):
             raise RuntimeError("the model's weights were modified (re-packed) after this episode's rollout: "
                                "its backward needs the weights the rollout used - call backward before "
                                "the optimiser step")
-        if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
-            na, nb, ns, shape, u8 = ctx.cfg_key
-            eng.configure(na, nb, ns, shape, img_u8=u8)
-        grads = {k: th.empty(s, device=eng.device) for k, s in zip(ctx.names, ctx.shapes)}
-        # the image is a differentiable input (the reference's crop is a masked_select of it,
-        # core/environment.py:95-126): asked for, its gradient comes out of the same backward pass
-        d_img = th.empty(ctx.img.shape, device=eng.device) if ctx.needs_input_grad[1] else None
-        eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img,
-                             g_probs=g_probs)
+        later_comm, eng.comm = eng.comm, ctx.comm
+        try:
+            if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
+                na, nb, ns, shape, u8 = ctx.cfg_key
+                eng.configure(na, nb, ns, shape, img_u8=u8)
+            grads = {k: th.empty(s, device=eng.device) for k, s in zip(ctx.names, ctx.shapes)}
+            # the image is a differentiable input (the reference's crop is a masked_select of it,
+            # core/environment.py:95-126): asked for, its gradient comes out of the same backward pass
+            d_img = th.empty(ctx.img.shape, device=eng.device) if ctx.needs_input_grad[1] else None
+            eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img,
+                                 g_probs=g_probs)
+        finally:
+            eng.comm = later_comm
         eng.train_ws_release(ctx.ws)
         ctx.ws = None
         # (a frozen model: the parameter gradients are computed and dropped here)

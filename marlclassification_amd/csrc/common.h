@@ -407,6 +407,11 @@ int launch_gn_silu_bwd(const float* da, int64_t ldda, int da_chw, const float* z
 // message mean over the other agents (networks/message.py:5-17); self-adjoint, so the
 // same kernel is its own backward.
 int launch_agg_msg(const float* m, float* out, int ld, int na, int nb, int n, hipStream_t st);
+// message mixing over a communication graph: out[a] = sum_a' M[a, a'] * m[a'] (transpose: M^T, the
+// backward); mix = [na, na] fp32 on the device, row = receiver.  out == m is legal.
+int launch_mix_msg(const float* m, float* out, int ld, int na, int nb, int n, const float* mix, int transpose,
+                   hipStream_t st);
+int mix_msg_max_agents();
 
 // map_pos (networks/state.py): lambda = SiLU(LN(W * (pos / size) + b)) -> out (ld ldo)
 // (npos_in != null: use these normalised positions [rows,2] instead of pos / size)
@@ -565,11 +570,15 @@ struct PanelFwdProb {
     // layer l's input panel in LDS (encoder -> mean -> decoder in ONE launch) and stores the
     // aggregated rows to xbar [M, ld_xbar].
     int by_batch, g_na, g_nb, agg_at, ld_xbar;
+    // communication graph (marl_comm_matrix): non-null = the [g_na, g_na] mixing matrix (row = receiver) the agg_at
+    // site applies instead of the mean: mbar[a] = sum_a' mix[a, a'] * m[a'], zero entries skipped
+    const float* mix;
 };
 struct PanelFwdBatch {
     PanelFwdProb p[2];
     int count;
     int off_panel1, off_red, off_part, off_prm;  // LDS float offsets (filled by the launcher)
+    int off_mix;  // LDS copy of the mixing matrix (launches with a p[].mix only)
     // optional (count == 1): extra workgroups behind the panel ones run the sampling kernel's
     // rows (one wave per row) - an independent small kernel riding along in the same launch
     int has_sample, panel_blocks;
@@ -716,6 +725,10 @@ struct PanelBwdProb {
     int has_cellb;
     LstmBwdArgs cellb;
     int off_e, off_prm, off_colp, off_part, off_rowmap;  // LDS float offsets (filled by the launcher)
+    // communication graph: non-null = the agg_at site applies the TRANSPOSE of this [g_na, g_na] mixing matrix
+    // (dm[a'] = sum_a mix[a, a'] * dmbar[a]) instead of the self-adjoint mean; off_mix: its LDS copy (launcher)
+    const float* mix;
+    int off_mix;
     int tail_lds;  // 1: the final dX is finished row-wise from an LDS panel (filled by the launcher)
     // optional: extra workgroups behind the panel ones run one LSTM cell's elementwise backward
     // (an independent memory-bound kernel riding along with this latency-bound one)

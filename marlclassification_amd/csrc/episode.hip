@@ -617,11 +617,24 @@ struct Ctx {
 
 static void register_split_images(const Dims& d, const WLayout& w, const float* W);
 static bool use_panels(const Dims& d);
+
+// marl_comm_matrix: the caller-owned [na, na] mixing matrix of the message exchange (row = receiver), or null =
+// the mean over the other agents.  Under a matrix the chained panel launches mix inside the workgroup (the MIX
+// instantiations of panel_fwd_kernel / panel_bwd_kernel); everywhere else - the decoder of step 0, the unchained
+// panel path, the GEMM path, the step API - the aggregation is mix_msg_kernel (rowops.hip) in a launch of its own
+// and the panel kernels stage plain rows.
+static const float* g_comm = nullptr;
+static int g_comm_na = 0;
 static bool use_side_stream();
 
 static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void* ews, size_t ebytes,
                     int train, void* stream, Ctx& c) {
     MARL_TRY(make_dims(cfg, c.d));
+    if (g_comm && g_comm_na != c.d.na) {  // (before anything is enqueued)
+        set_error("communication matrix is %d x %d but the configuration has %d agents", g_comm_na, g_comm_na,
+                  c.d.na);
+        return MARL_EINVAL;
+    }
     make_wlayout(c.d, c.w);
     make_elayout(c.d, train, c.e);
     if (wbytes < c.w.total * sizeof(float) || ebytes < c.e.total * sizeof(float)) {
@@ -797,6 +810,12 @@ static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, 
         p.agg_na = d.na;
         p.agg_nb = d.nb;
         p.xbar = c.at(c.e.MBAR, t);
+        if (g_comm) {  // mixed rows (pad columns included: the panel stages whole float4s) -> MBAR, staged as they are
+            MARL_TRY(launch_mix_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.ld_nm, g_comm, 0, st));
+            p.x = c.at(c.e.MBAR, t);
+            p.agg_na = p.agg_nb = 0;
+            p.xbar = nullptr;
+        }
         p.m = R;
         p.nlayers = 2;
         fill_dec_layers(c, t, p.layer);
@@ -807,7 +826,10 @@ static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, 
         }
         return launch_panel_fwd(pb, st);
     }
-    MARL_TRY(launch_agg_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.n_m, st));
+    if (g_comm)
+        MARL_TRY(launch_mix_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.n_m, g_comm, 0, st));
+    else
+        MARL_TRY(launch_agg_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.n_m, st));
     MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.MBAR, t), d.ld_nm, c.wp(MARL_P_DEC_W0), p4(d.n_m), d.n_m,
                                 c.at(c.e.ZD1, t), d.ld_nm2, R, d.nm2, c.wp(MARL_P_DEC_B0))));
     MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZD1, t), d.ld_nm2, c.wp(MARL_P_DEC_LN0W),
@@ -975,7 +997,10 @@ static int step_encode_policy(const Ctx& c, int t, int which) {
 //   backward: decoder(t) -> mean -> encoder(t-1) -> dh_t complete -> belief cell(t-1)
 static bool use_chain(const Dims& d) {
     return use_panels(d) && panel_chain_supported(d.na, d.n_m, 256) && d.n_mo <= 384 && d.nm2 <= 384 &&
-           d.n_m <= 384 && tune_get("panel_chain", 1) != 0;
+           d.n_m <= 384 && tune_get("panel_chain", 1) != 0 &&
+           // under a matrix the chained kernels also keep it in LDS (16 x 16 floats): with the input width bounded
+           // like the others every admitted plan has room for it; wider models take mix_msg_kernel
+           (!g_comm || d.n_b <= 384);
 }
 static int step_chain(const Ctx& c, int t) {
     const Dims& d = c.d;
@@ -992,6 +1017,7 @@ static int step_chain(const Ctx& c, int t) {
         pe.agg_at = 2;
         pe.xbar = c.at(c.e.MBAR, t + 1);
         pe.ld_xbar = d.ld_nm;
+        pe.mix = g_comm;  // (null: the mean)
     }
     fill_pol_prob(c, t, pb.p[1]);
     return launch_panel_fwd(pb, c.st);
@@ -1663,6 +1689,7 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                 if (t > 0) {
                     pd.nlayers = 4;
                     pd.agg_at = 2;
+                    pd.mix = g_comm;  // (null: the self-adjoint mean; else the kernel applies M^T)
                     pd.layer[2] = PanelBwdLayer{c.at(c.e.ZE2, t - 1), d.ld_nm, c.at(c.e.STE2, t - 1),
                                                 c.wp(MARL_P_ENC_LN1W), c.wp(MARL_P_ENC_LN1B), d.n_m,
                                                 c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm, d.ld_nm,
@@ -1696,6 +1723,11 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                 pe.ldda = d.ld_nm;
                 pe.agg_na = d.na;
                 pe.agg_nb = d.nb;
+                if (g_comm) {  // M^T in place (a thread owns one (batch, column) over all agents), then plain rows
+                    MARL_TRY(launch_mix_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.ld_nm, g_comm,
+                                            1, st));
+                    pe.agg_na = pe.agg_nb = 0;
+                }
                 pe.m = R;
                 pe.nlayers = 2;
                 pe.layer[0] = PanelBwdLayer{c.at(c.e.ZE2, t - 1), d.ld_nm, c.at(c.e.STE2, t - 1),
@@ -1731,7 +1763,10 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
             MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wt(MARL_P_DEC_W0), p4(d.nm2), d.nm2,
                                         c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
             float* dze2 = c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm;
-            MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, st));
+            if (g_comm)  // the transpose of the mixing matrix
+                MARL_TRY(launch_mix_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, g_comm, 1, st));
+            else
+                MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, st));
             const int efirst = (t == ns - 1);
             MARL_TRY(ln_bwd(c, dze2, d.ld_nm, c.at(c.e.ZE2, t - 1), d.ld_nm, c.at(c.e.STE2, t - 1),
                             MARL_P_ENC_LN1W, MARL_P_ENC_LN1B, d.R, d.n_m, grads, !efirst));
@@ -1749,7 +1784,10 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
         // (DMBAR = dL/d(mean message) of step 0; the mean is self-adjoint and may run in place: every thread
         // owns one (batch, column) over all agents)
         if (sb->d_msg) {
-            MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.n_m, st));
+            if (g_comm)  // d msg goes through M^T, also in place (the kernel holds all agents' inputs in registers)
+                MARL_TRY(launch_mix_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.n_m, g_comm, 1, st));
+            else
+                MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.n_m, st));
             MARL_TRY(launch_copy2d(c.at(c.e.DMBAR), d.ld_nm, sb->d_msg, d.n_m, d.R, d.n_m, st));
         }
         if (sb->d_h) MARL_TRY(launch_copy2d(c.DHs(0), d.ld_nb, sb->d_h, d.n_b, d.R, d.n_b, st));
@@ -2267,6 +2305,25 @@ int marl_backward_heads_event(void* hip_event) {
     return MARL_OK;
 }
 
+int marl_comm_matrix(const float* m_dev, int nb_agents) {
+    if (!m_dev) {
+        g_comm = nullptr;
+        g_comm_na = 0;
+        return MARL_OK;
+    }
+    if (nb_agents < 1) {
+        set_error("comm_matrix: %d agents", nb_agents);
+        return MARL_EINVAL;
+    }
+    if (nb_agents > mix_msg_max_agents()) {
+        set_error("comm_matrix: %d agents, the mixing kernel serves at most %d", nb_agents, mix_msg_max_agents());
+        return MARL_ELIMIT;
+    }
+    g_comm = m_dev;
+    g_comm_na = nb_agents;
+    return MARL_OK;
+}
+
 int marl_draw_episode(const marl_config* cfg, uint64_t seed, uint64_t offset, const void* counters,
                       int64_t* pos0, float* h0, float* c0, float* hc0, float* cc0, float* noise,
                       void* stream) {
@@ -2726,6 +2783,15 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
                  g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR);
     else if (!strcmp(key, "g3_tn_pipe")) *value = tune_get("g3_tn_pipe", 1) != 0;  // phase-pipelined row contractions
     else if (!strcmp(key, "wgrad3")) *value = tune_get("wgrad3", 1) != 0;  // conv weight gradients on the bf16 pipe (cin >= 16)
+    // message exchange: "comm" = a mixing matrix is set; "comm_form" = how the aggregation is launched now
+    // (0 = mean inside the chained panel launch, 1 = mean while a panel stages, 2 = agg_msg_kernel, 3 = mix_msg_kernel
+    // ahead of a plain panel launch, 4 = mix_msg_kernel ahead of the GEMM path, 5 = mixed inside the chained panel
+    // launch - the decoder of step 0 and the step API then take form 3); "panel_chain" = the chained launch
+    else if (!strcmp(key, "comm")) *value = g_comm != nullptr;
+    else if (!strcmp(key, "panel_chain")) *value = use_chain(d) && !use_side_stream();
+    else if (!strcmp(key, "comm_form"))
+        *value = g_comm ? ((use_chain(d) && !use_side_stream()) ? 5 : use_panels(d) ? 3 : 4)
+                        : (use_chain(d) && !use_side_stream()) ? 0 : use_panels(d) ? 1 : 2;
     else {
         set_error("unknown plan key %s", key);
         return MARL_EINVAL;

@@ -193,7 +193,9 @@ __device__ __forceinline__ void panel_ln_rows(const PanelLayer& Lr, float* outp,
 // ===========================================================================
 // SAMPLE: 0 = panels only; 4 / MARL_MAX_ACTIONS = sampling workgroups ride along behind the panel ones, with
 // the action loops of sample.h bounded at that many actions
-template <int SAMPLE>
+// MIX: the agg_at site mixes over a communication graph (P.mix) instead of taking the mean; the plain instantiations
+// carry none of it
+template <int SAMPLE, bool MIX = false>
 __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (SAMPLE > 0 && (int)blockIdx.x >= B.panel_blocks) {
@@ -246,6 +248,9 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             pv[l][2] = P.layer[l].beta[tid];
         }
     }
+    // the mixing coefficients join the same batch of loads (g_na <= 16: one per thread of the first four waves)
+    float cmv = 0.f;
+    if (MIX && P.mix && tid < P.g_na * P.g_na) cmv = P.mix[tid];
 
     // ---- stage the 32-row input panel (zero-filled past k0 and past M)
     {
@@ -334,6 +339,7 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             }
         }
     }
+    if (MIX && P.mix && tid < P.g_na * P.g_na) lds[B.off_mix + tid] = cmv;
     MARL_TS();
     lds_barrier();
     MARL_TS();
@@ -363,7 +369,25 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e - lr * c4) * 4;
                     const int a = lr / bpb, i = lr - a * bpb;
-                    if (a < na && na > 1) {
+                    if (MIX) {
+                        // communication graph: one fmaf chain over the senders, ascending; a sender whose
+                        // coefficient is exactly 0 is not read (its NaN / Inf cannot leak through 0 * x)
+                        if (a < na) {
+                            const float* crow = lds + B.off_mix + a * na;
+                            float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
+                            for (int a2 = 0; a2 < na; ++a2) {
+                                const float cf = crow[a2];
+                                if (cf != 0.f) {
+                                    const float4 q = *reinterpret_cast<const float4*>(in + (a2 * bpb + i) * stride + k);
+                                    sm.x = fmaf(cf, q.x, sm.x);
+                                    sm.y = fmaf(cf, q.y, sm.y);
+                                    sm.z = fmaf(cf, q.z, sm.z);
+                                    sm.w = fmaf(cf, q.w, sm.w);
+                                }
+                            }
+                            v[it] = sm;
+                        }
+                    } else if (a < na && na > 1) {
                         float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
                         for (int a2 = 0; a2 < na; ++a2) {
                             const float4 q = *reinterpret_cast<const float4*>(in + (a2 * bpb + i) * stride + k);
@@ -488,9 +512,14 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
             set_error("panel kernel: in-panel message mean outside its range");
             return MARL_ELIMIT;
         }
+        if (p.mix && (p.agg_at <= 0 || i != 0 || (b.has_sample && b.count == 1))) {
+            set_error("panel kernel: a mixing matrix needs the in-panel aggregation of problem 0");
+            return MARL_ELIMIT;
+        }
         x0 = s0 > x0 ? s0 : x0;
         x1 = s1 > x1 ? s1 : x1;
     }
+    const bool mixed = b.count > 0 && b.p[0].mix != nullptr;
     if (waves < 4) waves = 4;  // the LayerNorm row loop covers <= 4 rows per wave
     b.off_panel1 = x0;
     b.off_red = x0 + x1;
@@ -502,16 +531,21 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
         for (int l = 0; l < b.p[i].nlayers; ++l) q += 3 * b.p[i].layer[l].n;
         prm = q > prm ? q : prm;
     }
-    const size_t lds = (size_t)(b.off_prm + prm + 16) * sizeof(float);
+    // (+ the mixing matrix, g_na^2 <= kPanelRows^2 floats.  Every plan use_chain admits has widths <= 384: two panels
+    // of 16 x 388, 11 x 512 partials and 12 x 384 parameters are under 100 KiB, so the matrix always fits; the check
+    // below stays as the backstop)
+    b.off_mix = b.off_prm + prm + 16;
+    const size_t lds = (size_t)(b.off_mix + (mixed ? kPanelRows * kPanelRows : 0)) * sizeof(float);
     if (lds > kPanelMaxLds) {
         set_error("panel kernel: shape outside its range");
         return MARL_ELIMIT;
     }
     static bool raised = false;
     if (!raised) {
-        const void* kerns[3] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
+        const void* kerns[4] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4>),
-                                reinterpret_cast<const void*>(panel_fwd_kernel<MARL_MAX_ACTIONS>)};
+                                reinterpret_cast<const void*>(panel_fwd_kernel<MARL_MAX_ACTIONS>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<0, true>)};
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
@@ -539,8 +573,11 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
             hipLaunchKernelGGL(panel_fwd_kernel<MARL_MAX_ACTIONS>, dim3(pblocks + sblocks, 1), dim3(64 * waves), lds, st, b);
     } else {
         b.has_sample = 0;
-        hipLaunchKernelGGL(panel_fwd_kernel<0>, dim3(pblocks, (unsigned)b.count), dim3(64 * waves),
-                           lds, st, b);
+        if (mixed)
+            hipLaunchKernelGGL((panel_fwd_kernel<0, true>), dim3(pblocks, (unsigned)b.count), dim3(64 * waves),
+                               lds, st, b);
+        else
+            hipLaunchKernelGGL(panel_fwd_kernel<0>, dim3(pblocks, (unsigned)b.count), dim3(64 * waves), lds, st, b);
     }
     prof_after(4, st);
     MARL_LAUNCH_CHECK();
@@ -562,7 +599,8 @@ constexpr int kBwdMaxCols = kPanelMaxCols;  // columns per lane in the row pass:
 // MAXC: LayerNorm columns per lane the row pass is unrolled for (widths up to 64 * MAXC).  The chained
 // encoder / decoder backward of the README dimensions has widths <= 128: two column slots instead of six
 // are a third of the row pass's instructions and 24 fewer registers.
-template <bool CELL, int MAXC>
+// MIX: the agg_at site applies the transpose of a communication graph's mixing matrix (P.mix) instead of the mean
+template <bool CELL, int MAXC, bool MIX = false>
 __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (CELL && (int)blockIdx.x >= P.panel_blocks) {
@@ -631,6 +669,11 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                 pv[l][1] = P.layer[l].beta[tid];
             }
         }
+        float cmv = 0.f;  // M^T, oriented while it is loaded (row = the sender whose gradient is formed): requested
+        if (MIX && tid < P.g_na * P.g_na) {  // with the vectors above, stored behind them - one batch of loads
+            const int a = tid / P.g_na, a2 = tid - a * P.g_na;
+            cmv = P.mix[a2 * P.g_na + a];
+        }
         int off = 0;
 #pragma unroll
         for (int l = 0; l < kPanelMaxLayers; ++l) {
@@ -643,6 +686,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                 off += 2 * n;
             }
         }
+        if (MIX && tid < P.g_na * P.g_na) lds[P.off_mix + tid] = cmv;
         const int n = P.layer[0].n, ds = panel_stride(n), n16 = (n + 15) & ~15, c4 = n16 >> 2;
         const int n4 = (n + 3) & ~3;
         for (int e = tid; e < kPanelRows * c4; e += blockDim.x) {
@@ -710,7 +754,25 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e - lr * c4) * 4;
                     const int a = lr / bpb, i = lr - a * bpb;
-                    if (a < na && na > 1) {
+                    if (MIX) {
+                        // the mixing matrix is not self-adjoint: dm[a] = sum_a2 M[a2, a] * dmbar[a2] (the LDS copy
+                        // is M^T), one fmaf chain over a2 ascending, zero entries skipped
+                        if (a < na) {
+                            const float* crow = lds + P.off_mix + a * na;
+                            float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
+                            for (int a2 = 0; a2 < na; ++a2) {
+                                const float cf = crow[a2];
+                                if (cf != 0.f) {
+                                    const float4 q = *reinterpret_cast<const float4*>(D + (a2 * bpb + i) * ds + k);
+                                    sm.x = fmaf(cf, q.x, sm.x);
+                                    sm.y = fmaf(cf, q.y, sm.y);
+                                    sm.z = fmaf(cf, q.z, sm.z);
+                                    sm.w = fmaf(cf, q.w, sm.w);
+                                }
+                            }
+                            v[it] = sm;
+                        }
+                    } else if (a < na && na > 1) {
                         float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
                         for (int a2 = 0; a2 < na; ++a2) {
                             const float4 q = *reinterpret_cast<const float4*>(D + (a2 * bpb + i) * ds + k);
@@ -988,12 +1050,19 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
     p.off_colp = p.off_prm + prm + 16;
     p.off_part = p.off_colp + waves * 2 * nmax;
     p.off_rowmap = p.off_part + (waves - 1) * 512;
-    const size_t lds = (size_t)(p.off_rowmap + kPanelRows) * sizeof(float);
+    p.off_mix = p.off_rowmap + kPanelRows;  // (g_na^2 <= kPanelRows^2 floats; fits every plan use_chain admits, see forward)
+    if (p.mix && p.agg_at <= 0) {
+        set_error("panel backward: a mixing matrix needs the in-panel aggregation");
+        return MARL_ELIMIT;
+    }
+    const size_t lds = (size_t)(p.off_mix + (p.mix ? kPanelRows * kPanelRows : 0)) * sizeof(float);
     if (p.agg_at > 0 && (p.by_batch < 1 || p.g_na * p.by_batch > kPanelRows || p.agg_at >= p.nlayers ||
                          !panel_chain_supported(p.g_na, p.layer[p.agg_at].n, 256))) {
         set_error("panel backward: in-panel message mean outside its range");
         return MARL_ELIMIT;
     }
+    // (the matrix's 1 KiB could tip a plan that kept tail_lds without one into the retry below - same results, the
+    // final dX then leaves without the LDS tail; with n_b <= 384 under a matrix (use_chain) no admitted plan gets here)
     if (lds > kPanelMaxLds && tail_lds) {
         tail_lds = false;
         goto plan;
@@ -1004,10 +1073,14 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
     }
     static bool raised = false;
     if (!raised) {
-        const void* kerns[4] = {reinterpret_cast<const void*>(panel_bwd_kernel<false, 2>),
+        const void* kerns[8] = {reinterpret_cast<const void*>(panel_bwd_kernel<false, 2>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<true, 2>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols>)};
+                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<false, 2, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<true, 2, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols, true>)};
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
@@ -1026,7 +1099,22 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
     p.ts = rec ? d_ts : nullptr;
 #endif
     const int maxc = nmax <= 128 ? 2 : kBwdMaxCols;
-    if (p.has_cell) {
+    if (p.mix) {
+        const dim3 blk(64 * waves);
+        unsigned cblocks = 0;
+        if (p.has_cell) {
+            p.panel_blocks = (int)pblocks;
+            cblocks = (unsigned)cdiv(p.cell_rows * (p.cell_vec4 ? p.cell.n / 4 : p.cell.n), 64 * waves);
+        }
+        if (p.has_cell && maxc == 2)
+            hipLaunchKernelGGL((panel_bwd_kernel<true, 2, true>), dim3(pblocks + cblocks), blk, lds, st, p);
+        else if (p.has_cell)
+            hipLaunchKernelGGL((panel_bwd_kernel<true, kBwdMaxCols, true>), dim3(pblocks + cblocks), blk, lds, st, p);
+        else if (maxc == 2)
+            hipLaunchKernelGGL((panel_bwd_kernel<false, 2, true>), dim3(pblocks), blk, lds, st, p);
+        else
+            hipLaunchKernelGGL((panel_bwd_kernel<false, kBwdMaxCols, true>), dim3(pblocks), blk, lds, st, p);
+    } else if (p.has_cell) {
         p.panel_blocks = (int)pblocks;
         const unsigned cblocks = (unsigned)cdiv(p.cell_rows * (p.cell_vec4 ? p.cell.n / 4 : p.cell.n), 64 * waves);
         if (maxc == 2)

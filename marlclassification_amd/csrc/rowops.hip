@@ -1059,6 +1059,68 @@ int launch_agg_msg(const float* m, float* out, int ld, int na, int nb, int n, hi
 }
 
 // ---------------------------------------------------------------------------
+// message mixing over a communication graph: out[a, b, :] = sum_a' C[a, a'] * m[a', b, :] with C = M
+// (forward) or M^T (transpose: the gradient of the messages from the gradient of the aggregate).
+// One thread owns one (batch, column) over ALL agents and holds the na inputs in registers before it
+// writes any output, so out == m (in place) is legal.  fp32, one fmaf chain over a' ascending; an
+// entry that is exactly 0 is skipped, not multiplied (a non-neighbour's NaN / Inf cannot leak
+// through 0 * x).  The coefficients are staged once per workgroup into LDS, already oriented, and
+// read back as wave-uniform broadcasts.  No atomics: bit-reproducible.
+// ---------------------------------------------------------------------------
+template <int NA>
+__global__ __launch_bounds__(256) void mix_msg_kernel(const float* m, float* out, int ld, int na, int nb, int n,
+                                                      const float* __restrict__ mix, int transpose) {
+    __shared__ float coef[NA * NA];  // coef[a * na + a2]: weight of sender a2 in output row a
+    for (int e = threadIdx.x; e < na * na; e += blockDim.x) {
+        const int a = e / na, a2 = e - a * na;
+        coef[e] = transpose ? mix[a2 * na + a] : mix[e];
+    }
+    __syncthreads();
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)nb * n) return;
+    const int b = (int)(idx / n), k = (int)(idx % n);
+    const size_t astr = (size_t)nb * ld, o0 = (size_t)b * ld + k;
+    float v[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) v[a] = a < na ? m[o0 + (size_t)a * astr] : 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        if (a < na) {
+            float s = 0.f;
+#pragma unroll
+            for (int a2 = 0; a2 < NA; ++a2) {
+                if (a2 < na) {
+                    const float cf = coef[a * na + a2];
+                    if (cf != 0.f) s = fmaf(cf, v[a2], s);
+                }
+            }
+            out[o0 + (size_t)a * astr] = s;
+        }
+    }
+}
+
+int mix_msg_max_agents() { return 32; }
+
+int launch_mix_msg(const float* m, float* out, int ld, int na, int nb, int n, const float* mix, int transpose,
+                   hipStream_t st) {
+    if (!mix || na < 1 || na > mix_msg_max_agents() || n > ld) {
+        set_error("message mixing: %d agents / %d columns outside the kernel's range (<= %d agents)", na, n,
+                  mix_msg_max_agents());
+        return MARL_ELIMIT;
+    }
+    const int64_t tot = (int64_t)nb * n;
+    const dim3 grid((unsigned)cdiv(tot, 256)), blk(256);
+    if (na <= 8)
+        hipLaunchKernelGGL(mix_msg_kernel<8>, grid, blk, 0, st, m, out, ld, na, nb, n, mix, transpose);
+    else if (na <= 16)
+        hipLaunchKernelGGL(mix_msg_kernel<16>, grid, blk, 0, st, m, out, ld, na, nb, n, mix, transpose);
+    else
+        hipLaunchKernelGGL(mix_msg_kernel<32>, grid, blk, 0, st, m, out, ld, na, nb, n, mix, transpose);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
+// ---------------------------------------------------------------------------
 // map_pos (networks/state.py:14-16) on normalised positions (core/environment.py:74-81)
 // ---------------------------------------------------------------------------
 __global__ void pos_embed_fwd_kernel(const int32_t* __restrict__ pos,

@@ -205,10 +205,54 @@ class HipEngine:
         self._fwd_img: Optional[th.Tensor] = None
         self._fwd_key: Optional[Tuple] = None
         self._clip_scratch: Optional[th.Tensor] = None  # partial sums + the norm of grad_clip
+        # communication graph of the message exchange (comm.py): fp32 [Na, Na] on this device, None = the mean
+        # over the other agents.  The library's matrix is per-process state: it is installed around every call
+        # that aggregates and cleared behind it, so engines with different graphs never see each other's.
+        self.comm: Optional[th.Tensor] = None
+
+    # -- communication graph ----------------------------------------------------------
+    def set_comm(self, matrix: Optional[th.Tensor]) -> None:
+        """The mixing matrix of the message exchange (row = receiver, column = sender; ``comm.py`` builds the usual
+        graphs) for every later episode / step call of this engine; None restores the mean over the other agents.
+        Checked here, before anything is enqueued: fp32-convertible square finite matrix on the engine's device, at
+        most ``comm.MAX_AGENTS`` agents, and the configured number of agents if the engine is configured."""
+        if matrix is None:
+            self.comm = None
+            return
+        from . import comm as _comm
+
+        m = _comm.validate(matrix, None)
+        if m.device != self.device:
+            raise ValueError(f"communication matrix lives on {m.device}, the engine on {self.device}")
+        if self.cfg is not None and m.shape[0] != self.cfg.nb_agents:
+            raise ValueError(f"communication matrix is {tuple(m.shape)} but the engine is configured for "
+                             f"{self.cfg.nb_agents} agents")
+        self.comm = m.clone()  # (never the caller's storage)
+
+    def _agg(self, fn, *args) -> None:
+        """A library call that aggregates messages: under this engine's matrix, if it has one."""
+        m = self.comm
+        if m is None:
+            check(fn(*args))
+            return
+        check(self.lib.marl_comm_matrix(m.data_ptr(), m.shape[0]))
+        try:
+            check(fn(*args))
+        finally:
+            self.lib.marl_comm_matrix(None, 0)
+
+    def plan_query(self, key: str, train: bool = True) -> int:
+        """marl_plan_query under this engine's communication matrix."""
+        v = C.c_int(0)
+        self._agg(self.lib.marl_plan_query, C.byref(self.cfg), int(train), key.encode(), C.byref(v))
+        return v.value
 
     # -- configuration / workspaces -------------------------------------------------
     def configure(self, nb_agents: int, batch: int, nb_steps: int, img_shape: Sequence[int],
                   img_u8: bool = False) -> MarlConfig:
+        if self.comm is not None and self.comm.shape[0] != nb_agents:
+            raise ValueError(f"configure: {nb_agents} agents, but the communication matrix is "
+                             f"{tuple(self.comm.shape)} (set_comm(None) or a matrix of that size first)")
         key = (nb_agents, batch, nb_steps, tuple(img_shape), bool(img_u8))
         if key != self._cfg_key:
             c, h, w = img_shape
@@ -356,9 +400,9 @@ class HipEngine:
                 _ptr(counters), out.step_preds.data_ptr(), out.step_log_probas.data_ptr(), out.step_values.data_ptr(),
                 out.step_pos.data_ptr(), out.step_actions.data_ptr())
         if out.step_probs is None:
-            check(self.lib.marl_episode_forward(*head, int(train), _stream(dev)))
+            self._agg(self.lib.marl_episode_forward, *head, int(train), _stream(dev))
         else:
-            check(self.lib.marl_episode_forward_probs(*head, out.step_probs.data_ptr(), int(train), _stream(dev)))
+            self._agg(self.lib.marl_episode_forward_probs, *head, out.step_probs.data_ptr(), int(train), _stream(dev))
         if train and ws is None:  # (an episode with its own workspace does not touch the engine's)
             self.fwd_generation += 1
             self._fwd_img = img
@@ -412,12 +456,12 @@ class HipEngine:
             head = (C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews), image.data_ptr(),
                     _ptr(gp), _ptr(gl), _ptr(gv), self._table(grads))
             if g_probs is not None:
-                check(self.lib.marl_episode_backward_probs(*head, _ptr(d_img), g_probs.data_ptr(),
-                                                           _stream(self.device)))
+                self._agg(self.lib.marl_episode_backward_probs, *head, _ptr(d_img), g_probs.data_ptr(),
+                          _stream(self.device))
             elif d_img is None:
-                check(self.lib.marl_episode_backward(*head, _stream(self.device)))
+                self._agg(self.lib.marl_episode_backward, *head, _stream(self.device))
             else:
-                check(self.lib.marl_episode_backward_img(*head, d_img.data_ptr(), _stream(self.device)))
+                self._agg(self.lib.marl_episode_backward_img, *head, d_img.data_ptr(), _stream(self.device))
 
         if ws is not None:  # an episode that owns its workspace (autograd path)
             if getattr(ws, "_marl_key", None) != (self._cfg_key, _tune_epoch) or img is None:
@@ -650,10 +694,10 @@ class HipEngine:
             fn, ews = self.lib.marl_step_forward_train, ws
         else:
             fn, ews = self.lib.marl_step_forward, self.episode_ws(False)
-        check(fn(
-            C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews),
+        self._agg(
+            fn, C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews),
             *[t.data_ptr() for t in ins], *[t.data_ptr() for t in outs], _ptr(nz), seed & _U64,
-            offset & _U64, _ptr(act), _ptr(lp), _stream(dev)))
+            offset & _U64, _ptr(act), _ptr(lp), _stream(dev))
         return outs + extra
 
     def _check_ws(self, ws: th.Tensor, what: str) -> None:
@@ -685,9 +729,10 @@ class HipEngine:
         widths = (cfg.n_m, cfg.n_b, cfg.n_b, cfg.n_a, cfg.n_a)
         outs = tuple(th.empty(na, nb, n, device=dev) if w else None for n, w in zip(widths, want))
         wws = self.packed_weights_ws()
-        check(self.lib.marl_step_backward(
+        self._agg(
+            self.lib.marl_step_backward,
             C.byref(cfg), wws.data_ptr(), _nbytes(wws), ws.data_ptr(), _nbytes(ws), obs.data_ptr(),
-            *[_ptr(t) for t in ups], self._table(grads), *[_ptr(t) for t in outs], _stream(dev)))
+            *[_ptr(t) for t in ups], self._table(grads), *[_ptr(t) for t in outs], _stream(dev))
         return outs
 
     def draw_episode(self, seed: int, offset: int, with_noise: bool = False,

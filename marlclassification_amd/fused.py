@@ -232,7 +232,8 @@ class FusedA2C:
         # (the tune epoch: after engine.tune() the workspaces baked into a captured graph are freed /
         # re-laid-out - the graph must be captured again)
         beta = self.entropy_coef
-        key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch, beta)
+        key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch, beta,
+               None if eng.comm is None else eng.comm.data_ptr())  # (the captured kernels keep the matrix pointer)
         if self._graph is None or self._graph[0] != key:
             if self._graph is not None:
                 eng.lib.marl_graph_destroy(self._graph[1])

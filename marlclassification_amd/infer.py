@@ -35,6 +35,8 @@ def infer_main(main_config: MainConfig, infer_config: InferConfig) -> int:
     with open(infer_config.class_to_idx, "r", encoding="utf-8") as f:
         class_to_idx = json.load(f)
     marl_config = ModelConfig.load_marl_config(infer_config.json_path)
+    if infer_config.comm is not None:
+        marl_config.comm = infer_config.comm
     nn_models, marl_m, env = marl_config.build_marl(main_config.nb_agent)
     nn_models.load_state_dict(th.load(infer_config.state_dict_path, map_location="cpu"))
     nn_models.eval()

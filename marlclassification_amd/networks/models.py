@@ -72,6 +72,7 @@ class _StepFunction(th.autograd.Function):
         outs = eng.step_forward(obs, msg, norm_pos, h, c, hc, cc, noise, rng=rng, ws=lease.ws)
         ctx.eng, ctx.lease, ctx.obs = eng, lease, obs.contiguous()
         ctx.cfg_key = eng._cfg_key
+        ctx.comm = eng.comm  # the backward goes through the transpose of THIS step's matrix, whatever is set by then
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
         ctx.sampled = len(outs) == 10
@@ -93,14 +94,18 @@ class _StepFunction(th.autograd.Function):
             raise RuntimeError("the model's weights were modified (re-packed) after this step's forward: its "
                                "backward needs the weights the forward used - call backward before the "
                                "optimiser step")
-        if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
-            na, nb, ns, shape, u8 = ctx.cfg_key
-            eng.configure(na, nb, ns, shape, img_u8=u8)
-        g_logp = rest[1] if ctx.sampled else None
-        grads = {k: th.empty(p.shape, device=eng.device) for k, p in zip(ctx.names, params)}
-        want = ctx.needs_input_grad[6:11]
-        d_in = eng.step_backward(lease.ws, ctx.obs, grads, g_probs, g_logp, g_values, g_preds, g_msg, g_h,
-                                 g_c, g_hc, g_cc, want=want)
+        later_comm, eng.comm = eng.comm, ctx.comm
+        try:
+            if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
+                na, nb, ns, shape, u8 = ctx.cfg_key
+                eng.configure(na, nb, ns, shape, img_u8=u8)
+            g_logp = rest[1] if ctx.sampled else None
+            grads = {k: th.empty(p.shape, device=eng.device) for k, p in zip(ctx.names, params)}
+            want = ctx.needs_input_grad[6:11]
+            d_in = eng.step_backward(lease.ws, ctx.obs, grads, g_probs, g_logp, g_values, g_preds, g_msg, g_h,
+                                     g_c, g_hc, g_cc, want=want)
+        finally:
+            eng.comm = later_comm
         lease.release()
         return (None,) * 6 + d_in + tuple(grads[k] for k in ctx.names)
 
@@ -159,6 +164,31 @@ class ModelsWrapper(nn.Module):
         self.__flat: Optional[FlatParams] = None
         self.__engines: Dict[Tuple, HipEngine] = {}
         self.__packed_token: Dict[int, Tuple] = {}
+        # communication graph (comm.py), None = the reference's mean over the other agents.  Non-persistent: the
+        # state-dict keys stay the reference's; a buffer, so .to(device) moves it with the module.
+        self.register_buffer("comm_matrix", None, persistent=False)
+
+    # ---- communication graph -------------------------------------------------------------
+    @property
+    def comm(self) -> Optional[th.Tensor]:
+        """The mixing matrix of the message exchange ([Na, Na] fp32, row = receiver), or None (the mean)."""
+        return self.comm_matrix
+
+    def set_comm(self, matrix: Optional[th.Tensor]) -> None:
+        """Every later step / episode of this model (forward, MultiAgent.act, EpisodeSampler, Trainer) aggregates
+        messages with ``matrix`` ([Na, Na], row = receiver, column = sender; ``comm.ring`` ...); None restores the
+        mean over the other agents.  ValueError for a non-square / non-finite matrix, more agents than the
+        mixing kernel serves, or a matrix on another device than the model."""
+        if matrix is None:
+            self.comm_matrix = None
+            return
+        from .. import comm as _comm
+
+        m = _comm.validate(matrix, None)
+        if m.device != self.device:
+            raise ValueError(f"communication matrix lives on {m.device}, the model on {self.device}: "
+                             "move it first (matrix.to(model.device))")
+        self.comm_matrix = m.clone()  # (never the caller's storage)
 
     # ---- reference surface -------------------------------------------------------------
     @property
@@ -236,6 +266,7 @@ class ModelsWrapper(nn.Module):
         if eng is None:
             eng = HipEngine(self.model_spec(actions), dev)
             self.__engines[key] = eng
+        eng.comm = self.comm_matrix  # (checked by set_comm; moved with the module)
         return eng
 
     def flat_state(self) -> FlatParams:
