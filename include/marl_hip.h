@@ -255,8 +255,8 @@ int marl_backward_heads_event(void* hip_event);
  * row = receiver, column = sender; while it is installed (per-process state, NULL restores the mean over the other
  * agents) every episode / step entry aggregates
  *     mbar[a, b, :] = sum_a' M[a, a'] * m[a', b, :]
- * in fp32 as one fmaf chain over a' ascending, and its backward uses M^T in the same fixed order (no atomics; no
- * gradient with respect to M).  An entry that is exactly 0 is skipped, not multiplied: a non-neighbour's NaN / Inf
+ * in fp32 as one fmaf chain over a' ascending, and its backward uses M^T in the same fixed order (no atomics; the
+ * gradient with respect to M itself is marl_comm_grad's).  An entry that is exactly 0 is skipped, not multiplied: a non-neighbour's NaN / Inf
  * does not leak through 0 * x.  Self-loops, asymmetric and negative weights are legal; the caller checks that the
  * entries are finite.  The matrix is read when the kernels run, so it must stay alive and unchanged until the work
  * enqueued under it has finished; a captured graph keeps the pointer.  Under a matrix the chained panel launches
@@ -268,6 +268,31 @@ int marl_backward_heads_event(void* hip_event);
  * a plain panel launch / ahead of the GEMM path) and "panel_chain" report the form.  Returns MARL_ELIMIT for nb_agents above 32; an entry whose configuration has
  * another nb_agents returns MARL_EINVAL before anything is enqueued. */
 int marl_comm_matrix(const float* m_dev, int nb_agents);
+
+/* Gradient with respect to the mixing matrix (same ABI version: two added entries, nothing else moves).  It
+ * differentiates the aggregation above - networks/message.py:5-17 under the matrix of marl_comm_matrix - with respect
+ * to M: with torch ops in its place, M.requires_grad_() and loss.backward() fill M.grad with
+ *     d_comm[a, a'] = sum_t sum_b sum_k dmbar_t[a, b, k] * m_t[a', b, k],    dmbar_t = dZd1_t * W_dec0
+ * where m_t is the message step t aggregated and dZd1_t the gradient of the decoder's first linear layer - both are
+ * what a finished backward leaves in its workspace, so this entry runs right AFTER marl_episode_backward* (ws = the
+ * episode workspace, nb_steps = cfg->nb_steps) or marl_step_backward (ws = the step workspace, nb_steps = 1: the message
+ * is the caller's msg) on the same stream, before anything else writes that workspace, with the weights that backward
+ * used, and while a matrix of cfg->nb_agents is installed (its VALUES are not read: the node that calls this keeps the
+ * matrix of its own forward).  nb_steps is the step count of the workspace's layout; cfg->nb_steps is ignored.
+ * d_comm: fp32 [Na, Na], row = receiver, OVERWRITTEN.  DENSE: an entry of M that is exactly 0 still receives its sum -
+ * the zero-skipping above is a property of the forward values, not of this derivative - so a NaN / Inf message of a
+ * non-neighbour appears in ITS column of d_comm (and nowhere it did not appear before).
+ * Two launches: workgroups that each own a contiguous range of (t, b) pairs write one Na x Na partial into `scratch`
+ * (caller-owned, >= marl_comm_grad_scratch_bytes(cfg with that nb_steps); 0 = bad configuration), then a second kernel
+ * sums the partials in a fixed order with fp64 accumulators: no atomics, bit-reproducible run to run.  Serves every
+ * kernel family of the backward (chained / unchained panels, the GEMM + row-kernel path, the step entry).
+ * Errors, each before anything is enqueued: MARL_EINVAL - a null pointer, no matrix installed, or a matrix of another
+ * agent count; MARL_ESIZE - a workspace or the scratch too small; MARL_ELIMIT - more than 32 agents, or a decoder
+ * weight [2 n_m, n_m] that does not fit the kernel's 160 KiB of LDS next to the staged rows. */
+size_t marl_comm_grad_scratch_bytes(const marl_config* cfg);
+int marl_comm_grad(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes,
+                   const void* ws, size_t ws_bytes, int nb_steps, float* d_comm,
+                   void* scratch, size_t scratch_bytes, void* stream);
 
 /* Loss of Trainer.train_epoch (training/trainer.py:76-111; training/functions.py:7-55)
  * and its gradient w.r.t. the episode outputs in one pass.

@@ -83,6 +83,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="lambda of the generalised advantage estimate (1: the reference's full returns - values)")
     t.add_argument("--max-grad-norm", type=float, default=None, dest="max_grad_norm",
                    help="clip the global gradient norm to X before every Adam step (default: no clipping)")
+    t.add_argument("--learn-comm", action="store_true", dest="learn_comm",
+                   help="learn the communication graph: row-softmax weights over the support of --comm (default "
+                        "support: full), updated by their own Adam; every checkpoint epoch also writes "
+                        "models/comm_epoch_{e}.npy, which test / infer load with --comm FILE.npy")
+    t.add_argument("--comm-lr", type=float, default=None, dest="comm_lr", metavar="LR",
+                   help="learning rate of the graph's logits with --learn-comm (default: --lr)")
     for sp in (t, e, i):
         sp.add_argument("--comm", type=_comm_arg, default=None, dest="comm", metavar="GRAPH",
                         help="communication graph of the message exchange: full | none | ring[:k] | star[:hub] | "
@@ -98,12 +104,28 @@ def _comm_arg(text: str) -> str:
         raise argparse.ArgumentTypeError(str(err))
 
 
+def check_learn_comm(parser: argparse.ArgumentParser, args) -> None:
+    """--learn-comm needs a graph with at least one link (its support is fixed); --comm-lr needs --learn-comm."""
+    if args.main_choice != "train":
+        return
+    if args.comm_lr is not None and not args.learn_comm:
+        parser.error("--comm-lr needs --learn-comm")
+    if args.comm_lr is not None and not args.comm_lr > 0.0:
+        parser.error("--comm-lr must be > 0")
+    if args.learn_comm and args.comm == "none":
+        parser.error("--learn-comm needs a graph with links to learn on: --comm none has no support")
+
+
 def main(argv=None) -> None:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_learn_comm(parser, args)
     main_config = MainConfig(step=args.step, run_id=args.run_id, cuda=args.cuda, nb_agent=args.agents)
     if args.main_choice == "train":
         from .train import train_main
 
+        if args.learn_comm and args.comm is None:
+            args.comm = "full"  # (the default support)
         model_config = ModelConfig(
             ft_extr_str=args.ft_extr_str, window_size=args.f, hidden_size_belief=args.n_b,
             hidden_size_action=args.n_a, hidden_size_msg=args.n_m,
@@ -117,6 +139,7 @@ def main(argv=None) -> None:
             batch_size=args.batch_size, resources_dir=args.res_folder, output_dir=args.output_dir,
             gamma=args.gamma, entropy_coef=args.entropy_coef, ppo_epochs=args.ppo_epochs,
             ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, max_grad_norm=args.max_grad_norm,
+            learn_comm=args.learn_comm, comm_lr=args.comm_lr,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":

@@ -78,7 +78,8 @@ EXPORTS = (
     "marl_gemm_tn_images_cell marl_gemm_tn_images_cell_scratch marl_backward_heads_event "
     "marl_step_forward_train marl_step_backward marl_episode_backward_img "
     "marl_episode_forward_probs marl_episode_backward_probs marl_a2c_loss_entropy_fwd_bwd "
-    "marl_advantages marl_ppo_loss_fwd_bwd marl_grad_clip marl_comm_matrix"
+    "marl_advantages marl_ppo_loss_fwd_bwd marl_grad_clip marl_comm_matrix "
+    "marl_comm_grad marl_comm_grad_scratch_bytes"
 ).split()
 
 _lib: Optional[C.CDLL] = None
@@ -161,6 +162,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_plan_query.argtypes = [_cfgp, _i, C.c_char_p, C.POINTER(_i)]
     lib.marl_backward_heads_event.argtypes = [_vp]
     lib.marl_comm_matrix.argtypes = [_vp, _i]
+    lib.marl_comm_grad_scratch_bytes.restype = _sz
+    lib.marl_comm_grad_scratch_bytes.argtypes = [_cfgp]
+    lib.marl_comm_grad.argtypes = [_cfgp, _vp, _sz, _vp, _sz, _i, _vp, _vp, _sz, _vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("marl_abi_version", "marl_tune_get"):

@@ -15,6 +15,7 @@ import re
 from typing import Optional, Sequence, Union
 
 import torch as th
+from torch import nn
 
 MAX_AGENTS = 32  # what the mixing kernel serves (mix_msg_kernel holds every agent's input in registers)
 
@@ -170,3 +171,115 @@ def check_spelling(text: str) -> str:
 
 
 Graph = Union[str, th.Tensor, None]
+
+
+# ---- live sources: a matrix that is learned -------------------------------------------------------------------------
+def is_live(source) -> bool:
+    """Is ``source`` a LIVE matrix source for ``set_comm`` - a tensor that requires grad, a module or a callable that
+    returns the matrix - rather than a constant (which ``set_comm`` clones)?"""
+    if isinstance(source, th.Tensor):
+        return source.requires_grad
+    return callable(source)
+
+
+def evaluate(source, na: Optional[int], device) -> "tuple[th.Tensor, th.Tensor]":
+    """One evaluation of a live source: (the matrix as the source gave it - attached to its autograd graph when grad
+    mode is on -, its detached contiguous fp32 value, which is what the library reads).  Checks shape, dtype and
+    device only: a finiteness check would synchronise the host with the device on every forward."""
+    m = source if isinstance(source, th.Tensor) else source()
+    if not isinstance(m, th.Tensor):
+        raise TypeError(f"the communication source returned {type(m).__name__}, not a tensor")
+    if m.dim() != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
+        raise ValueError(f"communication matrix must be square [Na, Na], got shape {tuple(m.shape)}")
+    if na is not None and m.shape[0] != na:
+        raise ValueError(f"communication matrix is {tuple(m.shape)} but there are {na} agents")
+    if m.shape[0] > MAX_AGENTS:
+        raise ValueError(f"communication matrix for {m.shape[0]} agents: at most {MAX_AGENTS} are supported")
+    if not m.is_floating_point():
+        raise ValueError(f"a learnable communication matrix must be floating point, got {m.dtype}")
+    if device is not None and m.device != th.device(device):
+        raise ValueError(f"communication matrix lives on {m.device}, expected {th.device(device)}")
+    return m, m.detach().to(th.float32).contiguous()
+
+
+def leaves(source) -> "list[th.Tensor]":
+    """The tensors an optimiser updates behind a live source: the tensor itself, a module's parameters that require
+    grad, or what a callable's ``parameters()`` yields (a plain function has none to offer: [])."""
+    if isinstance(source, th.Tensor):
+        return [source] if source.requires_grad else []
+    params = getattr(source, "parameters", None)
+    if callable(params):
+        return [p for p in params() if p.requires_grad]
+    return []
+
+
+class LearnableComm(nn.Module):
+    """A learnable communication graph on a FIXED support: ``forward()`` is the row softmax of the logits over the
+    support, so every row with a neighbour stays a convex combination of its neighbours and entries off the support
+    are exact zeros - the mixing kernels keep skipping them and team isolation keeps holding bit for bit.  A row
+    without support is all zero.
+
+    ``init`` [Na, Na] (row = receiver): its entries on the support must be positive; the logits start at
+    ``log(init)`` there, so ``forward()`` at construction is the row-normalised ``init`` (``comm.ring(16)`` gives
+    ``comm.ring(16)``).  ``mask`` (bool [Na, Na], default ``init != 0``) is the support.  The logits' gradient off the
+    support is exactly 0.  ``model.set_comm(LearnableComm(comm.ring(16)).to(device))`` makes it the model's live
+    source; ``from_matrix`` / ``to_matrix`` are the checkpoint format (the matrix itself: ``--comm FILE.npy``)."""
+
+    def __init__(self, init, mask=None) -> None:
+        super().__init__()
+        m = validate(init, None).to(th.float64)
+        if mask is None:
+            support = m != 0
+        else:
+            support = th.as_tensor(mask)
+            if support.dtype != th.bool or tuple(support.shape) != tuple(m.shape):
+                raise ValueError(f"mask must be a bool tensor of shape {tuple(m.shape)}, got {support.dtype} "
+                                 f"{tuple(support.shape)}")
+            support = support.to(m.device)
+        if bool((m[support] <= 0).any()):
+            raise ValueError("LearnableComm: entries of init on the support must be positive (they are softmax "
+                             "weights: logits start at log(init))")
+        logits = th.where(support, m.clamp_min(1e-300).log(), th.zeros_like(m)).to(th.float32)
+        self.logits = nn.Parameter(logits)
+        self.register_buffer("support", support.clone())
+
+    @property
+    def nb_agents(self) -> int:
+        return self.logits.shape[0]
+
+    def forward(self) -> th.Tensor:
+        sup = self.support
+        z = self.logits.masked_fill(~sup, float("-inf"))
+        # (a row without support: shift by 0, exp(-inf) = 0, and the guarded denominator keeps it at 0 - no NaN in
+        # the value or in the gradient; masked_fill / where cut the gradient off the support to exactly 0;
+        # the shift is detached: the softmax does not depend on it
+        top = z.detach().amax(dim=1, keepdim=True)
+        top = th.where(th.isfinite(top), top, th.zeros_like(top))
+        e = th.where(sup, (z - top).exp(), th.zeros_like(z))
+        den = e.sum(dim=1, keepdim=True)
+        return e / th.where(den > 0, den, th.ones_like(den))
+
+    @classmethod
+    def from_matrix(cls, matrix, mask=None) -> "LearnableComm":
+        """From a stored matrix (``to_matrix`` / ``comm_epoch_{e}.npy``): same ``forward()``.  ``mask``: the stored
+        support (``to_mask``).  Without it the support is ``matrix != 0``, which loses a link whose weight underflowed
+        to exactly 0 in fp32; with it such a link stays on the support and restarts from the smallest positive
+        weight."""
+        if mask is None:
+            return cls(matrix)
+        m = validate(matrix, None)
+        support = th.as_tensor(mask).to(m.device)
+        if support.dtype != th.bool or tuple(support.shape) != tuple(m.shape):
+            raise ValueError(f"mask must be a bool tensor of shape {tuple(m.shape)}")
+        tiny = th.finfo(th.float32).tiny
+        return cls(th.where(support & (m == 0), th.full_like(m, tiny), m), support)
+
+    @th.no_grad()
+    def to_mask(self) -> th.Tensor:
+        """The support, on the CPU (bool [Na, Na]) - store it next to ``to_matrix()`` to reload with ``from_matrix``."""
+        return self.support.detach().to("cpu").clone()
+
+    @th.no_grad()
+    def to_matrix(self) -> th.Tensor:
+        """The current matrix, detached, on the CPU (fp32 [Na, Na]) - what ``--comm FILE.npy`` loads."""
+        return self.forward().detach().to("cpu", th.float32).contiguous()

@@ -97,6 +97,10 @@ class TrainConfig(BaseModel):
     ppo_clip: float = 0.2
     gae_lambda: float = 1.0
     max_grad_norm: Optional[float] = None
+    # --learn-comm: the communication graph is a comm.LearnableComm on the support of ModelConfig.comm (None: full)
+    # with its own Adam at comm_lr (None: learning_rate)
+    learn_comm: bool = False
+    comm_lr: Optional[float] = None
 
 
 class EvalConfig(BaseModel):

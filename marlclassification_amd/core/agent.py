@@ -66,10 +66,10 @@ class MultiAgent:
         else:
             noise = th.empty(na, nb, model.nb_action, device=observation.device).exponential_(1.0)
         state = (self.__last_msg, hid.h, hid.c, hid.h_caret, hid.c_caret)
-        if step_needs_graph(model, observation, norm_pos, *state):
+        if step_needs_graph(model, observation, norm_pos, *state, comm=eng.comm_live):
             named = list(model.named_parameters())
             probs, values, preds, msg, h, c, hc, cc, actions, logp = _StepFunction.apply(
-                eng, observation, norm_pos, noise, rng, tuple(k for k, _ in named), *state,
+                eng, observation, norm_pos, noise, rng, tuple(k for k, _ in named), eng.comm_live, *state,
                 *[p for _, p in named])
         else:
             probs, values, preds, msg, h, c, hc, cc, actions, logp = eng.step_forward(

@@ -46,11 +46,13 @@ class _EpisodeFunction(th.autograd.Function):
     """Autograd boundary around the fused episode: inputs are the image batch and the model parameters,
     outputs step_preds / step_log_probas / step_values (+ non-differentiable positions and actions) and, with
     ``probs``, the differentiable step_probs as a sixth output.  ``forced`` (int64 [Ns,Na,Nb] or None) replaces
-    the sampling (trajectory replay)."""
+    the sampling (trajectory replay).  ``comm``: the mixing matrix as a differentiable input - the engine's live
+    matrix (``HipEngine.comm_live``: its detached value is what the kernels read) or None; asked for, its gradient is
+    marl_comm_grad's, two launches behind the backward pass."""
 
     @staticmethod
     def forward(ctx, eng: HipEngine, img: th.Tensor, draws: EpisodeDraws, names, probs: bool,
-                forced: Optional[th.Tensor], *params):
+                forced: Optional[th.Tensor], comm: Optional[th.Tensor], *params):
         # every episode owns its saved activations (a training workspace from the engine's pool), so
         # several rollouts of one model can be alive at once and (loss1 + loss2).backward() works as
         # with the reference's autograd graph (reference core/episode.py:84)
@@ -60,6 +62,7 @@ class _EpisodeFunction(th.autograd.Function):
         ctx.eng, ctx.ws, ctx.img = eng, ws, img
         ctx.cfg_key = eng._cfg_key
         ctx.comm = eng.comm  # the backward goes through the transpose of THIS rollout's matrix, whatever is set by then
+        ctx.comm_dtype = None if comm is None else comm.dtype
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
         ctx.shapes = [p.shape for p in params]
@@ -86,15 +89,23 @@ class _EpisodeFunction(th.autograd.Function):
             # the image is a differentiable input (the reference's crop is a masked_select of it,
             # core/environment.py:95-126): asked for, its gradient comes out of the same backward pass
             d_img = th.empty(ctx.img.shape, device=eng.device) if ctx.needs_input_grad[1] else None
-            eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img,
-                                 g_probs=g_probs)
+            d_comm = None
+            if ctx.needs_input_grad[6]:  # (the matrix of THIS rollout sits in eng.comm for the call)
+                d_comm = th.empty(ctx.comm.shape, device=eng.device)
+            if d_comm is None:  # what this backward has always called
+                eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img,
+                                     g_probs=g_probs)
+            else:
+                eng.episode_backward(g_preds, g_logp, g_values, grads, ws=ctx.ws, img=ctx.img, d_img=d_img,
+                                     g_probs=g_probs, d_comm=d_comm)
+                d_comm = d_comm.to(ctx.comm_dtype)
         finally:
             eng.comm = later_comm
         eng.train_ws_release(ctx.ws)
         ctx.ws = None
         # (a frozen model: the parameter gradients are computed and dropped here)
-        return (None, d_img, None, None, None, None) + tuple(
-            grads[k] if need else None for k, need in zip(ctx.names, ctx.needs_input_grad[6:]))
+        return (None, d_img, None, None, None, None, d_comm) + tuple(
+            grads[k] if need else None for k, need in zip(ctx.names, ctx.needs_input_grad[7:]))
 
 
 class EpisodeSampler:
@@ -194,10 +205,12 @@ class EpisodeSampler:
         forced = None if replay is None else replay.actions.to(img.device)
         model = self.__agents.model
         want_probs = bool(self.return_probs)
-        if th.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in model.parameters())):
+        live = eng.comm_live  # (prepare() evaluated the model's live source, if it has one, for this forward)
+        if th.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in model.parameters()) or
+                                     (live is not None and live.requires_grad)):
             named = list(model.named_parameters())
             names = tuple(k for k, _ in named)
-            res = _EpisodeFunction.apply(eng, img, draws, names, want_probs, forced, *[p for _, p in named])
+            res = _EpisodeFunction.apply(eng, img, draws, names, want_probs, forced, live, *[p for _, p in named])
             preds, logp, values, pos, act = res[:5]
             probs = res[5] if want_probs else None
         else:

@@ -412,6 +412,12 @@ int launch_agg_msg(const float* m, float* out, int ld, int na, int nb, int n, hi
 int launch_mix_msg(const float* m, float* out, int ld, int na, int nb, int n, const float* mix, int transpose,
                    hipStream_t st);
 int mix_msg_max_agents();
+// gradient of the mixing matrix: out[a, a'] = sum over (t, b, k) of (dz_t * w)[a, b, k] * msg_t[a', b, k] for dz / msg
+// [steps * na * nb, ld] and the packed weight w [n2, ldw]; part: comm_grad_blocks(steps * nb) * na * na floats
+int comm_grad_blocks(int64_t pairs, int* per_out);
+int comm_grad_supported(int na, int n, int n2, int ldw);
+int launch_comm_grad(const float* dz, int lddz, const float* msg, int ldmsg, const float* w, int ldw, int na, int nb,
+                     int steps, int n2, int n, float* part, float* out, hipStream_t st);
 
 // map_pos (networks/state.py): lambda = SiLU(LN(W * (pos / size) + b)) -> out (ld ldo)
 // (npos_in != null: use these normalised positions [rows,2] instead of pos / size)

@@ -2324,6 +2324,60 @@ int marl_comm_matrix(const float* m_dev, int nb_agents) {
     return MARL_OK;
 }
 
+size_t marl_comm_grad_scratch_bytes(const marl_config* cfg) {
+    Dims d;
+    if (make_dims(cfg, d) != MARL_OK) return 0;
+    return (size_t)comm_grad_blocks((int64_t)d.ns * d.nb, nullptr) * d.na * d.na * sizeof(float);
+}
+
+int marl_comm_grad(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes, const void* ws,
+                   size_t ws_bytes, int nb_steps, float* d_comm, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!cfg || !d_comm || !scratch || !weights_ws || !ws) {
+        set_error("comm_grad: null argument");
+        return MARL_EINVAL;
+    }
+    if (!g_comm) {
+        set_error("comm_grad: no communication matrix installed (marl_comm_matrix)");
+        return MARL_EINVAL;
+    }
+    if (nb_steps < 1) {
+        set_error("comm_grad: %d steps", nb_steps);
+        return MARL_EINVAL;
+    }
+    marl_config lay = *cfg;  // the layout of the workspace the backward ran on: an episode's, or ONE step's
+    lay.nb_steps = nb_steps;
+    Dims d;
+    MARL_TRY(make_dims(&lay, d));
+    if (g_comm_na != d.na) {
+        set_error("communication matrix is %d x %d but the configuration has %d agents", g_comm_na, g_comm_na, d.na);
+        return MARL_EINVAL;
+    }
+    WLayout w;
+    make_wlayout(d, w);
+    ELayout e;
+    make_elayout(d, 1, e);
+    if (weights_ws_bytes < w.total * sizeof(float) || ws_bytes < e.total * sizeof(float)) {
+        set_error("comm_grad: workspace too small for the current configuration / tuning knobs: weights %zu of %zu "
+                  "bytes, episode %zu of %zu bytes", weights_ws_bytes, w.total * sizeof(float), ws_bytes,
+                  e.total * sizeof(float));
+        return MARL_ESIZE;
+    }
+    const size_t need = (size_t)comm_grad_blocks((int64_t)d.ns * d.nb, nullptr) * d.na * d.na * sizeof(float);
+    if (scratch_bytes < need) {
+        set_error("comm_grad: scratch of %zu bytes, %zu needed", scratch_bytes, need);
+        return MARL_ESIZE;
+    }
+    if (!comm_grad_supported(d.na, d.n_m, d.nm2, w.ldp[MARL_P_DEC_W0])) {
+        set_error("comm_grad: %d agents / message size %d outside the kernel's range", d.na, d.n_m);
+        return MARL_ELIMIT;
+    }
+    const float* W = static_cast<const float*>(weights_ws);
+    const float* E = static_cast<const float*>(ws);
+    return launch_comm_grad(E + e.DAD1, d.ld_nm2, E + e.MSG, d.ld_nm, W + w.wp[MARL_P_DEC_W0], w.ldp[MARL_P_DEC_W0],
+                            d.na, d.nb, d.ns, d.nm2, d.n_m, static_cast<float*>(scratch), d_comm,
+                            static_cast<hipStream_t>(stream));
+}
+
 int marl_draw_episode(const marl_config* cfg, uint64_t seed, uint64_t offset, const void* counters,
                       int64_t* pos0, float* h0, float* c0, float* hc0, float* cc0, float* noise,
                       void* stream) {

@@ -1121,6 +1121,174 @@ int launch_mix_msg(const float* m, float* out, int ld, int na, int nb, int n, co
 }
 
 // ---------------------------------------------------------------------------
+// gradient of the mixing matrix (the derivative of networks/message.py:5-17 under a matrix, with respect to it):
+//     dM[a, a'] = sum_t sum_b sum_k dmbar_t[a, b, k] * m_t[a', b, k],   dmbar_t = dZ_t * W
+// from what a finished backward keeps: dZ [steps * R, lddz] (rows t * R + a * nb + b), the gradient of the decoder's
+// first linear layer; m [steps * R, ldmsg], the messages that layer's aggregate was mixed from; W [n2, ldw] the
+// packed weight of that layer.  A workgroup owns a contiguous range of (t, b) pairs: W stays in LDS for all of them,
+// every pair stages its na rows of dZ and of m, forms the na x n product dZ * W in LDS (a thread owns a float4 of
+// columns of one row) and adds its na^2 dot products with the message rows to register accumulators (thread e and
+// e + 256, ... own entry e: up to four entries each at 32 agents).  One na^2 partial per workgroup, summed by
+// comm_grad_sum_kernel in a fixed order with fp64 accumulators: no atomics, bit-reproducible.  Dense: an entry of
+// M that is 0 still gets its sum (the zero-skipping of mix_msg_kernel is a property of the forward values).
+// ---------------------------------------------------------------------------
+constexpr int kCommGradThreads = 256;
+constexpr int kCommGradMaxBlocks = 1024;  // (48 KiB of LDS at the flagship shape: three workgroups per CU)
+constexpr size_t kCommGradMaxLds = 160 * 1024;
+
+struct CommGradLds {  // float offsets of the LDS regions (each a whole number of float4s)
+    size_t w, g, d, m, total;
+    int ldm;  // row stride of the staged messages: odd, so that the rows a' of one column hit different banks
+};
+static __host__ __device__ CommGradLds comm_grad_lds(int na, int n, int n2, int ldw) {
+    CommGradLds l;
+    auto r4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
+    l.ldm = n | 1;
+    l.w = 0;
+    l.g = l.w + r4((size_t)n2 * ldw);
+    l.d = l.g + r4((size_t)na * n2);
+    l.m = l.d + r4((size_t)na * ldw);
+    l.total = l.m + r4((size_t)na * l.ldm);
+    return l;
+}
+
+__global__ __launch_bounds__(kCommGradThreads) void comm_grad_kernel(
+    const float* __restrict__ dz, int lddz, const float* __restrict__ msg, int ldmsg, const float* __restrict__ w,
+    int ldw, int na, int nb, int n2, int n, int64_t pairs, int per, float* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) float cg_lds[];
+    const CommGradLds l = comm_grad_lds(na, n, n2, ldw);
+    float* Ws = cg_lds + l.w;
+    float* Gs = cg_lds + l.g;
+    float* Ds = cg_lds + l.d;
+    float* Ms = cg_lds + l.m;
+    const int tid = threadIdx.x, q = ldw >> 2, nn = na * na;
+    for (int e = tid; e < n2 * q; e += kCommGradThreads)
+        reinterpret_cast<float4*>(Ws)[e] = reinterpret_cast<const float4*>(w)[e];
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const int64_t p0 = (int64_t)blockIdx.x * per;
+    const int64_t p1 = p0 + per < pairs ? p0 + per : pairs;
+    const size_t R = (size_t)na * nb;
+    for (int64_t p = p0; p < p1; ++p) {
+        const size_t row0 = (size_t)(p / nb) * R + (size_t)(p % nb);  // row of agent 0; agent a: + a * nb
+        for (int e = tid; e < na * n2; e += kCommGradThreads) {
+            const int a = e / n2, j = e - a * n2;
+            Gs[e] = dz[(row0 + (size_t)a * nb) * lddz + j];
+        }
+        for (int e = tid; e < na * n; e += kCommGradThreads) {
+            const int a = e / n, k = e - a * n;
+            Ms[a * l.ldm + k] = msg[(row0 + (size_t)a * nb) * ldmsg + k];
+        }
+        __syncthreads();  // (also orders the staging of W ahead of the first product)
+        for (int it = tid; it < na * q; it += kCommGradThreads) {
+            const int a = it / q, k4 = it - a * q;
+            const float* gr = Gs + a * n2;
+            const float* wc = Ws + 4 * k4;
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+            for (int j = 0; j < n2; ++j) {
+                const float gv = gr[j];
+                const float4 wv = *reinterpret_cast<const float4*>(wc + (size_t)j * ldw);
+                s.x = fmaf(gv, wv.x, s.x);
+                s.y = fmaf(gv, wv.y, s.y);
+                s.z = fmaf(gv, wv.z, s.z);
+                s.w = fmaf(gv, wv.w, s.w);
+            }
+            *reinterpret_cast<float4*>(Ds + a * ldw + 4 * k4) = s;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + i * kCommGradThreads;
+            if (e < nn) {
+                const int a = e / na, a2 = e - a * na;
+                const float* dr = Ds + a * ldw;
+                const float* mr = Ms + a2 * l.ldm;
+                float s = 0.f;
+                for (int k = 0; k < n; ++k) s = fmaf(dr[k], mr[k], s);
+                acc[i] += s;
+            }
+        }
+        __syncthreads();  // the next pair's staging overwrites what this one read
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = tid + i * kCommGradThreads;
+        if (e < nn) part[(size_t)blockIdx.x * nn + e] = acc[i];
+    }
+}
+
+// Final sum: a workgroup owns 16 consecutive entries, thread (slice, entry) adds a contiguous range of the partials
+// in fp64 (the loads of a range are independent: issued eight at a time), then the 16 slices of an entry are added in
+// slice order.  The split is a function of (blocks) alone: same order, same bits, every run.
+constexpr int kCommSumEntries = 16, kCommSumSlices = kCommGradThreads / kCommSumEntries;
+__global__ __launch_bounds__(kCommGradThreads) void comm_grad_sum_kernel(const float* __restrict__ part, int blocks,
+                                                                         int nn, float* __restrict__ out) {
+    __shared__ double sl[kCommSumSlices][kCommSumEntries];
+    const int el = threadIdx.x % kCommSumEntries, slice = threadIdx.x / kCommSumEntries;
+    const int e = blockIdx.x * kCommSumEntries + el;
+    const int chunk = (blocks + kCommSumSlices - 1) / kCommSumSlices;
+    const int b0 = slice * chunk, b1 = b0 + chunk < blocks ? b0 + chunk : blocks;
+    double s = 0.0;
+    if (e < nn) {
+        int b = b0;
+        for (; b + 8 <= b1; b += 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(b + u) * nn + e];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += (double)v[u];
+        }
+        for (; b < b1; ++b) s += (double)part[(size_t)b * nn + e];
+    }
+    sl[slice][el] = s;
+    __syncthreads();
+    if (slice == 0 && e < nn) {
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < kCommSumSlices; ++q) t += sl[q][el];
+        out[e] = (float)t;
+    }
+}
+
+int comm_grad_max_agents() { return 32; }  // (four entries per thread)
+
+// workgroups (= partials) for this many (step, batch) pairs, and the pairs each of them owns
+int comm_grad_blocks(int64_t pairs, int* per_out) {
+    if (pairs < 1) pairs = 1;
+    const int64_t per = cdiv(pairs, (int64_t)kCommGradMaxBlocks);
+    if (per_out) *per_out = (int)per;
+    return (int)cdiv(pairs, per);
+}
+
+int comm_grad_supported(int na, int n, int n2, int ldw) {
+    return na >= 1 && na <= comm_grad_max_agents() && n >= 1 && n2 >= 1 && ldw >= n && (ldw & 3) == 0 &&
+           comm_grad_lds(na, n, n2, ldw).total * sizeof(float) <= kCommGradMaxLds;
+}
+
+int launch_comm_grad(const float* dz, int lddz, const float* msg, int ldmsg, const float* w, int ldw, int na, int nb,
+                     int steps, int n2, int n, float* part, float* out, hipStream_t st) {
+    if (!comm_grad_supported(na, n, n2, ldw) || n2 > lddz || n > ldmsg || nb < 1 || steps < 1) {
+        set_error("mixing-matrix gradient: %d agents, %d x %d decoder weight outside the kernel's range (<= %d agents, "
+                  "%zu bytes of LDS)", na, n2, n, comm_grad_max_agents(), kCommGradMaxLds);
+        return MARL_ELIMIT;
+    }
+    const size_t lds = comm_grad_lds(na, n, n2, ldw).total * sizeof(float);
+    if (lds > 64 * 1024)  // (the opt-in is per device and cheap: asked for at every such launch, no cached flag)
+        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(comm_grad_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCommGradMaxLds));
+    const int64_t pairs = (int64_t)steps * nb;
+    int per = 1;
+    const int blocks = comm_grad_blocks(pairs, &per);
+    hipLaunchKernelGGL(comm_grad_kernel, dim3((unsigned)blocks), dim3(kCommGradThreads), lds, st, dz, lddz, msg, ldmsg,
+                       w, ldw, na, nb, n2, n, pairs, per, part);
+    MARL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(comm_grad_sum_kernel, dim3((unsigned)cdiv(na * na, kCommSumEntries)), dim3(kCommGradThreads), 0, st,
+                       part, blocks, na * na, out);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
+// ---------------------------------------------------------------------------
 // map_pos (networks/state.py:14-16) on normalised positions (core/environment.py:74-81)
 // ---------------------------------------------------------------------------
 __global__ void pos_embed_fwd_kernel(const int32_t* __restrict__ pos,

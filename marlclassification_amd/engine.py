@@ -209,18 +209,33 @@ class HipEngine:
         # over the other agents.  The library's matrix is per-process state: it is installed around every call
         # that aggregates and cleared behind it, so engines with different graphs never see each other's.
         self.comm: Optional[th.Tensor] = None
+        # a LIVE source of that matrix (a tensor that requires grad, a module or a callable; held by reference):
+        # ``refresh_comm`` evaluates it - for every forward, by whoever starts one - into ``comm`` (the detached fp32
+        # value the library reads) and ``comm_live`` (the matrix as the source gave it, attached to its graph: what the
+        # autograd nodes take as their input and what a trainer calls ``backward(d_comm)`` on)
+        self.comm_source = None
+        self.comm_live: Optional[th.Tensor] = None
+        self._comm_scratch: Optional[th.Tensor] = None  # the partials of marl_comm_grad (pooled, grown on demand)
 
     # -- communication graph ----------------------------------------------------------
-    def set_comm(self, matrix: Optional[th.Tensor]) -> None:
+    def set_comm(self, matrix) -> None:
         """The mixing matrix of the message exchange (row = receiver, column = sender; ``comm.py`` builds the usual
         graphs) for every later episode / step call of this engine; None restores the mean over the other agents.
         Checked here, before anything is enqueued: fp32-convertible square finite matrix on the engine's device, at
-        most ``comm.MAX_AGENTS`` agents, and the configured number of agents if the engine is configured."""
+        most ``comm.MAX_AGENTS`` agents, and the configured number of agents if the engine is configured.
+        A tensor that requires grad, a module or a callable that returns the matrix is a LIVE source
+        (``comm.is_live``): kept by reference and evaluated by ``refresh_comm`` (shape, dtype and device are checked
+        at every evaluation; finiteness is not - that would synchronise)."""
+        from . import comm as _comm
+
+        self.comm_source = self.comm_live = None
         if matrix is None:
             self.comm = None
             return
-        from . import comm as _comm
-
+        if _comm.is_live(matrix):
+            self.comm_source = matrix
+            self.refresh_comm()
+            return
         m = _comm.validate(matrix, None)
         if m.device != self.device:
             raise ValueError(f"communication matrix lives on {m.device}, the engine on {self.device}")
@@ -228,6 +243,41 @@ class HipEngine:
             raise ValueError(f"communication matrix is {tuple(m.shape)} but the engine is configured for "
                              f"{self.cfg.nb_agents} agents")
         self.comm = m.clone()  # (never the caller's storage)
+
+    def refresh_comm(self) -> Optional[th.Tensor]:
+        """Evaluates the live source (if there is one) for the forward that is about to run: ``comm`` becomes its
+        detached fp32 value, ``comm_live`` the graph-attached matrix, which is also returned (None: constant / mean)."""
+        if self.comm_source is None:
+            self.comm_live = None
+            return None
+        from . import comm as _comm
+
+        # (the agent count is checked by configure() and, before anything is enqueued, by the library)
+        live, value = _comm.evaluate(self.comm_source, None, self.device)
+        self.comm, self.comm_live = value, live
+        return live
+
+    def comm_grad(self, ws: th.Tensor, nb_steps: int, d_comm: th.Tensor) -> th.Tensor:
+        """marl_comm_grad: the gradient with respect to the mixing matrix out of the workspace a backward just
+        finished on (``nb_steps`` = the steps of its layout: the episode's, 1 for a step workspace) into ``d_comm``
+        ([Na, Na] fp32, overwritten).  The partials' scratch is pooled by the engine."""
+        cfg = self.cfg
+        assert cfg is not None
+        if self.comm is None:
+            raise ValueError("comm_grad: the engine has no communication matrix (the mean has no matrix to learn)")
+        na = cfg.nb_agents
+        if (not isinstance(d_comm, th.Tensor) or tuple(d_comm.shape) != (na, na) or d_comm.dtype != th.float32 or
+                d_comm.device != self.device or not d_comm.is_contiguous()):
+            raise ValueError(f"comm_grad: d_comm must be a contiguous fp32 [{na}, {na}] tensor on {self.device}")
+        lay = MarlConfig.from_buffer_copy(cfg)
+        lay.nb_steps = nb_steps
+        need = self.lib.marl_comm_grad_scratch_bytes(C.byref(lay))
+        if self._comm_scratch is None or _nbytes(self._comm_scratch) < need:
+            self._comm_scratch = th.empty(need // 4 + 1, dtype=th.float32, device=self.device)
+        sc, wws = self._comm_scratch, self.packed_weights_ws()
+        self._agg(self.lib.marl_comm_grad, C.byref(cfg), wws.data_ptr(), _nbytes(wws), ws.data_ptr(), _nbytes(ws),
+                  int(nb_steps), d_comm.data_ptr(), sc.data_ptr(), _nbytes(sc), _stream(self.device))
+        return d_comm
 
     def _agg(self, fn, *args) -> None:
         """A library call that aggregates messages: under this engine's matrix, if it has one."""
@@ -428,6 +478,7 @@ class HipEngine:
         generation: Optional[int] = None,
         ws: Optional[th.Tensor] = None, img: Optional[th.Tensor] = None,
         d_img: Optional[th.Tensor] = None, g_probs: Optional[th.Tensor] = None,
+        d_comm: Optional[th.Tensor] = None,
     ) -> None:
         """Backward of the LAST training rollout.  `generation` (the value of
         ``fwd_generation`` right after that rollout) makes a stale call fail loudly: the saved
@@ -435,9 +486,13 @@ class HipEngine:
         ``d_img`` ([Nb,C,H,W] fp32, overwritten): also the gradient w.r.t. the image batch
         (marl_episode_backward_img); None: the plain entry, nothing extra is launched.
         ``g_probs`` ([Ns,Na,Nb,nA] fp32): dL/d(step_probs) (marl_episode_backward_probs, with or without ``d_img``);
-        None: the entries above, verbatim."""
+        None: the entries above, verbatim.
+        ``d_comm`` ([Na,Na] fp32, overwritten): also the gradient w.r.t. the mixing matrix (marl_comm_grad, two
+        launches behind the backward on the same workspace); None: nothing more is launched."""
         cfg = self.cfg
         assert cfg is not None
+        if d_comm is not None and self.comm is None:
+            raise ValueError("episode_backward(d_comm=...): the engine has no communication matrix")
         if g_probs is not None:
             want = (cfg.nb_steps, cfg.nb_agents, cfg.batch, cfg.nb_action)
             if not isinstance(g_probs, th.Tensor) or tuple(g_probs.shape) != want:
@@ -462,6 +517,8 @@ class HipEngine:
                 self._agg(self.lib.marl_episode_backward, *head, _stream(self.device))
             else:
                 self._agg(self.lib.marl_episode_backward_img, *head, d_img.data_ptr(), _stream(self.device))
+            if d_comm is not None:
+                self.comm_grad(ews, cfg.nb_steps, d_comm)
 
         if ws is not None:  # an episode that owns its workspace (autograd path)
             if getattr(ws, "_marl_key", None) != (self._cfg_key, _tune_epoch) or img is None:
@@ -713,14 +770,18 @@ class HipEngine:
         g_msg: Optional[th.Tensor] = None, g_h: Optional[th.Tensor] = None,
         g_c: Optional[th.Tensor] = None, g_hc: Optional[th.Tensor] = None,
         g_cc: Optional[th.Tensor] = None, want: Sequence[bool] = (True,) * 5,
+        d_comm: Optional[th.Tensor] = None,
     ) -> Tuple[Optional[th.Tensor], ...]:
         """marl_step_backward of the step whose activations ``ws`` holds (``step_forward(ws=ws)``).
         Upstream gradients may be None (zero); ``g_logp`` only if that forward sampled.  Writes the
         parameter gradients into ``grads`` (overwritten) and returns the input gradients
-        (d_msg, d_h, d_c, d_hc, d_cc) in [Na,Nb,..], None where ``want`` is False."""
+        (d_msg, d_h, d_c, d_hc, d_cc) in [Na,Nb,..], None where ``want`` is False.  ``d_comm`` ([Na,Na] fp32,
+        overwritten): also this step's gradient w.r.t. the mixing matrix (marl_comm_grad on the step workspace)."""
         cfg = self.cfg
         assert cfg is not None
         self._check_ws(ws, "step_backward")
+        if d_comm is not None and self.comm is None:
+            raise ValueError("step_backward(d_comm=...): the engine has no communication matrix")
         na, nb, dev = cfg.nb_agents, cfg.batch, self.device
         obs = _need(obs, th.float32, "obs")
         ups = [None if t is None else _need(t, th.float32, n) for t, n in (
@@ -733,6 +794,8 @@ class HipEngine:
             self.lib.marl_step_backward,
             C.byref(cfg), wws.data_ptr(), _nbytes(wws), ws.data_ptr(), _nbytes(ws), obs.data_ptr(),
             *[_ptr(t) for t in ups], self._table(grads), *[_ptr(t) for t in outs], _stream(dev))
+        if d_comm is not None:
+            self.comm_grad(ws, 1, d_comm)
         return outs
 
     def draw_episode(self, seed: int, offset: int, with_noise: bool = False,

@@ -10,7 +10,7 @@ all-reduce (parallel.py).  No host synchronisation happens inside ``iteration``.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch as th
 
@@ -118,6 +118,54 @@ def ppo_options_on(ppo_epochs: int, ppo_clip: float, gae_lambda: float, max_grad
     return ppo_epochs != 1 or ppo_clip != 0.2 or gae_lambda != 1.0 or max_grad_norm is not None
 
 
+class CommUpdate:
+    """The update of a LIVE communication source (``set_comm`` with a tensor that requires grad, a module or a
+    callable) next to the flat Adam step; ``Trainer`` and ``FusedA2C`` both run this when they are given a
+    ``comm_lr``.  Per update: the backward also writes ``d_comm`` (marl_comm_grad) into ``buffer()``; ``step``
+    sums it over the ranks with the collective the flat gradient took and applies the same scale (1 / world),
+    back-propagates it from the matrix the forward evaluated to the source's leaves (``matrix.backward(d_comm)``)
+    and steps a ``torch.optim.Adam`` over those leaves - a dozen tiny torch launches on Na^2 values.
+    ``max_grad_norm`` does not reach here: the global-norm clip covers the flat parameter buffer only."""
+
+    def __init__(self, source, leaves: Sequence[th.Tensor], lr: float) -> None:
+        if not lr > 0.0:
+            raise ValueError(f"comm_lr must be > 0 or None, got {lr}")
+        leaves = list(leaves)
+        if not leaves:
+            raise ValueError("comm_lr: the live communication source has no leaf that requires grad (a plain "
+                             "callable offers no parameters(): pass a module or a tensor)")
+        self.source = source
+        self.opt = th.optim.Adam(leaves, lr=lr)
+        self._d: Optional[th.Tensor] = None
+
+    def buffer(self, eng: HipEngine) -> th.Tensor:
+        na = eng.cfg.nb_agents
+        if self._d is None or self._d.shape[0] != na or self._d.device != eng.device:
+            self._d = th.empty(na, na, device=eng.device)
+        return self._d
+
+    def step(self, live: Optional[th.Tensor], allreduce, scale: float) -> None:
+        if live is None or not live.requires_grad:
+            raise RuntimeError("comm_lr: the communication source was evaluated without a graph (grad mode off, or a "
+                               "source that does not depend on its leaves): nothing to update")
+        d = self._d
+        if allreduce is not None:
+            allreduce(d)  # (sum over ranks; `scale` = what the flat gradient's collective returned)
+        self.opt.zero_grad(set_to_none=True)
+        live.backward((d if scale == 1.0 else d * scale).to(live.dtype))
+        self.opt.step()
+
+
+def comm_update_for(current: Optional[CommUpdate], source, leaves, comm_lr: Optional[float]) -> Optional[CommUpdate]:
+    """The ``CommUpdate`` of this iteration: None without a ``comm_lr`` or a live source (the caller then runs
+    today's sequence of calls, verbatim); the current one while the source is the same object; else a new one."""
+    if comm_lr is None or source is None:
+        return None
+    if current is not None and current.source is source:
+        return current
+    return CommUpdate(source, leaves(), comm_lr)
+
+
 def ppo_bufs_fit(bufs, out: EpisodeTensors, entropy: bool) -> bool:
     """Do the persistent ``HipEngine.new_ppo_bufs`` tensors match this episode?"""
     return (bufs is not None and len(bufs) == (8 if entropy else 7) and bufs[0].shape == out.step_preds.shape and
@@ -126,13 +174,17 @@ def ppo_bufs_fit(bufs, out: EpisodeTensors, entropy: bool) -> bool:
 
 def ppo_epochs_loop(eng: HipEngine, flat: "FlatParams", out: EpisodeTensors, y: th.Tensor, bufs, epochs: int,
                     clip: float, beta: float, lr: float, allreduce, max_grad_norm: Optional[float], gviews,
-                    replay: Callable[[], EpisodeTensors], repack: Callable[[], None]) -> Optional[th.Tensor]:
+                    replay: Callable[[], EpisodeTensors], repack: Callable[[], None],
+                    comm: Optional[CommUpdate] = None) -> Optional[th.Tensor]:
     """The K update epochs of one rollout ``out`` whose advantages already sit in ``bufs`` (``HipEngine.advantages``);
     ``Trainer`` and ``FusedA2C`` both run this.  Epoch k > 0 starts with ``replay()``: the stored trajectory (same
     draws, the rollout's actions forced) under the weights the last epoch packed.  Then ppo_loss -> backward (bucketed
     hooks as in the A2C step) -> all-reduce -> [grad_clip, after the all-reduce and its scale: every rank clips the
     same averaged gradient] -> Adam (``flat.step`` += 1) -> ``repack()``.  Returns the device scalar with the last
-    epoch's gradient norm (None without ``max_grad_norm``)."""
+    epoch's gradient norm (None without ``max_grad_norm``).  ``comm`` (a live communication source under a
+    ``comm_lr``): every epoch's backward also writes d_comm and the source's leaves take their Adam step after the flat
+    one; the source is evaluated again by every ``replay()``, so epoch k runs under the matrix epoch k - 1 produced.
+    The gradient-norm clip covers the flat buffer only."""
     gp, gl, gv, _, _, advn, ret = bufs[:7]
     gpr = bufs[7] if beta > 0 else None
     # the old log-probabilities are the rollout's own output tensor: a replay writes fresh outputs, so epoch 0 has
@@ -150,16 +202,21 @@ def ppo_epochs_loop(eng: HipEngine, flat: "FlatParams", out: EpisodeTensors, y: 
         if bucketed:
             allreduce.before_backward(eng)
         try:
-            eng.episode_backward(gp, gl, gv, gviews, g_probs=gpr)
+            if comm is None:
+                eng.episode_backward(gp, gl, gv, gviews, g_probs=gpr)
+            else:
+                eng.episode_backward(gp, gl, gv, gviews, g_probs=gpr, d_comm=comm.buffer(eng))
         finally:
             if bucketed:
                 allreduce.after_backward(eng)
-        scale = 1.0 if allreduce is None else allreduce(flat.grads)
+        scale = rank_scale = 1.0 if allreduce is None else allreduce(flat.grads)
         if max_grad_norm is not None:
             norm = eng.grad_clip(flat.grads, max_grad_norm, grad_scale=scale)
             scale = 1.0
         flat.step += 1
         eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, lr, grad_scale=scale)
+        if comm is not None:
+            comm.step(eng.comm_live, allreduce, rank_scale)
         repack()
     return norm
 
@@ -171,9 +228,20 @@ class FusedA2C:
                  allreduce: Optional[Callable[[th.Tensor], float]] = None,
                  use_graph: bool = False, entropy_coef: float = 0.0, ppo_epochs: int = 1,
                  ppo_clip: float = 0.2, gae_lambda: float = 1.0,
-                 max_grad_norm: Optional[float] = None) -> None:
+                 max_grad_norm: Optional[float] = None, comm_lr: Optional[float] = None) -> None:
+        """``comm_lr``: learning rate of the engine's LIVE communication source (``engine.set_comm`` with a tensor
+        that requires grad or a module such as ``comm.LearnableComm``): every update also takes d_comm out of the
+        backward and steps a ``torch.optim.Adam`` over the source's leaves (``CommUpdate``).  None, or a constant
+        matrix: today's sequence of calls, verbatim.  ``max_grad_norm`` keeps covering the flat buffer only."""
         if use_graph and allreduce is not None:
             raise ValueError("hipGraph replay covers the single-GPU iteration (no collective inside)")
+        if comm_lr is not None and not comm_lr > 0.0:
+            raise ValueError(f"comm_lr must be > 0 or None, got {comm_lr}")
+        if use_graph and comm_lr is not None and engine.comm_source is not None:
+            raise ValueError("hipGraph replay does not cover the update of a live communication source (torch "
+                             "launches between the captured calls): use_graph with comm_lr and a live source")
+        self.comm_lr = None if comm_lr is None else float(comm_lr)
+        self._comm_update: Optional[CommUpdate] = None
         if not entropy_coef >= 0.0:
             raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
         check_ppo_options(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
@@ -210,6 +278,8 @@ class FusedA2C:
                 forced_actions: Optional[th.Tensor] = None, probs: bool = False) -> EpisodeTensors:
         if self._packed_gen != self.engine.weights_token():  # never packed, or the workspace was re-laid-out
             self.pack()
+        if self.engine.comm_source is not None:  # a live matrix: evaluated once for this forward
+            self.engine.refresh_comm()
         return self.engine.episode_forward(img, draws.pos0, draws.h0, draws.c0, draws.hc0,
                                            draws.cc0, draws.noise, forced_actions, train,
                                            rng=draws.rng, probs=probs)
@@ -227,6 +297,9 @@ class FusedA2C:
         if self._ppo:
             raise ValueError("iteration_graph captures the one-update A2C iteration: ppo_epochs / ppo_clip / "
                              "gae_lambda / max_grad_norm must stay at their defaults")
+        if self.comm_lr is not None and eng.comm_source is not None:
+            raise ValueError("iteration_graph does not cover the update of a live communication source (torch "
+                             "launches between the captured calls): run iteration(), or drop comm_lr")
         from . import engine as _engine_mod
 
         # (the tune epoch: after engine.tune() the workspaces baked into a captured graph are freed /
@@ -308,10 +381,14 @@ class FusedA2C:
         gp, gl, gv, scalars = bufs[:4]
         gpr = bufs[5] if beta > 0 else None
         bucketed = hasattr(self.allreduce, "before_backward")
+        comm = self._comm()
         if bucketed:  # (two buckets: the heads' slice leaves while the reverse loop still runs)
             self.allreduce.before_backward(eng)
         try:
-            eng.episode_backward(gp, gl, gv, self._gviews, g_probs=gpr)
+            if comm is None:
+                eng.episode_backward(gp, gl, gv, self._gviews, g_probs=gpr)
+            else:
+                eng.episode_backward(gp, gl, gv, self._gviews, g_probs=gpr, d_comm=comm.buffer(eng))
         finally:
             if bucketed:
                 self.allreduce.after_backward(eng)
@@ -321,8 +398,17 @@ class FusedA2C:
         self.flat.step += 1
         eng.adam(self.flat.params, self.flat.grads, self.flat.exp_avg, self.flat.exp_avg_sq,
                  self.flat.step, self.lr, grad_scale=scale)
+        if comm is not None:
+            comm.step(eng.comm_live, self.allreduce, scale)
         self.pack()
         return out, scalars
+
+    def _comm(self) -> Optional[CommUpdate]:
+        from . import comm as _comm_mod
+
+        src = self.engine.comm_source
+        self._comm_update = comm_update_for(self._comm_update, src, lambda: _comm_mod.leaves(src), self.comm_lr)
+        return self._comm_update
 
     def _iteration_ppo(self, img: th.Tensor, y: th.Tensor, draws: EpisodeDraws) -> Tuple[EpisodeTensors, th.Tensor]:
         """One rollout, ``ppo_epochs`` updates; returns the rollout's outputs and the last epoch's scalars
@@ -338,7 +424,7 @@ class FusedA2C:
             eng, self.flat, out, y, bufs, self.ppo_epochs, self.ppo_clip, beta, self.lr, self.allreduce,
             self.max_grad_norm, self._gviews,
             replay=lambda: self.rollout(img, draws, True, forced_actions=out.step_actions, probs=ent),
-            repack=self.pack)
+            repack=self.pack, comm=self._comm())
         if norm is not None:
             self.last_grad_norm = norm
         return out, bufs[3]

@@ -44,10 +44,12 @@ class _StepLease:
             pass
 
 
-def step_needs_graph(model: nn.Module, obs: th.Tensor, norm_pos: th.Tensor, *state: th.Tensor) -> bool:
-    """A step becomes an autograd node when grad mode is on and a parameter or an input of the
-    recurrent state (msg, h, c, h^, c^) requires grad; otherwise it is the plain marl_step_forward
-    call.  An observation / position that requires grad is refused rather than silently cut."""
+def step_needs_graph(model: nn.Module, obs: th.Tensor, norm_pos: th.Tensor, *state: th.Tensor,
+                     comm: Optional[th.Tensor] = None) -> bool:
+    """A step becomes an autograd node when grad mode is on and a parameter, an input of the
+    recurrent state (msg, h, c, h^, c^) or the live mixing matrix ``comm`` requires grad; otherwise it is
+    the plain marl_step_forward call.  An observation / position that requires grad is refused rather than
+    silently cut."""
     if not th.is_grad_enabled():
         return False
     for t, n in ((obs, "observation"), (norm_pos, "norm_pos")):
@@ -56,16 +58,19 @@ def step_needs_graph(model: nn.Module, obs: th.Tensor, norm_pos: th.Tensor, *sta
                 f"the {n} requires grad: the HIP step has no gradient w.r.t. the observation or the "
                 "positions (the reference crops them from an image batch that does not require grad) - "
                 "pass it detached")
-    return any(p.requires_grad for p in model.parameters()) or any(t.requires_grad for t in state)
+    return (any(p.requires_grad for p in model.parameters()) or any(t.requires_grad for t in state) or
+            (comm is not None and comm.requires_grad))
 
 
 class _StepFunction(th.autograd.Function):
     """Autograd boundary around ONE step (ModelsWrapper.forward / MultiAgent.act): inputs msg, h, c,
     h^, c^ and the model parameters; outputs probs, values, preds, msg, h, c, h^, c^ (+ the
-    non-differentiable actions and their log-probabilities when the step samples)."""
+    non-differentiable actions and their log-probabilities when the step samples).  ``comm``: the mixing matrix as
+    a differentiable input (the engine's live matrix, or None); asked for, its gradient is marl_comm_grad's on the
+    step workspace, where the message is this step's ``msg``."""
 
     @staticmethod
-    def forward(ctx, eng: HipEngine, obs, norm_pos, noise, rng, names, msg, h, c, hc, cc, *params):
+    def forward(ctx, eng: HipEngine, obs, norm_pos, noise, rng, names, comm, msg, h, c, hc, cc, *params):
         # every live step owns its saved activations (a one-step training workspace from the engine's
         # pool): an unrolled loop keeps one per step until backward, as the reference's graph does
         lease = _StepLease(eng)
@@ -73,6 +78,7 @@ class _StepFunction(th.autograd.Function):
         ctx.eng, ctx.lease, ctx.obs = eng, lease, obs.contiguous()
         ctx.cfg_key = eng._cfg_key
         ctx.comm = eng.comm  # the backward goes through the transpose of THIS step's matrix, whatever is set by then
+        ctx.comm_dtype = None if comm is None else comm.dtype
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
         ctx.sampled = len(outs) == 10
@@ -101,13 +107,20 @@ class _StepFunction(th.autograd.Function):
                 eng.configure(na, nb, ns, shape, img_u8=u8)
             g_logp = rest[1] if ctx.sampled else None
             grads = {k: th.empty(p.shape, device=eng.device) for k, p in zip(ctx.names, params)}
-            want = ctx.needs_input_grad[6:11]
-            d_in = eng.step_backward(lease.ws, ctx.obs, grads, g_probs, g_logp, g_values, g_preds, g_msg, g_h,
-                                     g_c, g_hc, g_cc, want=want)
+            want = ctx.needs_input_grad[7:12]
+            d_comm = None
+            if ctx.needs_input_grad[6]:
+                d_comm = th.empty(ctx.comm.shape, device=eng.device)
+                d_in = eng.step_backward(lease.ws, ctx.obs, grads, g_probs, g_logp, g_values, g_preds, g_msg, g_h,
+                                         g_c, g_hc, g_cc, want=want, d_comm=d_comm)
+                d_comm = d_comm.to(ctx.comm_dtype)
+            else:  # what this backward has always called
+                d_in = eng.step_backward(lease.ws, ctx.obs, grads, g_probs, g_logp, g_values, g_preds, g_msg, g_h,
+                                         g_c, g_hc, g_cc, want=want)
         finally:
             eng.comm = later_comm
         lease.release()
-        return (None,) * 6 + d_in + tuple(grads[k] for k in ctx.names)
+        return (None,) * 6 + (d_comm,) + d_in + tuple(grads[k] for k in ctx.names)
 
 
 @dataclass
@@ -167,23 +180,63 @@ class ModelsWrapper(nn.Module):
         # communication graph (comm.py), None = the reference's mean over the other agents.  Non-persistent: the
         # state-dict keys stay the reference's; a buffer, so .to(device) moves it with the module.
         self.register_buffer("comm_matrix", None, persistent=False)
+        # a LIVE source of the matrix (set_comm with a tensor that requires grad, a module or a callable): held by
+        # reference inside a tuple, so that nn.Module registers nothing - no state-dict key, no entry in
+        # parameters() / FlatParams; () = none
+        self.__comm_source: Tuple = ()
 
     # ---- communication graph -------------------------------------------------------------
     @property
     def comm(self) -> Optional[th.Tensor]:
-        """The mixing matrix of the message exchange ([Na, Na] fp32, row = receiver), or None (the mean)."""
+        """The mixing matrix of the message exchange ([Na, Na] fp32, row = receiver), or None (the mean).  Under a
+        live source: its current value, detached (evaluated here, without a graph)."""
+        if self.__comm_source:
+            from .. import comm as _comm
+
+            with th.no_grad():
+                return _comm.evaluate(self.__comm_source[0], None, self.device)[1]
         return self.comm_matrix
 
-    def set_comm(self, matrix: Optional[th.Tensor]) -> None:
+    @property
+    def comm_source(self):
+        """The live source ``set_comm`` was given, or None (a constant matrix / the mean)."""
+        return self.__comm_source[0] if self.__comm_source else None
+
+    def comm_parameters(self) -> List[th.Tensor]:
+        """The leaves behind the live source - what an optimiser of the graph updates (``Trainer(comm_lr=...)``
+        builds its Adam on them); [] without a live source.  They are not in ``parameters()`` / ``state_dict()``."""
+        if not self.__comm_source:
+            return []
+        from .. import comm as _comm
+
+        return _comm.leaves(self.__comm_source[0])
+
+    def set_comm(self, matrix) -> None:
         """Every later step / episode of this model (forward, MultiAgent.act, EpisodeSampler, Trainer) aggregates
         messages with ``matrix`` ([Na, Na], row = receiver, column = sender; ``comm.ring`` ...); None restores the
         mean over the other agents.  ValueError for a non-square / non-finite matrix, more agents than the
-        mixing kernel serves, or a matrix on another device than the model."""
+        mixing kernel serves, or a matrix on another device than the model.
+
+        A tensor that does not require grad is cloned: a constant.  A tensor that requires grad, a module
+        (``comm.LearnableComm``) or a callable that returns the matrix is a LIVE source: held by reference, evaluated
+        every time a forward fetches the engine - once per episode, once per ``forward`` / ``act`` call, twice for the
+        first rollout of a PPO update - (shape, dtype and device are checked then; finiteness is not - it would synchronise the host),
+        its detached fp32 value goes to the kernels, and the episode / step autograd nodes take the evaluated matrix
+        as a differentiable input: ``loss.backward()`` reaches the source's leaves (``comm_parameters()``) as it
+        would through torch ops.  The source is not registered: state-dict keys stay the reference's, and it does
+        not move with ``.to(device)`` - keep it on the model's device."""
+        from .. import comm as _comm
+
+        self.__comm_source = ()
         if matrix is None:
             self.comm_matrix = None
             return
-        from .. import comm as _comm
-
+        if _comm.is_live(matrix):
+            with th.no_grad():
+                _comm.evaluate(matrix, None, self.device)  # (a source of the wrong shape / device fails here)
+            self.comm_matrix = None
+            self.__comm_source = (matrix,)
+            return
         m = _comm.validate(matrix, None)
         if m.device != self.device:
             raise ValueError(f"communication matrix lives on {m.device}, the model on {self.device}: "
@@ -234,10 +287,10 @@ class ModelsWrapper(nn.Module):
         self.ensure_packed(eng)
         rh = recurrent_hidden
         state = (msg_t, rh.h, rh.c, rh.h_caret, rh.c_caret)
-        if step_needs_graph(self, img_patch, norm_pos, *state):
+        if step_needs_graph(self, img_patch, norm_pos, *state, comm=eng.comm_live):
             named = list(self.named_parameters())
             probs, values, preds, msg, h, c, hc, cc = _StepFunction.apply(
-                eng, img_patch, norm_pos, None, None, tuple(k for k, _ in named), *state,
+                eng, img_patch, norm_pos, None, None, tuple(k for k, _ in named), eng.comm_live, *state,
                 *[p for _, p in named])
         else:
             probs, values, preds, msg, h, c, hc, cc = eng.step_forward(
@@ -266,7 +319,12 @@ class ModelsWrapper(nn.Module):
         if eng is None:
             eng = HipEngine(self.model_spec(actions), dev)
             self.__engines[key] = eng
-        eng.comm = self.comm_matrix  # (checked by set_comm; moved with the module)
+        if self.__comm_source:  # a live source: evaluated here, at every fetch (a step of an act loop is a forward)
+            eng.comm_source = self.__comm_source[0]
+            eng.refresh_comm()
+        else:
+            eng.comm_source = eng.comm_live = None
+            eng.comm = self.comm_matrix  # (checked by set_comm; moved with the module)
         return eng
 
     def flat_state(self) -> FlatParams:

@@ -165,6 +165,17 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         with open(join(output_dir, "class_to_idx.json"), "w", encoding="utf-8") as f:
             json.dump(dataset.class_to_idx, f)
     nn_models.to(device)
+    learned = None
+    if train_config.learn_comm:
+        # the graph is learned: row-softmax weights over the support of --comm (deterministic initial logits:
+        # identical on every rank, and d_comm is averaged over the ranks, so they stay identical)
+        from . import comm as _comm
+
+        init = _comm.parse(model_config.comm or "full", main_config.nb_agent)
+        if not bool((init != 0).any()):
+            raise ValueError(f'--learn-comm: the graph "{model_config.comm}" has no link to learn on')
+        learned = _comm.LearnableComm(init).to(device)
+        nn_models.set_comm(learned)
     if distributed:  # identical initial weights on every rank
         for p in nn_models.parameters():
             dist.broadcast(p.data, src=0)
@@ -198,10 +209,13 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
                                                exact_standardize else None),
                       entropy_coef=train_config.entropy_coef, ppo_epochs=train_config.ppo_epochs,
                       ppo_clip=train_config.ppo_clip, gae_lambda=train_config.gae_lambda,
-                      max_grad_norm=train_config.max_grad_norm)
+                      max_grad_norm=train_config.max_grad_norm,
+                      comm_lr=((train_config.comm_lr if train_config.comm_lr is not None else
+                                train_config.learning_rate) if learned is not None else None))
     if rank == 0:
         print("update: " + ", ".join(f"{k}={getattr(train_config, k)}" for k in (
-            "entropy_coef", "ppo_epochs", "ppo_clip", "gae_lambda", "max_grad_norm")), flush=True)
+            "entropy_coef", "ppo_epochs", "ppo_clip", "gae_lambda", "max_grad_norm")) +
+              (f", learn_comm on {model_config.comm or 'full'}" if learned is not None else ""), flush=True)
     for e in range(train_config.nb_epoch):
         for bs in samplers:
             bs.set_epoch(e)
@@ -216,6 +230,10 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
             print(f"epoch {e}: " + ", ".join(f"{k}={v:.4f}" for k, v in m.items()), flush=True)
             conf.save_conf_matrix(e, output_dir, "eval")  # reference train.py:134
             th.save(nn_models.state_dict(), join(model_dir, f"nn_models_epoch_{e}.pt"))
+            if learned is not None:  # the learned matrix: `test` / `infer` load it with --comm FILE.npy
+                import numpy as np
+
+                np.save(join(model_dir, f"comm_epoch_{e}.npy"), learned.to_matrix().numpy())
     if rank == 0 and len(idx) > cut:
         # one evaluation image, step by step (reference train.py:149-166): frames + GIF in output_dir
         from .visualization import visualize_steps

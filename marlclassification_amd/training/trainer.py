@@ -16,7 +16,7 @@ import torch as th
 
 from ..core import EpisodeSampler
 from ..engine import EpisodeTensors
-from ..fused import check_ppo_options, ppo_bufs_fit, ppo_epochs_loop, ppo_options_on
+from ..fused import CommUpdate, check_ppo_options, comm_update_for, ppo_bufs_fit, ppo_epochs_loop, ppo_options_on
 from ..metrics import ConfusionMeter, LossMeter
 from ..networks import ModelsWrapper
 
@@ -40,10 +40,23 @@ class Trainer:
         ppo_clip: float = 0.2,
         gae_lambda: float = 1.0,
         max_grad_norm: Optional[float] = None,
+        comm_lr: Optional[float] = None,
     ) -> None:
+        """``comm_lr``: learning rate of the model's LIVE communication source (``model.set_comm`` with a tensor that
+        requires grad, a module such as ``comm.LearnableComm`` or a callable with ``parameters()``).  Each update then
+        evaluates the source, rolls out, takes the loss, runs the backward WITH d_comm (marl_comm_grad), sums d_comm
+        over the ranks with the scale the flat gradient gets, calls ``matrix.backward(d_comm)`` and steps a
+        ``torch.optim.Adam(model.comm_parameters(), lr=comm_lr)`` - in all three ``train_step`` paths and in every PPO
+        epoch (the source is evaluated again before every replay).  None, or a constant matrix: today's sequence of
+        calls, verbatim.  ``max_grad_norm`` keeps covering the flat parameter buffer only: the graph's leaves are
+        not part of the clipped norm."""
         if not entropy_coef >= 0.0:
             raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
         check_ppo_options(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
+        if comm_lr is not None and not comm_lr > 0.0:
+            raise ValueError(f"comm_lr must be > 0 or None, got {comm_lr}")
+        self.__comm_lr = None if comm_lr is None else float(comm_lr)
+        self.__comm_update: Optional[CommUpdate] = None
         self.__model = model
         self.__nb_class = nb_class
         self.__lr = learning_rate
@@ -80,6 +93,36 @@ class Trainer:
     def curr_step(self) -> int:
         return self.__curr_step
 
+    def __comm(self) -> Optional[CommUpdate]:
+        """The update of the model's live communication source for this step (None: no ``comm_lr`` or no live source)."""
+        model = self.__model
+        self.__comm_update = comm_update_for(self.__comm_update, model.comm_source, model.comm_parameters,
+                                             self.__comm_lr)
+        return self.__comm_update
+
+    def __backward_and_adam(self, eng, flat, gp, gl, gv, g_probs=None) -> None:
+        """backward -> [all-reduce] -> Adam -> re-pack of the A2C steps.  Under a live communication source with a
+        ``comm_lr`` the backward also writes d_comm and the source's leaves take their Adam step after the flat one;
+        otherwise the calls are the ones this step has always made."""
+        comm = self.__comm()
+        bucketed = hasattr(self.__allreduce, "before_backward")  # parallel.BucketedGradAllReduce
+        if bucketed:
+            self.__allreduce.before_backward(eng)
+        try:
+            if comm is None:
+                eng.episode_backward(gp, gl, gv, flat.grad_views(), g_probs=g_probs)
+            else:
+                eng.episode_backward(gp, gl, gv, flat.grad_views(), g_probs=g_probs, d_comm=comm.buffer(eng))
+        finally:
+            if bucketed:
+                self.__allreduce.after_backward(eng)
+        scale = 1.0 if self.__allreduce is None else self.__allreduce(flat.grads)
+        flat.step += 1
+        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, self.__lr, grad_scale=scale)
+        if comm is not None:
+            comm.step(eng.comm_live, self.__allreduce, scale)
+        self.__model.mark_updated(eng)
+
     # one optimisation step on a batch (reference trainer.py:67-116)
     def train_step(self, x: th.Tensor, y: th.Tensor, sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
         model = self.__model
@@ -104,20 +147,7 @@ class Trainer:
             _, _, _, _, stats = eng.a2c_loss(out, y, self.__gamma, 1, self.__loss_bufs)
             allreduce_adv_stats(stats, self.__exact_group)
             gp, gl, gv, scalars, _ = eng.a2c_loss(out, y, self.__gamma, 2, self.__loss_bufs)
-        flat = model.flat_state()
-        bucketed = hasattr(self.__allreduce, "before_backward")  # parallel.BucketedGradAllReduce
-        if bucketed:
-            self.__allreduce.before_backward(eng)
-        try:
-            eng.episode_backward(gp, gl, gv, flat.grad_views())
-        finally:
-            if bucketed:
-                self.__allreduce.after_backward(eng)
-        scale = 1.0 if self.__allreduce is None else self.__allreduce(flat.grads)
-        flat.step += 1
-        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, self.__lr,
-                 grad_scale=scale)
-        model.mark_updated(eng)
+        self.__backward_and_adam(eng, model.flat_state(), gp, gl, gv)
         return out, scalars
 
     def __train_step_entropy(self, x: th.Tensor, y: th.Tensor,
@@ -137,20 +167,7 @@ class Trainer:
             stats = eng.a2c_loss(out, y, gamma, 1, self.__loss_bufs, entropy_coef=beta)[4]
             allreduce_adv_stats(stats, self.__exact_group)
             gp, gl, gv, scalars, _, gpr = eng.a2c_loss(out, y, gamma, 2, self.__loss_bufs, entropy_coef=beta)
-        flat = model.flat_state()
-        bucketed = hasattr(self.__allreduce, "before_backward")
-        if bucketed:
-            self.__allreduce.before_backward(eng)
-        try:
-            eng.episode_backward(gp, gl, gv, flat.grad_views(), g_probs=gpr)
-        finally:
-            if bucketed:
-                self.__allreduce.after_backward(eng)
-        scale = 1.0 if self.__allreduce is None else self.__allreduce(flat.grads)
-        flat.step += 1
-        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, self.__lr,
-                 grad_scale=scale)
-        model.mark_updated(eng)
+        self.__backward_and_adam(eng, model.flat_state(), gp, gl, gv, g_probs=gpr)
         return out, scalars
 
     def __train_step_ppo(self, x: th.Tensor, y: th.Tensor,
@@ -180,7 +197,7 @@ class Trainer:
             self.__max_grad_norm, flat.grad_views(),
             replay=lambda: sampler.run_episode_raw(img, train=True, draws=draws, probs=ent,
                                                    forced=out.step_actions)[1],
-            repack=lambda: model.mark_updated(eng))
+            repack=lambda: model.mark_updated(eng), comm=self.__comm())
         if norm is not None:
             self.__grad_norm = norm
         return out, bufs[3]
