@@ -537,8 +537,10 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
  * "g3_lstm" = the fused LSTM launch does, "lstm_plan" = the tile plan that launch takes (the launcher's own rule: 2 =
  * 128-row tiles, 3 / 4 = the gate-split small-batch plans, 1 / 5 / 6 by knob), "small_r" = lstm_plan is 3 or 4,
  * "g3_tn_cell" = both weight gradients of an LSTM cell come from one launch, "g3_tn_pipe" = the row contractions run
- * the phase-pipelined step, "wgrad3" = conv weight gradients (cin >= 16) on the bf16 pipe.  *value = 0 / 1 (a plan
- * number for "lstm_plan"). */
+ * the phase-pipelined step, "wgrad3" = conv weight gradients (cin >= 16) on the bf16 pipe, "panel_sample" = the episode
+ * forward samples step t's actions inside the chained panel launch, as the epilogue of its policy workgroups (no
+ * sample_kernel launch; at most four actions; MARL_PANEL_SAMPLE=0 in the environment, read once, restores the
+ * separate launch - same results bit for bit).  *value = 0 / 1 (a plan number for "lstm_plan"). */
 int marl_plan_query(const marl_config* cfg, int train, const char* key, int* value);
 
 #ifdef __cplusplus

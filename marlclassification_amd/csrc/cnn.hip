@@ -114,25 +114,28 @@ int launch_obs_im2col(const float* obs, float* cols, int ldk, int64_t rows, int 
 // ---------------------------------------------------------------------------
 #ifdef MARL_KERNEL_TS
 int ts_begin(long long** dev, int call) {
-    if (!*dev) (void)hipMalloc(dev, 16 * 48 * sizeof(long long));
+    constexpr size_t bytes = (size_t)kTsRoles * kTsWaves * kTsSlots * sizeof(long long);
+    if (!*dev) (void)hipMalloc(dev, bytes);
     const char* e = getenv("MARL_TS_CALL");
     const int want = e ? atoi(e) : 100;
     if (call != want) return 0;
-    (void)hipMemset(*dev, 0, 16 * 48 * sizeof(long long));
+    (void)hipMemset(*dev, 0, bytes);
     return 1;
 }
-void ts_report(const char* tag, long long* dev, int waves) {
-    static long long h[16 * 48];
+void ts_report(const char* tag, long long* dev, int waves, int role) {
+    static long long h[kTsRoles * kTsWaves * kTsSlots];
     (void)hipMemcpy(h, dev, sizeof(h), hipMemcpyDeviceToHost);
+    const long long t00 = h[0];  // first stamp of role 0, wave 0
     for (int w = 0; w < waves; w += (waves > 1 ? waves - 1 : 1)) {
-        const long long* t = h + w * 48;
+        const long long* t = h + (role * kTsWaves + w) * kTsSlots;
         fprintf(stderr, "[ts] %s wave %d/%d:", tag, w, waves);
         long long tot = 0;
-        for (int i = 1; i < 48 && t[i]; ++i) {
+        for (int i = 1; i < kTsSlots && t[i]; ++i) {
             fprintf(stderr, " %lld", t[i] - t[i - 1]);
             tot += t[i] - t[i - 1];
         }
-        fprintf(stderr, " | total %.2f us\n", tot / 100.0);
+        fprintf(stderr, " | total %.2f us, start %+.2f end %+.2f us\n", tot / 100.0, (t[0] - t00) / 100.0,
+                (t[0] + tot - t00) / 100.0);
     }
 }
 #endif

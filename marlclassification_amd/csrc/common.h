@@ -588,6 +588,10 @@ struct PanelFwdBatch {
     // optional (count == 1): extra workgroups behind the panel ones run the sampling kernel's
     // rows (one wave per row) - an independent small kernel riding along in the same launch
     int has_sample, panel_blocks;
+    // optional (sample.nA <= 4): 1 + the index of the problem whose last layer's output is sample.a_pol - each wave of
+    // its workgroups runs the sampling chain of the rows it has just normalised, as the epilogue of that layer, so
+    // that sample(t) needs no launch behind the one that computes policy(t); 0 = off
+    int epi_prob;
     int ln_narrow_max;  // LayerNorm widths up to this use the two-column-slot row pass (launcher: 128, knob off: 0)
     SampleArgs sample;
 #ifdef MARL_KERNEL_TS
@@ -597,6 +601,7 @@ struct PanelFwdBatch {
 // the encoder -> mean -> decoder chain in one workgroup: all agents of a batch element fit a panel
 int panel_chain_supported(int na, int n_msg, int threads);
 int panel_supported(int k0, int n0, int n1);
+int panel_sample_supported(int n_actions);  // the sampling epilogue (PanelFwdBatch::epi_prob) covers this action count
 int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st);
 
 // LSTM cell backward (networks/recurrent.py:19-35 differentiated): gates holds the activated
@@ -762,14 +767,17 @@ int launch_panel_bwd(PanelBwdProb& p, hipStream_t st);
 // Fused per-step CNN forward (cnn.hip): gather + [im2col -> conv -> GroupNorm -> SiLU] x L
 // ---------------------------------------------------------------------------
 // In-kernel phase timestamps (make EXTRA=-DMARL_KERNEL_TS): lane 0 of every wave of one
-// workgroup records wall_clock64() (100 MHz) at each MARL_TS() in kernel order.
+// workgroup records wall_clock64() (100 MHz) at each MARL_TS() in kernel order.  Workgroups (37, 0) and (37, 1) record
+// (the two roles of a two-problem panel launch); ts_report prints one role's phases and its start and end on the clock
+// of role 0, wave 0.
 #ifdef MARL_KERNEL_TS
+constexpr int kTsWaves = 16, kTsSlots = 48, kTsRoles = 2;
 #define MARL_TS_DECL(ptr) long long* ts_ = (ptr); int tsi_ = 0
-#define MARL_TS()                                                                         \
-    if (ts_ && (threadIdx.x & 63) == 0 && blockIdx.x == 37 && blockIdx.y == 0 && tsi_ < 48) \
-    ts_[(threadIdx.x >> 6) * 48 + tsi_++] = wall_clock64()
+#define MARL_TS()                                                                              \
+    if (ts_ && (threadIdx.x & 63) == 0 && blockIdx.x == 37 && blockIdx.y < kTsRoles && tsi_ < kTsSlots) \
+    ts_[((int)blockIdx.y * kTsWaves + (threadIdx.x >> 6)) * kTsSlots + tsi_++] = wall_clock64()
 int ts_begin(long long** dev, int call);                 // returns 1 when this call records
-void ts_report(const char* tag, long long* dev, int waves);
+void ts_report(const char* tag, long long* dev, int waves, int role = 0);
 #else
 #define MARL_TS_DECL(ptr)
 #define MARL_TS()

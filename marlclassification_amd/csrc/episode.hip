@@ -1002,7 +1002,18 @@ static bool use_chain(const Dims& d) {
            // like the others every admitted plan has room for it; wider models take mix_msg_kernel
            (!g_comm || d.n_b <= 384);
 }
-static int step_chain(const Ctx& c, int t) {
+// sample(t) as the epilogue of the chain launch's policy workgroups (MARL_PANEL_SAMPLE=0: chain launch, then
+// sample_kernel - the earlier form, kept for comparison in one binary)
+static bool use_panel_sample(const Dims& d) {
+    static int enabled = -1;
+    if (enabled < 0) {
+        const char* e = getenv("MARL_PANEL_SAMPLE");
+        enabled = (e && e[0] == '0') ? 0 : 1;
+    }
+    return enabled && panel_sample_supported(d.nA);
+}
+// `sample`: the step's sampling arguments, run inside this launch when use_panel_sample() (else ignored)
+static int step_chain(const Ctx& c, int t, const SampleArgs* sample = nullptr) {
     const Dims& d = c.d;
     PanelFwdBatch pb{};
     pb.count = 2;
@@ -1020,6 +1031,10 @@ static int step_chain(const Ctx& c, int t) {
         pe.mix = g_comm;  // (null: the mean)
     }
     fill_pol_prob(c, t, pb.p[1]);
+    if (sample && use_panel_sample(d)) {
+        pb.epi_prob = 2;
+        pb.sample = *sample;
+    }
     return launch_panel_fwd(pb, c.st);
 }
 
@@ -2152,16 +2167,6 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
         else if (!decoded_ahead)
             MARL_TRY(step_decode(c, t));
         MARL_TRY(step_pos_lstm(c, t, in, t > 0));  // lambda_t (t > 0) came from sample(t-1)
-        if (chain) {
-            MARL_TRY(step_chain(c, t));  // encoder(t) -> decoder(t+1) || policy layer(t)
-        } else if (side) {
-            MARL_TRY(g_side.order(c.st, c2.st));  // side stream: after the LSTM of step t
-            MARL_TRY(step_encode_policy(c2, t, 1));
-            if (t + 1 < d.ns) MARL_TRY(step_decode(c2, t + 1));
-            MARL_TRY(step_encode_policy(c, t, 2));
-        } else {
-            MARL_TRY(step_encode_policy(c, t, 3));
-        }
         SampleArgs a;
         fill_sample_args(c, cfg, t, a);
         a.noise = noise ? noise + (size_t)t * d.R * d.nA : nullptr;
@@ -2192,11 +2197,22 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
                 a.pe_col0 = d.nf + d.n_mo;
             }
         }
+        if (chain) {
+            MARL_TRY(step_chain(c, t, &a));  // encoder(t) -> decoder(t+1) || policy layer(t) [-> sample(t)]
+        } else if (side) {
+            MARL_TRY(g_side.order(c.st, c2.st));  // side stream: after the LSTM of step t
+            MARL_TRY(step_encode_policy(c2, t, 1));
+            if (t + 1 < d.ns) MARL_TRY(step_decode(c2, t + 1));
+            MARL_TRY(step_encode_policy(c, t, 2));
+        } else {
+            MARL_TRY(step_encode_policy(c, t, 3));
+        }
         // sample(t) and decoder(t+1) are independent (the decoder needs MSG[t+1], written by the
-        // encoder above): one launch runs both
+        // encoder above): one launch runs both.  Under the chain launch decoder(t+1) is already inside it, and so
+        // is sample(t) when its policy workgroups ran it as their epilogue
         decoded_ahead = chain && t + 1 < d.ns;
         if (!side && !chain && t + 1 < d.ns) MARL_TRY(step_decode(c, t + 1, &a, &decoded_ahead));
-        if (chain || !decoded_ahead) MARL_TRY(launch_sample(a, c.st));
+        if (chain ? !use_panel_sample(d) : !decoded_ahead) MARL_TRY(launch_sample(a, c.st));
     }
     if (side) MARL_TRY(g_side.order(c2.st, c.st));  // join before the caller's stream continues
     MARL_TRY(heads_batched(c, 0, d.NR, step_values, step_preds));
@@ -2843,6 +2859,8 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     // launch - the decoder of step 0 and the step API then take form 3); "panel_chain" = the chained launch
     else if (!strcmp(key, "comm")) *value = g_comm != nullptr;
     else if (!strcmp(key, "panel_chain")) *value = use_chain(d) && !use_side_stream();
+    // the forward loop samples inside the chained launch (the policy workgroups' epilogue): no sample_kernel launch
+    else if (!strcmp(key, "panel_sample")) *value = use_chain(d) && !use_side_stream() && use_panel_sample(d);
     else if (!strcmp(key, "comm_form"))
         *value = g_comm ? ((use_chain(d) && !use_side_stream()) ? 5 : use_panels(d) ? 3 : 4)
                         : (use_chain(d) && !use_side_stream()) ? 0 : use_panels(d) ? 1 : 2;

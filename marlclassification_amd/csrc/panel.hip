@@ -188,17 +188,62 @@ __device__ __forceinline__ void panel_ln_rows(const PanelLayer& Lr, float* outp,
     }
 }
 
+// Sampling epilogue of the policy workgroups (EPI instantiations): the wave that has just normalised a row of the
+// policy hidden layer runs that row's chain of sample.h - output layer, softmax, draw, log p, bounded move, position
+// embedding of the next step - on the LDS panel row it wrote.  Per lane these are the columns lane + 64 u it stored
+// itself (no barrier needed), in sample_kernel's order: the results are the separate launch's, bit for bit.
+// UNI: the row's prefetched values move to scalar registers before the embedding's parameters are requested - the MIX
+// instantiation, which has one vector register fewer (a scalar spill lane), needs that to stay out of scratch; the plain
+// one fits without it and is 1.5 us per launch faster without (the moves wait for loads the chain would not yet need)
+template <int MAXA, bool UNI>
+__device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const float* outp, int ys, const int* rowmap,
+                                                  int wave, int nwaves, int lane) {
+    for (int lr = __builtin_amdgcn_readfirstlane(wave); lr < kPanelRows; lr += nwaves) {  // wave-uniform: scalar
+        const int row = __builtin_amdgcn_readfirstlane(rowmap[lr]);
+        if (row < 0) continue;
+        // (the lane index is made opaque per row: hoisted out of this loop, the chain's per-lane addresses would
+        // stay live across it - some forty registers the kernel's budget of 80 does not have)
+        int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));  // (from no live register)
+        asm volatile("" : "+v"(ln));
+        int zero = 0;  // (likewise the arguments: read where the chain uses them, not all ahead of the loop)
+        asm volatile("" : "+s"(zero));
+        const SampleArgs& A = (&A0)[zero];
+        float p[MAXA];
+        SamplePre<MAXA> S;
+        sample_prefetch_row<MAXA>(A, row, ln, S);
+        sample_row_logits_at<MAXA, kPanelMaxCols>(A, outp + lr * ys, p, ln);
+        // the row's prefetched values are the same in every lane and have arrived (their loads were issued ahead of
+        // the logits'): into scalar registers, out of the way of the embedding's 20 vector registers
+        if (UNI) {
+            auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j) {
+                S.b1[j] = uni(S.b1[j]);
+                S.nz[j] = uni(S.nz[j]);
+            }
+            S.ctr = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(S.ctr >> 32)) << 32) |
+                    (uint32_t)__builtin_amdgcn_readfirstlane((int)S.ctr);
+            S.pi0 = __builtin_amdgcn_readfirstlane(S.pi0);
+            S.pi1 = __builtin_amdgcn_readfirstlane(S.pi1);
+            S.forced = __builtin_amdgcn_readfirstlane(S.forced);
+        }
+        sample_prefetch_pe<MAXA>(A, ln, S);  // in flight under the reductions, the softmax and the draw
+        sample_finish<MAXA>(A, row, p, ln, S);
+    }
+}
+
 // ===========================================================================
 // forward
 // ===========================================================================
-// SAMPLE: 0 = panels only; 4 / MARL_MAX_ACTIONS = sampling workgroups ride along behind the panel ones, with
-// the action loops of sample.h bounded at that many actions
+// SAMPLE: 0 = panels only; 4 / MARL_MAX_ACTIONS = the action loops of sample.h bounded at that many actions, for
+// the sampling workgroups that ride along behind the panel ones (EPI = false) or for the sampling epilogue of the
+// workgroups of problem B.epi_prob - 1 (EPI = true: sample(t) inside the launch that computes policy(t))
 // MIX: the agg_at site mixes over a communication graph (P.mix) instead of taking the mean; the plain instantiations
 // carry none of it
-template <int SAMPLE, bool MIX = false>
+template <int SAMPLE, bool MIX = false, bool EPI = false>
 __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (SAMPLE > 0 && (int)blockIdx.x >= B.panel_blocks) {
+    if (!EPI && SAMPLE > 0 && (int)blockIdx.x >= B.panel_blocks) {
         // ride-along sampling workgroup: one wave per row of the policy activations
         const int r = ((int)blockIdx.x - B.panel_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
         if (r >= B.sample.R) return;
@@ -459,6 +504,12 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
         MARL_TS();
         K = n;
     }
+    // (outside the layer loop: none of the loop's layer descriptors stays live across the chain)
+    if (EPI && (int)(&P - B.p) + 1 == B.epi_prob) {  // (not blockIdx.y: one scalar fewer kept to the end)
+        constexpr int MAXA = SAMPLE > 0 ? SAMPLE : 4;
+        panel_sample_rows<MAXA, MIX>(B.sample, (P.nlayers & 1) ? Y : X, panel_stride(K), rowmap, wave, nwaves, lane);
+        MARL_TS();
+    }
 }
 
 constexpr size_t kPanelMaxLds = 144 * 1024;
@@ -475,6 +526,10 @@ int panel_chain_supported(int na, int n_msg, int threads) {
     const int K16 = (n_msg + 15) & ~15;  // (two passes of the workgroup cover the message panel)
     return na >= 1 && na <= kPanelRows && kPanelRows * (K16 / 4) <= 2 * threads;
 }
+
+// the sampling epilogue is instantiated for the four-action bound only (a sixteen-action one is 4x the chain's code
+// and registers inside the 80-register kernel): larger action sets keep the separate sample_kernel launch
+int panel_sample_supported(int n_actions) { return n_actions >= 1 && n_actions <= 4; }
 
 int panel_supported(int k0, int n0, int n1) {
     if (n0 > 32 * kPanelMaxWaves || n1 > 32 * kPanelMaxWaves) return 0;  // one column tile per wave
@@ -542,10 +597,12 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
     }
     static bool raised = false;
     if (!raised) {
-        const void* kerns[4] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
+        const void* kerns[6] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<MARL_MAX_ACTIONS>),
-                                reinterpret_cast<const void*>(panel_fwd_kernel<0, true>)};
+                                reinterpret_cast<const void*>(panel_fwd_kernel<0, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, false, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true>)};
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
@@ -563,8 +620,25 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
     const int rec = ts_begin(&d_ts, calls++);
     b.ts = rec ? d_ts : nullptr;
 #endif
+    if (b.epi_prob) {
+        const PanelFwdProb* p = b.epi_prob >= 1 && b.epi_prob <= b.count ? &b.p[b.epi_prob - 1] : nullptr;
+        if (!p || !panel_sample_supported(b.sample.nA) || p->nlayers < 1 || p->m != b.sample.R ||
+            p->layer[p->nlayers - 1].a != b.sample.a_pol || p->layer[p->nlayers - 1].n != b.sample.nla) {
+            set_error("panel kernel: the sampling epilogue needs the problem whose last layer writes its activations");
+            return MARL_EINVAL;
+        }
+    }
     prof_before(4, st);
-    if (b.has_sample && b.count == 1) {
+    if (b.epi_prob) {
+        // sample(t) as the epilogue of the policy workgroups: no ride-along workgroups
+        b.has_sample = 0;
+        if (mixed)
+            hipLaunchKernelGGL((panel_fwd_kernel<4, true, true>), dim3(pblocks, (unsigned)b.count), dim3(64 * waves),
+                               lds, st, b);
+        else
+            hipLaunchKernelGGL((panel_fwd_kernel<4, false, true>), dim3(pblocks, (unsigned)b.count), dim3(64 * waves),
+                               lds, st, b);
+    } else if (b.has_sample && b.count == 1) {
         b.panel_blocks = (int)pblocks;
         const unsigned sblocks = (unsigned)cdiv(b.sample.R, waves);
         if (b.sample.nA <= 4)
@@ -583,8 +657,12 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
     MARL_LAUNCH_CHECK();
 #ifdef MARL_KERNEL_TS
     if (rec) {
-        fprintf(stderr, "[ts] panel_fwd count %d sample %d waves %d lds %zu\n", b.count, b.has_sample, waves, lds);
+        fprintf(stderr, "[ts] panel_fwd count %d sample %d epilogue %d waves %d lds %zu\n", b.count, b.has_sample,
+                b.epi_prob, waves, lds);
         ts_report("panel_fwd", d_ts, waves);
+        // the second role of a two-problem launch (the policy layer beside the chain; its last phase is the sampling
+        // epilogue when there is one): start / end on role 0's clock show the slack before and after
+        if (b.count == 2) ts_report("panel_fwd role 1", d_ts, waves, 1);
     }
 #endif
     return MARL_OK;

@@ -38,19 +38,21 @@ __device__ __forceinline__ float philox_u01(uint32_t v) { return ((float)(v >> 8
 // (MAXA: compile-time bound of the action loops - 4 for the usual four moves, MARL_MAX_ACTIONS otherwise.
 // The loops are fully unrolled; at 16 the kernel was 24 KB of code of which a four-action model executes a
 // quarter, branching over the rest line by line)
-template <int MAXA>
-__device__ __forceinline__ void sample_logits_chunk(const SampleArgs& A, const float (&a)[8], int base,
+// (NU: column slots a lane holds per chunk - 8 in sample_kernel; the panel kernel's epilogue, whose rows are at most
+// 64 * 6 wide, holds 6: the two slots it drops would add a[u] * w = 0 * 0 to a sum, which changes no bit of it)
+template <int MAXA, int NU = 8>
+__device__ __forceinline__ void sample_logits_chunk(const SampleArgs& A, const float (&a)[NU], int base,
                                                     float (&p)[MAXA], int lane) {
 #pragma unroll
     for (int j0 = 0; j0 < MAXA; j0 += 4) {
         if (j0 < A.nA) {
-            float wv[4][8];
+            float wv[4][NU];
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
                 const int j = j0 + jj < A.nA ? j0 + jj : A.nA - 1;
                 const float* wj = A.w1 + (size_t)j * A.ldw;
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {  // (clamped address, no branch between two loads)
+                for (int u = 0; u < NU; ++u) {  // (clamped address, no branch between two loads)
                     const int k = base + lane + 64 * u;
                     const float v = wj[k < A.nla ? k : 0];
                     wv[jj][u] = k < A.nla ? v : 0.f;
@@ -60,29 +62,34 @@ __device__ __forceinline__ void sample_logits_chunk(const SampleArgs& A, const f
             for (int jj = 0; jj < 4; ++jj) {
                 float s = 0.f;
 #pragma unroll
-                for (int u = 0; u < 8; ++u) s += a[u] * wv[jj][u];
+                for (int u = 0; u < NU; ++u) s += a[u] * wv[jj][u];
                 p[j0 + jj] += s;
             }
         }
     }
 }
 
-// One wave = one row r: the activation row is read into registers 512 columns at a time
-template <int MAXA>
-__device__ __forceinline__ void sample_row_logits(const SampleArgs& A, int r, float (&p)[MAXA], int lane) {
-    const float* ar = A.a_pol + (size_t)r * A.ld_a;
+// One wave = one row: the activation row at `ar` (global memory, or the LDS panel row a policy workgroup of the
+// panel kernel has just normalised) is read into registers 512 columns at a time (NU < 8: a row of at most 64 * NU
+// columns, one chunk)
+template <int MAXA, int NU = 8>
+__device__ __forceinline__ void sample_row_logits_at(const SampleArgs& A, const float* ar, float (&p)[MAXA], int lane) {
 #pragma unroll
     for (int j = 0; j < MAXA; ++j) p[j] = 0.f;
-    for (int base = 0; base < A.nla; base += 512) {
-        float a[8];
+    for (int base = 0; base < (NU < 8 ? 1 : A.nla); base += 512) {
+        float a[NU];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
+        for (int u = 0; u < NU; ++u) {
             const int k = base + lane + 64 * u;
             const float v = ar[k < A.nla ? k : 0];
             a[u] = k < A.nla ? v : 0.f;
         }
-        sample_logits_chunk<MAXA>(A, a, base, p, lane);
+        sample_logits_chunk<MAXA, NU>(A, a, base, p, lane);
     }
+}
+template <int MAXA>
+__device__ __forceinline__ void sample_row_logits(const SampleArgs& A, int r, float (&p)[MAXA], int lane) {
+    sample_row_logits_at<MAXA>(A, A.a_pol + (size_t)r * A.ld_a, p, lane);
 }
 
 // Everything of a row whose address does not depend on the draw, requested BEFORE the logits are waited
@@ -104,9 +111,9 @@ __device__ __forceinline__ bool sample_pe_fast(const SampleArgs& A) {
     return A.pe_W && A.step_logp && (al & 15) == 0 && A.pe_nd <= 256 && ((A.pe_nd | A.pe_ldz | A.pe_ldo) & 3) == 0 &&
            (A.pe_col0 & 3) == 0;
 }
-// (PE = false: without the embedding's parameters - for the ride-along form inside the 80-register panel kernel)
-template <int MAXA, bool PE = true>
-__device__ __forceinline__ void sample_prefetch(const SampleArgs& A, int r, int lane, SamplePre<MAXA>& S) {
+// The row's own part (output bias, noise / forced action, generator counter, position) ...
+template <int MAXA>
+__device__ __forceinline__ void sample_prefetch_row(const SampleArgs& A, int r, int lane, SamplePre<MAXA>& S) {
 #pragma unroll
     for (int j = 0; j < MAXA; ++j) S.b1[j] = A.b1[j < A.nA ? j : A.nA - 1];
     if (A.noise) {
@@ -124,8 +131,14 @@ __device__ __forceinline__ void sample_prefetch(const SampleArgs& A, int r, int 
         S.pi1 = A.pos_in[r * 2 + 1];
         if (A.forced) S.forced = (int)A.forced[r];
     }
-    S.pe_fast = PE && sample_pe_fast(A);
-    if (PE && S.pe_fast) {
+    S.pe_fast = false;
+}
+// ... and the embedding's parameters, 28 registers a lane.  The panel kernel's sampling epilogue asks for them
+// behind the logits' loads (both sets at once do not fit its 80 registers); sample_kernel asks for both up front.
+template <int MAXA>
+__device__ __forceinline__ void sample_prefetch_pe(const SampleArgs& A, int lane, SamplePre<MAXA>& S) {
+    S.pe_fast = sample_pe_fast(A);
+    if (S.pe_fast) {
         const int j4 = 4 * lane < A.pe_nd ? 4 * lane : 0;
         S.qb = *reinterpret_cast<const float4*>(A.pe_b + j4);
         S.qg = *reinterpret_cast<const float4*>(A.pe_gamma + j4);
@@ -133,6 +146,12 @@ __device__ __forceinline__ void sample_prefetch(const SampleArgs& A, int r, int 
 #pragma unroll
         for (int q = 0; q < 4; ++q) S.qw[q] = *reinterpret_cast<const float4*>(A.pe_W + 4 * (j4 + q));
     }
+}
+// (PE = false: without the embedding's parameters - for the ride-along form inside the 80-register panel kernel)
+template <int MAXA, bool PE = true>
+__device__ __forceinline__ void sample_prefetch(const SampleArgs& A, int r, int lane, SamplePre<MAXA>& S) {
+    sample_prefetch_row<MAXA>(A, r, lane, S);
+    if (PE) sample_prefetch_pe<MAXA>(A, lane, S);
 }
 
 // p[] holds this lane's partial logits of row r; every lane of the wave must call this

@@ -1,5 +1,8 @@
 """Runs one product of libmarl_hip.so a few times (profiling / timestamp runs).
-usage: python tools/ts_run.py nt M N K | tn ROWS NI NJ"""
+usage: python tools/ts_run.py nt M N K | tn ROWS NI NJ
+(the timestamps of a whole episode's launches - both roles of a chained panel launch, the policy role's sampling
+epilogue included - come from bench.py under such a build: tools/panel_sample_bench.py --ts-lib LIB, MARL_TS_CALL=N
+choosing the launch)"""
 import os, sys, torch as th
 sys.path.insert(0, os.getcwd())
 from marlclassification_amd import _lib
