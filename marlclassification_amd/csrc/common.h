@@ -939,66 +939,54 @@ int launch_col2im(const float* dcols, int ldk, float* da, int64_t rows, int hin,
 // ---------------------------------------------------------------------------
 // loss (loss.hip)
 // ---------------------------------------------------------------------------
-struct LossArgs {
+// what the three loss entries share: episode outputs, labels, the loss scratch and the sizes
+struct LossCommon {
     const float* preds;   // [Ns, Na, Nb, nC]
-    const float* logp;    // [Ns, Na, Nb]
     const float* values;  // [Ns, Na, Nb]
     const int64_t* y;     // [Nb]
-    float* g_preds;       // [Ns*R, ld_gp]
+    float* scratch;       // rewards / returns / raw advantages [3][Ns*R], vote error, partial sums
+    int ns, na, nb, nc;
+};
+// ... and what the two loss passes (A2C, PPO) add: the policy term's input, the output gradients, the scalars and
+// the optional entropy bonus (probs != nullptr)
+struct LossGradArgs : LossCommon {
+    const float* logp;  // [Ns, Na, Nb]
+    float* g_preds;     // [Ns*R, ld_gp]
     int ld_gp;
     float* g_logp;
     float* g_values;
-    float* scalars;  // [4]
-    double* adv_stats;  // [3] = n, sum, sum of squares of the advantages
-    float* scratch;  // returns/adv [2][Ns*R] + partial sums
-    int ns, na, nb, nc;
-    float gamma;
-    int phase;
-    // marl_a2c_loss_entropy_fwd_bwd (probs != nullptr): the entropy bonus, scalars is [5] then
+    float* scalars;                // A2C: [4], [5] with the bonus; PPO: [7]
     const float* probs = nullptr;  // [Ns*R, nA] tight
     float* g_probs = nullptr;      // [Ns*R, nA] tight
     int n_act = 0;
     float entropy_coef = 0.f;
 };
+
+// marl_a2c_loss_fwd_bwd, marl_a2c_loss_entropy_fwd_bwd
+struct LossArgs : LossGradArgs {
+    double* adv_stats;  // [3] = n, sum, sum of squares of the advantages
+    float gamma;
+    int phase;
+};
 size_t loss_scratch_floats(int ns, int na, int nb);
 int launch_loss(const LossArgs& a, hipStream_t st);
 
 // marl_advantages: rewards -> GAE(lambda) -> standardise, into caller-owned advn / ret
-struct AdvArgs {
-    const float* preds;   // [Ns, Na, Nb, nC]
-    const float* values;  // [Ns, Na, Nb]
-    const int64_t* y;     // [Nb]
-    float* advn;          // [Ns*R] standardised advantage
-    float* ret;           // [Ns*R] critic target
-    double* adv_stats;    // [3]
-    float* scratch;       // the loss scratch (rewards, raw advantages, partials)
-    int ns, na, nb, nc;
+struct AdvArgs : LossCommon {
+    float* advn;        // [Ns*R] standardised advantage
+    float* ret;         // [Ns*R] critic target
+    double* adv_stats;  // [3]
     float gamma, lam;
     int phase;
 };
 int launch_advantages(const AdvArgs& a, hipStream_t st);
 
 // marl_ppo_loss_fwd_bwd: clipped surrogate + critic + vote error (- entropy bonus when probs != nullptr)
-struct PpoArgs {
-    const float* preds;
-    const float* logp;
-    const float* values;
-    const int64_t* y;
+struct PpoArgs : LossGradArgs {
     const float* old_logp;  // [Ns*R]
     const float* advn;      // [Ns*R]
     const float* ret;       // [Ns*R]
     float clip_eps;
-    float* g_preds;
-    int ld_gp;
-    float* g_logp;
-    float* g_values;
-    float* scalars;  // [7]
-    float* scratch;
-    int ns, na, nb, nc;
-    const float* probs = nullptr;
-    float* g_probs = nullptr;
-    int n_act = 0;
-    float entropy_coef = 0.f;
 };
 int launch_ppo_loss(const PpoArgs& a, hipStream_t st);
 

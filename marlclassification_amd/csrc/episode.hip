@@ -2248,72 +2248,61 @@ int marl_episode_forward_probs(const marl_config* cfg, const void* weights_ws, s
                                step_logp, step_values, step_pos, step_actions, step_probs, train, stream);
 }
 
-int marl_episode_backward(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
-                          void* episode_ws, size_t episode_ws_bytes, const void* img, const float* g_preds, const float* g_logp,
-                          const float* g_values, float* const* grads_host, void* stream) {
+// the three backward exports: context, gradient table, and - with a d_img, or when the entry's contract requires one
+// (need_dimg) - the image-gradient guards, all before anything is enqueued
+static int episode_backward_entry(const char* who, bool need_dimg, const marl_config* cfg, void* weights_ws,
+                                  size_t weights_ws_bytes, void* episode_ws, size_t episode_ws_bytes, const void* img,
+                                  const float* g_preds, const float* g_logp, const float* g_values,
+                                  float* const* grads_host, float* d_img, const float* g_probs, void* stream) {
     Ctx c;
     SplitRegistryScope reg_scope;
     MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, 1, stream, c));
     if (!grads_host) {
-        set_error("episode_backward: null gradient table");
+        set_error("%s: null gradient table", who);
         return MARL_EINVAL;
     }
-    return episode_backward(c, img, cfg->img_u8 != 0, g_preds, g_logp, g_values, grads_host);
+    if (d_img || need_dimg) {
+        if (cfg->img_u8 != 0) {
+            set_error("%s: an integer (uint8) image batch has no gradient", who);
+            return MARL_EINVAL;
+        }
+        if (!d_img || !img) {
+            set_error("%s: null %s", who, d_img ? "img" : "d_img");
+            return MARL_EINVAL;
+        }
+        if (!cnn_dimg_supported(cnn_dimg_shape(c.d))) {
+            set_error("%s: shape outside the image-gradient kernel's range", who);
+            return MARL_ELIMIT;
+        }
+    }
+    return episode_backward(c, img, d_img ? 0 : cfg->img_u8 != 0, g_preds, g_logp, g_values, grads_host, nullptr,
+                            d_img, g_probs);
+}
+
+int marl_episode_backward(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
+                          void* episode_ws, size_t episode_ws_bytes, const void* img, const float* g_preds, const float* g_logp,
+                          const float* g_values, float* const* grads_host, void* stream) {
+    return episode_backward_entry("episode_backward", false, cfg, weights_ws, weights_ws_bytes, episode_ws,
+                                  episode_ws_bytes, img, g_preds, g_logp, g_values, grads_host, nullptr, nullptr,
+                                  stream);
 }
 
 int marl_episode_backward_img(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
                               void* episode_ws, size_t episode_ws_bytes, const void* img, const float* g_preds,
                               const float* g_logp, const float* g_values, float* const* grads_host, float* d_img,
                               void* stream) {
-    Ctx c;
-    SplitRegistryScope reg_scope;
-    MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, 1, stream, c));
-    if (!grads_host) {
-        set_error("episode_backward_img: null gradient table");
-        return MARL_EINVAL;
-    }
-    if (cfg->img_u8 != 0) {
-        set_error("episode_backward_img: an integer (uint8) image batch has no gradient");
-        return MARL_EINVAL;
-    }
-    if (!d_img || !img) {
-        set_error("episode_backward_img: null %s", d_img ? "img" : "d_img");
-        return MARL_EINVAL;
-    }
-    if (!cnn_dimg_supported(cnn_dimg_shape(c.d))) {  // (before anything is enqueued)
-        set_error("episode_backward_img: shape outside the image-gradient kernel's range");
-        return MARL_ELIMIT;
-    }
-    return episode_backward(c, img, 0, g_preds, g_logp, g_values, grads_host, nullptr, d_img);
+    return episode_backward_entry("episode_backward_img", true, cfg, weights_ws, weights_ws_bytes, episode_ws,
+                                  episode_ws_bytes, img, g_preds, g_logp, g_values, grads_host, d_img, nullptr,
+                                  stream);
 }
 
 int marl_episode_backward_probs(const marl_config* cfg, void* weights_ws, size_t weights_ws_bytes,
                                 void* episode_ws, size_t episode_ws_bytes, const void* img, const float* g_preds,
                                 const float* g_logp, const float* g_values, float* const* grads_host, float* d_img,
                                 const float* g_probs, void* stream) {
-    Ctx c;
-    SplitRegistryScope reg_scope;
-    MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, 1, stream, c));
-    if (!grads_host) {
-        set_error("episode_backward_probs: null gradient table");
-        return MARL_EINVAL;
-    }
-    if (d_img) {  // the checks of marl_episode_backward_img, before anything is enqueued
-        if (cfg->img_u8 != 0) {
-            set_error("episode_backward_probs: an integer (uint8) image batch has no gradient");
-            return MARL_EINVAL;
-        }
-        if (!img) {
-            set_error("episode_backward_probs: null img");
-            return MARL_EINVAL;
-        }
-        if (!cnn_dimg_supported(cnn_dimg_shape(c.d))) {
-            set_error("episode_backward_probs: shape outside the image-gradient kernel's range");
-            return MARL_ELIMIT;
-        }
-    }
-    return episode_backward(c, img, d_img ? 0 : cfg->img_u8 != 0, g_preds, g_logp, g_values, grads_host, nullptr,
-                            d_img, g_probs);
+    return episode_backward_entry("episode_backward_probs", false, cfg, weights_ws, weights_ws_bytes, episode_ws,
+                                  episode_ws_bytes, img, g_preds, g_logp, g_values, grads_host, d_img, g_probs,
+                                  stream);
 }
 
 int marl_backward_heads_event(void* hip_event) {
@@ -2464,94 +2453,17 @@ int marl_graph_destroy(void* graph_exec) {
     return MARL_OK;
 }
 
-int marl_a2c_loss_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
-                          const float* step_preds,
-                          const float* step_logp, const float* step_values, const int64_t* y,
-                          float gamma, float* g_preds, float* g_logp, float* g_values,
-                          float* scalars_out, double* adv_stats, int phase, void* stream) {
+// what every loss entry starts with: the dimensions, its own argument check (`bad`, evaluated by the caller), the
+// training-layout size check, and the fields of LossCommon - the loss scratch is the last buffer of either
+// episode-workspace layout
+static int loss_entry(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes, bool bad, const char* who,
+                      const float* step_preds, const float* step_values, const int64_t* y, LossCommon& a) {
     Dims d;
     MARL_TRY(make_dims(cfg, d));
-    if (!episode_ws || !step_preds || !step_logp || !step_values || !y || !scalars_out ||
-        !adv_stats || phase < 0 || phase > 2) {
-        set_error("a2c_loss: bad argument");
+    if (bad) {
+        set_error("%s: bad argument", who);
         return MARL_EINVAL;
     }
-    // the loss scratch is the last buffer of either episode-workspace layout
-    ELayout e;
-    make_elayout(d, 1, e);
-    if (episode_ws_bytes < e.total * sizeof(float)) {
-        set_error("a2c_loss: episode workspace too small (%zu of %zu bytes, training layout)", episode_ws_bytes,
-                  e.total * sizeof(float));
-        return MARL_ESIZE;
-    }
-    LossArgs a;
-    a.preds = step_preds;
-    a.logp = step_logp;
-    a.values = step_values;
-    a.y = y;
-    a.g_preds = g_preds;
-    a.ld_gp = d.nC;
-    a.g_logp = g_logp;
-    a.g_values = g_values;
-    a.scalars = scalars_out;
-    a.adv_stats = adv_stats;
-    a.scratch = static_cast<float*>(episode_ws) + e.LOSS;
-    a.ns = d.ns;
-    a.na = d.na;
-    a.nb = d.nb;
-    a.nc = d.nC;
-    a.gamma = gamma;
-    a.phase = phase;
-    return launch_loss(a, static_cast<hipStream_t>(stream));
-}
-
-int marl_a2c_loss_entropy_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
-                                  const float* step_preds, const float* step_logp, const float* step_values,
-                                  const int64_t* y, float gamma, const float* step_probs, float entropy_coef,
-                                  float* g_preds, float* g_logp, float* g_values, float* g_probs,
-                                  float* scalars_out, double* adv_stats, int phase, void* stream) {
-    Dims d;
-    MARL_TRY(make_dims(cfg, d));
-    if (!episode_ws || !step_preds || !step_logp || !step_values || !y || !step_probs || !g_probs ||
-        !scalars_out || !adv_stats || phase < 0 || phase > 2 || !(entropy_coef >= 0.f)) {
-        set_error("a2c_loss_entropy: bad argument");
-        return MARL_EINVAL;
-    }
-    ELayout e;
-    make_elayout(d, 1, e);
-    if (episode_ws_bytes < e.total * sizeof(float)) {
-        set_error("a2c_loss_entropy: episode workspace too small (%zu of %zu bytes, training layout)",
-                  episode_ws_bytes, e.total * sizeof(float));
-        return MARL_ESIZE;
-    }
-    LossArgs a;
-    a.preds = step_preds;
-    a.logp = step_logp;
-    a.values = step_values;
-    a.y = y;
-    a.g_preds = g_preds;
-    a.ld_gp = d.nC;
-    a.g_logp = g_logp;
-    a.g_values = g_values;
-    a.scalars = scalars_out;
-    a.adv_stats = adv_stats;
-    a.scratch = static_cast<float*>(episode_ws) + e.LOSS;
-    a.ns = d.ns;
-    a.na = d.na;
-    a.nb = d.nb;
-    a.nc = d.nC;
-    a.gamma = gamma;
-    a.phase = phase;
-    a.probs = step_probs;
-    a.g_probs = g_probs;
-    a.n_act = d.nA;
-    a.entropy_coef = entropy_coef;
-    return launch_loss(a, static_cast<hipStream_t>(stream));
-}
-
-// the loss scratch (tail of the training layout) for the PPO entries; MARL_ESIZE when the workspace is too small
-static int loss_scratch_of(const Dims& d, void* episode_ws, size_t episode_ws_bytes, const char* who,
-                           float** scratch) {
     ELayout e;
     make_elayout(d, 1, e);
     if (episode_ws_bytes < e.total * sizeof(float)) {
@@ -2559,32 +2471,82 @@ static int loss_scratch_of(const Dims& d, void* episode_ws, size_t episode_ws_by
                   e.total * sizeof(float));
         return MARL_ESIZE;
     }
-    *scratch = static_cast<float*>(episode_ws) + e.LOSS;
+    a.preds = step_preds;
+    a.values = step_values;
+    a.y = y;
+    a.scratch = static_cast<float*>(episode_ws) + e.LOSS;
+    a.ns = d.ns;
+    a.na = d.na;
+    a.nb = d.nb;
+    a.nc = d.nC;
     return MARL_OK;
+}
+
+// ... and the fields of LossGradArgs (after loss_entry: ld_gp is the class count)
+static void fill_loss_grads(LossGradArgs& a, const marl_config* cfg, const float* step_logp, const float* step_probs,
+                            float entropy_coef, float* g_preds, float* g_logp, float* g_values, float* g_probs,
+                            float* scalars_out) {
+    a.logp = step_logp;
+    a.g_preds = g_preds;
+    a.ld_gp = a.nc;
+    a.g_logp = g_logp;
+    a.g_values = g_values;
+    a.scalars = scalars_out;
+    a.probs = step_probs;
+    a.g_probs = g_probs;
+    a.n_act = cfg->nb_action;
+    a.entropy_coef = entropy_coef;
+}
+
+// marl_a2c_loss_fwd_bwd (step_probs == nullptr) and marl_a2c_loss_entropy_fwd_bwd
+static int a2c_loss_all(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes, bool bad, const char* who,
+                        const float* step_preds, const float* step_logp, const float* step_values, const int64_t* y,
+                        float gamma, const float* step_probs, float entropy_coef, float* g_preds, float* g_logp,
+                        float* g_values, float* g_probs, float* scalars_out, double* adv_stats, int phase,
+                        void* stream) {
+    LossArgs a;
+    MARL_TRY(loss_entry(cfg, episode_ws, episode_ws_bytes,
+                        bad || !episode_ws || !step_preds || !step_logp || !step_values || !y || !scalars_out ||
+                            !adv_stats || phase < 0 || phase > 2,
+                        who, step_preds, step_values, y, a));
+    fill_loss_grads(a, cfg, step_logp, step_probs, entropy_coef, g_preds, g_logp, g_values, g_probs, scalars_out);
+    a.adv_stats = adv_stats;
+    a.gamma = gamma;
+    a.phase = phase;
+    return launch_loss(a, static_cast<hipStream_t>(stream));
+}
+
+int marl_a2c_loss_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
+                          const float* step_preds,
+                          const float* step_logp, const float* step_values, const int64_t* y,
+                          float gamma, float* g_preds, float* g_logp, float* g_values,
+                          float* scalars_out, double* adv_stats, int phase, void* stream) {
+    return a2c_loss_all(cfg, episode_ws, episode_ws_bytes, false, "a2c_loss", step_preds, step_logp, step_values, y,
+                        gamma, nullptr, 0.f, g_preds, g_logp, g_values, nullptr, scalars_out, adv_stats, phase,
+                        stream);
+}
+
+int marl_a2c_loss_entropy_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes,
+                                  const float* step_preds, const float* step_logp, const float* step_values,
+                                  const int64_t* y, float gamma, const float* step_probs, float entropy_coef,
+                                  float* g_preds, float* g_logp, float* g_values, float* g_probs,
+                                  float* scalars_out, double* adv_stats, int phase, void* stream) {
+    return a2c_loss_all(cfg, episode_ws, episode_ws_bytes, !step_probs || !g_probs || !(entropy_coef >= 0.f),
+                        "a2c_loss_entropy", step_preds, step_logp, step_values, y, gamma, step_probs, entropy_coef,
+                        g_preds, g_logp, g_values, g_probs, scalars_out, adv_stats, phase, stream);
 }
 
 int marl_advantages(const marl_config* cfg, void* episode_ws, size_t episode_ws_bytes, const float* step_preds,
                     const float* step_values, const int64_t* y, float gamma, float lam, float* advn, float* ret,
                     double* adv_stats, int phase, void* stream) {
-    Dims d;
-    MARL_TRY(make_dims(cfg, d));
-    if (!episode_ws || !step_preds || !step_values || !y || !advn || !ret || !adv_stats || phase < 0 ||
-        phase > 2 || !(lam >= 0.f && lam <= 1.f)) {
-        set_error("advantages: bad argument");
-        return MARL_EINVAL;
-    }
     AdvArgs a;
-    MARL_TRY(loss_scratch_of(d, episode_ws, episode_ws_bytes, "advantages", &a.scratch));
-    a.preds = step_preds;
-    a.values = step_values;
-    a.y = y;
+    MARL_TRY(loss_entry(cfg, episode_ws, episode_ws_bytes,
+                        !episode_ws || !step_preds || !step_values || !y || !advn || !ret || !adv_stats ||
+                            phase < 0 || phase > 2 || !(lam >= 0.f && lam <= 1.f),
+                        "advantages", step_preds, step_values, y, a));
     a.advn = advn;
     a.ret = ret;
     a.adv_stats = adv_stats;
-    a.ns = d.ns;
-    a.na = d.na;
-    a.nb = d.nb;
-    a.nc = d.nC;
     a.gamma = gamma;
     a.lam = lam;
     a.phase = phase;
@@ -2596,37 +2558,18 @@ int marl_ppo_loss_fwd_bwd(const marl_config* cfg, void* episode_ws, size_t episo
                           const int64_t* y, const float* old_logp, const float* advn, const float* ret,
                           float clip_eps, const float* step_probs, float entropy_coef, float* g_preds, float* g_logp,
                           float* g_values, float* g_probs, float* scalars_out, void* stream) {
-    Dims d;
-    MARL_TRY(make_dims(cfg, d));
-    if (!episode_ws || !step_preds || !step_logp || !step_values || !y || !old_logp || !advn || !ret ||
-        !scalars_out || !(clip_eps > 0.f) || (step_probs == nullptr) != (g_probs == nullptr) ||
-        (step_probs && !(entropy_coef >= 0.f))) {
-        set_error("ppo_loss: bad argument");
-        return MARL_EINVAL;
-    }
     PpoArgs a;
-    MARL_TRY(loss_scratch_of(d, episode_ws, episode_ws_bytes, "ppo_loss", &a.scratch));
-    a.preds = step_preds;
-    a.logp = step_logp;
-    a.values = step_values;
-    a.y = y;
+    MARL_TRY(loss_entry(cfg, episode_ws, episode_ws_bytes,
+                        !episode_ws || !step_preds || !step_logp || !step_values || !y || !old_logp || !advn ||
+                            !ret || !scalars_out || !(clip_eps > 0.f) ||
+                            (step_probs == nullptr) != (g_probs == nullptr) ||
+                            (step_probs && !(entropy_coef >= 0.f)),
+                        "ppo_loss", step_preds, step_values, y, a));
+    fill_loss_grads(a, cfg, step_logp, step_probs, entropy_coef, g_preds, g_logp, g_values, g_probs, scalars_out);
     a.old_logp = old_logp;
     a.advn = advn;
     a.ret = ret;
     a.clip_eps = clip_eps;
-    a.g_preds = g_preds;
-    a.ld_gp = d.nC;
-    a.g_logp = g_logp;
-    a.g_values = g_values;
-    a.scalars = scalars_out;
-    a.ns = d.ns;
-    a.na = d.na;
-    a.nb = d.nb;
-    a.nc = d.nC;
-    a.probs = step_probs;
-    a.g_probs = g_probs;
-    a.n_act = d.nA;
-    a.entropy_coef = entropy_coef;
     return launch_ppo_loss(a, static_cast<hipStream_t>(stream));
 }
 

@@ -6,6 +6,9 @@
 // All cross-thread sums go through fixed-order partials (fp64) -> bit-reproducible.
 #include "common.h"
 
+#include <cassert>
+#include <type_traits>
+
 namespace marl {
 
 __device__ __forceinline__ float wsum(float v) {
@@ -19,6 +22,68 @@ __device__ __forceinline__ float wmax(float v) {
     return v;
 }
 
+// tree over K per-thread fp64 values; thread 0 ends up with the block sums in sh[k][0]
+template <int K>
+__device__ __forceinline__ void block_tree(double (*sh)[256], const double (&v)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+}
+
+// advn = (adv - mean) / (std + 1e-8) with the global mean / unbiased std of adv_stats (functions.py:54-55)
+__device__ __forceinline__ float standardized(float adv, const double* __restrict__ adv_stats) {
+    const double n = adv_stats[0];
+    const double mean_d = adv_stats[1] / n;
+    const double var_d = (adv_stats[2] - adv_stats[1] * mean_d) / (n - 1.0);
+    const float mean = (float)mean_d;
+    const float sd = (float)sqrt(var_d > 0.0 ? var_d : 0.0);
+    return (adv - mean) / (sd + 1e-8f);
+}
+
+// smooth-L1 of d = value - return (the critic term); *grad = its derivative
+__device__ __forceinline__ float smooth_l1(float d, float* grad) {
+    const float ad = fabsf(d);
+    *grad = ad < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f);
+    return ad < 1.0f ? 0.5f * d * d : ad - 0.5f;
+}
+
+// entropy bonus of one row of the step distributions [nA]: returns sum_j p_j log p_j (= -H) and writes
+// g[j] = scale * (log p_j + 1).  0 * log 0 = 0: an exactly zero probability adds nothing to H and gets a zero gradient
+// (nothing becomes NaN / Inf).  VEC: nA % 4 == 0 and 16-byte aligned tensors - the row moves as float4s.
+template <bool VEC>
+__device__ __forceinline__ float row_entropy(const float* __restrict__ p, float* __restrict__ g, int nA, float scale) {
+    float h = 0.f;
+    auto term = [&](float pj) {  // adds p log p to h, returns the gradient
+        if (!(pj > 0.f)) return 0.f;
+        const float lp = logf(pj);
+        h = fmaf(pj, lp, h);
+        return scale * (lp + 1.0f);
+    };
+    if (VEC) {
+        const float4* pv = reinterpret_cast<const float4*>(p);
+        float4* gv = reinterpret_cast<float4*>(g);
+        for (int k = 0; k < nA / 4; ++k) {
+            const float4 v = pv[k];
+            float4 o;
+            o.x = term(v.x);
+            o.y = term(v.y);
+            o.z = term(v.z);
+            o.w = term(v.w);
+            gv[k] = o;
+        }
+    } else {
+        for (int j = 0; j < nA; ++j) g[j] = term(p[j]);
+    }
+    return h;
+}
+
 struct LossLayout {
     double* part_adv;   // [blocksC][2]
     double* part_loss;  // [blocksE][2]
@@ -27,6 +92,7 @@ struct LossLayout {
     float* ret;         // [Ns*R]
     float* adv;         // [Ns*R]
     float* err;         // [Ns*Nb]
+    double* spare;      // the 16 floats behind err, from the first 8-byte boundary
     int blocksC, blocksE;
 };
 
@@ -44,6 +110,7 @@ static LossLayout loss_layout(float* scratch, int ns, int na, int nb) {
     L.ret = f + NR;
     L.adv = f + 2 * NR;
     L.err = f + 3 * NR;
+    L.spare = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(L.err + (int64_t)ns * nb) + 7) & ~(uintptr_t)7);
     return L;
 }
 
@@ -51,6 +118,29 @@ size_t loss_scratch_floats(int ns, int na, int nb) {
     const int64_t R = (int64_t)na * nb, NR = R * ns;
     const int64_t dbl = 2 * cdiv(R, 256) + 2 * cdiv(NR, 256) + 2;
     return (size_t)(2 * dbl + 3 * NR + (int64_t)ns * nb + 16);
+}
+
+// where a grads kernel keeps the k doubles per block it sums beyond part_loss (k = 1: the A2C entropy, k = 3: PPO).
+// One block: the 16 spare floats behind `err` - 3 doubles and up to 7 bytes of alignment are 31 of their 64 bytes.
+// More blocks: the place of the rewards [NR floats], dead since the returns / GAE kernel read them (an earlier phase
+// or marl_advantages) - blocksE > 1 means NR >= 257, and k * blocksE doubles are 2 k cdiv(NR, 256) <= 6 (NR / 256 + 1)
+// floats, which is below NR from NR = 7 on.
+static double* extra_partials(const LossLayout& L, int k) {
+    assert(k <= 3);
+    return L.blocksE == 1 ? L.spare : reinterpret_cast<double*>(L.rew);
+}
+
+// the one place that picks the <ENT, VEC> instance of a grads kernel: launch(ent, vec) gets two std::bool_constant
+template <class F>
+static void with_grads_instance(const LossGradArgs& a, F&& launch) {
+    const bool vec = a.n_act % 4 == 0 && (reinterpret_cast<uintptr_t>(a.probs) & 15) == 0 &&
+                     (reinterpret_cast<uintptr_t>(a.g_probs) & 15) == 0;
+    if (!a.probs)
+        launch(std::false_type{}, std::false_type{});
+    else if (vec)
+        launch(std::true_type{}, std::true_type{});
+    else
+        launch(std::true_type{}, std::false_type{});
 }
 
 // rew[t, r] = (log nC - CE(preds[t, r, :], y[b])) / log nC ; one wave per (t, r)
@@ -120,7 +210,7 @@ __global__ __launch_bounds__(256) void loss_returns_kernel(const float* __restri
                                                            int64_t R, float gamma) {
     __shared__ double sh[2][256];
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;
+    double s[2] = {0.0, 0.0};
     if (r < R) {
         float S = 0.f;
         for (int t = ns - 1; t >= 0; --t) {
@@ -130,20 +220,11 @@ __global__ __launch_bounds__(256) void loss_returns_kernel(const float* __restri
             const float ad = rt - values[(int64_t)t * R + r];
             ret[(int64_t)t * R + r] = rt;
             adv[(int64_t)t * R + r] = ad;
-            s1 += (double)ad;
-            s2 += (double)ad * (double)ad;
+            s[0] += (double)ad;
+            s[1] += (double)ad * (double)ad;
         }
     }
-    sh[0][threadIdx.x] = s1;
-    sh[1][threadIdx.x] = s2;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    block_tree<2>(sh, s);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = sh[0][0];
         part[2 * blockIdx.x + 1] = sh[1][0];
@@ -155,21 +236,13 @@ __global__ __launch_bounds__(256) void loss_stats_kernel(
     const double* __restrict__ part, int nblocks, const float* __restrict__ err, int64_t nerr,
     double* __restrict__ part_err, double* __restrict__ adv_stats, double n) {
     __shared__ double sh[3][256];
-    double s1 = 0.0, s2 = 0.0, e = 0.0;
+    double s[3] = {0.0, 0.0, 0.0};
     for (int i = threadIdx.x; i < nblocks; i += 256) {
-        s1 += part[2 * i];
-        s2 += part[2 * i + 1];
+        s[0] += part[2 * i];
+        s[1] += part[2 * i + 1];
     }
-    for (int64_t i = threadIdx.x; i < nerr; i += 256) e += (double)err[i];
-    sh[0][threadIdx.x] = s1;
-    sh[1][threadIdx.x] = s2;
-    sh[2][threadIdx.x] = e;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o)
-            for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + o];
-        __syncthreads();
-    }
+    for (int64_t i = threadIdx.x; i < nerr; i += 256) s[2] += (double)err[i];
+    block_tree<3>(sh, s);
     if (threadIdx.x == 0) {
         adv_stats[0] = n;
         adv_stats[1] = sh[0][0];
@@ -179,9 +252,8 @@ __global__ __launch_bounds__(256) void loss_stats_kernel(
 }
 
 // ENT (marl_a2c_loss_entropy_fwd_bwd): the same pass also reads row i of the step distributions [NR][nA] and writes
-// H_i = -sum_j p_j log p_j into a third partial and g_probs[i][j] = beta / R * (log p_j + 1).  0 * log 0 = 0: an
-// exactly zero probability adds nothing to H and gets a zero gradient (nothing becomes NaN / Inf).  VEC: nA % 4 == 0
-// and 16-byte aligned tensors - a row moves as float4s.  ENT = false is the kernel of marl_a2c_loss_fwd_bwd.
+// H_i = -sum_j p_j log p_j into a third partial and g_probs[i][j] = beta / R * (log p_j + 1) (row_entropy<VEC>).
+// ENT = false is the kernel of marl_a2c_loss_fwd_bwd.
 template <bool ENT, bool VEC>
 __global__ __launch_bounds__(256) void loss_grads_kernel(
     const float* __restrict__ logp, const float* __restrict__ values,
@@ -190,66 +262,25 @@ __global__ __launch_bounds__(256) void loss_grads_kernel(
     float* __restrict__ g_values, double* __restrict__ part, int64_t NR, int64_t R,
     const float* __restrict__ probs, float* __restrict__ g_probs, double* __restrict__ part_ent, int nA,
     float beta) {
-    __shared__ double sh[ENT ? 3 : 2][256];
+    constexpr int K = ENT ? 3 : 2;
+    __shared__ double sh[K][256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    double s[K] = {};
     if (i < NR) {
-        const double n = adv_stats[0];
-        const double mean_d = adv_stats[1] / n;
-        const double var_d = (adv_stats[2] - adv_stats[1] * mean_d) / (n - 1.0);
-        const float mean = (float)mean_d;
-        const float sd = (float)sqrt(var_d > 0.0 ? var_d : 0.0);
-        const float advn = (adv[i] - mean) / (sd + 1e-8f);
+        const float advn = standardized(adv[i], adv_stats);
         const float invR = 1.0f / (float)R;
-        s1 = (double)(-logp[i] * advn);
-        const float d = values[i] - ret[i];
-        const float ad = fabsf(d);
-        s2 = (double)(ad < 1.0f ? 0.5f * d * d : ad - 0.5f);
+        s[0] = (double)(-logp[i] * advn);
+        float dg;
+        s[1] = (double)smooth_l1(values[i] - ret[i], &dg);
         if (g_logp) g_logp[i] = -advn * invR;
-        if (g_values) g_values[i] = (ad < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f)) * invR;
-        if (ENT) {
-            const float scale = beta * invR;
-            float h = 0.f;
-            auto term = [&](float p) {  // adds p log p to h, returns the gradient
-                if (!(p > 0.f)) return 0.f;
-                const float lp = logf(p);
-                h = fmaf(p, lp, h);
-                return scale * (lp + 1.0f);
-            };
-            if (VEC) {
-                const float4* pv = reinterpret_cast<const float4*>(probs + i * nA);
-                float4* gv = reinterpret_cast<float4*>(g_probs + i * nA);
-                for (int k = 0; k < nA / 4; ++k) {
-                    const float4 p = pv[k];
-                    float4 g;
-                    g.x = term(p.x);
-                    g.y = term(p.y);
-                    g.z = term(p.z);
-                    g.w = term(p.w);
-                    gv[k] = g;
-                }
-            } else {
-                for (int j = 0; j < nA; ++j) g_probs[i * nA + j] = term(probs[i * nA + j]);
-            }
-            s3 = (double)(-h);
-        }
+        if (g_values) g_values[i] = dg * invR;
+        if constexpr (ENT) s[2] = (double)(-row_entropy<VEC>(probs + i * nA, g_probs + i * nA, nA, beta * invR));
     }
-    sh[0][threadIdx.x] = s1;
-    sh[1][threadIdx.x] = s2;
-    if (ENT) sh[2][threadIdx.x] = s3;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-            if (ENT) sh[2][threadIdx.x] += sh[2][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    block_tree<K>(sh, s);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = sh[0][0];
         part[2 * blockIdx.x + 1] = sh[1][0];
-        if (ENT) part_ent[blockIdx.x] = sh[2][0];
+        if constexpr (ENT) part_ent[blockIdx.x] = sh[2][0];
     }
 }
 
@@ -259,33 +290,21 @@ template <bool ENT>
 __global__ __launch_bounds__(256) void loss_final_kernel(
     const double* __restrict__ part, int nblocks, const double* __restrict__ part_err,
     float* __restrict__ scalars, int ns, int nb, int64_t R, const double* __restrict__ part_ent, float beta) {
-    __shared__ double sh[ENT ? 3 : 2][256];
-    double p = 0.0, c = 0.0, h = 0.0;
+    constexpr int K = ENT ? 3 : 2;
+    __shared__ double sh[K][256];
+    double s[K] = {};
     for (int i = threadIdx.x; i < nblocks; i += 256) {
-        p += part[2 * i];
-        c += part[2 * i + 1];
-        if (ENT) h += part_ent[i];
+        s[0] += part[2 * i];
+        s[1] += part[2 * i + 1];
+        if constexpr (ENT) s[2] += part_ent[i];
     }
-    sh[0][threadIdx.x] = p;
-    sh[1][threadIdx.x] = c;
-    if (ENT) sh[2][threadIdx.x] = h;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-            if (ENT) sh[2][threadIdx.x] += sh[2][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    block_tree<K>(sh, s);
     if (threadIdx.x == 0) {
-        p = sh[0][0];
-        c = sh[1][0];
-        const double path = p / (double)R, critic = c / (double)R;
+        const double path = sh[0][0] / (double)R, critic = sh[1][0] / (double)R;
         const double esum = part_err[0];
         double loss = path + esum / (double)nb + critic;
-        if (ENT) {
-            h = sh[2][0];
+        if constexpr (ENT) {
+            const double h = sh[2][0];
             loss -= (double)beta * (h / (double)R);
             scalars[4] = (float)(h / ((double)R * ns));
         }
@@ -321,59 +340,28 @@ int launch_loss(const LossArgs& a, hipStream_t st) {
         MARL_LAUNCH_CHECK();
     }
     if (a.phase == 0 || a.phase == 2) {
-        const dim3 grid((unsigned)L.blocksE), block(256);
-        if (!a.probs) {
-            hipLaunchKernelGGL((loss_grads_kernel<false, false>), grid, block, 0, st, a.logp, a.values, L.ret, L.adv,
-                               stats, a.g_logp, a.g_values, L.part_loss, NR, R, nullptr, nullptr, nullptr, 0, 0.f);
-            MARL_LAUNCH_CHECK();
-            hipLaunchKernelGGL(loss_final_kernel<false>, dim3(1), dim3(256), 0, st, L.part_loss, L.blocksE,
-                               L.part_err, a.scalars, a.ns, a.nb, R, nullptr, 0.f);
-            MARL_LAUNCH_CHECK();
-        } else {
-            // the entropy partials [blocksE] take the place of the rewards, dead since loss_returns_kernel (phases 0
-            // and 1); a single (t, r) row has no room there - the 16 spare floats behind `err` hold its one partial
-            double* part_ent =
-                NR >= 2 ? reinterpret_cast<double*>(L.rew)
-                        : reinterpret_cast<double*>(
-                              (reinterpret_cast<uintptr_t>(L.err + (int64_t)a.ns * a.nb) + 7) & ~(uintptr_t)7);
-            const bool vec = a.n_act % 4 == 0 && (reinterpret_cast<uintptr_t>(a.probs) & 15) == 0 &&
-                             (reinterpret_cast<uintptr_t>(a.g_probs) & 15) == 0;
-            if (vec)
-                hipLaunchKernelGGL((loss_grads_kernel<true, true>), grid, block, 0, st, a.logp, a.values, L.ret,
-                                   L.adv, stats, a.g_logp, a.g_values, L.part_loss, NR, R, a.probs, a.g_probs,
-                                   part_ent, a.n_act, a.entropy_coef);
-            else
-                hipLaunchKernelGGL((loss_grads_kernel<true, false>), grid, block, 0, st, a.logp, a.values, L.ret,
-                                   L.adv, stats, a.g_logp, a.g_values, L.part_loss, NR, R, a.probs, a.g_probs,
-                                   part_ent, a.n_act, a.entropy_coef);
-            MARL_LAUNCH_CHECK();
-            hipLaunchKernelGGL(loss_final_kernel<true>, dim3(1), dim3(256), 0, st, L.part_loss, L.blocksE,
-                               L.part_err, a.scalars, a.ns, a.nb, R, part_ent, a.entropy_coef);
-            MARL_LAUNCH_CHECK();
-        }
+        double* part_ent = extra_partials(L, 1);  // (not touched without the bonus)
+        with_grads_instance(a, [&](auto ent, auto vec) {
+            hipLaunchKernelGGL((loss_grads_kernel<decltype(ent)::value, decltype(vec)::value>), dim3((unsigned)L.blocksE),
+                               dim3(256), 0, st, a.logp, a.values, L.ret, L.adv, stats, a.g_logp, a.g_values,
+                               L.part_loss, NR, R, a.probs, a.g_probs, part_ent, a.n_act, a.entropy_coef);
+        });
+        MARL_LAUNCH_CHECK();
+        if (a.probs)
+            hipLaunchKernelGGL(loss_final_kernel<true>, dim3(1), dim3(256), 0, st, L.part_loss, L.blocksE, L.part_err,
+                               a.scalars, a.ns, a.nb, R, part_ent, a.entropy_coef);
+        else
+            hipLaunchKernelGGL(loss_final_kernel<false>, dim3(1), dim3(256), 0, st, L.part_loss, L.blocksE, L.part_err,
+                               a.scalars, a.ns, a.nb, R, nullptr, 0.f);
+        MARL_LAUNCH_CHECK();
     }
     return MARL_OK;
 }
 
 // ---------------------------------------------------------------------------
-// PPO on the fused path (marl_advantages, marl_ppo_loss_fwd_bwd, marl_grad_clip).  Nothing above moves: the A2C
-// entries launch what they launched.  Same conventions: fp64 partials, fixed-order trees, no float atomics.
+// PPO on the fused path (marl_advantages, marl_ppo_loss_fwd_bwd, marl_grad_clip).  Same conventions: fp64 partials,
+// fixed-order trees, no float atomics.
 // ---------------------------------------------------------------------------
-
-// tree over K per-thread fp64 values; thread 0 ends up with the block sums in sh[k][0]
-template <int K>
-__device__ __forceinline__ void block_tree(double (*sh)[256], const double (&v)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-}
 
 // thread per row r, t from Ns - 1 down: delta_t = r_t + gamma V_{t+1} - V_t (V_Ns = 0: the reference's returns have no
 // bootstrap), A_t = delta_t + gamma lam A_{t+1}, ret_t = A_t + V_t; partials of sum A and sum A^2 as in
@@ -408,18 +396,12 @@ __global__ __launch_bounds__(256) void loss_gae_kernel(const float* __restrict__
     }
 }
 
-// advn = (adv - mean) / (std + 1e-8): functions.py:54-55, the expression of loss_grads_kernel
 __global__ __launch_bounds__(256) void loss_standardize_kernel(const float* __restrict__ adv,
                                                                const double* __restrict__ adv_stats,
                                                                float* __restrict__ advn, int64_t NR) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= NR) return;
-    const double n = adv_stats[0];
-    const double mean_d = adv_stats[1] / n;
-    const double var_d = (adv_stats[2] - adv_stats[1] * mean_d) / (n - 1.0);
-    const float mean = (float)mean_d;
-    const float sd = (float)sqrt(var_d > 0.0 ? var_d : 0.0);
-    advn[i] = (adv[i] - mean) / (sd + 1e-8f);
+    advn[i] = standardized(adv[i], adv_stats);
 }
 
 int launch_advantages(const AdvArgs& a, hipStream_t st) {
@@ -454,7 +436,7 @@ int launch_advantages(const AdvArgs& a, hipStream_t st) {
 // one thread per (t, r): rho = exp(logp - old_logp); surrogate -min(rho A, clamp(rho, 1 - eps, 1 + eps) A) and
 // g_logp = -A rho / R where the unclipped term is the active one, 0 where the clip is (A > 0 and rho > 1 + eps, or
 // A < 0 and rho < 1 - eps).  With old_logp == logp bit for bit rho is exactly 1 and (-A * rho) * (1 / R) is
-// loss_grads_kernel's -advn * invR, bit for bit; the critic term and g_values ARE that kernel's expressions.
+// loss_grads_kernel's -advn * invR, bit for bit; the critic term and g_values are that kernel's smooth_l1.
 // part[2 i] / [2 i + 1] = surrogate / critic, extra[3 i ..] = entropy / old_logp - logp / clipped count.
 // ENT / VEC: as in loss_grads_kernel.
 template <bool ENT, bool VEC>
@@ -475,39 +457,13 @@ __global__ __launch_bounds__(256) void ppo_grads_kernel(
         const bool clipped = (advn > 0.f && rho > hi) || (advn < 0.f && rho < lo);
         const float rc = fminf(fmaxf(rho, lo), hi);
         s[0] = (double)(-(clipped ? rc : rho) * advn);
-        const float d = values[i] - ret[i];
-        const float ad = fabsf(d);
-        s[1] = (double)(ad < 1.0f ? 0.5f * d * d : ad - 0.5f);
+        float dg;
+        s[1] = (double)smooth_l1(values[i] - ret[i], &dg);
         s[3] = (double)(olp - lp);
         s[4] = clipped ? 1.0 : 0.0;
         if (g_logp) g_logp[i] = clipped ? 0.f : (-advn * rho) * invR;
-        if (g_values) g_values[i] = (ad < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f)) * invR;
-        if (ENT) {
-            const float scale = beta * invR;
-            float h = 0.f;
-            auto term = [&](float p) {  // adds p log p to h, returns the gradient
-                if (!(p > 0.f)) return 0.f;
-                const float l = logf(p);
-                h = fmaf(p, l, h);
-                return scale * (l + 1.0f);
-            };
-            if (VEC) {
-                const float4* pv = reinterpret_cast<const float4*>(probs + i * nA);
-                float4* gv = reinterpret_cast<float4*>(g_probs + i * nA);
-                for (int k = 0; k < nA / 4; ++k) {
-                    const float4 p = pv[k];
-                    float4 g;
-                    g.x = term(p.x);
-                    g.y = term(p.y);
-                    g.z = term(p.z);
-                    g.w = term(p.w);
-                    gv[k] = g;
-                }
-            } else {
-                for (int j = 0; j < nA; ++j) g_probs[i * nA + j] = term(probs[i * nA + j]);
-            }
-            s[2] = (double)(-h);
-        }
+        if (g_values) g_values[i] = dg * invR;
+        if (ENT) s[2] = (double)(-row_entropy<VEC>(probs + i * nA, g_probs + i * nA, nA, beta * invR));
     }
     block_tree<5>(sh, s);
     if (threadIdx.x == 0) {
@@ -558,31 +514,15 @@ int launch_ppo_loss(const PpoArgs& a, hipStream_t st) {
     }
     const int64_t R = (int64_t)a.na * a.nb, NR = R * a.ns, nerr = (int64_t)a.ns * a.nb;
     LossLayout L = loss_layout(a.scratch, a.ns, a.na, a.nb);
-    // three more partials per block than the A2C pass keeps: they take the place of the rewards (dead once
-    // marl_advantages returned; 6 floats per 256 rows); one block (NR <= 256): the 16 spare floats behind `err`
-    double* extra = L.blocksE > 1 ? reinterpret_cast<double*>(L.rew)
-                                  : reinterpret_cast<double*>(
-                                        (reinterpret_cast<uintptr_t>(L.err + nerr) + 7) & ~(uintptr_t)7);
+    double* extra = extra_partials(L, 3);  // entropy / old_logp - logp / clipped count
     hipLaunchKernelGGL(loss_error_kernel, dim3((unsigned)cdiv(nerr, 4)), dim3(256), 0, st, a.preds, a.y, L.err,
                        a.g_preds, a.ld_gp, a.ns, a.na, a.nb, a.nc);
     MARL_LAUNCH_CHECK();
-    const dim3 grid((unsigned)L.blocksE), block(256);
-    if (!a.probs) {
-        hipLaunchKernelGGL((ppo_grads_kernel<false, false>), grid, block, 0, st, a.logp, a.old_logp, a.values, a.ret,
-                           a.advn, a.clip_eps, a.g_logp, a.g_values, L.part_loss, extra, NR, R, nullptr, nullptr, 0,
-                           0.f);
-    } else {
-        const bool vec = a.n_act % 4 == 0 && (reinterpret_cast<uintptr_t>(a.probs) & 15) == 0 &&
-                         (reinterpret_cast<uintptr_t>(a.g_probs) & 15) == 0;
-        if (vec)
-            hipLaunchKernelGGL((ppo_grads_kernel<true, true>), grid, block, 0, st, a.logp, a.old_logp, a.values,
-                               a.ret, a.advn, a.clip_eps, a.g_logp, a.g_values, L.part_loss, extra, NR, R, a.probs,
-                               a.g_probs, a.n_act, a.entropy_coef);
-        else
-            hipLaunchKernelGGL((ppo_grads_kernel<true, false>), grid, block, 0, st, a.logp, a.old_logp, a.values,
-                               a.ret, a.advn, a.clip_eps, a.g_logp, a.g_values, L.part_loss, extra, NR, R, a.probs,
-                               a.g_probs, a.n_act, a.entropy_coef);
-    }
+    with_grads_instance(a, [&](auto ent, auto vec) {
+        hipLaunchKernelGGL((ppo_grads_kernel<decltype(ent)::value, decltype(vec)::value>), dim3((unsigned)L.blocksE),
+                           dim3(256), 0, st, a.logp, a.old_logp, a.values, a.ret, a.advn, a.clip_eps, a.g_logp,
+                           a.g_values, L.part_loss, extra, NR, R, a.probs, a.g_probs, a.n_act, a.entropy_coef);
+    });
     MARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(ppo_final_kernel, dim3(1), dim3(256), 0, st, L.part_loss, extra, L.blocksE, L.err, nerr,
                        a.scalars, a.ns, a.nb, R, a.probs ? a.entropy_coef : 0.f);

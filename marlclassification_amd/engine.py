@@ -486,7 +486,7 @@ class HipEngine:
         ``d_img`` ([Nb,C,H,W] fp32, overwritten): also the gradient w.r.t. the image batch
         (marl_episode_backward_img); None: the plain entry, nothing extra is launched.
         ``g_probs`` ([Ns,Na,Nb,nA] fp32): dL/d(step_probs) (marl_episode_backward_probs, with or without ``d_img``);
-        None: the entries above, verbatim.
+        None: the entries above.
         ``d_comm`` ([Na,Na] fp32, overwritten): also the gradient w.r.t. the mixing matrix (marl_comm_grad, two
         launches behind the backward on the same workspace); None: nothing more is launched."""
         cfg = self.cfg
@@ -507,45 +507,37 @@ class HipEngine:
             if cfg.img_u8 or tuple(d_img.shape) != (cfg.batch, cfg.img_c, cfg.img_h, cfg.img_w):
                 raise RuntimeError("episode_backward: d_img needs a float image batch of the configured shape")
 
-        def run(ews: th.Tensor, image: th.Tensor, gp, gl, gv) -> None:
-            head = (C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews), image.data_ptr(),
-                    _ptr(gp), _ptr(gl), _ptr(gv), self._table(grads))
-            if g_probs is not None:
-                self._agg(self.lib.marl_episode_backward_probs, *head, _ptr(d_img), g_probs.data_ptr(),
-                          _stream(self.device))
-            elif d_img is None:
-                self._agg(self.lib.marl_episode_backward, *head, _stream(self.device))
-            else:
-                self._agg(self.lib.marl_episode_backward_img, *head, d_img.data_ptr(), _stream(self.device))
-            if d_comm is not None:
-                self.comm_grad(ews, cfg.nb_steps, d_comm)
-
         if ws is not None:  # an episode that owns its workspace (autograd path)
             if getattr(ws, "_marl_key", None) != (self._cfg_key, _tune_epoch) or img is None:
                 raise RuntimeError(
                     "episode_backward: the engine was re-configured (other batch size / image shape / "
                     "layout knob) since this episode's rollout - its workspace no longer fits")
-            gp = None if g_preds is None else _need(g_preds, th.float32, "g_preds")
-            gl = None if g_logp is None else _need(g_logp, th.float32, "g_logp")
-            gv = None if g_values is None else _need(g_values, th.float32, "g_values")
-            wws = self.packed_weights_ws()
-            run(ws, img, gp, gl, gv)
-            return
-        if self._fwd_img is None or self._fwd_key != self._cfg_key:
-            raise RuntimeError(
-                "episode_backward without a matching training rollout: the engine was "
-                "re-configured (other batch size / image shape) or never ran episode_forward("
-                "train=True) - its workspace no longer holds this episode's activations")
-        if generation is not None and generation != self.fwd_generation:
-            raise RuntimeError(
-                "episode_backward for an episode whose saved activations were overwritten by a "
-                "later training rollout (one live episode per engine: call backward before the "
-                "next run_episode, or accumulate gradients across backward calls instead)")
-        gp = None if g_preds is None else _need(g_preds, th.float32, "g_preds")
-        gl = None if g_logp is None else _need(g_logp, th.float32, "g_logp")
-        gv = None if g_values is None else _need(g_values, th.float32, "g_values")
-        wws, ews = self.packed_weights_ws(), self.episode_ws(True)
-        run(ews, self._fwd_img, gp, gl, gv)
+        else:
+            if self._fwd_img is None or self._fwd_key != self._cfg_key:
+                raise RuntimeError(
+                    "episode_backward without a matching training rollout: the engine was "
+                    "re-configured (other batch size / image shape) or never ran episode_forward("
+                    "train=True) - its workspace no longer holds this episode's activations")
+            if generation is not None and generation != self.fwd_generation:
+                raise RuntimeError(
+                    "episode_backward for an episode whose saved activations were overwritten by a "
+                    "later training rollout (one live episode per engine: call backward before the "
+                    "next run_episode, or accumulate gradients across backward calls instead)")
+        gp, gl, gv = (None if g is None else _need(g, th.float32, name)
+                      for g, name in ((g_preds, "g_preds"), (g_logp, "g_logp"), (g_values, "g_values")))
+        wws = self.packed_weights_ws()
+        ews, image = (self.episode_ws(True), self._fwd_img) if ws is None else (ws, img)
+        head = (C.byref(cfg), wws.data_ptr(), _nbytes(wws), ews.data_ptr(), _nbytes(ews), image.data_ptr(),
+                _ptr(gp), _ptr(gl), _ptr(gv), self._table(grads))
+        if g_probs is not None:
+            self._agg(self.lib.marl_episode_backward_probs, *head, _ptr(d_img), g_probs.data_ptr(),
+                      _stream(self.device))
+        elif d_img is None:
+            self._agg(self.lib.marl_episode_backward, *head, _stream(self.device))
+        else:
+            self._agg(self.lib.marl_episode_backward_img, *head, d_img.data_ptr(), _stream(self.device))
+        if d_comm is not None:
+            self.comm_grad(ews, cfg.nb_steps, d_comm)
 
     def a2c_loss(
         self, out: EpisodeTensors, y: th.Tensor, gamma: float, phase: int = 0,
@@ -554,7 +546,7 @@ class HipEngine:
         """Returns (g_preds, g_logp, g_values, scalars[4], adv_stats[3] float64).
         ``entropy_coef`` > 0 (marl_a2c_loss_entropy_fwd_bwd; ``out.step_probs`` needed): the loss minus
         ``entropy_coef * mean_{a,b} sum_t H``; returns (g_preds, g_logp, g_values, scalars[5], adv_stats, g_probs)
-        with scalars[4] = the mean entropy.  0: the plain entry, verbatim."""
+        with scalars[4] = the mean entropy.  0: the plain entry."""
         cfg = self.cfg
         assert cfg is not None
         dev = self.device
@@ -566,49 +558,42 @@ class HipEngine:
             raise ValueError("a2c_loss(entropy_coef > 0) needs the episode's step_probs: episode_forward(probs=True)")
         if bufs is None:
             bufs = self.new_loss_bufs(out, ent)
-        ews = self.episode_ws(True)
-        if not ent:
-            gp, gl, gv, sc, st = bufs
-            check(self.lib.marl_a2c_loss_fwd_bwd(
-                C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(),
-                out.step_log_probas.data_ptr(), out.step_values.data_ptr(), y.data_ptr(),
-                C.c_float(gamma), gp.data_ptr(), gl.data_ptr(), gv.data_ptr(), sc.data_ptr(),
-                st.data_ptr(), phase, _stream(dev)))
-            return bufs
-        if len(bufs) != 6 or bufs[3].numel() != 5 or bufs[5].shape != out.step_probs.shape:
+        if ent and (len(bufs) != 6 or bufs[3].numel() != 5 or bufs[5].shape != out.step_probs.shape):
             raise ValueError("a2c_loss(entropy_coef > 0): buffers from new_loss_bufs(out, True) needed")
-        gp, gl, gv, sc, st, gpr = bufs
-        check(self.lib.marl_a2c_loss_entropy_fwd_bwd(
+        gp, gl, gv, sc, st = bufs[:5] if ent else bufs
+        ews = self.episode_ws(True)
+        entry, bonus, g_bonus = self.lib.marl_a2c_loss_fwd_bwd, (), ()
+        if ent:  # the same argument list with (probs, coef) and g_probs slotted in
+            entry = self.lib.marl_a2c_loss_entropy_fwd_bwd
+            bonus = (_need(out.step_probs, th.float32, "step_probs").data_ptr(), C.c_float(entropy_coef))
+            g_bonus = (bufs[5].data_ptr(),)
+        check(entry(
             C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(),
             out.step_log_probas.data_ptr(), out.step_values.data_ptr(), y.data_ptr(),
-            C.c_float(gamma), _need(out.step_probs, th.float32, "step_probs").data_ptr(),
-            C.c_float(entropy_coef), gp.data_ptr(), gl.data_ptr(), gv.data_ptr(), gpr.data_ptr(),
+            C.c_float(gamma), *bonus, gp.data_ptr(), gl.data_ptr(), gv.data_ptr(), *g_bonus,
             sc.data_ptr(), st.data_ptr(), phase, _stream(dev)))
         return bufs
 
+    def _grad_bufs(self, out: EpisodeTensors, n_scalars: int) -> Tuple[th.Tensor, ...]:
+        """(g_preds, g_logp, g_values, scalars[n_scalars], adv_stats[3] float64): what both loss passes write."""
+        return (
+            th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
+            th.empty_like(out.step_values), th.zeros(n_scalars, device=self.device),
+            th.zeros(3, dtype=th.float64, device=self.device),
+        )
+
     def new_loss_bufs(self, out: EpisodeTensors, entropy: bool = False) -> Tuple[th.Tensor, ...]:
         """The output tensors of ``a2c_loss`` (persistent ones for a trainer / a captured graph)."""
-        dev = self.device
-        bufs = (
-            th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
-            th.empty_like(out.step_values), th.zeros(5 if entropy else 4, device=dev),
-            th.zeros(3, dtype=th.float64, device=dev),
-        )
+        bufs = self._grad_bufs(out, 5 if entropy else 4)
         return bufs + (th.empty_like(out.step_probs),) if entropy else bufs
 
     # -- PPO: GAE(lambda) advantages, clipped surrogate, global-norm clipping ---------------------------------
     def new_ppo_bufs(self, out: EpisodeTensors, entropy: bool = False) -> Tuple[th.Tensor, ...]:
         """The tensors ``advantages`` and ``ppo_loss`` write (persistent ones for a trainer):
         (g_preds, g_logp, g_values, scalars[7], adv_stats[3] float64, advn, ret) + (g_probs,) with ``entropy``."""
-        dev = self.device
         if entropy and out.step_probs is None:
             raise ValueError("new_ppo_bufs(entropy=True) needs the episode's step_probs: episode_forward(probs=True)")
-        bufs = (
-            th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
-            th.empty_like(out.step_values), th.zeros(7, device=dev),
-            th.zeros(3, dtype=th.float64, device=dev),
-            th.empty_like(out.step_values), th.empty_like(out.step_values),
-        )
+        bufs = self._grad_bufs(out, 7) + (th.empty_like(out.step_values), th.empty_like(out.step_values))
         return bufs + (th.empty_like(out.step_probs),) if entropy else bufs
 
     def _check_ppo_bufs(self, out: EpisodeTensors, bufs: Tuple[th.Tensor, ...], what: str) -> None:

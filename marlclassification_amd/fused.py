@@ -114,7 +114,7 @@ def check_ppo_options(ppo_epochs: int, ppo_clip: float, gae_lambda: float, max_g
 
 
 def ppo_options_on(ppo_epochs: int, ppo_clip: float, gae_lambda: float, max_grad_norm: Optional[float]) -> bool:
-    """False = all four at their defaults: the A2C entries, verbatim."""
+    """False = all four at their defaults: the A2C entries."""
     return ppo_epochs != 1 or ppo_clip != 0.2 or gae_lambda != 1.0 or max_grad_norm is not None
 
 
@@ -172,25 +172,53 @@ def ppo_bufs_fit(bufs, out: EpisodeTensors, entropy: bool) -> bool:
             (not entropy or bufs[7].shape == out.step_probs.shape))
 
 
+def apply_update(eng: HipEngine, flat: "FlatParams", gp, gl, gv, g_probs, gviews, lr: float, allreduce,
+                 max_grad_norm: Optional[float], repack: Callable[[], None],
+                 comm: Optional[CommUpdate] = None) -> Optional[th.Tensor]:
+    """One update from the output gradients a loss entry wrote - the A2C, entropy and PPO steps of ``Trainer`` and
+    ``FusedA2C`` all end here: backward (bucketed hooks around it: two buckets, the heads' slice leaves while the
+    reverse loop still runs) -> all-reduce -> [grad_clip, after the all-reduce and its scale: every rank clips the
+    same averaged gradient] -> Adam (``flat.step`` += 1) -> ``repack()``.  ``comm`` (a live communication source
+    under a ``comm_lr``): the backward also writes d_comm and the source's leaves take their Adam step after the flat
+    one; None: ``episode_backward`` is called without ``d_comm``.  Returns the device scalar with the gradient norm
+    (None without ``max_grad_norm``)."""
+    bucketed = hasattr(allreduce, "before_backward")  # parallel.BucketedGradAllReduce
+    if bucketed:
+        allreduce.before_backward(eng)
+    try:
+        d_comm = {} if comm is None else {"d_comm": comm.buffer(eng)}
+        eng.episode_backward(gp, gl, gv, gviews, g_probs=g_probs, **d_comm)
+    finally:
+        if bucketed:
+            allreduce.after_backward(eng)
+    scale = rank_scale = 1.0 if allreduce is None else allreduce(flat.grads)
+    norm = None
+    if max_grad_norm is not None:
+        norm = eng.grad_clip(flat.grads, max_grad_norm, grad_scale=scale)
+        scale = 1.0
+    flat.step += 1
+    eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, lr, grad_scale=scale)
+    if comm is not None:
+        comm.step(eng.comm_live, allreduce, rank_scale)
+    repack()
+    return norm
+
+
 def ppo_epochs_loop(eng: HipEngine, flat: "FlatParams", out: EpisodeTensors, y: th.Tensor, bufs, epochs: int,
                     clip: float, beta: float, lr: float, allreduce, max_grad_norm: Optional[float], gviews,
                     replay: Callable[[], EpisodeTensors], repack: Callable[[], None],
                     comm: Optional[CommUpdate] = None) -> Optional[th.Tensor]:
     """The K update epochs of one rollout ``out`` whose advantages already sit in ``bufs`` (``HipEngine.advantages``);
     ``Trainer`` and ``FusedA2C`` both run this.  Epoch k > 0 starts with ``replay()``: the stored trajectory (same
-    draws, the rollout's actions forced) under the weights the last epoch packed.  Then ppo_loss -> backward (bucketed
-    hooks as in the A2C step) -> all-reduce -> [grad_clip, after the all-reduce and its scale: every rank clips the
-    same averaged gradient] -> Adam (``flat.step`` += 1) -> ``repack()``.  Returns the device scalar with the last
-    epoch's gradient norm (None without ``max_grad_norm``).  ``comm`` (a live communication source under a
-    ``comm_lr``): every epoch's backward also writes d_comm and the source's leaves take their Adam step after the flat
-    one; the source is evaluated again by every ``replay()``, so epoch k runs under the matrix epoch k - 1 produced.
+    draws, the rollout's actions forced) under the weights the last epoch packed.  Then ppo_loss -> ``apply_update``.
+    Returns the device scalar with the last epoch's gradient norm (None without ``max_grad_norm``).  ``comm``: the
+    source is evaluated again by every ``replay()``, so epoch k runs under the matrix epoch k - 1 produced.
     The gradient-norm clip covers the flat buffer only."""
     gp, gl, gv, _, _, advn, ret = bufs[:7]
     gpr = bufs[7] if beta > 0 else None
     # the old log-probabilities are the rollout's own output tensor: a replay writes fresh outputs, so epoch 0 has
     # rho == 1 bit for bit and no copy is needed - as long as the replay really returns other storage
     old_logp = out.step_log_probas
-    bucketed = hasattr(allreduce, "before_backward")  # parallel.BucketedGradAllReduce
     cur, norm = out, None
     for k in range(epochs):
         if k > 0:
@@ -199,25 +227,7 @@ def ppo_epochs_loop(eng: HipEngine, flat: "FlatParams", out: EpisodeTensors, y: 
                 raise RuntimeError("PPO replay wrote over the rollout's log-probabilities (persistent output "
                                    "tensors?): the ratios would all be 1")
         eng.ppo_loss(cur, y, old_logp, advn, ret, clip, bufs, entropy_coef=beta)
-        if bucketed:
-            allreduce.before_backward(eng)
-        try:
-            if comm is None:
-                eng.episode_backward(gp, gl, gv, gviews, g_probs=gpr)
-            else:
-                eng.episode_backward(gp, gl, gv, gviews, g_probs=gpr, d_comm=comm.buffer(eng))
-        finally:
-            if bucketed:
-                allreduce.after_backward(eng)
-        scale = rank_scale = 1.0 if allreduce is None else allreduce(flat.grads)
-        if max_grad_norm is not None:
-            norm = eng.grad_clip(flat.grads, max_grad_norm, grad_scale=scale)
-            scale = 1.0
-        flat.step += 1
-        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, lr, grad_scale=scale)
-        if comm is not None:
-            comm.step(eng.comm_live, allreduce, rank_scale)
-        repack()
+        norm = apply_update(eng, flat, gp, gl, gv, gpr, gviews, lr, allreduce, max_grad_norm, repack, comm)
     return norm
 
 
@@ -379,28 +389,8 @@ class FusedA2C:
             self._loss_bufs = eng.new_loss_bufs(out, beta > 0)
         bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
         gp, gl, gv, scalars = bufs[:4]
-        gpr = bufs[5] if beta > 0 else None
-        bucketed = hasattr(self.allreduce, "before_backward")
-        comm = self._comm()
-        if bucketed:  # (two buckets: the heads' slice leaves while the reverse loop still runs)
-            self.allreduce.before_backward(eng)
-        try:
-            if comm is None:
-                eng.episode_backward(gp, gl, gv, self._gviews, g_probs=gpr)
-            else:
-                eng.episode_backward(gp, gl, gv, self._gviews, g_probs=gpr, d_comm=comm.buffer(eng))
-        finally:
-            if bucketed:
-                self.allreduce.after_backward(eng)
-        scale = 1.0
-        if self.allreduce is not None:
-            scale = self.allreduce(self.flat.grads)
-        self.flat.step += 1
-        eng.adam(self.flat.params, self.flat.grads, self.flat.exp_avg, self.flat.exp_avg_sq,
-                 self.flat.step, self.lr, grad_scale=scale)
-        if comm is not None:
-            comm.step(eng.comm_live, self.allreduce, scale)
-        self.pack()
+        apply_update(eng, self.flat, gp, gl, gv, bufs[5] if beta > 0 else None, self._gviews, self.lr,
+                     self.allreduce, None, self.pack, self._comm())
         return out, scalars
 
     def _comm(self) -> Optional[CommUpdate]:

@@ -16,7 +16,8 @@ import torch as th
 
 from ..core import EpisodeSampler
 from ..engine import EpisodeTensors
-from ..fused import CommUpdate, check_ppo_options, comm_update_for, ppo_bufs_fit, ppo_epochs_loop, ppo_options_on
+from ..fused import (CommUpdate, apply_update, check_ppo_options, comm_update_for, ppo_bufs_fit, ppo_epochs_loop,
+                     ppo_options_on)
 from ..metrics import ConfusionMeter, LossMeter
 from ..networks import ModelsWrapper
 
@@ -46,10 +47,11 @@ class Trainer:
         requires grad, a module such as ``comm.LearnableComm`` or a callable with ``parameters()``).  Each update then
         evaluates the source, rolls out, takes the loss, runs the backward WITH d_comm (marl_comm_grad), sums d_comm
         over the ranks with the scale the flat gradient gets, calls ``matrix.backward(d_comm)`` and steps a
-        ``torch.optim.Adam(model.comm_parameters(), lr=comm_lr)`` - in all three ``train_step`` paths and in every PPO
-        epoch (the source is evaluated again before every replay).  None, or a constant matrix: today's sequence of
-        calls, verbatim.  ``max_grad_norm`` keeps covering the flat parameter buffer only: the graph's leaves are
-        not part of the clipped norm."""
+        ``torch.optim.Adam(model.comm_parameters(), lr=comm_lr)`` - in ``train_step`` with or without the entropy bonus
+        and in every PPO epoch (the source is evaluated again before every replay): ``fused.apply_update``.  None, or a
+        constant matrix: ``episode_backward`` is called without ``d_comm`` and nothing more is launched.
+        ``max_grad_norm`` keeps covering the flat parameter buffer only: the graph's leaves are not part of the
+        clipped norm."""
         if not entropy_coef >= 0.0:
             raise ValueError(f"entropy_coef must be >= 0, got {entropy_coef}")
         check_ppo_options(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
@@ -100,75 +102,38 @@ class Trainer:
                                              self.__comm_lr)
         return self.__comm_update
 
-    def __backward_and_adam(self, eng, flat, gp, gl, gv, g_probs=None) -> None:
-        """backward -> [all-reduce] -> Adam -> re-pack of the A2C steps.  Under a live communication source with a
-        ``comm_lr`` the backward also writes d_comm and the source's leaves take their Adam step after the flat one;
-        otherwise the calls are the ones this step has always made."""
-        comm = self.__comm()
-        bucketed = hasattr(self.__allreduce, "before_backward")  # parallel.BucketedGradAllReduce
-        if bucketed:
-            self.__allreduce.before_backward(eng)
-        try:
-            if comm is None:
-                eng.episode_backward(gp, gl, gv, flat.grad_views(), g_probs=g_probs)
-            else:
-                eng.episode_backward(gp, gl, gv, flat.grad_views(), g_probs=g_probs, d_comm=comm.buffer(eng))
-        finally:
-            if bucketed:
-                self.__allreduce.after_backward(eng)
-        scale = 1.0 if self.__allreduce is None else self.__allreduce(flat.grads)
-        flat.step += 1
-        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, self.__lr, grad_scale=scale)
-        if comm is not None:
-            comm.step(eng.comm_live, self.__allreduce, scale)
-        self.__model.mark_updated(eng)
+    def __exact_phases(self, call: Callable[[int], Tuple[th.Tensor, ...]]) -> None:
+        """``call(phase)`` (``a2c_loss`` / ``advantages``; adv_stats = result[4]) in one piece, or - with an
+        ``exact_standardize_group`` - around one 3-double all-reduce: global mean / std of the advantages (the only
+        batch-wide statistic: phase 1 leaves the entropy alone)."""
+        if self.__exact_group is None:
+            call(0)
+            return
+        from ..parallel import allreduce_adv_stats
+
+        allreduce_adv_stats(call(1)[4], self.__exact_group)
+        call(2)
 
     # one optimisation step on a batch (reference trainer.py:67-116)
     def train_step(self, x: th.Tensor, y: th.Tensor, sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
         model = self.__model
-        device = model.device
-        y = y.to(device)
+        y = y.to(model.device)
         if self.__ppo:
             return self.__train_step_ppo(x, y, sampler)
-        if self.__entropy_coef > 0:
-            return self.__train_step_entropy(x, y, sampler)
-        eng, out = sampler.run_episode_raw(x, train=True)
-        if self.__loss_bufs is None or self.__loss_bufs[0].shape != out.step_preds.shape:
-            self.__loss_bufs = (
-                th.empty_like(out.step_preds), th.empty_like(out.step_log_probas),
-                th.empty_like(out.step_values), th.zeros(4, device=device),
-                th.zeros(3, dtype=th.float64, device=device),
-            )
-        if self.__exact_group is None:
-            gp, gl, gv, scalars, _ = eng.a2c_loss(out, y, self.__gamma, 0, self.__loss_bufs)
-        else:  # global mean / std of the advantages: one 3-double all-reduce between phases
-            from ..parallel import allreduce_adv_stats
-
-            _, _, _, _, stats = eng.a2c_loss(out, y, self.__gamma, 1, self.__loss_bufs)
-            allreduce_adv_stats(stats, self.__exact_group)
-            gp, gl, gv, scalars, _ = eng.a2c_loss(out, y, self.__gamma, 2, self.__loss_bufs)
-        self.__backward_and_adam(eng, model.flat_state(), gp, gl, gv)
-        return out, scalars
-
-    def __train_step_entropy(self, x: th.Tensor, y: th.Tensor,
-                             sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
-        """train_step with the entropy bonus: the same sequence through the three entries that carry the step
-        distributions (scalars[4] = the mean entropy)."""
-        model, beta, gamma = self.__model, self.__entropy_coef, self.__gamma
-        eng, out = sampler.run_episode_raw(x, train=True, probs=True)
-        if (self.__loss_bufs is None or len(self.__loss_bufs) != 6 or
-                self.__loss_bufs[5].shape != out.step_probs.shape or self.__loss_bufs[0].shape != out.step_preds.shape):
-            self.__loss_bufs = eng.new_loss_bufs(out, True)
-        if self.__exact_group is None:
-            gp, gl, gv, scalars, _, gpr = eng.a2c_loss(out, y, gamma, 0, self.__loss_bufs, entropy_coef=beta)
-        else:  # (phase 1 leaves the entropy alone: only the advantages have a batch-wide statistic)
-            from ..parallel import allreduce_adv_stats
-
-            stats = eng.a2c_loss(out, y, gamma, 1, self.__loss_bufs, entropy_coef=beta)[4]
-            allreduce_adv_stats(stats, self.__exact_group)
-            gp, gl, gv, scalars, _, gpr = eng.a2c_loss(out, y, gamma, 2, self.__loss_bufs, entropy_coef=beta)
-        self.__backward_and_adam(eng, model.flat_state(), gp, gl, gv, g_probs=gpr)
-        return out, scalars
+        # with the entropy bonus: the same sequence through the three entries that carry the step distributions
+        # (scalars[4] = the mean entropy)
+        beta = self.__entropy_coef
+        ent = beta > 0
+        eng, out = sampler.run_episode_raw(x, train=True, probs=ent)
+        bufs = self.__loss_bufs
+        if (bufs is None or len(bufs) != (6 if ent else 5) or bufs[0].shape != out.step_preds.shape or
+                (ent and bufs[5].shape != out.step_probs.shape)):
+            bufs = self.__loss_bufs = eng.new_loss_bufs(out, ent)
+        self.__exact_phases(lambda phase: eng.a2c_loss(out, y, self.__gamma, phase, bufs, entropy_coef=beta))
+        flat = model.flat_state()
+        apply_update(eng, flat, bufs[0], bufs[1], bufs[2], bufs[5] if ent else None, flat.grad_views(), self.__lr,
+                     self.__allreduce, None, lambda: model.mark_updated(eng), self.__comm())
+        return out, bufs[3]
 
     def __train_step_ppo(self, x: th.Tensor, y: th.Tensor,
                          sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
@@ -183,14 +148,7 @@ class Trainer:
         if not ppo_bufs_fit(self.__ppo_bufs, out, ent):
             self.__ppo_bufs = eng.new_ppo_bufs(out, ent)
         bufs = self.__ppo_bufs
-        if self.__exact_group is None:
-            eng.advantages(out, y, self.__gamma, self.__gae_lambda, 0, bufs)
-        else:  # global mean / std of the advantages: one 3-double all-reduce between phases
-            from ..parallel import allreduce_adv_stats
-
-            eng.advantages(out, y, self.__gamma, self.__gae_lambda, 1, bufs)
-            allreduce_adv_stats(bufs[4], self.__exact_group)
-            eng.advantages(out, y, self.__gamma, self.__gae_lambda, 2, bufs)
+        self.__exact_phases(lambda phase: eng.advantages(out, y, self.__gamma, self.__gae_lambda, phase, bufs))
         flat = model.flat_state()
         norm = ppo_epochs_loop(
             eng, flat, out, y, bufs, self.__ppo_epochs, self.__ppo_clip, beta, self.__lr, self.__allreduce,

@@ -184,6 +184,92 @@ def test_ppo_loss_matches_float64_autograd(device, name, eps, beta):
         assert th.equal(bufs[j], again[j]), "two runs differ"
 
 
+# ---- 2b: where the extra per-block partials live ------------------------------------------------------------------
+# (Ns, Na, Nb): one block with an odd error count in front of the 8-byte alignment of the spare floats; exactly one
+# full block; a second block with four rows (the partials move to the place of the rewards)
+PARTIAL_SIZES = [(3, 1, 1), (1, 2, 128), (1, 2, 130)]
+
+
+def _synthetic_outputs(k, ns, na, nb, seed):
+    from marlclassification_amd.engine import EpisodeTensors
+
+    gen = th.Generator().manual_seed(seed)
+    c = k.cfg
+    preds = th.randn(ns, na, nb, c.nb_class, generator=gen)
+    values = th.randn(ns, na, nb, generator=gen)
+    probs = th.randn(ns, na, nb, c.nb_action, generator=gen).softmax(-1)
+    act = th.randint(c.nb_action, (ns, na, nb), generator=gen)
+    logp = probs.gather(-1, act.unsqueeze(-1)).squeeze(-1).log()
+    y = th.randint(c.nb_class, (nb,), generator=gen)
+    return EpisodeTensors(preds, logp, values, th.zeros(ns, na, nb, 2, dtype=th.int64), act, probs), y
+
+
+@pytest.mark.parametrize("size", PARTIAL_SIZES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("name", ["g1", "wide"])
+def test_losses_match_float64_at_the_partial_placement_sizes(device, name, size):
+    """a2c_loss with the bonus, advantages and ppo_loss on synthetic episode outputs at the sizes where the extra
+    per-block partials change place (one block: the spare floats behind the vote error; more: the rewards' place),
+    with four actions (float4 rows) and six (scalar rows), against the float64 references above."""
+    from marlclassification_amd.engine import EpisodeTensors, HipEngine
+
+    k = Case(name)
+    ns, na, nb = size
+    gamma, lam, beta = 0.97, 0.9, 0.05
+    eng = HipEngine(model_spec(k.cfg), device)
+    eng.configure(na, nb, ns, k.img.shape[1:])
+    host, y = _synthetic_outputs(k, ns, na, nb, 1000 + ns * na * nb)
+    out = EpisodeTensors(*(t.to(device) for t in (host.step_preds, host.step_log_probas, host.step_values,
+                                                  host.step_pos, host.step_actions, host.step_probs)))
+    yd = y.to(device)
+    tag = f"partials/{name}/{ns}x{na}x{nb}"
+
+    def leaves():
+        return [t.double().requires_grad_() for t in (host.step_preds, host.step_log_probas, host.step_values,
+                                                      host.step_probs)]
+
+    # the A2C entry with the bonus: its entropy partial is the one the unified placement moved
+    a2c = [t.clone() for t in eng.a2c_loss(out, yd, gamma, entropy_coef=beta)]
+    lv = leaves()
+    lo = mo.a2c_loss(lv[0], lv[1], lv[2], y, gamma)
+    ent = masked_entropy(lv[3])
+    loss = lo.loss - beta * ent.sum(0).mean()
+    loss.backward()
+    ref_scalars = th.stack([loss, lo.path, lo.error, lo.critic, ent.mean()]).detach()
+    for j, what in enumerate(("loss", "path", "error", "critic", "entropy")):
+        _close_fwd(a2c[3][j], ref_scalars[j], f"{tag}/a2c/scalar_{what}")
+    for got, leaf, what in zip((a2c[0], a2c[1], a2c[2], a2c[5]), lv, ("g_preds", "g_logp", "g_values", "g_probs")):
+        _close_grad(got, leaf.grad, f"{tag}/a2c/{what}")
+    for a, b in zip(a2c, eng.a2c_loss(out, yd, gamma, entropy_coef=beta)):
+        assert th.equal(a, b), "two a2c_loss runs differ"
+
+    adv = [t.clone() for t in eng.advantages(out, yd, gamma, lam)]
+    advn64, ret64, _ = ref_advantages(host.step_preds.double(), host.step_values.double(), y, gamma, lam)
+    _close_fwd(adv[5], advn64, f"{tag}/advn")
+    _close_fwd(adv[6], ret64, f"{tag}/ret")
+    again = eng.advantages(out, yd, gamma, lam)
+    for j in (4, 5, 6):
+        assert th.equal(adv[j], again[j]), "two advantages runs differ"
+
+    advn, ret = adv[5], adv[6]
+    old_logp = out.step_log_probas - ratio_deltas(out.step_log_probas.shape).float().to(device)
+    for eps in (0.1, 0.3):
+        bufs = [t.clone() for t in eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)]
+        lv = leaves()
+        loss, ref_scalars, rho, _ = ref_ppo(*lv, y, old_logp.double().cpu(), advn.double().cpu(), ret.double().cpu(),
+                                            eps, beta)
+        assert_clear_of_bounds(rho, eps)
+        loss.backward()
+        for j, what in enumerate(SCALARS):
+            _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/eps{eps}/scalar_{what}")
+        assert bufs[3][6].item() == ref_scalars[6].float().item(), "clip_frac is a count: it must be exact"
+        for got, leaf, what in zip((bufs[0], bufs[1], bufs[2], bufs[7]), lv, ("g_preds", "g_logp", "g_values",
+                                                                               "g_probs")):
+            _close_grad(got, leaf.grad, f"{tag}/eps{eps}/{what}")
+        again = eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)
+        for j in (0, 1, 2, 3, 7):
+            assert th.equal(bufs[j], again[j]), "two ppo_loss runs differ"
+
+
 # ---- 3: exactly zero probabilities ----------------------------------------------------------------------------------
 def test_zero_probabilities_give_finite_scalars_and_gradients(device):
     k = Case("g1")
