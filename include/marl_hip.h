@@ -294,6 +294,28 @@ int marl_comm_grad(const marl_config* cfg, const void* weights_ws, size_t weight
                    const void* ws, size_t ws_bytes, int nb_steps, float* d_comm,
                    void* scratch, size_t scratch_bytes, void* stream);
 
+/* Range-limited communication (same ABI version: one added entry, nothing else moves).  While a radius >= 0 is
+ * installed (per-process state, like the matrix; radius < 0 clears it) the matrix of marl_comm_matrix is the BASE B
+ * of a dynamic graph: in image b, for the message emitted in step t, agent a hears agent a' only if the two are within
+ * `radius` pixels at the positions of step t (window corners; MARL_COMM_CHEBYSHEV: max(|dy|, |dx|) <= radius;
+ * MARL_COMM_EUCLIDEAN: dy^2 + dx^2 <= radius^2 - integer arithmetic, exact).  The weights are
+ *     u[a, a'] = B[a, a'] * g[a, a']          (g[a, a] = 1: B's diagonal decides self-loops)
+ *     w = u                                    normalize == 0
+ *     w[a, a'] = u[a, a'] * (S_a / s_a)        normalize != 0, S_a = sum_a'' B[a, a''], s_a = sum_a'' u[a, a''] (fp32,
+ *                                              ascending); s_a <= 0: the row is 0, the receiver hears nothing
+ * (normalize expects B >= 0; the caller checks).  The message step t emits is encoded from the belief after observing at
+ * POS[t] and aggregated - for the decoder of step t + 1 - under the gate of POS[t]; the zero message of step 0 under
+ * POS[0].  The mixing stays one fmaf chain over the senders, ascending, exact zeros skipped; the backward applies the
+ * transpose of the same per-(step, image) matrix, rebuilt from the saved positions by the same arithmetic.  The chained
+ * panel launches build the matrices of their images in LDS (the GATE instantiations); the decoder of step 0, the
+ * unchained panel path and the GEMM + row-kernel path take mix_msg_gated_kernel.  marl_plan_query key "comm_range": the
+ * radius, or -1.  MARL_EINVAL: an unknown metric; and, each before anything is enqueued, an episode entry under a range
+ * without a matrix, marl_step_forward* / marl_step_backward under a range (a single step has no integer positions of
+ * the emission step) and marl_comm_grad under a range. */
+#define MARL_COMM_CHEBYSHEV 0
+#define MARL_COMM_EUCLIDEAN 1
+int marl_comm_range(int radius, int metric, int normalize);
+
 /* Loss of Trainer.train_epoch (training/trainer.py:76-111; training/functions.py:7-55)
  * and its gradient w.r.t. the episode outputs in one pass.
  * y int64 [Nb].  scalars_out[4] = {loss, path, error, critic} (trainer.py:111,119-122).

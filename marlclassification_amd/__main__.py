@@ -6,7 +6,7 @@ import argparse
 import re
 from os.path import abspath, dirname, join
 
-from .comm import check_spelling
+from .comm import check_spelling, parse_range
 from .config import EvalConfig, InferConfig, MainConfig, ModelConfig, TrainConfig
 from .networks.vision import CNN_BY_NAME
 
@@ -94,12 +94,25 @@ def build_parser() -> argparse.ArgumentParser:
                         help="communication graph of the message exchange: full | none | ring[:k] | star[:hub] | "
                              "grid:RxC | teams:a,b,... | FILE.npy ([Na,Na], row = receiver); default: the mean over "
                              "the other agents (test / infer: what marl.json names)")
+        sp.add_argument("--comm-range", type=_comm_range_arg, default=None, dest="comm_range",
+                        metavar="R[:METRIC][:raw]",
+                        help="range-limited communication: an agent hears the agents within R pixels of it, per "
+                             "image and step (METRIC chebyshev - the default - or euclidean; --comm, default full, is "
+                             "the base whose out-of-range links are cut; a receiver's remaining weights are rescaled "
+                             "to the base row's sum unless :raw); default: off (test / infer: what marl.json names)")
     return p
 
 
 def _comm_arg(text: str) -> str:
     try:
         return check_spelling(text)
+    except ValueError as err:
+        raise argparse.ArgumentTypeError(str(err))
+
+
+def _comm_range_arg(text: str) -> str:
+    try:
+        return parse_range(text).spelling()
     except ValueError as err:
         raise argparse.ArgumentTypeError(str(err))
 
@@ -114,6 +127,8 @@ def check_learn_comm(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--comm-lr must be > 0")
     if args.learn_comm and args.comm == "none":
         parser.error("--learn-comm needs a graph with links to learn on: --comm none has no support")
+    if args.learn_comm and args.comm_range is not None:
+        parser.error("--learn-comm with --comm-range: the gradient of a gated base matrix is not computed")
 
 
 def main(argv=None) -> None:
@@ -132,7 +147,7 @@ def main(argv=None) -> None:
             hidden_size_msg_output=args.n_m_o, hidden_size_state=args.n_d, state_dim=args.dim,
             actions=parse_actions(args.action, args.dim), nb_class=args.nb_class,
             hidden_size_linear_belief=args.n_l_b, hidden_size_linear_action=args.n_l_a,
-            comm=args.comm,
+            comm=args.comm, comm_range=args.comm_range,
         )
         train_config = TrainConfig(
             img_size=args.img_size, nb_epoch=args.nb_epoch, learning_rate=args.learning_rate,
@@ -148,7 +163,7 @@ def main(argv=None) -> None:
         eval_main(main_config, EvalConfig(
             img_size=args.img_size, state_dict_path=args.state_dict_path, batch_size=args.batch_size,
             json_path=args.json_path, dataset_path=args.dataset_path, output_dir=args.output_dir,
-            comm=args.comm))
+            comm=args.comm, comm_range=args.comm_range))
     elif args.main_choice == "infer":
         import os
 
@@ -160,7 +175,7 @@ def main(argv=None) -> None:
         infer_main(main_config, InferConfig(
             state_dict_path=args.state_dict_path, json_path=args.json_path, images_path=args.infer_images,
             output_dir=args.output_image_dir, class_to_idx=args.class_to_idx, saliency=args.saliency,
-            comm=args.comm))
+            comm=args.comm, comm_range=args.comm_range))
 
 
 if __name__ == "__main__":

@@ -79,7 +79,7 @@ EXPORTS = (
     "marl_step_forward_train marl_step_backward marl_episode_backward_img "
     "marl_episode_forward_probs marl_episode_backward_probs marl_a2c_loss_entropy_fwd_bwd "
     "marl_advantages marl_ppo_loss_fwd_bwd marl_grad_clip marl_comm_matrix "
-    "marl_comm_grad marl_comm_grad_scratch_bytes"
+    "marl_comm_grad marl_comm_grad_scratch_bytes marl_comm_range"
 ).split()
 
 _lib: Optional[C.CDLL] = None
@@ -165,6 +165,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_comm_grad_scratch_bytes.restype = _sz
     lib.marl_comm_grad_scratch_bytes.argtypes = [_cfgp]
     lib.marl_comm_grad.argtypes = [_cfgp, _vp, _sz, _vp, _sz, _i, _vp, _vp, _sz, _vp]
+    lib.marl_comm_range.argtypes = [_i, _i, _i]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("marl_abi_version", "marl_tune_get"):

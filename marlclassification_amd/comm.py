@@ -12,7 +12,7 @@ row-normalised by degree (every neighbour weighs 1 / degree, an agent without ne
 from __future__ import annotations
 
 import re
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import torch as th
 from torch import nn
@@ -171,6 +171,83 @@ def check_spelling(text: str) -> str:
 
 
 Graph = Union[str, th.Tensor, None]
+
+
+# ---- range-limited communication: the graph follows the agents ------------------------------------------------------
+METRICS = ("chebyshev", "euclidean")  # (the library's MARL_COMM_CHEBYSHEV / MARL_COMM_EUCLIDEAN, in this order)
+
+
+class CommRange(NamedTuple):
+    """``set_comm_range``'s setting: agents hear each other within ``radius`` pixels (window corners)."""
+
+    radius: int
+    metric: str = "chebyshev"
+    normalize: bool = True
+
+    @property
+    def metric_id(self) -> int:
+        return METRICS.index(self.metric)
+
+    def spelling(self) -> str:
+        """The command-line form ``R[:metric][:raw]`` (``parse_range`` reads it back)."""
+        return (str(self.radius) + ("" if self.metric == "chebyshev" else ":" + self.metric) +
+                ("" if self.normalize else ":raw"))
+
+
+def check_range(radius, metric: str = "chebyshev", normalize: bool = True) -> CommRange:
+    """The setting as a ``CommRange``; ValueError for a radius that is not an integer >= 0 (below 2^31) or an unknown
+    metric."""
+    if not isinstance(radius, int) or isinstance(radius, bool) or not 0 <= radius < 2 ** 31:
+        raise ValueError(f"communication range: the radius must be an integer >= 0 (pixels), got {radius!r}")
+    if metric not in METRICS:
+        raise ValueError(f'communication range: unknown metric {metric!r} ("chebyshev" or "euclidean")')
+    return CommRange(radius, metric, bool(normalize))
+
+
+def check_range_base(base: th.Tensor, normalize: bool) -> None:
+    """``normalize`` rescales a receiver's in-range weights to the row sum of the base: that needs a base >= 0."""
+    if normalize and bool((base < 0).any()):
+        raise ValueError("communication range with normalize=True needs a base matrix >= 0 (a row's in-range weights "
+                         "are rescaled to the row's sum); use normalize=False for signed weights")
+
+
+def parse_range(text: str) -> CommRange:
+    """The command-line spelling ``R[:chebyshev|euclidean][:raw]`` (``raw``: normalize=False)."""
+    m = re.fullmatch(rf"({_INT})(?::(chebyshev|euclidean))?(?::(raw))?", text) if isinstance(text, str) else None
+    if not m:
+        raise ValueError(f'unknown communication range "{text}" (R[:chebyshev|euclidean][:raw], R in pixels)')
+    return check_range(int(m.group(1)), m.group(2) or "chebyshev", m.group(3) is None)
+
+
+def range_matrices(base, pos, radius: int, metric: str = "chebyshev", normalize: bool = True) -> th.Tensor:
+    """The mixing matrices of a range-limited exchange, ``[..., Na, Na]`` fp32 (row = receiver), for positions ``pos``
+    ``[Na, ..., 2]`` (integers; the layout of ``step_pos[t]``: agents first): ``base[a, a']`` (None: ``full(Na)``)
+    where agents a and a' are within ``radius`` pixels of each other - chebyshev: max(|dy|, |dx|) <= radius, euclidean:
+    dy^2 + dx^2 <= radius^2 -, 0 elsewhere; an agent is always in range of itself, so the base's diagonal decides
+    self-loops.  ``normalize``: every row is rescaled by S_a / s_a (S_a the row sum of the base, s_a of its in-range
+    part), a row with s_a <= 0 is all zero - for ``full`` the mean over the in-range other agents.  This is what the
+    fused episode builds in its kernels per (step, image) from the positions of the step that emitted the message; here
+    in plain torch, for users, documentation and visualisation."""
+    r = check_range(radius, metric, normalize)
+    pos = th.as_tensor(pos)
+    if pos.dim() < 2 or pos.shape[-1] != 2 or pos.is_floating_point() or pos.is_complex() or pos.dtype == th.bool:
+        raise ValueError(f"positions must be an integer tensor [Na, ..., 2], got {pos.dtype} {tuple(pos.shape)}")
+    na = pos.shape[0]
+    b = full(na) if base is None else validate(base, na)
+    check_range_base(b, r.normalize)
+    p = pos.to(th.int64).movedim(0, -2)                      # [..., Na, 2]
+    d = (p.unsqueeze(-2) - p.unsqueeze(-3)).abs()            # [..., Na(receiver), Na(sender), 2]
+    if r.metric == "chebyshev":
+        gate = d.amax(dim=-1) <= r.radius
+    else:
+        gate = (d * d).sum(dim=-1) <= r.radius * r.radius
+    b = b.to(p.device)
+    u = th.where(gate, b, th.zeros_like(b))
+    if not r.normalize:
+        return u
+    big, small = b.sum(dim=-1, keepdim=True), u.sum(dim=-1, keepdim=True)
+    ok = small > 0
+    return th.where(ok, u * (big / th.where(ok, small, th.ones_like(small))), th.zeros_like(u))
 
 
 # ---- live sources: a matrix that is learned -------------------------------------------------------------------------

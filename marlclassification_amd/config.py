@@ -42,11 +42,16 @@ class ModelConfig(BaseModel):
     # communication graph in the command-line spelling (comm.parse: full | none | ring[:k] | star[:hub] | grid:RxC |
     # teams:a,b,... | FILE.npy); None: the reference's mean over the other agents - and the reference's marl.json
     comm: Optional[str] = None
+    # range-limited communication in the command-line spelling (comm.parse_range: R[:chebyshev|euclidean][:raw]);
+    # None: off - and the key is not written
+    comm_range: Optional[str] = None
 
     def save_marl_config(self, out_json_path: str) -> None:
         raw = {k: getattr(self, k) for k in _MODEL_KEYS}
         if self.comm is not None:  # (only when one was given: a default run writes the reference's file)
             raw["comm"] = self.comm
+        if self.comm_range is not None:
+            raw["comm_range"] = self.comm_range
         with open(out_json_path, "w", encoding="utf-8") as f:
             json.dump(raw, f)
 
@@ -55,7 +60,7 @@ class ModelConfig(BaseModel):
         assert exists(json_path) and isfile(json_path), f'"{json_path}" does not exist or is not a file'
         with open(json_path, "r", encoding="utf-8") as f:
             raw = json.load(f)
-        return cls(**{k: raw[k] for k in _MODEL_KEYS}, comm=raw.get("comm"))
+        return cls(**{k: raw[k] for k in _MODEL_KEYS}, comm=raw.get("comm"), comm_range=raw.get("comm_range"))
 
     def build_networks(self) -> ModelsWrapper:
         assert self.ft_extr_str in CNN_BY_NAME, (
@@ -78,6 +83,10 @@ class ModelConfig(BaseModel):
             from . import comm as _comm
 
             networks.set_comm(_comm.parse(self.comm, nb_agents))  # (moves with networks.to(device))
+        if self.comm_range is not None:
+            from . import comm as _comm
+
+            networks.set_comm_range(*_comm.parse_range(self.comm_range))
         return networks, MultiAgent(nb_agents, networks), self.build_environment()
 
 
@@ -111,6 +120,7 @@ class EvalConfig(BaseModel):
     dataset_path: str
     output_dir: str
     comm: Optional[str] = None  # --comm: replaces the graph marl.json names (None: keep it)
+    comm_range: Optional[str] = None  # --comm-range: replaces the range marl.json names (None: keep it)
 
 
 class InferConfig(BaseModel):
@@ -121,3 +131,4 @@ class InferConfig(BaseModel):
     class_to_idx: str
     saliency: bool = False  # also write saliency.png (|d logit / d pixel|) next to the step frames
     comm: Optional[str] = None  # --comm: replaces the graph marl.json names (None: keep it)
+    comm_range: Optional[str] = None  # --comm-range: replaces the range marl.json names (None: keep it)

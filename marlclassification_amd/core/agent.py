@@ -45,6 +45,7 @@ class MultiAgent:
         if self.__hidden is None:
             self.reset(observation.shape[1])
         model = self.__model
+        model.check_no_comm_range("MultiAgent.act")
         na, nb = observation.shape[:2]
         eng = model.hip_engine(None)
         eng.configure(na, nb, 1, (observation.shape[2], observation.shape[3] + 1,

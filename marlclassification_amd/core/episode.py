@@ -62,6 +62,7 @@ class _EpisodeFunction(th.autograd.Function):
         ctx.eng, ctx.ws, ctx.img = eng, ws, img
         ctx.cfg_key = eng._cfg_key
         ctx.comm = eng.comm  # the backward goes through the transpose of THIS rollout's matrix, whatever is set by then
+        ctx.comm_range = eng.comm_range  # (likewise the range: the backward rebuilds THIS rollout's gates)
         ctx.comm_dtype = None if comm is None else comm.dtype
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
@@ -81,6 +82,7 @@ class _EpisodeFunction(th.autograd.Function):
                                "its backward needs the weights the rollout used - call backward before "
                                "the optimiser step")
         later_comm, eng.comm = eng.comm, ctx.comm
+        later_range, eng.comm_range = eng.comm_range, ctx.comm_range
         try:
             if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
                 na, nb, ns, shape, u8 = ctx.cfg_key
@@ -101,6 +103,7 @@ class _EpisodeFunction(th.autograd.Function):
                 d_comm = d_comm.to(ctx.comm_dtype)
         finally:
             eng.comm = later_comm
+            eng.comm_range = later_range
         eng.train_ws_release(ctx.ws)
         ctx.ws = None
         # (a frozen model: the parameter gradients are computed and dropped here)

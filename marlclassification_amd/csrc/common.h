@@ -412,6 +412,59 @@ int launch_agg_msg(const float* m, float* out, int ld, int na, int nb, int n, hi
 int launch_mix_msg(const float* m, float* out, int ld, int na, int nb, int n, const float* mix, int transpose,
                    hipStream_t st);
 int mix_msg_max_agents();
+// range-limited communication (marl_comm_range): the mixing matrix is gated per image by the agents' positions,
+// w[a, a'] = B[a, a'] * g[a, a'] with g = 1 iff the two agents are within `radius` pixels of each other (metric 0:
+// Chebyshev max(|dy|, |dx|); 1: Euclidean on squared integers - exact either way), rescaled per receiver row by
+// S_a / s_a under `normalize` (S_a = sum_a'' B[a, a''], s_a = sum_a'' B[a, a''] g[a, a''], fp32, ascending; a row
+// with s_a <= 0 is all zero).  pos: int32 [na * nb][2] of the gating step (row a * nb + b); null = no gate.
+struct CommGate {
+    const int32_t* pos;
+    int radius, metric, normalize;
+};
+__device__ __forceinline__ bool comm_in_range(int2 p, int2 q, int radius, int metric) {
+    const int dy = p.x > q.x ? p.x - q.x : q.x - p.x, dx = p.y > q.y ? p.y - q.y : q.y - p.y;
+    if (metric) return (int64_t)dy * dy + (int64_t)dx * dx <= (int64_t)radius * radius;
+    return (dy > dx ? dy : dx) <= radius;
+}
+// w[a, a2] of batch element b.  Straight-line over MAXA >= na senders (clamped addresses, no loop to wait in).
+template <int MAXA>
+__device__ __forceinline__ float comm_gate_weight(const float* __restrict__ base, const CommGate& G, int na, int nb,
+                                                  int b, int a, int a2) {
+    const int2* __restrict__ pos = reinterpret_cast<const int2*>(G.pos);
+    const int2 pa = pos[(size_t)a * nb + b];
+    if (!G.normalize) {
+        const int2 q = pos[(size_t)a2 * nb + b];
+        const float bv = base[a * na + a2];
+        return comm_in_range(pa, q, G.radius, G.metric) ? bv : 0.f;
+    }
+    // (eight senders at a time: their loads fly together, and the panel kernels' head has no registers for sixteen)
+    constexpr int CH = MAXA < 8 ? MAXA : 8;
+    float S = 0.f, s = 0.f, u = 0.f;
+#pragma unroll
+    for (int j0 = 0; j0 < MAXA; j0 += CH) {
+        int2 q[CH];
+        float bv[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const int jj = j0 + j < na ? j0 + j : na - 1;
+            q[j] = pos[(size_t)jj * nb + b];
+            bv[j] = base[a * na + jj];
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            if (j0 + j < na) {
+                const float uj = comm_in_range(pa, q[j], G.radius, G.metric) ? bv[j] : 0.f;
+                S += bv[j];
+                s += uj;
+                if (j0 + j == a2) u = uj;
+            }
+        }
+    }
+    return s > 0.f ? u * (S / s) : 0.f;
+}
+// the same mixing under a gate: the matrices of the images a workgroup owns are built in LDS from `gate.pos`
+int launch_mix_msg_gated(const float* m, float* out, int ld, int na, int nb, int n, const float* mix,
+                         const CommGate& gate, int transpose, hipStream_t st);
 // gradient of the mixing matrix: out[a, a'] = sum over (t, b, k) of (dz_t * w)[a, b, k] * msg_t[a', b, k] for dz / msg
 // [steps * na * nb, ld] and the packed weight w [n2, ldw]; part: comm_grad_blocks(steps * nb) * na * na floats
 int comm_grad_blocks(int64_t pairs, int* per_out);
@@ -579,6 +632,9 @@ struct PanelFwdProb {
     // communication graph (marl_comm_matrix): non-null = the [g_na, g_na] mixing matrix (row = receiver) the agg_at
     // site applies instead of the mean: mbar[a] = sum_a' mix[a, a'] * m[a'], zero entries skipped
     const float* mix;
+    // range-limited communication (marl_comm_range): gate.pos non-null = mix is the base matrix and the workgroup
+    // builds the gated matrix of each of its by_batch images in LDS (row (i, a) at off_mix + (i * g_na + a) * g_na)
+    CommGate gate;
 };
 struct PanelFwdBatch {
     PanelFwdProb p[2];
@@ -749,6 +805,9 @@ struct PanelBwdProb {
     int cell_vec4;  // (filled by the launcher) the riding-along cell runs four units per thread
     // reported by the launcher: the gate-gradient images asked for (cellb.g3 / cell.g3) are written
     int cellb_img_done, cell_img_done;
+    // range-limited communication: gate.pos non-null = mix is the base matrix, gated per image (see PanelFwdProb) and
+    // stored transposed (behind the launcher's fields: no earlier member moves)
+    CommGate gate;
 #ifdef MARL_KERNEL_TS
     long long* ts;  // phase timestamps of one workgroup (debug builds only)
 #endif

@@ -625,6 +625,11 @@ static bool use_panels(const Dims& d);
 // and the panel kernels stage plain rows.
 static const float* g_comm = nullptr;
 static int g_comm_na = 0;
+// marl_comm_range: radius >= 0 = the matrix above is the BASE of a range-limited exchange - per image and step it is
+// gated by the agents' positions (CommGate, common.h).  The message emitted in step t (MSG[t + 1]) is aggregated under
+// the positions of its emission, POS[t]; the zero message of step 0 under POS[0].  The chained panel launches build
+// the gated matrices in their workgroups (the GATE instantiations), every other site takes mix_msg_gated_kernel.
+static CommGate g_range = {nullptr, -1, 0, 1};
 static bool use_side_stream();
 
 static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void* ews, size_t ebytes,
@@ -633,6 +638,10 @@ static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void
     if (g_comm && g_comm_na != c.d.na) {  // (before anything is enqueued)
         set_error("communication matrix is %d x %d but the configuration has %d agents", g_comm_na, g_comm_na,
                   c.d.na);
+        return MARL_EINVAL;
+    }
+    if (g_range.radius >= 0 && !g_comm) {
+        set_error("a communication range is installed without its base matrix (marl_comm_matrix)");
         return MARL_EINVAL;
     }
     make_wlayout(c.d, c.w);
@@ -773,6 +782,20 @@ static int step_cnn(const Ctx& c, int t, const StepIn& in) {
     return MARL_OK;
 }
 
+// the gate under which MSG[t] is aggregated (pos null: no range installed): the positions of its emission step
+static CommGate comm_gate(const Ctx& c, int t) {
+    CommGate g = g_range;
+    g.pos = g_range.radius >= 0 ? c.POSs(t > 0 ? t - 1 : 0) : nullptr;
+    return g;
+}
+// the exchange of MSG[t] (or, transpose, of its gradient) under the installed matrix, in a launch of its own
+static int mix_msg(const Ctx& c, int t, const float* m, float* out, int n, int transpose) {
+    const Dims& d = c.d;
+    if (g_range.radius >= 0)
+        return launch_mix_msg_gated(m, out, d.ld_nm, d.na, d.nb, n, g_comm, comm_gate(c, t), transpose, c.st);
+    return launch_mix_msg(m, out, d.ld_nm, d.na, d.nb, n, g_comm, transpose, c.st);
+}
+
 // the decoder's two layers of step t (outputs: AD1[t], U[t][:, nf:nf+n_mo])
 static void fill_dec_layers(const Ctx& c, int t, PanelLayer* layer) {
     const Dims& d = c.d;
@@ -811,7 +834,7 @@ static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, 
         p.agg_nb = d.nb;
         p.xbar = c.at(c.e.MBAR, t);
         if (g_comm) {  // mixed rows (pad columns included: the panel stages whole float4s) -> MBAR, staged as they are
-            MARL_TRY(launch_mix_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.ld_nm, g_comm, 0, st));
+            MARL_TRY(mix_msg(c, t, c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, 0));
             p.x = c.at(c.e.MBAR, t);
             p.agg_na = p.agg_nb = 0;
             p.xbar = nullptr;
@@ -827,7 +850,7 @@ static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, 
         return launch_panel_fwd(pb, st);
     }
     if (g_comm)
-        MARL_TRY(launch_mix_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.n_m, g_comm, 0, st));
+        MARL_TRY(mix_msg(c, t, c.MSGs(t), c.at(c.e.MBAR, t), d.n_m, 0));
     else
         MARL_TRY(launch_agg_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.n_m, st));
     MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.MBAR, t), d.ld_nm, c.wp(MARL_P_DEC_W0), p4(d.n_m), d.n_m,
@@ -1029,6 +1052,7 @@ static int step_chain(const Ctx& c, int t, const SampleArgs* sample = nullptr) {
         pe.xbar = c.at(c.e.MBAR, t + 1);
         pe.ld_xbar = d.ld_nm;
         pe.mix = g_comm;  // (null: the mean)
+        if (g_comm) pe.gate = comm_gate(c, t + 1);
     }
     fill_pol_prob(c, t, pb.p[1]);
     if (sample && use_panel_sample(d)) {
@@ -1705,6 +1729,7 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                     pd.nlayers = 4;
                     pd.agg_at = 2;
                     pd.mix = g_comm;  // (null: the self-adjoint mean; else the kernel applies M^T)
+                    if (g_comm) pd.gate = comm_gate(c, t);
                     pd.layer[2] = PanelBwdLayer{c.at(c.e.ZE2, t - 1), d.ld_nm, c.at(c.e.STE2, t - 1),
                                                 c.wp(MARL_P_ENC_LN1W), c.wp(MARL_P_ENC_LN1B), d.n_m,
                                                 c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm, d.ld_nm,
@@ -1739,8 +1764,7 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                 pe.agg_na = d.na;
                 pe.agg_nb = d.nb;
                 if (g_comm) {  // M^T in place (a thread owns one (batch, column) over all agents), then plain rows
-                    MARL_TRY(launch_mix_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.ld_nm, g_comm,
-                                            1, st));
+                    MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, 1));
                     pe.agg_na = pe.agg_nb = 0;
                 }
                 pe.m = R;
@@ -1779,7 +1803,7 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                                         c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
             float* dze2 = c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm;
             if (g_comm)  // the transpose of the mixing matrix
-                MARL_TRY(launch_mix_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, g_comm, 1, st));
+                MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), dze2, d.n_m, 1));
             else
                 MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, st));
             const int efirst = (t == ns - 1);
@@ -2329,6 +2353,19 @@ int marl_comm_matrix(const float* m_dev, int nb_agents) {
     return MARL_OK;
 }
 
+int marl_comm_range(int radius, int metric, int normalize) {
+    if (radius < 0) {
+        g_range = CommGate{nullptr, -1, 0, 1};
+        return MARL_OK;
+    }
+    if (metric != MARL_COMM_CHEBYSHEV && metric != MARL_COMM_EUCLIDEAN) {
+        set_error("comm_range: unknown metric %d", metric);
+        return MARL_EINVAL;
+    }
+    g_range = CommGate{nullptr, radius, metric, normalize != 0};
+    return MARL_OK;
+}
+
 size_t marl_comm_grad_scratch_bytes(const marl_config* cfg) {
     Dims d;
     if (make_dims(cfg, d) != MARL_OK) return 0;
@@ -2343,6 +2380,11 @@ int marl_comm_grad(const marl_config* cfg, const void* weights_ws, size_t weight
     }
     if (!g_comm) {
         set_error("comm_grad: no communication matrix installed (marl_comm_matrix)");
+        return MARL_EINVAL;
+    }
+    if (g_range.radius >= 0) {
+        set_error("comm_grad: a communication range is installed - the gradient of a gated base matrix is not "
+                  "computed");
         return MARL_EINVAL;
     }
     if (nb_steps < 1) {
@@ -2612,6 +2654,11 @@ static int step_forward(const marl_config* cfg, const void* weights_ws, size_t w
                         float* values, float* preds, float* new_msg, float* h_out, float* c_out, float* hc_out,
                         float* cc_out, const float* noise, uint64_t rng_seed, uint64_t rng_offset,
                         int64_t* actions_out, float* logp_out, int train, void* stream) {
+    if (g_range.radius >= 0) {  // (before anything is enqueued)
+        set_error("step_forward: a communication range is installed - a single step has no integer positions of "
+                  "the emission step; run the fused episode");
+        return MARL_EINVAL;
+    }
     Ctx c;
     SplitRegistryScope reg_scope;
     MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, train, stream, c));
@@ -2689,6 +2736,11 @@ int marl_step_backward(const marl_config* cfg, void* weights_ws, size_t weights_
                        float* d_msg, float* d_h, float* d_c, float* d_hc, float* d_cc, void* stream) {
     if (!cfg) {
         set_error("step_backward: null configuration");
+        return MARL_EINVAL;
+    }
+    if (g_range.radius >= 0) {  // (before anything is enqueued)
+        set_error("step_backward: a communication range is installed - a single step has no integer positions of "
+                  "the emission step; run the fused episode");
         return MARL_EINVAL;
     }
     marl_config one = *cfg;
@@ -2801,6 +2853,7 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     // ahead of a plain panel launch, 4 = mix_msg_kernel ahead of the GEMM path, 5 = mixed inside the chained panel
     // launch - the decoder of step 0 and the step API then take form 3); "panel_chain" = the chained launch
     else if (!strcmp(key, "comm")) *value = g_comm != nullptr;
+    else if (!strcmp(key, "comm_range")) *value = g_range.radius >= 0 ? g_range.radius : -1;  // the radius, or -1
     else if (!strcmp(key, "panel_chain")) *value = use_chain(d) && !use_side_stream();
     // the forward loop samples inside the chained launch (the policy workgroups' epilogue): no sample_kernel launch
     else if (!strcmp(key, "panel_sample")) *value = use_chain(d) && !use_side_stream() && use_panel_sample(d);

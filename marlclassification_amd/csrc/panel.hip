@@ -239,8 +239,9 @@ __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const fl
 // the sampling workgroups that ride along behind the panel ones (EPI = false) or for the sampling epilogue of the
 // workgroups of problem B.epi_prob - 1 (EPI = true: sample(t) inside the launch that computes policy(t))
 // MIX: the agg_at site mixes over a communication graph (P.mix) instead of taking the mean; the plain instantiations
-// carry none of it
-template <int SAMPLE, bool MIX = false, bool EPI = false>
+// carry none of it.  GATE (with MIX): the matrix is gated by the agents' positions (P.gate, marl_comm_range): one matrix
+// per image of the workgroup, built here from the base matrix P.mix; the constant-MIX instantiations carry none of it
+template <int SAMPLE, bool MIX = false, bool EPI = false, bool GATE = false>
 __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (!EPI && SAMPLE > 0 && (int)blockIdx.x >= B.panel_blocks) {
@@ -295,14 +296,19 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
     }
     // the mixing coefficients join the same batch of loads (g_na <= 16: one per thread of the first four waves)
     float cmv = 0.f;
-    if (MIX && P.mix && tid < P.g_na * P.g_na) cmv = P.mix[tid];
+    if (MIX && !GATE && P.mix && tid < P.g_na * P.g_na) cmv = P.mix[tid];
+    if (MIX && GATE && tid < bpb * P.g_na * P.g_na) {  // (by_batch * g_na^2 <= kPanelRows * g_na <= 256 entries)
+        const int na = P.g_na, i = tid / (na * na), e = tid - i * na * na, a = e / na;
+        const int b = (int)blockIdx.x * bpb + i;
+        if (b < P.g_nb) cmv = comm_gate_weight<kPanelRows>(P.mix, P.gate, na, P.g_nb, b, a, e - a * na);
+    }
 
     // ---- stage the 32-row input panel (zero-filled past k0 and past M)
     {
         const int k0 = P.k0, xs = panel_stride(k0), K16 = (k0 + 15) & ~15;
         const int c4 = K16 >> 2;
         const int K4 = (k0 + 3) & ~3;
-        if (P.agg_na > 0) {
+        if (!GATE && P.agg_na > 0) {  // (GATE: the launcher admits the agg_at site only)
             // message mean over the OTHER agents (networks/message.py:5-17), 4 loads in flight
             const int na = P.agg_na, nb = P.agg_nb;
             const float den = (float)(na - 1);
@@ -384,7 +390,8 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             }
         }
     }
-    if (MIX && P.mix && tid < P.g_na * P.g_na) lds[B.off_mix + tid] = cmv;
+    if (MIX && !GATE && P.mix && tid < P.g_na * P.g_na) lds[B.off_mix + tid] = cmv;
+    if (MIX && GATE && tid < bpb * P.g_na * P.g_na) lds[B.off_mix + tid] = cmv;
     MARL_TS();
     lds_barrier();
     MARL_TS();
@@ -418,7 +425,7 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
                         // communication graph: one fmaf chain over the senders, ascending; a sender whose
                         // coefficient is exactly 0 is not read (its NaN / Inf cannot leak through 0 * x)
                         if (a < na) {
-                            const float* crow = lds + B.off_mix + a * na;
+                            const float* crow = lds + B.off_mix + (GATE ? i * na + a : a) * na;
                             float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
                             for (int a2 = 0; a2 < na; ++a2) {
                                 const float cf = crow[a2];
@@ -571,10 +578,18 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
             set_error("panel kernel: a mixing matrix needs the in-panel aggregation of problem 0");
             return MARL_ELIMIT;
         }
+        // (the gated instantiations carry no staged mean, in any problem of the launch)
+        if ((p.gate.pos && (!p.mix || p.by_batch * p.g_na * p.g_na > kPanelRows * kPanelRows)) ||
+            (b.p[0].gate.pos && p.agg_na > 0)) {
+            set_error("panel kernel: a position gate needs a base matrix, no staged mean and by_batch * agents^2 <= %d",
+                      kPanelRows * kPanelRows);
+            return MARL_ELIMIT;
+        }
         x0 = s0 > x0 ? s0 : x0;
         x1 = s1 > x1 ? s1 : x1;
     }
     const bool mixed = b.count > 0 && b.p[0].mix != nullptr;
+    const bool gated = mixed && b.p[0].gate.pos != nullptr;
     if (waves < 4) waves = 4;  // the LayerNorm row loop covers <= 4 rows per wave
     b.off_panel1 = x0;
     b.off_red = x0 + x1;
@@ -597,12 +612,14 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
     }
     static bool raised = false;
     if (!raised) {
-        const void* kerns[6] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
+        const void* kerns[8] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<MARL_MAX_ACTIONS>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<0, true>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4, false, true>),
-                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true>)};
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<0, true, false, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true, true>)};
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
@@ -632,7 +649,10 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
     if (b.epi_prob) {
         // sample(t) as the epilogue of the policy workgroups: no ride-along workgroups
         b.has_sample = 0;
-        if (mixed)
+        if (gated)
+            hipLaunchKernelGGL((panel_fwd_kernel<4, true, true, true>), dim3(pblocks, (unsigned)b.count),
+                               dim3(64 * waves), lds, st, b);
+        else if (mixed)
             hipLaunchKernelGGL((panel_fwd_kernel<4, true, true>), dim3(pblocks, (unsigned)b.count), dim3(64 * waves),
                                lds, st, b);
         else
@@ -647,7 +667,10 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
             hipLaunchKernelGGL(panel_fwd_kernel<MARL_MAX_ACTIONS>, dim3(pblocks + sblocks, 1), dim3(64 * waves), lds, st, b);
     } else {
         b.has_sample = 0;
-        if (mixed)
+        if (gated)
+            hipLaunchKernelGGL((panel_fwd_kernel<0, true, false, true>), dim3(pblocks, (unsigned)b.count),
+                               dim3(64 * waves), lds, st, b);
+        else if (mixed)
             hipLaunchKernelGGL((panel_fwd_kernel<0, true>), dim3(pblocks, (unsigned)b.count), dim3(64 * waves),
                                lds, st, b);
         else
@@ -678,7 +701,9 @@ constexpr int kBwdMaxCols = kPanelMaxCols;  // columns per lane in the row pass:
 // encoder / decoder backward of the README dimensions has widths <= 128: two column slots instead of six
 // are a third of the row pass's instructions and 24 fewer registers.
 // MIX: the agg_at site applies the transpose of a communication graph's mixing matrix (P.mix) instead of the mean
-template <bool CELL, int MAXC, bool MIX = false>
+// GATE (with MIX): one matrix per image of the workgroup, gated by the positions of the forward's emission step (P.gate)
+// and built by the forward's arithmetic (comm_gate_weight), stored transposed
+template <bool CELL, int MAXC, bool MIX = false, bool GATE = false>
 __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (CELL && (int)blockIdx.x >= P.panel_blocks) {
@@ -748,9 +773,14 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
             }
         }
         float cmv = 0.f;  // M^T, oriented while it is loaded (row = the sender whose gradient is formed): requested
-        if (MIX && tid < P.g_na * P.g_na) {  // with the vectors above, stored behind them - one batch of loads
+        if (MIX && !GATE && tid < P.g_na * P.g_na) {  // with the vectors above, stored behind them - one batch of loads
             const int a = tid / P.g_na, a2 = tid - a * P.g_na;
             cmv = P.mix[a2 * P.g_na + a];
+        }
+        if (MIX && GATE && tid < bpb * P.g_na * P.g_na) {  // entry (i, a, a2) of the LDS copy = w_i[a2, a]
+            const int na = P.g_na, i = tid / (na * na), e = tid - i * na * na, a = e / na;
+            const int b = (int)blockIdx.x * bpb + i;
+            if (b < P.g_nb) cmv = comm_gate_weight<kPanelRows>(P.mix, P.gate, na, P.g_nb, b, e - a * na, a);
         }
         int off = 0;
 #pragma unroll
@@ -764,7 +794,8 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                 off += 2 * n;
             }
         }
-        if (MIX && tid < P.g_na * P.g_na) lds[P.off_mix + tid] = cmv;
+        if (MIX && !GATE && tid < P.g_na * P.g_na) lds[P.off_mix + tid] = cmv;
+        if (MIX && GATE && tid < bpb * P.g_na * P.g_na) lds[P.off_mix + tid] = cmv;
         const int n = P.layer[0].n, ds = panel_stride(n), n16 = (n + 15) & ~15, c4 = n16 >> 2;
         const int n4 = (n + 3) & ~3;
         for (int e = tid; e < kPanelRows * c4; e += blockDim.x) {
@@ -836,7 +867,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                         // the mixing matrix is not self-adjoint: dm[a] = sum_a2 M[a2, a] * dmbar[a2] (the LDS copy
                         // is M^T), one fmaf chain over a2 ascending, zero entries skipped
                         if (a < na) {
-                            const float* crow = lds + P.off_mix + a * na;
+                            const float* crow = lds + P.off_mix + (GATE ? i * na + a : a) * na;
                             float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
                             for (int a2 = 0; a2 < na; ++a2) {
                                 const float cf = crow[a2];
@@ -1133,6 +1164,11 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
         set_error("panel backward: a mixing matrix needs the in-panel aggregation");
         return MARL_ELIMIT;
     }
+    if (p.gate.pos && (!p.mix || p.by_batch * p.g_na * p.g_na > kPanelRows * kPanelRows)) {
+        set_error("panel backward: a position gate needs a base matrix and by_batch * agents^2 <= %d",
+                  kPanelRows * kPanelRows);
+        return MARL_ELIMIT;
+    }
     const size_t lds = (size_t)(p.off_mix + (p.mix ? kPanelRows * kPanelRows : 0)) * sizeof(float);
     if (p.agg_at > 0 && (p.by_batch < 1 || p.g_na * p.by_batch > kPanelRows || p.agg_at >= p.nlayers ||
                          !panel_chain_supported(p.g_na, p.layer[p.agg_at].n, 256))) {
@@ -1151,14 +1187,18 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
     }
     static bool raised = false;
     if (!raised) {
-        const void* kerns[8] = {reinterpret_cast<const void*>(panel_bwd_kernel<false, 2>),
+        const void* kerns[12] = {reinterpret_cast<const void*>(panel_bwd_kernel<false, 2>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<true, 2>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<false, 2, true>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<true, 2, true>),
                                 reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols, true>)};
+                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<false, 2, true, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<true, 2, true, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols, true, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols, true, true>)};
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
@@ -1184,7 +1224,17 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
             p.panel_blocks = (int)pblocks;
             cblocks = (unsigned)cdiv(p.cell_rows * (p.cell_vec4 ? p.cell.n / 4 : p.cell.n), 64 * waves);
         }
-        if (p.has_cell && maxc == 2)
+        if (p.gate.pos) {
+            if (p.has_cell && maxc == 2)
+                hipLaunchKernelGGL((panel_bwd_kernel<true, 2, true, true>), dim3(pblocks + cblocks), blk, lds, st, p);
+            else if (p.has_cell)
+                hipLaunchKernelGGL((panel_bwd_kernel<true, kBwdMaxCols, true, true>), dim3(pblocks + cblocks), blk, lds,
+                                   st, p);
+            else if (maxc == 2)
+                hipLaunchKernelGGL((panel_bwd_kernel<false, 2, true, true>), dim3(pblocks), blk, lds, st, p);
+            else
+                hipLaunchKernelGGL((panel_bwd_kernel<false, kBwdMaxCols, true, true>), dim3(pblocks), blk, lds, st, p);
+        } else if (p.has_cell && maxc == 2)
             hipLaunchKernelGGL((panel_bwd_kernel<true, 2, true>), dim3(pblocks + cblocks), blk, lds, st, p);
         else if (p.has_cell)
             hipLaunchKernelGGL((panel_bwd_kernel<true, kBwdMaxCols, true>), dim3(pblocks + cblocks), blk, lds, st, p);

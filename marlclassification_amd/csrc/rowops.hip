@@ -1121,6 +1121,98 @@ int launch_mix_msg(const float* m, float* out, int ld, int na, int nb, int n, co
 }
 
 // ---------------------------------------------------------------------------
+// the same mixing under a position gate (marl_comm_range): every image has its own matrix, w_b = gate_b(B) (common.h,
+// comm_gate_weight - the arithmetic the chained panel kernels use, so every kernel family sees the same bits).  A
+// workgroup owns `ipb` consecutive images: one thread per (image, receiver) builds that receiver's row from the row of
+// B and the image's na positions and stores it into LDS, already oriented (transpose: entry [a][a2] = w_b[a2, a]);
+// then one thread per (image, column) over ALL agents, as mix_msg_kernel: inputs in registers first (out == m is
+// legal), one fmaf chain over the senders ascending, exact zeros skipped.  No atomics: bit-reproducible.
+// ---------------------------------------------------------------------------
+constexpr int kMixGatedThreads = 256;
+constexpr int kMixGatedMaxLdsFloats = 8192;  // 32 KiB: ipb * na^2 matrices
+template <int NA>
+__global__ __launch_bounds__(kMixGatedThreads) void mix_msg_gated_kernel(const float* m, float* out, int ld, int na,
+                                                                         int nb, int n, const float* __restrict__ mix,
+                                                                         const CommGate gate, int transpose, int ipb) {
+    extern __shared__ __attribute__((aligned(16))) float coef[];  // [ipb][na][na]
+    const int b0 = (int)blockIdx.x * ipb;
+    for (int e = threadIdx.x; e < ipb * na; e += kMixGatedThreads) {
+        const int i = e / na, a = e - i * na, b = b0 + i;
+        if (b >= nb) continue;
+        const int2* __restrict__ pos = reinterpret_cast<const int2*>(gate.pos);
+        const int2 pa = pos[(size_t)a * nb + b];
+        float u[NA];
+        float S = 0.f, s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int jj = j < na ? j : na - 1;
+            const float bv = mix[a * na + jj];
+            u[j] = comm_in_range(pa, pos[(size_t)jj * nb + b], gate.radius, gate.metric) ? bv : 0.f;
+            if (j < na) {  // fp32, ascending: comm_gate_weight's sums
+                S += bv;
+                s += u[j];
+            }
+        }
+        const float scale = gate.normalize ? (s > 0.f ? S / s : 0.f) : 1.f;
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            if (j < na) {
+                const float w = gate.normalize ? (s > 0.f ? u[j] * scale : 0.f) : u[j];
+                coef[(i * na + (transpose ? j : a)) * na + (transpose ? a : j)] = w;
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < ipb * n; e += kMixGatedThreads) {
+        const int i = e / n, k = e - i * n, b = b0 + i;
+        if (b >= nb) break;
+        const size_t astr = (size_t)nb * ld, o0 = (size_t)b * ld + k;
+        const float* cf0 = coef + i * na * na;
+        float v[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) v[a] = a < na ? m[o0 + (size_t)a * astr] : 0.f;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            if (a < na) {
+                float acc = 0.f;
+#pragma unroll
+                for (int a2 = 0; a2 < NA; ++a2) {
+                    if (a2 < na) {
+                        const float cf = cf0[a * na + a2];
+                        if (cf != 0.f) acc = fmaf(cf, v[a2], acc);
+                    }
+                }
+                out[o0 + (size_t)a * astr] = acc;
+            }
+        }
+    }
+}
+
+int launch_mix_msg_gated(const float* m, float* out, int ld, int na, int nb, int n, const float* mix,
+                         const CommGate& gate, int transpose, hipStream_t st) {
+    if (!mix || !gate.pos || gate.radius < 0 || na < 1 || na > mix_msg_max_agents() || n > ld || n < 1 || nb < 1) {
+        set_error("gated message mixing: %d agents / %d columns outside the kernel's range (<= %d agents)", na, n,
+                  mix_msg_max_agents());
+        return MARL_ELIMIT;
+    }
+    // images per workgroup: enough for one pass of the threads over their columns, within the LDS budget
+    int ipb = kMixGatedThreads / n;
+    const int cap = kMixGatedMaxLdsFloats / (na * na);
+    ipb = ipb > cap ? cap : ipb;
+    ipb = ipb < 1 ? 1 : ipb > nb ? nb : ipb;
+    const size_t lds = (size_t)ipb * na * na * sizeof(float);
+    const dim3 grid((unsigned)cdiv(nb, ipb)), blk(kMixGatedThreads);
+    if (na <= 8)
+        hipLaunchKernelGGL(mix_msg_gated_kernel<8>, grid, blk, lds, st, m, out, ld, na, nb, n, mix, gate, transpose, ipb);
+    else if (na <= 16)
+        hipLaunchKernelGGL(mix_msg_gated_kernel<16>, grid, blk, lds, st, m, out, ld, na, nb, n, mix, gate, transpose, ipb);
+    else
+        hipLaunchKernelGGL(mix_msg_gated_kernel<32>, grid, blk, lds, st, m, out, ld, na, nb, n, mix, gate, transpose, ipb);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
+// ---------------------------------------------------------------------------
 // gradient of the mixing matrix (the derivative of networks/message.py:5-17 under a matrix, with respect to it):
 //     dM[a, a'] = sum_t sum_b sum_k dmbar_t[a, b, k] * m_t[a', b, k],   dmbar_t = dZ_t * W
 // from what a finished backward keeps: dZ [steps * R, lddz] (rows t * R + a * nb + b), the gradient of the decoder's

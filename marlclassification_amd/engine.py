@@ -216,6 +216,10 @@ class HipEngine:
         self.comm_source = None
         self.comm_live: Optional[th.Tensor] = None
         self._comm_scratch: Optional[th.Tensor] = None  # the partials of marl_comm_grad (pooled, grown on demand)
+        # range-limited communication (comm.CommRange, None = off): the matrix above - or comm.full(Na) without one -
+        # is the base the kernels gate per (step, image) by the agents' positions.  Installed and cleared with it.
+        self.comm_range = None
+        self._comm_full: Optional[th.Tensor] = None  # the base of a range without a matrix (cached per agent count)
 
     # -- communication graph ----------------------------------------------------------
     def set_comm(self, matrix) -> None:
@@ -228,6 +232,11 @@ class HipEngine:
         at every evaluation; finiteness is not - that would synchronise)."""
         from . import comm as _comm
 
+        if matrix is not None and self.comm_range is not None:
+            if _comm.is_live(matrix):
+                raise ValueError("a live (learnable) communication source under a communication range: the gradient "
+                                 "of a gated base matrix is not computed (set_comm_range(None) first)")
+            _comm.check_range_base(_comm.validate(matrix, None), self.comm_range.normalize)
         self.comm_source = self.comm_live = None
         if matrix is None:
             self.comm = None
@@ -243,6 +252,38 @@ class HipEngine:
             raise ValueError(f"communication matrix is {tuple(m.shape)} but the engine is configured for "
                              f"{self.cfg.nb_agents} agents")
         self.comm = m.clone()  # (never the caller's storage)
+
+    def set_comm_range(self, radius, metric: str = "chebyshev", normalize: bool = True) -> None:
+        """Range-limited communication for every later episode call of this engine: agents hear each other within
+        ``radius`` pixels (``comm.range_matrices`` has the semantics; None switches it off).  The matrix of
+        ``set_comm`` - ``comm.full(Na)`` without one - is the base; a live source cannot be gated, and
+        ``normalize=True`` needs a base >= 0: ValueError, from whichever call comes second.  The step calls
+        (``step_forward`` / ``step_backward``) raise under a range: only the fused episode knows the positions."""
+        from . import comm as _comm
+
+        if radius is None:
+            self.comm_range = None
+            return
+        r = _comm.check_range(radius, metric, normalize)
+        if self.comm_source is not None:
+            raise ValueError("a communication range under a live (learnable) communication source: the gradient of "
+                             "a gated base matrix is not computed (set_comm with a constant matrix first)")
+        if self.comm is not None:
+            _comm.check_range_base(self.comm, r.normalize)
+        self.comm_range = r
+
+    def _range_base(self) -> th.Tensor:
+        """The base matrix a range gates: this engine's matrix, or the complete graph of the configured agents."""
+        if self.comm is not None:
+            return self.comm
+        from . import comm as _comm
+
+        na = self.cfg.nb_agents
+        if na > _comm.MAX_AGENTS:
+            raise ValueError(f"communication range for {na} agents: at most {_comm.MAX_AGENTS} are supported")
+        if self._comm_full is None or self._comm_full.shape[0] != na:
+            self._comm_full = _comm.full(na).to(self.device)
+        return self._comm_full
 
     def refresh_comm(self) -> Optional[th.Tensor]:
         """Evaluates the live source (if there is one) for the forward that is about to run: ``comm`` becomes its
@@ -281,15 +322,19 @@ class HipEngine:
 
     def _agg(self, fn, *args) -> None:
         """A library call that aggregates messages: under this engine's matrix, if it has one."""
-        m = self.comm
+        r = self.comm_range
+        m = self.comm if r is None else self._range_base()
         if m is None:
             check(fn(*args))
             return
         check(self.lib.marl_comm_matrix(m.data_ptr(), m.shape[0]))
         try:
+            if r is not None:
+                check(self.lib.marl_comm_range(r.radius, r.metric_id, int(r.normalize)))
             check(fn(*args))
         finally:
             self.lib.marl_comm_matrix(None, 0)
+            self.lib.marl_comm_range(-1, 0, 1)
 
     def plan_query(self, key: str, train: bool = True) -> int:
         """marl_plan_query under this engine's communication matrix."""
@@ -493,6 +538,9 @@ class HipEngine:
         assert cfg is not None
         if d_comm is not None and self.comm is None:
             raise ValueError("episode_backward(d_comm=...): the engine has no communication matrix")
+        if d_comm is not None and self.comm_range is not None:
+            raise ValueError("episode_backward(d_comm=...): under a communication range the gradient of the base "
+                             "matrix is not computed")
         if g_probs is not None:
             want = (cfg.nb_steps, cfg.nb_agents, cfg.batch, cfg.nb_action)
             if not isinstance(g_probs, th.Tensor) or tuple(g_probs.shape) != want:

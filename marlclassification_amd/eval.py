@@ -30,6 +30,8 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
     marl_config = ModelConfig.load_marl_config(eval_config.json_path)
     if eval_config.comm is not None:
         marl_config.comm = eval_config.comm
+    if eval_config.comm_range is not None:
+        marl_config.comm_range = eval_config.comm_range
     nn_models, marl_m, env = marl_config.build_marl(main_config.nb_agent)
     nn_models.load_state_dict(th.load(eval_config.state_dict_path, map_location="cpu"))
     nn_models.eval()

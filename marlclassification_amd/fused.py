@@ -316,7 +316,8 @@ class FusedA2C:
         # re-laid-out - the graph must be captured again)
         beta = self.entropy_coef
         key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch, beta,
-               None if eng.comm is None else eng.comm.data_ptr())  # (the captured kernels keep the matrix pointer)
+               None if eng.comm is None else eng.comm.data_ptr(),  # (the captured kernels keep the matrix pointer
+               eng.comm_range)                                     # and the range's radius / metric / normalize)
         if self._graph is None or self._graph[0] != key:
             if self._graph is not None:
                 eng.lib.marl_graph_destroy(self._graph[1])

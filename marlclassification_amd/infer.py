@@ -37,6 +37,8 @@ def infer_main(main_config: MainConfig, infer_config: InferConfig) -> int:
     marl_config = ModelConfig.load_marl_config(infer_config.json_path)
     if infer_config.comm is not None:
         marl_config.comm = infer_config.comm
+    if infer_config.comm_range is not None:
+        marl_config.comm_range = infer_config.comm_range
     nn_models, marl_m, env = marl_config.build_marl(main_config.nb_agent)
     nn_models.load_state_dict(th.load(infer_config.state_dict_path, map_location="cpu"))
     nn_models.eval()

@@ -184,6 +184,8 @@ class ModelsWrapper(nn.Module):
         # reference inside a tuple, so that nn.Module registers nothing - no state-dict key, no entry in
         # parameters() / FlatParams; () = none
         self.__comm_source: Tuple = ()
+        # range-limited communication (set_comm_range): a comm.CommRange, None = off
+        self.__comm_range = None
 
     # ---- communication graph -------------------------------------------------------------
     @property
@@ -227,6 +229,11 @@ class ModelsWrapper(nn.Module):
         not move with ``.to(device)`` - keep it on the model's device."""
         from .. import comm as _comm
 
+        if matrix is not None and self.__comm_range is not None:
+            if _comm.is_live(matrix):
+                raise ValueError("a live (learnable) communication source under a communication range: the gradient "
+                                 "of a gated base matrix is not computed (set_comm_range(None) first)")
+            _comm.check_range_base(_comm.validate(matrix, None), self.__comm_range.normalize)
         self.__comm_source = ()
         if matrix is None:
             self.comm_matrix = None
@@ -242,6 +249,43 @@ class ModelsWrapper(nn.Module):
             raise ValueError(f"communication matrix lives on {m.device}, the model on {self.device}: "
                              "move it first (matrix.to(model.device))")
         self.comm_matrix = m.clone()  # (never the caller's storage)
+
+    @property
+    def comm_range(self):
+        """The range-limited communication ``set_comm_range`` installed (a ``comm.CommRange``: radius, metric,
+        normalize), or None."""
+        return self.__comm_range
+
+    def set_comm_range(self, radius, metric: str = "chebyshev", normalize: bool = True) -> None:
+        """Range-limited communication: in every later fused episode of this model (EpisodeSampler, Trainer, the PPO
+        epochs) an agent hears the agents within ``radius`` pixels of it (integer >= 0; ``metric`` "chebyshev" -
+        max(|dy|, |dx|) on the window corners, so ``radius = f - 1`` means "windows overlap" - or "euclidean"), per
+        image and per step: the message emitted in step t is exchanged under the positions of step t.  The constant
+        matrix of ``set_comm`` - the complete graph without one - is the base whose out-of-range links are cut;
+        ``normalize`` rescales a receiver's remaining weights to the base row's sum (the mean over the in-range agents
+        for the complete graph; a receiver with nobody in range hears zeros) and needs a base >= 0.
+        ``comm.range_matrices`` builds the same matrices in torch.  None switches it off.  It composes with
+        ``set_comm`` in either order; with a live (learnable) source whichever call comes second raises ValueError.
+        The positions exist inside the fused episode only: ``forward`` and ``MultiAgent.act`` raise under a range."""
+        from .. import comm as _comm
+
+        if radius is None:
+            self.__comm_range = None
+            return
+        r = _comm.check_range(radius, metric, normalize)
+        if self.__comm_source:
+            raise ValueError("a communication range under a live (learnable) communication source: the gradient of "
+                             "a gated base matrix is not computed (set_comm with a constant matrix first)")
+        if self.comm_matrix is not None:
+            _comm.check_range_base(self.comm_matrix, r.normalize)
+        self.__comm_range = r
+
+    def check_no_comm_range(self, who: str) -> None:
+        """The single-step surface has no positions of the emission step: RuntimeError under a range."""
+        if self.__comm_range is not None:
+            raise RuntimeError(f"{who}: range-limited communication (set_comm_range) runs inside the fused episode "
+                               "only (EpisodeSampler / Trainer): a single step has no positions to gate the exchange "
+                               "with - set_comm_range(None) for the step API")
 
     # ---- reference surface -------------------------------------------------------------
     @property
@@ -281,6 +325,7 @@ class ModelsWrapper(nn.Module):
         ``marl_step_forward``.  With grad enabled and a parameter (or msg / state) requiring
         grad, the step is one autograd node (``_StepFunction``) whose backward is
         ``marl_step_backward``: gradients reach the parameters and msg_t / the recurrent state."""
+        self.check_no_comm_range("ModelsWrapper.forward")
         na, nb = img_patch.shape[:2]
         eng = self.hip_engine(None)
         eng.configure(na, nb, 1, (img_patch.shape[2], img_patch.shape[3] + 1, img_patch.shape[4] + 1))
@@ -325,6 +370,7 @@ class ModelsWrapper(nn.Module):
         else:
             eng.comm_source = eng.comm_live = None
             eng.comm = self.comm_matrix  # (checked by set_comm; moved with the module)
+        eng.comm_range = self.__comm_range
         return eng
 
     def flat_state(self) -> FlatParams:

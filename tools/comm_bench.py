@@ -4,6 +4,7 @@ communication graphs, next to the plain step of ANOTHER checkout (the parent com
     python tools/comm_bench.py --parent DIR [--rounds 3] [--steps 30] [--warmup 5] [--out profiles/comm_c3.json]
     python tools/comm_bench.py --one GRAPH [--tree DIR]       # one leg: plain | full | ring | none (a JSON line)
     python tools/comm_bench.py --grad --parent DIR [--out profiles/comm_grad_c3.json]   # the learnable graph
+    python tools/comm_bench.py --range R --parent DIR [--out profiles/comm_range_c3.json]   # range-limited exchange
 
 Every leg is a fresh child process; a round runs parent-plain, plain, full, ring, none in that order, so the legs
 alternate with the yardstick on one box.  ``--tree DIR`` imports the package (and bench.py's constants) from DIR.
@@ -13,7 +14,10 @@ and Adam on Na^2 values) - a round runs the PARENT's constant full(16), this tre
 the parent's constant-matrix step and its own round-to-round spread.  ``--trace`` (with ``--grad``) then runs the
 constant and the ``learn_full`` leg once more under ``rocprofv3 --kernel-trace``, lists every kernel the learnable step
 launches beyond the constant one (calls per step, average duration, the new kernels against their 8 us estimate) and
-compares the legs' excess with the sum of those durations plus the parent's spread."""
+compares the legs' excess with the sum of those durations plus the parent's spread.
+``--range R``: the cost of gating the exchange by the agents' positions (``set_comm_range(R)``) - a round runs the
+PARENT's constant full(16), this tree's constant full(16), then ``range_full`` and ``range_ring`` (that base under the
+range); the yardstick is again the parent's constant-matrix step and its own round-to-round spread."""
 import argparse
 import json
 import os
@@ -26,9 +30,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEGS = ("plain", "full", "ring", "none")
 GRAD_LEGS = ("full", "learn_full", "learn_ring")  # (after the parent's constant full)
+RANGE_LEGS = ("full", "range_full", "range_ring")  # (likewise)
 
 
-def one(graph: str, tree: str, steps: int, warmup: int, batch: int) -> None:
+def one(graph: str, tree: str, steps: int, warmup: int, batch: int, radius: int = -1) -> None:
     sys.path.insert(0, tree)
     import torch as th
 
@@ -49,6 +54,13 @@ def one(graph: str, tree: str, steps: int, warmup: int, batch: int) -> None:
 
         model.set_comm(comm.LearnableComm(getattr(comm, graph[6:])(bench.NA)).to(dev))
         kw = {"comm_lr": bench.LR}
+    elif graph.startswith("range_"):
+        from marlclassification_amd import comm
+
+        if radius < 0:
+            raise SystemExit("comm_bench: a range_* leg needs --range R")
+        model.set_comm(getattr(comm, graph[6:])(bench.NA).to(dev))
+        model.set_comm_range(radius)
     elif graph != "plain":
         from marlclassification_amd import comm
 
@@ -70,13 +82,18 @@ def one(graph: str, tree: str, steps: int, warmup: int, batch: int) -> None:
         raise SystemExit("comm_bench: non-finite outputs")
     if graph != "plain":
         form = model.hip_engine(actions).plan_query("comm_form")
-    print(json.dumps({"graph": graph, "ms_per_step": ms, "steps": steps, "batch": batch, "comm_form": form,
-                      "loss": scalars[0].item()}))
+    res = {"graph": graph, "ms_per_step": ms, "steps": steps, "batch": batch, "comm_form": form,
+           "loss": scalars[0].item()}
+    if graph.startswith("range_"):
+        res["comm_range"] = model.hip_engine(actions).plan_query("comm_range")
+    print(json.dumps(res))
 
 
 def leg(graph: str, tree: str, args) -> dict:
     cmd = [sys.executable, os.path.abspath(__file__), "--one", graph, "--tree", tree, "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--batch", str(args.batch)]
+    if graph.startswith("range_"):
+        cmd += ["--range", str(args.range)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tree)
     if r.returncode != 0:
         raise SystemExit(f"leg {graph} in {tree} failed ({r.returncode}):\n{r.stdout[-2000:]}{r.stderr[-2000:]}")
@@ -85,7 +102,9 @@ def leg(graph: str, tree: str, args) -> dict:
 
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--one", choices=LEGS + GRAD_LEGS[1:])
+    ap.add_argument("--one", choices=LEGS + GRAD_LEGS[1:] + RANGE_LEGS[1:])
+    ap.add_argument("--range", type=int, default=None, metavar="R",
+                    help="the range-limited legs (radius R, chebyshev, normalised) against the parent's constant full")
     ap.add_argument("--grad", action="store_true", help="the learnable-graph legs against the parent's constant full")
     ap.add_argument("--trace", action="store_true", help="with --grad: kernel traces of the launches a learnable step adds")
     ap.add_argument("--trace-steps", type=int, default=10)
@@ -98,12 +117,16 @@ def main() -> None:
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.one:
-        one(args.one, os.path.abspath(args.tree), args.steps, args.warmup, args.batch)
+        one(args.one, os.path.abspath(args.tree), args.steps, args.warmup, args.batch,
+            -1 if args.range is None else args.range)
         return
     if not args.parent:
         ap.error("--parent DIR (or --one GRAPH)")
     if args.grad:
         grad_rounds(args)
+        return
+    if args.range is not None:
+        range_rounds(args)
         return
     res = {"parent_plain": []}
     res.update({g: [] for g in LEGS})
@@ -197,6 +220,31 @@ def grad_rounds(args) -> None:
             k: {"excess_ms": summary["excess_over_parent_median_ms"][k], "added_launches_plus_spread_ms": allowed,
                 "explained": summary["excess_over_parent_median_ms"][k] <= allowed}
             for k in ("learn_full", "learn_ring")}
+    print(json.dumps(summary))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(summary, f, indent=1)
+
+
+def range_rounds(args) -> None:
+    res = {"parent_full": []}
+    res.update({g: [] for g in RANGE_LEGS})
+    for rnd in range(args.rounds):
+        res["parent_full"].append(leg("full", os.path.abspath(args.parent), args)["ms_per_step"])
+        for g in RANGE_LEGS:
+            res[g].append(leg(g, ROOT, args)["ms_per_step"])
+        print(f"round {rnd}: " + ", ".join(f"{k} {v[-1]:.3f} ms" for k, v in res.items()), flush=True)
+    p = res["parent_full"]
+    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+    summary = {"workload": "Trainer.train_step, bench.py C3 (RESISC45 dims, 16 agents, 16 steps), full(16) / ring(16) "
+                           f"under set_comm_range({args.range})",
+               "radius": args.range, "batch": args.batch, "steps": args.steps, "warmup": args.warmup,
+               "rounds": args.rounds, "ms_per_step": res, "parent_spread_ms": max(p) - min(p),
+               "parent_median_ms": med["parent_full"], "median_ms": med,
+               "excess_over_parent_median_ms": {k: med[k] - med["parent_full"] for k in RANGE_LEGS}}
+    summary["const_inside_parent_spread"] = min(p) <= med["full"] <= max(p)
+    summary["gated_inside_parent_spread"] = {
+        k: summary["excess_over_parent_median_ms"][k] <= summary["parent_spread_ms"] for k in RANGE_LEGS[1:]}
     print(json.dumps(summary))
     if args.out:
         with open(args.out, "w") as f:
