@@ -529,7 +529,8 @@ int marl_cnn_wgrad(const float* dz, const void* img, int img_u8, const int32_t* 
 size_t marl_cnn_wgrad_scratch(int64_t rows, int cin, int cout, int hin, int groups, int first);
 
 /* Perf-experiment hook: overrides an internal tuning knob (same names as the MARL_<KEY>
- * environment variables, lower case, e.g. "wgrad_rb", "mfma_split"); tools/ and tests only.
+ * environment variables, lower case, e.g. "dgrad_min_chunks", "mfma_split"); tools/ and tests only.
+ * A key outside the library's table of knobs (csrc/rowops.hip, kKnownKnobs) returns MARL_EINVAL and sets nothing.
  * Several knobs change the LAYOUT of the episode workspace (tile plans, split-K targets,
  * mfma_split ...): marl_workspace_sizes() must be asked again and the workspace re-allocated
  * after such a call; a stale buffer is refused with MARL_ESIZE (ABI 3: sizes are passed in).  (The
@@ -562,7 +563,19 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
  * the phase-pipelined step, "wgrad3" = conv weight gradients (cin >= 16) on the bf16 pipe, "panel_sample" = the episode
  * forward samples step t's actions inside the chained panel launch, as the epilogue of its policy workgroups (no
  * sample_kernel launch; at most four actions; MARL_PANEL_SAMPLE=0 in the environment, read once, restores the
- * separate launch - same results bit for bit).  *value = 0 / 1 (a plan number for "lstm_plan"). */
+ * separate launch - same results bit for bit).  *value = 0 / 1 (a plan number for "lstm_plan").
+ * "g3_tn_pipe" and "wgrad3" report what runs, not the knob: the first is 0 where the image weight gradients are off,
+ * the second is 0 unless some conv layer of the model takes cnn_wgrad3_kernel.
+ * The CNN launchers' plans, each from the launcher's own routine (host arithmetic only, no GPU needed):
+ *   "cnn_fwd"         0 = the unfused path (im2col + GEMM + row kernels); 1..5 = the cnn_fwd2_kernel / cnn_fwd3_kernel
+ *                     instantiation (1 Resisc f = 12, 2 / 3 Mnist f = 6 / 12, 4 / 5 Aid f = 24 / 32); 6 = the general
+ *                     cnn_fwd_kernel (`train` counts here: im2col rows kept for backward rule out 1..5)
+ *   "cnn_fwd_rb"      patches per chunk of that launch (0 on the unfused path)
+ *   "cnn_fwd_blocks"  its grid; cnn_fwd_blocks < ceil(R / cnn_fwd_rb) means workgroups walk several chunks
+ *   "cnn_dgrad_rb<l>" conv layer l >= 1: patches per chunk of the fused layer backward, 0 = the col2im fallback
+ *   "cnn_wgrad_rb<l>", "cnn_wgrad_chunks<l>", "cnn_wgrad_blocks<l>"  conv layer l >= 0: patches per chunk, chunks and
+ *                     workgroups of the activation-based weight gradient (blocks: the device-independent upper bound;
+ *                     the launch trims it to what is resident), all 0 where the layer takes the im2col GEMM instead. */
 int marl_plan_query(const marl_config* cfg, int train, const char* key, int* value);
 
 #ifdef __cplusplus

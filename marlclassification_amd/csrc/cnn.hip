@@ -827,6 +827,11 @@ static bool fwd2_matches(const CnnFwdArgs& a) {
     return true;
 }
 
+// The persistent launches (cnn_fwd2 / cnn_fwd3) take one workgroup per chunk up to 256 workgroups; above that a
+// workgroup walks chunk += gridDim.x.  launch_cnn_fwd and cnn_fwd_launch_plan (marl_plan_query) both ask here.
+constexpr int kFwd2Rows = 8;  // patches per chunk of cnn_fwd2_kernel: one per wave
+static int fwd2_grid(int64_t nchunks) { return nchunks < 256 ? (int)nchunks : 256; }
+
 template <class N>
 static int fwd2_launch(CnnFwdArgs& a, hipStream_t st) {
     static bool raised = false;  // per process; one process drives one GPU
@@ -837,8 +842,8 @@ static int fwd2_launch(CnnFwdArgs& a, hipStream_t st) {
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         raised = true;
     }
-    const int nchunks = (int)cdiv(a.rows, 8);
-    const int blocks = nchunks < 256 ? nchunks : 256;
+    const int nchunks = (int)cdiv(a.rows, kFwd2Rows);
+    const int blocks = fwd2_grid(nchunks);
 #ifdef MARL_KERNEL_TS
     static long long* d_ts2 = nullptr;
     static int calls2 = 0;
@@ -1362,7 +1367,7 @@ static int fwd3_launch(CnnFwdArgs& a, hipStream_t st) {
         raised = true;
     }
     const int ngroups = (int)cdiv(a.rows, PL::GP);
-    const int blocks = ngroups < 256 ? ngroups : 256;
+    const int blocks = fwd2_grid(ngroups);
 #ifdef MARL_KERNEL_TS
     static long long* d_ts3 = nullptr;
     static int calls3 = 0;
@@ -1447,6 +1452,33 @@ int cnn_fwd_supported(const CnnFwdArgs& a0) {
     return cnn_fwd_plan(a, 1) * sizeof(float) <= 144 * 1024;
 }
 
+// patches per workgroup of the general cnn_fwd_kernel: as many as fit three workgroups per CU (the conv weights are
+// re-read from L2 by every workgroup), but keep >= 256 workgroups.  Leaves the plan of that rb in `a`.
+static int cnn_fwd_rb(CnnFwdArgs& a) {
+    constexpr int rb_max = 8, lds_cap = 52;  // patches per workgroup (<= 16: per-patch LDS tables), LDS cap in KB
+    int rb = rb_max;
+    while (rb > 1 && (cnn_fwd_plan(a, rb) * sizeof(float) > (size_t)lds_cap * 1024 || cdiv(a.rows, rb) < 256)) --rb;
+    return rb;
+}
+
+CnnFwdPlan cnn_fwd_launch_plan(const CnnFwdArgs& a0) {
+    CnnFwdArgs a = a0;
+    CnnFwdPlan p{};
+    p.which = cnn_fwd2_which(a);
+    if (p.which >= 1 && p.which <= 3) {
+        p.rb = kFwd2Rows;
+        p.blocks = fwd2_grid(cdiv(a.rows, p.rb));
+    } else if (p.which) {
+        p.rb = p.which == 4 ? Plan3Aid24::GP : Plan3Aid32::GP;
+        p.blocks = fwd2_grid(cdiv(a.rows, p.rb));
+    } else {
+        p.which = 6;
+        p.rb = cnn_fwd_rb(a);
+        p.blocks = (int)cdiv(a.rows, p.rb);
+    }
+    return p;
+}
+
 int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st) {
     if (a.rows <= 0) return MARL_OK;
     switch (cnn_fwd2_which(a)) {
@@ -1457,11 +1489,7 @@ int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st) {
         case 5: return fwd3_launch<Fwd3Aid32, Plan3Aid32>(a, st);
         default: break;
     }
-    // as many patches per workgroup as fit three workgroups per CU (the conv weights are
-    // re-read from L2 by every workgroup), but keep >= 256 workgroups
-    constexpr int rb_max = 8, lds_cap = 52;  // patches per workgroup (<= 16: per-patch LDS tables), LDS cap in KB
-    int rb = rb_max;
-    while (rb > 1 && (cnn_fwd_plan(a, rb) * sizeof(float) > (size_t)lds_cap * 1024 || cdiv(a.rows, rb) < 256)) --rb;
+    const int rb = cnn_fwd_rb(a);
     const size_t lds = cnn_fwd_plan(a, rb) * sizeof(float);
     if (lds > 144 * 1024) {
         set_error("fused CNN forward: window %d outside its range", a.f);
@@ -2098,6 +2126,11 @@ static void cnn_dgrad_raise_lds() {
 #endif
         raised = true;
     }
+}
+
+int cnn_dgrad_launch_rb(const CnnDgradArgs& a0) {
+    CnnDgradArgs a = a0;
+    return cnn_dgrad_rb(a);
 }
 
 // device-independent upper bound of cnn_dgrad_blocks (the workspace layout is computed without a GPU)
@@ -2908,6 +2941,30 @@ static size_t cnn_wgrad_plan(CnnWgradArgs& a) {
     return 0;
 }
 
+// the form launch_cnn_wgrad takes for these shapes, its plan in `a`, its dynamic LDS bytes in *lds:
+// 3 = bf16x6 (cnn_wgrad3_kernel: layers with >= 16 input channels), 1 = fp32 MFMA (cnn_wgrad_kernel), 0 = neither
+static int cnn_wgrad_form(CnnWgradArgs& a, size_t* lds) {
+    CnnWgradArgs b = a;
+    const size_t lds3 = cnn_wgrad3_plan(b);
+    if (lds3) {
+        a = b;
+        *lds = lds3;
+        return 3;
+    }
+    const size_t fl = cnn_wgrad_plan(a);
+    *lds = fl * sizeof(float);
+    return fl ? 1 : 0;
+}
+
+CnnWgradPlanInfo cnn_wgrad_launch_plan(const CnnWgradArgs& a0) {
+    CnnWgradArgs a = a0;
+    size_t lds = 0;
+    CnnWgradPlanInfo p{};
+    p.form = cnn_wgrad_form(a, &lds);
+    if (p.form) p.rb = a.rb, p.chunks = a.nchunks, p.blocks = a.blocks;
+    return p;
+}
+
 int cnn_wgrad_supported(const CnnWgradArgs& a0) {
     if (getenv("MARL_CNN_FUSED") && getenv("MARL_CNN_FUSED")[0] == '0') return 0;
     CnnWgradArgs a = a0;
@@ -2992,21 +3049,16 @@ static int wgrad3_launch(CnnWgradArgs& a, float* part_w, size_t lds, hipStream_t
 
 int launch_cnn_wgrad(CnnWgradArgs& a, hipStream_t st) {
     float* part_w = a.part_w;
-    {   // layers with >= 16 input channels: the bf16x6 form
-        CnnWgradArgs b = a;
-        const size_t lds3 = cnn_wgrad3_plan(b);
-        if (lds3) {
-            a = b;
-            if (a.skt == 9) return a.pd == 4 ? wgrad3_launch<9, 4, 4>(a, part_w, lds3, st) : wgrad3_launch<9, 2, 2>(a, part_w, lds3, st);
-            return a.pd == 4 ? wgrad3_launch<5, 4, 4>(a, part_w, lds3, st) : wgrad3_launch<5, 2, 2>(a, part_w, lds3, st);
-        }
+    size_t lds = 0;
+    const int form = cnn_wgrad_form(a, &lds);
+    if (form == 3) {  // layers with >= 16 input channels: the bf16x6 form
+        if (a.skt == 9) return a.pd == 4 ? wgrad3_launch<9, 4, 4>(a, part_w, lds, st) : wgrad3_launch<9, 2, 2>(a, part_w, lds, st);
+        return a.pd == 4 ? wgrad3_launch<5, 4, 4>(a, part_w, lds, st) : wgrad3_launch<5, 2, 2>(a, part_w, lds, st);
     }
-    const size_t fl = cnn_wgrad_plan(a);
-    if (!fl) {
+    if (!form) {
         set_error("conv weight gradient: shape outside the fused kernel's range");
         return MARL_ELIMIT;
     }
-    const size_t lds = fl * sizeof(float);
     const int sct = a.sct, skt = a.skt;
     const bool deep = a.pd == 4;
     // grid = what is resident at once (a persistent workgroup that has to wait for a slot only

@@ -888,6 +888,13 @@ struct CnnFwdArgs {
 int cnn_fwd_supported(const CnnFwdArgs& a);
 int cnn_fwd_writes_image(const CnnFwdArgs& a);  // the launch selected for these shapes honours a.u3
 int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st);
+// what launch_cnn_fwd does with these shapes under the current knobs (host arithmetic; marl_plan_query reports it):
+// which = cnn_fwd2_kernel / cnn_fwd3_kernel instantiation 1..5 or 6 = the general cnn_fwd_kernel, rb = patches per
+// chunk, blocks = the grid (blocks < cdiv(rows, rb): workgroups walk several chunks)
+struct CnnFwdPlan {
+    int which, rb, blocks;
+};
+CnnFwdPlan cnn_fwd_launch_plan(const CnnFwdArgs& a);
 
 // ---------------------------------------------------------------------------
 // Fused CNN layer backward (cnn.hip): dZ_l -> [transposed conv] -> dA_{l-1} -> [GroupNorm +
@@ -924,6 +931,7 @@ struct CnnDgradArgs {
 int cnn_dgrad_supported(const CnnDgradArgs& a);
 int cnn_dgrad_blocks(const CnnDgradArgs& a);      // partial rows the launch writes (persistent grid)
 int cnn_dgrad_blocks_max(const CnnDgradArgs& a);  // its device-independent upper bound
+int cnn_dgrad_launch_rb(const CnnDgradArgs& a);   // patches per chunk of the launch (0: no plan fits)
 int launch_cnn_dgrad(CnnDgradArgs& a, hipStream_t st);
 int cnn_dgrad_w0_ok(const CnnDgradArgs& a, int cin0, int f0);  // (see w0_part)
 
@@ -975,6 +983,12 @@ struct CnnWgradArgs {
 int cnn_wgrad_supported(const CnnWgradArgs& a);
 int cnn_wgrad_blocks(const CnnWgradArgs& a);   // partial slabs the launch writes
 int launch_cnn_wgrad(CnnWgradArgs& a, hipStream_t st);
+// what launch_cnn_wgrad does with these shapes: form 3 = cnn_wgrad3_kernel (bf16x6), 1 = cnn_wgrad_kernel, 0 = neither;
+// rb / chunks / blocks of that form's plan (blocks: the device-independent bound the launch trims to what is resident)
+struct CnnWgradPlanInfo {
+    int form, rb, chunks, blocks;
+};
+CnnWgradPlanInfo cnn_wgrad_launch_plan(const CnnWgradArgs& a);
 // out[i * ldc + j] = sum over z < splits (fixed order) of part[z * stride + i * nj + j];
 // bias (nullable): same over bpart[z * ni + i]
 int launch_slab_reduce(const float* part, int64_t stride, int splits, float* c, int ldc, int ni,

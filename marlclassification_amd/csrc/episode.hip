@@ -317,6 +317,9 @@ static CnnFwdArgs cnn_fwd_shape(const Dims& d) {
                                  d.ldk[l], nullptr};
     return a;
 }
+// forward keeps a layer's im2col rows only for a weight gradient the activation-based kernel does not cover
+// (step_cnn fills CnnFwdLayer::cols by this; marl_plan_query asks the same question)
+static bool cnn_fwd_keeps_cols(const bool* wgrad_ok, int train, int l) { return train != 0 && !wgrad_ok[l]; }
 static CnnWgradArgs cnn_wgrad_shape(const Dims& d, int l) {
     CnnWgradArgs g{};
     g.rows = d.NR;
@@ -737,7 +740,7 @@ static int step_cnn(const Ctx& c, int t, const StepIn& in) {
         a.L = d.L;
         for (int l = 0; l < d.L; ++l)
             a.layer[l] = CnnFwdLayer{c.wp(4 * l), c.wp(4 * l + 1), c.wp(4 * l + 2), c.wp(4 * l + 3),
-                                     keep && !c.e.wgrad_ok[l] ? c.at(c.e.COLS[l], t) : nullptr,
+                                     cnn_fwd_keeps_cols(c.e.wgrad_ok, c.train, l) ? c.at(c.e.COLS[l], t) : nullptr,
                                      keep ? c.at(c.e.Z[l], t) : nullptr,
                                      keep ? c.at(c.e.GST[l], t) : nullptr,
                                      d.ch[l], d.ch[l + 1], d.grp[l], d.hw[l], d.hw[l + 1], d.P[l],
@@ -2846,8 +2849,64 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     else if (!strcmp(key, "g3_tn_cell"))  // both weight gradients of a cell from one launch (gemm_tn3_cell_kernel)
         *value = g3_enabled(d) && g3_tn_enabled(d) && g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) &&
                  g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR);
-    else if (!strcmp(key, "g3_tn_pipe")) *value = tune_get("g3_tn_pipe", 1) != 0;  // phase-pipelined row contractions
-    else if (!strcmp(key, "wgrad3")) *value = tune_get("wgrad3", 1) != 0;  // conv weight gradients on the bf16 pipe (cin >= 16)
+    else if (!strcmp(key, "g3_tn_pipe"))  // phase-pipelined row contractions: only where the image weight gradients run
+        *value = g3_enabled(d) && g3_tn_enabled(d) && tune_get("g3_tn_pipe", 1) != 0;
+    else if (!strcmp(key, "wgrad3")) {  // a conv weight gradient of this model runs on the bf16 pipe (cin >= 16)
+        ELayout e;
+        make_elayout(d, 1, e);
+        *value = 0;
+        for (int l = 0; l < d.L; ++l)
+            if (e.wgrad_ok[l] && cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l)).form == 3) *value = 1;
+    }
+    // what the CNN launchers do with this shape (their own routines, host arithmetic only; see marl_hip.h)
+    else if (!strncmp(key, "cnn_fwd", 7)) {
+        ELayout e;
+        make_elayout(d, train, e);
+        WLayout w;
+        make_wlayout(d, w);
+        CnnFwdPlan p{};  // unfused path: all 0
+        if (e.fused_fwd) {
+            // the shapes of step_cnn's launch: which optional buffers exist decides the instantiation
+            static float here;
+            CnnFwdArgs a = cnn_fwd_shape(d);
+            for (int l = 0; l < d.L; ++l) {
+                a.layer[l].cols = cnn_fwd_keeps_cols(e.wgrad_ok, train, l) ? &here : nullptr;
+                a.layer[l].wfrag = w.wf[4 * l] ? &here : nullptr;
+            }
+            p = cnn_fwd_launch_plan(a);
+        }
+        if (!strcmp(key, "cnn_fwd")) *value = p.which;
+        else if (!strcmp(key, "cnn_fwd_rb")) *value = p.rb;
+        else if (!strcmp(key, "cnn_fwd_blocks")) *value = p.blocks;
+        else {
+            set_error("unknown plan key %s", key);
+            return MARL_EINVAL;
+        }
+    }
+    else if (!strncmp(key, "cnn_dgrad_rb", 12) || !strncmp(key, "cnn_wgrad_", 10)) {
+        const bool dg = key[4] == 'd';
+        const char* rest = key + (dg ? 12 : 10);
+        int field = 0;  // wgrad: 1 = rb, 2 = chunks, 3 = blocks
+        if (!dg) {
+            if (!strncmp(rest, "rb", 2)) field = 1, rest += 2;
+            else if (!strncmp(rest, "chunks", 6)) field = 2, rest += 6;
+            else if (!strncmp(rest, "blocks", 6)) field = 3, rest += 6;
+        }
+        const int l = (rest[0] >= '0' && rest[0] <= '9' && !rest[1]) ? rest[0] - '0' : -1;
+        if ((!dg && !field) || l < (dg ? 1 : 0) || l >= d.L) {
+            set_error("unknown plan key %s (layers %d..%d)", key, dg ? 1 : 0, d.L - 1);
+            return MARL_EINVAL;
+        }
+        ELayout e;
+        make_elayout(d, 1, e);
+        if (dg)
+            *value = e.dgrad_ok[l] ? cnn_dgrad_launch_rb(cnn_dgrad_shape(d, l)) : 0;
+        else {
+            CnnWgradPlanInfo p{};
+            if (e.wgrad_ok[l]) p = cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l));
+            *value = field == 1 ? p.rb : field == 2 ? p.chunks : p.blocks;
+        }
+    }
     // message exchange: "comm" = a mixing matrix is set; "comm_form" = how the aggregation is launched now
     // (0 = mean inside the chained panel launch, 1 = mean while a panel stages, 2 = agg_msg_kernel, 3 = mix_msg_kernel
     // ahead of a plain panel launch, 4 = mix_msg_kernel ahead of the GEMM path, 5 = mixed inside the chained panel

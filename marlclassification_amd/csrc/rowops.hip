@@ -45,7 +45,23 @@ Knob* knob(const char* key, bool create) {
 }
 }  // namespace
 
+// every knob the library reads (tests/test_gpu_round6.py pins each at every value; the last two are read in
+// MARL_G3_ABLATE builds only).  marl_tune refuses any other key: a misspelt or retired knob used to be stored and
+// never read, and the A/B built on it compared two identical runs.
+static const char* const kKnownKnobs[] = {
+    "g3", "g3_lstm", "g3_tn", "g3_min_units", "g3_safe", "mfma_split", "g3_lstm_variant", "g3_nt_variant",
+    "g3_tn_variant", "g3_tn_cell", "g3_tn_pipe", "g3_tn_wgs", "nt_xcd", "tn_xcd", "panel_chain", "red_defer",
+    "tn_split_waves", "wgrad3", "cnn_fwd2", "cnn_fwd3", "dgrad_wgs", "dgrad_min_chunks",
+    "g3_clk", "g3_tn_abl",
+};
+
 int tune_set(const char* key, int value) {
+    bool known = false;
+    for (const char* name : kKnownKnobs) known = known || !strcmp(name, key);
+    if (!known) {
+        set_error("marl_tune: unknown knob %s", key);
+        return MARL_EINVAL;
+    }
     Knob* k = knob(key, true);
     if (!k) {
         set_error("marl_tune: knob table full or key too long (%s)", key);

@@ -8,11 +8,9 @@ import pytest
 import torch as th
 
 from oracle import marl_oracle as mo
-from tests.util import Golden, model_spec, record, uniform_params
+from tests.util import PLAN_INVARIANTS, Golden, assert_witness, distinct_image_parity, model_spec, plan_witness
 
 pytestmark = pytest.mark.gpu
-
-ATOL = 1e-5
 
 C3_CFG = mo.OracleConfig("resisc45", 12, 256, 256, 64, 96, 16, 45, 384, 384)
 C4_CFG = mo.OracleConfig("aid", 24, 256, 256, 64, 96, 16, 30, 320, 320, actions=[[3, 0], [-3, 0], [0, 3], [0, -3]])
@@ -28,13 +26,35 @@ DISTINCT = {
 }
 
 
-def _engine(cfg, device, na, nb, ns, shape, params):
-    from marlclassification_amd.engine import HipEngine
-
-    eng = HipEngine(model_spec(cfg), device)
-    eng.configure(na, nb, ns, shape)
-    eng.pack({k: v.to(device) for k, v in params.items()})
-    return eng
+# the plans each tag is there for (marl_plan_query, every value from the launcher's own routine), asserted AHEAD of the
+# parity run: a changed threshold fails here instead of quietly moving the tag onto another plan
+DISTINCT_WITNESS = {
+    # 65 536 contraction rows: image GEMMs, image weight gradients (one launch per cell, phase-pipelined), the 128-row
+    # LSTM tile plan, the chained panel launch; Fwd2Resisc walks 512 chunks on 256 workgroups; the layer backward and
+    # the weight gradients run their largest chunks, persistent (blocks < chunks)
+    "c3_resisc_b256": ["R == 4096", "g3 == 1", "g3_tn == 1", "g3_tn_cell == 1", "g3_tn_pipe == 1", "lstm_plan == 2",
+                       "small_r == 0", "panel_chain == 1", "comm_form == 0", "cnn_fwd == 1", "cnn_fwd_blocks == 256",
+                       "cnn_fwd_blocks < cdiv(R, cnn_fwd_rb)", "cnn_dgrad_rb1 == 8", "cnn_dgrad_rb2 == 8", "wgrad3 == 1",
+                       "cnn_wgrad_rb0 == 4", "cnn_wgrad_rb1 == 7", "cnn_wgrad_rb2 == 8",
+                       "all(w[f'cnn_wgrad_blocks{l}'] < w[f'cnn_wgrad_chunks{l}'] for l in range(3))"],
+    # 8 192 contraction rows: the smallest batch with the per-cell image weight gradients, the gate-split small-R LSTM
+    # plan; Fwd3Aid24 without a walk (128 groups of 4); four-layer backward at rb 2 / 5 / 8
+    "c4_aid_b32": ["R == 512", "g3 == 1", "g3_tn == 1", "g3_tn_cell == 1", "lstm_plan == 3", "small_r == 1",
+                   "panel_chain == 1", "comm_form == 0", "cnn_fwd == 4", "cnn_fwd_rb == 4",
+                   "cnn_fwd_blocks == cdiv(R, 4)", "cnn_dgrad_rb1 == 2", "cnn_dgrad_rb2 == 5", "cnn_dgrad_rb3 == 8",
+                   "wgrad3 == 1", "cnn_wgrad_blocks3 == 256", "cnn_wgrad_chunks3 == 1171"],
+    # 64 agents: no chained launch (the mean while a panel stages, comm_form 1); Fwd3Aid32 walks 512 groups; window 32:
+    # single-patch first layer backward, 65 536 one-patch weight-gradient chunks on 512 workgroups
+    "c5_synth_b32": ["R == 2048", "g3 == 1", "g3_tn == 1", "g3_tn_cell == 1", "lstm_plan == 2", "small_r == 0",
+                     "panel_chain == 0", "comm_form == 1", "cnn_fwd == 5", "cnn_fwd_blocks == 256",
+                     "cnn_fwd_blocks < cdiv(R, cnn_fwd_rb)", "cnn_dgrad_rb1 == 1", "cnn_dgrad_rb2 == 3",
+                     "cnn_dgrad_rb3 == 6", "cnn_wgrad_rb1 == 1", "cnn_wgrad_chunks1 == 65536", "cnn_wgrad_blocks1 == 512"],
+    # configs[3] at 256 images: Fwd3Aid24 walks 1024 groups, the 128-row LSTM plan at stride 3
+    "c4_aid_b256": ["R == 4096", "g3 == 1", "g3_tn == 1", "g3_tn_cell == 1", "lstm_plan == 2", "small_r == 0",
+                    "panel_chain == 1", "comm_form == 0", "cnn_fwd == 4", "cnn_fwd_blocks == 256",
+                    "cnn_fwd_blocks < cdiv(R, cnn_fwd_rb)", "cnn_dgrad_rb1 == 2", "cnn_dgrad_rb2 == 5",
+                    "cnn_dgrad_rb3 == 8", "cnn_wgrad_blocks3 == 256", "cnn_wgrad_chunks3 == 9363"],
+}
 
 
 @pytest.mark.parametrize("tag", list(DISTINCT))
@@ -47,60 +67,12 @@ def test_full_size_parity_on_distinct_shuffled_images(device, tag):
     images), which the identical-replica tests of rounds 2-4 could not see.  With the oracle batch's advantage
     statistics (loss phase 2) the big batch's gradient is the oracle's: every entry within 1e-4 of its tensor's
     scale.  The size-dependent plans (column-pass / 256 x 256 row contractions, 256 x 128 NT tiles, two-launch
-    panels at 64 agents, split-K slab counts, small-R tile plans) all run on this data."""
+    panels at 64 agents, split-K slab counts, small-R tile plans) all run on this data: DISTINCT_WITNESS says which,
+    and the plan query confirms it first.  (The body is tests/util.py::distinct_image_parity.)"""
     cfg, na, nd, ns, shape, rep = DISTINCT[tag]
-    params = uniform_params(cfg, 7)
-    img = th.rand(nd, *shape, generator=th.Generator().manual_seed(21))
-    y = th.randint(0, cfg.nb_class, (nd,), generator=th.Generator().manual_seed(22))
-    inp = mo.draw_episode_inputs(cfg, na, nd, ns, shape[1:], 23)
-    tr, lo, grads = mo.train_iteration(params, cfg, img, y, inp, ns, 0.99)
-
-    small = [t.to(device) for t in (inp.pos0, inp.h0, inp.c0, inp.hc0, inp.cc0, inp.q)]
-    eng1 = _engine(cfg, device, na, nd, ns, shape, params)
-    out1 = eng1.episode_forward(img.to(device), *small, tr.step_actions.to(device), True)
-    stats = eng1.a2c_loss(out1, y.to(device), 0.99, phase=1)[4].clone()
-    del eng1, out1
-
-    nb = nd * rep
-    src = th.arange(nd).repeat(rep)[th.randperm(nb, generator=th.Generator().manual_seed(24))]  # slot -> source image
-    assert all(int((src == s).sum()) == rep for s in range(nd)) and not th.equal(src, th.arange(nd).repeat(rep))
-    pick = lambda t, dim: t.index_select(dim, src)  # noqa: E731
-    eng = _engine(cfg, device, na, nb, ns, shape, params)
-    big = [pick(inp.pos0, 1), pick(inp.h0, 1), pick(inp.c0, 1), pick(inp.hc0, 1), pick(inp.cc0, 1), pick(inp.q, 2)]
-    out = eng.episode_forward(pick(img, 0).to(device), *[t.to(device) for t in big],
-                              pick(tr.step_actions, 2).to(device), True)
-    assert th.equal(out.step_pos.cpu(), pick(tr.step_pos, 2)), "a slot's positions differ from its source image's"
-    errs = {}
-    for name, got, ref in (("preds", out.step_preds, tr.step_preds), ("logp", out.step_log_probas, tr.step_log_probas),
-                           ("values", out.step_values, tr.step_values)):
-        errs[name] = (got.cpu().double() - pick(ref.detach(), 2).double()).abs().max().item()
-        assert errs[name] <= ATOL, (name, errs[name])
-    # copies of one source image are bit-identical wherever they sit in the batch
-    first = [int((src == s).nonzero()[0]) for s in range(nd)]
-    for name in ("step_preds", "step_log_probas", "step_values"):
-        t = getattr(out, name).cpu()
-        assert th.equal(t, t.index_select(2, th.tensor(first)).index_select(2, src)), f"{name}: copies differ"
-    yb = pick(y, 0).to(device)
-    bufs = eng.a2c_loss(out, yb, 0.99, phase=1)
-    assert th.allclose(bufs[4], stats * rep, rtol=1e-9), (bufs[4], stats * rep)
-    bufs[4].copy_(stats)  # standardize with the oracle batch's own n / sum / sum of squares
-    gp, gl, gv, sc, _ = eng.a2c_loss(out, yb, 0.99, phase=2, bufs=bufs)
-    assert abs(sc[0].item() - lo.loss.item()) <= 5e-5 * max(1.0, abs(lo.loss.item()))
-    g_out = {k: th.zeros_like(v, device=device) for k, v in params.items()}
-    eng.episode_backward(gp, gl, gv, g_out)
-    bad, worst, n = {}, 0.0, 0
-    for k, ref in grads.items():
-        err = (g_out[k].cpu().double() - ref.double()).abs().max().item()
-        scale = ref.abs().max().item()
-        n += ref.numel()
-        worst = max(worst, err / scale if scale > 1e-12 else 0.0)
-        if not err <= 1e-4 * scale + 1e-7:
-            bad[k.replace("_ModelsWrapper__", "")] = "%.2e/%.2e" % (err, scale)
-    assert not bad, "\n".join(f"{k}: {v}" for k, v in bad.items())
-    record(f"distinct_{tag}", {"batch": nb, "distinct_images": nd, "rows": na * nb, "positions_equal": True,
-                               "abs_err": errs, "abs_tolerance": ATOL,
-                               "gradient_entries": n, "grad_max_err_over_tensor_scale": worst, "grad_tolerance": 1e-4,
-                               "margin": {"outputs": ATOL / max(errs.values()), "gradient": 1e-4 / max(worst, 1e-30)}})
+    w = plan_witness(cfg, na, nd * rep, ns, shape)
+    assert_witness(w, DISTINCT_WITNESS[tag] + PLAN_INVARIANTS)
+    distinct_image_parity(device, cfg, na, nd, ns, shape, rep, f"distinct_{tag}")
 
 
 # ---- weights workspace: batch-independent layout, invalidated by layout knobs -------------------------

@@ -6,7 +6,7 @@ import pytest
 import torch as th
 
 from tests.test_gpu_round5 import _run
-from tests.util import Golden, model_spec
+from tests.util import Golden, library_knobs, model_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -149,14 +149,9 @@ def test_every_knob_value_keeps_reference_parity(device, knob, value):
 
 
 def test_knob_table_matches_the_library_sources():
-    """the cases above cover every knob the library reads (a new tune_get() must come with its parity case)"""
-    import glob
-    import os
-    import re
-
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "marlclassification_amd", "csrc")
-    found = set()
-    for f in glob.glob(os.path.join(root, "*.hip")):
-        found |= set(re.findall(r'tune_get\("([a-z0-9_]+)"', open(f, encoding="utf-8").read()))
+    """the cases above cover every knob the library reads (a new tune_get() must come with its parity case), and the
+    table marl_tune accepts keys from (csrc/rowops.hip, kKnownKnobs) is exactly that set: three lists, one content"""
+    found, table = library_knobs()
     debug_only = {"g3_clk", "g3_tn_abl"}  # read in MARL_G3_ABLATE builds only
     assert found - debug_only == set(KNOB_DEFAULTS), (found - debug_only) ^ set(KNOB_DEFAULTS)
+    assert len(table) == len(set(table)) and set(table) == found, set(table) ^ found

@@ -21,15 +21,13 @@ for rows, ni, nih, nhh in ((65536, 1024, 368, 256), (65536, 1024, 624, 256)):
 
     us_old = timeit(old, 20)
     ref_ih, ref_hh = c_ih.clone(), c_hh.clone()
-    for splits, order in ((64, 0), (0, 2), (64, 0), (0, 2), (60, 2), (90, 2)):
-        check(lib.marl_tune(b"g3_tn_cell_splits", splits))
-        check(lib.marl_tune(b"g3_tn_cell_teams", 1 if order == 2 else 0))
+    for rep in range(2):  # (the split count and the team order are the launcher's choice: two repeats)
         sb = lib.marl_gemm_tn_images_cell_scratch(ni, nih, nhh, rows)
         sc = th.zeros(sb // 4 + 16, device=dev)
         new = lambda: check(lib.marl_gemm_tn_images_cell(g3.data_ptr(), ni, u3.data_ptr(), nih, h3.data_ptr(), nhh, rows, c_ih.data_ptr(), c_ih.shape[1], c_hh.data_ptr(), nhh, cs.data_ptr(), sc.data_ptr(), sb, None))
         us = timeit(new, 20)
         d = max((c_ih - ref_ih).abs().max().item(), (c_hh - ref_hh).abs().max().item())
-        out.append(dict(rows=rows, nih=nih, nhh=nhh, splits=splits, order=order, us_cell=round(us, 1), us_two_launches=round(us_old, 1), max_diff=d,
+        out.append(dict(rows=rows, nih=nih, nhh=nhh, repeat=rep, us_cell=round(us, 1), us_two_launches=round(us_old, 1), max_diff=d,
                         tf=round(2.0 * rows * ni * (nih + nhh) / us / 1e6, 1)))
         print(out[-1], flush=True)
 json.dump(out, open("gpurun_out/tn_cell_lab.json", "w"), indent=1)

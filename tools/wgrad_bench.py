@@ -99,6 +99,7 @@ for rnd in range(2):
     for v in variants:
         for kv in filter(None, v.split(",")):
             k, val = kv.split("=")
-            lib.marl_tune(k.encode(), int(val))
+            if lib.marl_tune(k.encode(), int(val)) != 0:  # (an unknown knob is refused, not stored)
+                raise SystemExit(lib.marl_last_error().decode())
         res = [run(l, rnd == 0 and v == variants[0]) for l in LAYERS]
         print(f"round {rnd} [{v or 'default'}]: " + "  ".join(f"L{i}: {us:7.1f} us {tf:5.1f} TF" for i, (us, tf) in enumerate(res)))
