@@ -82,6 +82,9 @@ EXPORTS = (
     "marl_comm_grad marl_comm_grad_scratch_bytes marl_comm_range"
 ).split()
 
+# kernel-level test hooks that include/marl_hip_rowops.h declares (outside the versioned ABI above)
+ROWOP_HOOKS = ("marl_ln_silu_bwd", "marl_gn_silu_bwd")
+
 _lib: Optional[C.CDLL] = None
 
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -166,7 +169,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_comm_grad_scratch_bytes.argtypes = [_cfgp]
     lib.marl_comm_grad.argtypes = [_cfgp, _vp, _sz, _vp, _sz, _i, _vp, _vp, _sz, _vp]
     lib.marl_comm_range.argtypes = [_i, _i, _i]
-    for name in EXPORTS:
+    lib.marl_ln_silu_bwd.argtypes = [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _vp, _sz, _i, _i, _vp]
+    lib.marl_gn_silu_bwd.argtypes = [_vp, _i64, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _vp]
+    for name in EXPORTS + list(ROWOP_HOOKS):
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("marl_abi_version", "marl_tune_get"):
             fn.restype = _i
@@ -184,7 +189,7 @@ def load() -> C.CDLL:
             "or `python -c 'import __graft_entry__ as g; g.build()'`."
         )
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in EXPORTS if not hasattr(lib, s)]
+    missing = [s for s in EXPORTS + list(ROWOP_HOOKS) if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f"{LIB_PATH} lacks symbols {missing}")
     _declare(lib)

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/marl_hip_rowops.h"
 #include "common.h"
 
 namespace marl {
@@ -3065,6 +3066,55 @@ int marl_ln_silu_fwd(const float* z, int ldz, const float* gamma, const float* b
                      int ldo, float* stats, int m, int n, void* stream) {
     return launch_ln_silu_fwd(z, ldz, gamma, beta, out, ldo, stats, m, n,
                               static_cast<hipStream_t>(stream));
+}
+
+// ---- kernel-level hooks of the row passes (include/marl_hip_rowops.h; not part of the versioned ABI) ----
+int marl_ln_silu_bwd(const float* da, int ldda, const float* g, int ldg, int kin, const float* w1t, int ldw,
+                     const float* z, int ldz, const float* stats, const float* gamma, const float* beta,
+                     float* dz, int lddz, float* dgamma, float* dbeta, float* scratch, size_t scratch_bytes,
+                     int m, int n, void* stream) {
+    if (!z || !stats || !gamma || !beta || !dz || !dgamma || !dbeta || !scratch || m < 0 || n < 1 ||
+        (kin == 0 ? !da : (!g || !w1t))) {
+        set_error("marl_ln_silu_bwd: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    if (n > 2048) {
+        set_error("LayerNorm width %d > 2048 unsupported", n);
+        return MARL_ELIMIT;
+    }
+    if (m == 0) return MARL_OK;
+    const int blocks = ln_bwd_blocks(m, n);
+    if (scratch_bytes < (size_t)blocks * 2 * n * sizeof(float)) {
+        set_error("marl_ln_silu_bwd: scratch too small (%zu bytes needed)", (size_t)blocks * 2 * n * sizeof(float));
+        return MARL_ESIZE;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (kin == 0)
+        MARL_TRY(launch_ln_silu_bwd(da, ldda, z, ldz, stats, gamma, beta, dz, lddz, scratch, m, n, st));
+    else
+        MARL_TRY(launch_ln_silu_bwd_rank(g, ldg, kin, w1t, ldw, z, ldz, stats, gamma, beta, dz, lddz, scratch, m,
+                                         n, st));
+    return launch_reduce_affine(scratch, blocks, n, dgamma, dbeta, 0, st, nullptr);
+}
+
+int marl_gn_silu_bwd(const float* da, int64_t ldda, int da_chw, const float* z, const float* stats,
+                     const float* gamma, const float* beta, float* dz, float* dgamma, float* dbeta,
+                     float* scratch, size_t scratch_bytes, int64_t rows, int p, int c, int groups,
+                     void* stream) {
+    if (!da || !z || !stats || !gamma || !beta || !dz || !dgamma || !dbeta || !scratch || rows < 0 || p < 1 ||
+        c < 1 || groups < 1 || c % groups) {
+        set_error("marl_gn_silu_bwd: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    if (rows == 0) return MARL_OK;
+    const int blocks = gn_bwd_blocks(rows, c);
+    if (scratch_bytes < (size_t)blocks * 2 * c * sizeof(float)) {
+        set_error("marl_gn_silu_bwd: scratch too small (%zu bytes needed)", (size_t)blocks * 2 * c * sizeof(float));
+        return MARL_ESIZE;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MARL_TRY(launch_gn_silu_bwd(da, ldda, da_chw, z, stats, gamma, beta, dz, scratch, rows, p, c, groups, st));
+    return launch_reduce_affine(scratch, blocks, c, dgamma, dbeta, 0, st, nullptr);
 }
 
 }  // extern "C"

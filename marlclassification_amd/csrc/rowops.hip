@@ -399,6 +399,121 @@ __global__ __launch_bounds__(1024) void ln_silu_bwd_reg_kernel(
     }
 }
 
+// The same pass for FULL rows (n == 64 * U) whose source is known at compile time: KIN == 0 reads
+// da, KIN in 1..4 is the rank form with the sum ((g0 b0 + g1 b1) + g2 b2) + g3 b3 truncated at KIN
+// (the terms it drops are exact zeros in the run-time form).  No column predicates, no selects.
+// The wave index goes through readfirstlane, so the row, its base pointers, stats[r] and g[r][.]
+// are scalar values and a lane's part of an address is lane * 4 plus an immediate.
+// Rows go to waves and blocks, and partials to `part`, exactly as in the run-time form, and every
+// element sees the operation sequence of ln_silu_bwd_reg_kernel<U>: the products that form fuses
+// with the sum that follows them (the affine map, the SiLU derivative inside silu_grad, the dz
+// combination: three per element at U = 6) are spelled out here and contraction is off for the
+// rest, so both forms round alike whatever the vectoriser makes of either loop.
+template <int U, int KIN>
+__global__ __launch_bounds__(1024) void ln_silu_bwd_full_kernel(
+    const float* __restrict__ da, int ldda, const float* __restrict__ g, int ldg,
+    const float* __restrict__ bt, int ldbt, const float* __restrict__ z, int ldz,
+    const float* __restrict__ stats, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ dz, int lddz, float* __restrict__ part,
+    int64_t m, int rpw) {
+    extern __shared__ __attribute__((aligned(16))) float sacc[];  // [waves][2][n]
+    constexpr int n = 64 * U;
+    constexpr int KR = KIN > 0 ? KIN : 1;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nwaves = blockDim.x >> 6;
+    float gam[U], bet[U], pga[U], pgb[U], bw[U][KR];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int c = lane + 64 * u;
+        gam[u] = gamma[c];
+        bet[u] = beta[c];
+        pga[u] = pgb[u] = 0.f;
+#pragma unroll
+        for (int j = 0; j < KR; ++j) bw[u][j] = KIN > 0 ? bt[(size_t)c * ldbt + j] : 0.f;
+    }
+    const float inv_n = 1.0f / (float)n;
+    const int64_t row_base = ((int64_t)blockIdx.x * nwaves + wave) * rpw;
+    const int64_t left = m - row_base;
+    const int rows = left < rpw ? (int)left : rpw;  // (<= 0: a wave past the end)
+    struct Row {
+        float z[U], d[U], g[KR], mean, rstd;
+    };
+    auto fetch = [&](int64_t r, Row& w) {
+        const float* sr = stats + r * 2;
+        w.mean = sr[0];
+        w.rstd = sr[1];
+        if constexpr (KIN > 0) {
+            const float* gr = g + r * ldg;
+#pragma unroll
+            for (int j = 0; j < KR; ++j) w.g[j] = gr[j];
+        }
+        const float* zr = z + r * ldz + lane;
+#pragma unroll
+        for (int u = 0; u < U; ++u) w.z[u] = zr[64 * u];
+        if constexpr (KIN == 0) {
+            const float* dar = da + r * ldda + lane;
+#pragma unroll
+            for (int u = 0; u < U; ++u) w.d[u] = dar[64 * u];
+        }
+    };
+    auto step = [&](int64_t row, const Row& w) {
+#pragma clang fp contract(off)
+        float xh[U], dxh[U];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float dav;
+            if constexpr (KIN == 0) {
+                dav = w.d[u];
+            } else {
+                dav = w.g[0] * bw[u][0];
+#pragma unroll
+                for (int j = 1; j < KR; ++j) dav = dav + w.g[j] * bw[u][j];
+            }
+            xh[u] = (w.z[u] - w.mean) * w.rstd;
+            const float dy = dav * silu_grad(__builtin_fmaf(gam[u], xh[u], bet[u]));
+            dxh[u] = dy * gam[u];
+            s1 += dxh[u];
+            s2 += dxh[u] * xh[u];
+            pga[u] += dy * xh[u];
+            pgb[u] += dy;
+        }
+        const float m1 = wave_sum(s1) * inv_n, m2 = wave_sum(s2) * inv_n;
+        float* dzr = dz + row * lddz + lane;
+#pragma unroll
+        for (int u = 0; u < U; ++u) dzr[64 * u] = w.rstd * __builtin_fmaf(-xh[u], m2, dxh[u] - m1);
+    };
+    // Two rows in flight: the loads of row rr + 1 are issued before row rr is processed.  The last
+    // row is peeled off the loop, so every pass of the loop has a next row to fetch and the counter
+    // waits the compiler places in it leave those loads pending (with the prefetch under a condition
+    // the waits are sized for the pass that has none and drain the next row's loads on every pass).
+    if (rows > 0) {
+        Row cur, nxt;
+        fetch(row_base, cur);
+        for (int rr = 0; rr + 1 < rows; ++rr) {
+            fetch(row_base + rr + 1, nxt);
+            step(row_base + rr, cur);
+            cur = nxt;
+        }
+        step(row_base + rows - 1, cur);
+    }
+    float* ga = sacc + (size_t)wave * 2 * n;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int c = lane + 64 * u;
+        ga[c] = pga[u];
+        ga[n + c] = pgb[u];
+    }
+    __syncthreads();
+    float* p = part + (size_t)blockIdx.x * 2 * n;
+    for (int c = threadIdx.x; c < 2 * n; c += blockDim.x) {
+        float t = 0.f;
+        for (int w = 0; w < nwaves; ++w) t += sacc[(size_t)w * 2 * n + c];
+        p[c] = t;
+    }
+}
+
 // da == nullptr: rank-kin source (g, bt), see the kernel
 static int launch_ln_silu_bwd_any(const float* da, int ldda, const float* g, int ldg, int kin,
                                   const float* bt, int ldbt, const float* z, int ldz,
@@ -412,14 +527,28 @@ static int launch_ln_silu_bwd_any(const float* da, int ldda, const float* g, int
 #define MARL_LN_REG(U_)                                                                         \
     hipLaunchKernelGGL(ln_silu_bwd_reg_kernel<U_>, grid, blk, lds, st, da, ldda, g, ldg, kin, bt, \
                        ldbt, z, ldz, stats, gamma, beta, dz, lddz, part, m, n, rpw)
+#define MARL_LN_FULL(U_, KIN_)                                                                      \
+    hipLaunchKernelGGL((ln_silu_bwd_full_kernel<U_, KIN_>), grid, blk, lds, st, da, ldda, g, ldg, bt, \
+                       ldbt, z, ldz, stats, gamma, beta, dz, lddz, part, m, rpw)
+    // Full 384-wide rows with the sources the heads use (plain, critic, policy) take the compile-time
+    // forms.  Narrower full rows stay on the run-time form: the compiler fuses other products there
+    // (five per element at U = 2 and 4, three at U = 6), and a compile-time form has to round like
+    // the form it replaces.
     if (n <= 64)
         MARL_LN_REG(1);
     else if (n <= 128)
         MARL_LN_REG(2);
     else if (n <= 256)
         MARL_LN_REG(4);
+    else if (n == 384 && kin == 0)
+        MARL_LN_FULL(6, 0);
+    else if (n == 384 && kin == 1)
+        MARL_LN_FULL(6, 1);
+    else if (n == 384 && kin == 4)
+        MARL_LN_FULL(6, 4);
     else
         MARL_LN_REG(6);
+#undef MARL_LN_FULL
 #undef MARL_LN_REG
     MARL_LAUNCH_CHECK();
     return MARL_OK;
