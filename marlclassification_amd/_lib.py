@@ -84,6 +84,20 @@ EXPORTS = (
 
 # kernel-level test hooks that include/marl_hip_rowops.h declares (outside the versioned ABI above)
 ROWOP_HOOKS = ("marl_ln_silu_bwd", "marl_gn_silu_bwd")
+# ... and those of the conv backward that include/marl_hip_cnnops.h declares
+CNNOP_HOOKS = ("marl_cnn_dgrad", "marl_cnn_dgrad_scratch", "marl_cnn_bwd_plan")
+_HOOKS = ROWOP_HOOKS + CNNOP_HOOKS
+
+
+class CnnBwdPlan(C.Structure):
+    """Mirror of ``marl_cnn_bwd_plan_info`` (include/marl_hip_cnnops.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in (
+        "wg_form wg_rb wg_chunks wg_blocks wg_sct wg_skt wg_tgc wg_tgk wg_ms wg_slabs wg_pd wg_pi "
+        "dg_supported dg_rb dg_mt dg_nt dg_blocks").split()]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 _lib: Optional[C.CDLL] = None
 
@@ -171,7 +185,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_comm_range.argtypes = [_i, _i, _i]
     lib.marl_ln_silu_bwd.argtypes = [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _vp, _sz, _i, _i, _vp]
     lib.marl_gn_silu_bwd.argtypes = [_vp, _i64, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _vp]
-    for name in EXPORTS + list(ROWOP_HOOKS):
+    lib.marl_cnn_dgrad.argtypes = [_vp, _vp, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _i, _vp]
+    lib.marl_cnn_dgrad_scratch.restype = _sz
+    lib.marl_cnn_dgrad_scratch.argtypes = [_i64, _i, _i, _i, _i]
+    lib.marl_cnn_bwd_plan.argtypes = [_i64, _i, _i, _i, _i, _i, C.POINTER(CnnBwdPlan)]
+    for name in EXPORTS + list(_HOOKS):
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("marl_abi_version", "marl_tune_get"):
             fn.restype = _i
@@ -189,7 +207,7 @@ def load() -> C.CDLL:
             "or `python -c 'import __graft_entry__ as g; g.build()'`."
         )
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in EXPORTS + list(ROWOP_HOOKS) if not hasattr(lib, s)]
+    missing = [s for s in EXPORTS + list(_HOOKS) if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f"{LIB_PATH} lacks symbols {missing}")
     _declare(lib)

@@ -2133,6 +2133,16 @@ int cnn_dgrad_launch_rb(const CnnDgradArgs& a0) {
     return cnn_dgrad_rb(a);
 }
 
+CnnDgradPlanInfo cnn_dgrad_launch_plan(const CnnDgradArgs& a0) {
+    CnnDgradArgs a = a0;
+    CnnDgradPlanInfo p{};
+    p.rb = cnn_dgrad_rb(a);
+    if (p.rb <= 0) return CnnDgradPlanInfo{};
+    (void)cnn_dgrad_plan(a, p.rb);  // (cnn_dgrad_rb leaves the last rb it tried in `a`)
+    p.MT = a.MT, p.NT = a.NT, p.blocks = cnn_dgrad_blocks_max(a0);
+    return p;
+}
+
 // device-independent upper bound of cnn_dgrad_blocks (the workspace layout is computed without a GPU)
 int cnn_dgrad_blocks_max(const CnnDgradArgs& a0) {
     CnnDgradArgs a = a0;
@@ -2961,7 +2971,10 @@ CnnWgradPlanInfo cnn_wgrad_launch_plan(const CnnWgradArgs& a0) {
     size_t lds = 0;
     CnnWgradPlanInfo p{};
     p.form = cnn_wgrad_form(a, &lds);
-    if (p.form) p.rb = a.rb, p.chunks = a.nchunks, p.blocks = a.blocks;
+    if (p.form) {
+        p.rb = a.rb, p.chunks = a.nchunks, p.blocks = a.blocks;
+        p.sct = a.sct, p.skt = a.skt, p.tgc = a.tgc, p.tgk = a.tgk, p.ms = a.ms, p.slabs = a.slabs, p.pd = a.pd, p.pi = a.pi;
+    }
     return p;
 }
 

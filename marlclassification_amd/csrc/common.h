@@ -932,6 +932,12 @@ int cnn_dgrad_supported(const CnnDgradArgs& a);
 int cnn_dgrad_blocks(const CnnDgradArgs& a);      // partial rows the launch writes (persistent grid)
 int cnn_dgrad_blocks_max(const CnnDgradArgs& a);  // its device-independent upper bound
 int cnn_dgrad_launch_rb(const CnnDgradArgs& a);   // patches per chunk of the launch (0: no plan fits)
+// what launch_cnn_dgrad does with these shapes under the current knobs (host arithmetic): rb patches per chunk, MT x NT
+// 16-wide row / column tiles of the chunk's dA panel, blocks = cnn_dgrad_blocks_max; all 0 where no plan fits
+struct CnnDgradPlanInfo {
+    int rb, MT, NT, blocks;
+};
+CnnDgradPlanInfo cnn_dgrad_launch_plan(const CnnDgradArgs& a);
 int launch_cnn_dgrad(CnnDgradArgs& a, hipStream_t st);
 int cnn_dgrad_w0_ok(const CnnDgradArgs& a, int cin0, int f0);  // (see w0_part)
 
@@ -984,9 +990,11 @@ int cnn_wgrad_supported(const CnnWgradArgs& a);
 int cnn_wgrad_blocks(const CnnWgradArgs& a);   // partial slabs the launch writes
 int launch_cnn_wgrad(CnnWgradArgs& a, hipStream_t st);
 // what launch_cnn_wgrad does with these shapes: form 3 = cnn_wgrad3_kernel (bf16x6), 1 = cnn_wgrad_kernel, 0 = neither;
-// rb / chunks / blocks of that form's plan (blocks: the device-independent bound the launch trims to what is resident)
+// rb / chunks / blocks of that form's plan (blocks: the device-independent bound the launch trims to what is resident),
+// the instantiation (sct x skt accumulator tiles per wave, prefetch depth pd / pi), the wave roles and the k-slabs
 struct CnnWgradPlanInfo {
     int form, rb, chunks, blocks;
+    int sct, skt, tgc, tgk, ms, slabs, pd, pi;
 };
 CnnWgradPlanInfo cnn_wgrad_launch_plan(const CnnWgradArgs& a);
 // out[i * ldc + j] = sum over z < splits (fixed order) of part[z * stride + i * nj + j];

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "../../include/marl_hip_rowops.h"
+#include "../../include/marl_hip_cnnops.h"
 #include "common.h"
 
 namespace marl {
@@ -3115,6 +3116,90 @@ int marl_gn_silu_bwd(const float* da, int64_t ldda, int da_chw, const float* z, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     MARL_TRY(launch_gn_silu_bwd(da, ldda, da_chw, z, stats, gamma, beta, dz, scratch, rows, p, c, groups, st));
     return launch_reduce_affine(scratch, blocks, c, dgamma, dbeta, 0, st, nullptr);
+}
+
+// ---- kernel-level hooks of the conv backward (include/marl_hip_cnnops.h; not part of the versioned ABI) ----
+static CnnDgradArgs dgrad_api_args(int64_t rows, int cin, int cout, int hin, int groups) {
+    CnnDgradArgs g{};
+    g.rows = rows;
+    g.cin = cin;
+    g.cout = cout;
+    g.hin = hin;
+    g.hout = (hin - 1) / 2 + 1;
+    g.P = g.hout * g.hout;
+    g.Pin = hin * hin;
+    g.G = groups;
+    return g;
+}
+static bool dgrad_api_ok(int64_t rows, int cin, int cout, int hin, int groups) {
+    return rows >= 1 && cin >= 1 && cout >= 1 && hin >= 1 && groups >= 1 &&
+           cnn_dgrad_supported(dgrad_api_args(rows, cin, cout, hin, groups)) != 0;
+}
+
+size_t marl_cnn_dgrad_scratch(int64_t rows, int cin, int cout, int hin, int groups) {
+    if (!dgrad_api_ok(rows, cin, cout, hin, groups)) return 0;
+    return (size_t)cnn_dgrad_blocks_max(dgrad_api_args(rows, cin, cout, hin, groups)) * 2 * cin * sizeof(float);
+}
+
+int marl_cnn_dgrad(const float* dz, const float* wt, int ldwt, const float* zin, const float* gst,
+                   const float* gamma, const float* beta, float* dzin, float* dgamma, float* dbeta, float* scratch,
+                   size_t scratch_bytes, int64_t rows, int cin, int cout, int hin, int groups, void* stream) {
+    auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if (!dz || !wt || !zin || !gst || !gamma || !beta || !dzin || !dgamma || !dbeta || !scratch || rows < 1 ||
+        cin < 1 || cout < 1 || hin < 1 || groups < 1 || ldwt < cout || (ldwt & 3) || misaligned(dz) ||
+        misaligned(wt) || misaligned(zin) || misaligned(dzin)) {
+        set_error("marl_cnn_dgrad: null or misaligned pointer, or bad size");
+        return MARL_EINVAL;
+    }
+    if (!dgrad_api_ok(rows, cin, cout, hin, groups)) {
+        set_error("marl_cnn_dgrad: shape outside the fused kernel's range (cin %d cout %d hin %d groups %d)", cin, cout,
+                  hin, groups);
+        return MARL_ELIMIT;
+    }
+    CnnDgradArgs g = dgrad_api_args(rows, cin, cout, hin, groups);
+    const int nblk = cnn_dgrad_blocks(g);  // the grid = the partial rows written (<= the bound the query returns)
+    if (nblk < 1) {
+        set_error("marl_cnn_dgrad: no device");
+        return MARL_EHIP;
+    }
+    if (scratch_bytes < (size_t)nblk * 2 * cin * sizeof(float)) {
+        set_error("marl_cnn_dgrad: scratch too small (%zu bytes needed)", (size_t)nblk * 2 * cin * sizeof(float));
+        return MARL_ESIZE;
+    }
+    g.dz = dz;
+    g.wt = wt;
+    g.ldwt = ldwt;
+    g.zin = zin;
+    g.gst = gst;
+    g.gamma = gamma;
+    g.beta = beta;
+    g.dzin = dzin;
+    g.part = scratch;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MARL_TRY(launch_cnn_dgrad(g, st));
+    return launch_reduce_affine(scratch, nblk, cin, dgamma, dbeta, 0, st, nullptr);
+}
+
+int marl_cnn_bwd_plan(int64_t rows, int cin, int cout, int hin, int groups, int first,
+                      marl_cnn_bwd_plan_info* out) {
+    if (!out || rows < 1 || cin < 1 || cout < 1 || hin < 1 || (!first && groups < 1)) {
+        set_error("marl_cnn_bwd_plan: bad argument");
+        return MARL_EINVAL;
+    }
+    *out = marl_cnn_bwd_plan_info{};
+    // (the shapes marl_cnn_wgrad / marl_cnn_wgrad_scratch plan with: the image's size does not enter the plan)
+    const CnnWgradArgs w = wgrad_api_args(rows, 1, cin, hin + 1, hin + 1, cin, cout, hin, groups, first != 0);
+    if (cnn_wgrad_supported(w)) {
+        const CnnWgradPlanInfo p = cnn_wgrad_launch_plan(w);
+        out->wg_form = p.form, out->wg_rb = p.rb, out->wg_chunks = p.chunks, out->wg_blocks = p.blocks;
+        out->wg_sct = p.sct, out->wg_skt = p.skt, out->wg_tgc = p.tgc, out->wg_tgk = p.tgk, out->wg_ms = p.ms;
+        out->wg_slabs = p.slabs, out->wg_pd = p.pd, out->wg_pi = p.pi;
+    }
+    if (!first && dgrad_api_ok(rows, cin, cout, hin, groups)) {
+        const CnnDgradPlanInfo p = cnn_dgrad_launch_plan(dgrad_api_args(rows, cin, cout, hin, groups));
+        out->dg_supported = 1, out->dg_rb = p.rb, out->dg_mt = p.MT, out->dg_nt = p.NT, out->dg_blocks = p.blocks;
+    }
+    return MARL_OK;
 }
 
 }  // extern "C"
