@@ -549,7 +549,9 @@ int marl_profile_end(double* total_ms, int* launches);
 
 /* test hook: float offset and leading dimension of a named per-step activation inside
  * episode_ws ("U","H","C","HC","CC","MSG","PROBS","COLS0","Z0","GB","DU","DH","DHC"), or - "WP<i>" /
- * "WT<i>" - of the packed / transposed fp32 copy of parameter slot i inside weights_ws. */
+ * "WT<i>" - of the packed / transposed fp32 copy of parameter slot i inside weights_ws; "WPF<i>" / "WTF<i>" - of the
+ * panel kernels' fragment-order copy of that packed / transposed copy (ld = its 16-deep K groups per tile; error if
+ * the slot has none). */
 int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t,
                       int64_t* offset_floats, int* ld);
 

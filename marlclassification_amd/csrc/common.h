@@ -542,6 +542,10 @@ struct PermDesc {
     int dst_ld;
     int rd, rs1, rs2;    // src offset = (r / rd) * rs1 + (r % rd) * rs2
     int cd, cs1, cs2;    //            + (c / cd) * cs1 + (c % cd) * cs2
+    // frag > 0: dst is the panel kernels' fragment-order copy (panel_frag_index below, frag = 16-deep K groups per
+    // tile) of the row-major matrix src [rows, cols], leading dimension rs1; only the rows x cols real entries are
+    // written - the padding of the copy stays as the (zeroed) workspace holds it
+    int frag;
     const float* src2;   // optional: dst = src + src2 (same indexing), e.g. b_ih + b_hh
 };
 constexpr int kMaxPerm = 56;  // 64-byte descriptors: the batch stays under the 4 KB kernel-argument limit
@@ -550,6 +554,20 @@ struct PermBatch {
     int count;
 };
 int launch_permute(const PermBatch& b, hipStream_t st);
+
+// Fragment-order weight copy of the panel kernels (panel_gemm): the matrix W [n, K] (row = output column of the
+// product) as [tile of 32 rows][16-deep K group][half: rows l16 | 16 + l16][lane = quad * 16 + l16][4 floats], so that
+// one load instruction of a wave reads 1 KB contiguous and a 64-deep chunk of a tile 8 KB.  Rows >= n and columns >= K
+// are zero; three groups of slack behind the last tile keep the unconditional loads of a chunk that starts at the
+// last group inside the copy.
+__host__ __device__ inline int panel_frag_groups(int K) { return (K + 15) >> 4; }
+__host__ __device__ inline size_t panel_frag_floats(int n, int K) {
+    return ((size_t)((n + 31) >> 5) * panel_frag_groups(K) + 3) * 512;
+}
+__host__ __device__ inline size_t panel_frag_index(int r, int k, int groups) {
+    return ((((size_t)(r >> 5) * groups + (k >> 4)) * 2 + ((r >> 4) & 1)) * 64 + ((k >> 2) & 3) * 16 + (r & 15)) * 4 +
+           (k & 3);
+}
 
 // Device-resident per-iteration counters (marl_counters_* in marl_hip.h): what changes from one
 // training iteration to the next WITHOUT host involvement, so that a captured hipGraph can be
@@ -598,8 +616,8 @@ int launch_rowdot(const float* a, int lda, const float* w, const float* b, float
 // row-panel MLP kernels (panel.hip)
 // ---------------------------------------------------------------------------
 struct PanelLayer {
-    const float* w;  // [n, ldw] packed, K-contiguous
-    int ldw;
+    const float* wfrag;  // fragment-order copy of the weight [n, K] (panel_frag_index)
+    int wgroups;         // its 16-deep K groups per tile: panel_frag_groups(K)
     const float* bias;
     const float* gamma;
     const float* beta;
@@ -767,8 +785,8 @@ struct PanelBwdLayer {
     float* dz;  // out: d loss / d z [M, lddz] (kept for the weight gradients)
     int lddz;
     float* part;      // out: [gridDim.x][2][n] partial dgamma | dbeta of this launch
-    const float* wt;  // transposed weights [k_in, ldwt] (ldwt >= pad4(n)): dX = dz * W
-    int ldwt;
+    const float* wtfrag;  // fragment-order copy of the transposed weights [k_in, n] (panel_frag_index): dX = dz * W
+    int wgroups;          // its 16-deep groups per tile: panel_frag_groups(n)
     int k_in;  // width of this layer's input
 };
 struct PanelBwdProb {

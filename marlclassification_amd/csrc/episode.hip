@@ -199,6 +199,10 @@ struct WLayout {
     size_t wp3[MARL_NPARAMS], wt3[MARL_NPARAMS];  // bf16x3 images of wp / wt (gemm_split.hip)
     size_t wp3k[MARL_NPARAMS], wt3k[MARL_NPARAMS];  // k16 images of wp / wt (gemm3.hip, split.h), 0 = none
     size_t wf[MARL_NPARAMS];  // conv weights in MFMA-fragment order (cnn_fwd3), 0 = none
+    // fragment-order copies of wp / wt for the panel kernels (panel_frag_index, common.h), 0 = none; gpf / gtf:
+    // their 16-deep groups per tile
+    size_t wpf[MARL_NPARAMS], wtf[MARL_NPARAMS];
+    int gpf[MARL_NPARAMS], gtf[MARL_NPARAMS];
     size_t bsum_b, bsum_a;    // b_ih + b_hh
     size_t total;
 };
@@ -235,12 +239,27 @@ static bool g3_tn_enabled(const Dims& d) {
 // conv weights whose tiles are whole (16 output channels x 16-deep K steps) get a fragment-order copy
 static bool conv_frag_ok(const ParamMeta& m) { return m.kind == PK_CONV && m.n % 16 == 0 && m.k % 16 == 0; }
 
+// The matrices the panel kernels stream (panel_gemm): forward from the packed copies, backward (the four message
+// matrices) from the transposed ones.  Like g3_model_ok a property of the MODEL only - the weights workspace must not
+// move with the batch, nor with the MARL_PANELS switch.
+static bool panel_model_ok(const Dims& d) {
+    return panel_supported(d.n_m, d.nm2, d.n_mo) && panel_supported(d.n_b, d.nm2, d.n_m) &&
+           panel_supported(d.n_a, d.nla, 0);
+}
+static bool panel_frag_fwd(int i) {
+    return i == MARL_P_ENC_W0 || i == MARL_P_ENC_W1 || i == MARL_P_DEC_W0 || i == MARL_P_DEC_W1 || i == MARL_P_POL_W0;
+}
+static bool panel_frag_bwd(int i) {
+    return i == MARL_P_ENC_W0 || i == MARL_P_ENC_W1 || i == MARL_P_DEC_W0 || i == MARL_P_DEC_W1;
+}
+
 static void make_wlayout(const Dims& d, WLayout& w) {
     Bump b;
     for (int i = 0; i < MARL_NPARAMS; ++i) {
         const ParamMeta m = param_meta(d, i);
         w.wp[i] = w.wt[i] = w.gp[i] = w.wp3[i] = w.wt3[i] = w.wf[i] = w.wp3k[i] = w.wt3k[i] = 0;
-        w.ldp[i] = w.ldt[i] = 0;
+        w.wpf[i] = w.wtf[i] = 0;
+        w.ldp[i] = w.ldt[i] = w.gpf[i] = w.gtf[i] = 0;
         if (m.kind == PK_MATRIX || m.kind == PK_CONV) {
             w.ldp[i] = p4(m.k);
             w.wp[i] = b.take((size_t)m.n * w.ldp[i]);
@@ -265,6 +284,22 @@ static void make_wlayout(const Dims& d, WLayout& w) {
     }
     w.bsum_b = b.take((size_t)4 * d.n_b);
     w.bsum_a = b.take((size_t)4 * d.n_a);
+    // (behind everything else: no earlier offset moves; the pack writes the real entries only, the padding and the
+    // three groups of slack are the caller's zeros)
+    if (panel_model_ok(d)) {
+        for (int i = 0; i < MARL_NPARAMS; ++i) {
+            const ParamMeta m = param_meta(d, i);
+            if (m.kind != PK_MATRIX) continue;
+            if (panel_frag_fwd(i)) {  // W [n, k]: tiles over n, contraction over k
+                w.gpf[i] = panel_frag_groups(m.k);
+                w.wpf[i] = b.take(panel_frag_floats(m.n, m.k));
+            }
+            if (panel_frag_bwd(i)) {  // W^T [k, n]: tiles over k, contraction over n
+                w.gtf[i] = panel_frag_groups(m.n);
+                w.wtf[i] = b.take(panel_frag_floats(m.k, m.n));
+            }
+        }
+    }
     w.total = b.off;
 }
 
@@ -604,6 +639,9 @@ struct Ctx {
     char* img(size_t off) const { return reinterpret_cast<char*>(E + off); }
     const float* wp(int i) const { return W + w.wp[i]; }
     const float* wt(int i) const { return W + w.wt[i]; }
+    // fragment-order copies for the panel kernels (null: this model has none - the launchers refuse)
+    const float* wpf(int i) const { return w.wpf[i] ? W + w.wpf[i] : nullptr; }
+    const float* wtf(int i) const { return w.wtf[i] ? W + w.wtf[i] : nullptr; }
     float* gp(int i) const { return W + w.gp[i]; }
     float* at(size_t off) const { return E + off; }
     float* at(const SBuf& s, int t) const { return E + s.at(train ? t : 0); }
@@ -805,11 +843,11 @@ static int mix_msg(const Ctx& c, int t, const float* m, float* out, int n, int t
 static void fill_dec_layers(const Ctx& c, int t, PanelLayer* layer) {
     const Dims& d = c.d;
     const bool keep = c.train != 0;
-    layer[0] = PanelLayer{c.wp(MARL_P_DEC_W0), p4(d.n_m), c.wp(MARL_P_DEC_B0),
+    layer[0] = PanelLayer{c.wpf(MARL_P_DEC_W0), c.w.gpf[MARL_P_DEC_W0], c.wp(MARL_P_DEC_B0),
                           c.wp(MARL_P_DEC_LN0W), c.wp(MARL_P_DEC_LN0B), d.nm2,
                           keep ? c.at(c.e.ZD1, t) : nullptr, d.ld_nm2,
                           keep ? c.at(c.e.STD1, t) : nullptr, c.at(c.e.AD1, t), d.ld_nm2};
-    layer[1] = PanelLayer{c.wp(MARL_P_DEC_W1), d.ld_nm2, c.wp(MARL_P_DEC_B1),
+    layer[1] = PanelLayer{c.wpf(MARL_P_DEC_W1), c.w.gpf[MARL_P_DEC_W1], c.wp(MARL_P_DEC_B1),
                           c.wp(MARL_P_DEC_LN1W), c.wp(MARL_P_DEC_LN1B), d.n_mo,
                           keep ? c.at(c.e.ZD2, t) : nullptr, d.ld_nmo,
                           keep ? c.at(c.e.STD2, t) : nullptr, c.at(c.e.U, t) + d.nf, d.ld_nin};
@@ -952,11 +990,11 @@ static void fill_enc_prob(const Ctx& c, int t, PanelFwdProb& pe) {
     pe.k0 = d.n_b;
     pe.m = (int)d.R;
     pe.nlayers = 2;
-    pe.layer[0] = PanelLayer{c.wp(MARL_P_ENC_W0), d.ld_nb, c.wp(MARL_P_ENC_B0),
+    pe.layer[0] = PanelLayer{c.wpf(MARL_P_ENC_W0), c.w.gpf[MARL_P_ENC_W0], c.wp(MARL_P_ENC_B0),
                              c.wp(MARL_P_ENC_LN0W), c.wp(MARL_P_ENC_LN0B), d.nm2,
                              keep ? c.at(c.e.ZE1, t) : nullptr, d.ld_nm2,
                              keep ? c.at(c.e.STE1, t) : nullptr, c.at(c.e.AE1, t), d.ld_nm2};
-    pe.layer[1] = PanelLayer{c.wp(MARL_P_ENC_W1), d.ld_nm2, c.wp(MARL_P_ENC_B1),
+    pe.layer[1] = PanelLayer{c.wpf(MARL_P_ENC_W1), c.w.gpf[MARL_P_ENC_W1], c.wp(MARL_P_ENC_B1),
                              c.wp(MARL_P_ENC_LN1W), c.wp(MARL_P_ENC_LN1B), d.n_m,
                              keep ? c.at(c.e.ZE2, t) : nullptr, d.ld_nm,
                              keep ? c.at(c.e.STE2, t) : nullptr, c.MSGs(t + 1), d.ld_nm};
@@ -969,7 +1007,7 @@ static void fill_pol_prob(const Ctx& c, int t, PanelFwdProb& pp) {
     pp.k0 = d.n_a;
     pp.m = (int)d.R;
     pp.nlayers = 1;
-    pp.layer[0] = PanelLayer{c.wp(MARL_P_POL_W0), d.ld_na, c.wp(MARL_P_POL_B0),
+    pp.layer[0] = PanelLayer{c.wpf(MARL_P_POL_W0), c.w.gpf[MARL_P_POL_W0], c.wp(MARL_P_POL_B0),
                              c.wp(MARL_P_POL_LNW), c.wp(MARL_P_POL_LNB), d.nla,
                              keep ? c.at(c.e.ZP1, t) : nullptr, d.ld_nla,
                              keep ? c.at(c.e.STP1, t) : nullptr, c.at(c.e.AP1, t), d.ld_nla};
@@ -1199,6 +1237,7 @@ static PermDesc perm(const float* src, float* dst, int rows, int cols, int dst_l
     p.cd = cd;
     p.cs1 = cs1;
     p.cs2 = cs2;
+    p.frag = 0;
     p.src2 = src2;
     return p;
 }
@@ -1270,6 +1309,20 @@ static int pack_weights(const Dims& d, const WLayout& w, const float* const* par
         const int steps = m.k / 16;
         q.push(perm(W + w.wp[i], W + w.wf[i], (m.n / 16) * steps * 4, 64, 64, steps * 4, 16 * w.ldp[i], 4, 4,
                     w.ldp[i], 1));
+    }
+    // fragment-order copies for the panel kernels, from the packed / transposed copies just written
+    for (int i = 0; i < MARL_NPARAMS; ++i) {
+        const ParamMeta m = param_meta(d, i);
+        if (w.wpf[i]) {
+            PermDesc p = perm(W + w.wp[i], W + w.wpf[i], m.n, m.k, 0, 1, w.ldp[i], 0, 1, 1, 0);
+            p.frag = w.gpf[i];
+            q.push(p);
+        }
+        if (w.wtf[i]) {
+            PermDesc p = perm(W + w.wt[i], W + w.wtf[i], m.k, m.n, 0, 1, w.ldt[i], 0, 1, 1, 0);
+            p.frag = w.gtf[i];
+            q.push(p);
+        }
     }
     q.flush();
     MARL_TRY(q.rc);
@@ -1708,11 +1761,11 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
             pd.layer[0] = PanelBwdLayer{c.at(c.e.ZD2, t), d.ld_nmo, c.at(c.e.STD2, t),
                                         c.wp(MARL_P_DEC_LN1W), c.wp(MARL_P_DEC_LN1B), d.n_mo, ddbar,
                                         d.ld_dbl, c.at(c.e.PLN[0]) + (size_t)t * pblk * d.n_mo,
-                                        c.wt(MARL_P_DEC_W1), p4(d.n_mo), d.nm2};
+                                        c.wtf(MARL_P_DEC_W1), c.w.gtf[MARL_P_DEC_W1], d.nm2};
             pd.layer[1] = PanelBwdLayer{c.at(c.e.ZD1, t), d.ld_nm2, c.at(c.e.STD1, t),
                                         c.wp(MARL_P_DEC_LN0W), c.wp(MARL_P_DEC_LN0B), d.nm2, dad1,
                                         d.ld_nm2, c.at(c.e.PLN[1]) + (size_t)t * pblk * d.nm2,
-                                        c.wt(MARL_P_DEC_W0), p4(d.nm2), d.n_m};
+                                        c.wtf(MARL_P_DEC_W0), c.w.gtf[MARL_P_DEC_W0], d.n_m};
             pd.dx = c.at(c.e.DMBAR);
             pd.lddx = d.ld_nm;
             pd.accumulate = 0;
@@ -1739,12 +1792,12 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                                                 c.wp(MARL_P_ENC_LN1W), c.wp(MARL_P_ENC_LN1B), d.n_m,
                                                 c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm, d.ld_nm,
                                                 c.at(c.e.PLN[2]) + (size_t)(t - 1) * pblk * d.n_m,
-                                                c.wt(MARL_P_ENC_W1), p4(d.n_m), d.nm2};
+                                                c.wtf(MARL_P_ENC_W1), c.w.gtf[MARL_P_ENC_W1], d.nm2};
                     pd.layer[3] = PanelBwdLayer{c.at(c.e.ZE1, t - 1), d.ld_nm2, c.at(c.e.STE1, t - 1),
                                                 c.wp(MARL_P_ENC_LN0W), c.wp(MARL_P_ENC_LN0B), d.nm2,
                                                 c.at(c.e.DAE1) + (size_t)(t - 1) * s_nm2, d.ld_nm2,
                                                 c.at(c.e.PLN[3]) + (size_t)(t - 1) * pblk * d.nm2,
-                                                c.wt(MARL_P_ENC_W0), p4(d.nm2), d.n_b};
+                                                c.wtf(MARL_P_ENC_W0), c.w.gtf[MARL_P_ENC_W0], d.n_b};
                     pd.dx = c.DHs(t);
                     pd.lddx = d.ld_nb;
                     pd.accumulate = 1;
@@ -1778,12 +1831,12 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                                             c.wp(MARL_P_ENC_LN1W), c.wp(MARL_P_ENC_LN1B), d.n_m,
                                             dze2, d.ld_nm,
                                             c.at(c.e.PLN[2]) + (size_t)(t - 1) * pblk * d.n_m,
-                                            c.wt(MARL_P_ENC_W1), p4(d.n_m), d.nm2};
+                                            c.wtf(MARL_P_ENC_W1), c.w.gtf[MARL_P_ENC_W1], d.nm2};
                 pe.layer[1] = PanelBwdLayer{c.at(c.e.ZE1, t - 1), d.ld_nm2, c.at(c.e.STE1, t - 1),
                                             c.wp(MARL_P_ENC_LN0W), c.wp(MARL_P_ENC_LN0B), d.nm2,
                                             dae1, d.ld_nm2,
                                             c.at(c.e.PLN[3]) + (size_t)(t - 1) * pblk * d.nm2,
-                                            c.wt(MARL_P_ENC_W0), p4(d.nm2), d.n_b};
+                                            c.wtf(MARL_P_ENC_W0), c.w.gtf[MARL_P_ENC_W0], d.n_b};
                 pe.dx = c.DHs(t);
                 pe.lddx = d.ld_nb;
                 pe.accumulate = 1;
@@ -2792,6 +2845,15 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
         const int idx = atoi(name + 2);
         WLayout w;
         make_wlayout(d, w);
+        if (name[2] == 'F') {  // WPF<idx> / WTF<idx>: its fragment-order copy (ld: the 16-deep groups per tile)
+            const int fi = atoi(name + 3);
+            const size_t off = fi >= 0 && fi < MARL_NPARAMS ? (name[1] == 'P' ? w.wpf[fi] : w.wtf[fi]) : 0;
+            if (!off) {
+                set_error("parameter %d has no fragment-order copy", fi);
+                return MARL_EINVAL;
+            }
+            return set(off, name[1] == 'P' ? w.gpf[fi] : w.gtf[fi]);
+        }
         if (idx < 0 || idx >= MARL_NPARAMS || param_meta(d, idx).kind == PK_NONE) {
             set_error("no parameter %d", idx);
             return MARL_EINVAL;

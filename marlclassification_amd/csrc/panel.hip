@@ -3,10 +3,10 @@
 //
 // At R = Na*Nb rows and 64..384 features these layers are a few dozen MFLOP each: far too
 // small for a tiled GEMM launch + a LayerNorm launch per layer (each launch is latency
-// bound at ~10-20 us).  Here ONE workgroup owns a 32-row panel end to end:
+// bound at ~10-20 us).  Here ONE workgroup owns a 16-row panel (kPanelRows) end to end:
 //   stage the input rows in LDS (optionally computing the message mean over the other
-//   agents on the fly) -> [ X * W^T on the matrix cores, one 32x32 tile per wave, weights
-//   streamed straight from L2 -> bias -> LayerNorm + SiLU in the MFMA accumulator layout
+//   agents on the fly) -> [ X * W^T on the matrix cores, one 16x32 tile per wave, weights
+//   streamed straight from L2 (fragment-order copies) -> bias -> LayerNorm + SiLU in the MFMA accumulator layout
 //   (cross-lane + cross-wave row reductions) -> next layer's input panel in LDS ] x {1,2}.
 // The backward kernel walks the same chain in reverse (LayerNorm/SiLU backward in the tile
 // layout, dX GEMMs against the transposed weight copies) and emits per-panel partial sums
@@ -42,29 +42,27 @@ __host__ __device__ inline int panel_stride(int k) { return ((k + 15) & ~15) + 4
 // acc[t] = in[16 x Kslice] (LDS) * W[16 tile rows, Kslice]^T.  Weight fragments come straight
 // from global memory (L2), 8 x 16-byte loads (a 64-deep chunk of both sub-tiles) in flight
 // per wave; splitting K over waves puts ALL of a layer's weight loads in flight at once.
+// The weights are read from their fragment-order copy (panel_frag_index, common.h): each of the eight
+// loads of a chunk is 1 KB contiguous over the wave, at lane * 16 B behind a wave-uniform base, and the
+// chunk's 8 KB are consecutive.  The copy's padding (rows >= n, columns >= K) is zero and the loads past
+// a slice's end are never multiplied, so no address is clamped.
 // C/D layout of the 16x16 tile: col = lane & 15, row = 4 * (lane >> 4) + reg.
-__device__ __forceinline__ void panel_gemm(f32x4 (&acc)[2], const float* in, int stride, int K,
-                                           const float* __restrict__ w, int ldw, int n, int j,
+__device__ __forceinline__ void panel_gemm(f32x4 (&acc)[2], const float* in, int stride,
+                                           const float* __restrict__ wfrag, int groups, int j,
                                            int kbeg, int kend, int lane) {
-    const int K4 = (K + 3) & ~3;
     const int quad = lane >> 4, l16 = lane & 15;
     const float* arow = in + l16 * stride + 4 * quad;
-    int r0 = j * 32 + l16, r1 = r0 + 16;
-    r0 = r0 < n ? r0 : n - 1;
-    r1 = r1 < n ? r1 : n - 1;
-    const float* w0 = w + (size_t)r0 * ldw + 4 * quad;
-    const float* w1 = w + (size_t)r1 * ldw + 4 * quad;
+    const int g0 = __builtin_amdgcn_readfirstlane(j * groups + (kbeg >> 4));
+    const float* wb = wfrag + (size_t)g0 * 512;  // wave-uniform: tile j, first group of this slice
+    const unsigned lo = 4u * (unsigned)lane;
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[0][r] = acc[1][r] = 0.f;
-    for (int k0 = kbeg; k0 < kend; k0 += 64) {
+    for (int k0 = kbeg; k0 < kend; k0 += 64, wb += 4 * 512) {
         float4 b0[4], b1[4];
-        // columns [K, round16(K)) of the LDS panel are zero: a clamped (finite) read is exact
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int kk = k0 + 16 * i;
-            const int off = kk + 4 * quad < K4 ? kk : -4 * quad;
-            b0[i] = *reinterpret_cast<const float4*>(w0 + off);
-            b1[i] = *reinterpret_cast<const float4*>(w1 + off);
+            b0[i] = *reinterpret_cast<const float4*>(wb + 512 * i + lo);
+            b1[i] = *reinterpret_cast<const float4*>(wb + 512 * i + 256 + lo);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -476,7 +474,7 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
         const int kbeg = s * kper;
         const int kend = kbeg + kper < K16 ? kbeg + kper : K16;
         f32x4 acc[2];
-        if (active) panel_gemm(acc, in, stride, K, Lr.w, Lr.ldw, n, j, kbeg, kend, lane);
+        if (active) panel_gemm(acc, in, stride, Lr.wfrag, Lr.wgroups, j, kbeg, kend, lane);
         MARL_TS();
         panel_ksum(acc, part, nt, ks, j, s, lane, active);
         MARL_TS();
@@ -553,7 +551,17 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
     for (int i = 0; i < b.count; ++i) {
         const PanelFwdProb& p = b.p[i];
         for (int l = 0; l < p.nlayers; ++l) {
-            const int w = panel_waves_for(l == 0 ? p.k0 : p.layer[l - 1].n, p.layer[l].n);
+            const int kin = l == 0 ? p.k0 : p.layer[l - 1].n;
+            if (!p.layer[l].wfrag) {
+                set_error("panel kernel: layer %d has no fragment-order weight copy", l);
+                return MARL_EINVAL;
+            }
+            if (p.layer[l].wgroups != panel_frag_groups(kin)) {
+                set_error("panel kernel: layer %d's weight copy has %d K groups, its input width %d needs %d", l,
+                          p.layer[l].wgroups, kin, panel_frag_groups(kin));
+                return MARL_ELIMIT;
+            }
+            const int w = panel_waves_for(kin, p.layer[l].n);
             if (w < 0) {
                 set_error("panel kernel: layer width %d too large", p.layer[l].n);
                 return MARL_ELIMIT;
@@ -998,7 +1006,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
             const int kbeg = s * kper;
             const int kend = kbeg + kper < n16 ? kbeg + kper : n16;
             f32x4 acc[2];
-            if (active) panel_gemm(acc, D, ds, n, Lr.wt, Lr.ldwt, nout, j, kbeg, kend, lane);
+            if (active) panel_gemm(acc, D, ds, Lr.wtfrag, Lr.wgroups, j, kbeg, kend, lane);
             // slice partials are indexed by the tile's slot in this round
             panel_ksum(acc, part, tiles_round, ks, wave % tiles_round, s, lane, active);
             if (active && s == 0) {
@@ -1141,6 +1149,15 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
     p.tail_lds = tail_lds ? 1 : 0;
     for (int l = 0; l < p.nlayers; ++l) {
         const PanelBwdLayer& L = p.layer[l];
+        if (!L.wtfrag) {
+            set_error("panel backward: layer %d has no fragment-order copy of its transposed weight", l);
+            return MARL_EINVAL;
+        }
+        if (L.wgroups != panel_frag_groups(L.n)) {
+            set_error("panel backward: layer %d's weight copy has %d groups, its width %d needs %d", l, L.wgroups, L.n,
+                      panel_frag_groups(L.n));
+            return MARL_ELIMIT;
+        }
         if (L.n > 64 * kBwdMaxCols) {
             set_error("panel backward: LayerNorm width %d > %d", L.n, 64 * kBwdMaxCols);
             return MARL_ELIMIT;

@@ -1740,6 +1740,14 @@ int launch_draw_episode(uint64_t seed, uint64_t offset, const uint64_t* offset_d
 __global__ void permute_kernel(const PermBatch B) {
     const PermDesc& d = B.d[blockIdx.y];
     const int64_t tot = (int64_t)d.rows * d.cols;
+    if (d.frag > 0) {  // fragment-order copy of a row-major matrix (real entries only)
+        for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot;
+             idx += (int64_t)gridDim.x * blockDim.x) {
+            const int r = (int)(idx / d.cols), c = (int)(idx % d.cols);
+            d.dst[panel_frag_index(r, c, d.frag)] = d.src[(int64_t)r * d.rs1 + c];
+        }
+        return;
+    }
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot;
          idx += (int64_t)gridDim.x * blockDim.x) {
         const int r = (int)(idx / d.cols), c = (int)(idx % d.cols);
