@@ -673,7 +673,6 @@ static int g_comm_na = 0;
 // the positions of its emission, POS[t]; the zero message of step 0 under POS[0].  The chained panel launches build
 // the gated matrices in their workgroups (the GATE instantiations), every other site takes mix_msg_gated_kernel.
 static CommGate g_range = {nullptr, -1, 0, 1};
-static bool use_side_stream();
 
 static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void* ews, size_t ebytes,
                     int train, void* stream, Ctx& c) {
@@ -715,7 +714,7 @@ static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void
     CnnFwdArgs probe = cnn_fwd_shape(c.d);  // (with the fragment-order weight copies the AidCnn kernels ask for)
     for (int l = 0; l < c.d.L; ++l) probe.layer[l].wfrag = c.w.wf[4 * l] ? c.W + c.w.wf[4 * l] : nullptr;
     c.u3_by_producers = c.e.g3 && tune_get("g3_lstm", 1) != 0 && c.e.fused_fwd &&
-                        cnn_fwd_writes_image(probe) && use_panels(c.d) && !use_side_stream() &&
+                        cnn_fwd_writes_image(probe) && use_panels(c.d) &&
                         ((c.d.nf | c.d.n_mo | c.d.n_d) & 3) == 0 &&
                         // (the producers write exactly nin columns: a K pad of the last 16-deep step would be
                         // whatever the workspace held - only the stand-alone image pass zeroes it)
@@ -1013,48 +1012,35 @@ static void fill_pol_prob(const Ctx& c, int t, PanelFwdProb& pp) {
                              keep ? c.at(c.e.STP1, t) : nullptr, c.at(c.e.AP1, t), d.ld_nla};
 }
 
-// message encoder -> MSG[t+1] (which = 1), policy hidden layer -> AP1[t] (which = 2), or both
-// in one launch (which = 3).                                   (needs H / H^[t+1])
-static int step_encode_policy(const Ctx& c, int t, int which) {
+// message encoder -> MSG[t+1] and policy hidden layer -> AP1[t]  (needs H / H^[t+1])
+static int step_encode_policy(const Ctx& c, int t) {
     const Dims& d = c.d;
     const int R = (int)d.R;
     hipStream_t st = c.st;
     if (use_panels(d)) {
         PanelFwdBatch pb{};
-        pb.count = 0;
-        if (which & 1) fill_enc_prob(c, t, pb.p[pb.count++]);
-        if (which & 2) fill_pol_prob(c, t, pb.p[pb.count++]);
+        pb.count = 2;
+        fill_enc_prob(c, t, pb.p[0]);
+        fill_pol_prob(c, t, pb.p[1]);
         return launch_panel_fwd(pb, st);
     }
-    if (which == 3) {
-        MARL_TRY(gemm2(c,
-                       gemm_prob(c.Hs(t + 1), d.ld_nb, c.wp(MARL_P_ENC_W0), d.ld_nb, d.n_b,
-                                 c.at(c.e.ZE1, t), d.ld_nm2, R, d.nm2, c.wp(MARL_P_ENC_B0)),
-                       gemm_prob(c.HCs(t + 1), d.ld_na, c.wp(MARL_P_POL_W0), d.ld_na, d.n_a,
-                                 c.at(c.e.ZP1, t), d.ld_nla, R, d.nla, c.wp(MARL_P_POL_B0))));
-    } else if (which == 1) {
-        MARL_TRY(gemm1(c, gemm_prob(c.Hs(t + 1), d.ld_nb, c.wp(MARL_P_ENC_W0), d.ld_nb, d.n_b,
-                                    c.at(c.e.ZE1, t), d.ld_nm2, R, d.nm2, c.wp(MARL_P_ENC_B0))));
-    } else {
-        MARL_TRY(gemm1(c, gemm_prob(c.HCs(t + 1), d.ld_na, c.wp(MARL_P_POL_W0), d.ld_na, d.n_a,
-                                    c.at(c.e.ZP1, t), d.ld_nla, R, d.nla, c.wp(MARL_P_POL_B0))));
-    }
-    if (which & 2)
-        MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZP1, t), d.ld_nla, c.wp(MARL_P_POL_LNW),
-                                    c.wp(MARL_P_POL_LNB), c.at(c.e.AP1, t), d.ld_nla,
-                                    c.at(c.e.STP1, t), d.R, d.nla, st));
-    if (which & 1) {
-        MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZE1, t), d.ld_nm2, c.wp(MARL_P_ENC_LN0W),
-                                    c.wp(MARL_P_ENC_LN0B), c.at(c.e.AE1, t), d.ld_nm2,
-                                    c.at(c.e.STE1, t), d.R, d.nm2, st));
-        MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AE1, t), d.ld_nm2, c.wp(MARL_P_ENC_W1), d.ld_nm2,
-                                    d.nm2, c.at(c.e.ZE2, t), d.ld_nm, R, d.n_m,
-                                    c.wp(MARL_P_ENC_B1))));
-        MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZE2, t), d.ld_nm, c.wp(MARL_P_ENC_LN1W),
-                                    c.wp(MARL_P_ENC_LN1B), c.MSGs(t + 1), d.ld_nm,
-                                    c.at(c.e.STE2, t), d.R, d.n_m, st));
-    }
-    return MARL_OK;
+    MARL_TRY(gemm2(c,
+                   gemm_prob(c.Hs(t + 1), d.ld_nb, c.wp(MARL_P_ENC_W0), d.ld_nb, d.n_b,
+                             c.at(c.e.ZE1, t), d.ld_nm2, R, d.nm2, c.wp(MARL_P_ENC_B0)),
+                   gemm_prob(c.HCs(t + 1), d.ld_na, c.wp(MARL_P_POL_W0), d.ld_na, d.n_a,
+                             c.at(c.e.ZP1, t), d.ld_nla, R, d.nla, c.wp(MARL_P_POL_B0))));
+    MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZP1, t), d.ld_nla, c.wp(MARL_P_POL_LNW),
+                                c.wp(MARL_P_POL_LNB), c.at(c.e.AP1, t), d.ld_nla,
+                                c.at(c.e.STP1, t), d.R, d.nla, st));
+    MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZE1, t), d.ld_nm2, c.wp(MARL_P_ENC_LN0W),
+                                c.wp(MARL_P_ENC_LN0B), c.at(c.e.AE1, t), d.ld_nm2,
+                                c.at(c.e.STE1, t), d.R, d.nm2, st));
+    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AE1, t), d.ld_nm2, c.wp(MARL_P_ENC_W1), d.ld_nm2,
+                                d.nm2, c.at(c.e.ZE2, t), d.ld_nm, R, d.n_m,
+                                c.wp(MARL_P_ENC_B1))));
+    return launch_ln_silu_fwd(c.at(c.e.ZE2, t), d.ld_nm, c.wp(MARL_P_ENC_LN1W),
+                              c.wp(MARL_P_ENC_LN1B), c.MSGs(t + 1), d.ld_nm,
+                              c.at(c.e.STE2, t), d.R, d.n_m, st);
 }
 
 // All agents of a batch element in one workgroup (rows a * nb + b for every a), so that the
@@ -1110,41 +1096,7 @@ static int step_core(const Ctx& c, int t, const StepIn& in) {
     MARL_TRY(step_cnn(c, t, in));
     MARL_TRY(step_decode(c, t));
     MARL_TRY(step_pos_lstm(c, t, in));
-    return step_encode_policy(c, t, 3);
-}
-
-// ---------------------------------------------------------------------------
-// side stream: chains that are independent within a step run concurrently
-//   forward : message encoder(t) -> decoder(t+1)   ||  policy(t) -> sample(t) -> CNN(t+1)
-//   backward: W_hh recurrent GEMM(t)               ||  decoder / encoder backward chain(t)
-// ---------------------------------------------------------------------------
-struct SideStream {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[64];
-    int next = 0;
-    int init() {
-        if (s) return MARL_OK;
-        MARL_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        for (auto& e : ev) MARL_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        return MARL_OK;
-    }
-    // everything enqueued on `from` so far happens before what is enqueued on `to` afterwards
-    int order(hipStream_t from, hipStream_t to) {
-        hipEvent_t e = ev[next];
-        next = (next + 1) % 64;
-        MARL_HIP_CHECK(hipEventRecord(e, from));
-        MARL_HIP_CHECK(hipStreamWaitEvent(to, e, 0));
-        return MARL_OK;
-    }
-};
-static SideStream g_side;
-
-static bool use_side_stream() {
-    static int enabled = -1;
-    // measured on MI355X (C3, rounds 1-2): no gain (16.38 vs 16.28 ms / iteration; round 2: 11.15 vs 10.23) - the
-    // cross-stream event waits cost what the overlap buys.  The environment switch is gone; the form stays for reference.
-    (void)enabled;
-    return false;
+    return step_encode_policy(c, t);
 }
 
 // critic + prediction heads on `rows` rows starting at state slice t0 (+1)
@@ -1514,35 +1466,89 @@ struct StepBwd {
     float *d_msg = nullptr, *d_h = nullptr, *d_c = nullptr, *d_hc = nullptr, *d_cc = nullptr;
 };
 
-static int episode_backward(const Ctx& c0, const void* img, int img_u8, const float* g_preds,
-                            const float* g_logp, const float* g_values, float* const* grads,
-                            const StepBwd* sb = nullptr, float* d_img = nullptr,
-                            const float* g_probs = nullptr) {
-    Ctx c = c0;
-    RedQueue rq;
-    rq.reset(c.at(c.e.RED), c.e.red_floats, c.st);
-    // 1: the small LayerNorm / GroupNorm affine partials wait for one launch at the end; the
-    // weight-gradient slabs (~0.4 GB per iteration in all) are reduced at once, while the
-    // Infinity Cache still holds them (2: defer those too - measured slower at C3 / C4: 0.43 GB of
-    // slabs come back from HBM).  3 (default): as 1, plus the slabs of at most red_defer_kb KB
-    // each (8 MB: larger thresholds lose again at C4) - on small problems (C2: 22 weight gradients) one batched
-    // reduction replaces 22 launches: 0.953 -> 0.897 ms per iteration.
-    const int defer = tune_get("red_defer", 3);
-    TnQueue tq;
-    if (defer) c.rq = &rq;
-    if (defer) c.tq = &tq;
-    c.defer_slabs = defer == 2;
-    c.defer_small = defer == 3 ? (size_t)8192 * 1024 : 0;
+// ---- one builder per descriptor (the backward's counterparts of fill_dec_layers / fill_enc_prob) ----
+
+// elementwise backward of the belief (which = 0) or action (1) cell of step t: dh = DH / DH^[t + 1], gates G[t]
+static LstmBwdArgs cell_bwd_args(const Ctx& c, int which, int t, int skip_f32) {
     const Dims& d = c.d;
+    const int n = which ? d.n_a : d.n_b, ld = which ? d.ld_na : d.ld_nb;
+    return LstmBwdArgs{which ? c.DHCs(t + 1) : c.DHs(t + 1), c.at(which ? c.e.DCC : c.e.DC),
+                       c.at(which ? c.e.GA : c.e.GB, t), which ? c.CCs(t) : c.Cs(t),
+                       which ? c.CCs(t + 1) : c.Cs(t + 1), ld, ld, which ? d.ld_ga : d.ld_gb, ld, n,
+                       c.e.g3 ? c.img(which ? c.e.GA3 : c.e.GB3) : nullptr, (int)((int64_t)t * d.R), img_steps(4 * n),
+                       skip_f32};
+}
+
+// the decoder's two layers of step t, output side first (pblk: floats per step and column of a PLN partial)
+static void fill_dec_bwd_layers(const Ctx& c, int t, size_t pblk, float* ddbar, float* dad1, PanelBwdLayer* layer) {
+    const Dims& d = c.d;
+    layer[0] = PanelBwdLayer{c.at(c.e.ZD2, t), d.ld_nmo, c.at(c.e.STD2, t), c.wp(MARL_P_DEC_LN1W),
+                             c.wp(MARL_P_DEC_LN1B), d.n_mo, ddbar, d.ld_dbl,
+                             c.at(c.e.PLN[0]) + (size_t)t * pblk * d.n_mo, c.wtf(MARL_P_DEC_W1),
+                             c.w.gtf[MARL_P_DEC_W1], d.nm2};
+    layer[1] = PanelBwdLayer{c.at(c.e.ZD1, t), d.ld_nm2, c.at(c.e.STD1, t), c.wp(MARL_P_DEC_LN0W),
+                             c.wp(MARL_P_DEC_LN0B), d.nm2, dad1, d.ld_nm2,
+                             c.at(c.e.PLN[1]) + (size_t)t * pblk * d.nm2, c.wtf(MARL_P_DEC_W0),
+                             c.w.gtf[MARL_P_DEC_W0], d.n_m};
+}
+// the encoder's two layers of step t (dz -> DZE2[t], DAE1[t])
+static void fill_enc_bwd_layers(const Ctx& c, int t, size_t pblk, PanelBwdLayer* layer) {
+    const Dims& d = c.d;
+    layer[0] = PanelBwdLayer{c.at(c.e.ZE2, t), d.ld_nm, c.at(c.e.STE2, t), c.wp(MARL_P_ENC_LN1W),
+                             c.wp(MARL_P_ENC_LN1B), d.n_m, c.at(c.e.DZE2) + (size_t)t * d.R * d.ld_nm, d.ld_nm,
+                             c.at(c.e.PLN[2]) + (size_t)t * pblk * d.n_m, c.wtf(MARL_P_ENC_W1),
+                             c.w.gtf[MARL_P_ENC_W1], d.nm2};
+    layer[1] = PanelBwdLayer{c.at(c.e.ZE1, t), d.ld_nm2, c.at(c.e.STE1, t), c.wp(MARL_P_ENC_LN0W),
+                             c.wp(MARL_P_ENC_LN0B), d.nm2, c.at(c.e.DAE1) + (size_t)t * d.R * d.ld_nm2, d.ld_nm2,
+                             c.at(c.e.PLN[3]) + (size_t)t * pblk * d.nm2, c.wtf(MARL_P_ENC_W0),
+                             c.w.gtf[MARL_P_ENC_W0], d.n_b};
+}
+
+// `floats` of per-workgroup weight-gradient slabs: the deferred queue's scratch when their reduction may wait, else TNS
+static float* slab_scratch(const Ctx& c, size_t floats) {
+    if (c.rq && c.defer_this(floats * sizeof(float))) {
+        float* p = c.rq->take(floats);
+        if (c.rq->rc == MARL_OK) return p;
+    }
+    return c.at(c.e.TNS);
+}
+// ... and their reduction into gp(pidx) [co, k] and bias [co]: queued behind the scratch taken, or launched now
+static int slab_reduce(const Ctx& c, float* part_w, float* part_b, int blocks, int co, int k, int pidx, float* bias) {
+    if (c.rq && part_w != c.at(c.e.TNS)) {
+        c.rq->push(part_w, (int64_t)co * k, blocks, co * k, c.gp(pidx), co * k, k, c.w.ldp[pidx], nullptr, 0);
+        c.rq->push(part_b, co, blocks, co, bias, co, co, co, nullptr, 0);
+        return MARL_OK;
+    }
+    return launch_slab_reduce(part_w, (int64_t)co * k, blocks, c.gp(pidx), c.w.ldp[pidx], co, k, part_b, bias, c.st);
+}
+
+// ---- the backward driver: what lives across its parts ----
+struct BwdState {
+    Ctx c;  // the caller's context with the queues below installed (the rows path drops them before its loop)
+    RedQueue rq;
+    TnQueue tq;
+    float* const* grads;
+    const StepBwd* sb;
+    bool enc_last = false;     // a standalone step with an upstream gradient of its new message
+    bool heads_early = false;  // the heads' gradients were flushed and unpacked ahead of the loop
+    bool panels = false;       // the loop runs panel launches (else GEMM + ln_bwd rows)
+    bool chain = false;        // ... the chained ones
+    int skip_f32 = 0;          // every consumer of the gate gradients reads their images: no fp32 copy at all
+    int pln_blocks = 0;        // workgroups of one panel launch = partial rows per step in PLN
+    bool action_done = false;  // the action cell of this step was handled by the ride-along
+    bool belief_done = false;  // the belief cell: by the epilogue of the chained panel launch
+};
+
+// ---- heads, batched over all steps -----------------------------------------------
+static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, const float* g_values,
+                     const float* g_probs) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    const StepBwd* sb = s.sb;
+    float* const* grads = s.grads;
     hipStream_t st = c.st;
     const int64_t NR = d.NR;
-    const int R = (int)d.R, ns = d.ns;
-    for (int i = 0; i < MARL_NPARAMS; ++i)
-        if (param_meta(d, i).kind != PK_NONE && !grads[i]) {
-            set_error("gradient buffer %d is null", i);
-            return MARL_EINVAL;
-        }
-    // ---- heads, batched over all steps -----------------------------------------------
+    const int ns = d.ns;
     // prediction head (networks/prediction.py:11-14)
     {   // output gradients into the padded layouts + the zero initial state gradients: one launch
         PermQueue q(st);
@@ -1616,266 +1622,229 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
 
     // Data parallelism (parallel.py, BucketedGradAllReduce): every gradient of the three heads' parameters (POL_*,
     // CRI_*, PRE_*) is complete here, ahead of the ~1.4 ms reverse loop - flush what they queued and mark the point.
-    const bool heads_early = g_heads_event != nullptr && !sb;
-    if (heads_early) {
-        if (c.tq) MARL_TRY(launch_tn_queue(tq, c.rq, st));
-        MARL_TRY(rq.flush());
+    s.heads_early = g_heads_event != nullptr && !sb;
+    if (s.heads_early) {
+        if (c.tq) MARL_TRY(launch_tn_queue(s.tq, c.rq, st));
+        MARL_TRY(s.rq.flush());
         MARL_TRY(unpack_grads(c, grads, 1));  // (their matrices leave the packed layout now; the end skips them)
         MARL_HIP_CHECK(hipEventRecord(g_heads_event, st));
     }
+    return MARL_OK;
+}
 
-    // ---- reverse-time loop over the recurrent chain ----------------------------------
-    const size_t s_nmo = (size_t)d.R * d.ld_dbl, s_nm2 = (size_t)d.R * d.ld_nm2,
-                 s_nm = (size_t)d.R * d.ld_nm;
-    const bool panels = use_panels(d) && d.n_mo <= 384 && d.nm2 <= 384 && d.n_m <= 384;
+// ---- reverse-time loop over the recurrent chain ----------------------------------
+
+// rows path: the encoder of step t backward from a ready DZE2[t] (d loss / d its message); adds dL/dh into dh
+static int enc_bwd_rows(const BwdState& s, int t, int acc, float* dh) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    const int R = (int)d.R;
+    float* dze2 = c.at(c.e.DZE2) + (size_t)t * d.R * d.ld_nm;
+    float* dae1 = c.at(c.e.DAE1) + (size_t)t * d.R * d.ld_nm2;
+    MARL_TRY(ln_bwd(c, dze2, d.ld_nm, c.at(c.e.ZE2, t), d.ld_nm, c.at(c.e.STE2, t), MARL_P_ENC_LN1W,
+                    MARL_P_ENC_LN1B, d.R, d.n_m, s.grads, acc));
+    MARL_TRY(gemm1(c, gemm_prob(dze2, d.ld_nm, c.wt(MARL_P_ENC_W1), p4(d.n_m), d.n_m, dae1, d.ld_nm2, R, d.nm2)));
+    MARL_TRY(ln_bwd(c, dae1, d.ld_nm2, c.at(c.e.ZE1, t), d.ld_nm2, c.at(c.e.STE1, t), MARL_P_ENC_LN0W,
+                    MARL_P_ENC_LN0B, d.R, d.nm2, s.grads, acc));
+    return gemm1(c, gemm_prob(dae1, d.ld_nm2, c.wt(MARL_P_ENC_W0), p4(d.nm2), d.nm2, dh, d.ld_nb, R, d.n_b, nullptr, 1));
+}
+
+// recurrent paths dh_{t-1} += dgates * W_hh, and d(decoded message) = columns [nf, nf + n_mo) of dU - independent
+// products of the same gate gradients, one launch
+static int bwd_recurrent(const BwdState& s, int t, float* ddbar, float* ddbar2) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    const int R = (int)d.R;
+    // (gates of cell `which`, weight, its first row, output, ld, width, accumulate).  The panel paths take all four,
+    // of EQUAL depth (a two-segment one would run twice as long as the others and finish the launch alone): each
+    // cell's share of dU[:, nf:] - the decoded-message AND the position-embedding columns, which sit next to each
+    // other and fit the same two 64-wide tiles - goes to its own buffer; the decoder panel sums the message halves
+    // while staging, the embedding halves are summed once after the loop.  The big dU product then only covers the
+    // CNN features.
+    const struct { int which, w, row0; float* out; int ldo, n, acc; } prod[4] = {
+        {0, MARL_P_LB_WHH, 0, c.DHs(t), d.ld_nb, d.n_b, 1},
+        {1, MARL_P_LA_WHH, 0, c.DHCs(t), d.ld_na, d.n_a, 1},
+        {0, MARL_P_LB_WIH, d.nf, ddbar, d.ld_dbl, d.n_mo + d.n_d, 0},
+        {1, MARL_P_LA_WIH, d.nf, ddbar2, d.ld_dbl, d.n_mo + d.n_d, 0}};
+    const int count = s.panels ? 4 : 2;
+    if (s.panels && c.e.g3) {  // from the images of the gate gradients
+        G3Batch g{};
+        for (int i = 0; i < count; ++i) {
+            const auto& q = prod[i];
+            g.p[i] = g3_prob(c.img(q.which ? c.e.GA3 : c.e.GB3), (int)((int64_t)t * d.R), c.wt3k(q.w), q.row0,
+                             4 * (q.which ? d.n_a : d.n_b), q.out, q.ldo, R, q.n, nullptr, q.acc);
+        }
+        g.count = count;
+        return launch_gemm_nt3(g, c.st);
+    }
+    GemmBatch gb{};
+    for (int i = 0; i < count; ++i) {
+        const auto& q = prod[i];
+        const int ldg = q.which ? d.ld_ga : d.ld_gb;
+        gb.p[i] = gemm_prob(c.at(q.which ? c.e.GA : c.e.GB, t), ldg, c.wt(q.w) + (size_t)q.row0 * ldg, ldg,
+                            4 * (q.which ? d.n_a : d.n_b), q.out, q.ldo, R, q.n, nullptr, q.acc);
+    }
+    gb.count = count;
+    if (!s.panels) {  // rows path: only the message columns, both cells' shares summed by one two-segment product
+        GemmProb& p = gb.p[gb.count++];
+        p = gemm_prob(c.at(c.e.GB, t), d.ld_gb, c.wt(MARL_P_LB_WIH) + (size_t)d.nf * d.ld_gb, d.ld_gb, 4 * d.n_b,
+                      ddbar, d.ld_dbl, R, d.n_mo);
+        gemm_add_seg(p, c.at(c.e.GA, t), d.ld_ga, c.wt(MARL_P_LA_WIH) + (size_t)d.nf * d.ld_ga, d.ld_ga, 4 * d.n_a);
+    }
+    return launch_gemm_nt(gb, c.st);
+}
+
+// the decoder panel of step t as both panel bodies launch it.  The action cell's backward of step t-1 only needs
+// dh^_t, which is complete after step t's W_hh product; it rides along (extra workgroups) with this launch, so that
+// from the second iteration on only the belief cell is left for the separate launch.
+static void fill_dec_bwd_prob(BwdState& s, int t, float* ddbar, float* ddbar2, PanelBwdProb& pd) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    pd.da = ddbar;
+    pd.ldda = d.ld_dbl;
+    pd.da2 = ddbar2;
+    pd.ldda2 = d.ld_dbl;
+    pd.m = (int)d.R;
+    pd.nlayers = 2;
+    fill_dec_bwd_layers(c, t, (size_t)s.pln_blocks * 2, ddbar, c.at(c.e.DAD1) + (size_t)t * d.R * d.ld_nm2, pd.layer);
+    pd.dx = c.at(c.e.DMBAR);
+    pd.lddx = d.ld_nm;
+    pd.accumulate = 0;
+    if (t > 0) {  // action cell of step t-1: gates GA[t-1], dh^ = DHC[t]
+        pd.has_cell = 1;
+        pd.cell = cell_bwd_args(c, 1, t - 1, s.skip_f32);
+        pd.cell_rows = d.R;
+        s.action_done = true;
+    }
+}
+
+// chained panels: decoder(t) -> mean -> encoder(t-1) -> dh_t -> belief cell(t-1), one launch
+static int bwd_step_chain(BwdState& s, int t, float* ddbar, float* ddbar2) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    PanelBwdProb pd{};
+    fill_dec_bwd_prob(s, t, ddbar, ddbar2, pd);
+    pd.by_batch = panel_chain_by_batch(d.na);
+    pd.g_na = d.na;
+    pd.g_nb = d.nb;
+    if (t > 0) {
+        pd.nlayers = 4;
+        pd.agg_at = 2;
+        pd.mix = g_comm;  // (null: the self-adjoint mean; else the kernel applies M^T)
+        if (g_comm) pd.gate = comm_gate(c, t);
+        fill_enc_bwd_layers(c, t - 1, (size_t)s.pln_blocks * 2, pd.layer + 2);
+        pd.dx = c.DHs(t);
+        pd.lddx = d.ld_nb;
+        pd.accumulate = 1;
+        pd.has_cellb = 1;
+        pd.cellb = cell_bwd_args(c, 0, t - 1, s.skip_f32);
+        s.belief_done = true;
+    }
+    MARL_TRY(launch_panel_bwd(pd, c.st));
+    return gate_image_fallback(c, pd, t - 1);
+}
+
+// unchained panels: decoder(t) -> DMBAR, then (t > 0) the exchange and encoder(t-1) -> dh_t in a second launch
+static int bwd_step_panels(BwdState& s, int t, float* ddbar, float* ddbar2) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    PanelBwdProb pd{};
+    fill_dec_bwd_prob(s, t, ddbar, ddbar2, pd);
+    MARL_TRY(launch_panel_bwd(pd, c.st));
+    MARL_TRY(gate_image_fallback(c, pd, t - 1));
+    if (t == 0) return MARL_OK;
+    PanelBwdProb pe{};
+    pe.da = c.at(c.e.DMBAR);  // message mean applied while staging
+    pe.ldda = d.ld_nm;
+    pe.agg_na = d.na;
+    pe.agg_nb = d.nb;
+    if (g_comm) {  // M^T in place (a thread owns one (batch, column) over all agents), then plain rows
+        MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, 1));
+        pe.agg_na = pe.agg_nb = 0;
+    }
+    pe.m = (int)d.R;
+    pe.nlayers = 2;
+    fill_enc_bwd_layers(c, t - 1, (size_t)s.pln_blocks * 2, pe.layer);
+    pe.dx = c.DHs(t);
+    pe.lddx = d.ld_nb;
+    pe.accumulate = 1;
+    return launch_panel_bwd(pe, c.st);
+}
+
+// rows: GEMM + ln_bwd per layer; the LayerNorm reductions accumulate into the gradients step by step
+static int bwd_step_rows(const BwdState& s, int t, float* ddbar) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    const int R = (int)d.R;
+    const int first = (t == d.ns - 1);
+    float* dad1 = c.at(c.e.DAD1) + (size_t)t * d.R * d.ld_nm2;
+    MARL_TRY(ln_bwd(c, ddbar, d.ld_dbl, c.at(c.e.ZD2, t), d.ld_nmo, c.at(c.e.STD2, t),
+                    MARL_P_DEC_LN1W, MARL_P_DEC_LN1B, d.R, d.n_mo, s.grads, !first));
+    MARL_TRY(gemm1(c, gemm_prob(ddbar, d.ld_dbl, c.wt(MARL_P_DEC_W1), p4(d.n_mo), d.n_mo, dad1,
+                                d.ld_nm2, R, d.nm2)));
+    MARL_TRY(ln_bwd(c, dad1, d.ld_nm2, c.at(c.e.ZD1, t), d.ld_nm2, c.at(c.e.STD1, t),
+                    MARL_P_DEC_LN0W, MARL_P_DEC_LN0B, d.R, d.nm2, s.grads, !first));
+    // dL/d(mean message): of the step's input message (step API), or on its way into the encoder of step t-1
+    if (t > 0 || (s.sb && s.sb->d_msg))
+        MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wt(MARL_P_DEC_W0), p4(d.nm2), d.nm2,
+                                    c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
+    if (t == 0) return MARL_OK;
+    float* dze2 = c.at(c.e.DZE2) + (size_t)(t - 1) * d.R * d.ld_nm;
+    if (g_comm)  // the transpose of the mixing matrix
+        MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), dze2, d.n_m, 1));
+    else  // the message mean is self-adjoint
+        MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, c.st));
+    return enc_bwd_rows(s, t - 1, !first, c.DHs(t));
+}
+
+static int bwd_loop(BwdState& s) {
+    Ctx& c = s.c;
+    const Dims& d = c.d;
+    const StepBwd* sb = s.sb;
+    float* const* grads = s.grads;
+    hipStream_t st = c.st;
+    const int ns = d.ns;
+    const size_t s_nmo = (size_t)d.R * d.ld_dbl;
+    s.panels = use_panels(d) && d.n_mo <= 384 && d.nm2 <= 384 && d.n_m <= 384;
     // the per-step LayerNorm reductions of the unfused path accumulate into the gradients step
     // by step: nothing of a parameter may still be queued then, so that path does not defer
-    if (!panels) {
-        MARL_TRY(launch_tn_queue(tq, c.rq, st));  // (what the heads queued so far)
+    if (!s.panels) {
+        MARL_TRY(launch_tn_queue(s.tq, c.rq, st));  // (what the heads queued so far)
         c.rq = nullptr;
         c.tq = nullptr;
     }
     // In an episode the last step's message has no consumer.  A standalone step's new message may have one
     // (the caller's next step, a loss): its encoder runs backward from dL/d(new message) here, ahead of the
     // belief cell of that step, to which it adds dL/dh.
-    const bool enc_last = sb && sb->g_msg;
-    if (enc_last) {
-        const int t = ns - 1;
-        float* dze2 = c.at(c.e.DZE2) + (size_t)t * s_nm;
-        float* dae1 = c.at(c.e.DAE1) + (size_t)t * s_nm2;
-        MARL_TRY(launch_copy2d(sb->g_msg, d.n_m, dze2, d.ld_nm, d.R, d.n_m, st));
-        MARL_TRY(ln_bwd(c, dze2, d.ld_nm, c.at(c.e.ZE2, t), d.ld_nm, c.at(c.e.STE2, t), MARL_P_ENC_LN1W,
-                        MARL_P_ENC_LN1B, d.R, d.n_m, grads, 0));
-        MARL_TRY(gemm1(c, gemm_prob(dze2, d.ld_nm, c.wt(MARL_P_ENC_W1), p4(d.n_m), d.n_m, dae1, d.ld_nm2, R,
-                                    d.nm2)));
-        MARL_TRY(ln_bwd(c, dae1, d.ld_nm2, c.at(c.e.ZE1, t), d.ld_nm2, c.at(c.e.STE1, t), MARL_P_ENC_LN0W,
-                        MARL_P_ENC_LN0B, d.R, d.nm2, grads, 0));
-        MARL_TRY(gemm1(c, gemm_prob(dae1, d.ld_nm2, c.wt(MARL_P_ENC_W0), p4(d.nm2), d.nm2, c.DHs(ns), d.ld_nb, R,
-                                    d.n_b, nullptr, 1)));
+    if (s.enc_last) {
+        MARL_TRY(launch_copy2d(sb->g_msg, d.n_m, c.at(c.e.DZE2) + (size_t)(ns - 1) * d.R * d.ld_nm, d.ld_nm, d.R,
+                               d.n_m, st));
+        MARL_TRY(enc_bwd_rows(s, ns - 1, 0, c.DHs(ns)));
     }
-    // The action cell's backward of step t-1 only needs dh^_t, which is complete after step t's
-    // W_hh product; it rides along (extra workgroups) with step t's decoder-panel launch, so
-    // that from the second iteration on only the belief cell is left for the separate launch.
-    const bool ride = panels && !use_side_stream();
-    const bool dl_in_loop = ride;  // dU[:, nf:] (message + embedding columns) comes out of the loop
-    bool action_done = false;  // the action cell of this step was handled by the ride-along
-    bool belief_done = false;  // the belief cell: by the epilogue of the chained panel launch
-    const bool chain = ride && use_chain(d);
-    const bool g3 = c.e.g3;  // the gate gradients also leave as k16 images; the products below read those
+    // with panels dU[:, nf:] (message + embedding columns) comes out of the loop
+    s.chain = s.panels && use_chain(d);
     // every consumer on images (in-loop batch, dU, the four weight gradients): no fp32 copy of them at all
-    const int skip_f32 = g3 && dl_in_loop && g3_tn_enabled(d);
-    const int pln_blocks = chain ? panel_chain_blocks(d.na, d.nb) : panel_bwd_blocks(R);
+    s.skip_f32 = c.e.g3 && s.panels && g3_tn_enabled(d);
+    s.pln_blocks = s.chain ? panel_chain_blocks(d.na, d.nb) : panel_bwd_blocks((int)d.R);
     for (int t = ns - 1; t >= 0; --t) {
-        const int first = (t == ns - 1);
         {   // cells of step t not yet handled inside the previous iteration's panel launch
             LstmBwdBatch lb{};
             int nc = 0;
-            if (!belief_done)
-                lb.a[nc++] = LstmBwdArgs{c.DHs(t + 1), c.at(c.e.DC), c.at(c.e.GB, t), c.Cs(t), c.Cs(t + 1), d.ld_nb,
-                                         d.ld_nb, d.ld_gb, d.ld_nb, d.n_b, g3 ? c.img(c.e.GB3) : nullptr,
-                                         (int)((int64_t)t * d.R), img_steps(4 * d.n_b), skip_f32};
-            if (!action_done)
-                lb.a[nc++] = LstmBwdArgs{c.DHCs(t + 1), c.at(c.e.DCC), c.at(c.e.GA, t), c.CCs(t), c.CCs(t + 1), d.ld_na,
-                                         d.ld_na, d.ld_ga, d.ld_na, d.n_a, g3 ? c.img(c.e.GA3) : nullptr,
-                                         (int)((int64_t)t * d.R), img_steps(4 * d.n_a), skip_f32};
+            if (!s.belief_done) lb.a[nc++] = cell_bwd_args(c, 0, t, s.skip_f32);
+            if (!s.action_done) lb.a[nc++] = cell_bwd_args(c, 1, t, s.skip_f32);
             lb.rows = d.R;
             if (nc) MARL_TRY(launch_lstm_cell_bwd_batch(lb, nc, st));
         }
-        action_done = belief_done = false;
-        // The W_hh recurrent GEMM (main stream) and the decoder / encoder backward chain (side
-        // stream) only meet at DH[t]: the chain's last kernel waits for the GEMM.
-        const bool side = panels && use_side_stream();
-        Ctx cs = c;
-        if (side) {
-            MARL_TRY(g_side.init());
-            cs.st = g_side.s;
-            MARL_TRY(g_side.order(c.st, cs.st));
-        }
-        hipStream_t st = cs.st;  // stream of the message chain below
-        // recurrent paths dh_{t-1} += dgates * W_hh, and d(decoded message) = columns
-        // [nf, nf + n_mo) of dU - three independent products of the same gate gradients
+        s.action_done = s.belief_done = false;
         float* ddbar = c.at(c.e.DDBAR) + (size_t)t * s_nmo;
-        {
-            GemmBatch gb{};
-            gb.p[0] = gemm_prob(c.at(c.e.GB, t), d.ld_gb, c.wt(MARL_P_LB_WHH), d.ld_gb, 4 * d.n_b,
-                                c.DHs(t), d.ld_nb, R, d.n_b, nullptr, 1);
-            gb.p[1] = gemm_prob(c.at(c.e.GA, t), d.ld_ga, c.wt(MARL_P_LA_WHH), d.ld_ga, 4 * d.n_a,
-                                c.DHCs(t), d.ld_na, R, d.n_a, nullptr, 1);
-            GemmProb p = gemm_prob(c.at(c.e.GB, t), d.ld_gb,
-                                   c.wt(MARL_P_LB_WIH) + (size_t)d.nf * d.ld_gb, d.ld_gb, 4 * d.n_b,
-                                   ddbar, d.ld_dbl, R, d.n_mo);
-            gemm_add_seg(p, c.at(c.e.GA, t), d.ld_ga, c.wt(MARL_P_LA_WIH) + (size_t)d.nf * d.ld_ga,
-                         d.ld_ga, 4 * d.n_a);
-            if (side) {  // W_hh products on the main stream, the message chain on the side stream
-                gb.count = 2;
-                MARL_TRY(launch_gemm_nt(gb, c.st));
-                MARL_TRY(gemm1(cs, p));
-            } else if (dl_in_loop) {
-                // four products of EQUAL depth (a two-segment one would run twice as long as the
-                // others and finish the launch alone): each cell's share of dU[:, nf:] - the
-                // decoded-message AND the position-embedding columns, which sit next to each
-                // other and fit the same two 64-wide tiles - goes to its own buffer; the decoder
-                // panel sums the message halves while staging, the embedding halves are summed
-                // once after the loop.  The big dU product then only covers the CNN features.
-                gb.p[2] = gemm_prob(c.at(c.e.GB, t), d.ld_gb,
-                                    c.wt(MARL_P_LB_WIH) + (size_t)d.nf * d.ld_gb, d.ld_gb, 4 * d.n_b,
-                                    ddbar, d.ld_dbl, R, d.n_mo + d.n_d);
-                gb.p[3] = gemm_prob(c.at(c.e.GA, t), d.ld_ga,
-                                    c.wt(MARL_P_LA_WIH) + (size_t)d.nf * d.ld_ga, d.ld_ga, 4 * d.n_a,
-                                    c.at(c.e.DDBAR2) + (size_t)t * s_nmo, d.ld_dbl, R, d.n_mo + d.n_d);
-                gb.count = 4;
-                if (g3) {
-                    const int r0 = (int)((int64_t)t * d.R);
-                    G3Batch g{};
-                    g.p[0] = g3_prob(c.img(c.e.GB3), r0, c.wt3k(MARL_P_LB_WHH), 0, 4 * d.n_b, c.DHs(t), d.ld_nb, R,
-                                     d.n_b, nullptr, 1);
-                    g.p[1] = g3_prob(c.img(c.e.GA3), r0, c.wt3k(MARL_P_LA_WHH), 0, 4 * d.n_a, c.DHCs(t), d.ld_na, R,
-                                     d.n_a, nullptr, 1);
-                    g.p[2] = g3_prob(c.img(c.e.GB3), r0, c.wt3k(MARL_P_LB_WIH), d.nf, 4 * d.n_b, ddbar, d.ld_dbl, R,
-                                     d.n_mo + d.n_d);
-                    g.p[3] = g3_prob(c.img(c.e.GA3), r0, c.wt3k(MARL_P_LA_WIH), d.nf, 4 * d.n_a,
-                                     c.at(c.e.DDBAR2) + (size_t)t * s_nmo, d.ld_dbl, R, d.n_mo + d.n_d);
-                    g.count = 4;
-                    MARL_TRY(launch_gemm_nt3(g, c.st));
-                } else {
-                    MARL_TRY(launch_gemm_nt(gb, c.st));
-                }
-            } else {
-                gb.p[2] = p;
-                gb.count = 3;
-                MARL_TRY(launch_gemm_nt(gb, c.st));
-            }
-        }
-        float* dad1 = c.at(c.e.DAD1) + (size_t)t * s_nm2;
-        if (panels) {
-            const size_t pblk = (size_t)pln_blocks * 2;
-            PanelBwdProb pd{};
-            pd.da = ddbar;
-            pd.ldda = d.ld_dbl;
-            if (dl_in_loop) {
-                pd.da2 = c.at(c.e.DDBAR2) + (size_t)t * s_nmo;
-                pd.ldda2 = d.ld_dbl;
-            }
-            pd.m = R;
-            pd.nlayers = 2;
-            pd.layer[0] = PanelBwdLayer{c.at(c.e.ZD2, t), d.ld_nmo, c.at(c.e.STD2, t),
-                                        c.wp(MARL_P_DEC_LN1W), c.wp(MARL_P_DEC_LN1B), d.n_mo, ddbar,
-                                        d.ld_dbl, c.at(c.e.PLN[0]) + (size_t)t * pblk * d.n_mo,
-                                        c.wtf(MARL_P_DEC_W1), c.w.gtf[MARL_P_DEC_W1], d.nm2};
-            pd.layer[1] = PanelBwdLayer{c.at(c.e.ZD1, t), d.ld_nm2, c.at(c.e.STD1, t),
-                                        c.wp(MARL_P_DEC_LN0W), c.wp(MARL_P_DEC_LN0B), d.nm2, dad1,
-                                        d.ld_nm2, c.at(c.e.PLN[1]) + (size_t)t * pblk * d.nm2,
-                                        c.wtf(MARL_P_DEC_W0), c.w.gtf[MARL_P_DEC_W0], d.n_m};
-            pd.dx = c.at(c.e.DMBAR);
-            pd.lddx = d.ld_nm;
-            pd.accumulate = 0;
-            if (ride && t > 0) {  // action cell of step t-1: gates GA[t-1], dh^ = DHC[t]
-                pd.has_cell = 1;
-                pd.cell = LstmBwdArgs{c.DHCs(t), c.at(c.e.DCC), c.at(c.e.GA, t - 1), c.CCs(t - 1),
-                                      c.CCs(t), d.ld_na, d.ld_na, d.ld_ga, d.ld_na, d.n_a,
-                                      g3 ? c.img(c.e.GA3) : nullptr, (int)((int64_t)(t - 1) * d.R), img_steps(4 * d.n_a),
-                                      skip_f32};
-                pd.cell_rows = d.R;
-                action_done = true;
-            }
-            if (chain) {
-                // decoder(t) -> mean -> encoder(t-1) -> dh_t -> belief cell(t-1), one launch
-                pd.by_batch = panel_chain_by_batch(d.na);
-                pd.g_na = d.na;
-                pd.g_nb = d.nb;
-                if (t > 0) {
-                    pd.nlayers = 4;
-                    pd.agg_at = 2;
-                    pd.mix = g_comm;  // (null: the self-adjoint mean; else the kernel applies M^T)
-                    if (g_comm) pd.gate = comm_gate(c, t);
-                    pd.layer[2] = PanelBwdLayer{c.at(c.e.ZE2, t - 1), d.ld_nm, c.at(c.e.STE2, t - 1),
-                                                c.wp(MARL_P_ENC_LN1W), c.wp(MARL_P_ENC_LN1B), d.n_m,
-                                                c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm, d.ld_nm,
-                                                c.at(c.e.PLN[2]) + (size_t)(t - 1) * pblk * d.n_m,
-                                                c.wtf(MARL_P_ENC_W1), c.w.gtf[MARL_P_ENC_W1], d.nm2};
-                    pd.layer[3] = PanelBwdLayer{c.at(c.e.ZE1, t - 1), d.ld_nm2, c.at(c.e.STE1, t - 1),
-                                                c.wp(MARL_P_ENC_LN0W), c.wp(MARL_P_ENC_LN0B), d.nm2,
-                                                c.at(c.e.DAE1) + (size_t)(t - 1) * s_nm2, d.ld_nm2,
-                                                c.at(c.e.PLN[3]) + (size_t)(t - 1) * pblk * d.nm2,
-                                                c.wtf(MARL_P_ENC_W0), c.w.gtf[MARL_P_ENC_W0], d.n_b};
-                    pd.dx = c.DHs(t);
-                    pd.lddx = d.ld_nb;
-                    pd.accumulate = 1;
-                    pd.has_cellb = 1;
-                    pd.cellb = LstmBwdArgs{c.DHs(t), c.at(c.e.DC), c.at(c.e.GB, t - 1), c.Cs(t - 1), c.Cs(t),
-                                           d.ld_nb, d.ld_nb, d.ld_gb, d.ld_nb, d.n_b, g3 ? c.img(c.e.GB3) : nullptr,
-                                           (int)((int64_t)(t - 1) * d.R), img_steps(4 * d.n_b), skip_f32};
-                    belief_done = true;
-                }
-                MARL_TRY(launch_panel_bwd(pd, st));
-                MARL_TRY(gate_image_fallback(c, pd, t - 1));
-                continue;
-            }
-            MARL_TRY(launch_panel_bwd(pd, st));
-            MARL_TRY(gate_image_fallback(c, pd, t - 1));
-            if (t > 0) {
-                float* dze2 = c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm;
-                float* dae1 = c.at(c.e.DAE1) + (size_t)(t - 1) * s_nm2;
-                PanelBwdProb pe{};
-                pe.da = c.at(c.e.DMBAR);  // message mean applied while staging
-                pe.ldda = d.ld_nm;
-                pe.agg_na = d.na;
-                pe.agg_nb = d.nb;
-                if (g_comm) {  // M^T in place (a thread owns one (batch, column) over all agents), then plain rows
-                    MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, 1));
-                    pe.agg_na = pe.agg_nb = 0;
-                }
-                pe.m = R;
-                pe.nlayers = 2;
-                pe.layer[0] = PanelBwdLayer{c.at(c.e.ZE2, t - 1), d.ld_nm, c.at(c.e.STE2, t - 1),
-                                            c.wp(MARL_P_ENC_LN1W), c.wp(MARL_P_ENC_LN1B), d.n_m,
-                                            dze2, d.ld_nm,
-                                            c.at(c.e.PLN[2]) + (size_t)(t - 1) * pblk * d.n_m,
-                                            c.wtf(MARL_P_ENC_W1), c.w.gtf[MARL_P_ENC_W1], d.nm2};
-                pe.layer[1] = PanelBwdLayer{c.at(c.e.ZE1, t - 1), d.ld_nm2, c.at(c.e.STE1, t - 1),
-                                            c.wp(MARL_P_ENC_LN0W), c.wp(MARL_P_ENC_LN0B), d.nm2,
-                                            dae1, d.ld_nm2,
-                                            c.at(c.e.PLN[3]) + (size_t)(t - 1) * pblk * d.nm2,
-                                            c.wtf(MARL_P_ENC_W0), c.w.gtf[MARL_P_ENC_W0], d.n_b};
-                pe.dx = c.DHs(t);
-                pe.lddx = d.ld_nb;
-                pe.accumulate = 1;
-                if (side) MARL_TRY(g_side.order(c.st, cs.st));  // after the W_hh GEMM's DH[t] update
-                MARL_TRY(launch_panel_bwd(pe, st));
-            }
-            if (side) MARL_TRY(g_side.order(cs.st, c.st));  // join before step t-1
-            continue;
-        }
-        MARL_TRY(ln_bwd(c, ddbar, d.ld_dbl, c.at(c.e.ZD2, t), d.ld_nmo, c.at(c.e.STD2, t),
-                        MARL_P_DEC_LN1W, MARL_P_DEC_LN1B, d.R, d.n_mo, grads, !first));
-        MARL_TRY(gemm1(c, gemm_prob(ddbar, d.ld_dbl, c.wt(MARL_P_DEC_W1), p4(d.n_mo), d.n_mo, dad1,
-                                    d.ld_nm2, R, d.nm2)));
-        MARL_TRY(ln_bwd(c, dad1, d.ld_nm2, c.at(c.e.ZD1, t), d.ld_nm2, c.at(c.e.STD1, t),
-                        MARL_P_DEC_LN0W, MARL_P_DEC_LN0B, d.R, d.nm2, grads, !first));
-        if (t == 0 && sb && sb->d_msg)  // dL/d(mean message) of the step's input message
-            MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wt(MARL_P_DEC_W0), p4(d.nm2), d.nm2,
-                                        c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
-        if (t > 0) {
-            // through the message mean (self-adjoint) into the encoder of step t-1
-            MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wt(MARL_P_DEC_W0), p4(d.nm2), d.nm2,
-                                        c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
-            float* dze2 = c.at(c.e.DZE2) + (size_t)(t - 1) * s_nm;
-            if (g_comm)  // the transpose of the mixing matrix
-                MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), dze2, d.n_m, 1));
-            else
-                MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, st));
-            const int efirst = (t == ns - 1);
-            MARL_TRY(ln_bwd(c, dze2, d.ld_nm, c.at(c.e.ZE2, t - 1), d.ld_nm, c.at(c.e.STE2, t - 1),
-                            MARL_P_ENC_LN1W, MARL_P_ENC_LN1B, d.R, d.n_m, grads, !efirst));
-            float* dae1 = c.at(c.e.DAE1) + (size_t)(t - 1) * s_nm2;
-            MARL_TRY(gemm1(c, gemm_prob(dze2, d.ld_nm, c.wt(MARL_P_ENC_W1), p4(d.n_m), d.n_m, dae1,
-                                        d.ld_nm2, R, d.nm2)));
-            MARL_TRY(ln_bwd(c, dae1, d.ld_nm2, c.at(c.e.ZE1, t - 1), d.ld_nm2,
-                            c.at(c.e.STE1, t - 1), MARL_P_ENC_LN0W, MARL_P_ENC_LN0B, d.R, d.nm2,
-                            grads, !efirst));
-            MARL_TRY(gemm1(c, gemm_prob(dae1, d.ld_nm2, c.wt(MARL_P_ENC_W0), p4(d.nm2), d.nm2,
-                                        c.DHs(t), d.ld_nb, R, d.n_b, nullptr, 1)));
-        }
+        float* ddbar2 = c.at(c.e.DDBAR2) + (size_t)t * s_nmo;
+        MARL_TRY(bwd_recurrent(s, t, ddbar, ddbar2));
+        if (s.chain)
+            MARL_TRY(bwd_step_chain(s, t, ddbar, ddbar2));
+        else if (s.panels)
+            MARL_TRY(bwd_step_panels(s, t, ddbar, ddbar2));
+        else
+            MARL_TRY(bwd_step_rows(s, t, ddbar));
     }
     if (sb) {  // gradients of the step's inputs: what the loop left for step -1
         // (DMBAR = dL/d(mean message) of step 0; the mean is self-adjoint and may run in place: every thread
@@ -1892,8 +1861,8 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
         if (sb->d_hc) MARL_TRY(launch_copy2d(c.DHCs(0), d.ld_na, sb->d_hc, d.n_a, d.R, d.n_a, st));
         if (sb->d_cc) MARL_TRY(launch_copy2d(c.at(c.e.DCC), d.ld_na, sb->d_cc, d.n_a, d.R, d.n_a, st));
     }
-    if (panels) {  // LayerNorm affine gradients of the in-loop layers: one reduction each
-        const int64_t nblk = pln_blocks;
+    if (s.panels) {  // LayerNorm affine gradients of the in-loop layers: one reduction each
+        const int64_t nblk = s.pln_blocks;
         MARL_TRY(launch_reduce_affine(c.at(c.e.PLN[0]), nblk * ns, d.n_mo, grads[MARL_P_DEC_LN1W],
                                       grads[MARL_P_DEC_LN1B], 0, st, c.rq));
         MARL_TRY(launch_reduce_affine(c.at(c.e.PLN[1]), nblk * ns, d.nm2, grads[MARL_P_DEC_LN0W],
@@ -1905,194 +1874,201 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
                                           grads[MARL_P_ENC_LN0W], grads[MARL_P_ENC_LN0B], 0, st, c.rq));
         }
     }
+    return MARL_OK;
+}
 
-    // ---- weight gradients of the recurrent chain: one contraction over all steps -------
+// ---- weight gradients of the recurrent chain: one contraction over all steps -------
+static int bwd_chain_wgrads(const BwdState& s) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    float* const* grads = s.grads;
+    const int64_t NR = d.NR;
+    const int ns = d.ns;
     MARL_TRY(tn(c, c.at(c.e.DDBAR), d.ld_dbl, c.at(c.e.AD1, 0), d.ld_nm2, MARL_P_DEC_W1, d.n_mo, d.nm2, NR, grads[MARL_P_DEC_B1]));
     MARL_TRY(tn(c, c.at(c.e.DAD1), d.ld_nm2, c.at(c.e.MBAR, 0), d.ld_nm, MARL_P_DEC_W0, d.nm2, d.n_m, NR, grads[MARL_P_DEC_B0]));
-    if (ns > 1 || enc_last) {
+    if (ns > 1 || s.enc_last) {
         // the last step's message is never read in an episode; a standalone step's may be
-        const int64_t er = (int64_t)(enc_last ? ns : ns - 1) * d.R;
+        const int64_t er = (int64_t)(s.enc_last ? ns : ns - 1) * d.R;
         MARL_TRY(tn(c, c.at(c.e.DZE2), d.ld_nm, c.at(c.e.AE1, 0), d.ld_nm2, MARL_P_ENC_W1, d.n_m, d.nm2, er, grads[MARL_P_ENC_B1]));
         MARL_TRY(tn(c, c.at(c.e.DAE1), d.ld_nm2, c.Hs(1), d.ld_nb, MARL_P_ENC_W0, d.nm2, d.n_b, er, grads[MARL_P_ENC_B0]));
     } else {
         const int enc[] = {MARL_P_ENC_B0, MARL_P_ENC_LN0W, MARL_P_ENC_LN0B, MARL_P_ENC_B1,
                            MARL_P_ENC_LN1W, MARL_P_ENC_LN1B};
-        for (int i : enc) MARL_TRY(launch_fill(grads[i], param_meta(d, i).n, 0.f, st));
-        MARL_TRY(launch_fill(c.gp(MARL_P_ENC_W0), (int64_t)d.nm2 * c.w.ldp[MARL_P_ENC_W0], 0.f, st));
-        MARL_TRY(launch_fill(c.gp(MARL_P_ENC_W1), (int64_t)d.n_m * c.w.ldp[MARL_P_ENC_W1], 0.f, st));
+        for (int i : enc) MARL_TRY(launch_fill(grads[i], param_meta(d, i).n, 0.f, c.st));
+        MARL_TRY(launch_fill(c.gp(MARL_P_ENC_W0), (int64_t)d.nm2 * c.w.ldp[MARL_P_ENC_W0], 0.f, c.st));
+        MARL_TRY(launch_fill(c.gp(MARL_P_ENC_W1), (int64_t)d.n_m * c.w.ldp[MARL_P_ENC_W1], 0.f, c.st));
     }
-    if (g3 && g3_tn_enabled(d)) {
-        // contraction over the rows of the images written by the cell-backward kernels (gate gradients),
-        // the forward kernels (U) and the LSTM epilogues (h, h^); bias gradients = column sums of A
-        if (g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, NR)) {
-            MARL_TRY(tn3_cell(c, c.img(c.e.GB3), 4 * d.n_b, c.img(c.e.U3), d.nin, MARL_P_LB_WIH, c.img(c.e.H3), d.n_b,
-                              MARL_P_LB_WHH, NR, grads[MARL_P_LB_BIH]));
+    const bool tn_img = c.e.g3 && g3_tn_enabled(d);
+    for (int which = 0; which < 2; ++which) {  // belief cell, action cell: W_ih, then W_hh with the bias
+        const int n = which ? d.n_a : d.n_b;
+        const int p_ih = which ? MARL_P_LA_WIH : MARL_P_LB_WIH, p_hh = which ? MARL_P_LA_WHH : MARL_P_LB_WHH;
+        float* bias = grads[which ? MARL_P_LA_BIH : MARL_P_LB_BIH];
+        if (tn_img) {
+            // contraction over the rows of the images written by the cell-backward kernels (gate gradients),
+            // the forward kernels (U) and the LSTM epilogues (h, h^); bias gradients = column sums of A
+            const char* g3 = c.img(which ? c.e.GA3 : c.e.GB3);
+            const char* h3 = c.img(which ? c.e.HC3 : c.e.H3);
+            if (g3_tn_cell_ok(4 * n, d.nin, n, NR)) {
+                MARL_TRY(tn3_cell(c, g3, 4 * n, c.img(c.e.U3), d.nin, p_ih, h3, n, p_hh, NR, bias));
+            } else {
+                MARL_TRY(tn3(c, g3, 4 * n, c.img(c.e.U3), d.nin, p_ih, NR, nullptr));
+                MARL_TRY(tn3(c, g3, 4 * n, h3, n, p_hh, NR, bias));
+            }
         } else {
-            MARL_TRY(tn3(c, c.img(c.e.GB3), 4 * d.n_b, c.img(c.e.U3), d.nin, MARL_P_LB_WIH, NR, nullptr));
-            MARL_TRY(tn3(c, c.img(c.e.GB3), 4 * d.n_b, c.img(c.e.H3), d.n_b, MARL_P_LB_WHH, NR, grads[MARL_P_LB_BIH]));
+            const float* g = c.at(which ? c.e.GA : c.e.GB, 0);
+            const int ldg = which ? d.ld_ga : d.ld_gb;
+            MARL_TRY(tn(c, g, ldg, c.at(c.e.U, 0), d.ld_nin, p_ih, 4 * n, d.nin, NR));
+            MARL_TRY(tn(c, g, ldg, which ? c.HCs(0) : c.Hs(0), which ? d.ld_na : d.ld_nb, p_hh, 4 * n, n, NR, bias));
         }
-        if (g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, NR)) {
-            MARL_TRY(tn3_cell(c, c.img(c.e.GA3), 4 * d.n_a, c.img(c.e.U3), d.nin, MARL_P_LA_WIH, c.img(c.e.HC3), d.n_a,
-                              MARL_P_LA_WHH, NR, grads[MARL_P_LA_BIH]));
-        } else {
-            MARL_TRY(tn3(c, c.img(c.e.GA3), 4 * d.n_a, c.img(c.e.U3), d.nin, MARL_P_LA_WIH, NR, nullptr));
-            MARL_TRY(tn3(c, c.img(c.e.GA3), 4 * d.n_a, c.img(c.e.HC3), d.n_a, MARL_P_LA_WHH, NR, grads[MARL_P_LA_BIH]));
-        }
-    } else {
-    MARL_TRY(tn(c, c.at(c.e.GB, 0), d.ld_gb, c.at(c.e.U, 0), d.ld_nin, MARL_P_LB_WIH, 4 * d.n_b, d.nin, NR));
-    MARL_TRY(tn(c, c.at(c.e.GB, 0), d.ld_gb, c.Hs(0), d.ld_nb, MARL_P_LB_WHH, 4 * d.n_b, d.n_b, NR, grads[MARL_P_LB_BIH]));
-    MARL_TRY(tn(c, c.at(c.e.GA, 0), d.ld_ga, c.at(c.e.U, 0), d.ld_nin, MARL_P_LA_WIH, 4 * d.n_a, d.nin, NR));
-    MARL_TRY(tn(c, c.at(c.e.GA, 0), d.ld_ga, c.HCs(0), d.ld_na, MARL_P_LA_WHH, 4 * d.n_a, d.n_a, NR, grads[MARL_P_LA_BIH]));
     }
+    return MARL_OK;
+}
 
-    // ---- dU for all steps, then position embedding and CNN backward -------------------
-    {
-        // with the [nf, nin) columns already produced step by step, only the CNN features remain
-        if (g3 && dl_in_loop) {
-            G3Batch g{};
-            g.p[0] = g3_prob(c.img(c.e.GB3), 0, c.wt3k(MARL_P_LB_WIH), 0, 4 * d.n_b, c.at(c.e.DU), d.ld_nin, (int)NR,
-                             d.nf);
-            g3_add_seg(g.p[0], c.img(c.e.GA3), 0, c.wt3k(MARL_P_LA_WIH), 0, 4 * d.n_a);
-            g.count = 1;
-            MARL_TRY(launch_gemm_nt3(g, st));
+// ---- dU for all steps, then position embedding and CNN backward -------------------
+
+// dW_l (and db_l) of conv layer l from dZ_l and the layer's input, recomputed from what forward kept (Z_{l-1} +
+// statistics, or the image patch): no im2col rows in HBM
+static int bwd_conv_wgrad(const BwdState& s, int l, const float* dz, const void* img, int img_u8) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    const int co = d.ch[l + 1];
+    CnnWgradArgs w = cnn_wgrad_shape(d, l);
+    w.dz = dz;
+    w.img = img;
+    w.img_u8 = img_u8;
+    w.pos = c.POSs(0);
+    if (l > 0) {
+        w.zin = c.at(c.e.Z[l - 1], 0);
+        w.gst = c.at(c.e.GST[l - 1], 0);
+        w.gamma = c.wp(4 * (l - 1) + 2);
+        w.beta = c.wp(4 * (l - 1) + 3);
+    } else if (s.sb) {
+        // standalone step: the caller's patches obs [R, C, f, f] are R one-patch images of
+        // f x f at position 0 (POSs(0) zeroed by the heads' part) - the gather reads exactly obs[r]
+        w.img = s.sb->obs;
+        w.img_u8 = 0;
+        w.nb = (int)d.R;
+        w.H = w.W = d.f;
+    } else if (!img) {
+        set_error("episode_backward: the image batch of the forward call is needed");
+        return MARL_EINVAL;
+    }
+    // per-workgroup slabs; the launcher places part_b behind the weight slabs
+    w.part_w = slab_scratch(c, (size_t)cnn_wgrad_blocks(w) * ((size_t)co * d.K[l] + co));
+    MARL_TRY(launch_cnn_wgrad(w, c.st));
+    return slab_reduce(c, w.part_w, w.part_b, w.blocks, co, d.K[l], 4 * l, s.grads[4 * l + 1]);
+}
+
+// the extractor backward from dU[:, :nf], last layer first; leaves dZ_0 in the workspace unless layer 0's weight
+// gradient rode along with the launch that produced it
+static int bwd_cnn_layers(const BwdState& s, const void* img, int img_u8, const float* d_img) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    float* const* grads = s.grads;
+    hipStream_t st = c.st;
+    const int64_t NR = d.NR;
+    const float* da = c.at(c.e.DU);
+    int64_t ldda = d.ld_nin;
+    int chw = 1;
+    bool have_dz = false;  // DZ[l] already produced by the fused layer backward of layer l+1
+    bool w0_done = false;  // ... which also formed layer 0's weight gradient (dZ_0 never left LDS)
+    for (int l = d.L - 1; l >= 0; --l) {
+        const int co = d.ch[l + 1];
+        const int64_t rows = NR * d.P[l];
+        float* dz = c.at(c.e.DZ[l]);
+        if (!have_dz) {
+            RedQueue* q;
+            float* part = part_scratch(c, gn_bwd_blocks(NR, co), co, 0, q);
+            MARL_TRY(launch_gn_silu_bwd(da, ldda, chw, c.at(c.e.Z[l], 0), c.at(c.e.GST[l], 0),
+                                        c.wp(4 * l + 2), c.wp(4 * l + 3), dz, part, NR, d.P[l], co,
+                                        d.grp[l], st));
+            MARL_TRY(launch_reduce_affine(part, gn_bwd_blocks(NR, co), co, grads[4 * l + 2],
+                                          grads[4 * l + 3], 0, st, q));
+        }
+        have_dz = false;
+        if (l == 0 && w0_done) {
+            // (layer 0's weight and bias gradient came out of the launch that produced dZ_0)
+        } else if (c.e.wgrad_ok[l]) {
+            MARL_TRY(bwd_conv_wgrad(s, l, dz, img, img_u8));
         } else {
+            MARL_TRY(tn(c, dz, co, c.at(c.e.COLS[l], 0), d.ldk[l], 4 * l, co, d.K[l], rows, grads[4 * l + 1]));
+        }
+        if (l == 0) break;
+        // dZ_l -> dZ_{l-1} in one launch (transposed conv + GroupNorm/SiLU backward)
+        CnnDgradArgs g = cnn_dgrad_shape(d, l);
+        g.dz = dz;
+        g.wt = c.wt(4 * l);
+        g.ldwt = p4(co);
+        g.zin = c.at(c.e.Z[l - 1], 0);
+        g.gst = c.at(c.e.GST[l - 1], 0);
+        g.gamma = c.wp(4 * (l - 1) + 2);
+        g.beta = c.wp(4 * (l - 1) + 3);
+        g.dzin = c.at(c.e.DZ[l - 1]);
+        if (g.w0 && !img) g.w0 = 0;  // (the step API has no image batch: layer 0 takes the separate launch)
+        if (d_img) g.w0 = 0;         // (the image gradient reads dZ_0 from the workspace)
+        if (c.e.dgrad_ok[l] && (size_t)cnn_dgrad_blocks(g) * 2 * d.ch[l] <= c.e.part_floats) {
+            RedQueue* q;
+            const int nblk = cnn_dgrad_blocks(g);
+            g.part = part_scratch(c, nblk, d.ch[l], 0, q);
+            const int co0 = d.ch[l], k0 = d.K[0];
+            if (g.w0) {  // + layer 0's weight gradient: per-workgroup slabs (tiny: 448 floats each at RESISC)
+                g.w0_part = slab_scratch(c, (size_t)nblk * ((size_t)co0 * k0 + co0));
+                g.w0_bpart = g.w0_part + (size_t)nblk * co0 * k0;
+                g.img = img;
+                g.img_u8 = img_u8;
+                g.pos = c.POSs(0);
+                g.dzin = nullptr;  // dZ_0 stays in LDS
+            }
+            MARL_TRY(launch_cnn_dgrad(g, st));
+            MARL_TRY(launch_reduce_affine(g.part, nblk, d.ch[l], grads[4 * (l - 1) + 2], grads[4 * (l - 1) + 3], 0,
+                                          st, q));
+            if (g.w0) {
+                MARL_TRY(slab_reduce(c, g.w0_part, g.w0_bpart, nblk, co0, k0, 0, grads[1]));
+                w0_done = true;
+            }
+            have_dz = true;
+            continue;
+        }
+        MARL_TRY(gemm1(c, gemm_prob(dz, co, c.wt(4 * l), p4(co), co, c.at(c.e.DCOLS[l]),
+                                    d.ldk[l], (int)rows, d.K[l])));
+        MARL_TRY(launch_col2im(c.at(c.e.DCOLS[l]), d.ldk[l], c.at(c.e.DA[l - 1]), NR,
+                               d.hw[l], d.ch[l], st));
+        da = c.at(c.e.DA[l - 1]);
+        ldda = (int64_t)d.P[l - 1] * d.ch[l];
+        chw = 0;
+    }
+    return MARL_OK;
+}
+
+static int bwd_inputs(const BwdState& s, const void* img, int img_u8, float* d_img) {
+    const Ctx& c = s.c;
+    const Dims& d = c.d;
+    float* const* grads = s.grads;
+    hipStream_t st = c.st;
+    const int64_t NR = d.NR;
+    // with the [nf, nin) columns already produced step by step (panels), only the CNN features remain
+    if (c.e.g3 && s.panels) {
+        G3Batch g{};
+        g.p[0] = g3_prob(c.img(c.e.GB3), 0, c.wt3k(MARL_P_LB_WIH), 0, 4 * d.n_b, c.at(c.e.DU), d.ld_nin, (int)NR,
+                         d.nf);
+        g3_add_seg(g.p[0], c.img(c.e.GA3), 0, c.wt3k(MARL_P_LA_WIH), 0, 4 * d.n_a);
+        g.count = 1;
+        MARL_TRY(launch_gemm_nt3(g, st));
+    } else {
         GemmProb p = gemm_prob(c.at(c.e.GB, 0), d.ld_gb, c.wt(MARL_P_LB_WIH), d.ld_gb, 4 * d.n_b,
-                               c.at(c.e.DU), d.ld_nin, (int)NR, dl_in_loop ? d.nf : d.nin);
+                               c.at(c.e.DU), d.ld_nin, (int)NR, s.panels ? d.nf : d.nin);
         gemm_add_seg(p, c.at(c.e.GA, 0), d.ld_ga, c.wt(MARL_P_LA_WIH), d.ld_ga, 4 * d.n_a);
         MARL_TRY(gemm1(c, p));
-        }
-        if (dl_in_loop)  // d(position embedding) = belief share + action share
-            MARL_TRY(launch_add2d(c.at(c.e.DDBAR) + d.n_mo, d.ld_dbl, c.at(c.e.DDBAR2) + d.n_mo, d.ld_dbl,
-                                  c.at(c.e.DU) + d.nf + d.n_mo, d.ld_nin, NR, d.n_d, st));
     }
+    if (s.panels)  // d(position embedding) = belief share + action share
+        MARL_TRY(launch_add2d(c.at(c.e.DDBAR) + d.n_mo, d.ld_dbl, c.at(c.e.DDBAR2) + d.n_mo, d.ld_dbl,
+                              c.at(c.e.DU) + d.nf + d.n_mo, d.ld_nin, NR, d.n_d, st));
     MARL_TRY(ln_bwd(c, c.at(c.e.DU) + d.nf + d.n_mo, d.ld_nin, c.at(c.e.ZPOS, 0), d.ld_nd,
                     c.at(c.e.STPOS, 0), MARL_P_POS_LNW, MARL_P_POS_LNB, NR, d.n_d, grads, 0,
                     c.at(c.e.DZPOS), d.ld_nd));
     MARL_TRY(tn(c, c.at(c.e.DZPOS), d.ld_nd, c.at(c.e.NPOS, 0), 4, MARL_P_POS_W, d.n_d, 2, NR, grads[MARL_P_POS_B]));
-    {
-        const float* da = c.at(c.e.DU);
-        int64_t ldda = d.ld_nin;
-        int chw = 1;
-        bool have_dz = false;  // DZ[l] already produced by the fused layer backward of layer l+1
-        bool w0_done = false;  // ... which also formed layer 0's weight gradient (dZ_0 never left LDS)
-        for (int l = d.L - 1; l >= 0; --l) {
-            const int co = d.ch[l + 1];
-            const int64_t rows = NR * d.P[l];
-            float* dz = c.at(c.e.DZ[l]);
-            if (!have_dz) {
-                RedQueue* q;
-                float* part = part_scratch(c, gn_bwd_blocks(NR, co), co, 0, q);
-                MARL_TRY(launch_gn_silu_bwd(da, ldda, chw, c.at(c.e.Z[l], 0), c.at(c.e.GST[l], 0),
-                                            c.wp(4 * l + 2), c.wp(4 * l + 3), dz, part, NR, d.P[l], co,
-                                            d.grp[l], st));
-                MARL_TRY(launch_reduce_affine(part, gn_bwd_blocks(NR, co), co, grads[4 * l + 2],
-                                              grads[4 * l + 3], 0, st, q));
-            }
-            have_dz = false;
-            if (l == 0 && w0_done) {
-                // (layer 0's weight and bias gradient came out of the launch that produced dZ_0)
-            } else if (c.e.wgrad_ok[l]) {
-                // dW_l (and db_l) from dZ_l and the layer's input, recomputed from what forward
-                // kept (Z_{l-1} + statistics, or the image patch): no im2col rows in HBM
-                CnnWgradArgs w = cnn_wgrad_shape(d, l);
-                w.dz = dz;
-                w.img = img;
-                w.img_u8 = img_u8;
-                w.pos = c.POSs(0);
-                if (l > 0) {
-                    w.zin = c.at(c.e.Z[l - 1], 0);
-                    w.gst = c.at(c.e.GST[l - 1], 0);
-                    w.gamma = c.wp(4 * (l - 1) + 2);
-                    w.beta = c.wp(4 * (l - 1) + 3);
-                } else if (sb) {
-                    // standalone step: the caller's patches obs [R, C, f, f] are R one-patch images of
-                    // f x f at position 0 (POSs(0) zeroed above) - the gather reads exactly obs[r]
-                    w.img = sb->obs;
-                    w.img_u8 = 0;
-                    w.nb = (int)d.R;
-                    w.H = w.W = d.f;
-                } else if (!img) {
-                    set_error("episode_backward: the image batch of the forward call is needed");
-                    return MARL_EINVAL;
-                }
-                // per-workgroup slabs; the launcher places part_b behind the weight slabs
-                w.part_w = c.at(c.e.TNS);
-                if (c.rq && c.defer_this((size_t)cnn_wgrad_blocks(w) * ((size_t)co * d.K[l] + co) * sizeof(float))) {
-                    float* p = c.rq->take((size_t)cnn_wgrad_blocks(w) * ((size_t)co * d.K[l] + co));
-                    if (c.rq->rc == MARL_OK) w.part_w = p;
-                }
-                MARL_TRY(launch_cnn_wgrad(w, st));
-                if (c.rq && w.part_w != c.at(c.e.TNS)) {
-                    c.rq->push(w.part_w, (int64_t)co * d.K[l], w.blocks, co * d.K[l], c.gp(4 * l),
-                               co * d.K[l], d.K[l], c.w.ldp[4 * l], nullptr, 0);
-                    c.rq->push(w.part_b, co, w.blocks, co, grads[4 * l + 1], co, co, co, nullptr, 0);
-                } else {
-                    MARL_TRY(launch_slab_reduce(w.part_w, (int64_t)co * d.K[l], w.blocks, c.gp(4 * l),
-                                                c.w.ldp[4 * l], co, d.K[l], w.part_b, grads[4 * l + 1], st));
-                }
-            } else {
-                MARL_TRY(tn(c, dz, co, c.at(c.e.COLS[l], 0), d.ldk[l], 4 * l, co, d.K[l], rows, grads[4 * l + 1]));
-            }
-            if (l > 0) {
-                // dZ_l -> dZ_{l-1} in one launch (transposed conv + GroupNorm/SiLU backward)
-                CnnDgradArgs g = cnn_dgrad_shape(d, l);
-                g.dz = dz;
-                g.wt = c.wt(4 * l);
-                g.ldwt = p4(co);
-                g.zin = c.at(c.e.Z[l - 1], 0);
-                g.gst = c.at(c.e.GST[l - 1], 0);
-                g.gamma = c.wp(4 * (l - 1) + 2);
-                g.beta = c.wp(4 * (l - 1) + 3);
-                g.dzin = c.at(c.e.DZ[l - 1]);
-                if (g.w0 && !img) g.w0 = 0;  // (the step API has no image batch: layer 0 takes the separate launch)
-                if (d_img) g.w0 = 0;         // (the image gradient reads dZ_0 from the workspace)
-                if (c.e.dgrad_ok[l] &&
-                    (size_t)cnn_dgrad_blocks(g) * 2 * d.ch[l] <= c.e.part_floats) {
-                    RedQueue* q;
-                    const int nblk = cnn_dgrad_blocks(g);
-                    g.part = part_scratch(c, nblk, d.ch[l], 0, q);
-                    const int co0 = d.ch[l], k0 = d.K[0];
-                    if (g.w0) {  // + layer 0's weight gradient: per-workgroup slabs (tiny: 448 floats each at RESISC)
-                        const size_t fl = (size_t)nblk * ((size_t)co0 * k0 + co0);
-                        g.w0_part = c.at(c.e.TNS);
-                        if (c.rq && c.defer_this(fl * sizeof(float))) {
-                            float* p = c.rq->take(fl);
-                            if (c.rq->rc == MARL_OK) g.w0_part = p;
-                        }
-                        g.w0_bpart = g.w0_part + (size_t)nblk * co0 * k0;
-                        g.img = img;
-                        g.img_u8 = img_u8;
-                        g.pos = c.POSs(0);
-                        g.dzin = nullptr;  // dZ_0 stays in LDS
-                    }
-                    MARL_TRY(launch_cnn_dgrad(g, st));
-                    MARL_TRY(launch_reduce_affine(g.part, nblk, d.ch[l],
-                                                  grads[4 * (l - 1) + 2], grads[4 * (l - 1) + 3], 0, st, q));
-                    if (g.w0) {
-                        if (c.rq && g.w0_part != c.at(c.e.TNS)) {
-                            c.rq->push(g.w0_part, (int64_t)co0 * k0, nblk, co0 * k0, c.gp(0), co0 * k0, k0, c.w.ldp[0], nullptr, 0);
-                            c.rq->push(g.w0_bpart, co0, nblk, co0, grads[1], co0, co0, co0, nullptr, 0);
-                        } else {
-                            MARL_TRY(launch_slab_reduce(g.w0_part, (int64_t)co0 * k0, nblk, c.gp(0), c.w.ldp[0], co0, k0,
-                                                        g.w0_bpart, grads[1], st));
-                        }
-                        w0_done = true;
-                    }
-                    have_dz = true;
-                    continue;
-                }
-                g.w0 = 0;
-                MARL_TRY(gemm1(c, gemm_prob(dz, co, c.wt(4 * l), p4(co), co, c.at(c.e.DCOLS[l]),
-                                            d.ldk[l], (int)rows, d.K[l])));
-                MARL_TRY(launch_col2im(c.at(c.e.DCOLS[l]), d.ldk[l], c.at(c.e.DA[l - 1]), NR,
-                                       d.hw[l], d.ch[l], st));
-                da = c.at(c.e.DA[l - 1]);
-                ldda = (int64_t)d.P[l - 1] * d.ch[l];
-                chw = 0;
-            }
-        }
-    }
-    if (d_img) {  // dL/d(img): dZ_0 (left in the workspace by the layer loop above) back through the crops of every step
+    MARL_TRY(bwd_cnn_layers(s, img, img_u8, d_img));
+    if (d_img) {  // dL/d(img): dZ_0 (left in the workspace by the layer loop) back through the crops of every step
         CnnDimgArgs a = cnn_dimg_shape(d);
         a.dz0 = c.at(c.e.DZ[0]);
         a.wt0 = c.wt(0);
@@ -2101,9 +2077,43 @@ static int episode_backward(const Ctx& c0, const void* img, int img_u8, const fl
         a.d_img = d_img;
         MARL_TRY(launch_cnn_dimg(a, st));
     }
-    if (c.tq) MARL_TRY(launch_tn_queue(tq, c.rq, st));  // the small weight gradients, one launch
-    MARL_TRY(rq.flush());
-    return unpack_grads(c, grads, heads_early ? 2 : 0);
+    return MARL_OK;
+}
+
+static int episode_backward(const Ctx& c0, const void* img, int img_u8, const float* g_preds,
+                            const float* g_logp, const float* g_values, float* const* grads,
+                            const StepBwd* sb = nullptr, float* d_img = nullptr,
+                            const float* g_probs = nullptr) {
+    BwdState s;
+    s.c = c0;
+    s.grads = grads;
+    s.sb = sb;
+    s.enc_last = sb && sb->g_msg;
+    Ctx& c = s.c;
+    s.rq.reset(c.at(c.e.RED), c.e.red_floats, c.st);
+    // 1: the small LayerNorm / GroupNorm affine partials wait for one launch at the end; the
+    // weight-gradient slabs (~0.4 GB per iteration in all) are reduced at once, while the
+    // Infinity Cache still holds them (2: defer those too - measured slower at C3 / C4: 0.43 GB of
+    // slabs come back from HBM).  3 (default): as 1, plus the slabs of at most red_defer_kb KB
+    // each (8 MB: larger thresholds lose again at C4) - on small problems (C2: 22 weight gradients) one batched
+    // reduction replaces 22 launches: 0.953 -> 0.897 ms per iteration.
+    const int defer = tune_get("red_defer", 3);
+    if (defer) c.rq = &s.rq;
+    if (defer) c.tq = &s.tq;
+    c.defer_slabs = defer == 2;
+    c.defer_small = defer == 3 ? (size_t)8192 * 1024 : 0;
+    for (int i = 0; i < MARL_NPARAMS; ++i)
+        if (param_meta(c.d, i).kind != PK_NONE && !grads[i]) {
+            set_error("gradient buffer %d is null", i);
+            return MARL_EINVAL;
+        }
+    MARL_TRY(bwd_heads(s, g_preds, g_logp, g_values, g_probs));
+    MARL_TRY(bwd_loop(s));
+    MARL_TRY(bwd_chain_wgrads(s));
+    MARL_TRY(bwd_inputs(s, img, img_u8, d_img));
+    if (c.tq) MARL_TRY(launch_tn_queue(s.tq, c.rq, c.st));  // the small weight gradients, one launch
+    MARL_TRY(s.rq.flush());
+    return unpack_grads(c, grads, s.heads_early ? 2 : 0);
 }
 
 }  // namespace marl
@@ -2234,20 +2244,11 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
     StepIn in;
     in.img = img;
     in.img_u8 = cfg->img_u8 != 0;
-    const bool side = use_side_stream();
-    Ctx c2 = c;
-    if (side) {
-        MARL_TRY(g_side.init());
-        c2.st = g_side.s;
-    }
     bool decoded_ahead = false;  // decoder(t) already ran with the sampling of step t-1
-    const bool chain = !side && use_chain(d);
+    const bool chain = use_chain(d);
     for (int t = 0; t < d.ns; ++t) {
         MARL_TRY(step_cnn(c, t, in));
-        if (side && t > 0)
-            MARL_TRY(g_side.order(c2.st, c.st));  // decoder(t) ran on the side stream
-        else if (!decoded_ahead)
-            MARL_TRY(step_decode(c, t));
+        if (!decoded_ahead) MARL_TRY(step_decode(c, t));
         MARL_TRY(step_pos_lstm(c, t, in, t > 0));  // lambda_t (t > 0) came from sample(t-1)
         SampleArgs a;
         fill_sample_args(c, cfg, t, a);
@@ -2281,22 +2282,16 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
         }
         if (chain) {
             MARL_TRY(step_chain(c, t, &a));  // encoder(t) -> decoder(t+1) || policy layer(t) [-> sample(t)]
-        } else if (side) {
-            MARL_TRY(g_side.order(c.st, c2.st));  // side stream: after the LSTM of step t
-            MARL_TRY(step_encode_policy(c2, t, 1));
-            if (t + 1 < d.ns) MARL_TRY(step_decode(c2, t + 1));
-            MARL_TRY(step_encode_policy(c, t, 2));
         } else {
-            MARL_TRY(step_encode_policy(c, t, 3));
+            MARL_TRY(step_encode_policy(c, t));
         }
         // sample(t) and decoder(t+1) are independent (the decoder needs MSG[t+1], written by the
         // encoder above): one launch runs both.  Under the chain launch decoder(t+1) is already inside it, and so
         // is sample(t) when its policy workgroups ran it as their epilogue
         decoded_ahead = chain && t + 1 < d.ns;
-        if (!side && !chain && t + 1 < d.ns) MARL_TRY(step_decode(c, t + 1, &a, &decoded_ahead));
+        if (!chain && t + 1 < d.ns) MARL_TRY(step_decode(c, t + 1, &a, &decoded_ahead));
         if (chain ? !use_panel_sample(d) : !decoded_ahead) MARL_TRY(launch_sample(a, c.st));
     }
-    if (side) MARL_TRY(g_side.order(c2.st, c.st));  // join before the caller's stream continues
     MARL_TRY(heads_batched(c, 0, d.NR, step_values, step_preds));
     if (step_probs) MARL_TRY(launch_copy2d(c.PROBSs(0), d.nA, step_probs, d.nA, d.NR, d.nA, c.st));
     return MARL_OK;
@@ -2977,12 +2972,11 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     // launch - the decoder of step 0 and the step API then take form 3); "panel_chain" = the chained launch
     else if (!strcmp(key, "comm")) *value = g_comm != nullptr;
     else if (!strcmp(key, "comm_range")) *value = g_range.radius >= 0 ? g_range.radius : -1;  // the radius, or -1
-    else if (!strcmp(key, "panel_chain")) *value = use_chain(d) && !use_side_stream();
+    else if (!strcmp(key, "panel_chain")) *value = use_chain(d);
     // the forward loop samples inside the chained launch (the policy workgroups' epilogue): no sample_kernel launch
-    else if (!strcmp(key, "panel_sample")) *value = use_chain(d) && !use_side_stream() && use_panel_sample(d);
+    else if (!strcmp(key, "panel_sample")) *value = use_chain(d) && use_panel_sample(d);
     else if (!strcmp(key, "comm_form"))
-        *value = g_comm ? ((use_chain(d) && !use_side_stream()) ? 5 : use_panels(d) ? 3 : 4)
-                        : (use_chain(d) && !use_side_stream()) ? 0 : use_panels(d) ? 1 : 2;
+        *value = g_comm ? (use_chain(d) ? 5 : use_panels(d) ? 3 : 4) : use_chain(d) ? 0 : use_panels(d) ? 1 : 2;
     else {
         set_error("unknown plan key %s", key);
         return MARL_EINVAL;
