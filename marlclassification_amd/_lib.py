@@ -84,8 +84,8 @@ EXPORTS = (
 
 # kernel-level test hooks that include/marl_hip_rowops.h declares (outside the versioned ABI above)
 ROWOP_HOOKS = ("marl_ln_silu_bwd", "marl_gn_silu_bwd")
-# ... and those of the conv backward that include/marl_hip_cnnops.h declares
-CNNOP_HOOKS = ("marl_cnn_dgrad", "marl_cnn_dgrad_scratch", "marl_cnn_bwd_plan")
+# ... and those of the conv kernels that include/marl_hip_cnnops.h declares
+CNNOP_HOOKS = ("marl_cnn_dgrad", "marl_cnn_dgrad_scratch", "marl_cnn_bwd_plan", "marl_cnn_fwd", "marl_cnn_fwd_plan")
 _HOOKS = ROWOP_HOOKS + CNNOP_HOOKS
 
 
@@ -98,6 +98,29 @@ class CnnBwdPlan(C.Structure):
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class CnnFwdIo(C.Structure):
+    """Mirror of ``marl_cnn_fwd_io`` (include/marl_hip_cnnops.h)."""
+
+    _fields_ = [("img", C.c_void_p), ("pos", C.c_void_p), ("obs", C.c_void_p), ("rows", C.c_int64),
+                ("u", C.c_void_p), ("ldu", C.c_int32),
+                ("z", C.c_void_p * MARL_MAX_CNN_LAYERS), ("gst", C.c_void_p * MARL_MAX_CNN_LAYERS),
+                ("cols", C.c_void_p * MARL_MAX_CNN_LAYERS),
+                ("u3", C.c_void_p), ("u3_row0", C.c_int32), ("u3_steps", C.c_int32)]
+
+
+class CnnFwdPlan(C.Structure):
+    """Mirror of ``marl_cnn_fwd_plan_info`` (include/marl_hip_cnnops.h)."""
+
+    _fields_ = [("fused", C.c_int32), ("which", C.c_int32), ("rb", C.c_int32), ("blocks", C.c_int32),
+                ("keeps_cols", C.c_int32 * MARL_MAX_CNN_LAYERS), ("writes_image", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        out = {name: getattr(self, name) for name, _ in self._fields_}
+        out["keeps_cols"] = list(self.keeps_cols)
+        return out
+
 
 _lib: Optional[C.CDLL] = None
 
@@ -189,6 +212,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_cnn_dgrad_scratch.restype = _sz
     lib.marl_cnn_dgrad_scratch.argtypes = [_i64, _i, _i, _i, _i]
     lib.marl_cnn_bwd_plan.argtypes = [_i64, _i, _i, _i, _i, _i, C.POINTER(CnnBwdPlan)]
+    lib.marl_cnn_fwd.argtypes = [_cfgp, _vp, _sz, C.POINTER(CnnFwdIo), _vp]
+    lib.marl_cnn_fwd_plan.argtypes = [_cfgp, _i, _i64, C.POINTER(CnnFwdPlan)]
     for name in EXPORTS + list(_HOOKS):
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("marl_abi_version", "marl_tune_get"):

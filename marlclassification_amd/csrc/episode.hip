@@ -756,42 +756,77 @@ static bool use_panels(const Dims& d) {
            panel_supported(d.n_a, d.nla, 0);
 }
 
+// What one launch of the fused extractor forward reads and writes.  step_cnn fills it from the episode workspace,
+// marl_cnn_fwd (include/marl_hip_cnnops.h) from its caller's buffers; cnn_fwd_args is the only place that turns it
+// into the kernels' arguments.
+struct CnnFwdIo {
+    const void* img = nullptr;
+    const float* obs = nullptr;
+    const int32_t* pos = nullptr;
+    int img_u8 = 0;
+    int64_t rows = 0;
+    float* cols[MARL_MAX_CNN_LAYERS] = {};  // null: not kept
+    float* z[MARL_MAX_CNN_LAYERS] = {};
+    float* gst[MARL_MAX_CNN_LAYERS] = {};
+    float* u = nullptr;
+    int ldu = 0;
+    char* u3 = nullptr;
+    int u3_row0 = 0, u3_steps = 0;
+};
+static CnnFwdArgs cnn_fwd_args(const Dims& d, const WLayout& w, const float* W, const CnnFwdIo& io) {
+    CnnFwdArgs a{};
+    a.img = io.img;
+    a.obs = io.obs;
+    a.pos = io.pos;
+    a.img_u8 = io.img_u8;
+    a.rows = io.rows;
+    a.nb = d.nb;
+    a.c_img = d.c_img;
+    a.H = d.H;
+    a.W = d.W;
+    a.f = d.f;
+    a.L = d.L;
+    for (int l = 0; l < d.L; ++l)
+        a.layer[l] = CnnFwdLayer{W + w.wp[4 * l], W + w.wp[4 * l + 1], W + w.wp[4 * l + 2], W + w.wp[4 * l + 3],
+                                 io.cols[l], io.z[l], io.gst[l],
+                                 d.ch[l], d.ch[l + 1], d.grp[l], d.hw[l], d.hw[l + 1], d.P[l],
+                                 d.K[l], d.ldk[l], w.wf[4 * l] ? W + w.wf[4 * l] : nullptr};
+    a.u = io.u;
+    a.ldu = io.ldu;
+    a.u3 = io.u3;
+    a.u3_row0 = io.u3_row0;
+    a.u3_steps = io.u3_steps;
+    return a;
+}
+
 // ---- the five phases of one step; each only depends on what the comment names -----------
 
 // observation -> CNN features b_t -> U[t][:, :nf]            (needs POS[t])
 static int step_cnn(const Ctx& c, int t, const StepIn& in) {
     const Dims& d = c.d;
     hipStream_t st = c.st;
-    {
+    if (c.e.fused_fwd) {
         // one fused launch for the whole extractor when the shapes allow it
-        const bool keep = c.train != 0;
-        CnnFwdArgs a{};
-        a.img = in.img;
-        a.obs = in.obs;
-        a.pos = c.POSs(t);
-        a.img_u8 = in.img_u8;
-        a.rows = d.R;
-        a.nb = d.nb;
-        a.c_img = d.c_img;
-        a.H = d.H;
-        a.W = d.W;
-        a.f = d.f;
-        a.L = d.L;
-        for (int l = 0; l < d.L; ++l)
-            a.layer[l] = CnnFwdLayer{c.wp(4 * l), c.wp(4 * l + 1), c.wp(4 * l + 2), c.wp(4 * l + 3),
-                                     cnn_fwd_keeps_cols(c.e.wgrad_ok, c.train, l) ? c.at(c.e.COLS[l], t) : nullptr,
-                                     keep ? c.at(c.e.Z[l], t) : nullptr,
-                                     keep ? c.at(c.e.GST[l], t) : nullptr,
-                                     d.ch[l], d.ch[l + 1], d.grp[l], d.hw[l], d.hw[l + 1], d.P[l],
-                                     d.K[l], d.ldk[l], c.w.wf[4 * l] ? c.W + c.w.wf[4 * l] : nullptr};
-        a.u = c.at(c.e.U, t);
-        a.ldu = d.ld_nin;
-        if (c.u3_by_producers) {
-            a.u3 = c.img(c.e.U3);
-            a.u3_row0 = c.u3_row(t);
-            a.u3_steps = img_steps(d.nin);
+        CnnFwdIo io;
+        io.img = in.img;
+        io.obs = in.obs;
+        io.pos = c.POSs(t);
+        io.img_u8 = in.img_u8;
+        io.rows = d.R;
+        for (int l = 0; l < d.L; ++l) {
+            io.cols[l] = cnn_fwd_keeps_cols(c.e.wgrad_ok, c.train, l) ? c.at(c.e.COLS[l], t) : nullptr;
+            io.z[l] = c.train ? c.at(c.e.Z[l], t) : nullptr;
+            io.gst[l] = c.train ? c.at(c.e.GST[l], t) : nullptr;
         }
-        if (c.e.fused_fwd) return launch_cnn_fwd(a, st);
+        io.u = c.at(c.e.U, t);
+        io.ldu = d.ld_nin;
+        if (c.u3_by_producers) {
+            io.u3 = c.img(c.e.U3);
+            io.u3_row0 = c.u3_row(t);
+            io.u3_steps = img_steps(d.nin);
+        }
+        CnnFwdArgs a = cnn_fwd_args(d, c.w, c.W, io);
+        return launch_cnn_fwd(a, st);
     }
     if (in.obs)
         MARL_TRY(launch_obs_im2col(in.obs, c.at(c.e.COLS[0], t), d.ldk[0], d.R, d.c_img, d.ch[0],
@@ -3256,6 +3291,93 @@ int marl_cnn_bwd_plan(int64_t rows, int cin, int cout, int hin, int groups, int 
         out->dg_supported = 1, out->dg_rb = p.rb, out->dg_mt = p.MT, out->dg_nt = p.NT, out->dg_blocks = p.blocks;
     }
     return MARL_OK;
+}
+
+// ---- the fused extractor forward through its own entry point --------------------------------------------------
+// the dimensions of a launch over `rows` rows of cfg's model: everything but the row count as in an episode
+static int cnn_fwd_api_dims(const marl_config* cfg, int64_t rows, Dims& d) {
+    MARL_TRY(make_dims(cfg, d));
+    if (rows < 1 || rows * d.ns >= (1ll << 31)) {
+        set_error("cnn_fwd: %lld rows", (long long)rows);
+        return MARL_EINVAL;
+    }
+    d.R = rows;
+    d.NR = rows * d.ns;
+    return MARL_OK;
+}
+
+int marl_cnn_fwd_plan(const marl_config* cfg, int train, int64_t rows, marl_cnn_fwd_plan_info* out) {
+    if (!out) {
+        set_error("marl_cnn_fwd_plan: null argument");
+        return MARL_EINVAL;
+    }
+    *out = marl_cnn_fwd_plan_info{};
+    Dims d;
+    MARL_TRY(cnn_fwd_api_dims(cfg, rows, d));
+    ELayout e;
+    make_elayout(d, train, e);  // (fused_fwd and wgrad_ok as every entry of the episode decides them)
+    if (!e.fused_fwd) return MARL_OK;
+    WLayout w;
+    make_wlayout(d, w);
+    static float here;
+    CnnFwdArgs a = cnn_fwd_shape(d);
+    for (int l = 0; l < d.L; ++l) {
+        out->keeps_cols[l] = cnn_fwd_keeps_cols(e.wgrad_ok, train, l);
+        a.layer[l].cols = out->keeps_cols[l] ? &here : nullptr;
+        a.layer[l].wfrag = w.wf[4 * l] ? &here : nullptr;
+    }
+    const CnnFwdPlan p = cnn_fwd_launch_plan(a);
+    out->fused = 1, out->which = p.which, out->rb = p.rb, out->blocks = p.blocks;
+    out->writes_image = cnn_fwd_writes_image(a);
+    return MARL_OK;
+}
+
+int marl_cnn_fwd(const marl_config* cfg, const void* weights_ws, size_t weights_ws_bytes, const marl_cnn_fwd_io* io,
+                 void* stream) {
+    if (!io) {
+        set_error("marl_cnn_fwd: null argument");
+        return MARL_EINVAL;
+    }
+    Dims d;
+    MARL_TRY(cnn_fwd_api_dims(cfg, io->rows, d));
+    if (!cnn_fwd_supported(cnn_fwd_shape(d))) {  // (the question make_elayout asks: ELayout::fused_fwd)
+        set_error("marl_cnn_fwd: the fused forward does not cover this model (window %d, %d layers)", d.f, d.L);
+        return MARL_ELIMIT;
+    }
+    auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    bool bad = !weights_ws || (reinterpret_cast<uintptr_t>(weights_ws) & 255) || !io->u || misaligned(io->u) ||
+               io->ldu < d.nf || (io->ldu & 3) || (!io->obs && (!io->img || !io->pos));
+    for (int l = 0; l < d.L; ++l) bad = bad || misaligned(io->z[l]) || misaligned(io->gst[l]) || misaligned(io->cols[l]);
+    if (io->u3) bad = bad || misaligned(io->u3) || io->u3_row0 < 0 || io->u3_steps < img_steps(d.nf);
+    if (bad) {
+        set_error("marl_cnn_fwd: null or misaligned pointer, or bad size");
+        return MARL_EINVAL;
+    }
+    WLayout w;
+    make_wlayout(d, w);
+    if (weights_ws_bytes < w.total * sizeof(float)) {
+        set_error("marl_cnn_fwd: weights workspace too small (%zu of %zu bytes)", weights_ws_bytes,
+                  w.total * sizeof(float));
+        return MARL_ESIZE;
+    }
+    CnnFwdIo f;
+    f.img = io->img;
+    f.obs = io->obs;
+    f.pos = io->pos;
+    f.img_u8 = cfg->img_u8 != 0;
+    f.rows = io->rows;
+    for (int l = 0; l < d.L; ++l) f.cols[l] = io->cols[l], f.z[l] = io->z[l], f.gst[l] = io->gst[l];
+    f.u = io->u;
+    f.ldu = io->ldu;
+    f.u3 = static_cast<char*>(io->u3);
+    f.u3_row0 = io->u3_row0;
+    f.u3_steps = io->u3_steps;
+    CnnFwdArgs a = cnn_fwd_args(d, w, static_cast<const float*>(weights_ws), f);
+    if (io->u3 && !cnn_fwd_writes_image(a)) {
+        set_error("marl_cnn_fwd: the kernel selected for this launch does not write the image of U");
+        return MARL_EINVAL;
+    }
+    return launch_cnn_fwd(a, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -1,11 +1,13 @@
-"""marl_cnn_bwd_plan (include/marl_hip_cnnops.h) on the host: the plans of the conv backward launchers for a raw layer
-shape, from the launchers' own routines.  It must agree with what marl_plan_query reports for a whole configuration, and
-the grid of tests/test_gpu_conv_bwd.py must witness every cnn_wgrad_kernel instantiation a model can select.  No GPU:
-the library loads without one (tests/test_plan_witness_host.py relies on the same)."""
+"""marl_cnn_bwd_plan and marl_cnn_fwd_plan (include/marl_hip_cnnops.h) on the host: the plans of the conv launchers
+- backward for a raw layer shape, forward for a model and a row count - from the launchers' own routines.  They must
+agree with what marl_plan_query reports for a whole configuration, and the grids of tests/test_gpu_conv_bwd.py and
+tests/test_gpu_conv_fwd.py must witness every instantiation a model can select.  No GPU: the library loads without one
+(tests/test_plan_witness_host.py relies on the same)."""
 import ctypes as C
 
 import pytest
 
+from tests import test_gpu_conv_fwd as fwd
 from tests.test_gpu_conv_bwd import DG_SHAPES, WG_DEEP, WG_FIRST, assert_wgrad_witness, plan
 from tests.util import CASES, PLAN_CASES, plan_witness
 
@@ -110,3 +112,94 @@ def test_refusals_need_no_gpu():
     assert lib.marl_cnn_dgrad(None, 4096, 32, 4096, 4096, 4096, 4096, 4096, 4096, 4096, 4096, 1 << 20, 10, 16, 32, 4, 2,
                               None) == -1
     assert lib.marl_cnn_dgrad_scratch(10, 16, 32, 4, 2) == 10 * 2 * 16 * 4
+
+
+# ---- forward (tests/test_gpu_conv_fwd.py) ----------------------------------------------------------------------------
+@pytest.mark.parametrize("cfg,na,nb,ns,shape", [
+    (CASES["g4_resisc_b2"], 16, 255, 4, (3, 256, 256)),  # Fwd2Resisc on its persistent walk
+    (PLAN_CASES["worldstrat16"][0], 4, 7 * 37, 3, (3, 72, 80)),  # the general kernel at rb = 4
+    (CASES["g2_mnist_c1"], 3, 1024, 5, (1, 28, 28)),  # Fwd2Mnist6; the general kernel under cnn_fwd2 = 0
+], ids=["resisc45", "worldstrat", "mnist"])
+def test_the_forward_hook_agrees_with_plan_query(cfg, na, nb, ns, shape):
+    from tests.util import model_spec
+
+    lib = _lib()
+    mc = model_spec(cfg).config(na, nb, ns, *shape)
+    seen = set()
+    try:
+        for knob in (1, 0):
+            assert lib.marl_tune(b"cnn_fwd2", knob) == 0
+            for train in (0, 1):
+                w = plan_witness(cfg, na, nb, ns, shape, train=bool(train))
+                p = fwd.plan(mc, train, na * nb)
+                assert p["fused"] == 1
+                assert (p["which"], p["rb"], p["blocks"]) == (w["cnn_fwd"], w["cnn_fwd_rb"], w["cnn_fwd_blocks"]), (p, w)
+                assert p["writes_image"] == (p["which"] in (1, 2, 4, 5)) and not any(p["keeps_cols"])
+                seen.add((knob, p["which"]))
+    finally:
+        lib.marl_tune(b"cnn_fwd2", 1)
+    assert all(which == 6 for knob, which in seen if knob == 0)
+    assert {which for knob, which in seen if knob == 1} in ({1}, {2}, {6})
+
+
+def test_the_forward_grid_witnesses_every_selectable_plan():
+    """the (which, keeps_cols) pairs that a CNN_SPECS model - or the custom stack the kept-rows scan adds - selects at a
+    window of 4..32 under the default knobs, as a rollout or a training launch, are exactly those the witnesses of
+    tests/test_gpu_conv_fwd.py name; and every model is covered by the fused forward"""
+    from marlclassification_amd.engine import CNN_SPECS
+
+    selected = {}
+    for name, stack in list(CNN_SPECS.items()) + list(fwd.COLS_EXTRA.items()):
+        for f in range(4, 33):
+            for train in (0, 1):
+                p = fwd.plan(fwd.config(stack, f, f + 8, f + 10), train, 1000)
+                assert p["fused"] == 1, (name, f)
+                selected.setdefault((p["which"], tuple(p["keeps_cols"])), (name, f, train))
+    witnessed = {(w["which"], tuple(w["keeps_cols"])) for rows in fwd.GRID.values() for w in rows.values()}
+    witnessed |= {(w["which"], tuple(w["keeps_cols"])) for w in fwd.COLS_GRID.values()}
+    assert set(selected) == witnessed, (selected, witnessed)
+    assert {k[0] for k in selected} == {1, 2, 3, 4, 5, 6}
+    # rows are kept on the fused path by no CNN_SPECS model: only by the custom stack, from its smallest window on
+    assert fwd.smallest_cols_config()[:3] == (fwd.COLS_MIN[0], fwd.CUSTOM, fwd.COLS_MIN[1])
+
+
+def test_the_forward_grid_tables_hold_on_the_host():
+    """the witnesses of the GPU grid without a GPU, the shapes its comments promise, and the knobs back at their
+    defaults afterwards"""
+    lib = _lib()
+    for model, rows_w in fwd.GRID.items():
+        with fwd.knobs(model):
+            for rows, w in rows_w.items():
+                assert fwd.plan(fwd.model_config(model), 1, rows) == w, (model, rows)
+                if rows > w["rb"]:
+                    assert rows % w["rb"] == 1
+                if rows > 1000:
+                    assert (w["blocks"] == 256 < -(-rows // w["rb"])) if w["which"] != 6 else w["blocks"] == -(-rows // w["rb"])
+        assert lib.marl_tune_get(b"cnn_fwd2", 1) == 1 and lib.marl_tune_get(b"cnn_fwd3", 1) == 1
+    for rows, w in fwd.COLS_GRID.items():
+        assert fwd.plan(fwd.model_config(fwd.COLS_MIN[2]), 1, rows) == w
+    for model, rows in fwd.FORMS.items():  # the image forms compare launches of one plan
+        p1, p0 = (fwd.plan(fwd.model_config(model), t, rows) for t in (1, 0))
+        assert (p1["which"], p1["rb"]) == (p0["which"], p0["rb"]) and rows in fwd.GRID[model]
+
+
+def test_forward_refusals_need_no_gpu():
+    from marlclassification_amd._lib import CnnFwdIo, CnnFwdPlan
+
+    lib = _lib()
+    cfg = fwd.model_config("mnist10")
+    p = CnnFwdPlan()
+    assert lib.marl_cnn_fwd_plan(C.byref(cfg), 1, 10, None) == -1
+    assert lib.marl_cnn_fwd_plan(None, 1, 10, C.byref(p)) == -1 and lib.marl_cnn_fwd_plan(C.byref(cfg), 1, 0, C.byref(p)) == -1
+    # one channel per group: outside the fused forward - every field 0, and the launch refuses before it reads anything
+    refused = fwd.config(([1, 8, 16], [8, 4]), 10, 28, 30)
+    assert fwd.plan(refused, 1, 10) == dict(fused=0, which=0, rb=0, blocks=0, keeps_cols=[0] * 5, writes_image=0)
+    io = CnnFwdIo()
+    io.img = io.pos = io.u = 4096  # (aligned non-null addresses)
+    io.rows, io.ldu = 10, 144
+    assert lib.marl_cnn_fwd(C.byref(refused), 4096, 1 << 30, C.byref(io), None) == -2
+    assert b"does not cover" in lib.marl_last_error()
+    assert lib.marl_cnn_fwd(C.byref(cfg), 4096, 0, C.byref(io), None) == -4
+    io.u = None
+    assert lib.marl_cnn_fwd(C.byref(cfg), 4096, 1 << 30, C.byref(io), None) == -1
+    assert lib.marl_cnn_fwd(C.byref(cfg), 4096, 1 << 30, None, None) == -1

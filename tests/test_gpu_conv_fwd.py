@@ -1,0 +1,578 @@
+"""GPU: the fused extractor forward of csrc/cnn.hip through its own entry point - cnn_fwd_kernel, cnn_fwd2_kernel<Fwd2Resisc
+| Fwd2Mnist6 | Fwd2Mnist12> and cnn_fwd3_kernel<Fwd3Aid24 | Fwd3Aid32> through marl_cnn_fwd (include/marl_hip_cnnops.h),
+the launch the CNN phase of a step makes - against float64 torch on the CPU: crop at pos, then per layer conv2d(stride 2,
+pad 1) -> group_norm(eps 1e-5) -> silu.  Compared: the saved conv outputs Z_l (NHWC), the statistics GST_l (mean, rstd per
+row and group), the features U[r][c * P_last + p] and, where the launch keeps them, the im2col rows COLS_l.
+
+Every case first asserts its witness from marl_cnn_fwd_plan (what the launcher chooses, from the launcher's own routines),
+so a changed plan rule fails here instead of turning a case into a copy of another; tests/test_conv_plan_host.py checks
+the tables below without a GPU.  Weights come out of a weights workspace written by marl_pack_weights, as in the product.
+Images and positions sit between NaNs (255 for bytes), every output inside a sentinel-filled buffer: the sentinels must
+survive outside the tensor - columns [nf, ldu) of every row of U included - and be gone inside; every call runs twice and
+must repeat bit for bit; knobs are restored.
+
+Bounds, relative to the float64 tensor's largest magnitude, per output kind (U, each Z_l, mean, rstd, deeper COLS_l): the
+cap 1e-5 (the forward parity budget of DESIGN.md section 2 that cnn_silu is written against), and err <= max(MULT * e32,
+floor), where e32 is the error of the same computation by torch on the CPU in float32 on the same data and floor the worst
+e32 of the whole grid for that kind.  MULT = 4 as in tests/test_gpu_conv_bwd.py: another summation order (tiles of four
+along K) and the hardware exp / rcp.  Every case's inputs satisfy e32 <= 2.5e-6 = cap / MULT (asserted before anything
+runs on the GPU).  Layer 0's kept im2col rows are exact copies of the pixels (b / 255 in fp32 for bytes), padded taps
+exact zeros.  With MARL_CONV_FWD_ERRORS=<file> in the environment the achieved errors, e32 and ratios of every case are
+written there as JSON; profiles/conv_fwd_errors.json is one such run.  Its worst err / max(MULT * e32, floor) * MULT (the
+bound is 4): 3.2 for rstd (worldstrat16, one row: eight values per group), 2.9 for U (custom4, two rows), 2.1 for Z_0, at
+most 2.0 for the deeper Z_l and the means, 1.7 for the deeper COLS_l; its largest error is 2.2e-6 of U's scale
+(worldstrat16, 2041 rows), 1.6e-6 for rstd, below 1e-6 for every Z_l and mean."""
+import ctypes as C
+import functools
+import json
+import os
+import re
+
+import pytest
+import torch as th
+import torch.nn.functional as F
+
+from tests.test_gpu_conv_bwd import PAD, SENTINEL, _embed, _Out, _rel
+
+pytestmark = pytest.mark.gpu
+
+CAP = 1e-5
+MULT = 4
+E32_MAX = CAP / MULT  # the condition on every case's inputs
+NB = 5  # distinct images of every case
+_errors = {}
+
+# ---- the grid (module level: tests/test_conv_plan_host.py reads it) --------------------------------------------------
+MNIST, RESISC = ([1, 8, 16], [2, 4]), ([3, 16, 32, 64], [2, 4, 8])
+AID, WORLDSTRAT = ([3, 16, 32, 64, 128], [2, 4, 8, 16]), ([3, 16, 32, 64, 128, 256], [2, 4, 8, 16, 32])
+# no CNN_SPECS model: a half-filled second 16-channel tile (20 = 16 + 4), 12 channels per group, four input channels;
+# its weight gradients are outside the activation-based kernel's range (512 % (cout / 4) != 0), so a training launch
+# keeps the im2col rows of both layers
+CUSTOM = ([4, 12, 20], [1, 5])
+# name: (channels, groups), window f, image H x W (non-square; positions 0 .. H - f - 1), knobs
+MODELS = {
+    "resisc12": (RESISC, 12, 28, 30, {}),
+    "mnist6": (MNIST, 6, 20, 22, {}),
+    "mnist12": (MNIST, 12, 28, 30, {}),
+    "aid24": (AID, 24, 40, 44, {}),
+    "aid32": (AID, 32, 44, 48, {}),
+    "mnist10": (MNIST, 10, 28, 30, {}),          # odd sides 5 -> 3
+    "mnist7": (MNIST, 7, 20, 22, {}),            # odd window
+    "resisc16": (RESISC, 16, 28, 30, {}),        # odd rb
+    "aid20": (AID, 20, 40, 44, {}),
+    "worldstrat16": (WORLDSTRAT, 16, 28, 30, {}),  # five layers, P = 1 in the last two, 32 groups
+    "custom9": (CUSTOM, 9, 20, 22, {}),
+    "custom4": (CUSTOM, 4, 12, 14, {}),          # the smallest configuration that keeps im2col rows (COLS_MIN)
+    "mnist6_general": (MNIST, 6, 20, 22, {"cnn_fwd2": 0}),
+    "aid24_general": (AID, 24, 40, 44, {"cnn_fwd3": 0}),
+}
+KNOB_TWIN = {"mnist6_general": "mnist6", "aid24_general": "aid24"}  # the specialised kernel of the same shape
+_K0 = [0, 0, 0, 0, 0]
+_KC = [1, 1, 0, 0, 0]  # custom9 in training mode
+
+
+def _w(which, rb, blocks, image=0, cols=_K0):
+    return dict(fused=1, which=which, rb=rb, blocks=blocks, keeps_cols=cols, writes_image=image)
+
+
+# model -> {rows: witness of the training launch}.  cnn_fwd2 (which 1..3): 2065 rows = 259 chunks of 8 on 256 workgroups,
+# workgroups 0..2 walk twice, the last chunk has one row.  cnn_fwd3 (4, 5): 1029 rows = 258 groups of 4 on 256
+# workgroups, a one-row last group.  General kernel (6): rb = 1, then 2 with a one-row last chunk (511 = 255 * 2 + 1),
+# then the largest rb inside the 52 KB cap that leaves 256 chunks, again with a one-row last chunk (2041 = 1 mod 2, 3,
+# 4, 5, 6, 8).
+GRID = {
+    "resisc12": {1: _w(1, 8, 1, 1), 9: _w(1, 8, 2, 1), 2065: _w(1, 8, 256, 1)},
+    "mnist6": {1: _w(2, 8, 1, 1), 9: _w(2, 8, 2, 1), 2065: _w(2, 8, 256, 1)},
+    "mnist12": {1: _w(3, 8, 1), 9: _w(3, 8, 2), 2065: _w(3, 8, 256)},
+    "aid24": {1: _w(4, 4, 1, 1), 5: _w(4, 4, 2, 1), 1029: _w(4, 4, 256, 1)},
+    "aid32": {1: _w(5, 4, 1, 1), 5: _w(5, 4, 2, 1), 1029: _w(5, 4, 256, 1)},
+    "mnist10": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 8, 256)},
+    "mnist7": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 8, 256)},
+    "resisc16": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 5, 409)},
+    "aid20": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 3, 681)},
+    "worldstrat16": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 4, 511)},
+    "custom9": {1: _w(6, 1, 1, cols=_KC), 511: _w(6, 2, 256, cols=_KC), 2041: _w(6, 8, 256, cols=_KC)},
+    "mnist6_general": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 8, 256)},
+    "aid24_general": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 2, 1021)},
+}
+# image forms, one model per kernel family (and the MnistCnn instantiation for the RGB-data case): model -> rows
+FORMS = {"resisc12": 9, "mnist6": 9, "aid24": 5, "mnist10": 511}
+# kept im2col rows: the scan's candidates beyond CNN_SPECS, (channels, groups) - windows 4..32 - what it must find, and
+# that configuration's cases {rows: witness} (rb = 1 at these row counts: 1 and rb + 1 rows)
+COLS_EXTRA = {"custom": CUSTOM}
+COLS_MIN = ("custom", 4, "custom4")
+COLS_GRID = {1: _w(6, 1, 1, cols=_KC), 2: _w(6, 1, 2, cols=_KC)}
+
+
+# ---- configurations and plans (host only) ----------------------------------------------------------------------------
+def config(stack, f, H, W, nb=NB, c_img=None, u8=0):
+    """marl_config of a conv stack: the rest of the model is as small as the library takes it"""
+    from marlclassification_amd._lib import MarlConfig
+
+    (ch, groups) = stack
+    cfg = MarlConfig()
+    cfg.nb_agents, cfg.batch, cfg.nb_steps = 1, nb, 1
+    cfg.img_c, cfg.img_h, cfg.img_w = (c_img or ch[0]), H, W
+    cfg.window, cfg.cnn_layers = f, len(groups)
+    for i, c in enumerate(ch):
+        cfg.cnn_ch[i] = c
+    for i, g in enumerate(groups):
+        cfg.cnn_groups[i] = g
+    cfg.n_b = cfg.n_a = cfg.n_m = cfg.n_m_o = cfg.n_d = cfg.nlb = cfg.nla = 8
+    cfg.nb_action, cfg.nb_class = 4, 4
+    for j, a in enumerate([[1, 0], [-1, 0], [0, 1], [0, -1]]):
+        cfg.actions[j][0], cfg.actions[j][1] = a
+    cfg.img_u8 = u8
+    return cfg
+
+
+def model_config(model, **kw):
+    stack, f, H, W, _ = MODELS[model]
+    return config(stack, f, H, W, **kw)
+
+
+def plan(cfg, train, rows):
+    from marlclassification_amd import _lib
+
+    p = _lib.CnnFwdPlan()
+    _lib.check(_lib.load().marl_cnn_fwd_plan(C.byref(cfg), train, rows, C.byref(p)))
+    return p.as_dict()
+
+
+class knobs:
+    """the knobs of a model for the length of a with block; the defaults (1) afterwards, whatever happens inside"""
+
+    def __init__(self, model):
+        self.k = MODELS[model][4]
+
+    def __enter__(self):
+        from marlclassification_amd import _lib
+
+        for k, v in self.k.items():
+            _lib.check(_lib.load().marl_tune(k.encode(), v))
+
+    def __exit__(self, *exc):
+        from marlclassification_amd import _lib
+
+        for k in self.k:
+            _lib.check(_lib.load().marl_tune(k.encode(), 1))
+
+
+def smallest_cols_config():
+    """the smallest configuration - by window, CNN_SPECS models first - whose fused training forward keeps the im2col
+    rows of some layer: (name, stack, window, keeps_cols), or None"""
+    from marlclassification_amd.engine import CNN_SPECS
+
+    for f in range(4, 33):
+        for name, stack in list(CNN_SPECS.items()) + list(COLS_EXTRA.items()):
+            p = plan(config(stack, f, f + 8, f + 10), 1, 1)
+            if p["fused"] and any(p["keeps_cols"]):
+                return name, stack, f, p["keeps_cols"]
+    return None
+
+
+# ---- data and the float64 / float32 references -----------------------------------------------------------------------
+def _seed(model, rows):
+    return 1000 * list(MODELS).index(model) + rows
+
+
+@functools.lru_cache(maxsize=None)
+def weights(stack_key):
+    """conv weights N(0, 1) / sqrt(K), bias and beta 0.1 N, gamma 1 + 0.1 N: [(w, b, gamma, beta)] per layer"""
+    ch, groups = stack_key
+    gen = th.Generator().manual_seed(sum((i + 1) * c for i, c in enumerate(ch)) + 7 * len(groups))
+    out = []
+    for l in range(len(groups)):
+        K = 9 * ch[l]
+        out.append((th.randn(ch[l + 1], ch[l], 3, 3, generator=gen) / K ** 0.5, 0.1 * th.randn(ch[l + 1], generator=gen),
+                    1 + 0.1 * th.randn(ch[l + 1], generator=gen), 0.1 * th.randn(ch[l + 1], generator=gen)))
+    return out
+
+
+def _key(stack):
+    return tuple(stack[0]), tuple(stack[1])
+
+
+def inputs(stack, f, H, W, rows, seed, u8=0, c_img=None):
+    """images (channels the model does not read are NaN), positions over the environment's range with the four corner
+    combinations of its two ends among the first rows, and the pixels as the reference reads them"""
+    cin = stack[0][0]
+    c_img = c_img or cin
+    gen = th.Generator().manual_seed(seed)
+    if u8:
+        img = th.randint(0, 256, (NB, c_img, H, W), generator=gen, dtype=th.uint8)
+        img64, img32 = img.double() / 255, img.float() / 255
+    else:
+        img = th.rand(NB, c_img, H, W, generator=gen)
+        img[:, cin:] = float("nan")
+        img64, img32 = img.double(), img
+    pos = th.stack([th.randint(0, H - f, (rows,), generator=gen), th.randint(0, W - f, (rows,), generator=gen)], 1)
+    ends = th.tensor([[H - f - 1, W - f - 1], [0, 0], [0, W - f - 1], [H - f - 1, 0]])
+    pos[:min(rows, 4)] = ends[:min(rows, 4)]
+    if rows >= 4:
+        assert {(0, 0), (0, W - f - 1), (H - f - 1, 0), (H - f - 1, W - f - 1)} <= {tuple(p) for p in pos.tolist()}
+    return img, pos.to(th.int32), img64, img32
+
+
+def crops(src, pos, rows, cin, f):
+    return th.stack([src[r % NB, :cin, pos[r, 0]:pos[r, 0] + f, pos[r, 1]:pos[r, 1] + f] for r in range(rows)])
+
+
+def forward(x, stack, dt, cols_of=()):
+    """{u, z<l>, mean<l>, rstd<l>, cols<l> for l in cols_of} of the extractor on patches x [rows][cin][f][f] in dtype dt"""
+    ch, groups = stack
+    rows = x.shape[0]
+    out = {}
+    x = x.to(dt)
+    for l, (w, b, gamma, beta) in enumerate(weights(_key(stack))):
+        if l in cols_of:  # [(r P + m)][tap * cin + ci]
+            u = F.unfold(x, 3, padding=1, stride=2)  # [rows][ci * 9 + tap][P]
+            out[f"cols{l}"] = u.view(rows, ch[l], 9, -1).permute(0, 3, 2, 1).reshape(-1, 9 * ch[l])
+        z = F.conv2d(x, w.to(dt), b.to(dt), stride=2, padding=1)
+        out[f"z{l}"] = z.permute(0, 2, 3, 1).reshape(rows, -1, ch[l + 1])
+        zz = z.reshape(rows, groups[l], -1)
+        out[f"mean{l}"] = zz.mean(-1)
+        out[f"rstd{l}"] = 1.0 / th.sqrt(zz.var(-1, unbiased=False) + 1e-5)
+        x = F.silu(F.group_norm(z, groups[l], gamma.to(dt), beta.to(dt), 1e-5))
+    out["u"] = x.reshape(rows, -1)
+    return out
+
+
+def kind(key):
+    """the output kind whose floor a key shares: u, z<l>, cols<l>, mean, rstd"""
+    return re.sub(r"\d", "", key) if key.startswith(("mean", "rstd")) else key
+
+
+_refs = {}
+
+
+def reference(model, rows, u8=0, c_img=None):
+    """(inputs, float64 outputs, e32 per output) of a case, computed once and never changed"""
+    k = (model, rows, u8, c_img)
+    if k not in _refs:
+        stack, f, H, W, _ = MODELS[model]
+        with knobs(model):
+            cols_of = [l for l, c in enumerate(plan(model_config(model), 1, rows)["keeps_cols"]) if c]
+        data = inputs(stack, f, H, W, rows, _seed(model, rows) + 17 * u8 + (c_img or 0), u8, c_img)
+        _, pos, img64, img32 = data
+        r64 = forward(crops(img64, pos, rows, stack[0][0], f), stack, th.float64, cols_of)
+        r32 = forward(crops(img32, pos, rows, stack[0][0], f), stack, th.float32, cols_of)
+        e32 = {key: _rel(r32[key], r64[key]) for key in r64}
+        assert all(v <= E32_MAX for v in e32.values()), (k, e32)
+        _refs[k] = (data, r64, e32)
+    return _refs[k]
+
+
+def grid_cases():
+    return [(m, r) for m in GRID for r in GRID[m]]
+
+
+@functools.lru_cache(maxsize=None)
+def grid_floor():
+    """the worst e32 of the whole grid per output kind; computing it asserts e32 <= 2.5e-6 for every case"""
+    floor = {}
+    for m, r in grid_cases():
+        for key, v in reference(m, r)[2].items():
+            floor[kind(key)] = max(floor.get(kind(key), 0.0), v)
+    return floor
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _error_record():
+    yield
+    path = os.environ.get("MARL_CONV_FWD_ERRORS")
+    if path and _errors:
+        worst = {}
+        for e in _errors.values():
+            for k, v in e.get("ratio", {}).items():
+                worst[kind(k)] = max(worst.get(kind(k), 0.0), v)
+        with open(path, "w") as f:
+            json.dump({"cap_rel_to_max": CAP, "multiple_of_e32": MULT, "floor_worst_e32_of_the_grid": grid_floor(),
+                       "worst_ratio_err_over_max_of_e32_and_floor": worst, "cases": _errors}, f, indent=1,
+                      sort_keys=True)
+
+
+# ---- the launch ------------------------------------------------------------------------------------------------------
+_packed = {}
+
+
+def packed_weights(device, model):
+    """the weights workspace of a model as marl_pack_weights writes it into a zeroed buffer (once per stack and window:
+    the layout does not move with the image, the batch or these knobs)"""
+    from marlclassification_amd import _lib
+
+    stack, f = MODELS[model][:2]
+    k = _key(stack) + (f,)
+    if k not in _packed:
+        lib = _lib.load()
+        cfg = model_config(model)
+        wb = C.c_size_t(0)
+        _lib.check(lib.marl_workspace_sizes(C.byref(cfg), 1, C.byref(wb), None))
+        gen = th.Generator().manual_seed(5)
+        table, keep = (C.c_void_p * _lib.MARL_NPARAMS)(), []
+        conv = weights(_key(stack))
+        for i in range(_lib.MARL_NPARAMS):
+            n = lib.marl_param_numel(C.byref(cfg), i)
+            if n > 0:
+                t = conv[i // 4][i % 4].reshape(-1) if i < 20 else 0.1 * th.randn(n, generator=gen)
+                assert t.numel() == n
+                keep.append(t.contiguous().to(device))
+                table[i] = keep[-1].data_ptr()
+        wws = th.zeros(wb.value // 4, device=device)
+        _lib.check(lib.marl_pack_weights(C.byref(cfg), table, wws.data_ptr(), wb.value, None))
+        th.cuda.synchronize()
+        _packed[k] = wws
+    return _packed[k]
+
+
+class _OutCols(_Out):
+    """an output of [n][ld] whose columns [keep, ld) nobody has to write: U (the decoder and the sampling launch own
+    [nf, ldu): the sentinels there must survive) and COLS_0 (columns K .. ldk - 1, see test_kept_im2col_rows)"""
+
+    def __init__(self, n, ld, keep, device, rest_untouched):
+        super().__init__((n, ld), device)
+        self.keep, self.rest_untouched = keep, rest_untouched
+
+    def get(self):
+        b = self.buf.cpu()
+        assert th.all(b[:PAD] == SENTINEL) and th.all(b[PAD + self.n:] == SENTINEL), "wrote outside the tensor"
+        inner = b[PAD:PAD + self.n].reshape(self.shape)
+        assert not th.any(inner[:, :self.keep] == SENTINEL), "left part of the tensor unwritten"
+        if self.rest_untouched:
+            assert th.all(inner[:, self.keep:] == SENTINEL), "wrote columns of the row that are not its own"
+        return inner.clone()
+
+
+def launch(device, model, rows, data, *, train=1, u8=0, c_img=None, obs=None, ldu_extra=8, u3=None, want=None):
+    """marl_cnn_fwd on `data` - twice, bit-identical, sentinels checked - with the buffers a training (train = 1: Z,
+    GST, and COLS where the plan keeps them) or a rollout launch has.  Returns ({key: tensor}, plan)."""
+    from marlclassification_amd import _lib
+
+    lib = _lib.load()
+    stack, f, H, W, _ = MODELS[model]
+    ch, groups = stack
+    L = len(groups)
+    cfg = model_config(model, c_img=c_img, u8=u8)
+    p = plan(cfg, train, rows)
+    if want is not None:
+        assert p == want, (p, want)
+    img, pos = data[0], data[1]
+    hw = [f]
+    for l in range(L):
+        hw.append((hw[-1] - 1) // 2 + 1)
+    P = [hw[l + 1] ** 2 for l in range(L)]
+    nf = ch[L] * P[L - 1]
+    ldu = nf + ldu_extra
+    io = _lib.CnnFwdIo()
+    keepalive = []
+    if obs is not None:
+        keepalive.append(_embed(obs, device))
+        io.obs = keepalive[-1][1].data_ptr()
+    else:
+        keepalive += [_embed(img, device), _embed(pos, device)]
+        io.img, io.pos = keepalive[0][1].data_ptr(), keepalive[1][1].data_ptr()
+    io.rows = rows
+    outs = {"u": _OutCols(rows, ldu, nf, device, True)}
+    io.u, io.ldu = outs["u"].ptr(), ldu
+    if train:
+        for l in range(L):
+            outs[f"z{l}"] = _Out((rows, P[l], ch[l + 1]), device)
+            outs[f"gst{l}"] = _Out((rows, groups[l], 2), device)
+            io.z[l], io.gst[l] = outs[f"z{l}"].ptr(), outs[f"gst{l}"].ptr()
+            if p["keeps_cols"][l]:
+                K = 9 * ch[l]
+                outs[f"cols{l}"] = _OutCols(rows * P[l], (K + 3) & ~3, K, device, False)
+                io.cols[l] = outs[f"cols{l}"].ptr()
+    if u3 is not None:
+        io.u3, io.u3_row0, io.u3_steps = u3
+    wws = packed_weights(device, model)
+    res = []
+    for _ in range(2):
+        for o in outs.values():
+            o.reset()
+        _lib.check(lib.marl_cnn_fwd(C.byref(cfg), wws.data_ptr(), wws.numel() * 4, C.byref(io), None))
+        th.cuda.synchronize()
+        res.append({k: o.get() for k, o in outs.items()})
+    for k in outs:
+        assert th.equal(res[0][k], res[1][k]), f"two runs differ in {k}"
+    got = dict(res[0])
+    got["u"] = got["u"][:, :nf]
+    for l in range(L):
+        if f"gst{l}" in got:
+            g = got.pop(f"gst{l}")
+            got[f"mean{l}"], got[f"rstd{l}"] = g[..., 0], g[..., 1]
+    return got, p
+
+
+def check_bounds(name, got, r64, e32, extra=None):
+    floor = grid_floor()
+    e = {"err": {}, "e32": {}, "ratio": {}}
+    for k in got:
+        if k == "cols0":
+            continue
+        bound = max(MULT * e32[k], floor[kind(k)])
+        e["err"][k], e["e32"][k] = _rel(got[k], r64[k]), e32[k]
+        e["ratio"][k] = e["err"][k] / bound * MULT
+    e.update(extra or {})
+    _errors[name] = e
+    print(name, e)
+    for k, v in e["err"].items():
+        assert v <= CAP, (k, v)
+        assert v <= max(MULT * e32[k], floor[kind(k)]), (k, v, e32[k], floor[kind(k)])
+
+
+def check_cols0(got, data, stack, f, rows, u8):
+    """layer 0's kept rows: bit-exact copies of the pixels (b.float() / 255 for bytes), exact zeros at padded taps;
+    columns K .. ldk - 1 are not compared (see test_kept_im2col_rows)"""
+    cin = stack[0][0]
+    x = crops(data[3] if u8 else data[0], data[1], rows, cin, f)
+    u = F.unfold(x, 3, padding=1, stride=2)
+    want = u.view(rows, cin, 9, -1).permute(0, 3, 2, 1).reshape(-1, 9 * cin)
+    assert th.equal(got[:, :9 * cin], want), "layer 0's im2col rows are no exact copies of the pixels"
+
+
+# ---- the grid --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("model,rows", grid_cases(), ids=[f"{m}-{r}" for m, r in grid_cases()])
+def test_forward_grid(device, model, rows):
+    stack, f, H, W, _ = MODELS[model]
+    data, r64, e32 = reference(model, rows)
+    with knobs(model):
+        got, p = launch(device, model, rows, data, want=GRID[model][rows])
+    if rows > p["rb"]:  # a ragged one-row last chunk
+        assert rows % p["rb"] == 1
+    if rows > 1000 and p["which"] != 6:  # the persistent walk: fewer workgroups than chunks
+        assert p["blocks"] == 256 < -(-rows // p["rb"])
+    if "cols0" in got:
+        check_cols0(got["cols0"], data, stack, f, rows, 0)
+    check_bounds(f"grid {model} rows={rows}", got, r64, e32, {"which": p["which"], "rb": p["rb"], "blocks": p["blocks"]})
+    if model in KNOB_TWIN:  # the general kernel against the specialised one of the same shape
+        twin, _ = launch(device, KNOB_TWIN[model], rows, data)
+        floor = grid_floor()
+        for k in got:
+            d = (got[k].double() - twin[k].double()).abs().max().item() / r64[k].abs().max().item()
+            assert d <= min(CAP, max(MULT * e32[k], floor[kind(k)])), (k, d)
+
+
+def test_kept_im2col_rows(device):
+    """The smallest configuration whose fused training forward keeps im2col rows (found by the scan, so a plan rule
+    that starts or stops keeping rows elsewhere fails tests/test_conv_plan_host.py), at 1 and rb + 1 rows; the custom
+    stack of the grid runs the same checks at 511 and 2041 rows.  Layer 0's rows are exact pixels and exact zeros,
+    deeper layers fall within the bound.  The consumer of COLS_l is the weight-gradient GEMM of the episode backward,
+    tn(dZ_l, cout, COLS_l, ldk, .., ni = cout, nj = K, rows): it contracts columns [0, K) only; columns K .. ldk - 1
+    (layer 0 with 9 cin % 4 != 0 only) are loaded with the last float4 of a row and meet products that are never
+    stored, so all the consumer needs of them is that they lie inside the buffer - which the sentinel frame shows -
+    and this test asserts nothing about their contents.  (The configurations that keep rows today read four input
+    channels: K = 36 = ldk, there are no such columns.)"""
+    name, stack, f, keeps = smallest_cols_config()
+    model = COLS_MIN[2]
+    assert (name, f) == COLS_MIN[:2] and MODELS[model][:2] == (stack, f) and keeps == _KC
+    assert sorted(COLS_GRID) == [1, plan(model_config(model), 1, 1)["rb"] + 1]
+    for rows, want in COLS_GRID.items():
+        data, r64, e32 = reference(model, rows)
+        got, p = launch(device, model, rows, data, want=want)
+        assert "cols0" in got and "cols1" in got
+        check_cols0(got["cols0"], data, stack, f, rows, 0)
+        check_bounds(f"cols {model} rows={rows}", got, r64, e32)
+
+
+# ---- image forms -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("model", list(FORMS))
+def test_uint8_images(device, model):
+    """bytes, converted on the fly, against float64 of x / 255"""
+    rows = FORMS[model]
+    data, r64, e32 = reference(model, rows, u8=1)
+    got, p = launch(device, model, rows, data, u8=1, want=GRID[model][rows])
+    check_bounds(f"uint8 {model} rows={rows}", got, r64, e32)
+
+
+@pytest.mark.parametrize("model", ["mnist6", "mnist10"])
+def test_unread_image_channels(device, model):
+    """MnistCnn on RGB data reads channel 0: channels 1 and 2 are NaN, and the result is, bit for bit, that of the
+    one-channel images holding the same pixels"""
+    rows = FORMS[model]
+    data, r64, e32 = reference(model, rows, c_img=3)
+    assert data[0].shape[1] == 3 and th.isnan(data[0][:, 1:]).all() and not th.isnan(data[0][:, 0]).any()
+    got3, _ = launch(device, model, rows, data, c_img=3, want=GRID[model][rows])
+    check_bounds(f"c_img3 {model} rows={rows}", got3, r64, e32)
+    got1, _ = launch(device, model, rows, (data[0][:, :1].contiguous(), data[1]))
+    for k in got1:
+        assert th.equal(got1[k], got3[k]), k
+
+
+@pytest.mark.parametrize("model", list(FORMS))
+def test_patches_and_rollout_forms(device, model):
+    """obs holding the exact fp32 crops gives U, Z and GST bit-identical to the img + pos call; a rollout launch (nothing
+    kept) gives U bit-identical to the training launch wherever which and rb agree between the two plans"""
+    rows = FORMS[model]
+    stack, f, H, W, _ = MODELS[model]
+    data, _, _ = reference(model, rows)
+    got, p = launch(device, model, rows, data, want=GRID[model][rows])
+    obs = crops(data[0], data[1], rows, stack[0][0], f).contiguous()
+    got_obs, _ = launch(device, model, rows, data, obs=obs, want=GRID[model][rows])
+    assert set(got_obs) == set(got)
+    for k in got:
+        assert th.equal(got[k], got_obs[k]), f"obs form differs in {k}"
+    got_roll, p0 = launch(device, model, rows, data, train=0)
+    assert set(got_roll) == {"u"} and (p0["which"], p0["rb"]) == (p["which"], p["rb"])
+    assert th.equal(got_roll["u"], got["u"]), "rollout and training launch differ in U"
+
+
+@pytest.mark.parametrize("model,rows,row0", [("resisc12", 9, 0), ("mnist6", 9, 32), ("aid24", 5, 0), ("aid32", 5, 0)])
+def test_u_image(device, model, rows, row0):
+    """where the plan writes the k16 image of U: pre-filled with the image of an all-zero [row0 + rows][ldu] matrix, it
+    must afterwards be byte-equal to marl_image_build of the U just written (other rows and columns zero)"""
+    from marlclassification_amd import _lib
+
+    lib = _lib.load()
+    data, _, _ = reference(model, rows)
+    assert GRID[model][rows]["writes_image"] == 1
+    got, _ = launch(device, model, rows, data)
+    nf = got["u"].shape[1]
+    k = nf + 24  # (columns the decoder and the sampling launch would fill: zero here)
+    nbytes = lib.marl_image_bytes(row0 + rows, k)
+
+    def image_of(mat):
+        m = mat.to(device).contiguous()
+        out = th.full((nbytes + 2 * 4 * PAD,), 0x5A, dtype=th.uint8, device=device)
+        _lib.check(lib.marl_image_build(m.data_ptr(), m.shape[1], m.shape[0], k, out.data_ptr() + 4 * PAD, None))
+        th.cuda.synchronize()
+        return out
+
+    buf = image_of(th.zeros(row0 + rows, k))
+    got2, _ = launch(device, model, rows, data, u3=(buf.data_ptr() + 4 * PAD, row0, -(-k // 16)))
+    assert th.equal(got2["u"], got["u"])
+    full = th.zeros(row0 + rows, k)
+    full[row0:, :nf] = got["u"]
+    assert th.equal(buf.cpu(), image_of(full).cpu()), "the image of U differs from marl_image_build of U"
+
+
+def test_guards(device):
+    """a null u, a workspace that is too small and a model the fused forward refuses return their codes with every
+    sentinel untouched"""
+    from marlclassification_amd import _lib
+
+    lib = _lib.load()
+    stack, f, H, W, _ = MODELS["mnist10"]
+    data, _, _ = reference("mnist10", 1)
+    wws = packed_weights(device, "mnist10")
+    out = th.full((1 << 14,), SENTINEL, device=device)
+    keep = [_embed(data[0], device), _embed(data[1], device)]
+
+    def call(cfg, u=out.data_ptr() + 4 * PAD, wbytes=wws.numel() * 4, img=keep[0][1].data_ptr(), ldu=152):
+        io = _lib.CnnFwdIo()
+        io.img, io.pos, io.rows, io.u, io.ldu = img, keep[1][1].data_ptr(), 1, u, ldu
+        return lib.marl_cnn_fwd(C.byref(cfg), wws.data_ptr(), wbytes, C.byref(io), None)
+
+    cfg = model_config("mnist10")
+    assert call(cfg, u=None) == -1 and call(cfg, img=None) == -1
+    assert call(cfg, ldu=140) == -1 and call(cfg, ldu=146) == -1  # (nf = 144: too narrow, no multiple of 4)
+    assert call(cfg, wbytes=wws.numel() * 4 - 4) == -4
+    # one channel per group: a float4 of the normalisation would straddle groups - the episode takes its GEMM path
+    refused = config(([1, 8, 16], [8, 4]), f, H, W)
+    assert plan(refused, 1, 1)["fused"] == 0 and call(refused) == -2
+    assert lib.marl_cnn_fwd(C.byref(cfg), wws.data_ptr(), wws.numel() * 4, None, None) == -1
+    th.cuda.synchronize()
+    assert th.all(out == SENTINEL), "a refused call wrote"
+    assert call(cfg) == 0
+    th.cuda.synchronize()
+    assert not th.any(out[PAD:PAD + 144] == SENTINEL) and th.all(out[PAD + 144:] == SENTINEL)
