@@ -84,11 +84,25 @@ struct GemmSeg {
     const float* a;
     const float* b;
     int lda, ldb, k;
-    // filled by the bf16x6 launcher when b is a registered weight matrix: its pre-split image
-    // [row][k / 32][plane][32] bf16 and the number of 32-deep K tiles per row
+    // b's pre-split image [row][k / 32][plane][32] bf16 and its 32-deep K tiles per row, as the caller's
+    // GemmB stated them (null: none, the bf16x6 kernels split b while they stage it)
     const void* b3;
     int kt3;
 };
+
+// The B operand of one segment: [rows][ld] fp32 with k valid columns, and its pre-split image where the
+// caller holds one (the weight copies: marl_pack_weights writes it next to them).
+struct GemmB {
+    const float* b;
+    int ld, k;
+    const void* b3;  // null: no image
+    int kt3;
+    GemmB from_row(int row0) const {
+        return GemmB{b + (size_t)row0 * ld, ld, k,
+                     b3 ? static_cast<const char*>(b3) + (size_t)row0 * kt3 * 192 : nullptr, kt3};
+    }
+};
+inline GemmB gemm_b(const float* b, int ld, int k) { return GemmB{b, ld, k, nullptr, 0}; }
 
 struct GemmProb {
     GemmSeg seg[2];
@@ -135,9 +149,9 @@ __device__ __forceinline__ void xcd_tile(unsigned gx, unsigned gy, unsigned gz, 
 }
 int xcd_map_enabled();
 
-GemmProb gemm_prob(const float* a, int lda, const float* b, int ldb, int k, float* c, int ldc,
-                   int m, int n, const float* bias = nullptr, int accumulate = 0);
-void gemm_add_seg(GemmProb& p, const float* a, int lda, const float* b, int ldb, int k);
+GemmProb gemm_prob(const float* a, int lda, const GemmB& b, float* c, int ldc, int m, int n,
+                   const float* bias = nullptr, int accumulate = 0);
+void gemm_add_seg(GemmProb& p, const float* a, int lda, const GemmB& b);
 
 int launch_gemm_nt(const GemmBatch& batch, hipStream_t st);
 // LSTM cell: gates = seg products + bias over 4*n_units rows of B, then the cell update.
@@ -161,15 +175,7 @@ struct SplitBatch {
     int count;
 };
 int launch_split_weights(const SplitBatch& b, hipStream_t st);
-// host-side table fp32 copy -> image, rebuilt by every entry point that lays out the weights
-// workspace; the launchers look the B operands of a product up in it
-void split_registry_reset();
-void split_registry_add(const float* base, int rows, int ld, int k, const void* image);
-struct SplitRegistryScope {  // clears the table when the registering entry point returns
-    SplitRegistryScope() = default;
-    SplitRegistryScope(const SplitRegistryScope&) = delete;
-    ~SplitRegistryScope() { split_registry_reset(); }
-};
+// The NT launchers take the image-copying kernels when every segment of the batch carries an image (GemmB).
 int launch_gemm_nt_split(const GemmBatch& batch, int max_m, int max_n, int64_t blocks128, hipStream_t st);
 int launch_gemm_lstm_split(const GemmBatch& batch, int max_m, int max_n, hipStream_t st);
 int launch_gemm_tn_split(const float* a, int lda, const float* b, int ldb, float* out, int ldo,

@@ -639,6 +639,16 @@ struct Ctx {
     char* img(size_t off) const { return reinterpret_cast<char*>(E + off); }
     const float* wp(int i) const { return W + w.wp[i]; }
     const float* wt(int i) const { return W + w.wt[i]; }
+    // the packed [n, k] / transposed [k, n] copy of matrix i as the B operand of a product, with the image
+    // marl_pack_weights wrote next to it (a conv weight has none)
+    GemmB wpB(int i) const {
+        const ParamMeta m = param_meta(d, i);
+        return GemmB{wp(i), w.ldp[i], m.k, m.kind == PK_MATRIX ? W + w.wp3[i] : nullptr, (m.k + 31) / 32};
+    }
+    GemmB wtB(int i) const {
+        const ParamMeta m = param_meta(d, i);
+        return GemmB{wt(i), w.ldt[i], m.n, m.kind == PK_MATRIX ? W + w.wt3[i] : nullptr, (m.n + 31) / 32};
+    }
     // fragment-order copies for the panel kernels (null: this model has none - the launchers refuse)
     const float* wpf(int i) const { return w.wpf[i] ? W + w.wpf[i] : nullptr; }
     const float* wtf(int i) const { return w.wtf[i] ? W + w.wtf[i] : nullptr; }
@@ -658,7 +668,6 @@ struct Ctx {
     float* DHCs(int t) const { return E + e.DHC + (size_t)t * d.R * d.ld_na; }
 };
 
-static void register_split_images(const Dims& d, const WLayout& w, const float* W);
 static bool use_panels(const Dims& d);
 
 // marl_comm_matrix: the caller-owned [na, na] mixing matrix of the message exchange (row = receiver), or null =
@@ -706,7 +715,6 @@ static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void
         set_error("workspaces must be 256-byte aligned");
         return MARL_EINVAL;
     }
-    register_split_images(c.d, c.w, c.W);
     // the three kernels that write U[t] (fused CNN: features; decoder panel: message columns; sampling
     // launch: position embedding) also write its image when all of them are on the path and the column
     // ranges keep 8-byte image pieces whole; else (and for step 0, whose embedding comes from the
@@ -837,7 +845,7 @@ static int step_cnn(const Ctx& c, int t, const StepIn& in) {
     for (int l = 0; l < d.L; ++l) {
         const int co = d.ch[l + 1];
         const int64_t rows = d.R * d.P[l];
-        MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.COLS[l], t), d.ldk[l], c.wp(4 * l), d.ldk[l], d.K[l],
+        MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.COLS[l], t), d.ldk[l], c.wpB(4 * l),
                                     c.at(c.e.Z[l], t), co, (int)rows, co, c.wp(4 * l + 1))));
         if (l + 1 < d.L && gn_fwd_im2col_supported(d.P[l], co)) {
             // GroupNorm + SiLU + the next layer's im2col in one pass (A_l is never materialised)
@@ -930,12 +938,12 @@ static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, 
         MARL_TRY(mix_msg(c, t, c.MSGs(t), c.at(c.e.MBAR, t), d.n_m, 0));
     else
         MARL_TRY(launch_agg_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.n_m, st));
-    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.MBAR, t), d.ld_nm, c.wp(MARL_P_DEC_W0), p4(d.n_m), d.n_m,
+    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.MBAR, t), d.ld_nm, c.wpB(MARL_P_DEC_W0),
                                 c.at(c.e.ZD1, t), d.ld_nm2, R, d.nm2, c.wp(MARL_P_DEC_B0))));
     MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZD1, t), d.ld_nm2, c.wp(MARL_P_DEC_LN0W),
                                 c.wp(MARL_P_DEC_LN0B), c.at(c.e.AD1, t), d.ld_nm2,
                                 c.at(c.e.STD1, t), d.R, d.nm2, st));
-    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AD1, t), d.ld_nm2, c.wp(MARL_P_DEC_W1), d.ld_nm2, d.nm2,
+    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AD1, t), d.ld_nm2, c.wpB(MARL_P_DEC_W1),
                                 c.at(c.e.ZD2, t), d.ld_nmo, R, d.n_mo, c.wp(MARL_P_DEC_B1))));
     return launch_ln_silu_fwd(c.at(c.e.ZD2, t), d.ld_nmo, c.wp(MARL_P_DEC_LN1W),
                               c.wp(MARL_P_DEC_LN1B), c.at(c.e.U, t) + d.nf, d.ld_nin,
@@ -994,9 +1002,8 @@ static int step_pos_lstm(const Ctx& c, int t, const StepIn& in, bool pos_done = 
     GemmBatch b{};
     b.count = 2;
     GemmProb& pb = b.p[0];
-    pb = gemm_prob(c.at(c.e.U, t), d.ld_nin, c.wp(MARL_P_LB_WIH), d.ld_nin, d.nin, nullptr, 0, R,
-                   d.n_b, c.W + c.w.bsum_b);
-    gemm_add_seg(pb, c.Hs(t), d.ld_nb, c.wp(MARL_P_LB_WHH), d.ld_nb, d.n_b);
+    pb = gemm_prob(c.at(c.e.U, t), d.ld_nin, c.wpB(MARL_P_LB_WIH), nullptr, 0, R, d.n_b, c.W + c.w.bsum_b);
+    gemm_add_seg(pb, c.Hs(t), d.ld_nb, c.wpB(MARL_P_LB_WHH));
     pb.c_prev = c.Cs(t);
     pb.h_next = c.Hs(t + 1);
     pb.c_next = c.Cs(t + 1);
@@ -1004,9 +1011,8 @@ static int step_pos_lstm(const Ctx& c, int t, const StepIn& in, bool pos_done = 
     pb.ld_state = d.ld_nb;
     pb.ld_gates = d.ld_gb;
     GemmProb& pa = b.p[1];
-    pa = gemm_prob(c.at(c.e.U, t), d.ld_nin, c.wp(MARL_P_LA_WIH), d.ld_nin, d.nin, nullptr, 0, R,
-                   d.n_a, c.W + c.w.bsum_a);
-    gemm_add_seg(pa, c.HCs(t), d.ld_na, c.wp(MARL_P_LA_WHH), d.ld_na, d.n_a);
+    pa = gemm_prob(c.at(c.e.U, t), d.ld_nin, c.wpB(MARL_P_LA_WIH), nullptr, 0, R, d.n_a, c.W + c.w.bsum_a);
+    gemm_add_seg(pa, c.HCs(t), d.ld_na, c.wpB(MARL_P_LA_WHH));
     pa.c_prev = c.CCs(t);
     pa.h_next = c.HCs(t + 1);
     pa.c_next = c.CCs(t + 1);
@@ -1060,9 +1066,9 @@ static int step_encode_policy(const Ctx& c, int t) {
         return launch_panel_fwd(pb, st);
     }
     MARL_TRY(gemm2(c,
-                   gemm_prob(c.Hs(t + 1), d.ld_nb, c.wp(MARL_P_ENC_W0), d.ld_nb, d.n_b,
+                   gemm_prob(c.Hs(t + 1), d.ld_nb, c.wpB(MARL_P_ENC_W0),
                              c.at(c.e.ZE1, t), d.ld_nm2, R, d.nm2, c.wp(MARL_P_ENC_B0)),
-                   gemm_prob(c.HCs(t + 1), d.ld_na, c.wp(MARL_P_POL_W0), d.ld_na, d.n_a,
+                   gemm_prob(c.HCs(t + 1), d.ld_na, c.wpB(MARL_P_POL_W0),
                              c.at(c.e.ZP1, t), d.ld_nla, R, d.nla, c.wp(MARL_P_POL_B0))));
     MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZP1, t), d.ld_nla, c.wp(MARL_P_POL_LNW),
                                 c.wp(MARL_P_POL_LNB), c.at(c.e.AP1, t), d.ld_nla,
@@ -1070,9 +1076,8 @@ static int step_encode_policy(const Ctx& c, int t) {
     MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZE1, t), d.ld_nm2, c.wp(MARL_P_ENC_LN0W),
                                 c.wp(MARL_P_ENC_LN0B), c.at(c.e.AE1, t), d.ld_nm2,
                                 c.at(c.e.STE1, t), d.R, d.nm2, st));
-    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AE1, t), d.ld_nm2, c.wp(MARL_P_ENC_W1), d.ld_nm2,
-                                d.nm2, c.at(c.e.ZE2, t), d.ld_nm, R, d.n_m,
-                                c.wp(MARL_P_ENC_B1))));
+    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AE1, t), d.ld_nm2, c.wpB(MARL_P_ENC_W1), c.at(c.e.ZE2, t), d.ld_nm, R,
+                                d.n_m, c.wp(MARL_P_ENC_B1))));
     return launch_ln_silu_fwd(c.at(c.e.ZE2, t), d.ld_nm, c.wp(MARL_P_ENC_LN1W),
                               c.wp(MARL_P_ENC_LN1B), c.MSGs(t + 1), d.ld_nm,
                               c.at(c.e.STE2, t), d.R, d.n_m, st);
@@ -1149,9 +1154,9 @@ static int heads_batched(const Ctx& c, int t0, int64_t rows, float* values, floa
         MARL_TRY(launch_gemm_nt3(g, st));
     } else
     MARL_TRY(gemm2(c,
-                   gemm_prob(c.HCs(t0 + 1), d.ld_na, c.wp(MARL_P_CRI_W0), d.ld_na, d.n_a,
+                   gemm_prob(c.HCs(t0 + 1), d.ld_na, c.wpB(MARL_P_CRI_W0),
                              c.at(c.e.ZC1), d.ld_nla, (int)rows, d.nla, c.wp(MARL_P_CRI_B0)),
-                   gemm_prob(c.Hs(t0 + 1), d.ld_nb, c.wp(MARL_P_PRE_W0), d.ld_nb, d.n_b,
+                   gemm_prob(c.Hs(t0 + 1), d.ld_nb, c.wpB(MARL_P_PRE_W0),
                              c.at(c.e.ZQ1), d.ld_nlb, (int)rows, d.nlb, c.wp(MARL_P_PRE_B0))));
     const bool vdot = d.nla <= 384;  // the critic's output layer rides in the LayerNorm kernel
     MARL_TRY(launch_ln_silu_fwd(c.at(c.e.ZC1), d.ld_nla, c.wp(MARL_P_CRI_LNW), c.wp(MARL_P_CRI_LNB),
@@ -1162,7 +1167,7 @@ static int heads_batched(const Ctx& c, int t0, int64_t rows, float* values, floa
     if (!vdot)
         MARL_TRY(launch_rowdot(c.at(c.e.AC1), d.ld_nla, c.wp(MARL_P_CRI_W1), c.wp(MARL_P_CRI_B1),
                                values, rows, d.nla, st));
-    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AQ1), d.ld_nlb, c.wp(MARL_P_PRE_W1), d.ld_nlb, d.nlb,
+    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.AQ1), d.ld_nlb, c.wpB(MARL_P_PRE_W1),
                                 preds, d.nC, (int)rows, d.nC, c.wp(MARL_P_PRE_B1))));
     return MARL_OK;
 }
@@ -1336,17 +1341,6 @@ static int pack_weights(const Dims& d, const WLayout& w, const float* const* par
         ib.d[ib.count++] = ImgDesc{W + w.wt[i], W + w.wt3k[i], m.k, m.n, w.ldt[i]};
     }
     return launch_images(ib, st);
-}
-
-// tells the bf16x6 launchers where the image of each fp32 weight copy lives
-static void register_split_images(const Dims& d, const WLayout& w, const float* W) {
-    split_registry_reset();
-    for (int i = 0; i < MARL_NPARAMS; ++i) {
-        const ParamMeta m = param_meta(d, i);
-        if (m.kind != PK_MATRIX) continue;
-        split_registry_add(W + w.wp[i], m.n, w.ldp[i], m.k, W + w.wp3[i]);
-        split_registry_add(W + w.wt[i], m.k, w.ldt[i], m.n, W + w.wt3[i]);
-    }
 }
 
 // which: 0 every parameter, 1 only the heads' matrices (MARL_P_POL_W0 .. MARL_P_PRE_B1: final before the reverse loop -
@@ -1602,7 +1596,7 @@ static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, con
         // patch positions of the first convolution's weight gradient: every patch at (0, 0) of its own image
         MARL_TRY(launch_fill(reinterpret_cast<float*>(c.POSs(0)), d.R * 2, 0.f, st));
     }
-    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.GPRED), d.ld_nC, c.wt(MARL_P_PRE_W1), p4(d.nC), d.nC,
+    MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.GPRED), d.ld_nC, c.wtB(MARL_P_PRE_W1),
                                 c.at(c.e.DAQ1), d.ld_nlb, (int)NR, d.nlb)));
     MARL_TRY(tn(c, c.at(c.e.GPRED), d.ld_nC, c.at(c.e.AQ1), d.ld_nlb, MARL_P_PRE_W1, d.nC, d.nlb, NR, grads[MARL_P_PRE_B1]));
     MARL_TRY(ln_bwd(c, c.at(c.e.DAQ1), d.ld_nlb, c.at(c.e.ZQ1), d.ld_nlb, c.at(c.e.STQ1),
@@ -1615,7 +1609,7 @@ static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, con
                              c.at(c.e.STC1), MARL_P_CRI_LNW, MARL_P_CRI_LNB, NR, d.nla, grads,
                              c.at(c.e.DAC1), d.ld_nla));
     } else {
-        MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.DVAL), 4, c.wt(MARL_P_CRI_W1), 4, 1, c.at(c.e.DAC1),
+        MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.DVAL), 4, c.wtB(MARL_P_CRI_W1), c.at(c.e.DAC1),
                                     d.ld_nla, (int)NR, d.nla)));
         MARL_TRY(ln_bwd(c, c.at(c.e.DAC1), d.ld_nla, c.at(c.e.ZC1), d.ld_nla, c.at(c.e.STC1),
                         MARL_P_CRI_LNW, MARL_P_CRI_LNB, NR, d.nla, grads, 0));
@@ -1635,7 +1629,7 @@ static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, con
                              d.ld_nla, c.at(c.e.STP1, 0), MARL_P_POL_LNW, MARL_P_POL_LNB, NR, d.nla,
                              grads, c.at(c.e.DAP1), d.ld_nla));
     } else {
-        MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.DLOG), d.ld_nA, c.wt(MARL_P_POL_W1), p4(d.nA), d.nA,
+        MARL_TRY(gemm1(c, gemm_prob(c.at(c.e.DLOG), d.ld_nA, c.wtB(MARL_P_POL_W1),
                                     c.at(c.e.DAP1), d.ld_nla, (int)NR, d.nla)));
         MARL_TRY(ln_bwd(c, c.at(c.e.DAP1), d.ld_nla, c.at(c.e.ZP1, 0), d.ld_nla, c.at(c.e.STP1, 0),
                         MARL_P_POL_LNW, MARL_P_POL_LNB, NR, d.nla, grads, 0));
@@ -1643,11 +1637,9 @@ static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, con
     MARL_TRY(tn(c, c.at(c.e.DAP1), d.ld_nla, c.HCs(1), d.ld_na, MARL_P_POL_W0, d.nla, d.n_a, NR, grads[MARL_P_POL_B0]));
     // gradients reaching h_t / h^_t from the heads, all steps at once
     {
-        GemmProb ph = gemm_prob(c.at(c.e.DAQ1), d.ld_nlb, c.wt(MARL_P_PRE_W0), d.ld_nlb, d.nlb,
-                                c.DHs(1), d.ld_nb, (int)NR, d.n_b);
-        GemmProb pa = gemm_prob(c.at(c.e.DAP1), d.ld_nla, c.wt(MARL_P_POL_W0), d.ld_nla, d.nla,
-                                c.DHCs(1), d.ld_na, (int)NR, d.n_a);
-        gemm_add_seg(pa, c.at(c.e.DAC1), d.ld_nla, c.wt(MARL_P_CRI_W0), d.ld_nla, d.nla);
+        GemmProb ph = gemm_prob(c.at(c.e.DAQ1), d.ld_nlb, c.wtB(MARL_P_PRE_W0), c.DHs(1), d.ld_nb, (int)NR, d.n_b);
+        GemmProb pa = gemm_prob(c.at(c.e.DAP1), d.ld_nla, c.wtB(MARL_P_POL_W0), c.DHCs(1), d.ld_na, (int)NR, d.n_a);
+        gemm_add_seg(pa, c.at(c.e.DAC1), d.ld_nla, c.wtB(MARL_P_CRI_W0));
         MARL_TRY(gemm2(c, ph, pa));
     }
     if (sb) {  // + the upstream dL/dh, dL/dh^ of the step's new hidden states
@@ -1678,10 +1670,10 @@ static int enc_bwd_rows(const BwdState& s, int t, int acc, float* dh) {
     float* dae1 = c.at(c.e.DAE1) + (size_t)t * d.R * d.ld_nm2;
     MARL_TRY(ln_bwd(c, dze2, d.ld_nm, c.at(c.e.ZE2, t), d.ld_nm, c.at(c.e.STE2, t), MARL_P_ENC_LN1W,
                     MARL_P_ENC_LN1B, d.R, d.n_m, s.grads, acc));
-    MARL_TRY(gemm1(c, gemm_prob(dze2, d.ld_nm, c.wt(MARL_P_ENC_W1), p4(d.n_m), d.n_m, dae1, d.ld_nm2, R, d.nm2)));
+    MARL_TRY(gemm1(c, gemm_prob(dze2, d.ld_nm, c.wtB(MARL_P_ENC_W1), dae1, d.ld_nm2, R, d.nm2)));
     MARL_TRY(ln_bwd(c, dae1, d.ld_nm2, c.at(c.e.ZE1, t), d.ld_nm2, c.at(c.e.STE1, t), MARL_P_ENC_LN0W,
                     MARL_P_ENC_LN0B, d.R, d.nm2, s.grads, acc));
-    return gemm1(c, gemm_prob(dae1, d.ld_nm2, c.wt(MARL_P_ENC_W0), p4(d.nm2), d.nm2, dh, d.ld_nb, R, d.n_b, nullptr, 1));
+    return gemm1(c, gemm_prob(dae1, d.ld_nm2, c.wtB(MARL_P_ENC_W0), dh, d.ld_nb, R, d.n_b, nullptr, 1));
 }
 
 // recurrent paths dh_{t-1} += dgates * W_hh, and d(decoded message) = columns [nf, nf + n_mo) of dU - independent
@@ -1715,16 +1707,14 @@ static int bwd_recurrent(const BwdState& s, int t, float* ddbar, float* ddbar2) 
     GemmBatch gb{};
     for (int i = 0; i < count; ++i) {
         const auto& q = prod[i];
-        const int ldg = q.which ? d.ld_ga : d.ld_gb;
-        gb.p[i] = gemm_prob(c.at(q.which ? c.e.GA : c.e.GB, t), ldg, c.wt(q.w) + (size_t)q.row0 * ldg, ldg,
-                            4 * (q.which ? d.n_a : d.n_b), q.out, q.ldo, R, q.n, nullptr, q.acc);
+        gb.p[i] = gemm_prob(c.at(q.which ? c.e.GA : c.e.GB, t), q.which ? d.ld_ga : d.ld_gb,
+                            c.wtB(q.w).from_row(q.row0), q.out, q.ldo, R, q.n, nullptr, q.acc);
     }
     gb.count = count;
     if (!s.panels) {  // rows path: only the message columns, both cells' shares summed by one two-segment product
         GemmProb& p = gb.p[gb.count++];
-        p = gemm_prob(c.at(c.e.GB, t), d.ld_gb, c.wt(MARL_P_LB_WIH) + (size_t)d.nf * d.ld_gb, d.ld_gb, 4 * d.n_b,
-                      ddbar, d.ld_dbl, R, d.n_mo);
-        gemm_add_seg(p, c.at(c.e.GA, t), d.ld_ga, c.wt(MARL_P_LA_WIH) + (size_t)d.nf * d.ld_ga, d.ld_ga, 4 * d.n_a);
+        p = gemm_prob(c.at(c.e.GB, t), d.ld_gb, c.wtB(MARL_P_LB_WIH).from_row(d.nf), ddbar, d.ld_dbl, R, d.n_mo);
+        gemm_add_seg(p, c.at(c.e.GA, t), d.ld_ga, c.wtB(MARL_P_LA_WIH).from_row(d.nf));
     }
     return launch_gemm_nt(gb, c.st);
 }
@@ -1815,14 +1805,12 @@ static int bwd_step_rows(const BwdState& s, int t, float* ddbar) {
     float* dad1 = c.at(c.e.DAD1) + (size_t)t * d.R * d.ld_nm2;
     MARL_TRY(ln_bwd(c, ddbar, d.ld_dbl, c.at(c.e.ZD2, t), d.ld_nmo, c.at(c.e.STD2, t),
                     MARL_P_DEC_LN1W, MARL_P_DEC_LN1B, d.R, d.n_mo, s.grads, !first));
-    MARL_TRY(gemm1(c, gemm_prob(ddbar, d.ld_dbl, c.wt(MARL_P_DEC_W1), p4(d.n_mo), d.n_mo, dad1,
-                                d.ld_nm2, R, d.nm2)));
+    MARL_TRY(gemm1(c, gemm_prob(ddbar, d.ld_dbl, c.wtB(MARL_P_DEC_W1), dad1, d.ld_nm2, R, d.nm2)));
     MARL_TRY(ln_bwd(c, dad1, d.ld_nm2, c.at(c.e.ZD1, t), d.ld_nm2, c.at(c.e.STD1, t),
                     MARL_P_DEC_LN0W, MARL_P_DEC_LN0B, d.R, d.nm2, s.grads, !first));
     // dL/d(mean message): of the step's input message (step API), or on its way into the encoder of step t-1
     if (t > 0 || (s.sb && s.sb->d_msg))
-        MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wt(MARL_P_DEC_W0), p4(d.nm2), d.nm2,
-                                    c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
+        MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wtB(MARL_P_DEC_W0), c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
     if (t == 0) return MARL_OK;
     float* dze2 = c.at(c.e.DZE2) + (size_t)(t - 1) * d.R * d.ld_nm;
     if (g_comm)  // the transpose of the mixing matrix
@@ -2064,8 +2052,7 @@ static int bwd_cnn_layers(const BwdState& s, const void* img, int img_u8, const 
             have_dz = true;
             continue;
         }
-        MARL_TRY(gemm1(c, gemm_prob(dz, co, c.wt(4 * l), p4(co), co, c.at(c.e.DCOLS[l]),
-                                    d.ldk[l], (int)rows, d.K[l])));
+        MARL_TRY(gemm1(c, gemm_prob(dz, co, c.wtB(4 * l), c.at(c.e.DCOLS[l]), d.ldk[l], (int)rows, d.K[l])));
         MARL_TRY(launch_col2im(c.at(c.e.DCOLS[l]), d.ldk[l], c.at(c.e.DA[l - 1]), NR,
                                d.hw[l], d.ch[l], st));
         da = c.at(c.e.DA[l - 1]);
@@ -2090,9 +2077,9 @@ static int bwd_inputs(const BwdState& s, const void* img, int img_u8, float* d_i
         g.count = 1;
         MARL_TRY(launch_gemm_nt3(g, st));
     } else {
-        GemmProb p = gemm_prob(c.at(c.e.GB, 0), d.ld_gb, c.wt(MARL_P_LB_WIH), d.ld_gb, 4 * d.n_b,
+        GemmProb p = gemm_prob(c.at(c.e.GB, 0), d.ld_gb, c.wtB(MARL_P_LB_WIH),
                                c.at(c.e.DU), d.ld_nin, (int)NR, s.panels ? d.nf : d.nin);
-        gemm_add_seg(p, c.at(c.e.GA, 0), d.ld_ga, c.wt(MARL_P_LA_WIH), d.ld_ga, 4 * d.n_a);
+        gemm_add_seg(p, c.at(c.e.GA, 0), d.ld_ga, c.wtB(MARL_P_LA_WIH));
         MARL_TRY(gemm1(c, p));
     }
     if (s.panels)  // d(position embedding) = belief share + action share
@@ -2263,7 +2250,6 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
                                float* step_values, int64_t* step_pos, int64_t* step_actions, float* step_probs,
                                int train, void* stream) {
     Ctx c;
-    SplitRegistryScope reg_scope;
     MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, train, stream, c));
     if (!img || !pos0 || !h0 || !c0 || !hc0 || !cc0 || !step_preds || !step_logp || !step_values) {
         set_error("episode_forward: null argument");
@@ -2367,7 +2353,6 @@ static int episode_backward_entry(const char* who, bool need_dimg, const marl_co
                                   const float* g_preds, const float* g_logp, const float* g_values,
                                   float* const* grads_host, float* d_img, const float* g_probs, void* stream) {
     Ctx c;
-    SplitRegistryScope reg_scope;
     MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, 1, stream, c));
     if (!grads_host) {
         set_error("%s: null gradient table", who);
@@ -2748,7 +2733,6 @@ static int step_forward(const marl_config* cfg, const void* weights_ws, size_t w
         return MARL_EINVAL;
     }
     Ctx c;
-    SplitRegistryScope reg_scope;
     MARL_TRY(make_ctx(cfg, weights_ws, weights_ws_bytes, episode_ws, episode_ws_bytes, train, stream, c));
     if (!obs || !msg || !norm_pos || !h || !cc_ || !hc || !cca || !probs || !values || !preds ||
         !new_msg || !h_out || !c_out || !hc_out || !cc_out) {
@@ -2834,7 +2818,6 @@ int marl_step_backward(const marl_config* cfg, void* weights_ws, size_t weights_
     marl_config one = *cfg;
     one.nb_steps = 1;
     Ctx c;
-    SplitRegistryScope reg_scope;
     MARL_TRY(make_ctx(&one, weights_ws, weights_ws_bytes, step_ws, step_ws_bytes, 1, stream, c));
     if (!grads_host || !obs) {
         set_error("step_backward: null gradient table or observation");
@@ -3051,9 +3034,8 @@ int marl_profile_end(double* total_ms, int* launches) { return profile_end(total
 // ---- kernel-level entry points -------------------------------------------------------
 int marl_gemm_nt(const float* a, int lda, const float* b, int ldb, const float* bias, float* c,
                  int ldc, int m, int n, int k, int accumulate, void* stream) {
-    split_registry_reset();  // plain fp32 operands: no image of B is known to this call
     GemmBatch bt{};
-    bt.p[0] = gemm_prob(a, lda, b, ldb, k, c, ldc, m, n, bias, accumulate);
+    bt.p[0] = gemm_prob(a, lda, gemm_b(b, ldb, k), c, ldc, m, n, bias, accumulate);  // never an image
     bt.count = 1;
     return launch_gemm_nt(bt, static_cast<hipStream_t>(stream));
 }
@@ -3071,14 +3053,10 @@ int marl_gemm_nt_weights(const float* a, int lda, const float* b, int ldb, const
     sb.d[0] = SplitDesc{b, image_scratch, n, k, ldb, (k + 31) / 32};
     sb.count = 1;
     MARL_TRY(launch_split_weights(sb, st));
-    split_registry_reset();
-    split_registry_add(b, n, ldb, k, image_scratch);
     GemmBatch bt{};
-    bt.p[0] = gemm_prob(a, lda, b, ldb, k, c, ldc, m, n, bias, accumulate);
+    bt.p[0] = gemm_prob(a, lda, GemmB{b, ldb, k, image_scratch, (k + 31) / 32}, c, ldc, m, n, bias, accumulate);
     bt.count = 1;
-    const int rc = launch_gemm_nt(bt, st);
-    split_registry_reset();
-    return rc;
+    return launch_gemm_nt(bt, st);
 }
 
 size_t marl_gemm_tn_scratch(int ni, int nj, int64_t rows) { return gemm_tn_scratch_bytes(ni, nj, rows); }

@@ -873,10 +873,10 @@ int RedQueue::flush() {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-GemmProb gemm_prob(const float* a, int lda, const float* b, int ldb, int k, float* c, int ldc,
-                   int m, int n, const float* bias, int accumulate) {
+GemmProb gemm_prob(const float* a, int lda, const GemmB& b, float* c, int ldc, int m, int n,
+                   const float* bias, int accumulate) {
     GemmProb p{};
-    p.seg[0] = GemmSeg{a, b, lda, ldb, k};
+    p.seg[0] = GemmSeg{a, b.b, lda, b.ld, b.k, b.b3, b.kt3};
     p.nseg = 1;
     p.m = m;
     p.n = n;
@@ -887,8 +887,8 @@ GemmProb gemm_prob(const float* a, int lda, const float* b, int ldb, int k, floa
     return p;
 }
 
-void gemm_add_seg(GemmProb& p, const float* a, int lda, const float* b, int ldb, int k) {
-    p.seg[1] = GemmSeg{a, b, lda, ldb, k};
+void gemm_add_seg(GemmProb& p, const float* a, int lda, const GemmB& b) {
+    p.seg[1] = GemmSeg{a, b.b, lda, b.ld, b.k, b.b3, b.kt3};
     p.nseg = 2;
 }
 

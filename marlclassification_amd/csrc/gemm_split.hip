@@ -608,39 +608,6 @@ int launch_split_weights(const SplitBatch& b, hipStream_t st) {
     return MARL_OK;
 }
 
-namespace {
-struct SplitReg {
-    const float* base;
-    size_t floats;
-    int ld, k;
-    const char* image;
-};
-// (per THREAD and per CALL: ctypes releases the GIL, two engines may be inside the library at once; every
-// entry point that registers clears the table again before it returns - SplitRegistryScope - so a later
-// kernel-level call can never meet the image of a workspace that was freed or rewritten since)
-thread_local SplitReg g_reg[kMaxSplitDesc];
-thread_local int g_nreg = 0;
-// b = base + row0 * ld of a registered matrix with the same row stride and depth -> its image rows
-bool split_lookup(const GemmSeg& g, const void*& b3, int& kt) {
-    for (int i = 0; i < g_nreg; ++i) {
-        const SplitReg& r = g_reg[i];
-        if (g.b < r.base || g.b >= r.base + r.floats || g.ldb != r.ld || g.k != r.k) continue;
-        const size_t off = (size_t)(g.b - r.base);
-        if (off % (size_t)r.ld) return false;
-        kt = (r.k + 31) / 32;
-        b3 = r.image + (off / (size_t)r.ld) * (size_t)kt * 192;
-        return true;
-    }
-    return false;
-}
-}  // namespace
-
-void split_registry_reset() { g_nreg = 0; }
-void split_registry_add(const float* base, int rows, int ld, int k, const void* image) {
-    if (g_nreg < kMaxSplitDesc)
-        g_reg[g_nreg++] = SplitReg{base, (size_t)rows * ld, ld, k, static_cast<const char*>(image)};
-}
-
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -653,14 +620,13 @@ static int launch_nt_split_variant(dim3 grid, const GemmBatch& batch_in, hipStre
     batch.gy = (int)grid.y;
     batch.xcd_map = batch.count == 1 && !LSTM && tune_get("nt_xcd", 1);
     if (batch.xcd_map) grid = dim3(grid.x * grid.y * grid.z);
-    // every B operand a registered weight matrix: the kernel copies their pre-split tiles
+    // every B operand comes with its pre-split image: the kernel copies their tiles
     bool pre = true;
     for (int i = 0; i < batch.count && pre; ++i)
         for (int sg = 0; sg < batch.p[i].nseg && pre; ++sg) {
-            GemmSeg& g = batch.p[i].seg[sg];
-            pre = split_lookup(g, g.b3, g.kt3);
+            const GemmSeg& g = batch.p[i].seg[sg];
             // 32-bit byte offsets into the image
-            if (pre && (int64_t)(LSTM ? 4 : 1) * batch.p[i].n * g.kt3 * 192 >= (1ll << 32)) pre = false;
+            pre = g.b3 && (int64_t)(LSTM ? 4 : 1) * batch.p[i].n * g.kt3 * 192 < (1ll << 32);
         }
     constexpr size_t lds = (size_t)3 * (128 + BN) * SROW;
 #ifdef MARL_KERNEL_TS

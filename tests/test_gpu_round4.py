@@ -1,6 +1,7 @@
-"""GPU, round 4: the ABI sees workspace sizes (MARL_ESIZE instead of out-of-bounds writes), the bf16x3 weight-image
-registry is scoped to the call that filled it, and the image-GEMM path of the episode (csrc/gemm3.hip) is the
-one the parity fixtures with R % 32 == 0 run - checked against the fp32-operand path on the same episode."""
+"""GPU, round 4: the ABI sees workspace sizes (MARL_ESIZE instead of out-of-bounds writes), a bf16x3 weight image
+reaches a product only inside the operand its caller passes, and the image-GEMM path of the episode
+(csrc/gemm3.hip) is the one the parity fixtures with R % 32 == 0 run - checked against the fp32-operand path on the
+same episode."""
 import ctypes as C
 
 import pytest
@@ -75,13 +76,14 @@ def test_workspace_sizes_are_checked_by_the_abi(device):
 
 
 def test_gemm_nt_never_meets_a_stale_weight_image(device):
-    """the fp32 -> image registry used to outlive the episode call that filled it; a later
-    marl_gemm_nt on the same addresses then multiplied by the OLD weights' image."""
+    """a host-side table fp32 address -> image used to outlive the episode call that filled it; a later
+    marl_gemm_nt on the same addresses then multiplied by the OLD weights' image.  Now the image travels inside the
+    B operand of the call that owns it, and marl_gemm_nt builds a plain operand: it never takes one."""
     from marlclassification_amd import _lib
 
     g = Golden("g2_mnist_c1")
     eng = _engine(g, device)
-    _forward(eng, g, device)  # registers the images of every weight copy inside weights_ws
+    _forward(eng, g, device)  # multiplies by the images of the weight copies inside weights_ws
     off, ld = C.c_int64(0), C.c_int(0)
     idx = _lib.P["POL_W0"]
     _lib.check(eng.lib.marl_debug_buffer(C.byref(eng.cfg), 1, f"WP{idx}".encode(), 0, C.byref(off), C.byref(ld)))

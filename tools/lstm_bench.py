@@ -1,4 +1,4 @@
-"""Times the NT products of the C3 iteration that have registered weights as B (bf16x6 path):
+"""Times the NT products of the C3 iteration whose B is a weight copy with its pre-split image (bf16x6 path):
 runs bench-like forward steps through the engine and reports class timings via the profile hook."""
 import ctypes as C, os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
