@@ -7,6 +7,8 @@ import re
 from os.path import abspath, dirname, join
 
 from .comm import check_spelling, parse_range
+from .explore import check as check_exploration
+from .explore import parse_eps, parse_temperature
 from .config import EvalConfig, InferConfig, MainConfig, ModelConfig, TrainConfig
 from .networks.vision import CNN_BY_NAME
 
@@ -89,6 +91,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "models/comm_epoch_{e}.npy, which test / infer load with --comm FILE.npy")
     t.add_argument("--comm-lr", type=float, default=None, dest="comm_lr", metavar="LR",
                    help="learning rate of the graph's logits with --learn-comm (default: --lr)")
+    t.add_argument("--temperature", type=_arg(parse_temperature), default=None, dest="temperature",
+                   metavar="T[:T_end]",
+                   help="sampling temperature: actions are drawn from softmax(z / T); T:T_end is interpolated "
+                        "linearly over the epochs and applied at each epoch's start (default: 1)")
+    t.add_argument("--explore-eps", type=_arg(parse_eps), default=None, dest="explore_eps", metavar="E[:E_end]",
+                   help="eps-soft behaviour policy (1 - E) softmax(z / T) + E / nb_action, E in [0, 0.5], with the "
+                        "same per-epoch schedule spelling (default: 0)")
+    for sp in (e, i):
+        sp.add_argument("--greedy", action="store_true", dest="greedy",
+                        help="deterministic acting: every agent takes the argmax of its policy (no random draw)")
+        sp.add_argument("--temperature", type=_arg(_temperature), default=1.0, dest="temperature", metavar="T",
+                        help="the policy is softmax(z / T) (default: 1)")
     for sp in (t, e, i):
         sp.add_argument("--comm", type=_comm_arg, default=None, dest="comm", metavar="GRAPH",
                         help="communication graph of the message exchange: full | none | ring[:k] | star[:hub] | "
@@ -101,6 +115,20 @@ def build_parser() -> argparse.ArgumentParser:
                              "the base whose out-of-range links are cut; a receiver's remaining weights are rescaled "
                              "to the base row's sum unless :raw); default: off (test / infer: what marl.json names)")
     return p
+
+
+def _arg(parse):
+    """argparse type from a parser that raises ValueError."""
+    def convert(text: str):
+        try:
+            return parse(text)
+        except ValueError as err:
+            raise argparse.ArgumentTypeError(str(err))
+    return convert
+
+
+def _temperature(text: str) -> float:
+    return check_exploration(temperature=float(text)).temperature
 
 
 def _comm_arg(text: str) -> str:
@@ -155,6 +183,7 @@ def main(argv=None) -> None:
             gamma=args.gamma, entropy_coef=args.entropy_coef, ppo_epochs=args.ppo_epochs,
             ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, max_grad_norm=args.max_grad_norm,
             learn_comm=args.learn_comm, comm_lr=args.comm_lr,
+            temperature=args.temperature, explore_eps=args.explore_eps,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":
@@ -163,7 +192,7 @@ def main(argv=None) -> None:
         eval_main(main_config, EvalConfig(
             img_size=args.img_size, state_dict_path=args.state_dict_path, batch_size=args.batch_size,
             json_path=args.json_path, dataset_path=args.dataset_path, output_dir=args.output_dir,
-            comm=args.comm, comm_range=args.comm_range))
+            comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature))
     elif args.main_choice == "infer":
         import os
 
@@ -175,7 +204,7 @@ def main(argv=None) -> None:
         infer_main(main_config, InferConfig(
             state_dict_path=args.state_dict_path, json_path=args.json_path, images_path=args.infer_images,
             output_dir=args.output_image_dir, class_to_idx=args.class_to_idx, saliency=args.saliency,
-            comm=args.comm, comm_range=args.comm_range))
+            comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature))
 
 
 if __name__ == "__main__":

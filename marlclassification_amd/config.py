@@ -110,6 +110,10 @@ class TrainConfig(BaseModel):
     # with its own Adam at comm_lr (None: learning_rate)
     learn_comm: bool = False
     comm_lr: Optional[float] = None
+    # exploration schedules (explore.py): (start, end) of the sampling temperature and of the eps-soft mixture,
+    # interpolated linearly over the epochs and applied at each epoch's start; None: the plain policy
+    temperature: Optional[Tuple[float, float]] = None
+    explore_eps: Optional[Tuple[float, float]] = None
 
 
 class EvalConfig(BaseModel):
@@ -121,6 +125,8 @@ class EvalConfig(BaseModel):
     output_dir: str
     comm: Optional[str] = None  # --comm: replaces the graph marl.json names (None: keep it)
     comm_range: Optional[str] = None  # --comm-range: replaces the range marl.json names (None: keep it)
+    greedy: bool = False  # --greedy: deterministic acting, the argmax of the policy (a run-time choice, not in marl.json)
+    temperature: float = 1.0  # --temperature: the policy is softmax(z / T)
 
 
 class InferConfig(BaseModel):
@@ -132,3 +138,5 @@ class InferConfig(BaseModel):
     saliency: bool = False  # also write saliency.png (|d logit / d pixel|) next to the step frames
     comm: Optional[str] = None  # --comm: replaces the graph marl.json names (None: keep it)
     comm_range: Optional[str] = None  # --comm-range: replaces the range marl.json names (None: keep it)
+    greedy: bool = False  # --greedy: deterministic acting, the argmax of the policy (a run-time choice, not in marl.json)
+    temperature: float = 1.0  # --temperature: the policy is softmax(z / T)

@@ -64,6 +64,7 @@ class _EpisodeFunction(th.autograd.Function):
         ctx.comm = eng.comm  # the backward goes through the transpose of THIS rollout's matrix, whatever is set by then
         ctx.comm_range = eng.comm_range  # (likewise the range: the backward rebuilds THIS rollout's gates)
         ctx.comm_dtype = None if comm is None else comm.dtype
+        ctx.exploration = eng.exploration  # (and the behaviour policy THIS rollout's probabilities were saved under)
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
         ctx.shapes = [p.shape for p in params]
@@ -83,6 +84,7 @@ class _EpisodeFunction(th.autograd.Function):
                                "the optimiser step")
         later_comm, eng.comm = eng.comm, ctx.comm
         later_range, eng.comm_range = eng.comm_range, ctx.comm_range
+        later_explore, eng.exploration = eng.exploration, ctx.exploration
         try:
             if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
                 na, nb, ns, shape, u8 = ctx.cfg_key
@@ -104,6 +106,7 @@ class _EpisodeFunction(th.autograd.Function):
         finally:
             eng.comm = later_comm
             eng.comm_range = later_range
+            eng.exploration = later_explore
         eng.train_ws_release(ctx.ws)
         ctx.ws = None
         # (a frozen model: the parameter gradients are computed and dropped here)

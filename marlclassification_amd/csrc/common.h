@@ -529,8 +529,13 @@ struct SampleArgs {
     // optional: the same values into the k16 image of U[t+1] (columns pe_col0 .., image row r + pe_row0)
     char* pe_img;
     int pe_row0, pe_steps, pe_col0;
+    // exploration controls (marl_policy_explore; read by the EXPLORE instantiations only, behind everything else so
+    // that no other member moves): 1 / tau, 1 - eps, eps / nA, and greedy = argmax instead of a draw
+    float ex_inv_tau, ex_keep, ex_floor;
+    int ex_greedy;
 };
-int launch_sample(const SampleArgs& a, hipStream_t st);
+// explore: the EXPLORE instantiation of sample_kernel (a.ex_* filled), else the plain one
+int launch_sample(const SampleArgs& a, hipStream_t st, bool explore = false);
 
 // Perf-mode episode draws (the reference's reset draws, core/environment.py:33-43 and
 // networks/models.py:148-159, from a counter-based generator): pos0[r][d] uniform in
@@ -611,6 +616,12 @@ int launch_policy_dlogits(const float* dlogp, const float* probs, const int32_t*
 int launch_policy_dlogits_probs(const float* dlogp, const float* dprobs, const float* probs,
                                 const int32_t* actions, float* out, int ld, int64_t rows, int nA,
                                 hipStream_t st);
+// the same two cases under exploration controls (policy_dlogits_explore_kernel; dprobs nullable): with
+// s_j = (probs_j - floor) / keep and G_j = keep (g_j + dlogp 1[j == a] / probs_a),
+// dlogits_j = inv_tau s_j (G_j - sum_k s_k G_k)
+int launch_policy_dlogits_explore(const float* dlogp, const float* dprobs, const float* probs,
+                                  const int32_t* actions, float* out, int ld, int64_t rows, int nA,
+                                  float inv_tau, float keep, float floor, hipStream_t st);
 // dst[r][c] += src[r][c] for c < cols (src null: nothing)
 int launch_acc2d(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t rows, int cols,
                  hipStream_t st);
@@ -682,7 +693,8 @@ struct PanelFwdBatch {
 int panel_chain_supported(int na, int n_msg, int threads);
 int panel_supported(int k0, int n0, int n1);
 int panel_sample_supported(int n_actions);  // the sampling epilogue (PanelFwdBatch::epi_prob) covers this action count
-int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st);
+// explore (with epi_prob): the EXPLORE instantiations of the sampling epilogue (b.sample.ex_* filled)
+int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore = false);
 
 // LSTM cell backward (networks/recurrent.py:19-35 differentiated): gates holds the activated
 // i,f,g,o on entry and the pre-activation gradients on exit; dc holds dL/dc_t on entry and

@@ -21,6 +21,7 @@
 
 #include "../../include/marl_hip_rowops.h"
 #include "../../include/marl_hip_cnnops.h"
+#include "../../include/marl_hip_explore.h"
 #include "common.h"
 
 namespace marl {
@@ -682,6 +683,27 @@ static int g_comm_na = 0;
 // the positions of its emission, POS[t]; the zero message of step 0 under POS[0].  The chained panel launches build
 // the gated matrices in their workgroups (the GATE instantiations), every other site takes mix_msg_gated_kernel.
 static CommGate g_range = {nullptr, -1, 0, 1};
+// marl_policy_explore (marl_hip_explore.h): exploration controls of every sampling site and of the policy head's
+// backward, process-global like the two above.  on = anything but (tau 1, eps 0, sampled): only then does a call take
+// the EXPLORE kernels - with it off every entry launches what it always launched.
+struct Explore {
+    bool on;
+    float inv_tau, keep, eps;  // 1 / tau, 1 - eps, eps (the floor eps / nA is formed where nA is known)
+    int greedy;
+};
+static Explore g_explore = {false, 1.f, 1.f, 0.f, 0};
+// the sampling arguments of a call under the installed controls (greedy reads neither noise nor generator)
+static void explore_sample_args(SampleArgs& a) {
+    if (!g_explore.on) return;
+    a.ex_inv_tau = g_explore.inv_tau;
+    a.ex_keep = g_explore.keep;
+    a.ex_floor = g_explore.eps / (float)a.nA;
+    a.ex_greedy = g_explore.greedy;
+    if (g_explore.greedy) {
+        a.noise = nullptr;
+        a.rng_on = 0;
+    }
+}
 
 static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void* ews, size_t ebytes,
                     int train, void* stream, Ctx& c) {
@@ -1127,6 +1149,7 @@ static int step_chain(const Ctx& c, int t, const SampleArgs* sample = nullptr) {
     if (sample && use_panel_sample(d)) {
         pb.epi_prob = 2;
         pb.sample = *sample;
+        return launch_panel_fwd(pb, c.st, g_explore.on);  // (the EXPLORE epilogues under exploration controls)
     }
     return launch_panel_fwd(pb, c.st);
 }
@@ -1617,7 +1640,13 @@ static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, con
     MARL_TRY(tn(c, c.at(c.e.DAC1), d.ld_nla, c.HCs(1), d.ld_na, MARL_P_CRI_W0, d.nla, d.n_a, NR, grads[MARL_P_CRI_B0]));
     // policy head: logp = log softmax(logits)[a]  (networks/policy.py:12-16, core/agent.py:57-61)
     if (sb && sb->g_probs) g_probs = sb->g_probs;
-    if (g_probs)  // dL/dprobs from the caller (+ the dlogp term): a standalone step [R, nA] or all steps [Ns, R, nA]
+    // the saved rows hold the behaviour policy (marl_policy_explore): its own backward, both cases (greedy alone
+    // leaves the distribution the plain softmax: the kernels below, as always)
+    if (g_explore.on && (g_explore.inv_tau != 1.f || g_explore.eps != 0.f))
+        MARL_TRY(launch_policy_dlogits_explore(g_logp, g_probs, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG), d.ld_nA, NR,
+                                               d.nA, g_explore.inv_tau, g_explore.keep,
+                                               g_explore.eps / (float)d.nA, st));
+    else if (g_probs)  // dL/dprobs from the caller (+ the dlogp term): a standalone step [R, nA] or all steps [Ns, R, nA]
         MARL_TRY(launch_policy_dlogits_probs(g_logp, g_probs, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG),
                                              d.ld_nA, NR, d.nA, st));
     else
@@ -2282,6 +2311,7 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
         a.step_pos = step_pos ? step_pos + (size_t)t * d.R * 2 : nullptr;
         a.step_actions = step_actions ? step_actions + (size_t)t * d.R : nullptr;
         a.step_logp = step_logp + (size_t)t * d.R;
+        explore_sample_args(a);
         if (t + 1 < d.ns) {  // position embedding of step t+1 rides along with the move
             a.pe_W = c.wp(MARL_P_POS_W);
             a.pe_b = c.wp(MARL_P_POS_B);
@@ -2310,8 +2340,12 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
         // encoder above): one launch runs both.  Under the chain launch decoder(t+1) is already inside it, and so
         // is sample(t) when its policy workgroups ran it as their epilogue
         decoded_ahead = chain && t + 1 < d.ns;
-        if (!chain && t + 1 < d.ns) MARL_TRY(step_decode(c, t + 1, &a, &decoded_ahead));
-        if (chain ? !use_panel_sample(d) : !decoded_ahead) MARL_TRY(launch_sample(a, c.st));
+        // (under exploration controls only the chain launch's epilogue samples in-launch: the ride-along workgroups
+        // of the plain decoder launch have no EXPLORE form - sample_kernel's runs behind it)
+        bool rode = false;
+        if (!chain && t + 1 < d.ns) MARL_TRY(step_decode(c, t + 1, g_explore.on ? nullptr : &a, &rode));
+        if (chain ? !use_panel_sample(d) : !rode) MARL_TRY(launch_sample(a, c.st, g_explore.on));
+        if (!chain) decoded_ahead = t + 1 < d.ns && use_panels(d);
     }
     MARL_TRY(heads_batched(c, 0, d.NR, step_values, step_preds));
     if (step_probs) MARL_TRY(launch_copy2d(c.PROBSs(0), d.nA, step_probs, d.nA, d.NR, d.nA, c.st));
@@ -2436,6 +2470,20 @@ int marl_comm_range(int radius, int metric, int normalize) {
         return MARL_EINVAL;
     }
     g_range = CommGate{nullptr, radius, metric, normalize != 0};
+    return MARL_OK;
+}
+
+int marl_policy_explore(float temperature, float eps, int greedy) {
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) {
+        set_error("policy_explore: temperature %g, need a finite value > 0", (double)temperature);
+        return MARL_EINVAL;
+    }
+    if (!(eps >= 0.f && eps <= 0.5f)) {
+        set_error("policy_explore: eps %g outside [0, 0.5]", (double)eps);
+        return MARL_EINVAL;
+    }
+    const bool on = temperature != 1.f || eps != 0.f || greedy != 0;
+    g_explore = Explore{on, 1.0f / temperature, 1.0f - eps, eps, greedy != 0};
     return MARL_OK;
 }
 
@@ -2758,7 +2806,8 @@ static int step_forward(const marl_config* cfg, const void* weights_ws, size_t w
     } else {
         a.step_logp = nullptr;  // probabilities only
     }
-    MARL_TRY(launch_sample(a, c.st));
+    explore_sample_args(a);  // (probabilities only: the behaviour policy's)
+    MARL_TRY(launch_sample(a, c.st, g_explore.on));
     MARL_TRY(heads_batched(c, 0, d.R, values, preds));
     MARL_TRY(launch_copy2d(c.MSGs(1), d.ld_nm, new_msg, d.n_m, d.R, d.n_m, c.st));
     MARL_TRY(launch_copy2d(c.Hs(1), d.ld_nb, h_out, d.n_b, d.R, d.n_b, c.st));
@@ -2993,6 +3042,11 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     else if (!strcmp(key, "panel_chain")) *value = use_chain(d);
     // the forward loop samples inside the chained launch (the policy workgroups' epilogue): no sample_kernel launch
     else if (!strcmp(key, "panel_sample")) *value = use_chain(d) && use_panel_sample(d);
+    // exploration controls (marl_policy_explore): "explore" = installed; "explore_form" = where the forward loop
+    // samples under them (0 = off, 1 = the EXPLORE epilogue of the chained launch, 2 = sample_kernel's EXPLORE form)
+    else if (!strcmp(key, "explore")) *value = g_explore.on;
+    else if (!strcmp(key, "explore_form"))
+        *value = !g_explore.on ? 0 : (use_chain(d) && use_panel_sample(d)) ? 1 : 2;
     else if (!strcmp(key, "comm_form"))
         *value = g_comm ? (use_chain(d) ? 5 : use_panels(d) ? 3 : 4) : use_chain(d) ? 0 : use_panels(d) ? 1 : 2;
     else {

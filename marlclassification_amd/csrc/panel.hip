@@ -193,7 +193,8 @@ __device__ __forceinline__ void panel_ln_rows(const PanelLayer& Lr, float* outp,
 // UNI: the row's prefetched values move to scalar registers before the embedding's parameters are requested - the MIX
 // instantiation, which has one vector register fewer (a scalar spill lane), needs that to stay out of scratch; the plain
 // one fits without it and is 1.5 us per launch faster without (the moves wait for loads the chain would not yet need)
-template <int MAXA, bool UNI>
+// EXPLORE: sample_finish under exploration controls (sample.h)
+template <int MAXA, bool UNI, bool EXPLORE = false>
 __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const float* outp, int ys, const int* rowmap,
                                                   int wave, int nwaves, int lane) {
     for (int lr = __builtin_amdgcn_readfirstlane(wave); lr < kPanelRows; lr += nwaves) {  // wave-uniform: scalar
@@ -226,7 +227,7 @@ __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const fl
             S.forced = __builtin_amdgcn_readfirstlane(S.forced);
         }
         sample_prefetch_pe<MAXA>(A, ln, S);  // in flight under the reductions, the softmax and the draw
-        sample_finish<MAXA>(A, row, p, ln, S);
+        sample_finish<MAXA, EXPLORE>(A, row, p, ln, S);
     }
 }
 
@@ -239,7 +240,8 @@ __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const fl
 // MIX: the agg_at site mixes over a communication graph (P.mix) instead of taking the mean; the plain instantiations
 // carry none of it.  GATE (with MIX): the matrix is gated by the agents' positions (P.gate, marl_comm_range): one matrix
 // per image of the workgroup, built here from the base matrix P.mix; the constant-MIX instantiations carry none of it
-template <int SAMPLE, bool MIX = false, bool EPI = false, bool GATE = false>
+// EXPLORE (with EPI): the epilogue samples under exploration controls (marl_policy_explore); the others carry none of it
+template <int SAMPLE, bool MIX = false, bool EPI = false, bool GATE = false, bool EXPLORE = false>
 __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (!EPI && SAMPLE > 0 && (int)blockIdx.x >= B.panel_blocks) {
@@ -512,7 +514,8 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
     // (outside the layer loop: none of the loop's layer descriptors stays live across the chain)
     if (EPI && (int)(&P - B.p) + 1 == B.epi_prob) {  // (not blockIdx.y: one scalar fewer kept to the end)
         constexpr int MAXA = SAMPLE > 0 ? SAMPLE : 4;
-        panel_sample_rows<MAXA, MIX>(B.sample, (P.nlayers & 1) ? Y : X, panel_stride(K), rowmap, wave, nwaves, lane);
+        // (the plain EXPLORE instantiation takes the UNI form too: without it, it holds two registers too many)
+        panel_sample_rows<MAXA, MIX || EXPLORE, EXPLORE>(B.sample, (P.nlayers & 1) ? Y : X, panel_stride(K), rowmap, wave, nwaves, lane);
         MARL_TS();
     }
 }
@@ -546,7 +549,7 @@ int panel_supported(int k0, int n0, int n1) {
     return lds <= kPanelMaxLds;
 }
 
-int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
+int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
     int waves = 1, x0 = 0, x1 = 0;
     for (int i = 0; i < b.count; ++i) {
         const PanelFwdProb& p = b.p[i];
@@ -620,14 +623,17 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
     }
     static bool raised = false;
     if (!raised) {
-        const void* kerns[8] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
+        const void* kerns[11] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<MARL_MAX_ACTIONS>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<0, true>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4, false, true>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<0, true, false, true>),
-                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true, true>)};
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, false, true, false, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true, false, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<4, true, true, true, true>)};
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
@@ -653,8 +659,23 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st) {
             return MARL_EINVAL;
         }
     }
+    if (explore && !b.epi_prob) {
+        set_error("panel kernel: exploration controls are served by the sampling epilogue only");
+        return MARL_EINVAL;
+    }
     prof_before(4, st);
-    if (b.epi_prob) {
+    if (b.epi_prob && explore) {  // the same three forms, sampling from the behaviour policy
+        b.has_sample = 0;
+        if (gated)
+            hipLaunchKernelGGL((panel_fwd_kernel<4, true, true, true, true>), dim3(pblocks, (unsigned)b.count),
+                               dim3(64 * waves), lds, st, b);
+        else if (mixed)
+            hipLaunchKernelGGL((panel_fwd_kernel<4, true, true, false, true>), dim3(pblocks, (unsigned)b.count),
+                               dim3(64 * waves), lds, st, b);
+        else
+            hipLaunchKernelGGL((panel_fwd_kernel<4, false, true, false, true>), dim3(pblocks, (unsigned)b.count),
+                               dim3(64 * waves), lds, st, b);
+    } else if (b.epi_prob) {
         // sample(t) as the epilogue of the policy workgroups: no ride-along workgroups
         b.has_sample = 0;
         if (gated)

@@ -1631,7 +1631,7 @@ int launch_lstm_cell_bwd2(const float* dh0, int lddh0, float* dc0, int lddc0, fl
 // Policy output layer + softmax + multinomial (argmax p/q) + log-prob + bounded move
 // (networks/policy.py:15-16, core/agent.py:53-61, core/environment.py:56-66,128-150)
 // ---------------------------------------------------------------------------
-template <int MAXA>
+template <int MAXA, bool EXPLORE = false>
 __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs A) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1640,12 +1640,17 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs A) {
     SamplePre<MAXA> S;
     sample_prefetch<MAXA>(A, r, lane, S);
     sample_row_logits<MAXA>(A, r, p, lane);
-    sample_finish<MAXA>(A, r, p, lane, S);
+    sample_finish<MAXA, EXPLORE>(A, r, p, lane, S);
 }
 
-int launch_sample(const SampleArgs& a, hipStream_t st) {
+int launch_sample(const SampleArgs& a, hipStream_t st, bool explore) {
     if (a.nA > MARL_MAX_ACTIONS) return MARL_ELIMIT;
-    if (a.nA <= 4)
+    if (explore) {
+        if (a.nA <= 4)
+            hipLaunchKernelGGL((sample_kernel<4, true>), dim3((unsigned)cdiv(a.R, 4)), dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL((sample_kernel<MARL_MAX_ACTIONS, true>), dim3((unsigned)cdiv(a.R, 4)), dim3(256), 0, st, a);
+    } else if (a.nA <= 4)
         hipLaunchKernelGGL(sample_kernel<4>, dim3((unsigned)cdiv(a.R, 4)), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL(sample_kernel<MARL_MAX_ACTIONS>, dim3((unsigned)cdiv(a.R, 4)), dim3(256), 0, st, a);
@@ -2008,6 +2013,96 @@ int launch_policy_dlogits_probs(const float* dlogp, const float* dprobs, const f
     }
     hipLaunchKernelGGL(policy_dlogits_probs_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, st,
                        dlogp, dprobs, probs, actions, out, ld, rows, nA);
+    MARL_LAUNCH_CHECK();
+    return MARL_OK;
+}
+
+// Backward of the behaviour policy pi_b = keep softmax(z inv_tau) + floor (marl_policy_explore), one row per thread:
+// the saved row holds pi_b, s = (pi_b - floor) / keep recovers the softmax, G_j = keep (g_j + gl 1[j == a] / pi_b[a])
+// is dL/ds_j, and dz_j = inv_tau s_j (G_j - sum_k s_k G_k).  dprobs == null: g = 0 (the log-prob-only case);
+// a sampled / forced action of probability exactly 0 (keep == 1 only) drops its log-prob term, and an s_k of
+// exactly 0 adds nothing to the sum.  NV > 0: nA = 4 NV, rows as 16-byte loads and stores; NV = 0: any nA <=
+// MARL_MAX_ACTIONS, scalar.
+template <int NV>
+__global__ __launch_bounds__(256) void policy_dlogits_explore_kernel(const float* __restrict__ dlogp,
+                                                                     const float* __restrict__ dprobs,
+                                                                     const float* __restrict__ probs,
+                                                                     const int32_t* __restrict__ actions,
+                                                                     float* __restrict__ out, int ld, int64_t rows,
+                                                                     int nA_rt, float inv_tau, float keep, float floor) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    constexpr int CAP = NV > 0 ? 4 * NV : MARL_MAX_ACTIONS;
+    const int nA = NV > 0 ? 4 * NV : (nA_rt < CAP ? nA_rt : CAP);
+    float s[CAP], G[CAP];
+    if (NV > 0) {
+        const float4* pv = reinterpret_cast<const float4*>(probs + r * nA);
+        const float4* gv = dprobs ? reinterpret_cast<const float4*>(dprobs + r * nA) : nullptr;
+#pragma unroll
+        for (int k = 0; k < (NV > 0 ? NV : 1); ++k) {
+            const float4 a = pv[k], b = gv ? gv[k] : make_float4(0.f, 0.f, 0.f, 0.f);
+            s[4 * k] = a.x, s[4 * k + 1] = a.y, s[4 * k + 2] = a.z, s[4 * k + 3] = a.w;
+            G[4 * k] = b.x, G[4 * k + 1] = b.y, G[4 * k + 2] = b.z, G[4 * k + 3] = b.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < CAP; ++j) {
+            s[j] = j < nA ? probs[r * nA + j] : 0.f;
+            G[j] = (j < nA && dprobs) ? dprobs[r * nA + j] : 0.f;
+        }
+    }
+    const float gl = dlogp ? dlogp[r] : 0.f;
+    const int a = dlogp ? actions[r] : -1;
+    float pa = 0.f;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j)
+        if (j == a) pa = s[j];
+    const float la = pa > 0.f ? gl / pa : 0.f;
+    const float inv_keep = 1.0f / keep;
+    float dot = 0.f;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+        G[j] = keep * (G[j] + (j == a ? la : 0.f));
+        s[j] = j < nA ? fmaxf(s[j] - floor, 0.f) * inv_keep : 0.f;
+        if (s[j] > 0.f) dot = fmaf(s[j], G[j], dot);
+    }
+    if (NV > 0) {
+        float4* ov = reinterpret_cast<float4*>(out + r * ld);
+#pragma unroll
+        for (int k = 0; k < (NV > 0 ? NV : 1); ++k) {
+            float o[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = 4 * k + q;
+                o[q] = s[j] > 0.f ? inv_tau * s[j] * (G[j] - dot) : 0.f;
+            }
+            ov[k] = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < CAP; ++j)
+            if (j < nA) out[r * ld + j] = s[j] > 0.f ? inv_tau * s[j] * (G[j] - dot) : 0.f;
+    }
+}
+
+int launch_policy_dlogits_explore(const float* dlogp, const float* dprobs, const float* probs,
+                                  const int32_t* actions, float* out, int ld, int64_t rows, int nA,
+                                  float inv_tau, float keep, float floor, hipStream_t st) {
+    if (rows <= 0) return MARL_OK;
+    if (nA < 1 || nA > MARL_MAX_ACTIONS) return MARL_ELIMIT;
+    const dim3 grid((unsigned)cdiv(rows, 256)), block(256);
+    const bool v4 = nA % 4 == 0 && ld % 4 == 0 && aligned16(probs) && aligned16(out) && (!dprobs || aligned16(dprobs));
+#define MARL_DLOG_EXPLORE(NV)                                                                                   \
+    hipLaunchKernelGGL(policy_dlogits_explore_kernel<NV>, grid, block, 0, st, dlogp, dprobs, probs, actions, out, \
+                       ld, rows, nA, inv_tau, keep, floor)
+    switch (v4 ? nA / 4 : 0) {
+    case 1: MARL_DLOG_EXPLORE(1); break;
+    case 2: MARL_DLOG_EXPLORE(2); break;
+    case 3: MARL_DLOG_EXPLORE(3); break;
+    case 4: MARL_DLOG_EXPLORE(4); break;
+    default: MARL_DLOG_EXPLORE(0); break;
+    }
+#undef MARL_DLOG_EXPLORE
     MARL_LAUNCH_CHECK();
     return MARL_OK;
 }

@@ -154,8 +154,18 @@ __device__ __forceinline__ void sample_prefetch(const SampleArgs& A, int r, int 
     if (PE) sample_prefetch_pe<MAXA>(A, lane, S);
 }
 
+// Exploration controls (marl_policy_explore, EXPLORE instantiations only): the behaviour policy
+// pi_b = (1 - eps) softmax(z / tau) + eps / nA.  The two halves below are the only place the three constants
+// (formed once on the host: A.ex_inv_tau = 1 / tau, A.ex_keep = 1 - eps, A.ex_floor = eps / nA) are applied, so
+// sample_kernel, the panel kernel's epilogue and the single-step entries produce the same bits.
+__device__ __forceinline__ float explore_logit(const SampleArgs& A, float z) { return z * A.ex_inv_tau; }
+__device__ __forceinline__ float explore_mix(const SampleArgs& A, float s) { return fmaf(A.ex_keep, s, A.ex_floor); }
+
 // p[] holds this lane's partial logits of row r; every lane of the wave must call this
-template <int MAXA>
+// (EXPLORE = false: the plain policy softmax(z), today's code; true: pi_b above is what is sampled from, saved as
+// the step's distribution and what log p is taken from, and A.ex_greedy picks argmax pi_b - lowest index on a tie -
+// without reading noise or generator)
+template <int MAXA, bool EXPLORE = false>
 __device__ __forceinline__ void sample_finish(const SampleArgs& A, int r, float (&p)[MAXA], int lane,
                                               const SamplePre<MAXA>& S) {
     float mx = -INFINITY;
@@ -163,6 +173,7 @@ __device__ __forceinline__ void sample_finish(const SampleArgs& A, int r, float 
     for (int j = 0; j < MAXA; ++j) {
         if (j < A.nA) {
             p[j] = wave_sum(p[j]) + S.b1[j];
+            if (EXPLORE) p[j] = explore_logit(A, p[j]);
             mx = fmaxf(mx, p[j]);
         } else {
             p[j] = 0.f;
@@ -181,6 +192,13 @@ __device__ __forceinline__ void sample_finish(const SampleArgs& A, int r, float 
     for (int j = 0; j < MAXA; ++j)
         if (j < A.nA) {
             p[j] = p[j] / den;
+            if (EXPLORE) {
+                p[j] = explore_mix(A, p[j]);
+                if (A.ex_greedy && p[j] > best) {  // (the host passes neither noise nor generator with it)
+                    best = p[j];
+                    act = j;
+                }
+            }
             if (A.noise) {
                 const float sc = p[j] / S.nz[j];
                 if (sc > best) {

@@ -220,6 +220,12 @@ class HipEngine:
         # is the base the kernels gate per (step, image) by the agents' positions.  Installed and cleared with it.
         self.comm_range = None
         self._comm_full: Optional[th.Tensor] = None  # the base of a range without a matrix (cached per agent count)
+        # exploration controls (explore.Exploration; the default = the plain policy, sampled): like the matrix,
+        # per-process state of the library - installed around every call that samples or back-propagates through
+        # the sampling and cleared behind it; at the default nothing is installed and nothing more is called
+        from . import explore as _explore
+
+        self.exploration = _explore.DEFAULT
 
     # -- communication graph ----------------------------------------------------------
     def set_comm(self, matrix) -> None:
@@ -320,7 +326,30 @@ class HipEngine:
                   int(nb_steps), d_comm.data_ptr(), sc.data_ptr(), _nbytes(sc), _stream(self.device))
         return d_comm
 
+    def set_exploration(self, temperature=1.0, eps=0.0, greedy=False) -> None:
+        """The behaviour policy of every later sampling call of this engine (``explore.py``): pi_b =
+        (1 - eps) softmax(z / temperature) + eps / nA, sampled or - ``greedy`` - its argmax.  ValueError for a
+        temperature that is not finite and > 0 or an eps outside [0, 0.5].  A backward runs under the setting of
+        ITS forward: the autograd nodes keep it; a direct caller of ``episode_backward`` / ``step_backward`` leaves
+        it unchanged in between."""
+        from . import explore as _explore
+
+        self.exploration = _explore.check(temperature, eps, greedy)
+
     def _agg(self, fn, *args) -> None:
+        """A library call that samples, back-propagates through the sampling or aggregates messages: under this
+        engine's exploration controls and matrix, where it has them."""
+        x = self.exploration
+        if x.is_default:
+            self._agg_comm(fn, *args)
+            return
+        check(self.lib.marl_policy_explore(x.temperature, x.eps, int(x.greedy)))
+        try:
+            self._agg_comm(fn, *args)
+        finally:
+            self.lib.marl_policy_explore(1.0, 0.0, 0)
+
+    def _agg_comm(self, fn, *args) -> None:
         """A library call that aggregates messages: under this engine's matrix, if it has one."""
         r = self.comm_range
         m = self.comm if r is None else self._range_base()
@@ -337,7 +366,7 @@ class HipEngine:
             self.lib.marl_comm_range(-1, 0, 1)
 
     def plan_query(self, key: str, train: bool = True) -> int:
-        """marl_plan_query under this engine's communication matrix."""
+        """marl_plan_query under this engine's communication matrix and exploration controls."""
         v = C.c_int(0)
         self._agg(self.lib.marl_plan_query, C.byref(self.cfg), int(train), key.encode(), C.byref(v))
         return v.value

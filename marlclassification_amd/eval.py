@@ -36,6 +36,8 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
     nn_models.load_state_dict(th.load(eval_config.state_dict_path, map_location="cpu"))
     nn_models.eval()
     nn_models.to(device)
+    if eval_config.greedy or eval_config.temperature != 1.0:  # (--greedy: two runs of one checkpoint report the same)
+        nn_models.set_exploration(temperature=eval_config.temperature, greedy=eval_config.greedy)
     loader = DevicePrefetcher(DataLoader(dataset, batch_size=eval_config.batch_size, shuffle=True,
                                          num_workers=0, drop_last=False, pin_memory=True), device)
     sampler = EpisodeSampler(marl_m, env, main_config.step)

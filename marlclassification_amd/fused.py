@@ -238,8 +238,13 @@ class FusedA2C:
                  allreduce: Optional[Callable[[th.Tensor], float]] = None,
                  use_graph: bool = False, entropy_coef: float = 0.0, ppo_epochs: int = 1,
                  ppo_clip: float = 0.2, gae_lambda: float = 1.0,
-                 max_grad_norm: Optional[float] = None, comm_lr: Optional[float] = None) -> None:
-        """``comm_lr``: learning rate of the engine's LIVE communication source (``engine.set_comm`` with a tensor
+                 max_grad_norm: Optional[float] = None, comm_lr: Optional[float] = None,
+                 temperature: Optional[float] = None, explore_eps: Optional[float] = None) -> None:
+        """``temperature`` / ``explore_eps``: the behaviour policy of the rollouts (``HipEngine.set_exploration``;
+        replays run under the rollout's setting) - plain attributes that may be changed between iterations (a captured
+        graph is keyed by the setting); None: the engine's own setting is left alone.
+
+        ``comm_lr``: learning rate of the engine's LIVE communication source (``engine.set_comm`` with a tensor
         that requires grad or a module such as ``comm.LearnableComm``): every update also takes d_comm out of the
         backward and steps a ``torch.optim.Adam`` over the source's leaves (``CommUpdate``).  None, or a constant
         matrix: today's sequence of calls, verbatim.  ``max_grad_norm`` keeps covering the flat buffer only."""
@@ -250,6 +255,10 @@ class FusedA2C:
         if use_graph and comm_lr is not None and engine.comm_source is not None:
             raise ValueError("hipGraph replay does not cover the update of a live communication source (torch "
                              "launches between the captured calls): use_graph with comm_lr and a live source")
+        from . import explore as _explore
+
+        _explore.check(1.0 if temperature is None else temperature, 0.0 if explore_eps is None else explore_eps)
+        self.temperature, self.explore_eps = temperature, explore_eps
         self.comm_lr = None if comm_lr is None else float(comm_lr)
         self._comm_update: Optional[CommUpdate] = None
         if not entropy_coef >= 0.0:
@@ -284,8 +293,17 @@ class FusedA2C:
         self.engine.pack(self._pviews)
         self._packed_gen = self.engine.weights_generation
 
+    def _explore(self) -> None:
+        """Hands this object's ``temperature`` / ``explore_eps`` (where not None) to the engine."""
+        if self.temperature is None and self.explore_eps is None:
+            return
+        x0 = self.engine.exploration
+        self.engine.set_exploration(x0.temperature if self.temperature is None else self.temperature,
+                                    x0.eps if self.explore_eps is None else self.explore_eps, x0.greedy)
+
     def rollout(self, img: th.Tensor, draws: EpisodeDraws, train: bool,
                 forced_actions: Optional[th.Tensor] = None, probs: bool = False) -> EpisodeTensors:
+        self._explore()
         if self._packed_gen != self.engine.weights_token():  # never packed, or the workspace was re-laid-out
             self.pack()
         if self.engine.comm_source is not None:  # a live matrix: evaluated once for this forward
@@ -315,9 +333,11 @@ class FusedA2C:
         # (the tune epoch: after engine.tune() the workspaces baked into a captured graph are freed /
         # re-laid-out - the graph must be captured again)
         beta = self.entropy_coef
+        self._explore()
         key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch, beta,
                None if eng.comm is None else eng.comm.data_ptr(),  # (the captured kernels keep the matrix pointer
-               eng.comm_range)                                     # and the range's radius / metric / normalize)
+               eng.comm_range,                                     # and the range's radius / metric / normalize
+               eng.exploration)                                    # and the exploration constants in their arguments)
         if self._graph is None or self._graph[0] != key:
             if self._graph is not None:
                 eng.lib.marl_graph_destroy(self._graph[1])

@@ -43,6 +43,8 @@ def infer_main(main_config: MainConfig, infer_config: InferConfig) -> int:
     nn_models.load_state_dict(th.load(infer_config.state_dict_path, map_location="cpu"))
     nn_models.eval()
     nn_models.to(device)
+    if infer_config.greedy or infer_config.temperature != 1.0:  # (--greedy: two runs of one checkpoint report the same)
+        nn_models.set_exploration(temperature=infer_config.temperature, greedy=infer_config.greedy)
     sampler = EpisodeSampler(marl_m, env, main_config.step)
 
     paths = sorted(p for pattern in infer_config.images_path for p in glob.glob(pattern, recursive=True))

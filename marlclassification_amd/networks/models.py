@@ -79,6 +79,7 @@ class _StepFunction(th.autograd.Function):
         ctx.cfg_key = eng._cfg_key
         ctx.comm = eng.comm  # the backward goes through the transpose of THIS step's matrix, whatever is set by then
         ctx.comm_dtype = None if comm is None else comm.dtype
+        ctx.exploration = eng.exploration  # (likewise the behaviour policy the step's probabilities were saved under)
         ctx.pack_generation = eng.pack_generation
         ctx.names = names
         ctx.sampled = len(outs) == 10
@@ -101,6 +102,7 @@ class _StepFunction(th.autograd.Function):
                                "backward needs the weights the forward used - call backward before the "
                                "optimiser step")
         later_comm, eng.comm = eng.comm, ctx.comm
+        later_explore, eng.exploration = eng.exploration, ctx.exploration
         try:
             if ctx.cfg_key != eng._cfg_key:  # another shape ran in between: switch the engine back
                 na, nb, ns, shape, u8 = ctx.cfg_key
@@ -119,6 +121,7 @@ class _StepFunction(th.autograd.Function):
                                          g_c, g_hc, g_cc, want=want)
         finally:
             eng.comm = later_comm
+            eng.exploration = later_explore
         lease.release()
         return (None,) * 6 + (d_comm,) + d_in + tuple(grads[k] for k in ctx.names)
 
@@ -186,6 +189,28 @@ class ModelsWrapper(nn.Module):
         self.__comm_source: Tuple = ()
         # range-limited communication (set_comm_range): a comm.CommRange, None = off
         self.__comm_range = None
+        # exploration controls (set_exploration): an explore.Exploration.  A run-time choice: no state-dict key
+        from .. import explore as _explore
+
+        self.__exploration = _explore.DEFAULT
+
+    # ---- exploration controls ------------------------------------------------------------
+    @property
+    def exploration(self):
+        """The ``explore.Exploration`` (temperature, eps, greedy) ``set_exploration`` installed."""
+        return self.__exploration
+
+    def set_exploration(self, temperature=1.0, eps=0.0, greedy=False) -> None:
+        """Every later step / episode of this model (forward, MultiAgent.act, EpisodeSampler, Trainer, the PPO
+        epochs) acts under the behaviour policy pi_b = (1 - eps) softmax(z / temperature) + eps / nA
+        (``explore.behaviour_probs`` is the same map in torch): it is sampled from - or, ``greedy``, its argmax is
+        taken, the lowest index on a tie, without a random draw -, returned as the step's probabilities and its log
+        is the step's log-probability; the backward differentiates through it.  The defaults restore the plain
+        policy, bit for bit.  ValueError for a temperature that is not finite and > 0 or an eps outside [0, 0.5].
+        The setting is not saved with the model."""
+        from .. import explore as _explore
+
+        self.__exploration = _explore.check(temperature, eps, greedy)
 
     # ---- communication graph -------------------------------------------------------------
     @property
@@ -371,6 +396,7 @@ class ModelsWrapper(nn.Module):
             eng.comm_source = eng.comm_live = None
             eng.comm = self.comm_matrix  # (checked by set_comm; moved with the module)
         eng.comm_range = self.__comm_range
+        eng.exploration = self.__exploration
         return eng
 
     def flat_state(self) -> FlatParams:

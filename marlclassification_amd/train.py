@@ -212,13 +212,21 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
                       max_grad_norm=train_config.max_grad_norm,
                       comm_lr=((train_config.comm_lr if train_config.comm_lr is not None else
                                 train_config.learning_rate) if learned is not None else None))
+    from . import explore as _explore
+
+    t_ends, e_ends = train_config.temperature, train_config.explore_eps
     if rank == 0:
         print("update: " + ", ".join(f"{k}={getattr(train_config, k)}" for k in (
             "entropy_coef", "ppo_epochs", "ppo_clip", "gae_lambda", "max_grad_norm")) +
-              (f", learn_comm on {model_config.comm or 'full'}" if learned is not None else ""), flush=True)
+              (f", learn_comm on {model_config.comm or 'full'}" if learned is not None else "") +
+              (f", temperature {t_ends}, explore_eps {e_ends}" if t_ends or e_ends else ""), flush=True)
     for e in range(train_config.nb_epoch):
         for bs in samplers:
             bs.set_epoch(e)
+        if t_ends is not None:  # (the exploration schedules: linear over the epochs, applied at each epoch's start)
+            trainer.temperature = _explore.schedule_value(t_ends, e, train_config.nb_epoch)
+        if e_ends is not None:
+            trainer.explore_eps = _explore.schedule_value(e_ends, e, train_config.nb_epoch)
         trainer.train_epoch(loaders[0], e, sampler)
         conf = trainer.eval_epoch(loaders[1], e, sampler)
         if distributed:

@@ -42,8 +42,15 @@ class Trainer:
         gae_lambda: float = 1.0,
         max_grad_norm: Optional[float] = None,
         comm_lr: Optional[float] = None,
+        temperature: Optional[float] = None,
+        explore_eps: Optional[float] = None,
     ) -> None:
-        """``comm_lr``: learning rate of the model's LIVE communication source (``model.set_comm`` with a tensor that
+        """``temperature`` / ``explore_eps``: the behaviour policy of the rollouts, (1 - eps) softmax(z / T) + eps / nA
+        (``ModelsWrapper.set_exploration``; replays and PPO epochs run under the rollout's setting).  Plain
+        attributes that may be changed between ``train_step``s; each ``train_step`` hands the values that are not
+        None to the model (its ``greedy`` flag stays); None: the model's own setting is left alone.
+
+        ``comm_lr``: learning rate of the model's LIVE communication source (``model.set_comm`` with a tensor that
         requires grad, a module such as ``comm.LearnableComm`` or a callable with ``parameters()``).  Each update then
         evaluates the source, rolls out, takes the loss, runs the backward WITH d_comm (marl_comm_grad), sums d_comm
         over the ranks with the scale the flat gradient gets, calls ``matrix.backward(d_comm)`` and steps a
@@ -57,6 +64,10 @@ class Trainer:
         check_ppo_options(ppo_epochs, ppo_clip, gae_lambda, max_grad_norm)
         if comm_lr is not None and not comm_lr > 0.0:
             raise ValueError(f"comm_lr must be > 0 or None, got {comm_lr}")
+        from .. import explore as _explore
+
+        _explore.check(1.0 if temperature is None else temperature, 0.0 if explore_eps is None else explore_eps)
+        self.temperature, self.explore_eps = temperature, explore_eps
         self.__comm_lr = None if comm_lr is None else float(comm_lr)
         self.__comm_update: Optional[CommUpdate] = None
         self.__model = model
@@ -118,6 +129,10 @@ class Trainer:
     def train_step(self, x: th.Tensor, y: th.Tensor, sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
         model = self.__model
         y = y.to(model.device)
+        if self.temperature is not None or self.explore_eps is not None:  # (checked here: ValueError before any call)
+            x0 = model.exploration
+            model.set_exploration(x0.temperature if self.temperature is None else self.temperature,
+                                  x0.eps if self.explore_eps is None else self.explore_eps, x0.greedy)
         if self.__ppo:
             return self.__train_step_ppo(x, y, sampler)
         # with the entropy bonus: the same sequence through the three entries that carry the step distributions
