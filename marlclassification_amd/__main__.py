@@ -6,6 +6,8 @@ import argparse
 import re
 from os.path import abspath, dirname, join
 
+from .augment import parse as parse_augment
+from .augment import parse_tta
 from .comm import check_spelling, parse_range
 from .explore import check as check_exploration
 from .explore import parse_eps, parse_temperature
@@ -98,6 +100,13 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--explore-eps", type=_arg(parse_eps), default=None, dest="explore_eps", metavar="E[:E_end]",
                    help="eps-soft behaviour policy (1 - E) softmax(z / T) + E / nb_action, E in [0, 0.5], with the "
                         "same per-epoch schedule spelling (default: 0)")
+    t.add_argument("--augment", type=_arg(_augment_arg), default=None, dest="augment", metavar="SPEC",
+                   help="device-side augmentation of the training split, fused into the batch gather: a comma-separated "
+                        "list of hflip, vflip, rot90, d4, shift:T[:reflect|zero], erase:S[:p] (rot90 / d4 need square "
+                        "images; default: none)")
+    e.add_argument("--tta", type=_arg(_tta_arg), default=None, dest="tta", metavar="SPEC",
+                   help="test-time augmentation: every batch runs once per flip / rotation the spec allows (hflip, "
+                        "vflip, rot90, d4) and the predictions are averaged (default: one run)")
     for sp in (e, i):
         sp.add_argument("--greedy", action="store_true", dest="greedy",
                         help="deterministic acting: every agent takes the argmax of its policy (no random draw)")
@@ -125,6 +134,14 @@ def _arg(parse):
         except ValueError as err:
             raise argparse.ArgumentTypeError(str(err))
     return convert
+
+
+def _augment_arg(text: str) -> str:
+    return parse_augment(text).spec
+
+
+def _tta_arg(text: str) -> str:
+    return parse_tta(text).spec
 
 
 def _temperature(text: str) -> float:
@@ -183,7 +200,7 @@ def main(argv=None) -> None:
             gamma=args.gamma, entropy_coef=args.entropy_coef, ppo_epochs=args.ppo_epochs,
             ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, max_grad_norm=args.max_grad_norm,
             learn_comm=args.learn_comm, comm_lr=args.comm_lr,
-            temperature=args.temperature, explore_eps=args.explore_eps,
+            temperature=args.temperature, explore_eps=args.explore_eps, augment=args.augment,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":
@@ -192,7 +209,8 @@ def main(argv=None) -> None:
         eval_main(main_config, EvalConfig(
             img_size=args.img_size, state_dict_path=args.state_dict_path, batch_size=args.batch_size,
             json_path=args.json_path, dataset_path=args.dataset_path, output_dir=args.output_dir,
-            comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature))
+            comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature,
+            tta=args.tta))
     elif args.main_choice == "infer":
         import os
 

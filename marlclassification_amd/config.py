@@ -114,6 +114,9 @@ class TrainConfig(BaseModel):
     # interpolated linearly over the epochs and applied at each epoch's start; None: the plain policy
     temperature: Optional[Tuple[float, float]] = None
     explore_eps: Optional[Tuple[float, float]] = None
+    # --augment: device-side augmentation of the training split in the command-line spelling (augment.parse); a run-time
+    # choice like the exploration controls, not written to marl.json.  None: every batch is the plain gather
+    augment: Optional[str] = None
 
 
 class EvalConfig(BaseModel):
@@ -127,6 +130,7 @@ class EvalConfig(BaseModel):
     comm_range: Optional[str] = None  # --comm-range: replaces the range marl.json names (None: keep it)
     greedy: bool = False  # --greedy: deterministic acting, the argmax of the policy (a run-time choice, not in marl.json)
     temperature: float = 1.0  # --temperature: the policy is softmax(z / T)
+    tta: Optional[str] = None  # --tta: test-time augmentation, the mean over the views of augment.parse(SPEC).views()
 
 
 class InferConfig(BaseModel):

@@ -66,11 +66,16 @@ class DevicePrefetcher:
     synchronously at the top of the iteration (training/trainer.py:67-68) behind a pin_memory
     DataLoader (train.py:91-107); here batch i+1 is copied (uint8: a quarter of the fp32 bytes,
     ToTensor runs in the gather kernel) from pinned staging memory on a COPY stream while batch
-    i trains, and the compute stream only waits for the copy's event."""
+    i trains, and the compute stream only waits for the copy's event.
 
-    def __init__(self, loader, device: th.device) -> None:
+    ``augment`` (an ``augment.Policy``): the uploaded batch goes through ``augment.apply`` into a fresh tensor on the
+    compute stream, behind the wait on the copy's event, under ops drawn from ``generator`` (a generator of
+    ``device``).  None: exactly the code above."""
+
+    def __init__(self, loader, device: th.device, augment=None, generator=None) -> None:
         self.loader = loader
         self.device = th.device(device)
+        self.augment, self.generator = augment, _device_generator(augment, generator, self.device)
 
     def _upload(self, batch, stream):
         if batch is None:
@@ -98,10 +103,30 @@ class DevicePrefetcher:
             cur.wait_event(ev)
             xd.record_stream(cur)
             yd.record_stream(cur)
+            if self.augment is not None:
+                xd = _augmented(self.augment, self.generator, xd, None)
             yield xd, yd
 
     def __len__(self) -> int:
         return len(self.loader)
+
+
+def _device_generator(policy, generator, device: th.device):
+    """the generator a loader draws ops from: the caller's, or (policy without one) a fresh one of the device, seed 0"""
+    if policy is None or generator is not None:
+        return generator
+    return th.Generator(device=device).manual_seed(0)
+
+
+def _augmented(policy, generator, x: th.Tensor, rows):
+    """``augment.apply`` of ``x[rows]`` (``rows`` None: ``x`` itself) under freshly drawn ops; a policy that turns
+    images refuses non-square ones before anything is enqueued"""
+    from . import augment as _augment
+
+    policy.check_size(x.shape[-2], x.shape[-1])
+    batch = x.shape[0] if rows is None else rows.shape[0]
+    ops = policy.draw(batch, generator, size=(x.shape[-2], x.shape[-1]))
+    return _augment.apply(x, rows, ops, pad_mode=policy.pad_mode, fill=policy.fill)
 
 
 class _Stripe:
@@ -160,16 +185,22 @@ class ResidentLoader:
     shards are exchanged with one all-gather, so the host work is not repeated per rank.
 
     ``batch_sampler`` yields lists of dataset indices (this rank's slice of every global
-    batch, train.ShardedBatchSampler); ``indices`` is the set it draws from."""
+    batch, train.ShardedBatchSampler); ``indices`` is the set it draws from.
+
+    ``augment`` (an ``augment.Policy``): every batch is ``augment.apply(resident set, rows, ops)`` - the gather with
+    flips, quarter turns, shifts and erasing fused in, one launch that moves the bytes ``index_select`` moves - under
+    ops drawn from ``generator`` (a generator of ``device``) without a host synchronisation.  Labels are gathered as
+    before.  None: exactly the ``index_select`` above."""
 
     def __init__(self, dataset, indices, batch_sampler, device, workers: int = 0,
-                 rank: int = 0, world: int = 1, group=None, chunk: int = 16) -> None:
+                 rank: int = 0, world: int = 1, group=None, chunk: int = 16, augment=None, generator=None) -> None:
         self.dataset, self.batch_sampler = dataset, batch_sampler
         self.indices = list(indices)
         self.device = th.device(device)
         self.workers, self.rank, self.world, self.group, self.chunk = workers, rank, world, group, chunk
         self._x = self._y = self._row_of = None
         self.fill_img_s = float("nan")
+        self.augment, self.generator = augment, _device_generator(augment, generator, self.device)
 
     @staticmethod
     def nbytes(dataset, n: int) -> int:
@@ -226,7 +257,10 @@ class ResidentLoader:
             self._fill()
         for batch in self.batch_sampler:
             rows = self._row_of[th.tensor(batch, dtype=th.long).to(self.device, non_blocking=True)]
-            yield self._x.index_select(0, rows), self._y.index_select(0, rows)
+            if self.augment is None:
+                yield self._x.index_select(0, rows), self._y.index_select(0, rows)
+            else:
+                yield _augmented(self.augment, self.generator, self._x, rows), self._y.index_select(0, rows)
 
     def __len__(self) -> int:
         return len(self.batch_sampler)

@@ -42,10 +42,25 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
                                          num_workers=0, drop_last=False, pin_memory=True), device)
     sampler = EpisodeSampler(marl_m, env, main_config.step)
     meter = ConfusionMeter(nn_models.nb_class)
+    views = None
+    if eval_config.tta is not None:  # (--tta: one episode per flip / rotation of the spec, predictions averaged)
+        from . import augment as _augment
+
+        policy = _augment.parse_tta(eval_config.tta)
+        policy.check_size(eval_config.img_size, eval_config.img_size)
+        views = policy.views().to(device)
     with th.no_grad():
         for x, y in loader:
-            out = sampler.run_episode_get_last_step(x)
-            meter.add(out.prediction.mean(dim=0), y)  # mean over agents; stays on the device
+            if views is None or views.shape[0] == 1:
+                out = sampler.run_episode_get_last_step(x)
+                meter.add(out.prediction.mean(dim=0), y)  # mean over agents; stays on the device
+                continue
+            pred = None
+            for v in range(views.shape[0]):
+                xv = _augment.apply(x, None, views[v: v + 1].expand(x.shape[0], -1).contiguous())
+                p = sampler.run_episode_get_last_step(xv).prediction.mean(dim=0)
+                pred = p if pred is None else pred + p
+            meter.add(pred / views.shape[0], y)
 
     print(meter.conf_mat().cpu())
     precs, recs = meter.precision(), meter.recall()

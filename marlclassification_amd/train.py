@@ -189,16 +189,26 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
     if rank == 0:
         print(f"input pipeline: {'HBM-resident uint8 image set' if resident else 'streamed'}, "
               f"{workers} decode processes per rank", flush=True)
+    # --augment: the training split only (loaders[1] stays plain); ops are drawn on the device from a generator of
+    # its own, seeded per rank, so ranks draw differently and MARL_SEED repeats a run
+    policy = aug_gen = None
+    if train_config.augment is not None:
+        from . import augment as _augment
+
+        policy = _augment.parse(train_config.augment)
+        policy.check_size(train_config.img_size, train_config.img_size)
+        aug_gen = th.Generator(device=device).manual_seed(base_seed + 104729 * (rank + 1))
     for k, part in enumerate((idx[:cut].tolist(), idx[cut:].tolist())):
+        aug = {"augment": policy, "generator": aug_gen} if policy is not None and k == 0 else {}
         bs = ShardedBatchSampler(part, train_config.batch_size, rank, world, shuffle=True,
                                  seed=base_seed + 1 + k)
         samplers.append(bs)
         if resident:  # decoded once (1/world per rank), then batches are row gathers in HBM
-            loaders.append(ResidentLoader(dataset, part, bs, device, workers=workers, rank=rank, world=world))
+            loaders.append(ResidentLoader(dataset, part, bs, device, workers=workers, rank=rank, world=world, **aug))
             continue
         # (MARL_LOADER_STRIPES DataLoaders share the workers: one collate / pin thread each, data.StripedLoader)
         dl = StripedLoader(dataset, bs, workers, int(os.environ.get("MARL_LOADER_STRIPES", max(1, workers // 8))))
-        loaders.append(DevicePrefetcher(dl, device))  # upload of batch i+1 overlaps step i
+        loaders.append(DevicePrefetcher(dl, device, **aug))  # upload of batch i+1 overlaps step i
 
     sampler = EpisodeSampler(marl_m, env, main_config.step)
     trainer = Trainer(nn_models, marl_m.nb_class, train_config.learning_rate, train_config.gamma,
@@ -219,7 +229,8 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         print("update: " + ", ".join(f"{k}={getattr(train_config, k)}" for k in (
             "entropy_coef", "ppo_epochs", "ppo_clip", "gae_lambda", "max_grad_norm")) +
               (f", learn_comm on {model_config.comm or 'full'}" if learned is not None else "") +
-              (f", temperature {t_ends}, explore_eps {e_ends}" if t_ends or e_ends else ""), flush=True)
+              (f", temperature {t_ends}, explore_eps {e_ends}" if t_ends or e_ends else "") +
+              (f", augment {policy.spec}" if policy is not None else ""), flush=True)
     for e in range(train_config.nb_epoch):
         for bs in samplers:
             bs.set_epoch(e)
