@@ -8,6 +8,7 @@ from os.path import abspath, dirname, join
 
 from .augment import parse as parse_augment
 from .augment import parse_tta
+from .class_loss import check_label_smoothing, parse_class_weights, parse_error_steps
 from .comm import check_spelling, parse_range
 from .explore import check as check_exploration
 from .explore import parse_eps, parse_temperature
@@ -104,6 +105,19 @@ def build_parser() -> argparse.ArgumentParser:
                    help="device-side augmentation of the training split, fused into the batch gather: a comma-separated "
                         "list of hflip, vflip, rot90, d4, shift:T[:reflect|zero], erase:S[:p] (rot90 / d4 need square "
                         "images; default: none)")
+    t.add_argument("--class-weights", type=_arg(parse_class_weights), default=None, dest="class_weights",
+                   metavar="balanced|FILE.npy|w0,w1,...",
+                   help="class weights of the vote error: balanced = N / (nb_class * n_c) from the whole training "
+                        "split, a .npy vector, or one weight per class (default: all 1)")
+    t.add_argument("--label-smoothing", type=_arg(_label_smoothing), default=0.0, dest="label_smoothing", metavar="E",
+                   help="label smoothing of the vote error, E in [0, 1): the target is (1 - E) onehot + E / nb_class "
+                        "(default: 0)")
+    t.add_argument("--error-steps", type=_arg(parse_error_steps), default=None, dest="error_steps",
+                   metavar="all|last[:K]|linear",
+                   help="which steps' votes the error term asks to be right: all, the last K (last = last:1), or "
+                        "weights ramping linearly to 1 at the last step (default: all)")
+    t.add_argument("--weight-rewards", action="store_true", dest="weight_rewards",
+                   help="cost-sensitive rewards: every agent's reward is multiplied by its image's class weight")
     e.add_argument("--tta", type=_arg(_tta_arg), default=None, dest="tta", metavar="SPEC",
                    help="test-time augmentation: every batch runs once per flip / rotation the spec allows (hflip, "
                         "vflip, rot90, d4) and the predictions are averaged (default: one run)")
@@ -142,6 +156,10 @@ def _augment_arg(text: str) -> str:
 
 def _tta_arg(text: str) -> str:
     return parse_tta(text).spec
+
+
+def _label_smoothing(text: str) -> float:
+    return check_label_smoothing(float(text))
 
 
 def _temperature(text: str) -> float:
@@ -201,6 +219,8 @@ def main(argv=None) -> None:
             ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, max_grad_norm=args.max_grad_norm,
             learn_comm=args.learn_comm, comm_lr=args.comm_lr,
             temperature=args.temperature, explore_eps=args.explore_eps, augment=args.augment,
+            class_weights=args.class_weights, label_smoothing=args.label_smoothing, error_steps=args.error_steps,
+            weight_rewards=args.weight_rewards,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":

@@ -90,7 +90,9 @@ CNNOP_HOOKS = ("marl_cnn_dgrad", "marl_cnn_dgrad_scratch", "marl_cnn_bwd_plan", 
 EXPLORE_ENTRIES = ("marl_policy_explore",)
 # ... and the augmenting batch gather that include/marl_hip_augment.h declares (likewise; augment.py binds it)
 AUGMENT_ENTRIES = ("marl_batch_augment", "marl_batch_augment_plan")
-_HOOKS = ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES
+# ... and the options of the vote error and the rewards that include/marl_hip_classloss.h declares (likewise)
+CLASSLOSS_ENTRIES = ("marl_class_loss",)
+_HOOKS = ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES
 
 
 class CnnBwdPlan(C.Structure):
@@ -211,6 +213,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_comm_grad.argtypes = [_cfgp, _vp, _sz, _vp, _sz, _i, _vp, _vp, _sz, _vp]
     lib.marl_comm_range.argtypes = [_i, _i, _i]
     lib.marl_policy_explore.argtypes = [_f, _f, _i]
+    lib.marl_class_loss.argtypes = [_vp, _i, _f, _vp, _i, _i]
     lib.marl_batch_augment.argtypes = [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
     lib.marl_batch_augment_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
     lib.marl_ln_silu_bwd.argtypes = [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _vp, _sz, _i, _i, _vp]

@@ -4,7 +4,7 @@ side loads on the other.  ``build_marl`` is the constructor path for the hot-pat
 
 import json
 from os.path import exists, isfile
-from typing import List, Optional, Tuple
+from typing import List, Optional, Tuple, Union
 
 from pydantic import BaseModel
 
@@ -117,6 +117,12 @@ class TrainConfig(BaseModel):
     # --augment: device-side augmentation of the training split in the command-line spelling (augment.parse); a run-time
     # choice like the exploration controls, not written to marl.json.  None: every batch is the plain gather
     augment: Optional[str] = None
+    # options of the vote error and the rewards (class_loss.py), run-time choices like the two above: "balanced", a
+    # .npy path or one weight per class; the smoothing; all | last[:K] | linear; rewards times the class weight
+    class_weights: Optional[Union[str, Tuple[float, ...]]] = None
+    label_smoothing: float = 0.0
+    error_steps: Optional[str] = None
+    weight_rewards: bool = False
 
 
 class EvalConfig(BaseModel):

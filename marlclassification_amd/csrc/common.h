@@ -1063,6 +1063,12 @@ struct LossCommon {
     const int64_t* y;     // [Nb]
     float* scratch;       // rewards / returns / raw advantages [3][Ns*R], vote error, partial sums
     int ns, na, nb, nc;
+    // options of the vote error and the rewards (marl_class_loss; cls == false: the plain kernels, as ever)
+    bool cls = false;
+    const float* cls_w = nullptr;   // [nc] class weights, nullptr = all ones
+    const float* cls_sw = nullptr;  // [ns] step weights of the vote error, nullptr = all ones
+    float cls_eps = 0.f;            // label smoothing
+    bool cls_wrew = false;          // rewards times w[y]
 };
 // ... and what the two loss passes (A2C, PPO) add: the policy term's input, the output gradients, the scalars and
 // the optional entropy bonus (probs != nullptr)

@@ -22,6 +22,7 @@
 #include "../../include/marl_hip_rowops.h"
 #include "../../include/marl_hip_cnnops.h"
 #include "../../include/marl_hip_explore.h"
+#include "../../include/marl_hip_classloss.h"
 #include "common.h"
 
 namespace marl {
@@ -704,6 +705,19 @@ static void explore_sample_args(SampleArgs& a) {
         a.rng_on = 0;
     }
 }
+// marl_class_loss (marl_hip_classloss.h): options of the vote error and the rewards of every loss entry,
+// process-global like the three above.  on = anything was installed (neutral values too): only then does a loss
+// entry take the option instances of the two kernels - with it off every entry launches what it always launched.
+struct ClassLoss {
+    bool on;
+    const float* w;   // [nc] device, nullptr = all ones
+    int nc;
+    float eps;
+    const float* sw;  // [ns] device, nullptr = all ones
+    int ns;
+    bool wrew;
+};
+static ClassLoss g_class_loss = {false, nullptr, 0, 0.f, nullptr, 0, false};
 
 static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void* ews, size_t ebytes,
                     int train, void* stream, Ctx& c) {
@@ -2487,6 +2501,23 @@ int marl_policy_explore(float temperature, float eps, int greedy) {
     return MARL_OK;
 }
 
+int marl_class_loss(const float* class_weights_dev, int nb_class, float label_smoothing,
+                    const float* step_weights_dev, int nb_steps, int weight_rewards) {
+    if (!std::isfinite(label_smoothing) || !(label_smoothing >= 0.f && label_smoothing < 1.f)) {
+        set_error("class_loss: label_smoothing %g outside [0, 1)", (double)label_smoothing);
+        return MARL_EINVAL;
+    }
+    if (nb_class < 0 || nb_steps < 0 || (class_weights_dev && nb_class == 0) || (step_weights_dev && nb_steps == 0)) {
+        set_error("class_loss: %d class weights / %d step weights: a pointer needs its length, and none is negative",
+                  nb_class, nb_steps);
+        return MARL_EINVAL;
+    }
+    const bool on = class_weights_dev || step_weights_dev || label_smoothing != 0.f || weight_rewards != 0;
+    g_class_loss = ClassLoss{on, class_weights_dev, nb_class, label_smoothing, step_weights_dev, nb_steps,
+                             weight_rewards != 0};
+    return MARL_OK;
+}
+
 size_t marl_comm_grad_scratch_bytes(const marl_config* cfg) {
     Dims d;
     if (make_dims(cfg, d) != MARL_OK) return 0;
@@ -2634,6 +2665,12 @@ static int loss_entry(const marl_config* cfg, void* episode_ws, size_t episode_w
                   e.total * sizeof(float));
         return MARL_ESIZE;
     }
+    const ClassLoss& k = g_class_loss;
+    if (k.on && ((k.nc != 0 && k.nc != d.nC) || (k.ns != 0 && k.ns != d.ns))) {
+        set_error("%s: the installed class-loss options are for %d classes / %d steps, the configuration has %d / %d",
+                  who, k.nc, k.ns, d.nC, d.ns);
+        return MARL_EINVAL;
+    }
     a.preds = step_preds;
     a.values = step_values;
     a.y = y;
@@ -2642,6 +2679,13 @@ static int loss_entry(const marl_config* cfg, void* episode_ws, size_t episode_w
     a.na = d.na;
     a.nb = d.nb;
     a.nc = d.nC;
+    a.cls = k.on;  // (marl_class_loss; off: the fields keep their neutral defaults and nobody reads them)
+    if (k.on) {
+        a.cls_w = k.w;
+        a.cls_sw = k.sw;
+        a.cls_eps = k.eps;
+        a.cls_wrew = k.wrew;
+    }
     return MARL_OK;
 }
 
@@ -3045,6 +3089,7 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     // exploration controls (marl_policy_explore): "explore" = installed; "explore_form" = where the forward loop
     // samples under them (0 = off, 1 = the EXPLORE epilogue of the chained launch, 2 = sample_kernel's EXPLORE form)
     else if (!strcmp(key, "explore")) *value = g_explore.on;
+    else if (!strcmp(key, "class_loss")) *value = g_class_loss.on;  // (marl_class_loss: a setting is installed)
     else if (!strcmp(key, "explore_form"))
         *value = !g_explore.on ? 0 : (use_chain(d) && use_panel_sample(d)) ? 1 : 2;
     else if (!strcmp(key, "comm_form"))

@@ -4,6 +4,8 @@
 //   (functions.py:35-51, flip-cumsum order) -> global mean / unbiased std
 //   (functions.py:54-55) -> path / critic terms and gradients (trainer.py:96-111).
 // All cross-thread sums go through fixed-order partials (fp64) -> bit-reproducible.
+// Under marl_class_loss (include/marl_hip_classloss.h) the rewards and the vote error run their option instances:
+// class weights, label smoothing, step weights, rewards times the label's weight - same launches, same order.
 #include "common.h"
 
 #include <cassert>
@@ -143,11 +145,24 @@ static void with_grads_instance(const LossGradArgs& a, F&& launch) {
         launch(std::true_type{}, std::false_type{});
 }
 
+// Options of the vote error and the rewards (marl_class_loss, include/marl_hip_classloss.h) as the OPT instances of
+// the two kernels below take them; the plain instances carry an empty struct and none of it.
+struct NoClassOpt {};
+struct ClassOpt {
+    const float* w;   // [nC] class weights, nullptr = all ones
+    const float* sw;  // [Ns] step weights, nullptr = all ones
+    float keep;       // 1 - eps
+    float eps_nc;     // eps / nC
+};
+
 // rew[t, r] = (log nC - CE(preds[t, r, :], y[b])) / log nC ; one wave per (t, r)
+// OPT (weight_rewards): times w[y[b]], the cost-sensitive reward
+template <bool OPT>
 __global__ __launch_bounds__(256) void loss_rewards_kernel(const float* __restrict__ preds,
                                                            const int64_t* __restrict__ y,
                                                            float* __restrict__ rew, int64_t NR,
-                                                           int nb, int nc, float rnd) {
+                                                           int nb, int nc, float rnd,
+                                                           std::conditional_t<OPT, ClassOpt, NoClassOpt> o) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= NR) return;
@@ -161,16 +176,25 @@ __global__ __launch_bounds__(256) void loss_rewards_kernel(const float* __restri
     if (lane == 0) {
         const int b = (int)(row % nb);
         const float ce = -(p[y[b]] - mx - logf(s));
-        rew[row] = (rnd - ce) / rnd;
+        if constexpr (OPT)
+            rew[row] = o.w[y[b]] * ((rnd - ce) / rnd);  // (launched with weights only)
+        else
+            rew[row] = (rnd - ce) / rnd;
     }
 }
 
 // err[t, b] = CE(mean_a preds[t, a, b, :], y[b]);  g_preds[t, a, b, c] = (softmax - onehot) / R
+// OPT: with nll_c = -(z_c - max z - log sum exp(z - max z)), q_c = (1 - eps) w_y 1[c == y] + (eps / nC) w_c:
+//   err[t, b] = s_t sum_c q_c nll_c,   g_preds[t, a, b, c] = s_t / R (softmax_c sum_c' q_c' - q_c)
+// sum_c w_c nll_c and sum_c w_c are two more wave sums (fixed order); the wave reads w once, into LDS beside the vote.
+// With w == 1, eps == 0, s_t == 1 every product is by 1 and every sum adds a zero: the plain instance's bits.
+template <bool OPT>
 __global__ __launch_bounds__(256) void loss_error_kernel(const float* __restrict__ preds,
                                                          const int64_t* __restrict__ y,
                                                          float* __restrict__ err,
                                                          float* __restrict__ g_preds, int ld_gp,
-                                                         int ns, int na, int nb, int nc) {
+                                                         int ns, int na, int nb, int nc,
+                                                         std::conditional_t<OPT, ClassOpt, NoClassOpt> o) {
     __shared__ float pbar[4][1024];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t tb = (int64_t)blockIdx.x * 4 + wave;
@@ -190,13 +214,44 @@ __global__ __launch_bounds__(256) void loss_error_kernel(const float* __restrict
     for (int c = lane; c < nc; c += 64) s += expf(pbar[wave][c] - mx);
     s = wsum(s);
     const int yb = (int)y[b];
-    if (lane == 0) err[tb] = -(pbar[wave][yb] - mx - logf(s));
-    if (g_preds) {
-        const float inv = 1.0f / (float)R;
+    if constexpr (!OPT) {
+        if (lane == 0) err[tb] = -(pbar[wave][yb] - mx - logf(s));
+        if (g_preds) {
+            const float inv = 1.0f / (float)R;
+            for (int c = lane; c < nc; c += 64) {
+                const float g = (expf(pbar[wave][c] - mx) / s - (c == yb ? 1.0f : 0.0f)) * inv;
+                for (int a = 0; a < na; ++a)
+                    g_preds[((int64_t)t * R + (int64_t)a * nb + b) * ld_gp + c] = g;
+            }
+        }
+    } else {
+        __shared__ float wcls[4][1024];
+        const float ls = logf(s);
+        float wn = 0.f, wt = 0.f;  // sum_c w_c nll_c, sum_c w_c
         for (int c = lane; c < nc; c += 64) {
-            const float g = (expf(pbar[wave][c] - mx) / s - (c == yb ? 1.0f : 0.0f)) * inv;
-            for (int a = 0; a < na; ++a)
-                g_preds[((int64_t)t * R + (int64_t)a * nb + b) * ld_gp + c] = g;
+            const float wc = o.w ? o.w[c] : 1.0f;
+            wcls[wave][c] = wc;
+            wn = fmaf(wc, -(pbar[wave][c] - mx - ls), wn);
+            wt += wc;
+        }
+        wn = wsum(wn);
+        wt = wsum(wt);
+        const float st = o.sw ? o.sw[t] : 1.0f;
+        const float qy = o.keep * (o.w ? o.w[yb] : 1.0f);  // the label's own share of q
+        if (lane == 0) {
+            float e = qy * -(pbar[wave][yb] - mx - ls);
+            if (o.eps_nc != 0.f) e = fmaf(o.eps_nc, wn, e);
+            err[tb] = st * e;
+        }
+        if (g_preds) {
+            const float sc = st * (1.0f / (float)R);
+            const float qs = o.eps_nc != 0.f ? fmaf(o.eps_nc, wt, qy) : qy;  // sum_c q_c
+            for (int c = lane; c < nc; c += 64) {
+                const float qc = (c == yb ? qy : 0.0f) + o.eps_nc * wcls[wave][c];
+                const float g = (expf(pbar[wave][c] - mx) / s * qs - qc) * sc;
+                for (int a = 0; a < na; ++a)
+                    g_preds[((int64_t)t * R + (int64_t)a * nb + b) * ld_gp + c] = g;
+            }
         }
     }
 }
@@ -315,6 +370,33 @@ __global__ __launch_bounds__(256) void loss_final_kernel(
     }
 }
 
+// the one place that picks the instance of the rewards / vote-error kernel: the plain one unless marl_class_loss
+// installed options (the rewards: unless it installed weight_rewards with class weights)
+static ClassOpt class_opt(const LossCommon& a) {
+    return ClassOpt{a.cls_w, a.cls_sw, 1.0f - a.cls_eps, a.cls_eps / (float)a.nc};
+}
+
+static void launch_rewards(const LossCommon& a, float* rew, hipStream_t st) {
+    const int64_t NR = (int64_t)a.na * a.nb * a.ns;
+    const float rnd = (float)log((double)a.nc);
+    if (a.cls && a.cls_wrew && a.cls_w)
+        hipLaunchKernelGGL(loss_rewards_kernel<true>, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st, a.preds, a.y, rew,
+                           NR, a.nb, a.nc, rnd, class_opt(a));
+    else
+        hipLaunchKernelGGL(loss_rewards_kernel<false>, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st, a.preds, a.y,
+                           rew, NR, a.nb, a.nc, rnd, NoClassOpt{});
+}
+
+static void launch_error(const LossGradArgs& a, float* err, hipStream_t st) {
+    const dim3 grid((unsigned)cdiv((int64_t)a.ns * a.nb, 4));
+    if (a.cls)
+        hipLaunchKernelGGL(loss_error_kernel<true>, grid, dim3(256), 0, st, a.preds, a.y, err, a.g_preds, a.ld_gp, a.ns,
+                           a.na, a.nb, a.nc, class_opt(a));
+    else
+        hipLaunchKernelGGL(loss_error_kernel<false>, grid, dim3(256), 0, st, a.preds, a.y, err, a.g_preds, a.ld_gp,
+                           a.ns, a.na, a.nb, a.nc, NoClassOpt{});
+}
+
 int launch_loss(const LossArgs& a, hipStream_t st) {
     if (a.nc > 1024) {
         set_error("nb_class %d > 1024 unsupported by the loss kernel", a.nc);
@@ -324,13 +406,9 @@ int launch_loss(const LossArgs& a, hipStream_t st) {
     LossLayout L = loss_layout(a.scratch, a.ns, a.na, a.nb);
     double* stats = reinterpret_cast<double*>(a.adv_stats);
     if (a.phase == 0 || a.phase == 1) {
-        const float rnd = (float)log((double)a.nc);
-        hipLaunchKernelGGL(loss_rewards_kernel, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st,
-                           a.preds, a.y, L.rew, NR, a.nb, a.nc, rnd);
+        launch_rewards(a, L.rew, st);
         MARL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(loss_error_kernel, dim3((unsigned)cdiv((int64_t)a.ns * a.nb, 4)),
-                           dim3(256), 0, st, a.preds, a.y, L.err, a.g_preds, a.ld_gp, a.ns, a.na,
-                           a.nb, a.nc);
+        launch_error(a, L.err, st);
         MARL_LAUNCH_CHECK();
         hipLaunchKernelGGL(loss_returns_kernel, dim3((unsigned)L.blocksC), dim3(256), 0, st, L.rew,
                            a.values, L.ret, L.adv, L.part_adv, a.ns, R, a.gamma);
@@ -409,9 +487,7 @@ int launch_advantages(const AdvArgs& a, hipStream_t st) {
     LossLayout L = loss_layout(a.scratch, a.ns, a.na, a.nb);
     double* stats = reinterpret_cast<double*>(a.adv_stats);
     if (a.phase == 0 || a.phase == 1) {
-        const float rnd = (float)log((double)a.nc);
-        hipLaunchKernelGGL(loss_rewards_kernel, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st, a.preds, a.y, L.rew,
-                           NR, a.nb, a.nc, rnd);
+        launch_rewards(a, L.rew, st);
         MARL_LAUNCH_CHECK();
         if (a.lam == 1.0f)
             hipLaunchKernelGGL(loss_returns_kernel, dim3((unsigned)L.blocksC), dim3(256), 0, st, L.rew, a.values,
@@ -515,8 +591,7 @@ int launch_ppo_loss(const PpoArgs& a, hipStream_t st) {
     const int64_t R = (int64_t)a.na * a.nb, NR = R * a.ns, nerr = (int64_t)a.ns * a.nb;
     LossLayout L = loss_layout(a.scratch, a.ns, a.na, a.nb);
     double* extra = extra_partials(L, 3);  // entropy / old_logp - logp / clipped count
-    hipLaunchKernelGGL(loss_error_kernel, dim3((unsigned)cdiv(nerr, 4)), dim3(256), 0, st, a.preds, a.y, L.err,
-                       a.g_preds, a.ld_gp, a.ns, a.na, a.nb, a.nc);
+    launch_error(a, L.err, st);
     MARL_LAUNCH_CHECK();
     with_grads_instance(a, [&](auto ent, auto vec) {
         hipLaunchKernelGGL((ppo_grads_kernel<decltype(ent)::value, decltype(vec)::value>), dim3((unsigned)L.blocksE),

@@ -226,6 +226,13 @@ class HipEngine:
         from . import explore as _explore
 
         self.exploration = _explore.DEFAULT
+        # options of the vote error and the rewards (set_class_loss: a class_loss.ClassLoss, None = the reference's
+        # loss): per-process state of the library too - installed around every loss call and cleared behind it.  The
+        # device copies of the class / step weights (ClassLoss -> (w, s), either None) are made once per setting and
+        # kept for the engine's life - a captured graph keeps the pointers, so none is ever dropped: nC + Ns floats
+        # per DISTINCT setting, which is expected to be one or a few per run (not a per-step schedule)
+        self.class_loss = None
+        self._class_loss_dev: Dict[object, Tuple[Optional[th.Tensor], Optional[th.Tensor]]] = {}
 
     # -- communication graph ----------------------------------------------------------
     def set_comm(self, matrix) -> None:
@@ -348,6 +355,50 @@ class HipEngine:
             self._agg_comm(fn, *args)
         finally:
             self.lib.marl_policy_explore(1.0, 0.0, 0)
+
+    def set_class_loss(self, class_loss=None) -> None:
+        """The options of the vote error and the rewards (a ``class_loss.ClassLoss``: class weights, label smoothing,
+        step weights, cost-sensitive rewards) for every later ``a2c_loss`` / ``advantages`` / ``ppo_loss`` of this
+        engine; None restores the reference's loss.  Handled like ``set_exploration``: kept here, installed in the
+        library (marl_class_loss) around each of those calls and cleared behind it.  Every distinct setting keeps
+        its device copy of the weights (nC + Ns floats) for the engine's life, because a captured graph may read it:
+        use one or a few settings per run, not a new one per step.  ValueError for anything but a
+        ``ClassLoss`` and - here if the engine is configured, else at the call - for one whose classes / steps are not
+        the configured ones."""
+        from . import class_loss as _cl
+
+        if class_loss is not None and not isinstance(class_loss, _cl.ClassLoss):
+            raise ValueError(f"class_loss must be a class_loss.ClassLoss or None, got {type(class_loss).__name__}")
+        if class_loss is not None and self.cfg is not None:
+            self._check_class_loss(class_loss)
+        self.class_loss = class_loss
+
+    def _check_class_loss(self, c) -> None:
+        cfg = self.cfg
+        if c.nb_class != cfg.nb_class or c.nb_steps != cfg.nb_steps:
+            raise ValueError(f"class_loss is for {c.nb_class} classes / {c.nb_steps} steps, the engine is configured "
+                             f"for {cfg.nb_class} / {cfg.nb_steps}")
+
+    def _loss_call(self, fn, *args) -> None:
+        """A loss entry under this engine's ``class_loss`` (None, or one with nothing given: the plain call and
+        nothing more).  Checked against the configured classes / steps before anything is enqueued."""
+        c = self.class_loss
+        if c is None or c.is_default:
+            check(fn(*args))
+            return
+        self._check_class_loss(c)
+        dev = self._class_loss_dev.get(c)
+        if dev is None:
+            dev = self._class_loss_dev[c] = tuple(
+                None if v is None else th.tensor(v, dtype=th.float32, device=self.device)
+                for v in (c.class_weights, c.step_weights))
+        w, s = dev
+        check(self.lib.marl_class_loss(_ptr(w), c.nb_class if w is not None else 0, C.c_float(c.label_smoothing),
+                                       _ptr(s), c.nb_steps if s is not None else 0, int(c.weight_rewards)))
+        try:
+            check(fn(*args))
+        finally:
+            self.lib.marl_class_loss(None, 0, C.c_float(0.0), None, 0, 0)
 
     def _agg_comm(self, fn, *args) -> None:
         """A library call that aggregates messages: under this engine's matrix, if it has one."""
@@ -621,6 +672,8 @@ class HipEngine:
         bufs: Optional[Tuple[th.Tensor, ...]] = None, entropy_coef: float = 0.0,
     ) -> Tuple[th.Tensor, ...]:
         """Returns (g_preds, g_logp, g_values, scalars[4], adv_stats[3] float64).
+        Under ``set_class_loss`` (here, in ``advantages`` and in ``ppo_loss``): class weights, label smoothing and step
+        weights of the vote error, cost-sensitive rewards.
         ``entropy_coef`` > 0 (marl_a2c_loss_entropy_fwd_bwd; ``out.step_probs`` needed): the loss minus
         ``entropy_coef * mean_{a,b} sum_t H``; returns (g_preds, g_logp, g_values, scalars[5], adv_stats, g_probs)
         with scalars[4] = the mean entropy.  0: the plain entry."""
@@ -644,11 +697,12 @@ class HipEngine:
             entry = self.lib.marl_a2c_loss_entropy_fwd_bwd
             bonus = (_need(out.step_probs, th.float32, "step_probs").data_ptr(), C.c_float(entropy_coef))
             g_bonus = (bufs[5].data_ptr(),)
-        check(entry(
+        self._loss_call(
+            entry,
             C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(),
             out.step_log_probas.data_ptr(), out.step_values.data_ptr(), y.data_ptr(),
             C.c_float(gamma), *bonus, gp.data_ptr(), gl.data_ptr(), gv.data_ptr(), *g_bonus,
-            sc.data_ptr(), st.data_ptr(), phase, _stream(dev)))
+            sc.data_ptr(), st.data_ptr(), phase, _stream(dev))
         return bufs
 
     def _grad_bufs(self, out: EpisodeTensors, n_scalars: int) -> Tuple[th.Tensor, ...]:
@@ -696,10 +750,11 @@ class HipEngine:
             bufs = self.new_ppo_bufs(out, out.step_probs is not None)
         self._check_ppo_bufs(out, bufs, "advantages")
         ews = self.episode_ws(True)
-        check(self.lib.marl_advantages(
+        self._loss_call(
+            self.lib.marl_advantages,
             C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(), out.step_values.data_ptr(),
             y.data_ptr(), C.c_float(gamma), C.c_float(lam), bufs[5].data_ptr(), bufs[6].data_ptr(),
-            bufs[4].data_ptr(), phase, _stream(self.device)))
+            bufs[4].data_ptr(), phase, _stream(self.device))
         return bufs
 
     def ppo_loss(
@@ -734,12 +789,13 @@ class HipEngine:
             raise ValueError("ppo_loss(entropy_coef > 0): buffers from new_ppo_bufs(out, True) needed")
         probs = _need(out.step_probs, th.float32, "step_probs") if ent else None
         ews = self.episode_ws(True)
-        check(self.lib.marl_ppo_loss_fwd_bwd(
+        self._loss_call(
+            self.lib.marl_ppo_loss_fwd_bwd,
             C.byref(cfg), ews.data_ptr(), _nbytes(ews), out.step_preds.data_ptr(),
             out.step_log_probas.data_ptr(), out.step_values.data_ptr(), y.data_ptr(), ins[0].data_ptr(),
             ins[1].data_ptr(), ins[2].data_ptr(), C.c_float(clip_eps), _ptr(probs), C.c_float(entropy_coef),
             bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[7].data_ptr() if ent else None,
-            bufs[3].data_ptr(), _stream(self.device)))
+            bufs[3].data_ptr(), _stream(self.device))
         return bufs
 
     def grad_clip(self, grads: th.Tensor, max_norm: float, grad_scale: float = 1.0) -> th.Tensor:

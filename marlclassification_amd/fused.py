@@ -9,6 +9,7 @@ all-reduce (parallel.py).  No host synchronisation happens inside ``iteration``.
 
 from __future__ import annotations
 
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -166,6 +167,48 @@ def comm_update_for(current: Optional[CommUpdate], source, leaves, comm_lr: Opti
     return CommUpdate(source, leaves(), comm_lr)
 
 
+class ClassLossOptions:
+    """The four loss options as ``Trainer`` and ``FusedA2C`` take them (``class_weights``, ``label_smoothing``,
+    ``error_step_weights``: a ``class_loss.step_schedule`` spec or a sequence, ``weight_rewards``), checked as far as
+    they can be without the episode's sizes; ``resolve`` makes the ``class_loss.ClassLoss`` of a configured engine -
+    once per (classes, steps) - or None with all four at their defaults; ``with installed(eng):`` runs loss calls
+    under it (``HipEngine.set_class_loss``) and puts the engine's own setting back behind them, so another trainer on
+    the same engine never inherits it - with all four at their defaults the engine's own setting is left alone."""
+
+    def __init__(self, class_weights=None, label_smoothing: float = 0.0, error_step_weights=None,
+                 weight_rewards: bool = False) -> None:
+        from . import class_loss as _cl
+
+        _cl.check_label_smoothing(label_smoothing)
+        if isinstance(error_step_weights, str):
+            _cl.parse_error_steps(error_step_weights)
+        if class_weights is not None:  # (finite, >= 0, not all zero; the length waits for the class count)
+            class_weights = _cl.check_vector(class_weights, "class weights", len(class_weights))
+        self.options = (class_weights, label_smoothing, error_step_weights, weight_rewards)
+        self._resolved: Dict[Tuple[int, int], object] = {}
+
+    def resolve(self, eng: HipEngine):
+        from . import class_loss as _cl
+
+        key = (eng.cfg.nb_class, eng.cfg.nb_steps)
+        if key not in self._resolved:
+            self._resolved[key] = _cl.from_options(key[0], key[1], *self.options)
+        return self._resolved[key]
+
+    @contextmanager
+    def installed(self, eng: HipEngine):
+        c = self.resolve(eng)
+        if c is None:
+            yield
+            return
+        before = eng.class_loss
+        eng.set_class_loss(c)
+        try:
+            yield
+        finally:
+            eng.class_loss = before
+
+
 def ppo_bufs_fit(bufs, out: EpisodeTensors, entropy: bool) -> bool:
     """Do the persistent ``HipEngine.new_ppo_bufs`` tensors match this episode?"""
     return (bufs is not None and len(bufs) == (8 if entropy else 7) and bufs[0].shape == out.step_preds.shape and
@@ -239,8 +282,15 @@ class FusedA2C:
                  use_graph: bool = False, entropy_coef: float = 0.0, ppo_epochs: int = 1,
                  ppo_clip: float = 0.2, gae_lambda: float = 1.0,
                  max_grad_norm: Optional[float] = None, comm_lr: Optional[float] = None,
-                 temperature: Optional[float] = None, explore_eps: Optional[float] = None) -> None:
-        """``temperature`` / ``explore_eps``: the behaviour policy of the rollouts (``HipEngine.set_exploration``;
+                 temperature: Optional[float] = None, explore_eps: Optional[float] = None,
+                 class_weights=None, label_smoothing: float = 0.0, error_step_weights=None,
+                 weight_rewards: bool = False) -> None:
+        """``class_weights`` / ``label_smoothing`` / ``error_step_weights`` / ``weight_rewards``: the options of the
+        vote error and the rewards (``class_loss.py``) of every loss call of this object - installed on the engine
+        around them and taken off behind them; all four at their defaults: the engine's own ``set_class_loss`` setting
+        (none: today's sequence of calls, verbatim) applies.
+
+        ``temperature`` / ``explore_eps``: the behaviour policy of the rollouts (``HipEngine.set_exploration``;
         replays run under the rollout's setting) - plain attributes that may be changed between iterations (a captured
         graph is keyed by the setting); None: the engine's own setting is left alone.
 
@@ -259,6 +309,7 @@ class FusedA2C:
 
         _explore.check(1.0 if temperature is None else temperature, 0.0 if explore_eps is None else explore_eps)
         self.temperature, self.explore_eps = temperature, explore_eps
+        self._class_loss = ClassLossOptions(class_weights, label_smoothing, error_step_weights, weight_rewards)
         self.comm_lr = None if comm_lr is None else float(comm_lr)
         self._comm_update: Optional[CommUpdate] = None
         if not entropy_coef >= 0.0:
@@ -334,10 +385,13 @@ class FusedA2C:
         # re-laid-out - the graph must be captured again)
         beta = self.entropy_coef
         self._explore()
+        closs = self._class_loss.resolve(eng) if eng.cfg is not None else None
         key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch, beta,
                None if eng.comm is None else eng.comm.data_ptr(),  # (the captured kernels keep the matrix pointer
                eng.comm_range,                                     # and the range's radius / metric / normalize
-               eng.exploration)                                    # and the exploration constants in their arguments)
+               eng.exploration,                                    # and the exploration constants in their arguments)
+               # (and the loss options, this object's or else the engine's own: their constants and the engine's device
+               closs if closs is not None else eng.class_loss)  # copies of the weights, one pair per value)
         if self._graph is None or self._graph[0] != key:
             if self._graph is not None:
                 eng.lib.marl_graph_destroy(self._graph[1])
@@ -359,7 +413,8 @@ class FusedA2C:
                     eng.draw_episode(seed, 0, into=draws, counters=cnt)
                     eng.episode_forward(img, draws[0], draws[1], draws[2], draws[3], draws[4], None,
                                         None, True, rng=(seed, 0), out=out, counters=cnt)
-                    bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
+                    with self._class_loss.installed(eng):
+                        bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
                     gp, gl, gv, scalars = bufs[:4]
                     eng.episode_backward(gp, gl, gv, gviews, g_probs=bufs[5] if beta > 0 else None)
                     eng.adam(self.flat.params, self.flat.grads, self.flat.exp_avg,
@@ -408,7 +463,8 @@ class FusedA2C:
         if (self._loss_bufs is None or self._loss_bufs[0].shape != out.step_preds.shape or
                 len(self._loss_bufs) != (6 if beta > 0 else 5)):
             self._loss_bufs = eng.new_loss_bufs(out, beta > 0)
-        bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
+        with self._class_loss.installed(eng):
+            bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
         gp, gl, gv, scalars = bufs[:4]
         apply_update(eng, self.flat, gp, gl, gv, bufs[5] if beta > 0 else None, self._gviews, self.lr,
                      self.allreduce, None, self.pack, self._comm())
@@ -430,12 +486,13 @@ class FusedA2C:
         bufs = self._ppo_bufs
         if not ppo_bufs_fit(bufs, out, ent):
             bufs = self._ppo_bufs = eng.new_ppo_bufs(out, ent)
-        eng.advantages(out, y, self.gamma, self.gae_lambda, 0, bufs)
-        norm = ppo_epochs_loop(
-            eng, self.flat, out, y, bufs, self.ppo_epochs, self.ppo_clip, beta, self.lr, self.allreduce,
-            self.max_grad_norm, self._gviews,
-            replay=lambda: self.rollout(img, draws, True, forced_actions=out.step_actions, probs=ent),
-            repack=self.pack, comm=self._comm())
+        with self._class_loss.installed(eng):
+            eng.advantages(out, y, self.gamma, self.gae_lambda, 0, bufs)
+            norm = ppo_epochs_loop(
+                eng, self.flat, out, y, bufs, self.ppo_epochs, self.ppo_clip, beta, self.lr, self.allreduce,
+                self.max_grad_norm, self._gviews,
+                replay=lambda: self.rollout(img, draws, True, forced_actions=out.step_actions, probs=ent),
+                repack=self.pack, comm=self._comm())
         if norm is not None:
             self.last_grad_norm = norm
         return out, bufs[3]

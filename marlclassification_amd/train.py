@@ -54,6 +54,15 @@ def _dataset(model_config: ModelConfig, train_config: TrainConfig):
     return dataset
 
 
+def _split_labels(dataset, indices) -> th.Tensor:
+    """The labels of ``indices`` without decoding an image (both dataset classes keep them in memory)."""
+    if isinstance(dataset, SyntheticImages):
+        return dataset.y[th.as_tensor(indices, dtype=th.int64)]
+    if isinstance(dataset, ImageFolderU8):
+        return th.tensor([dataset.items[i][1] for i in indices], dtype=th.int64)
+    return th.tensor([int(dataset[i][1]) for i in indices], dtype=th.int64)
+
+
 class ShardedBatchSampler(Sampler):
     """Batches of dataset INDICES for one rank.  Every rank derives the same shuffled order of
     the same index list from (seed, epoch) and takes its contiguous slice of every global batch,
@@ -183,6 +192,15 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
     g = th.Generator().manual_seed(base_seed)  # same split on every rank
     idx = th.randperm(len(dataset), generator=g)
     cut = int(0.85 * idx.shape[0])
+    # --class-weights: `balanced` counts the labels of the WHOLE training split (before the per-rank sharding: every
+    # rank gets the same weights); a file or a list is checked against the class count
+    from . import class_loss as _class_loss
+
+    class_weights = _class_loss.resolve_class_weights(
+        train_config.class_weights, model_config.nb_class,
+        _split_labels(dataset, idx[:cut].tolist()) if train_config.class_weights == "balanced" else None)
+    if train_config.error_steps is not None:
+        _class_loss.step_schedule(train_config.error_steps, main_config.step)  # (last:K against --step)
     loaders, samplers = [], []
     workers = loader_workers(dataset)
     resident = resident_fits(dataset)
@@ -221,16 +239,22 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
                       ppo_clip=train_config.ppo_clip, gae_lambda=train_config.gae_lambda,
                       max_grad_norm=train_config.max_grad_norm,
                       comm_lr=((train_config.comm_lr if train_config.comm_lr is not None else
-                                train_config.learning_rate) if learned is not None else None))
+                                train_config.learning_rate) if learned is not None else None),
+                      class_weights=class_weights, label_smoothing=train_config.label_smoothing,
+                      error_step_weights=train_config.error_steps, weight_rewards=train_config.weight_rewards)
     from . import explore as _explore
 
-    t_ends, e_ends = train_config.temperature, train_config.explore_eps
+    t_ends, e_ends, cw_spec = train_config.temperature, train_config.explore_eps, train_config.class_weights
     if rank == 0:
         print("update: " + ", ".join(f"{k}={getattr(train_config, k)}" for k in (
             "entropy_coef", "ppo_epochs", "ppo_clip", "gae_lambda", "max_grad_norm")) +
               (f", learn_comm on {model_config.comm or 'full'}" if learned is not None else "") +
               (f", temperature {t_ends}, explore_eps {e_ends}" if t_ends or e_ends else "") +
-              (f", augment {policy.spec}" if policy is not None else ""), flush=True)
+              (f", augment {policy.spec}" if policy is not None else "") +
+              (f", class weights {cw_spec if isinstance(cw_spec, str) else 'given'}" if cw_spec is not None else "") +
+              (f", label_smoothing {train_config.label_smoothing}" if train_config.label_smoothing else "") +
+              (f", error steps {train_config.error_steps}" if train_config.error_steps else "") +
+              (", weighted rewards" if train_config.weight_rewards else ""), flush=True)
     for e in range(train_config.nb_epoch):
         for bs in samplers:
             bs.set_epoch(e)

@@ -16,8 +16,8 @@ import torch as th
 
 from ..core import EpisodeSampler
 from ..engine import EpisodeTensors
-from ..fused import (CommUpdate, apply_update, check_ppo_options, comm_update_for, ppo_bufs_fit, ppo_epochs_loop,
-                     ppo_options_on)
+from ..fused import (ClassLossOptions, CommUpdate, apply_update, check_ppo_options, comm_update_for, ppo_bufs_fit,
+                     ppo_epochs_loop, ppo_options_on)
 from ..metrics import ConfusionMeter, LossMeter
 from ..networks import ModelsWrapper
 
@@ -44,8 +44,20 @@ class Trainer:
         comm_lr: Optional[float] = None,
         temperature: Optional[float] = None,
         explore_eps: Optional[float] = None,
+        class_weights=None,
+        label_smoothing: float = 0.0,
+        error_step_weights=None,
+        weight_rewards: bool = False,
     ) -> None:
-        """``temperature`` / ``explore_eps``: the behaviour policy of the rollouts, (1 - eps) softmax(z / T) + eps / nA
+        """``class_weights`` ([nb_class], >= 0) / ``label_smoothing`` (in [0, 1)) / ``error_step_weights`` (``all``,
+        ``last``, ``last:K``, ``linear`` or one weight per step) / ``weight_rewards``: the options of the vote error and
+        the rewards (``class_loss.py``: err[t,b] = s_t * weighted, smoothed cross-entropy of the vote; rewards times
+        w_y) in ``train_step`` and in every PPO epoch: each step installs them on the model's engine
+        (``HipEngine.set_class_loss``) around its loss calls and puts the engine's own setting back behind them, so a
+        second trainer on the same model never inherits them.  All four at their defaults: the engine's own setting
+        applies - without one the reference's loss, through today's sequence of calls.
+
+        ``temperature`` / ``explore_eps``: the behaviour policy of the rollouts, (1 - eps) softmax(z / T) + eps / nA
         (``ModelsWrapper.set_exploration``; replays and PPO epochs run under the rollout's setting).  Plain
         attributes that may be changed between ``train_step``s; each ``train_step`` hands the values that are not
         None to the model (its ``greedy`` flag stays); None: the model's own setting is left alone.
@@ -68,6 +80,9 @@ class Trainer:
 
         _explore.check(1.0 if temperature is None else temperature, 0.0 if explore_eps is None else explore_eps)
         self.temperature, self.explore_eps = temperature, explore_eps
+        if class_weights is not None and len(class_weights) != nb_class:
+            raise ValueError(f"class_weights must have nb_class = {nb_class} entries, got {len(class_weights)}")
+        self.__class_loss = ClassLossOptions(class_weights, label_smoothing, error_step_weights, weight_rewards)
         self.__comm_lr = None if comm_lr is None else float(comm_lr)
         self.__comm_update: Optional[CommUpdate] = None
         self.__model = model
@@ -144,7 +159,8 @@ class Trainer:
         if (bufs is None or len(bufs) != (6 if ent else 5) or bufs[0].shape != out.step_preds.shape or
                 (ent and bufs[5].shape != out.step_probs.shape)):
             bufs = self.__loss_bufs = eng.new_loss_bufs(out, ent)
-        self.__exact_phases(lambda phase: eng.a2c_loss(out, y, self.__gamma, phase, bufs, entropy_coef=beta))
+        with self.__class_loss.installed(eng):
+            self.__exact_phases(lambda phase: eng.a2c_loss(out, y, self.__gamma, phase, bufs, entropy_coef=beta))
         flat = model.flat_state()
         apply_update(eng, flat, bufs[0], bufs[1], bufs[2], bufs[5] if ent else None, flat.grad_views(), self.__lr,
                      self.__allreduce, None, lambda: model.mark_updated(eng), self.__comm())
@@ -163,14 +179,15 @@ class Trainer:
         if not ppo_bufs_fit(self.__ppo_bufs, out, ent):
             self.__ppo_bufs = eng.new_ppo_bufs(out, ent)
         bufs = self.__ppo_bufs
-        self.__exact_phases(lambda phase: eng.advantages(out, y, self.__gamma, self.__gae_lambda, phase, bufs))
         flat = model.flat_state()
-        norm = ppo_epochs_loop(
-            eng, flat, out, y, bufs, self.__ppo_epochs, self.__ppo_clip, beta, self.__lr, self.__allreduce,
-            self.__max_grad_norm, flat.grad_views(),
-            replay=lambda: sampler.run_episode_raw(img, train=True, draws=draws, probs=ent,
-                                                   forced=out.step_actions)[1],
-            repack=lambda: model.mark_updated(eng), comm=self.__comm())
+        with self.__class_loss.installed(eng):
+            self.__exact_phases(lambda phase: eng.advantages(out, y, self.__gamma, self.__gae_lambda, phase, bufs))
+            norm = ppo_epochs_loop(
+                eng, flat, out, y, bufs, self.__ppo_epochs, self.__ppo_clip, beta, self.__lr, self.__allreduce,
+                self.__max_grad_norm, flat.grad_views(),
+                replay=lambda: sampler.run_episode_raw(img, train=True, draws=draws, probs=ent,
+                                                       forced=out.step_actions)[1],
+                repack=lambda: model.mark_updated(eng), comm=self.__comm())
         if norm is not None:
             self.__grad_norm = norm
         return out, bufs[3]
