@@ -12,6 +12,7 @@ from .class_loss import check_label_smoothing, parse_class_weights, parse_error_
 from .comm import check_spelling, parse_range
 from .explore import check as check_exploration
 from .explore import parse_eps, parse_temperature
+from .optim import OptimOptions, parse_betas, parse_groups, parse_schedule
 from .config import EvalConfig, InferConfig, MainConfig, ModelConfig, TrainConfig
 from .networks.vision import CNN_BY_NAME
 
@@ -118,6 +119,34 @@ def build_parser() -> argparse.ArgumentParser:
                         "weights ramping linearly to 1 at the last step (default: all)")
     t.add_argument("--weight-rewards", action="store_true", dest="weight_rewards",
                    help="cost-sensitive rewards: every agent's reward is multiplied by its image's class weight")
+    t.add_argument("--weight-decay", type=_arg(_weight_decay), default=0.0, dest="weight_decay", metavar="W",
+                   help="decoupled (AdamW) weight decay of the matrices: conv and linear weights; biases and "
+                        "LayerNorm / GroupNorm gains do not decay (default: 0)")
+    t.add_argument("--decay-all", action="store_true", dest="decay_all",
+                   help="--weight-decay reaches every tensor, biases and norm gains included")
+    t.add_argument("--lr-groups", type=_arg(_lr_groups), default=None, dest="lr_groups",
+                   metavar="NAME=MULT[:WD],...",
+                   help="learning-rate multiplier (0 freezes) and optionally a weight decay per module: map_obs (= "
+                        "cnn), map_pos, encode_msg, decode_msg, belief_unit, action_unit, policy, critic, predict; "
+                        "e.g. cnn=0.1,policy=0,critic=1:0.01")
+    t.add_argument("--lr-schedule", type=_arg(_lr_schedule), default=None, dest="lr_schedule",
+                   metavar="constant|linear|cosine[:FINAL_RATIO]",
+                   help="learning rate after the warm-up: constant, or a linear / cosine decay to FINAL_RATIO * "
+                        "--learning-rate (default 0) at the run's last optimiser step = nb_epoch * iterations per "
+                        "epoch * ppo_epochs (default: constant)")
+    t.add_argument("--warmup-steps", type=int, default=0, dest="warmup_steps", metavar="N",
+                   help="linear warm-up of the learning rate over the first N optimiser steps (default: 0)")
+    t.add_argument("--adam-betas", type=_arg(parse_betas), default=None, dest="adam_betas", metavar="B1,B2",
+                   help="Adam's betas (default: 0.9,0.999)")
+    t.add_argument("--ema", type=_arg(_ema), default=None, dest="ema", metavar="D",
+                   help="keep an exponential moving average of the weights with decay D in (0, 1); every checkpoint "
+                        "epoch also writes models/nn_models_ema_epoch_{e}.pt, loadable by test / infer")
+    t.add_argument("--eval-ema", action="store_true", dest="eval_ema",
+                   help="with --ema: the evaluation after every epoch runs on the averaged weights")
+    t.add_argument("--resume", type=str, default=None, dest="resume", metavar="FILE",
+                   help="continue an interrupted run bit for bit from models/trainer_epoch_{e}.pt (written every "
+                        "checkpoint epoch next to nn_models_epoch_{e}.pt, which is loaded with it): Adam moments, "
+                        "averaged weights, optimiser step, generator position; same flags as the interrupted run")
     e.add_argument("--tta", type=_arg(_tta_arg), default=None, dest="tta", metavar="SPEC",
                    help="test-time augmentation: every batch runs once per flip / rotation the spec allows (hflip, "
                         "vflip, rot90, d4) and the predictions are averaged (default: one run)")
@@ -160,6 +189,26 @@ def _tta_arg(text: str) -> str:
 
 def _label_smoothing(text: str) -> float:
     return check_label_smoothing(float(text))
+
+
+def _weight_decay(text: str) -> float:
+    OptimOptions(weight_decay=float(text))
+    return float(text)
+
+
+def _ema(text: str) -> float:
+    OptimOptions(ema_decay=float(text))
+    return float(text)
+
+
+def _lr_groups(text: str) -> str:
+    OptimOptions(groups=parse_groups(text))
+    return text
+
+
+def _lr_schedule(text: str) -> str:
+    parse_schedule(text)
+    return text
 
 
 def _temperature(text: str) -> float:
@@ -221,6 +270,9 @@ def main(argv=None) -> None:
             temperature=args.temperature, explore_eps=args.explore_eps, augment=args.augment,
             class_weights=args.class_weights, label_smoothing=args.label_smoothing, error_steps=args.error_steps,
             weight_rewards=args.weight_rewards,
+            weight_decay=args.weight_decay, decay_all=args.decay_all, lr_groups=args.lr_groups,
+            lr_schedule=args.lr_schedule, warmup_steps=args.warmup_steps, adam_betas=args.adam_betas, ema=args.ema,
+            eval_ema=args.eval_ema, resume=args.resume,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":

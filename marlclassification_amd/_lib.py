@@ -92,7 +92,9 @@ EXPLORE_ENTRIES = ("marl_policy_explore",)
 AUGMENT_ENTRIES = ("marl_batch_augment", "marl_batch_augment_plan")
 # ... and the options of the vote error and the rewards that include/marl_hip_classloss.h declares (likewise)
 CLASSLOSS_ENTRIES = ("marl_class_loss",)
-_HOOKS = ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES
+# ... and the flat optimiser step that include/marl_hip_optim.h declares (likewise; optim.py holds its structures)
+OPTIM_ENTRIES = ("marl_optim_step",)
+_HOOKS = ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES
 
 
 class CnnBwdPlan(C.Structure):
@@ -214,6 +216,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_comm_range.argtypes = [_i, _i, _i]
     lib.marl_policy_explore.argtypes = [_f, _f, _i]
     lib.marl_class_loss.argtypes = [_vp, _i, _f, _vp, _i, _i]
+    _d = C.c_double
+    lib.marl_optim_step.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp, _i, _d, _d, _d, _vp, _i64, _vp, _d, _vp,
+                                    _vp]
     lib.marl_batch_augment.argtypes = [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
     lib.marl_batch_augment_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
     lib.marl_ln_silu_bwd.argtypes = [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _vp, _sz, _i, _i, _vp]

@@ -123,6 +123,23 @@ class TrainConfig(BaseModel):
     label_smoothing: float = 0.0
     error_steps: Optional[str] = None
     weight_rewards: bool = False
+    # the flat optimiser step (optim.py), run-time choices too: all at their defaults = the plain Adam step.  lr_groups /
+    # lr_schedule in the command-line spelling (optim.parse_groups / parse_schedule); ema = the decay of the averaged
+    # weights; eval_ema: eval_epoch runs on them; resume = a models/trainer_epoch_{e}.pt to continue from
+    weight_decay: float = 0.0
+    decay_all: bool = False
+    lr_groups: Optional[str] = None
+    lr_schedule: Optional[str] = None
+    warmup_steps: int = 0
+    adam_betas: Optional[Tuple[float, float]] = None
+    ema: Optional[float] = None
+    eval_ema: bool = False
+    resume: Optional[str] = None
+
+    def optim_on(self) -> bool:
+        return (self.weight_decay != 0.0 or self.decay_all or self.lr_groups is not None or
+                self.lr_schedule is not None or self.warmup_steps != 0 or self.adam_betas is not None or
+                self.ema is not None)
 
 
 class EvalConfig(BaseModel):

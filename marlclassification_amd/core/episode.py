@@ -152,6 +152,24 @@ class EpisodeSampler:
     def env(self) -> Environment:
         return self.__env
 
+    def rng_state(self) -> dict:
+        """Position of this sampler's generator stream (``device_rng``): the torch seed that keys it and the number
+        of episodes drawn under it - numbers only, so a checkpoint can hold it (``Trainer.state_dict``)."""
+        seed = th.initial_seed()
+        episodes = self.__episodes if seed == self.__rng_seed else 0
+        return {"seed": int(seed), "episodes": int(episodes)}
+
+    def set_rng_state(self, state: dict) -> None:
+        """Continue the stream ``rng_state`` described: the next episode draws what the interrupted run's next one
+        would have drawn.  The stream is keyed by torch's seed, so a process seeded otherwise is re-seeded
+        (``th.manual_seed``) with the stored one."""
+        seed, episodes = int(state["seed"]), int(state["episodes"])
+        if episodes < 0:
+            raise ValueError(f"rng state: episodes must be >= 0, got {episodes}")
+        if th.initial_seed() != seed:
+            th.manual_seed(seed)
+        self.__rng_seed, self.__episodes = seed, episodes
+
     def draw_key(self, seed: int) -> int:
         """Generator key of this sampler's draws: (torch seed, rank, sampler id)."""
         import os

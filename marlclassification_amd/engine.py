@@ -830,6 +830,35 @@ class HipEngine:
             params.numel(), step, lr, betas[0], betas[1], eps, grad_scale, _ptr(counters),
             _stream(self.device)))
 
+    def optim_step(
+        self, params: th.Tensor, grads: th.Tensor, exp_avg: th.Tensor, exp_avg_sq: th.Tensor, table, opts,
+        step: int = 0, ema: Optional[th.Tensor] = None, grad_scale: float = 1.0,
+        counters: Optional[th.Tensor] = None, scalars_out: Optional[th.Tensor] = None,
+    ) -> None:
+        """marl_optim_step: one AdamW step over the flat buffers under ``opts`` (an ``optim.OptimOptions`` whose
+        schedule has its ``base_lr``) and ``table`` (``optim.segments``; or a ready ``optim.Segment`` array with its
+        length: ``(array, n)``).  ``step``: the 1-based step, or ``counters``: the block whose step field the kernel
+        reads.  ``ema``: the averaged weights, updated in the same launch.  ``scalars_out`` (fp32 [4], device):
+        receives {lr_t, 1 - beta1^t, 1 - beta2^t, t}."""
+        from . import optim as _optim
+
+        for t in (params, grads, exp_avg, exp_avg_sq) + (() if ema is None else (ema,)):
+            if not t.is_cuda or t.dtype != th.float32 or not t.is_contiguous() or t.numel() != params.numel():
+                raise RuntimeError("optim_step buffers must be contiguous fp32 GPU tensors of one length")
+        if scalars_out is not None and (not scalars_out.is_cuda or scalars_out.dtype != th.float32 or
+                                        scalars_out.numel() < 4 or not scalars_out.is_contiguous()):
+            raise RuntimeError("optim_step: scalars_out must be a contiguous fp32 GPU tensor of 4 elements")
+        if isinstance(table, tuple) and len(table) == 2 and not isinstance(table[0], tuple):
+            arr, nseg = table
+        else:
+            arr, nseg = _optim.segment_array(table), len(table)
+        desc = opts.schedule.desc()
+        check(self.lib.marl_optim_step(
+            params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), _ptr(ema),
+            params.numel(), grad_scale, C.cast(arr, C.c_void_p), nseg, opts.betas[0], opts.betas[1], opts.eps,
+            C.cast(C.pointer(desc), C.c_void_p), step, _ptr(counters),
+            0.0 if opts.ema_decay is None else opts.ema_decay, _ptr(scalars_out), _stream(self.device)))
+
     def step_forward(
         self, obs: th.Tensor, msg: th.Tensor, norm_pos: th.Tensor, h: th.Tensor, c: th.Tensor,
         hc: th.Tensor, cc: th.Tensor, noise: Optional[th.Tensor] = None,

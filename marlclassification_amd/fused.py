@@ -78,7 +78,17 @@ class FlatParams:
         self.grads = th.zeros(off, device=device)
         self.exp_avg = th.zeros(off, device=device)
         self.exp_avg_sq = th.zeros(off, device=device)
+        self.ema: Optional[th.Tensor] = None  # averaged weights (optim.OptimOptions.ema_decay): see ema_buffer()
         self.step = 0
+
+    def ema_buffer(self) -> th.Tensor:
+        """The averaged copy of the weights; allocated when first asked for, as a copy of ``params``."""
+        if self.ema is None:
+            self.ema = self.params.clone()
+        return self.ema
+
+    def ema_views(self) -> Dict[str, th.Tensor]:
+        return self._views(self.ema_buffer())
 
     def _views(self, flat: th.Tensor) -> Dict[str, th.Tensor]:
         out = {}
@@ -209,6 +219,43 @@ class ClassLossOptions:
             eng.class_loss = before
 
 
+class OptimRun:
+    """The optimiser options (``optim.OptimOptions``) as ``Trainer`` and ``FusedA2C`` hold them: the schedule's base
+    rate filled in from the learning rate, the merged segment table of each flat buffer it met (host arrays, built
+    once), and the device block {lr_t, 1 - beta1^t, 1 - beta2^t, t} the kernel writes for the meters."""
+
+    def __init__(self, opts, lr: float) -> None:
+        from . import optim as _optim
+
+        if not isinstance(opts, _optim.OptimOptions):
+            raise ValueError(f"optim must be an optim.OptimOptions or None, got {opts!r}")
+        self.opts = opts.with_lr(lr)
+        self._tables: Dict[int, tuple] = {}
+        self.scalars: Optional[th.Tensor] = None
+
+    def table(self, flat: "FlatParams"):
+        """(segment table, its ctypes array, the frozen element ranges) of ``flat``."""
+        from . import optim as _optim
+
+        hit = self._tables.get(id(flat))
+        if hit is None or hit[0] is not flat:
+            tab = _optim.segments(flat, self.opts)
+            hit = self._tables[id(flat)] = (flat, tab, _optim.segment_array(tab), _optim.frozen_ranges(tab))
+        return hit[1:]
+
+    def scalars_for(self, eng: HipEngine) -> th.Tensor:
+        if self.scalars is None or self.scalars.device != eng.device:
+            self.scalars = th.zeros(4, device=eng.device)
+        return self.scalars
+
+    def step(self, eng: HipEngine, flat: "FlatParams", step: int, grad_scale: float = 1.0,
+             counters: Optional[th.Tensor] = None) -> None:
+        tab, arr, _ = self.table(flat)
+        eng.optim_step(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, (arr, len(tab)), self.opts, step=step,
+                       ema=flat.ema_buffer() if self.opts.ema_decay is not None else None, grad_scale=grad_scale,
+                       counters=counters, scalars_out=self.scalars_for(eng))
+
+
 def ppo_bufs_fit(bufs, out: EpisodeTensors, entropy: bool) -> bool:
     """Do the persistent ``HipEngine.new_ppo_bufs`` tensors match this episode?"""
     return (bufs is not None and len(bufs) == (8 if entropy else 7) and bufs[0].shape == out.step_preds.shape and
@@ -217,14 +264,16 @@ def ppo_bufs_fit(bufs, out: EpisodeTensors, entropy: bool) -> bool:
 
 def apply_update(eng: HipEngine, flat: "FlatParams", gp, gl, gv, g_probs, gviews, lr: float, allreduce,
                  max_grad_norm: Optional[float], repack: Callable[[], None],
-                 comm: Optional[CommUpdate] = None) -> Optional[th.Tensor]:
+                 comm: Optional[CommUpdate] = None, optim: Optional[OptimRun] = None) -> Optional[th.Tensor]:
     """One update from the output gradients a loss entry wrote - the A2C, entropy and PPO steps of ``Trainer`` and
     ``FusedA2C`` all end here: backward (bucketed hooks around it: two buckets, the heads' slice leaves while the
     reverse loop still runs) -> all-reduce -> [grad_clip, after the all-reduce and its scale: every rank clips the
     same averaged gradient] -> Adam (``flat.step`` += 1) -> ``repack()``.  ``comm`` (a live communication source
     under a ``comm_lr``): the backward also writes d_comm and the source's leaves take their Adam step after the flat
     one; None: ``episode_backward`` is called without ``d_comm``.  Returns the device scalar with the gradient norm
-    (None without ``max_grad_norm``)."""
+    (None without ``max_grad_norm``).  ``optim`` (an ``OptimRun``): ``marl_optim_step`` under its options takes the
+    place of Adam, and with ``max_grad_norm`` the gradient slices of frozen groups are zeroed before the clip, so the
+    clipped norm is that of the trainable parameters; None: today's sequence of calls, verbatim."""
     bucketed = hasattr(allreduce, "before_backward")  # parallel.BucketedGradAllReduce
     if bucketed:
         allreduce.before_backward(eng)
@@ -237,10 +286,16 @@ def apply_update(eng: HipEngine, flat: "FlatParams", gp, gl, gv, g_probs, gviews
     scale = rank_scale = 1.0 if allreduce is None else allreduce(flat.grads)
     norm = None
     if max_grad_norm is not None:
+        if optim is not None:
+            for begin, end in optim.table(flat)[2]:
+                flat.grads[begin:end].zero_()
         norm = eng.grad_clip(flat.grads, max_grad_norm, grad_scale=scale)
         scale = 1.0
     flat.step += 1
-    eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, lr, grad_scale=scale)
+    if optim is None:
+        eng.adam(flat.params, flat.grads, flat.exp_avg, flat.exp_avg_sq, flat.step, lr, grad_scale=scale)
+    else:
+        optim.step(eng, flat, flat.step, grad_scale=scale)
     if comm is not None:
         comm.step(eng.comm_live, allreduce, rank_scale)
     repack()
@@ -250,7 +305,7 @@ def apply_update(eng: HipEngine, flat: "FlatParams", gp, gl, gv, g_probs, gviews
 def ppo_epochs_loop(eng: HipEngine, flat: "FlatParams", out: EpisodeTensors, y: th.Tensor, bufs, epochs: int,
                     clip: float, beta: float, lr: float, allreduce, max_grad_norm: Optional[float], gviews,
                     replay: Callable[[], EpisodeTensors], repack: Callable[[], None],
-                    comm: Optional[CommUpdate] = None) -> Optional[th.Tensor]:
+                    comm: Optional[CommUpdate] = None, optim: Optional[OptimRun] = None) -> Optional[th.Tensor]:
     """The K update epochs of one rollout ``out`` whose advantages already sit in ``bufs`` (``HipEngine.advantages``);
     ``Trainer`` and ``FusedA2C`` both run this.  Epoch k > 0 starts with ``replay()``: the stored trajectory (same
     draws, the rollout's actions forced) under the weights the last epoch packed.  Then ppo_loss -> ``apply_update``.
@@ -270,7 +325,7 @@ def ppo_epochs_loop(eng: HipEngine, flat: "FlatParams", out: EpisodeTensors, y: 
                 raise RuntimeError("PPO replay wrote over the rollout's log-probabilities (persistent output "
                                    "tensors?): the ratios would all be 1")
         eng.ppo_loss(cur, y, old_logp, advn, ret, clip, bufs, entropy_coef=beta)
-        norm = apply_update(eng, flat, gp, gl, gv, gpr, gviews, lr, allreduce, max_grad_norm, repack, comm)
+        norm = apply_update(eng, flat, gp, gl, gv, gpr, gviews, lr, allreduce, max_grad_norm, repack, comm, optim)
     return norm
 
 
@@ -284,8 +339,13 @@ class FusedA2C:
                  max_grad_norm: Optional[float] = None, comm_lr: Optional[float] = None,
                  temperature: Optional[float] = None, explore_eps: Optional[float] = None,
                  class_weights=None, label_smoothing: float = 0.0, error_step_weights=None,
-                 weight_rewards: bool = False) -> None:
-        """``class_weights`` / ``label_smoothing`` / ``error_step_weights`` / ``weight_rewards``: the options of the
+                 weight_rewards: bool = False, optim=None) -> None:
+        """``optim`` (an ``optim.OptimOptions``): every update is one ``marl_optim_step`` under these options - AdamW
+        with parameter groups, a schedule whose base rate is ``lr`` (unless it names its own) and, with ``ema_decay``,
+        the averaged weights in ``flat.ema``; ``iteration_graph`` captures it reading the counter block's step, so a
+        schedule costs no ``counters_set`` between replays.  None: ``marl_adam_step`` exactly as before.
+
+        ``class_weights`` / ``label_smoothing`` / ``error_step_weights`` / ``weight_rewards``: the options of the
         vote error and the rewards (``class_loss.py``) of every loss call of this object - installed on the engine
         around them and taken off behind them; all four at their defaults: the engine's own ``set_class_loss`` setting
         (none: today's sequence of calls, verbatim) applies.
@@ -310,6 +370,7 @@ class FusedA2C:
         _explore.check(1.0 if temperature is None else temperature, 0.0 if explore_eps is None else explore_eps)
         self.temperature, self.explore_eps = temperature, explore_eps
         self._class_loss = ClassLossOptions(class_weights, label_smoothing, error_step_weights, weight_rewards)
+        self._optim: Optional[OptimRun] = None if optim is None else OptimRun(optim, lr)
         self.comm_lr = None if comm_lr is None else float(comm_lr)
         self._comm_update: Optional[CommUpdate] = None
         if not entropy_coef >= 0.0:
@@ -391,7 +452,8 @@ class FusedA2C:
                eng.comm_range,                                     # and the range's radius / metric / normalize
                eng.exploration,                                    # and the exploration constants in their arguments)
                # (and the loss options, this object's or else the engine's own: their constants and the engine's device
-               closs if closs is not None else eng.class_loss)  # copies of the weights, one pair per value)
+               closs if closs is not None else eng.class_loss,  # copies of the weights, one pair per value)
+               None if self._optim is None else self._optim.opts)  # (and the optimiser's constants and segment table)
         if self._graph is None or self._graph[0] != key:
             if self._graph is not None:
                 eng.lib.marl_graph_destroy(self._graph[1])
@@ -417,8 +479,11 @@ class FusedA2C:
                         bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
                     gp, gl, gv, scalars = bufs[:4]
                     eng.episode_backward(gp, gl, gv, gviews, g_probs=bufs[5] if beta > 0 else None)
-                    eng.adam(self.flat.params, self.flat.grads, self.flat.exp_avg,
-                             self.flat.exp_avg_sq, 1, self.lr, counters=cnt)
+                    if self._optim is None:
+                        eng.adam(self.flat.params, self.flat.grads, self.flat.exp_avg,
+                                 self.flat.exp_avg_sq, 1, self.lr, counters=cnt)
+                    else:  # (lr_t and the bias corrections come from cnt's step inside the kernel)
+                        self._optim.step(eng, self.flat, 0, counters=cnt)
                     eng.pack(self._pviews)
                     eng.counters_tick(cnt, self.lr)
                 except BaseException:
@@ -467,7 +532,7 @@ class FusedA2C:
             bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
         gp, gl, gv, scalars = bufs[:4]
         apply_update(eng, self.flat, gp, gl, gv, bufs[5] if beta > 0 else None, self._gviews, self.lr,
-                     self.allreduce, None, self.pack, self._comm())
+                     self.allreduce, None, self.pack, self._comm(), self._optim)
         return out, scalars
 
     def _comm(self) -> Optional[CommUpdate]:
@@ -492,7 +557,7 @@ class FusedA2C:
                 eng, self.flat, out, y, bufs, self.ppo_epochs, self.ppo_clip, beta, self.lr, self.allreduce,
                 self.max_grad_norm, self._gviews,
                 replay=lambda: self.rollout(img, draws, True, forced_actions=out.step_actions, probs=ent),
-                repack=self.pack, comm=self._comm())
+                repack=self.pack, comm=self._comm(), optim=self._optim)
         if norm is not None:
             self.last_grad_norm = norm
         return out, bufs[3]

@@ -419,6 +419,8 @@ class ModelsWrapper(nn.Module):
             if flat is not None and flat.params.device == dev and flat.numel == fresh.numel:
                 fresh.exp_avg.copy_(flat.exp_avg)
                 fresh.exp_avg_sq.copy_(flat.exp_avg_sq)
+                if flat.ema is not None:  # (the averaged weights of optim.OptimOptions.ema_decay)
+                    fresh.ema = flat.ema.clone()
                 fresh.step = flat.step
             self.__flat = fresh
             self.__packed_token = {}

@@ -156,7 +156,16 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
     # mix the rank in (core/episode.py), so shards draw differently.  MARL_SEED unset: a fresh seed per run
     # like the reference (train.py never seeds), agreed on by all ranks; it is printed, so a run can be
     # repeated with MARL_SEED=<that value>.
-    if "MARL_SEED" in os.environ:
+    # --resume: the trainer state of a checkpoint epoch; it names the run's seed (data order, generator streams)
+    resumed = None
+    if train_config.resume is not None:
+        resumed = th.load(train_config.resume, map_location="cpu", weights_only=True)
+        for k in ("epoch", "base_seed"):
+            if k not in resumed:
+                raise ValueError(f'"{train_config.resume}" is no trainer checkpoint of this program (no {k})')
+    if resumed is not None:
+        base_seed = int(resumed["base_seed"])
+    elif "MARL_SEED" in os.environ:
         base_seed = int(os.environ["MARL_SEED"])
     else:
         t = th.tensor([int.from_bytes(os.urandom(4), "little")], dtype=th.int64, device=device)
@@ -229,6 +238,22 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         loaders.append(DevicePrefetcher(dl, device, **aug))  # upload of batch i+1 overlaps step i
 
     sampler = EpisodeSampler(marl_m, env, main_config.step)
+    # the flat optimiser step (optim.py): any of its flags makes every update a marl_optim_step; none: plain Adam
+    optim_opts = None
+    if train_config.optim_on():
+        from . import optim as _optim
+
+        total_steps = train_config.nb_epoch * len(samplers[0]) * train_config.ppo_epochs
+        optim_opts = _optim.OptimOptions(
+            weight_decay=train_config.weight_decay, decay="all" if train_config.decay_all else "matrices",
+            groups=_optim.parse_groups(train_config.lr_groups or ""),
+            betas=train_config.adam_betas or (0.9, 0.999),
+            schedule=_optim.parse_schedule(train_config.lr_schedule or "constant", train_config.warmup_steps,
+                                           max(total_steps, train_config.warmup_steps),
+                                           train_config.learning_rate),
+            ema_decay=train_config.ema)
+    if train_config.eval_ema and train_config.ema is None:
+        raise ValueError("--eval-ema needs --ema")
     trainer = Trainer(nn_models, marl_m.nb_class, train_config.learning_rate, train_config.gamma,
                       metric_logger=metric_logger if rank == 0 else None,
                       allreduce=(BucketedGradAllReduce(world, None, nn_models.flat_state().offsets, nn_models.flat_state().numel,
@@ -241,7 +266,17 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
                       comm_lr=((train_config.comm_lr if train_config.comm_lr is not None else
                                 train_config.learning_rate) if learned is not None else None),
                       class_weights=class_weights, label_smoothing=train_config.label_smoothing,
-                      error_step_weights=train_config.error_steps, weight_rewards=train_config.weight_rewards)
+                      error_step_weights=train_config.error_steps, weight_rewards=train_config.weight_rewards,
+                      optim=optim_opts)
+    first_epoch = 0
+    if resumed is not None:
+        first_epoch = int(resumed["epoch"]) + 1
+        weights = join(os.path.dirname(os.path.abspath(train_config.resume)),
+                       f"nn_models_epoch_{first_epoch - 1}.pt")
+        nn_models.load_state_dict(th.load(weights, map_location=device, weights_only=True))
+        trainer.load_state_dict(resumed, sampler)
+        if rank == 0:
+            print(f"resumed from epoch {first_epoch - 1}: optimiser step {nn_models.flat_state().step}", flush=True)
     from . import explore as _explore
 
     t_ends, e_ends, cw_spec = train_config.temperature, train_config.explore_eps, train_config.class_weights
@@ -254,8 +289,9 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
               (f", class weights {cw_spec if isinstance(cw_spec, str) else 'given'}" if cw_spec is not None else "") +
               (f", label_smoothing {train_config.label_smoothing}" if train_config.label_smoothing else "") +
               (f", error steps {train_config.error_steps}" if train_config.error_steps else "") +
-              (", weighted rewards" if train_config.weight_rewards else ""), flush=True)
-    for e in range(train_config.nb_epoch):
+              (", weighted rewards" if train_config.weight_rewards else "") +
+              (f", optim {trainer.optim_options.fingerprint()}" if optim_opts is not None else ""), flush=True)
+    for e in range(first_epoch, train_config.nb_epoch):
         for bs in samplers:
             bs.set_epoch(e)
         if t_ends is not None:  # (the exploration schedules: linear over the epochs, applied at each epoch's start)
@@ -263,16 +299,28 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         if e_ends is not None:
             trainer.explore_eps = _explore.schedule_value(e_ends, e, train_config.nb_epoch)
         trainer.train_epoch(loaders[0], e, sampler)
-        conf = trainer.eval_epoch(loaders[1], e, sampler)
+        if train_config.eval_ema:
+            with trainer.ema_weights():
+                conf = trainer.eval_epoch(loaders[1], e, sampler)
+        else:
+            conf = trainer.eval_epoch(loaders[1], e, sampler)
         if distributed:
             conf.all_reduce()  # every rank evaluated its shard only
         if rank == 0:
             m: Dict[str, float] = trainer.metrics()
             m["eval_prec"] = conf.precision().mean().item()
             m["eval_recs"] = conf.recall().mean().item()
-            print(f"epoch {e}: " + ", ".join(f"{k}={v:.4f}" for k, v in m.items()), flush=True)
+            print(f"epoch {e}: " + ", ".join(f"{k}={v:.8e}" if k == "lr" else f"{k}={v:.4f}" for k, v in m.items()),
+                  flush=True)
             conf.save_conf_matrix(e, output_dir, "eval")  # reference train.py:134
             th.save(nn_models.state_dict(), join(model_dir, f"nn_models_epoch_{e}.pt"))
+            # what --resume continues from (rank 0's generator position: a multi-GPU run resumes its ranks from it)
+            state = trainer.state_dict(sampler)
+            state["epoch"], state["base_seed"] = e, base_seed
+            th.save(state, join(model_dir, f"trainer_epoch_{e}.pt"))
+            if train_config.ema is not None:  # (reference state-dict keys: test / infer load it as it is)
+                with trainer.ema_weights():
+                    th.save(nn_models.state_dict(), join(model_dir, f"nn_models_ema_epoch_{e}.pt"))
             if learned is not None:  # the learned matrix: `test` / `infer` load it with --comm FILE.npy
                 import numpy as np
 

@@ -10,13 +10,14 @@ feeds K updates: ``marl_advantages`` once, then per epoch [replay forward] -> ``
 Same constructor and ``train_epoch`` / ``eval_epoch`` signatures as the reference.
 """
 
+from contextlib import contextmanager
 from typing import Callable, Dict, Iterable, Optional, Tuple
 
 import torch as th
 
 from ..core import EpisodeSampler
 from ..engine import EpisodeTensors
-from ..fused import (ClassLossOptions, CommUpdate, apply_update, check_ppo_options, comm_update_for, ppo_bufs_fit,
+from ..fused import (ClassLossOptions, CommUpdate, OptimRun, apply_update, check_ppo_options, comm_update_for, ppo_bufs_fit,
                      ppo_epochs_loop, ppo_options_on)
 from ..metrics import ConfusionMeter, LossMeter
 from ..networks import ModelsWrapper
@@ -48,8 +49,16 @@ class Trainer:
         label_smoothing: float = 0.0,
         error_step_weights=None,
         weight_rewards: bool = False,
+        optim=None,
     ) -> None:
-        """``class_weights`` ([nb_class], >= 0) / ``label_smoothing`` (in [0, 1)) / ``error_step_weights`` (``all``,
+        """``optim`` (an ``optim.OptimOptions``): every update - ``train_step`` with or without the entropy bonus, every
+        PPO epoch, on every rank - is one ``marl_optim_step`` under these options: AdamW with decoupled weight decay,
+        per-module learning-rate multipliers (0 freezes a module; with ``max_grad_norm`` its gradient leaves the
+        clipped norm), a schedule whose base rate is ``learning_rate`` (unless it names its own) and, with
+        ``ema_decay``, an averaged copy of the weights (``ema_weights()``).  ``metrics()["lr"]`` is the rate the last
+        step applied, as the kernel wrote it.  None: ``marl_adam_step`` exactly as before.
+
+        ``class_weights`` ([nb_class], >= 0) / ``label_smoothing`` (in [0, 1)) / ``error_step_weights`` (``all``,
         ``last``, ``last:K``, ``linear`` or one weight per step) / ``weight_rewards``: the options of the vote error and
         the rewards (``class_loss.py``: err[t,b] = s_t * weighted, smoothed cross-entropy of the vote; rewards times
         w_y) in ``train_step`` and in every PPO epoch: each step installs them on the model's engine
@@ -83,6 +92,8 @@ class Trainer:
         if class_weights is not None and len(class_weights) != nb_class:
             raise ValueError(f"class_weights must have nb_class = {nb_class} entries, got {len(class_weights)}")
         self.__class_loss = ClassLossOptions(class_weights, label_smoothing, error_step_weights, weight_rewards)
+        self.__optim: Optional[OptimRun] = None if optim is None else OptimRun(optim, learning_rate)
+        self.__comm_pending: Optional[dict] = None  # (a loaded state of the communication source's Adam)
         self.__comm_lr = None if comm_lr is None else float(comm_lr)
         self.__comm_update: Optional[CommUpdate] = None
         self.__model = model
@@ -126,6 +137,9 @@ class Trainer:
         model = self.__model
         self.__comm_update = comm_update_for(self.__comm_update, model.comm_source, model.comm_parameters,
                                              self.__comm_lr)
+        if self.__comm_update is not None and self.__comm_pending is not None:
+            self.__comm_update.opt.load_state_dict(self.__comm_pending)
+            self.__comm_pending = None
         return self.__comm_update
 
     def __exact_phases(self, call: Callable[[int], Tuple[th.Tensor, ...]]) -> None:
@@ -163,7 +177,7 @@ class Trainer:
             self.__exact_phases(lambda phase: eng.a2c_loss(out, y, self.__gamma, phase, bufs, entropy_coef=beta))
         flat = model.flat_state()
         apply_update(eng, flat, bufs[0], bufs[1], bufs[2], bufs[5] if ent else None, flat.grad_views(), self.__lr,
-                     self.__allreduce, None, lambda: model.mark_updated(eng), self.__comm())
+                     self.__allreduce, None, lambda: model.mark_updated(eng), self.__comm(), self.__optim)
         return out, bufs[3]
 
     def __train_step_ppo(self, x: th.Tensor, y: th.Tensor,
@@ -187,7 +201,7 @@ class Trainer:
                 self.__max_grad_norm, flat.grad_views(),
                 replay=lambda: sampler.run_episode_raw(img, train=True, draws=draws, probs=ent,
                                                        forced=out.step_actions)[1],
-                repack=lambda: model.mark_updated(eng), comm=self.__comm())
+                repack=lambda: model.mark_updated(eng), comm=self.__comm(), optim=self.__optim)
         if norm is not None:
             self.__grad_norm = norm
         return out, bufs[3]
@@ -221,7 +235,94 @@ class Trainer:
         for k in ("approx_kl", "clip_frac", "grad_norm"):  # (only with the matching PPO option on)
             if k in self.__meters:
                 m[k] = self.__meters[k].loss()
+        if self.__optim is not None and self.__optim.scalars is not None:  # (the rate of the last step, from the kernel)
+            m["lr"] = self.__optim.scalars[0].item()
         return m
+
+    @property
+    def optim_options(self):
+        """The ``optim.OptimOptions`` in force (the schedule's base rate filled in), or None."""
+        return None if self.__optim is None else self.__optim.opts
+
+    @contextmanager
+    def ema_weights(self):
+        """Inside the context the model holds the AVERAGED weights (``optim.OptimOptions.ema_decay``): episodes,
+        ``eval_epoch`` and ``model.state_dict()`` see them; on exit the trained weights are back, bit for bit.  No
+        ``train_step`` may run inside."""
+        if self.__optim is None or self.__optim.opts.ema_decay is None:
+            raise ValueError("ema_weights(): the trainer keeps no averaged weights (OptimOptions.ema_decay)")
+        model = self.__model
+        flat = model.flat_state()
+        ema = flat.ema_views()
+        named = list(model.named_parameters())
+        saved = {k: p.detach().clone() for k, p in named}
+        with th.no_grad():
+            for k, p in named:  # (through the parameters: their version counters tell ensure_packed to re-pack)
+                p.copy_(ema[k])
+        try:
+            yield model
+        finally:
+            with th.no_grad():
+                for k, p in named:
+                    p.copy_(saved[k])
+
+    # ---- resume ---------------------------------------------------------------------------------------------------
+    def __fingerprint(self) -> str:
+        return f"adam;lr={self.__lr!r}" if self.__optim is None else self.__optim.opts.fingerprint()
+
+    def state_dict(self, sampler: Optional[EpisodeSampler] = None) -> Dict[str, object]:
+        """Everything beside the model's weights that an interrupted run needs to continue bit for bit: the Adam
+        moments per parameter (``exp_avg.<key>``, ``exp_avg_sq.<key>``), the averaged weights when there are any
+        (``ema.<key>``), the optimiser step, ``curr_step``, the fingerprint of the update rule, the state of the
+        communication source's Adam, and ``sampler``'s generator position.  Tensors, numbers and strings only:
+        ``th.load(weights_only=True)`` reads it."""
+        flat = self.__model.flat_state()
+        out: Dict[str, object] = {"format": 1, "optim_step": int(flat.step), "curr_step": int(self.__curr_step),
+                                  "fingerprint": self.__fingerprint()}
+        for tag, buf in (("exp_avg", flat.exp_avg), ("exp_avg_sq", flat.exp_avg_sq), ("ema", flat.ema)):
+            if buf is None:
+                continue
+            for k, v in flat._views(buf).items():
+                out[f"{tag}.{k}"] = v.detach().cpu().clone()
+        if self.__comm_update is not None:
+            out["comm_adam"] = self.__comm_update.opt.state_dict()
+        if sampler is not None:
+            rng = sampler.rng_state()
+            out["rng_seed"], out["rng_episodes"] = rng["seed"], rng["episodes"]
+        return out
+
+    def load_state_dict(self, state: Dict[str, object], sampler: Optional[EpisodeSampler] = None) -> None:
+        """Continue from ``state_dict()``'s dictionary (the model's weights are loaded separately, before this).
+        ValueError: another update rule (fingerprint), a missing entry or another shape."""
+        if state.get("format") != 1:
+            raise ValueError(f"trainer state: unknown format {state.get('format')!r}")
+        if state.get("fingerprint") != self.__fingerprint():
+            raise ValueError("trainer state: it was written under another update rule\n"
+                             f"  file:    {state.get('fingerprint')}\n  trainer: {self.__fingerprint()}")
+        flat = self.__model.flat_state()
+        want_ema = self.__optim is not None and self.__optim.opts.ema_decay is not None
+        loads = []
+        for tag in ("exp_avg", "exp_avg_sq") + (("ema",) if want_ema else ()):
+            for k, shape in flat.shapes.items():
+                t = state.get(f"{tag}.{k}")
+                if not isinstance(t, th.Tensor) or tuple(t.shape) != tuple(shape):
+                    raise ValueError(f"trainer state: {tag}.{k} is "
+                                     f"{'missing' if t is None else tuple(getattr(t, 'shape', ()))}, "
+                                     f"the model needs {tuple(shape)}")
+                loads.append((tag, k, t))
+        bufs = {"exp_avg": flat.exp_avg, "exp_avg_sq": flat.exp_avg_sq}
+        if want_ema:
+            bufs["ema"] = flat.ema_buffer()
+        views = {tag: flat._views(b) for tag, b in bufs.items()}
+        with th.no_grad():
+            for tag, k, t in loads:  # (nothing is written before everything is checked)
+                views[tag][k].copy_(t)
+        flat.step = int(state["optim_step"])
+        self.__curr_step = int(state["curr_step"])
+        if "comm_adam" in state:
+            self.__comm_pending, self.__comm_update = state["comm_adam"], None
+        if sampler is not None and "rng_seed" in state:
+            sampler.set_rng_state({"seed": state["rng_seed"], "episodes": state["rng_episodes"]})
 
     def eval_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler) -> ConfusionMeter:
         self.__model.eval()
