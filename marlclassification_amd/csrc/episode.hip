@@ -227,17 +227,6 @@ static bool g3_model_ok(const Dims& d) {
 static bool g3_enabled(const Dims& d) {
     return g3_model_ok(d) && d.R % 32 == 0 && d.R >= 32;
 }
-// the four large weight gradients on images (gemm_tn3_kernel: 256-column tiles of A, whole 256 x 256 tiles
-// or column passes, g3_tn_plan): only where that form wins - >= 32768 contraction rows (at C4's 8192 rows the
-// fp32-operand kernel is 25 % faster) and at most three column passes on the B side
-static bool g3_tn_enabled(const Dims& d) {
-    if (tune_get("g3_lstm", 1) == 0 || tune_get("g3_tn", 1) == 0) return false;
-    if (tune_get("g3_tn", 1) == 2) return true;
-    if (d.nin > 640 || d.n_b > 512 || d.n_a > 512) return false;
-    // (round 5: the one-launch-per-cell form wins from 8 192 rows on - C4 at 32 images per GPU: 3.62 vs 3.69 ms)
-    return d.NR >= 32768 || (g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) && g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR));
-}
-
 // conv weights whose tiles are whole (16 output channels x 16-deep K steps) get a fragment-order copy
 static bool conv_frag_ok(const ParamMeta& m) { return m.kind == PK_CONV && m.n % 16 == 0 && m.k % 16 == 0; }
 
@@ -618,6 +607,72 @@ static void make_elayout(const Dims& d, int train, ELayout& e) {
 }
 
 // ---------------------------------------------------------------------------
+// what the setters installed, and the plan of one call
+// ---------------------------------------------------------------------------
+// marl_policy_explore (marl_hip_explore.h): exploration controls of every sampling site and of the policy head's
+// backward.  on = anything but (tau 1, eps 0, sampled): only then does a call take the EXPLORE kernels - with it off
+// every entry launches what it always launched.
+struct Explore {
+    bool on;
+    float inv_tau, keep, eps;  // 1 / tau, 1 - eps, eps (the floor eps / nA is formed where nA is known)
+    int greedy;
+};
+// marl_class_loss (marl_hip_classloss.h): options of the vote error and the rewards of every loss entry.  on = anything
+// was installed (neutral values too): only then does a loss entry take the option instances of the two kernels - with
+// it off every entry launches what it always launched.
+struct ClassLoss {
+    bool on;
+    const float* w;   // [nc] device, nullptr = all ones
+    int nc;
+    float eps;
+    const float* sw;  // [ns] device, nullptr = all ones
+    int ns;
+    bool wrew;
+};
+// The process-global settings.  The five setters are the only writers of g_installed; an entry point copies it once
+// (make_ctx into Ctx::opt, the entries without a context at their top) and everything below reads that copy.
+struct Installed {
+    // marl_comm_matrix: the caller-owned [na, na] mixing matrix of the message exchange (row = receiver), or null =
+    // the mean over the other agents (which launch applies it: Plan::comm_form)
+    const float* comm = nullptr;
+    int comm_na = 0;
+    // marl_comm_range: radius >= 0 = the matrix above is the BASE of a range-limited exchange - per image and step it
+    // is gated by the agents' positions (CommGate, common.h).  The message emitted in step t (MSG[t + 1]) is aggregated
+    // under the positions of its emission, POS[t]; the zero message of step 0 under POS[0].
+    CommGate range = {nullptr, -1, 0, 1};
+    Explore explore = {false, 1.f, 1.f, 0.f, 0};
+    ClassLoss class_loss = {false, nullptr, 0, 0.f, nullptr, 0, false};
+    hipEvent_t heads_event = nullptr;  // marl_backward_heads_event: recorded once the heads' gradients are final
+};
+static Installed g_installed;
+
+// where sample(t) of the forward loop runs: a sample_kernel launch of its own behind the step's other launches, the
+// epilogue of the chain launch's policy workgroups, or extra workgroups of the unchained decoder(t+1) launch
+enum SampleSite { SAMPLE_OWN = 0, SAMPLE_EPILOGUE, SAMPLE_RIDE };
+// Which kernel family every launch site of a call takes.  make_plan is the only place that decides it: the forward
+// and backward drivers branch on Ctx::plan, marl_plan_query reports the same object.
+struct Plan {
+    bool panels;        // forward: the MLPs run as panel launches (else GEMM + LayerNorm rows)
+    bool panels_bwd;    // backward loop: the same, for the narrower range of its kernels (every message width <= 384)
+    bool chain;         // the chained panel launches, forward and backward (all agents of an image in one workgroup)
+    bool panel_sample;  // ... whose policy workgroups sample as their epilogue
+    bool g3_lstm;       // both cells and the heads' first layers from k16 images (gemm3.hip)
+    bool g3_tn, g3_tn_pipe;  // the four large weight gradients from images; ... phase-pipelined
+    bool u3_by_producers;    // the kernels that write U also write its image (no separate pass)
+    int skip_f32;       // every consumer of the gate gradients reads their images: no fp32 copy at all
+    int lstm_plan;      // tile plan of the two-cell LSTM launch (gemm3.hip: 2 = 128-row tiles, 3 / 4 = the 32- / 64-row
+                        // gate-split plans, 1 / 5 / 6 by knob; 0 = not on images)
+    SampleSite sample;  // (SAMPLE_RIDE: but for the last step, which has no decoder(t+1) launch)
+    // The aggregation of the messages: 0 = mean inside the chained panel launch, 1 = mean while a panel stages, 2 =
+    // agg_msg_kernel; under a matrix 5 = mixed inside the chained launch (the MIX / GATE instantiations of
+    // panel_fwd_kernel / panel_bwd_kernel; the decoder of step 0 and the step API then take form 3), 3 / 4 =
+    // mix_msg[_gated]_kernel (rowops.hip) in a launch of its own ahead of a plain panel launch / the GEMM path
+    int comm_form;
+    int explore_form;   // sampling under the controls: 0 = off, 1 = the chain launch's EXPLORE epilogue, 2 = sample_kernel's
+    int comm, comm_range, explore, class_loss;  // what is installed: matrix set, its radius or -1, controls / options on
+};
+
+// ---------------------------------------------------------------------------
 // context shared by the forward / backward drivers
 // ---------------------------------------------------------------------------
 struct Ctx {
@@ -633,7 +688,8 @@ struct Ctx {
     bool defer_slabs = false;  // also the split-K / conv weight-gradient slabs (tens of MB each)
     size_t defer_small = 0;    // ... or only those of at most this many bytes (they stay in the L2)
     bool defer_this(size_t slab_bytes) const { return defer_slabs || (defer_small && slab_bytes <= defer_small); }
-    bool u3_by_producers = false;  // the kernels that write U also write its image (no separate pass)
+    Installed opt;  // the settings of this call: g_installed as make_ctx found it
+    Plan plan;      // make_plan(d, w, e, opt)
     int u3_row(int t) const { return (int)(e.u3_stride_rows * (size_t)t); }
 
     const char* wp3k(int i) const { return reinterpret_cast<const char*>(W + w.wp3k[i]); }
@@ -670,64 +726,77 @@ struct Ctx {
     float* DHCs(int t) const { return E + e.DHC + (size_t)t * d.R * d.ld_na; }
 };
 
-static bool use_panels(const Dims& d);
+static Plan make_plan(const Dims& d, const WLayout& w, const ELayout& e, const Installed& opt) {
+    auto env_on = [](const char* v) { return !(v && v[0] == '0'); };
+    // MARL_PANEL_SAMPLE=0: chain launch, then sample_kernel - the earlier form, kept for comparison in one binary
+    static const bool env_panels = env_on(getenv("MARL_PANELS")), env_sample = env_on(getenv("MARL_PANEL_SAMPLE"));
+    Plan p{};
+    p.panels = env_panels && panel_model_ok(d);
+    p.panels_bwd = p.panels && d.n_mo <= 384 && d.nm2 <= 384 && d.n_m <= 384;
+    // chain: all agents of a batch element in one workgroup (rows a * nb + b for every a), so that the message mean
+    // over the other agents needs no second launch (fwd_step_chain, bwd_step_chain).  Under a matrix the chained
+    // kernels also keep it in LDS (16 x 16 floats): with the input width bounded like the others every admitted plan
+    // has room for it; wider models take mix_msg_kernel.
+    p.chain = p.panels_bwd && panel_chain_supported(d.na, d.n_m, 256) && tune_get("panel_chain", 1) != 0 &&
+              (!opt.comm || d.n_b <= 384);
+    p.panel_sample = p.chain && env_sample && panel_sample_supported(d.nA);
+    // sample(t) and decoder(t+1) are independent: without the chain one launch runs both - but not under exploration
+    // controls (the ride-along workgroups of the plain decoder launch have no EXPLORE form)
+    p.sample = p.chain ? (p.panel_sample ? SAMPLE_EPILOGUE : SAMPLE_OWN)
+                       : (p.panels && !opt.explore.on ? SAMPLE_RIDE : SAMPLE_OWN);
+    p.comm_form = opt.comm ? (p.chain ? 5 : p.panels ? 3 : 4) : p.chain ? 0 : p.panels ? 1 : 2;
+    p.explore_form = !opt.explore.on ? 0 : p.panel_sample ? 1 : 2;
+    p.comm = opt.comm != nullptr;
+    p.comm_range = opt.range.radius >= 0 ? opt.range.radius : -1;
+    p.explore = opt.explore.on;
+    p.class_loss = opt.class_loss.on;
 
-// marl_comm_matrix: the caller-owned [na, na] mixing matrix of the message exchange (row = receiver), or null =
-// the mean over the other agents.  Under a matrix the chained panel launches mix inside the workgroup (the MIX
-// instantiations of panel_fwd_kernel / panel_bwd_kernel); everywhere else - the decoder of step 0, the unchained
-// panel path, the GEMM path, the step API - the aggregation is mix_msg_kernel (rowops.hip) in a launch of its own
-// and the panel kernels stage plain rows.
-static const float* g_comm = nullptr;
-static int g_comm_na = 0;
-// marl_comm_range: radius >= 0 = the matrix above is the BASE of a range-limited exchange - per image and step it is
-// gated by the agents' positions (CommGate, common.h).  The message emitted in step t (MSG[t + 1]) is aggregated under
-// the positions of its emission, POS[t]; the zero message of step 0 under POS[0].  The chained panel launches build
-// the gated matrices in their workgroups (the GATE instantiations), every other site takes mix_msg_gated_kernel.
-static CommGate g_range = {nullptr, -1, 0, 1};
-// marl_policy_explore (marl_hip_explore.h): exploration controls of every sampling site and of the policy head's
-// backward, process-global like the two above.  on = anything but (tau 1, eps 0, sampled): only then does a call take
-// the EXPLORE kernels - with it off every entry launches what it always launched.
-struct Explore {
-    bool on;
-    float inv_tau, keep, eps;  // 1 / tau, 1 - eps, eps (the floor eps / nA is formed where nA is known)
-    int greedy;
-};
-static Explore g_explore = {false, 1.f, 1.f, 0.f, 0};
-// the sampling arguments of a call under the installed controls (greedy reads neither noise nor generator)
-static void explore_sample_args(SampleArgs& a) {
-    if (!g_explore.on) return;
-    a.ex_inv_tau = g_explore.inv_tau;
-    a.ex_keep = g_explore.keep;
-    a.ex_floor = g_explore.eps / (float)a.nA;
-    a.ex_greedy = g_explore.greedy;
-    if (g_explore.greedy) {
-        a.noise = nullptr;
-        a.rng_on = 0;
+    const int k_lstm = tune_get("g3_lstm", 1), k_tn = tune_get("g3_tn", 1);
+    p.g3_lstm = e.g3 && k_lstm != 0;
+    if (p.g3_lstm) {  // the launcher's own rule with the shapes of the launch
+        G3Batch b{};
+        b.count = 2;
+        b.p[0].m = b.p[1].m = (int)d.R;
+        b.p[0].n = d.n_b;
+        b.p[1].n = d.n_a;
+        p.lstm_plan = tune_get("g3_lstm_variant", 0);
+        if (!p.lstm_plan) p.lstm_plan = g3_lstm_plan(b);
     }
+    // the four large weight gradients on images (gemm_tn3_kernel: 256-column tiles of A, whole 256 x 256 tiles
+    // or column passes, g3_tn_plan): only where that form wins - >= 32768 contraction rows (at C4's 8192 rows the
+    // fp32-operand kernel is 25 % faster) and at most three column passes on the B side
+    // (round 5: the one-launch-per-cell form wins from 8 192 rows on - C4 at 32 images per GPU: 3.62 vs 3.69 ms)
+    p.g3_tn = p.g3_lstm && k_tn != 0 &&
+              (k_tn == 2 || (d.nin <= 640 && d.n_b <= 512 && d.n_a <= 512 &&
+                             (d.NR >= 32768 || (g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) &&
+                                                g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR)))));
+    p.g3_tn_pipe = p.g3_tn && tune_get("g3_tn_pipe", 1) != 0;
+    p.skip_f32 = p.panels_bwd && p.g3_tn;
+    // the three kernels that write U[t] (fused CNN: features; decoder panel: message columns; sampling
+    // launch: position embedding) also write its image when all of them are on the path and the column
+    // ranges keep 8-byte image pieces whole; else (and for step 0, whose embedding comes from the
+    // stand-alone kernel) one image pass over U[t] runs ahead of the LSTM launch
+    static float here;  // (only the presence of the fragment-order weight copies the AidCnn kernels ask for matters)
+    CnnFwdArgs probe = cnn_fwd_shape(d);
+    for (int l = 0; l < d.L; ++l) probe.layer[l].wfrag = w.wf[4 * l] ? &here : nullptr;
+    p.u3_by_producers = p.g3_lstm && e.fused_fwd && cnn_fwd_writes_image(probe) && p.panels &&
+                        ((d.nf | d.n_mo | d.n_d) & 3) == 0 &&
+                        // (the producers write exactly nin columns: a K pad of the last 16-deep step would be
+                        // whatever the workspace held - only the stand-alone image pass zeroes it)
+                        d.nin % 16 == 0;
+    return p;
 }
-// marl_class_loss (marl_hip_classloss.h): options of the vote error and the rewards of every loss entry,
-// process-global like the three above.  on = anything was installed (neutral values too): only then does a loss
-// entry take the option instances of the two kernels - with it off every entry launches what it always launched.
-struct ClassLoss {
-    bool on;
-    const float* w;   // [nc] device, nullptr = all ones
-    int nc;
-    float eps;
-    const float* sw;  // [ns] device, nullptr = all ones
-    int ns;
-    bool wrew;
-};
-static ClassLoss g_class_loss = {false, nullptr, 0, 0.f, nullptr, 0, false};
 
 static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void* ews, size_t ebytes,
                     int train, void* stream, Ctx& c) {
     MARL_TRY(make_dims(cfg, c.d));
-    if (g_comm && g_comm_na != c.d.na) {  // (before anything is enqueued)
-        set_error("communication matrix is %d x %d but the configuration has %d agents", g_comm_na, g_comm_na,
-                  c.d.na);
+    c.opt = g_installed;
+    if (c.opt.comm && c.opt.comm_na != c.d.na) {  // (before anything is enqueued)
+        set_error("communication matrix is %d x %d but the configuration has %d agents", c.opt.comm_na,
+                  c.opt.comm_na, c.d.na);
         return MARL_EINVAL;
     }
-    if (g_range.radius >= 0 && !g_comm) {
+    if (c.opt.range.radius >= 0 && !c.opt.comm) {
         set_error("a communication range is installed without its base matrix (marl_comm_matrix)");
         return MARL_EINVAL;
     }
@@ -751,18 +820,7 @@ static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void
         set_error("workspaces must be 256-byte aligned");
         return MARL_EINVAL;
     }
-    // the three kernels that write U[t] (fused CNN: features; decoder panel: message columns; sampling
-    // launch: position embedding) also write its image when all of them are on the path and the column
-    // ranges keep 8-byte image pieces whole; else (and for step 0, whose embedding comes from the
-    // stand-alone kernel) one image pass over U[t] runs ahead of the LSTM launch
-    CnnFwdArgs probe = cnn_fwd_shape(c.d);  // (with the fragment-order weight copies the AidCnn kernels ask for)
-    for (int l = 0; l < c.d.L; ++l) probe.layer[l].wfrag = c.w.wf[4 * l] ? c.W + c.w.wf[4 * l] : nullptr;
-    c.u3_by_producers = c.e.g3 && tune_get("g3_lstm", 1) != 0 && c.e.fused_fwd &&
-                        cnn_fwd_writes_image(probe) && use_panels(c.d) &&
-                        ((c.d.nf | c.d.n_mo | c.d.n_d) & 3) == 0 &&
-                        // (the producers write exactly nin columns: a K pad of the last 16-deep step would be
-                        // whatever the workspace held - only the stand-alone image pass zeroes it)
-                        c.d.nin % 16 == 0;
+    c.plan = make_plan(c.d, c.w, c.e, c.opt);
     return MARL_OK;
 }
 
@@ -789,16 +847,6 @@ struct StepIn {
     const void* img = nullptr;
     int img_u8 = 0;
 };
-
-static bool use_panels(const Dims& d) {
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("MARL_PANELS");
-        enabled = (e && e[0] == '0') ? 0 : 1;
-    }
-    return enabled && panel_supported(d.n_m, d.nm2, d.n_mo) && panel_supported(d.n_b, d.nm2, d.n_m) &&
-           panel_supported(d.n_a, d.nla, 0);
-}
 
 // What one launch of the fused extractor forward reads and writes.  step_cnn fills it from the episode workspace,
 // marl_cnn_fwd (include/marl_hip_cnnops.h) from its caller's buffers; cnn_fwd_args is the only place that turns it
@@ -864,7 +912,7 @@ static int step_cnn(const Ctx& c, int t, const StepIn& in) {
         }
         io.u = c.at(c.e.U, t);
         io.ldu = d.ld_nin;
-        if (c.u3_by_producers) {
+        if (c.plan.u3_by_producers) {
             io.u3 = c.img(c.e.U3);
             io.u3_row0 = c.u3_row(t);
             io.u3_steps = img_steps(d.nin);
@@ -905,16 +953,16 @@ static int step_cnn(const Ctx& c, int t, const StepIn& in) {
 
 // the gate under which MSG[t] is aggregated (pos null: no range installed): the positions of its emission step
 static CommGate comm_gate(const Ctx& c, int t) {
-    CommGate g = g_range;
-    g.pos = g_range.radius >= 0 ? c.POSs(t > 0 ? t - 1 : 0) : nullptr;
+    CommGate g = c.opt.range;
+    g.pos = g.radius >= 0 ? c.POSs(t > 0 ? t - 1 : 0) : nullptr;
     return g;
 }
 // the exchange of MSG[t] (or, transpose, of its gradient) under the installed matrix, in a launch of its own
 static int mix_msg(const Ctx& c, int t, const float* m, float* out, int n, int transpose) {
     const Dims& d = c.d;
-    if (g_range.radius >= 0)
-        return launch_mix_msg_gated(m, out, d.ld_nm, d.na, d.nb, n, g_comm, comm_gate(c, t), transpose, c.st);
-    return launch_mix_msg(m, out, d.ld_nm, d.na, d.nb, n, g_comm, transpose, c.st);
+    if (c.opt.range.radius >= 0)
+        return launch_mix_msg_gated(m, out, d.ld_nm, d.na, d.nb, n, c.opt.comm, comm_gate(c, t), transpose, c.st);
+    return launch_mix_msg(m, out, d.ld_nm, d.na, d.nb, n, c.opt.comm, transpose, c.st);
 }
 
 // the decoder's two layers of step t (outputs: AD1[t], U[t][:, nf:nf+n_mo])
@@ -929,7 +977,7 @@ static void fill_dec_layers(const Ctx& c, int t, PanelLayer* layer) {
                           c.wp(MARL_P_DEC_LN1W), c.wp(MARL_P_DEC_LN1B), d.n_mo,
                           keep ? c.at(c.e.ZD2, t) : nullptr, d.ld_nmo,
                           keep ? c.at(c.e.STD2, t) : nullptr, c.at(c.e.U, t) + d.nf, d.ld_nin};
-    if (c.u3_by_producers) {
+    if (c.plan.u3_by_producers) {
         layer[1].a3 = c.img(c.e.U3);
         layer[1].a3_row0 = c.u3_row(t);
         layer[1].a3_steps = img_steps(d.nin);
@@ -938,13 +986,12 @@ static void fill_dec_layers(const Ctx& c, int t, PanelLayer* layer) {
 }
 
 // message mean over the other agents + decoder -> U[t][:, nf:nf+n_mo]   (needs MSG[t])
-// `sample` (panel path only): the sampling rows of the PREVIOUS step ride along in the same
-// launch (they are independent of the decoder); *fused reports whether that happened
-static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, bool* fused = nullptr) {
+// `sample` (panel path only, SAMPLE_RIDE): the sampling rows of the PREVIOUS step ride along in the same launch
+static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr) {
     const Dims& d = c.d;
     const int R = (int)d.R;
     hipStream_t st = c.st;
-    if (use_panels(d)) {
+    if (c.plan.panels) {
         PanelFwdBatch pb{};
         pb.count = 1;
         PanelFwdProb& p = pb.p[0];
@@ -954,7 +1001,7 @@ static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, 
         p.agg_na = d.na;
         p.agg_nb = d.nb;
         p.xbar = c.at(c.e.MBAR, t);
-        if (g_comm) {  // mixed rows (pad columns included: the panel stages whole float4s) -> MBAR, staged as they are
+        if (c.opt.comm) {  // mixed rows (pad columns included: the panel stages whole float4s) -> MBAR, staged as they are
             MARL_TRY(mix_msg(c, t, c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, 0));
             p.x = c.at(c.e.MBAR, t);
             p.agg_na = p.agg_nb = 0;
@@ -966,11 +1013,10 @@ static int step_decode(const Ctx& c, int t, const SampleArgs* sample = nullptr, 
         if (sample) {
             pb.has_sample = 1;
             pb.sample = *sample;
-            if (fused) *fused = true;
         }
         return launch_panel_fwd(pb, st);
     }
-    if (g_comm)
+    if (c.opt.comm)
         MARL_TRY(mix_msg(c, t, c.MSGs(t), c.at(c.e.MBAR, t), d.n_m, 0));
     else
         MARL_TRY(launch_agg_msg(c.MSGs(t), c.at(c.e.MBAR, t), d.ld_nm, d.na, d.nb, d.n_m, st));
@@ -996,11 +1042,11 @@ static int step_pos_lstm(const Ctx& c, int t, const StepIn& in, bool pos_done = 
                                   c.wp(MARL_P_POS_B), c.wp(MARL_P_POS_LNW), c.wp(MARL_P_POS_LNB),
                                   c.at(c.e.NPOS, t), c.at(c.e.ZPOS, t), d.ld_nd, c.at(c.e.STPOS, t),
                                   c.at(c.e.U, t) + d.nf + d.n_mo, d.ld_nin, d.R, d.n_d, st));
-    if (c.e.g3 && tune_get("g3_lstm", 1) != 0) {
+    if (c.plan.g3_lstm) {
         // image form: U[t] is complete here -> its k16 image (until its three producers write it
         // themselves), then both cells from images; the epilogue writes the images of h' / h^'
         const int u_row0 = c.u3_row(t);
-        if (!c.u3_by_producers || t == 0 || in.obs) {
+        if (!c.plan.u3_by_producers || t == 0 || in.obs) {
             ImgBatch ib{};
             ib.d[0] = ImgDesc{c.at(c.e.U, t), c.img(c.e.U3) + img_off(u_row0, 0, img_steps(d.nin)), d.R, d.nin, d.ld_nin};
             ib.count = 1;
@@ -1094,7 +1140,7 @@ static int step_encode_policy(const Ctx& c, int t) {
     const Dims& d = c.d;
     const int R = (int)d.R;
     hipStream_t st = c.st;
-    if (use_panels(d)) {
+    if (c.plan.panels) {
         PanelFwdBatch pb{};
         pb.count = 2;
         fill_enc_prob(c, t, pb.p[0]);
@@ -1119,29 +1165,8 @@ static int step_encode_policy(const Ctx& c, int t) {
                               c.at(c.e.STE2, t), d.R, d.n_m, st);
 }
 
-// All agents of a batch element in one workgroup (rows a * nb + b for every a), so that the
-// message mean over the other agents needs no second launch:
-//   forward : encoder(t) -> MSG[t+1] -> mean -> decoder(t+1) -> U[t+1]  ||  policy hidden layer(t)
-//   backward: decoder(t) -> mean -> encoder(t-1) -> dh_t complete -> belief cell(t-1)
-static bool use_chain(const Dims& d) {
-    return use_panels(d) && panel_chain_supported(d.na, d.n_m, 256) && d.n_mo <= 384 && d.nm2 <= 384 &&
-           d.n_m <= 384 && tune_get("panel_chain", 1) != 0 &&
-           // under a matrix the chained kernels also keep it in LDS (16 x 16 floats): with the input width bounded
-           // like the others every admitted plan has room for it; wider models take mix_msg_kernel
-           (!g_comm || d.n_b <= 384);
-}
-// sample(t) as the epilogue of the chain launch's policy workgroups (MARL_PANEL_SAMPLE=0: chain launch, then
-// sample_kernel - the earlier form, kept for comparison in one binary)
-static bool use_panel_sample(const Dims& d) {
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("MARL_PANEL_SAMPLE");
-        enabled = (e && e[0] == '0') ? 0 : 1;
-    }
-    return enabled && panel_sample_supported(d.nA);
-}
-// `sample`: the step's sampling arguments, run inside this launch when use_panel_sample() (else ignored)
-static int step_chain(const Ctx& c, int t, const SampleArgs* sample = nullptr) {
+// the chain launch of step t: encoder(t) -> decoder(t+1) || policy layer(t) [-> sample(t) under SAMPLE_EPILOGUE]
+static int step_chain(const Ctx& c, int t, const SampleArgs& sample) {
     const Dims& d = c.d;
     PanelFwdBatch pb{};
     pb.count = 2;
@@ -1156,14 +1181,14 @@ static int step_chain(const Ctx& c, int t, const SampleArgs* sample = nullptr) {
         pe.agg_at = 2;
         pe.xbar = c.at(c.e.MBAR, t + 1);
         pe.ld_xbar = d.ld_nm;
-        pe.mix = g_comm;  // (null: the mean)
-        if (g_comm) pe.gate = comm_gate(c, t + 1);
+        pe.mix = c.opt.comm;  // (null: the mean)
+        if (c.opt.comm) pe.gate = comm_gate(c, t + 1);
     }
     fill_pol_prob(c, t, pb.p[1]);
-    if (sample && use_panel_sample(d)) {
+    if (c.plan.sample == SAMPLE_EPILOGUE) {
         pb.epi_prob = 2;
-        pb.sample = *sample;
-        return launch_panel_fwd(pb, c.st, g_explore.on);  // (the EXPLORE epilogues under exploration controls)
+        pb.sample = sample;
+        return launch_panel_fwd(pb, c.st, c.opt.explore.on);  // (the EXPLORE epilogues under exploration controls)
     }
     return launch_panel_fwd(pb, c.st);
 }
@@ -1180,7 +1205,7 @@ static int step_core(const Ctx& c, int t, const StepIn& in) {
 static int heads_batched(const Ctx& c, int t0, int64_t rows, float* values, float* preds) {
     const Dims& d = c.d;
     hipStream_t st = c.st;
-    if (c.e.g3 && tune_get("g3_lstm", 1) != 0) {  // A = the images the LSTM epilogues wrote
+    if (c.plan.g3_lstm) {  // A = the images the LSTM epilogues wrote
         const int r1 = (int)((int64_t)(t0 + 1) * d.R);
         G3Batch g{};
         g.p[0] = g3_prob(c.img(c.e.HC3), r1, c.wp3k(MARL_P_CRI_W0), 0, d.n_a, c.at(c.e.ZC1), d.ld_nla, (int)rows, d.nla,
@@ -1209,9 +1234,63 @@ static int heads_batched(const Ctx& c, int t0, int64_t rows, float* values, floa
     return MARL_OK;
 }
 
-static void fill_sample_args(const Ctx& c, const marl_config* cfg, int t, SampleArgs& a) {
+// the sampling arguments of a call under the installed controls (greedy reads neither noise nor generator)
+static void explore_sample_args(const Explore& ex, SampleArgs& a) {
+    if (!ex.on) return;
+    a.ex_inv_tau = ex.inv_tau;
+    a.ex_keep = ex.keep;
+    a.ex_floor = ex.eps / (float)a.nA;
+    a.ex_greedy = ex.greedy;
+    if (ex.greedy) {
+        a.noise = nullptr;
+        a.rng_on = 0;
+    }
+}
+
+// a call's sampling inputs and outputs, [Ns] leading (step t takes its slice)
+struct SampleIo {
+    const float* noise = nullptr;     // [Ns, R, nA] Exp(1) draws, or null
+    const int64_t* forced = nullptr;  // [Ns, R] forced actions, or null
+    uint64_t rng_seed = 0, rng_offset = 0;
+    const void* counters = nullptr;
+    int64_t *step_pos = nullptr, *step_actions = nullptr;
+    float* step_logp = nullptr;       // null: probabilities only - no draw, no generator, none of the outputs above
+    bool embed_next = false;          // the position embedding of step t+1 rides along with the move (episode loop)
+};
+// the one builder of step t's SampleArgs
+static void fill_sample_args(const Ctx& c, const marl_config* cfg, int t, const SampleIo& io, SampleArgs& a) {
     const Dims& d = c.d;
     memset(&a, 0, sizeof(a));
+    if (io.step_logp) {
+        a.noise = io.noise ? io.noise + (size_t)t * d.R * d.nA : nullptr;
+        a.rng_on = !io.noise && !io.forced;  // perf mode: Exp(1) drawn inside the kernel
+        a.rng_seed = io.rng_seed ^ 0x9E3779B97F4A7C15ull;  // a key of its own (marl_draw_episode uses rng_seed)
+        a.rng_ctr = (io.rng_offset << 16) + (uint64_t)t;
+        a.rng_off_dev = io.counters ? &static_cast<const Counters*>(io.counters)->rng_offset : nullptr;
+        a.forced = io.forced ? io.forced + (size_t)t * d.R : nullptr;
+        a.step_pos = io.step_pos ? io.step_pos + (size_t)t * d.R * 2 : nullptr;
+        a.step_actions = io.step_actions ? io.step_actions + (size_t)t * d.R : nullptr;
+        a.step_logp = io.step_logp + (size_t)t * d.R;
+    }
+    if (io.embed_next && t + 1 < d.ns) {
+        a.pe_W = c.wp(MARL_P_POS_W);
+        a.pe_b = c.wp(MARL_P_POS_B);
+        a.pe_gamma = c.wp(MARL_P_POS_LNW);
+        a.pe_beta = c.wp(MARL_P_POS_LNB);
+        a.pe_npos = c.at(c.e.NPOS, t + 1);
+        a.pe_z = c.at(c.e.ZPOS, t + 1);
+        a.pe_stats = c.at(c.e.STPOS, t + 1);
+        a.pe_out = c.at(c.e.U, t + 1) + d.nf + d.n_mo;
+        a.pe_ldz = d.ld_nd;
+        a.pe_ldo = d.ld_nin;
+        a.pe_nd = d.n_d;
+        if (c.plan.u3_by_producers) {
+            a.pe_img = c.img(c.e.U3);
+            a.pe_row0 = c.u3_row(t + 1);
+            a.pe_steps = img_steps(d.nin);
+            a.pe_col0 = d.nf + d.n_mo;
+        }
+    }
     a.a_pol = c.at(c.e.AP1, t);
     a.ld_a = d.ld_nla;
     a.nla = d.nla;
@@ -1231,6 +1310,37 @@ static void fill_sample_args(const Ctx& c, const marl_config* cfg, int t, Sample
         a.table[j][0] = cfg->actions[j][0];
         a.table[j][1] = cfg->actions[j][1];
     }
+    explore_sample_args(c.opt.explore, a);
+}
+
+// ---- the forward loop's step t, one function per form (Plan::chain / panels) ----
+// what every form opens with: extractor, decoder(t) unless step t-1 ran it, lambda_t (t > 0: by sample(t-1)) + cells
+static int fwd_open(const Ctx& c, int t, const StepIn& in, bool decode) {
+    MARL_TRY(step_cnn(c, t, in));
+    if (decode) MARL_TRY(step_decode(c, t));
+    return step_pos_lstm(c, t, in, t > 0);
+}
+// chained panels: ... -> chain launch (encoder(t) -> decoder(t+1) || policy(t) [-> sample(t)])
+static int fwd_step_chain(const Ctx& c, int t, const StepIn& in, const SampleArgs& a) {
+    MARL_TRY(fwd_open(c, t, in, t == 0));
+    MARL_TRY(step_chain(c, t, a));
+    return c.plan.sample == SAMPLE_EPILOGUE ? MARL_OK : launch_sample(a, c.st, c.opt.explore.on);
+}
+// unchained panels: ... -> encoder(t) || policy(t) -> decoder(t+1) [|| sample(t): not for the last step]
+static int fwd_step_panels(const Ctx& c, int t, const StepIn& in, const SampleArgs& a) {
+    const bool ride = c.plan.sample == SAMPLE_RIDE && t + 1 < c.d.ns;
+    MARL_TRY(fwd_open(c, t, in, t == 0));
+    MARL_TRY(step_encode_policy(c, t));
+    if (t + 1 < c.d.ns) MARL_TRY(step_decode(c, t + 1, ride ? &a : nullptr));
+    return ride ? MARL_OK : launch_sample(a, c.st, c.opt.explore.on);
+}
+// rows (GEMM + LayerNorm launches): decoder(t) -> ... -> encoder(t), policy(t) -> decoder(t+1) -> sample(t).  (This
+// form has always issued decoder(t+1) twice - here and at the top of step t+1, same inputs, same outputs.)
+static int fwd_step_rows(const Ctx& c, int t, const StepIn& in, const SampleArgs& a) {
+    MARL_TRY(fwd_open(c, t, in, true));
+    MARL_TRY(step_encode_policy(c, t));
+    if (t + 1 < c.d.ns) MARL_TRY(step_decode(c, t + 1));
+    return launch_sample(a, c.st, c.opt.explore.on);
 }
 
 // ---------------------------------------------------------------------------
@@ -1519,9 +1629,6 @@ static int gate_image_fallback(const Ctx& c, const PanelBwdProb& pd, int t) {
     return launch_images(ib, c.st);
 }
 
-// marl_backward_heads_event: recorded by episode_backward once the heads' parameter gradients are final
-static hipEvent_t g_heads_event = nullptr;
-
 // marl_step_backward: what one standalone step (nb_steps = 1) adds to the episode's backward
 struct StepBwd {
     const float* obs = nullptr;      // [R, C, f, f]: the first convolution's input (there is no image batch)
@@ -1535,14 +1642,14 @@ struct StepBwd {
 // ---- one builder per descriptor (the backward's counterparts of fill_dec_layers / fill_enc_prob) ----
 
 // elementwise backward of the belief (which = 0) or action (1) cell of step t: dh = DH / DH^[t + 1], gates G[t]
-static LstmBwdArgs cell_bwd_args(const Ctx& c, int which, int t, int skip_f32) {
+static LstmBwdArgs cell_bwd_args(const Ctx& c, int which, int t) {
     const Dims& d = c.d;
     const int n = which ? d.n_a : d.n_b, ld = which ? d.ld_na : d.ld_nb;
     return LstmBwdArgs{which ? c.DHCs(t + 1) : c.DHs(t + 1), c.at(which ? c.e.DCC : c.e.DC),
                        c.at(which ? c.e.GA : c.e.GB, t), which ? c.CCs(t) : c.Cs(t),
                        which ? c.CCs(t + 1) : c.Cs(t + 1), ld, ld, which ? d.ld_ga : d.ld_gb, ld, n,
                        c.e.g3 ? c.img(which ? c.e.GA3 : c.e.GB3) : nullptr, (int)((int64_t)t * d.R), img_steps(4 * n),
-                       skip_f32};
+                       c.plan.skip_f32};
 }
 
 // the decoder's two layers of step t, output side first (pblk: floats per step and column of a PLN partial)
@@ -1597,9 +1704,6 @@ struct BwdState {
     const StepBwd* sb;
     bool enc_last = false;     // a standalone step with an upstream gradient of its new message
     bool heads_early = false;  // the heads' gradients were flushed and unpacked ahead of the loop
-    bool panels = false;       // the loop runs panel launches (else GEMM + ln_bwd rows)
-    bool chain = false;        // ... the chained ones
-    int skip_f32 = 0;          // every consumer of the gate gradients reads their images: no fp32 copy at all
     int pln_blocks = 0;        // workgroups of one panel launch = partial rows per step in PLN
     bool action_done = false;  // the action cell of this step was handled by the ride-along
     bool belief_done = false;  // the belief cell: by the epilogue of the chained panel launch
@@ -1656,10 +1760,10 @@ static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, con
     if (sb && sb->g_probs) g_probs = sb->g_probs;
     // the saved rows hold the behaviour policy (marl_policy_explore): its own backward, both cases (greedy alone
     // leaves the distribution the plain softmax: the kernels below, as always)
-    if (g_explore.on && (g_explore.inv_tau != 1.f || g_explore.eps != 0.f))
+    const Explore& ex = c.opt.explore;
+    if (ex.on && (ex.inv_tau != 1.f || ex.eps != 0.f))
         MARL_TRY(launch_policy_dlogits_explore(g_logp, g_probs, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG), d.ld_nA, NR,
-                                               d.nA, g_explore.inv_tau, g_explore.keep,
-                                               g_explore.eps / (float)d.nA, st));
+                                               d.nA, ex.inv_tau, ex.keep, ex.eps / (float)d.nA, st));
     else if (g_probs)  // dL/dprobs from the caller (+ the dlogp term): a standalone step [R, nA] or all steps [Ns, R, nA]
         MARL_TRY(launch_policy_dlogits_probs(g_logp, g_probs, c.PROBSs(0), c.ACTs(0), c.at(c.e.DLOG),
                                              d.ld_nA, NR, d.nA, st));
@@ -1692,12 +1796,12 @@ static int bwd_heads(BwdState& s, const float* g_preds, const float* g_logp, con
 
     // Data parallelism (parallel.py, BucketedGradAllReduce): every gradient of the three heads' parameters (POL_*,
     // CRI_*, PRE_*) is complete here, ahead of the ~1.4 ms reverse loop - flush what they queued and mark the point.
-    s.heads_early = g_heads_event != nullptr && !sb;
+    s.heads_early = c.opt.heads_event != nullptr && !sb;
     if (s.heads_early) {
         if (c.tq) MARL_TRY(launch_tn_queue(s.tq, c.rq, st));
         MARL_TRY(s.rq.flush());
         MARL_TRY(unpack_grads(c, grads, 1));  // (their matrices leave the packed layout now; the end skips them)
-        MARL_HIP_CHECK(hipEventRecord(g_heads_event, st));
+        MARL_HIP_CHECK(hipEventRecord(c.opt.heads_event, st));
     }
     return MARL_OK;
 }
@@ -1736,8 +1840,8 @@ static int bwd_recurrent(const BwdState& s, int t, float* ddbar, float* ddbar2) 
         {1, MARL_P_LA_WHH, 0, c.DHCs(t), d.ld_na, d.n_a, 1},
         {0, MARL_P_LB_WIH, d.nf, ddbar, d.ld_dbl, d.n_mo + d.n_d, 0},
         {1, MARL_P_LA_WIH, d.nf, ddbar2, d.ld_dbl, d.n_mo + d.n_d, 0}};
-    const int count = s.panels ? 4 : 2;
-    if (s.panels && c.e.g3) {  // from the images of the gate gradients
+    const int count = c.plan.panels_bwd ? 4 : 2;
+    if (c.plan.panels_bwd && c.e.g3) {  // from the images of the gate gradients
         G3Batch g{};
         for (int i = 0; i < count; ++i) {
             const auto& q = prod[i];
@@ -1754,7 +1858,7 @@ static int bwd_recurrent(const BwdState& s, int t, float* ddbar, float* ddbar2) 
                             c.wtB(q.w).from_row(q.row0), q.out, q.ldo, R, q.n, nullptr, q.acc);
     }
     gb.count = count;
-    if (!s.panels) {  // rows path: only the message columns, both cells' shares summed by one two-segment product
+    if (!c.plan.panels_bwd) {  // rows path: only the message columns, both cells' shares summed by one two-segment product
         GemmProb& p = gb.p[gb.count++];
         p = gemm_prob(c.at(c.e.GB, t), d.ld_gb, c.wtB(MARL_P_LB_WIH).from_row(d.nf), ddbar, d.ld_dbl, R, d.n_mo);
         gemm_add_seg(p, c.at(c.e.GA, t), d.ld_ga, c.wtB(MARL_P_LA_WIH).from_row(d.nf));
@@ -1780,7 +1884,7 @@ static void fill_dec_bwd_prob(BwdState& s, int t, float* ddbar, float* ddbar2, P
     pd.accumulate = 0;
     if (t > 0) {  // action cell of step t-1: gates GA[t-1], dh^ = DHC[t]
         pd.has_cell = 1;
-        pd.cell = cell_bwd_args(c, 1, t - 1, s.skip_f32);
+        pd.cell = cell_bwd_args(c, 1, t - 1);
         pd.cell_rows = d.R;
         s.action_done = true;
     }
@@ -1798,14 +1902,14 @@ static int bwd_step_chain(BwdState& s, int t, float* ddbar, float* ddbar2) {
     if (t > 0) {
         pd.nlayers = 4;
         pd.agg_at = 2;
-        pd.mix = g_comm;  // (null: the self-adjoint mean; else the kernel applies M^T)
-        if (g_comm) pd.gate = comm_gate(c, t);
+        pd.mix = c.opt.comm;  // (null: the self-adjoint mean; else the kernel applies M^T)
+        if (c.opt.comm) pd.gate = comm_gate(c, t);
         fill_enc_bwd_layers(c, t - 1, (size_t)s.pln_blocks * 2, pd.layer + 2);
         pd.dx = c.DHs(t);
         pd.lddx = d.ld_nb;
         pd.accumulate = 1;
         pd.has_cellb = 1;
-        pd.cellb = cell_bwd_args(c, 0, t - 1, s.skip_f32);
+        pd.cellb = cell_bwd_args(c, 0, t - 1);
         s.belief_done = true;
     }
     MARL_TRY(launch_panel_bwd(pd, c.st));
@@ -1826,7 +1930,7 @@ static int bwd_step_panels(BwdState& s, int t, float* ddbar, float* ddbar2) {
     pe.ldda = d.ld_nm;
     pe.agg_na = d.na;
     pe.agg_nb = d.nb;
-    if (g_comm) {  // M^T in place (a thread owns one (batch, column) over all agents), then plain rows
+    if (c.opt.comm) {  // M^T in place (a thread owns one (batch, column) over all agents), then plain rows
         MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, 1));
         pe.agg_na = pe.agg_nb = 0;
     }
@@ -1856,7 +1960,7 @@ static int bwd_step_rows(const BwdState& s, int t, float* ddbar) {
         MARL_TRY(gemm1(c, gemm_prob(dad1, d.ld_nm2, c.wtB(MARL_P_DEC_W0), c.at(c.e.DMBAR), d.ld_nm, R, d.n_m)));
     if (t == 0) return MARL_OK;
     float* dze2 = c.at(c.e.DZE2) + (size_t)(t - 1) * d.R * d.ld_nm;
-    if (g_comm)  // the transpose of the mixing matrix
+    if (c.opt.comm)  // the transpose of the mixing matrix
         MARL_TRY(mix_msg(c, t, c.at(c.e.DMBAR), dze2, d.n_m, 1));
     else  // the message mean is self-adjoint
         MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), dze2, d.ld_nm, d.na, d.nb, d.n_m, c.st));
@@ -1871,10 +1975,9 @@ static int bwd_loop(BwdState& s) {
     hipStream_t st = c.st;
     const int ns = d.ns;
     const size_t s_nmo = (size_t)d.R * d.ld_dbl;
-    s.panels = use_panels(d) && d.n_mo <= 384 && d.nm2 <= 384 && d.n_m <= 384;
     // the per-step LayerNorm reductions of the unfused path accumulate into the gradients step
     // by step: nothing of a parameter may still be queued then, so that path does not defer
-    if (!s.panels) {
+    if (!c.plan.panels_bwd) {
         MARL_TRY(launch_tn_queue(s.tq, c.rq, st));  // (what the heads queued so far)
         c.rq = nullptr;
         c.tq = nullptr;
@@ -1888,16 +1991,13 @@ static int bwd_loop(BwdState& s) {
         MARL_TRY(enc_bwd_rows(s, ns - 1, 0, c.DHs(ns)));
     }
     // with panels dU[:, nf:] (message + embedding columns) comes out of the loop
-    s.chain = s.panels && use_chain(d);
-    // every consumer on images (in-loop batch, dU, the four weight gradients): no fp32 copy of them at all
-    s.skip_f32 = c.e.g3 && s.panels && g3_tn_enabled(d);
-    s.pln_blocks = s.chain ? panel_chain_blocks(d.na, d.nb) : panel_bwd_blocks((int)d.R);
+    s.pln_blocks = c.plan.chain ? panel_chain_blocks(d.na, d.nb) : panel_bwd_blocks((int)d.R);
     for (int t = ns - 1; t >= 0; --t) {
         {   // cells of step t not yet handled inside the previous iteration's panel launch
             LstmBwdBatch lb{};
             int nc = 0;
-            if (!s.belief_done) lb.a[nc++] = cell_bwd_args(c, 0, t, s.skip_f32);
-            if (!s.action_done) lb.a[nc++] = cell_bwd_args(c, 1, t, s.skip_f32);
+            if (!s.belief_done) lb.a[nc++] = cell_bwd_args(c, 0, t);
+            if (!s.action_done) lb.a[nc++] = cell_bwd_args(c, 1, t);
             lb.rows = d.R;
             if (nc) MARL_TRY(launch_lstm_cell_bwd_batch(lb, nc, st));
         }
@@ -1905,9 +2005,9 @@ static int bwd_loop(BwdState& s) {
         float* ddbar = c.at(c.e.DDBAR) + (size_t)t * s_nmo;
         float* ddbar2 = c.at(c.e.DDBAR2) + (size_t)t * s_nmo;
         MARL_TRY(bwd_recurrent(s, t, ddbar, ddbar2));
-        if (s.chain)
+        if (c.plan.chain)
             MARL_TRY(bwd_step_chain(s, t, ddbar, ddbar2));
-        else if (s.panels)
+        else if (c.plan.panels_bwd)
             MARL_TRY(bwd_step_panels(s, t, ddbar, ddbar2));
         else
             MARL_TRY(bwd_step_rows(s, t, ddbar));
@@ -1916,8 +2016,8 @@ static int bwd_loop(BwdState& s) {
         // (DMBAR = dL/d(mean message) of step 0; the mean is self-adjoint and may run in place: every thread
         // owns one (batch, column) over all agents)
         if (sb->d_msg) {
-            if (g_comm)  // d msg goes through M^T, also in place (the kernel holds all agents' inputs in registers)
-                MARL_TRY(launch_mix_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.n_m, g_comm, 1, st));
+            if (c.opt.comm)  // d msg goes through M^T, also in place (the kernel holds all agents' inputs in registers)
+                MARL_TRY(launch_mix_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.n_m, c.opt.comm, 1, st));
             else
                 MARL_TRY(launch_agg_msg(c.at(c.e.DMBAR), c.at(c.e.DMBAR), d.ld_nm, d.na, d.nb, d.n_m, st));
             MARL_TRY(launch_copy2d(c.at(c.e.DMBAR), d.ld_nm, sb->d_msg, d.n_m, d.R, d.n_m, st));
@@ -1927,7 +2027,7 @@ static int bwd_loop(BwdState& s) {
         if (sb->d_hc) MARL_TRY(launch_copy2d(c.DHCs(0), d.ld_na, sb->d_hc, d.n_a, d.R, d.n_a, st));
         if (sb->d_cc) MARL_TRY(launch_copy2d(c.at(c.e.DCC), d.ld_na, sb->d_cc, d.n_a, d.R, d.n_a, st));
     }
-    if (s.panels) {  // LayerNorm affine gradients of the in-loop layers: one reduction each
+    if (c.plan.panels_bwd) {  // LayerNorm affine gradients of the in-loop layers: one reduction each
         const int64_t nblk = s.pln_blocks;
         MARL_TRY(launch_reduce_affine(c.at(c.e.PLN[0]), nblk * ns, d.n_mo, grads[MARL_P_DEC_LN1W],
                                       grads[MARL_P_DEC_LN1B], 0, st, c.rq));
@@ -1964,12 +2064,11 @@ static int bwd_chain_wgrads(const BwdState& s) {
         MARL_TRY(launch_fill(c.gp(MARL_P_ENC_W0), (int64_t)d.nm2 * c.w.ldp[MARL_P_ENC_W0], 0.f, c.st));
         MARL_TRY(launch_fill(c.gp(MARL_P_ENC_W1), (int64_t)d.n_m * c.w.ldp[MARL_P_ENC_W1], 0.f, c.st));
     }
-    const bool tn_img = c.e.g3 && g3_tn_enabled(d);
     for (int which = 0; which < 2; ++which) {  // belief cell, action cell: W_ih, then W_hh with the bias
         const int n = which ? d.n_a : d.n_b;
         const int p_ih = which ? MARL_P_LA_WIH : MARL_P_LB_WIH, p_hh = which ? MARL_P_LA_WHH : MARL_P_LB_WHH;
         float* bias = grads[which ? MARL_P_LA_BIH : MARL_P_LB_BIH];
-        if (tn_img) {
+        if (c.plan.g3_tn) {
             // contraction over the rows of the images written by the cell-backward kernels (gate gradients),
             // the forward kernels (U) and the LSTM epilogues (h, h^); bias gradients = column sums of A
             const char* g3 = c.img(which ? c.e.GA3 : c.e.GB3);
@@ -2112,7 +2211,7 @@ static int bwd_inputs(const BwdState& s, const void* img, int img_u8, float* d_i
     hipStream_t st = c.st;
     const int64_t NR = d.NR;
     // with the [nf, nin) columns already produced step by step (panels), only the CNN features remain
-    if (c.e.g3 && s.panels) {
+    if (c.e.g3 && c.plan.panels_bwd) {
         G3Batch g{};
         g.p[0] = g3_prob(c.img(c.e.GB3), 0, c.wt3k(MARL_P_LB_WIH), 0, 4 * d.n_b, c.at(c.e.DU), d.ld_nin, (int)NR,
                          d.nf);
@@ -2121,11 +2220,11 @@ static int bwd_inputs(const BwdState& s, const void* img, int img_u8, float* d_i
         MARL_TRY(launch_gemm_nt3(g, st));
     } else {
         GemmProb p = gemm_prob(c.at(c.e.GB, 0), d.ld_gb, c.wtB(MARL_P_LB_WIH),
-                               c.at(c.e.DU), d.ld_nin, (int)NR, s.panels ? d.nf : d.nin);
+                               c.at(c.e.DU), d.ld_nin, (int)NR, c.plan.panels_bwd ? d.nf : d.nin);
         gemm_add_seg(p, c.at(c.e.GA, 0), d.ld_ga, c.wtB(MARL_P_LA_WIH));
         MARL_TRY(gemm1(c, p));
     }
-    if (s.panels)  // d(position embedding) = belief share + action share
+    if (c.plan.panels_bwd)  // d(position embedding) = belief share + action share
         MARL_TRY(launch_add2d(c.at(c.e.DDBAR) + d.n_mo, d.ld_dbl, c.at(c.e.DDBAR2) + d.n_mo, d.ld_dbl,
                               c.at(c.e.DU) + d.nf + d.n_mo, d.ld_nin, NR, d.n_d, st));
     MARL_TRY(ln_bwd(c, c.at(c.e.DU) + d.nf + d.n_mo, d.ld_nin, c.at(c.e.ZPOS, 0), d.ld_nd,
@@ -2308,58 +2407,16 @@ static int episode_forward_all(const marl_config* cfg, const void* weights_ws, s
     StepIn in;
     in.img = img;
     in.img_u8 = cfg->img_u8 != 0;
-    bool decoded_ahead = false;  // decoder(t) already ran with the sampling of step t-1
-    const bool chain = use_chain(d);
+    const SampleIo io{noise, forced_actions, rng_seed, rng_offset, counters, step_pos, step_actions, step_logp, true};
     for (int t = 0; t < d.ns; ++t) {
-        MARL_TRY(step_cnn(c, t, in));
-        if (!decoded_ahead) MARL_TRY(step_decode(c, t));
-        MARL_TRY(step_pos_lstm(c, t, in, t > 0));  // lambda_t (t > 0) came from sample(t-1)
         SampleArgs a;
-        fill_sample_args(c, cfg, t, a);
-        a.noise = noise ? noise + (size_t)t * d.R * d.nA : nullptr;
-        a.rng_on = !noise && !forced_actions;  // perf mode: Exp(1) drawn inside the kernel
-        a.rng_seed = rng_seed ^ 0x9E3779B97F4A7C15ull;  // a key of its own (marl_draw_episode uses rng_seed)
-        a.rng_ctr = (rng_offset << 16) + (uint64_t)t;
-        a.rng_off_dev = counters ? &static_cast<const Counters*>(counters)->rng_offset : nullptr;
-        a.forced = forced_actions ? forced_actions + (size_t)t * d.R : nullptr;
-        a.step_pos = step_pos ? step_pos + (size_t)t * d.R * 2 : nullptr;
-        a.step_actions = step_actions ? step_actions + (size_t)t * d.R : nullptr;
-        a.step_logp = step_logp + (size_t)t * d.R;
-        explore_sample_args(a);
-        if (t + 1 < d.ns) {  // position embedding of step t+1 rides along with the move
-            a.pe_W = c.wp(MARL_P_POS_W);
-            a.pe_b = c.wp(MARL_P_POS_B);
-            a.pe_gamma = c.wp(MARL_P_POS_LNW);
-            a.pe_beta = c.wp(MARL_P_POS_LNB);
-            a.pe_npos = c.at(c.e.NPOS, t + 1);
-            a.pe_z = c.at(c.e.ZPOS, t + 1);
-            a.pe_stats = c.at(c.e.STPOS, t + 1);
-            a.pe_out = c.at(c.e.U, t + 1) + d.nf + d.n_mo;
-            a.pe_ldz = d.ld_nd;
-            a.pe_ldo = d.ld_nin;
-            a.pe_nd = d.n_d;
-            if (c.u3_by_producers) {
-                a.pe_img = c.img(c.e.U3);
-                a.pe_row0 = c.u3_row(t + 1);
-                a.pe_steps = img_steps(d.nin);
-                a.pe_col0 = d.nf + d.n_mo;
-            }
-        }
-        if (chain) {
-            MARL_TRY(step_chain(c, t, &a));  // encoder(t) -> decoder(t+1) || policy layer(t) [-> sample(t)]
-        } else {
-            MARL_TRY(step_encode_policy(c, t));
-        }
-        // sample(t) and decoder(t+1) are independent (the decoder needs MSG[t+1], written by the
-        // encoder above): one launch runs both.  Under the chain launch decoder(t+1) is already inside it, and so
-        // is sample(t) when its policy workgroups ran it as their epilogue
-        decoded_ahead = chain && t + 1 < d.ns;
-        // (under exploration controls only the chain launch's epilogue samples in-launch: the ride-along workgroups
-        // of the plain decoder launch have no EXPLORE form - sample_kernel's runs behind it)
-        bool rode = false;
-        if (!chain && t + 1 < d.ns) MARL_TRY(step_decode(c, t + 1, g_explore.on ? nullptr : &a, &rode));
-        if (chain ? !use_panel_sample(d) : !rode) MARL_TRY(launch_sample(a, c.st, g_explore.on));
-        if (!chain) decoded_ahead = t + 1 < d.ns && use_panels(d);
+        fill_sample_args(c, cfg, t, io, a);
+        if (c.plan.chain)
+            MARL_TRY(fwd_step_chain(c, t, in, a));
+        else if (c.plan.panels)
+            MARL_TRY(fwd_step_panels(c, t, in, a));
+        else
+            MARL_TRY(fwd_step_rows(c, t, in, a));
     }
     MARL_TRY(heads_batched(c, 0, d.NR, step_values, step_preds));
     if (step_probs) MARL_TRY(launch_copy2d(c.PROBSs(0), d.nA, step_probs, d.nA, d.NR, d.nA, c.st));
@@ -2451,14 +2508,14 @@ int marl_episode_backward_probs(const marl_config* cfg, void* weights_ws, size_t
 }
 
 int marl_backward_heads_event(void* hip_event) {
-    g_heads_event = static_cast<hipEvent_t>(hip_event);
+    g_installed.heads_event = static_cast<hipEvent_t>(hip_event);
     return MARL_OK;
 }
 
 int marl_comm_matrix(const float* m_dev, int nb_agents) {
     if (!m_dev) {
-        g_comm = nullptr;
-        g_comm_na = 0;
+        g_installed.comm = nullptr;
+        g_installed.comm_na = 0;
         return MARL_OK;
     }
     if (nb_agents < 1) {
@@ -2469,21 +2526,21 @@ int marl_comm_matrix(const float* m_dev, int nb_agents) {
         set_error("comm_matrix: %d agents, the mixing kernel serves at most %d", nb_agents, mix_msg_max_agents());
         return MARL_ELIMIT;
     }
-    g_comm = m_dev;
-    g_comm_na = nb_agents;
+    g_installed.comm = m_dev;
+    g_installed.comm_na = nb_agents;
     return MARL_OK;
 }
 
 int marl_comm_range(int radius, int metric, int normalize) {
     if (radius < 0) {
-        g_range = CommGate{nullptr, -1, 0, 1};
+        g_installed.range = CommGate{nullptr, -1, 0, 1};
         return MARL_OK;
     }
     if (metric != MARL_COMM_CHEBYSHEV && metric != MARL_COMM_EUCLIDEAN) {
         set_error("comm_range: unknown metric %d", metric);
         return MARL_EINVAL;
     }
-    g_range = CommGate{nullptr, radius, metric, normalize != 0};
+    g_installed.range = CommGate{nullptr, radius, metric, normalize != 0};
     return MARL_OK;
 }
 
@@ -2497,7 +2554,7 @@ int marl_policy_explore(float temperature, float eps, int greedy) {
         return MARL_EINVAL;
     }
     const bool on = temperature != 1.f || eps != 0.f || greedy != 0;
-    g_explore = Explore{on, 1.0f / temperature, 1.0f - eps, eps, greedy != 0};
+    g_installed.explore = Explore{on, 1.0f / temperature, 1.0f - eps, eps, greedy != 0};
     return MARL_OK;
 }
 
@@ -2513,8 +2570,8 @@ int marl_class_loss(const float* class_weights_dev, int nb_class, float label_sm
         return MARL_EINVAL;
     }
     const bool on = class_weights_dev || step_weights_dev || label_smoothing != 0.f || weight_rewards != 0;
-    g_class_loss = ClassLoss{on, class_weights_dev, nb_class, label_smoothing, step_weights_dev, nb_steps,
-                             weight_rewards != 0};
+    g_installed.class_loss = ClassLoss{on, class_weights_dev, nb_class, label_smoothing, step_weights_dev, nb_steps,
+                                       weight_rewards != 0};
     return MARL_OK;
 }
 
@@ -2530,11 +2587,12 @@ int marl_comm_grad(const marl_config* cfg, const void* weights_ws, size_t weight
         set_error("comm_grad: null argument");
         return MARL_EINVAL;
     }
-    if (!g_comm) {
+    const Installed opt = g_installed;
+    if (!opt.comm) {
         set_error("comm_grad: no communication matrix installed (marl_comm_matrix)");
         return MARL_EINVAL;
     }
-    if (g_range.radius >= 0) {
+    if (opt.range.radius >= 0) {
         set_error("comm_grad: a communication range is installed - the gradient of a gated base matrix is not "
                   "computed");
         return MARL_EINVAL;
@@ -2547,8 +2605,9 @@ int marl_comm_grad(const marl_config* cfg, const void* weights_ws, size_t weight
     lay.nb_steps = nb_steps;
     Dims d;
     MARL_TRY(make_dims(&lay, d));
-    if (g_comm_na != d.na) {
-        set_error("communication matrix is %d x %d but the configuration has %d agents", g_comm_na, g_comm_na, d.na);
+    if (opt.comm_na != d.na) {
+        set_error("communication matrix is %d x %d but the configuration has %d agents", opt.comm_na, opt.comm_na,
+                  d.na);
         return MARL_EINVAL;
     }
     WLayout w;
@@ -2665,7 +2724,7 @@ static int loss_entry(const marl_config* cfg, void* episode_ws, size_t episode_w
                   e.total * sizeof(float));
         return MARL_ESIZE;
     }
-    const ClassLoss& k = g_class_loss;
+    const ClassLoss k = g_installed.class_loss;
     if (k.on && ((k.nc != 0 && k.nc != d.nC) || (k.ns != 0 && k.ns != d.ns))) {
         set_error("%s: the installed class-loss options are for %d classes / %d steps, the configuration has %d / %d",
                   who, k.nc, k.ns, d.nC, d.ns);
@@ -2819,7 +2878,7 @@ static int step_forward(const marl_config* cfg, const void* weights_ws, size_t w
                         float* values, float* preds, float* new_msg, float* h_out, float* c_out, float* hc_out,
                         float* cc_out, const float* noise, uint64_t rng_seed, uint64_t rng_offset,
                         int64_t* actions_out, float* logp_out, int train, void* stream) {
-    if (g_range.radius >= 0) {  // (before anything is enqueued)
+    if (g_installed.range.radius >= 0) {  // (before anything is enqueued)
         set_error("step_forward: a communication range is installed - a single step has no integer positions of "
                   "the emission step; run the fused episode");
         return MARL_EINVAL;
@@ -2837,21 +2896,13 @@ static int step_forward(const marl_config* cfg, const void* weights_ws, size_t w
     in.obs = obs;
     in.npos = norm_pos;
     MARL_TRY(step_core(c, 0, in));
+    SampleIo io;  // (left empty: probabilities only - the behaviour policy's under exploration controls)
+    if (actions_out && logp_out)  // also sample (positions of the scratch slot are unused)
+        io = SampleIo{noise, nullptr, rng_seed, rng_offset, nullptr, nullptr, actions_out, logp_out, false};
     SampleArgs a;
-    fill_sample_args(c, cfg, 0, a);
+    fill_sample_args(c, cfg, 0, io, a);
     a.probs = probs;
-    if (actions_out && logp_out) {  // also sample (positions of the scratch slot are unused)
-        a.noise = noise;
-        a.rng_on = !noise;
-        a.rng_seed = rng_seed ^ 0x9E3779B97F4A7C15ull;
-        a.rng_ctr = rng_offset << 16;
-        a.step_actions = actions_out;
-        a.step_logp = logp_out;
-    } else {
-        a.step_logp = nullptr;  // probabilities only
-    }
-    explore_sample_args(a);  // (probabilities only: the behaviour policy's)
-    MARL_TRY(launch_sample(a, c.st, g_explore.on));
+    MARL_TRY(launch_sample(a, c.st, c.opt.explore.on));
     MARL_TRY(heads_batched(c, 0, d.R, values, preds));
     MARL_TRY(launch_copy2d(c.MSGs(1), d.ld_nm, new_msg, d.n_m, d.R, d.n_m, c.st));
     MARL_TRY(launch_copy2d(c.Hs(1), d.ld_nb, h_out, d.n_b, d.R, d.n_b, c.st));
@@ -2903,7 +2954,7 @@ int marl_step_backward(const marl_config* cfg, void* weights_ws, size_t weights_
         set_error("step_backward: null configuration");
         return MARL_EINVAL;
     }
-    if (g_range.radius >= 0) {  // (before anything is enqueued)
+    if (g_installed.range.radius >= 0) {  // (before anything is enqueued)
         set_error("step_backward: a communication range is installed - a single step has no integer positions of "
                   "the emission step; run the fused episode");
         return MARL_EINVAL;
@@ -2994,46 +3045,31 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
 int marl_plan_query(const marl_config* cfg, int train, const char* key, int* value) {
     Dims d;
     MARL_TRY(make_dims(cfg, d));
-    (void)train;
     if (!key || !value) return MARL_EINVAL;
-    if (!strcmp(key, "g3")) *value = g3_enabled(d);
+    // the plan as make_ctx builds it (a witness answers from the routine that decides)
+    WLayout w;
+    make_wlayout(d, w);
+    ELayout e;
+    make_elayout(d, train, e);
+    const Plan plan = make_plan(d, w, e, g_installed);
+    if (!strcmp(key, "g3")) *value = e.g3;
     else if (!strcmp(key, "g3_model")) *value = g3_model_ok(d);
-    else if (!strcmp(key, "g3_lstm")) *value = g3_enabled(d) && tune_get("g3_lstm", 1) != 0;
-    else if (!strcmp(key, "g3_tn")) *value = g3_enabled(d) && g3_tn_enabled(d);
-    else if (!strcmp(key, "lstm_plan") || !strcmp(key, "small_r")) {
-        // the tile plan the fused two-cell LSTM launch takes (gemm3.hip: 2 = 128-row tiles, 3 / 4 = the 32- / 64-row
-        // gate-split plans, 1 / 5 / 6 by knob) - asked of the launcher's own rule with the shapes of the launch (ADVICE
-        // r5: this used to re-derive the threshold by hand); "small_r" = one of the gate-split plans
-        int plan = 0;
-        if (g3_enabled(d) && tune_get("g3_lstm", 1) != 0) {
-            G3Batch b{};
-            b.count = 2;
-            b.p[0].m = b.p[1].m = (int)d.R;
-            b.p[0].n = d.n_b;
-            b.p[1].n = d.n_a;
-            plan = tune_get("g3_lstm_variant", 0);
-            if (!plan) plan = g3_lstm_plan(b);
-        }
-        *value = !strcmp(key, "small_r") ? (plan == 3 || plan == 4) : plan;
-    }
+    else if (!strcmp(key, "g3_lstm")) *value = plan.g3_lstm;
+    else if (!strcmp(key, "g3_tn")) *value = plan.g3_tn;
+    else if (!strcmp(key, "lstm_plan")) *value = plan.lstm_plan;
+    else if (!strcmp(key, "small_r")) *value = plan.lstm_plan == 3 || plan.lstm_plan == 4;  // one of the gate-split plans
     else if (!strcmp(key, "g3_tn_cell"))  // both weight gradients of a cell from one launch (gemm_tn3_cell_kernel)
-        *value = g3_enabled(d) && g3_tn_enabled(d) && g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) &&
-                 g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR);
-    else if (!strcmp(key, "g3_tn_pipe"))  // phase-pipelined row contractions: only where the image weight gradients run
-        *value = g3_enabled(d) && g3_tn_enabled(d) && tune_get("g3_tn_pipe", 1) != 0;
+        *value = plan.g3_tn && g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) && g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR);
+    else if (!strcmp(key, "g3_tn_pipe")) *value = plan.g3_tn_pipe;  // only where the image weight gradients run
     else if (!strcmp(key, "wgrad3")) {  // a conv weight gradient of this model runs on the bf16 pipe (cin >= 16)
-        ELayout e;
-        make_elayout(d, 1, e);
+        ELayout e1;
+        make_elayout(d, 1, e1);
         *value = 0;
         for (int l = 0; l < d.L; ++l)
-            if (e.wgrad_ok[l] && cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l)).form == 3) *value = 1;
+            if (e1.wgrad_ok[l] && cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l)).form == 3) *value = 1;
     }
     // what the CNN launchers do with this shape (their own routines, host arithmetic only; see marl_hip.h)
     else if (!strncmp(key, "cnn_fwd", 7)) {
-        ELayout e;
-        make_elayout(d, train, e);
-        WLayout w;
-        make_wlayout(d, w);
         CnnFwdPlan p{};  // unfused path: all 0
         if (e.fused_fwd) {
             // the shapes of step_cnn's launch: which optional buffers exist decides the instantiation
@@ -3067,33 +3103,24 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
             set_error("unknown plan key %s (layers %d..%d)", key, dg ? 1 : 0, d.L - 1);
             return MARL_EINVAL;
         }
-        ELayout e;
-        make_elayout(d, 1, e);
+        ELayout e1;
+        make_elayout(d, 1, e1);
         if (dg)
-            *value = e.dgrad_ok[l] ? cnn_dgrad_launch_rb(cnn_dgrad_shape(d, l)) : 0;
+            *value = e1.dgrad_ok[l] ? cnn_dgrad_launch_rb(cnn_dgrad_shape(d, l)) : 0;
         else {
             CnnWgradPlanInfo p{};
-            if (e.wgrad_ok[l]) p = cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l));
+            if (e1.wgrad_ok[l]) p = cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l));
             *value = field == 1 ? p.rb : field == 2 ? p.chunks : p.blocks;
         }
     }
-    // message exchange: "comm" = a mixing matrix is set; "comm_form" = how the aggregation is launched now
-    // (0 = mean inside the chained panel launch, 1 = mean while a panel stages, 2 = agg_msg_kernel, 3 = mix_msg_kernel
-    // ahead of a plain panel launch, 4 = mix_msg_kernel ahead of the GEMM path, 5 = mixed inside the chained panel
-    // launch - the decoder of step 0 and the step API then take form 3); "panel_chain" = the chained launch
-    else if (!strcmp(key, "comm")) *value = g_comm != nullptr;
-    else if (!strcmp(key, "comm_range")) *value = g_range.radius >= 0 ? g_range.radius : -1;  // the radius, or -1
-    else if (!strcmp(key, "panel_chain")) *value = use_chain(d);
-    // the forward loop samples inside the chained launch (the policy workgroups' epilogue): no sample_kernel launch
-    else if (!strcmp(key, "panel_sample")) *value = use_chain(d) && use_panel_sample(d);
-    // exploration controls (marl_policy_explore): "explore" = installed; "explore_form" = where the forward loop
-    // samples under them (0 = off, 1 = the EXPLORE epilogue of the chained launch, 2 = sample_kernel's EXPLORE form)
-    else if (!strcmp(key, "explore")) *value = g_explore.on;
-    else if (!strcmp(key, "class_loss")) *value = g_class_loss.on;  // (marl_class_loss: a setting is installed)
-    else if (!strcmp(key, "explore_form"))
-        *value = !g_explore.on ? 0 : (use_chain(d) && use_panel_sample(d)) ? 1 : 2;
-    else if (!strcmp(key, "comm_form"))
-        *value = g_comm ? (use_chain(d) ? 5 : use_panels(d) ? 3 : 4) : use_chain(d) ? 0 : use_panels(d) ? 1 : 2;
+    else if (!strcmp(key, "comm")) *value = plan.comm;
+    else if (!strcmp(key, "comm_range")) *value = plan.comm_range;
+    else if (!strcmp(key, "panel_chain")) *value = plan.chain;
+    else if (!strcmp(key, "panel_sample")) *value = plan.panel_sample;
+    else if (!strcmp(key, "explore")) *value = plan.explore;
+    else if (!strcmp(key, "class_loss")) *value = plan.class_loss;
+    else if (!strcmp(key, "explore_form")) *value = plan.explore_form;
+    else if (!strcmp(key, "comm_form")) *value = plan.comm_form;
     else {
         set_error("unknown plan key %s", key);
         return MARL_EINVAL;

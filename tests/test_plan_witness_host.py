@@ -75,6 +75,113 @@ def test_plan_coverage_cases_reach_their_plans(tag):
     assert [w0[k] for k in ("cnn_fwd", "cnn_fwd_rb", "cnn_fwd_blocks")] == [w[k] for k in ("cnn_fwd", "cnn_fwd_rb", "cnn_fwd_blocks")]
 
 
+# ---- the plan under the installed settings: marl_plan_query reports the Plan object the drivers run ----
+_FAKE = 1 << 12  # a "device pointer": the setters only store it, marl_plan_query never follows it
+SETTINGS = ("none", "ring", "ring+range", "explore", "greedy", "class_loss")
+SETTING_KEYS = ("comm", "comm_range", "comm_form", "explore", "explore_form", "class_loss")
+
+
+def _clear(lib):
+    assert lib.marl_comm_range(-1, 0, 1) == 0 and lib.marl_comm_matrix(None, 0) == 0
+    assert lib.marl_policy_explore(1.0, 0.0, 0) == 0 and lib.marl_class_loss(None, 0, 0.0, None, 0, 0) == 0
+
+
+def _install(lib, setting, na, nc):
+    if setting in ("ring", "ring+range"):
+        assert lib.marl_comm_matrix(_FAKE, na) == 0
+    if setting == "ring+range":
+        assert lib.marl_comm_range(8, 0, 1) == 0  # Chebyshev, normalised
+    if setting == "explore":
+        assert lib.marl_policy_explore(2.0, 0.1, 0) == 0
+    if setting == "greedy":
+        assert lib.marl_policy_explore(1.0, 0.0, 1) == 0
+    if setting == "class_loss":
+        assert lib.marl_class_loss(_FAKE, nc, 0.1, None, 0, 1) == 0
+
+
+def full_witness(cfg, na, nb, ns, shape):
+    """every key of plan_witness plus the settings' own keys and marl_workspace_sizes, for train = 0 and 1"""
+    lib = _lib()
+    mc = model_spec(cfg).config(na, nb, ns, *shape)
+    out = {}
+    for train in (0, 1):
+        w = plan_witness(cfg, na, nb, ns, shape, train=bool(train))
+        for k in SETTING_KEYS:
+            v = C.c_int(-7)
+            assert lib.marl_plan_query(C.byref(mc), train, k.encode(), C.byref(v)) == 0, k
+            w[k] = v.value
+        wb, eb = C.c_size_t(0), C.c_size_t(0)
+        assert lib.marl_workspace_sizes(C.byref(mc), train, C.byref(wb), C.byref(eb)) == 0
+        w["weights_bytes"], w["episode_bytes"] = wb.value, eb.value
+        out[train] = w
+    return out
+
+
+def _shapes():
+    out = {tag: _golden_shape(tag) for tag in CASES}
+    for tag, (cfg, na, nd, rep, ns, shape) in PLAN_CASES.items():
+        out[tag] = (cfg, na, nd * rep, ns, shape)
+    return out
+
+
+PLAN_RELATIONS = ["panel_sample <= panel_chain", "(comm_form in (0, 1, 2)) == (comm == 0)",
+                  "(comm_form == 5) == (comm == 1 and panel_chain == 1)", "(explore_form == 0) == (explore == 0)",
+                  "(explore_form == 1) == (explore == 1 and panel_sample == 1)", "small_r == (lstm_plan in (3, 4))",
+                  "(lstm_plan == 0) == (g3_lstm == 0)"]
+
+
+def _is_layout_key(k):
+    return k.startswith(("g3", "cnn_")) or k in ("wgrad3", "weights_bytes", "episode_bytes")
+
+
+@pytest.mark.parametrize("tag", list(CASES) + list(PLAN_CASES))
+def test_the_plan_under_every_installed_setting(tag):
+    """(a) the relations the plan encodes hold under every setting; (b) no setting moves a layout: both workspace
+    sizes and every g3* / cnn_* / wgrad3 key are those of the uninstalled library; (c) clearing a setting restores
+    every key."""
+    lib = _lib()
+    cfg, na, nb, ns, shape = _shapes()[tag]
+    _clear(lib)
+    base = full_witness(cfg, na, nb, ns, shape)
+    try:
+        for setting in SETTINGS:
+            _install(lib, setting, na, cfg.nb_class)
+            got = full_witness(cfg, na, nb, ns, shape)
+            _clear(lib)
+            for train in (0, 1):
+                w = got[train]
+                assert_witness(w, PLAN_RELATIONS + PLAN_INVARIANTS)
+                moved = {k: (base[train][k], w[k]) for k in w if _is_layout_key(k) and w[k] != base[train][k]}
+                assert not moved, (setting, train, moved)
+                assert w["comm"] == (setting in ("ring", "ring+range")), (setting, w)
+                assert w["comm_range"] == (8 if setting == "ring+range" else -1), (setting, w)
+                assert w["explore"] == (setting in ("explore", "greedy")) and w["class_loss"] == (setting == "class_loss")
+            assert full_witness(cfg, na, nb, ns, shape) == base, setting
+    finally:
+        _clear(lib)
+
+
+def test_a_matrix_takes_a_wide_belief_cell_off_the_chain():
+    """belief width above 384 with every message width at or below it: chained without a matrix, and under one the
+    unchained panel launches behind mix_msg_kernel (the chained kernels keep the matrix in the LDS the wide input
+    panel would need) - the one place where an installed setting changes the kernel family"""
+    from oracle import marl_oracle as mo
+
+    lib = _lib()
+    cfg = mo.OracleConfig("mnist", 6, 388, 64, 16, 24, 8, 10, 96, 96)
+    _clear(lib)
+    try:
+        w = full_witness(cfg, 3, 4, 3, (1, 28, 28))[1]
+        assert (w["panel_chain"], w["comm_form"], w["panel_sample"]) == (1, 0, 1)
+        _install(lib, "ring", 3, cfg.nb_class)
+        w = full_witness(cfg, 3, 4, 3, (1, 28, 28))[1]
+        assert (w["panel_chain"], w["comm_form"], w["panel_sample"]) == (0, 3, 0)
+        narrow = mo.OracleConfig("mnist", 6, 384, 64, 16, 24, 8, 10, 96, 96)
+        assert full_witness(narrow, 3, 4, 3, (1, 28, 28))[1]["comm_form"] == 5
+    finally:
+        _clear(lib)
+
+
 def test_witness_keys_are_parsed_strictly():
     lib = _lib()
     mc = model_spec(CASES["g4_resisc_b2"]).config(16, 4, 2, 3, 64, 64)  # three conv layers
