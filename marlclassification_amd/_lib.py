@@ -94,7 +94,77 @@ AUGMENT_ENTRIES = ("marl_batch_augment", "marl_batch_augment_plan")
 CLASSLOSS_ENTRIES = ("marl_class_loss",)
 # ... and the flat optimiser step that include/marl_hip_optim.h declares (likewise; optim.py holds its structures)
 OPTIM_ENTRIES = ("marl_optim_step",)
-_HOOKS = ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES
+# ... and the kernel-level hooks of the row-panel kernels that include/marl_hip_panelops.h declares (tests only)
+PANELOP_HOOKS = ("marl_panel_fwd", "marl_panel_bwd", "marl_panel_scratch_bytes", "marl_panel_plan")
+_HOOKS = (ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES +
+          PANELOP_HOOKS)
+MARL_PANEL_MAX_LAYERS = 4
+
+
+class PanelLayer(C.Structure):
+    """Mirror of ``marl_panel_layer`` (include/marl_hip_panelops.h)."""
+
+    _fields_ = [("w", C.c_void_p), ("ldw", C.c_int), ("bias", C.c_void_p), ("gamma", C.c_void_p),
+                ("beta", C.c_void_p), ("n", C.c_int), ("z", C.c_void_p), ("ldz", C.c_int), ("stats", C.c_void_p),
+                ("a", C.c_void_p), ("lda", C.c_int), ("a3", C.c_void_p), ("a3_row0", C.c_int), ("a3_steps", C.c_int),
+                ("a3_col0", C.c_int)]
+
+
+class PanelFwdProb(C.Structure):
+    """Mirror of ``marl_panel_fwd_prob``."""
+
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int), ("k0", C.c_int), ("m", C.c_int), ("nlayers", C.c_int),
+                ("layer", PanelLayer * MARL_PANEL_MAX_LAYERS), ("agg_na", C.c_int), ("agg_nb", C.c_int),
+                ("xbar", C.c_void_p), ("by_batch", C.c_int), ("g_na", C.c_int), ("g_nb", C.c_int),
+                ("agg_at", C.c_int), ("ld_xbar", C.c_int), ("mix", C.c_void_p), ("sample", C.c_int),
+                ("explore", C.c_int), ("gate_pos", C.c_void_p)]
+
+
+class PanelCell(C.Structure):
+    """Mirror of ``marl_panel_cell``."""
+
+    _fields_ = [("dh", C.c_void_p), ("dc", C.c_void_p), ("gates", C.c_void_p), ("c_prev", C.c_void_p),
+                ("c_new", C.c_void_p), ("lddh", C.c_int), ("lddc", C.c_int), ("ldg", C.c_int), ("ldc", C.c_int),
+                ("n", C.c_int), ("g3", C.c_void_p), ("g3_row0", C.c_int), ("g3_steps", C.c_int),
+                ("skip_f32", C.c_int)]
+
+
+class PanelBwdLayer(C.Structure):
+    """Mirror of ``marl_panel_bwd_layer``."""
+
+    _fields_ = [("z", C.c_void_p), ("ldz", C.c_int), ("stats", C.c_void_p), ("gamma", C.c_void_p),
+                ("beta", C.c_void_p), ("n", C.c_int), ("k_in", C.c_int), ("w", C.c_void_p), ("ldw", C.c_int),
+                ("dz", C.c_void_p), ("lddz", C.c_int), ("part", C.c_void_p)]
+
+
+class PanelBwdProb(C.Structure):
+    """Mirror of ``marl_panel_bwd_prob``."""
+
+    _fields_ = [("da", C.c_void_p), ("ldda", C.c_int), ("da2", C.c_void_p), ("ldda2", C.c_int),
+                ("agg_na", C.c_int), ("agg_nb", C.c_int), ("m", C.c_int), ("nlayers", C.c_int),
+                ("layer", PanelBwdLayer * MARL_PANEL_MAX_LAYERS), ("dx", C.c_void_p), ("lddx", C.c_int),
+                ("accumulate", C.c_int), ("by_batch", C.c_int), ("g_na", C.c_int), ("g_nb", C.c_int),
+                ("agg_at", C.c_int), ("mix", C.c_void_p), ("has_cellb", C.c_int), ("cellb", PanelCell),
+                ("has_cell", C.c_int), ("cell", PanelCell), ("cell_rows", C.c_int64), ("gate_pos", C.c_void_p),
+                ("cellb_img_done", C.c_int), ("cell_img_done", C.c_int)]
+
+
+class PanelPlan(C.Structure):
+    """Mirror of ``marl_panel_plan_info``."""
+
+    _PER_LAYER = ("layer_waves", "nt", "ks", "kper", "empty", "rounds", "ln_slots")
+    _fields_ = ([("waves", C.c_int), ("lds_bytes", C.c_int), ("blocks", C.c_int), ("cell_blocks", C.c_int),
+                 ("by_batch", C.c_int * 2), ("nlayers", C.c_int)] +
+                [(name, C.c_int * (2 * MARL_PANEL_MAX_LAYERS)) for name in _PER_LAYER] +
+                [(name, C.c_int) for name in ("maxc", "tail_lds", "retried", "cell_vec4", "cellb_img_done",
+                                              "cell_img_done")])
+
+    def as_dict(self) -> dict:
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            out[name] = list(v)[: self.nlayers] if name in self._PER_LAYER else (list(v) if name == "by_batch" else v)
+        return out
 
 
 class CnnBwdPlan(C.Structure):
@@ -229,6 +299,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_cnn_bwd_plan.argtypes = [_i64, _i, _i, _i, _i, _i, C.POINTER(CnnBwdPlan)]
     lib.marl_cnn_fwd.argtypes = [_cfgp, _vp, _sz, C.POINTER(CnnFwdIo), _vp]
     lib.marl_cnn_fwd_plan.argtypes = [_cfgp, _i, _i64, C.POINTER(CnnFwdPlan)]
+    lib.marl_panel_scratch_bytes.restype = _sz
+    lib.marl_panel_scratch_bytes.argtypes = [_i, _i, C.POINTER(_i), C.POINTER(_i)]
+    lib.marl_panel_fwd.argtypes = [C.POINTER(PanelFwdProb), _i, _vp, _sz, _vp]
+    lib.marl_panel_bwd.argtypes = [C.POINTER(PanelBwdProb), _vp, _sz, _vp]
+    lib.marl_panel_plan.argtypes = [C.POINTER(PanelFwdProb), _i, C.POINTER(PanelBwdProb), C.POINTER(PanelPlan)]
     for name in EXPORTS + list(_HOOKS):
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("marl_abi_version", "marl_tune_get"):

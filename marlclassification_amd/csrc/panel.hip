@@ -549,7 +549,18 @@ int panel_supported(int k0, int n0, int n1) {
     return lds <= kPanelMaxLds;
 }
 
-int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
+// slice length of a K split (what both kernels compute from panel_ksplit's ks); slice s is empty when s * kper >= K16
+static int panel_kper_host(int K16, int ks) { return (((K16 + ks - 1) / ks) + 15) & ~15; }
+
+// What launch_panel_fwd decides before it launches: the checks, the LDS layout (written into b), the wave count and the
+// grid.  Host arithmetic only: marl_panel_plan (marl_hip_panelops.h) reports it from this same routine.
+struct PanelFwdPlan {
+    int waves;
+    size_t lds;
+    unsigned pblocks;
+    bool mixed, gated;
+};
+static int panel_fwd_plan(PanelFwdBatch& b, PanelFwdPlan& pl) {
     int waves = 1, x0 = 0, x1 = 0;
     for (int i = 0; i < b.count; ++i) {
         const PanelFwdProb& p = b.p[i];
@@ -621,6 +632,28 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
         set_error("panel kernel: shape outside its range");
         return MARL_ELIMIT;
     }
+    b.ln_narrow_max = 128;  // widths that take the two-slot row pass
+    unsigned pblocks = 0;
+    for (int i = 0; i < b.count; ++i) {
+        const PanelFwdProb& p = b.p[i];
+        const unsigned nblk = p.by_batch > 0 ? (unsigned)cdiv(p.g_nb, p.by_batch) : (unsigned)cdiv(p.m, kPanelRows);
+        pblocks = nblk > pblocks ? nblk : pblocks;
+    }
+    pl.waves = waves;
+    pl.lds = lds;
+    pl.pblocks = pblocks;
+    pl.mixed = mixed;
+    pl.gated = gated;
+    return MARL_OK;
+}
+
+int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
+    PanelFwdPlan pl;
+    MARL_TRY(panel_fwd_plan(b, pl));
+    const int waves = pl.waves;
+    const size_t lds = pl.lds;
+    const unsigned pblocks = pl.pblocks;
+    const bool mixed = pl.mixed, gated = pl.gated;
     static bool raised = false;
     if (!raised) {
         const void* kerns[11] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
@@ -637,13 +670,6 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
-    }
-    b.ln_narrow_max = 128;  // widths that take the two-slot row pass
-    unsigned pblocks = 0;
-    for (int i = 0; i < b.count; ++i) {
-        const PanelFwdProb& p = b.p[i];
-        const unsigned nblk = p.by_batch > 0 ? (unsigned)cdiv(p.g_nb, p.by_batch) : (unsigned)cdiv(p.m, kPanelRows);
-        pblocks = nblk > pblocks ? nblk : pblocks;
     }
 #ifdef MARL_KERNEL_TS
     static long long* d_ts = nullptr;
@@ -662,6 +688,19 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
     if (explore && !b.epi_prob) {
         set_error("panel kernel: exploration controls are served by the sampling epilogue only");
         return MARL_EINVAL;
+    }
+    // A single agent has no other agents: the staged mean is zero (networks/message.py:5-17) and the kernel stages
+    // zeros without storing them.  xbar is an output all the same - the decoder's weight gradient reads it - so its
+    // rows (the float4-rounded columns the kernel would have stored) are zeroed here instead of being left as found.
+    for (int i = 0; i < b.count; ++i) {
+        const PanelFwdProb& p = b.p[i];
+        if (p.agg_na == 1 && p.xbar) {
+            PermBatch z{};
+            z.count = 1;
+            z.d[0].dst = p.xbar, z.d[0].rows = p.m, z.d[0].cols = (p.k0 + 3) & ~3, z.d[0].dst_ld = p.ldx;
+            z.d[0].rd = z.d[0].cd = 1;
+            MARL_TRY(launch_permute(z, st));
+        }
     }
     prof_before(4, st);
     if (b.epi_prob && explore) {  // the same three forms, sampling from the behaviour policy
@@ -1155,8 +1194,17 @@ int panel_bwd_blocks(int m) { return (int)cdiv(m, kPanelRows); }
 int panel_chain_blocks(int na, int nb) { return na >= 1 && na <= kPanelRows ? (int)cdiv(nb, kPanelRows / na) : 0; }
 int panel_chain_by_batch(int na) { return na >= 1 && na <= kPanelRows ? kPanelRows / na : 0; }
 
-int launch_panel_bwd(PanelBwdProb& p, hipStream_t st) {
+// What launch_panel_bwd decides before it launches (checks, LDS layout and the launcher-filled fields written into p);
+// host arithmetic only, shared with marl_panel_plan (marl_hip_panelops.h).
+struct PanelBwdPlan {
+    int waves, maxc;
+    size_t lds;
+    unsigned pblocks, cblocks;
+    bool retried;
+};
+static int panel_bwd_plan(PanelBwdProb& p, PanelBwdPlan& pl) {
     int waves = 8, pmax = 0, nmax = 0, prm = 0;
+    pl.retried = false;
     // the last layer's dX goes through LDS and is finished row-wise (16-byte accesses) when its
     // rows keep float4 alignment
     const PanelBwdLayer& Ll = p.layer[p.nlayers - 1];
@@ -1217,12 +1265,36 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
     // final dX then leaves without the LDS tail; with n_b <= 384 under a matrix (use_chain) no admitted plan gets here)
     if (lds > kPanelMaxLds && tail_lds) {
         tail_lds = false;
+        pl.retried = true;
         goto plan;
     }
     if (lds > kPanelMaxLds) {
         set_error("panel backward: shape outside its range");
         return MARL_ELIMIT;
     }
+    pl.pblocks = p.by_batch > 0 ? (unsigned)cdiv(p.g_nb, p.by_batch) : (unsigned)cdiv(p.m, kPanelRows);
+    p.cellb_img_done = p.has_cellb && p.cellb.g3 && tail_lds;
+    p.cell_vec4 = p.has_cell && lstm_bwd_vec4_ok(p.cell);
+    p.cell_img_done = p.has_cell && p.cell.g3 && p.cell_vec4;
+    if (!p.cellb_img_done) p.cellb.skip_f32 = 0;  // (the fallback builds the image from the fp32 gradients)
+    if (!p.cell_img_done) p.cell.skip_f32 = 0;
+    pl.waves = waves;
+    pl.lds = lds;
+    pl.maxc = nmax <= 128 ? 2 : kBwdMaxCols;
+    pl.cblocks = 0;
+    if (p.has_cell) {
+        p.panel_blocks = (int)pl.pblocks;
+        pl.cblocks = (unsigned)cdiv(p.cell_rows * (p.cell_vec4 ? p.cell.n / 4 : p.cell.n), 64 * waves);
+    }
+    return MARL_OK;
+}
+
+int launch_panel_bwd(PanelBwdProb& p, hipStream_t st) {
+    PanelBwdPlan pl;
+    MARL_TRY(panel_bwd_plan(p, pl));
+    const int waves = pl.waves, maxc = pl.maxc;
+    const size_t lds = pl.lds;
+    const unsigned pblocks = pl.pblocks;
     static bool raised = false;
     if (!raised) {
         const void* kerns[12] = {reinterpret_cast<const void*>(panel_bwd_kernel<false, 2>),
@@ -1241,27 +1313,16 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
     }
-    const unsigned pblocks = p.by_batch > 0 ? (unsigned)cdiv(p.g_nb, p.by_batch) : (unsigned)cdiv(p.m, kPanelRows);
     prof_before(4, st);
-    p.cellb_img_done = p.has_cellb && p.cellb.g3 && tail_lds;
-    p.cell_vec4 = p.has_cell && lstm_bwd_vec4_ok(p.cell);
-    p.cell_img_done = p.has_cell && p.cell.g3 && p.cell_vec4;
-    if (!p.cellb_img_done) p.cellb.skip_f32 = 0;  // (the fallback builds the image from the fp32 gradients)
-    if (!p.cell_img_done) p.cell.skip_f32 = 0;
 #ifdef MARL_KERNEL_TS
     static long long* d_ts = nullptr;
     static int calls = 0;
     const int rec = ts_begin(&d_ts, calls++);
     p.ts = rec ? d_ts : nullptr;
 #endif
-    const int maxc = nmax <= 128 ? 2 : kBwdMaxCols;
+    const unsigned cblocks = pl.cblocks;
     if (p.mix) {
         const dim3 blk(64 * waves);
-        unsigned cblocks = 0;
-        if (p.has_cell) {
-            p.panel_blocks = (int)pblocks;
-            cblocks = (unsigned)cdiv(p.cell_rows * (p.cell_vec4 ? p.cell.n / 4 : p.cell.n), 64 * waves);
-        }
         if (p.gate.pos) {
             if (p.has_cell && maxc == 2)
                 hipLaunchKernelGGL((panel_bwd_kernel<true, 2, true, true>), dim3(pblocks + cblocks), blk, lds, st, p);
@@ -1281,8 +1342,6 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
         else
             hipLaunchKernelGGL((panel_bwd_kernel<false, kBwdMaxCols, true>), dim3(pblocks), blk, lds, st, p);
     } else if (p.has_cell) {
-        p.panel_blocks = (int)pblocks;
-        const unsigned cblocks = (unsigned)cdiv(p.cell_rows * (p.cell_vec4 ? p.cell.n / 4 : p.cell.n), 64 * waves);
         if (maxc == 2)
             hipLaunchKernelGGL((panel_bwd_kernel<true, 2>), dim3(pblocks + cblocks), dim3(64 * waves), lds, st, p);
         else
@@ -1305,3 +1364,385 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
 }
 
 }  // namespace marl
+
+// ===========================================================================
+// kernel-level hooks of the panel launchers (include/marl_hip_panelops.h; not part of the versioned ABI): host code
+// only - plain-C descriptors in, PanelFwdBatch / PanelBwdProb to the launchers above as the episode would fill them
+// ===========================================================================
+#include "../../include/marl_hip_panelops.h"
+
+using namespace marl;
+
+namespace {
+
+constexpr int kApiMaxWidth = 64 * kPanelMaxCols;  // 384: the widest LayerNorm row either kernel holds
+static float g_here[4];                           // stands for a weight copy where only its presence matters (plans)
+
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int round4(int v) { return (v + 3) & ~3; }
+
+// a [rows][ld] fp32 matrix the kernels access 16 bytes at a time, cols rounded up to 4 per row
+bool vec_ok(const void* p, int ld, int cols) { return p && al16(p) && (ld & 3) == 0 && ld >= round4(cols); }
+
+LstmBwdArgs cell_args(const marl_panel_cell& c) {
+    LstmBwdArgs a{};
+    a.dh = c.dh, a.dc = c.dc, a.gates = c.gates, a.c_prev = c.c_prev, a.c_new = c.c_new;
+    a.lddh = c.lddh, a.lddc = c.lddc, a.ldg = c.ldg, a.ldc = c.ldc, a.n = c.n;
+    a.g3 = static_cast<char*>(c.g3), a.g3_row0 = c.g3_row0, a.g3_steps = c.g3_steps, a.skip_f32 = c.skip_f32;
+    return a;
+}
+
+// the fragment-order copies a call builds: zero fill of the scratch, (backward) row-major transposes, then the
+// frag form of launch_permute - the routine that builds the product's copies (episode.hip, pack)
+struct FragJobs {
+    PermBatch transposes, frags;
+    size_t floats;
+};
+
+// by_batch / g_na / g_nb / m of either direction
+int check_grouping(const char* who, int& by_batch, int g_na, int g_nb, int m, int agg_at, int nlayers,
+                   const float* mix) {
+    if (by_batch < 0) by_batch = panel_chain_by_batch(g_na);
+    if (by_batch > 0) {
+        if (g_na < 1 || g_nb < 1 || (int64_t)g_na * g_nb != m) {
+            set_error("%s: by_batch needs g_na, g_nb >= 1 and m == g_na * g_nb", who);
+            return MARL_EINVAL;
+        }
+        if (by_batch * g_na > kPanelRows) {
+            set_error("%s: by_batch * g_na = %d > %d panel rows", who, by_batch * g_na, kPanelRows);
+            return MARL_ELIMIT;
+        }
+    }
+    if (mix && agg_at <= 0) {
+        set_error("%s: a mixing matrix needs the in-panel aggregation (agg_at > 0)", who);
+        return MARL_ELIMIT;
+    }
+    if (agg_at < 0 || (agg_at > 0 && (by_batch < 1 || agg_at >= nlayers))) {
+        set_error("%s: agg_at needs by_batch > 0 and 0 < agg_at < nlayers", who);
+        return MARL_EINVAL;
+    }
+    return MARL_OK;
+}
+
+int build_fwd(const marl_panel_fwd_prob* probs, int count, float* scratch, size_t scratch_bytes, bool plan_only,
+              PanelFwdBatch& b, FragJobs& jobs) {
+    if (!probs || count < 1 || count > 2) {
+        set_error("marl_panel_fwd: one or two problems");
+        return MARL_EINVAL;
+    }
+    b = PanelFwdBatch{};
+    b.count = count;
+    jobs.transposes.count = jobs.frags.count = 0;
+    jobs.floats = 0;
+    for (int i = 0; i < count; ++i) {
+        const marl_panel_fwd_prob& q = probs[i];
+        PanelFwdProb& p = b.p[i];
+        if (q.sample || q.explore || q.gate_pos) {
+            set_error("marl_panel_fwd: the sampling epilogue, exploration controls and the position gate are not served here");
+            return MARL_EINVAL;
+        }
+        if (q.nlayers < 1 || q.nlayers > kPanelMaxLayers || q.m < 1 || q.k0 < 1) {
+            set_error("marl_panel_fwd: 1..%d layers, m >= 1, k0 >= 1", kPanelMaxLayers);
+            return MARL_EINVAL;
+        }
+        if (!vec_ok(q.x, q.ldx, q.k0)) {
+            set_error("marl_panel_fwd: x must be 16-byte aligned with ldx %% 4 == 0 and ldx >= round4(k0)");
+            return MARL_EINVAL;
+        }
+        int by_batch = q.by_batch;
+        MARL_TRY(check_grouping("marl_panel_fwd", by_batch, q.g_na, q.g_nb, q.m, q.agg_at, q.nlayers, q.mix));
+        if (q.agg_na < 0 || (q.agg_na > 0 && (q.agg_nb < 1 || (int64_t)q.agg_na * q.agg_nb != q.m))) {
+            set_error("marl_panel_fwd: the staged mean needs m == agg_na * agg_nb");
+            return MARL_EINVAL;
+        }
+        if (q.xbar && q.agg_na > 0 && !al16(q.xbar)) {
+            set_error("marl_panel_fwd: xbar must be 16-byte aligned");
+            return MARL_EINVAL;
+        }
+        p.x = q.x, p.ldx = q.ldx, p.k0 = q.k0, p.agg_na = q.agg_na, p.agg_nb = q.agg_nb, p.xbar = q.xbar;
+        p.m = q.m, p.nlayers = q.nlayers;
+        p.by_batch = by_batch, p.g_na = q.g_na, p.g_nb = q.g_nb, p.agg_at = q.agg_at, p.ld_xbar = q.ld_xbar;
+        p.mix = q.mix;
+        int kin = q.k0;
+        for (int l = 0; l < q.nlayers; ++l) {
+            const marl_panel_layer& s = q.layer[l];
+            if (s.n < 1 || s.n > kApiMaxWidth || (l > 0 && kin > kApiMaxWidth)) {
+                set_error("marl_panel_fwd: layer %d width %d outside 1..%d", l, s.n, kApiMaxWidth);
+                return MARL_ELIMIT;
+            }
+            if (!s.w) {
+                set_error("marl_panel_fwd: layer %d has no weight (null fragment source)", l);
+                return MARL_EINVAL;
+            }
+            if (s.ldw < kin || !s.bias || !s.gamma || !s.beta || !s.a || s.lda < s.n || (s.z && s.ldz < s.n)) {
+                set_error("marl_panel_fwd: layer %d: null vector or output, or a leading dimension below its width", l);
+                return MARL_EINVAL;
+            }
+            if (s.a3 && ((s.n & 3) || (s.a3_col0 & 3) || s.a3_col0 < 0 || s.a3_row0 < 0 ||
+                         s.a3_col0 + s.n > 16 * s.a3_steps)) {
+                set_error("marl_panel_fwd: layer %d: an image needs n and a3_col0 multiples of 4 inside a3_steps", l);
+                return MARL_EINVAL;
+            }
+            if (l == q.agg_at && l > 0 && q.xbar && !vec_ok(q.xbar, q.ld_xbar, kin)) {
+                set_error("marl_panel_fwd: xbar must be 16-byte aligned with ld_xbar %% 4 == 0 and >= round4(width)");
+                return MARL_EINVAL;
+            }
+            PanelLayer& d = p.layer[l];
+            d.wgroups = panel_frag_groups(kin);
+            d.bias = s.bias, d.gamma = s.gamma, d.beta = s.beta, d.n = s.n;
+            d.z = s.z, d.ldz = s.ldz, d.stats = s.stats, d.a = s.a, d.lda = s.lda;
+            d.a3 = static_cast<char*>(s.a3), d.a3_row0 = s.a3_row0, d.a3_steps = s.a3_steps, d.a3_col0 = s.a3_col0;
+            const size_t fl = panel_frag_floats(s.n, kin);
+            if (plan_only) {
+                d.wfrag = g_here;
+            } else {
+                d.wfrag = scratch + jobs.floats;
+                PermDesc pd{};
+                pd.src = s.w, pd.dst = scratch + jobs.floats, pd.rows = s.n, pd.cols = kin;
+                pd.rd = 1, pd.rs1 = s.ldw, pd.cd = 1, pd.cs1 = 1, pd.frag = d.wgroups;
+                jobs.frags.d[jobs.frags.count++] = pd;
+            }
+            jobs.floats += fl;
+            kin = s.n;
+        }
+    }
+    if (!plan_only && (!scratch || !al16(scratch) || scratch_bytes < jobs.floats * sizeof(float))) {
+        set_error("marl_panel_fwd: scratch too small or misaligned (%zu bytes needed)", jobs.floats * sizeof(float));
+        return MARL_ESIZE;
+    }
+    return MARL_OK;
+}
+
+int check_cell(const char* which, const marl_panel_cell& c, bool needs_dh) {
+    if (c.n < 1 || !c.dc || !c.gates || !c.c_prev || !c.c_new || (needs_dh && (!c.dh || c.lddh < c.n)) ||
+        c.lddc < c.n || c.ldc < c.n || c.ldg < 4 * c.n) {
+        set_error("marl_panel_bwd: %s: null pointer or a leading dimension below its width", which);
+        return MARL_EINVAL;
+    }
+    // the four-wide forms (chosen by the launcher from n and the leading dimensions) access 16 bytes at a time
+    if (!al16(c.dc) || !al16(c.gates) || !al16(c.c_prev) || !al16(c.c_new) || (needs_dh && !al16(c.dh))) {
+        set_error("marl_panel_bwd: %s: pointers must be 16-byte aligned", which);
+        return MARL_EINVAL;
+    }
+    if (c.g3 && (c.g3_row0 < 0 || 4 * c.n > 16 * c.g3_steps)) {
+        set_error("marl_panel_bwd: %s: the image needs g3_steps >= 4 n / 16", which);
+        return MARL_EINVAL;
+    }
+    return MARL_OK;
+}
+
+int build_bwd(const marl_panel_bwd_prob* qp, float* scratch, size_t scratch_bytes, bool plan_only, PanelBwdProb& p,
+              FragJobs& jobs) {
+    if (!qp) {
+        set_error("marl_panel_bwd: null argument");
+        return MARL_EINVAL;
+    }
+    const marl_panel_bwd_prob& q = *qp;
+    p = PanelBwdProb{};
+    jobs.transposes.count = jobs.frags.count = 0;
+    jobs.floats = 0;
+    if (q.gate_pos) {
+        set_error("marl_panel_bwd: the position gate is not served here");
+        return MARL_EINVAL;
+    }
+    if (q.nlayers < 1 || q.nlayers > kPanelMaxLayers || q.m < 1) {
+        set_error("marl_panel_bwd: 1..%d layers, m >= 1", kPanelMaxLayers);
+        return MARL_EINVAL;
+    }
+    int by_batch = q.by_batch;
+    MARL_TRY(check_grouping("marl_panel_bwd", by_batch, q.g_na, q.g_nb, q.m, q.agg_at, q.nlayers, q.mix));
+    if (q.agg_na < 0 || (q.agg_na > 0 && (q.agg_nb < 1 || (int64_t)q.agg_na * q.agg_nb != q.m))) {
+        set_error("marl_panel_bwd: the staged mean needs m == agg_na * agg_nb");
+        return MARL_EINVAL;
+    }
+    if (!vec_ok(q.da, q.ldda, q.layer[0].n) || (q.da2 && !vec_ok(q.da2, q.ldda2, q.layer[0].n))) {
+        set_error("marl_panel_bwd: da / da2 must be 16-byte aligned with ld %% 4 == 0 and ld >= round4(n)");
+        return MARL_EINVAL;
+    }
+    const int k_last = q.layer[q.nlayers - 1].k_in;
+    if (!q.dx || !al16(q.dx) || q.lddx < k_last) {
+        set_error("marl_panel_bwd: dx must be 16-byte aligned with lddx >= the first layer's input width");
+        return MARL_EINVAL;
+    }
+    p.da = q.da, p.ldda = q.ldda, p.da2 = q.da2, p.ldda2 = q.ldda2, p.agg_na = q.agg_na, p.agg_nb = q.agg_nb;
+    p.m = q.m, p.nlayers = q.nlayers, p.dx = q.dx, p.lddx = q.lddx, p.accumulate = q.accumulate ? 1 : 0;
+    p.by_batch = by_batch, p.g_na = q.g_na, p.g_nb = q.g_nb, p.agg_at = q.agg_at, p.mix = q.mix;
+    size_t tr_floats = 0;
+    for (int l = 0; l < q.nlayers; ++l) {
+        const marl_panel_bwd_layer& s = q.layer[l];
+        if (s.n < 1 || s.n > kApiMaxWidth || s.k_in < 1) {
+            set_error("marl_panel_bwd: layer %d width %d outside 1..%d", l, s.n, kApiMaxWidth);
+            return MARL_ELIMIT;
+        }
+        if (l + 1 < q.nlayers && q.layer[l + 1].n != s.k_in) {
+            set_error("marl_panel_bwd: layer %d's input width %d is not layer %d's width %d", l, s.k_in, l + 1,
+                      q.layer[l + 1].n);
+            return MARL_EINVAL;
+        }
+        if (!s.w) {
+            set_error("marl_panel_bwd: layer %d has no weight (null fragment source)", l);
+            return MARL_EINVAL;
+        }
+        if (s.ldw < s.k_in || !s.z || s.ldz < s.n || !s.stats || !s.gamma || !s.beta || !s.dz || s.lddz < s.n ||
+            !s.part) {
+            set_error("marl_panel_bwd: layer %d: null pointer or a leading dimension below its width", l);
+            return MARL_EINVAL;
+        }
+        PanelBwdLayer& d = p.layer[l];
+        d.z = s.z, d.ldz = s.ldz, d.stats = s.stats, d.gamma = s.gamma, d.beta = s.beta, d.n = s.n;
+        d.dz = s.dz, d.lddz = s.lddz, d.part = s.part, d.k_in = s.k_in;
+        d.wgroups = panel_frag_groups(s.n);
+        d.wtfrag = g_here;
+        jobs.floats += panel_frag_floats(s.k_in, s.n);
+        tr_floats += (size_t)s.k_in * s.n;
+    }
+    if (q.has_cellb) {
+        MARL_TRY(check_cell("cellb", q.cellb, false));
+        if (q.cellb.n != k_last) {
+            set_error("marl_panel_bwd: cellb.n %d is not the first layer's input width %d", q.cellb.n, k_last);
+            return MARL_EINVAL;
+        }
+        p.has_cellb = 1;
+        p.cellb = cell_args(q.cellb);
+    }
+    if (q.has_cell) {
+        MARL_TRY(check_cell("cell", q.cell, true));
+        if (q.cell_rows < 1) {
+            set_error("marl_panel_bwd: cell_rows < 1");
+            return MARL_EINVAL;
+        }
+        p.has_cell = 1;
+        p.cell = cell_args(q.cell);
+        p.cell_rows = q.cell_rows;
+    }
+    const size_t frag_floats = jobs.floats;
+    jobs.floats += (tr_floats + 3) & ~(size_t)3;
+    if (plan_only) return MARL_OK;
+    if (!scratch || !al16(scratch) || scratch_bytes < jobs.floats * sizeof(float)) {
+        set_error("marl_panel_bwd: scratch too small or misaligned (%zu bytes needed)", jobs.floats * sizeof(float));
+        return MARL_ESIZE;
+    }
+    size_t off = 0, toff = frag_floats;
+    for (int l = 0; l < q.nlayers; ++l) {
+        const marl_panel_bwd_layer& s = q.layer[l];
+        // W^T [k_in][n] row-major behind the copies, then its fragment-order copy
+        PermDesc t{};
+        t.src = s.w, t.dst = scratch + toff, t.rows = s.k_in, t.cols = s.n, t.dst_ld = s.n;
+        t.rd = 1, t.rs1 = 1, t.rs2 = 0, t.cd = 1, t.cs1 = s.ldw, t.cs2 = 0;
+        jobs.transposes.d[jobs.transposes.count++] = t;
+        PermDesc f{};
+        f.src = scratch + toff, f.dst = scratch + off, f.rows = s.k_in, f.cols = s.n;
+        f.rd = 1, f.rs1 = s.n, f.cd = 1, f.cs1 = 1, f.frag = p.layer[l].wgroups;
+        jobs.frags.d[jobs.frags.count++] = f;
+        p.layer[l].wtfrag = scratch + off;
+        off += panel_frag_floats(s.k_in, s.n);
+        toff += (size_t)s.k_in * s.n;
+    }
+    return MARL_OK;
+}
+
+int run_jobs(const FragJobs& jobs, float* scratch, hipStream_t st) {
+    MARL_TRY(launch_fill(scratch, (int64_t)jobs.floats, 0.f, st));
+    if (jobs.transposes.count) MARL_TRY(launch_permute(jobs.transposes, st));
+    return launch_permute(jobs.frags, st);
+}
+
+void slice_plan(marl_panel_plan_info* out, int i, int K, int n_out, int nwaves) {
+    const int nt = (n_out + 31) >> 5, K16 = (K + 15) & ~15;
+    const int w = panel_waves_for(K, n_out);
+    const int ks = panel_ksplit(K, nt, nwaves), kper = panel_kper_host(K16, ks);
+    out->layer_waves[i] = w;
+    out->rounds[i] = w < 0;
+    out->nt[i] = nt, out->ks[i] = ks, out->kper[i] = kper;
+    int empty = 0;
+    for (int s = 0; s < ks; ++s)
+        if (s * kper >= K16) empty |= 1 << s;
+    out->empty[i] = empty;
+}
+
+}  // namespace
+
+size_t marl_panel_scratch_bytes(int backward, int nlayers, const int* n, const int* k) {
+    if (nlayers < 1 || nlayers > kPanelMaxLayers || !n || !k) return 0;
+    size_t floats = 0, tr = 0;
+    for (int l = 0; l < nlayers; ++l) {
+        if (n[l] < 1 || k[l] < 1) return 0;
+        floats += backward ? panel_frag_floats(k[l], n[l]) : panel_frag_floats(n[l], k[l]);
+        tr += (size_t)n[l] * k[l];
+    }
+    if (backward) floats += (tr + 3) & ~(size_t)3;
+    return floats * sizeof(float);
+}
+
+int marl_panel_fwd(const marl_panel_fwd_prob* probs, int count, float* scratch, size_t scratch_bytes, void* stream) {
+    static PanelFwdBatch b;  // (4 KB-class descriptors: kept off the stack; the entries are not re-entrant)
+    static FragJobs jobs;
+    MARL_TRY(build_fwd(probs, count, scratch, scratch_bytes, false, b, jobs));
+    {
+        PanelFwdBatch probe = b;  // every refusal of the launcher before anything is enqueued
+        PanelFwdPlan pl;
+        MARL_TRY(panel_fwd_plan(probe, pl));
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MARL_TRY(run_jobs(jobs, scratch, st));
+    return launch_panel_fwd(b, st);
+}
+
+int marl_panel_bwd(marl_panel_bwd_prob* prob, float* scratch, size_t scratch_bytes, void* stream) {
+    static PanelBwdProb p;
+    static FragJobs jobs;
+    MARL_TRY(build_bwd(prob, scratch, scratch_bytes, false, p, jobs));
+    {
+        PanelBwdProb probe = p;
+        PanelBwdPlan pl;
+        MARL_TRY(panel_bwd_plan(probe, pl));
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MARL_TRY(run_jobs(jobs, scratch, st));
+    MARL_TRY(launch_panel_bwd(p, st));
+    prob->cellb_img_done = p.cellb_img_done;
+    prob->cell_img_done = p.cell_img_done;
+    return MARL_OK;
+}
+
+int marl_panel_plan(const marl_panel_fwd_prob* fwd, int count, const marl_panel_bwd_prob* bwd,
+                    marl_panel_plan_info* out) {
+    if (!out || (fwd != nullptr) == (bwd != nullptr)) {
+        set_error("marl_panel_plan: exactly one of the forward and the backward descriptor, and an output");
+        return MARL_EINVAL;
+    }
+    *out = marl_panel_plan_info{};
+    static FragJobs jobs;
+    if (fwd) {
+        static PanelFwdBatch b;
+        MARL_TRY(build_fwd(fwd, count, nullptr, 0, true, b, jobs));
+        PanelFwdPlan pl;
+        MARL_TRY(panel_fwd_plan(b, pl));
+        out->waves = pl.waves, out->lds_bytes = (int)pl.lds, out->blocks = (int)pl.pblocks;
+        int i = 0;
+        for (int q = 0; q < b.count; ++q) {
+            out->by_batch[q] = b.p[q].by_batch;
+            int kin = b.p[q].k0;
+            for (int l = 0; l < b.p[q].nlayers; ++l, ++i) {
+                slice_plan(out, i, kin, b.p[q].layer[l].n, pl.waves);
+                out->ln_slots[i] = b.p[q].layer[l].n <= b.ln_narrow_max ? 2 : kPanelMaxCols;
+                kin = b.p[q].layer[l].n;
+            }
+        }
+        out->nlayers = i;
+        return MARL_OK;
+    }
+    static PanelBwdProb p;
+    MARL_TRY(build_bwd(bwd, nullptr, 0, true, p, jobs));
+    PanelBwdPlan pl;
+    MARL_TRY(panel_bwd_plan(p, pl));
+    out->waves = pl.waves, out->lds_bytes = (int)pl.lds, out->blocks = (int)pl.pblocks;
+    out->cell_blocks = (int)pl.cblocks, out->by_batch[0] = p.by_batch, out->nlayers = p.nlayers;
+    for (int l = 0; l < p.nlayers; ++l) {  // the dX product: contraction over n, tiles over k_in
+        slice_plan(out, l, p.layer[l].n, p.layer[l].k_in, pl.waves);
+        out->ln_slots[l] = pl.maxc;
+    }
+    out->maxc = pl.maxc, out->tail_lds = p.tail_lds, out->retried = pl.retried ? 1 : 0;
+    out->cell_vec4 = p.cell_vec4, out->cellb_img_done = p.cellb_img_done, out->cell_img_done = p.cell_img_done;
+    return MARL_OK;
+}
