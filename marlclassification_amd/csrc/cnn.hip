@@ -828,22 +828,46 @@ static bool fwd2_matches(const CnnFwdArgs& a) {
 }
 
 // The persistent launches (cnn_fwd2 / cnn_fwd3) take one workgroup per chunk up to 256 workgroups; above that a
-// workgroup walks chunk += gridDim.x.  launch_cnn_fwd and cnn_fwd_launch_plan (marl_plan_query) both ask here.
+// workgroup walks chunk += gridDim.x.  cnn_fwd_plan (CnnFwdPlan::blocks) asks here.
 constexpr int kFwd2Rows = 8;  // patches per chunk of cnn_fwd2_kernel: one per wave
 static int fwd2_grid(int64_t nchunks) { return nchunks < 256 ? (int)nchunks : 256; }
 
+// The device-dependent steps of the conv launchers (everything else is host arithmetic in their plan routines).
+// Raises a kernel's dynamic-LDS limit the first time the kernel is seen (per process; one process drives one GPU).
+static hipError_t cnn_raise_lds(const void* kern, int bytes) {
+    static const void* done[64];
+    static int ndone = 0;
+    for (int i = 0; i < ndone; ++i)
+        if (done[i] == kern) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && ndone < 64) done[ndone++] = kern;
+    return e;
+}
+// resident 512-thread workgroups per CU of a kernel at this dynamic LDS size (registers, LDS, wave slots); the same
+// instantiation serves layers with different LDS sizes, so the answer is cached per (kernel, LDS bytes)
+static int cnn_occupancy(const void* kern, size_t lds) {
+    struct Seen {
+        const void* kern;
+        size_t lds;
+        int occ;
+    };
+    static Seen seen[64];
+    static int nseen = 0;
+    for (int i = 0; i < nseen; ++i)
+        if (seen[i].kern == kern && seen[i].lds == lds) return seen[i].occ;
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 512, lds) != hipSuccess || occ < 1) occ = 1;
+    if (nseen < 64) seen[nseen++] = Seen{kern, lds, occ};
+    return occ;
+}
+
 template <class N>
-static int fwd2_launch(CnnFwdArgs& a, hipStream_t st) {
-    static bool raised = false;  // per process; one process drives one GPU
+static int fwd2_launch(CnnFwdArgs& a, const CnnFwdPlan& p, hipStream_t st) {
     auto kern = cnn_fwd2_kernel<N>;
-    constexpr size_t lds = (size_t)N::lds_floats() * sizeof(float);
-    if (!raised) {
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-    }
-    const int nchunks = (int)cdiv(a.rows, kFwd2Rows);
-    const int blocks = fwd2_grid(nchunks);
+    const size_t lds = p.lds_bytes;
+    MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
+    const int nchunks = (int)cdiv(a.rows, p.rb);
+    const int blocks = p.blocks;
 #ifdef MARL_KERNEL_TS
     static long long* d_ts2 = nullptr;
     static int calls2 = 0;
@@ -1357,17 +1381,12 @@ using Plan3Aid32 = Fwd3Plan<Fwd3Aid32, 4>;
 static_assert(Plan3Aid24::ok() && Plan3Aid32::ok(), "fwd3 nets");
 
 template <class N, class PL>
-static int fwd3_launch(CnnFwdArgs& a, hipStream_t st) {
-    static bool raised = false;  // per process; one process drives one GPU
+static int fwd3_launch(CnnFwdArgs& a, const CnnFwdPlan& p, hipStream_t st) {
     auto kern = cnn_fwd3_kernel<N, PL>;
-    constexpr size_t lds = (size_t)PL::lds_floats() * sizeof(float);
-    if (!raised) {
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-    }
-    const int ngroups = (int)cdiv(a.rows, PL::GP);
-    const int blocks = fwd2_grid(ngroups);
+    const size_t lds = p.lds_bytes;
+    MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
+    const int ngroups = (int)cdiv(a.rows, p.rb);
+    const int blocks = p.blocks;
 #ifdef MARL_KERNEL_TS
     static long long* d_ts3 = nullptr;
     static int calls3 = 0;
@@ -1400,7 +1419,7 @@ static int cnn_fwd2_which(const CnnFwdArgs& a) {
 }
 
 // LDS floats for rb patches per workgroup; fills the launcher-owned fields of `a`
-static size_t cnn_fwd_plan(CnnFwdArgs& a, int rb) {
+static size_t cnn_fwd_lds_floats(CnnFwdArgs& a, int rb) {
     size_t b0 = 0, b1 = 0, st = 0;
     for (int l = 0; l < a.L; ++l) {
         const CnnFwdLayer& L = a.layer[l];
@@ -1433,74 +1452,61 @@ static size_t cnn_fwd_plan(CnnFwdArgs& a, int rb) {
     return patch + b0 + b1 + st;
 }
 
-int cnn_fwd_writes_image(const CnnFwdArgs& a) {
-    // Fwd2Resisc / Fwd2Mnist6 (mode-1 last layer) and the two AidCnn plans (packed last layer): the last
-    // layer has four positions per patch, a lane's four outputs are four consecutive columns of U
-    const int w = cnn_fwd2_which(a);
-    return w == 1 || w == 2 || w == 4 || w == 5;
+bool cnn_fused_enabled() {
+    const char* e = getenv("MARL_CNN_FUSED");
+    return !(e && e[0] == '0');
 }
 
-int cnn_fwd_supported(const CnnFwdArgs& a0) {
-    if (getenv("MARL_CNN_FUSED") && getenv("MARL_CNN_FUSED")[0] == '0') return 0;
-    CnnFwdArgs a = a0;
-    if (cnn_fwd2_which(a)) return 1;
+// The one planning routine of launch_cnn_fwd (common.h: CnnFwdPlan).
+CnnFwdPlan cnn_fwd_plan(CnnFwdArgs& a) {
+    CnnFwdPlan p{};
+    if (!cnn_fused_enabled()) return p;
+    if (const int w = cnn_fwd2_which(a)) {
+        static const int kRb[5] = {kFwd2Rows, kFwd2Rows, kFwd2Rows, Plan3Aid24::GP, Plan3Aid32::GP};
+        static const int kLdsFloats[5] = {Fwd2Resisc::lds_floats(), Fwd2Mnist6::lds_floats(), Fwd2Mnist12::lds_floats(),
+                                          Plan3Aid24::lds_floats(), Plan3Aid32::lds_floats()};
+        p.which = w;
+        p.rb = kRb[w - 1];
+        p.blocks = fwd2_grid(cdiv(a.rows, p.rb));
+        p.lds_bytes = (size_t)kLdsFloats[w - 1] * sizeof(float);
+        // Fwd2Resisc / Fwd2Mnist6 (mode-1 last layer) and the two AidCnn plans (packed last layer): the last
+        // layer has four positions per patch, a lane's four outputs are four consecutive columns of U
+        p.writes_image = w != 3;
+        return p;
+    }
     for (int l = 0; l < a.L; ++l) {
         const CnnFwdLayer& L = a.layer[l];
-        if (L.cout % L.G != 0 || ((L.cout / L.G) & 3) || (L.cout & 3)) return 0;  // float4 stays inside a group
-        if (l > 0 && (L.cin & 3)) return 0;
+        if (L.cout % L.G != 0 || ((L.cout / L.G) & 3) || (L.cout & 3)) return p;  // float4 stays inside a group
+        if (l > 0 && (L.cin & 3)) return p;
     }
-    return cnn_fwd_plan(a, 1) * sizeof(float) <= 144 * 1024;
-}
-
-// patches per workgroup of the general cnn_fwd_kernel: as many as fit three workgroups per CU (the conv weights are
-// re-read from L2 by every workgroup), but keep >= 256 workgroups.  Leaves the plan of that rb in `a`.
-static int cnn_fwd_rb(CnnFwdArgs& a) {
+    // the general cnn_fwd_kernel covers what fits its LDS limit at one patch per workgroup ...
+    if (cnn_fwd_lds_floats(a, 1) * sizeof(float) > 144 * 1024) return p;
+    // ... and launches with as many patches per workgroup as fit three workgroups per CU (the conv weights are re-read
+    // from L2 by every workgroup), but keeps >= 256 workgroups
     constexpr int rb_max = 8, lds_cap = 52;  // patches per workgroup (<= 16: per-patch LDS tables), LDS cap in KB
     int rb = rb_max;
-    while (rb > 1 && (cnn_fwd_plan(a, rb) * sizeof(float) > (size_t)lds_cap * 1024 || cdiv(a.rows, rb) < 256)) --rb;
-    return rb;
-}
-
-CnnFwdPlan cnn_fwd_launch_plan(const CnnFwdArgs& a0) {
-    CnnFwdArgs a = a0;
-    CnnFwdPlan p{};
-    p.which = cnn_fwd2_which(a);
-    if (p.which >= 1 && p.which <= 3) {
-        p.rb = kFwd2Rows;
-        p.blocks = fwd2_grid(cdiv(a.rows, p.rb));
-    } else if (p.which) {
-        p.rb = p.which == 4 ? Plan3Aid24::GP : Plan3Aid32::GP;
-        p.blocks = fwd2_grid(cdiv(a.rows, p.rb));
-    } else {
-        p.which = 6;
-        p.rb = cnn_fwd_rb(a);
-        p.blocks = (int)cdiv(a.rows, p.rb);
-    }
+    while (rb > 1 && (cnn_fwd_lds_floats(a, rb) * sizeof(float) > (size_t)lds_cap * 1024 || cdiv(a.rows, rb) < 256)) --rb;
+    p.which = 6;
+    p.rb = rb;
+    p.blocks = (int)cdiv(a.rows, rb);
+    p.lds_bytes = cnn_fwd_lds_floats(a, rb) * sizeof(float);  // (leaves the plan of that rb in `a`)
     return p;
 }
 
 int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st) {
     if (a.rows <= 0) return MARL_OK;
-    switch (cnn_fwd2_which(a)) {
-        case 1: return fwd2_launch<Fwd2Resisc>(a, st);
-        case 2: return fwd2_launch<Fwd2Mnist6>(a, st);
-        case 3: return fwd2_launch<Fwd2Mnist12>(a, st);
-        case 4: return fwd3_launch<Fwd3Aid24, Plan3Aid24>(a, st);
-        case 5: return fwd3_launch<Fwd3Aid32, Plan3Aid32>(a, st);
-        default: break;
+    const CnnFwdPlan p = cnn_fwd_plan(a);
+    switch (p.which) {
+        case 1: return fwd2_launch<Fwd2Resisc>(a, p, st);
+        case 2: return fwd2_launch<Fwd2Mnist6>(a, p, st);
+        case 3: return fwd2_launch<Fwd2Mnist12>(a, p, st);
+        case 4: return fwd3_launch<Fwd3Aid24, Plan3Aid24>(a, p, st);
+        case 5: return fwd3_launch<Fwd3Aid32, Plan3Aid32>(a, p, st);
+        case 6: break;
+        default: set_error("fused CNN forward: window %d outside its range", a.f); return MARL_ELIMIT;
     }
-    const int rb = cnn_fwd_rb(a);
-    const size_t lds = cnn_fwd_plan(a, rb) * sizeof(float);
-    if (lds > 144 * 1024) {
-        set_error("fused CNN forward: window %d outside its range", a.f);
-        return MARL_ELIMIT;
-    }
-    static bool raised = false;
-    if (!raised) {
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn_fwd_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        raised = true;
-    }
+    const size_t lds = p.lds_bytes;
+    MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(cnn_fwd_kernel), 144 * 1024));
 #ifdef MARL_KERNEL_TS
     static long long* d_ts = nullptr;
     static int calls = 0;
@@ -1508,7 +1514,7 @@ int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st) {
     a.ts = rec ? d_ts : nullptr;
 #endif
     prof_before(3, st);
-    hipLaunchKernelGGL(cnn_fwd_kernel, dim3((unsigned)cdiv(a.rows, rb)), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(cnn_fwd_kernel, dim3((unsigned)p.blocks), dim3(512), lds, st, a);
     prof_after(3, st);
     MARL_LAUNCH_CHECK();
 #ifdef MARL_KERNEL_TS
@@ -1533,12 +1539,7 @@ __device__ __forceinline__ float cnn_silu_grad(float y) {
     return silu_grad_fast(y);
 }
 
-// W0 (the launch that produces dZ_0): the FIRST layer's weight gradient is formed right here from the dZ_0 panel in
-// LDS and the raw image patch (gathered at the saved positions into a zero-bordered LDS image), as in
-// cnn_wgrad_kernel<.., FIRST>: dZ_0 - the largest activation gradient of the network (1 GB at BASELINE configs[4]) -
-// is neither written nor read back, and the separate first-layer launch disappears.
-template <bool W0>
-__global__ __launch_bounds__(512, W0 ? 4 : 1) void cnn_dgrad_kernel(const CnnDgradArgs A) {
+__global__ __launch_bounds__(512, 1) void cnn_dgrad_kernel(const CnnDgradArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Dz = lds;                    // [rb * P][cout + 4]
     float* Zin = lds + A.off_zin;       // [rb * Pin][cin + 4]
@@ -1580,64 +1581,7 @@ __global__ __launch_bounds__(512, W0 ? 4 : 1) void cnn_dgrad_kernel(const CnnDgr
             *reinterpret_cast<float4*>(Zin + m * cs + k) = *reinterpret_cast<const float4*>(zsrc + (int64_t)m * cin + k);
         }
         for (int idx = tid; idx < nrow * G * 2; idx += nthreads) gstat[idx] = A.gst[row0 * G * 2 + idx];
-        if constexpr (W0) {  // raw patches of the chunk -> interior of the zero-bordered images [lr][y + 1][x + 1][ci]
-            // Batches of kU elements per thread with every load of a batch in flight at once (positions first, then
-            // pixels; clamped indices, predicated LDS writes) instead of two dependent global round trips per element.
-            // (Measured: the fused form still loses to the separate first-layer launch - C3 +0.08...0.16 ms, C5 +0.16,
-            // C4 +0.06 - so the gather was not what costs; see cnn_dgrad_w0_ok.)
-            float* Pix = lds + A.off_pix;
-            const int f0 = A.f0, ff = f0 * f0, pe = A.cin0 * ff, tot = nrow * pe;
-            const int64_t plane = (int64_t)A.c_img * A.H * A.W;
-            const float* imgf = static_cast<const float*>(A.img);
-            const unsigned char* imgb = static_cast<const unsigned char*>(A.img);
-            constexpr int kU = 4;
-            for (int base = tid; base < tot; base += kU * nthreads) {
-                int lo[kU], p0[kU], p1[kU], go[kU], img_i[kU];
-#pragma unroll
-                for (int u = 0; u < kU; ++u) {
-                    int idx = base + u * nthreads;
-                    idx = idx < tot ? idx : tot - 1;
-                    const int lr = fdiv(idx, A.dpe0), e = idx - lr * pe;
-                    const int ci = fdiv(e, A.dff0), e2 = e - ci * ff;
-                    const int iy = fdiv(e2, A.df0), ix = e2 - iy * f0;
-                    const int64_t r = row0 + lr;
-                    p0[u] = A.pos[r * 2];
-                    p1[u] = A.pos[r * 2 + 1];
-                    img_i[u] = (int)(r % A.nb);
-                    go[u] = (ci * A.H + iy) * A.W + ix;
-                    lo[u] = lr * A.pix_per + ((iy + 1) * (f0 + 2) + ix + 1) * A.cs0 + ci;
-                }
-                float pv[kU];
-#pragma unroll
-                for (int u = 0; u < kU; ++u) {
-                    const int64_t off = img_i[u] * plane + (int64_t)p0[u] * A.W + p1[u] + go[u];
-                    pv[u] = A.img_u8 ? (float)imgb[off] / 255.0f : imgf[off];
-                }
-#pragma unroll
-                for (int u = 0; u < kU; ++u)
-                    if (base + u * nthreads < tot) Pix[lo[u]] = pv[u];
-            }
-        }
     };
-    // first-layer weight gradient (W0): per-lane window offsets of the lane's im2col columns, accumulators that
-    // live across all chunks of the workgroup (two 16-wide k tiles cover K0 = 9 * cin0 <= 32)
-    constexpr int NK0 = 2;
-    int toff0[NK0];
-    cf32x4 acc0[NK0];
-    float bsum0 = 0.f;
-    if constexpr (W0) {
-#pragma unroll
-        for (int j = 0; j < NK0; ++j) {
-            int kc = j * 16 + l16;
-            kc = kc < A.K0 ? kc : A.K0 - 1;
-            const int tap = kc / A.cin0, ci = kc - tap * A.cin0;
-            toff0[j] = ((tap / 3) * (A.f0 + 2) + (tap % 3)) * A.cs0 + ci;
-            acc0[j] = cf32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        float* Pix = lds + A.off_pix;  // zero once: the borders are never written again
-        for (int i = tid; i < A.rb * A.pix_per; i += nthreads) Pix[i] = 0.f;
-        __syncthreads();
-    }
 
     // transposed convolution: wave w owns column tile nt = w % NT and a CONTIGUOUS range of row tiles
     // (same parity class -> same taps, so one weight fragment feeds all of them)
@@ -1883,26 +1827,6 @@ __global__ __launch_bounds__(512, W0 ? 4 : 1) void cnn_dgrad_kernel(const CnnDgr
         MARL_TS();
         __syncthreads();
         MARL_TS();
-        if constexpr (W0) {
-            // ---- dW_0[co][k] += sum_m dZ_0[m][co] * im2col(patch)[m][k] on 16x16x4 f32 MFMA tiles: A = the dZ_0 panel
-            // (rows m = patch-major layer-0 output positions), B gathered from the pixel image; wave w takes the row
-            // steps s = w, w + nwaves, ...
-            const float* Pix = lds + A.off_pix;
-            const int M0 = nrow * Pin, msteps = (M0 + 3) >> 2;
-            for (int s0 = wave; s0 < msteps; s0 += nwaves) {
-                const int m = s0 * 4 + quad;
-                const bool mv = m < M0;
-                const int mm = mv ? m : 0;
-                const int lr = fdiv(mm, A.dPin), ipos = mm - lr * Pin;
-                const int oy = fdiv(ipos, A.dhin0), ox = ipos - oy * hin;
-                const float a = (mv && l16 < cin) ? Da[mm * cs + l16] : 0.f;
-                const float* win = Pix + lr * A.pix_per + (2 * oy * (A.f0 + 2) + 2 * ox) * A.cs0;
-                bsum0 += a;
-#pragma unroll
-                for (int j = 0; j < NK0; ++j) acc0[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, win[toff0[j]], acc0[j], 0, 0, 0);
-            }
-            __syncthreads();  // the pixel images are free: the next chunk's may land
-        }
         // ---- the next chunk's loads go out first (Dz, Zin and the statistics are free from here on),
         // then dZ_{l-1} of this chunk -> global (coalesced)
         if (chunk + (int)gridDim.x < nchunks) stage(chunk + (int)gridDim.x);
@@ -1933,38 +1857,10 @@ __global__ __launch_bounds__(512, W0 ? 4 : 1) void cnn_dgrad_kernel(const CnnDgr
         for (int w = gg; w < nwaves; w += G) t += gsum[(w * 2 + which) * cpg + c2];
         A.part[(size_t)blockIdx.x * 2 * cin + e] = t;
     }
-    if constexpr (W0) {
-        // ---- the waves' partial tiles (different row steps) are summed in a fixed order; one slab per workgroup
-        __syncthreads();
-        float* red = lds;  // [nwaves][NK0][64 lanes][4] + [nwaves][64] bias partials
-        float* redb = lds + nwaves * NK0 * 256;
-#pragma unroll
-        for (int j = 0; j < NK0; ++j) *reinterpret_cast<cf32x4*>(red + ((wave * NK0 + j) * 64 + lane) * 4) = acc0[j];
-        redb[wave * 64 + lane] = bsum0;
-        __syncthreads();
-        if (wave == 0) {
-            float* pw = A.w0_part + (size_t)blockIdx.x * cin * A.K0;
-#pragma unroll
-            for (int j = 0; j < NK0; ++j) {
-                cf32x4 v = acc0[j];
-                for (int q = 1; q < nwaves; ++q) v += *reinterpret_cast<const cf32x4*>(red + ((q * NK0 + j) * 64 + lane) * 4);
-                const int kcol = j * 16 + l16;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = 4 * quad + r;
-                    if (co < cin && kcol < A.K0) pw[(size_t)co * A.K0 + kcol] = v[r];
-                }
-            }
-            // bias gradient of layer 0 = column sums of dZ_0: lane (quad, l16) summed channel l16 over its rows
-            float t = 0.f;
-            for (int q = 0; q < nwaves; ++q)
-                t += ((redb[q * 64 + l16] + redb[q * 64 + 16 + l16]) + redb[q * 64 + 32 + l16]) + redb[q * 64 + 48 + l16];
-            if (quad == 0 && l16 < cin) A.w0_bpart[(size_t)blockIdx.x * cin + l16] = t;
-        }
-    }
 }
 
-static size_t cnn_dgrad_plan(CnnDgradArgs& a, int rb) {
+// LDS floats for rb patches per chunk; fills the launcher-owned fields of `a`
+static size_t cnn_dgrad_lds_floats(CnnDgradArgs& a, int rb) {
     a.rb = rb;
     a.MT = (rb * a.Pin + 15) / 16;
     a.NT = (a.cin + 15) / 16;
@@ -1985,19 +1881,6 @@ static size_t cnn_dgrad_plan(CnnDgradArgs& a, int rb) {
     off += (size_t)rb * a.G * 2;
     a.off_gsum = (int)off;
     off += (size_t)8 * 2 * cpg;
-    if (a.w0) {  // zero-bordered raw patches of the chunk [rb][f0 + 2][f0 + 2][cin0]
-        off = (off + 3) & ~(size_t)3;
-        a.cs0 = a.cin0;
-        a.pix_per = (a.f0 + 2) * (a.f0 + 2) * a.cs0;
-        a.off_pix = (int)off;
-        off += (size_t)rb * a.pix_per;
-        a.dpe0 = make_fdiv(a.cin0 * a.f0 * a.f0);
-        a.dff0 = make_fdiv(a.f0 * a.f0);
-        a.df0 = make_fdiv(a.f0);
-        a.dhin0 = make_fdiv(a.hin);
-        const size_t red = (size_t)8 * 2 * 256 + 8 * 64;  // the final tile reduction lives at the start of LDS
-        if (off < red) off = red;
-    }
     // Row tiles -> wave slots: contiguous ranges (one parity class -> one set of taps, so one
     // weight fragment feeds every tile of a range) of about equal cost; a tile costs one unit
     // plus one per tap of the classes it touches (1, 2, 2, 4 taps), <= kDgradTiles per slot.
@@ -2038,135 +1921,58 @@ static size_t cnn_dgrad_plan(CnnDgradArgs& a, int rb) {
     return off;
 }
 
-static int cnn_dgrad_rb(CnnDgradArgs& a) {
-    // largest rb <= 8 whose panels fit 72 KiB (two workgroups per CU) with at most
-    // kDgradTiles row tiles per wave, keeping >= 512 workgroups when the problem allows it
-    const int nt = (a.cin + 15) / 16;
-    const int wpn = 8 / nt;
-    if (wpn < 1) return 0;
-    const int rb_max = 8;
+// The one planning routine of launch_cnn_dgrad (common.h: CnnDgradPlan): the largest rb <= 8 whose panels fit 72 KiB
+// (two workgroups per CU) with at most kDgradTiles row tiles per wave, keeping >= dgrad_min_chunks (512) chunks when the
+// problem allows it.
+CnnDgradPlan cnn_dgrad_plan(CnnDgradArgs& a) {
+    CnnDgradPlan p{};
+    if (!cnn_fused_enabled()) return p;
+    if ((a.cin & 3) || (a.cout & 3) || a.cin % a.G != 0) return p;
+    const int cpg = a.cin / a.G;
+    if (cpg > 64 || (cpg & (cpg - 1)) || 8 % a.G != 0) return p;  // lane <-> channel ownership
+    if (a.hin > 255 || a.rows <= 0) return p;
+    const int wpn = 8 / ((a.cin + 15) / 16);
+    if (wpn < 1) return p;
     const size_t lds_cap = (size_t)72 * 1024;
-    for (int rb = rb_max < 8 ? (rb_max < 1 ? 1 : rb_max) : 8; rb >= 1; --rb) {
-        if (cnn_dgrad_plan(a, rb) * sizeof(float) > lds_cap) continue;
+    for (int rb = 8; rb >= 1; --rb) {
+        const size_t lds = cnn_dgrad_lds_floats(a, rb) * sizeof(float);
+        if (lds > lds_cap) continue;
         if (a.MT > kDgradTiles * wpn || a.MT > 64) continue;
         if (rb > 1 && cdiv(a.rows, rb) < tune_get("dgrad_min_chunks", 512)) continue;
-        return rb;
+        p.rb = rb, p.MT = a.MT, p.NT = a.NT, p.chunks = (int)cdiv(a.rows, rb), p.lds_bytes = lds;
+        return p;
     }
-    return 0;
+    return p;
 }
 
-int cnn_dgrad_supported(const CnnDgradArgs& a0) {
-    if (getenv("MARL_CNN_FUSED") && getenv("MARL_CNN_FUSED")[0] == '0') return 0;
-    CnnDgradArgs a = a0;
-    if ((a.cin & 3) || (a.cout & 3) || a.cin % a.G != 0) return 0;
-    const int cpg = a.cin / a.G;
-    if (cpg > 64 || (cpg & (cpg - 1)) || 8 % a.G != 0) return 0;  // lane <-> channel ownership
-    if (a.hin > 255 || a.rows <= 0) return 0;
-    return cnn_dgrad_rb(a) > 0;
-}
-
-// can the launch that produces dZ_0 also form layer 0's weight gradient? (cin = layer 0's output channels: one
-// 16-wide tile; K0 = 9 * cin0 <= 32: two k tiles)
-// EXPERIMENT BUILD ONLY (EXTRA=-DMARL_DGRAD_W0; round 5's knob dgrad_w0 is gone): measured SLOWER than the separate first-layer launch on every BASELINE shape (C3 7.68
-// vs 7.59 ms, C4 3.71 vs 3.63, C5 18.45 vs 18.25: DESIGN 4.0c) - the extra phase adds two barriers, a scattered
-// pixel gather and ~4 us of dependent latency to each chunk of a kernel that is a latency chain already, which costs
-// more than the 100 us launch and the dZ_0 round trip it removes.
-int cnn_dgrad_w0_ok(const CnnDgradArgs& a, int cin0, int f0) {
-#ifdef MARL_DGRAD_W0  // experiment build only (make EXTRA=-DMARL_DGRAD_W0): the form lost every A/B, the product does not carry it
-    return a.cin <= 16 && 9 * cin0 <= 32 && cin0 >= 1 && (f0 - 1) / 2 + 1 == a.hin;
-#else
-    (void)a, (void)cin0, (void)f0;
-    return 0;
-#endif
-}
-
-// Persistent grid: as many workgroups as are resident at once (occupancy x CUs), never more than
-// there are chunks.  This is also the number of affine partial rows the kernel writes.
-static int cnn_dgrad_grid(const CnnDgradArgs& a, int rb, size_t lds) {
+// Persistent grid: as many workgroups as are resident at once (occupancy x CUs, or the knob dgrad_wgs), never more than
+// there are chunks.  This is also the number of affine partial rows the kernel writes.  0: no plan, or no device.
+static int cnn_dgrad_grid(const CnnDgradPlan& p) {
     static int num_cu = 0;
-    static size_t occ_lds[8];
-    static int occ_val[8], occ_n = 0;
+    if (p.rb <= 0) return 0;
+    const void* kern = reinterpret_cast<const void*>(cnn_dgrad_kernel);
+    (void)cnn_raise_lds(kern, 144 * 1024);
     if (!num_cu) {
         int dev = 0;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
         num_cu = prop.multiProcessorCount;
     }
-    int occ = 0;
-    const size_t key = lds * 2 + (a.w0 ? 1 : 0);  // (the two instantiations differ in registers)
-    for (int i = 0; i < occ_n; ++i)
-        if (occ_lds[i] == key) occ = occ_val[i];
-    if (!occ) {
-#ifdef MARL_DGRAD_W0
-        const void* kern = a.w0 ? reinterpret_cast<const void*>(cnn_dgrad_kernel<true>)
-                                     : reinterpret_cast<const void*>(cnn_dgrad_kernel<false>);
-#else
-        const void* kern = reinterpret_cast<const void*>(cnn_dgrad_kernel<false>);
-#endif
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 512, lds) != hipSuccess || occ < 1) occ = 1;
-        if (occ_n < 8) {
-            occ_lds[occ_n] = key;
-            occ_val[occ_n++] = occ;
-        }
-    }
     int64_t cap = (int64_t)tune_get("dgrad_wgs", 0);  // <= 0: every workgroup resident at once
-    if (cap <= 0) cap = (int64_t)occ * num_cu;
-    const int64_t chunks = cdiv(a.rows, rb);
-    return (int)(chunks < cap ? chunks : (cap < 1 ? 1 : cap));
+    if (cap <= 0) cap = (int64_t)cnn_occupancy(kern, p.lds_bytes) * num_cu;
+    return (int)(p.chunks < cap ? p.chunks : (cap < 1 ? 1 : cap));
 }
 
-static void cnn_dgrad_raise_lds() {
-    static bool raised = false;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cnn_dgrad_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-#ifdef MARL_DGRAD_W0
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cnn_dgrad_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-#endif
-        raised = true;
-    }
-}
-
-int cnn_dgrad_launch_rb(const CnnDgradArgs& a0) {
-    CnnDgradArgs a = a0;
-    return cnn_dgrad_rb(a);
-}
-
-CnnDgradPlanInfo cnn_dgrad_launch_plan(const CnnDgradArgs& a0) {
-    CnnDgradArgs a = a0;
-    CnnDgradPlanInfo p{};
-    p.rb = cnn_dgrad_rb(a);
-    if (p.rb <= 0) return CnnDgradPlanInfo{};
-    (void)cnn_dgrad_plan(a, p.rb);  // (cnn_dgrad_rb leaves the last rb it tried in `a`)
-    p.MT = a.MT, p.NT = a.NT, p.blocks = cnn_dgrad_blocks_max(a0);
-    return p;
-}
-
-// device-independent upper bound of cnn_dgrad_blocks (the workspace layout is computed without a GPU)
-int cnn_dgrad_blocks_max(const CnnDgradArgs& a0) {
-    CnnDgradArgs a = a0;
-    const int rb = cnn_dgrad_rb(a);
-    return rb > 0 ? (int)cdiv(a.rows, rb) : 0;
-}
-
-int cnn_dgrad_blocks(const CnnDgradArgs& a0) {
-    CnnDgradArgs a = a0;
-    const int rb = cnn_dgrad_rb(a);
-    if (rb <= 0) return 0;
-    cnn_dgrad_raise_lds();
-    return cnn_dgrad_grid(a, rb, cnn_dgrad_plan(a, rb) * sizeof(float));
-}
+int cnn_dgrad_blocks(CnnDgradArgs& a) { return cnn_dgrad_grid(cnn_dgrad_plan(a)); }
 
 int launch_cnn_dgrad(CnnDgradArgs& a, hipStream_t st) {
-    const int rb = cnn_dgrad_rb(a);
-    if (rb <= 0) {
+    const CnnDgradPlan p = cnn_dgrad_plan(a);
+    if (p.rb <= 0) {
         set_error("fused CNN layer backward: shape outside its range");
         return MARL_ELIMIT;
     }
-    const size_t lds = cnn_dgrad_plan(a, rb) * sizeof(float);
-    cnn_dgrad_raise_lds();
-    const int grid = cnn_dgrad_grid(a, rb, lds);
+    const size_t lds = p.lds_bytes;
+    const int grid = cnn_dgrad_grid(p);
 #ifdef MARL_KERNEL_TS
     static long long* d_ts = nullptr;
     static int calls = 0;
@@ -2175,26 +1981,12 @@ int launch_cnn_dgrad(CnnDgradArgs& a, hipStream_t st) {
     a.ts = rec ? d_ts : nullptr;
 #endif
     prof_before(5, st);
-    if (a.w0 && (!a.w0_part || !a.w0_bpart || !a.img || !a.pos)) {
-        set_error("fused CNN layer backward: first-layer weight gradient without its buffers");
-        return MARL_EINVAL;
-    }
-#ifdef MARL_DGRAD_W0
-    if (a.w0)
-        hipLaunchKernelGGL(cnn_dgrad_kernel<true>, dim3((unsigned)grid), dim3(512), lds, st, a);
-    else
-#else
-    if (a.w0) {
-        set_error("cnn_dgrad: the fused first-layer form is not in this build");
-        return MARL_EINVAL;
-    }
-#endif
-        hipLaunchKernelGGL(cnn_dgrad_kernel<false>, dim3((unsigned)grid), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(cnn_dgrad_kernel, dim3((unsigned)grid), dim3(512), lds, st, a);
     prof_after(5, st);
     MARL_LAUNCH_CHECK();
 #ifdef MARL_KERNEL_TS
     if (rec) {
-        fprintf(stderr, "[ts] dgrad rb %d lds %zu cin %d cout %d blocks %d\n", rb, lds, a.cin, a.cout, grid);
+        fprintf(stderr, "[ts] dgrad rb %d lds %zu cin %d cout %d blocks %d\n", p.rb, lds, a.cin, a.cout, grid);
         ts_report("cnn_dgrad", d_ts, 8);
     }
 #endif
@@ -2773,7 +2565,7 @@ __global__ __launch_bounds__(512) void cnn_wgrad3_kernel(const CnnWgradArgs A) {
 }
 
 // wave roles / chunk size of the bf16x6 form; returns the dynamic LDS BYTES (0 = this form does not apply)
-static size_t cnn_wgrad3_plan(CnnWgradArgs& a) {
+static size_t cnn_wgrad3_lds_bytes(CnnWgradArgs& a) {
     if (a.first || !split_mode() || tune_get("wgrad3", 1) == 0) return 0;
     if ((a.cin & 15) || (a.cout & 31) || a.cout > 256 || 512 % (a.cout / 4) != 0 || 512 % (a.cin / 4) != 0 ||
         a.cin % a.G != 0 || ((a.cin / a.G) & 3) || a.hin > 64 || a.rows <= 0)
@@ -2818,8 +2610,7 @@ static size_t cnn_wgrad3_plan(CnnWgradArgs& a) {
     a.dcin = make_fdiv(a.cin);
     if (best_nkt == 0) return 0;
     const int lds_cap_kb = best_nkt == 9 ? 150 : 76;
-    int rb_cap = 16;
-    if (rb_cap < 1) rb_cap = 1;
+    const int rb_cap = 16;
     for (int v = 0; v < 2; ++v) {
         const int PD = kWgPref[0][v][0], PI = kWgPref[0][v][1];
         for (int rb = rb_cap; rb >= 1; --rb) {
@@ -2852,8 +2643,8 @@ static size_t cnn_wgrad3_plan(CnnWgradArgs& a) {
     return 0;
 }
 
-// picks the wave roles and the chunk size; returns the dynamic LDS floats (0 = unsupported)
-static size_t cnn_wgrad_plan(CnnWgradArgs& a) {
+// picks the wave roles and the chunk size of the fp32 form; returns the dynamic LDS floats (0 = unsupported)
+static size_t cnn_wgrad1_lds_floats(CnnWgradArgs& a) {
     if ((a.cout & 3) || 512 % (a.cout / 4) != 0 || a.cout > 2048) return 0;
     if (!a.first && ((a.cin & 3) || 512 % (a.cin / 4) != 0 || a.cin % a.G != 0 || ((a.cin / a.G) & 3)))
         return 0;
@@ -2909,9 +2700,7 @@ static size_t cnn_wgrad_plan(CnnWgradArgs& a) {
     a.dff = make_fdiv(a.hin * a.hin);
     a.df = make_fdiv(a.hin);
     const int lds_cap_kb = 76;
-    int rb_cap = 16;
-    if (rb_cap < 1) rb_cap = 1;
-    const int wg_per_cu = 0;  // 0 = by layer size
+    const int rb_cap = 16;
     const size_t red = a.ms > 1 ? (size_t)8 * bct * bkt * 256 : 0;
     // the shallow prefetch variant first (fewer registers -> two workgroups per CU)
     for (int v = 0; v < 2; ++v) {
@@ -2941,7 +2730,7 @@ static size_t cnn_wgrad_plan(CnnWgradArgs& a) {
             // persistent workgroups: an upper bound here (it sizes the partial-slab scratch); the
             // launcher trims it to what is actually resident.  Small layers are staging-bound and
             // want more workgroups per CU in flight, their slabs are small.
-            const int per_cu = wg_per_cu > 0 ? wg_per_cu : ((int64_t)a.cout * a.K <= 8192 ? 4 : 2);
+            const int per_cu = (int64_t)a.cout * a.K <= 8192 ? 4 : 2;
             int blocks = 256 * per_cu / a.slabs;
             if (blocks < 64) blocks = 64;
             a.blocks = a.nchunks < blocks ? a.nchunks : blocks;
@@ -2951,153 +2740,80 @@ static size_t cnn_wgrad_plan(CnnWgradArgs& a) {
     return 0;
 }
 
-// the form launch_cnn_wgrad takes for these shapes, its plan in `a`, its dynamic LDS bytes in *lds:
-// 3 = bf16x6 (cnn_wgrad3_kernel: layers with >= 16 input channels), 1 = fp32 MFMA (cnn_wgrad_kernel), 0 = neither
-static int cnn_wgrad_form(CnnWgradArgs& a, size_t* lds) {
-    CnnWgradArgs b = a;
-    const size_t lds3 = cnn_wgrad3_plan(b);
-    if (lds3) {
-        a = b;
-        *lds = lds3;
-        return 3;
-    }
-    const size_t fl = cnn_wgrad_plan(a);
-    *lds = fl * sizeof(float);
-    return fl ? 1 : 0;
-}
-
-CnnWgradPlanInfo cnn_wgrad_launch_plan(const CnnWgradArgs& a0) {
-    CnnWgradArgs a = a0;
-    size_t lds = 0;
-    CnnWgradPlanInfo p{};
-    p.form = cnn_wgrad_form(a, &lds);
-    if (p.form) {
-        p.rb = a.rb, p.chunks = a.nchunks, p.blocks = a.blocks;
-        p.sct = a.sct, p.skt = a.skt, p.tgc = a.tgc, p.tgk = a.tgk, p.ms = a.ms, p.slabs = a.slabs, p.pd = a.pd, p.pi = a.pi;
-    }
+// The one planning routine of launch_cnn_wgrad (common.h: CnnWgradPlan): the bf16x6 form (cnn_wgrad3_kernel: layers with
+// >= 16 input channels) where it applies, else the fp32 MFMA form (cnn_wgrad_kernel); the chosen form's plan in `a`.
+CnnWgradPlan cnn_wgrad_plan(CnnWgradArgs& a) {
+    CnnWgradPlan p{};
+    CnnWgradArgs a1 = a, a3 = a;
+    const size_t lds1 = cnn_wgrad1_lds_floats(a1) * sizeof(float), lds3 = cnn_wgrad3_lds_bytes(a3);
+    const int n1 = lds1 ? a1.blocks : 0, n3 = lds3 ? a3.blocks : 0;
+    p.blocks_bound = n1 > n3 ? n1 : n3;
+    if (!lds1 || !cnn_fused_enabled()) return p;
+    p.form = lds3 ? 3 : 1;
+    p.lds_bytes = lds3 ? lds3 : lds1;
+    a = lds3 ? a3 : a1;
+    p.rb = a.rb, p.chunks = a.nchunks, p.blocks = a.blocks;
+    p.sct = a.sct, p.skt = a.skt, p.tgc = a.tgc, p.tgk = a.tgk, p.ms = a.ms, p.slabs = a.slabs, p.pd = a.pd, p.pi = a.pi;
     return p;
 }
 
-int cnn_wgrad_supported(const CnnWgradArgs& a0) {
-    if (getenv("MARL_CNN_FUSED") && getenv("MARL_CNN_FUSED")[0] == '0') return 0;
-    CnnWgradArgs a = a0;
-    return cnn_wgrad_plan(a) > 0;  // (the bf16x6 form covers a subset of these shapes)
-}
-
-int cnn_wgrad_blocks(const CnnWgradArgs& a0) {
-    // (an upper bound for the scratch: the larger of the two forms' workgroup counts)
-    CnnWgradArgs a = a0, b = a0;
-    const int n1 = cnn_wgrad_plan(a) > 0 ? a.blocks : 0;
-    const int n3 = cnn_wgrad3_plan(b) > 0 ? b.blocks : 0;
-    return n1 > n3 ? n1 : n3;
-}
-
-template <int NCT, int NKT, bool FIRST, int PD, int PI>
-static int wgrad_launch(const CnnWgradArgs& a, size_t lds, hipStream_t st) {
-    auto kern = cnn_wgrad_kernel<NCT, NKT, FIRST, PD, PI>;
-    if (lds > 64 * 1024) {
-        static bool raised = false;  // per process; one process drives one GPU (see marl_hip.h)
-        if (!raised) {
-            MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            raised = true;
-        }
-    }
-    prof_before(5, st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.blocks, (unsigned)a.slabs), dim3(512), lds, st, a);
-    prof_after(5, st);
-    MARL_LAUNCH_CHECK();
-    return MARL_OK;
-}
-
-// resident workgroups per CU of one instantiation at this LDS size (registers, LDS, wave slots)
-template <int NCT, int NKT, bool FIRST, int PD, int PI>
-static int wgrad_occupancy(size_t lds) {
-    static size_t seen_lds[8];  // (the same instantiation serves layers with different LDS sizes)
-    static int seen_occ[8], nseen = 0;
-    for (int i = 0; i < nseen; ++i)
-        if (seen_lds[i] == lds) return seen_occ[i];
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &occ, reinterpret_cast<const void*>(cnn_wgrad_kernel<NCT, NKT, FIRST, PD, PI>), 512, lds) !=
-            hipSuccess || occ < 1)
-        occ = 1;
-    if (nseen < 8) {
-        seen_lds[nseen] = lds;
-        seen_occ[nseen++] = occ;
-    }
-    return occ;
-}
-
-template <int NKT, int PD, int PI>
-static int wgrad3_launch(CnnWgradArgs& a, float* part_w, size_t lds, hipStream_t st) {
-    auto kern = cnn_wgrad3_kernel<NKT, PD, PI>;
-    static bool raised = false;  // per process; one process drives one GPU (see marl_hip.h)
-    if (!raised) {
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        raised = true;
-    }
-    static size_t seen_lds[8];
-    static int seen_occ[8], nseen = 0;
-    int occ = 0;
-    for (int i = 0; i < nseen; ++i)
-        if (seen_lds[i] == lds) occ = seen_occ[i];
-    if (!occ) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), 512, lds) != hipSuccess ||
-            occ < 1)
-            occ = 1;
-        if (nseen < 8) seen_lds[nseen] = lds, seen_occ[nseen++] = occ;
-    }
-    int res = 256 * occ / a.slabs;
+// One instantiation's launch.  The grid is what is resident at once (a persistent workgroup that has to wait for a slot
+// only lengthens the tail), never more than the bound of the plan; part_b sits behind the weight slabs actually written.
+using WgradLaunchFn = int (*)(CnnWgradArgs&, const CnnWgradPlan&, hipStream_t);
+template <class Kern>
+static int wgrad_launch_kernel(Kern kern, bool raise, CnnWgradArgs& a, const CnnWgradPlan& p, hipStream_t st) {
+    if (raise) MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(kern), 150 * 1024));
+    int res = 256 * cnn_occupancy(reinterpret_cast<const void*>(kern), p.lds_bytes) / a.slabs;
     if (res < 64) res = 64;
     if (res < a.blocks) a.blocks = res;
-    a.part_b = part_w + (size_t)a.blocks * a.cout * a.K;
+    a.part_b = a.part_w + (size_t)a.blocks * a.cout * a.K;
     prof_before(5, st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.blocks, (unsigned)a.slabs), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.blocks, (unsigned)a.slabs), dim3(512), p.lds_bytes, st, a);
     prof_after(5, st);
     MARL_LAUNCH_CHECK();
     return MARL_OK;
 }
+template <int NCT, int NKT, bool FIRST, int PD, int PI>
+static int wgrad_launch(CnnWgradArgs& a, const CnnWgradPlan& p, hipStream_t st) {
+    return wgrad_launch_kernel(cnn_wgrad_kernel<NCT, NKT, FIRST, PD, PI>, p.lds_bytes > 64 * 1024, a, p, st);
+}
+template <int NKT, int PD, int PI>
+static int wgrad3_launch(CnnWgradArgs& a, const CnnWgradPlan& p, hipStream_t st) {
+    return wgrad_launch_kernel(cnn_wgrad3_kernel<NKT, PD, PI>, true, a, p, st);
+}
+
+// Launch tables keyed by (form, sct, skt, first layer, prefetch depth).  Their entries stand in the order the kernels
+// have always been instantiated in, which is the kernels' order in the code object: reordering them moves the fat binary.
+// The instantiations of the bf16x6 form: [skt != 9][shallow prefetch] ...
+static const WgradLaunchFn kWgrad3Table[2][2] = {{wgrad3_launch<9, 4, 4>, wgrad3_launch<9, 2, 2>},
+                                                 {wgrad3_launch<5, 4, 4>, wgrad3_launch<5, 2, 2>}};
+// ... and of the fp32 form: per accumulator shape sct x skt, [deeper layer][shallow prefetch].  The first layer only
+// plans 1 x 1..3 (cnn_wgrad1_lds_floats); its entries in the other rows name the 1 x 1 kernel and are never reached.
+#define MARL_WG_ROW(CT, KT)                                                                                   \
+    {                                                                                                         \
+        CT, KT, {                                                                                             \
+            {wgrad_launch<1, (KT <= 3 ? KT : 1), true, 4, 14>, wgrad_launch<1, (KT <= 3 ? KT : 1), true, 2, 4>}, \
+            {wgrad_launch<CT, KT, false, 4, 4>, wgrad_launch<CT, KT, false, 2, 2>}                            \
+        }                                                                                                     \
+    }
+static const struct {
+    int sct, skt;
+    WgradLaunchFn fn[2][2];
+} kWgradTable[] = {MARL_WG_ROW(1, 1), MARL_WG_ROW(1, 2), MARL_WG_ROW(1, 3), MARL_WG_ROW(1, 5),
+                   MARL_WG_ROW(1, 9), MARL_WG_ROW(2, 5), MARL_WG_ROW(2, 9)};
+#undef MARL_WG_ROW
 
 int launch_cnn_wgrad(CnnWgradArgs& a, hipStream_t st) {
-    float* part_w = a.part_w;
-    size_t lds = 0;
-    const int form = cnn_wgrad_form(a, &lds);
-    if (form == 3) {  // layers with >= 16 input channels: the bf16x6 form
-        if (a.skt == 9) return a.pd == 4 ? wgrad3_launch<9, 4, 4>(a, part_w, lds, st) : wgrad3_launch<9, 2, 2>(a, part_w, lds, st);
-        return a.pd == 4 ? wgrad3_launch<5, 4, 4>(a, part_w, lds, st) : wgrad3_launch<5, 2, 2>(a, part_w, lds, st);
-    }
-    if (!form) {
+    const CnnWgradPlan p = cnn_wgrad_plan(a);
+    if (!p.form) {
         set_error("conv weight gradient: shape outside the fused kernel's range");
         return MARL_ELIMIT;
     }
-    const int sct = a.sct, skt = a.skt;
-    const bool deep = a.pd == 4;
-    // grid = what is resident at once (a persistent workgroup that has to wait for a slot only
-    // lengthens the tail); never more than the bound the scratch was sized for
-#define MARL_WG_GO(...)                                                                          \
-    {                                                                                            \
-        const int occ_ = wgrad_occupancy<__VA_ARGS__>(lds);                                      \
-        int res_ = 256 * occ_ / a.slabs;                                                         \
-        if (res_ < 64) res_ = 64;                                                                \
-        if (res_ < a.blocks) a.blocks = res_;                                                    \
-        a.part_b = part_w + (size_t)a.blocks * a.cout * a.K;                                     \
-        return wgrad_launch<__VA_ARGS__>(a, lds, st);                                            \
-    }
-#define MARL_WG(CT, KT)                                                                          \
-    if (sct == CT && skt == KT) {                                                                \
-        if (a.first) {                                                                           \
-            if (deep) MARL_WG_GO(1, (KT <= 3 ? KT : 1), true, 4, 14)                             \
-            MARL_WG_GO(1, (KT <= 3 ? KT : 1), true, 2, 4)                                        \
-        }                                                                                        \
-        if (deep) MARL_WG_GO(CT, KT, false, 4, 4)                                                \
-        MARL_WG_GO(CT, KT, false, 2, 2)                                                          \
-    }
-    MARL_WG(1, 1) MARL_WG(1, 2) MARL_WG(1, 3) MARL_WG(1, 5) MARL_WG(1, 9) MARL_WG(2, 5) MARL_WG(2, 9)
-#undef MARL_WG
-#undef MARL_WG_GO
-    set_error("conv weight gradient: no kernel for tile shape %d x %d", sct, skt);
+    const int shallow = p.pd != 4;
+    if (p.form == 3) return kWgrad3Table[p.skt != 9][shallow](a, p, st);
+    for (const auto& row : kWgradTable)
+        if (row.sct == p.sct && row.skt == p.skt) return row.fn[a.first == 0][shallow](a, p, st);
+    set_error("conv weight gradient: no kernel for tile shape %d x %d", p.sct, p.skt);
     return MARL_ELIMIT;
 }
 

@@ -921,16 +921,21 @@ struct CnnFwdArgs {
     long long* ts;  // phase timestamps of one workgroup (debug builds only)
 #endif
 };
-int cnn_fwd_supported(const CnnFwdArgs& a);
-int cnn_fwd_writes_image(const CnnFwdArgs& a);  // the launch selected for these shapes honours a.u3
-int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st);
-// what launch_cnn_fwd does with these shapes under the current knobs (host arithmetic; marl_plan_query reports it):
-// which = cnn_fwd2_kernel / cnn_fwd3_kernel instantiation 1..5 or 6 = the general cnn_fwd_kernel, rb = patches per
-// chunk, blocks = the grid (blocks < cdiv(rows, rb): workgroups walk several chunks)
+// MARL_CNN_FUSED=0 switches every fused conv launch off (read at each call: a process may change it between calls)
+bool cnn_fused_enabled();
+// What launch_cnn_fwd does with these shapes under the current knobs (host arithmetic; the one routine the launcher,
+// make_elayout, marl_plan_query and the marl_cnn_fwd* hooks ask).  which: 0 = not covered, 1..5 = the cnn_fwd2_kernel /
+// cnn_fwd3_kernel instantiation, 6 = the general cnn_fwd_kernel; rb = patches per chunk; blocks = the grid (blocks <
+// cdiv(rows, rb): workgroups walk several chunks); lds_bytes = its dynamic LDS; writes_image: the launch honours a.u3.
+// Which optional buffers exist (layer[l].cols, layer[l].wfrag) enters `which`.  Also fills the launcher-owned fields
+// of `a` for the general kernel.
 struct CnnFwdPlan {
     int which, rb, blocks;
+    size_t lds_bytes;
+    bool writes_image;
 };
-CnnFwdPlan cnn_fwd_launch_plan(const CnnFwdArgs& a);
+CnnFwdPlan cnn_fwd_plan(CnnFwdArgs& a);
+int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // Fused CNN layer backward (cnn.hip): dZ_l -> [transposed conv] -> dA_{l-1} -> [GroupNorm +
@@ -950,32 +955,21 @@ struct CnnDgradArgs {
     int rb, MT, NT, off_zin, off_da, off_perm, off_stat, off_gsum;
     int tbeg[17];  // row-tile range of wave slot s: [tbeg[s], tbeg[s + 1])
     FDiv dc4o, dc4i, dPin, dcpg, dG;
-    // optional (the launch that produces dZ_0, w0_part != null): layer 0's weight / bias gradient formed in the same
-    // launch from the dZ_0 panel and the raw patch - dZ_0 is then not written when dzin is null
-    const void* img;       // image batch [nb][c_img][H][W] float or uint8
-    const int32_t* pos;    // [rows][2] patch positions (row r reads image r % nb)
-    float* w0_part;        // [workgroups][cin * K0] partial slabs (cin = layer 0's output channels here)
-    float* w0_bpart;       // [workgroups][cin]
-    int w0;                // 1: this launch also forms layer 0's weight gradient (decides the LDS plan)
-    int img_u8, nb, c_img, H, W, cin0, f0, K0;
-    int off_pix, pix_per, cs0;  // filled by the launcher
-    FDiv dpe0, dff0, df0, dhin0;
 #ifdef MARL_KERNEL_TS
     long long* ts;
 #endif
 };
-int cnn_dgrad_supported(const CnnDgradArgs& a);
-int cnn_dgrad_blocks(const CnnDgradArgs& a);      // partial rows the launch writes (persistent grid)
-int cnn_dgrad_blocks_max(const CnnDgradArgs& a);  // its device-independent upper bound
-int cnn_dgrad_launch_rb(const CnnDgradArgs& a);   // patches per chunk of the launch (0: no plan fits)
-// what launch_cnn_dgrad does with these shapes under the current knobs (host arithmetic): rb patches per chunk, MT x NT
-// 16-wide row / column tiles of the chunk's dA panel, blocks = cnn_dgrad_blocks_max; all 0 where no plan fits
-struct CnnDgradPlanInfo {
-    int rb, MT, NT, blocks;
+// What launch_cnn_dgrad does with these shapes under the current knobs (host arithmetic): rb patches per chunk (0 = not
+// covered, then all 0), MT x NT 16-wide row / column tiles of the chunk's dA panel, lds_bytes of dynamic LDS, chunks =
+// cdiv(rows, rb) - the device-independent upper bound of the persistent grid, which sizes the partial-row scratch.
+// Also fills the launcher-owned fields of `a`.
+struct CnnDgradPlan {
+    int rb, MT, NT, chunks;
+    size_t lds_bytes;
 };
-CnnDgradPlanInfo cnn_dgrad_launch_plan(const CnnDgradArgs& a);
+CnnDgradPlan cnn_dgrad_plan(CnnDgradArgs& a);
+int cnn_dgrad_blocks(CnnDgradArgs& a);  // partial rows the launch writes: chunks trimmed to the resident workgroups
 int launch_cnn_dgrad(CnnDgradArgs& a, hipStream_t st);
-int cnn_dgrad_w0_ok(const CnnDgradArgs& a, int cin0, int f0);  // (see w0_part)
 
 // ---------------------------------------------------------------------------
 // Gradient w.r.t. the image batch (cnn.hip): transposed first convolution of dZ_0 scattered back
@@ -1022,17 +1016,20 @@ struct CnnWgradArgs {
     int pd, pi;                   // prefetch depth per thread (template shape of the launch)
     FDiv dP, dhout, dPin, dhin, dcin, dc4o, dc4i, dpe, dff, df;
 };
-int cnn_wgrad_supported(const CnnWgradArgs& a);
-int cnn_wgrad_blocks(const CnnWgradArgs& a);   // partial slabs the launch writes
-int launch_cnn_wgrad(CnnWgradArgs& a, hipStream_t st);
-// what launch_cnn_wgrad does with these shapes: form 3 = cnn_wgrad3_kernel (bf16x6), 1 = cnn_wgrad_kernel, 0 = neither;
-// rb / chunks / blocks of that form's plan (blocks: the device-independent bound the launch trims to what is resident),
-// the instantiation (sct x skt accumulator tiles per wave, prefetch depth pd / pi), the wave roles and the k-slabs
-struct CnnWgradPlanInfo {
-    int form, rb, chunks, blocks;
+// What launch_cnn_wgrad does with these shapes: form 3 = cnn_wgrad3_kernel (bf16x6), 1 = cnn_wgrad_kernel, 0 = not covered
+// (covered = the fp32 form plans: the bf16x6 form covers a subset of its shapes); rb / chunks / blocks of that form's
+// plan (blocks: the device-independent bound the launch trims to what is resident), the instantiation (sct x skt
+// accumulator tiles per wave, prefetch depth pd / pi), the wave roles, the k-slabs and the dynamic LDS.
+// blocks_bound = the larger of the two forms' workgroup counts, whatever form is chosen and whether or not the launch is
+// covered: the partial-slab scratch is sized by it, so that a knob that flips the form does not move a workspace.
+// Also fills the launcher-owned fields of `a` with the chosen form's plan.
+struct CnnWgradPlan {
+    int form, rb, chunks, blocks, blocks_bound;
     int sct, skt, tgc, tgk, ms, slabs, pd, pi;
+    size_t lds_bytes;
 };
-CnnWgradPlanInfo cnn_wgrad_launch_plan(const CnnWgradArgs& a);
+CnnWgradPlan cnn_wgrad_plan(CnnWgradArgs& a);
+int launch_cnn_wgrad(CnnWgradArgs& a, hipStream_t st);
 // out[i * ldc + j] = sum over z < splits (fixed order) of part[z * stride + i * nj + j];
 // bias (nullable): same over bpart[z * ni + i]
 int launch_slab_reduce(const float* part, int64_t stride, int splits, float* c, int ldc, int ni,

@@ -324,13 +324,20 @@ struct ELayout {
     size_t RED, red_floats;  // scratch of the deferred-reduction queue (sum over every use)
     size_t part_floats, tns_bytes, loss_floats;
     size_t total;
-    // which fused CNN kernels cover this shape (decides what is kept for backward)
-    bool fused_fwd;                          // one launch for the whole extractor
-    bool wgrad_ok[MARL_MAX_CNN_LAYERS];      // weight gradient from the activations (no im2col rows)
-    bool dgrad_ok[MARL_MAX_CNN_LAYERS];      // fused transposed conv + GroupNorm backward (l >= 1)
+    // what the fused CNN launchers do with this shape: the plans of their own routines (cnn.hip), which also decide
+    // what is kept for backward
+    CnnFwdPlan fwd;                            // which != 0: one launch for the whole extractor (plan of cnn_fwd_probe)
+    CnnWgradPlan wgrad[MARL_MAX_CNN_LAYERS];   // form != 0: weight gradient from the activations (no im2col rows)
+    CnnDgradPlan dgrad[MARL_MAX_CNN_LAYERS];   // rb != 0: fused transposed conv + GroupNorm backward (l >= 1)
+    // forward keeps a layer's im2col rows only for a weight gradient the activation-based kernel does not cover
+    bool keeps_cols[MARL_MAX_CNN_LAYERS];
 };
 
-static CnnFwdArgs cnn_fwd_shape(const Dims& d) {
+// The arguments launch_cnn_fwd is planned with: the shapes, and which optional buffers exist - the im2col rows kept for
+// backward (keeps_cols: they rule the cnn_fwd2 / cnn_fwd3 instantiations out) and the fragment-order weight copies
+// (cnn_fwd3 needs them).  Only their presence matters to cnn_fwd_plan; cnn_fwd_args gives the launch the same pattern.
+static CnnFwdArgs cnn_fwd_probe(const Dims& d, const WLayout& w, const bool* keeps_cols) {
+    static float here;
     CnnFwdArgs a{};
     a.rows = d.R;
     a.nb = d.nb;
@@ -340,14 +347,11 @@ static CnnFwdArgs cnn_fwd_shape(const Dims& d) {
     a.f = d.f;
     a.L = d.L;
     for (int l = 0; l < d.L; ++l)
-        a.layer[l] = CnnFwdLayer{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+        a.layer[l] = CnnFwdLayer{nullptr, nullptr, nullptr, nullptr, keeps_cols[l] ? &here : nullptr, nullptr, nullptr,
                                  d.ch[l], d.ch[l + 1], d.grp[l], d.hw[l], d.hw[l + 1], d.P[l], d.K[l],
-                                 d.ldk[l], nullptr};
+                                 d.ldk[l], w.wf[4 * l] ? &here : nullptr};
     return a;
 }
-// forward keeps a layer's im2col rows only for a weight gradient the activation-based kernel does not cover
-// (step_cnn fills CnnFwdLayer::cols by this; marl_plan_query asks the same question)
-static bool cnn_fwd_keeps_cols(const bool* wgrad_ok, int train, int l) { return train != 0 && !wgrad_ok[l]; }
 static CnnWgradArgs cnn_wgrad_shape(const Dims& d, int l) {
     CnnWgradArgs g{};
     g.rows = d.NR;
@@ -375,18 +379,6 @@ static CnnDgradArgs cnn_dgrad_shape(const Dims& d, int l) {
     g.P = d.P[l];
     g.Pin = d.P[l - 1];
     g.G = d.grp[l - 1];
-    // the launch that produces dZ_0 also forms layer 0's weight gradient when the shapes allow it (cnn.hip)
-    if (l == 1 && cnn_dgrad_w0_ok(g, d.ch[0], d.f) && cnn_wgrad_supported(cnn_wgrad_shape(d, 0))) {
-        g.w0 = 1;
-        g.cin0 = d.ch[0];
-        g.f0 = d.f;
-        g.K0 = d.K[0];
-        g.nb = d.nb;
-        g.c_img = d.c_img;
-        g.H = d.H;
-        g.W = d.W;
-        if (!cnn_dgrad_supported(g)) g.w0 = 0;  // (the pixel images do not fit next to the panels: separate launches)
-    }
     return g;
 }
 
@@ -406,7 +398,7 @@ static CnnDimgArgs cnn_dimg_shape(const Dims& d) {
     return a;
 }
 
-static void make_elayout(const Dims& d, int train, ELayout& e) {
+static void make_elayout(const Dims& d, const WLayout& w, int train, ELayout& e) {
     Bump b;
     const size_t R = (size_t)d.R, NR = (size_t)d.NR, S1 = (size_t)d.ns + 1;
     e.POS = b.take(S1 * R * 2);
@@ -427,22 +419,34 @@ static void make_elayout(const Dims& d, int train, ELayout& e) {
         s.off = b.take(n);
         s.stride = 0;
     };
-    e.fused_fwd = cnn_fwd_supported(cnn_fwd_shape(d)) != 0;
-    for (int l = 0; l < MARL_MAX_CNN_LAYERS; ++l) e.wgrad_ok[l] = e.dgrad_ok[l] = false;
-    for (int l = 0; l < d.L; ++l) {
-        e.wgrad_ok[l] = cnn_wgrad_supported(cnn_wgrad_shape(d, l)) != 0;
-        if (l > 0) e.dgrad_ok[l] = cnn_dgrad_supported(cnn_dgrad_shape(d, l)) != 0;
+    for (int l = 0; l < MARL_MAX_CNN_LAYERS; ++l) {
+        e.wgrad[l] = CnnWgradPlan{};
+        e.dgrad[l] = CnnDgradPlan{};
+        if (l < d.L) {
+            CnnWgradArgs wg = cnn_wgrad_shape(d, l);
+            e.wgrad[l] = cnn_wgrad_plan(wg);
+        }
+        if (l > 0 && l < d.L) {
+            CnnDgradArgs dg = cnn_dgrad_shape(d, l);
+            e.dgrad[l] = cnn_dgrad_plan(dg);
+        }
+        e.keeps_cols[l] = l < d.L && train != 0 && !e.wgrad[l].form;
     }
+    {
+        CnnFwdArgs probe = cnn_fwd_probe(d, w, e.keeps_cols);
+        e.fwd = cnn_fwd_plan(probe);
+    }
+    const bool fused_fwd = e.fwd.which != 0;
     for (int l = 0; l < d.L; ++l) {
         // im2col rows: kept for every step only when the weight gradient needs them (shapes the
         // activation-based kernel does not cover); one scratch slice for the unfused forward
-        if (train && !e.wgrad_ok[l])
+        if (e.keeps_cols[l])
             per(e.COLS[l], R * d.P[l] * d.ldk[l]);
-        else if (!e.fused_fwd)
+        else if (!fused_fwd)
             once(e.COLS[l], R * d.P[l] * d.ldk[l]);
         per(e.Z[l], R * d.P[l] * d.ch[l + 1]);
         per(e.GST[l], R * d.grp[l] * 2);
-        if (l + 1 < d.L && !e.fused_fwd) once(e.A[l], R * d.P[l] * d.ch[l + 1]);
+        if (l + 1 < d.L && !fused_fwd) once(e.A[l], R * d.P[l] * d.ch[l + 1]);
     }
     per(e.U, R * d.ld_nin);
     per(e.MBAR, R * d.ld_nm);
@@ -517,8 +521,8 @@ static void make_elayout(const Dims& d, int train, ELayout& e) {
         for (int l = 0; l < d.L; ++l) {
             e.DZ[l] = b.take(NR * d.P[l] * d.ch[l + 1]);
             // only the unfused layer backward materialises dCOLS_l and dA_{l-1}
-            e.DCOLS[l] = (l > 0 && !e.dgrad_ok[l]) ? b.take(NR * d.P[l] * d.ldk[l]) : 0;
-            e.DA[l] = (l + 1 < d.L && !e.dgrad_ok[l + 1]) ? b.take(NR * d.P[l] * d.ch[l + 1]) : 0;
+            e.DCOLS[l] = (l > 0 && !e.dgrad[l].rb) ? b.take(NR * d.P[l] * d.ldk[l]) : 0;
+            e.DA[l] = (l + 1 < d.L && !e.dgrad[l + 1].rb) ? b.take(NR * d.P[l] * d.ch[l + 1]) : 0;
         }
         // scratch sizes: maxima over every use
         size_t part = 0, tns = 0, red = 0;
@@ -541,7 +545,7 @@ static void make_elayout(const Dims& d, int train, ELayout& e) {
         upd_part(ln_bwd_blocks(r, d.n_m), d.n_m);
         for (int l = 0; l < d.L; ++l) upd_part(gn_bwd_blocks(nr, d.ch[l + 1]), d.ch[l + 1]);
         for (int l = 1; l < d.L; ++l)  // fused layer backward: one partial row per workgroup
-            if (e.dgrad_ok[l]) upd_part(cnn_dgrad_blocks_max(cnn_dgrad_shape(d, l)), d.ch[l]);
+            if (e.dgrad[l].rb) upd_part(e.dgrad[l].chunks, d.ch[l]);
         upd_tn(d.nC, d.nlb, nr);
         upd_tn(d.nlb, d.n_b, nr);
         upd_tn(1, d.nla, nr);
@@ -570,19 +574,9 @@ static void make_elayout(const Dims& d, int train, ELayout& e) {
                 }
         }
         upd_tn(d.n_d, 2, nr);
-        if (d.L > 1 && e.dgrad_ok[1]) {  // layer 0's weight gradient out of the dZ_0 launch: one small slab per workgroup
-            const CnnDgradArgs g1 = cnn_dgrad_shape(d, 1);
-            if (g1.w0) {
-                int64_t nb_ = cnn_dgrad_blocks_max(g1);
-                if (nb_ > 2048) nb_ = 2048;  // (persistent grid: occupancy <= 8 workgroups x 256 CUs)
-                const size_t v = (size_t)nb_ * ((size_t)d.ch[1] * d.K[0] + d.ch[1]) * sizeof(float);
-                tns = v > tns ? v : tns;
-                red += v / sizeof(float) + 64 * ((size_t)d.ch[1] * (d.K[0] + 1)) + 192;
-            }
-        }
         for (int l = 0; l < d.L; ++l) {
-            if (e.wgrad_ok[l]) {  // per-workgroup partial slabs of the activation-based kernel
-                const size_t v = (size_t)cnn_wgrad_blocks(cnn_wgrad_shape(d, l)) *
+            if (e.wgrad[l].form) {  // per-workgroup partial slabs of the activation-based kernel
+                const size_t v = (size_t)e.wgrad[l].blocks_bound *
                                  ((size_t)d.ch[l + 1] * d.K[l] + d.ch[l + 1]) * sizeof(float);
                 tns = v > tns ? v : tns;
                 red += v / sizeof(float) + 64 * ((size_t)d.ch[l + 1] * (d.K[l] + 1)) + 192;
@@ -776,10 +770,7 @@ static Plan make_plan(const Dims& d, const WLayout& w, const ELayout& e, const I
     // launch: position embedding) also write its image when all of them are on the path and the column
     // ranges keep 8-byte image pieces whole; else (and for step 0, whose embedding comes from the
     // stand-alone kernel) one image pass over U[t] runs ahead of the LSTM launch
-    static float here;  // (only the presence of the fragment-order weight copies the AidCnn kernels ask for matters)
-    CnnFwdArgs probe = cnn_fwd_shape(d);
-    for (int l = 0; l < d.L; ++l) probe.layer[l].wfrag = w.wf[4 * l] ? &here : nullptr;
-    p.u3_by_producers = p.g3_lstm && e.fused_fwd && cnn_fwd_writes_image(probe) && p.panels &&
+    p.u3_by_producers = p.g3_lstm && e.fwd.writes_image && p.panels &&
                         ((d.nf | d.n_mo | d.n_d) & 3) == 0 &&
                         // (the producers write exactly nin columns: a K pad of the last 16-deep step would be
                         // whatever the workspace held - only the stand-alone image pass zeroes it)
@@ -801,7 +792,7 @@ static int make_ctx(const marl_config* cfg, const void* wws, size_t wbytes, void
         return MARL_EINVAL;
     }
     make_wlayout(c.d, c.w);
-    make_elayout(c.d, train, c.e);
+    make_elayout(c.d, c.w, train, c.e);
     if (wbytes < c.w.total * sizeof(float) || ebytes < c.e.total * sizeof(float)) {
         set_error("workspace too small for the current configuration / tuning knobs: weights %zu of %zu "
                   "bytes, episode %zu of %zu bytes (ask marl_workspace_sizes again)", wbytes,
@@ -897,7 +888,7 @@ static CnnFwdArgs cnn_fwd_args(const Dims& d, const WLayout& w, const float* W, 
 static int step_cnn(const Ctx& c, int t, const StepIn& in) {
     const Dims& d = c.d;
     hipStream_t st = c.st;
-    if (c.e.fused_fwd) {
+    if (c.e.fwd.which) {
         // one fused launch for the whole extractor when the shapes allow it
         CnnFwdIo io;
         io.img = in.img;
@@ -906,7 +897,7 @@ static int step_cnn(const Ctx& c, int t, const StepIn& in) {
         io.img_u8 = in.img_u8;
         io.rows = d.R;
         for (int l = 0; l < d.L; ++l) {
-            io.cols[l] = cnn_fwd_keeps_cols(c.e.wgrad_ok, c.train, l) ? c.at(c.e.COLS[l], t) : nullptr;
+            io.cols[l] = c.e.keeps_cols[l] ? c.at(c.e.COLS[l], t) : nullptr;
             io.z[l] = c.train ? c.at(c.e.Z[l], t) : nullptr;
             io.gst[l] = c.train ? c.at(c.e.GST[l], t) : nullptr;
         }
@@ -2119,14 +2110,13 @@ static int bwd_conv_wgrad(const BwdState& s, int l, const float* dz, const void*
         return MARL_EINVAL;
     }
     // per-workgroup slabs; the launcher places part_b behind the weight slabs
-    w.part_w = slab_scratch(c, (size_t)cnn_wgrad_blocks(w) * ((size_t)co * d.K[l] + co));
+    w.part_w = slab_scratch(c, (size_t)c.e.wgrad[l].blocks_bound * ((size_t)co * d.K[l] + co));
     MARL_TRY(launch_cnn_wgrad(w, c.st));
     return slab_reduce(c, w.part_w, w.part_b, w.blocks, co, d.K[l], 4 * l, s.grads[4 * l + 1]);
 }
 
-// the extractor backward from dU[:, :nf], last layer first; leaves dZ_0 in the workspace unless layer 0's weight
-// gradient rode along with the launch that produced it
-static int bwd_cnn_layers(const BwdState& s, const void* img, int img_u8, const float* d_img) {
+// the extractor backward from dU[:, :nf], last layer first; leaves dZ_0 in the workspace
+static int bwd_cnn_layers(const BwdState& s, const void* img, int img_u8) {
     const Ctx& c = s.c;
     const Dims& d = c.d;
     float* const* grads = s.grads;
@@ -2136,7 +2126,6 @@ static int bwd_cnn_layers(const BwdState& s, const void* img, int img_u8, const 
     int64_t ldda = d.ld_nin;
     int chw = 1;
     bool have_dz = false;  // DZ[l] already produced by the fused layer backward of layer l+1
-    bool w0_done = false;  // ... which also formed layer 0's weight gradient (dZ_0 never left LDS)
     for (int l = d.L - 1; l >= 0; --l) {
         const int co = d.ch[l + 1];
         const int64_t rows = NR * d.P[l];
@@ -2151,9 +2140,7 @@ static int bwd_cnn_layers(const BwdState& s, const void* img, int img_u8, const 
                                           grads[4 * l + 3], 0, st, q));
         }
         have_dz = false;
-        if (l == 0 && w0_done) {
-            // (layer 0's weight and bias gradient came out of the launch that produced dZ_0)
-        } else if (c.e.wgrad_ok[l]) {
+        if (c.e.wgrad[l].form) {
             MARL_TRY(bwd_conv_wgrad(s, l, dz, img, img_u8));
         } else {
             MARL_TRY(tn(c, dz, co, c.at(c.e.COLS[l], 0), d.ldk[l], 4 * l, co, d.K[l], rows, grads[4 * l + 1]));
@@ -2169,28 +2156,13 @@ static int bwd_cnn_layers(const BwdState& s, const void* img, int img_u8, const 
         g.gamma = c.wp(4 * (l - 1) + 2);
         g.beta = c.wp(4 * (l - 1) + 3);
         g.dzin = c.at(c.e.DZ[l - 1]);
-        if (g.w0 && !img) g.w0 = 0;  // (the step API has no image batch: layer 0 takes the separate launch)
-        if (d_img) g.w0 = 0;         // (the image gradient reads dZ_0 from the workspace)
-        if (c.e.dgrad_ok[l] && (size_t)cnn_dgrad_blocks(g) * 2 * d.ch[l] <= c.e.part_floats) {
+        const int nblk = c.e.dgrad[l].rb ? cnn_dgrad_blocks(g) : 0;  // (plan + what is resident on this device)
+        if (c.e.dgrad[l].rb && (size_t)nblk * 2 * d.ch[l] <= c.e.part_floats) {
             RedQueue* q;
-            const int nblk = cnn_dgrad_blocks(g);
             g.part = part_scratch(c, nblk, d.ch[l], 0, q);
-            const int co0 = d.ch[l], k0 = d.K[0];
-            if (g.w0) {  // + layer 0's weight gradient: per-workgroup slabs (tiny: 448 floats each at RESISC)
-                g.w0_part = slab_scratch(c, (size_t)nblk * ((size_t)co0 * k0 + co0));
-                g.w0_bpart = g.w0_part + (size_t)nblk * co0 * k0;
-                g.img = img;
-                g.img_u8 = img_u8;
-                g.pos = c.POSs(0);
-                g.dzin = nullptr;  // dZ_0 stays in LDS
-            }
             MARL_TRY(launch_cnn_dgrad(g, st));
             MARL_TRY(launch_reduce_affine(g.part, nblk, d.ch[l], grads[4 * (l - 1) + 2], grads[4 * (l - 1) + 3], 0,
                                           st, q));
-            if (g.w0) {
-                MARL_TRY(slab_reduce(c, g.w0_part, g.w0_bpart, nblk, co0, k0, 0, grads[1]));
-                w0_done = true;
-            }
             have_dz = true;
             continue;
         }
@@ -2231,7 +2203,7 @@ static int bwd_inputs(const BwdState& s, const void* img, int img_u8, float* d_i
                     c.at(c.e.STPOS, 0), MARL_P_POS_LNW, MARL_P_POS_LNB, NR, d.n_d, grads, 0,
                     c.at(c.e.DZPOS), d.ld_nd));
     MARL_TRY(tn(c, c.at(c.e.DZPOS), d.ld_nd, c.at(c.e.NPOS, 0), 4, MARL_P_POS_W, d.n_d, 2, NR, grads[MARL_P_POS_B]));
-    MARL_TRY(bwd_cnn_layers(s, img, img_u8, d_img));
+    MARL_TRY(bwd_cnn_layers(s, img, img_u8));
     if (d_img) {  // dL/d(img): dZ_0 (left in the workspace by the layer loop) back through the crops of every step
         CnnDimgArgs a = cnn_dimg_shape(d);
         a.dz0 = c.at(c.e.DZ[0]);
@@ -2305,7 +2277,7 @@ int marl_workspace_sizes(const marl_config* cfg, int train, size_t* wbytes, size
     WLayout w;
     make_wlayout(d, w);
     ELayout e;
-    make_elayout(d, train, e);
+    make_elayout(d, w, train, e);
     if (wbytes) *wbytes = w.total * sizeof(float);
     if (ebytes) *ebytes = e.total * sizeof(float);
     return MARL_OK;
@@ -2613,7 +2585,7 @@ int marl_comm_grad(const marl_config* cfg, const void* weights_ws, size_t weight
     WLayout w;
     make_wlayout(d, w);
     ELayout e;
-    make_elayout(d, 1, e);
+    make_elayout(d, w, 1, e);
     if (weights_ws_bytes < w.total * sizeof(float) || ws_bytes < e.total * sizeof(float)) {
         set_error("comm_grad: workspace too small for the current configuration / tuning knobs: weights %zu of %zu "
                   "bytes, episode %zu of %zu bytes", weights_ws_bytes, w.total * sizeof(float), ws_bytes,
@@ -2717,8 +2689,10 @@ static int loss_entry(const marl_config* cfg, void* episode_ws, size_t episode_w
         set_error("%s: bad argument", who);
         return MARL_EINVAL;
     }
+    WLayout w;
+    make_wlayout(d, w);
     ELayout e;
-    make_elayout(d, 1, e);
+    make_elayout(d, w, 1, e);
     if (episode_ws_bytes < e.total * sizeof(float)) {
         set_error("%s: episode workspace too small (%zu of %zu bytes, training layout)", who, episode_ws_bytes,
                   e.total * sizeof(float));
@@ -2988,8 +2962,10 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
                       int64_t* offset_floats, int* ld) {
     Dims d;
     MARL_TRY(make_dims(cfg, d));
+    WLayout w;
+    make_wlayout(d, w);
     ELayout e;
-    make_elayout(d, train, e);
+    make_elayout(d, w, train, e);
     if (!name || !offset_floats || !ld || t < 0 || t > d.ns) return MARL_EINVAL;
     const size_t R = (size_t)d.R;
     const int ts = train ? t : 0;
@@ -3000,8 +2976,6 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
     };
     if (!strncmp(name, "WP", 2) || !strncmp(name, "WT", 2)) {  // weights workspace: packed / transposed copy of parameter <idx>
         const int idx = atoi(name + 2);
-        WLayout w;
-        make_wlayout(d, w);
         if (name[2] == 'F') {  // WPF<idx> / WTF<idx>: its fragment-order copy (ld: the 16-deep groups per tile)
             const int fi = atoi(name + 3);
             const size_t off = fi >= 0 && fi < MARL_NPARAMS ? (name[1] == 'P' ? w.wpf[fi] : w.wtf[fi]) : 0;
@@ -3025,7 +2999,7 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
     if (!strcmp(name, "MSG")) return set(e.MSG + (size_t)t * R * d.ld_nm, d.ld_nm);
     if (!strcmp(name, "PROBS")) return set(e.PROBS + (size_t)t * R * d.nA, d.nA);
     if (!strcmp(name, "COLS0")) {
-        if (e.fused_fwd && (!train || e.wgrad_ok[0])) {
+        if (e.fwd.which && !e.keeps_cols[0]) {
             set_error("COLS0 is not materialised for this shape (fused CNN kernels)");
             return MARL_EINVAL;
         }
@@ -3050,7 +3024,7 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     WLayout w;
     make_wlayout(d, w);
     ELayout e;
-    make_elayout(d, train, e);
+    make_elayout(d, w, train, e);
     const Plan plan = make_plan(d, w, e, g_installed);
     if (!strcmp(key, "g3")) *value = e.g3;
     else if (!strcmp(key, "g3_model")) *value = g3_model_ok(d);
@@ -3062,25 +3036,13 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
         *value = plan.g3_tn && g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) && g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR);
     else if (!strcmp(key, "g3_tn_pipe")) *value = plan.g3_tn_pipe;  // only where the image weight gradients run
     else if (!strcmp(key, "wgrad3")) {  // a conv weight gradient of this model runs on the bf16 pipe (cin >= 16)
-        ELayout e1;
-        make_elayout(d, 1, e1);
         *value = 0;
         for (int l = 0; l < d.L; ++l)
-            if (e1.wgrad_ok[l] && cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l)).form == 3) *value = 1;
+            if (e.wgrad[l].form == 3) *value = 1;
     }
     // what the CNN launchers do with this shape (their own routines, host arithmetic only; see marl_hip.h)
     else if (!strncmp(key, "cnn_fwd", 7)) {
-        CnnFwdPlan p{};  // unfused path: all 0
-        if (e.fused_fwd) {
-            // the shapes of step_cnn's launch: which optional buffers exist decides the instantiation
-            static float here;
-            CnnFwdArgs a = cnn_fwd_shape(d);
-            for (int l = 0; l < d.L; ++l) {
-                a.layer[l].cols = cnn_fwd_keeps_cols(e.wgrad_ok, train, l) ? &here : nullptr;
-                a.layer[l].wfrag = w.wf[4 * l] ? &here : nullptr;
-            }
-            p = cnn_fwd_launch_plan(a);
-        }
+        const CnnFwdPlan& p = e.fwd;  // the plan of step_cnn's launch (unfused path: all 0)
         if (!strcmp(key, "cnn_fwd")) *value = p.which;
         else if (!strcmp(key, "cnn_fwd_rb")) *value = p.rb;
         else if (!strcmp(key, "cnn_fwd_blocks")) *value = p.blocks;
@@ -3103,13 +3065,11 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
             set_error("unknown plan key %s (layers %d..%d)", key, dg ? 1 : 0, d.L - 1);
             return MARL_EINVAL;
         }
-        ELayout e1;
-        make_elayout(d, 1, e1);
+        // (the backward plans do not depend on `train`: the layout at hand answers for the training one)
         if (dg)
-            *value = e1.dgrad_ok[l] ? cnn_dgrad_launch_rb(cnn_dgrad_shape(d, l)) : 0;
+            *value = e.dgrad[l].rb;
         else {
-            CnnWgradPlanInfo p{};
-            if (e1.wgrad_ok[l]) p = cnn_wgrad_launch_plan(cnn_wgrad_shape(d, l));
+            const CnnWgradPlan& p = e.wgrad[l];
             *value = field == 1 ? p.rb : field == 2 ? p.chunks : p.blocks;
         }
     }
@@ -3213,8 +3173,8 @@ static CnnWgradArgs wgrad_api_args(int64_t rows, int nb, int c_img, int h, int w
 }
 
 size_t marl_cnn_wgrad_scratch(int64_t rows, int cin, int cout, int hin, int groups, int first) {
-    const CnnWgradArgs g = wgrad_api_args(rows, 1, cin, hin + 1, hin + 1, cin, cout, hin, groups, first);
-    return (size_t)cnn_wgrad_blocks(g) * ((size_t)cout * 9 * cin + cout) * sizeof(float);
+    CnnWgradArgs g = wgrad_api_args(rows, 1, cin, hin + 1, hin + 1, cin, cout, hin, groups, first);
+    return (size_t)cnn_wgrad_plan(g).blocks_bound * ((size_t)cout * 9 * cin + cout) * sizeof(float);
 }
 
 int marl_cnn_wgrad(const float* dz, const void* img, int img_u8, const int32_t* pos,
@@ -3229,11 +3189,12 @@ int marl_cnn_wgrad(const float* dz, const void* img, int img_u8, const int32_t* 
         return MARL_EINVAL;
     }
     CnnWgradArgs g = wgrad_api_args(rows, nb, c_img, h, w, cin, cout, hin, groups, first);
-    if (!cnn_wgrad_supported(g)) {
+    const CnnWgradPlan plan = cnn_wgrad_plan(g);
+    if (!plan.form) {
         set_error("cnn_wgrad: shape outside the kernel's range (cin %d cout %d hin %d)", cin, cout, hin);
         return MARL_ELIMIT;
     }
-    if (scratch_bytes < marl_cnn_wgrad_scratch(rows, cin, cout, hin, groups, first)) {
+    if (scratch_bytes < (size_t)plan.blocks_bound * ((size_t)cout * 9 * cin + cout) * sizeof(float)) {
         set_error("cnn_wgrad: scratch too small");
         return MARL_ESIZE;
     }
@@ -3326,14 +3287,15 @@ static CnnDgradArgs dgrad_api_args(int64_t rows, int cin, int cout, int hin, int
     g.G = groups;
     return g;
 }
-static bool dgrad_api_ok(int64_t rows, int cin, int cout, int hin, int groups) {
-    return rows >= 1 && cin >= 1 && cout >= 1 && hin >= 1 && groups >= 1 &&
-           cnn_dgrad_supported(dgrad_api_args(rows, cin, cout, hin, groups)) != 0;
+// the plan for a caller's raw shapes (rb 0: bad sizes, or not covered)
+static CnnDgradPlan dgrad_api_plan(int64_t rows, int cin, int cout, int hin, int groups) {
+    if (rows < 1 || cin < 1 || cout < 1 || hin < 1 || groups < 1) return CnnDgradPlan{};
+    CnnDgradArgs g = dgrad_api_args(rows, cin, cout, hin, groups);
+    return cnn_dgrad_plan(g);
 }
 
 size_t marl_cnn_dgrad_scratch(int64_t rows, int cin, int cout, int hin, int groups) {
-    if (!dgrad_api_ok(rows, cin, cout, hin, groups)) return 0;
-    return (size_t)cnn_dgrad_blocks_max(dgrad_api_args(rows, cin, cout, hin, groups)) * 2 * cin * sizeof(float);
+    return (size_t)dgrad_api_plan(rows, cin, cout, hin, groups).chunks * 2 * cin * sizeof(float);
 }
 
 int marl_cnn_dgrad(const float* dz, const float* wt, int ldwt, const float* zin, const float* gst,
@@ -3346,7 +3308,7 @@ int marl_cnn_dgrad(const float* dz, const float* wt, int ldwt, const float* zin,
         set_error("marl_cnn_dgrad: null or misaligned pointer, or bad size");
         return MARL_EINVAL;
     }
-    if (!dgrad_api_ok(rows, cin, cout, hin, groups)) {
+    if (!dgrad_api_plan(rows, cin, cout, hin, groups).rb) {
         set_error("marl_cnn_dgrad: shape outside the fused kernel's range (cin %d cout %d hin %d groups %d)", cin, cout,
                   hin, groups);
         return MARL_ELIMIT;
@@ -3383,16 +3345,15 @@ int marl_cnn_bwd_plan(int64_t rows, int cin, int cout, int hin, int groups, int 
     }
     *out = marl_cnn_bwd_plan_info{};
     // (the shapes marl_cnn_wgrad / marl_cnn_wgrad_scratch plan with: the image's size does not enter the plan)
-    const CnnWgradArgs w = wgrad_api_args(rows, 1, cin, hin + 1, hin + 1, cin, cout, hin, groups, first != 0);
-    if (cnn_wgrad_supported(w)) {
-        const CnnWgradPlanInfo p = cnn_wgrad_launch_plan(w);
+    CnnWgradArgs w = wgrad_api_args(rows, 1, cin, hin + 1, hin + 1, cin, cout, hin, groups, first != 0);
+    if (const CnnWgradPlan p = cnn_wgrad_plan(w); p.form) {
         out->wg_form = p.form, out->wg_rb = p.rb, out->wg_chunks = p.chunks, out->wg_blocks = p.blocks;
         out->wg_sct = p.sct, out->wg_skt = p.skt, out->wg_tgc = p.tgc, out->wg_tgk = p.tgk, out->wg_ms = p.ms;
         out->wg_slabs = p.slabs, out->wg_pd = p.pd, out->wg_pi = p.pi;
     }
-    if (!first && dgrad_api_ok(rows, cin, cout, hin, groups)) {
-        const CnnDgradPlanInfo p = cnn_dgrad_launch_plan(dgrad_api_args(rows, cin, cout, hin, groups));
-        out->dg_supported = 1, out->dg_rb = p.rb, out->dg_mt = p.MT, out->dg_nt = p.NT, out->dg_blocks = p.blocks;
+    if (!first) {
+        const CnnDgradPlan p = dgrad_api_plan(rows, cin, cout, hin, groups);
+        out->dg_supported = p.rb != 0, out->dg_rb = p.rb, out->dg_mt = p.MT, out->dg_nt = p.NT, out->dg_blocks = p.chunks;
     }
     return MARL_OK;
 }
@@ -3418,21 +3379,15 @@ int marl_cnn_fwd_plan(const marl_config* cfg, int train, int64_t rows, marl_cnn_
     *out = marl_cnn_fwd_plan_info{};
     Dims d;
     MARL_TRY(cnn_fwd_api_dims(cfg, rows, d));
-    ELayout e;
-    make_elayout(d, train, e);  // (fused_fwd and wgrad_ok as every entry of the episode decides them)
-    if (!e.fused_fwd) return MARL_OK;
     WLayout w;
     make_wlayout(d, w);
-    static float here;
-    CnnFwdArgs a = cnn_fwd_shape(d);
-    for (int l = 0; l < d.L; ++l) {
-        out->keeps_cols[l] = cnn_fwd_keeps_cols(e.wgrad_ok, train, l);
-        a.layer[l].cols = out->keeps_cols[l] ? &here : nullptr;
-        a.layer[l].wfrag = w.wf[4 * l] ? &here : nullptr;
-    }
-    const CnnFwdPlan p = cnn_fwd_launch_plan(a);
+    ELayout e;
+    make_elayout(d, w, train, e);  // (the forward plan and what it keeps as every entry of the episode decides them)
+    const CnnFwdPlan& p = e.fwd;
+    if (!p.which) return MARL_OK;
+    for (int l = 0; l < d.L; ++l) out->keeps_cols[l] = e.keeps_cols[l];
     out->fused = 1, out->which = p.which, out->rb = p.rb, out->blocks = p.blocks;
-    out->writes_image = cnn_fwd_writes_image(a);
+    out->writes_image = p.writes_image;
     return MARL_OK;
 }
 
@@ -3444,7 +3399,13 @@ int marl_cnn_fwd(const marl_config* cfg, const void* weights_ws, size_t weights_
     }
     Dims d;
     MARL_TRY(cnn_fwd_api_dims(cfg, io->rows, d));
-    if (!cnn_fwd_supported(cnn_fwd_shape(d))) {  // (the question make_elayout asks: ELayout::fused_fwd)
+    WLayout w;
+    make_wlayout(d, w);
+    bool keeps_cols[MARL_MAX_CNN_LAYERS] = {};
+    for (int l = 0; l < d.L; ++l) keeps_cols[l] = io->cols[l] != nullptr;
+    CnnFwdArgs probe = cnn_fwd_probe(d, w, keeps_cols);  // (the launch below has the same optional buffers)
+    const CnnFwdPlan plan = cnn_fwd_plan(probe);
+    if (!plan.which) {
         set_error("marl_cnn_fwd: the fused forward does not cover this model (window %d, %d layers)", d.f, d.L);
         return MARL_ELIMIT;
     }
@@ -3457,8 +3418,6 @@ int marl_cnn_fwd(const marl_config* cfg, const void* weights_ws, size_t weights_
         set_error("marl_cnn_fwd: null or misaligned pointer, or bad size");
         return MARL_EINVAL;
     }
-    WLayout w;
-    make_wlayout(d, w);
     if (weights_ws_bytes < w.total * sizeof(float)) {
         set_error("marl_cnn_fwd: weights workspace too small (%zu of %zu bytes)", weights_ws_bytes,
                   w.total * sizeof(float));
@@ -3477,7 +3436,7 @@ int marl_cnn_fwd(const marl_config* cfg, const void* weights_ws, size_t weights_
     f.u3_row0 = io->u3_row0;
     f.u3_steps = io->u3_steps;
     CnnFwdArgs a = cnn_fwd_args(d, w, static_cast<const float*>(weights_ws), f);
-    if (io->u3 && !cnn_fwd_writes_image(a)) {
+    if (io->u3 && !plan.writes_image) {
         set_error("marl_cnn_fwd: the kernel selected for this launch does not write the image of U");
         return MARL_EINVAL;
     }
