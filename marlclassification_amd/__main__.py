@@ -106,6 +106,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="device-side augmentation of the training split, fused into the batch gather: a comma-separated "
                         "list of hflip, vflip, rot90, d4, shift:T[:reflect|zero], erase:S[:p] (rot90 / d4 need square "
                         "images; default: none)")
+    t.add_argument("--mix", type=_arg(_mix_arg), default=None, dest="mix", metavar="SPEC",
+                   help="CutMix / Mixup of the training split, fused into the batch gather: a comma-separated list of "
+                        "cutmix[:alpha[:p]] and mixup[:alpha[:p]] (lam ~ Beta(alpha, alpha), per-image probability p; "
+                        "defaults 1 and 0.5, the probabilities sum to at most 1); the loss takes the mixed target "
+                        "distributions (default: none)")
     t.add_argument("--class-weights", type=_arg(parse_class_weights), default=None, dest="class_weights",
                    metavar="balanced|FILE.npy|w0,w1,...",
                    help="class weights of the vote error: balanced = N / (nb_class * n_c) from the whole training "
@@ -181,6 +186,12 @@ def _arg(parse):
 
 def _augment_arg(text: str) -> str:
     return parse_augment(text).spec
+
+
+def _mix_arg(text: str) -> str:
+    from .mix import parse as parse_mix
+
+    return parse_mix(text).spec
 
 
 def _tta_arg(text: str) -> str:
@@ -267,7 +278,7 @@ def main(argv=None) -> None:
             gamma=args.gamma, entropy_coef=args.entropy_coef, ppo_epochs=args.ppo_epochs,
             ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, max_grad_norm=args.max_grad_norm,
             learn_comm=args.learn_comm, comm_lr=args.comm_lr,
-            temperature=args.temperature, explore_eps=args.explore_eps, augment=args.augment,
+            temperature=args.temperature, explore_eps=args.explore_eps, augment=args.augment, mix=args.mix,
             class_weights=args.class_weights, label_smoothing=args.label_smoothing, error_steps=args.error_steps,
             weight_rewards=args.weight_rewards,
             weight_decay=args.weight_decay, decay_all=args.decay_all, lr_groups=args.lr_groups,

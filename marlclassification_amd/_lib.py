@@ -92,12 +92,16 @@ EXPLORE_ENTRIES = ("marl_policy_explore",)
 AUGMENT_ENTRIES = ("marl_batch_augment", "marl_batch_augment_plan")
 # ... and the options of the vote error and the rewards that include/marl_hip_classloss.h declares (likewise)
 CLASSLOSS_ENTRIES = ("marl_class_loss",)
+# ... and the target distributions of the same two kernels that include/marl_hip_softtargets.h declares (likewise)
+SOFTTARGET_ENTRIES = ("marl_soft_targets",)
+# ... and the mixing batch gather that include/marl_hip_mix.h declares (likewise; mix.py binds it)
+MIX_ENTRIES = ("marl_batch_mix", "marl_batch_mix_plan")
 # ... and the flat optimiser step that include/marl_hip_optim.h declares (likewise; optim.py holds its structures)
 OPTIM_ENTRIES = ("marl_optim_step",)
 # ... and the kernel-level hooks of the row-panel kernels that include/marl_hip_panelops.h declares (tests only)
 PANELOP_HOOKS = ("marl_panel_fwd", "marl_panel_bwd", "marl_panel_scratch_bytes", "marl_panel_plan")
 _HOOKS = (ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES +
-          PANELOP_HOOKS)
+          PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES)
 MARL_PANEL_MAX_LAYERS = 4
 
 
@@ -291,6 +295,9 @@ def _declare(lib: C.CDLL) -> None:
                                     _vp]
     lib.marl_batch_augment.argtypes = [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
     lib.marl_batch_augment_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
+    lib.marl_soft_targets.argtypes = [_vp, _i, _i]
+    lib.marl_batch_mix.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
+    lib.marl_batch_mix_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
     lib.marl_ln_silu_bwd.argtypes = [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _vp, _sz, _i, _i, _vp]
     lib.marl_gn_silu_bwd.argtypes = [_vp, _i64, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _vp]
     lib.marl_cnn_dgrad.argtypes = [_vp, _vp, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _i, _vp]

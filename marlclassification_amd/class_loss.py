@@ -105,15 +105,34 @@ def _vector(v, n: int, like: th.Tensor, what: str) -> th.Tensor:
     return t
 
 
+def _targets(targets: th.Tensor, nb: int, nc: int, like: th.Tensor) -> th.Tensor:
+    q = targets.to(like.device, like.dtype)
+    if tuple(q.shape) != (nb, nc):
+        raise ValueError(f"targets must be [Nb = {nb}, nC = {nc}], got {tuple(q.shape)}")
+    return q
+
+
 def vote_error(step_preds: th.Tensor, y: th.Tensor, class_weights=None, label_smoothing: float = 0.0,
-               step_weights=None) -> th.Tensor:
+               step_weights=None, targets: Optional[th.Tensor] = None) -> th.Tensor:
     """err [Ns, Nb] of the module docstring from ``step_preds`` [Ns, Na, Nb, nC] and ``y`` [Nb], differentiable, in the
-    dtype of ``step_preds``.  nll comes from the logits (log_softmax), never log(softmax)."""
+    dtype of ``step_preds``.  nll comes from the logits (log_softmax), never log(softmax).
+    ``targets`` (include/marl_hip_softtargets.h): a target distribution Q [Nb, nC] in place of ``y`` -
+    q_c = w_c ((1 - eps) Q[b,c] + eps / nC), err[t,b] = s_t sum_c q_c nll_c, which without s_t is
+    ``F.cross_entropy(z, Q, weight=w, label_smoothing=eps, reduction="none")``; entries with Q[b,c] == 0 are skipped,
+    not multiplied."""
     z, y = _vote(step_preds, y)
     ns, nb, nc = z.shape
     eps = check_label_smoothing(label_smoothing)
     nll = -th.log_softmax(z, dim=-1)  # [Ns, Nb, nC]
     w = z.new_ones(nc) if class_weights is None else _vector(class_weights, nc, z, "class_weights")
+    if targets is not None:
+        q = _targets(targets, nb, nc, z)
+        err = (1.0 - eps) * th.where(q != 0, q * w * nll, th.zeros_like(nll)).sum(dim=-1)
+        if eps != 0.0:
+            err = err + (eps / nc) * (nll * w).sum(dim=-1)
+        if step_weights is not None:
+            err = err * _vector(step_weights, ns, z, "step_weights").view(ns, 1)
+        return err
     wy = w[y]  # [Nb]
     err = (1.0 - eps) * wy * nll.gather(-1, y.view(1, nb, 1).expand(ns, nb, 1)).squeeze(-1)
     if eps != 0.0:
@@ -123,11 +142,20 @@ def vote_error(step_preds: th.Tensor, y: th.Tensor, class_weights=None, label_sm
     return err
 
 
-def rewards(step_preds: th.Tensor, y: th.Tensor, class_weights=None) -> th.Tensor:
+def rewards(step_preds: th.Tensor, y: th.Tensor, class_weights=None,
+            targets: Optional[th.Tensor] = None) -> th.Tensor:
     """rew [Ns, Na, Nb] = w_y * (log nC - CE(step_preds[t, a, b, :], y[b])) / log nC (functions.py:7-32 with
-    ``class_weights`` None)."""
+    ``class_weights`` None).  ``targets``: Q [Nb, nC] in place of ``y`` -
+    rew = sum_c w_c Q[b,c] (log nC - nll_c) / log nC, linear in Q; entries with Q[b,c] == 0 are skipped."""
     _, y = _vote(step_preds, y)
     ns, na, nb, nc = step_preds.shape
+    if targets is not None:
+        q = _targets(targets, nb, nc, step_preds)
+        rnd = math.log(nc)
+        per_class = (rnd - -th.log_softmax(step_preds, dim=-1)) / rnd  # [Ns, Na, Nb, nC]
+        if class_weights is not None:
+            per_class = per_class * _vector(class_weights, nc, step_preds, "class_weights")
+        return th.where(q != 0, q * per_class, th.zeros_like(per_class)).sum(dim=-1)
     ce = -th.log_softmax(step_preds, dim=-1).gather(-1, y.view(1, 1, nb, 1).expand(ns, na, nb, 1)).squeeze(-1)
     rnd = math.log(nc)
     rew = (rnd - ce) / rnd

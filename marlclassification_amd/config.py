@@ -117,6 +117,9 @@ class TrainConfig(BaseModel):
     # --augment: device-side augmentation of the training split in the command-line spelling (augment.parse); a run-time
     # choice like the exploration controls, not written to marl.json.  None: every batch is the plain gather
     augment: Optional[str] = None
+    # --mix: CutMix / Mixup of the training split in the command-line spelling (mix.parse), fused into the same batch
+    # gather; the loss then takes the batch's target distributions.  A run-time choice too, not written to marl.json
+    mix: Optional[str] = None
     # options of the vote error and the rewards (class_loss.py), run-time choices like the two above: "balanced", a
     # .npy path or one weight per class; the smoothing; all | last[:K] | linear; rewards times the class weight
     class_weights: Optional[Union[str, Tuple[float, ...]]] = None

@@ -1066,6 +1066,8 @@ struct LossCommon {
     const float* cls_sw = nullptr;  // [ns] step weights of the vote error, nullptr = all ones
     float cls_eps = 0.f;            // label smoothing
     bool cls_wrew = false;          // rewards times w[y]
+    // a target distribution per image in place of y (marl_soft_targets; nullptr: the label kernels, as ever)
+    const float* soft_q = nullptr;  // [nb, nc]
 };
 // ... and what the two loss passes (A2C, PPO) add: the policy term's input, the output gradients, the scalars and
 // the optional entropy bonus (probs != nullptr)

@@ -23,6 +23,7 @@
 #include "../../include/marl_hip_cnnops.h"
 #include "../../include/marl_hip_explore.h"
 #include "../../include/marl_hip_classloss.h"
+#include "../../include/marl_hip_softtargets.h"
 #include "common.h"
 
 namespace marl {
@@ -623,7 +624,14 @@ struct ClassLoss {
     int ns;
     bool wrew;
 };
-// The process-global settings.  The five setters are the only writers of g_installed; an entry point copies it once
+// marl_soft_targets (marl_hip_softtargets.h): a target distribution per image in place of the label, in the vote error
+// and the rewards of every loss entry.  q != nullptr: a loss entry takes the soft instances of the two kernels - with
+// none installed every entry launches what it always launched.
+struct SoftTargets {
+    const float* q;  // [nb, nc] device, caller-owned
+    int nb, nc;
+};
+// The process-global settings.  The six setters are the only writers of g_installed; an entry point copies it once
 // (make_ctx into Ctx::opt, the entries without a context at their top) and everything below reads that copy.
 struct Installed {
     // marl_comm_matrix: the caller-owned [na, na] mixing matrix of the message exchange (row = receiver), or null =
@@ -636,6 +644,7 @@ struct Installed {
     CommGate range = {nullptr, -1, 0, 1};
     Explore explore = {false, 1.f, 1.f, 0.f, 0};
     ClassLoss class_loss = {false, nullptr, 0, 0.f, nullptr, 0, false};
+    SoftTargets soft = {nullptr, 0, 0};
     hipEvent_t heads_event = nullptr;  // marl_backward_heads_event: recorded once the heads' gradients are final
 };
 static Installed g_installed;
@@ -664,6 +673,7 @@ struct Plan {
     int comm_form;
     int explore_form;   // sampling under the controls: 0 = off, 1 = the chain launch's EXPLORE epilogue, 2 = sample_kernel's
     int comm, comm_range, explore, class_loss;  // what is installed: matrix set, its radius or -1, controls / options on
+    int soft_targets;                           // ... and a target distribution per image (marl_soft_targets)
 };
 
 // ---------------------------------------------------------------------------
@@ -744,6 +754,7 @@ static Plan make_plan(const Dims& d, const WLayout& w, const ELayout& e, const I
     p.comm_range = opt.range.radius >= 0 ? opt.range.radius : -1;
     p.explore = opt.explore.on;
     p.class_loss = opt.class_loss.on;
+    p.soft_targets = opt.soft.q != nullptr;
 
     const int k_lstm = tune_get("g3_lstm", 1), k_tn = tune_get("g3_tn", 1);
     p.g3_lstm = e.g3 && k_lstm != 0;
@@ -2547,6 +2558,16 @@ int marl_class_loss(const float* class_weights_dev, int nb_class, float label_sm
     return MARL_OK;
 }
 
+int marl_soft_targets(const float* q_dev, int batch, int nb_class) {
+    if (batch < 0 || nb_class < 0 || (q_dev && (batch == 0 || nb_class == 0)) || (!q_dev && (batch || nb_class))) {
+        set_error("soft_targets: a [%d, %d] target tensor: the pointer needs both sizes, and none is negative", batch,
+                  nb_class);
+        return MARL_EINVAL;
+    }
+    g_installed.soft = SoftTargets{q_dev, batch, nb_class};
+    return MARL_OK;
+}
+
 size_t marl_comm_grad_scratch_bytes(const marl_config* cfg) {
     Dims d;
     if (make_dims(cfg, d) != MARL_OK) return 0;
@@ -2704,9 +2725,16 @@ static int loss_entry(const marl_config* cfg, void* episode_ws, size_t episode_w
                   who, k.nc, k.ns, d.nC, d.ns);
         return MARL_EINVAL;
     }
+    const SoftTargets q = g_installed.soft;
+    if (q.q && (q.nb != d.nb || q.nc != d.nC)) {
+        set_error("%s: the installed soft targets are [%d, %d], the configuration has batch %d and %d classes", who,
+                  q.nb, q.nc, d.nb, d.nC);
+        return MARL_EINVAL;
+    }
     a.preds = step_preds;
     a.values = step_values;
     a.y = y;
+    a.soft_q = q.q;  // (marl_soft_targets; nullptr: the label kernels, as ever)
     a.scratch = static_cast<float*>(episode_ws) + e.LOSS;
     a.ns = d.ns;
     a.na = d.na;
@@ -3079,6 +3107,7 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     else if (!strcmp(key, "panel_sample")) *value = plan.panel_sample;
     else if (!strcmp(key, "explore")) *value = plan.explore;
     else if (!strcmp(key, "class_loss")) *value = plan.class_loss;
+    else if (!strcmp(key, "soft_targets")) *value = plan.soft_targets;
     else if (!strcmp(key, "explore_form")) *value = plan.explore_form;
     else if (!strcmp(key, "comm_form")) *value = plan.comm_form;
     else {

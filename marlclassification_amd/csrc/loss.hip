@@ -6,6 +6,8 @@
 // All cross-thread sums go through fixed-order partials (fp64) -> bit-reproducible.
 // Under marl_class_loss (include/marl_hip_classloss.h) the rewards and the vote error run their option instances:
 // class weights, label smoothing, step weights, rewards times the label's weight - same launches, same order.
+// Under marl_soft_targets (include/marl_hip_softtargets.h) the same two launches run their soft instances: a target
+// distribution per image where the label was.
 #include "common.h"
 
 #include <cassert>
@@ -256,6 +258,134 @@ __global__ __launch_bounds__(256) void loss_error_kernel(const float* __restrict
     }
 }
 
+// ---- a target distribution per image in place of the label (marl_soft_targets, include/marl_hip_softtargets.h) ------
+// The label kernels above stay what they are; these are further instances of the same two launches.  Q is [nb, nc];
+// entries with Q[b, c] == 0 are skipped, not multiplied (a logit of -inf beside them stays out of every sum).  Every
+// class sum is a fixed-order wave sum, and the arithmetic is ordered so that a one-hot Q gives the label kernels' bits:
+// the one term that is not skipped is the label kernel's own expression times 1, and the sums add zeros to it.
+
+// rew[t, r] = sum_c omega_c Q[b, c] (log nC - nll_c(preds[t, r, :])) / log nC ; one wave per (t, r)
+// OPT (weight_rewards): omega = w, else 1
+template <bool OPT>
+__global__ __launch_bounds__(256) void loss_rewards_soft_kernel(const float* __restrict__ preds,
+                                                                const float* __restrict__ q,
+                                                                float* __restrict__ rew, int64_t NR,
+                                                                int nb, int nc, float rnd,
+                                                                std::conditional_t<OPT, ClassOpt, NoClassOpt> o) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= NR) return;
+    const float* p = preds + row * nc;
+    float mx = -INFINITY;
+    for (int c = lane; c < nc; c += 64) mx = fmaxf(mx, p[c]);
+    mx = wmax(mx);
+    float s = 0.f;
+    for (int c = lane; c < nc; c += 64) s += expf(p[c] - mx);
+    s = wsum(s);
+    const float* qb = q + (int64_t)(row % nb) * nc;
+    float acc = 0.f;
+    for (int c = lane; c < nc; c += 64) {
+        const float qc = qb[c];
+        if (qc == 0.f) continue;
+        const float ce = -(p[c] - mx - logf(s));
+        if constexpr (OPT)
+            acc += o.w[c] * (qc * ((rnd - ce) / rnd));  // (launched with weights only)
+        else
+            acc += qc * ((rnd - ce) / rnd);
+    }
+    acc = wsum(acc);
+    if (lane == 0) rew[row] = acc;
+}
+
+// err[t, b] = s_t sum_c q_c nll_c,  g_preds[t, a, b, c] = s_t / R (softmax_c sum_c' q_c' - q_c) with
+// q_c = w_c ((1 - eps) Q[b, c] + eps / nC); the plain instance has w = 1, eps = 0, s = 1 and none of their arithmetic.
+// q_c is formed as (keep w_c) Q[b, c] + (eps / nC) w_c: loss_error_kernel<true>'s qy 1[c == y] + (eps / nC) w_c.
+template <bool OPT>
+__global__ __launch_bounds__(256) void loss_error_soft_kernel(const float* __restrict__ preds,
+                                                              const float* __restrict__ q,
+                                                              float* __restrict__ err,
+                                                              float* __restrict__ g_preds, int ld_gp,
+                                                              int ns, int na, int nb, int nc,
+                                                              std::conditional_t<OPT, ClassOpt, NoClassOpt> o) {
+    __shared__ float pbar[4][1024];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tb = (int64_t)blockIdx.x * 4 + wave;
+    if (tb >= (int64_t)ns * nb) return;
+    const int t = (int)(tb / nb), b = (int)(tb % nb);
+    const int64_t R = (int64_t)na * nb;
+    float mx = -INFINITY;
+    for (int c = lane; c < nc; c += 64) {
+        float s = 0.f;
+        for (int a = 0; a < na; ++a) s += preds[((int64_t)t * R + (int64_t)a * nb + b) * nc + c];
+        s = s / (float)na;
+        pbar[wave][c] = s;
+        mx = fmaxf(mx, s);
+    }
+    mx = wmax(mx);
+    float s = 0.f;
+    for (int c = lane; c < nc; c += 64) s += expf(pbar[wave][c] - mx);
+    s = wsum(s);
+    const float* qb = q + (int64_t)b * nc;
+    if constexpr (!OPT) {
+        float hn = 0.f, hs = 0.f;  // sum_c Q_c nll_c, sum_c Q_c
+        for (int c = lane; c < nc; c += 64) {
+            const float qc = qb[c];
+            if (qc == 0.f) continue;
+            hn += qc * -(pbar[wave][c] - mx - logf(s));
+            hs += qc;
+        }
+        hn = wsum(hn);
+        hs = wsum(hs);
+        if (lane == 0) err[tb] = hn;
+        if (g_preds) {
+            const float inv = 1.0f / (float)R;
+            for (int c = lane; c < nc; c += 64) {
+                const float g = (expf(pbar[wave][c] - mx) / s * hs - qb[c]) * inv;
+                for (int a = 0; a < na; ++a)
+                    g_preds[((int64_t)t * R + (int64_t)a * nb + b) * ld_gp + c] = g;
+            }
+        }
+    } else {
+        __shared__ float wcls[4][1024];
+        const float ls = logf(s);
+        float wn = 0.f, wt = 0.f;  // sum_c w_c nll_c, sum_c w_c
+        float hn = 0.f, hs = 0.f;  // sum_c h_c nll_c, sum_c h_c with h_c = (keep w_c) Q_c, the targets' own share of q
+        for (int c = lane; c < nc; c += 64) {
+            const float wc = o.w ? o.w[c] : 1.0f;
+            wcls[wave][c] = wc;
+            const float nll = -(pbar[wave][c] - mx - ls);
+            wn = fmaf(wc, nll, wn);
+            wt += wc;
+            const float qc = qb[c];
+            if (qc == 0.f) continue;
+            const float hc = o.keep * wc * qc;
+            hn += hc * nll;
+            hs += hc;
+        }
+        wn = wsum(wn);
+        wt = wsum(wt);
+        hn = wsum(hn);
+        hs = wsum(hs);
+        const float st = o.sw ? o.sw[t] : 1.0f;
+        if (lane == 0) {
+            float e = hn;
+            if (o.eps_nc != 0.f) e = fmaf(o.eps_nc, wn, e);
+            err[tb] = st * e;
+        }
+        if (g_preds) {
+            const float sc = st * (1.0f / (float)R);
+            const float qs = o.eps_nc != 0.f ? fmaf(o.eps_nc, wt, hs) : hs;  // sum_c q_c
+            for (int c = lane; c < nc; c += 64) {
+                const float qv = qb[c];
+                const float qc = (qv == 0.f ? 0.0f : o.keep * wcls[wave][c] * qv) + o.eps_nc * wcls[wave][c];
+                const float g = (expf(pbar[wave][c] - mx) / s * qs - qc) * sc;
+                for (int a = 0; a < na; ++a)
+                    g_preds[((int64_t)t * R + (int64_t)a * nb + b) * ld_gp + c] = g;
+            }
+        }
+    }
+}
+
 // thread per row r: returns by the reference's flip-cumsum-flip of rew * gamma^t, / gamma^t
 __global__ __launch_bounds__(256) void loss_returns_kernel(const float* __restrict__ rew,
                                                            const float* __restrict__ values,
@@ -379,6 +509,15 @@ static ClassOpt class_opt(const LossCommon& a) {
 static void launch_rewards(const LossCommon& a, float* rew, hipStream_t st) {
     const int64_t NR = (int64_t)a.na * a.nb * a.ns;
     const float rnd = (float)log((double)a.nc);
+    if (a.soft_q) {  // (marl_soft_targets: the same launch, its soft instance)
+        if (a.cls && a.cls_wrew && a.cls_w)
+            hipLaunchKernelGGL(loss_rewards_soft_kernel<true>, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st, a.preds,
+                               a.soft_q, rew, NR, a.nb, a.nc, rnd, class_opt(a));
+        else
+            hipLaunchKernelGGL(loss_rewards_soft_kernel<false>, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st, a.preds,
+                               a.soft_q, rew, NR, a.nb, a.nc, rnd, NoClassOpt{});
+        return;
+    }
     if (a.cls && a.cls_wrew && a.cls_w)
         hipLaunchKernelGGL(loss_rewards_kernel<true>, dim3((unsigned)cdiv(NR, 4)), dim3(256), 0, st, a.preds, a.y, rew,
                            NR, a.nb, a.nc, rnd, class_opt(a));
@@ -389,6 +528,15 @@ static void launch_rewards(const LossCommon& a, float* rew, hipStream_t st) {
 
 static void launch_error(const LossGradArgs& a, float* err, hipStream_t st) {
     const dim3 grid((unsigned)cdiv((int64_t)a.ns * a.nb, 4));
+    if (a.soft_q) {
+        if (a.cls)
+            hipLaunchKernelGGL(loss_error_soft_kernel<true>, grid, dim3(256), 0, st, a.preds, a.soft_q, err, a.g_preds,
+                               a.ld_gp, a.ns, a.na, a.nb, a.nc, class_opt(a));
+        else
+            hipLaunchKernelGGL(loss_error_soft_kernel<false>, grid, dim3(256), 0, st, a.preds, a.soft_q, err, a.g_preds,
+                               a.ld_gp, a.ns, a.na, a.nb, a.nc, NoClassOpt{});
+        return;
+    }
     if (a.cls)
         hipLaunchKernelGGL(loss_error_kernel<true>, grid, dim3(256), 0, st, a.preds, a.y, err, a.g_preds, a.ld_gp, a.ns,
                            a.na, a.nb, a.nc, class_opt(a));

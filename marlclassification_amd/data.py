@@ -5,7 +5,7 @@ gather kernel.  A synthetic dataset of the same interface serves benchmarks and 
 (no dataset can be downloaded here)."""
 
 import os
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch as th
 from torch.utils.data import Dataset
@@ -70,12 +70,19 @@ class DevicePrefetcher:
 
     ``augment`` (an ``augment.Policy``): the uploaded batch goes through ``augment.apply`` into a fresh tensor on the
     compute stream, behind the wait on the copy's event, under ops drawn from ``generator`` (a generator of
-    ``device``).  None: exactly the code above."""
+    ``device``).  None: exactly the code above.
 
-    def __init__(self, loader, device: th.device, augment=None, generator=None) -> None:
+    ``mix`` (a ``mix.Policy``, with ``nb_class``): the batch is mixed with a permutation of itself (CutMix / Mixup,
+    ``mix.apply``: the views are the augmented ones, still one launch) and the loader yields ``(x, y_primary, Q)`` with
+    the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes."""
+
+    def __init__(self, loader, device: th.device, augment=None, generator=None, mix=None,
+                 nb_class: Optional[int] = None) -> None:
         self.loader = loader
         self.device = th.device(device)
-        self.augment, self.generator = augment, _device_generator(augment, generator, self.device)
+        self.mix, self.nb_class = mix, _mix_classes(mix, nb_class)
+        self.augment = augment
+        self.generator = _device_generator(augment if mix is None else mix, generator, self.device)
 
     def _upload(self, batch, stream):
         if batch is None:
@@ -103,6 +110,9 @@ class DevicePrefetcher:
             cur.wait_event(ev)
             xd.record_stream(cur)
             yd.record_stream(cur)
+            if self.mix is not None:
+                yield _mixed(self.augment, self.mix, self.generator, xd, None, yd, self.nb_class)
+                continue
             if self.augment is not None:
                 xd = _augmented(self.augment, self.generator, xd, None)
             yield xd, yd
@@ -127,6 +137,28 @@ def _augmented(policy, generator, x: th.Tensor, rows):
     batch = x.shape[0] if rows is None else rows.shape[0]
     ops = policy.draw(batch, generator, size=(x.shape[-2], x.shape[-1]))
     return _augment.apply(x, rows, ops, pad_mode=policy.pad_mode, fill=policy.fill)
+
+
+def _mix_classes(policy, nb_class) -> Optional[int]:
+    if policy is not None and (isinstance(nb_class, bool) or not isinstance(nb_class, int) or nb_class < 1):
+        raise ValueError(f"a mixing loader needs nb_class (the width of the target distributions), got {nb_class!r}")
+    return nb_class
+
+
+def _mixed(augment, policy, generator, x: th.Tensor, rows, y: th.Tensor, nb_class: int):
+    """``(mix.apply of x[rows], primary labels, target distributions)`` under freshly drawn ops (``augment``, may be
+    None) and a freshly drawn mix, in this order from one generator; ``y`` are the labels of the batch"""
+    from . import mix as _mix
+
+    h, w = x.shape[-2], x.shape[-1]
+    batch = x.shape[0] if rows is None else rows.shape[0]
+    ops, pad_mode, fill = None, "reflect", 0
+    if augment is not None:
+        augment.check_size(h, w)
+        ops, pad_mode, fill = augment.draw(batch, generator, size=(h, w)), augment.pad_mode, augment.fill
+    m = policy.draw(batch, generator, size=(h, w))
+    out = _mix.apply(x, rows, ops, m, pad_mode=pad_mode, fill=fill)
+    return out, _mix.primary_labels(y, m, h, w), _mix.soft_targets(y, m, h, w, nb_class)
 
 
 class _Stripe:
@@ -190,17 +222,24 @@ class ResidentLoader:
     ``augment`` (an ``augment.Policy``): every batch is ``augment.apply(resident set, rows, ops)`` - the gather with
     flips, quarter turns, shifts and erasing fused in, one launch that moves the bytes ``index_select`` moves - under
     ops drawn from ``generator`` (a generator of ``device``) without a host synchronisation.  Labels are gathered as
-    before.  None: exactly the ``index_select`` above."""
+    before.  None: exactly the ``index_select`` above.
+
+    ``mix`` (a ``mix.Policy``, with ``nb_class``): every batch is mixed with a permutation of itself (CutMix / Mixup,
+    ``mix.apply`` from the resident set: the views are the augmented ones, still one launch) and the loader yields
+    ``(x, y_primary, Q)`` with the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes."""
 
     def __init__(self, dataset, indices, batch_sampler, device, workers: int = 0,
-                 rank: int = 0, world: int = 1, group=None, chunk: int = 16, augment=None, generator=None) -> None:
+                 rank: int = 0, world: int = 1, group=None, chunk: int = 16, augment=None, generator=None,
+                 mix=None, nb_class: Optional[int] = None) -> None:
         self.dataset, self.batch_sampler = dataset, batch_sampler
         self.indices = list(indices)
         self.device = th.device(device)
         self.workers, self.rank, self.world, self.group, self.chunk = workers, rank, world, group, chunk
         self._x = self._y = self._row_of = None
         self.fill_img_s = float("nan")
-        self.augment, self.generator = augment, _device_generator(augment, generator, self.device)
+        self.mix, self.nb_class = mix, _mix_classes(mix, nb_class)
+        self.augment = augment
+        self.generator = _device_generator(augment if mix is None else mix, generator, self.device)
 
     @staticmethod
     def nbytes(dataset, n: int) -> int:
@@ -257,7 +296,10 @@ class ResidentLoader:
             self._fill()
         for batch in self.batch_sampler:
             rows = self._row_of[th.tensor(batch, dtype=th.long).to(self.device, non_blocking=True)]
-            if self.augment is None:
+            if self.mix is not None:
+                yield _mixed(self.augment, self.mix, self.generator, self._x, rows, self._y.index_select(0, rows),
+                             self.nb_class)
+            elif self.augment is None:
                 yield self._x.index_select(0, rows), self._y.index_select(0, rows)
             else:
                 yield _augmented(self.augment, self.generator, self._x, rows), self._y.index_select(0, rows)

@@ -232,6 +232,9 @@ class HipEngine:
         # kept for the engine's life - a captured graph keeps the pointers, so none is ever dropped: nC + Ns floats
         # per DISTINCT setting, which is expected to be one or a few per run (not a per-step schedule)
         self.class_loss = None
+        # a target distribution per image in place of the labels (set_soft_targets: fp32 [Nb, nC] on the device, None =
+        # the labels), installed and cleared around each loss call like the options above
+        self.soft_targets: Optional[th.Tensor] = None
         self._class_loss_dev: Dict[object, Tuple[Optional[th.Tensor], Optional[th.Tensor]]] = {}
 
     # -- communication graph ----------------------------------------------------------
@@ -379,7 +382,55 @@ class HipEngine:
             raise ValueError(f"class_loss is for {c.nb_class} classes / {c.nb_steps} steps, the engine is configured "
                              f"for {cfg.nb_class} / {cfg.nb_steps}")
 
+    def set_soft_targets(self, q: Optional[th.Tensor] = None, check_values: bool = True) -> None:
+        """A target distribution per image, ``q`` fp32 ``[Nb, nC]`` on this engine's device, for every later
+        ``a2c_loss`` / ``advantages`` / ``ppo_loss`` of this engine in place of the labels (CutMix, Mixup, a teacher's
+        distribution; include/marl_hip_softtargets.h); None restores the labels.  Kept here, installed in the library
+        (marl_soft_targets) around each of those calls and cleared behind it.  The tensor is not copied: the launches
+        read it, and a captured graph reads the capturing call's tensor.  Checked: dtype, device, contiguous, the
+        configured sizes (here if the engine is configured, else at the call), and - ``check_values``, one host
+        synchronisation - finite, >= 0, no all-zero row."""
+        if q is None:
+            self.soft_targets = None
+            return
+        if not isinstance(q, th.Tensor):
+            raise TypeError(f"soft targets must be a tensor or None, got {type(q).__name__}")
+        if q.dtype != th.float32:
+            raise TypeError(f"soft targets must be float32, got {q.dtype}")
+        if not q.is_cuda:
+            raise RuntimeError(f"soft targets live on {q.device}, the engine on {self.device}: the HIP path only "
+                               "reads device memory")
+        if q.dim() != 2 or not q.is_contiguous():
+            raise ValueError(f"soft targets must be a contiguous [Nb, nC] tensor, got {tuple(q.shape)}")
+        if self.cfg is not None:
+            self._check_soft_targets(q)
+        if check_values:
+            ok = th.isfinite(q).all() & (q >= 0).all() & (q > 0).any(dim=1).all()
+            if not bool(ok):
+                raise ValueError("soft targets must be finite and >= 0, and no row may be all zero")
+        self.soft_targets = q
+
+    def _check_soft_targets(self, q: th.Tensor) -> None:
+        cfg = self.cfg
+        if tuple(q.shape) != (cfg.batch, cfg.nb_class):
+            raise ValueError(f"soft targets are {tuple(q.shape)}, the engine is configured for batch {cfg.batch} and "
+                             f"{cfg.nb_class} classes")
+
     def _loss_call(self, fn, *args) -> None:
+        """A loss entry under this engine's ``soft_targets`` and ``class_loss`` (both None: the plain call and nothing
+        more).  Checked against the configured sizes before anything is enqueued."""
+        q = self.soft_targets
+        if q is None:
+            self._class_loss_call(fn, *args)
+            return
+        self._check_soft_targets(q)
+        check(self.lib.marl_soft_targets(q.data_ptr(), q.shape[0], q.shape[1]))
+        try:
+            self._class_loss_call(fn, *args)
+        finally:
+            self.lib.marl_soft_targets(None, 0, 0)
+
+    def _class_loss_call(self, fn, *args) -> None:
         """A loss entry under this engine's ``class_loss`` (None, or one with nothing given: the plain call and
         nothing more).  Checked against the configured classes / steps before anything is enqueued."""
         c = self.class_loss

@@ -219,6 +219,21 @@ class ClassLossOptions:
             eng.class_loss = before
 
 
+@contextmanager
+def soft_targets_installed(eng: HipEngine, targets: Optional[th.Tensor], check_values: bool = True):
+    """``with soft_targets_installed(eng, Q):`` runs loss calls under the target distributions ``Q`` (fp32 [Nb, nC],
+    ``HipEngine.set_soft_targets``) and puts the engine's own setting back behind them; None: nothing is touched."""
+    if targets is None:
+        yield
+        return
+    before = eng.soft_targets
+    eng.set_soft_targets(targets, check_values)
+    try:
+        yield
+    finally:
+        eng.soft_targets = before
+
+
 class OptimRun:
     """The optimiser options (``optim.OptimOptions``) as ``Trainer`` and ``FusedA2C`` hold them: the schedule's base
     rate filled in from the learning rate, the merged segment table of each flat buffer it met (host arrays, built
@@ -425,13 +440,13 @@ class FusedA2C:
                                            rng=draws.rng, probs=probs)
 
     def iteration_graph(self, img: th.Tensor, y: th.Tensor, seed: int,
-                        offset: int) -> Tuple[EpisodeTensors, th.Tensor]:
+                        offset: int, targets: Optional[th.Tensor] = None) -> Tuple[EpisodeTensors, th.Tensor]:
         """The same iteration as ONE hipGraph replay (launch-bound shapes: hundreds of small
         kernels per iteration).  The first call runs one eager iteration (one-off set-up inside
         the library), then captures draw -> rollout -> loss -> backward -> Adam -> re-pack ->
         counter tick on a side stream; later calls replay it.  What changes between iterations
-        lives on the device (generator offset, Adam step: the counter block), ``img`` / ``y`` are
-        read from the tensors of the capturing call (same storage every call, or re-capture).
+        lives on the device (generator offset, Adam step: the counter block), ``img`` / ``y`` /
+        ``targets`` are read from the tensors of the capturing call (same storage every call, or re-capture).
         Outputs are persistent tensors, overwritten by every replay."""
         eng = self.engine
         if self._ppo:
@@ -447,7 +462,8 @@ class FusedA2C:
         beta = self.entropy_coef
         self._explore()
         closs = self._class_loss.resolve(eng) if eng.cfg is not None else None
-        key = (img.data_ptr(), y.data_ptr(), eng._cfg_key, seed, _engine_mod._tune_epoch, beta,
+        key = (img.data_ptr(), y.data_ptr(), None if targets is None else targets.data_ptr(), eng._cfg_key, seed,
+               _engine_mod._tune_epoch, beta,
                None if eng.comm is None else eng.comm.data_ptr(),  # (the captured kernels keep the matrix pointer
                eng.comm_range,                                     # and the range's radius / metric / normalize
                eng.exploration,                                    # and the exploration constants in their arguments)
@@ -459,7 +475,8 @@ class FusedA2C:
                 eng.lib.marl_graph_destroy(self._graph[1])
                 self._graph = None
             # this call runs eagerly (one-off set-up inside the library happens here) ...
-            eager = self.iteration(img, y, draw_episode_device(eng, seed, offset))
+            # (... and the targets' values are checked here, outside the capture: the check synchronises)
+            eager = self.iteration(img, y, draw_episode_device(eng, seed, offset), targets=targets)
             offset += 1  # ... and the graph captured below starts at the NEXT iteration
             stream = th.cuda.Stream(device=eng.device)
             out = eng.new_outputs(beta > 0)
@@ -475,7 +492,7 @@ class FusedA2C:
                     eng.draw_episode(seed, 0, into=draws, counters=cnt)
                     eng.episode_forward(img, draws[0], draws[1], draws[2], draws[3], draws[4], None,
                                         None, True, rng=(seed, 0), out=out, counters=cnt)
-                    with self._class_loss.installed(eng):
+                    with self._class_loss.installed(eng), soft_targets_installed(eng, targets, False):
                         bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
                     gp, gl, gv, scalars = bufs[:4]
                     eng.episode_backward(gp, gl, gv, gviews, g_probs=bufs[5] if beta > 0 else None)
@@ -517,18 +534,21 @@ class FusedA2C:
         expect.update(offset=offset + 1, step=self.flat.step + 1)
         return out, scalars
 
-    def iteration(self, img: th.Tensor, y: th.Tensor, draws: EpisodeDraws) -> Tuple[EpisodeTensors, th.Tensor]:
+    def iteration(self, img: th.Tensor, y: th.Tensor, draws: EpisodeDraws,
+                  targets: Optional[th.Tensor] = None) -> Tuple[EpisodeTensors, th.Tensor]:
         """Returns the episode outputs and the device tensor {loss, path, error, critic} (with an entropy
-        bonus: the loss includes it and a fifth scalar holds the mean entropy)."""
+        bonus: the loss includes it and a fifth scalar holds the mean entropy).  ``targets``: fp32 [Nb, nC] target
+        distributions that the vote error and the rewards take in place of ``y`` (``HipEngine.set_soft_targets``),
+        installed around the loss calls of this iteration - every PPO epoch among them - and cleared behind them."""
         eng = self.engine
         beta = self.entropy_coef
         if self._ppo:
-            return self._iteration_ppo(img, y, draws)
+            return self._iteration_ppo(img, y, draws, targets)
         out = self.rollout(img, draws, True, probs=beta > 0)
         if (self._loss_bufs is None or self._loss_bufs[0].shape != out.step_preds.shape or
                 len(self._loss_bufs) != (6 if beta > 0 else 5)):
             self._loss_bufs = eng.new_loss_bufs(out, beta > 0)
-        with self._class_loss.installed(eng):
+        with self._class_loss.installed(eng), soft_targets_installed(eng, targets):
             bufs = eng.a2c_loss(out, y, self.gamma, 0, self._loss_bufs, entropy_coef=beta)
         gp, gl, gv, scalars = bufs[:4]
         apply_update(eng, self.flat, gp, gl, gv, bufs[5] if beta > 0 else None, self._gviews, self.lr,
@@ -542,7 +562,8 @@ class FusedA2C:
         self._comm_update = comm_update_for(self._comm_update, src, lambda: _comm_mod.leaves(src), self.comm_lr)
         return self._comm_update
 
-    def _iteration_ppo(self, img: th.Tensor, y: th.Tensor, draws: EpisodeDraws) -> Tuple[EpisodeTensors, th.Tensor]:
+    def _iteration_ppo(self, img: th.Tensor, y: th.Tensor, draws: EpisodeDraws,
+                       targets: Optional[th.Tensor] = None) -> Tuple[EpisodeTensors, th.Tensor]:
         """One rollout, ``ppo_epochs`` updates; returns the rollout's outputs and the last epoch's scalars
         {loss, surrogate, error, critic, entropy, approx_kl, clip_frac}."""
         eng, beta = self.engine, self.entropy_coef
@@ -551,7 +572,7 @@ class FusedA2C:
         bufs = self._ppo_bufs
         if not ppo_bufs_fit(bufs, out, ent):
             bufs = self._ppo_bufs = eng.new_ppo_bufs(out, ent)
-        with self._class_loss.installed(eng):
+        with self._class_loss.installed(eng), soft_targets_installed(eng, targets):
             eng.advantages(out, y, self.gamma, self.gae_lambda, 0, bufs)
             norm = ppo_epochs_loop(
                 eng, self.flat, out, y, bufs, self.ppo_epochs, self.ppo_clip, beta, self.lr, self.allreduce,

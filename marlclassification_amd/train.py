@@ -225,8 +225,18 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         policy = _augment.parse(train_config.augment)
         policy.check_size(train_config.img_size, train_config.img_size)
         aug_gen = th.Generator(device=device).manual_seed(base_seed + 104729 * (rank + 1))
+    # --mix: likewise the training split only, drawn from the same per-rank device generator (behind the ops)
+    mix_policy = None
+    if train_config.mix is not None:
+        from . import mix as _mix
+
+        mix_policy = _mix.parse(train_config.mix)
+        if aug_gen is None:
+            aug_gen = th.Generator(device=device).manual_seed(base_seed + 104729 * (rank + 1))
     for k, part in enumerate((idx[:cut].tolist(), idx[cut:].tolist())):
         aug = {"augment": policy, "generator": aug_gen} if policy is not None and k == 0 else {}
+        if mix_policy is not None and k == 0:
+            aug.update(mix=mix_policy, nb_class=model_config.nb_class, generator=aug_gen)
         bs = ShardedBatchSampler(part, train_config.batch_size, rank, world, shuffle=True,
                                  seed=base_seed + 1 + k)
         samplers.append(bs)
@@ -286,6 +296,7 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
               (f", learn_comm on {model_config.comm or 'full'}" if learned is not None else "") +
               (f", temperature {t_ends}, explore_eps {e_ends}" if t_ends or e_ends else "") +
               (f", augment {policy.spec}" if policy is not None else "") +
+              (f", mix {mix_policy.spec}" if mix_policy is not None else "") +
               (f", class weights {cw_spec if isinstance(cw_spec, str) else 'given'}" if cw_spec is not None else "") +
               (f", label_smoothing {train_config.label_smoothing}" if train_config.label_smoothing else "") +
               (f", error steps {train_config.error_steps}" if train_config.error_steps else "") +

@@ -18,7 +18,7 @@ import torch as th
 from ..core import EpisodeSampler
 from ..engine import EpisodeTensors
 from ..fused import (ClassLossOptions, CommUpdate, OptimRun, apply_update, check_ppo_options, comm_update_for, ppo_bufs_fit,
-                     ppo_epochs_loop, ppo_options_on)
+                     ppo_epochs_loop, ppo_options_on, soft_targets_installed)
 from ..metrics import ConfusionMeter, LossMeter
 from ..networks import ModelsWrapper
 
@@ -155,7 +155,12 @@ class Trainer:
         call(2)
 
     # one optimisation step on a batch (reference trainer.py:67-116)
-    def train_step(self, x: th.Tensor, y: th.Tensor, sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
+    def train_step(self, x: th.Tensor, y: th.Tensor, sampler: EpisodeSampler,
+                   targets: Optional[th.Tensor] = None) -> Tuple[EpisodeTensors, th.Tensor]:
+        """``targets``: fp32 [Nb, nC] target distributions on the device (``mix.soft_targets`` of a CutMix / Mixup
+        batch, a teacher's distribution) that the vote error and the rewards take in place of ``y``
+        (``HipEngine.set_soft_targets``), installed around this step's loss calls - every PPO epoch among them - and
+        cleared behind them; ``y`` stays the hard label for the meters."""
         model = self.__model
         y = y.to(model.device)
         if self.temperature is not None or self.explore_eps is not None:  # (checked here: ValueError before any call)
@@ -163,7 +168,7 @@ class Trainer:
             model.set_exploration(x0.temperature if self.temperature is None else self.temperature,
                                   x0.eps if self.explore_eps is None else self.explore_eps, x0.greedy)
         if self.__ppo:
-            return self.__train_step_ppo(x, y, sampler)
+            return self.__train_step_ppo(x, y, sampler, targets)
         # with the entropy bonus: the same sequence through the three entries that carry the step distributions
         # (scalars[4] = the mean entropy)
         beta = self.__entropy_coef
@@ -173,15 +178,15 @@ class Trainer:
         if (bufs is None or len(bufs) != (6 if ent else 5) or bufs[0].shape != out.step_preds.shape or
                 (ent and bufs[5].shape != out.step_probs.shape)):
             bufs = self.__loss_bufs = eng.new_loss_bufs(out, ent)
-        with self.__class_loss.installed(eng):
+        with self.__class_loss.installed(eng), soft_targets_installed(eng, targets):
             self.__exact_phases(lambda phase: eng.a2c_loss(out, y, self.__gamma, phase, bufs, entropy_coef=beta))
         flat = model.flat_state()
         apply_update(eng, flat, bufs[0], bufs[1], bufs[2], bufs[5] if ent else None, flat.grad_views(), self.__lr,
                      self.__allreduce, None, lambda: model.mark_updated(eng), self.__comm(), self.__optim)
         return out, bufs[3]
 
-    def __train_step_ppo(self, x: th.Tensor, y: th.Tensor,
-                         sampler: EpisodeSampler) -> Tuple[EpisodeTensors, th.Tensor]:
+    def __train_step_ppo(self, x: th.Tensor, y: th.Tensor, sampler: EpisodeSampler,
+                         targets: Optional[th.Tensor] = None) -> Tuple[EpisodeTensors, th.Tensor]:
         """One rollout, K updates.  Returns the ROLLOUT's outputs (meters and confusion matrix stay on-policy) and
         the last epoch's scalars {loss, surrogate, error, critic, entropy, approx_kl, clip_frac}."""
         model, beta = self.__model, self.__entropy_coef
@@ -194,7 +199,7 @@ class Trainer:
             self.__ppo_bufs = eng.new_ppo_bufs(out, ent)
         bufs = self.__ppo_bufs
         flat = model.flat_state()
-        with self.__class_loss.installed(eng):
+        with self.__class_loss.installed(eng), soft_targets_installed(eng, targets):
             self.__exact_phases(lambda phase: eng.advantages(out, y, self.__gamma, self.__gae_lambda, phase, bufs))
             norm = ppo_epochs_loop(
                 eng, flat, out, y, bufs, self.__ppo_epochs, self.__ppo_clip, beta, self.__lr, self.__allreduce,
@@ -208,8 +213,8 @@ class Trainer:
 
     def train_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler) -> None:
         self.__model.train()
-        for x_train, y_train in dataloader:
-            out, scalars = self.train_step(x_train, y_train, episode_sampler)
+        for x_train, y_train, *rest in dataloader:  # (a mixing loader yields (x, y_primary, Q): data.py)
+            out, scalars = self.train_step(x_train, y_train, episode_sampler, targets=rest[0] if rest else None)
             # device-side meters, no sync (select last step, mean over agents: trainer.py:124-128)
             self.__conf_meter.add(out.step_preds[-1].mean(dim=0), y_train)
             for k in self.__meter_keys:
