@@ -100,8 +100,12 @@ MIX_ENTRIES = ("marl_batch_mix", "marl_batch_mix_plan")
 OPTIM_ENTRIES = ("marl_optim_step",)
 # ... and the kernel-level hooks of the row-panel kernels that include/marl_hip_panelops.h declares (tests only)
 PANELOP_HOOKS = ("marl_panel_fwd", "marl_panel_bwd", "marl_panel_scratch_bytes", "marl_panel_plan")
+# ... and the host-only witness of the matrix-product launchers that include/marl_hip_gemmops.h declares (tests only)
+GEMMOP_HOOKS = ("marl_gemm_plan",)
 _HOOKS = (ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES +
-          PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES)
+          PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES + GEMMOP_HOOKS)
+# the launchers marl_gemm_plan answers for (its `kind`)
+GEMM_KINDS = ("nt", "lstm", "tn", "nt_images", "lstm_images", "tn_images", "tn_images_cell")
 MARL_PANEL_MAX_LAYERS = 4
 
 
@@ -169,6 +173,19 @@ class PanelPlan(C.Structure):
             v = getattr(self, name)
             out[name] = list(v)[: self.nlayers] if name in self._PER_LAYER else (list(v) if name == "by_batch" else v)
         return out
+
+
+class GemmPlan(C.Structure):
+    """Mirror of ``marl_gemm_plan_info`` (include/marl_hip_gemmops.h)."""
+
+    _fields_ = ([(name, C.c_int32) for name in (
+        "kind family variant row_id bm bn wm wn nst pipelined threads gx gy gz blocks xcd_map single_buf pre safe "
+        "splits").split()] + [("rows_per_split", C.c_int64)] +
+        [(name, C.c_int32) for name in "ok teams ih256 ih128 hh256 hh128".split()] +
+        [("lds_bytes", C.c_uint64), ("scratch_bytes", C.c_uint64)])
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class CnnBwdPlan(C.Structure):
@@ -310,6 +327,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_panel_scratch_bytes.argtypes = [_i, _i, C.POINTER(_i), C.POINTER(_i)]
     lib.marl_panel_fwd.argtypes = [C.POINTER(PanelFwdProb), _i, _vp, _sz, _vp]
     lib.marl_panel_bwd.argtypes = [C.POINTER(PanelBwdProb), _vp, _sz, _vp]
+    lib.marl_gemm_plan.argtypes = [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i64, _i, _i, C.POINTER(GemmPlan)]
     lib.marl_panel_plan.argtypes = [C.POINTER(PanelFwdProb), _i, C.POINTER(PanelBwdProb), C.POINTER(PanelPlan)]
     for name in EXPORTS + list(_HOOKS):
         fn = getattr(lib, name)

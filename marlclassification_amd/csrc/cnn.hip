@@ -832,17 +832,8 @@ static bool fwd2_matches(const CnnFwdArgs& a) {
 constexpr int kFwd2Rows = 8;  // patches per chunk of cnn_fwd2_kernel: one per wave
 static int fwd2_grid(int64_t nchunks) { return nchunks < 256 ? (int)nchunks : 256; }
 
-// The device-dependent steps of the conv launchers (everything else is host arithmetic in their plan routines).
-// Raises a kernel's dynamic-LDS limit the first time the kernel is seen (per process; one process drives one GPU).
-static hipError_t cnn_raise_lds(const void* kern, int bytes) {
-    static const void* done[64];
-    static int ndone = 0;
-    for (int i = 0; i < ndone; ++i)
-        if (done[i] == kern) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess && ndone < 64) done[ndone++] = kern;
-    return e;
-}
+// The device-dependent steps of the conv launchers (everything else is host arithmetic in their plan routines):
+// raise_lds (common.h) and this one.
 // resident 512-thread workgroups per CU of a kernel at this dynamic LDS size (registers, LDS, wave slots); the same
 // instantiation serves layers with different LDS sizes, so the answer is cached per (kernel, LDS bytes)
 static int cnn_occupancy(const void* kern, size_t lds) {
@@ -865,7 +856,7 @@ template <class N>
 static int fwd2_launch(CnnFwdArgs& a, const CnnFwdPlan& p, hipStream_t st) {
     auto kern = cnn_fwd2_kernel<N>;
     const size_t lds = p.lds_bytes;
-    MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
+    MARL_HIP_CHECK(raise_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
     const int nchunks = (int)cdiv(a.rows, p.rb);
     const int blocks = p.blocks;
 #ifdef MARL_KERNEL_TS
@@ -1384,7 +1375,7 @@ template <class N, class PL>
 static int fwd3_launch(CnnFwdArgs& a, const CnnFwdPlan& p, hipStream_t st) {
     auto kern = cnn_fwd3_kernel<N, PL>;
     const size_t lds = p.lds_bytes;
-    MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
+    MARL_HIP_CHECK(raise_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
     const int ngroups = (int)cdiv(a.rows, p.rb);
     const int blocks = p.blocks;
 #ifdef MARL_KERNEL_TS
@@ -1506,7 +1497,7 @@ int launch_cnn_fwd(CnnFwdArgs& a, hipStream_t st) {
         default: set_error("fused CNN forward: window %d outside its range", a.f); return MARL_ELIMIT;
     }
     const size_t lds = p.lds_bytes;
-    MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(cnn_fwd_kernel), 144 * 1024));
+    MARL_HIP_CHECK(raise_lds(reinterpret_cast<const void*>(cnn_fwd_kernel), 144 * 1024));
 #ifdef MARL_KERNEL_TS
     static long long* d_ts = nullptr;
     static int calls = 0;
@@ -1951,7 +1942,7 @@ static int cnn_dgrad_grid(const CnnDgradPlan& p) {
     static int num_cu = 0;
     if (p.rb <= 0) return 0;
     const void* kern = reinterpret_cast<const void*>(cnn_dgrad_kernel);
-    (void)cnn_raise_lds(kern, 144 * 1024);
+    (void)raise_lds(kern, 144 * 1024);
     if (!num_cu) {
         int dev = 0;
         hipDeviceProp_t prop;
@@ -2762,7 +2753,7 @@ CnnWgradPlan cnn_wgrad_plan(CnnWgradArgs& a) {
 using WgradLaunchFn = int (*)(CnnWgradArgs&, const CnnWgradPlan&, hipStream_t);
 template <class Kern>
 static int wgrad_launch_kernel(Kern kern, bool raise, CnnWgradArgs& a, const CnnWgradPlan& p, hipStream_t st) {
-    if (raise) MARL_HIP_CHECK(cnn_raise_lds(reinterpret_cast<const void*>(kern), 150 * 1024));
+    if (raise) MARL_HIP_CHECK(raise_lds(reinterpret_cast<const void*>(kern), 150 * 1024));
     int res = 256 * cnn_occupancy(reinterpret_cast<const void*>(kern), p.lds_bytes) / a.slabs;
     if (res < 64) res = 64;
     if (res < a.blocks) a.blocks = res;

@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "../../include/marl_hip.h"
+#include "../../include/marl_hip_gemmops.h"
 #include "split.h"
 
 namespace marl {
@@ -147,12 +148,29 @@ __device__ __forceinline__ void xcd_tile(unsigned gx, unsigned gy, unsigned gz, 
     bx = r / gy;
     by = r - bx * gy;
 }
-int xcd_map_enabled();
+
+// Raises a kernel's dynamic-LDS limit (above the 64 KiB a launch may ask for by default) the first time the kernel is
+// seen (per process; one process drives one GPU).
+inline hipError_t raise_lds(const void* kern, size_t bytes) {
+    static const void* done[128];
+    static int ndone = 0;
+    for (int i = 0; i < ndone; ++i)
+        if (done[i] == kern) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && ndone < 128) done[ndone++] = kern;
+    return e;
+}
 
 GemmProb gemm_prob(const float* a, int lda, const GemmB& b, float* c, int ldc, int m, int n,
                    const float* bias = nullptr, int accumulate = 0);
 void gemm_add_seg(GemmProb& p, const float* a, int lda, const GemmB& b);
 
+// What a launcher does with a shape: one struct for all of them, the one marl_gemm_plan hands out (marl_hip_gemmops.h
+// documents the fields).  A launcher calls its planning routine once; nothing below asks a knob the plan answers.
+using GemmPlan = marl_gemm_plan_info;
+inline dim3 plan_grid(const GemmPlan& p) { return p.xcd_map ? dim3(p.gx * p.gy * p.gz) : dim3(p.gx, p.gy, p.gz); }
+GemmPlan gemm_nt_plan(const GemmBatch& batch);
+GemmPlan gemm_lstm_plan(const GemmBatch& batch);
 int launch_gemm_nt(const GemmBatch& batch, hipStream_t st);
 // LSTM cell: gates = seg products + bias over 4*n_units rows of B, then the cell update.
 int launch_gemm_lstm(const GemmBatch& batch, hipStream_t st);
@@ -161,6 +179,7 @@ int launch_gemm_lstm(const GemmBatch& batch, hipStream_t st);
 // terms while they are staged, six bf16 MFMA products per fp32 product, fp32 accumulation.
 // split_mode(): knob "mfma_split" (default 1); 0 = the exact-fp32 v_mfma_f32_32x32x2_f32 kernels.
 int split_mode();
+constexpr int kSplitRowBytes = 80;  // LDS bytes per tile row of these kernels: 32 bf16 + 16 B pad (3 stages in all of them)
 // Pre-split images of the weight matrices (built by marl_pack_weights next to their fp32 copies):
 // a matrix [rows][ld] fp32 with k valid columns -> [rows][ceil(k / 32)][3][32] bf16, zero-padded.
 size_t split_image_floats(int rows, int k);  // size of an image in units of 4 bytes
@@ -176,11 +195,9 @@ struct SplitBatch {
 };
 int launch_split_weights(const SplitBatch& b, hipStream_t st);
 // The NT launchers take the image-copying kernels when every segment of the batch carries an image (GemmB).
-int launch_gemm_nt_split(const GemmBatch& batch, int max_m, int max_n, int64_t blocks128, hipStream_t st);
-int launch_gemm_lstm_split(const GemmBatch& batch, int max_m, int max_n, hipStream_t st);
+int launch_gemm_nt_split(const GemmBatch& batch, const GemmPlan& plan, bool lstm, hipStream_t st);
 int launch_gemm_tn_split(const float* a, int lda, const float* b, int ldb, float* out, int ldo,
-                         int64_t stride, int ni, int nj, int64_t rows, int64_t rows_per_split,
-                         float* csum, dim3 grid, int gx, int gy, int gz, hipStream_t st);
+                         int64_t stride, int ni, int nj, int64_t rows, float* csum, const GemmPlan& plan, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // Image GEMMs (gemm3.hip): both operands are k16 images (split.h) written by their producers
@@ -221,9 +238,11 @@ struct G3Batch {
 G3Prob g3_prob(const void* a3, int a_row0, const void* b3, int b_row0, int k, float* c, int ldc, int m, int n,
                const float* bias = nullptr, int accumulate = 0);
 void g3_add_seg(G3Prob& p, const void* a3, int a_row0, const void* b3, int b_row0, int k);
+// variant 0: the knob, else the automatic choice by launch size.  Reads m and n of the problems only.
+GemmPlan g3_nt_plan(const G3Batch& batch, int variant = 0);
+GemmPlan g3_lstm_plan(const G3Batch& batch, int variant = 0);  // (marl_plan_query reports .variant)
 int launch_gemm_nt3(const G3Batch& batch, hipStream_t st, int variant = 0);
 int launch_gemm_lstm3(const G3Batch& batch, hipStream_t st, int variant = 0);
-int g3_lstm_plan(const G3Batch& batch);  // the tile plan launch_gemm_lstm3 takes for this batch (marl_plan_query reports it)
 // weight-gradient form: contraction over the ROWS of two images (gemm_tn3_kernel)
 struct G3TnArgs {
     const char* a3;
@@ -242,11 +261,7 @@ struct G3TnArgs {
     int abl;
 #endif
 };
-struct G3TnPlan {
-    int variant, splits;
-    int64_t rows_per_split;
-};
-G3TnPlan g3_tn_plan(int ni, int nj, int64_t rows);
+GemmPlan g3_tn_plan(int ni, int nj, int64_t rows, bool launch = true);  // (as tn_plan)
 // Both weight gradients of ONE LSTM cell - dW_ih = G^T U and dW_hh = G^T H, the same gate-gradient image G as
 // A - as one launch (gemm_tn3_cell_kernel): the column tiles of U and of H that belong to the same (256-column
 // tile of G, row slab) are adjacent workgroups on one XCD, run in step and share G's slab through that XCD's L2,
@@ -259,12 +274,12 @@ struct G3TnCell {
     int gx, gz;
     int teams;               // equal-work team dispatch (see the kernel)
 };
-bool g3_tn_cell_ok(int ni, int nj_ih, int nj_hh, int64_t rows);
-G3TnPlan g3_tn_cell_plan(int ni, int nj_ih, int nj_hh, int64_t rows);
-size_t g3_tn_cell_scratch_bytes(int ni, int nj_ih, int nj_hh, int64_t rows);
-int launch_gemm_tn3_cell(G3TnArgs ih, G3TnArgs hh, const G3TnPlan& plan, hipStream_t st);
-size_t g3_tn_scratch_bytes(int ni, int nj, int64_t rows);
-int launch_gemm_tn3(G3TnArgs a, const G3TnPlan& plan, hipStream_t st);
+GemmPlan g3_tn_cell_plan(int ni, int nj_ih, int nj_hh, int64_t rows);
+int gemm_tn3(const GemmPlan& plan, const char* a3, int ni, const char* b3, int nj, int64_t rows, float* c, int ldc,
+             float* colsum, float* scratch, hipStream_t st);
+int gemm_tn3_cell(const GemmPlan& plan, const char* g3, int ni, const char* u3, int nih, const char* h3, int nhh,
+                  int64_t rows, float* c_ih, int ld_ih, float* c_hh, int ld_hh, float* colsum, float* scratch,
+                  hipStream_t st);
 
 // fp32 [rows][ld] (k valid columns) -> its image (rows padded to whole blocks: zeros)
 struct ImgDesc {
@@ -289,6 +304,7 @@ int profile_end(double* total_ms, int* launches);
 
 struct RedQueue;
 // C[NI,NJ] = sum_r A[r,i] * B[r,j]  (weight gradients; contraction over rows).
+GemmPlan tn_plan(int ni, int nj, int64_t rows, bool launch = true);  // launch = false: sizing only, no launch knob read
 size_t gemm_tn_scratch_bytes(int ni, int nj, int64_t rows);
 // colsum_out (nullable): also writes out[i] = sum_r A[r,i] (the matching bias gradient)
 // q != null: the slab reduction is queued there instead of launched (scratch comes from q too)
@@ -325,7 +341,6 @@ struct TnQueue {
     Item it[kMaxTnBatch];
     int n = 0;
 };
-bool gemm_tn_is_small(int ni, int nj, int64_t rows);  // takes the 64 x 64 plan
 // launches what is queued; the split slabs live in q's scratch and their reductions are queued there
 int launch_tn_queue(TnQueue& tq, RedQueue* q, hipStream_t st);
 

@@ -321,6 +321,8 @@ struct ELayout {
     size_t U3, H3, HC3;  // images of U (train: every step, else one slice), H / H^ [(Ns+1) R]
     size_t u3_stride_rows;  // image rows between the U3 slices of consecutive steps (0: one shared slice)
     bool g3;
+    // both weight gradients of the belief [0] / action [1] cell from one launch: planned where the scratch is sized
+    GemmPlan tn_cell[2];
     size_t PART, TNS, LOSS;
     size_t RED, red_floats;  // scratch of the deferred-reduction queue (sum over every use)
     size_t part_floats, tns_bytes, loss_floats;
@@ -479,7 +481,10 @@ static void make_elayout(const Dims& d, const WLayout& w, int train, ELayout& e)
     e.g3 = g3_enabled(d);
     e.GB3 = e.GA3 = e.U3 = e.H3 = e.HC3 = 0;
     e.u3_stride_rows = 0;
+    e.tn_cell[0] = e.tn_cell[1] = GemmPlan{};
     if (e.g3) {
+        e.tn_cell[0] = g3_tn_cell_plan(4 * d.n_b, d.nin, d.n_b, d.NR);
+        e.tn_cell[1] = g3_tn_cell_plan(4 * d.n_a, d.nin, d.n_a, d.NR);
         e.u3_stride_rows = train ? R : 0;
         e.U3 = b.take(img_bytes((int64_t)(train ? NR : R), d.nin) / sizeof(float));
         e.H3 = b.take(img_bytes((int64_t)(S1 * R), d.n_b) / sizeof(float));
@@ -563,16 +568,11 @@ static void make_elayout(const Dims& d, const WLayout& w, int train, ELayout& e)
         if (e.g3) {  // the same four products on images (gemm_tn3_kernel) have their own split plan
             const int tn3[4][2] = {{4 * d.n_b, d.nin}, {4 * d.n_b, d.n_b}, {4 * d.n_a, d.nin}, {4 * d.n_a, d.n_a}};
             for (const auto& q : tn3) {
-                const size_t v = g3_tn_scratch_bytes(q[0], q[1], nr);
+                const size_t v = g3_tn_plan(q[0], q[1], nr, false).scratch_bytes;
                 tns = v > tns ? v : tns;
             }
-            // (both products of a cell in one launch: their slabs side by side)
-            const int cell[2][3] = {{4 * d.n_b, d.nin, d.n_b}, {4 * d.n_a, d.nin, d.n_a}};
-            for (const auto& q : cell)
-                if (g3_tn_cell_ok(q[0], q[1], q[2], nr)) {
-                    const size_t v = g3_tn_cell_scratch_bytes(q[0], q[1], q[2], nr);
-                    tns = v > tns ? v : tns;
-                }
+            // (both products of a cell in one launch: their slabs side by side; 0 bytes outside the plan)
+            for (const GemmPlan& q : e.tn_cell) tns = q.scratch_bytes > tns ? q.scratch_bytes : tns;
         }
         upd_tn(d.n_d, 2, nr);
         for (int l = 0; l < d.L; ++l) {
@@ -661,6 +661,7 @@ struct Plan {
     bool panel_sample;  // ... whose policy workgroups sample as their epilogue
     bool g3_lstm;       // both cells and the heads' first layers from k16 images (gemm3.hip)
     bool g3_tn, g3_tn_pipe;  // the four large weight gradients from images; ... phase-pipelined
+    bool g3_tn_cell;         // ... and both cells take the one-launch-per-cell form (ELayout::tn_cell)
     bool u3_by_producers;    // the kernels that write U also write its image (no separate pass)
     int skip_f32;       // every consumer of the gate gradients reads their images: no fp32 copy at all
     int lstm_plan;      // tile plan of the two-cell LSTM launch (gemm3.hip: 2 = 128-row tiles, 3 / 4 = the 32- / 64-row
@@ -764,8 +765,7 @@ static Plan make_plan(const Dims& d, const WLayout& w, const ELayout& e, const I
         b.p[0].m = b.p[1].m = (int)d.R;
         b.p[0].n = d.n_b;
         b.p[1].n = d.n_a;
-        p.lstm_plan = tune_get("g3_lstm_variant", 0);
-        if (!p.lstm_plan) p.lstm_plan = g3_lstm_plan(b);
+        p.lstm_plan = g3_lstm_plan(b).variant;
     }
     // the four large weight gradients on images (gemm_tn3_kernel: 256-column tiles of A, whole 256 x 256 tiles
     // or column passes, g3_tn_plan): only where that form wins - >= 32768 contraction rows (at C4's 8192 rows the
@@ -773,9 +773,9 @@ static Plan make_plan(const Dims& d, const WLayout& w, const ELayout& e, const I
     // (round 5: the one-launch-per-cell form wins from 8 192 rows on - C4 at 32 images per GPU: 3.62 vs 3.69 ms)
     p.g3_tn = p.g3_lstm && k_tn != 0 &&
               (k_tn == 2 || (d.nin <= 640 && d.n_b <= 512 && d.n_a <= 512 &&
-                             (d.NR >= 32768 || (g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) &&
-                                                g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR)))));
-    p.g3_tn_pipe = p.g3_tn && tune_get("g3_tn_pipe", 1) != 0;
+                             (d.NR >= 32768 || (e.tn_cell[0].ok && e.tn_cell[1].ok))));
+    p.g3_tn_cell = p.g3_tn && e.tn_cell[0].ok && e.tn_cell[1].ok;
+    p.g3_tn_pipe = p.g3_tn && e.tn_cell[0].pipelined;  // (knob g3_tn_pipe: g3_tn_cell_plan carries it even when !ok)
     p.skip_f32 = p.panels_bwd && p.g3_tn;
     // the three kernels that write U[t] (fused CNN: features; decoder panel: message columns; sampling
     // launch: position embedding) also write its image when all of them are on the path and the column
@@ -1529,57 +1529,22 @@ static int tn(const Ctx& c, const float* a, int lda, const float* b, int ldb, in
 }
 // the same from images (rows = contraction index; A [rows, ni], B [rows, nj], both starting at image row 0)
 static int tn3(const Ctx& c, const char* a3, int ni, const char* b3, int nj, int pidx, int64_t rows, float* bias) {
-    const G3TnPlan plan = g3_tn_plan(ni, nj, rows);
-    if (g3_tn_scratch_bytes(ni, nj, rows) > c.e.tns_bytes) {
+    const GemmPlan plan = g3_tn_plan(ni, nj, rows);
+    if (plan.scratch_bytes > c.e.tns_bytes) {
         set_error("tn3: scratch too small");
         return MARL_ESIZE;
     }
-    float* scratch = c.at(c.e.TNS);
-    G3TnArgs a{};
-    a.a3 = a3;
-    a.b3 = b3;
-    a.a_steps = img_steps(ni);
-    a.b_steps = img_steps(nj);
-    a.out = scratch;
-    a.ldo = nj;
-    a.out_split_stride = (int64_t)ni * nj;
-    a.ni = ni;
-    a.nj = nj;
-    a.rows = rows;
-    a.csum = bias ? scratch + (size_t)plan.splits * ni * nj : nullptr;
-    MARL_TRY(launch_gemm_tn3(a, plan, c.st));
-    return launch_slab_reduce(scratch, (int64_t)ni * nj, plan.splits, c.gp(pidx), c.w.ldp[pidx], ni, nj, a.csum, bias, c.st);
+    return gemm_tn3(plan, a3, ni, b3, nj, rows, c.gp(pidx), c.w.ldp[pidx], bias, c.at(c.e.TNS), c.st);
 }
 // both weight gradients of one LSTM cell from one launch (gemm3.hip, gemm_tn3_cell_kernel): G read once
-static int tn3_cell(const Ctx& c, const char* g3, int ni, const char* u3, int nin, int p_ih, const char* h3, int nh,
-                    int p_hh, int64_t rows, float* bias) {
-    const G3TnPlan plan = g3_tn_cell_plan(ni, nin, nh, rows);
-    if (g3_tn_cell_scratch_bytes(ni, nin, nh, rows) > c.e.tns_bytes) {
+static int tn3_cell(const Ctx& c, const GemmPlan& plan, const char* g3, int ni, const char* u3, int nin, int p_ih,
+                    const char* h3, int nh, int p_hh, int64_t rows, float* bias) {
+    if (plan.scratch_bytes > c.e.tns_bytes) {
         set_error("tn3_cell: scratch too small");
         return MARL_ESIZE;
     }
-    float* s_ih = c.at(c.e.TNS);
-    float* s_hh = s_ih + (size_t)plan.splits * ni * nin;
-    float* s_cs = s_hh + (size_t)plan.splits * ni * nh;
-    G3TnArgs ih{}, hh{};
-    ih.a3 = hh.a3 = g3;
-    ih.a_steps = hh.a_steps = img_steps(ni);
-    ih.ni = hh.ni = ni;
-    ih.rows = hh.rows = rows;
-    ih.b3 = u3;
-    ih.b_steps = img_steps(nin);
-    ih.nj = ih.ldo = nin;
-    ih.out = s_ih;
-    ih.out_split_stride = (int64_t)ni * nin;
-    ih.csum = bias ? s_cs : nullptr;  // (the column sums of G ride on the first tile of the launch)
-    hh.b3 = h3;
-    hh.b_steps = img_steps(nh);
-    hh.nj = hh.ldo = nh;
-    hh.out = s_hh;
-    hh.out_split_stride = (int64_t)ni * nh;
-    MARL_TRY(launch_gemm_tn3_cell(ih, hh, plan, c.st));
-    MARL_TRY(launch_slab_reduce(s_ih, (int64_t)ni * nin, plan.splits, c.gp(p_ih), c.w.ldp[p_ih], ni, nin, nullptr, nullptr, c.st));
-    return launch_slab_reduce(s_hh, (int64_t)ni * nh, plan.splits, c.gp(p_hh), c.w.ldp[p_hh], ni, nh, ih.csum, bias, c.st);
+    return gemm_tn3_cell(plan, g3, ni, u3, nin, h3, nh, rows, c.gp(p_ih), c.w.ldp[p_ih], c.gp(p_hh), c.w.ldp[p_hh], bias,
+                         c.at(c.e.TNS), c.st);
 }
 // scratch for `blocks` affine partial rows of width 2n: the queue's when the reduction can wait
 static float* part_scratch(const Ctx& c, int64_t blocks, int n, int acc, RedQueue*& q) {
@@ -2075,8 +2040,8 @@ static int bwd_chain_wgrads(const BwdState& s) {
             // the forward kernels (U) and the LSTM epilogues (h, h^); bias gradients = column sums of A
             const char* g3 = c.img(which ? c.e.GA3 : c.e.GB3);
             const char* h3 = c.img(which ? c.e.HC3 : c.e.H3);
-            if (g3_tn_cell_ok(4 * n, d.nin, n, NR)) {
-                MARL_TRY(tn3_cell(c, g3, 4 * n, c.img(c.e.U3), d.nin, p_ih, h3, n, p_hh, NR, bias));
+            if (c.e.tn_cell[which].ok) {
+                MARL_TRY(tn3_cell(c, c.e.tn_cell[which], g3, 4 * n, c.img(c.e.U3), d.nin, p_ih, h3, n, p_hh, NR, bias));
             } else {
                 MARL_TRY(tn3(c, g3, 4 * n, c.img(c.e.U3), d.nin, p_ih, NR, nullptr));
                 MARL_TRY(tn3(c, g3, 4 * n, h3, n, p_hh, NR, bias));
@@ -3061,7 +3026,7 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     else if (!strcmp(key, "lstm_plan")) *value = plan.lstm_plan;
     else if (!strcmp(key, "small_r")) *value = plan.lstm_plan == 3 || plan.lstm_plan == 4;  // one of the gate-split plans
     else if (!strcmp(key, "g3_tn_cell"))  // both weight gradients of a cell from one launch (gemm_tn3_cell_kernel)
-        *value = plan.g3_tn && g3_tn_cell_ok(4 * d.n_b, d.nin, d.n_b, d.NR) && g3_tn_cell_ok(4 * d.n_a, d.nin, d.n_a, d.NR);
+        *value = plan.g3_tn_cell;
     else if (!strcmp(key, "g3_tn_pipe")) *value = plan.g3_tn_pipe;  // only where the image weight gradients run
     else if (!strcmp(key, "wgrad3")) {  // a conv weight gradient of this model runs on the bf16 pipe (cin >= 16)
         *value = 0;

@@ -19,7 +19,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;          // row depth of one staged tile of the TN kernel
 
-
 // (gate non-linearities of the fused LSTM epilogue: sigmoid_acc / tanh_fast of common.h; the accurate
 // libm forms cost ~10 us per launch in the epilogue of a 120 us kernel)
 
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(256 * GROUPS) void gemm_nt_kernel(const GemmBatch b
                           (grp * BM + wm * (BM / WM) + frag_row) * LDS_K + frag_k;         \
         const float* Bs = smem + (buf_) * BUF + GROUPS * BM * LDS_K +                      \
                           (wn * (BN / WN) + frag_row) * LDS_K + frag_k;                    \
-        if (LSTM) __builtin_amdgcn_s_setprio(1); /* compile-time: see launch_nt_variant */ \
+        if (LSTM) __builtin_amdgcn_s_setprio(1); /* compile-time: see launch_nt_fp32 */ \
         _Pragma("unroll") for (int kk = 0; kk < BK / 8; ++kk) {                            \
             float4 a4[TM], b4[TN];                                                         \
             _Pragma("unroll") for (int i = 0; i < TM; ++i)                                 \
@@ -892,43 +891,65 @@ void gemm_add_seg(GemmProb& p, const float* a, int lda, const GemmB& b) {
     p.nseg = 2;
 }
 
-
-template <int BM, int BN, int WM, int WN, bool LSTM, int GROUPS>
-static int launch_nt_variant(dim3 grid, const GemmBatch& batch_in, hipStream_t st) {
-    GemmBatch batch = batch_in;
-    batch.gx = (int)grid.x;
-    batch.gy = (int)grid.y;
+// The tile plan of an NT / LSTM launch (common.h, GemmPlan).  fp32 family: 128 x 128 tiles with one LDS stage when
+// they fill the chip, else 64 x 64 with two; bf16x6 family: 128-row tiles, 128 columns wide when they fill the chip
+// (two workgroups per CU), else 64; the LSTM kernels of both: 128 rows x 32 units.
+static GemmPlan nt_plan(const GemmBatch& batch, bool lstm) {
+    int max_m = 0, max_n = 0;
+    int64_t blocks128 = 0;
+    for (int i = 0; i < batch.count; ++i) {
+        max_m = batch.p[i].m > max_m ? batch.p[i].m : max_m;
+        max_n = batch.p[i].n > max_n ? batch.p[i].n : max_n;
+        blocks128 += cdiv(batch.p[i].m, 128) * cdiv(batch.p[i].n, 128);
+    }
+    GemmPlan p{};
+    p.kind = lstm ? MARL_GEMM_LSTM : MARL_GEMM_NT;
+    p.family = split_mode() != 0;
+    p.threads = 256;
+    if (lstm) p.bm = p.bn = 128;
+    else if (p.family) p.bm = 128, p.bn = blocks128 >= 384 && max_n >= 96 ? 128 : 64;
+    else p.bm = p.bn = blocks128 >= 256 && max_n >= 96 ? 128 : 64;
+    p.gx = (int)cdiv(max_m, p.bm);
+    p.gy = (int)cdiv(max_n, lstm ? 32 : p.bn);
+    p.gz = batch.count;
+    p.blocks = p.gx * p.gy * p.gz;
     // XCD-ordered tiles (column block fastest inside an XCD's chunk) when the launch is ONE
     // product: its row panels are then read through one L2 once.  Batched launches of unequal
     // problems would load the XCDs unevenly (measured slower), they keep the plain order.
-    batch.xcd_map = xcd_map_enabled() || (batch.count == 1 && !LSTM && tune_get("nt_xcd", 1));
-    if (batch.xcd_map) grid = dim3(grid.x * grid.y * grid.z);
-    constexpr size_t lds2 = (size_t)2 * (GROUPS * BM + BN) * (32 + 4) * sizeof(float);
-    batch.single_buf = GROUPS == 1 && !LSTM && BM == 128 && true;
+    p.xcd_map = batch.count == 1 && !lstm && tune_get("nt_xcd", 1);
+    if (p.family) {
+        p.pre = 1;
+        for (int i = 0; i < batch.count && p.pre; ++i)
+            for (int sg = 0; sg < batch.p[i].nseg && p.pre; ++sg) {
+                const GemmSeg& g = batch.p[i].seg[sg];
+                // 32-bit byte offsets into the image
+                p.pre = g.b3 && (int64_t)(lstm ? 4 : 1) * batch.p[i].n * g.kt3 * 192 < (1ll << 32);
+            }
+        p.lds_bytes = (size_t)3 * (128 + p.bn) * kSplitRowBytes;
+    } else {
+        p.single_buf = !lstm && p.bm == 128;
+        p.lds_bytes = (size_t)(p.single_buf ? 1 : 2) * (p.bm + p.bn) * (32 + 4) * sizeof(float);
+    }
+    return p;
+}
+GemmPlan gemm_nt_plan(const GemmBatch& batch) { return nt_plan(batch, false); }
+GemmPlan gemm_lstm_plan(const GemmBatch& batch) { return nt_plan(batch, true); }
+
+template <int BM, int BN, int WM, int WN, bool LSTM>
+static int launch_nt_fp32(GemmBatch batch, const GemmPlan& plan, hipStream_t st) {
+    batch.gx = plan.gx;
+    batch.gy = plan.gy;
+    batch.xcd_map = plan.xcd_map;
+    batch.single_buf = plan.single_buf;
     // (LSTM instantiation: s_setprio(1) around the matrix phase - the scheduler prefers the wave
     // that is feeding the matrix pipe over a co-resident one that is staging: -3 % on the launch.
     // Compile-time only: even a never-taken run-time branch around the cluster cost the other
     // plans 3-4 %, it splits the block in which the compiler interleaves LDS reads and MFMAs.)
-    const size_t lds = batch.single_buf ? lds2 / 2 : lds2;
-    auto kern = gemm_nt_kernel<BM, BN, WM, WN, LSTM, GROUPS>;
-    if (lds2 > 64 * 1024) {
-        static bool raised = false;  // opt in to > 64 KiB of dynamic LDS once per kernel
-        if (!raised) {
-            MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256 * GROUPS), lds, st, batch);
+    auto kern = gemm_nt_kernel<BM, BN, WM, WN, LSTM, 1>;
+    if (plan.lds_bytes > 64 * 1024) MARL_HIP_CHECK(raise_lds(reinterpret_cast<const void*>(kern), plan.lds_bytes));
+    hipLaunchKernelGGL(kern, plan_grid(plan), dim3(plan.threads), plan.lds_bytes, st, batch);
     return MARL_OK;
 }
-
-int xcd_map_enabled() { return 0; }  // (the fp32-operand NT kernels: measured neutral-to-negative; the image kernels map by knob nt_xcd / tn_xcd)
-
-// 1 = plain 4-wave loop (default), 2 = ping-pong wave groups (MARL_GEMM_GROUPS=2).  Measured on
-// MI355X: the two-group schedule gains 2-7 % on single large products (M = 65536) but loses
-// on this workload's small / batched products (bigger tiles -> worse tail), so it is opt-in.
-static int gemm_groups() { return 1; }
 
 static int check_prob(const GemmProb& p) {
     for (int s = 0; s < p.nseg; ++s) {
@@ -956,14 +977,9 @@ static int check_prob(const GemmProb& p) {
 
 int launch_gemm_nt(const GemmBatch& batch, hipStream_t st) {
     if (batch.count < 1 || batch.count > kMaxGemmBatch) return MARL_EINVAL;
-    int max_m = 0, max_n = 0;
-    int64_t blocks128 = 0;
     for (int i = 0; i < batch.count; ++i) {
         MARL_TRY(check_prob(batch.p[i]));
         if (!batch.p[i].c) return MARL_EINVAL;
-        max_m = batch.p[i].m > max_m ? batch.p[i].m : max_m;
-        max_n = batch.p[i].n > max_n ? batch.p[i].n : max_n;
-        blocks128 += cdiv(batch.p[i].m, 128) * cdiv(batch.p[i].n, 128);
     }
     static const bool log_shapes = getenv("MARL_GEMM_LOG") != nullptr;  // perf debugging aid
     if (log_shapes)
@@ -972,24 +988,14 @@ int launch_gemm_nt(const GemmBatch& batch, hipStream_t st) {
                     batch.count, batch.p[i].m, batch.p[i].n, batch.p[i].seg[0].k,
                     batch.p[i].nseg > 1 ? batch.p[i].seg[1].k : 0, batch.p[i].accumulate,
                     batch.p[i].bias != nullptr, batch.p[i].seg[0].lda, batch.p[i].ldc);
+    const GemmPlan plan = gemm_nt_plan(batch);
     prof_before(1, st);
-    if (split_mode()) {
-        MARL_TRY(launch_gemm_nt_split(batch, max_m, max_n, blocks128, st));
-    } else if (blocks128 >= 256 && max_n >= 96) {
-        const int g = gemm_groups();
-        dim3 grid((unsigned)cdiv(max_m, 128 * g), (unsigned)cdiv(max_n, 128), (unsigned)batch.count);
-        if (g == 2)
-            MARL_TRY((launch_nt_variant<128, 128, 2, 2, false, 2>(grid, batch, st)));
-        else
-            MARL_TRY((launch_nt_variant<128, 128, 2, 2, false, 1>(grid, batch, st)));
-    } else {
-        const int g = gemm_groups();
-        dim3 grid((unsigned)cdiv(max_m, 64 * g), (unsigned)cdiv(max_n, 64), (unsigned)batch.count);
-        if (g == 2)
-            MARL_TRY((launch_nt_variant<64, 64, 2, 2, false, 2>(grid, batch, st)));
-        else
-            MARL_TRY((launch_nt_variant<64, 64, 2, 2, false, 1>(grid, batch, st)));
-    }
+    if (plan.family)
+        MARL_TRY(launch_gemm_nt_split(batch, plan, false, st));
+    else if (plan.bm == 128)
+        MARL_TRY((launch_nt_fp32<128, 128, 2, 2, false>(batch, plan, st)));
+    else
+        MARL_TRY((launch_nt_fp32<64, 64, 2, 2, false>(batch, plan, st)));
     prof_after(1, st);
     MARL_LAUNCH_CHECK();
     return MARL_OK;
@@ -1046,76 +1052,74 @@ int profile_end(double* total_ms, int* launches) {
 
 int launch_gemm_lstm(const GemmBatch& batch, hipStream_t st) {
     if (batch.count < 1 || batch.count > kMaxGemmBatch) return MARL_EINVAL;
-    int max_m = 0, max_n = 0;
     for (int i = 0; i < batch.count; ++i) {
         const GemmProb& p = batch.p[i];
         MARL_TRY(check_prob(p));
         if (!p.bias || !p.c_prev || !p.h_next || !p.c_next) return MARL_EINVAL;
-        max_m = p.m > max_m ? p.m : max_m;
-        max_n = p.n > max_n ? p.n : max_n;
     }
-    const int g = gemm_groups();
-    dim3 grid((unsigned)cdiv(max_m, 128 * g), (unsigned)cdiv(max_n, 32), (unsigned)batch.count);
+    const GemmPlan plan = gemm_lstm_plan(batch);
     prof_before(0, st);
-    if (split_mode())
-        MARL_TRY(launch_gemm_lstm_split(batch, max_m, max_n, st));
-    else if (g == 2)
-        MARL_TRY((launch_nt_variant<128, 128, 4, 1, true, 2>(grid, batch, st)));
+    if (plan.family)
+        MARL_TRY(launch_gemm_nt_split(batch, plan, true, st));
     else
-        MARL_TRY((launch_nt_variant<128, 128, 4, 1, true, 1>(grid, batch, st)));
+        MARL_TRY((launch_nt_fp32<128, 128, 4, 1, true>(batch, plan, st)));
     prof_after(0, st);
     MARL_LAUNCH_CHECK();
     return MARL_OK;
 }
 
-struct TnPlan {
-    int bm;  // 128 or 64 (square tiles)
-    int splits;
-    int64_t rows_per_split;
-};
-
-static TnPlan tn_plan(int ni, int nj, int64_t rows) {
-    TnPlan p;
+// launch = false: the tile and split fields only - make_elayout sizes the scratch of every product at every entry
+// point, the knobs only a launch needs (tn_split_waves, tn_xcd) are not read for it
+GemmPlan tn_plan(int ni, int nj, int64_t rows, bool launch) {
+    GemmPlan p{};
+    p.kind = MARL_GEMM_TN;
     // 128-wide tiles only when there are enough of them: with < 4 tiles the 768-workgroup
     // target turns into hundreds of row slabs and the slab reduction costs more than the product
-    p.bm = (ni >= 96 && nj >= 96 && cdiv(ni, 128) * cdiv(nj, 128) >= 4) ? 128 : 64;
-    const int64_t tiles = cdiv(ni, p.bm) * cdiv(nj, p.bm);
+    p.bm = p.bn = (ni >= 96 && nj >= 96 && cdiv(ni, 128) * cdiv(nj, 128) >= 4) ? 128 : 64;
+    p.family = p.bm == 128 && split_mode();
+    p.gx = (int)cdiv(ni, p.bm);
+    p.gy = (int)cdiv(nj, p.bm);
+    const int64_t tiles = (int64_t)p.gx * p.gy;
     // (the bf16x6 kernel keeps two workgroups per CU resident, the fp32 one three)
-    const int target = (p.bm == 128 && split_mode()) ? 512 : 768;
+    const int target = p.family ? 512 : 768;
     int64_t s = cdiv(target, tiles);
     const int64_t max_s = cdiv(rows, 4 * BK);  // at least 4 K tiles per split
     if (s > max_s) s = max_s;
     if (s > 512) s = 512;
     if (s < 1) s = 1;
     int64_t rps = cdiv(cdiv(rows, s), BK) * BK;
-    p.splits = (int)cdiv(rows, rps);
+    p.splits = p.gz = (int)cdiv(rows, rps);
     p.rows_per_split = rps;
+    p.blocks = p.gx * p.gy * p.gz;
+    p.scratch_bytes = p.splits > 1 ? ((size_t)p.splits * ni * nj + (size_t)p.splits * ni) * sizeof(float) : 0;
+    p.lds_bytes = p.family ? (size_t)3 * 256 * kSplitRowBytes : (size_t)(p.bm == 128 ? 1 : 2) * BK * 2 * p.bm * sizeof(float);
+    if (!launch) return p;
+    p.threads = p.family && tune_get("tn_split_waves", 8) == 8 ? 512 : 256;
+    // XCD-ordered tiles by default: all tiles of a row slab run on one XCD and read its A / B row
+    // panels through that XCD's L2 once (measured: FETCH_SIZE 706 -> 292 MB per launch = 1.07x the
+    // algorithmic bytes, same duration - the kernel is matrix-pipe bound)
+    p.xcd_map = tune_get("tn_xcd", 1) != 0;
     return p;
 }
 
-size_t gemm_tn_scratch_bytes(int ni, int nj, int64_t rows) {
-    TnPlan p = tn_plan(ni, nj, rows);
-    // split partials of the product + of the optional column sums
-    return p.splits > 1 ? ((size_t)p.splits * ni * nj + (size_t)p.splits * ni) * sizeof(float) : 0;
-}
-
-bool gemm_tn_is_small(int ni, int nj, int64_t rows) { return tn_plan(ni, nj, rows).bm == 64; }
+size_t gemm_tn_scratch_bytes(int ni, int nj, int64_t rows) { return tn_plan(ni, nj, rows, false).scratch_bytes; }
 
 int launch_tn_queue(TnQueue& tq, RedQueue* q, hipStream_t st) {
     if (tq.n == 0) return MARL_OK;
     if (!q) return MARL_EINVAL;
     // all slabs must come out of the scratch in one piece of time: no flush between the takes
     size_t need = 0;
-    for (int i = 0; i < tq.n; ++i)
-        need += (gemm_tn_scratch_bytes(tq.it[i].ni, tq.it[i].nj, tq.it[i].rows) / sizeof(float) + 63) & ~(size_t)63;
+    GemmPlan plan[kMaxTnBatch];
+    for (int i = 0; i < tq.n; ++i) {
+        plan[i] = tn_plan(tq.it[i].ni, tq.it[i].nj, tq.it[i].rows, false);  // (the batch kernel has no launch knob)
+        need += (plan[i].scratch_bytes / sizeof(float) + 63) & ~(size_t)63;
+    }
     if (q->off + need > q->cap) MARL_TRY(q->flush());
     TnBatch tb{};
     float* scr[kMaxTnBatch];
-    TnPlan plan[kMaxTnBatch];
     int blocks = 0;
     for (int i = 0; i < tq.n; ++i) {
         const TnQueue::Item& it = tq.it[i];
-        plan[i] = tn_plan(it.ni, it.nj, it.rows);
         scr[i] = nullptr;
         TnBatchProb& P = tb.p[i];
         P.a = it.a;
@@ -1126,12 +1130,12 @@ int launch_tn_queue(TnQueue& tq, RedQueue* q, hipStream_t st) {
         P.nj = it.nj;
         P.rows = it.rows;
         P.rows_per_split = plan[i].rows_per_split;
-        P.gx = (int)cdiv(it.ni, 64);
-        P.gy = (int)cdiv(it.nj, 64);
+        P.gx = plan[i].gx;
+        P.gy = plan[i].gy;
         P.first_block = blocks;
         blocks += P.gx * P.gy * plan[i].splits;
         if (plan[i].splits > 1) {
-            scr[i] = q->take(gemm_tn_scratch_bytes(it.ni, it.nj, it.rows) / sizeof(float), false);
+            scr[i] = q->take(plan[i].scratch_bytes / sizeof(float), false);
             if (!scr[i]) {
                 set_error("tn queue: reduction scratch too small");
                 return MARL_ESIZE;
@@ -1149,7 +1153,7 @@ int launch_tn_queue(TnQueue& tq, RedQueue* q, hipStream_t st) {
     }
     tb.count = tq.n;
     prof_before(2, st);
-    hipLaunchKernelGGL(gemm_tn_batch_kernel, dim3((unsigned)blocks), dim3(256), (size_t)2 * 32 * 2 * 64 * sizeof(float), st, tb);
+    hipLaunchKernelGGL(gemm_tn_batch_kernel, dim3((unsigned)blocks), dim3(256), plan[0].lds_bytes, st, tb);
     prof_after(2, st);
     MARL_LAUNCH_CHECK();
     for (int i = 0; i < tq.n; ++i) {
@@ -1172,22 +1176,22 @@ int launch_gemm_tn(const float* a, int lda, const float* b, int ldb, float* c, i
                   (long long)rows, lda, ldb);
         return MARL_EINVAL;
     }
-    TnPlan p = tn_plan(ni, nj, rows);
-    if (tq && q && p.bm == 64) {  // small product: runs with the others, later
+    if (tq && q && tn_plan(ni, nj, rows, false).bm == 64) {  // small product: runs (and is planned) with the others, later
         if (tq->n == kMaxTnBatch) MARL_TRY(launch_tn_queue(*tq, q, st));
         tq->it[tq->n++] = TnQueue::Item{a, b, c, colsum_out, lda, ldb, ldc, ni, nj, rows};
         return MARL_OK;
     }
+    const GemmPlan p = tn_plan(ni, nj, rows);
     float* out = c;
     int ldo = ldc;
     int64_t stride = 0;
     if (p.splits > 1 && q) {  // partial slabs live in the queue's scratch until its flush
-        scratch = q->take(gemm_tn_scratch_bytes(ni, nj, rows) / sizeof(float));
-        scratch_bytes = gemm_tn_scratch_bytes(ni, nj, rows);
+        scratch = q->take(p.scratch_bytes / sizeof(float));
+        scratch_bytes = p.scratch_bytes;
         if (q->rc != MARL_OK) return q->rc;
     }
     if (p.splits > 1) {
-        if (!scratch || scratch_bytes < gemm_tn_scratch_bytes(ni, nj, rows)) {
+        if (!scratch || scratch_bytes < p.scratch_bytes) {
             set_error("gemm_tn: scratch too small");
             return MARL_ESIZE;
         }
@@ -1201,43 +1205,21 @@ int launch_gemm_tn(const float* a, int lda, const float* b, int ldb, float* c, i
     if (log_shapes)
         fprintf(stderr, "[gemm_tn] ni=%d nj=%d rows=%lld bm=%d splits=%d colsum=%d\n", ni, nj,
                 (long long)rows, p.bm, p.splits, colsum_out != nullptr);
-    dim3 grid((unsigned)cdiv(ni, p.bm), (unsigned)cdiv(nj, p.bm), (unsigned)p.splits);
-    // XCD-ordered tiles by default: all tiles of a row slab run on one XCD and read its A / B row
-    // panels through that XCD's L2 once (measured: FETCH_SIZE 706 -> 292 MB per launch = 1.07x the
-    // algorithmic bytes, same duration - the kernel is matrix-pipe bound)
-    int gx = 0, gy = 0, gz = 0;
-    if (xcd_map_enabled() || tune_get("tn_xcd", 1)) {
-        gx = (int)grid.x;
-        gy = (int)grid.y;
-        gz = (int)grid.z;
-        grid = dim3(grid.x * grid.y * grid.z);
-    }
+    const dim3 grid = plan_grid(p);
+    const int gx = p.xcd_map ? p.gx : 0, gy = p.xcd_map ? p.gy : 0, gz = p.xcd_map ? p.gz : 0;  // (0: the kernel reads blockIdx)
     prof_before(2, st);
-    // s_setprio(1) around the matrix phase (see launch_nt_variant): -3 % on the weight gradients.
+    // s_setprio(1) around the matrix phase (see launch_nt_fp32): -3 % on the weight gradients.
     // (Kept behind this run-time flag on purpose: the unconditional form compiles to a 20 % SLOWER
     // loop - measured 307 vs 254 us - the branch changes how hipcc schedules the cluster.)
     const int tn_prio = 1;
-    constexpr int tbk = 32;
-#define MARL_TN_LAUNCH(BM_, BK_)                                                               \
-    hipLaunchKernelGGL((gemm_tn_kernel<BM_, BM_, 2, 2, BK_>), grid, dim3(256),                 \
-                       (size_t)2 * BK_ * 2 * BM_ * sizeof(float), st, a, lda, b, ldb, out, ldo, \
-                       stride, ni, nj, rows, p.rows_per_split, csum, gx, gy, gz, tn_prio)
-    if (p.bm == 128 && split_mode())
-        MARL_TRY(launch_gemm_tn_split(a, lda, b, ldb, out, ldo, stride, ni, nj, rows, p.rows_per_split, csum,
-                                      grid, gx, gy, gz, st));
-    else if (p.bm == 128 && tbk == 32)
-        hipLaunchKernelGGL((gemm_tn_kernel<128, 128, 2, 2, 32, 1>), grid, dim3(256),
-                           (size_t)32 * 2 * 128 * sizeof(float), st, a, lda, b, ldb, out, ldo, stride, ni, nj,
-                           rows, p.rows_per_split, csum, gx, gy, gz, tn_prio);
-    else if (p.bm == 128 && tbk == 32)
-        MARL_TN_LAUNCH(128, 32);
+    if (p.family)
+        MARL_TRY(launch_gemm_tn_split(a, lda, b, ldb, out, ldo, stride, ni, nj, rows, csum, p, st));
     else if (p.bm == 128)
-        MARL_TN_LAUNCH(128, 16);
-    else if (tbk == 32)
-        MARL_TN_LAUNCH(64, 32);
+        hipLaunchKernelGGL((gemm_tn_kernel<128, 128, 2, 2, 32, 1>), grid, dim3(256), p.lds_bytes, st, a, lda, b, ldb, out,
+                           ldo, stride, ni, nj, rows, p.rows_per_split, csum, gx, gy, gz, tn_prio);
     else
-        MARL_TN_LAUNCH(64, 16);
-#undef MARL_TN_LAUNCH
+        hipLaunchKernelGGL((gemm_tn_kernel<64, 64, 2, 2, 32>), grid, dim3(256), p.lds_bytes, st, a, lda, b, ldb, out, ldo,
+                           stride, ni, nj, rows, p.rows_per_split, csum, gx, gy, gz, tn_prio);
     prof_after(2, st);
     MARL_LAUNCH_CHECK();
     if (p.splits > 1 && q) {

@@ -1407,93 +1407,149 @@ void g3_add_seg(G3Prob& p, const void* a3, int a_row0, const void* b3, int b_row
     p.nseg = 2;
 }
 
-template <int BM, int BN, int WM, int WN, int NST, bool LSTM>
-static int launch_g3_variant(G3Batch batch, int max_m, int max_n, hipStream_t st) {
-    dim3 grid((unsigned)cdiv(max_m, BM), (unsigned)cdiv(max_n, LSTM ? 32 : BN), (unsigned)batch.count);
-    batch.gx = (int)grid.x;
-    batch.gy = (int)grid.y;
-    // XCD-contiguous tile order: single products always; the two-cell LSTM launch by knob (each half of the XCDs then
-    // streams ONE cell's 3.8 MB of weight images - they fit its L2 - at the price of fetching A's row tiles twice)
-    // (round 6: also several products of ONE shape - the two batched heads: their three 128-column tiles per row tile
-    // were spread over the XCDs and A left HBM three times; knob nt_xcd_multi)
-    bool same = true;
-    for (int i = 1; i < batch.count; ++i) same = same && batch.p[i].m == batch.p[0].m && batch.p[i].n == batch.p[0].n;
-    batch.xcd_map = tune_get("nt_xcd", 1) &&
-                    !LSTM && (batch.count == 1 || same);  // (the two-cell LSTM launch keeps the dispatch order: measured twice)
-    if (batch.xcd_map) grid = dim3(grid.x * grid.y * grid.z);
-    batch.safe = tune_get("g3_safe", 0);
-    constexpr size_t lds = (size_t)NST * (BM + BN) * kImgRowBytes;
-    static_assert(lds <= 160 * 1024, "LDS ring");
-    static_assert((size_t)WM * WN * 32 * 36 * 4 <= lds, "epilogue panels fit the ring");
-    static_assert(!(LSTM && WN == 4) || (size_t)WM * 5 * 32 * 36 * 4 <= lds, "gate panels + h' panels fit the ring");
-    const int abl = batch.safe;
-#ifdef MARL_G3_ABLATE
-    static long long* d_clk = nullptr;
-    if (!d_clk) MARL_HIP_CHECK(hipMalloc(&d_clk, 4 * sizeof(long long)));
-    batch.clk = tune_get("g3_clk", 0) ? d_clk : nullptr;
-#endif
-#define G3_LAUNCH(ABL_)                                                                                   \
-    {                                                                                                     \
-        auto kern = gemm_nt3_kernel<BM, BN, WM, WN, NST, LSTM, ABL_>;                                     \
-        static bool raised = false;                                                                       \
-        if (lds > 64 * 1024 && !raised) {                                                                 \
-            MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                      \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    \
-            raised = true;                                                                                \
-        }                                                                                                 \
-        hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, st, batch);                               \
-    }
-    if (abl == 0) G3_LAUNCH(0)
-    else if (abl == 1) G3_LAUNCH(1)
-#ifdef MARL_G3_ABLATE
-    else if (abl == 2) G3_LAUNCH(2)
-    else if (abl == 3) G3_LAUNCH(3)
-    else if (abl == 4) G3_LAUNCH(4)
-    else if (abl == 5) G3_LAUNCH(5)
-    else if (abl == 6) G3_LAUNCH(6)
-#endif
-    else return MARL_EINVAL;
-#undef G3_LAUNCH
-#ifdef MARL_G3_ABLATE
-    if (batch.clk) {
-        long long h[4];
-        MARL_HIP_CHECK(hipMemcpy(h, batch.clk, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[g3 clk] block 0: %.1f us, %.0f MHz shader clock\n", (h[3] - h[1]) * 0.01,
-                (double)(h[2] - h[0]) / ((h[3] - h[1]) * 0.01));
-    }
-#endif
+// One row of a kernel family's variant table: the tile shape behind a variant id and the launch function of its one
+// template instantiation.  Planning routine and launcher index the same table (g3_row).
+struct G3Tile {
+    int id;  // 0: the row every id outside the table takes (GemmPlan::row_id)
+    int bm, bn, wm, wn, nst;
+    bool pipelined;  // gemm_nt3p_kernel (one 256-row workgroup per CU) instead of gemm_nt3_kernel
+    int (*launch)(G3Batch batch, const GemmPlan& plan, hipStream_t st);
+};
+
+// one launch of an image kernel: its dynamic-LDS limit is raised the first time the kernel is seen
+template <class K, class A>
+static int g3_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t st, const A& args) {
+    if (lds > 64 * 1024) MARL_HIP_CHECK(raise_lds(reinterpret_cast<const void*>(kern), lds));
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, args);
     MARL_LAUNCH_CHECK();
     return MARL_OK;
 }
 
-// the phase-pipelined kernels (gemm_nt3p_kernel): one 256-row workgroup per CU
-template <int BM, int BN, int WM, int WN, int NST, bool LSTM>
-static int launch_g3p_variant(G3Batch batch, int max_m, int max_n, hipStream_t st) {
-    dim3 grid((unsigned)cdiv(max_m, BM), (unsigned)cdiv(max_n, LSTM ? 32 : BN), (unsigned)batch.count);
-    batch.gx = (int)grid.x;
-    batch.gy = (int)grid.y;
+// The one instantiation behind a table row: gemm_nt3_kernel or (PIPE) gemm_nt3p_kernel; the launch comes from the plan.
+template <int BM, int BN, int WM, int WN, int NST, bool LSTM, bool PIPE>
+static int launch_g3_tile(G3Batch batch, const GemmPlan& plan, hipStream_t st) {
+    constexpr size_t lds = (size_t)NST * (BM + BN) * kImgRowBytes;
+    static_assert(lds <= 160 * 1024, "LDS ring");
+    static_assert((size_t)WM * WN * 32 * 36 * 4 <= lds, "epilogue panels fit the ring");
+    static_assert(PIPE || !(LSTM && WN == 4) || (size_t)WM * 5 * 32 * 36 * 4 <= lds, "gate panels + h' panels fit the ring");
+    batch.gx = plan.gx;
+    batch.gy = plan.gy;
+    batch.xcd_map = plan.xcd_map;
+    batch.safe = plan.safe;
+    const dim3 grid = plan_grid(plan);
+    if constexpr (PIPE) {
+        return g3_launch(gemm_nt3p_kernel<BM, BN, WM, WN, NST, LSTM>, grid, plan.threads, plan.lds_bytes, st, batch);
+    } else {
+#ifdef MARL_G3_ABLATE
+        static long long* d_clk = nullptr;
+        if (!d_clk) MARL_HIP_CHECK(hipMalloc(&d_clk, 4 * sizeof(long long)));
+        batch.clk = tune_get("g3_clk", 0) ? d_clk : nullptr;
+#endif
+        int rc;
+        switch (plan.safe) {  // (the ablation forms of the kernel ride on the knob of the debug form)
+#define G3_ABL(ABL_)                                                                                              \
+    case ABL_:                                                                                                    \
+        rc = g3_launch(gemm_nt3_kernel<BM, BN, WM, WN, NST, LSTM, ABL_>, grid, plan.threads, plan.lds_bytes, st, batch); \
+        break;
+            G3_ABL(0)
+            G3_ABL(1)
+#ifdef MARL_G3_ABLATE
+            G3_ABL(2)
+            G3_ABL(3)
+            G3_ABL(4)
+            G3_ABL(5)
+            G3_ABL(6)
+#endif
+#undef G3_ABL
+            default: return MARL_EINVAL;
+        }
+#ifdef MARL_G3_ABLATE
+        if (rc == MARL_OK && batch.clk) {
+            long long h[4];
+            MARL_HIP_CHECK(hipMemcpy(h, batch.clk, sizeof(h), hipMemcpyDeviceToHost));
+            fprintf(stderr, "[g3 clk] block 0: %.1f us, %.0f MHz shader clock\n", (h[3] - h[1]) * 0.01,
+                    (double)(h[2] - h[0]) / ((h[3] - h[1]) * 0.01));
+        }
+#endif
+        return rc;
+    }
+}
+
+// The variant tables: id -> tile and its instantiation; row 0 is the one every other id takes.
+#define G3_ROW(ID_, BM_, BN_, WM_, WN_, NST_, LSTM_, PIPE_) \
+    {ID_, BM_, BN_, WM_, WN_, NST_, PIPE_, launch_g3_tile<BM_, BN_, WM_, WN_, NST_, LSTM_, PIPE_>}
+// NT (perf experiments by argument / knob g3_nt_variant): wave tiles of 32 x 32 (7, 11, 12) or 64 x 64
+static const G3Tile kNtTiles[] = {
+    G3_ROW(0, 128, 64, 2, 2, 4, false, false),
+    G3_ROW(1, 256, 128, 4, 2, 4, false, false),
+    G3_ROW(2, 128, 128, 2, 2, 3, false, false),
+    G3_ROW(7, 64, 64, 2, 2, 4, false, false),
+    G3_ROW(11, 128, 64, 4, 2, 3, false, false),
+    G3_ROW(12, 64, 64, 2, 2, 3, false, false),
+    G3_ROW(21, 256, 256, 2, 4, 3, false, true),  // phase-pipelined, 256 x 256 / 8 waves (round 6)
+    G3_ROW(22, 256, 128, 4, 2, 4, false, true),  // phase-pipelined, 256 x 128 / 8 waves
+#ifdef MARL_G3_ABLATE
+    G3_ROW(4, 128, 128, 2, 2, 6, false, false),  // one workgroup per CU, six stages
+    G3_ROW(5, 128, 128, 4, 2, 3, false, false),  // eight waves on a 128 x 128 tile
+    G3_ROW(6, 256, 128, 4, 2, 3, false, false),  // eight waves, 256 x 128, three stages (2 workgroups would need 216 KB: still 1 per CU)
+#endif
+};
+// fused LSTM launch: bn = 128 gate columns = 32 units; wn = 4: one gate per wave (the gate-split plans)
+static const G3Tile kLstmTiles[] = {
+    G3_ROW(0, 128, 128, 4, 1, 3, true, false),
+    G3_ROW(1, 256, 128, 8, 1, 4, true, false),
+    G3_ROW(3, 32, 128, 1, 4, 4, true, false),
+    G3_ROW(4, 64, 128, 2, 4, 4, true, false),
+    G3_ROW(5, 256, 128, 4, 2, 4, true, true),  // phase-pipelined 256-row tiles (round 6): eight waves of 64 x 64 ...
+    G3_ROW(6, 256, 128, 2, 2, 4, true, true),  // ... or four waves of 128 x 64 (one per SIMD)
+#ifdef MARL_G3_ABLATE
+    G3_ROW(7, 256, 128, 2, 2, 3, true, true),  // (ring depth probe, tools/lstm_p_depth.py: three stages instead of four)
+#endif
+};
+#undef G3_ROW
+
+template <size_t N>
+static const G3Tile* g3_row(const G3Tile (&table)[N], int id) {
+    for (const G3Tile& t : table)
+        if (t.id == id) return &t;
+    return &table[0];
+}
+template <size_t N>
+static GemmPlan g3_plan(const G3Batch& batch, int variant, const G3Tile (&table)[N], bool lstm) {
+    const G3Tile* tile = g3_row(table, variant);
+    GemmPlan p{};
+    p.kind = lstm ? MARL_GEMM_LSTM_IMAGES : MARL_GEMM_NT_IMAGES;
+    p.variant = variant;
+    p.row_id = tile->id;
+    p.bm = tile->bm;
+    p.bn = tile->bn;
+    p.wm = tile->wm;
+    p.wn = tile->wn;
+    p.nst = tile->nst;
+    p.pipelined = tile->pipelined;
+    p.threads = p.wm * p.wn * 64;
+    int max_m = 0, max_n = 0;
     bool same = true;
-    for (int i = 1; i < batch.count; ++i) same = same && batch.p[i].m == batch.p[0].m && batch.p[i].n == batch.p[0].n;
-    batch.xcd_map = tune_get("nt_xcd", 1) && !LSTM && (batch.count == 1 || same);
-    if (batch.xcd_map) grid = dim3(grid.x * grid.y * grid.z);
-    batch.safe = tune_get("g3_safe", 0);
+    for (int i = 0; i < batch.count; ++i) {
+        max_m = batch.p[i].m > max_m ? batch.p[i].m : max_m;
+        max_n = batch.p[i].n > max_n ? batch.p[i].n : max_n;
+        same = same && batch.p[i].m == batch.p[0].m && batch.p[i].n == batch.p[0].n;
+    }
+    p.gx = (int)cdiv(max_m, p.bm);
+    p.gy = (int)cdiv(max_n, lstm ? 32 : p.bn);
+    p.gz = batch.count;
+    p.blocks = p.gx * p.gy * p.gz;
+    // XCD-contiguous tile order: single products always, and several products of ONE shape (the two batched heads:
+    // their three 128-column tiles per row tile were spread over the XCDs and A left HBM three times).  The two-cell
+    // LSTM launch keeps the dispatch order (measured twice).
+    p.xcd_map = tune_get("nt_xcd", 1) && !lstm && (batch.count == 1 || same);
+    p.safe = tune_get("g3_safe", 0);
 #ifndef MARL_G3_ABLATE
-    batch.safe = batch.safe != 0;
+    if (p.pipelined) p.safe = p.safe != 0;
 #endif
-    constexpr size_t lds = (size_t)NST * (BM + BN) * kImgRowBytes;
-    static_assert(lds <= 160 * 1024, "LDS ring");
-    static_assert((size_t)WM * WN * 32 * 36 * 4 <= lds, "epilogue panels fit the ring");
-    auto kern = gemm_nt3p_kernel<BM, BN, WM, WN, NST, LSTM>;
-    static bool raised = false;
-    if (!raised) {
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        raised = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, st, batch);
-    MARL_LAUNCH_CHECK();
-    return MARL_OK;
+    p.lds_bytes = (size_t)p.nst * (p.bm + p.bn) * kImgRowBytes;
+    return p;
 }
-
 static int check_g3(const G3Prob& p, bool lstm) {
     if (p.m <= 0 || p.n <= 0 || p.nseg < 1 || p.nseg > 2) {
         set_error("g3: empty problem m=%d n=%d nseg=%d", p.m, p.n, p.nseg);
@@ -1516,21 +1572,15 @@ static int check_g3(const G3Prob& p, bool lstm) {
     return MARL_OK;
 }
 
-// variant: 0 = automatic, else (perf experiments) 1: 256 x 128 / 8 waves, 2: 128 x 128 / 4 waves,
-// 3: 128 x 64 / 4 waves, 7: 64 x 64 / 4 waves, 11: 128 x 64 / 8 waves, 12: 64 x 64 / 4 waves with a 3-stage ring
-int launch_gemm_nt3(const G3Batch& batch, hipStream_t st, int variant) {
-    if (batch.count < 1 || batch.count > kMaxG3) return MARL_EINVAL;
-    int max_m = 0, max_n = 0;
-    int64_t blocks128 = 0;
-    for (int i = 0; i < batch.count; ++i) {
-        MARL_TRY(check_g3(batch.p[i], false));
-        if (!batch.p[i].c) return MARL_EINVAL;
-        max_m = batch.p[i].m > max_m ? batch.p[i].m : max_m;
-        max_n = batch.p[i].n > max_n ? batch.p[i].n : max_n;
-        blocks128 += cdiv(batch.p[i].m, 128) * cdiv(batch.p[i].n, 128);
-    }
+GemmPlan g3_nt_plan(const G3Batch& batch, int variant) {
     if (!variant) variant = tune_get("g3_nt_variant", 0);
     if (!variant) {
+        int max_n = 0;
+        int64_t blocks128 = 0;
+        for (int i = 0; i < batch.count; ++i) {
+            max_n = batch.p[i].n > max_n ? batch.p[i].n : max_n;
+            blocks128 += cdiv(batch.p[i].m, 128) * cdiv(batch.p[i].n, 128);
+        }
         // Tile plans by launch size (tools/small_r_lab.py, profiles/r05_small_r_lab.json):
         // big = one product with >= 1024 tiles of 128 x 128, mid = >= 256, small = everything else (the in-loop
         // backward batch at every batch size, the narrow heads, all launches of a 32-image batch).  Wave tiles
@@ -1542,33 +1592,18 @@ int launch_gemm_nt3(const G3Batch& batch, hipStream_t st, int variant) {
         // (lab 182 -> 165 us on [65536 x 256 x 1024]; iteration -0.02 ms; the heads, n = 384, keep 128 x 128: 88 vs 78 us)
         if (variant == 2 && blocks128 >= 1024 && batch.count == 1 && max_n % 256 == 0) variant = 21;
     }
-    prof_before(1, st);
-    int rc;
-    if (variant == 1)
-        rc = launch_g3_variant<256, 128, 4, 2, 4, false>(batch, max_m, max_n, st);
-    else if (variant == 2)
-        rc = launch_g3_variant<128, 128, 2, 2, 3, false>(batch, max_m, max_n, st);
-#ifdef MARL_G3_ABLATE
-    else if (variant == 4)  // one workgroup per CU, six stages
-        rc = launch_g3_variant<128, 128, 2, 2, 6, false>(batch, max_m, max_n, st);
-    else if (variant == 5)  // eight waves on a 128 x 128 tile
-        rc = launch_g3_variant<128, 128, 4, 2, 3, false>(batch, max_m, max_n, st);
-    else if (variant == 6)  // eight waves, 256 x 128, three stages (2 workgroups would need 216 KB: still 1 per CU)
-        rc = launch_g3_variant<256, 128, 4, 2, 3, false>(batch, max_m, max_n, st);
-#endif
-    else if (variant == 7)
-        rc = launch_g3_variant<64, 64, 2, 2, 4, false>(batch, max_m, max_n, st);
-    else if (variant == 11)
-        rc = launch_g3_variant<128, 64, 4, 2, 3, false>(batch, max_m, max_n, st);
-    else if (variant == 12)
-        rc = launch_g3_variant<64, 64, 2, 2, 3, false>(batch, max_m, max_n, st);
-    else if (variant == 21)  // phase-pipelined, 256 x 256 / 8 waves (round 6)
-        rc = launch_g3p_variant<256, 256, 2, 4, 3, false>(batch, max_m, max_n, st);
-    else if (variant == 22)  // phase-pipelined, 256 x 128 / 8 waves
-        rc = launch_g3p_variant<256, 128, 4, 2, 4, false>(batch, max_m, max_n, st);
+    return g3_plan(batch, variant, kNtTiles, false);
+}
 
-    else
-        rc = launch_g3_variant<128, 64, 2, 2, 4, false>(batch, max_m, max_n, st);
+int launch_gemm_nt3(const G3Batch& batch, hipStream_t st, int variant) {
+    if (batch.count < 1 || batch.count > kMaxG3) return MARL_EINVAL;
+    for (int i = 0; i < batch.count; ++i) {
+        MARL_TRY(check_g3(batch.p[i], false));
+        if (!batch.p[i].c) return MARL_EINVAL;
+    }
+    const GemmPlan plan = g3_nt_plan(batch, variant);
+    prof_before(1, st);
+    const int rc = g3_row(kNtTiles, plan.row_id)->launch(batch, plan, st);
     prof_after(1, st);
     return rc;
 }
@@ -1576,155 +1611,141 @@ int launch_gemm_nt3(const G3Batch& batch, hipStream_t st, int variant) {
 // Tile plan of the fused LSTM launch.  128 x 128 tiles (variant 2) need >= 2 workgroups per CU to cover each
 // other's prologue / epilogue; below that (BASELINE configs[3] / [4] at 32 images per GPU: 64 / 256 tiles on 256
 // CUs) the gate-split plans run - 64- or 32-row tiles with one gate per wave, whichever still fills the chip.
-int g3_lstm_plan(const G3Batch& batch) {
-    int64_t t128 = 0, t64 = 0;
-    for (int i = 0; i < batch.count; ++i) {
-        t128 += cdiv(batch.p[i].m, 128) * cdiv(batch.p[i].n, 32);
-        t64 += cdiv(batch.p[i].m, 64) * cdiv(batch.p[i].n, 32);
+GemmPlan g3_lstm_plan(const G3Batch& batch, int variant) {
+    if (!variant) variant = tune_get("g3_lstm_variant", 0);
+    if (!variant) {
+        int64_t t128 = 0, t64 = 0;
+        for (int i = 0; i < batch.count; ++i) {
+            t128 += cdiv(batch.p[i].m, 128) * cdiv(batch.p[i].n, 32);
+            t64 += cdiv(batch.p[i].m, 64) * cdiv(batch.p[i].n, 32);
+        }
+        // measured (two cells, n = 256, K = 880): R = 512: 35.0 / 22.9 / 18.6 us (128-row / 64-row / 32-row plan),
+        // R = 1024: 37.3 / 28.9 / 27.4, R = 2048: 45.3 / 47.0 / 56.1, R = 4096: 63-65 / 66-68 / 84
+        variant = t128 >= 192 ? 2 : t64 >= 384 ? 4 : 3;
     }
-    // measured (two cells, n = 256, K = 880): R = 512: 35.0 / 22.9 / 18.6 us (128-row / 64-row / 32-row plan),
-    // R = 1024: 37.3 / 28.9 / 27.4, R = 2048: 45.3 / 47.0 / 56.1, R = 4096: 63-65 / 66-68 / 84
-    if (t128 >= 192) return 2;
-    return t64 >= 384 ? 4 : 3;
+    return g3_plan(batch, variant, kLstmTiles, true);
 }
 
 int launch_gemm_lstm3(const G3Batch& batch, hipStream_t st, int variant) {
     if (batch.count < 1 || batch.count > kMaxG3) return MARL_EINVAL;
-    int max_m = 0, max_n = 0;
     for (int i = 0; i < batch.count; ++i) {
         const G3Prob& p = batch.p[i];
         MARL_TRY(check_g3(p, true));
         if (!p.bias || !p.c_prev || !p.h_next || !p.c_next) return MARL_EINVAL;
-        max_m = p.m > max_m ? p.m : max_m;
-        max_n = p.n > max_n ? p.n : max_n;
     }
-    if (!variant) variant = tune_get("g3_lstm_variant", 0);
-    if (!variant) variant = g3_lstm_plan(batch);
+    const GemmPlan plan = g3_lstm_plan(batch, variant);
     prof_before(0, st);
-    int rc;
-    if (variant == 1)
-        rc = launch_g3_variant<256, 128, 8, 1, 4, true>(batch, max_m, max_n, st);
-    else if (variant == 3)
-        rc = launch_g3_variant<32, 128, 1, 4, 4, true>(batch, max_m, max_n, st);
-    else if (variant == 4)
-        rc = launch_g3_variant<64, 128, 2, 4, 4, true>(batch, max_m, max_n, st);
-    else if (variant == 5)  // phase-pipelined 256-row tiles (round 6): eight waves of 64 x 64 ...
-        rc = launch_g3p_variant<256, 128, 4, 2, 4, true>(batch, max_m, max_n, st);
-    else if (variant == 6)  // ... or four waves of 128 x 64 (one per SIMD)
-        rc = launch_g3p_variant<256, 128, 2, 2, 4, true>(batch, max_m, max_n, st);
-#ifdef MARL_G3_ABLATE
-    else if (variant == 7)  // (ring depth probe, tools/lstm_p_depth.py: three stages instead of four)
-        rc = launch_g3p_variant<256, 128, 2, 2, 3, true>(batch, max_m, max_n, st);
-#endif
-    else
-        rc = launch_g3_variant<128, 128, 4, 1, 3, true>(batch, max_m, max_n, st);
+    const int rc = g3_row(kLstmTiles, plan.row_id)->launch(batch, plan, st);
     prof_after(0, st);
     return rc;
 }
 
 // knob g3_tn_pipe (default 1): the phase-pipelined step of the 256-column row-contraction bodies (round 6)
-static bool tn_pipe() { return tune_get("g3_tn_pipe", 1) != 0; }
+
+// The row-contraction variants: id -> tile, LDS ring and launch function (row 0 also serves every id outside the table)
+struct G3TnTile {
+    int id, bi, bj, threads;
+    size_t lds;
+    int (*launch)(const G3TnArgs& a, const GemmPlan& plan, dim3 grid, hipStream_t st);
+};
+constexpr size_t tn3_lds(int bi, int bj, int nst) { return (size_t)nst * ((bi + bj) / 16) * 16 * kImgRowBytes; }
 
 template <int BI, int BJ, int WI, int WJ, int NST, bool DB, int ABL = 0, bool PIPE = false>
-static int launch_tn3_variant(const G3TnArgs& a, dim3 grid, hipStream_t st) {
-    constexpr size_t lds = (size_t)NST * ((BI + BJ) / 16) * 16 * kImgRowBytes;
+static int launch_tn3_tile(const G3TnArgs& a, const GemmPlan& plan, dim3 grid, hipStream_t st) {
+    constexpr size_t lds = tn3_lds(BI, BJ, NST);
     static_assert(lds <= 160 * 1024 && (size_t)WI * WJ * 32 * 36 * 4 <= lds, "LDS ring / epilogue panels");
-    auto kern = gemm_tn3_kernel<BI, BJ, WI, WJ, NST, DB, ABL, PIPE>;
-    static bool raised = false;
-    if (lds > 64 * 1024 && !raised) {
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        raised = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(WI * WJ * 64), lds, st, a);
-    MARL_LAUNCH_CHECK();
-    return MARL_OK;
+    return g3_launch(gemm_tn3_kernel<BI, BJ, WI, WJ, NST, DB, ABL, PIPE>, grid, plan.threads, plan.lds_bytes, st, a);
 }
+static int launch_tn3_256(const G3TnArgs& a, const GemmPlan& plan, dim3 grid, hipStream_t st) {
+#ifdef MARL_G3_ABLATE
+    if (a.abl == 1) return launch_tn3_tile<256, 256, 4, 2, 3, false, 1>(a, plan, grid, st);
+    if (a.abl == 2) return launch_tn3_tile<256, 256, 4, 2, 3, false, 2>(a, plan, grid, st);
+    if (a.abl == 3) return launch_tn3_tile<256, 256, 4, 2, 3, false, 3>(a, plan, grid, st);
+    if (a.abl == 4) return launch_tn3_tile<256, 256, 4, 2, 3, false, 4>(a, plan, grid, st);
+#endif
+    return plan.pipelined ? launch_tn3_tile<256, 256, 4, 2, 3, false, 0, true>(a, plan, grid, st)
+                     : launch_tn3_tile<256, 256, 4, 2, 3, false>(a, plan, grid, st);
+}
+static int launch_tn3_passes(const G3TnArgs& a, const GemmPlan& plan, dim3 grid, hipStream_t st) {
+    return plan.pipelined ? g3_launch(gemm_tn3_passes_kernel<true>, grid, plan.threads, plan.lds_bytes, st, a)
+                     : g3_launch(gemm_tn3_passes_kernel<false>, grid, plan.threads, plan.lds_bytes, st, a);
+}
+static const G3TnTile kTnTiles[] = {
+    {2, 128, 128, 256, tn3_lds(128, 128, 3), launch_tn3_tile<128, 128, 2, 2, 3, true>},
+    {1, 256, 128, 512, tn3_lds(256, 128, 4), launch_tn3_tile<256, 128, 4, 2, 4, true>},
+    {3, 256, 256, 512, tn3_lds(256, 256, 3), launch_tn3_256},
+    // column passes over B under one 256-column tile of A; the 256 x 256 ring covers the 256 x 128 one of the last pass
+    {4, 256, 128, 512, tn3_lds(256, 256, 3), launch_tn3_passes},
+};
 
 // rows per split are whole row blocks; the slabs (and the column-sum slabs behind them) are reduced by
 // the caller (launch_slab_reduce / the deferred queue) exactly like those of the fp32-operand kernels
-G3TnPlan g3_tn_plan(int ni, int nj, int64_t rows) {
-    G3TnPlan p;
-    p.variant = tune_get("g3_tn_variant", 0);
+GemmPlan g3_tn_plan(int ni, int nj, int64_t rows, bool launch) {
+    GemmPlan p{};
+    p.kind = MARL_GEMM_TN_IMAGES;
+    int variant = tune_get("g3_tn_variant", 0);
     // 256-column tiles of A when both sides fill them (measured: wins from 32768 rows on): whole 256 x 256
     // tiles when B's width is (nearly) a multiple of 256, else column passes with a 128-wide last pass
     // (NJ = 368: 373 vs 386 us; NJ = 624: 604 vs 907 us, fp32-operand kernel 660)
-    if (!p.variant) {
+    if (!variant) {
         const int rem = nj % 256;
-        p.variant = !(ni >= 256 && nj >= 192 && rows >= 32768) ? 2 : (rem > 0 && rem <= 128 && nj > 256) ? 4 : 3;
+        variant = !(ni >= 256 && nj >= 192 && rows >= 32768) ? 2 : (rem > 0 && rem <= 128 && nj > 256) ? 4 : 3;
     }
-    const int bi = p.variant == 2 ? 128 : 256, bj = p.variant == 3 ? 256 : 128;
-    const int64_t tiles = p.variant == 4 ? cdiv(ni, 256) : cdiv(ni, bi) * cdiv(nj, bj);
-    int64_t s = cdiv(tune_get("g3_tn_wgs", p.variant == 2 ? 512 : 256), tiles);
+    const G3TnTile* tile = &kTnTiles[0];
+    for (const G3TnTile& t : kTnTiles)
+        if (t.id == variant) tile = &t;
+    p.variant = tile->id;
+    p.bm = tile->bi;
+    p.bn = tile->bj;
+    p.threads = tile->threads;
+    p.lds_bytes = tile->lds;
+    p.gx = (int)cdiv(ni, p.bm);
+    p.gy = p.variant == 4 ? 1 : (int)cdiv(nj, p.bn);
+    int64_t s = cdiv(tune_get("g3_tn_wgs", p.variant == 2 ? 512 : 256), (int64_t)p.gx * p.gy);
     const int64_t max_s = cdiv(rows, 256);  // at least 16 stages per split
     if (s > max_s) s = max_s;
     if (s > 512) s = 512;
     if (s < 1) s = 1;
     const int64_t rps = cdiv(cdiv(rows, s), 32) * 32;
-    p.splits = (int)cdiv(rows, rps);
+    p.splits = p.gz = (int)cdiv(rows, rps);
     p.rows_per_split = rps;
+    p.blocks = p.gx * p.gy * p.gz;
+    p.scratch_bytes = ((size_t)p.splits * ni * nj + (size_t)p.splits * ni) * sizeof(float);
+    if (!launch) return p;
+    p.xcd_map = tune_get("tn_xcd", 1) != 0;
+    p.pipelined = (p.variant == 3 || p.variant == 4) && tune_get("g3_tn_pipe", 1) != 0;
     return p;
 }
-size_t g3_tn_scratch_bytes(int ni, int nj, int64_t rows) {
-    const G3TnPlan p = g3_tn_plan(ni, nj, rows);
-    return ((size_t)p.splits * ni * nj + (size_t)p.splits * ni) * sizeof(float);
-}
 
-int launch_gemm_tn3(G3TnArgs a, const G3TnPlan& plan, hipStream_t st) {
+// operands (`same`: a cell's products share A and the rows); 32-bit offsets: column steps x one row block, one split
+static int check_tn3(const G3TnArgs& a, const GemmPlan& plan, bool same, const char* who) {
     if (!a.a3 || !a.b3 || !a.out || a.ni <= 0 || a.nj <= 0 || a.rows <= 0 || (a.rows & 31) || (a.a_row0 & 31) ||
-        (a.b_row0 & 31) || a.a_steps < img_steps(a.ni) || a.b_steps < img_steps(a.nj)) {
-        set_error("gemm_tn3: bad operand (ni=%d nj=%d rows=%lld)", a.ni, a.nj, (long long)a.rows);
+        (a.b_row0 & 31) || a.a_steps < img_steps(a.ni) || a.b_steps < img_steps(a.nj) || !same) {
+        set_error("%s: bad operand (ni=%d nj=%d rows=%lld)", who, a.ni, a.nj, (long long)a.rows);
         return MARL_EINVAL;
     }
-    // 32-bit offsets: column steps of an operand x one row block, and the row blocks of one split
     if ((int64_t)(plan.rows_per_split >> 5) * a.a_steps * kImgChunkBytes >= (1ll << 31) ||
         (int64_t)(plan.rows_per_split >> 5) * a.b_steps * kImgChunkBytes >= (1ll << 31)) {
-        set_error("gemm_tn3: split too long for 32-bit offsets");
+        set_error("%s: split too long for 32-bit offsets", who);
         return MARL_ELIMIT;
     }
+    return MARL_OK;
+}
+
+static int launch_gemm_tn3(G3TnArgs a, const GemmPlan& plan, hipStream_t st) {
+    MARL_TRY(check_tn3(a, plan, true, "gemm_tn3"));
     a.rows_per_split = plan.rows_per_split;
     a.safe = tune_get("g3_safe", 0) != 0;
 #ifdef MARL_G3_ABLATE
     a.abl = tune_get("g3_tn_abl", 0);
 #endif
-    const int bi = plan.variant == 2 ? 128 : 256, bj = plan.variant == 3 ? 256 : 128;
-    dim3 grid((unsigned)cdiv(a.ni, bi), (unsigned)(plan.variant == 4 ? 1 : cdiv(a.nj, bj)), (unsigned)plan.splits);
-    a.gx = a.gy = a.gz = 0;
-    if (tune_get("tn_xcd", 1)) {
-        a.gx = (int)grid.x;
-        a.gy = (int)grid.y;
-        a.gz = (int)grid.z;
-        grid = dim3(grid.x * grid.y * grid.z);
-    }
+    a.gx = plan.xcd_map ? plan.gx : 0;  // (0: the kernel reads blockIdx)
+    a.gy = plan.xcd_map ? plan.gy : 0;
+    a.gz = plan.xcd_map ? plan.gz : 0;
+    int rc = MARL_EINVAL;
     prof_before(2, st);
-    int rc;
-    if (plan.variant == 4) {
-        constexpr size_t lds = (size_t)3 * 32 * 16 * kImgRowBytes;  // the 256 x 256 ring covers the 256 x 128 one
-        static bool raised = false;
-        if (!raised) {
-            MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3_passes_kernel<false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3_passes_kernel<true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            raised = true;
-        }
-        if (tn_pipe()) hipLaunchKernelGGL(gemm_tn3_passes_kernel<true>, grid, dim3(512), lds, st, a);
-        else hipLaunchKernelGGL(gemm_tn3_passes_kernel<false>, grid, dim3(512), lds, st, a);
-        rc = hipGetLastError() == hipSuccess ? MARL_OK : MARL_EHIP;
-    } else if (plan.variant == 1)
-        rc = launch_tn3_variant<256, 128, 4, 2, 4, true>(a, grid, st);
-#ifdef MARL_G3_ABLATE
-    else if (plan.variant == 3 && a.abl == 1) rc = launch_tn3_variant<256, 256, 4, 2, 3, false, 1>(a, grid, st);
-    else if (plan.variant == 3 && a.abl == 2) rc = launch_tn3_variant<256, 256, 4, 2, 3, false, 2>(a, grid, st);
-    else if (plan.variant == 3 && a.abl == 3) rc = launch_tn3_variant<256, 256, 4, 2, 3, false, 3>(a, grid, st);
-    else if (plan.variant == 3 && a.abl == 4) rc = launch_tn3_variant<256, 256, 4, 2, 3, false, 4>(a, grid, st);
-#endif
-    else if (plan.variant == 3 && tn_pipe())
-        rc = launch_tn3_variant<256, 256, 4, 2, 3, false, 0, true>(a, grid, st);
-    else if (plan.variant == 3)
-        rc = launch_tn3_variant<256, 256, 4, 2, 3, false>(a, grid, st);
-    else
-        rc = launch_tn3_variant<128, 128, 2, 2, 3, true>(a, grid, st);
+    for (const G3TnTile& t : kTnTiles)
+        if (t.id == plan.variant) rc = t.launch(a, plan, plan_grid(plan), st);
     prof_after(2, st);
     return rc;
 }
@@ -1739,63 +1760,48 @@ static void tn_cell_tiles(int nj, int& n256, int& n128) {
     if (rem > 128) ++n256;
     else if (rem > 0) n128 = 1;
 }
-bool g3_tn_cell_ok(int ni, int nj_ih, int nj_hh, int64_t rows) {
-    if (tune_get("g3_tn_cell", 1) == 0 || ni < 256 || rows < 8192 || (rows & 31)) return false;
-    int a256, a128, b256, b128;
-    tn_cell_tiles(nj_ih, a256, a128);
-    tn_cell_tiles(nj_hh, b256, b128);
-    return a128 + b128 <= 1 && a256 + b256 + a128 + b128 <= kMaxTnCell && a256 + b256 >= 1;
-}
-// teams (see the kernel): a narrow last tile exists and G's 256-column tiles pair up
-static bool g3_tn_cell_teams(int ni, int nj_ih, int nj_hh) {
-    int a256, a128, b256, b128;
-    tn_cell_tiles(nj_ih, a256, a128);
-    tn_cell_tiles(nj_hh, b256, b128);
-    return a128 + b128 == 1 && ni % 512 == 0;
-}
-G3TnPlan g3_tn_cell_plan(int ni, int nj_ih, int nj_hh, int64_t rows) {
-    G3TnPlan p;
+GemmPlan g3_tn_cell_plan(int ni, int nj_ih, int nj_hh, int64_t rows) {
+    GemmPlan p{};
+    p.kind = MARL_GEMM_TN_IMAGES_CELL;
     p.variant = 5;
-    // ONE round of equal workgroups: every workgroup of the launch is resident at once (<= 256: one per CU), walks a
-    // long row slab and writes one partial tile - measured against 3 rounds of a third the length (760 workgroups):
-    // C3 7.37 vs 7.47 ms, C5 17.60 vs 17.78 (a third of the partial-slab traffic, no dispatch stagger inside a team);
-    // two rounds: no gain.
+    p.pipelined = tune_get("g3_tn_pipe", 1) != 0;  // (set whether or not the shape is inside the plan: make_plan reads it)
+    if (tune_get("g3_tn_cell", 1) == 0 || ni < 256 || rows < 8192 || (rows & 31)) return p;
     int a256, a128, b256, b128;
     tn_cell_tiles(nj_ih, a256, a128);
     tn_cell_tiles(nj_hh, b256, b128);
     const int n256 = a256 + b256, n128 = a128 + b128;
-    const int64_t per_slab = g3_tn_cell_teams(ni, nj_ih, nj_hh) ? (int64_t)(ni / 512) * (2 * n256 + 1)
-                                                                : (int64_t)cdiv(ni, 256) * (n256 + n128);
-    int64_t s = 256 / (per_slab > 0 ? per_slab : 1);
+    if (n128 > 1 || n256 + n128 > kMaxTnCell || n256 < 1) return p;
+    p.ok = 1;
+    p.bm = p.bn = 256;
+    p.threads = 512;
+    p.ih256 = a256;
+    p.ih128 = a128;
+    p.hh256 = b256;
+    p.hh128 = b128;
+    // teams (see the kernel): a narrow last tile exists and G's 256-column tiles pair up
+    p.teams = n128 == 1 && ni % 512 == 0;
+    // ONE round of equal workgroups: every workgroup of the launch is resident at once (<= 256: one per CU), walks a
+    // long row slab and writes one partial tile - measured against 3 rounds of a third the length (760 workgroups):
+    // C3 7.37 vs 7.47 ms, C5 17.60 vs 17.78 (a third of the partial-slab traffic, no dispatch stagger inside a team);
+    // two rounds: no gain.
+    const int64_t per_slab = p.teams ? (int64_t)(ni / 512) * (2 * n256 + 1) : (int64_t)cdiv(ni, 256) * (n256 + n128);
+    int64_t s = 256 / per_slab;
     const int64_t max_s = cdiv(rows, 256);
     if (s > max_s) s = max_s;
     if (s < 1) s = 1;
     const int64_t rps = cdiv(cdiv(rows, s), 32) * 32;
     p.splits = (int)cdiv(rows, rps);
     p.rows_per_split = rps;
+    p.blocks = (int)(per_slab * p.splits);
+    p.lds_bytes = tn3_lds(256, 256, 3);
+    p.scratch_bytes = (size_t)p.splits * ((size_t)ni * nj_ih + (size_t)ni * nj_hh + 2 * (size_t)ni) * sizeof(float);
     return p;
 }
-size_t g3_tn_cell_scratch_bytes(int ni, int nj_ih, int nj_hh, int64_t rows) {
-    const G3TnPlan p = g3_tn_cell_plan(ni, nj_ih, nj_hh, rows);
-    return (size_t)p.splits * ((size_t)ni * nj_ih + (size_t)ni * nj_hh + 2 * (size_t)ni) * sizeof(float);
-}
 
-int launch_gemm_tn3_cell(G3TnArgs ih, G3TnArgs hh, const G3TnPlan& plan, hipStream_t st) {
-    for (const G3TnArgs* q : {&ih, &hh}) {
-        const G3TnArgs& a = *q;
-        if (!a.a3 || !a.b3 || !a.out || a.ni <= 0 || a.nj <= 0 || a.rows <= 0 || (a.rows & 31) || (a.a_row0 & 31) ||
-            (a.b_row0 & 31) || a.a_steps < img_steps(a.ni) || a.b_steps < img_steps(a.nj) || a.ni != ih.ni ||
-            a.rows != ih.rows || a.a3 != ih.a3) {
-            set_error("gemm_tn3_cell: bad operand (ni=%d nj=%d rows=%lld)", a.ni, a.nj, (long long)a.rows);
-            return MARL_EINVAL;
-        }
-        if ((int64_t)(plan.rows_per_split >> 5) * a.a_steps * kImgChunkBytes >= (1ll << 31) ||
-            (int64_t)(plan.rows_per_split >> 5) * a.b_steps * kImgChunkBytes >= (1ll << 31)) {
-            set_error("gemm_tn3_cell: split too long for 32-bit offsets");
-            return MARL_ELIMIT;
-        }
-    }
-    if (!g3_tn_cell_ok(ih.ni, ih.nj, hh.nj, ih.rows)) {
+static int launch_gemm_tn3_cell(G3TnArgs ih, G3TnArgs hh, const GemmPlan& plan, hipStream_t st) {
+    for (const G3TnArgs* q : {&ih, &hh})
+        MARL_TRY(check_tn3(*q, plan, q->ni == ih.ni && q->rows == ih.rows && q->a3 == ih.a3, "gemm_tn3_cell"));
+    if (!plan.ok) {
         set_error("gemm_tn3_cell: shape outside the plan (ni=%d nj=%d/%d)", ih.ni, ih.nj, hh.nj);
         return MARL_EINVAL;
     }
@@ -1818,27 +1824,66 @@ int launch_gemm_tn3_cell(G3TnArgs ih, G3TnArgs hh, const G3TnPlan& plan, hipStre
     // read the same G; the narrow tile's body carries no column-sum accumulators)
     c.t[0].csum = ih.csum ? ih.csum : hh.csum;
     c.n256 = n;
+    if (n != plan.ih256 + plan.hh256 || have128 != (plan.ih128 + plan.hh128 == 1)) {
+        set_error("gemm_tn3_cell: the plan is not the plan of these shapes (ni=%d nj=%d/%d)", ih.ni, ih.nj, hh.nj);
+        return MARL_EINVAL;
+    }
     if (have128) c.t[n++] = last128;
     c.nt = n;
     c.gx = (int)cdiv(ih.ni, 256);
     c.gz = plan.splits;
-    c.teams = have128 && g3_tn_cell_teams(ih.ni, ih.nj, hh.nj);
-    const unsigned total = c.teams ? (unsigned)((c.gx >> 1) * (2 * c.n256 + 1) * c.gz) : (unsigned)(c.gx * c.nt * c.gz);
-    constexpr size_t lds = (size_t)3 * 32 * 16 * kImgRowBytes;
-    static bool raised = false;
-    if (!raised) {
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3_cell_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MARL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3_cell_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        raised = true;
-    }
+    c.teams = plan.teams;
     prof_before(2, st);
-    if (tn_pipe()) hipLaunchKernelGGL(gemm_tn3_cell_kernel<true>, dim3(total), dim3(512), lds, st, c);
-    else hipLaunchKernelGGL(gemm_tn3_cell_kernel<false>, dim3(total), dim3(512), lds, st, c);
-    const int rc = hipGetLastError() == hipSuccess ? MARL_OK : MARL_EHIP;
+    const int rc = plan.pipelined ? g3_launch(gemm_tn3_cell_kernel<true>, dim3(plan.blocks), plan.threads, plan.lds_bytes, st, c)
+                                  : g3_launch(gemm_tn3_cell_kernel<false>, dim3(plan.blocks), plan.threads, plan.lds_bytes, st, c);
     prof_after(2, st);
     return rc;
+}
+
+// launch + slab reductions of one product / of both products of a cell into their destinations; scratch holds
+// plan.scratch_bytes (the episode's drivers and the kernel-level entries below)
+int gemm_tn3(const GemmPlan& plan, const char* a3, int ni, const char* b3, int nj, int64_t rows, float* c, int ldc,
+             float* colsum, float* scratch, hipStream_t st) {
+    G3TnArgs a{};
+    a.a3 = a3;
+    a.b3 = b3;
+    a.a_steps = img_steps(ni);
+    a.b_steps = img_steps(nj);
+    a.out = scratch;
+    a.ldo = nj;
+    a.out_split_stride = (int64_t)ni * nj;
+    a.ni = ni;
+    a.nj = nj;
+    a.rows = rows;
+    a.csum = colsum ? scratch + (size_t)plan.splits * ni * nj : nullptr;
+    MARL_TRY(launch_gemm_tn3(a, plan, st));
+    return launch_slab_reduce(scratch, (int64_t)ni * nj, plan.splits, c, ldc, ni, nj, a.csum, colsum, st);
+}
+int gemm_tn3_cell(const GemmPlan& plan, const char* g3, int ni, const char* u3, int nih, const char* h3, int nhh,
+                  int64_t rows, float* c_ih, int ld_ih, float* c_hh, int ld_hh, float* colsum, float* scratch,
+                  hipStream_t st) {
+    float* s_ih = scratch;
+    float* s_hh = s_ih + (size_t)plan.splits * ni * nih;
+    float* s_cs = s_hh + (size_t)plan.splits * ni * nhh;
+    G3TnArgs ih{}, hh{};
+    ih.a3 = hh.a3 = g3;
+    ih.a_steps = hh.a_steps = img_steps(ni);
+    ih.ni = hh.ni = ni;
+    ih.rows = hh.rows = rows;
+    ih.b3 = u3;
+    ih.b_steps = img_steps(nih);
+    ih.nj = ih.ldo = nih;
+    ih.out = s_ih;
+    ih.out_split_stride = (int64_t)ni * nih;
+    ih.csum = colsum ? s_cs : nullptr;  // (the column sums of G ride on the first tile of the launch)
+    hh.b3 = h3;
+    hh.b_steps = img_steps(nhh);
+    hh.nj = hh.ldo = nhh;
+    hh.out = s_hh;
+    hh.out_split_stride = (int64_t)ni * nhh;
+    MARL_TRY(launch_gemm_tn3_cell(ih, hh, plan, st));
+    MARL_TRY(launch_slab_reduce(s_ih, (int64_t)ni * nih, plan.splits, c_ih, ld_ih, ni, nih, nullptr, nullptr, st));
+    return launch_slab_reduce(s_hh, (int64_t)ni * nhh, plan.splits, c_hh, ld_hh, ni, nhh, ih.csum, colsum, st);
 }
 
 }  // namespace marl
@@ -1921,7 +1966,7 @@ int marl_lstm_images(const void* u3, int nin, const void* h3, const void* wih3, 
 // colsum (nullable) [NI] = column sums of A; scratch >= marl_gemm_tn_images_scratch() bytes
 size_t marl_gemm_tn_images_scratch(int ni, int nj, int64_t rows) {
     if (ni < 1 || nj < 1 || rows < 32 || rows % 32 != 0) return 0;  // (the plan divides by the tile count)
-    return marl::g3_tn_scratch_bytes(ni, nj, rows);
+    return marl::g3_tn_plan(ni, nj, rows, false).scratch_bytes;
 }
 int marl_gemm_tn_images(const void* a3, const void* b3, float* c, int ldc, int ni, int nj, int64_t rows,
                         float* colsum, float* scratch, size_t scratch_bytes, void* stream) {
@@ -1931,71 +1976,88 @@ int marl_gemm_tn_images(const void* a3, const void* b3, float* c, int ldc, int n
                   (long long)rows);
         return MARL_EINVAL;
     }
-    if (!scratch || scratch_bytes < g3_tn_scratch_bytes(ni, nj, rows)) {
+    const GemmPlan plan = g3_tn_plan(ni, nj, rows);
+    if (!scratch || scratch_bytes < plan.scratch_bytes) {
         set_error("gemm_tn_images: scratch too small");
         return MARL_ESIZE;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const G3TnPlan plan = g3_tn_plan(ni, nj, rows);
-    G3TnArgs a{};
-    a.a3 = static_cast<const char*>(a3);
-    a.b3 = static_cast<const char*>(b3);
-    a.a_steps = img_steps(ni);
-    a.b_steps = img_steps(nj);
-    a.out = scratch;
-    a.ldo = nj;
-    a.out_split_stride = (int64_t)ni * nj;
-    a.ni = ni;
-    a.nj = nj;
-    a.rows = rows;
-    a.csum = colsum ? scratch + (size_t)plan.splits * ni * nj : nullptr;
-    MARL_TRY(launch_gemm_tn3(a, plan, st));
-    return launch_slab_reduce(scratch, (int64_t)ni * nj, plan.splits, c, ldc, ni, nj, a.csum, colsum, st);
+    return gemm_tn3(plan, static_cast<const char*>(a3), ni, static_cast<const char*>(b3), nj, rows, c, ldc,
+                    colsum, scratch, static_cast<hipStream_t>(stream));
 }
 
 // both weight gradients of one LSTM cell (C_ih [NI, NIH] = G^T U, C_hh [NI, NHH] = G^T H, colsum = column sums of
 // G) from one launch that reads G once (gemm_tn3_cell_kernel); 0 bytes = shape outside the plan
 size_t marl_gemm_tn_images_cell_scratch(int ni, int nih, int nhh, int64_t rows) {
-    if (ni < 1 || nih < 1 || nhh < 1 || rows < 32 || rows % 32 != 0 || !marl::g3_tn_cell_ok(ni, nih, nhh, rows)) return 0;
-    return marl::g3_tn_cell_scratch_bytes(ni, nih, nhh, rows);
+    if (ni < 1 || nih < 1 || nhh < 1 || rows < 32 || rows % 32 != 0) return 0;
+    return marl::g3_tn_cell_plan(ni, nih, nhh, rows).scratch_bytes;
 }
 int marl_gemm_tn_images_cell(const void* g3, int ni, const void* u3, int nih, const void* h3, int nhh, int64_t rows,
                              float* c_ih, int ld_ih, float* c_hh, int ld_hh, float* colsum, float* scratch,
                              size_t scratch_bytes, void* stream) {
     using namespace marl;
-    if (ni < 1 || nih < 1 || nhh < 1 || rows < 32 || rows % 32 != 0 || !g3 || !u3 || !h3 || !c_ih || !c_hh ||
-        !g3_tn_cell_ok(ni, nih, nhh, rows)) {
+    if (ni < 1 || nih < 1 || nhh < 1 || rows < 32 || rows % 32 != 0 || !g3 || !u3 || !h3 || !c_ih || !c_hh) {
+        set_error("gemm_tn_images_cell: bad argument (ni=%d nih=%d nhh=%d rows=%lld)", ni, nih, nhh, (long long)rows);
+        return MARL_EINVAL;
+    }
+    const GemmPlan plan = g3_tn_cell_plan(ni, nih, nhh, rows);
+    if (!plan.ok) {
         set_error("gemm_tn_images_cell: shape outside the plan (ni=%d nih=%d nhh=%d rows=%lld)", ni, nih, nhh, (long long)rows);
         return MARL_EINVAL;
     }
-    if (!scratch || scratch_bytes < g3_tn_cell_scratch_bytes(ni, nih, nhh, rows)) {
+    if (!scratch || scratch_bytes < plan.scratch_bytes) {
         set_error("gemm_tn_images_cell: scratch too small");
         return MARL_ESIZE;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const G3TnPlan plan = g3_tn_cell_plan(ni, nih, nhh, rows);
-    float* s_ih = scratch;
-    float* s_hh = s_ih + (size_t)plan.splits * ni * nih;
-    float* s_cs = s_hh + (size_t)plan.splits * ni * nhh;
-    G3TnArgs ih{}, hh{};
-    ih.a3 = hh.a3 = static_cast<const char*>(g3);
-    ih.a_steps = hh.a_steps = img_steps(ni);
-    ih.ni = hh.ni = ni;
-    ih.rows = hh.rows = rows;
-    ih.b3 = static_cast<const char*>(u3);
-    ih.b_steps = img_steps(nih);
-    ih.nj = ih.ldo = nih;
-    ih.out = s_ih;
-    ih.out_split_stride = (int64_t)ni * nih;
-    ih.csum = colsum ? s_cs : nullptr;
-    hh.b3 = static_cast<const char*>(h3);
-    hh.b_steps = img_steps(nhh);
-    hh.nj = hh.ldo = nhh;
-    hh.out = s_hh;
-    hh.out_split_stride = (int64_t)ni * nhh;
-    MARL_TRY(launch_gemm_tn3_cell(ih, hh, plan, st));
-    MARL_TRY(launch_slab_reduce(s_ih, (int64_t)ni * nih, plan.splits, c_ih, ld_ih, ni, nih, nullptr, nullptr, st));
-    return launch_slab_reduce(s_hh, (int64_t)ni * nhh, plan.splits, c_hh, ld_hh, ni, nhh, ih.csum, colsum, st);
+    return gemm_tn3_cell(plan, static_cast<const char*>(g3), ni, static_cast<const char*>(u3), nih,
+                         static_cast<const char*>(h3), nhh, rows, c_ih, ld_ih, c_hh, ld_hh, colsum, scratch,
+                         static_cast<hipStream_t>(stream));
+}
+
+// what a launcher does with a shape: its own planning routine, no HIP call (include/marl_hip_gemmops.h)
+int marl_gemm_plan(int kind, int count, const int* m, const int* n, const int* k, int64_t rows, int has_images,
+                   int variant, marl_gemm_plan_info* out) {
+    using namespace marl;
+    const bool tn = kind == MARL_GEMM_TN || kind == MARL_GEMM_TN_IMAGES || kind == MARL_GEMM_TN_IMAGES_CELL;
+    if (!out || !m || !n || kind < MARL_GEMM_NT || kind > MARL_GEMM_TN_IMAGES_CELL || count < 1 || count > kMaxG3 ||
+        (tn && (rows < 1 || count != (kind == MARL_GEMM_TN_IMAGES_CELL ? 2 : 1))) || (has_images && !k)) {
+        set_error("gemm_plan: bad argument (kind=%d count=%d)", kind, count);
+        return MARL_EINVAL;
+    }
+    bool bad = (kind == MARL_GEMM_TN_IMAGES && rows % 32) || (kind == MARL_GEMM_TN_IMAGES_CELL && m[0] != m[1]);
+    for (int i = 0; i < count; ++i) bad = bad || m[i] < 1 || n[i] < 1 || (k && k[i] < 1);
+    if (bad) {
+        set_error("gemm_plan: bad shape (kind=%d rows=%lld; sizes >= 1, image rows in whole blocks of 32)", kind, (long long)rows);
+        return MARL_EINVAL;
+    }
+    if (kind == MARL_GEMM_NT || kind == MARL_GEMM_LSTM) {
+        static const char image_stub = 0;  // (the plan asks only whether an image is there)
+        GemmBatch b{};
+        b.count = count;
+        for (int i = 0; i < count; ++i) {
+            b.p[i].m = m[i];
+            b.p[i].n = n[i];
+            b.p[i].nseg = 1;
+            b.p[i].seg[0].k = k ? k[i] : 1;
+            b.p[i].seg[0].b3 = has_images ? &image_stub : nullptr;
+            b.p[i].seg[0].kt3 = (b.p[i].seg[0].k + 31) / 32;
+        }
+        *out = kind == MARL_GEMM_NT ? gemm_nt_plan(b) : gemm_lstm_plan(b);
+    } else if (kind == MARL_GEMM_NT_IMAGES || kind == MARL_GEMM_LSTM_IMAGES) {
+        G3Batch b{};
+        b.count = count;
+        for (int i = 0; i < count; ++i) {
+            b.p[i].m = m[i];
+            b.p[i].n = n[i];
+        }
+        *out = kind == MARL_GEMM_NT_IMAGES ? g3_nt_plan(b, variant) : g3_lstm_plan(b, variant);
+    } else if (kind == MARL_GEMM_TN) {
+        *out = tn_plan(m[0], n[0], rows);
+    } else if (kind == MARL_GEMM_TN_IMAGES) {
+        *out = g3_tn_plan(m[0], n[0], rows);
+    } else {
+        *out = g3_tn_cell_plan(m[0], n[0], n[1], rows);
+    }
+    return MARL_OK;
 }
 
 }  // extern "C"

@@ -34,7 +34,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int SK = 32;     // K depth of a staged tile (two 16-deep MFMA steps)
-constexpr int SROW = 80;   // LDS bytes per tile row: 32 bf16 + 16 B pad
+constexpr int SROW = kSplitRowBytes;  // LDS bytes per tile row: 32 bf16 + 16 B pad
 
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -614,61 +614,44 @@ int launch_split_weights(const SplitBatch& b, hipStream_t st) {
 int split_mode() { return tune_get("mfma_split", 1); }
 
 template <int BN, bool LSTM>
-static int launch_nt_split_variant(dim3 grid, const GemmBatch& batch_in, hipStream_t st) {
-    GemmBatch batch = batch_in;
-    batch.gx = (int)grid.x;
-    batch.gy = (int)grid.y;
-    batch.xcd_map = batch.count == 1 && !LSTM && tune_get("nt_xcd", 1);
-    if (batch.xcd_map) grid = dim3(grid.x * grid.y * grid.z);
-    // every B operand comes with its pre-split image: the kernel copies their tiles
-    bool pre = true;
-    for (int i = 0; i < batch.count && pre; ++i)
-        for (int sg = 0; sg < batch.p[i].nseg && pre; ++sg) {
-            const GemmSeg& g = batch.p[i].seg[sg];
-            // 32-bit byte offsets into the image
-            pre = g.b3 && (int64_t)(LSTM ? 4 : 1) * batch.p[i].n * g.kt3 * 192 < (1ll << 32);
-        }
-    constexpr size_t lds = (size_t)3 * (128 + BN) * SROW;
+static int launch_nt_split_variant(GemmBatch batch, const GemmPlan& plan, hipStream_t st) {
+    batch.gx = plan.gx;
+    batch.gy = plan.gy;
+    batch.xcd_map = plan.xcd_map;
+    const dim3 grid = plan_grid(plan);
 #ifdef MARL_KERNEL_TS
     static long long* d_ts = nullptr;
     static int calls = 0;
     const int rec = ts_begin(&d_ts, calls++);
     batch.ts = rec ? d_ts : nullptr;
 #endif
-    if (pre)
-        hipLaunchKernelGGL((gemm_nt_split_kernel<BN, LSTM, true>), grid, dim3(256), lds, st, batch);
+    // every B operand comes with its pre-split image: the kernel copies their tiles
+    if (plan.pre)
+        hipLaunchKernelGGL((gemm_nt_split_kernel<BN, LSTM, true>), grid, dim3(plan.threads), plan.lds_bytes, st, batch);
     else
-        hipLaunchKernelGGL((gemm_nt_split_kernel<BN, LSTM, false>), grid, dim3(256), lds, st, batch);
+        hipLaunchKernelGGL((gemm_nt_split_kernel<BN, LSTM, false>), grid, dim3(plan.threads), plan.lds_bytes, st, batch);
 #ifdef MARL_KERNEL_TS
-    if (rec) ts_report(pre ? "nt_split_pre" : "nt_split", d_ts, 4);
+    if (rec) ts_report(plan.pre ? "nt_split_pre" : "nt_split", d_ts, 4);
 #endif
     return MARL_OK;
 }
 
-int launch_gemm_nt_split(const GemmBatch& batch, int max_m, int max_n, int64_t blocks128, hipStream_t st) {
-    // 128-wide column tiles when they fill the chip (two workgroups per CU), else 128 x 64
-    if (blocks128 >= 384 && max_n >= 96) {
-        dim3 grid((unsigned)cdiv(max_m, 128), (unsigned)cdiv(max_n, 128), (unsigned)batch.count);
-        return launch_nt_split_variant<128, false>(grid, batch, st);
-    }
-    dim3 grid((unsigned)cdiv(max_m, 128), (unsigned)cdiv(max_n, 64), (unsigned)batch.count);
-    return launch_nt_split_variant<64, false>(grid, batch, st);
-}
-
-int launch_gemm_lstm_split(const GemmBatch& batch, int max_m, int max_n, hipStream_t st) {
-    dim3 grid((unsigned)cdiv(max_m, 128), (unsigned)cdiv(max_n, 32), (unsigned)batch.count);
-    return launch_nt_split_variant<128, true>(grid, batch, st);
+int launch_gemm_nt_split(const GemmBatch& batch, const GemmPlan& plan, bool lstm, hipStream_t st) {
+    if (lstm) return launch_nt_split_variant<128, true>(batch, plan, st);
+    if (plan.bn == 128) return launch_nt_split_variant<128, false>(batch, plan, st);
+    return launch_nt_split_variant<64, false>(batch, plan, st);
 }
 
 int launch_gemm_tn_split(const float* a, int lda, const float* b, int ldb, float* out, int ldo,
-                         int64_t stride, int ni, int nj, int64_t rows, int64_t rows_per_split,
-                         float* csum, dim3 grid, int gx, int gy, int gz, hipStream_t st) {
-    if (tune_get("tn_split_waves", 8) == 8)
-        hipLaunchKernelGGL(gemm_tn_split_kernel<8>, grid, dim3(512), (size_t)3 * 256 * SROW, st, a, lda, b, ldb,
-                           out, ldo, stride, ni, nj, rows, rows_per_split, csum, gx, gy, gz);
+                         int64_t stride, int ni, int nj, int64_t rows, float* csum, const GemmPlan& plan, hipStream_t st) {
+    const dim3 grid = plan_grid(plan);
+    const int gx = plan.xcd_map ? plan.gx : 0, gy = plan.xcd_map ? plan.gy : 0, gz = plan.xcd_map ? plan.gz : 0;
+    if (plan.threads == 512)
+        hipLaunchKernelGGL(gemm_tn_split_kernel<8>, grid, dim3(512), plan.lds_bytes, st, a, lda, b, ldb, out, ldo, stride, ni,
+                           nj, rows, plan.rows_per_split, csum, gx, gy, gz);
     else
-        hipLaunchKernelGGL(gemm_tn_split_kernel<4>, grid, dim3(256), (size_t)3 * 256 * SROW, st, a, lda, b, ldb,
-                           out, ldo, stride, ni, nj, rows, rows_per_split, csum, gx, gy, gz);
+        hipLaunchKernelGGL(gemm_tn_split_kernel<4>, grid, dim3(256), plan.lds_bytes, st, a, lda, b, ldb, out, ldo, stride, ni,
+                           nj, rows, plan.rows_per_split, csum, gx, gy, gz);
     return MARL_OK;
 }
 

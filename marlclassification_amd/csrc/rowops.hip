@@ -3,7 +3,6 @@
 // bounded move, deterministic reductions, weight (un)packing and Adam.
 // One 64-lane wave owns a row wherever a row reduction is needed.
 #include <stdarg.h>
-#include <stdlib.h>
 
 #include <ctype.h>
 #include <stdlib.h>
