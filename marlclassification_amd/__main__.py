@@ -155,6 +155,18 @@ def build_parser() -> argparse.ArgumentParser:
     e.add_argument("--tta", type=_arg(_tta_arg), default=None, dest="tta", metavar="SPEC",
                    help="test-time augmentation: every batch runs once per flip / rotation the spec allows (hflip, "
                         "vflip, rot90, d4) and the predictions are averaged (default: one run)")
+    for sp in (t, e):
+        sp.add_argument("--report", action="store_true", dest="report",
+                        help="episode report on the device: vote accuracy, top-k, NLL and agreement per step, every "
+                             "agent's accuracy, calibration (ECE) and early-exit statistics; writes report*.json and "
+                             "accuracy_per_step*.png beside the confusion matrix (default: the confusion matrix only)")
+        sp.add_argument("--report-topk", type=int, default=5, dest="report_topk", metavar="K",
+                        help="with --report: ranks reported, 1 .. 16 (default: 5)")
+        sp.add_argument("--report-bins", type=int, default=15, dest="report_bins", metavar="B",
+                        help="with --report: confidence bins of the calibration, 1 .. 64 (default: 15)")
+        sp.add_argument("--exit-at", type=_arg(_exit_at), default=None, dest="exit_at", metavar="t1,t2,...",
+                        help="with --report: up to 8 confidences in [0, 1]; reports the steps an episode needs and its "
+                             "accuracy when it stops at the first step whose vote is that confident")
     for sp in (e, i):
         sp.add_argument("--greedy", action="store_true", dest="greedy",
                         help="deterministic acting: every agent takes the argmax of its policy (no random draw)")
@@ -192,6 +204,13 @@ def _mix_arg(text: str) -> str:
     from .mix import parse as parse_mix
 
     return parse_mix(text).spec
+
+
+def _exit_at(text: str) -> str:
+    from .report import ReportOptions, parse_exit_at
+
+    ReportOptions(exit_thresholds=parse_exit_at(text))
+    return text
 
 
 def _tta_arg(text: str) -> str:
@@ -240,6 +259,22 @@ def _comm_range_arg(text: str) -> str:
         raise argparse.ArgumentTypeError(str(err))
 
 
+def check_report(parser: argparse.ArgumentParser, args) -> None:
+    """--report-topk / --report-bins / --exit-at need --report and values the kernel serves."""
+    if args.main_choice not in ("train", "test"):
+        return
+    if not args.report:
+        if args.report_topk != 5 or args.report_bins != 15 or args.exit_at is not None:
+            parser.error("--report-topk / --report-bins / --exit-at need --report")
+        return
+    from .report import ReportOptions, parse_exit_at
+
+    try:
+        ReportOptions(args.report_topk, args.report_bins, parse_exit_at(args.exit_at))
+    except ValueError as err:
+        parser.error(str(err))
+
+
 def check_learn_comm(parser: argparse.ArgumentParser, args) -> None:
     """--learn-comm needs a graph with at least one link (its support is fixed); --comm-lr needs --learn-comm."""
     if args.main_choice != "train":
@@ -258,6 +293,7 @@ def main(argv=None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
     check_learn_comm(parser, args)
+    check_report(parser, args)
     main_config = MainConfig(step=args.step, run_id=args.run_id, cuda=args.cuda, nb_agent=args.agents)
     if args.main_choice == "train":
         from .train import train_main
@@ -284,6 +320,7 @@ def main(argv=None) -> None:
             weight_decay=args.weight_decay, decay_all=args.decay_all, lr_groups=args.lr_groups,
             lr_schedule=args.lr_schedule, warmup_steps=args.warmup_steps, adam_betas=args.adam_betas, ema=args.ema,
             eval_ema=args.eval_ema, resume=args.resume,
+            report=args.report, report_topk=args.report_topk, report_bins=args.report_bins, exit_at=args.exit_at,
         )
         train_main(main_config, model_config, train_config, exact_standardize=args.exact_standardize)
     elif args.main_choice == "test":
@@ -293,7 +330,8 @@ def main(argv=None) -> None:
             img_size=args.img_size, state_dict_path=args.state_dict_path, batch_size=args.batch_size,
             json_path=args.json_path, dataset_path=args.dataset_path, output_dir=args.output_dir,
             comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature,
-            tta=args.tta))
+            tta=args.tta, report=args.report, report_topk=args.report_topk, report_bins=args.report_bins,
+            exit_at=args.exit_at))
     elif args.main_choice == "infer":
         import os
 

@@ -102,8 +102,10 @@ OPTIM_ENTRIES = ("marl_optim_step",)
 PANELOP_HOOKS = ("marl_panel_fwd", "marl_panel_bwd", "marl_panel_scratch_bytes", "marl_panel_plan")
 # ... and the host-only witness of the matrix-product launchers that include/marl_hip_gemmops.h declares (tests only)
 GEMMOP_HOOKS = ("marl_gemm_plan",)
+# ... and the episode report that include/marl_hip_report.h declares (beside the versioned ABI; report.py binds it)
+REPORT_ENTRIES = ("marl_report_layout", "marl_report_scratch_bytes", "marl_episode_report")
 _HOOKS = (ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES +
-          PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES + GEMMOP_HOOKS)
+          PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES + GEMMOP_HOOKS + REPORT_ENTRIES)
 # the launchers marl_gemm_plan answers for (its `kind`)
 GEMM_KINDS = ("nt", "lstm", "tn", "nt_images", "lstm_images", "tn_images", "tn_images_cell")
 MARL_PANEL_MAX_LAYERS = 4
@@ -315,6 +317,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_soft_targets.argtypes = [_vp, _i, _i]
     lib.marl_batch_mix.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
     lib.marl_batch_mix_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
+    lib.marl_report_layout.argtypes = [_i] * 6 + [C.POINTER(_i64)]
+    lib.marl_report_scratch_bytes.restype = _sz
+    lib.marl_report_scratch_bytes.argtypes = [_i] * 7
+    lib.marl_episode_report.argtypes = [_vp, _vp] + [_i] * 6 + [C.POINTER(_f), _i, _i, _vp, _sz, _vp, _sz, _vp]
     lib.marl_ln_silu_bwd.argtypes = [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _vp, _sz, _i, _i, _vp]
     lib.marl_gn_silu_bwd.argtypes = [_vp, _i64, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _vp]
     lib.marl_cnn_dgrad.argtypes = [_vp, _vp, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _i, _vp]

@@ -138,6 +138,12 @@ class TrainConfig(BaseModel):
     ema: Optional[float] = None
     eval_ema: bool = False
     resume: Optional[str] = None
+    # --report: the evaluation after every epoch (and the training meter) is an episode report (report.py): per-step
+    # accuracy, top-k, NLL, calibration, early exit at the exit_at confidences ("t1,t2,..."); off: the confusion meter
+    report: bool = False
+    report_topk: int = 5
+    report_bins: int = 15
+    exit_at: Optional[str] = None
 
     def optim_on(self) -> bool:
         return (self.weight_decay != 0.0 or self.decay_all or self.lr_groups is not None or
@@ -157,6 +163,12 @@ class EvalConfig(BaseModel):
     greedy: bool = False  # --greedy: deterministic acting, the argmax of the policy (a run-time choice, not in marl.json)
     temperature: float = 1.0  # --temperature: the policy is softmax(z / T)
     tta: Optional[str] = None  # --tta: test-time augmentation, the mean over the views of augment.parse(SPEC).views()
+    # --report: the episode report (report.py) beside the confusion matrix - one table row per step, report.json and
+    # accuracy_per_step.png; exit_at = "t1,t2,...", the confidences of the early-exit statistics.  Off: today's path
+    report: bool = False
+    report_topk: int = 5
+    report_bins: int = 15
+    exit_at: Optional[str] = None
 
 
 class InferConfig(BaseModel):

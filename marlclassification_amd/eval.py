@@ -49,8 +49,26 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
         policy = _augment.parse_tta(eval_config.tta)
         policy.check_size(eval_config.img_size, eval_config.img_size)
         views = policy.views().to(device)
+    rep = None
+    if eval_config.report:  # (--report: every step of every episode into an episode report, report.py)
+        from .report import EpisodeReport, ReportOptions, parse_exit_at, step_table
+
+        opts = ReportOptions(eval_config.report_topk, eval_config.report_bins, parse_exit_at(eval_config.exit_at))
+        n_views = 1 if views is None else views.shape[0]
+        # (under --tta the views are stacked along the agent axis: the vote is the mean over views x agents)
+        rep = EpisodeReport(main_config.step, main_config.nb_agent * n_views, nn_models.nb_class, opts, device)
+        with th.no_grad():
+            for x, y in loader:
+                if n_views == 1:
+                    preds = sampler.run_episode(x).step_preds
+                else:
+                    preds = th.cat([sampler.run_episode(_augment.apply(
+                        x, None, views[v: v + 1].expand(x.shape[0], -1).contiguous())).step_preds
+                        for v in range(n_views)], dim=1)
+                rep.add(preds, y.to(device))
+        meter = rep  # (it has the meter's reading methods)
     with th.no_grad():
-        for x, y in loader:
+        for x, y in (() if rep is not None else loader):
             if views is None or views.shape[0] == 1:
                 out = sampler.run_episode_get_last_step(x)
                 meter.add(out.prediction.mean(dim=0), y)  # mean over agents; stays on the device
@@ -69,4 +87,9 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
     print(f"Recall : {format_metric(recs, dataset.class_to_idx)}")
     print(f"Recall mean : {recs.mean().item()}")
     meter.save_conf_matrix(0, eval_config.output_dir, "test")
+    if rep is not None:
+        for line in step_table(rep.result(), opts):
+            print(line)
+        rep.to_json(os.path.join(eval_config.output_dir, "report.json"))
+        rep.save_step_curve(os.path.join(eval_config.output_dir, "accuracy_per_step.png"))
     return meter

@@ -264,7 +264,14 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
             ema_decay=train_config.ema)
     if train_config.eval_ema and train_config.ema is None:
         raise ValueError("--eval-ema needs --ema")
+    report_opts = None
+    if train_config.report:  # (--report: the training meter and the evaluation are episode reports, report.py)
+        from .report import EpisodeReport, ReportOptions, parse_exit_at, summary_metrics
+
+        report_opts = ReportOptions(train_config.report_topk, train_config.report_bins,
+                                    parse_exit_at(train_config.exit_at))
     trainer = Trainer(nn_models, marl_m.nb_class, train_config.learning_rate, train_config.gamma,
+                      report=report_opts,
                       metric_logger=metric_logger if rank == 0 else None,
                       allreduce=(BucketedGradAllReduce(world, None, nn_models.flat_state().offsets, nn_models.flat_state().numel,
                                                       device) if distributed else None),
@@ -310,17 +317,25 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         if e_ends is not None:
             trainer.explore_eps = _explore.schedule_value(e_ends, e, train_config.nb_epoch)
         trainer.train_epoch(loaders[0], e, sampler)
+        eval_kw = {}
+        if report_opts is not None:
+            eval_kw["report"] = EpisodeReport(main_config.step, main_config.nb_agent, marl_m.nb_class, report_opts,
+                                              device)
         if train_config.eval_ema:
             with trainer.ema_weights():
-                conf = trainer.eval_epoch(loaders[1], e, sampler)
+                conf = trainer.eval_epoch(loaders[1], e, sampler, **eval_kw)
         else:
-            conf = trainer.eval_epoch(loaders[1], e, sampler)
+            conf = trainer.eval_epoch(loaders[1], e, sampler, **eval_kw)
         if distributed:
             conf.all_reduce()  # every rank evaluated its shard only
         if rank == 0:
             m: Dict[str, float] = trainer.metrics()
             m["eval_prec"] = conf.precision().mean().item()
             m["eval_recs"] = conf.recall().mean().item()
+            if report_opts is not None:
+                m.update(summary_metrics(conf.result(), report_opts, "eval"))
+                conf.to_json(join(output_dir, f"report_epoch_{e}.json"))
+                conf.save_step_curve(join(output_dir, f"accuracy_per_step_epoch_{e}.png"))
             print(f"epoch {e}: " + ", ".join(f"{k}={v:.8e}" if k == "lr" else f"{k}={v:.4f}" for k, v in m.items()),
                   flush=True)
             conf.save_conf_matrix(e, output_dir, "eval")  # reference train.py:134

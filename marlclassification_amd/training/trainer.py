@@ -50,8 +50,15 @@ class Trainer:
         error_step_weights=None,
         weight_rewards: bool = False,
         optim=None,
+        report=None,
     ) -> None:
-        """``optim`` (an ``optim.OptimOptions``): every update - ``train_step`` with or without the entropy bonus, every
+        """``report`` (a ``report.ReportOptions``): the per-iteration training meter is a windowed
+        ``report.EpisodeReport`` (``meter_window_size`` batches) that every ``train_step`` feeds from ALL of the
+        rollout's ``step_preds`` with one ``marl_episode_report`` call, in place of ``ConfusionMeter.add`` on the last
+        step's vote; ``metrics()`` gains ``train_acc``, ``train_top{k}``, ``train_nll`` and ``train_ece``, and
+        ``train_prec`` / ``train_rec`` come from the report's confusion matrix.  None: the confusion meter, as before.
+
+        ``optim`` (an ``optim.OptimOptions``): every update - ``train_step`` with or without the entropy bonus, every
         PPO epoch, on every rank - is one ``marl_optim_step`` under these options: AdamW with decoupled weight decay,
         per-module learning-rate multipliers (0 freezes a module; with ``max_grad_norm`` its gradient leaves the
         clipped norm), a schedule whose base rate is ``learning_rate`` (unless it names its own) and, with
@@ -118,6 +125,14 @@ class Trainer:
         self.__curr_step = 0
         self.__loss_bufs: Optional[Tuple[th.Tensor, ...]] = None
         self.__conf_meter = ConfusionMeter(nb_class, window_size=meter_window_size)
+        if report is not None:
+            from ..report import ReportOptions
+
+            if not isinstance(report, ReportOptions):
+                raise ValueError(f"report must be a report.ReportOptions or None, got {type(report).__name__}")
+        self.__report_opts = report
+        self.__report = None  # (the EpisodeReport: made at the first step, which knows the steps and the agents)
+        self.__meter_window_size = meter_window_size
         self.__meter_keys = ("loss", "path", "error", "critic") + (("entropy",) if entropy_coef > 0 else ())
         # (scalars index of every meter: the PPO scalars keep the entropy slot, zero without a bonus)
         self.__meter_idx = {k: i for i, k in enumerate(self.__meter_keys)}
@@ -167,8 +182,29 @@ class Trainer:
             x0 = model.exploration
             model.set_exploration(x0.temperature if self.temperature is None else self.temperature,
                                   x0.eps if self.explore_eps is None else self.explore_eps, x0.greedy)
-        if self.__ppo:
-            return self.__train_step_ppo(x, y, sampler, targets)
+        step = self.__train_step_ppo if self.__ppo else self.__train_step_a2c
+        out, scalars = step(x, y, sampler, targets)
+        if self.__report_opts is not None:  # (here, not in train_epoch: all steps and the labels are at hand)
+            self.__report_add(out.step_preds, y)
+        return out, scalars
+
+    def __report_add(self, step_preds: th.Tensor, y: th.Tensor) -> None:
+        if self.__report is None:
+            from ..report import EpisodeReport
+
+            ns, na = step_preds.shape[0], step_preds.shape[1]
+            self.__report = EpisodeReport(ns, na, self.__nb_class, self.__report_opts, step_preds.device,
+                                          window_size=self.__meter_window_size)
+        self.__report.add(step_preds, y)
+
+    @property
+    def report(self):
+        """The training meter's ``EpisodeReport`` (None without ``report`` or before the first step)."""
+        return self.__report
+
+    def __train_step_a2c(self, x: th.Tensor, y: th.Tensor, sampler: EpisodeSampler,
+                         targets: Optional[th.Tensor] = None) -> Tuple[EpisodeTensors, th.Tensor]:
+        model = self.__model
         # with the entropy bonus: the same sequence through the three entries that carry the step distributions
         # (scalars[4] = the mean entropy)
         beta = self.__entropy_coef
@@ -216,7 +252,8 @@ class Trainer:
         for x_train, y_train, *rest in dataloader:  # (a mixing loader yields (x, y_primary, Q): data.py)
             out, scalars = self.train_step(x_train, y_train, episode_sampler, targets=rest[0] if rest else None)
             # device-side meters, no sync (select last step, mean over agents: trainer.py:124-128)
-            self.__conf_meter.add(out.step_preds[-1].mean(dim=0), y_train)
+            if self.__report_opts is None:  # (else train_step fed the report)
+                self.__conf_meter.add(out.step_preds[-1].mean(dim=0), y_train)
             for k in self.__meter_keys:
                 self.__meters[k].add(scalars[self.__meter_idx[k]].clone())
             if self.__max_grad_norm is not None:  # (the norm before clipping, of the last epoch's gradient)
@@ -227,14 +264,19 @@ class Trainer:
 
     def metrics(self) -> Dict[str, float]:
         """Synchronises: windowed means of the loss terms + train precision / recall."""
+        meter = self.__conf_meter if self.__report is None else self.__report
         m = {
             "error": self.__meters["error"].loss(),
             "path_loss": self.__meters["path"].loss(),
             "loss": self.__meters["loss"].loss(),
             "critic_loss": self.__meters["critic"].loss(),
-            "train_prec": self.__conf_meter.precision().mean().item(),
-            "train_rec": self.__conf_meter.recall().mean().item(),
+            "train_prec": meter.precision().mean().item(),
+            "train_rec": meter.recall().mean().item(),
         }
+        if self.__report is not None:
+            from ..report import summary_metrics
+
+            m.update(summary_metrics(self.__report.result(), self.__report_opts, "train"))
         if "entropy" in self.__meters:  # (only with an entropy bonus: the plain trainer never sees the distributions)
             m["entropy"] = self.__meters["entropy"].loss()
         for k in ("approx_kl", "clip_frac", "grad_norm"):  # (only with the matching PPO option on)
@@ -329,8 +371,17 @@ class Trainer:
         if sampler is not None and "rng_seed" in state:
             sampler.set_rng_state({"seed": state["rng_seed"], "episodes": state["rng_episodes"]})
 
-    def eval_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler) -> ConfusionMeter:
+    def eval_epoch(self, dataloader: Iterable, epoch_index: int, episode_sampler: EpisodeSampler,
+                   report=None) -> ConfusionMeter:
+        """``report`` (a ``report.EpisodeReport`` on the model's device): every batch runs ``run_episode``, which
+        returns all steps, and fills the report, which is returned - it has ``ConfusionMeter``'s reading methods.
+        None: the last step's vote into a ``ConfusionMeter``, as before."""
         self.__model.eval()
+        if report is not None:
+            with th.no_grad():
+                for x_test, y_test in dataloader:
+                    report.add(episode_sampler.run_episode(x_test).step_preds, y_test.to(self.__model.device))
+            return report
         conf_meter = ConfusionMeter(self.__nb_class, None)
         with th.no_grad():
             for x_test, y_test in dataloader:
