@@ -105,7 +105,8 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--augment", type=_arg(_augment_arg), default=None, dest="augment", metavar="SPEC",
                    help="device-side augmentation of the training split, fused into the batch gather: a comma-separated "
                         "list of hflip, vflip, rot90, d4, shift:T[:reflect|zero], erase:S[:p] (rot90 / d4 need square "
-                        "images; default: none)")
+                        "images) and, resampled bilinearly in the same launch, rotate:DEG (any angle in [-DEG, DEG]), "
+                        "scale:LO:HI (zoom, log-uniform) and stretch:R (aspect in [1/R, R]); default: none")
     t.add_argument("--mix", type=_arg(_mix_arg), default=None, dest="mix", metavar="SPEC",
                    help="CutMix / Mixup of the training split, fused into the batch gather: a comma-separated list of "
                         "cutmix[:alpha[:p]] and mixup[:alpha[:p]] (lam ~ Beta(alpha, alpha), per-image probability p; "
@@ -154,7 +155,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "averaged weights, optimiser step, generator position; same flags as the interrupted run")
     e.add_argument("--tta", type=_arg(_tta_arg), default=None, dest="tta", metavar="SPEC",
                    help="test-time augmentation: every batch runs once per flip / rotation the spec allows (hflip, "
-                        "vflip, rot90, d4) and the predictions are averaged (default: one run)")
+                        "vflip, rot90, d4), with zoom:Z1/Z2/... once per flip / rotation and zoom factor (multi-scale "
+                        "views, resampled bilinearly), and the predictions are averaged (default: one run)")
     for sp in (t, e):
         sp.add_argument("--report", action="store_true", dest="report",
                         help="episode report on the device: vote accuracy, top-k, NLL and agreement per step, every "

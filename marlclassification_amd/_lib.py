@@ -104,8 +104,10 @@ PANELOP_HOOKS = ("marl_panel_fwd", "marl_panel_bwd", "marl_panel_scratch_bytes",
 GEMMOP_HOOKS = ("marl_gemm_plan",)
 # ... and the episode report that include/marl_hip_report.h declares (beside the versioned ABI; report.py binds it)
 REPORT_ENTRIES = ("marl_report_layout", "marl_report_scratch_bytes", "marl_episode_report")
+# ... and the resampling batch gather that include/marl_hip_warp.h declares (likewise; warp.py binds it)
+WARP_ENTRIES = ("marl_batch_warp", "marl_batch_warp_plan")
 _HOOKS = (ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES +
-          PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES + GEMMOP_HOOKS + REPORT_ENTRIES)
+          PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES + GEMMOP_HOOKS + REPORT_ENTRIES + WARP_ENTRIES)
 # the launchers marl_gemm_plan answers for (its `kind`)
 GEMM_KINDS = ("nt", "lstm", "tn", "nt_images", "lstm_images", "tn_images", "tn_images_cell")
 MARL_PANEL_MAX_LAYERS = 4
@@ -314,6 +316,8 @@ def _declare(lib: C.CDLL) -> None:
                                     _vp]
     lib.marl_batch_augment.argtypes = [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
     lib.marl_batch_augment_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
+    lib.marl_batch_warp.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
+    lib.marl_batch_warp_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
     lib.marl_soft_targets.argtypes = [_vp, _i, _i]
     lib.marl_batch_mix.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp]
     lib.marl_batch_mix_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]

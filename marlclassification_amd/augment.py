@@ -16,11 +16,17 @@ So ``d4`` = 0 identity, 2 ``flip(-1)``, 4 ``flip(-2)``, 6 ``rot90(k=2)``, 1 tran
 (bit 0 dropped where ``H != W``), rows clamped to ``[0, N)``, ``|dy| <= H-1`` and ``|dx| <= W-1`` by clamping, the
 rectangle intersected with the image.  ``reference_apply`` is this definition in plain torch, on any device; ``apply``
 is the product: one kernel of libmarl_hip.so (include/marl_hip_augment.h), bit for bit the same.
+
+Rotation by any angle, zoom and aspect stretch (``rotate:DEG``, ``scale:LO:HI``, ``stretch:R``, the test-time
+``zoom:Z1/Z2/...``) are no index remapping: a policy with one of them (``Policy.has_warp``) draws a matrix per image
+besides the ops (``Policy.draw_warp``, ``Policy.warp_views``) and its batches go through the resampling gather of
+``warp.py``.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import struct
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -100,6 +106,15 @@ class Policy:
     erase_p: float = 0.5
     fill: int = 0
     spec: str = ""
+    rotate: float = 0.0                        # rotate:DEG - theta uniform in [-DEG, DEG]; 0: off
+    scale: Tuple[float, float] = (1.0, 1.0)    # scale:LO:HI - zoom log-uniform in [LO, HI]
+    stretch: float = 1.0                       # stretch:R - aspect log-uniform in [1/R, R]
+    zooms: Tuple[float, ...] = ()              # zoom:Z1/Z2/... - test-time views only (parse_tta)
+
+    @property
+    def has_warp(self) -> bool:
+        """The policy resamples (``warp.apply`` with ``draw_warp`` / ``warp_views``) rather than remaps indices."""
+        return self.rotate > 0 or self.scale != (1.0, 1.0) or self.stretch != 1.0 or len(self.zooms) > 0
 
     def group(self) -> Tuple[int, ...]:
         """The ``d4`` codes the spec allows."""
@@ -148,11 +163,45 @@ class Policy:
             ops[:, 5:7] = (on.to(th.int32) * self.erase).unsqueeze(1)
         return ops
 
+    def draw_warp(self, batch: int, generator: th.Generator,
+                  size: Optional[Tuple[int, int]] = None) -> Tuple[th.Tensor, th.Tensor]:
+        """``(ops, mats)`` on the generator's device, torch ops only (no host synchronisation).  The ops are drawn FIRST
+        through ``draw`` (a policy without warp tokens consumes the generator exactly as ``draw`` does), then one
+        uniform per image for each of ``rotate`` / ``scale`` / ``stretch`` the spec has, in this order; ``mats`` are
+        ``warp.matrices`` of them (``[batch, 8]`` int32)."""
+        from . import warp as _warp
+
+        ops = self.draw(batch, generator, size)
+        dev = generator.device
+
+        def uniform():
+            return th.rand(batch, generator=generator, device=dev)
+
+        angle = (2.0 * uniform() - 1.0) * self.rotate if self.rotate > 0 else th.zeros(batch, device=dev)
+        lo, hi = math.log(self.scale[0]), math.log(self.scale[1])
+        zoom = th.exp(lo + uniform() * (hi - lo)) if self.scale != (1.0, 1.0) else th.ones(batch, device=dev)
+        ratio = (th.exp((2.0 * uniform() - 1.0) * math.log(self.stretch)) if self.stretch != 1.0
+                 else th.ones(batch, device=dev))
+        return ops, _warp.matrices(angle, zoom, ratio)
+
+    def warp_views(self) -> Tuple[th.Tensor, th.Tensor]:
+        """Test-time augmentation under ``zoom:Z1/Z2/...``: ``(ops, mats)`` on the CPU, one row per (zoom, code) - the
+        zooms in the spec's order (none: 1), under each the codes of the group in ``views``' order."""
+        from . import warp as _warp
+
+        codes = self.views()
+        zooms = th.tensor(self.zooms or (1.0,), dtype=th.float32)
+        mats = _warp.matrices(th.zeros_like(zooms), zooms, th.ones_like(zooms))
+        return codes.repeat(zooms.shape[0], 1), mats.repeat_interleave(codes.shape[0], dim=0)
+
     def views(self) -> th.Tensor:
         """Test-time augmentation: one op row per code of the group, in the group's order (``[len(group), 8]`` int32
         on the CPU).  Random parts have no deterministic view: a spec with ``shift`` / ``erase`` is refused."""
         if self.shift > 0 or self.erase > 0:
             raise ValueError(f'augment "{self.spec}": shift / erase have no test-time views (flips and rotations do)')
+        if self.rotate > 0 or self.scale != (1.0, 1.0) or self.stretch != 1.0:
+            raise ValueError(f'augment "{self.spec}": rotate / scale / stretch are random and have no test-time views '
+                             "(zoom:Z1/Z2/... has)")
         ops = th.zeros(len(self.group()), OPS_WIDTH, dtype=th.int32)
         ops[:, 0] = th.tensor(self.group(), dtype=th.int32)
         return ops
@@ -164,9 +213,24 @@ def _int(text: str, token: str, lo: int) -> int:
     return int(text)
 
 
+def _floats(texts, token: str, lo: float, hi: float, what: str):
+    try:
+        values = [float(t) for t in texts]
+    except ValueError:
+        values = [float("nan")]
+    if not values or not all(lo <= v <= hi for v in values):  # (NaN fails too)
+        raise ValueError(f'augment: bad token "{token}" ({what})')
+    return values
+
+
 def parse(spec: str) -> Policy:
     """``hflip``, ``vflip``, ``rot90``, ``d4``, ``shift:T[:reflect|zero]`` (default reflect), ``erase:S[:p]`` (default
-    p = 0.5, fill 0), comma-separated.  Anything else: ValueError naming the token."""
+    p = 0.5, fill 0), ``rotate:DEG`` (0 < DEG <= 180), ``scale:LO:HI`` (1/16 <= LO <= HI <= 16), ``stretch:R``
+    (1 <= R <= 4), comma-separated.  Anything else: ValueError naming the token."""
+    return _parse(spec, tta=False)
+
+
+def _parse(spec: str, tta: bool) -> Policy:
     if not isinstance(spec, str):
         raise ValueError(f"augment: the spec must be a string, got {spec!r}")
     kw = {}
@@ -190,15 +254,33 @@ def parse(spec: str) -> Policy:
                 if not 0.0 <= p <= 1.0:  # (NaN fails too)
                     raise ValueError(f'augment: bad token "{token}" (the probability lies in [0, 1])')
                 kw["erase_p"] = p
+        elif head == "rotate" and len(rest) == 1:
+            kw["rotate"] = _floats(rest, token, 0.0, 180.0, "an angle in (0, 180] degrees is expected")[0]
+            if kw["rotate"] == 0.0:
+                raise ValueError(f'augment: bad token "{token}" (an angle in (0, 180] degrees is expected)')
+        elif head == "scale" and len(rest) == 2:
+            lo, hi = _floats(rest, token, 1.0 / 16, 16.0, "1/16 <= LO <= HI <= 16 is expected")
+            if lo > hi:
+                raise ValueError(f'augment: bad token "{token}" (1/16 <= LO <= HI <= 16 is expected)')
+            kw["scale"] = (lo, hi)
+        elif head == "stretch" and len(rest) == 1:
+            kw["stretch"] = _floats(rest, token, 1.0, 4.0, "an aspect ratio in [1, 4] is expected")[0]
+        elif head == "zoom" and len(rest) == 1:
+            if not tta:
+                raise ValueError(f'augment: bad token "{token}" (zoom views exist at test time only: test --tta; '
+                                 "scale:LO:HI draws zooms in training)")
+            kw["zooms"] = tuple(_floats(rest[0].split("/"), token, 1.0 / 16, 16.0,
+                                        "zoom factors Z1/Z2/... in [1/16, 16] are expected"))
         else:
             raise ValueError(f'augment: unknown token "{token}" (hflip, vflip, rot90, d4, shift:T[:reflect|zero], '
-                             "erase:S[:p])")
+                             "erase:S[:p], rotate:DEG, scale:LO:HI, stretch:R; test --tta also zoom:Z1/Z2/...)")
     return Policy(spec=spec, **kw)
 
 
 def parse_tta(spec: str) -> Policy:
-    """``test --tta SPEC``: a spec with deterministic views only."""
-    policy = parse(spec)
+    """``test --tta SPEC``: a spec with deterministic views only - the flips and rotations, and ``zoom:Z1/Z2/...``
+    (every code of the group under every zoom factor: ``Policy.warp_views``)."""
+    policy = _parse(spec, tta=True)
     policy.views()
     return policy
 

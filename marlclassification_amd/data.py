@@ -81,7 +81,7 @@ class DevicePrefetcher:
         self.loader = loader
         self.device = th.device(device)
         self.mix, self.nb_class = mix, _mix_classes(mix, nb_class)
-        self.augment = augment
+        self.augment = _no_mixed_warp(augment, mix)
         self.generator = _device_generator(augment if mix is None else mix, generator, self.device)
 
     def _upload(self, batch, stream):
@@ -128,13 +128,27 @@ def _device_generator(policy, generator, device: th.device):
     return th.Generator(device=device).manual_seed(0)
 
 
+def _no_mixed_warp(augment, mix):
+    """the augment policy of a loader; together with a mix policy it may not resample"""
+    if mix is not None and augment is not None and augment.has_warp:
+        raise ValueError(f'augment "{augment.spec}" with a mix policy: mixing warped views is not built '
+                         "(marl_batch_mix remaps indices; rotate / scale / stretch resample)")
+    return augment
+
+
 def _augmented(policy, generator, x: th.Tensor, rows):
-    """``augment.apply`` of ``x[rows]`` (``rows`` None: ``x`` itself) under freshly drawn ops; a policy that turns
-    images refuses non-square ones before anything is enqueued"""
+    """``augment.apply`` of ``x[rows]`` (``rows`` None: ``x`` itself) under freshly drawn ops - ``warp.apply`` under
+    freshly drawn ops and matrices for a policy that resamples; a policy that turns images refuses non-square ones
+    before anything is enqueued"""
     from . import augment as _augment
 
     policy.check_size(x.shape[-2], x.shape[-1])
     batch = x.shape[0] if rows is None else rows.shape[0]
+    if policy.has_warp:
+        from . import warp as _warp
+
+        ops, mats = policy.draw_warp(batch, generator, size=(x.shape[-2], x.shape[-1]))
+        return _warp.apply(x, rows, mats, ops, pad_mode=policy.pad_mode, fill=policy.fill)
     ops = policy.draw(batch, generator, size=(x.shape[-2], x.shape[-1]))
     return _augment.apply(x, rows, ops, pad_mode=policy.pad_mode, fill=policy.fill)
 
@@ -222,7 +236,9 @@ class ResidentLoader:
     ``augment`` (an ``augment.Policy``): every batch is ``augment.apply(resident set, rows, ops)`` - the gather with
     flips, quarter turns, shifts and erasing fused in, one launch that moves the bytes ``index_select`` moves - under
     ops drawn from ``generator`` (a generator of ``device``) without a host synchronisation.  Labels are gathered as
-    before.  None: exactly the ``index_select`` above.
+    before.  None: exactly the ``index_select`` above.  A policy with ``rotate`` / ``scale`` / ``stretch``
+    (``Policy.has_warp``) goes through ``warp.apply`` under ``Policy.draw_warp`` instead: the gather with the bilinear
+    resampling fused in, still one launch and no host synchronisation.
 
     ``mix`` (a ``mix.Policy``, with ``nb_class``): every batch is mixed with a permutation of itself (CutMix / Mixup,
     ``mix.apply`` from the resident set: the views are the augmented ones, still one launch) and the loader yields
@@ -238,7 +254,7 @@ class ResidentLoader:
         self._x = self._y = self._row_of = None
         self.fill_img_s = float("nan")
         self.mix, self.nb_class = mix, _mix_classes(mix, nb_class)
-        self.augment = augment
+        self.augment = _no_mixed_warp(augment, mix)
         self.generator = _device_generator(augment if mix is None else mix, generator, self.device)
 
     @staticmethod

@@ -42,13 +42,24 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
                                          num_workers=0, drop_last=False, pin_memory=True), device)
     sampler = EpisodeSampler(marl_m, env, main_config.step)
     meter = ConfusionMeter(nn_models.nb_class)
-    views = None
+    views = view_mats = None
     if eval_config.tta is not None:  # (--tta: one episode per flip / rotation of the spec, predictions averaged)
         from . import augment as _augment
 
         policy = _augment.parse_tta(eval_config.tta)
         policy.check_size(eval_config.img_size, eval_config.img_size)
         views = policy.views().to(device)
+        if policy.has_warp:  # (zoom:Z1/Z2/...: every code under every zoom, through the resampling gather)
+            views, view_mats = (t.to(device) for t in policy.warp_views())
+
+    def view_of(x, v):
+        ops = views[v: v + 1].expand(x.shape[0], -1).contiguous()
+        if view_mats is None:
+            return _augment.apply(x, None, ops)
+        from . import warp as _warp
+
+        return _warp.apply(x, None, view_mats[v: v + 1].expand(x.shape[0], -1).contiguous(), ops)
+
     rep = None
     if eval_config.report:  # (--report: every step of every episode into an episode report, report.py)
         from .report import EpisodeReport, ReportOptions, parse_exit_at, step_table
@@ -59,24 +70,21 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
         rep = EpisodeReport(main_config.step, main_config.nb_agent * n_views, nn_models.nb_class, opts, device)
         with th.no_grad():
             for x, y in loader:
-                if n_views == 1:
+                if n_views == 1 and view_mats is None:
                     preds = sampler.run_episode(x).step_preds
                 else:
-                    preds = th.cat([sampler.run_episode(_augment.apply(
-                        x, None, views[v: v + 1].expand(x.shape[0], -1).contiguous())).step_preds
-                        for v in range(n_views)], dim=1)
+                    preds = th.cat([sampler.run_episode(view_of(x, v)).step_preds for v in range(n_views)], dim=1)
                 rep.add(preds, y.to(device))
         meter = rep  # (it has the meter's reading methods)
     with th.no_grad():
         for x, y in (() if rep is not None else loader):
-            if views is None or views.shape[0] == 1:
+            if views is None or (views.shape[0] == 1 and view_mats is None):
                 out = sampler.run_episode_get_last_step(x)
                 meter.add(out.prediction.mean(dim=0), y)  # mean over agents; stays on the device
                 continue
             pred = None
             for v in range(views.shape[0]):
-                xv = _augment.apply(x, None, views[v: v + 1].expand(x.shape[0], -1).contiguous())
-                p = sampler.run_episode_get_last_step(xv).prediction.mean(dim=0)
+                p = sampler.run_episode_get_last_step(view_of(x, v)).prediction.mean(dim=0)
                 pred = p if pred is None else pred + p
             meter.add(pred / views.shape[0], y)
 
