@@ -314,6 +314,42 @@ def _need_images(t: th.Tensor, name: str) -> None:
         raise ValueError(f"{name} must be a contiguous [N, C, H, W] tensor, got {tuple(t.shape)}")
 
 
+def _launch(who: str, entry: str, src: th.Tensor, nb: int, rows: Optional[th.Tensor], tables, mode: int, fill,
+            out: Optional[th.Tensor], rows_shape: str = "B", ready=None) -> th.Tensor:
+    """What the ``apply`` of ``augment``, ``mix`` and ``warp`` share, behind their pad-mode, ``src`` and batch-size
+    checks: ``rows``, the int32 ``[nb, width]`` ``tables`` (``(name, tensor or None, width)`` in the order ``entry``
+    takes them) and ``out`` are checked (``out`` allocated if None), then ``entry`` of libmarl_hip.so is called on the
+    current stream.  ``ready()``, if given, is called once everything is checked and returns the tensors to pass in
+    place of the tables."""
+    from . import _lib
+
+    dev = src.device
+    if rows is not None and (rows.device != dev or rows.dtype != th.int64 or tuple(rows.shape) != (nb,)
+                             or not rows.is_contiguous()):
+        raise ValueError(f"{who}: rows must be a contiguous int64 [{rows_shape}] tensor on {dev}")
+    for name, t, width in tables:
+        if t is not None and (t.device != dev or t.dtype != th.int32 or tuple(t.shape) != (nb, width)
+                              or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous int32 [{nb}, {width}] tensor on {dev}")
+    shape = (nb,) + tuple(src.shape[1:])
+    if out is None:
+        out = th.empty(shape, dtype=src.dtype, device=dev)
+    else:
+        _need_images(out, f"{who}: out")
+        if out.device != dev or out.dtype != src.dtype or tuple(out.shape) != shape:
+            raise ValueError(f"{who}: out must be a {src.dtype} {shape} tensor on {dev}")
+    if nb == 0:
+        return out
+    bits = _fill_bits(fill, src.dtype)
+    tensors = ready() if ready is not None else [t for _, t, _ in tables]
+    with th.cuda.device(dev):
+        _lib.check(getattr(_lib.load(), entry)(
+            src.data_ptr(), src.shape[0], out.data_ptr(), None if rows is None else rows.data_ptr(),
+            *(None if t is None else t.data_ptr() for t in tensors), nb, src.shape[1], src.shape[2], src.shape[3],
+            src.element_size(), mode, bits, th.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 def plan(src: th.Tensor, out: th.Tensor) -> dict:
     """What ``apply(src, ..., out=out)`` launches (``marl_batch_augment_plan``): store width, tiles, LDS bytes."""
     from . import _lib
@@ -330,31 +366,7 @@ def apply(src: th.Tensor, rows: Optional[th.Tensor] = None, ops: Optional[th.Ten
     """``reference_apply`` on GPU tensors, as one launch on the current stream: ``src`` contiguous ``[N, C, H, W]``
     uint8 or float32, ``rows`` int64 ``[B]`` (None: row b for image b), ``ops`` int32 ``[B, 8]`` (None: a plain
     gather), ``out`` (None: a fresh tensor) must not overlap ``src``."""
-    from . import _lib
-
     mode = _check_pad(pad_mode)
     _need_images(src, "augment.apply: src")
-    nb = _batch_of(src, rows, ops)
-    dev = src.device
-    if rows is not None and (rows.device != dev or rows.dtype != th.int64 or rows.dim() != 1
-                             or not rows.is_contiguous()):
-        raise ValueError(f"augment.apply: rows must be a contiguous int64 [B] tensor on {dev}")
-    if ops is not None and (ops.device != dev or ops.dtype != th.int32 or tuple(ops.shape) != (nb, OPS_WIDTH)
-                            or not ops.is_contiguous()):
-        raise ValueError(f"augment.apply: ops must be a contiguous int32 [{nb}, {OPS_WIDTH}] tensor on {dev}")
-    shape = (nb,) + tuple(src.shape[1:])
-    if out is None:
-        out = th.empty(shape, dtype=src.dtype, device=dev)
-    else:
-        _need_images(out, "augment.apply: out")
-        if out.device != dev or out.dtype != src.dtype or tuple(out.shape) != shape:
-            raise ValueError(f"augment.apply: out must be a {src.dtype} {shape} tensor on {dev}")
-    if nb == 0:
-        return out
-    bits = _fill_bits(fill, src.dtype)
-    with th.cuda.device(dev):
-        _lib.check(_lib.load().marl_batch_augment(
-            src.data_ptr(), src.shape[0], out.data_ptr(), None if rows is None else rows.data_ptr(),
-            None if ops is None else ops.data_ptr(), nb, src.shape[1], src.shape[2], src.shape[3],
-            src.element_size(), mode, bits, th.cuda.current_stream(dev).cuda_stream))
-    return out
+    return _launch("augment.apply", "marl_batch_augment", src, _batch_of(src, rows, ops), rows,
+                   [("ops", ops, OPS_WIDTH)], mode, fill, out)

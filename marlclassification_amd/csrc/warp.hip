@@ -13,7 +13,7 @@
 // plane.  The map is linear in integers, so the thread computes Sy, Sx of its first pixel with 64-bit products and
 // adds 2 a01, 2 a11 per pixel: the same integers as the definition's products.
 // Taps are direct global loads: neighbouring lanes' taps share cache lines under any rotation.
-#include "common.h"
+#include "gather.h"
 
 #include "../../include/marl_hip_warp.h"
 
@@ -90,12 +90,6 @@ __device__ __forceinline__ Axis resolve(int64_t s, int n, int reflect) {
 // what a thread keeps of a pixel besides the offset of tap (y0, x0)
 constexpr int kFy = 8, kStepX = 16, kStepY = 18, kOutX = 20, kOutY = 22, kErased = 24;
 
-template <int ELT>
-__device__ __forceinline__ uint32_t load_elt(const uint8_t* __restrict__ plane, uint32_t off) {
-    if constexpr (ELT == 1) return plane[off];
-    else return reinterpret_cast<const uint32_t*>(plane)[off];
-}
-
 __device__ __forceinline__ uint32_t blend_u8(const uint32_t v[4], uint32_t fx, uint32_t fy) {
     const uint32_t top = v[0] * (256u - fx) + v[1] * fx;
     const uint32_t bot = v[2] * (256u - fx) + v[3] * fx;
@@ -119,14 +113,6 @@ __device__ __forceinline__ uint32_t blend_f32(const uint32_t v[4], uint32_t fx, 
     return __float_as_uint(lerp_f32(top, bot, fy));
 }
 
-template <int V>
-__device__ __forceinline__ void store_vec(uint8_t* __restrict__ p, const uint32_t* q) {
-    if constexpr (V == 16) *reinterpret_cast<uint4*>(p) = make_uint4(q[0], q[1], q[2], q[3]);
-    else if constexpr (V == 8) *reinterpret_cast<uint2*>(p) = make_uint2(q[0], q[1]);
-    else if constexpr (V == 4) *reinterpret_cast<uint32_t*>(p) = q[0];
-    else *p = (uint8_t)q[0];
-}
-
 template <int ELT, int V>
 __global__ void __launch_bounds__(kWarpThreads) batch_warp_kernel(const WarpArgs a) {
     constexpr int N = V / ELT;
@@ -140,17 +126,17 @@ __global__ void __launch_bounds__(kWarpThreads) batch_warp_kernel(const WarpArgs
     const int64_t a00 = clamp64(m[0], -kMaxA, kMaxA), a01 = clamp64(m[1], -kMaxA, kMaxA);
     const int64_t a10 = clamp64(m[2], -kMaxA, kMaxA), a11 = clamp64(m[3], -kMaxA, kMaxA);
     const int64_t ty = clamp64(m[4], -kMaxT, kMaxT), tx = clamp64(m[5], -kMaxT, kMaxT);
+    // (fields 3..6 of ops[b] as gather.h's view_of reads them, read here: fields 0..2 are in the matrices, and taking
+    // the rectangle from view_of<false> moves this kernel's code - DESIGN 8.27)
     int ey0 = 0, ey1 = 0, ex0 = 0, ex1 = 0;
     if (a.ops != nullptr) {
         const int32_t* __restrict__ p = a.ops + (size_t)b * 8;
-        ey0 = (int)clamp64(p[3], 0, a.h);
-        ey1 = (int)clamp64((int64_t)p[3] + p[5], 0, a.h);
-        ex0 = (int)clamp64(p[4], 0, a.w);
-        ex1 = (int)clamp64((int64_t)p[4] + p[6], 0, a.w);
+        ey0 = clampl(p[3], 0, a.h);
+        ey1 = clampl((int64_t)p[3] + p[5], 0, a.h);
+        ex0 = clampl(p[4], 0, a.w);
+        ex1 = clampl((int64_t)p[4] + p[6], 0, a.w);
     }
-    int64_t row = a.rows ? a.rows[b] : (int64_t)b;
-    row = row < 0 ? 0 : (row >= a.n_src ? a.n_src - 1 : row);
-    const uint8_t* __restrict__ sp = a.src + row * a.img_bytes;  // 64-bit: a resident set is larger than 4 GB
+    const uint8_t* __restrict__ sp = a.src + clamp_row(a.rows ? a.rows[b] : (int64_t)b, a.n_src) * a.img_bytes;
 
     const uint32_t idx = (uint32_t)t * kWarpThreads + threadIdx.x;
     if (idx >= a.plane_vec) return;
@@ -211,11 +197,11 @@ __global__ void __launch_bounds__(kWarpThreads) batch_warp_kernel(const WarpArgs
                     if ((ox | oy) >> 1) v[k][3] = a.fill;
                 }
                 const uint32_t fx = pk[e] & 255u, fy = (pk[e] >> kFy) & 255u;
-                uint32_t o = ELT == 1 ? blend_u8(v[k], fx, fy) : blend_f32(v[k], fx, fy);
-                if ((pk[e] >> kErased) & 1u) o = a.fill;
-                if constexpr (ELT == 4) q[e] = o;
-                else if constexpr (V == 1) q[0] = o;
-                else q[e >> 2] |= o << (8 * (e & 3));
+                uint32_t px = ELT == 1 ? blend_u8(v[k], fx, fy) : blend_f32(v[k], fx, fy);
+                if ((pk[e] >> kErased) & 1u) px = a.fill;
+                if constexpr (ELT == 4) q[e] = px;
+                else if constexpr (V == 1) q[0] = px;
+                else q[e >> 2] |= px << (8 * (e & 3));  // (set_elt without its mask: px <= 255)
             }
             if constexpr (N > G) __builtin_amdgcn_sched_barrier(0);  // (keeps the next group's loads behind this blend)
         }
@@ -223,56 +209,6 @@ __global__ void __launch_bounds__(kWarpThreads) batch_warp_kernel(const WarpArgs
         sp += plane_bytes;
         dp += plane_bytes;
     }
-}
-
-struct WarpPlan {
-    int store_bytes, nv, blocks_per_image;
-    uint32_t plane_vec;
-};
-
-int warp_plan(const char* who, int c, int h, int w, int elt, const void* src, const void* dst, WarpPlan* p) {
-    if (elt != 1 && elt != 4) {
-        set_error("%s: elt_bytes %d is neither 1 nor 4", who, elt);
-        return MARL_EINVAL;
-    }
-    if (c <= 0 || h <= 0 || w <= 0) {
-        set_error("%s: sizes must be positive (c %d, h %d, w %d)", who, c, h, w);
-        return MARL_EINVAL;
-    }
-    const uintptr_t s = reinterpret_cast<uintptr_t>(src), d = reinterpret_cast<uintptr_t>(dst);
-    if (elt == 4 && ((s | d) & 3)) {
-        set_error("%s: 4-byte elements need 4-byte aligned src and dst", who);
-        return MARL_EINVAL;
-    }
-    const int64_t img_bytes = (int64_t)c * h * w * elt;
-    if (img_bytes >= (int64_t)1 << 31) {
-        set_error("%s: an image of %lld bytes (c %d, h %d, w %d) is beyond 2^31", who, (long long)img_bytes, c, h, w);
-        return MARL_ELIMIT;
-    }
-    const int64_t row_bytes = (int64_t)w * elt;
-    int v = 16;
-    while (v > elt && ((row_bytes % v) != 0 || (d % v) != 0)) v >>= 1;
-    if (v < 4) v = elt;  // (uint8 rows that are no multiple of 4 bytes: byte stores)
-    p->store_bytes = v;
-    p->nv = (int)(row_bytes / v);
-    p->plane_vec = (uint32_t)((int64_t)h * p->nv);
-    p->blocks_per_image = (int)cdiv(p->plane_vec, kWarpThreads);
-    return MARL_OK;
-}
-
-template <int ELT>
-int launch(const WarpArgs& a, int v, int64_t blocks, hipStream_t st) {
-    const dim3 grid((unsigned)blocks), block(kWarpThreads);
-    switch (v) {
-        case 16: batch_warp_kernel<ELT, 16><<<grid, block, 0, st>>>(a); break;
-        case 8: batch_warp_kernel<ELT, 8><<<grid, block, 0, st>>>(a); break;
-        case 4: batch_warp_kernel<ELT, 4><<<grid, block, 0, st>>>(a); break;
-        default:
-            if constexpr (ELT == 1) batch_warp_kernel<1, 1><<<grid, block, 0, st>>>(a);
-            break;
-    }
-    MARL_LAUNCH_CHECK();
-    return MARL_OK;
 }
 
 }  // namespace
@@ -286,14 +222,14 @@ extern "C" int marl_batch_warp_plan(int c, int h, int w, int elt_bytes, const vo
         set_error("marl_batch_warp_plan: null argument");
         return MARL_EINVAL;
     }
-    WarpPlan p{};
-    MARL_TRY(warp_plan("marl_batch_warp_plan", c, h, w, elt_bytes, src, dst, &p));
+    GatherPlan g{};
+    MARL_TRY(gather_plan("marl_batch_warp_plan", c, h, w, elt_bytes, src, dst, &g));
     *out = marl_warp_plan_info{};
-    out->store_bytes = p.store_bytes;
-    out->pixels_per_thread = p.store_bytes / elt_bytes;
-    out->vectors_per_row = p.nv;
+    out->store_bytes = g.store_bytes;
+    out->pixels_per_thread = g.store_bytes / elt_bytes;
+    out->vectors_per_row = g.nv;
     out->threads = kWarpThreads;
-    out->blocks_per_image = p.blocks_per_image;
+    out->blocks_per_image = (int)cdiv((int64_t)h * g.nv, kWarpThreads);
     out->lds_bytes = 0;
     return MARL_OK;
 }
@@ -302,58 +238,19 @@ extern "C" int marl_batch_warp(const void* src, int64_t n_src, void* dst, const 
                                const int32_t* ops, int batch, int c, int h, int w, int elt_bytes, int pad_mode,
                                uint32_t fill_bits, void* stream) {
     static const char* who = "marl_batch_warp";
-    if (src == nullptr || dst == nullptr) {
-        set_error("%s: null src / dst", who);
-        return MARL_EINVAL;
-    }
-    if (mats == nullptr) {
+    if (src != nullptr && dst != nullptr && mats == nullptr) {  // (behind the null src / dst answer, before the others)
         set_error("%s: null mats (a plain gather is marl_batch_augment's)", who);
         return MARL_EINVAL;
     }
-    if (pad_mode != MARL_AUGMENT_PAD_ZERO && pad_mode != MARL_AUGMENT_PAD_REFLECT) {
-        set_error("%s: unknown pad_mode %d", who, pad_mode);
-        return MARL_EINVAL;
-    }
-    if (batch <= 0 || n_src <= 0) {
-        set_error("%s: sizes must be positive (batch %d, n_src %lld)", who, batch, (long long)n_src);
-        return MARL_EINVAL;
-    }
-    WarpPlan p{};
-    MARL_TRY(warp_plan(who, c, h, w, elt_bytes, src, dst, &p));
-    if (rows == nullptr && n_src < batch) {
-        set_error("%s: rows == NULL takes row b for image b, but n_src %lld < batch %d", who, (long long)n_src, batch);
-        return MARL_EINVAL;
-    }
-    const int64_t img_bytes = (int64_t)c * h * w * elt_bytes;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
-    if (n_src > (INT64_MAX / 2) / img_bytes) {
-        set_error("%s: n_src %lld images of %lld bytes overflow", who, (long long)n_src, (long long)img_bytes);
-        return MARL_ELIMIT;
-    }
-    const uintptr_t s1 = s0 + (uintptr_t)(n_src * img_bytes), d1 = d0 + (uintptr_t)((int64_t)batch * img_bytes);
-    if (d0 < s1 && s0 < d1) {
-        set_error("%s: dst overlaps src (a tap would read what another workgroup wrote)", who);
-        return MARL_EINVAL;
-    }
-    const int64_t blocks = (int64_t)batch * p.blocks_per_image;
-    if (blocks > 0x7fffffffLL) {
-        set_error("%s: %lld workgroups (batch %d) are more than a grid holds", who, (long long)blocks, batch);
-        return MARL_ELIMIT;
-    }
-    WarpArgs a{};
-    a.src = static_cast<const uint8_t*>(src);
-    a.dst = static_cast<uint8_t*>(dst);
-    a.rows = rows;
+    const GatherCall call{src, n_src, dst, rows, ops, batch, c, h, w, elt_bytes, pad_mode, fill_bits};
+    GatherPlan g{};
+    MARL_TRY(gather_guard(who, "a tap would read what another workgroup wrote", call, &g));
+    WarpArgs a = gather_args<WarpArgs>(call, g);
     a.mats = mats;
-    a.ops = ops;
-    a.n_src = n_src;
-    a.img_bytes = img_bytes;
-    a.c = c, a.h = h, a.w = w;
-    a.nv = p.nv;
-    a.plane_vec = p.plane_vec;
-    a.blocks_per_image = p.blocks_per_image;
-    a.reflect = pad_mode == MARL_AUGMENT_PAD_REFLECT;
-    a.fill = elt_bytes == 1 ? (fill_bits & 0xffu) : fill_bits;
+    a.plane_vec = (uint32_t)((int64_t)h * g.nv);
+    a.blocks_per_image = (int)cdiv(a.plane_vec, kWarpThreads);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return elt_bytes == 1 ? launch<1>(a, p.store_bytes, blocks, st) : launch<4>(a, p.store_bytes, blocks, st);
+    return gather_launch(who, call, g, a.blocks_per_image, [&](auto elt, auto v, dim3 grid) {
+        batch_warp_kernel<elt, v><<<grid, kWarpThreads, 0, st>>>(a);
+    });
 }

@@ -248,37 +248,13 @@ def apply(src: th.Tensor, rows: Optional[th.Tensor] = None, ops: Optional[th.Ten
     uint8 or float32, ``rows`` int64 ``[B]`` (None: row b for image b), ``ops`` int32 ``[B, 8]`` (None: zeros), ``mix``
     int32 ``[B, 8]`` (None: zeros - then byte for byte ``augment.apply``), ``out`` (None: a fresh tensor) must not
     overlap ``src``."""
-    from . import _lib
-
     mode = _augment._check_pad(pad_mode)
     _augment._need_images(src, "mix.apply: src")
-    dev = src.device
     if rows is not None:
         nb = int(rows.shape[0])
     elif ops is not None:
         nb = int(ops.shape[0])
     else:
         nb = int(mix.shape[0]) if mix is not None else int(src.shape[0])
-    if rows is not None and (rows.device != dev or rows.dtype != th.int64 or rows.dim() != 1
-                             or not rows.is_contiguous()):
-        raise ValueError(f"mix.apply: rows must be a contiguous int64 [B] tensor on {dev}")
-    for name, t, width in (("ops", ops, _augment.OPS_WIDTH), ("mix", mix, MIX_WIDTH)):
-        if t is not None and (t.device != dev or t.dtype != th.int32 or tuple(t.shape) != (nb, width)
-                              or not t.is_contiguous()):
-            raise ValueError(f"mix.apply: {name} must be a contiguous int32 [{nb}, {width}] tensor on {dev}")
-    shape = (nb,) + tuple(src.shape[1:])
-    if out is None:
-        out = th.empty(shape, dtype=src.dtype, device=dev)
-    else:
-        _augment._need_images(out, "mix.apply: out")
-        if out.device != dev or out.dtype != src.dtype or tuple(out.shape) != shape:
-            raise ValueError(f"mix.apply: out must be a {src.dtype} {shape} tensor on {dev}")
-    if nb == 0:
-        return out
-    bits = _augment._fill_bits(fill, src.dtype)
-    with th.cuda.device(dev):
-        _lib.check(_lib.load().marl_batch_mix(
-            src.data_ptr(), src.shape[0], out.data_ptr(), None if rows is None else rows.data_ptr(),
-            None if ops is None else ops.data_ptr(), None if mix is None else mix.data_ptr(), nb, src.shape[1],
-            src.shape[2], src.shape[3], src.element_size(), mode, bits, th.cuda.current_stream(dev).cuda_stream))
-    return out
+    return _augment._launch("mix.apply", "marl_batch_mix", src, nb, rows,
+                            [("ops", ops, _augment.OPS_WIDTH), ("mix", mix, MIX_WIDTH)], mode, fill, out)

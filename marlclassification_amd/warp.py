@@ -35,7 +35,7 @@ from typing import Optional
 
 import torch as th
 
-from .augment import OPS_WIDTH, _check_pad, _fill_bits, _need_images
+from .augment import OPS_WIDTH, _check_pad, _launch, _need_images
 
 MATS_WIDTH = 8
 ONE = 65536  # 1.0 in Q16
@@ -229,8 +229,6 @@ def apply(src: th.Tensor, rows: Optional[th.Tensor], mats: th.Tensor, ops: Optio
     ``[B, 8]`` or None, ``out`` (None: a fresh tensor) must not overlap ``src``.  With ``ops``, its fields 0..2 (a
     dihedral code and a shift: "warp, then view") are folded into the matrices by ``compose_ops`` - a few torch ops on
     the device, no host synchronisation - and its rectangle goes to the kernel."""
-    from . import _lib
-
     mode = _check_pad(pad_mode)
     _need_images(src, "warp.apply: src")
     dev = src.device
@@ -238,27 +236,9 @@ def apply(src: th.Tensor, rows: Optional[th.Tensor], mats: th.Tensor, ops: Optio
             or mats.shape[1] != MATS_WIDTH or not mats.is_contiguous()):
         raise ValueError(f"warp.apply: mats must be a contiguous int32 [B, {MATS_WIDTH}] tensor on {dev}")
     nb = int(mats.shape[0])
-    if rows is not None and (rows.device != dev or rows.dtype != th.int64 or tuple(rows.shape) != (nb,)
-                             or not rows.is_contiguous()):
-        raise ValueError(f"warp.apply: rows must be a contiguous int64 [{nb}] tensor on {dev}")
-    if ops is not None and (ops.device != dev or ops.dtype != th.int32 or tuple(ops.shape) != (nb, OPS_WIDTH)
-                            or not ops.is_contiguous()):
-        raise ValueError(f"warp.apply: ops must be a contiguous int32 [{nb}, {OPS_WIDTH}] tensor on {dev}")
-    shape = (nb,) + tuple(src.shape[1:])
-    if out is None:
-        out = th.empty(shape, dtype=src.dtype, device=dev)
-    else:
-        _need_images(out, "warp.apply: out")
-        if out.device != dev or out.dtype != src.dtype or tuple(out.shape) != shape:
-            raise ValueError(f"warp.apply: out must be a {src.dtype} {shape} tensor on {dev}")
-    if nb == 0:
-        return out
-    bits = _fill_bits(fill, src.dtype)
-    if ops is not None:
-        mats = compose_ops(mats, ops, src.shape[2], src.shape[3]).contiguous()
-    with th.cuda.device(dev):
-        _lib.check(_lib.load().marl_batch_warp(
-            src.data_ptr(), src.shape[0], out.data_ptr(), None if rows is None else rows.data_ptr(), mats.data_ptr(),
-            None if ops is None else ops.data_ptr(), nb, src.shape[1], src.shape[2], src.shape[3],
-            src.element_size(), mode, bits, th.cuda.current_stream(dev).cuda_stream))
-    return out
+
+    def composed():  # "warp, then view", once ops is known to be what compose_ops takes
+        return [mats if ops is None else compose_ops(mats, ops, src.shape[2], src.shape[3]).contiguous(), ops]
+
+    return _launch("warp.apply", "marl_batch_warp", src, nb, rows, [("ops", ops, OPS_WIDTH)], mode, fill, out,
+                   rows_shape=str(nb), ready=composed)
