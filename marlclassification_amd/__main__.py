@@ -153,6 +153,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="continue an interrupted run bit for bit from models/trainer_epoch_{e}.pt (written every "
                         "checkpoint epoch next to nn_models_epoch_{e}.pt, which is loaded with it): Adam moments, "
                         "averaged weights, optimiser step, generator position; same flags as the interrupted run")
+    t.add_argument("--normalize", type=_arg(_normalize_arg), default=None, dest="normalize", metavar="SPEC",
+                   help="per-image input normalisation on the device, part of the model (written to marl.json; test "
+                        "and infer read it): normal | channel-normal | minmax | channel-minmax | "
+                        "user-normal:m0,m1,..:s0,s1,.. | user-minmax:lo0,..:hi0,.. | dataset (the mean / std of the "
+                        "training split, stored as user-normal:...); default: off")
+    for sp in (e, i):
+        sp.add_argument("--normalize", type=_arg(_normalize_override), default=None, dest="normalize",
+                        metavar="SPEC|none",
+                        help="replaces the input normalisation marl.json names (none: off; default: keep it)")
     e.add_argument("--tta", type=_arg(_tta_arg), default=None, dest="tta", metavar="SPEC",
                    help="test-time augmentation: every batch runs once per flip / rotation the spec allows (hflip, "
                         "vflip, rot90, d4), with zoom:Z1/Z2/... once per flip / rotation and zoom factor (multi-scale "
@@ -200,6 +209,19 @@ def _arg(parse):
 
 def _augment_arg(text: str) -> str:
     return parse_augment(text).spec
+
+
+def _normalize_arg(text: str) -> str:
+    from .transforms import parse as parse_normalize
+
+    return parse_normalize(text).spelling  # ("dataset" stays: train resolves it against the training split)
+
+
+def _normalize_override(text: str) -> str:
+    from .transforms import resolve
+
+    spec = resolve(text)  # ("dataset" has nothing to be resolved against here: refused)
+    return "none" if spec is None else spec.spelling
 
 
 def _mix_arg(text: str) -> str:
@@ -308,7 +330,7 @@ def main(argv=None) -> None:
             hidden_size_msg_output=args.n_m_o, hidden_size_state=args.n_d, state_dim=args.dim,
             actions=parse_actions(args.action, args.dim), nb_class=args.nb_class,
             hidden_size_linear_belief=args.n_l_b, hidden_size_linear_action=args.n_l_a,
-            comm=args.comm, comm_range=args.comm_range,
+            comm=args.comm, comm_range=args.comm_range, normalize=args.normalize,
         )
         train_config = TrainConfig(
             img_size=args.img_size, nb_epoch=args.nb_epoch, learning_rate=args.learning_rate,
@@ -332,7 +354,7 @@ def main(argv=None) -> None:
             img_size=args.img_size, state_dict_path=args.state_dict_path, batch_size=args.batch_size,
             json_path=args.json_path, dataset_path=args.dataset_path, output_dir=args.output_dir,
             comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature,
-            tta=args.tta, report=args.report, report_topk=args.report_topk, report_bins=args.report_bins,
+            tta=args.tta, normalize=args.normalize, report=args.report, report_topk=args.report_topk, report_bins=args.report_bins,
             exit_at=args.exit_at))
     elif args.main_choice == "infer":
         import os
@@ -345,7 +367,8 @@ def main(argv=None) -> None:
         infer_main(main_config, InferConfig(
             state_dict_path=args.state_dict_path, json_path=args.json_path, images_path=args.infer_images,
             output_dir=args.output_image_dir, class_to_idx=args.class_to_idx, saliency=args.saliency,
-            comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature))
+            comm=args.comm, comm_range=args.comm_range, greedy=args.greedy, temperature=args.temperature,
+            normalize=args.normalize))
 
 
 if __name__ == "__main__":

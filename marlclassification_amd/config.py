@@ -45,6 +45,10 @@ class ModelConfig(BaseModel):
     # range-limited communication in the command-line spelling (comm.parse_range: R[:chebyshev|euclidean][:raw]);
     # None: off - and the key is not written
     comm_range: Optional[str] = None
+    # per-image input normalisation in the command-line spelling (transforms.parse: normal | channel-normal | minmax |
+    # channel-minmax | user-normal:m..:s.. | user-minmax:lo..:hi..); part of the model like comm - train, test and infer
+    # must see the same pixels.  None: off - and the key is not written
+    normalize: Optional[str] = None
 
     def save_marl_config(self, out_json_path: str) -> None:
         raw = {k: getattr(self, k) for k in _MODEL_KEYS}
@@ -52,6 +56,8 @@ class ModelConfig(BaseModel):
             raw["comm"] = self.comm
         if self.comm_range is not None:
             raw["comm_range"] = self.comm_range
+        if self.normalize is not None:
+            raw["normalize"] = self.normalize
         with open(out_json_path, "w", encoding="utf-8") as f:
             json.dump(raw, f)
 
@@ -60,7 +66,8 @@ class ModelConfig(BaseModel):
         assert exists(json_path) and isfile(json_path), f'"{json_path}" does not exist or is not a file'
         with open(json_path, "r", encoding="utf-8") as f:
             raw = json.load(f)
-        return cls(**{k: raw[k] for k in _MODEL_KEYS}, comm=raw.get("comm"), comm_range=raw.get("comm_range"))
+        return cls(**{k: raw[k] for k in _MODEL_KEYS}, comm=raw.get("comm"), comm_range=raw.get("comm_range"),
+                   normalize=raw.get("normalize"))
 
     def build_networks(self) -> ModelsWrapper:
         assert self.ft_extr_str in CNN_BY_NAME, (
@@ -163,6 +170,7 @@ class EvalConfig(BaseModel):
     greedy: bool = False  # --greedy: deterministic acting, the argmax of the policy (a run-time choice, not in marl.json)
     temperature: float = 1.0  # --temperature: the policy is softmax(z / T)
     tta: Optional[str] = None  # --tta: test-time augmentation, the mean over the views of augment.parse(SPEC).views()
+    normalize: Optional[str] = None  # --normalize: replaces the transform marl.json names ("none": off; None: keep it)
     # --report: the episode report (report.py) beside the confusion matrix - one table row per step, report.json and
     # accuracy_per_step.png; exit_at = "t1,t2,...", the confidences of the early-exit statistics.  Off: today's path
     report: bool = False
@@ -178,6 +186,7 @@ class InferConfig(BaseModel):
     output_dir: str
     class_to_idx: str
     saliency: bool = False  # also write saliency.png (|d logit / d pixel|) next to the step frames
+    normalize: Optional[str] = None  # --normalize: replaces the transform marl.json names ("none": off; None: keep it)
     comm: Optional[str] = None  # --comm: replaces the graph marl.json names (None: keep it)
     comm_range: Optional[str] = None  # --comm-range: replaces the range marl.json names (None: keep it)
     greedy: bool = False  # --greedy: deterministic acting, the argmax of the policy (a run-time choice, not in marl.json)

@@ -74,12 +74,16 @@ class DevicePrefetcher:
 
     ``mix`` (a ``mix.Policy``, with ``nb_class``): the batch is mixed with a permutation of itself (CutMix / Mixup,
     ``mix.apply``: the views are the augmented ones, still one launch) and the loader yields ``(x, y_primary, Q)`` with
-    the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes."""
+    the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes.
+
+    ``normalize`` (a ``transforms.Spec`` or its spelling): the batch - the uploaded one, or what the augment / mix
+    policy made of it - is standardised per image by ``transforms.apply`` and yielded as fp32.  None: nothing changes."""
 
     def __init__(self, loader, device: th.device, augment=None, generator=None, mix=None,
-                 nb_class: Optional[int] = None) -> None:
+                 nb_class: Optional[int] = None, normalize=None) -> None:
         self.loader = loader
         self.device = th.device(device)
+        self.normalize = _normalize_spec(normalize)
         self.mix, self.nb_class = mix, _mix_classes(mix, nb_class)
         self.augment = _no_mixed_warp(augment, mix)
         self.generator = _device_generator(augment if mix is None else mix, generator, self.device)
@@ -111,11 +115,12 @@ class DevicePrefetcher:
             xd.record_stream(cur)
             yd.record_stream(cur)
             if self.mix is not None:
-                yield _mixed(self.augment, self.mix, self.generator, xd, None, yd, self.nb_class)
+                xm, yp, q = _mixed(self.augment, self.mix, self.generator, xd, None, yd, self.nb_class)
+                yield _normalized(self.normalize, xm, None), yp, q
                 continue
             if self.augment is not None:
                 xd = _augmented(self.augment, self.generator, xd, None)
-            yield xd, yd
+            yield _normalized(self.normalize, xd, None), yd
 
     def __len__(self) -> int:
         return len(self.loader)
@@ -151,6 +156,23 @@ def _augmented(policy, generator, x: th.Tensor, rows):
         return _warp.apply(x, rows, mats, ops, pad_mode=policy.pad_mode, fill=policy.fill)
     ops = policy.draw(batch, generator, size=(x.shape[-2], x.shape[-1]))
     return _augment.apply(x, rows, ops, pad_mode=policy.pad_mode, fill=policy.fill)
+
+
+def _normalize_spec(normalize):
+    """the transform of a loader: a ``transforms.Spec`` (or its spelling; "dataset" must be resolved before), or None"""
+    from . import transforms as _transforms
+
+    return _transforms.resolve(normalize)
+
+
+def _normalized(spec, x: th.Tensor, rows):
+    """``transforms.apply`` of ``x[rows]`` (``rows`` None: ``x`` itself) - the statistics are those of the batch as it is
+    handed to the episode; ``spec`` None: ``x`` as it is (``rows`` is then None too)"""
+    if spec is None:
+        return x
+    from . import transforms as _transforms
+
+    return _transforms.apply(x, rows, spec)
 
 
 def _mix_classes(policy, nb_class) -> Optional[int]:
@@ -242,11 +264,16 @@ class ResidentLoader:
 
     ``mix`` (a ``mix.Policy``, with ``nb_class``): every batch is mixed with a permutation of itself (CutMix / Mixup,
     ``mix.apply`` from the resident set: the views are the augmented ones, still one launch) and the loader yields
-    ``(x, y_primary, Q)`` with the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes."""
+    ``(x, y_primary, Q)`` with the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes.
+
+    ``normalize`` (a ``transforms.Spec`` or its spelling): every batch is standardised per image and yielded as fp32.
+    Without an augment / mix policy ``transforms.apply`` reads the resident set through ``rows`` - the ``index_select``
+    disappears; with one, the batch the policy produced is normalised.  None: exactly the code above."""
 
     def __init__(self, dataset, indices, batch_sampler, device, workers: int = 0,
                  rank: int = 0, world: int = 1, group=None, chunk: int = 16, augment=None, generator=None,
-                 mix=None, nb_class: Optional[int] = None) -> None:
+                 mix=None, nb_class: Optional[int] = None, normalize=None) -> None:
+        self.normalize = _normalize_spec(normalize)
         self.dataset, self.batch_sampler = dataset, batch_sampler
         self.indices = list(indices)
         self.device = th.device(device)
@@ -313,12 +340,17 @@ class ResidentLoader:
         for batch in self.batch_sampler:
             rows = self._row_of[th.tensor(batch, dtype=th.long).to(self.device, non_blocking=True)]
             if self.mix is not None:
-                yield _mixed(self.augment, self.mix, self.generator, self._x, rows, self._y.index_select(0, rows),
-                             self.nb_class)
+                xm, yp, q = _mixed(self.augment, self.mix, self.generator, self._x, rows,
+                                   self._y.index_select(0, rows), self.nb_class)
+                yield _normalized(self.normalize, xm, None), yp, q
             elif self.augment is None:
-                yield self._x.index_select(0, rows), self._y.index_select(0, rows)
+                if self.normalize is not None:  # (straight from the resident set: no index_select)
+                    yield _normalized(self.normalize, self._x, rows), self._y.index_select(0, rows)
+                else:
+                    yield self._x.index_select(0, rows), self._y.index_select(0, rows)
             else:
-                yield _augmented(self.augment, self.generator, self._x, rows), self._y.index_select(0, rows)
+                yield (_normalized(self.normalize, _augmented(self.augment, self.generator, self._x, rows), None),
+                       self._y.index_select(0, rows))
 
     def __len__(self) -> int:
         return len(self.batch_sampler)

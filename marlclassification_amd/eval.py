@@ -32,6 +32,8 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
         marl_config.comm = eval_config.comm
     if eval_config.comm_range is not None:
         marl_config.comm_range = eval_config.comm_range
+    if eval_config.normalize is not None:  # (--normalize SPEC|none: replaces what marl.json names)
+        marl_config.normalize = None if eval_config.normalize == "none" else eval_config.normalize
     nn_models, marl_m, env = marl_config.build_marl(main_config.nb_agent)
     nn_models.load_state_dict(th.load(eval_config.state_dict_path, map_location="cpu"))
     nn_models.eval()
@@ -40,6 +42,11 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
         nn_models.set_exploration(temperature=eval_config.temperature, greedy=eval_config.greedy)
     loader = DevicePrefetcher(DataLoader(dataset, batch_size=eval_config.batch_size, shuffle=True,
                                          num_workers=0, drop_last=False, pin_memory=True), device)
+    normalize = None
+    if marl_config.normalize is not None:
+        from . import transforms as _transforms
+
+        normalize = _transforms.resolve(marl_config.normalize)
     sampler = EpisodeSampler(marl_m, env, main_config.step)
     meter = ConfusionMeter(nn_models.nb_class)
     views = view_mats = None
@@ -52,13 +59,17 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
         if policy.has_warp:  # (zoom:Z1/Z2/...: every code under every zoom, through the resampling gather)
             views, view_mats = (t.to(device) for t in policy.warp_views())
 
+    def normalized(x):
+        """the batch as the episode takes it: under marl.json's transform, each view with its own statistics"""
+        return x if normalize is None else _transforms.apply(x, None, normalize)
+
     def view_of(x, v):
         ops = views[v: v + 1].expand(x.shape[0], -1).contiguous()
         if view_mats is None:
-            return _augment.apply(x, None, ops)
+            return normalized(_augment.apply(x, None, ops))
         from . import warp as _warp
 
-        return _warp.apply(x, None, view_mats[v: v + 1].expand(x.shape[0], -1).contiguous(), ops)
+        return normalized(_warp.apply(x, None, view_mats[v: v + 1].expand(x.shape[0], -1).contiguous(), ops))
 
     rep = None
     if eval_config.report:  # (--report: every step of every episode into an episode report, report.py)
@@ -71,7 +82,7 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
         with th.no_grad():
             for x, y in loader:
                 if n_views == 1 and view_mats is None:
-                    preds = sampler.run_episode(x).step_preds
+                    preds = sampler.run_episode(normalized(x)).step_preds
                 else:
                     preds = th.cat([sampler.run_episode(view_of(x, v)).step_preds for v in range(n_views)], dim=1)
                 rep.add(preds, y.to(device))
@@ -79,7 +90,7 @@ def eval_main(main_config: MainConfig, eval_config: EvalConfig) -> ConfusionMete
     with th.no_grad():
         for x, y in (() if rep is not None else loader):
             if views is None or (views.shape[0] == 1 and view_mats is None):
-                out = sampler.run_episode_get_last_step(x)
+                out = sampler.run_episode_get_last_step(normalized(x))
                 meter.add(out.prediction.mean(dim=0), y)  # mean over agents; stays on the device
                 continue
             pred = None

@@ -39,6 +39,13 @@ def infer_main(main_config: MainConfig, infer_config: InferConfig) -> int:
         marl_config.comm = infer_config.comm
     if infer_config.comm_range is not None:
         marl_config.comm_range = infer_config.comm_range
+    if infer_config.normalize is not None:  # (--normalize SPEC|none: replaces what marl.json names)
+        marl_config.normalize = None if infer_config.normalize == "none" else infer_config.normalize
+    normalize = None
+    if marl_config.normalize is not None:
+        from . import transforms as _transforms
+
+        normalize = _transforms.resolve(marl_config.normalize)
     nn_models, marl_m, env = marl_config.build_marl(main_config.nb_agent)
     nn_models.load_state_dict(th.load(infer_config.state_dict_path, map_location="cpu"))
     nn_models.eval()
@@ -54,13 +61,17 @@ def infer_main(main_config: MainConfig, infer_config: InferConfig) -> int:
         os.makedirs(out_dir, exist_ok=True)
         with open(join(out_dir, "info.txt"), "w", encoding="utf-8") as info:
             info.write(f"{img_path}\n{infer_config.json_path}\n{infer_config.state_dict_path}\n")
-        visualize_steps(sampler, x.to(device), x, marl_config.window_size, out_dir, class_to_idx)
+        # (the episode sees the normalised image; the frames paint the original uint8 one, the reference's x_ori)
+        x_in = x.to(device)
+        if normalize is not None:
+            x_in = _transforms.apply(x_in.unsqueeze(0).contiguous(), None, normalize)[0]
+        visualize_steps(sampler, x_in, x, marl_config.window_size, out_dir, class_to_idx)
         if infer_config.saliency:
             import matplotlib
 
             matplotlib.use("Agg")
             import matplotlib.pyplot as plt
 
-            sal = saliency_maps(sampler, x.unsqueeze(0))[0].cpu()
+            sal = saliency_maps(sampler, x.unsqueeze(0), normalize=normalize)[0].cpu()
             plt.imsave(join(out_dir, "saliency.png"), (sal / sal.max().clamp_min(1e-30)).numpy(), cmap="inferno")
     return len(paths)

@@ -54,6 +54,18 @@ def _dataset(model_config: ModelConfig, train_config: TrainConfig):
     return dataset
 
 
+def _split_spec(dataset, indices, device, chunk: int = 256):
+    """``--normalize dataset``: the mean / std of the images ``indices`` of ``dataset`` as a ``user-normal`` Spec
+    (``transforms.dataset_spec`` over uploaded chunks: the statistics are taken on the device, summed in integers)"""
+    from . import transforms as _transforms
+
+    def chunks():
+        for at in range(0, len(indices), chunk):
+            yield th.stack([dataset[i][0] for i in indices[at: at + chunk]]).to(device)
+
+    return _transforms.dataset_spec_of(chunks())
+
+
 def _split_labels(dataset, indices) -> th.Tensor:
     """The labels of ``indices`` without decoding an image (both dataset classes keep them in memory)."""
     if isinstance(dataset, SyntheticImages):
@@ -178,6 +190,18 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
 
     nn_models, marl_m, env = model_config.build_marl(main_config.nb_agent)
     dataset = _dataset(model_config, train_config)
+    g = th.Generator().manual_seed(base_seed)  # same split on every rank
+    idx = th.randperm(len(dataset), generator=g)
+    cut = int(0.85 * idx.shape[0])
+    # --normalize: part of the model (marl.json).  `dataset` is resolved here, on the whole training split before the
+    # per-rank sharding - every rank computes the same integers - and stored as the user-normal:... it stands for
+    normalize = None
+    if model_config.normalize is not None:
+        from . import transforms as _transforms
+
+        if model_config.normalize == "dataset":
+            model_config.normalize = _split_spec(dataset, idx[:cut].tolist(), device).spelling
+        normalize = _transforms.resolve(model_config.normalize)
     if rank == 0:
         model_config.save_marl_config(join(output_dir, "marl.json"))
         with open(join(output_dir, "class_to_idx.json"), "w", encoding="utf-8") as f:
@@ -198,9 +222,6 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         for p in nn_models.parameters():
             dist.broadcast(p.data, src=0)
 
-    g = th.Generator().manual_seed(base_seed)  # same split on every rank
-    idx = th.randperm(len(dataset), generator=g)
-    cut = int(0.85 * idx.shape[0])
     # --class-weights: `balanced` counts the labels of the WHOLE training split (before the per-rank sharding: every
     # rank gets the same weights); a file or a list is checked against the class count
     from . import class_loss as _class_loss
@@ -237,6 +258,8 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         aug = {"augment": policy, "generator": aug_gen} if policy is not None and k == 0 else {}
         if mix_policy is not None and k == 0:
             aug.update(mix=mix_policy, nb_class=model_config.nb_class, generator=aug_gen)
+        if normalize is not None:  # (both splits: the evaluation sees what the model was trained on)
+            aug["normalize"] = normalize
         bs = ShardedBatchSampler(part, train_config.batch_size, rank, world, shuffle=True,
                                  seed=base_seed + 1 + k)
         samplers.append(bs)
@@ -302,6 +325,7 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
             "entropy_coef", "ppo_epochs", "ppo_clip", "gae_lambda", "max_grad_norm")) +
               (f", learn_comm on {model_config.comm or 'full'}" if learned is not None else "") +
               (f", temperature {t_ends}, explore_eps {e_ends}" if t_ends or e_ends else "") +
+              (f", normalize {model_config.normalize}" if normalize is not None else "") +
               (f", augment {policy.spec}" if policy is not None else "") +
               (f", mix {mix_policy.spec}" if mix_policy is not None else "") +
               (f", class weights {cw_spec if isinstance(cw_spec, str) else 'given'}" if cw_spec is not None else "") +
@@ -357,8 +381,10 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
 
         pick = int(idx[cut + int(th.randint(0, len(idx) - cut, (1,)).item())])
         x_u8 = dataset[pick][0]
-        visualize_steps(sampler, x_u8.to(device), x_u8, model_config.window_size, output_dir,
-                        dataset.class_to_idx)
+        x_in = x_u8.to(device)
+        if normalize is not None:  # (the episode sees the normalised image; the frames paint the original)
+            x_in = _transforms.apply(x_in.unsqueeze(0).contiguous(), None, normalize)[0]
+        visualize_steps(sampler, x_in, x_u8, model_config.window_size, output_dir, dataset.class_to_idx)
     if distributed:
         dist.destroy_process_group()
     return trainer

@@ -13,15 +13,22 @@ from .core import EpisodeSampler
 
 
 def saliency_maps(episode_sampler: EpisodeSampler, img: th.Tensor,
-                  class_idx: Optional[Union[int, th.Tensor]] = None) -> th.Tensor:
+                  class_idx: Optional[Union[int, th.Tensor]] = None, normalize=None) -> th.Tensor:
     """Per-pixel attribution of ONE episode: ``|d logit / d pixel|`` maxed over the channels, [Nb, H, W].
     ``img`` [Nb, C, H, W] (fp32 in [0, 1], or uint8 - converted as ToTensor does) goes through the episode
     requiring grad; the logit is the chosen class's (``class_idx``: an int or int64 [Nb]; default: the
     predicted class) in the final agent-mean prediction.  Pixels no agent looked at are exactly 0.  The
-    model's parameter gradients are left untouched."""
+    model's parameter gradients are left untouched.  ``normalize`` (a ``transforms.Spec`` or its spelling): ``img`` is
+    the original image (uint8 or fp32) and the episode runs on ``transforms.apply`` of it - the normalised batch is the
+    leaf, so the map is the attribution per pixel of what the model sees."""
     device = episode_sampler.agents.device
     x = img.detach().to(device)
-    x = (x.float() / 255.0 if x.dtype == th.uint8 else x.float().clone()).requires_grad_()
+    if normalize is not None:
+        from . import transforms as _transforms
+
+        x = _transforms.apply(x.contiguous(), None, normalize).requires_grad_()
+    else:
+        x = (x.float() / 255.0 if x.dtype == th.uint8 else x.float().clone()).requires_grad_()
     with th.enable_grad():
         out = episode_sampler.run_episode(x)
         logits = out.step_preds[-1].mean(dim=0)  # [Nb, nC]
