@@ -565,7 +565,11 @@ int marl_debug_buffer(const marl_config* cfg, int train, const char* name, int t
  * the phase-pipelined step, "wgrad3" = conv weight gradients (cin >= 16) on the bf16 pipe, "panel_sample" = the episode
  * forward samples step t's actions inside the chained panel launch, as the epilogue of its policy workgroups (no
  * sample_kernel launch; at most four actions; MARL_PANEL_SAMPLE=0 in the environment, read once, restores the
- * separate launch - same results bit for bit).  *value = 0 / 1 (a plan number for "lstm_plan").
+ * separate launch - same results bit for bit), "panel_static" = the chained panel launches of the episode, forward and
+ * backward, take the static-shape kernels (the README widths 256 -> 128 -> 64 | mean | 64 -> 128 -> 96, policy 256 ->
+ * 384, four actions, n_d a multiple of 4 (the README's 16); no communication graph, no exploration controls; MARL_PANEL_STATIC=0 in the
+ * environment, read once, keeps the run-time-shape kernels - same results bit for bit).
+ * *value = 0 / 1 (a plan number for "lstm_plan").
  * "g3_tn_pipe" and "wgrad3" report what runs, not the knob: the first is 0 where the image weight gradients are off,
  * the second is 0 unless some conv layer of the model takes cnn_wgrad3_kernel.
  * The CNN launchers' plans, each from the launcher's own routine (host arithmetic only, no GPU needed):

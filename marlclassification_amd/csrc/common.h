@@ -708,6 +708,9 @@ struct PanelFwdBatch {
 int panel_chain_supported(int na, int n_msg, int threads);
 int panel_supported(int k0, int n0, int n1);
 int panel_sample_supported(int n_actions);  // the sampling epilogue (PanelFwdBatch::epi_prob) covers this action count
+// the plain chain launches of a model with these widths take the static-shape kernels in both directions (the
+// launchers match every launch's descriptors themselves; MARL_PANEL_STATIC=0: never)
+int panel_static_model(int n_b, int n_a, int nm2, int n_m, int n_mo, int nla, int n_actions, int n_d);
 // explore (with epi_prob): the EXPLORE instantiations of the sampling epilogue (b.sample.ex_* filled)
 int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore = false);
 

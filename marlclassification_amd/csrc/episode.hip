@@ -659,6 +659,7 @@ struct Plan {
     bool panels_bwd;    // backward loop: the same, for the narrower range of its kernels (every message width <= 384)
     bool chain;         // the chained panel launches, forward and backward (all agents of an image in one workgroup)
     bool panel_sample;  // ... whose policy workgroups sample as their epilogue
+    bool panel_static;  // ... and which take the static-shape panel kernels, forward and backward (README widths, plain)
     bool g3_lstm;       // both cells and the heads' first layers from k16 images (gemm3.hip)
     bool g3_tn, g3_tn_pipe;  // the four large weight gradients from images; ... phase-pipelined
     bool g3_tn_cell;         // ... and both cells take the one-launch-per-cell form (ELayout::tn_cell)
@@ -745,6 +746,9 @@ static Plan make_plan(const Dims& d, const WLayout& w, const ELayout& e, const I
     p.chain = p.panels_bwd && panel_chain_supported(d.na, d.n_m, 256) && tune_get("panel_chain", 1) != 0 &&
               (!opt.comm || d.n_b <= 384);
     p.panel_sample = p.chain && env_sample && panel_sample_supported(d.nA);
+    // the static-shape panel kernels: plain chain launches only (launch_panel_fwd / launch_panel_bwd match each launch)
+    p.panel_static = p.chain && !opt.comm && !opt.explore.on &&
+                     panel_static_model(d.n_b, d.n_a, d.nm2, d.n_m, d.n_mo, d.nla, d.nA, d.n_d);
     // sample(t) and decoder(t+1) are independent: without the chain one launch runs both - but not under exploration
     // controls (the ride-along workgroups of the plain decoder launch have no EXPLORE form)
     p.sample = p.chain ? (p.panel_sample ? SAMPLE_EPILOGUE : SAMPLE_OWN)
@@ -3070,6 +3074,7 @@ int marl_plan_query(const marl_config* cfg, int train, const char* key, int* val
     else if (!strcmp(key, "comm_range")) *value = plan.comm_range;
     else if (!strcmp(key, "panel_chain")) *value = plan.chain;
     else if (!strcmp(key, "panel_sample")) *value = plan.panel_sample;
+    else if (!strcmp(key, "panel_static")) *value = plan.panel_static;
     else if (!strcmp(key, "explore")) *value = plan.explore;
     else if (!strcmp(key, "class_loss")) *value = plan.class_loss;
     else if (!strcmp(key, "soft_targets")) *value = plan.soft_targets;

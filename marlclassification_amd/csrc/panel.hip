@@ -26,6 +26,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
+// a product rounded on its own, never contracted into an add that consumes it.  The backward row pass accumulates
+// (s1, s2) and (dbeta, dgamma) as pairs whose members are products (dy, dy * g) and products of those; which of them
+// the compiler contracts into the sums depends on how it pairs the lanes of each instantiation (the run-time forms pair
+// the two sums and contract none) - written out, every instantiation rounds as those do
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 __device__ __forceinline__ float silu_p(float y) { return silu_fast(y); }
 __device__ __forceinline__ float silu_grad_p(float y) { return silu_grad_fast(y); }
 
@@ -117,6 +125,162 @@ __host__ __device__ inline int panel_ksplit(int K, int nt, int nwaves) {
     return ks < 1 ? 1 : ks;
 }
 
+constexpr int panel_kper_c(int K16, int ks) { return (((K16 + ks - 1) / ks) + 15) & ~15; }
+constexpr int panel_ksplit_c(int K, int nt, int nwaves) {
+    const int K16 = (K + 15) & ~15, want = (K16 + 63) / 64;
+    int ks = nwaves / nt;
+    ks = ks < want ? ks : want;
+    return ks < 1 ? 1 : ks;
+}
+constexpr int panel_stride_c(int k) { return ((k + 15) & ~15) + 4; }
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+
+// ---------------------------------------------------------------------------
+// Shape descriptors.  Both kernels are written once over a shape class SH: PanelDyn reads every width, the layer
+// count, the wave count and the LDS offsets from the launch's descriptors (the form every shape can take);
+// PanelNet / PanelBwdNet carry them as constants (the forms of the README dimensions, see launch_panel_fwd /
+// launch_panel_bwd): the layer loop is unrolled, and slice bounds, strides, divisors and column guards fold.
+// The arithmetic is the same source either way - the results are the run-time form's, bit for bit.
+// ---------------------------------------------------------------------------
+struct PanelDyn {
+    static constexpr bool kStatic = false, kByBatch = false;
+    static constexpr int kLayers = kPanelMaxLayers, kSoft = 0, kWaves = 0, kK0 = 0, kAggAt = 0, kKLast = 0;
+    static constexpr int off_e = 0, off_prm = 0, off_colp = 0, off_part = 0, off_rowmap = 0;
+    static constexpr int n(int) { return 0; }
+    static constexpr int k(int) { return 0; }
+};
+// forward: WAVES of the launch's plan, input width K0, widths N...; AGG_AT: the in-panel message mean in front of
+// that layer (0: none; implies by_batch rows).  SOFT > 0: the launch may stop after SOFT layers (P.nlayers == SOFT,
+// then without the aggregation site): the last step's encoder-only form inside the same instantiation.
+template <int WAVES, int K0, int AGG_AT, int SOFT, int... N>
+struct PanelNet {
+    static constexpr bool kStatic = true, kByBatch = AGG_AT > 0;
+    static constexpr int kLayers = (int)sizeof...(N), kSoft = SOFT, kWaves = WAVES, kK0 = K0, kAggAt = AGG_AT;
+    static constexpr int n(int l) {
+        constexpr int w[] = {N...};
+        return w[l];
+    }
+    static constexpr int k(int l) { return l == 0 ? K0 : n(l - 1); }
+    // X: the input and the outputs of the odd layers; Y: the outputs of the even layers (panel_fwd_plan)
+    static constexpr int s0(int layers) {
+        int v = kPanelRows * panel_stride_c(K0);
+        for (int l = 1; l < layers; l += 2) v = cmax(v, kPanelRows * panel_stride_c(n(l)));
+        return v;
+    }
+    static constexpr int s1(int layers) {
+        int v = 0;
+        for (int l = 0; l < layers; l += 2) v = cmax(v, kPanelRows * panel_stride_c(n(l)));
+        return v;
+    }
+    static constexpr bool ok() {
+        for (int l = 0; l < kLayers; ++l) {
+            const int nt = (n(l) + 31) >> 5, K16 = (k(l) + 15) & ~15, ks = panel_ksplit_c(k(l), nt, WAVES);
+            if (nt * ks > WAVES || (ks - 1) * panel_kper_c(K16, ks) >= K16) return false;  // (no empty slice)
+            if ((n(l) & 15) || (k(l) & 15) || n(l) > 64 * kPanelMaxCols) return false;
+        }
+        return WAVES >= 4 && WAVES <= kPanelMaxWaves && (SOFT == 0 || (s0(SOFT) == s0(kLayers) && s1(SOFT) == s1(kLayers)));
+    }
+};
+// backward: layers listed from the output side, N... their widths, KLAST the input width of the last listed one
+template <int WAVES, int AGG_AT, int KLAST, int... N>
+struct PanelBwdNet {
+    static constexpr bool kStatic = true, kByBatch = true;
+    static constexpr int kLayers = (int)sizeof...(N), kSoft = 0, kWaves = WAVES, kAggAt = AGG_AT, kKLast = KLAST;
+    static constexpr int n(int l) {
+        constexpr int w[] = {N...};
+        return w[l];
+    }
+    static constexpr int k(int l) { return l + 1 < kLayers ? n(l + 1) : KLAST; }  // k_in
+    static constexpr int nmax() {
+        int v = 0;
+        for (int l = 0; l < kLayers; ++l) v = cmax(v, n(l));
+        return v;
+    }
+    // the LDS layout of panel_bwd_plan with the LDS tail
+    static constexpr int pmax() {
+        int v = 0;
+        for (int l = 0; l < kLayers; ++l) v = cmax(v, cmax(panel_stride_c(n(l)), panel_stride_c(k(l))));
+        return v;
+    }
+    static constexpr int prm() {
+        int v = 0;
+        for (int l = 0; l < kLayers; ++l) v += 2 * n(l);
+        return v;
+    }
+    static constexpr int off_e = kPanelRows * pmax(), off_prm = 2 * kPanelRows * pmax(), off_colp = off_prm + prm() + 16;
+    static constexpr int off_part = off_colp + WAVES * 2 * nmax(), off_rowmap = off_part + (WAVES - 1) * 512;
+    static constexpr bool ok() {
+        for (int l = 0; l < kLayers; ++l) {
+            const int nt = (k(l) + 31) >> 5, n16 = (n(l) + 15) & ~15, ks = panel_ksplit_c(n(l), nt, WAVES);
+            if (nt > WAVES || (ks - 1) * panel_kper_c(n16, ks) >= n16) return false;
+            if ((n(l) & 15) || (k(l) & 15)) return false;
+        }
+        return WAVES >= 8 && WAVES <= kPanelMaxWaves && nmax() <= 128 && (KLAST & 3) == 0;
+    }
+};
+
+// panel_gemm for a slice plan known at compile time: slice s of KS covers [s * KPER, min((s + 1) * KPER, K16)).  The
+// chunk loop is unrolled; a 16-deep group is multiplied under no test where every slice has it, under a wave-uniform
+// one where only the last slice is short, and groups past KPER are neither loaded nor multiplied.  Per accumulator the
+// MFMAs run in panel_gemm's order.
+template <int K16, int KS, int KPER>
+__device__ __forceinline__ void panel_gemm_st(f32x4 (&acc)[2], const float* in, int stride,
+                                              const float* __restrict__ wfrag, int j, int s, int lane) {
+    constexpr int groups = K16 >> 4, last0 = (KS - 1) * KPER;
+    static_assert(last0 < K16 && (KPER & 15) == 0, "slice plan");
+    const int quad = lane >> 4, l16 = lane & 15;
+    const int kbeg = __builtin_amdgcn_readfirstlane(s * KPER);
+    const float* arow = in + l16 * stride + 4 * quad + kbeg;
+    const int g0 = __builtin_amdgcn_readfirstlane(j * groups + (kbeg >> 4));
+    const float* wb = wfrag + (size_t)g0 * 512;
+    const unsigned lo = 4u * (unsigned)lane;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[0][r] = acc[1][r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < (KPER + 63) / 64; ++c) {
+        if (last0 + 64 * c < K16 || kbeg + 64 * c < K16) {  // (first test: constant)
+            float4 b0[4], b1[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (64 * c + 16 * i < KPER) {
+                    b0[i] = *reinterpret_cast<const float4*>(wb + 2048 * c + 512 * i + lo);
+                    b1[i] = *reinterpret_cast<const float4*>(wb + 2048 * c + 512 * i + 256 + lo);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (64 * c + 16 * i < KPER && (last0 + 64 * c + 16 * i < K16 || kbeg + 64 * c + 16 * i < K16)) {
+                    const float4 a = *reinterpret_cast<const float4*>(arow + 64 * c + 16 * i);
+                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0[i].x, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b1[i].x, acc[1], 0, 0, 0);
+                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b0[i].y, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1[i].y, acc[1], 0, 0, 0);
+                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b0[i].z, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b1[i].z, acc[1], 0, 0, 0);
+                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b0[i].w, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b1[i].w, acc[1], 0, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+// the product of layer l of shape SH (forward: K = k(l), tiles over n(l); backward: K = n(l), tiles over k(l)) - one
+// instantiation of panel_gemm_st per layer, picked by the unrolled layer index
+template <class SH, bool BWD, int L = 0>
+__device__ __forceinline__ void panel_gemm_layer(int l, f32x4 (&acc)[2], const float* in, int stride,
+                                                 const float* __restrict__ wfrag, int j, int s, int lane) {
+    if constexpr (SH::kStatic && L < SH::kLayers) {
+        if (l == L) {
+            constexpr int K = BWD ? SH::n(L) : SH::k(L), nout = BWD ? SH::k(L) : SH::n(L);
+            constexpr int K16 = (K + 15) & ~15, ks = panel_ksplit_c(K, (nout + 31) >> 5, SH::kWaves);
+            panel_gemm_st<K16, ks, panel_kper_c(K16, ks)>(acc, in, stride, wfrag, j, s, lane);
+        } else {
+            panel_gemm_layer<SH, BWD, L + 1>(l, acc, in, stride, wfrag, j, s, lane);
+        }
+    }
+}
+
 // LayerNorm + SiLU row pass of the forward panel kernel: wave w owns rows w, w + nwaves, ...; a row lives
 // in registers (NC columns per lane: widths up to 64 * NC), two-pass statistics with VALU wave reductions,
 // result written over the LDS panel (next layer's input) and to global.  NC = 2 for the message chain's
@@ -150,14 +314,19 @@ __device__ __forceinline__ void panel_ln_rows(const PanelLayer& Lr, float* outp,
                 if (Lr.z && row >= 0 && c < n) Lr.z[(size_t)row * Lr.ldz + c] = v[u];
             }
             const float mean = wave_sum(sm) * inv_n;
-            float q = 0.f;
 #pragma unroll
             for (int u = 0; u < NC; ++u) {
                 const int c = lane + 64 * u;
-                const float d = c < n ? v[u] - mean : 0.f;
-                v[u] = d;
-                q += d * d;
+                v[u] = c < n ? v[u] - mean : 0.f;
             }
+            // sum of squares, slot 0 first.  The first two terms are a sum of two products, which may be contracted
+            // either way (x * x cannot be -0, so the leading 0 + is gone before that is decided) - and was, differently
+            // from one instantiation to the next.  Written out the way every instantiation did before there were
+            // static ones: the second square rounded, the first fused onto it, the others fused in order.
+            static_assert(NC >= 2, "column slots");
+            float q = fmaf(v[0], v[0], mul_rn(v[1], v[1]));
+#pragma unroll
+            for (int u = 2; u < NC; ++u) q = fmaf(v[u], v[u], q);
             const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_n + 1e-5f);
             float* arow = Lr.a + (size_t)(row < 0 ? 0 : row) * Lr.lda;
 #pragma unroll
@@ -194,7 +363,10 @@ __device__ __forceinline__ void panel_ln_rows(const PanelLayer& Lr, float* outp,
 // instantiation, which has one vector register fewer (a scalar spill lane), needs that to stay out of scratch; the plain
 // one fits without it and is 1.5 us per launch faster without (the moves wait for loads the chain would not yet need)
 // EXPLORE: sample_finish under exploration controls (sample.h)
-template <int MAXA, bool UNI, bool EXPLORE = false>
+// NLA > 0 (the static forms): the launcher has matched the row's width NLA, exactly MAXA actions and the embedding's
+// four-columns-a-lane form (sample_pe_fast) - the chain is told so, and the action and column guards of sample.h fold;
+// the arithmetic is the same functions'
+template <int MAXA, bool UNI, bool EXPLORE = false, int NLA = 0>
 __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const float* outp, int ys, const int* rowmap,
                                                   int wave, int nwaves, int lane) {
     for (int lr = __builtin_amdgcn_readfirstlane(wave); lr < kPanelRows; lr += nwaves) {  // wave-uniform: scalar
@@ -207,6 +379,10 @@ __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const fl
         int zero = 0;  // (likewise the arguments: read where the chain uses them, not all ahead of the loop)
         asm volatile("" : "+s"(zero));
         const SampleArgs& A = (&A0)[zero];
+        if (NLA > 0) {  // (matched by the launcher: the action and column guards of sample.h fold)
+            __builtin_assume(A.nA == MAXA);
+            __builtin_assume(A.nla == NLA);
+        }
         float p[MAXA];
         SamplePre<MAXA> S;
         sample_prefetch_row<MAXA>(A, row, ln, S);
@@ -226,7 +402,7 @@ __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const fl
             S.pi1 = __builtin_amdgcn_readfirstlane(S.pi1);
             S.forced = __builtin_amdgcn_readfirstlane(S.forced);
         }
-        sample_prefetch_pe<MAXA>(A, ln, S);  // in flight under the reductions, the softmax and the draw
+        sample_prefetch_pe<MAXA, (NLA > 0)>(A, ln, S);  // in flight under the reductions, the softmax and the draw
         sample_finish<MAXA, EXPLORE>(A, row, p, ln, S);
     }
 }
@@ -241,31 +417,28 @@ __device__ __forceinline__ void panel_sample_rows(const SampleArgs& A0, const fl
 // carry none of it.  GATE (with MIX): the matrix is gated by the agents' positions (P.gate, marl_comm_range): one matrix
 // per image of the workgroup, built here from the base matrix P.mix; the constant-MIX instantiations carry none of it
 // EXPLORE (with EPI): the epilogue samples under exploration controls (marl_policy_explore); the others carry none of it
-template <int SAMPLE, bool MIX = false, bool EPI = false, bool GATE = false, bool EXPLORE = false>
-__global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (!EPI && SAMPLE > 0 && (int)blockIdx.x >= B.panel_blocks) {
-        // ride-along sampling workgroup: one wave per row of the policy activations
-        const int r = ((int)blockIdx.x - B.panel_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
-        if (r >= B.sample.R) return;
-        constexpr int MAXA = SAMPLE > 0 ? SAMPLE : 4;
-        float p[MAXA];
-        SamplePre<MAXA> S;
-        sample_prefetch<MAXA, false>(B.sample, r, threadIdx.x & 63, S);
-        sample_row_logits<MAXA>(B.sample, r, p, threadIdx.x & 63);
-        sample_finish<MAXA>(B.sample, r, p, threadIdx.x & 63, S);
-        return;
-    }
-    const PanelFwdProb& P = B.p[blockIdx.y];
+// One problem of a forward launch, the body of both kernels below.  SH: the problem's shape (PanelDyn: from P); LY: the
+// LDS float offsets of a static launch (PanelFwdLay; the run-time form reads the launcher's from B where it uses them)
+struct PanelDynLay {
+    static constexpr int panel1 = 0, red = 0, part = 0, prm = 0;
+};
+template <class SH, class LY, int SAMPLE, bool MIX, bool EPI, bool GATE, bool EXPLORE>
+__device__ __forceinline__ void panel_fwd_body(const PanelFwdBatch& B, const PanelFwdProb& P, float* lds) {
+    constexpr bool ST = SH::kStatic;
     const int m0 = blockIdx.x * kPanelRows;
-    const int bpb = P.by_batch;  // > 0: this workgroup owns all agents of bpb batch elements
-    if (bpb ? (int)blockIdx.x * bpb >= P.g_nb : m0 >= P.m) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    // > 0: this workgroup owns all agents of bpb batch elements (static forms: by-batch rows with AGG_AT, else tiled)
+    const int bpb = ST && !SH::kByBatch ? 0 : P.by_batch;
+    if ((ST ? SH::kByBatch : bpb != 0) ? (int)blockIdx.x * bpb >= P.g_nb : m0 >= P.m) return;
+// threads of the workgroup and layers of the launch (the latter a constant but for the SOFT forms, which also run their
+// first SOFT layers alone); the run-time form reads both where it uses them
+#define PANEL_NT (ST ? 64u * SH::kWaves : blockDim.x)
+#define PANEL_NL (ST && SH::kSoft == 0 ? SH::kLayers : P.nlayers)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = PANEL_NT >> 6;
     // global row of local row lr, or -1 (padding): a small table in LDS
-    int* rowmap = reinterpret_cast<int*>(lds + B.off_red);
+    int* rowmap = reinterpret_cast<int*>(lds + (ST ? LY::red : B.off_red));
     if (tid < kPanelRows) {
         int r = m0 + tid < P.m ? m0 + tid : -1;
-        if (bpb) {
+        if (ST ? SH::kByBatch : bpb != 0) {
             const int a = tid / bpb, b = (int)blockIdx.x * bpb + (tid - a * bpb);
             r = (a < P.g_na && b < P.g_nb) ? a * P.g_nb + b : -1;
         }
@@ -278,9 +451,9 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
 #endif
     MARL_TS();
     float* X = lds;
-    float* Y = lds + B.off_panel1;
-    float* part = lds + B.off_part;
-    float* prm = lds + B.off_prm;  // [layer][bias | gamma | beta][n] staged once
+    float* Y = lds + (ST ? LY::panel1 : B.off_panel1);
+    float* part = lds + (ST ? LY::part : B.off_part);
+    float* prm = lds + (ST ? LY::prm : B.off_prm);  // [layer][bias | gamma | beta][n] staged once
     // The per-channel vectors of EVERY layer and the input rows are requested before anything is
     // waited for (one round trip to L2 at the head of the kernel instead of one per layer plus
     // one per staging pass); the LDS stores follow the staging below.  n <= 32 * waves <= threads.
@@ -288,7 +461,8 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
 #pragma unroll
     for (int l = 0; l < kPanelMaxLayers; ++l) {
         pv[l][0] = pv[l][1] = pv[l][2] = 0.f;
-        if (l < P.nlayers && tid < P.layer[l].n) {
+        if (ST && l >= SH::kLayers) continue;
+        if (l < PANEL_NL && tid < (ST ? SH::n(l) : P.layer[l].n)) {
             pv[l][0] = P.layer[l].bias[tid];
             pv[l][1] = P.layer[l].gamma[tid];
             pv[l][2] = P.layer[l].beta[tid];
@@ -305,14 +479,14 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
 
     // ---- stage the 32-row input panel (zero-filled past k0 and past M)
     {
-        const int k0 = P.k0, xs = panel_stride(k0), K16 = (k0 + 15) & ~15;
+        const int k0 = ST ? SH::kK0 : P.k0, xs = panel_stride(k0), K16 = (k0 + 15) & ~15;
         const int c4 = K16 >> 2;
         const int K4 = (k0 + 3) & ~3;
-        if (!GATE && P.agg_na > 0) {  // (GATE: the launcher admits the agg_at site only)
+        if (!GATE && !ST && P.agg_na > 0) {  // (GATE / static forms: the launcher admits the agg_at site only)
             // message mean over the OTHER agents (networks/message.py:5-17), 4 loads in flight
             const int na = P.agg_na, nb = P.agg_nb;
             const float den = (float)(na - 1);
-            for (int e = tid; e < kPanelRows * c4; e += blockDim.x) {
+            for (int e = tid; e < kPanelRows * c4; e += PANEL_NT) {
                 const int lr = e / c4, k = (e % c4) * 4;
                 const int r = rowmap[lr];
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -350,7 +524,7 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             float4 xv[2];  // the first two passes' loads fly together
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
-                const int e = tid + it * (int)blockDim.x;
+                const int e = tid + it * (int)PANEL_NT;
                 xv[it] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e % c4) * 4;
@@ -360,13 +534,13 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             }
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
-                const int e = tid + it * (int)blockDim.x;
+                const int e = tid + it * (int)PANEL_NT;
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e % c4) * 4;
                     *reinterpret_cast<float4*>(X + lr * xs + k) = xv[it];
                 }
             }
-            for (int e = tid + 2 * (int)blockDim.x; e < kPanelRows * c4; e += blockDim.x) {
+            for (int e = tid + 2 * blockDim.x; e < kPanelRows * c4; e += PANEL_NT) {
                 const int lr = e / c4, k = (e % c4) * 4;
                 const int r = rowmap[lr];
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -376,17 +550,18 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
         }
     }
     {
-        int off = 0;
+        int poff = 0;
 #pragma unroll
         for (int l = 0; l < kPanelMaxLayers; ++l) {
-            if (l < P.nlayers) {
-                const int n = P.layer[l].n;
+            if (ST && l >= SH::kLayers) continue;
+            if (l < PANEL_NL) {
+                const int n = ST ? SH::n(l) : P.layer[l].n;
                 if (tid < n) {
-                    prm[off + tid] = pv[l][0];
-                    prm[off + n + tid] = pv[l][1];
-                    prm[off + 2 * n + tid] = pv[l][2];
+                    prm[poff + tid] = pv[l][0];
+                    prm[poff + n + tid] = pv[l][1];
+                    prm[poff + 2 * n + tid] = pv[l][2];
                 }
-                off += 3 * n;
+                poff += 3 * n;
             }
         }
     }
@@ -396,18 +571,22 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
     lds_barrier();
     MARL_TS();
 
-    int prm_off = 0, K = P.k0;
-    for (int l = 0; l < P.nlayers; ++l) {
+    int prm_off = 0, K = ST ? SH::kK0 : P.k0;
+    constexpr int kUnroll = ST ? SH::kLayers : 1;  // (the run-time form keeps its loop)
+#pragma unroll kUnroll
+    for (int l = 0; l < (ST ? SH::kLayers : PANEL_NL); ++l) {
+        if (ST && SH::kSoft > 0 && l >= SH::kSoft && PANEL_NL <= SH::kSoft) break;  // (scalar: the encoder-only form)
         const PanelLayer Lr = P.layer[l];  // by value: no scalar re-loads inside the loops
+        const int n = ST ? SH::n(l) : Lr.n;
         const float* lbias = prm + prm_off;
-        const float* lgamma = lbias + Lr.n;
-        const float* lbeta = lgamma + Lr.n;
-        prm_off += 3 * Lr.n;
+        const float* lgamma = lbias + n;
+        const float* lbeta = lgamma + n;
+        prm_off += 3 * n;
         float* in = (l & 1) ? Y : X;
         float* outp = (l & 1) ? X : Y;  // this layer's output panel (next layer's input)
         const int K16 = (K + 15) & ~15;
         const int stride = panel_stride(K);
-        if (l > 0 && l == P.agg_at) {
+        if (l > 0 && l == (ST ? SH::kAggAt : P.agg_at)) {
             // the panel holds the messages of every agent of this workgroup's batch elements:
             // message mean over the OTHER agents in place (sequential over agents, as the
             // reference's sum(dim=0)), kept in xbar for the weight gradients
@@ -416,11 +595,12 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             float4 v[2];
 #pragma unroll
             for (int it = 0; it < 2; ++it) {  // launcher: kPanelRows * c4 <= 2 * blockDim.x
-                const int e = tid + it * (int)blockDim.x;
+                const int e = tid + it * (int)PANEL_NT;
                 v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e - lr * c4) * 4;
-                    const int a = lr / bpb, i = lr - a * bpb;
+                    const int bd = ST && !SH::kByBatch ? 1 : bpb;  // (a tiled static role has no such site)
+                    const int a = lr / bd, i = lr - a * bd;
                     if (MIX) {
                         // communication graph: one fmaf chain over the senders, ascending; a sender whose
                         // coefficient is exactly 0 is not read (its NaN / Inf cannot leak through 0 * x)
@@ -457,7 +637,7 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             lds_barrier();
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
-                const int e = tid + it * (int)blockDim.x;
+                const int e = tid + it * (int)PANEL_NT;
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e - lr * c4) * 4;
                     *reinterpret_cast<float4*>(in + lr * stride + k) = v[it];
@@ -468,15 +648,19 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
             }
             lds_barrier();
         }
-        const int n = Lr.n, nt = (n + 31) >> 5;
+        const int nt = (n + 31) >> 5;
         const int ks = panel_ksplit(K, nt, nwaves);
         const int j = wave % nt, s = wave / nt;
         const bool active = s < ks;
-        const int kper = (((K16 + ks - 1) / ks) + 15) & ~15;
-        const int kbeg = s * kper;
-        const int kend = kbeg + kper < K16 ? kbeg + kper : K16;
         f32x4 acc[2];
-        if (active) panel_gemm(acc, in, stride, Lr.wfrag, Lr.wgroups, j, kbeg, kend, lane);
+        if constexpr (ST) {
+            if (active) panel_gemm_layer<SH, false>(l, acc, in, stride, Lr.wfrag, j, s, lane);
+        } else {
+            const int kper = (((K16 + ks - 1) / ks) + 15) & ~15;
+            const int kbeg = s * kper;
+            const int kend = kbeg + kper < K16 ? kbeg + kper : K16;
+            if (active) panel_gemm(acc, in, stride, Lr.wfrag, Lr.wgroups, j, kbeg, kend, lane);
+        }
         MARL_TS();
         panel_ksum(acc, part, nt, ks, j, s, lane, active);
         MARL_TS();
@@ -488,13 +672,13 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int col = j * 32 + 16 * t + l16;
-                const bool cv = col < n;
+                const bool cv = (ST && (n & 31) == 0) || col < n;  // (static widths: whole tiles)
                 const float bv = cv ? lbias[col] : 0.f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lr = 4 * quad + r;
                     const float zv = cv ? acc[t][r] + bv : 0.f;
-                    if (col < n16) outp[lr * ys + col] = zv;
+                    if ((ST && (n & 31) == 0) || col < n16) outp[lr * ys + col] = zv;
                 }
             }
         }
@@ -502,7 +686,7 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
         lds_barrier();
         MARL_TS();
         // LayerNorm + SiLU row pass (panel_ln_rows above), unrolled for this layer's width
-        if (n <= B.ln_narrow_max)
+        if (n <= (ST ? 128 : B.ln_narrow_max))
             panel_ln_rows<2>(Lr, outp, ys, n, lgamma, lbeta, rowmap, wave, nwaves, lane);
         else
             panel_ln_rows<kPanelMaxCols>(Lr, outp, ys, n, lgamma, lbeta, rowmap, wave, nwaves, lane);
@@ -512,12 +696,56 @@ __global__ __launch_bounds__(768, 6) void panel_fwd_kernel(const PanelFwdBatch B
         K = n;
     }
     // (outside the layer loop: none of the loop's layer descriptors stays live across the chain)
-    if (EPI && (int)(&P - B.p) + 1 == B.epi_prob) {  // (not blockIdx.y: one scalar fewer kept to the end)
+    if (EPI && (ST || (int)blockIdx.y + 1 == B.epi_prob)) {
         constexpr int MAXA = SAMPLE > 0 ? SAMPLE : 4;
         // (the plain EXPLORE instantiation takes the UNI form too: without it, it holds two registers too many)
-        panel_sample_rows<MAXA, MIX || EXPLORE, EXPLORE>(B.sample, (P.nlayers & 1) ? Y : X, panel_stride(K), rowmap, wave, nwaves, lane);
+        panel_sample_rows<MAXA, MIX || EXPLORE || ST, EXPLORE, ST ? SH::n(ST ? SH::kLayers - 1 : 0) : 0>(
+            B.sample, (PANEL_NL & 1) ? Y : X, panel_stride(K), rowmap, wave, nwaves, lane);
         MARL_TS();
     }
+}
+
+#undef PANEL_NT
+#undef PANEL_NL
+
+template <int SAMPLE, bool MIX = false, bool EPI = false, bool GATE = false, bool EXPLORE = false>
+__global__ __launch_bounds__(768, 6) 
+void panel_fwd_kernel(const PanelFwdBatch B) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (!EPI && SAMPLE > 0 && (int)blockIdx.x >= B.panel_blocks) {
+        // ride-along sampling workgroup: one wave per row of the policy activations
+        const int r = ((int)blockIdx.x - B.panel_blocks) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+        if (r >= B.sample.R) return;
+        constexpr int MAXA = SAMPLE > 0 ? SAMPLE : 4;
+        float p[MAXA];
+        SamplePre<MAXA> S;
+        sample_prefetch<MAXA, false>(B.sample, r, threadIdx.x & 63, S);
+        sample_row_logits<MAXA>(B.sample, r, p, threadIdx.x & 63);
+        sample_finish<MAXA>(B.sample, r, p, threadIdx.x & 63, S);
+        return;
+    }
+    panel_fwd_body<PanelDyn, PanelDynLay, SAMPLE, MIX, EPI, GATE, EXPLORE>(B, B.p[blockIdx.y], lds);
+}
+
+// The static forms of the chain launch: problem 0 = the message chain CH (by-batch rows; SOFT: also its encoder-only
+// form), problem 1 = the policy hidden layer PO (row-tiled), with the four-action sampling epilogue (EPI) or without.
+// Plain launches only: no mixing matrix, no gate, no exploration controls, no staged mean, no ride-along rows.
+template <class CH, class PO>
+struct PanelFwdLay {
+    static_assert(CH::ok() && PO::ok() && CH::kWaves == PO::kWaves && CH::kByBatch && !PO::kByBatch, "static panel nets");
+    static constexpr int waves = CH::kWaves;
+    static constexpr int panel1 = cmax(CH::s0(CH::kLayers), PO::s0(PO::kLayers));
+    static constexpr int red = panel1 + cmax(CH::s1(CH::kLayers), PO::s1(PO::kLayers));
+    static constexpr int part = red + (kPanelMaxWaves + 1) * 32, prm = part + (waves - 1) * 512;
+};
+template <class CH, class PO, bool EPI>
+__global__ __launch_bounds__(768, 6) void panel_fwd_static_kernel(const PanelFwdBatch B) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    using LY = PanelFwdLay<CH, PO>;
+    if (blockIdx.y == 0)
+        panel_fwd_body<CH, LY, 0, false, false, false, false>(B, B.p[0], lds);
+    else
+        panel_fwd_body<PO, LY, EPI ? 4 : 0, false, EPI, false, false>(B, B.p[1], lds);
 }
 
 constexpr size_t kPanelMaxLds = 144 * 1024;
@@ -647,6 +875,68 @@ static int panel_fwd_plan(PanelFwdBatch& b, PanelFwdPlan& pl) {
     return MARL_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The static forms (README dimensions: BASELINE C3 / C5, and C4's message chain).  MARL_PANEL_STATIC=0 keeps every
+// launch on the run-time form (same-binary comparison; read once per process).
+// ---------------------------------------------------------------------------
+using PanelChainNet = PanelNet<12, 256, 2, 2, 128, 64, 128, 96>;  // encoder 256 -> 128 -> 64 | mean | decoder -> 128 -> 96
+using PanelPolicyNet = PanelNet<12, 256, 0, 0, 384>;              // policy hidden layer 256 -> 384
+using PanelFwdStaticLay = PanelFwdLay<PanelChainNet, PanelPolicyNet>;
+using PanelBwdChainNet = PanelBwdNet<8, 2, 256, 96, 128, 64, 128>;  // decoder(t) | mean | encoder(t-1) -> dh
+using PanelBwdDecNet = PanelBwdNet<8, 0, 64, 96, 128>;              // step 0: the decoder alone
+static_assert(PanelBwdChainNet::ok() && PanelBwdDecNet::ok(), "static panel nets");
+constexpr int kPanelStaticActions = 4;
+
+static bool panel_static_env() {
+    static const bool on = [] {
+        const char* v = getenv("MARL_PANEL_STATIC");
+        return !(v && v[0] == '0');
+    }();
+    return on;
+}
+
+int panel_static_model(int n_b, int n_a, int nm2, int n_m, int n_mo, int nla, int n_actions, int n_d) {
+    using C = PanelChainNet;
+    return panel_static_env() && n_b == C::kK0 && nm2 == C::n(0) && n_m == C::n(1) && nm2 == C::n(2) && n_mo == C::n(3) &&
+           n_a == PanelPolicyNet::kK0 && nla == PanelPolicyNet::n(0) && n_actions == kPanelStaticActions &&
+           (n_d & 3) == 0 && n_d <= 256;  // (the embedding's four-columns-a-lane form, as the launcher asks of the epilogue)
+}
+
+template <class SH>
+static bool panel_fwd_matches(const PanelFwdProb& p, int layers) {
+    if (p.nlayers != layers || p.k0 != SH::kK0 || p.agg_na != 0 || p.mix || p.gate.pos) return false;
+    if (SH::kByBatch ? p.by_batch < 1 : p.by_batch != 0) return false;
+    if (p.agg_at != (layers > SH::kAggAt ? SH::kAggAt : 0)) return false;
+    for (int l = 0; l < layers; ++l)
+        if (p.layer[l].n != SH::n(l) || p.layer[l].wgroups != panel_frag_groups(SH::k(l))) return false;
+    return true;
+}
+// host twin of sample_pe_fast (sample.h): the static epilogue takes the four-columns-a-lane embedding for granted
+static bool panel_pe_fast_host(const SampleArgs& A) {
+    const uintptr_t al = (uintptr_t)A.pe_W | (uintptr_t)A.pe_b | (uintptr_t)A.pe_gamma | (uintptr_t)A.pe_beta |
+                         (uintptr_t)A.pe_z | (uintptr_t)A.pe_out;
+    return A.pe_W && A.step_logp && (al & 15) == 0 && A.pe_nd <= 256 && ((A.pe_nd | A.pe_ldz | A.pe_ldo) & 3) == 0 &&
+           (A.pe_col0 & 3) == 0;
+}
+// the launch is the plain chain launch of the static nets, planned as their layout has it
+static bool panel_fwd_static_ok(const PanelFwdBatch& b, const PanelFwdPlan& pl, bool explore) {
+    using LY = PanelFwdStaticLay;
+    if (!panel_static_env() || explore || pl.mixed || pl.gated || b.count != 2 || b.has_sample) return false;
+    if (!panel_fwd_matches<PanelChainNet>(b.p[0], PanelChainNet::kLayers) &&
+        !panel_fwd_matches<PanelChainNet>(b.p[0], PanelChainNet::kSoft))
+        return false;
+    if (!panel_fwd_matches<PanelPolicyNet>(b.p[1], 1)) return false;
+    if (pl.waves != LY::waves || b.off_panel1 != LY::panel1 || b.off_red != LY::red || b.off_part != LY::part ||
+        b.off_prm != LY::prm || b.ln_narrow_max != 128)
+        return false;
+    if (b.epi_prob) {
+        const SampleArgs& A = b.sample;
+        if (b.epi_prob != 2 || A.nA != kPanelStaticActions || A.nla != PanelPolicyNet::n(0)) return false;
+        if (A.pe_W && !panel_pe_fast_host(A)) return false;
+    }
+    return true;
+}
+
 int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
     PanelFwdPlan pl;
     MARL_TRY(panel_fwd_plan(b, pl));
@@ -656,7 +946,9 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
     const bool mixed = pl.mixed, gated = pl.gated;
     static bool raised = false;
     if (!raised) {
-        const void* kerns[11] = {reinterpret_cast<const void*>(panel_fwd_kernel<0>),
+        const void* kerns[13] = {reinterpret_cast<const void*>(panel_fwd_static_kernel<PanelChainNet, PanelPolicyNet, false>),
+                                reinterpret_cast<const void*>(panel_fwd_static_kernel<PanelChainNet, PanelPolicyNet, true>),
+                                reinterpret_cast<const void*>(panel_fwd_kernel<0>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<4>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<MARL_MAX_ACTIONS>),
                                 reinterpret_cast<const void*>(panel_fwd_kernel<0, true>),
@@ -703,7 +995,15 @@ int launch_panel_fwd(PanelFwdBatch& b, hipStream_t st, bool explore) {
         }
     }
     prof_before(4, st);
-    if (b.epi_prob && explore) {  // the same three forms, sampling from the behaviour policy
+    if (panel_fwd_static_ok(b, pl, explore)) {
+        b.has_sample = 0;
+        if (b.epi_prob)
+            hipLaunchKernelGGL((panel_fwd_static_kernel<PanelChainNet, PanelPolicyNet, true>),
+                               dim3(pblocks, (unsigned)b.count), dim3(64 * waves), lds, st, b);
+        else
+            hipLaunchKernelGGL((panel_fwd_static_kernel<PanelChainNet, PanelPolicyNet, false>),
+                               dim3(pblocks, (unsigned)b.count), dim3(64 * waves), lds, st, b);
+    } else if (b.epi_prob && explore) {  // the same three forms, sampling from the behaviour policy
         b.has_sample = 0;
         if (gated)
             hipLaunchKernelGGL((panel_fwd_kernel<4, true, true, true, true>), dim3(pblocks, (unsigned)b.count),
@@ -771,11 +1071,15 @@ constexpr int kBwdMaxCols = kPanelMaxCols;  // columns per lane in the row pass:
 // MIX: the agg_at site applies the transpose of a communication graph's mixing matrix (P.mix) instead of the mean
 // GATE (with MIX): one matrix per image of the workgroup, gated by the positions of the forward's emission step (P.gate)
 // and built by the forward's arithmetic (comm_gate_weight), stored transposed
-template <bool CELL, int MAXC, bool MIX = false, bool GATE = false>
+// SH: PanelDyn (every shape, from P) or a PanelBwdNet (by-batch rows, no staged mean, the LDS tail, the layout of
+// the net; launch_panel_bwd matches the descriptors before it picks one)
+template <class SH, bool CELL, int MAXC, bool MIX = false, bool GATE = false>
 __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr bool ST = SH::kStatic;
+    const int nthreads = ST ? 64 * SH::kWaves : (int)blockDim.x;
     if (CELL && (int)blockIdx.x >= P.panel_blocks) {
-        const int64_t idx = (int64_t)((int)blockIdx.x - P.panel_blocks) * blockDim.x + threadIdx.x;
+        const int64_t idx = (int64_t)((int)blockIdx.x - P.panel_blocks) * nthreads + threadIdx.x;
         if (P.cell_vec4)
             lstm_cell_bwd_elem4(P.cell, P.cell_rows, idx);
         else
@@ -784,19 +1088,20 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
     }
     const int m0 = blockIdx.x * kPanelRows;
     const int bpb = P.by_batch;  // > 0: this workgroup owns all agents of bpb batch elements
-    if (bpb ? (int)blockIdx.x * bpb >= P.g_nb : m0 >= P.m) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    if ((ST || bpb) ? (int)blockIdx.x * bpb >= P.g_nb : m0 >= P.m) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = nthreads >> 6;
     const int quad = lane >> 4, l16 = lane & 15;
+    const int nlayers = ST ? SH::kLayers : P.nlayers;
     float* D = lds;            // current gradient panel
-    float* E = lds + P.off_e;  // next one
-    float* prm = lds + P.off_prm;
-    float* colp = lds + P.off_colp;  // [nwaves][2][n]
-    float* part = lds + P.off_part;
+    float* E = lds + (ST ? SH::off_e : P.off_e);  // next one
+    float* prm = lds + (ST ? SH::off_prm : P.off_prm);
+    float* colp = lds + (ST ? SH::off_colp : P.off_colp);  // [nwaves][2][n]
+    float* part = lds + (ST ? SH::off_part : P.off_part);
     // global row of local row lr, or -1 (padding): a small table in LDS
-    int* rowmap = reinterpret_cast<int*>(lds + P.off_rowmap);
+    int* rowmap = reinterpret_cast<int*>(lds + (ST ? SH::off_rowmap : P.off_rowmap));
     if (tid < kPanelRows) {
         int r = m0 + tid < P.m ? m0 + tid : -1;
-        if (bpb) {
+        if (ST || bpb) {
             const int a = tid / bpb, b = (int)blockIdx.x * bpb + (tid - a * bpb);
             r = (a < P.g_na && b < P.g_nb) ? a * P.g_nb + b : -1;
         }
@@ -812,7 +1117,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
     // two rows of this wave for layer l + 1 fly while layer l's dX product runs.  Unconditional
     // loads (padding rows read row 0) so that no wait is widened by a branch.
     float zpre[2][MAXC], mpre[2], rpre[2];
-    auto zfetch = [&](const PanelBwdLayer& L) {
+    auto zfetch = [&](const PanelBwdLayer& L, const int ln) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int lr = wave + i * nwaves;
@@ -823,11 +1128,11 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
 #pragma unroll
             for (int u = 0; u < MAXC; ++u) {
                 const int c = lane + 64 * u;
-                zpre[i][u] = c < L.n ? L.z[rr * L.ldz + c] : 0.f;
+                zpre[i][u] = c < ln ? L.z[rr * L.ldz + c] : 0.f;
             }
         }
     };
-    zfetch(P.layer[0]);  // first: in flight behind the parameter and gradient-panel loads below
+    zfetch(P.layer[0], ST ? SH::n(0) : P.layer[0].n);  // first: in flight behind the parameter and gradient-panel loads below
     // LayerNorm affine parameters of every layer -> LDS; d(a_last) panel -> D
     {
         // (all layers' vectors requested before anything is waited for; n <= 384 <= threads)
@@ -835,7 +1140,8 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
 #pragma unroll
         for (int l = 0; l < kPanelMaxLayers; ++l) {
             pv[l][0] = pv[l][1] = 0.f;
-            if (l < P.nlayers && tid < P.layer[l].n) {
+            if (ST && l >= SH::kLayers) continue;
+            if (l < nlayers && tid < (ST ? SH::n(l) : P.layer[l].n)) {
                 pv[l][0] = P.layer[l].gamma[tid];
                 pv[l][1] = P.layer[l].beta[tid];
             }
@@ -853,8 +1159,9 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
         int off = 0;
 #pragma unroll
         for (int l = 0; l < kPanelMaxLayers; ++l) {
-            if (l < P.nlayers) {
-                const int n = P.layer[l].n;
+            if (ST && l >= SH::kLayers) continue;
+            if (l < nlayers) {
+                const int n = ST ? SH::n(l) : P.layer[l].n;
                 if (tid < n) {
                     prm[off + tid] = pv[l][0];
                     prm[off + n + tid] = pv[l][1];
@@ -864,13 +1171,14 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
         }
         if (MIX && !GATE && tid < P.g_na * P.g_na) lds[P.off_mix + tid] = cmv;
         if (MIX && GATE && tid < bpb * P.g_na * P.g_na) lds[P.off_mix + tid] = cmv;
-        const int n = P.layer[0].n, ds = panel_stride(n), n16 = (n + 15) & ~15, c4 = n16 >> 2;
+        const int n = ST ? SH::n(0) : P.layer[0].n, ds = panel_stride(n), n16 = (n + 15) & ~15, c4 = n16 >> 2;
         const int n4 = (n + 3) & ~3;
-        for (int e = tid; e < kPanelRows * c4; e += blockDim.x) {
+        const int agg_na = ST ? 0 : P.agg_na;  // (static forms: no staged mean)
+        for (int e = tid; e < kPanelRows * c4; e += nthreads) {
             const int lr = e / c4, k = (e % c4) * 4;
             const int r = rowmap[lr];
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r >= 0 && k < n4 && P.agg_na > 1) {
+            if (r >= 0 && k < n4 && agg_na > 1) {
                 const int na = P.agg_na, nb = P.agg_nb;
                 const float den = (float)(na - 1);
                 const float* base = P.da + (size_t)(r % nb) * P.ldda + k;
@@ -896,7 +1204,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                 const float4 me = *reinterpret_cast<const float4*>(P.da + (size_t)r * P.ldda + k);
                 v = make_float4((s.x - me.x) / den, (s.y - me.y) / den, (s.z - me.z) / den,
                                 (s.w - me.w) / den);
-            } else if (r >= 0 && k < n4 && P.agg_na == 0) {
+            } else if (r >= 0 && k < n4 && agg_na == 0) {
                 v = *reinterpret_cast<const float4*>(P.da + (size_t)r * P.ldda + k);
                 if (P.da2) {
                     const float4 w = *reinterpret_cast<const float4*>(P.da2 + (size_t)r * P.ldda2 + k);
@@ -911,13 +1219,15 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
     MARL_TS();
 
     int prm_off = 0;
-    for (int l = 0; l < P.nlayers; ++l) {
+    constexpr int kUnroll = ST ? SH::kLayers : 1;  // (the run-time form keeps its loop)
+#pragma unroll kUnroll
+    for (int l = 0; l < nlayers; ++l) {
         const PanelBwdLayer Lr = P.layer[l];  // by value: no scalar re-loads inside the loops
-        const int n = Lr.n, ds = panel_stride(n), n16 = (n + 15) & ~15;
+        const int n = ST ? SH::n(l) : Lr.n, ds = panel_stride(n), n16 = (n + 15) & ~15;
         const float* lgamma = prm + prm_off;
         const float* lbeta = lgamma + n;
         prm_off += 2 * n;
-        if (l > 0 && l == P.agg_at) {
+        if (l > 0 && l == (ST ? SH::kAggAt : P.agg_at)) {
             // D holds the gradient of the message MEAN for every agent of this workgroup's batch
             // elements: the mean over the other agents is self-adjoint - the same sum (sequential
             // over agents, as the staging version) gives the gradient of the messages
@@ -926,7 +1236,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
             float4 v[2];
 #pragma unroll
             for (int it = 0; it < 2; ++it) {  // launcher: kPanelRows * c4 <= 2 * blockDim.x
-                const int e = tid + it * (int)blockDim.x;
+                const int e = tid + it * nthreads;
                 v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e - lr * c4) * 4;
@@ -967,7 +1277,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
             lds_barrier();
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
-                const int e = tid + it * (int)blockDim.x;
+                const int e = tid + it * nthreads;
                 if (e < kPanelRows * c4) {
                     const int lr = e / c4, k = (e - lr * c4) * 4;
                     *reinterpret_cast<float4*>(D + lr * ds + k) = v[it];
@@ -1005,11 +1315,11 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                             xh[u] = dxh[u] = 0.f;
                             if (c < n) {
                                 xh[u] = (zpre[i][u] - mean) * rstd;
-                                const float dy = D[lr * ds + c] * silu_grad_p(g[u] * xh[u] + bt[u]);
-                                dxh[u] = dy * g[u];
+                                const float dy = mul_rn(D[lr * ds + c], silu_grad_p(g[u] * xh[u] + bt[u]));
+                                dxh[u] = mul_rn(dy, g[u]);
                                 s1 += dxh[u];
-                                s2 += dxh[u] * xh[u];
-                                pg[u] += dy * xh[u];
+                                s2 += mul_rn(dxh[u], xh[u]);
+                                pg[u] += mul_rn(dy, xh[u]);
                                 pb[u] += dy;
                             }
                         }
@@ -1045,28 +1355,33 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
         MARL_TS();
         lds_barrier();
         MARL_TS();
-        for (int c = tid; c < 2 * n; c += blockDim.x) {
+        for (int c = tid; c < 2 * n; c += nthreads) {
             float t = 0.f;
             for (int w = 0; w < nwaves; ++w) t += colp[(size_t)w * 2 * n + c];
             Lr.part[(size_t)blockIdx.x * 2 * n + c] = t;
         }
-        if (l + 1 < P.nlayers) zfetch(P.layer[l + 1]);
+        if (l + 1 < nlayers) zfetch(P.layer[l + 1], ST ? SH::n(l + 1 < SH::kLayers ? l + 1 : 0) : P.layer[l + 1].n);
         MARL_TS();
         // ---- dX = dz * W: out tiles over k_in columns, contraction over n
-        const int nout = Lr.k_in, nt = (nout + 31) >> 5;
+        const int nout = ST ? SH::k(l) : Lr.k_in, nt = (nout + 31) >> 5;
         const int ks = panel_ksplit(n, nt, nwaves);
         const int kper = (((n16 + ks - 1) / ks) + 15) & ~15;
-        const bool last = l + 1 == P.nlayers;
+        const bool last = l + 1 == nlayers;
+        const bool tail_lds = ST || P.tail_lds;
         const int es = panel_stride(nout), o16 = (nout + 15) & ~15;
         // more column tiles than waves: walk them in rounds (first layer's input can be wide)
         for (int t0 = 0; t0 < nt; t0 += nwaves / ks) {
             const int tiles_round = nwaves / ks;
             const int j = t0 + wave % tiles_round, s = wave / tiles_round;
             const bool active = s < ks && j < nt;
-            const int kbeg = s * kper;
-            const int kend = kbeg + kper < n16 ? kbeg + kper : n16;
             f32x4 acc[2];
-            if (active) panel_gemm(acc, D, ds, Lr.wtfrag, Lr.wgroups, j, kbeg, kend, lane);
+            if constexpr (ST) {
+                if (active) panel_gemm_layer<SH, true>(l, acc, D, ds, Lr.wtfrag, j, s, lane);
+            } else {
+                const int kbeg = s * kper;
+                const int kend = kbeg + kper < n16 ? kbeg + kper : n16;
+                if (active) panel_gemm(acc, D, ds, Lr.wtfrag, Lr.wgroups, j, kbeg, kend, lane);
+            }
             // slice partials are indexed by the tile's slot in this round
             panel_ksum(acc, part, tiles_round, ks, wave % tiles_round, s, lane, active);
             if (active && s == 0) {
@@ -1081,7 +1396,7 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
                         const int lr = 4 * quad + r;
                         const int row = rw[r];
                         const float v = col < nout ? acc[t][r] : 0.f;
-                        if (last && P.tail_lds) {  // final dX through LDS: finished row-wise below
+                        if (last && tail_lds) {  // final dX through LDS: finished row-wise below
                             if (col < o16) E[lr * es + col] = v;
                         } else if (last) {
                             if (col < nout && row >= 0) {
@@ -1099,23 +1414,23 @@ __global__ __launch_bounds__(768, 4) void panel_bwd_kernel(const PanelBwdProb P)
             lds_barrier();
         }
         MARL_TS();
-        if (last && P.tail_lds) {
+        if (last && tail_lds) {
             // Final dX (+ the belief cell's elementwise backward) ROW-wise from the LDS panel: four
             // consecutive columns per thread, 16-byte loads of everything two items need before
             // the first store.  In the accumulator layout the same work is eight scattered
             // elements per lane whose stores keep the next element's loads from being issued
             // (in-kernel timestamps: 20 us of the 46 us chain).
             const LstmBwdArgs& Cb = P.cellb;
-            const int c4n = nout >> 2, items = kPanelRows * c4n, cn = Cb.n;
+            const int c4n = nout >> 2, items = kPanelRows * c4n, cn = ST ? nout : Cb.n;  // (launcher: cellb.n == k_in)
             // (one item per pass: two in flight need 162 registers and then the riding-along cell
             // workgroups no longer fit beside a panel workgroup)
             constexpr int kIt = 1;
-            for (int base = 0; base < items; base += kIt * (int)blockDim.x) {
+            for (int base = 0; base < items; base += kIt * nthreads) {
                 float4 ov[kIt], gi[kIt], gf[kIt], gg[kIt], go[kIt], cnew[kIt], cprev[kIt], dcv[kIt];
                 int rowi[kIt], coli[kIt], lri[kIt];
 #pragma unroll
                 for (int k = 0; k < kIt; ++k) {
-                    const int i = base + tid + k * (int)blockDim.x;
+                    const int i = base + tid + k * nthreads;
                     const int lr = i < items ? i / c4n : 0;
                     const int c = i < items ? (i - lr * c4n) * 4 : 0;
                     const int row = i < items ? rowmap[lr] : -1;
@@ -1289,6 +1604,20 @@ plan:  // (second pass without the LDS tail when the extra output panel does not
     return MARL_OK;
 }
 
+// the launch is the plain by-batch chain of net SH, planned as SH's layout has it
+template <class SH>
+static bool panel_bwd_static_ok(const PanelBwdProb& p, const PanelBwdPlan& pl) {
+    if (!panel_static_env() || p.mix || p.gate.pos || p.nlayers != SH::kLayers || p.agg_na != 0 || p.by_batch < 1 ||
+        p.agg_at != SH::kAggAt || !p.tail_lds || pl.maxc != 2 || pl.waves != SH::kWaves)
+        return false;
+    for (int l = 0; l < SH::kLayers; ++l)
+        if (p.layer[l].n != SH::n(l) || p.layer[l].k_in != SH::k(l) || p.layer[l].wgroups != panel_frag_groups(SH::n(l)))
+            return false;
+    if (p.has_cellb && p.cellb.n != SH::kKLast) return false;
+    return p.off_e == SH::off_e && p.off_prm == SH::off_prm && p.off_colp == SH::off_colp && p.off_part == SH::off_part &&
+           p.off_rowmap == SH::off_rowmap;
+}
+
 int launch_panel_bwd(PanelBwdProb& p, hipStream_t st) {
     PanelBwdPlan pl;
     MARL_TRY(panel_bwd_plan(p, pl));
@@ -1297,18 +1626,21 @@ int launch_panel_bwd(PanelBwdProb& p, hipStream_t st) {
     const unsigned pblocks = pl.pblocks;
     static bool raised = false;
     if (!raised) {
-        const void* kerns[12] = {reinterpret_cast<const void*>(panel_bwd_kernel<false, 2>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, 2>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<false, 2, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, 2, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<false, 2, true, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, 2, true, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<false, kBwdMaxCols, true, true>),
-                                reinterpret_cast<const void*>(panel_bwd_kernel<true, kBwdMaxCols, true, true>)};
+        const void* kerns[15] = {reinterpret_cast<const void*>(panel_bwd_kernel<PanelBwdChainNet, false, 2>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelBwdChainNet, true, 2>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelBwdDecNet, false, 2>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, false, 2>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, true, 2>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, false, kBwdMaxCols>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, true, kBwdMaxCols>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, false, 2, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, true, 2, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, false, kBwdMaxCols, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, true, kBwdMaxCols, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, false, 2, true, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, true, 2, true, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, false, kBwdMaxCols, true, true>),
+                                reinterpret_cast<const void*>(panel_bwd_kernel<PanelDyn, true, kBwdMaxCols, true, true>)};
         for (const void* kf : kerns)
             MARL_HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelMaxLds));
         raised = true;
@@ -1321,35 +1653,43 @@ int launch_panel_bwd(PanelBwdProb& p, hipStream_t st) {
     p.ts = rec ? d_ts : nullptr;
 #endif
     const unsigned cblocks = pl.cblocks;
-    if (p.mix) {
+    if (panel_bwd_static_ok<PanelBwdChainNet>(p, pl)) {
+        if (p.has_cell)
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelBwdChainNet, true, 2>), dim3(pblocks + cblocks), dim3(64 * waves), lds,
+                               st, p);
+        else
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelBwdChainNet, false, 2>), dim3(pblocks), dim3(64 * waves), lds, st, p);
+    } else if (!p.has_cell && panel_bwd_static_ok<PanelBwdDecNet>(p, pl)) {
+        hipLaunchKernelGGL((panel_bwd_kernel<PanelBwdDecNet, false, 2>), dim3(pblocks), dim3(64 * waves), lds, st, p);
+    } else if (p.mix) {
         const dim3 blk(64 * waves);
         if (p.gate.pos) {
             if (p.has_cell && maxc == 2)
-                hipLaunchKernelGGL((panel_bwd_kernel<true, 2, true, true>), dim3(pblocks + cblocks), blk, lds, st, p);
+                hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, true, 2, true, true>), dim3(pblocks + cblocks), blk, lds, st, p);
             else if (p.has_cell)
-                hipLaunchKernelGGL((panel_bwd_kernel<true, kBwdMaxCols, true, true>), dim3(pblocks + cblocks), blk, lds,
+                hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, true, kBwdMaxCols, true, true>), dim3(pblocks + cblocks), blk, lds,
                                    st, p);
             else if (maxc == 2)
-                hipLaunchKernelGGL((panel_bwd_kernel<false, 2, true, true>), dim3(pblocks), blk, lds, st, p);
+                hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, false, 2, true, true>), dim3(pblocks), blk, lds, st, p);
             else
-                hipLaunchKernelGGL((panel_bwd_kernel<false, kBwdMaxCols, true, true>), dim3(pblocks), blk, lds, st, p);
+                hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, false, kBwdMaxCols, true, true>), dim3(pblocks), blk, lds, st, p);
         } else if (p.has_cell && maxc == 2)
-            hipLaunchKernelGGL((panel_bwd_kernel<true, 2, true>), dim3(pblocks + cblocks), blk, lds, st, p);
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, true, 2, true>), dim3(pblocks + cblocks), blk, lds, st, p);
         else if (p.has_cell)
-            hipLaunchKernelGGL((panel_bwd_kernel<true, kBwdMaxCols, true>), dim3(pblocks + cblocks), blk, lds, st, p);
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, true, kBwdMaxCols, true>), dim3(pblocks + cblocks), blk, lds, st, p);
         else if (maxc == 2)
-            hipLaunchKernelGGL((panel_bwd_kernel<false, 2, true>), dim3(pblocks), blk, lds, st, p);
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, false, 2, true>), dim3(pblocks), blk, lds, st, p);
         else
-            hipLaunchKernelGGL((panel_bwd_kernel<false, kBwdMaxCols, true>), dim3(pblocks), blk, lds, st, p);
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, false, kBwdMaxCols, true>), dim3(pblocks), blk, lds, st, p);
     } else if (p.has_cell) {
         if (maxc == 2)
-            hipLaunchKernelGGL((panel_bwd_kernel<true, 2>), dim3(pblocks + cblocks), dim3(64 * waves), lds, st, p);
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, true, 2>), dim3(pblocks + cblocks), dim3(64 * waves), lds, st, p);
         else
-            hipLaunchKernelGGL((panel_bwd_kernel<true, kBwdMaxCols>), dim3(pblocks + cblocks), dim3(64 * waves), lds, st, p);
+            hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, true, kBwdMaxCols>), dim3(pblocks + cblocks), dim3(64 * waves), lds, st, p);
     } else if (maxc == 2) {
-        hipLaunchKernelGGL((panel_bwd_kernel<false, 2>), dim3(pblocks), dim3(64 * waves), lds, st, p);
+        hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, false, 2>), dim3(pblocks), dim3(64 * waves), lds, st, p);
     } else {
-        hipLaunchKernelGGL((panel_bwd_kernel<false, kBwdMaxCols>), dim3(pblocks), dim3(64 * waves), lds, st, p);
+        hipLaunchKernelGGL((panel_bwd_kernel<PanelDyn, false, kBwdMaxCols>), dim3(pblocks), dim3(64 * waves), lds, st, p);
     }
     prof_after(4, st);
     MARL_LAUNCH_CHECK();

@@ -135,9 +135,11 @@ __device__ __forceinline__ void sample_prefetch_row(const SampleArgs& A, int r, 
 }
 // ... and the embedding's parameters, 28 registers a lane.  The panel kernel's sampling epilogue asks for them
 // behind the logits' loads (both sets at once do not fit its 80 registers); sample_kernel asks for both up front.
-template <int MAXA>
+// (FAST: the caller's launcher has evaluated sample_pe_fast's conditions on the host - all that is left is whether
+// there is an embedding at all)
+template <int MAXA, bool FAST = false>
 __device__ __forceinline__ void sample_prefetch_pe(const SampleArgs& A, int lane, SamplePre<MAXA>& S) {
-    S.pe_fast = sample_pe_fast(A);
+    S.pe_fast = FAST ? A.pe_W != nullptr : sample_pe_fast(A);
     if (S.pe_fast) {
         const int j4 = 4 * lane < A.pe_nd ? 4 * lane : 0;
         S.qb = *reinterpret_cast<const float4*>(A.pe_b + j4);

@@ -41,16 +41,16 @@ def med(v):
     return sorted(v)[len(v) // 2]
 
 
-def trace(tree, args):
-    """Kernel trace of one bench.py run (a run of its own): {short kernel name: {calls, avg_us, total_ms}} of the two
-    kernels this change touches, and the kernel time of everything."""
+def trace(tree, args, match=("sample_kernel", "panel_fwd_kernel"), env=None):
+    """Kernel trace of one bench.py run (a run of its own): {short kernel name: {calls, avg_us, total_ms}} of the
+    kernels this change touches (names containing one of `match`), and the kernel time of everything."""
     import sqlite3
 
     from rocpd_stats import short
 
     d = tempfile.mkdtemp(prefix="panel_sample_trace_")
     targs = argparse.Namespace(steps=20, warmup=5)
-    bench(tree, targs, env={"TMPDIR": "/tmp"}, prefix=["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "r", "--"])
+    bench(tree, targs, env=dict(env or {}, TMPDIR="/tmp"), prefix=["timeout", "-k", "10", "600", "rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "r", "--"])
     dbs = glob.glob(os.path.join(d, "**", "*.db"), recursive=True)
     if not dbs:
         raise SystemExit(f"no trace database under {d}")
@@ -61,7 +61,7 @@ def trace(tree, args):
     for n, dur in db.execute(f"select {namecol}, (end - start) from kernels"):
         total += dur
         n = short(n)
-        if "sample_kernel" in n or "panel_fwd_kernel" in n:
+        if any(m in n for m in match):
             a = agg.setdefault(n, [0, 0])
             a[0] += 1
             a[1] += dur
