@@ -22,6 +22,16 @@ def r16(v):
     return (v + 15) & ~15
 
 
+def frag_groups(k):
+    """16-wide K groups of a fragment-order weight copy (tests/test_gpu_panel_wfrag.py states the layout)"""
+    return (k + 15) // 16
+
+
+def frag_floats(n, k):
+    """floats of the fragment-order copy of an [n, k] matrix: 32-row tiles, three groups of slack"""
+    return (((n + 31) // 32) * frag_groups(k) + 3) * 512
+
+
 def gamma_n(n):
     """gamma_n = n u / (1 - n u), u = 2^-24: the bound of any fp32 sum of n rounded terms (Higham, Lemma 3.1)"""
     u = 2.0 ** -24

@@ -9,8 +9,8 @@ import pytest
 import torch as th
 
 from marlclassification_amd import comm
-from tests.test_comm_host import _model_config
 from tests.util import ROOT
+from tests.util import small_model_config as _model_config
 
 
 def _row_normalised(m):

@@ -8,6 +8,7 @@ import pytest
 import torch as th
 
 from marlclassification_amd import comm
+from tests.util import small_model_config as _model_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -136,15 +137,6 @@ def test_cli_accepts_the_spelling_and_rejects_malformed_ones(capsys):
     with pytest.raises(SystemExit):
         check_learn_comm(p, args)
     capsys.readouterr()
-
-
-def _model_config(**kw):
-    from marlclassification_amd.config import ModelConfig
-
-    return ModelConfig(ft_extr_str="mnist", window_size=6, hidden_size_belief=12, hidden_size_action=10,
-                       hidden_size_msg=8, hidden_size_msg_output=9, hidden_size_state=4, state_dim=2,
-                       actions=[[1, 0], [-1, 0], [0, 1], [0, -1]], nb_class=10, hidden_size_linear_belief=16,
-                       hidden_size_linear_action=16, **kw)
 
 
 def test_marl_json_round_trip(tmp_path):

@@ -1,14 +1,15 @@
 """marl_cnn_bwd_plan and marl_cnn_fwd_plan (include/marl_hip_cnnops.h) on the host: the plans of the conv launchers
 - backward for a raw layer shape, forward for a model and a row count - from the launchers' own routines.  They must
-agree with what marl_plan_query reports for a whole configuration, and the grids of tests/test_gpu_conv_bwd.py and
-tests/test_gpu_conv_fwd.py must witness every instantiation a model can select.  No GPU: the library loads without one
-(tests/test_plan_witness_host.py relies on the same)."""
+agree with what marl_plan_query reports for a whole configuration, and the grids of tests/conv_cases.py (the cases of
+tests/test_gpu_conv_bwd.py and tests/test_gpu_conv_fwd.py) must witness every instantiation a model can select.  No
+GPU: the library loads without one (tests/test_plan_witness_host.py relies on the same)."""
 import ctypes as C
 
 import pytest
 
-from tests import test_gpu_conv_fwd as fwd
-from tests.test_gpu_conv_bwd import DG_SHAPES, WG_DEEP, WG_FIRST, assert_wgrad_witness, plan
+from tests import conv_cases as fwd
+from tests.conv_cases import DG_SHAPES, WG_DEEP, WG_FIRST, assert_wgrad_witness
+from tests.conv_cases import bwd_plan as plan
 from tests.util import CASES, PLAN_CASES, plan_witness
 
 
@@ -131,7 +132,7 @@ def test_the_forward_hook_agrees_with_plan_query(cfg, na, nb, ns, shape):
             assert lib.marl_tune(b"cnn_fwd2", knob) == 0
             for train in (0, 1):
                 w = plan_witness(cfg, na, nb, ns, shape, train=bool(train))
-                p = fwd.plan(mc, train, na * nb)
+                p = fwd.fwd_plan(mc, train, na * nb)
                 assert p["fused"] == 1
                 assert (p["which"], p["rb"], p["blocks"]) == (w["cnn_fwd"], w["cnn_fwd_rb"], w["cnn_fwd_blocks"]), (p, w)
                 assert p["writes_image"] == (p["which"] in (1, 2, 4, 5)) and not any(p["keeps_cols"])
@@ -152,7 +153,7 @@ def test_the_forward_grid_witnesses_every_selectable_plan():
     for name, stack in list(CNN_SPECS.items()) + list(fwd.COLS_EXTRA.items()):
         for f in range(4, 33):
             for train in (0, 1):
-                p = fwd.plan(fwd.config(stack, f, f + 8, f + 10), train, 1000)
+                p = fwd.fwd_plan(fwd.config(stack, f, f + 8, f + 10), train, 1000)
                 assert p["fused"] == 1, (name, f)
                 selected.setdefault((p["which"], tuple(p["keeps_cols"])), (name, f, train))
     witnessed = {(w["which"], tuple(w["keeps_cols"])) for rows in fwd.GRID.values() for w in rows.values()}
@@ -170,16 +171,16 @@ def test_the_forward_grid_tables_hold_on_the_host():
     for model, rows_w in fwd.GRID.items():
         with fwd.knobs(model):
             for rows, w in rows_w.items():
-                assert fwd.plan(fwd.model_config(model), 1, rows) == w, (model, rows)
+                assert fwd.fwd_plan(fwd.model_config(model), 1, rows) == w, (model, rows)
                 if rows > w["rb"]:
                     assert rows % w["rb"] == 1
                 if rows > 1000:
                     assert (w["blocks"] == 256 < -(-rows // w["rb"])) if w["which"] != 6 else w["blocks"] == -(-rows // w["rb"])
         assert lib.marl_tune_get(b"cnn_fwd2", 1) == 1 and lib.marl_tune_get(b"cnn_fwd3", 1) == 1
     for rows, w in fwd.COLS_GRID.items():
-        assert fwd.plan(fwd.model_config(fwd.COLS_MIN[2]), 1, rows) == w
+        assert fwd.fwd_plan(fwd.model_config(fwd.COLS_MIN[2]), 1, rows) == w
     for model, rows in fwd.FORMS.items():  # the image forms compare launches of one plan
-        p1, p0 = (fwd.plan(fwd.model_config(model), t, rows) for t in (1, 0))
+        p1, p0 = (fwd.fwd_plan(fwd.model_config(model), t, rows) for t in (1, 0))
         assert (p1["which"], p1["rb"]) == (p0["which"], p0["rb"]) and rows in fwd.GRID[model]
 
 
@@ -193,7 +194,7 @@ def test_forward_refusals_need_no_gpu():
     assert lib.marl_cnn_fwd_plan(None, 1, 10, C.byref(p)) == -1 and lib.marl_cnn_fwd_plan(C.byref(cfg), 1, 0, C.byref(p)) == -1
     # one channel per group: outside the fused forward - every field 0, and the launch refuses before it reads anything
     refused = fwd.config(([1, 8, 16], [8, 4]), 10, 28, 30)
-    assert fwd.plan(refused, 1, 10) == dict(fused=0, which=0, rb=0, blocks=0, keeps_cols=[0] * 5, writes_image=0)
+    assert fwd.fwd_plan(refused, 1, 10) == dict(fused=0, which=0, rb=0, blocks=0, keeps_cols=[0] * 5, writes_image=0)
     io = CnnFwdIo()
     io.img = io.pos = io.u = 4096  # (aligned non-null addresses)
     io.rows, io.ldu = 10, 144

@@ -1,69 +1,12 @@
 """marl_gemm_plan (include/marl_hip_gemmops.h) on the host: what each matrix-product launcher does with a shape, from
 the planning routine the launcher itself calls, against a restatement of the rules written here from the launchers'
 source and the variant tables of DESIGN 8.x.  No GPU: the library loads without one."""
-import ctypes as C
 import itertools
 
 import pytest
 
+from tests.gemm_cases import DEFAULTS, KINDS, KNOB_SETTINGS, LSTM_ROWS, NT_ROWS, TN_ROWS, _lib, hook, knobs
 from tests.util import CASES, cdiv, plan_witness
-
-KINDS = ("nt", "lstm", "tn", "nt_images", "lstm_images", "tn_images", "tn_images_cell")
-DEFAULTS = {"mfma_split": 1, "g3_tn": 1, "g3_tn_pipe": 1, "nt_xcd": 1, "tn_xcd": 1, "tn_split_waves": 8,
-            "g3_nt_variant": 0, "g3_lstm_variant": 0, "g3_tn_variant": 0}
-# id -> (BM, BN, WM, WN, NST, pipelined); None: the row every other id takes (ids 4, 5, 6 of NT and 7 of LSTM exist
-# in MARL_G3_ABLATE builds only: the default build sends them to that row too)
-NT_ROWS = {1: (256, 128, 4, 2, 4, 0), 2: (128, 128, 2, 2, 3, 0), 7: (64, 64, 2, 2, 4, 0), 11: (128, 64, 4, 2, 3, 0),
-           12: (64, 64, 2, 2, 3, 0), 21: (256, 256, 2, 4, 3, 1), 22: (256, 128, 4, 2, 4, 1), None: (128, 64, 2, 2, 4, 0)}
-LSTM_ROWS = {1: (256, 128, 8, 1, 4, 0), 3: (32, 128, 1, 4, 4, 0), 4: (64, 128, 2, 4, 4, 0), 5: (256, 128, 4, 2, 4, 1),
-             6: (256, 128, 2, 2, 4, 1), None: (128, 128, 4, 1, 3, 0)}
-# id -> (BI, BJ, threads, ring of (BI + BJ) rows x stages); column passes (4) keep the 256 x 256 ring
-TN_ROWS = {1: (256, 128, 512, (384, 4)), 2: (128, 128, 256, (256, 3)), 3: (256, 256, 512, (512, 3)),
-           4: (256, 128, 512, (512, 3))}
-VARIANT_IDS = {"g3_nt_variant": [1, 2, 4, 5, 6, 7, 11, 12, 21, 22, 3, 99],
-               "g3_lstm_variant": [1, 2, 3, 4, 5, 6, 7, 99], "g3_tn_variant": [1, 2, 3, 4, 7]}
-KNOB_SETTINGS = ([{}] + [{k: v} for k, v in (("mfma_split", 0), ("g3_tn", 2), ("g3_tn_pipe", 0), ("nt_xcd", 0),
-                                              ("tn_xcd", 0), ("tn_split_waves", 4))] +
-                 [{k: v} for k, ids in VARIANT_IDS.items() for v in ids])
-
-
-def _lib():
-    from marlclassification_amd import _lib as L
-
-    return L
-
-
-def hook(kind, m, n, k=None, rows=0, has_images=0, variant=0, rc_only=False):
-    L = _lib()
-    out, cnt = L.GemmPlan(), len(m)
-    arr = lambda v: (C.c_int * cnt)(*v)  # noqa: E731
-    rc = L.load().marl_gemm_plan(KINDS.index(kind), cnt, arr(m), arr(n), arr(k) if k else None, rows, has_images,
-                                 variant, C.byref(out))
-    if rc_only:
-        return rc
-    L.check(rc)
-    return out.as_dict()
-
-
-class knobs:
-    """sets knobs through engine.tune, restores the defaults on exit"""
-
-    def __init__(self, setting):
-        self.setting = setting
-
-    def __enter__(self):
-        from marlclassification_amd import engine
-
-        for k, v in self.setting.items():
-            engine.tune(k, v)
-        return {**DEFAULTS, **self.setting}
-
-    def __exit__(self, *exc):
-        from marlclassification_amd import engine
-
-        for k in self.setting:
-            engine.tune(k, DEFAULTS[k])
-
 
 # ---- the rules, restated -------------------------------------------------------------------------------------------
 def blocks128(ms, ns):

@@ -8,6 +8,7 @@ import pytest
 import torch as th
 import torch.nn.functional as F
 
+from tests.cases import _golden_sampler
 from tests.util import Golden
 
 pytestmark = pytest.mark.gpu
@@ -79,23 +80,6 @@ def test_multi_agent_act_step_by_step(device):
         assert o.actions_log_probs.shape == (NA, NB) and o.predictions.shape == (NA, NB, NC)
         assert o.values.shape == (NA, NB)
         obs = env.step(o.actions)
-
-
-def _golden_sampler(g, device):
-    from marlclassification_amd.core import Environment, EpisodeSampler, MultiAgent
-    from marlclassification_amd.fused import EpisodeDraws
-    from marlclassification_amd.networks import ModelsWrapper
-    from marlclassification_amd.networks.vision import MnistCnn
-
-    c = g.cfg
-    model = ModelsWrapper(MnistCnn(c.window), c.n_b, c.n_a, c.n_m, c.n_m_o, c.n_d, 2,
-                          c.nb_action, c.nb_class, c.nlb, c.nla)
-    model.load_state_dict(g.params)
-    model.to(device)
-    sampler = EpisodeSampler(MultiAgent(g.na, model), Environment(c.actions, c.window), g.ns)
-    i = g.inp
-    sampler.fixed_draws = EpisodeDraws(*(t.to(device) for t in (i.pos0, i.h0, i.c0, i.hc0, i.cc0, i.q)))
-    return model, sampler
 
 
 def _reference_loss(out, y, gamma):

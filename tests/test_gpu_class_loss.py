@@ -1,250 +1,45 @@
 """GPU: class weights, label smoothing and step weights of the vote error, and cost-sensitive rewards, in the fused
 loss (marl_class_loss; the option instances of loss_error_kernel / loss_rewards_kernel) - through the three loss
 entries and marl_advantages, the trainer, hipGraph replay and two ranks.  The reference is float64 torch:
-``class_loss.vote_error`` / ``class_loss.rewards`` fed into a restatement of the remaining loss written here (the
-oracle's returns / standardise, the GAE recursion of tests/test_ppo_host.py, ``torch.minimum`` / ``clamp`` and
-``smooth_l1_loss``), as tests/test_gpu_ppo.py does.  Bounds are the project's: 1e-5 (x max(1, |ref|)) for forward
-quantities and scalars, 1e-4 of the tensor's scale for gradients, 2e-3 lr for an Adam update.  Achieved errors go through
-``tests.util.record`` (copied into profiles/class_loss_errors.json after the box run).
+``class_loss.vote_error`` / ``class_loss.rewards`` fed into the restatement of the remaining loss in tests/loss_ref.py
+(the oracle's returns / standardise, its GAE recursion, ``torch.minimum`` / ``clamp`` and ``smooth_l1_loss``), with the
+options ``c`` given.  Bounds are those of tests/parity.py: FWD_TOL 1e-5 (x max(1, |ref|)) for forward quantities and
+scalars, GRAD_TOL 1e-4 of the tensor's scale for gradients, UPDATE_TOL 2e-3 lr for an Adam update.  Achieved errors go
+through its ``Recorder`` (copied into profiles/class_loss_errors.json after the box run).
 
-Shapes: nC = 3 (less than a wave), 45, 70 (a second lane-stride pass with a ragged tail); Na = 1, 3 with Nb = 5, Ns = 3
-(Ns Nb = 15 and Ns R leave partial four-wave blocks); and Na = 16, Nb = 6 (Ns R = 288 > 256: the extra partials of the
-entropy / PPO passes sit where the weighted rewards were)."""
+Shapes (tests/loss_cases.py): nC = 3 (less than a wave), 45, 70 (a second lane-stride pass with a ragged tail); Na = 1, 3
+with Nb = 5, Ns = 3 (Ns Nb = 15 and Ns R leave partial four-wave blocks); and Na = 16, Nb = 6 (Ns R = 288 > 256: the
+extra partials of the entropy / PPO passes sit where the weighted rewards were)."""
 import pytest
 import torch as th
-import torch.nn.functional as F
 
 from marlclassification_amd import class_loss as cl
 from oracle import marl_oracle as mo
-from tests.test_gpu_policy_dist import _engine_episode, _oracle_loop, _sampler, masked_entropy
-from tests.test_gpu_ppo import TWO_EPOCH, assert_clear_of_bounds, clip_mask
-from tests.test_gpu_step_autograd import FWD_TOL, GRAD_TOL, NS, Case, _close
-from tests.test_ppo_host import gae, ratio_deltas
-from tests.util import model_spec, record
+from tests import loss_ref as ref64
+from tests.cases import (NS, TWO_EPOCH, Case, _engine_episode, _golden_sampler, _grads_of, _oracle_loop, _sampler)
+from tests.dp import run_ranks
+from tests.loss_cases import (GAMMA, SHAPES, STEP_W, _engine, _entries, _setting, _trainer_options, all_on,
+                              check_entries, synthetic, weights)
+from tests.loss_ref import assert_clear_of_bounds, under
+from tests.parity import GRAD_TOL, UPDATE_TOL, Recorder
+from tests.parity import close as _close
+from tests.util import model_spec
 
 pytestmark = pytest.mark.gpu
 
-_ERRORS = {}
-UPDATE_TOL = 2 * 1e-3  # (x lr: the bound of tests/test_gpu_ppo.py's update test)
-A2C_SCALARS = ("loss", "path", "error", "critic", "entropy")
-PPO_SCALARS = ("loss", "surrogate", "error", "critic", "entropy", "approx_kl", "clip_frac")
-GAMMA, BETA = 0.97, 0.05
-SHAPES = [(3, 1, 5), (3, 3, 5), (45, 1, 5), (45, 3, 5), (70, 1, 5), (70, 3, 5), (45, 16, 6)]  # (nC, Na, Nb), Ns = 3
-STEP_W = (0.0, 0.5, 2.0)
-
-
-def _record(tag, got, ref, tol):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[class_loss] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    record("class_loss_errors", _ERRORS)
-
-
-def _close_fwd(got, ref, what):
-    _record(what, got, ref, FWD_TOL)
-    err = (got.detach().double().cpu() - ref.detach().double().cpu()).abs().max().item()
-    assert err <= FWD_TOL * max(1.0, ref.abs().max().item()), f"{what}: max err {err:.3e}"
-
-
-def _close_grad(got, ref, what):
-    _record(what, got, ref, GRAD_TOL)
-    _close(got, ref, GRAD_TOL, what)
-
-
-# ---- settings and inputs ------------------------------------------------------------------------------------------
-def weights(nc, seed, zero=None):
-    """fp32 class weights in [0.25, 2.25); ``zero``: a class of weight exactly 0."""
-    w = th.rand(nc, generator=th.Generator().manual_seed(seed)) * 2.0 + 0.25
-    if zero is not None:
-        w[zero] = 0.0
-    return w
-
-
-def all_on(nc, y, ns=NS):
-    """Every option at once; the first image's class has weight exactly 0."""
-    return cl.ClassLoss(nc, ns, weights(nc, 50 + nc, zero=int(y[0])), 0.1, STEP_W[:ns], True)
-
-
-def _engine(nc, na, nb, ns, device, n_act=4):
-    from marlclassification_amd.engine import HipEngine
-
-    actions = [[1, 0], [-1, 0], [0, 1], [0, -1], [0, 0], [2, 2]][:n_act]
-    cfg = mo.OracleConfig("mnist", 6, 32, 32, 8, 12, 8, nc, 48, 48, actions=actions)
-    eng = HipEngine(model_spec(cfg), device)
-    eng.configure(na, nb, ns, (1, 28, 28))
-    return eng
-
-
-def synthetic(nc, na, nb, ns, device, n_act=4, seed=0, gap=None):
-    """Episode outputs with votes from vague to confident (logit scale 1 .. 15 per image); ``gap``: one class of every
-    second image is ``gap`` above the rest - the label on image 0, another class on image 2."""
-    from marlclassification_amd.engine import EpisodeTensors
-
-    gen = th.Generator().manual_seed(1000 + seed + nc * na * nb)
-    scale = th.linspace(1.0, 15.0, nb).view(1, 1, nb, 1)
-    preds = th.randn(ns, na, nb, nc, generator=gen) * scale
-    y = th.randint(nc, (nb,), generator=gen)
-    if gap is not None:
-        for b in range(0, nb, 2):
-            k = int(y[b]) if b % 4 == 0 else (int(y[b]) + 1) % nc
-            preds[:, :, b, k] += gap
-    values = th.randn(ns, na, nb, generator=gen)
-    probs = th.randn(ns, na, nb, n_act, generator=gen).softmax(-1)
-    act = th.randint(n_act, (ns, na, nb), generator=gen)
-    logp = probs.gather(-1, act.unsqueeze(-1)).squeeze(-1).log()
-    host = EpisodeTensors(preds, logp, values, th.zeros(ns, na, nb, 2, dtype=th.int64), act, probs)
-    out = EpisodeTensors(*(t.to(device) for t in (preds, logp, values, host.step_pos, act, probs)))
-    return host, out, y
-
-
-def _leaves(o):
-    return [t.detach().double().cpu().requires_grad_()
-            for t in (o.step_preds, o.step_log_probas, o.step_values, o.step_probs)]
-
-
-# ---- the float64 reference ----------------------------------------------------------------------------------------
-def _t(v):
-    return None if v is None else th.tensor(v, dtype=th.float64)
-
-
-def ref_error(preds, y, c):
-    """[Ns, 1, Nb], as the reference's error term broadcasts over the agents."""
-    return cl.vote_error(preds, y, _t(c.class_weights), c.label_smoothing, _t(c.step_weights)).unsqueeze(1)
-
-
-def ref_rewards(preds, y, c):
-    return cl.rewards(preds.detach(), y, _t(c.class_weights) if c.weight_rewards else None)
-
-
-def ref_a2c(preds, logp, values, probs, y, gamma, beta, c):
-    """training/trainer.py:76-111 with the vote error and the rewards of ``c``; returns (loss, scalars[5])."""
-    error = ref_error(preds, y, c)
-    returns = mo.discounted_returns(ref_rewards(preds, y, c), gamma)
-    adv = mo.standardize(returns - values.detach())
-    path = -logp * adv
-    critic = F.smooth_l1_loss(values, returns, reduction="none")
-    ent = masked_entropy(probs) if beta > 0 else th.zeros_like(logp)
-    loss = th.sum(path + error + critic, 0).mean() - beta * ent.sum(0).mean()
-    return loss, th.stack([loss, path.sum(0).mean(), error.mean(), critic.sum(0).mean(), ent.mean()]).detach()
-
-
-def ref_advantages(preds, values, y, gamma, lam, c):
-    adv, ret = gae(ref_rewards(preds, y, c), values.detach(), gamma, lam)
-    return mo.standardize(adv), ret
-
-
-def ref_ppo(preds, logp, values, probs, y, old_logp, advn, ret, eps, beta, c):
-    error = ref_error(preds, y, c)
-    rho = (logp - old_logp).exp()
-    surr = -th.minimum(rho * advn, rho.clamp(1 - eps, 1 + eps) * advn)
-    critic = F.smooth_l1_loss(values, ret, reduction="none")
-    ent = masked_entropy(probs) if beta > 0 else th.zeros_like(logp)
-    loss = th.sum(surr + error + critic, 0).mean() - beta * ent.sum(0).mean()
-    clipped = clip_mask(rho.detach(), advn, eps)
-    scalars = th.stack([loss, surr.sum(0).mean(), error.mean(), critic.sum(0).mean(), ent.mean(),
-                        (old_logp - logp).mean(), clipped.double().mean()]).detach()
-    return loss, scalars, rho.detach()
-
-
-class under:
-    """``with under(eng, c):`` - the engine's loss calls run under ``c`` (None: nothing installed)."""
-
-    def __init__(self, eng, c):
-        self.eng, self.c = eng, c
-
-    def __enter__(self):
-        self.eng.set_class_loss(self.c)
-
-    def __exit__(self, *exc):
-        self.eng.set_class_loss(None)
+REC = Recorder("class_loss_errors", "class_loss")
 
 
 # ---- one setting through every entry ------------------------------------------------------------------------------
 def check_all_entries(eng, out, y, c, tag, device):
     with under(eng, c):
-        return _check_all_entries(eng, out, y, c, tag, device)
-
-
-def _check_all_entries(eng, out, y, c, tag, device):
-    """a2c_loss (plain and entropy entry), advantages (lambda 1 and 0.9), ppo_loss (without and with the bonus) under
-    ``c`` against float64; phases 1 + 2 against phase 0 and a second run, bit for bit.  Returns the cloned buffers."""
-    yd = y.to(device)
-    kept = {}
-    for beta in (0.0, BETA):
-        bufs = [t.clone() for t in eng.a2c_loss(out, yd, GAMMA, entropy_coef=beta)]
-        lv = _leaves(out)
-        loss, ref_scalars = ref_a2c(*lv, y, GAMMA, beta, c)
-        loss.backward()
-        for j, what in enumerate(A2C_SCALARS[:bufs[3].numel()]):
-            _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/a2c/beta{beta}/scalar_{what}")
-        grads = [bufs[0], bufs[1], bufs[2]] + ([bufs[5]] if beta > 0 else [])
-        for got, leaf, what in zip(grads, lv, ("g_preds", "g_logp", "g_values", "g_probs")):
-            _close_grad(got, leaf.grad, f"{tag}/a2c/beta{beta}/{what}")
-        assert all(bool(th.isfinite(t).all()) for t in bufs)
-        two = eng.new_loss_bufs(out, beta > 0)
-        eng.a2c_loss(out, yd, GAMMA, 1, two, entropy_coef=beta)
-        eng.a2c_loss(out, yd, GAMMA, 2, two, entropy_coef=beta)
-        again = eng.a2c_loss(out, yd, GAMMA, entropy_coef=beta)
-        for a, b, d in zip(bufs, two, again):
-            assert th.equal(a, b), "a2c_loss: phases 1 + 2 differ from phase 0"
-            assert th.equal(a, d), "a2c_loss: two runs differ"
-        kept[f"a2c{beta}"] = bufs
-    for lam in (1.0, 0.9):
-        adv = [t.clone() for t in eng.advantages(out, yd, GAMMA, lam)]
-        advn64, ret64 = ref_advantages(out.step_preds.double().cpu(), out.step_values.double().cpu(), y, GAMMA, lam, c)
-        _close_fwd(adv[5], advn64, f"{tag}/lam{lam}/advn")
-        _close_fwd(adv[6], ret64, f"{tag}/lam{lam}/ret")
-        two = eng.new_ppo_bufs(out, True)
-        eng.advantages(out, yd, GAMMA, lam, 1, two)
-        eng.advantages(out, yd, GAMMA, lam, 2, two)
-        again = eng.advantages(out, yd, GAMMA, lam)
-        for j in (4, 5, 6):
-            assert th.equal(adv[j], two[j]), "advantages: phases 1 + 2 differ from phase 0"
-            assert th.equal(adv[j], again[j]), "advantages: two runs differ"
-        kept[f"adv{lam}"] = adv
-    advn, ret = kept["adv0.9"][5], kept["adv0.9"][6]
-    old_logp = out.step_log_probas - ratio_deltas(out.step_log_probas.shape).float().to(device)
-    eps = 0.1
-    for beta in (0.0, BETA):
-        bufs = [t.clone() for t in eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)]
-        lv = _leaves(out)
-        loss, ref_scalars, rho = ref_ppo(*lv, y, old_logp.double().cpu(), advn.double().cpu(), ret.double().cpu(),
-                                         eps, beta, c)
-        assert_clear_of_bounds(rho, eps)
-        loss.backward()
-        for j, what in enumerate(PPO_SCALARS):
-            _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/ppo/beta{beta}/scalar_{what}")
-        grads = [bufs[0], bufs[1], bufs[2]] + ([bufs[7]] if beta > 0 else [])
-        for got, leaf, what in zip(grads, lv, ("g_preds", "g_logp", "g_values", "g_probs")):
-            _close_grad(got, leaf.grad, f"{tag}/ppo/beta{beta}/{what}")
-        again = eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)
-        for j in (0, 1, 2, 3) + ((7,) if beta > 0 else ()):
-            assert th.equal(bufs[j], again[j]), "ppo_loss: two runs differ"
-        kept[f"ppo{beta}"] = bufs
-    return kept
+        return check_entries(REC, eng, out, y, c, None, tag, device)
 
 
 def plain_entries(eng, out, y, device, c=None):
     """The outputs of every entry (cloned) with ``c`` installed - None: nothing installed."""
     with under(eng, c):
         return _entries(eng, out, y, device)
-
-
-def _entries(eng, out, y, device):
-    yd = y.to(device)
-    res = []
-    for beta in (0.0, BETA):
-        res += [t.clone() for t in eng.a2c_loss(out, yd, GAMMA, entropy_coef=beta)]
-    for lam in (1.0, 0.9):
-        adv = eng.advantages(out, yd, GAMMA, lam)
-        res += [adv[j].clone() for j in (4, 5, 6)]
-    advn, ret = res[-2], res[-1]
-    old_logp = out.step_log_probas - ratio_deltas(out.step_log_probas.shape).float().to(device)
-    for beta in (0.0, BETA):
-        bufs = eng.ppo_loss(out, yd, old_logp, advn, ret, 0.1, entropy_coef=beta)
-        res += [bufs[j].clone() for j in (0, 1, 2, 3) + ((7,) if beta > 0 else ())]
-    return res
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -378,37 +173,6 @@ def test_defaults_launch_what_they_launched_before_any_setting(device, pristine)
 
 
 # ---- 6: through the trainer ---------------------------------------------------------------------------------------
-def _trainer_options(k, y):
-    return dict(class_weights=weights(k.cfg.nb_class, 21, zero=int(y[0])).tolist(), label_smoothing=0.1,
-                error_step_weights="last:2", weight_rewards=True)
-
-
-def _setting(k, opts):
-    return cl.from_options(k.cfg.nb_class, NS, **opts)
-
-
-def _check_update(tag, k, model, after, grad_sets, lr):
-    sd = model.state_dict()
-    worst = 0.0
-    for n in k.params:
-        ref_upd = after[n] - k.params[n].double()
-        upd = sd[n].double().cpu() - k.params[n].double()
-        big = th.ones_like(upd, dtype=th.bool)
-        for g in grad_sets:
-            big &= g[n].abs() > 1e-6
-        if big.any():
-            err = (upd[big] - ref_upd[big]).abs().max().item()
-            worst = max(worst, err)
-            assert err <= UPDATE_TOL * lr, f"{n}: {err:.3e}"
-    _ERRORS[f"{tag}/update"] = {"max_err": worst, "tol": UPDATE_TOL * lr}
-    print(f"[class_loss] {tag}/update: max err {worst:.3e} (bound {UPDATE_TOL * lr:.1e})")
-    record("class_loss_errors", _ERRORS)
-
-
-def _grads_of(p):
-    return {n: (v.grad if v.grad is not None else th.zeros_like(v)) for n, v in p.items()}
-
-
 def test_train_step_matches_the_float64_oracle_update(device):
     from marlclassification_amd.training import Trainer
 
@@ -424,15 +188,15 @@ def test_train_step_matches_the_float64_oracle_update(device):
 
     p64 = k.params64()
     tr = _oracle_loop(k, p64, k.img.double())
-    loss, scalars = ref_a2c(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, gamma, beta, _setting(k, opts))
+    loss, scalars = ref64.a2c(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, gamma, beta, _setting(k, opts))
     loss.backward()
-    _close_fwd(th.tensor(m["loss"]), scalars[0], "trainer/a2c/loss")
-    _close_fwd(th.tensor(m["error"]), scalars[2], "trainer/a2c/error")
+    REC.fwd("trainer/a2c/loss", th.tensor(m["loss"]), scalars[0])
+    REC.fwd("trainer/a2c/error", th.tensor(m["error"]), scalars[2])
     grads = _grads_of(p64)
     after = {n: v.detach().clone() for n, v in p64.items()}
     mo.adam_step(after, grads, {n: th.zeros_like(v) for n, v in after.items()},
                  {n: th.zeros_like(v) for n, v in after.items()}, 1, lr)
-    _check_update("trainer/a2c", k, model, after, [grads], lr)
+    REC.check_update("trainer/a2c", k, model, after, [grads], lr)
 
     # the plain trainer moves the weights elsewhere: the options reached the update
     plain = k.model(device)
@@ -454,9 +218,9 @@ def test_two_ppo_epochs_match_the_float64_oracle_update(device):
     p = k.params64()
     img64 = k.img.double()
     tr = _oracle_loop(k, p, img64)
-    advn, ret = ref_advantages(tr["preds"], tr["values"], y, gamma, lam, c)
+    advn, ret, _ = ref64.advantages(tr["preds"], tr["values"], y, gamma, lam, c)
     old_logp = tr["logp"].detach()
-    loss, _, _ = ref_ppo(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, old_logp, advn, ret, eps, beta, c)
+    loss = ref64.ppo(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, old_logp, advn, ret, eps, beta, c)[0]
     loss.backward()
     g1 = _grads_of(p)
     after = {n: v.detach().clone() for n, v in p.items()}
@@ -465,8 +229,8 @@ def test_two_ppo_epochs_match_the_float64_oracle_update(device):
     mo.adam_step(after, g1, m1, v1, 1, lr)
     p2 = {n: v.clone().requires_grad_() for n, v in after.items()}
     tr2 = _oracle_loop(k, p2, img64, forced=tr["act"])
-    loss2, sc2, rho = ref_ppo(tr2["preds"], tr2["logp"], tr2["values"], tr2["probs"], y, old_logp, advn, ret, eps,
-                              beta, c)
+    loss2, sc2, rho, _ = ref64.ppo(tr2["preds"], tr2["logp"], tr2["values"], tr2["probs"], y, old_logp, advn, ret, eps,
+                                   beta, c)
     assert_clear_of_bounds(rho, eps)
     frac_ref = sc2[6].item()
     assert 0.0 < frac_ref < 1.0, "the reference must clip some entries in the second epoch, not all"
@@ -482,9 +246,9 @@ def test_two_ppo_epochs_match_the_float64_oracle_update(device):
     assert model.flat_state().step == 2
     m = trainer.metrics()
     assert m["clip_frac"] == th.tensor(frac_ref, dtype=th.float64).float().item()
-    _close_fwd(th.tensor(m["error"]), sc2[2], "trainer/ppo/error")
-    _close_fwd(th.tensor(m["loss"]), sc2[0], "trainer/ppo/loss")
-    _check_update("trainer/ppo", k, model, after, [g1, g2], lr)
+    REC.fwd("trainer/ppo/error", th.tensor(m["error"]), sc2[2])
+    REC.fwd("trainer/ppo/loss", th.tensor(m["loss"]), sc2[0])
+    REC.check_update("trainer/ppo", k, model, after, [g1, g2], lr)
 
 
 def test_fused_iteration_is_the_trainers_step(device):
@@ -595,7 +359,6 @@ def _dp_worker(rank, world, port, out_q):
     from marlclassification_amd.fused import EpisodeDraws
     from marlclassification_amd.parallel import GradAllReduce, broadcast_parameters, shard_bounds
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
     from tests.util import Golden
 
     device = th.device("cuda:0")  # both ranks share the one GPU of the test box
@@ -626,23 +389,10 @@ def test_two_ranks_take_the_big_batch_update(device):
     big-batch one, so the reference is the single-process trainer on the whole batch under the same options - itself
     held to float64 by the trainer tests above; the two differ by fp32 summation order only, far inside the gradient
     and update bounds."""
-    import torch.multiprocessing as mp
-
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
-    from tests.test_gpu_round2 import _free_port
     from tests.util import Golden
 
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    sd, flat_grads = q.get(timeout=600)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    (sd, flat_grads), = run_ranks(_dp_worker, 2)
     sd = {n: th.from_numpy(v) for n, v in sd.items()}
     flat_grads = th.from_numpy(flat_grads)
 
@@ -664,8 +414,7 @@ def test_two_ranks_take_the_big_batch_update(device):
         moved = moved or bool((upd != 0).any())
         assert err <= UPDATE_TOL * g.lr, f"{n}: {err:.3e}"
     assert moved
-    _ERRORS["two_ranks/update"] = {"max_err": worst, "tol": UPDATE_TOL * g.lr}
-    record("class_loss_errors", _ERRORS)
+    REC.put("two_ranks/update", {"max_err": worst, "tol": UPDATE_TOL * g.lr})
 
 
 # ---- 8: guards ------------------------------------------------------------------------------------------------------

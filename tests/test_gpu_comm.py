@@ -1,11 +1,11 @@
 """GPU: communication graphs - a mixing matrix through the fused episode, the step API, the trainers and the
 captured graph (``ModelsWrapper.set_comm``, ``marl_comm_matrix``, ``mix_msg_kernel``).
 
-The float64 reference is the oracle's step loop (tests/test_gpu_policy_dist.py::_oracle_loop) with
+The float64 reference is the oracle's step loop (tests/cases.py::_oracle_loop) with
 ``marl_oracle.aggregate_messages`` replaced by ``einsum(M64, m)``: ``step_forward`` looks the function up at call
 time.  Every comparison with it is teacher-forced (the oracle's actions are passed as ``forced``), so no case
 depends on a sampled action.  Tolerances are the project's: outputs 1e-5 absolute (x max(1, |ref|)), gradients 1e-4
-of the tensor's scale, Adam update 1e-3 * lr per update.  Achieved errors go through ``tests.util.record``
+of the tensor's scale, Adam update 1e-3 * lr per update (tests/parity.py).  Achieved errors go through its ``Recorder``
 (``comm_errors``)."""
 import os
 import subprocess
@@ -16,57 +16,18 @@ import torch as th
 
 from marlclassification_amd import comm
 from oracle import marl_oracle as mo
-from tests import util
-from tests.test_gpu_policy_dist import _dist_loss, _oracle_loop, _sampler
-from tests.test_gpu_step_autograd import CASES as STEP_CASES
-from tests.test_gpu_step_autograd import FWD_TOL, GRAD_TOL, NS, Case, _a2c_like_loss, _act_loop, _close, _loss_terms
-from tests.util import record, uniform_params
+from tests.cases import (NS, TWO_EPOCH, TWO_EPOCH_EPS, CommCase, _a2c_like_loss, _act_loop, _case_with_loss, _dist_loss,
+                         _family, _force, _loss_terms, _oracle_loop, _replay, _run, _sampler, _unroll, _unroll_inputs,
+                         _y, dense, graph, two_epoch_reference)
+from tests.loss_ref import assert_clear_of_bounds
+from tests.parity import GRAD_TOL, Recorder
+from tests.parity import close as _close
 
 pytestmark = pytest.mark.gpu
 
-_ERRORS = {}
-
-# name -> (config, Na, Nb, image [C, H, W], seed); "g1" is the g1_conftest fixture (Na = 5, odd dimensions)
-EXTRA = {
-    "g2": (util.CASES["g2_mnist_c1"], 3, 6, (1, 28, 28), 21),
-    "resisc16": (util.CASES["g4_resisc_b2"], 16, 2, (3, 48, 48), 22),
-}
+REC = Recorder("comm_errors", "comm", _family())  # (a child process of another kernel family keeps a record of its own)
 SHAPES = ("g1", "g2", "resisc16")
 GRAPHS = ("ring", "star", "none", "teams", "dense")
-
-
-class CommCase(Case):
-    def __init__(self, name):
-        if name in STEP_CASES:
-            super().__init__(name)
-            return
-        self.cfg, self.na, self.nb, shape, seed = EXTRA[name]
-        self.params = uniform_params(self.cfg, seed)
-        self.img = th.rand(self.nb, *shape, generator=th.Generator().manual_seed(seed))
-        self.inp = mo.draw_episode_inputs(self.cfg, self.na, self.nb, NS, list(shape[1:]), seed)
-        self.gen = th.Generator().manual_seed(seed + 1000)
-        self.sizes = list(self.img.shape[2:])
-
-
-def dense(na, seed=5):
-    """Seeded dense asymmetric matrix with self-loops and (at least) one negative entry."""
-    m = th.randn(na, na, generator=th.Generator().manual_seed(seed)) / max(1.0, na ** 0.5)
-    m[0, na - 1] = -abs(m[0, na - 1]) - 0.1
-    m[na - 1, 0] = abs(m[na - 1, 0]) + 0.2
-    assert not th.equal(m, m.t()) and (m.diagonal() != 0).all() and (m < 0).any()
-    return m
-
-
-def graph(name, na):
-    if name == "ring":
-        return comm.ring(na, 1)
-    if name == "star":
-        return comm.star(na, na // 2)
-    if name == "none":
-        return comm.none(na)
-    if name == "teams":
-        return comm.teams([2, na - 2]) if na > 2 else comm.teams([1] * na)
-    return dense(na)
 
 
 @pytest.fixture
@@ -76,57 +37,6 @@ def oracle_comm(monkeypatch):
         m64 = m.double().cpu()
         monkeypatch.setattr(mo, "aggregate_messages", lambda msg: th.einsum("ac,cbk->abk", m64.to(msg.dtype), msg))
     return use
-
-
-def _save():
-    fam = _family()  # (a child process of another kernel family keeps a record of its own)
-    record("comm_errors" if fam == "default" else f"comm_errors_{fam}", _ERRORS)
-
-
-def _rec(tag, got, ref, tol):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[comm] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    _save()
-    return err, scale
-
-
-def _fwd(tag, got, ref):
-    err, scale = _rec(tag, got, ref, FWD_TOL)
-    assert err <= FWD_TOL * max(1.0, scale), f"{tag}: max err {err:.3e}"
-
-
-def _grad(tag, got, ref):
-    _rec(tag, got, ref, GRAD_TOL)
-    _close(got, ref, GRAD_TOL, tag)
-
-
-def _param_grads(tag, model, p64):
-    worst, where = 0.0, ""
-    for n, p in model.named_parameters():
-        ref = p64[n].grad
-        if p.grad is not None and ref is not None and ref.abs().max().item() > 0.0:
-            rel = (p.grad.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
-            if rel >= worst:
-                worst, where = rel, n
-    _ERRORS[tag] = {"worst_err_over_ref_max": worst, "param": where, "tol": GRAD_TOL}
-    print(f"[comm] {tag}: worst err / ref max {worst:.3e} ({where})")
-    _save()
-    for n, p in model.named_parameters():
-        assert p.grad is not None, f"{n}: no gradient"
-        _close(p.grad, p64[n].grad, GRAD_TOL, f"{tag}/{n}")
-
-
-def _replay(sampler, actions, device):
-    from marlclassification_amd.core.episode import Trajectory
-
-    return Trajectory(sampler.fixed_draws, actions.to(device))
-
-
-def _family():
-    return "panels0" if os.environ.get("MARL_PANELS") == "0" else (
-        "chain0" if os.environ.get("MARL_PANEL_CHAIN") == "0" else "default")
 
 
 # ---- 1: parity with the float64 oracle ---------------------------------------------------------------------------
@@ -147,10 +57,10 @@ def _parity(k, m, device, oracle_comm, tag):
     assert th.equal(ep.step_actions.cpu(), tr["act"]) and th.equal(ep.step_pos.cpu(), tr["pos"])
     for key, got in (("preds", ep.step_preds), ("logp", ep.step_log_probas), ("values", ep.step_values),
                      ("probs", ep.step_probs)):
-        _fwd(f"{tag}/{key}", got, tr[key])
+        REC.fwd(f"{tag}/{key}", got, tr[key])
     _dist_loss(ep.step_preds, ep.step_log_probas, ep.step_values, ep.step_probs, terms, w).backward()
-    _param_grads(f"{tag}/params", model, p64)
-    _grad(f"{tag}/d_img", img.grad, img64.grad)
+    REC.param_grads(f"{tag}/params", model, p64)
+    REC.grad(f"{tag}/d_img", img.grad, img64.grad)
     eng = model.hip_engine(k.cfg.actions)
     assert eng.plan_query("comm") == 1
     # (every shape of this file is inside the chained panel launch's range: mixed in the panel by default, by
@@ -186,28 +96,6 @@ def test_parity_in_the_other_kernel_families(device, env):
 
 
 # ---- 2: the default path is untouched ----------------------------------------------------------------------------
-def _run(k, model, device, actions=None):
-    sampler = _sampler(k, model, device)
-    img = k.img.to(device).requires_grad_()
-    replay = None if actions is None else _replay(sampler, actions, device)
-    ep = sampler.run_episode(img, replay=replay)
-    _dist_loss(ep.step_preds, ep.step_log_probas, ep.step_values, ep.step_probs, k.terms, k.w).backward()
-    res = {"preds": ep.step_preds.detach().clone(), "logp": ep.step_log_probas.detach().clone(),
-           "values": ep.step_values.detach().clone(), "probs": ep.step_probs.detach().clone(),
-           "act": ep.step_actions.clone(), "d_img": img.grad.clone()}
-    res.update({n: p.grad.clone() for n, p in model.named_parameters()})
-    model.zero_grad(set_to_none=True)
-    return res
-
-
-def _case_with_loss(name):
-    k = CommCase(name)
-    k.name = name
-    k.terms = _loss_terms(k)
-    k.w = k.randn(NS, k.na, k.nb, k.cfg.nb_action)
-    return k
-
-
 @pytest.mark.parametrize("shape", ["g1", "resisc16"])
 def test_default_path_is_bit_equal_after_a_matrix_was_set_and_cleared(device, shape):
     k = _case_with_loss(shape)
@@ -232,45 +120,13 @@ def test_full_graph_agrees_with_the_default_path(device, shape):
     model.set_comm(comm.full(k.na).to(device))
     got = _run(k, model, device, ref["act"])
     for key in ("preds", "logp", "values", "probs"):
-        _fwd(f"full/{shape}/{key}", got[key], ref[key])
+        REC.fwd(f"full/{shape}/{key}", got[key], ref[key])
     for key in ref:
         if key not in ("preds", "logp", "values", "probs", "act"):
-            _grad(f"full/{shape}/{key}", got[key], ref[key])
+            REC.grad(f"full/{shape}/{key}", got[key], ref[key])
 
 
 # ---- 4: isolation, bit for bit -----------------------------------------------------------------------------------
-def _unroll(k, model, device, obs, npos, st0, ws):
-    """ModelsWrapper.forward over NS steps, message and state chained, every output in the loss; returns the
-    outputs and the gradients of the initial state / message."""
-    from marlclassification_amd.networks.models import RecurrentOutput
-
-    leaves = [t.to(device).requires_grad_() for t in st0]
-    h, cst, hc, cc, msg = leaves
-    rec = RecurrentOutput(h, cst, hc, cc)
-    loss, outs = 0.0, []
-    for t in range(NS):
-        out, rec = model(obs[t].to(device), msg, npos[t].to(device), rec)
-        msg = out.messages
-        o = (out.actions_probabilities, out.values, out.predictions, out.messages, rec.h, rec.c, rec.h_caret,
-             rec.c_caret)
-        outs.append(o)
-        loss = loss + sum((w.to(device) * x).sum() for w, x in zip(ws[t], o))
-    loss.backward()
-    return outs, [g.grad for g in leaves]
-
-
-def _unroll_inputs(k):
-    c, na, nb = k.cfg, k.na, k.nb
-    pos = [th.stack([th.randint(s - c.window, (na, nb), generator=k.gen) for s in k.sizes], -1) for _ in range(NS)]
-    obs = [mo.crop_patches(k.img, p, c.window) for p in pos]
-    npos = [mo.normalized_positions(p, k.sizes) for p in pos]
-    i = k.inp
-    st0 = [i.h0, i.c0, i.hc0, i.cc0, 0.5 * k.randn(na, nb, c.n_m)]
-    widths = [c.nb_action, None, c.nb_class, c.n_m, c.n_b, c.n_b, c.n_a, c.n_a]
-    ws = [[k.randn(na, nb, w) if w else k.randn(na, nb) for w in widths] for _ in range(NS)]
-    return obs, npos, st0, ws
-
-
 @pytest.mark.parametrize("shape", ["g1", "resisc16"])
 def test_teams_are_isolated_bit_for_bit(device, shape):
     """teams([k, Na - k]): whatever only team B sees (its initial state and message, its observations / the image
@@ -362,7 +218,7 @@ def test_act_loop_under_a_matrix_agrees_with_the_fused_node(device, shape):
     out = _act_loop(k, model, device)
     assert th.equal(out["pos"], ep.step_pos), "the act loop moved otherwise than the episode"
     for key, ref in (("preds", ep.step_preds), ("logp", ep.step_log_probas), ("values", ep.step_values)):
-        _fwd(f"act_loop/{shape}/{key}", out[key], ref)
+        REC.fwd(f"act_loop/{shape}/{key}", out[key], ref)
     _a2c_like_loss(out["preds"], out["logp"], out["values"], k.terms).backward()
     for n, p in model.named_parameters():
         _close(p.grad, g_ep[n], GRAD_TOL, n)
@@ -388,47 +244,17 @@ def test_carried_message_gradient_goes_through_the_transpose(device, oracle_comm
         h, cst, hc, cc, msg = so.h, so.c, so.hc, so.cc, so.msg
         o = (so.probs, so.values, so.preds, so.msg, so.h, so.c, so.hc, so.cc)
         for j, (g, r) in enumerate(zip(outs[t], o)):
-            _fwd(f"unroll/{shape}/step{t}/out{j}", g, r)
+            REC.fwd(f"unroll/{shape}/step{t}/out{j}", g, r)
         loss64 = loss64 + sum((w.double() * x).sum() for w, x in zip(ws[t], o))
     loss64.backward()
-    _param_grads(f"unroll/{shape}/params", model, p64)
+    REC.param_grads(f"unroll/{shape}/params", model, p64)
     for n, g, r in zip(("h0", "c0", "hc0", "cc0", "msg0"), grads, leaves64):
-        _grad(f"unroll/{shape}/d_{n}", g, r.grad)
+        REC.grad(f"unroll/{shape}/d_{n}", g, r.grad)
     # (the test can see a missing transpose: M and M^T differ by far more than the tolerance)
     assert (m - m.t()).abs().max().item() > 0.1
 
 
 # ---- 6: trainers -------------------------------------------------------------------------------------------------
-def _force(sampler, actions, device):
-    """Teacher-forces the trainer's rollouts: run_episode_raw with the fixed draws and the oracle's actions."""
-    raw = sampler.run_episode_raw
-    forced = actions.to(device)
-
-    def run(x, train, draws=None, probs=False, forced_=None, **kw):
-        f = kw.get("forced", forced_)
-        return raw(x, train, draws=sampler.fixed_draws if draws is None else draws, probs=probs,
-                   forced=forced if f is None else f)
-    sampler.run_episode_raw = run
-
-
-def _updates_match(tag, k, model, after, grads_list, lr, n_updates):
-    sd = model.state_dict()
-    worst, bound = 0.0, n_updates * 1e-3 * lr
-    for n in k.params:
-        ref_upd = after[n] - k.params[n].double()
-        upd = sd[n].double().cpu() - k.params[n].double()
-        big = th.ones_like(ref_upd, dtype=th.bool)
-        for g in grads_list:  # (Adam's sign-like first update amplifies a gradient that is zero up to rounding)
-            big &= g[n].abs() > 1e-6
-        if big.any():
-            err = (upd[big] - ref_upd[big]).abs().max().item()
-            worst = max(worst, err)
-            assert err <= bound, f"{n}: {err:.3e}"
-    _ERRORS[tag] = {"max_err": worst, "tol": bound}
-    print(f"[comm] {tag}: max err {worst:.3e} (bound {bound:.1e})")
-    _save()
-
-
 @pytest.mark.parametrize("shape", ["g1", "resisc16"])
 def test_train_step_with_a_ring_matches_the_float64_adam_update(device, oracle_comm, shape):
     from marlclassification_amd.training import Trainer
@@ -454,14 +280,13 @@ def test_train_step_with_a_ring_matches_the_float64_adam_update(device, oracle_c
     trainer = Trainer(model, k.cfg.nb_class, lr, gamma)
     out, scalars = trainer.train_step(k.img, y, sampler)
     assert th.equal(out.step_actions.cpu(), tr["act"])
-    _fwd(f"train_step/{shape}/preds", out.step_preds, tr["preds"])
-    _fwd(f"train_step/{shape}/loss", scalars[0], lo.loss)
-    _updates_match(f"train_step/{shape}/update", k, model, after, [g], lr, 1)
+    REC.fwd(f"train_step/{shape}/preds", out.step_preds, tr["preds"])
+    REC.fwd(f"train_step/{shape}/loss", scalars[0], lo.loss)
+    REC.updates_match(f"train_step/{shape}/update", k, model, after, [g], lr, 1)
 
 
 def test_two_ppo_epochs_with_a_matrix_match_the_float64_oracle(device, oracle_comm):
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_ppo import TWO_EPOCH, TWO_EPOCH_EPS, _y, assert_clear_of_bounds, two_epoch_reference
 
     k = CommCase("g1")
     m = dense(k.na)
@@ -479,8 +304,8 @@ def test_two_ppo_epochs_with_a_matrix_match_the_float64_oracle(device, oracle_co
     trainer.train_epoch([(k.img, y)], 0, sampler)
     assert trainer.curr_step == 1 and model.flat_state().step == 2
     mt = trainer.metrics()
-    _fwd("ppo/g1/approx_kl", th.tensor(mt["approx_kl"]), ref["scalars2"][5])
-    _updates_match("ppo/g1/update", k, model, ref["after"], [ref["g1"], ref["g2"]], lr, 2)
+    REC.fwd("ppo/g1/approx_kl", th.tensor(mt["approx_kl"]), ref["scalars2"][5])
+    REC.updates_match("ppo/g1/update", k, model, ref["after"], [ref["g1"], ref["g2"]], lr, 2)
 
 
 def test_graph_replay_equals_eager_under_a_matrix(device):

@@ -1,10 +1,10 @@
 """GPU: the gradient with respect to the mixing matrix (``marl_comm_grad``) - through the fused episode node, the step
 nodes, ``comm.LearnableComm``, the trainers (``comm_lr``), PPO replay and two data-parallel ranks.
 
-The float64 reference is the oracle's step loop (tests/test_gpu_policy_dist.py::_oracle_loop) with
+The float64 reference is the oracle's step loop (tests/cases.py::_oracle_loop) with
 ``marl_oracle.aggregate_messages`` replaced by ``einsum(M64.requires_grad_(), m)``, teacher-forced: autograd's
 ``M64.grad`` is what ``d_comm`` must be.  Tolerances are the project's: gradients ``GRAD_TOL`` = 1e-4 of the tensor's
-scale (here max |dM|), Adam updates 1e-3 * lr per update.  Achieved errors go through ``tests.util.record``
+scale (here max |dM|), Adam updates 1e-3 * lr per update (tests/parity.py).  Achieved errors go through its ``Recorder``
 (``comm_grad_errors``)."""
 import os
 import subprocess
@@ -15,16 +15,20 @@ import torch as th
 
 from marlclassification_amd import comm
 from oracle import marl_oracle as mo
-from tests.test_gpu_comm import (CommCase, _case_with_loss, _family, _force, _replay, _run, _unroll, _unroll_inputs,
-                                 dense, graph)
-from tests.test_gpu_policy_dist import _dist_loss, _oracle_loop, _sampler
-from tests.test_gpu_step_autograd import GRAD_TOL, NS, _a2c_like_loss, _act_loop, _close, _loss_terms
+from tests import loss_ref as ref64
 from tests import util
-from tests.util import record, uniform_params
+from tests.cases import (NS, TWO_EPOCH, TWO_EPOCH_EPS, CommCase, _a2c_like_loss, _act_loop, _case_with_loss, _dist_loss,
+                         _family, _force, _golden_sampler, _grads_of, _loss_terms, _oracle_loop, _replay, _run,
+                         _sampler, _unroll, _unroll_inputs, _y, dense, graph)
+from tests.dp import run_ranks
+from tests.loss_ref import assert_clear_of_bounds
+from tests.parity import GRAD_TOL, Recorder
+from tests.util import uniform_params
 
 pytestmark = pytest.mark.gpu
 
-_ERRORS = {}
+REC = Recorder("comm_grad_errors", "comm_grad", _family())
+REC_COMM = Recorder("comm_errors", "comm", _family())  # (the PPO test's model update: tests/test_gpu_comm.py's record)
 
 GRAPHS = ("ring", "star", "teams", "dense")
 # (shape, graph): Na = 5 / 3 / 16 on the MNIST, RESISC45 and AID shapes, and one agent (a 1 x 1 matrix)
@@ -62,19 +66,9 @@ def _matrix(gname, na):
     return graph(gname, na)
 
 
-def _rec(tag, got, ref, tol=GRAD_TOL):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[comm_grad] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    fam = _family()
-    record("comm_grad_errors" if fam == "default" else f"comm_grad_errors_{fam}", _ERRORS)
-
-
 def _grad(tag, got, ref):
     assert got is not None, f"{tag}: no gradient"
-    _rec(tag, got, ref)
-    _close(got, ref, GRAD_TOL, tag)
+    REC.grad(tag, got, ref)
 
 
 @pytest.fixture
@@ -154,7 +148,7 @@ def test_entries_where_the_matrix_is_zero_carry_the_oracles_gradient(device, ora
     assert zero.any() and (ref0 != 0).all(), "the oracle's gradient is non-zero where M is 0"
     assert (got0 != 0).all()
     err = (got0 - ref0).abs().max().item()
-    _rec(f"dense/{shape}/{gname}", got0, ref0)
+    REC.rec(f"dense/{shape}/{gname}", got0, ref0, GRAD_TOL)
     assert err <= GRAD_TOL * ref.abs().max().item() + 1e-7, f"max err {err:.3e} on the entries where M == 0"
     assert ref0.abs().max().item() > 100 * GRAD_TOL * ref.abs().max().item(), "the zero entries must be visible"
 
@@ -309,9 +303,8 @@ def _logits_match(tag, lc, l0, grads, lr):
     assert big.any()
     err = ((got - l0)[big] - (ref - l0)[big]).abs().max().item()
     bound = len(grads) * 1e-3 * lr
-    _ERRORS[tag] = {"max_err": err, "tol": bound}
     print(f"[comm_grad] {tag}: max err {err:.3e} (bound {bound:.1e})")
-    record("comm_grad_errors", _ERRORS)
+    REC.put(tag, {"max_err": err, "tol": bound})
     assert err <= bound, f"{tag}: {err:.3e}"
     off = ~lc.support.cpu()
     assert th.equal(got[off], l0[off]), "logits off the support must not move"
@@ -356,8 +349,6 @@ def test_train_step_updates_the_logits_like_float64_adam_and_the_model_like_a_co
 
 def test_two_ppo_epochs_with_a_learnable_matrix_match_the_float64_oracle(device, oracle_live):
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_comm import _updates_match
-    from tests.test_gpu_ppo import TWO_EPOCH, TWO_EPOCH_EPS, _y, assert_clear_of_bounds, ref_advantages, ref_ppo
 
     k = CommCase("g1")
     eps = TWO_EPOCH_EPS["g1"]
@@ -374,10 +365,10 @@ def test_two_ppo_epochs_with_a_learnable_matrix_match_the_float64_oracle(device,
     img64 = k.img.double()
     p = k.params64()
     tr = _oracle_loop(k, p, img64)
-    advn, ret, _ = ref_advantages(tr["preds"], tr["values"], y, gamma, lam)
+    advn, ret, _ = ref64.advantages(tr["preds"], tr["values"], y, gamma, lam)
     old_logp = tr["logp"].detach()
-    ref_ppo(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, old_logp, advn, ret, eps, beta)[0].backward()
-    g1 = {n: (v.grad if v.grad is not None else th.zeros_like(v)) for n, v in p.items()}
+    ref64.ppo(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, old_logp, advn, ret, eps, beta)[0].backward()
+    g1 = _grads_of(p)
     gl1 = cur["l"].grad.clone()
     after = {n: v.detach().clone() for n, v in p.items()}
     m1 = {n: th.zeros_like(v) for n, v in after.items()}
@@ -386,11 +377,11 @@ def test_two_ppo_epochs_with_a_learnable_matrix_match_the_float64_oracle(device,
     p2 = {n: v.clone().requires_grad_() for n, v in after.items()}
     cur["l"] = _adam64(l0, [gl1], comm_lr).requires_grad_()  # the matrix is evaluated again for the second epoch
     tr2 = _oracle_loop(k, p2, img64, forced=tr["act"])
-    loss2, _, rho, _ = ref_ppo(tr2["preds"], tr2["logp"], tr2["values"], tr2["probs"], y, old_logp, advn, ret, eps,
+    loss2, _, rho, _ = ref64.ppo(tr2["preds"], tr2["logp"], tr2["values"], tr2["probs"], y, old_logp, advn, ret, eps,
                                beta)
     assert_clear_of_bounds(rho, eps)
     loss2.backward()
-    g2 = {n: (v.grad if v.grad is not None else th.zeros_like(v)) for n, v in p2.items()}
+    g2 = _grads_of(p2)
     gl2 = cur["l"].grad.clone()
     mo.adam_step(after, g2, m1, v1, 2, lr)
 
@@ -403,7 +394,7 @@ def test_two_ppo_epochs_with_a_learnable_matrix_match_the_float64_oracle(device,
                       entropy_coef=beta, comm_lr=comm_lr)
     trainer.train_epoch([(k.img, y)], 0, sampler)
     assert trainer.curr_step == 1 and model.flat_state().step == 2
-    _updates_match("comm_grad/ppo/g1/update", k, model, after, [g1, g2], lr, 2)
+    REC_COMM.updates_match("comm_grad/ppo/g1/update", k, model, after, [g1, g2], lr, 2)
     _logits_match("ppo/g1/logits", lc, l0, [gl1, gl2], comm_lr)
     # (the second epoch ran under the updated matrix: with the first one its gradient would be another)
     assert (gl1 - gl2).abs().max().item() > 1e-6
@@ -420,7 +411,6 @@ def _dp_worker(rank, world, port, out_q):
     from marlclassification_amd.fused import EpisodeDraws
     from marlclassification_amd.parallel import BucketedGradAllReduce, broadcast_parameters, shard_bounds
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
     from tests.util import Golden
 
     device = th.device("cuda:0")  # both ranks share the one GPU of the test box
@@ -451,29 +441,8 @@ def _dp_worker(rank, world, port, out_q):
 
 
 def _spawn(world, ranks):
-    import torch.multiprocessing as mp
-
-    from tests.test_gpu_round2 import _free_port
-
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_dp_worker, args=(r, world, port, q)) for r in ranks]
-    for p in procs:
-        p.start()
-    got = {}
-    try:
-        for _ in ranks:
-            r = q.get(timeout=600)
-            got[r[0]] = r[1:]
-    finally:
-        for p in procs:
-            p.join(timeout=120)
-            if p.is_alive():
-                p.kill()
-    for p in procs:
-        assert p.exitcode == 0
-    return got
+    """{rank: what it put} of the ranks started (world 1: one shard alone, no collective)"""
+    return {r[0]: r[1:] for r in run_ranks(_dp_worker, world, results=len(ranks), ranks=ranks)}
 
 
 def test_two_ranks_take_the_same_logit_update_from_the_averaged_gradient(device):

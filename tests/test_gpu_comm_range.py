@@ -6,14 +6,14 @@ The float64 reference is the oracle's step loop with ``marl_oracle.aggregate_mes
 ``einsum(w, m)`` with the float64 matrices ``w`` of ``range_matrices64`` below (the builder of THIS file, not the
 package's) at the oracle's own positions: step t >= 1 aggregates under the positions at which step t - 1 observed,
 step 0 (the zero message) under the initial ones.  The parity, bit-equality and isolation tests run NS = 4 steps, so
-three gated exchanges carry a message; the trainer tests keep the NS = 3 helpers of tests/test_gpu_comm.py and
-tests/test_gpu_ppo.py.  Every comparison is teacher-forced.  Tolerances are the project's: outputs 1e-5 absolute
+three gated exchanges carry a message; the trainer tests keep the NS = 3 helpers and the two-epoch PPO reference of
+tests/cases.py.  Every comparison is teacher-forced.  Tolerances are the project's: outputs 1e-5 absolute
 (x max(1, |ref|)), gradients 1e-4 of the tensor's scale, Adam update 1e-3 * lr per update.
 
 What a case exercises is asserted from the ORACLE's positions, never from the code under test: in every parity case the
 share of in-range ordered pairs a != a' over the gating steps lies in [0.15, 0.85] (Na = 1 has no pair and is
 exempt), and a case that claims an empty or a complete receiver row has one (``PARITY`` lists the claims; at least one
-case claims each).  Achieved errors go through ``tests.util.record`` (``comm_range_errors``)."""
+case claims each).  Achieved errors go through ``parity.Recorder`` (``comm_range_errors``)."""
 import os
 import subprocess
 import sys
@@ -24,17 +24,18 @@ import torch as th
 
 from marlclassification_amd import comm
 from oracle import marl_oracle as mo
-from tests import util
-from tests.test_gpu_comm import (CommCase, _case_with_loss, _force, _replay, _run, _updates_match, dense, graph)
-from tests.test_gpu_policy_dist import _dist_loss, _oracle_loop, _sampler
-from tests.test_gpu_step_autograd import FWD_TOL, GRAD_TOL, _close
-from tests.test_gpu_step_autograd import NS as NS3
-from tests.util import record
+from tests.cases import NS as NS3
+from tests.cases import NS4 as NS
+from tests.cases import (TWO_EPOCH, TWO_EPOCH_EPS, CommCase, RangeCase, _case_with_loss, _dist_loss, _family, _force,
+                         _grads_of, _oracle_loop, _replay, _run, _run4, _sampler, _y, dense, graph, inputs4,
+                         loss_terms4, sampler4, two_epoch_reference)
+from tests.loss_ref import assert_clear_of_bounds
+from tests.parity import Recorder
 
 pytestmark = pytest.mark.gpu
 
-NS = 4
-_ERRORS = {}
+REC = Recorder("comm_range_errors", "comm_range", _family())
+REC_COMM = Recorder("comm_errors", "comm", _family())  # (the trainer tests' updates: tests/test_gpu_comm.py's record)
 
 
 # ---- the float64 side ----------------------------------------------------------------------------------------------
@@ -62,7 +63,7 @@ def base_of(name, na):
         return name
     if name == "posdense":
         return pos_dense(na)
-    return graph(name, na)  # "ring", and the signed "dense" of tests/test_gpu_comm.py
+    return graph(name, na)  # "ring", and the signed "dense" of tests/cases.py
 
 
 class GatedOracle:
@@ -106,67 +107,6 @@ class GatedOracle:
         return share, bool((rows == 0).any()), bool((rows == na - 1).any())
 
 
-def inputs4(k, seed):
-    """The case's random draws for NS = 4 steps (the fixtures carry three)."""
-    k.inp = mo.draw_episode_inputs(k.cfg, k.na, k.nb, NS, k.sizes, seed)
-    return k
-
-
-def oracle_loop4(k, p64, img64, forced=None):
-    """tests/test_gpu_policy_dist.py::_oracle_loop over NS = 4 steps."""
-    c, i = k.cfg, k.inp
-    table = th.tensor(c.actions)
-    pos = i.pos0
-    h, cst, hc, cc = (t.double() for t in (i.h0, i.c0, i.hc0, i.cc0))
-    msg = th.zeros(k.na, k.nb, c.n_m, dtype=th.float64)
-    acc = {"preds": [], "logp": [], "values": [], "pos": [], "probs": [], "act": []}
-    for t in range(NS):
-        so = mo.step_forward(p64, c, mo.crop_patches(img64, pos, c.window), msg,
-                             mo.normalized_positions(pos, k.sizes).double(), h, cst, hc, cc)
-        h, cst, hc, cc, msg = so.h, so.c, so.hc, so.cc, so.msg
-        a = mo.sample_actions(so.probs, i.q[t].double()) if forced is None else forced[t]
-        logp = th.gather(so.probs, -1, a.unsqueeze(-1)).squeeze(-1).log()
-        pos = mo.transition(pos, a, table, c.window, k.sizes)
-        for key, v in zip(acc, (so.preds, logp, so.values, pos, so.probs, a)):
-            acc[key].append(v)
-    return {key: th.stack(v) for key, v in acc.items()}
-
-
-def sampler4(k, model, device, probs=True):
-    from marlclassification_amd.core import Environment, EpisodeSampler, MultiAgent
-    from marlclassification_amd.fused import EpisodeDraws
-
-    i = k.inp
-    sampler = EpisodeSampler(MultiAgent(k.na, model), Environment(k.cfg.actions, k.cfg.window), NS)
-    sampler.fixed_draws = EpisodeDraws(*(t.to(device) for t in (i.pos0, i.h0, i.c0, i.hc0, i.cc0, i.q[:NS])))
-    sampler.return_probs = probs
-    return sampler
-
-
-def loss_terms4(k):
-    adv = k.randn(NS, k.na, k.nb)
-    y = th.randint(k.cfg.nb_class, (NS, k.na, k.nb), generator=k.gen)
-    return adv, y, k.randn(NS, k.na, k.nb)
-
-
-# ---- cases ---------------------------------------------------------------------------------------------------------
-# "na20": twenty agents - past the chained panel launch (16 rows), so every family takes mix_msg_gated_kernel<32>
-WIDE = {"na20": (util.CASES["g1_conftest"], 20, 3, (1, 28, 28), 23)}
-
-
-class RangeCase(CommCase):
-    def __init__(self, name):
-        if name in WIDE:
-            self.cfg, self.na, self.nb, shape, seed = WIDE[name]
-            self.params = util.uniform_params(self.cfg, seed)
-            self.img = th.rand(self.nb, *shape, generator=th.Generator().manual_seed(seed))
-            self.gen = th.Generator().manual_seed(seed + 1000)
-            self.sizes = list(self.img.shape[2:])
-        else:
-            super().__init__(name)
-        inputs4(self, {"g1": 10, "g2": 21, "resisc16": 22, "na1": 13, "na20": 23}[name])
-
-
 # tag -> (shape, radius, metric, normalize, base, claims an empty receiver row, claims a complete one)
 PARITY = {
     "g1/r6": ("g1", 6, "chebyshev", True, None, True, True),
@@ -179,51 +119,6 @@ PARITY = {
     "resisc16/r24/euclid/posdense": ("resisc16", 24, "euclidean", True, "posdense", False, True),
     "na20/r8/ring": ("na20", 8, "chebyshev", True, "ring", False, False),
 }
-
-
-def _family():
-    return "panels0" if os.environ.get("MARL_PANELS") == "0" else (
-        "chain0" if os.environ.get("MARL_PANEL_CHAIN") == "0" else "default")
-
-
-def _save():
-    fam = _family()  # (a child process of another kernel family keeps a record of its own)
-    record("comm_range_errors" if fam == "default" else f"comm_range_errors_{fam}", _ERRORS)
-
-
-def _rec(tag, got, ref, tol):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[comm_range] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    _save()
-    return err, scale
-
-
-def _fwd(tag, got, ref):
-    err, scale = _rec(tag, got, ref, FWD_TOL)
-    assert err <= FWD_TOL * max(1.0, scale), f"{tag}: max err {err:.3e}"
-
-
-def _grad(tag, got, ref):
-    _rec(tag, got, ref, GRAD_TOL)
-    _close(got, ref, GRAD_TOL, tag)
-
-
-def _param_grads(tag, model, p64):
-    worst, where = 0.0, ""
-    for n, p in model.named_parameters():
-        ref = p64[n].grad
-        if p.grad is not None and ref is not None and ref.abs().max().item() > 0.0:
-            rel = (p.grad.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
-            if rel >= worst:
-                worst, where = rel, n
-    _ERRORS[tag] = {"worst_err_over_ref_max": worst, "param": where, "tol": GRAD_TOL}
-    print(f"[comm_range] {tag}: worst err / ref max {worst:.3e} ({where})")
-    _save()
-    for n, p in model.named_parameters():
-        assert p.grad is not None, f"{n}: no gradient"
-        _close(p.grad, p64[n].grad, GRAD_TOL, f"{tag}/{n}")
 
 
 def _install(model, device, base, radius, metric, normalize):
@@ -241,7 +136,7 @@ def oracle_case(monkeypatch, k, spec):
     w = k.randn(NS, k.na, k.nb, k.cfg.nb_action)
     p64 = k.params64()
     img64 = k.img.double().requires_grad_()
-    tr = oracle_loop4(k, p64, img64)
+    tr = _oracle_loop(k, p64, img64, ns=NS)
     _dist_loss(tr["preds"], tr["logp"], tr["values"], tr["probs"], terms, w).backward()
     return base, terms, w, p64, img64, tr, orc.stats()
 
@@ -262,10 +157,10 @@ def _parity(k, spec, device, monkeypatch, tag):
     assert th.equal(ep.step_actions.cpu(), tr["act"]) and th.equal(ep.step_pos.cpu(), tr["pos"])
     for key, got in (("preds", ep.step_preds), ("logp", ep.step_log_probas), ("values", ep.step_values),
                      ("probs", ep.step_probs)):
-        _fwd(f"{tag}/{key}", got, tr[key])
+        REC.fwd(f"{tag}/{key}", got, tr[key])
     _dist_loss(ep.step_preds, ep.step_log_probas, ep.step_values, ep.step_probs, terms, w).backward()
-    _param_grads(f"{tag}/params", model, p64)
-    _grad(f"{tag}/d_img", img.grad, img64.grad)
+    REC.param_grads(f"{tag}/params", model, p64)
+    REC.grad(f"{tag}/d_img", img.grad, img64.grad)
     eng = model.hip_engine(k.cfg.actions)
     assert eng.plan_query("comm") == 1 and eng.plan_query("comm_range") == radius
     chained = k.na <= 16  # (every shape of this file but na20 is inside the chained panel launch's range)
@@ -294,20 +189,6 @@ def test_parity_one_agent(device, monkeypatch, value):
 
 
 # ---- 2: everything in range is the constant matrix, bit for bit ---------------------------------------------------
-def _run4(k, model, device, actions=None):
-    sampler = sampler4(k, model, device)
-    img = k.img.to(device).requires_grad_()
-    replay = None if actions is None else _replay(sampler, actions, device)
-    ep = sampler.run_episode(img, replay=replay)
-    _dist_loss(ep.step_preds, ep.step_log_probas, ep.step_values, ep.step_probs, k.terms, k.w).backward()
-    res = {"preds": ep.step_preds.detach().clone(), "logp": ep.step_log_probas.detach().clone(),
-           "values": ep.step_values.detach().clone(), "probs": ep.step_probs.detach().clone(),
-           "act": ep.step_actions.clone(), "pos": ep.step_pos.clone(), "d_img": img.grad.clone(),
-           "flat_grad": th.cat([p.grad.flatten() for _, p in model.named_parameters()])}
-    model.zero_grad(set_to_none=True)
-    return res
-
-
 def _case4(name):
     k = RangeCase(name)
     k.terms = loss_terms4(k)
@@ -403,7 +284,7 @@ def test_out_of_range_nan_stays_with_its_owner(device):
     assert not bool(th.isfinite(ep.step_preds[-1, 1:]).all())
 
 
-# ---- 5: trainers (the NS = 3 helpers and bounds of tests/test_gpu_comm.py) -----------------------------------------
+# ---- 5: trainers (the NS = 3 helpers of tests/cases.py; the updates are recorded with tests/test_gpu_comm.py's) ----
 def test_train_step_matches_the_float64_adam_update(device, monkeypatch):
     from marlclassification_amd.training import Trainer
 
@@ -418,7 +299,7 @@ def test_train_step_matches_the_float64_adam_update(device, monkeypatch):
     assert 0.15 <= share <= 0.85, share
     lo = mo.a2c_loss(tr["preds"], tr["logp"], tr["values"], y, gamma)
     lo.loss.backward()
-    g = {n: (v.grad if v.grad is not None else th.zeros_like(v)) for n, v in p64.items()}
+    g = _grads_of(p64)
     after = {n: v.detach().clone() for n, v in p64.items()}
     mo.adam_step(after, g, {n: th.zeros_like(v) for n, v in after.items()},
                  {n: th.zeros_like(v) for n, v in after.items()}, 1, lr)
@@ -430,14 +311,13 @@ def test_train_step_matches_the_float64_adam_update(device, monkeypatch):
     trainer = Trainer(model, k.cfg.nb_class, lr, gamma)
     out, scalars = trainer.train_step(k.img, y, sampler)
     assert th.equal(out.step_actions.cpu(), tr["act"])
-    _fwd("train_step/g1/preds", out.step_preds, tr["preds"])
-    _fwd("train_step/g1/loss", scalars[0], lo.loss)
-    _updates_match("train_step/g1/update", k, model, after, [g], lr, 1)
+    REC.fwd("train_step/g1/preds", out.step_preds, tr["preds"])
+    REC.fwd("train_step/g1/loss", scalars[0], lo.loss)
+    REC_COMM.updates_match("train_step/g1/update", k, model, after, [g], lr, 1)
 
 
 def test_two_ppo_epochs_match_the_float64_oracle(device, monkeypatch):
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_ppo import TWO_EPOCH, TWO_EPOCH_EPS, _y, assert_clear_of_bounds, two_epoch_reference
 
     k = CommCase("g1")
     # (chebyshev: under the euclidean gate one float64 ratio of this case lies 4.5e-5 from the clip bound, inside the
@@ -457,8 +337,8 @@ def test_two_ppo_epochs_match_the_float64_oracle(device, monkeypatch):
                       gae_lambda=TWO_EPOCH["lam"], entropy_coef=TWO_EPOCH["beta"])
     trainer.train_epoch([(k.img, y)], 0, sampler)
     assert trainer.curr_step == 1 and model.flat_state().step == 2
-    _fwd("ppo/g1/approx_kl", th.tensor(trainer.metrics()["approx_kl"]), ref["scalars2"][5])
-    _updates_match("ppo/g1/update", k, model, ref["after"], [ref["g1"], ref["g2"]], lr, 2)
+    REC.fwd("ppo/g1/approx_kl", th.tensor(trainer.metrics()["approx_kl"]), ref["scalars2"][5])
+    REC_COMM.updates_match("ppo/g1/update", k, model, ref["after"], [ref["g1"], ref["g2"]], lr, 2)
 
 
 # ---- 6: graph replay and reproducibility ---------------------------------------------------------------------------

@@ -18,7 +18,6 @@ data; floor = 2e-6 for the weight gradient and, for the layer backward, the wors
 along K, per-workgroup slabs) and use the hardware exp / rcp.  With MARL_CONV_BWD_ERRORS=<file> in the environment the
 achieved errors, e32 and ratios of every case are written there as JSON (profiles/conv_bwd_errors.json is one such
 run)."""
-import ctypes as C
 import json
 import os
 
@@ -26,53 +25,16 @@ import pytest
 import torch as th
 import torch.nn.functional as F
 
+from tests.conv_cases import DG_SHAPES, SENTINEL, WG_DEEP, WG_FIRST, _embed, _Out, _rel, assert_wgrad_witness
+from tests.conv_cases import bwd_plan as plan
+
 pytestmark = pytest.mark.gpu
 
 WG_BOUND = 2e-6
 DG_BOUND = 1e-4
 MULT = 4
-PAD = 64  # floats (256 bytes) of NaN / sentinel on either side of every tensor: the kernels' 16-byte alignment holds
-SENTINEL = -777.0
 _errors = {}
 
-# ---- the grid (module level: tests/test_conv_plan_host.py reads the witnesses) ---------------------------------------
-# first-layer weight gradient (zin = NULL): name -> (cin, cout, window f, c_img, rows, nb, H, W, witness).  Every witness
-# names the instantiation (sct, skt, pd); rows % rb != 0 wherever rb > 1, but in the one-row case.
-WG_FIRST = {
-    "mnist6": (1, 8, 6, 1, 37, 5, 28, 30, dict(form=1, sct=1, skt=1, ms=8, rb=16, pd=2, pi=4)),
-    # MnistCnn on RGB data reads channel 0 only: channels 1 and 2 are NaN
-    "mnist6_cimg3": (1, 8, 6, 3, 37, 5, 28, 30, dict(form=1, sct=1, skt=1, ms=8, rb=16, pd=2, pi=4)),
-    "mnist6_one_row": (1, 8, 6, 1, 1, 3, 28, 30, dict(form=1, sct=1, skt=1, ms=8, rb=16, pd=2, pi=4)),
-    "resisc12": (3, 16, 12, 3, 11, 3, 40, 44, dict(form=1, sct=1, skt=1, rb=4, tgk=2, ms=4, pd=2, pi=4)),
-    "aid24": (3, 16, 24, 3, 5, 3, 50, 56, dict(form=1, sct=1, skt=1, rb=1, pd=2, pi=4)),
-    "aid32_lean": (3, 16, 32, 3, 5, 3, 64, 72, dict(form=1, sct=1, skt=1, rb=2, pd=4, pi=14)),  # <1, 1, true, 4, 14>
-    "cin4_skt3": (4, 16, 6, 4, 17, 5, 28, 30, dict(form=1, sct=1, skt=3, pd=2, rb=14)),
-    "cout32_tgc2": (3, 32, 6, 3, 17, 5, 28, 30, dict(form=1, sct=1, skt=1, tgc=2, pd=2, rb=14)),
-    # persistent: more chunks than the bound of workgroups (1024), which the launch trims further to what is resident
-    "mnist6_persistent": (1, 8, 6, 1, 16 * 1024 + 16 + 5, 5, 28, 30,
-                          dict(form=1, sct=1, skt=1, ms=8, rb=16, pd=2, chunks=1026, blocks=1024)),
-}
-# fp32 form on deeper layers: name -> (cin, cout, hin, G, rows, witness)
-WG_DEEP = {
-    "mnist_l1_h3": (8, 16, 3, 2, 37, dict(form=1, sct=1, skt=5, ms=8, pd=2, rb=16)),
-    "mnist_l1_h6": (8, 16, 6, 2, 31, dict(form=1, sct=1, skt=5, ms=8, pd=2, rb=14)),
-    "c4_c8_h4": (4, 8, 4, 1, 19, dict(form=1, sct=1, skt=3, pd=2, rb=16)),
-    # WorldStrat's last layer: too many k tiles for the bf16x6 form's two slabs; 65 chunks (the last one of 3 rows) on
-    # 64 workgroups x 8 k-slabs
-    "worldstrat_l4": (128, 256, 2, 16, 451, dict(form=1, sct=2, skt=9, slabs=8, rb=7, chunks=65, blocks=64, pd=2)),
-}
-# layer backward: name -> (cin, cout, G, hin, witness): nt column tiles, mt1 row tiles of a one-patch chunk, rb_big = the
-# chunk the launcher takes once dgrad_min_chunks = 1 lets it
-DG_SHAPES = {
-    "mnist_odd_side": (8, 16, 2, 3, dict(nt=1, mt1=1, rb_big=8)),
-    "resisc_l1": (16, 32, 2, 6, dict(nt=1, mt1=3, rb_big=8)),
-    "resisc_l2": (32, 64, 4, 3, dict(nt=2, mt1=1, rb_big=8)),
-    "aid_l3_nt4": (64, 128, 8, 4, dict(nt=4, mt1=1, rb_big=6)),
-    "aid_l1_mt16": (16, 32, 2, 16, dict(nt=1, mt1=16, rb_big=1)),
-    "no_odd_positions": (16, 32, 2, 1, dict(nt=1, mt1=1, rb_big=8)),
-    "small_edge": (16, 32, 2, 2, dict(nt=1, mt1=1, rb_big=8)),
-    "odd_side_unequal_classes": (16, 32, 2, 5, dict(nt=1, mt1=2, rb_big=8)),
-}
 DG_KNOBS = [512, 1]  # dgrad_min_chunks: the default (rb = 1 at these row counts), and 1 (the largest rb that fits)
 DG_ROWS = ["1", "rb+1", "3rb+2"]
 # persistent + ragged: rows -> (dgrad_wgs, witness); 551 chunks of two patches, the last one of one - on what is
@@ -85,20 +47,6 @@ def _lib():
     from marlclassification_amd import _lib
 
     return _lib.load(), _lib.check
-
-
-def plan(rows, cin, cout, hin, groups, first):
-    from marlclassification_amd import _lib
-
-    lib, check = _lib.load(), _lib.check
-    p = _lib.CnnBwdPlan()
-    check(lib.marl_cnn_bwd_plan(rows, cin, cout, hin, groups, first, C.byref(p)))
-    return p.as_dict()
-
-
-def assert_wgrad_witness(p, witness):
-    got = {k: p["wg_" + k] for k in witness}
-    assert got == witness, (got, witness, p)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -116,45 +64,6 @@ def _error_record():
             json.dump({"wgrad_bound_rel_to_max": WG_BOUND, "dgrad_bound_rel_to_max": DG_BOUND, "multiple_of_e32": MULT,
                        "worst_ratio_err_over_max_of_e32_and_floor": worst, "cases": _errors}, f, indent=1,
                       sort_keys=True)
-
-
-# ---- placement ---------------------------------------------------------------------------------------------------
-def _embed(t, device):
-    """`t` on the device inside a buffer whose surroundings are NaN (255 / a valid position for integer data)"""
-    flat = t.reshape(-1)
-    fill = float("nan") if t.is_floating_point() else (255 if t.dtype == th.uint8 else 0)
-    buf = th.full((flat.numel() + 2 * PAD,), fill, dtype=t.dtype, device=device)
-    buf[PAD:PAD + flat.numel()] = flat.to(device)
-    return buf, buf[PAD:PAD + flat.numel()]
-
-
-class _Out:
-    """an output tensor inside a sentinel-filled buffer"""
-
-    def __init__(self, shape, device):
-        self.shape = shape
-        self.n = 1
-        for s in shape:
-            self.n *= s
-        self.buf = th.empty(self.n + 2 * PAD, device=device)
-        self.reset()
-
-    def reset(self):
-        self.buf.fill_(SENTINEL)
-
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * PAD
-
-    def get(self):
-        b = self.buf.cpu()
-        assert th.all(b[:PAD] == SENTINEL) and th.all(b[PAD + self.n:] == SENTINEL), "wrote outside the tensor"
-        inner = b[PAD:PAD + self.n]
-        assert not th.any(inner == SENTINEL), "left part of the tensor unwritten"
-        return inner.reshape(self.shape).clone()
-
-
-def _rel(got, ref):
-    return (got.double() - ref.double()).abs().max().item() / max(ref.abs().max().item(), 1e-30)
 
 
 def _twice(run, outs):

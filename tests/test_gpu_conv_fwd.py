@@ -32,144 +32,16 @@ import pytest
 import torch as th
 import torch.nn.functional as F
 
-from tests.test_gpu_conv_bwd import PAD, SENTINEL, _embed, _Out, _rel
+from tests.conv_cases import (_KC, COLS_GRID, COLS_MIN, FORMS, GRID, KNOB_TWIN, MODELS, NB, PAD, SENTINEL, _embed, _Out,
+                              _rel, config, knobs, model_config, smallest_cols_config)
+from tests.conv_cases import fwd_plan as plan
 
 pytestmark = pytest.mark.gpu
 
 CAP = 1e-5
 MULT = 4
 E32_MAX = CAP / MULT  # the condition on every case's inputs
-NB = 5  # distinct images of every case
 _errors = {}
-
-# ---- the grid (module level: tests/test_conv_plan_host.py reads it) --------------------------------------------------
-MNIST, RESISC = ([1, 8, 16], [2, 4]), ([3, 16, 32, 64], [2, 4, 8])
-AID, WORLDSTRAT = ([3, 16, 32, 64, 128], [2, 4, 8, 16]), ([3, 16, 32, 64, 128, 256], [2, 4, 8, 16, 32])
-# no CNN_SPECS model: a half-filled second 16-channel tile (20 = 16 + 4), 12 channels per group, four input channels;
-# its weight gradients are outside the activation-based kernel's range (512 % (cout / 4) != 0), so a training launch
-# keeps the im2col rows of both layers
-CUSTOM = ([4, 12, 20], [1, 5])
-# name: (channels, groups), window f, image H x W (non-square; positions 0 .. H - f - 1), knobs
-MODELS = {
-    "resisc12": (RESISC, 12, 28, 30, {}),
-    "mnist6": (MNIST, 6, 20, 22, {}),
-    "mnist12": (MNIST, 12, 28, 30, {}),
-    "aid24": (AID, 24, 40, 44, {}),
-    "aid32": (AID, 32, 44, 48, {}),
-    "mnist10": (MNIST, 10, 28, 30, {}),          # odd sides 5 -> 3
-    "mnist7": (MNIST, 7, 20, 22, {}),            # odd window
-    "resisc16": (RESISC, 16, 28, 30, {}),        # odd rb
-    "aid20": (AID, 20, 40, 44, {}),
-    "worldstrat16": (WORLDSTRAT, 16, 28, 30, {}),  # five layers, P = 1 in the last two, 32 groups
-    "custom9": (CUSTOM, 9, 20, 22, {}),
-    "custom4": (CUSTOM, 4, 12, 14, {}),          # the smallest configuration that keeps im2col rows (COLS_MIN)
-    "mnist6_general": (MNIST, 6, 20, 22, {"cnn_fwd2": 0}),
-    "aid24_general": (AID, 24, 40, 44, {"cnn_fwd3": 0}),
-}
-KNOB_TWIN = {"mnist6_general": "mnist6", "aid24_general": "aid24"}  # the specialised kernel of the same shape
-_K0 = [0, 0, 0, 0, 0]
-_KC = [1, 1, 0, 0, 0]  # custom9 in training mode
-
-
-def _w(which, rb, blocks, image=0, cols=_K0):
-    return dict(fused=1, which=which, rb=rb, blocks=blocks, keeps_cols=cols, writes_image=image)
-
-
-# model -> {rows: witness of the training launch}.  cnn_fwd2 (which 1..3): 2065 rows = 259 chunks of 8 on 256 workgroups,
-# workgroups 0..2 walk twice, the last chunk has one row.  cnn_fwd3 (4, 5): 1029 rows = 258 groups of 4 on 256
-# workgroups, a one-row last group.  General kernel (6): rb = 1, then 2 with a one-row last chunk (511 = 255 * 2 + 1),
-# then the largest rb inside the 52 KB cap that leaves 256 chunks, again with a one-row last chunk (2041 = 1 mod 2, 3,
-# 4, 5, 6, 8).
-GRID = {
-    "resisc12": {1: _w(1, 8, 1, 1), 9: _w(1, 8, 2, 1), 2065: _w(1, 8, 256, 1)},
-    "mnist6": {1: _w(2, 8, 1, 1), 9: _w(2, 8, 2, 1), 2065: _w(2, 8, 256, 1)},
-    "mnist12": {1: _w(3, 8, 1), 9: _w(3, 8, 2), 2065: _w(3, 8, 256)},
-    "aid24": {1: _w(4, 4, 1, 1), 5: _w(4, 4, 2, 1), 1029: _w(4, 4, 256, 1)},
-    "aid32": {1: _w(5, 4, 1, 1), 5: _w(5, 4, 2, 1), 1029: _w(5, 4, 256, 1)},
-    "mnist10": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 8, 256)},
-    "mnist7": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 8, 256)},
-    "resisc16": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 5, 409)},
-    "aid20": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 3, 681)},
-    "worldstrat16": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 4, 511)},
-    "custom9": {1: _w(6, 1, 1, cols=_KC), 511: _w(6, 2, 256, cols=_KC), 2041: _w(6, 8, 256, cols=_KC)},
-    "mnist6_general": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 8, 256)},
-    "aid24_general": {1: _w(6, 1, 1), 511: _w(6, 2, 256), 2041: _w(6, 2, 1021)},
-}
-# image forms, one model per kernel family (and the MnistCnn instantiation for the RGB-data case): model -> rows
-FORMS = {"resisc12": 9, "mnist6": 9, "aid24": 5, "mnist10": 511}
-# kept im2col rows: the scan's candidates beyond CNN_SPECS, (channels, groups) - windows 4..32 - what it must find, and
-# that configuration's cases {rows: witness} (rb = 1 at these row counts: 1 and rb + 1 rows)
-COLS_EXTRA = {"custom": CUSTOM}
-COLS_MIN = ("custom", 4, "custom4")
-COLS_GRID = {1: _w(6, 1, 1, cols=_KC), 2: _w(6, 1, 2, cols=_KC)}
-
-
-# ---- configurations and plans (host only) ----------------------------------------------------------------------------
-def config(stack, f, H, W, nb=NB, c_img=None, u8=0):
-    """marl_config of a conv stack: the rest of the model is as small as the library takes it"""
-    from marlclassification_amd._lib import MarlConfig
-
-    (ch, groups) = stack
-    cfg = MarlConfig()
-    cfg.nb_agents, cfg.batch, cfg.nb_steps = 1, nb, 1
-    cfg.img_c, cfg.img_h, cfg.img_w = (c_img or ch[0]), H, W
-    cfg.window, cfg.cnn_layers = f, len(groups)
-    for i, c in enumerate(ch):
-        cfg.cnn_ch[i] = c
-    for i, g in enumerate(groups):
-        cfg.cnn_groups[i] = g
-    cfg.n_b = cfg.n_a = cfg.n_m = cfg.n_m_o = cfg.n_d = cfg.nlb = cfg.nla = 8
-    cfg.nb_action, cfg.nb_class = 4, 4
-    for j, a in enumerate([[1, 0], [-1, 0], [0, 1], [0, -1]]):
-        cfg.actions[j][0], cfg.actions[j][1] = a
-    cfg.img_u8 = u8
-    return cfg
-
-
-def model_config(model, **kw):
-    stack, f, H, W, _ = MODELS[model]
-    return config(stack, f, H, W, **kw)
-
-
-def plan(cfg, train, rows):
-    from marlclassification_amd import _lib
-
-    p = _lib.CnnFwdPlan()
-    _lib.check(_lib.load().marl_cnn_fwd_plan(C.byref(cfg), train, rows, C.byref(p)))
-    return p.as_dict()
-
-
-class knobs:
-    """the knobs of a model for the length of a with block; the defaults (1) afterwards, whatever happens inside"""
-
-    def __init__(self, model):
-        self.k = MODELS[model][4]
-
-    def __enter__(self):
-        from marlclassification_amd import _lib
-
-        for k, v in self.k.items():
-            _lib.check(_lib.load().marl_tune(k.encode(), v))
-
-    def __exit__(self, *exc):
-        from marlclassification_amd import _lib
-
-        for k in self.k:
-            _lib.check(_lib.load().marl_tune(k.encode(), 1))
-
-
-def smallest_cols_config():
-    """the smallest configuration - by window, CNN_SPECS models first - whose fused training forward keeps the im2col
-    rows of some layer: (name, stack, window, keeps_cols), or None"""
-    from marlclassification_amd.engine import CNN_SPECS
-
-    for f in range(4, 33):
-        for name, stack in list(CNN_SPECS.items()) + list(COLS_EXTRA.items()):
-            p = plan(config(stack, f, f + 8, f + 10), 1, 1)
-            if p["fused"] and any(p["keeps_cols"]):
-                return name, stack, f, p["keeps_cols"]
-    return None
-
 
 # ---- data and the float64 / float32 references -----------------------------------------------------------------------
 def _seed(model, rows):

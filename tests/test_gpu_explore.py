@@ -2,14 +2,15 @@
 (``ModelsWrapper.set_exploration``, ``marl_policy_explore``, the EXPLORE instantiations of ``sample_kernel`` and of the
 chained panel kernel's sampling epilogue, ``policy_dlogits_explore_kernel``).
 
-The float64 side is the step loop ``explore_loop4`` of THIS file (modelled on tests/test_gpu_comm_range.py::oracle_loop4):
+The float64 side is the step loop ``explore_loop4`` of THIS file (modelled on tests/cases.py::_oracle_loop, four steps):
 it maps the oracle's ``so.probs`` to the behaviour policy ``behaviour64`` - softmax(log p / tau) mixed with the uniform
 distribution - and takes ``argmax(pi_b / q)`` or, greedy, ``argmax(pi_b)``.  The free-running cases compare actions and
 positions bit for bit; their condition is asserted from the ORACLE, never from the code under test: every decision's
 top-two score ratio is >= 1 + 1e-4, and no decision is left out.  The trainer tests reuse the float64 helpers of
-tests/test_gpu_comm.py and tests/test_gpu_ppo.py with ``mo.step_forward`` wrapped by the same map (``oracle_explore``).
+tests/cases.py (teacher forcing, the two-epoch PPO reference) with ``mo.step_forward`` wrapped by the same map
+(``oracle_explore``).
 Tolerances are the project's: outputs 1e-5 x max(1, |ref|), gradients 1e-4 of the tensor's scale, Adam 1e-3 * lr per
-update.  Achieved errors and margins go through ``tests.util.record`` (``explore_errors``)."""
+update (tests/parity.py).  Achieved errors and margins go through its ``Recorder`` (``explore_errors``)."""
 import math
 import os
 import subprocess
@@ -21,18 +22,18 @@ import torch as th
 
 from oracle import marl_oracle as mo
 from tests import util
-from tests.test_gpu_comm import _force, _replay
-from tests.test_gpu_comm_range import NS, RangeCase, inputs4, loss_terms4, sampler4
-from tests.test_gpu_policy_dist import POL_BIAS, _dist_loss, _oracle_loop, _sampler
-from tests.test_gpu_step_autograd import FWD_TOL, GRAD_TOL, Case, _a2c_like_loss, _act_loop, _close, _loss_terms
-from tests.test_gpu_step_autograd import NS as NS3
-from tests.util import record
+from tests.cases import NS4 as NS
+from tests.cases import (POL_BIAS, TWO_EPOCH, TWO_EPOCH_EPS, Case, RangeCase, _a2c_like_loss, _act_loop, _dist_loss,
+                         _force, _grads_of, _loss_terms, _oracle_loop, _replay, _run4, _sampler, _y, inputs4,
+                         loss_terms4, sampler4, two_epoch_reference)
+from tests.loss_ref import assert_clear_of_bounds
+from tests.parity import GRAD_TOL, Recorder
+from tests.parity import close as _close
 
 pytestmark = pytest.mark.gpu
 
 MARGIN = 1.0 + 1e-4
 POL_WEIGHT = "_ModelsWrapper__policy.3.weight"
-_ERRORS = {}
 
 # (tau, eps, greedy)
 SETTINGS = [(1.0, 0.0, True), (0.5, 0.0, False), (2.0, 0.1, False), (1.0, 0.25, False), (0.25, 0.0, True)]
@@ -117,64 +118,7 @@ def oracle_explore(monkeypatch):
     return use
 
 
-# ---- records -------------------------------------------------------------------------------------------------------
-def _save():
-    fam = _family()  # (a child process of another kernel family keeps a record of its own)
-    record("explore_errors" if fam == "default" else f"explore_errors_{fam}", _ERRORS)
-
-
-def _rec(tag, got, ref, tol):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[explore] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    _save()
-    return err, scale
-
-
-def _fwd(tag, got, ref):
-    err, scale = _rec(tag, got, ref, FWD_TOL)
-    assert err <= FWD_TOL * max(1.0, scale), f"{tag}: max err {err:.3e}"
-
-
-def _grad(tag, got, ref):
-    _rec(tag, got, ref, GRAD_TOL)
-    _close(got, ref, GRAD_TOL, tag)
-
-
-def _param_grads(tag, model, p64):
-    worst, where = 0.0, ""
-    for n, p in model.named_parameters():
-        ref = p64[n].grad
-        if p.grad is not None and ref is not None and ref.abs().max().item() > 0.0:
-            rel = (p.grad.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
-            if rel >= worst:
-                worst, where = rel, n
-    _ERRORS[tag] = {"worst_err_over_ref_max": worst, "param": where, "tol": GRAD_TOL}
-    print(f"[explore] {tag}: worst err / ref max {worst:.3e} ({where})")
-    _save()
-    for n, p in model.named_parameters():
-        assert p.grad is not None, f"{n}: no gradient"
-        _close(p.grad, p64[n].grad, GRAD_TOL, f"{tag}/{n}")
-
-
-def _updates_match(tag, k, model, after, grads_list, lr, n_updates):
-    """tests/test_gpu_comm.py::_updates_match with this file's record."""
-    sd = model.state_dict()
-    worst, bound = 0.0, n_updates * 1e-3 * lr
-    for n in k.params:
-        ref_upd = after[n] - k.params[n].double()
-        upd = sd[n].double().cpu() - k.params[n].double()
-        big = th.ones_like(ref_upd, dtype=th.bool)
-        for g in grads_list:  # (Adam's sign-like first update amplifies a gradient that is zero up to rounding)
-            big &= g[n].abs() > 1e-6
-        if big.any():
-            err = (upd[big] - ref_upd[big]).abs().max().item()
-            worst = max(worst, err)
-            assert err <= bound, f"{n}: {err:.3e}"
-    _ERRORS[tag] = {"max_err": worst, "tol": bound}
-    print(f"[explore] {tag}: max err {worst:.3e} (bound {bound:.1e})")
-    _save()
+REC = Recorder("explore_errors", "explore", _family())  # (a child process of another family keeps its own record)
 
 
 def _tag(shape, tau, eps, greedy=False):
@@ -189,9 +133,8 @@ def _expect_form(shape):
 def _free_running(k, device, tau, eps, greedy):
     tag = _tag(k.name, tau, eps, greedy)
     tr = explore_loop4(k, {n: v.double() for n, v in k.params.items()}, k.img.double(), tau, eps, greedy)
-    _ERRORS[f"{tag}/margin"] = {"min_top_two_ratio": tr["ratio"], "decisions": tr["decisions"]}
     print(f"[explore] {tag}: min top-two score ratio {tr['ratio']:.6f} over {tr['decisions']} decisions")
-    _save()
+    REC.put(f"{tag}/margin", {"min_top_two_ratio": tr["ratio"], "decisions": tr["decisions"]})
     assert tr["decisions"] == NS * k.na * k.nb, "a decision was left out"
     assert tr["ratio"] >= MARGIN, f"{tag}: top-two ratio {tr['ratio']:.7f}: fp32 could decide otherwise"
     model = k.model(device)
@@ -204,7 +147,7 @@ def _free_running(k, device, tau, eps, greedy):
     assert th.equal(ep.step_pos.cpu(), tr["pos"]), f"{tag}: positions differ from the float64 loop"
     for key, got in (("probs", ep.step_probs), ("logp", ep.step_log_probas), ("values", ep.step_values),
                      ("preds", ep.step_preds)):
-        _fwd(f"{tag}/{key}", got, tr[key])
+        REC.fwd(f"{tag}/{key}", got, tr[key])
     eng = model.hip_engine(k.cfg.actions)
     assert eng.plan_query("explore") == 1 and eng.plan_query("explore_form") == _expect_form(k.name)
     return tr
@@ -253,10 +196,10 @@ def _gradients(k, device, tau, eps):
     assert th.equal(ep.step_actions.cpu(), tr["act"]) and th.equal(ep.step_pos.cpu(), tr["pos"])
     for key, got in (("probs", ep.step_probs), ("logp", ep.step_log_probas), ("values", ep.step_values),
                      ("preds", ep.step_preds)):
-        _fwd(f"{tag}/{key}", got, tr[key])
+        REC.fwd(f"{tag}/{key}", got, tr[key])
     _dist_loss(ep.step_preds, ep.step_log_probas, ep.step_values, ep.step_probs, terms, w).backward()
-    _param_grads(f"{tag}/params", model, p64)
-    _grad(f"{tag}/d_img", img.grad, img64.grad)
+    REC.param_grads(f"{tag}/params", model, p64)
+    REC.grad(f"{tag}/d_img", img.grad, img64.grad)
     assert model.hip_engine(k.cfg.actions).plan_query("explore_form") == _expect_form(k.name)
 
 
@@ -296,22 +239,6 @@ def test_other_kernel_families(device, env):
 
 
 # ---- 4: the defaults are today's path ------------------------------------------------------------------------------
-def _run4(k, model, device, actions=None, draws=None):
-    sampler = sampler4(k, model, device)
-    if draws is not None:
-        sampler.fixed_draws = draws
-    img = k.img.to(device).requires_grad_()
-    replay = None if actions is None else _replay(sampler, actions, device)
-    ep = sampler.run_episode(img, replay=replay)
-    _dist_loss(ep.step_preds, ep.step_log_probas, ep.step_values, ep.step_probs, k.terms, k.w).backward()
-    res = {"preds": ep.step_preds.detach().clone(), "logp": ep.step_log_probas.detach().clone(),
-           "values": ep.step_values.detach().clone(), "probs": ep.step_probs.detach().clone(),
-           "act": ep.step_actions.clone(), "pos": ep.step_pos.clone(), "d_img": img.grad.clone(),
-           "flat_grad": th.cat([p.grad.flatten() for _, p in model.named_parameters()])}
-    model.zero_grad(set_to_none=True)
-    return res
-
-
 def _case4(name):
     k = ExploreCase(name)
     k.terms = loss_terms4(k)
@@ -319,7 +246,7 @@ def _case4(name):
     return k
 
 
-def _same_bits(a, b, what):
+def _all_same_bits(a, b, what):
     for key, v in a.items():
         assert np.array_equal(v.cpu().numpy(), b[key].cpu().numpy()), f"{what}: {key} differs"
 
@@ -337,7 +264,7 @@ def test_defaults_are_todays_path(device, monkeypatch, shape):
     model = k.model(device)
     model.set_exploration(1, 0, False)
     again = _run4(k, model, device)
-    _same_bits(never, again, f"{shape}: set_exploration(1, 0, False)")
+    _all_same_bits(never, again, f"{shape}: set_exploration(1, 0, False)")
     eng = model.hip_engine(k.cfg.actions)
     assert eng.plan_query("explore") == 0 and eng.plan_query("explore_form") == 0
     assert calls == [], f"marl_policy_explore was called at the defaults: {calls}"
@@ -347,7 +274,7 @@ def test_defaults_are_todays_path(device, monkeypatch, shape):
     assert not th.equal(other["probs"], never["probs"]), "the setting changed nothing"
     assert calls and all(c == (1.0, 0.0, 0) for c in calls[1::2]), "every install is cleared behind its call"
     model.set_exploration()
-    _same_bits(never, _run4(k, model, device), f"{shape}: after a setting was cleared")
+    _all_same_bits(never, _run4(k, model, device), f"{shape}: after a setting was cleared")
 
 
 # ---- 5: greedy -----------------------------------------------------------------------------------------------------
@@ -362,7 +289,7 @@ def test_greedy_is_the_existing_path_with_noise_of_ones(device, shape):
     model = k.model(device)
     model.set_exploration(greedy=True)
     got = _run4(k, model, device)  # (the case's random noise is injected - and must not be read)
-    _same_bits(ref, got, f"{shape}: greedy at tau 1, eps 0")
+    _all_same_bits(ref, got, f"{shape}: greedy at tau 1, eps 0")
 
 
 def test_two_greedy_runs_under_different_seeds_are_identical(device):
@@ -378,7 +305,7 @@ def test_two_greedy_runs_under_different_seeds_are_identical(device):
             draws = EpisodeDraws(*(t.to(device) for t in (i.pos0, i.h0, i.c0, i.hc0, i.cc0)), None, (seed, 0))
             th.manual_seed(seed)
             runs[greedy, seed] = _run4(k, model, device, draws=draws)
-    _same_bits(runs[True, 1], runs[True, 2], "greedy under two seeds")
+    _all_same_bits(runs[True, 1], runs[True, 2], "greedy under two seeds")
     assert not th.equal(runs[False, 1]["act"], runs[False, 2]["act"]), "the sampled runs do not depend on the seed"
 
 
@@ -422,7 +349,7 @@ def test_eps_floor_keeps_a_forced_excluded_action_finite(device, shape):
     assert th.equal(res["act"].cpu(), forced)
     floor = (th.tensor(0.1, dtype=th.float32) / nA).item()  # (eps / nA as the host forms it: in fp32)
     assert (res["probs"][..., 1:] == floor).all(), "the excluded actions' softmax is not exactly 0"
-    _fwd(f"floor/{shape}/logp", res["logp"], th.full(res["logp"].shape, math.log(0.1 / nA), dtype=th.float64))
+    REC.fwd(f"floor/{shape}/logp", res["logp"], th.full(res["logp"].shape, math.log(0.1 / nA), dtype=th.float64))
     for key in ("d_img", "flat_grad", "preds", "values"):
         assert th.isfinite(res[key]).all(), key
 
@@ -465,7 +392,7 @@ def test_act_loop_under_a_setting_agrees_with_the_fused_episode(device, shape, s
     assert th.equal(out["act"], ep.step_actions) and th.equal(out["pos"], ep.step_pos)
     tag = f"act_loop/{shape}/t{setting[0]:g}_e{setting[1]:g}"
     for key, ref in (("preds", ep.step_preds), ("logp", ep.step_log_probas), ("values", ep.step_values)):
-        _fwd(f"{tag}/{key}", out[key], ref)
+        REC.fwd(f"{tag}/{key}", out[key], ref)
     _a2c_like_loss(out["preds"], out["logp"], out["values"], k.terms).backward()
     for n, p in model.named_parameters():
         _close(p.grad, g_ep[n], GRAD_TOL, n)
@@ -491,7 +418,7 @@ def test_step_probabilities_are_the_behaviour_policy(device):
         plain = model(obs, msg, npos, rec)[0].actions_probabilities
         model.set_exploration(2.0, 0.1)
         got = model(obs, msg, npos, rec)[0].actions_probabilities
-    _fwd("step/g1/probs", got, behaviour64(plain.double().cpu(), 2.0, 0.1))
+    REC.fwd("step/g1/probs", got, behaviour64(plain.double().cpu(), 2.0, 0.1))
 
 
 def test_backward_uses_the_setting_of_its_own_forward(device):
@@ -534,8 +461,8 @@ def test_two_engines_do_not_see_each_others_setting(device):
     ra = _run4(k, a, device)
     rb = _run4(k, b, device)  # after a call under a's setting: still the plain policy
     ra2 = _run4(k, a, device)
-    _same_bits(plain, rb, "the plain model after the other's call")
-    _same_bits(ra, ra2, "the exploring model after the plain one's call")
+    _all_same_bits(plain, rb, "the plain model after the other's call")
+    _all_same_bits(ra, ra2, "the exploring model after the plain one's call")
     assert not th.equal(ra["probs"], plain["probs"])
     assert b.hip_engine(k.cfg.actions).plan_query("explore") == 0
     assert a.hip_engine(k.cfg.actions).plan_query("explore") == 1
@@ -555,7 +482,7 @@ def test_train_step_under_a_setting_matches_the_float64_adam_update(device, orac
     tr = _oracle_loop(k, p64, k.img.double())
     lo = mo.a2c_loss(tr["preds"], tr["logp"], tr["values"], y, gamma)
     lo.loss.backward()
-    g = {n: (v.grad if v.grad is not None else th.zeros_like(v)) for n, v in p64.items()}
+    g = _grads_of(p64)
     after = {n: v.detach().clone() for n, v in p64.items()}
     mo.adam_step(after, g, {n: th.zeros_like(v) for n, v in after.items()},
                  {n: th.zeros_like(v) for n, v in after.items()}, 1, lr)
@@ -566,9 +493,9 @@ def test_train_step_under_a_setting_matches_the_float64_adam_update(device, orac
     out, scalars = trainer.train_step(k.img, y, sampler)
     assert model.exploration == (tau, eps, False)
     assert th.equal(out.step_actions.cpu(), tr["act"])
-    _fwd(f"train_step/{shape}/logp", out.step_log_probas, tr["logp"])
-    _fwd(f"train_step/{shape}/loss", scalars[0], lo.loss)
-    _updates_match(f"train_step/{shape}/update", k, model, after, [g], lr, 1)
+    REC.fwd(f"train_step/{shape}/logp", out.step_log_probas, tr["logp"])
+    REC.fwd(f"train_step/{shape}/loss", scalars[0], lo.loss)
+    REC.updates_match(f"train_step/{shape}/update", k, model, after, [g], lr, 1)
     # the attributes may change between steps: the next step runs under the new setting
     trainer.temperature, trainer.explore_eps = 1.0, 0.0
     trainer.train_step(k.img, y, sampler)
@@ -577,7 +504,6 @@ def test_train_step_under_a_setting_matches_the_float64_adam_update(device, orac
 
 def test_two_ppo_epochs_under_a_setting_match_the_float64_oracle(device, oracle_explore):
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_ppo import TWO_EPOCH, TWO_EPOCH_EPS, _y, assert_clear_of_bounds, two_epoch_reference
 
     # (the shape is chosen from the float64 side alone: under this setting the oracle's own ratios of "g1" come
     # within 9e-5 of the clip bound 0.9 - closer than assert_clear_of_bounds admits -, those of "resisc3" stay 1e-2 away)
@@ -607,10 +533,10 @@ def test_two_ppo_epochs_under_a_setting_match_the_float64_oracle(device, oracle_
     assert trainer.curr_step == 1 and model.flat_state().step == 2 and len(seen) == 2
     # the first epoch replays nothing: the ratio is 1 bit for bit under the rollout's own setting
     assert seen[0][5].item() == 0.0 and seen[0][6].item() == 0.0, "approx_kl / clip_frac of the first epoch"
-    _fwd("ppo/resisc3/approx_kl", seen[1][5], ref["scalars2"][5])
-    _fwd("ppo/resisc3/clip_frac", seen[1][6], ref["scalars2"][6])
-    _fwd("ppo/resisc3/loss", seen[1][0], ref["scalars2"][0])
-    _updates_match("ppo/resisc3/update", k, model, ref["after"], [ref["g1"], ref["g2"]], lr, 2)
+    REC.fwd("ppo/resisc3/approx_kl", seen[1][5], ref["scalars2"][5])
+    REC.fwd("ppo/resisc3/clip_frac", seen[1][6], ref["scalars2"][6])
+    REC.fwd("ppo/resisc3/loss", seen[1][0], ref["scalars2"][0])
+    REC.updates_match("ppo/resisc3/update", k, model, ref["after"], [ref["g1"], ref["g2"]], lr, 2)
 
 
 def test_graph_replay_equals_eager_and_a_changed_setting_captures_again(device):

@@ -6,12 +6,15 @@ import pytest
 import torch as th
 
 from marlclassification_amd import augment, mix
+from tests.buffers import N_SRC, SENTINEL
+from tests.buffers import guarded as _guarded
+from tests.buffers import guards_intact as _guards_intact
+from tests.buffers import same_bits as _same_bits
+from tests.buffers import source as _source
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256  # bytes before and after every destination
-SENTINEL = 0xA5
-N_SRC, ROWS = 11, [10, 0, 3, 3, 7]  # batch 5 from a resident set of 11 rows: repeated, unsorted
+ROWS = [10, 0, 3, 3, 7]  # batch 5 from a resident set of 11 rows: repeated, unsorted
 NB = len(ROWS)
 FILL = {th.uint8: 200, th.float32: -1.5}
 DTYPES = [th.uint8, th.float32]
@@ -24,30 +27,6 @@ SHAPES = {
     (1, 28, 28): (4, 16),
     (3, 64, 64): (16, 16),  # 16-byte stores; 3 bands per fp32 image
 }
-
-
-def _source(shape, dtype, n=N_SRC, seed=0):
-    g = th.Generator().manual_seed(seed + shape[1] * 7 + shape[2])
-    if dtype == th.uint8:
-        return th.randint(0, 256, (n,) + tuple(shape), dtype=th.uint8, generator=g)
-    return th.randn((n,) + tuple(shape), generator=g)
-
-
-def _guarded(shape, dtype, device, offset=0):
-    nbytes = th.Size(shape).numel() * th.empty((), dtype=dtype).element_size()
-    buf = th.full((GUARD + offset + nbytes + GUARD,), SENTINEL, dtype=th.uint8, device=device)
-    return buf, buf[GUARD + offset: GUARD + offset + nbytes].view(dtype).view(shape)
-
-
-def _guards_intact(buf, offset, nbytes):
-    head, tail = buf[: GUARD + offset], buf[GUARD + offset + nbytes:]
-    return bool((head == SENTINEL).all()) and bool((tail == SENTINEL).all()) and tail.numel() == GUARD
-
-
-def _same_bits(got, want):
-    if got.dtype == th.float32:
-        return th.equal(got.view(th.int32), want.view(th.int32))
-    return th.equal(got, want)
 
 
 def _op_sets(c, h, w):

@@ -11,6 +11,7 @@
 Shapes are the smallest that reach every path; the ones that depend on the chunk a workgroup reduces are taken from the
 plan.  Every destination sits inside a larger buffer whose guard bytes must survive."""
 import ctypes as C
+import functools
 import json
 import os
 
@@ -18,14 +19,18 @@ import pytest
 import torch as th
 
 from marlclassification_amd import augment, transforms
+from tests.buffers import N_SRC, source
+from tests.buffers import bits as _bits
+from tests.buffers import guarded as _guarded
+from tests.buffers import guards_intact as _guards_intact
+from tests.buffers import ulps as _ulps
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-SENTINEL = 0xA5
-N_SRC, ROWS = 11, [10, 0, 3, 3, 7]
+ROWS = [10, 0, 3, 3, 7]
 STAT_MODES = ("normal", "channel-normal", "minmax", "channel-minmax")
 DTYPES = pytest.mark.parametrize("dtype", [th.uint8, th.float32], ids=["u8", "f32"])
+_source = functools.partial(source, affine=(0.75, 1.5))  # fp32 rows with std >= 0.1 |mean|: asserted where it matters
 
 
 def _user(c):
@@ -34,33 +39,6 @@ def _user(c):
     lo, hi = [0.0, 0.1, -0.5, 0.2][:c], [1.0, 0.8, 2.0, 0.7][:c]
     return (transforms.Spec("user-normal", tuple(m), tuple(s)).spelling,
             transforms.Spec("user-minmax", tuple(lo), tuple(hi)).spelling)
-
-
-def _source(shape, dtype, n=N_SRC, seed=0):
-    g = th.Generator().manual_seed(seed + shape[1] * 7 + shape[2])
-    if dtype == th.uint8:
-        return th.randint(0, 256, (n,) + tuple(shape), dtype=th.uint8, generator=g)
-    return th.randn((n,) + tuple(shape), generator=g) * 0.75 + 1.5  # (std >= 0.1 |mean|: asserted where it matters)
-
-
-def _guarded(shape, dtype, device, offset=0):
-    nbytes = th.Size(shape).numel() * th.empty((), dtype=dtype).element_size()
-    buf = th.full((GUARD + offset + nbytes + GUARD,), SENTINEL, dtype=th.uint8, device=device)
-    return buf, buf[GUARD + offset: GUARD + offset + nbytes].view(dtype).view(shape)
-
-
-def _guards_intact(buf, offset, nbytes):
-    head, tail = buf[: GUARD + offset], buf[GUARD + offset + nbytes:]
-    return bool((head == SENTINEL).all()) and bool((tail == SENTINEL).all()) and tail.numel() == GUARD
-
-
-def _bits(t):
-    return t.contiguous().view(th.int32)
-
-
-def _ulps(a, b):
-    """distance in fp32 steps (the int32 patterns of same-signed floats are ordered like the floats)"""
-    return (_bits(a).to(th.int64) - _bits(b).to(th.int64)).abs()
 
 
 def _factor(n):

@@ -15,8 +15,8 @@ import torch as th
 
 from marlclassification_amd import _lib
 from marlclassification_amd import optim as O
-from tests.test_gpu_policy_dist import _sampler
-from tests.test_gpu_step_autograd import NS, Case
+from tests.cases import NS, Case, _golden_sampler, _sampler
+from tests.dp import run_ranks
 from tests.util import CASES, Golden, model_spec, record
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +33,7 @@ def _engine(device):
     return HipEngine(model_spec(CASES["g1_conftest"]), device)
 
 
-def _guarded(src, device):
+def _fenced(src, device):
     """``src`` (fp32, host) between guard floats on the device: (whole buffer, interior view)."""
     whole = th.full((src.numel() + 2 * GUARD,), 12345.5, device=device)
     whole[GUARD: GUARD + src.numel()] = src.to(device)
@@ -105,9 +105,9 @@ def test_three_steps_match_float64(device, layout, with_ema):
     opts = O.OptimOptions(betas=(0.9, 0.99), eps=1e-8, schedule=O.Schedule("cosine", 1e-2, 2, 5, 0.1),
                           ema_decay=0.9 if with_ema else None)
     p0, m0, v0 = _state(n, 1)
-    bufs = [_guarded(t, device) for t in (p0, th.zeros(n), m0, v0, p0 + 0.01)]
+    bufs = [_fenced(t, device) for t in (p0, th.zeros(n), m0, v0, p0 + 0.01)]
     (pw, p), (gw, g), (mw, m), (vw, v), (ew, e) = bufs
-    scal_w, scal = _guarded(th.zeros(4), device)
+    scal_w, scal = _fenced(th.zeros(4), device)
     live = th.ones(n, dtype=th.bool)
     gen = th.Generator().manual_seed(2)
     for step in (1, 2, 3):
@@ -139,7 +139,7 @@ def test_second_pass_of_the_grid_stride_loop(device):
     opts = O.OptimOptions(schedule=O.Schedule("linear", 1e-2, 0, 4, 0.0), ema_decay=0.99)
     p0, m0, v0 = _state(n, 5)
     g0 = th.randn(n, generator=th.Generator().manual_seed(6))
-    bufs = [_guarded(t, device) for t in (p0, g0, m0, v0, p0 * 0.5)]
+    bufs = [_fenced(t, device) for t in (p0, g0, m0, v0, p0 * 0.5)]
     (pw, p), (gw, g), (mw, m), (vw, v), (ew, e) = bufs
     ref = [t.double() for t in (p0, m0, v0, p0 * 0.5)]
     O.reference_step(ref[0], g0.double(), ref[1], ref[2], ref[3], table, opts, 2)
@@ -159,7 +159,7 @@ def test_lengths_that_are_no_multiple_of_four(device, n):
     opts = O.OptimOptions(schedule=O.Schedule("linear", 1e-2, 1, 3, 0.5), ema_decay=0.9)
     p0, m0, v0 = _state(n, 20 + n)
     g0 = th.randn(n, generator=th.Generator().manual_seed(n))
-    bufs = [_guarded(t, device) for t in (p0, g0, m0, v0, p0 * 0.5)]
+    bufs = [_fenced(t, device) for t in (p0, g0, m0, v0, p0 * 0.5)]
     (pw, p), (gw, g), (mw, m), (vw, v), (ew, e) = bufs
     ref = [t.double() for t in (p0, m0, v0, p0 * 0.5)]
     O.reference_step(ref[0], g0.double(), ref[1], ref[2], ref[3], table, opts, 2)
@@ -552,7 +552,6 @@ def _dp_worker(rank, world, port, out_q):
     from marlclassification_amd.fused import EpisodeDraws
     from marlclassification_amd.parallel import GradAllReduce, broadcast_parameters, shard_bounds
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
 
     device = th.device("cuda:0")  # both ranks share the one GPU of the test box
     g = Golden("g2_mnist_c1")
@@ -591,20 +590,8 @@ def _dp_worker(rank, world, port, out_q):
 
 def test_two_ranks_hold_identical_parameters_and_ema(device):
     import numpy as np
-    import torch.multiprocessing as mp
 
-    from tests.test_gpu_round2 import _free_port
-
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=600) for _ in range(2)], key=lambda r: r[0])
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = sorted(run_ranks(_dp_worker, 2, results=2), key=lambda r: r[0])
     (_, p0, e0, n0, s0), (_, p1, e1, n1, s1) = res
     assert s0 == s1 == 2
     assert np.array_equal(p0, p1), "parameters differ between the ranks"

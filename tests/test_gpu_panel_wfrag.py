@@ -30,6 +30,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle import marl_oracle as mo  # noqa: E402
+from tests.panel_harness import frag_floats, frag_groups  # noqa: E402
 
 gpu = pytest.mark.gpu
 
@@ -54,14 +55,6 @@ _errors = {}
 
 
 # ---- the documented layout, in numpy --------------------------------------------------------------------------------
-def frag_groups(k):
-    return (k + 15) // 16
-
-
-def frag_floats(n, k):
-    return (((n + 31) // 32) * frag_groups(k) + 3) * 512
-
-
 def frag_reference(w):
     """w [n, K] -> the fragment-order copy, zero padding and the three groups of slack included"""
     n, k = w.shape

@@ -2,30 +2,32 @@
 crop is a masked_select of the image batch (core/environment.py:95-126), so ``img.requires_grad_()`` ->
 ``run_episode`` -> ``loss.backward()`` fills ``img.grad`` there; here the image is a differentiable input of the
 episode's autograd node.  Checked against float64 autograd through the oracle (cases, seeds and NS of
-tests/test_gpu_step_autograd.py, the project's gradient tolerance), on overlapping windows, for its support, with a
+tests/cases.py, the gradient tolerance of tests/parity.py), on overlapping windows, for its support, with a
 frozen model, for bit-reproducibility, at the benchmark shape (full batch against two half batches) and through
-``visualization.saliency_maps``.  Achieved errors per case go through ``tests.util.record`` (copied into
+``visualization.saliency_maps``.  Achieved errors per case go through ``parity.Recorder`` (copied into
 profiles/pixel_grad_errors.json after the box run)."""
 import pytest
 import torch as th
 
 from oracle import marl_oracle as mo
-from tests.test_gpu_step_autograd import (CASES, GRAD_TOL, NS, Case, _a2c_like_loss, _close, _loss_terms,
-                                          _param_grads_match)
-from tests.util import record, uniform_params
+from tests.cases import CASES, NS, Case, _a2c_like_loss, _loss_terms
+from tests.parity import GRAD_TOL, Recorder
+from tests.parity import close as _close
+from tests.parity import param_grads_match as _param_grads_match
+from tests.util import uniform_params
 
 pytestmark = pytest.mark.gpu
 
-_ERRORS = {}
+REC = Recorder("pixel_grad_errors", "pixel grad")
 
 
-def _record(tag, got, ref):
+def _record_margin(tag, got, ref):
+    """(this record keeps the bound itself and the margin to it)"""
     got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
     err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
     bound = GRAD_TOL * scale + 1e-7
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "bound": bound, "margin": bound / err if err > 0 else None}
     print(f"[pixel grad] {tag}: max err {err:.3e}, ref max {scale:.3e}, bound {bound:.3e}")
-    record("pixel_grad_errors", _ERRORS)
+    REC.put(tag, {"max_err": err, "ref_max": scale, "bound": bound, "margin": bound / err if err > 0 else None})
 
 
 class _Custom(Case):
@@ -89,7 +91,7 @@ def _check_against_oracle(k, device, tag, frozen=False):
     tr = _oracle_loop(k, p64, img64)
     assert th.equal(ep.step_pos.cpu(), tr["pos"]), "the episode moved otherwise than the oracle"
     _a2c_like_loss(tr["preds"], tr["logp"], tr["values"], terms).backward()
-    _record(tag, img.grad, img64.grad)
+    _record_margin(tag, img.grad, img64.grad)
     _close(img.grad, img64.grad, GRAD_TOL, "d_img")
     if frozen:
         assert all(p.grad is None for p in model.parameters())
@@ -210,7 +212,7 @@ def test_full_batch_equals_two_half_batches_at_the_bench_shape(device):
     hi, pos_hi = run(slice(nb // 2, nb))
     assert th.equal(pos_full, th.cat([pos_lo, pos_hi], dim=2)), "the half batches moved otherwise than the full batch"
     halves = th.cat([lo, hi], dim=0)
-    _record("bench_shape_b64_full_vs_halves", full, halves)
+    _record_margin("bench_shape_b64_full_vs_halves", full, halves)
     _close(full, halves, GRAD_TOL, "d_img, full batch against two half batches")
     assert bool((full != 0).any(dim=3).any(dim=2).all()), "an image / channel without any gradient"
 

@@ -7,7 +7,7 @@ PLAN_WITNESS), then runs tests/util.py::distinct_image_parity, the method and to
 tests/test_gpu_round5.py::test_full_size_parity_on_distinct_shuffled_images.
 
 The inputs (uniform_params seed 7; image / label / draw seeds 21 / 22 / 23) keep the REFERENCE well inside the
-tolerances: the fp32 oracle against a float64 run of its own step loop (tests/test_gpu_policy_dist.py::_oracle_loop,
+tolerances: the fp32 oracle against a float64 run of its own step loop (tests/cases.py::_oracle_loop,
 teacher-forced to the fp32 oracle's actions; positions identical, |logit| <= 2.4) differs by at most
                         logits    log-probs  values
   mnist6_b1024          1.00e-06  7.41e-07   5.85e-07

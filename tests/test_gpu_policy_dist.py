@@ -1,96 +1,24 @@
 """GPU: the action distributions of the fused episode - ``EpisodeSampler.return_probs`` / ``step_probs``
 (marl_episode_forward_probs), gradients through them (marl_episode_backward_probs), the entropy bonus of the fused
-loss (marl_a2c_loss_entropy_fwd_bwd) in ``Trainer`` / ``FusedA2C``, and trajectory replay.  Cases, seeds, NS and
-tolerances are those of tests/test_gpu_step_autograd.py; the reference is float64 autograd through the oracle.
-Achieved errors go through ``tests.util.record`` (copied into profiles/policy_dist_errors.json after the box run)."""
+loss (marl_a2c_loss_entropy_fwd_bwd) in ``Trainer`` / ``FusedA2C``, and trajectory replay.  Cases, seeds and NS are
+those of tests/cases.py, the tolerances those of tests/parity.py; the reference is float64 autograd through the oracle
+(``cases._oracle_loop``).  Achieved errors go through ``parity.Recorder`` (copied into profiles/policy_dist_errors.json
+after the box run)."""
 import math
 
 import pytest
 import torch as th
 
 from oracle import marl_oracle as mo
-from tests.test_gpu_step_autograd import (CASES, FWD_TOL, GRAD_TOL, NS, Case, _a2c_like_loss, _close, _loss_terms,
-                                          _param_grads_match)
-from tests.util import model_spec, record
+from tests.cases import (CASES, NS, POL_BIAS, Case, _a2c_like_loss, _dist_loss, _engine_episode, _loss_terms,
+                         _oracle_loop, _sampler, masked_entropy)
+from tests.parity import FWD_TOL, GRAD_TOL, Recorder
+from tests.parity import close as _close
+from tests.util import model_spec
 
 pytestmark = pytest.mark.gpu
 
-_ERRORS = {}
-POL_BIAS = "_ModelsWrapper__policy.3.bias"
-
-
-def masked_entropy(p):
-    """H = -sum_j p_j log p_j over the last dimension with 0 log 0 = 0: a zero probability adds nothing and gets a
-    zero gradient (Categorical.entropy clamps instead; the naive sum is NaN there)."""
-    safe = th.where(p > 0, p, th.ones_like(p))
-    return -(p * safe.log()).sum(-1)
-
-
-def _record(tag, got, ref, tol):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[policy dist] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    record("policy_dist_errors", _ERRORS)
-
-
-def _close_fwd(got, ref, what):
-    _record(what, got, ref, FWD_TOL)
-    err = (got.detach().double().cpu() - ref.detach().double().cpu()).abs().max().item()
-    assert err <= FWD_TOL * max(1.0, ref.abs().max().item()), f"{what}: max err {err:.3e}"
-
-
-def _grads_match(tag, model, p64):
-    worst, where = 0.0, ""
-    for n, p in model.named_parameters():
-        ref = p64[n].grad
-        if p.grad is None or ref is None or ref.abs().max().item() == 0.0:
-            continue
-        rel = (p.grad.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
-        if rel >= worst:
-            worst, where = rel, n
-    _ERRORS[tag] = {"worst_err_over_ref_max": worst, "param": where, "tol": GRAD_TOL}
-    print(f"[policy dist] {tag}: worst err / ref max {worst:.3e} ({where})")
-    record("policy_dist_errors", _ERRORS)
-    _param_grads_match(model, p64)
-
-
-def _sampler(k, model, device, probs=True):
-    from marlclassification_amd.core import Environment, EpisodeSampler, MultiAgent
-    from marlclassification_amd.fused import EpisodeDraws
-
-    i = k.inp
-    sampler = EpisodeSampler(MultiAgent(k.na, model), Environment(k.cfg.actions, k.cfg.window), NS)
-    sampler.fixed_draws = EpisodeDraws(*(t.to(device) for t in (i.pos0, i.h0, i.c0, i.hc0, i.cc0, i.q[:NS])))
-    sampler.return_probs = probs
-    return sampler
-
-
-def _oracle_loop(k, p64, img64, forced=None):
-    """The episode in float64 (tests/test_gpu_pixel_grad.py::_oracle_loop plus the distributions, the actions and
-    teacher forcing)."""
-    c, i = k.cfg, k.inp
-    table = th.tensor(c.actions)
-    pos = i.pos0
-    h, cst, hc, cc = (t.double() for t in (i.h0, i.c0, i.hc0, i.cc0))
-    msg = th.zeros(k.na, k.nb, c.n_m, dtype=th.float64)
-    acc = {"preds": [], "logp": [], "values": [], "pos": [], "probs": [], "act": []}
-    for t in range(NS):
-        so = mo.step_forward(p64, c, mo.crop_patches(img64, pos, c.window), msg,
-                             mo.normalized_positions(pos, k.sizes).double(), h, cst, hc, cc)
-        h, cst, hc, cc, msg = so.h, so.c, so.hc, so.cc, so.msg
-        a = mo.sample_actions(so.probs, i.q[t].double()) if forced is None else forced[t]
-        logp = th.gather(so.probs, -1, a.unsqueeze(-1)).squeeze(-1).log()
-        pos = mo.transition(pos, a, table, c.window, k.sizes)
-        for key, v in zip(acc, (so.preds, logp, so.values, pos, so.probs, a)):
-            acc[key].append(v)
-    return {key: th.stack(v) for key, v in acc.items()}
-
-
-def _dist_loss(preds, logp, values, probs, terms, w, only_probs=False):
-    """An A2C-like loss + an entropy bonus + a fixed random linear form of the distributions (a general g_probs)."""
-    dist = -0.37 * masked_entropy(probs).sum(0).mean() + (w.to(probs.device, probs.dtype) * probs).sum()
-    return dist if only_probs else _a2c_like_loss(preds, logp, values, terms) + dist
+REC = Recorder("policy_dist_errors", "policy dist")
 
 
 # ---- 1: forward -----------------------------------------------------------------------------------------------
@@ -113,10 +41,10 @@ def test_step_probs_match_float64_oracle(device, name):
         assert o.step_probs.shape == (NS, k.na, k.nb, k.cfg.nb_action)
         assert th.equal(o.step_pos.cpu(), tr["pos"]), "the episode moved otherwise than the oracle"
         assert th.equal(o.step_actions.cpu(), tr["act"])
-        _close_fwd(o.step_probs, tr["probs"], f"{name}/{tag}/step_probs")
-        _close_fwd(o.step_probs.sum(-1), th.ones(NS, k.na, k.nb), f"{name}/{tag}/row_sums")
-        _close_fwd(o.step_log_probas.exp(), o.step_probs.gather(-1, o.step_actions.unsqueeze(-1)).squeeze(-1),
-                   f"{name}/{tag}/exp_logp_vs_gather")
+        REC.fwd(f"{name}/{tag}/step_probs", o.step_probs, tr["probs"])
+        REC.fwd(f"{name}/{tag}/row_sums", o.step_probs.sum(-1), th.ones(NS, k.na, k.nb))
+        REC.fwd(f"{name}/{tag}/exp_logp_vs_gather", o.step_log_probas.exp(),
+                o.step_probs.gather(-1, o.step_actions.unsqueeze(-1)).squeeze(-1))
     assert th.equal(plain.step_probs.view(NS, R, -1), rollout_ws), "step_probs is not the rollout layout's PROBS"
     assert th.equal(plain.step_probs, ep.step_probs.detach())
     # the training layout of the engine's own workspace (the fused trainer's path)
@@ -188,12 +116,11 @@ def _check_gradients(k, device, tag, only_probs=False, with_img=False, frozen=Fa
     _dist_loss(tr["preds"], tr["logp"], tr["values"], tr["probs"], terms, w, only_probs).backward()
     if with_img:
         assert img.grad is not None, "no gradient reached the image"
-        _record(f"{tag}/d_img", img.grad, img64.grad, GRAD_TOL)
-        _close(img.grad, img64.grad, GRAD_TOL, "d_img")
+        REC.grad(f"{tag}/d_img", img.grad, img64.grad)
     if frozen:
         assert all(p.grad is None for p in model.parameters())
     else:
-        _grads_match(f"{tag}/params", model, p64)
+        REC.param_grads(f"{tag}/params", model, p64)
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -249,25 +176,13 @@ def test_step_loop_gradients_equal_the_fused_episode(device, name):
         for key, v in zip(acc, (out.predictions, logp, out.values, out.actions_probabilities)):
             acc[key].append(v)
     o = {key: th.stack(v) for key, v in acc.items()}
-    _close_fwd(o["probs"], ep.step_probs, f"{name}/loop_probs_vs_fused")
+    REC.fwd(f"{name}/loop_probs_vs_fused", o["probs"], ep.step_probs)
     _dist_loss(o["preds"], o["logp"], o["values"], o["probs"], terms, w).backward()
     for n, p in model.named_parameters():
         _close(p.grad, g_ep[n], GRAD_TOL, n)
 
 
 # ---- 5: the fused loss ---------------------------------------------------------------------------------------------
-def _engine_episode(k, device):
-    from marlclassification_amd.engine import HipEngine
-
-    eng = HipEngine(model_spec(k.cfg), device)
-    eng.configure(k.na, k.nb, NS, k.img.shape[1:])
-    eng.pack({n: v.to(device) for n, v in k.params.items()})
-    i = k.inp
-    out = eng.episode_forward(k.img.to(device), *(t.to(device) for t in (i.pos0, i.h0, i.c0, i.hc0, i.cc0, i.q[:NS])),
-                              None, True, probs=True)
-    return eng, out
-
-
 @pytest.mark.parametrize("beta", [0.01, 0.5])
 @pytest.mark.parametrize("name", ["g1", "wide"])
 def test_fused_entropy_loss_matches_autograd(device, name, beta):
@@ -287,11 +202,10 @@ def test_fused_entropy_loss_matches_autograd(device, name, beta):
     ref_scalars = th.stack([loss, lo.path, lo.error, lo.critic, ent.mean()]).detach()
     tag = f"{name}/beta{beta}"
     for j, what in enumerate(("loss", "path", "error", "critic", "entropy")):
-        _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/scalar_{what}")
+        REC.fwd(f"{tag}/scalar_{what}", bufs[3][j], ref_scalars[j])
     for got, leaf, what in zip((bufs[0], bufs[1], bufs[2], bufs[5]), leaves, ("g_preds", "g_logp", "g_values",
                                                                                "g_probs")):
-        _record(f"{tag}/{what}", got, leaf.grad, GRAD_TOL)
-        _close(got, leaf.grad, GRAD_TOL, what)
+        REC.grad(f"{tag}/{what}", got, leaf.grad)
 
     # two phases with the statistics untouched in between = phase 0, bit for bit; and a second run too
     two = eng.new_loss_bufs(out, True)
@@ -401,7 +315,7 @@ def test_zero_probabilities_give_zero_entropy_and_finite_gradients(device):
     assert 0 < tr["probs"][..., 1:].max().item() < 1e-80 and 0 < masked_entropy(tr["probs"]).max().item() < 1e-75
     (_a2c_like_loss(tr["preds"], tr["logp"], tr["values"], terms) -
      0.37 * masked_entropy(tr["probs"]).sum(0).mean()).backward()
-    _grads_match("zero_prob/params", model, p64)  # every parameter, the policy head's included
+    REC.param_grads("zero_prob/params", model, p64)  # every parameter, the policy head's included
 
     # the fused loss on the same distributions: entropy exactly 0, nothing NaN / Inf, and its backward too
     eng, out = _engine_episode(k, device)
@@ -450,11 +364,11 @@ def test_replay_reproduces_and_follows_new_weights(device, name):
     p64 = k.params64()
     tr = _oracle_loop(k, p64, k.img.double(), forced=traj.actions.cpu())
     assert th.equal(new.step_pos.cpu(), tr["pos"])
-    _close_fwd(new.step_log_probas, tr["logp"], f"{name}/replay_logp")
-    _close_fwd(new.step_probs, tr["probs"], f"{name}/replay_probs")
+    REC.fwd(f"{name}/replay_logp", new.step_log_probas, tr["logp"])
+    REC.fwd(f"{name}/replay_probs", new.step_probs, tr["probs"])
     old_logp = first.step_log_probas.detach().double().cpu()
     ((tr["logp"] - old_logp).exp().sum() + _a2c_like_loss(tr["preds"], tr["logp"], tr["values"], terms)).backward()
-    _grads_match(f"{name}/replay_params", model, p64)
+    REC.param_grads(f"{name}/replay_params", model, p64)
 
 
 # ---- 9: guards -----------------------------------------------------------------------------------------------------

@@ -1,115 +1,26 @@
 """GPU: PPO on the fused path - GAE(lambda) advantages (marl_advantages), the clipped surrogate and its gradients
 (marl_ppo_loss_fwd_bwd), global-norm gradient clipping (marl_grad_clip), and ``Trainer`` / ``FusedA2C`` running K update
-epochs per rollout with epochs 1 .. K-1 replaying the stored trajectory.  Cases, NS and tolerances are those of
-tests/test_gpu_step_autograd.py; the reference is float64 torch written here from the oracle's rewards / standardise,
-the plain GAE recursion of tests/test_ppo_host.py, ``torch.minimum`` / ``clamp`` and ``smooth_l1_loss``.  Achieved errors
-go through ``tests.util.record`` (copied into profiles/ppo_errors.json after the box run)."""
+epochs per rollout with epochs 1 .. K-1 replaying the stored trajectory.  Cases and NS are those of tests/cases.py, the
+tolerances those of tests/parity.py; the reference is the float64 torch of tests/loss_ref.py with no options: the
+oracle's rewards / standardise, the plain GAE recursion (held to the oracle's returns by tests/test_ppo_host.py),
+``torch.minimum`` / ``clamp`` and ``smooth_l1_loss``.  Achieved errors go through ``parity.Recorder`` (copied into
+profiles/ppo_errors.json after the box run)."""
 import pytest
 import torch as th
-import torch.nn.functional as F
 
 from oracle import marl_oracle as mo
-from tests.test_gpu_policy_dist import POL_BIAS, _engine_episode, _oracle_loop, _sampler, masked_entropy
-from tests.test_gpu_step_autograd import FWD_TOL, GRAD_TOL, NS, Case, _close
-from tests.test_ppo_host import gae, ratio_deltas
-from tests.util import model_spec, record
+from tests import loss_ref as ref64
+from tests.cases import (NS, POL_BIAS, TWO_EPOCH, TWO_EPOCH_EPS, Case, _engine_episode, _golden_sampler, _sampler, _y,
+                         masked_entropy, two_epoch_reference)
+from tests.dp import run_ranks
+from tests.loss_ref import assert_clear_of_bounds, ratio_deltas
+from tests.parity import FWD_TOL, Recorder
+from tests.util import model_spec
 
 pytestmark = pytest.mark.gpu
 
-_ERRORS = {}
+REC = Recorder("ppo_errors", "ppo")
 SCALARS = ("loss", "surrogate", "error", "critic", "entropy", "approx_kl", "clip_frac")
-# epsilon of the two-epoch test: the first Adam step (lr = 1e-3, every parameter moves by lr) spreads the float64
-# reference's ratios over [0.65, 1.53]; at 0.1 it clips 23.5 % (g1) and 33.3 % (resisc3) of the entries in epoch 2 and
-# the nearest ratio stays 6.1e-4 / 5.7e-3 from a bound (scanned on the CPU; the test asserts >= 1e-4 again)
-TWO_EPOCH_EPS = {"g1": 0.1, "resisc3": 0.1}
-TWO_EPOCH = {"lr": 1e-3, "gamma": 0.99, "lam": 0.9, "beta": 0.05}
-
-
-def _record(tag, got, ref, tol):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[ppo] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    record("ppo_errors", _ERRORS)
-
-
-def _close_fwd(got, ref, what):
-    _record(what, got, ref, FWD_TOL)
-    err = (got.detach().double().cpu() - ref.detach().double().cpu()).abs().max().item()
-    assert err <= FWD_TOL * max(1.0, ref.abs().max().item()), f"{what}: max err {err:.3e}"
-
-
-def _close_grad(got, ref, what):
-    _record(what, got, ref, GRAD_TOL)
-    _close(got, ref, GRAD_TOL, what)
-
-
-# ---- the float64 reference ----------------------------------------------------------------------------------------
-def ref_advantages(preds, values, y, gamma, lam):
-    """(standardised advantage, critic target, raw advantage): rewards -> GAE(lam) -> standardise, all detached."""
-    rew = mo.classification_rewards(preds.detach(), y)
-    adv, ret = gae(rew, values.detach(), gamma, lam)
-    return mo.standardize(adv), ret, adv
-
-
-def clip_mask(rho, advn, eps):
-    return ((advn > 0) & (rho > 1 + eps)) | ((advn < 0) & (rho < 1 - eps))
-
-
-def ref_ppo(preds, logp, values, probs, y, old_logp, advn, ret, eps, beta):
-    """The loss of marl_ppo_loss_fwd_bwd and its seven scalars (training/trainer.py:76-111 with the path term
-    replaced by the clipped surrogate)."""
-    ns, _, nb, _ = preds.shape
-    error = F.cross_entropy(preds.mean(dim=1).flatten(0, 1), y.unsqueeze(0).repeat(ns, 1).flatten(0, 1),
-                            reduction="none").unflatten(0, (ns, 1, nb))
-    rho = (logp - old_logp).exp()
-    surr = -th.minimum(rho * advn, rho.clamp(1 - eps, 1 + eps) * advn)
-    critic = F.smooth_l1_loss(values, ret, reduction="none")
-    ent = masked_entropy(probs) if beta > 0 else th.zeros_like(logp)
-    loss = th.sum(surr + error + critic, 0).mean() - beta * ent.sum(0).mean()
-    clipped = clip_mask(rho.detach(), advn, eps)
-    scalars = th.stack([loss, surr.sum(0).mean(), error.mean(), critic.sum(0).mean(), ent.mean(),
-                        (old_logp - logp).mean(), clipped.double().mean()]).detach()
-    return loss, scalars, rho.detach(), clipped
-
-
-def assert_clear_of_bounds(rho, eps):
-    for bound in (1 - eps, 1 + eps):
-        gap = (rho - bound).abs().min().item()
-        assert gap >= 1e-4, f"a reference ratio lies {gap:.2e} from {bound}: fp32 could clip it otherwise"
-
-
-def two_epoch_reference(k, y, eps):
-    """Two PPO epochs on one batch in float64: oracle loop -> advantages and the loss at rho = 1 -> Adam 1 -> the
-    loop again under the updated parameters with the sampled actions forced -> the loss against the stored old
-    log-probabilities -> Adam 2 with carried moments."""
-    lr, gamma, lam, beta = (TWO_EPOCH[n] for n in ("lr", "gamma", "lam", "beta"))
-    img64 = k.img.double()
-    p = k.params64()
-    tr = _oracle_loop(k, p, img64)
-    advn, ret, _ = ref_advantages(tr["preds"], tr["values"], y, gamma, lam)
-    old_logp = tr["logp"].detach()
-    loss, sc1, _, _ = ref_ppo(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, old_logp, advn, ret, eps, beta)
-    loss.backward()
-    g1 = {n: (v.grad if v.grad is not None else th.zeros_like(v)) for n, v in p.items()}
-    after = {n: v.detach().clone() for n, v in p.items()}
-    m = {n: th.zeros_like(v) for n, v in after.items()}
-    v2 = {n: th.zeros_like(v) for n, v in after.items()}
-    mo.adam_step(after, g1, m, v2, 1, lr)
-    p2 = {n: v.clone().requires_grad_() for n, v in after.items()}
-    tr2 = _oracle_loop(k, p2, img64, forced=tr["act"])
-    assert th.equal(tr2["pos"], tr["pos"])
-    loss2, sc2, rho, clipped = ref_ppo(tr2["preds"], tr2["logp"], tr2["values"], tr2["probs"], y, old_logp, advn,
-                                       ret, eps, beta)
-    loss2.backward()
-    g2 = {n: (v.grad if v.grad is not None else th.zeros_like(v)) for n, v in p2.items()}
-    mo.adam_step(after, g2, m, v2, 2, lr)
-    return {"tr": tr, "after": after, "g1": g1, "g2": g2, "scalars1": sc1, "scalars2": sc2, "rho": rho,
-            "clipped": clipped}
-
-
-def _y(k):
-    return th.randint(k.cfg.nb_class, (k.nb,), generator=k.gen)
 
 
 # ---- 1: advantages -------------------------------------------------------------------------------------------------
@@ -121,15 +32,15 @@ def test_advantages_match_float64(device, name, lam):
     y = _y(k)
     eng, out = _engine_episode(k, device)
     bufs = [t.clone() for t in eng.advantages(out, y.to(device), gamma, lam)]
-    advn, ret, _ = ref_advantages(out.step_preds.double().cpu(), out.step_values.double().cpu(), y, gamma, lam)
+    advn, ret, _ = ref64.advantages(out.step_preds.double().cpu(), out.step_values.double().cpu(), y, gamma, lam)
     tag = f"{name}/lam{lam}"
-    _close_fwd(bufs[5], advn, f"{tag}/advn")
-    _close_fwd(bufs[6], ret, f"{tag}/ret")
+    REC.fwd(f"{tag}/advn", bufs[5], advn)
+    REC.fwd(f"{tag}/ret", bufs[6], ret)
     if lam == 1.0:
         # the oracle's own form too (its float32 discount factors are inside FWD_TOL) ...
         returns = mo.discounted_returns(mo.classification_rewards(out.step_preds.double().cpu(), y), gamma)
-        _close_fwd(bufs[6], returns, f"{tag}/ret_vs_discounted_returns")
-        _close_fwd(bufs[5], mo.standardize(returns - out.step_values.double().cpu()), f"{tag}/advn_vs_a2c")
+        REC.fwd(f"{tag}/ret_vs_discounted_returns", bufs[6], returns)
+        REC.fwd(f"{tag}/advn_vs_a2c", bufs[5], mo.standardize(returns - out.step_values.double().cpu()))
         # ... and with rho = 1 the PPO gradients ARE the A2C gradients, bit for bit
         ppo = eng.ppo_loss(out, y.to(device), out.step_log_probas, bufs[5], bufs[6], 0.2)
         a2c = eng.a2c_loss(out, y.to(device), gamma)
@@ -162,7 +73,7 @@ def test_ppo_loss_matches_float64_autograd(device, name, eps, beta):
 
     leaves = [t.detach().double().cpu().requires_grad_()
               for t in (out.step_preds, out.step_log_probas, out.step_values, out.step_probs)]
-    loss, ref_scalars, rho, clipped = ref_ppo(*leaves, y, old_logp.double().cpu(), advn.double().cpu(),
+    loss, ref_scalars, rho, clipped = ref64.ppo(*leaves, y, old_logp.double().cpu(), advn.double().cpu(),
                                               ret.double().cpu(), eps, beta)
     # fp32 and float64 must agree on the side of 1 +- eps of every ratio: asserted on the reference alone, and
     # both branches must be exercised, the clipped one with either sign of the advantage
@@ -173,11 +84,11 @@ def test_ppo_loss_matches_float64_autograd(device, name, eps, beta):
     loss.backward()
     tag = f"{name}/eps{eps}/beta{beta}"
     for j, what in enumerate(SCALARS):
-        _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/scalar_{what}")
+        REC.fwd(f"{tag}/scalar_{what}", bufs[3][j], ref_scalars[j])
     assert bufs[3][6].item() == ref_scalars[6].float().item(), "clip_frac is a count: it must be exact"
     grads = [(bufs[0], "g_preds"), (bufs[1], "g_logp"), (bufs[2], "g_values")] + ([(bufs[7], "g_probs")] if beta else [])
     for (got, what), leaf in zip(grads, leaves):
-        _close_grad(got, leaf.grad, f"{tag}/{what}")
+        REC.grad(f"{tag}/{what}", got, leaf.grad)
     assert bool((bufs[1][clipped.to(device)] == 0).all()), "a clipped entry must get a zero g_logp"
     again = eng.ppo_loss(out, y.to(device), old_logp, advn, ret, eps, entropy_coef=beta)
     for j in (0, 1, 2, 3) + ((7,) if beta else ()):  # (what ppo_loss writes: the gradients and the scalars)
@@ -236,16 +147,16 @@ def test_losses_match_float64_at_the_partial_placement_sizes(device, name, size)
     loss.backward()
     ref_scalars = th.stack([loss, lo.path, lo.error, lo.critic, ent.mean()]).detach()
     for j, what in enumerate(("loss", "path", "error", "critic", "entropy")):
-        _close_fwd(a2c[3][j], ref_scalars[j], f"{tag}/a2c/scalar_{what}")
+        REC.fwd(f"{tag}/a2c/scalar_{what}", a2c[3][j], ref_scalars[j])
     for got, leaf, what in zip((a2c[0], a2c[1], a2c[2], a2c[5]), lv, ("g_preds", "g_logp", "g_values", "g_probs")):
-        _close_grad(got, leaf.grad, f"{tag}/a2c/{what}")
+        REC.grad(f"{tag}/a2c/{what}", got, leaf.grad)
     for a, b in zip(a2c, eng.a2c_loss(out, yd, gamma, entropy_coef=beta)):
         assert th.equal(a, b), "two a2c_loss runs differ"
 
     adv = [t.clone() for t in eng.advantages(out, yd, gamma, lam)]
-    advn64, ret64, _ = ref_advantages(host.step_preds.double(), host.step_values.double(), y, gamma, lam)
-    _close_fwd(adv[5], advn64, f"{tag}/advn")
-    _close_fwd(adv[6], ret64, f"{tag}/ret")
+    advn64, ret64, _ = ref64.advantages(host.step_preds.double(), host.step_values.double(), y, gamma, lam)
+    REC.fwd(f"{tag}/advn", adv[5], advn64)
+    REC.fwd(f"{tag}/ret", adv[6], ret64)
     again = eng.advantages(out, yd, gamma, lam)
     for j in (4, 5, 6):
         assert th.equal(adv[j], again[j]), "two advantages runs differ"
@@ -255,16 +166,16 @@ def test_losses_match_float64_at_the_partial_placement_sizes(device, name, size)
     for eps in (0.1, 0.3):
         bufs = [t.clone() for t in eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)]
         lv = leaves()
-        loss, ref_scalars, rho, _ = ref_ppo(*lv, y, old_logp.double().cpu(), advn.double().cpu(), ret.double().cpu(),
+        loss, ref_scalars, rho, _ = ref64.ppo(*lv, y, old_logp.double().cpu(), advn.double().cpu(), ret.double().cpu(),
                                             eps, beta)
         assert_clear_of_bounds(rho, eps)
         loss.backward()
         for j, what in enumerate(SCALARS):
-            _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/eps{eps}/scalar_{what}")
+            REC.fwd(f"{tag}/eps{eps}/scalar_{what}", bufs[3][j], ref_scalars[j])
         assert bufs[3][6].item() == ref_scalars[6].float().item(), "clip_frac is a count: it must be exact"
         for got, leaf, what in zip((bufs[0], bufs[1], bufs[2], bufs[7]), lv, ("g_preds", "g_logp", "g_values",
                                                                                "g_probs")):
-            _close_grad(got, leaf.grad, f"{tag}/eps{eps}/{what}")
+            REC.grad(f"{tag}/eps{eps}/{what}", got, leaf.grad)
         again = eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)
         for j in (0, 1, 2, 3, 7):
             assert th.equal(bufs[j], again[j]), "two ppo_loss runs differ"
@@ -312,9 +223,9 @@ def test_grad_clip_matches_clip_grad_norm(device):
     norm = eng.grad_clip(flat.grads, max_norm).clone()
     rel = abs(norm.item() - ref_norm) / ref_norm
     err = (flat.grads.double().cpu() - ref.grad).abs().max().item()
-    _ERRORS["grad_clip"] = {"norm_rel_err": rel, "max_err_over_max_g": err / ref.grad.abs().max().item(), "tol": 1e-6}
-    print(f"[ppo] grad_clip: norm rel err {rel:.3e}, entries {_ERRORS['grad_clip']['max_err_over_max_g']:.3e}")
-    record("ppo_errors", _ERRORS)
+    entries = err / ref.grad.abs().max().item()
+    print(f"[ppo] grad_clip: norm rel err {rel:.3e}, entries {entries:.3e}")
+    REC.put("grad_clip", {"norm_rel_err": rel, "max_err_over_max_g": entries, "tol": 1e-6})
     assert rel <= 1e-6
     assert err <= 1e-6 * ref.grad.abs().max().item()
     clipped = flat.grads.clone()
@@ -415,22 +326,10 @@ def test_two_epochs_match_the_float64_oracle(device, name):
     m = trainer.metrics()
     print(f"[ppo] {name}: clip_frac {m['clip_frac']:.6f} (ref {frac_ref:.6f}), approx_kl {m['approx_kl']:.3e}")
     assert m["clip_frac"] == th.tensor(frac_ref, dtype=th.float64).float().item()
-    _close_fwd(th.tensor(m["approx_kl"]), ref["scalars2"][5], f"{name}/two_epochs/approx_kl")
+    REC.fwd(f"{name}/two_epochs/approx_kl", th.tensor(m["approx_kl"]), ref["scalars2"][5])
     for key, j in (("loss", 0), ("entropy", 4)):  # (the last epoch's, recorded only)
-        _record(f"{name}/two_epochs/{key}", th.tensor(m[key]), ref["scalars2"][j], FWD_TOL)
-    sd = model.state_dict()
-    worst = 0.0
-    for n in k.params:
-        ref_upd = ref["after"][n] - k.params[n].double()
-        upd = sd[n].double().cpu() - k.params[n].double()
-        big = (ref["g1"][n].abs() > 1e-6) & (ref["g2"][n].abs() > 1e-6)
-        if big.any():
-            err = (upd[big] - ref_upd[big]).abs().max().item()
-            worst = max(worst, err)
-            assert err <= 2 * 1e-3 * lr, f"{n}: {err:.3e}"
-    _ERRORS[f"{name}/two_epochs/update"] = {"max_err": worst, "tol": 2 * 1e-3 * lr}
-    print(f"[ppo] {name}/two_epochs/update: max err {worst:.3e} (bound {2 * 1e-3 * lr:.1e})")
-    record("ppo_errors", _ERRORS)
+        REC.rec(f"{name}/two_epochs/{key}", th.tensor(m[key]), ref["scalars2"][j], FWD_TOL)
+    REC.check_update(f"{name}/two_epochs", k, model, ref["after"], [ref["g1"], ref["g2"]], lr)
 
 
 # ---- 7: a replay leaves the generator alone -------------------------------------------------------------------------
@@ -470,7 +369,6 @@ def _dp_ppo_worker(rank, world, port, bucketed, out_q):
     from marlclassification_amd.fused import EpisodeDraws
     from marlclassification_amd.parallel import BucketedGradAllReduce, GradAllReduce, broadcast_parameters, shard_bounds
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
     from tests.util import Golden
 
     device = th.device("cuda:0")  # both ranks share the one GPU of the test box
@@ -502,22 +400,8 @@ def _dp_ppo_worker(rank, world, port, bucketed, out_q):
 
 def test_two_rank_ppo_gives_the_same_bits_with_one_and_two_buckets(device):
     import numpy as np
-    import torch.multiprocessing as mp
 
-    from tests.test_gpu_round2 import _free_port
-
-    res = {}
-    for bucketed in (False, True):
-        ctx = mp.get_context("spawn")
-        q = ctx.Queue()
-        port = _free_port()
-        procs = [ctx.Process(target=_dp_ppo_worker, args=(r, 2, port, bucketed, q)) for r in range(2)]
-        for p in procs:
-            p.start()
-        res[bucketed] = q.get(timeout=600)
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
+    res = {bucketed: run_ranks(_dp_ppo_worker, 2, bucketed)[0] for bucketed in (False, True)}
     assert res[False][3] == res[True][3] == 4
     assert np.array_equal(res[False][0], res[True][0]), "parameters differ"
     assert np.array_equal(res[False][1], res[True][1]), "clipped gradients differ"

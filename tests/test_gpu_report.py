@@ -18,6 +18,8 @@ import torch as th
 from marlclassification_amd import _lib
 from marlclassification_amd import report as R
 from marlclassification_amd.report import EpisodeReport, ReportOptions, reference_counts
+from tests.cases import _golden_sampler
+from tests.dp import run_ranks
 from tests.util import record
 
 pytestmark = pytest.mark.gpu
@@ -348,7 +350,6 @@ def test_add_on_a_side_stream(device):
 # ---- 7: trainer -------------------------------------------------------------------------------------------------------
 def test_trainer_metrics_come_from_the_report(device):
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
     from tests.util import Golden
 
     g = Golden("g1_conftest")
@@ -387,7 +388,6 @@ def test_trainer_metrics_come_from_the_report(device):
 
 def test_eval_epoch_fills_a_report(device):
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
     from tests.util import Golden
 
     g = Golden("g1_conftest")
@@ -477,20 +477,7 @@ def _dp_worker(rank, world, port, out_q):
 
 
 def test_two_ranks_all_reduce_to_the_report_of_the_whole_set(device):
-    import torch.multiprocessing as mp
-
-    from tests.test_gpu_round2 import _free_port
-
-    ctx = mp.get_context("spawn")
-    qu = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, qu)) for r in range(2)]
-    for pr in procs:
-        pr.start()
-    gi, gf = qu.get(timeout=600)
-    for pr in procs:
-        pr.join(timeout=120)
-        assert pr.exitcode == 0
+    (gi, gf), = run_ranks(_dp_worker, 2)
     shape = (4, 3, 37, 45)
     p, y, opts = _case(shape)
     single = _report_of(p[:, :, :36].contiguous(), y[:36], opts, device)

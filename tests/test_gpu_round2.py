@@ -6,87 +6,22 @@ bit-exact, fp32 outputs 1e-5, gradients 1e-4 of the tensor's scale."""
 import json
 import math
 import os
-import socket
 
 import pytest
 import torch as th
 
 from oracle import marl_oracle as mo
-from tests.util import Golden, model_spec, uniform_params
+from tests.cases import _golden_sampler
+from tests.dp import run_ranks
+from tests.episode_checks import ATOL, FLIPS, _maxerr
+from tests.episode_checks import check_against_oracle as _check_against_oracle
+from tests.episode_checks import oracle_case as _oracle_case
+from tests.episode_checks import oracle_engine as _engine
+from tests.util import Golden, uniform_params
 
 pytestmark = pytest.mark.gpu
 
-ATOL = 1e-5
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _maxerr(a, b):
-    return (a.detach().cpu().double() - b.double()).abs().max().item()
-
-
-def _engine(cfg, device, na, nb, ns, shape, params, img_u8=False):
-    from marlclassification_amd.engine import HipEngine
-
-    eng = HipEngine(model_spec(cfg), device)
-    eng.configure(na, nb, ns, shape, img_u8=img_u8)
-    eng.pack({k: v.to(device) for k, v in params.items()})
-    return eng
-
-
-def _oracle_case(cfg, na, nb, ns, shape, seed=7):
-    params = uniform_params(cfg, seed)
-    img = th.rand(nb, *shape, generator=th.Generator().manual_seed(seed + 4))
-    y = th.randint(0, cfg.nb_class, (nb,), generator=th.Generator().manual_seed(seed + 5))
-    inp = mo.draw_episode_inputs(cfg, na, nb, ns, shape[1:], seed + 6)
-    return params, img, y, inp
-
-
-def _check_against_oracle(eng, cfg, device, params, img, y, inp, ns, img_dev=None, free_running=True):
-    """Teacher-forced episode + loss + every gradient against the oracle; returns achieved errors."""
-    tr, lo, grads = mo.train_iteration(params, cfg, img, y, inp, ns, 0.99)
-    args = [t.to(device) for t in (inp.pos0, inp.h0, inp.c0, inp.hc0, inp.cc0, inp.q)]
-    img_dev = img.to(device) if img_dev is None else img_dev
-    out = eng.episode_forward(img_dev, *args, tr.step_actions.to(device), True)
-    assert th.equal(out.step_pos.cpu(), tr.step_pos), "agent positions differ"
-    errs = {"preds": _maxerr(out.step_preds, tr.step_preds), "logp": _maxerr(out.step_log_probas, tr.step_log_probas),
-            "values": _maxerr(out.step_values, tr.step_values)}
-    assert max(errs.values()) <= ATOL, errs
-    gp, gl, gv, sc, _ = eng.a2c_loss(out, y.to(device), 0.99)
-    assert abs(sc[0].item() - lo.loss.item()) <= 5e-5 * max(1.0, abs(lo.loss.item()))
-    g_out = {k: th.full_like(v, float("nan"), device=device) for k, v in params.items()}
-    eng.episode_backward(gp, gl, gv, g_out)
-    bad, worst = {}, 0.0
-    for k, ref in grads.items():
-        err = _maxerr(g_out[k], ref)
-        rel = err / (ref.abs().max().item() + 1e-30)
-        worst = max(worst, rel if ref.abs().max().item() > 1e-12 else 0.0)
-        if not err <= 1e-4 * ref.abs().max().item() + 1e-7:
-            bad[k.replace("_ModelsWrapper__", "")] = "%.2e/%.2e" % (err, ref.abs().max().item())
-    assert not bad, "\n".join(f"{k}: {v}" for k, v in bad.items())
-    if free_running:
-        free = eng.episode_forward(img_dev, *args, None, False)
-        nflip = (free.step_actions.cpu() != tr.step_actions).sum().item()
-        allowed = flip_budget(tr, inp, errs["logp"])
-        FLIPS.append({"numel": tr.step_actions.numel(), "flips": nflip, "allowed": allowed})
-        assert nflip <= allowed, f"{nflip} sampled actions differ (budget {allowed})"
-    errs["grad_rel"] = worst
-    return errs
-
-
-FLIPS = []  # (numel, flips, allowed) of every oracle-only free-running comparison of this session
-
-
-def flip_budget(tr, inp, logp_err):
-    """How many sampled indices MAY differ from the oracle's: a sample is argmax_k p_k / q_k
-    (core/agent.py:53-55); it can only flip where the two largest ratios are closer than the
-    relative error of the probabilities.  Counted on the oracle's own probabilities and noise
-    with 4x the measured log-prob error (>= 2e-6) as that relative error: 0 for almost every case."""
-    eps = 4.0 * max(logp_err, 5e-7)
-    if not hasattr(tr, "step_probs") or tr.step_probs is None:
-        return 0
-    ratio = tr.step_probs.double() / inp.q.double().view_as(tr.step_probs)
-    top2 = ratio.topk(2, dim=-1).values
-    return int(((top2[..., 0] - top2[..., 1]) <= eps * top2[..., 0]).sum().item())
 
 
 # ---- (a) the benched size: B = 256, R = 4096 rows, the 128x128 / grouped / split-K plans -----
@@ -374,7 +309,6 @@ def test_backward_of_an_overwritten_episode_raises(device):
     """The engine-level calls share ONE training workspace (the fused Trainer's path): a backward for a
     rollout that a later rollout overwrote is refused.  (Episodes run through autograd own their
     workspace since round 3 - tests/test_gpu_api.py::test_two_live_episodes_accumulate_like_autograd.)"""
-    from tests.test_gpu_api import _golden_sampler
 
     g = Golden("g1_conftest")
     model, sampler = _golden_sampler(g, device)
@@ -392,14 +326,6 @@ def test_backward_of_an_overwritten_episode_raises(device):
 
 
 # ---- data-parallel trainer: HIP path + all-reduce + exact standardize, 2 ranks over gloo --------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _dp_worker(rank, world, port, exact, out_q):
     import torch.distributed as dist
 
@@ -409,7 +335,6 @@ def _dp_worker(rank, world, port, exact, out_q):
     from marlclassification_amd.fused import EpisodeDraws
     from marlclassification_amd.parallel import GradAllReduce, broadcast_parameters, shard_bounds
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
 
     device = th.device("cuda:0")  # both ranks share the one GPU of the test box
     g = Golden("g2_mnist_c1")
@@ -438,20 +363,9 @@ def test_two_rank_hip_trainer_matches_big_batch_update(device, exact):
     all-reduce (+ the exact-standardize exchange): with global statistics the averaged gradient
     and the Adam update equal the REFERENCE's big-batch gradient / update of the fixture; with
     per-shard statistics they equal the mean of the oracle's shard gradients."""
-    import torch.multiprocessing as mp
-
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, exact, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    sd, flat_grads = q.get(timeout=600)
+    (sd, flat_grads), = run_ranks(_dp_worker, 2, exact)
     sd = {k: th.from_numpy(v) for k, v in sd.items()}
     flat_grads = th.from_numpy(flat_grads)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
     g = Golden("g2_mnist_c1")
     names = list(g.params)
     if exact:

@@ -129,7 +129,7 @@ def test_reference_parity_on_the_forced_image_path(device):
     Adam 1e-3 lr.  (The default knobs switch this path on from 128-unit cells / 32768 rows: the benched-size
     tests of rounds 2 and 3 run it as shipped.)"""
     from marlclassification_amd import _lib
-    from tests import test_gpu_episode as E0
+    from tests import episode_checks as E0
 
     with image_path():
         g = Golden("g2_mnist_c1")
@@ -141,10 +141,10 @@ def test_reference_parity_on_the_forced_image_path(device):
         eng.lib.marl_tune(b"g3", 1)
         assert sz[0].value > sz[2].value and sz[1].value > sz[3].value, "image layout not selected"
         for train in (True, False):
-            E0.test_rollout_matches_reference(device, "g2_mnist_c1", train)
-        E0.test_backward_and_adam_match_reference(device, "g2_mnist_c1")
-        E0.test_loss_and_output_gradients(device, "g2_mnist_c1")
-        E0.test_backward_resisc_dims_gradient_samples(device)
+            E0.rollout_matches_reference(device, "g2_mnist_c1", train)
+        E0.backward_and_adam_match_reference(device, "g2_mnist_c1")
+        E0.loss_and_output_gradients(device, "g2_mnist_c1")
+        E0.backward_resisc_dims_gradient_samples(device)
 
 
 @pytest.mark.parametrize("tag", ["g2_mnist_c1", "g4_resisc_b2"])
@@ -221,7 +221,7 @@ def test_full_size_c4_c5_replicas_match_the_oracle(device, tag, rep):
     tiled batch's gradient is the small batch's: every gradient entry within 1e-4 of its tensor's scale."""
     from marlclassification_amd.engine import HipEngine
     from oracle import marl_oracle as mo
-    from tests.test_gpu_episode import ATOL, BIG_CASES, _maxerr
+    from tests.episode_checks import ATOL, BIG_CASES, _maxerr
     from tests.util import uniform_params
 
     cfg, na, nb, ns, shape = BIG_CASES[tag]
@@ -290,9 +290,9 @@ def test_edge_sizes_match_the_oracle(device, na, nb, ns, shape):
     """Smallest / ragged episode shapes (empty-ish and ragged inputs): teacher-forced rollout,
     loss and EVERY gradient against the oracle, then the free-running trajectory."""
     from oracle import marl_oracle as mo
-    from tests.test_gpu_round2 import _check_against_oracle, _engine as engine2, _oracle_case
+    from tests.episode_checks import check_against_oracle, oracle_case, oracle_engine
 
     cfg = mo.OracleConfig("mnist", 6, 32, 32, 8, 12, 8, 10, 48, 48)
-    params, img, y, inp = _oracle_case(cfg, na, nb, ns, shape)
-    eng = engine2(cfg, device, na, nb, ns, shape, params)
-    _check_against_oracle(eng, cfg, device, params, img, y, inp, ns)
+    params, img, y, inp = oracle_case(cfg, na, nb, ns, shape)
+    eng = oracle_engine(cfg, device, na, nb, ns, shape, params)
+    check_against_oracle(eng, cfg, device, params, img, y, inp, ns)

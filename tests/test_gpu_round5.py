@@ -9,6 +9,7 @@ import torch as th
 
 from oracle import marl_oracle as mo
 from tests.util import PLAN_INVARIANTS, Golden, assert_witness, distinct_image_parity, model_spec, plan_witness
+from tests.util import run_update as _run
 
 pytestmark = pytest.mark.gpu
 
@@ -76,24 +77,6 @@ def test_full_size_parity_on_distinct_shuffled_images(device, tag):
 
 
 # ---- weights workspace: batch-independent layout, invalidated by layout knobs -------------------------
-def _slice_case(g, nb):
-    i = g.inp
-    return (g.img[:nb], mo.EpisodeInputs(i.pos0[:, :nb].contiguous(), i.h0[:, :nb].contiguous(),
-                                         i.c0[:, :nb].contiguous(), i.hc0[:, :nb].contiguous(),
-                                         i.cc0[:, :nb].contiguous(), i.q[:, :, :nb].contiguous()))
-
-
-def _run(eng, g, device, nb, train=True):
-    img, i = _slice_case(g, nb)
-    eng.configure(g.na, nb, g.ns, g.img.shape[1:])
-    out = eng.episode_forward(img.to(device), i.pos0.to(device), i.h0.to(device), i.c0.to(device), i.hc0.to(device),
-                              i.cc0.to(device), i.q.to(device), None, train)
-    gp, gl, gv, sc, _ = eng.a2c_loss(out, g.y[:nb].to(device), g.gamma)
-    grads = {k: th.zeros_like(v, device=device) for k, v in g.params.items()}
-    eng.episode_backward(gp, gl, gv, grads)
-    return out, {k: v.cpu() for k, v in grads.items()}
-
-
 @pytest.mark.parametrize("order", [(2, 1, 2), (1, 2, 1)])
 def test_weights_layout_does_not_move_with_the_batch(device, order):
     """with 16 agents, batch 2 gives R = 32 rows (image GEMMs on), batch 1 gives R = 16 (off).

@@ -5,8 +5,10 @@ left is pinned here).  Everything goes through the C ABI."""
 import pytest
 import torch as th
 
-from tests.test_gpu_round5 import _run
-from tests.util import Golden, library_knobs, model_spec
+from tests.cases import _golden_sampler
+from tests.dp import run_ranks
+from tests.util import KNOB_DEFAULTS, Golden, library_knobs, model_spec
+from tests.util import run_update as _run
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +58,6 @@ def _dp_bucket_worker(rank, world, port, bucketed, out_q):
     from marlclassification_amd.fused import EpisodeDraws
     from marlclassification_amd.parallel import BucketedGradAllReduce, GradAllReduce, broadcast_parameters, shard_bounds
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
 
     device = th.device("cuda:0")  # both ranks share the one GPU of the test box
     g = Golden("g2_mnist_c1")
@@ -86,22 +87,7 @@ def test_two_bucket_allreduce_gives_the_one_bucket_update(device):
     records ahead of the reverse loop (marl_backward_heads_event), the rest behind the backward pass - two HIP
     Trainer processes over gloo: parameters and summed gradients after two steps are BIT-equal to the single
     all-reduce of the flat buffer."""
-    import torch.multiprocessing as mp
-
-    from tests.test_gpu_round2 import _free_port
-
-    res = {}
-    for bucketed in (False, True):
-        ctx = mp.get_context("spawn")
-        q = ctx.Queue()
-        port = _free_port()
-        procs = [ctx.Process(target=_dp_bucket_worker, args=(r, 2, port, bucketed, q)) for r in range(2)]
-        for p in procs:
-            p.start()
-        res[bucketed] = q.get(timeout=600)
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
+    res = {bucketed: run_ranks(_dp_bucket_worker, 2, bucketed)[0] for bucketed in (False, True)}
     import numpy as np
 
     assert np.array_equal(res[False][0], res[True][0]), "parameters differ"
@@ -120,10 +106,6 @@ KNOB_CASES = [("g3", 0), ("g3_lstm", 0), ("g3_tn", 0), ("g3_tn", 2), ("g3_min_un
               ("g3_tn_cell", 0), ("g3_tn_pipe", 0), ("g3_tn_wgs", 64), ("nt_xcd", 0), ("tn_xcd", 0), ("panel_chain", 0),
               ("red_defer", 0), ("red_defer", 1), ("red_defer", 2), ("tn_split_waves", 4), ("wgrad3", 0), ("cnn_fwd2", 0),
               ("cnn_fwd3", 0), ("dgrad_wgs", 5), ("dgrad_min_chunks", 1)]
-KNOB_DEFAULTS = {"g3": 1, "g3_lstm": 1, "g3_tn": 1, "g3_min_units": 64, "g3_safe": 0, "mfma_split": 1, "g3_lstm_variant": 0,
-                 "g3_nt_variant": 0, "g3_tn_variant": 0, "g3_tn_cell": 1, "g3_tn_pipe": 1, "g3_tn_wgs": 256, "nt_xcd": 1, "tn_xcd": 1,
-                 "panel_chain": 1, "red_defer": 3, "tn_split_waves": 8, "wgrad3": 1, "cnn_fwd2": 1, "cnn_fwd3": 1, "dgrad_wgs": 0,
-                 "dgrad_min_chunks": 512}
 
 
 @pytest.mark.parametrize("knob,value", KNOB_CASES, ids=[f"{k}={v}" for k, v in KNOB_CASES])
@@ -132,7 +114,7 @@ def test_every_knob_value_keeps_reference_parity(device, knob, value):
     with ONE knob moved off its default: positions / actions bit-exact, logits / log-probs / values 1e-5, loss
     scalars, every gradient 1e-4 of its tensor's scale, the Adam update - the checks of tests/test_gpu_episode.py."""
     from marlclassification_amd import engine as E
-    from tests import test_gpu_episode as E0
+    from tests import episode_checks as E0
 
     assert set(k for k, _ in KNOB_CASES) <= set(KNOB_DEFAULTS)
     try:
@@ -140,9 +122,9 @@ def test_every_knob_value_keeps_reference_parity(device, knob, value):
         if knob == "g3_tn_variant":  # (the row-contraction plans only run where the image weight gradients do)
             E.tune("g3_tn", 2)
         for tag in ("g2_mnist_c1", "g4_resisc_b2"):
-            E0.test_rollout_matches_reference(device, tag, True)
-        E0.test_backward_and_adam_match_reference(device, "g2_mnist_c1")
-        E0.test_backward_resisc_dims_gradient_samples(device)
+            E0.rollout_matches_reference(device, tag, True)
+        E0.backward_and_adam_match_reference(device, "g2_mnist_c1")
+        E0.backward_resisc_dims_gradient_samples(device)
     finally:
         E.tune(knob, KNOB_DEFAULTS[knob])
         E.tune("g3_tn", 1)

@@ -2,12 +2,12 @@
 loss_rewards_kernel) - through the three loss entries and marl_advantages, the trainer, hipGraph replay, two ranks and
 ``train --mix``.  The reference is float64 torch: ``class_loss.vote_error(targets=)`` / ``class_loss.rewards(targets=)``
 (themselves held to ``F.cross_entropy`` with probabilities by tests/test_mix_host.py) fed into the restatement of the
-remaining loss that tests/test_gpu_class_loss.py uses.  Bounds are that file's: FWD_TOL 1e-5 (x max(1, |ref|)) for
-forward quantities and scalars, GRAD_TOL 1e-4 of the tensor's scale for gradients, UPDATE_TOL 2e-3 lr for an Adam
-update.  Achieved errors go through ``tests.util.record`` (profiles/mix_errors.json).
+remaining loss in tests/loss_ref.py, with the targets ``q`` given.  Bounds are those of tests/parity.py: FWD_TOL 1e-5
+(x max(1, |ref|)) for forward quantities and scalars, GRAD_TOL 1e-4 of the tensor's scale for gradients, UPDATE_TOL
+2e-3 lr for an Adam update.  Achieved errors go through its ``Recorder`` (profiles/mix_errors.json).
 
-Shapes are that file's too: nC = 3 (less than a wave), 45, 70 (a second lane-stride pass with a ragged tail); Na = 1, 3
-with Nb = 5, Ns = 3; and Na = 16, Nb = 6 (Ns R = 288 > 256)."""
+Shapes are those of tests/loss_cases.py: nC = 3 (less than a wave), 45, 70 (a second lane-stride pass with a ragged
+tail); Na = 1, 3 with Nb = 5, Ns = 3; and Na = 16, Nb = 6 (Ns R = 288 > 256)."""
 import dataclasses
 
 import pytest
@@ -16,40 +16,22 @@ import torch.nn.functional as F
 
 from marlclassification_amd import class_loss as cl
 from oracle import marl_oracle as mo
-from tests.test_gpu_class_loss import (A2C_SCALARS, BETA, GAMMA, PPO_SCALARS, SHAPES, STEP_W, UPDATE_TOL, _engine,
-                                       _entries, _grads_of, _leaves, _setting, _t, _trainer_options, all_on, synthetic,
-                                       under, weights)
-from tests.test_gpu_policy_dist import _engine_episode, _oracle_loop, _sampler, masked_entropy
-from tests.test_gpu_ppo import TWO_EPOCH, assert_clear_of_bounds, clip_mask
-from tests.test_gpu_step_autograd import FWD_TOL, GRAD_TOL, NS, Case, _close
-from tests.test_ppo_host import gae, ratio_deltas
-from tests.util import model_spec, record
+from tests import loss_ref as ref64
+from tests.cases import (NS, TWO_EPOCH, Case, _engine_episode, _golden_sampler, _grads_of, _oracle_loop, _sampler)
+from tests.dp import run_ranks
+from tests.loss_cases import (BETA, GAMMA, SHAPES, STEP_W, _engine, _entries, _setting, _trainer_options, all_on,
+                              check_entries, synthetic, weights)
+from tests.loss_ref import assert_clear_of_bounds, soft, under
+from tests.parity import GRAD_TOL, UPDATE_TOL, Recorder
+from tests.parity import close as _close
+from tests.util import model_spec
 
 pytestmark = pytest.mark.gpu
 
-_ERRORS = {}
+REC = Recorder("mix_errors", "soft_targets")
 
 
-def _record(tag, got, ref, tol):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    err, scale = (got - ref).abs().max().item(), ref.abs().max().item()
-    _ERRORS[tag] = {"max_err": err, "ref_max": scale, "tol": tol}
-    print(f"[soft_targets] {tag}: max err {err:.3e}, ref max {scale:.3e}, tol {tol:g}")
-    record("mix_errors", _ERRORS)
-
-
-def _close_fwd(got, ref, what):
-    _record(what, got, ref, FWD_TOL)
-    err = (got.detach().double().cpu() - ref.detach().double().cpu()).abs().max().item()
-    assert err <= FWD_TOL * max(1.0, ref.abs().max().item()), f"{what}: max err {err:.3e}"
-
-
-def _close_grad(got, ref, what):
-    _record(what, got, ref, GRAD_TOL)
-    _close(got, ref, GRAD_TOL, what)
-
-
-# ---- targets and the float64 reference ----------------------------------------------------------------------------
+# ---- targets ------------------------------------------------------------------------------------------------------
 def dense_targets(nb, nc, seed=0):
     """fp32 [nb, nc], rows summing to 1 (up to rounding): dense, but with exact zeros in row 1 and row 0 one-hot"""
     q = th.rand(nb, nc, generator=th.Generator().manual_seed(300 + seed + nb * nc)) + 0.05
@@ -57,64 +39,6 @@ def dense_targets(nb, nc, seed=0):
     q[0] = 0.0
     q[0, nc - 1] = 1.0
     return (q / q.sum(dim=1, keepdim=True)).float()
-
-
-class soft:
-    """``with soft(eng, q):`` - the engine's loss calls run under the targets ``q`` (None: the labels)."""
-
-    def __init__(self, eng, q):
-        self.eng, self.q = eng, q
-
-    def __enter__(self):
-        self.eng.set_soft_targets(self.q)
-
-    def __exit__(self, *exc):
-        self.eng.set_soft_targets(None)
-
-
-def _opts(c):
-    if c is None:
-        return None, 0.0, None, False
-    return _t(c.class_weights), c.label_smoothing, _t(c.step_weights), c.weight_rewards
-
-
-def ref_error(preds, y, c, q):
-    w, eps, sw, _ = _opts(c)
-    return cl.vote_error(preds, y, w, eps, sw, targets=None if q is None else q.double()).unsqueeze(1)
-
-
-def ref_rewards(preds, y, c, q):
-    w, _, _, wrew = _opts(c)
-    return cl.rewards(preds.detach(), y, w if wrew else None, targets=None if q is None else q.double())
-
-
-def ref_a2c(preds, logp, values, probs, y, gamma, beta, c, q):
-    error = ref_error(preds, y, c, q)
-    returns = mo.discounted_returns(ref_rewards(preds, y, c, q), gamma)
-    adv = mo.standardize(returns - values.detach())
-    path = -logp * adv
-    critic = F.smooth_l1_loss(values, returns, reduction="none")
-    ent = masked_entropy(probs) if beta > 0 else th.zeros_like(logp)
-    loss = th.sum(path + error + critic, 0).mean() - beta * ent.sum(0).mean()
-    return loss, th.stack([loss, path.sum(0).mean(), error.mean(), critic.sum(0).mean(), ent.mean()]).detach()
-
-
-def ref_advantages(preds, values, y, gamma, lam, c, q):
-    adv, ret = gae(ref_rewards(preds, y, c, q), values.detach(), gamma, lam)
-    return mo.standardize(adv), ret
-
-
-def ref_ppo(preds, logp, values, probs, y, old_logp, advn, ret, eps, beta, c, q):
-    error = ref_error(preds, y, c, q)
-    rho = (logp - old_logp).exp()
-    surr = -th.minimum(rho * advn, rho.clamp(1 - eps, 1 + eps) * advn)
-    critic = F.smooth_l1_loss(values, ret, reduction="none")
-    ent = masked_entropy(probs) if beta > 0 else th.zeros_like(logp)
-    loss = th.sum(surr + error + critic, 0).mean() - beta * ent.sum(0).mean()
-    clipped = clip_mask(rho.detach(), advn, eps)
-    scalars = th.stack([loss, surr.sum(0).mean(), error.mean(), critic.sum(0).mean(), ent.mean(),
-                        (old_logp - logp).mean(), clipped.double().mean()]).detach()
-    return loss, scalars, rho.detach()
 
 
 def entries(eng, out, y, device, c=None, q=None):
@@ -128,65 +52,7 @@ def check_all_entries(eng, out, y, c, q, tag, device):
     the options ``c`` and the targets ``q`` (host fp32) against float64; phases 1 + 2 against phase 0 and a second run,
     bit for bit.  ``y`` is passed and must not be read."""
     with under(eng, c), soft(eng, q.to(device)):
-        return _check_all_entries(eng, out, y, c, q, tag, device)
-
-
-def _check_all_entries(eng, out, y, c, q, tag, device):
-    yd = y.to(device)
-    kept = {}
-    for beta in (0.0, BETA):
-        bufs = [t.clone() for t in eng.a2c_loss(out, yd, GAMMA, entropy_coef=beta)]
-        lv = _leaves(out)
-        loss, ref_scalars = ref_a2c(*lv, y, GAMMA, beta, c, q)
-        loss.backward()
-        for j, what in enumerate(A2C_SCALARS[:bufs[3].numel()]):
-            _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/a2c/beta{beta}/scalar_{what}")
-        grads = [bufs[0], bufs[1], bufs[2]] + ([bufs[5]] if beta > 0 else [])
-        for got, leaf, what in zip(grads, lv, ("g_preds", "g_logp", "g_values", "g_probs")):
-            _close_grad(got, leaf.grad, f"{tag}/a2c/beta{beta}/{what}")
-        assert all(bool(th.isfinite(t).all()) for t in bufs)
-        two = eng.new_loss_bufs(out, beta > 0)
-        eng.a2c_loss(out, yd, GAMMA, 1, two, entropy_coef=beta)
-        eng.a2c_loss(out, yd, GAMMA, 2, two, entropy_coef=beta)
-        again = eng.a2c_loss(out, yd, GAMMA, entropy_coef=beta)
-        for a, b, d in zip(bufs, two, again):
-            assert th.equal(a, b), "a2c_loss: phases 1 + 2 differ from phase 0"
-            assert th.equal(a, d), "a2c_loss: two runs differ"
-        kept[f"a2c{beta}"] = bufs
-    for lam in (1.0, 0.9):
-        adv = [t.clone() for t in eng.advantages(out, yd, GAMMA, lam)]
-        advn64, ret64 = ref_advantages(out.step_preds.double().cpu(), out.step_values.double().cpu(), y, GAMMA, lam, c,
-                                       q)
-        _close_fwd(adv[5], advn64, f"{tag}/lam{lam}/advn")
-        _close_fwd(adv[6], ret64, f"{tag}/lam{lam}/ret")
-        two = eng.new_ppo_bufs(out, True)
-        eng.advantages(out, yd, GAMMA, lam, 1, two)
-        eng.advantages(out, yd, GAMMA, lam, 2, two)
-        again = eng.advantages(out, yd, GAMMA, lam)
-        for j in (4, 5, 6):
-            assert th.equal(adv[j], two[j]), "advantages: phases 1 + 2 differ from phase 0"
-            assert th.equal(adv[j], again[j]), "advantages: two runs differ"
-        kept[f"adv{lam}"] = adv
-    advn, ret = kept["adv0.9"][5], kept["adv0.9"][6]
-    old_logp = out.step_log_probas - ratio_deltas(out.step_log_probas.shape).float().to(device)
-    eps = 0.1
-    for beta in (0.0, BETA):
-        bufs = [t.clone() for t in eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)]
-        lv = _leaves(out)
-        loss, ref_scalars, rho = ref_ppo(*lv, y, old_logp.double().cpu(), advn.double().cpu(), ret.double().cpu(),
-                                         eps, beta, c, q)
-        assert_clear_of_bounds(rho, eps)
-        loss.backward()
-        for j, what in enumerate(PPO_SCALARS):
-            _close_fwd(bufs[3][j], ref_scalars[j], f"{tag}/ppo/beta{beta}/scalar_{what}")
-        grads = [bufs[0], bufs[1], bufs[2]] + ([bufs[7]] if beta > 0 else [])
-        for got, leaf, what in zip(grads, lv, ("g_preds", "g_logp", "g_values", "g_probs")):
-            _close_grad(got, leaf.grad, f"{tag}/ppo/beta{beta}/{what}")
-        again = eng.ppo_loss(out, yd, old_logp, advn, ret, eps, entropy_coef=beta)
-        for j in (0, 1, 2, 3) + ((7,) if beta > 0 else ()):
-            assert th.equal(bufs[j], again[j]), "ppo_loss: two runs differ"
-        kept[f"ppo{beta}"] = bufs
-    return kept
+        return check_entries(REC, eng, out, y, c, q, tag, device)
 
 
 # ---- 1: float64 parity under dense targets ------------------------------------------------------------------------
@@ -279,24 +145,6 @@ def test_zero_targets_beside_a_logit_of_minus_infinity_stay_finite(device, nc):
 
 
 # ---- 4: through the trainer ---------------------------------------------------------------------------------------
-def _check_update(tag, k, model, after, grad_sets, lr):
-    sd = model.state_dict()
-    worst = 0.0
-    for n in k.params:
-        ref_upd = after[n] - k.params[n].double()
-        upd = sd[n].double().cpu() - k.params[n].double()
-        big = th.ones_like(upd, dtype=th.bool)
-        for g in grad_sets:
-            big &= g[n].abs() > 1e-6
-        if big.any():
-            err = (upd[big] - ref_upd[big]).abs().max().item()
-            worst = max(worst, err)
-            assert err <= UPDATE_TOL * lr, f"{n}: {err:.3e}"
-    _ERRORS[f"{tag}/update"] = {"max_err": worst, "tol": UPDATE_TOL * lr}
-    print(f"[soft_targets] {tag}/update: max err {worst:.3e} (bound {UPDATE_TOL * lr:.1e})")
-    record("mix_errors", _ERRORS)
-
-
 def _mixed_targets(y, nc, seed=0):
     """What a CutMix / Mixup loader yields for the labels ``y``: (primary labels, Q) from a drawn mix"""
     from marlclassification_amd import mix
@@ -324,15 +172,15 @@ def test_train_step_under_targets_matches_the_float64_oracle_update(device):
 
     p64 = k.params64()
     tr = _oracle_loop(k, p64, k.img.double())
-    loss, scalars = ref_a2c(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, gamma, beta, _setting(k, opts), q)
+    loss, scalars = ref64.a2c(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, gamma, beta, _setting(k, opts), q)
     loss.backward()
-    _close_fwd(th.tensor(m["loss"]), scalars[0], "trainer/a2c/loss")
-    _close_fwd(th.tensor(m["error"]), scalars[2], "trainer/a2c/error")
+    REC.fwd("trainer/a2c/loss", th.tensor(m["loss"]), scalars[0])
+    REC.fwd("trainer/a2c/error", th.tensor(m["error"]), scalars[2])
     grads = _grads_of(p64)
     after = {n: v.detach().clone() for n, v in p64.items()}
     mo.adam_step(after, grads, {n: th.zeros_like(v) for n, v in after.items()},
                  {n: th.zeros_like(v) for n, v in after.items()}, 1, lr)
-    _check_update("trainer/a2c", k, model, after, [grads], lr)
+    REC.check_update("trainer/a2c", k, model, after, [grads], lr)
 
     # the label trainer moves the weights elsewhere: the targets reached the update
     plain = k.model(device)
@@ -355,9 +203,9 @@ def test_two_ppo_epochs_under_targets_match_the_float64_oracle_update(device):
     p = k.params64()
     img64 = k.img.double()
     tr = _oracle_loop(k, p, img64)
-    advn, ret = ref_advantages(tr["preds"], tr["values"], y, gamma, lam, None, q)
+    advn, ret, _ = ref64.advantages(tr["preds"], tr["values"], y, gamma, lam, None, q)
     old_logp = tr["logp"].detach()
-    loss, _, _ = ref_ppo(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, old_logp, advn, ret, eps, beta, None, q)
+    loss = ref64.ppo(tr["preds"], tr["logp"], tr["values"], tr["probs"], y, old_logp, advn, ret, eps, beta, None, q)[0]
     loss.backward()
     g1 = _grads_of(p)
     after = {n: v.detach().clone() for n, v in p.items()}
@@ -366,8 +214,8 @@ def test_two_ppo_epochs_under_targets_match_the_float64_oracle_update(device):
     mo.adam_step(after, g1, m1, v1, 1, lr)
     p2 = {n: v.clone().requires_grad_() for n, v in after.items()}
     tr2 = _oracle_loop(k, p2, img64, forced=tr["act"])
-    loss2, sc2, rho = ref_ppo(tr2["preds"], tr2["logp"], tr2["values"], tr2["probs"], y, old_logp, advn, ret, eps,
-                              beta, None, q)
+    loss2, _, rho, _ = ref64.ppo(tr2["preds"], tr2["logp"], tr2["values"], tr2["probs"], y, old_logp, advn, ret, eps,
+                                 beta, None, q)
     assert_clear_of_bounds(rho, eps)
     loss2.backward()
     g2 = _grads_of(p2)
@@ -378,7 +226,7 @@ def test_two_ppo_epochs_under_targets_match_the_float64_oracle_update(device):
     trainer = Trainer(model, k.cfg.nb_class, lr, gamma, ppo_epochs=2, ppo_clip=eps, gae_lambda=lam, entropy_coef=beta)
     trainer.train_step(k.img, yp, sampler, targets=q.to(device))  # (same batch, same Q in both epochs)
     assert model.flat_state().step == 2
-    _check_update("trainer/ppo", k, model, after, [g1, g2], lr)
+    REC.check_update("trainer/ppo", k, model, after, [g1, g2], lr)
 
 
 def test_fused_iteration_is_the_trainers_step(device):
@@ -474,7 +322,6 @@ def _dp_worker(rank, world, port, out_q):
     from marlclassification_amd.fused import EpisodeDraws
     from marlclassification_amd.parallel import GradAllReduce, broadcast_parameters, shard_bounds
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
     from tests.util import Golden
 
     device = th.device("cuda:0")  # both ranks share the one GPU of the test box
@@ -503,23 +350,10 @@ def test_two_ranks_take_the_big_batch_update(device):
     """Two processes, each on half of the G2 batch and its half of Q, with the flat-gradient all-reduce and the
     exact-standardize exchange (phases 1 and 2 under the targets), two steps; the reference is the single-process
     trainer on the whole batch under the whole Q - itself held to float64 by the trainer tests above."""
-    import torch.multiprocessing as mp
-
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_api import _golden_sampler
-    from tests.test_gpu_round2 import _free_port
     from tests.util import Golden
 
-    ctx = mp.get_context("spawn")
-    qu = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, qu)) for r in range(2)]
-    for p in procs:
-        p.start()
-    sd, flat_grads = qu.get(timeout=600)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    (sd, flat_grads), = run_ranks(_dp_worker, 2)
     sd = {n: th.from_numpy(v) for n, v in sd.items()}
     flat_grads = th.from_numpy(flat_grads)
 
@@ -542,8 +376,7 @@ def test_two_ranks_take_the_big_batch_update(device):
         moved = moved or bool((upd != 0).any())
         assert err <= UPDATE_TOL * g.lr, f"{n}: {err:.3e}"
     assert moved
-    _ERRORS["two_ranks/update"] = {"max_err": worst, "tol": UPDATE_TOL * g.lr}
-    record("mix_errors", _ERRORS)
+    REC.put("two_ranks/update", {"max_err": worst, "tol": UPDATE_TOL * g.lr})
 
 
 # ---- 6: guards, and nothing stays installed -------------------------------------------------------------------------

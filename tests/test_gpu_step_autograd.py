@@ -5,81 +5,15 @@ message / recurrent state are checked against float64 autograd through the oracl
 against the fused episode node (_EpisodeFunction)."""
 import pytest
 import torch as th
-import torch.nn.functional as F
 
 from oracle import marl_oracle as mo
-from tests.util import Golden, uniform_params
+from tests.cases import CASES, NS, Case, _a2c_like_loss, _act_loop, _loss_terms
+from tests.parity import GRAD_TOL
+from tests.parity import close as _close
+from tests.parity import close_fwd as _close_fwd
+from tests.parity import param_grads_match as _param_grads_match
 
 pytestmark = pytest.mark.gpu
-
-NS = 3
-FWD_TOL = 1e-5   # forward outputs (x max(1, |ref|))
-GRAD_TOL = 1e-4  # gradients (x max |ref|), the project's gradient tolerance
-STRIDE3 = [[3, 0], [-3, 0], [0, 3], [0, -3]]
-
-# name -> (config, Na, Nb, image [C, H, W], seed); "g1" takes everything from the g1_conftest fixture
-CASES = {
-    "g1": None,
-    "resisc3": (mo.OracleConfig("resisc45", 12, 32, 32, 8, 12, 8, 10, 48, 48), 3, 4, (3, 40, 40), 11),
-    "aid4": (mo.OracleConfig("aid", 16, 32, 32, 8, 12, 8, 5, 48, 48, actions=STRIDE3), 3, 4, (3, 48, 48), 12),
-    "na1": (mo.OracleConfig("mnist", 12, 23, 22, 21, 20, 19, 10, 24, 25), 1, 5, (1, 28, 28), 13),
-    # nA = 6 and nla = 400: the heads' backward without the rank-kin LayerNorm kernel (and, with nla past
-    # the panel limit, the unfused message chain)
-    "wide": (mo.OracleConfig("mnist", 12, 23, 22, 21, 20, 19, 10, 24, 400,
-                             actions=[[1, 0], [-1, 0], [0, 1], [0, -1], [0, 0], [2, 2]]), 2, 5, (1, 28, 28), 14),
-}
-
-
-class Case:
-    def __init__(self, name):
-        if CASES[name] is None:
-            g = Golden("g1_conftest")
-            self.cfg, self.na, self.nb, self.params, self.img = g.cfg, g.na, g.nb, g.params, g.img
-            self.inp = g.inp
-            seed = 10
-        else:
-            self.cfg, self.na, self.nb, shape, seed = CASES[name]
-            self.params = uniform_params(self.cfg, seed)
-            self.img = th.rand(self.nb, *shape, generator=th.Generator().manual_seed(seed))
-            self.inp = mo.draw_episode_inputs(self.cfg, self.na, self.nb, NS, list(shape[1:]), seed)
-        self.gen = th.Generator().manual_seed(seed + 1000)
-        self.sizes = list(self.img.shape[2:])
-
-    def randn(self, *shape):
-        return th.randn(*shape, generator=self.gen)
-
-    def model(self, device):
-        from marlclassification_amd.networks import ModelsWrapper
-        from marlclassification_amd.networks.vision import AidCnn, MnistCnn, Resisc45Cnn
-
-        c = self.cfg
-        cnn = {"mnist": MnistCnn, "resisc45": Resisc45Cnn, "aid": AidCnn}[c.ft_extr](c.window)
-        m = ModelsWrapper(cnn, c.n_b, c.n_a, c.n_m, c.n_m_o, c.n_d, 2, c.nb_action, c.nb_class, c.nlb, c.nla)
-        m.load_state_dict(self.params)
-        return m.to(device)
-
-    def params64(self):
-        return {k: v.double().requires_grad_() for k, v in self.params.items()}
-
-
-def _close(got, ref, tol, what):
-    got = got.detach().double().cpu()
-    # (no float64 gradient: the oracle's graph does not reach this tensor - Na = 1 has no message path)
-    ref = th.zeros_like(got) if ref is None else ref.detach().double().cpu()
-    assert got.shape == ref.shape, what
-    err = (got - ref).abs().max().item() if ref.numel() else 0.0
-    assert err <= tol * ref.abs().max().item() + 1e-7, f"{what}: max err {err:.3e} (ref max {ref.abs().max().item():.3e})"
-
-
-def _close_fwd(got, ref, what):
-    err = (got.detach().double().cpu() - ref.detach().double()).abs().max().item()
-    assert err <= FWD_TOL * max(1.0, ref.abs().max().item()), f"{what}: max err {err:.3e}"
-
-
-def _param_grads_match(model, p64, tol=GRAD_TOL):
-    for k, p in model.named_parameters():
-        assert p.grad is not None, f"{k}: no gradient"
-        _close(p.grad, p64[k].grad, tol, k)
 
 
 # ---- 1: ModelsWrapper.forward unrolled over 3 steps, every output in the loss ----------------------------------
@@ -133,26 +67,6 @@ def test_forward_unroll_matches_float64_oracle(device, name):
 
 
 # ---- 2 / 3: MultiAgent.act loop ------------------------------------------------------------------------------
-def _act_loop(k, model, device):
-    from marlclassification_amd.core import Environment, MultiAgent
-    from marlclassification_amd.networks.models import RecurrentOutput
-
-    i = k.inp
-    agents, env = MultiAgent(k.na, model), Environment(k.cfg.actions, k.cfg.window)
-    env.place(k.img.to(device), k.na, positions=i.pos0.to(device))
-    obs = env.observe()
-    agents.reset(k.nb)
-    agents._MultiAgent__hidden = RecurrentOutput(*(t.to(device) for t in (i.h0, i.c0, i.hc0, i.cc0)))
-    acc = {"preds": [], "logp": [], "values": [], "act": [], "pos": []}
-    for t in range(NS):
-        agents.fixed_noise = i.q[t].to(device)
-        o = agents.act(obs, env.normalized_positions)
-        obs = env.step(o.actions)
-        for key, v in zip(acc, (o.predictions, o.actions_log_probs, o.values, o.actions, env.positions)):
-            acc[key].append(v)
-    return {key: th.stack(v) for key, v in acc.items()}
-
-
 def _oracle_act_loop(k, p64):
     """The same loop in float64 (oracle run_episode with a float64 message)."""
     c, i = k.cfg, k.inp
@@ -172,20 +86,6 @@ def _oracle_act_loop(k, p64):
         for key, v in zip(acc, (so.preds, logp, so.values, a)):
             acc[key].append(v)
     return {key: th.stack(v) for key, v in acc.items()}
-
-
-def _loss_terms(k):
-    na, nb, c = k.na, k.nb, k.cfg
-    adv = k.randn(NS, na, nb)
-    y = th.randint(c.nb_class, (NS, na, nb), generator=k.gen)
-    ret = k.randn(NS, na, nb)
-    return adv, y, ret
-
-
-def _a2c_like_loss(preds, logp, values, terms):
-    adv, y, ret = (t.to(preds.device) for t in terms)
-    ce = F.cross_entropy(preds.flatten(0, 2), y.flatten(), reduction="sum")
-    return -(logp * adv.to(logp.dtype)).sum() + ce + F.mse_loss(values, ret.to(values.dtype), reduction="sum")
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -13,11 +13,13 @@ import pytest
 import torch as th
 
 from marlclassification_amd import augment, warp
+from tests.buffers import SENTINEL
+from tests.buffers import guarded as _guarded
+from tests.buffers import guards_intact as _guards_intact
+from tests.buffers import same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256  # bytes before and after every destination
-SENTINEL = 0xA5
 N_SRC = 7
 FRAME = 2  # rows in front of and behind the source rows
 FILL = {th.uint8: 250, th.float32: -1.5}
@@ -58,24 +60,6 @@ def _nothing_from_the_frame(got):
     if got.dtype == th.uint8:
         return bool((got >= 16).all())
     return bool((got.abs() < 1e6).all())
-
-
-def _guarded(shape, dtype, device, offset=0):
-    """(whole buffer, destination view): ``offset`` extra bytes in front of the view"""
-    nbytes = th.Size(shape).numel() * th.empty((), dtype=dtype).element_size()
-    buf = th.full((GUARD + offset + nbytes + GUARD,), SENTINEL, dtype=th.uint8, device=device)
-    return buf, buf[GUARD + offset: GUARD + offset + nbytes].view(dtype).view(shape)
-
-
-def _guards_intact(buf, offset, nbytes):
-    head, tail = buf[: GUARD + offset], buf[GUARD + offset + nbytes:]
-    return bool((head == SENTINEL).all()) and bool((tail == SENTINEL).all()) and tail.numel() == GUARD
-
-
-def _same_bits(got, want):
-    if got.dtype == th.float32:
-        return th.equal(got.view(th.int32), want.view(th.int32))
-    return th.equal(got, want)
 
 
 def _random_mats(nb, h, w, seed):

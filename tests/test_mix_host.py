@@ -13,6 +13,8 @@ import torch.nn.functional as F
 from marlclassification_amd import _lib, augment, mix
 from marlclassification_amd import class_loss as cl
 from marlclassification_amd.__main__ import build_parser
+from tests.buffers import same_bits as _same_bits
+from tests.buffers import source as _source
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -21,19 +23,6 @@ def _declared(header):
     with open(os.path.join(ROOT, "include", header), "r", encoding="utf-8") as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return set(re.findall(r"\b(marl_[a-z0-9_]+)\s*\(", text))
-
-
-def _source(shape, dtype, n=7, seed=0):
-    g = th.Generator().manual_seed(seed + shape[1] * 7 + shape[2])
-    if dtype == th.uint8:
-        return th.randint(0, 256, (n,) + tuple(shape), dtype=th.uint8, generator=g)
-    return th.randn((n,) + tuple(shape), generator=g)
-
-
-def _same_bits(got, want):
-    if got.dtype == th.float32:
-        return th.equal(got.view(th.int32), want.view(th.int32))
-    return th.equal(got, want)
 
 
 ROWS = th.tensor([6, 0, 3, 3, 5])
@@ -87,7 +76,7 @@ def test_command_line_takes_mix_for_training_only(capsys):
 def test_reference_properties(dtype, mode):
     shape = (3, 12, 20)
     c, h, w = shape
-    src = _source(shape, dtype)
+    src = _source(shape, dtype, n=7)
     fill = 200 if dtype == th.uint8 else -1.5
     views = augment.reference_apply(src, ROWS, OPS, mode, fill)
     nb = ROWS.shape[0]
@@ -132,7 +121,7 @@ def test_reference_properties(dtype, mode):
 @pytest.mark.parametrize("dtype", DTYPES, ids=["u8", "f32"])
 def test_hostile_values_stay_in_range(dtype):
     shape = (2, 8, 8)
-    src = _source(shape, dtype)
+    src = _source(shape, dtype, n=7)
     nb = 5
     rows, ops = ROWS, OPS
     views = augment.reference_apply(src, rows, ops)
@@ -320,4 +309,4 @@ def test_library_guards_answer_without_a_device():
 
 def test_apply_refuses_a_cpu_tensor():
     with pytest.raises(RuntimeError, match="GPU"):
-        mix.apply(_source((1, 5, 7), th.uint8))
+        mix.apply(_source((1, 5, 7), th.uint8, n=7))

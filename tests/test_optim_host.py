@@ -286,7 +286,7 @@ def test_trainer_state_dict_round_trip(tmp_path):
     """A real Trainer.state_dict() (the model on the CPU: no kernel runs) through th.save / th.load(weights_only=True)
     into a fresh trainer; another update rule or another shape is a ValueError."""
     from marlclassification_amd.training import Trainer
-    from tests.test_gpu_step_autograd import Case
+    from tests.cases import Case
 
     k = Case("g1")
     opts = O.OptimOptions(weight_decay=0.01, groups={"critic": 0.0}, ema_decay=0.9)

@@ -8,7 +8,7 @@ is the launchers' own host arithmetic.
   moving the case onto another form;
 * the exactness of the known-answer operands in fp32;
 * the refusals, with their messages;
-* marl_panel_scratch_bytes against frag_floats of tests/test_gpu_panel_wfrag.py."""
+* marl_panel_scratch_bytes against frag_floats of tests/panel_harness.py."""
 import ctypes as C
 
 import pytest
@@ -128,17 +128,15 @@ def test_known_answer_operands_are_exact_in_fp32():
 
 
 def test_scratch_bytes_equal_the_fragment_copies():
-    from tests.test_gpu_panel_wfrag import frag_floats
-
     _, lib = _lib()
     for tag, (k, n, _) in H.FWD_WIDTHS.items():
         got = lib.marl_panel_scratch_bytes(0, 1, (C.c_int * 1)(n), (C.c_int * 1)(k))
-        assert got == 4 * frag_floats(n, k), tag
+        assert got == 4 * H.frag_floats(n, k), tag
         got = lib.marl_panel_scratch_bytes(1, 1, (C.c_int * 1)(n), (C.c_int * 1)(k))
-        assert got == 4 * (frag_floats(k, n) + H.r4(n * k)), tag  # the [k, n] copy + the row-major transpose it is built from
+        assert got == 4 * (H.frag_floats(k, n) + H.r4(n * k)), tag  # the [k, n] copy + the row-major transpose it is built from
     widths, ks = (64, 32, 64, 48), (40, 64, 32, 64)
     got = lib.marl_panel_scratch_bytes(0, 4, (C.c_int * 4)(*widths), (C.c_int * 4)(*ks))
-    assert got == 4 * sum(frag_floats(n, k) for n, k in zip(widths, ks))
+    assert got == 4 * sum(H.frag_floats(n, k) for n, k in zip(widths, ks))
     assert lib.marl_panel_scratch_bytes(0, 0, None, None) == 0
     assert lib.marl_panel_scratch_bytes(0, 5, (C.c_int * 5)(), (C.c_int * 5)()) == 0
 

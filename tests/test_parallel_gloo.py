@@ -3,23 +3,14 @@ the flat gradient all-reduce (averaged gradient == mean of shard gradients), and
 3-double (n, sum, sum^2) exchange that makes ``standardize`` global.  Gradients come from
 the oracle (the HIP kernels need a GPU); the collective logic is what is under test."""
 import os
-import socket
 
 import pytest
 import torch as th
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle import marl_oracle as mo
+from tests.dp import run_ranks
 from tests.util import Golden
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _shard_inputs(g, lo, hi):
@@ -66,16 +57,7 @@ def _worker(rank, world, port, exact, out_q):
 
 @pytest.mark.parametrize("exact", [False, True])
 def test_two_rank_gradient_exchange(exact):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, exact, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = th.from_numpy(q.get(timeout=300))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = th.from_numpy(run_ranks(_worker, 2, exact, get_timeout=300)[0])
 
     g = Golden("g1_conftest")
     names = list(g.params)
@@ -132,16 +114,7 @@ def test_resident_image_set_equals_the_streamed_batches():
     from marlclassification_amd.data import SyntheticImages
     from marlclassification_amd.train import ShardedBatchSampler
 
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_resident_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=300) for _ in range(2))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = dict(run_ranks(_resident_worker, 2, results=2, get_timeout=300))
     ds = SyntheticImages(37, 3, 8, 5, seed=3)
     part = th.randperm(37, generator=th.Generator().manual_seed(1))[:31].tolist()
     for rank in range(2):
@@ -192,14 +165,5 @@ def test_two_bucket_gradient_exchange_equals_one_bucket():
     """the heads' slice of the flat gradient buffer (the tail: policy, critic, prediction) and the
     rest as two collectives give the same sums as one (world size 2, gloo, CPU); the split point is the first head
     parameter; a layout with the heads elsewhere falls back to the single all-reduce."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_bucket_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    same, scale_same, split_ok, fallback = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    (same, scale_same, split_ok, fallback), = run_ranks(_bucket_worker, 2, get_timeout=300)
     assert same and scale_same and split_ok and fallback

@@ -5,8 +5,8 @@ import ctypes as C
 
 import pytest
 
-from tests.util import (CASES, PLAN_CASES, PLAN_INVARIANTS, PLAN_WITNESS, Golden, assert_witness, cdiv, library_knobs,
-                        model_spec, plan_witness)
+from tests.util import (CASES, KNOB_DEFAULTS, PLAN_CASES, PLAN_INVARIANTS, PLAN_WITNESS, Golden, assert_witness, cdiv,
+                        library_knobs, model_spec, plan_witness)
 
 
 def _lib():
@@ -18,8 +18,6 @@ def _lib():
 def test_an_unknown_knob_is_refused_and_every_known_one_is_accepted():
     """marl_tune used to create any key: a test or lab that toggled a retired knob compared two identical runs.
     (Each known knob is set to the value it already has, so nothing moves for the tests that follow.)"""
-    from tests.test_gpu_round6 import KNOB_DEFAULTS
-
     lib = _lib()
     found, table = library_knobs()
     assert set(table) == set(KNOB_DEFAULTS) | {"g3_clk", "g3_tn_abl"} == found

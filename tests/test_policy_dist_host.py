@@ -84,7 +84,7 @@ def test_engine_signatures_default_to_the_plain_entries():
 
 
 def test_masked_entropy_reference():
-    from tests.test_gpu_policy_dist import masked_entropy
+    from tests.loss_ref import masked_entropy
 
     g = th.Generator().manual_seed(5)
     p = th.softmax(th.randn(64, 6, generator=g, dtype=th.float64), -1)

@@ -2,7 +2,7 @@
 library, declared behind marl_a2c_loss_entropy_fwd_bwd (same ABI version, old signatures unchanged) and required by the
 loader; ``train`` takes ``--ppo-epochs`` / ``--ppo-clip`` / ``--gae-lambda`` / ``--max-grad-norm``; ``Trainer``,
 ``FusedA2C`` and ``run_episode_raw`` carry the new keywords with their defaults and guard them; the GAE recursion and
-the ratio grid the GPU tests use as their reference are sound."""
+the ratio grid of tests/loss_ref.py, the GPU tests' reference, are sound."""
 import inspect
 import os
 import re
@@ -11,6 +11,7 @@ import pytest
 import torch as th
 
 from oracle import marl_oracle as mo
+from tests.loss_ref import gae, ratio_deltas
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("marl_advantages", "marl_ppo_loss_fwd_bwd", "marl_grad_clip")
@@ -119,21 +120,6 @@ def test_constructor_guards(kwargs):
         FusedA2C(None, None, 1e-3, 0.99, **kwargs)
 
 
-def gae(rewards, values, gamma, lam):
-    """Plain GAE(lambda) over dimension 0, V_Ns = 0 (no bootstrap): delta_t = r_t + gamma V_{t+1} - V_t,
-    A_t = delta_t + gamma lam A_{t+1}.  Returns (A, A + V)."""
-    ns = rewards.shape[0]
-    adv = th.zeros_like(rewards)
-    nxt_a = th.zeros_like(rewards[0])
-    nxt_v = th.zeros_like(values[0])
-    for t in range(ns - 1, -1, -1):
-        delta = rewards[t] + gamma * nxt_v - values[t]
-        nxt_a = delta + gamma * lam * nxt_a
-        adv[t] = nxt_a
-        nxt_v = values[t]
-    return adv, adv + values
-
-
 def discounted_returns64(rewards, gamma):
     """training/functions.py:35-51 (flip-cumsum-flip) with float64 discount factors.  ``mo.discounted_returns`` keeps
     the reference's float32 ``gamma ** t`` whatever the dtype of the rewards, so on float64 rewards it carries the
@@ -158,16 +144,6 @@ def test_gae_reference_at_both_ends_of_lambda():
     adv0, _ = gae(rew, val, gamma, 0.0)
     nxt = th.cat([val[1:], th.zeros_like(val[:1])])
     assert th.allclose(adv0, rew + gamma * nxt - val, rtol=1e-12, atol=0)
-
-
-def ratio_deltas(shape):
-    """old_logp = logp - delta with delta on a fixed grid over [-0.5, 0.5], permuted by a fixed stride so that
-    neighbouring entries differ: rho = exp(delta) spans [0.607, 1.649] on both sides of 1 +- eps."""
-    n = 1
-    for d in shape:
-        n *= d
-    i = (th.arange(n, dtype=th.float64) * 37) % n
-    return (i / max(n - 1, 1) - 0.5).view(*shape)
 
 
 @pytest.mark.parametrize("n", [3 * 5 * 19, 3 * 2 * 5, 3, 256, 260])

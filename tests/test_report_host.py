@@ -4,16 +4,15 @@ two-rank all-reduce, the library's exports and the command-line flags."""
 import ctypes as C
 import math
 import os
-import socket
 
 import pytest
 import torch as th
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from marlclassification_amd import _lib
 from marlclassification_amd import report as R
 from marlclassification_amd.report import EpisodeReport, ReportOptions, reference_counts
+from tests.dp import run_ranks
 
 
 def _fields(step_preds, y, opts):
@@ -238,14 +237,6 @@ def test_to_json(tmp_path):
 
 
 # ---- two ranks ---------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _case(seed=5):
     g = th.Generator().manual_seed(seed)
     p = th.randn(3, 2, 10, 4, generator=g) * th.tensor([1.0, 2.0, 4.0]).view(3, 1, 1, 1)
@@ -271,16 +262,7 @@ def _worker(rank, world, port, out_q):
 
 
 def test_two_rank_all_reduce():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for pr in procs:
-        pr.start()
-    gi, gf = q.get(timeout=300)
-    for pr in procs:
-        pr.join(timeout=120)
-        assert pr.exitcode == 0
+    (gi, gf), = run_ranks(_worker, 2, get_timeout=300)
     p, y, opts = _case()
     wi, wf = reference_counts(p, y, opts)
     assert th.equal(th.from_numpy(gi), wi)

@@ -9,6 +9,7 @@ import torch as th
 import torch.nn.functional as F
 
 from marlclassification_amd import augment, warp
+from tests.buffers import same_bits as _same_bits
 
 ONE = warp.ONE
 VIEW_SHAPES = [(1, 5, 7), (3, 16, 16), (3, 33, 33), (1, 1, 1), (2, 9, 4)]
@@ -20,12 +21,6 @@ def _images(n, shape, dtype, seed=0):
     if dtype == th.uint8:
         return th.randint(0, 256, (n,) + tuple(shape), dtype=th.uint8, generator=g)
     return th.randn((n,) + tuple(shape), generator=g)
-
-
-def _same_bits(got, want):
-    if got.dtype == th.float32:
-        return th.equal(got.view(th.int32), want.view(th.int32))
-    return th.equal(got, want)
 
 
 def _view_ops(h, w):

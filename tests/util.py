@@ -92,6 +92,44 @@ def model_spec(cfg):
                      cfg.nb_class, cfg.nlb, cfg.nla, [list(a) for a in cfg.actions])
 
 
+def small_model_config(**kw):
+    """The ModelConfig of the host tests of the communication options (MNIST extractor, odd widths)."""
+    from marlclassification_amd.config import ModelConfig
+
+    return ModelConfig(ft_extr_str="mnist", window_size=6, hidden_size_belief=12, hidden_size_action=10,
+                       hidden_size_msg=8, hidden_size_msg_output=9, hidden_size_state=4, state_dim=2,
+                       actions=[[1, 0], [-1, 0], [0, 1], [0, -1]], nb_class=10, hidden_size_linear_belief=16,
+                       hidden_size_linear_action=16, **kw)
+
+
+def slice_case(g, nb):
+    """(images, episode inputs) of the first ``nb`` images of a golden case"""
+    i = g.inp
+    return (g.img[:nb], mo.EpisodeInputs(i.pos0[:, :nb].contiguous(), i.h0[:, :nb].contiguous(),
+                                         i.c0[:, :nb].contiguous(), i.hc0[:, :nb].contiguous(),
+                                         i.cc0[:, :nb].contiguous(), i.q[:, :, :nb].contiguous()))
+
+
+def run_update(eng, g, device, nb, train=True):
+    """Episode, loss and backward of the first ``nb`` images on ``eng``: (episode outputs, gradients on the host)"""
+    img, i = slice_case(g, nb)
+    eng.configure(g.na, nb, g.ns, g.img.shape[1:])
+    out = eng.episode_forward(img.to(device), i.pos0.to(device), i.h0.to(device), i.c0.to(device), i.hc0.to(device),
+                              i.cc0.to(device), i.q.to(device), None, train)
+    gp, gl, gv, sc, _ = eng.a2c_loss(out, g.y[:nb].to(device), g.gamma)
+    grads = {k: th.zeros_like(v, device=device) for k, v in g.params.items()}
+    eng.episode_backward(gp, gl, gv, grads)
+    return out, {k: v.cpu() for k, v in grads.items()}
+
+
+# every tuning knob of the library and its default (tests/test_gpu_round6.py moves each off it; the host test of the
+# knob table checks the set against the sources)
+KNOB_DEFAULTS = {"g3": 1, "g3_lstm": 1, "g3_tn": 1, "g3_min_units": 64, "g3_safe": 0, "mfma_split": 1, "g3_lstm_variant": 0,
+                 "g3_nt_variant": 0, "g3_tn_variant": 0, "g3_tn_cell": 1, "g3_tn_pipe": 1, "g3_tn_wgs": 256, "nt_xcd": 1, "tn_xcd": 1,
+                 "panel_chain": 1, "red_defer": 3, "tn_split_waves": 8, "wgrad3": 1, "cnn_fwd2": 1, "cnn_fwd3": 1, "dgrad_wgs": 0,
+                 "dgrad_min_chunks": 512}
+
+
 def library_knobs():
     """(the keys of every tune_get("...") in the library's sources, the table marl_tune accepts keys from)"""
     import glob

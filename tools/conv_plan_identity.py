@@ -6,7 +6,7 @@
     python tools/conv_plan_identity.py kernels PARENT.so TREE.so [--record profiles/conv_plan_identity.json]
 
 `dump` writes what the library named by MARL_LIB_PATH (default: the tree's) plans, entry by entry:
-  * marl_cnn_fwd_plan for every CNN_SPECS stack plus the custom stack of tests/test_gpu_conv_fwd.py, windows 4..32, ROWS
+  * marl_cnn_fwd_plan for every CNN_SPECS stack plus the custom stack of tests/conv_cases.py, windows 4..32, ROWS
     rows, train 0 and 1;
   * marl_cnn_bwd_plan for every layer of those stacks at the same row counts (first = 1 for every layer's raw shape,
     first = 0 for the layers that have a layer below), and marl_cnn_dgrad_scratch for the latter;
@@ -37,7 +37,7 @@ DEFAULTS = {"cnn_fwd2": 1, "cnn_fwd3": 1, "wgrad3": 1, "dgrad_min_chunks": 512}
 
 def _stacks():
     from marlclassification_amd.engine import CNN_SPECS
-    from tests import test_gpu_conv_fwd as fwd
+    from tests import conv_cases as fwd
 
     return {**{k: (list(c), list(g)) for k, (c, g) in CNN_SPECS.items()}, "custom": fwd.CUSTOM}
 
@@ -63,7 +63,7 @@ def _shapes():
 
 def _sweep(lib):
     from marlclassification_amd import _lib
-    from tests import test_gpu_conv_fwd as fwd
+    from tests import conv_cases as fwd
     from tests.util import plan_witness
 
     out = {}
