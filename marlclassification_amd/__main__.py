@@ -112,6 +112,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "cutmix[:alpha[:p]] and mixup[:alpha[:p]] (lam ~ Beta(alpha, alpha), per-image probability p; "
                         "defaults 1 and 0.5, the probabilities sum to at most 1); the loss takes the mixed target "
                         "distributions (default: none)")
+    t.add_argument("--color", type=_arg(_color_arg), default=None, dest="color", metavar="SPEC",
+                   help="colour jitter of the training split, one per-image colour matrix applied in one launch behind "
+                        "the batch gather: a comma-separated list of brightness:B, contrast:C, saturation:S (factor "
+                        "uniform in [max(0, 1 - v), 1 + v], 0 < v <= 3), hue:H (angle uniform in [-H, H] turns, "
+                        "0 < H <= 0.5) and gray:p (a grey image with probability p); default: none")
     t.add_argument("--class-weights", type=_arg(parse_class_weights), default=None, dest="class_weights",
                    metavar="balanced|FILE.npy|w0,w1,...",
                    help="class weights of the vote error: balanced = N / (nb_class * n_c) from the whole training "
@@ -222,6 +227,12 @@ def _normalize_override(text: str) -> str:
 
     spec = resolve(text)  # ("dataset" has nothing to be resolved against here: refused)
     return "none" if spec is None else spec.spelling
+
+
+def _color_arg(text: str) -> str:
+    from .color import parse as parse_color
+
+    return parse_color(text).spec
 
 
 def _mix_arg(text: str) -> str:
@@ -338,7 +349,7 @@ def main(argv=None) -> None:
             gamma=args.gamma, entropy_coef=args.entropy_coef, ppo_epochs=args.ppo_epochs,
             ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, max_grad_norm=args.max_grad_norm,
             learn_comm=args.learn_comm, comm_lr=args.comm_lr,
-            temperature=args.temperature, explore_eps=args.explore_eps, augment=args.augment, mix=args.mix,
+            temperature=args.temperature, explore_eps=args.explore_eps, augment=args.augment, mix=args.mix, color=args.color,
             class_weights=args.class_weights, label_smoothing=args.label_smoothing, error_steps=args.error_steps,
             weight_rewards=args.weight_rewards,
             weight_decay=args.weight_decay, decay_all=args.decay_all, lr_groups=args.lr_groups,

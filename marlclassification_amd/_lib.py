@@ -109,9 +109,11 @@ WARP_ENTRIES = ("marl_batch_warp", "marl_batch_warp_plan")
 # ... and the per-image input normalisation that include/marl_hip_normalize.h declares (likewise; transforms.py binds it)
 NORMALIZE_ENTRIES = ("marl_batch_stats", "marl_batch_stats_scratch_bytes", "marl_batch_normalize",
                      "marl_batch_normalize_plan")
+# ... and the colour jitter that include/marl_hip_color.h declares (likewise; color.py binds it)
+COLOR_ENTRIES = ("marl_batch_color", "marl_batch_color_plan")
 _HOOKS = (ROWOP_HOOKS + CNNOP_HOOKS + EXPLORE_ENTRIES + AUGMENT_ENTRIES + CLASSLOSS_ENTRIES + OPTIM_ENTRIES +
           PANELOP_HOOKS + SOFTTARGET_ENTRIES + MIX_ENTRIES + GEMMOP_HOOKS + REPORT_ENTRIES + WARP_ENTRIES +
-          NORMALIZE_ENTRIES)
+          NORMALIZE_ENTRIES + COLOR_ENTRIES)
 # the launchers marl_gemm_plan answers for (its `kind`)
 GEMM_KINDS = ("nt", "lstm", "tn", "nt_images", "lstm_images", "tn_images", "tn_images_cell")
 MARL_PANEL_MAX_LAYERS = 4
@@ -330,6 +332,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_batch_stats_scratch_bytes.argtypes = [_i] * 5
     lib.marl_batch_normalize.argtypes = [_vp, _i64, _vp, _vp, _i, C.POINTER(_d), _i, _i, _i, _i, _i, _vp, _vp, _vp]
     lib.marl_batch_normalize_plan.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp]
+    lib.marl_batch_color.argtypes = [_vp, _i64, _vp, _vp, _vp, _i, _i, C.POINTER(_d), _i, _i, _i, _i, _i, _vp, _vp, _vp]
+    lib.marl_batch_color_plan.argtypes = [_i, _i, _i, _i, _i, _vp, _vp, _vp]
     lib.marl_report_layout.argtypes = [_i] * 6 + [C.POINTER(_i64)]
     lib.marl_report_scratch_bytes.restype = _sz
     lib.marl_report_scratch_bytes.argtypes = [_i] * 7

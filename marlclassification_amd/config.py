@@ -127,6 +127,9 @@ class TrainConfig(BaseModel):
     # --mix: CutMix / Mixup of the training split in the command-line spelling (mix.parse), fused into the same batch
     # gather; the loss then takes the batch's target distributions.  A run-time choice too, not written to marl.json
     mix: Optional[str] = None
+    # --color: colour jitter of the training split in the command-line spelling (color.parse), one launch behind the
+    # batch gather and before the normalisation.  A run-time choice too, not written to marl.json
+    color: Optional[str] = None
     # options of the vote error and the rewards (class_loss.py), run-time choices like the two above: "balanced", a
     # .npy path or one weight per class; the smoothing; all | last[:K] | linear; rewards times the class weight
     class_weights: Optional[Union[str, Tuple[float, ...]]] = None

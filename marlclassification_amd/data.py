@@ -77,16 +77,21 @@ class DevicePrefetcher:
     the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes.
 
     ``normalize`` (a ``transforms.Spec`` or its spelling): the batch - the uploaded one, or what the augment / mix
-    policy made of it - is standardised per image by ``transforms.apply`` and yielded as fp32.  None: nothing changes."""
+    policy made of it - is standardised per image by ``transforms.apply`` and yielded as fp32.  None: nothing changes.
+
+    ``color`` (a ``color.Policy``): the batch - the uploaded one, or what the augment / mix policy made of it - is
+    jittered by ``color.apply`` (one launch; with a ``user-*`` ``normalize`` the same launch writes the normalised fp32
+    batch) under parameters drawn last from ``generator``, before any normalisation.  None: nothing changes."""
 
     def __init__(self, loader, device: th.device, augment=None, generator=None, mix=None,
-                 nb_class: Optional[int] = None, normalize=None) -> None:
+                 nb_class: Optional[int] = None, normalize=None, color=None) -> None:
         self.loader = loader
         self.device = th.device(device)
         self.normalize = _normalize_spec(normalize)
         self.mix, self.nb_class = mix, _mix_classes(mix, nb_class)
         self.augment = _no_mixed_warp(augment, mix)
-        self.generator = _device_generator(augment if mix is None else mix, generator, self.device)
+        self.color = color
+        self.generator = _device_generator(_first_policy(mix, augment, color), generator, self.device)
 
     def _upload(self, batch, stream):
         if batch is None:
@@ -116,11 +121,11 @@ class DevicePrefetcher:
             yd.record_stream(cur)
             if self.mix is not None:
                 xm, yp, q = _mixed(self.augment, self.mix, self.generator, xd, None, yd, self.nb_class)
-                yield _normalized(self.normalize, xm, None), yp, q
+                yield _finished(self.color, self.normalize, self.generator, xm, None), yp, q
                 continue
             if self.augment is not None:
                 xd = _augmented(self.augment, self.generator, xd, None)
-            yield _normalized(self.normalize, xd, None), yd
+            yield _finished(self.color, self.normalize, self.generator, xd, None), yd
 
     def __len__(self) -> int:
         return len(self.loader)
@@ -131,6 +136,11 @@ def _device_generator(policy, generator, device: th.device):
     if policy is None or generator is not None:
         return generator
     return th.Generator(device=device).manual_seed(0)
+
+
+def _first_policy(*policies):
+    """the first policy that is given: what decides whether a loader needs a generator"""
+    return next((p for p in policies if p is not None), None)
 
 
 def _no_mixed_warp(augment, mix):
@@ -173,6 +183,24 @@ def _normalized(spec, x: th.Tensor, rows):
     from . import transforms as _transforms
 
     return _transforms.apply(x, rows, spec)
+
+
+def _finished(color, spec, generator, x: th.Tensor, rows):
+    """the last steps of a batch: ``color.apply`` of ``x[rows]`` (``rows`` None: ``x`` itself) under parameters drawn
+    now - the last draws of a batch - then ``_normalized``; a ``user-*`` transform of uint8 images rides the colour
+    launch (``out_form="norm"``), a statistic transform takes the statistics of the jittered batch.  ``color`` None:
+    ``_normalized`` alone"""
+    if color is None:
+        return _normalized(spec, x, rows)
+    from . import color as _color
+    from . import transforms as _transforms
+
+    batch = x.shape[0] if rows is None else rows.shape[0]
+    params = color.draw(batch, generator)
+    records = _transforms.stats(x, rows) if color.needs_stats and batch > 0 else None
+    if spec is not None and spec.is_user and x.dtype == th.uint8:
+        return _color.apply(x, rows, params, records, out_form="norm", normalize=spec)
+    return _normalized(spec, _color.apply(x, rows, params, records), None)
 
 
 def _mix_classes(policy, nb_class) -> Optional[int]:
@@ -268,12 +296,19 @@ class ResidentLoader:
 
     ``normalize`` (a ``transforms.Spec`` or its spelling): every batch is standardised per image and yielded as fp32.
     Without an augment / mix policy ``transforms.apply`` reads the resident set through ``rows`` - the ``index_select``
-    disappears; with one, the batch the policy produced is normalised.  None: exactly the code above."""
+    disappears; with one, the batch the policy produced is normalised.  None: exactly the code above.
+
+    ``color`` (a ``color.Policy``): every batch is jittered by ``color.apply`` - brightness, contrast, saturation, hue
+    as one colour matrix per image, one launch - after whatever gather made it and before the normalisation, under
+    parameters drawn last from ``generator``.  Without an augment / mix policy it reads the resident set through
+    ``rows`` (no ``index_select``; the statistics contrast needs go through ``rows`` too); with a ``user-*``
+    ``normalize`` the same launch writes the normalised fp32 batch.  None: exactly the code above."""
 
     def __init__(self, dataset, indices, batch_sampler, device, workers: int = 0,
                  rank: int = 0, world: int = 1, group=None, chunk: int = 16, augment=None, generator=None,
-                 mix=None, nb_class: Optional[int] = None, normalize=None) -> None:
+                 mix=None, nb_class: Optional[int] = None, normalize=None, color=None) -> None:
         self.normalize = _normalize_spec(normalize)
+        self.color = color
         self.dataset, self.batch_sampler = dataset, batch_sampler
         self.indices = list(indices)
         self.device = th.device(device)
@@ -282,7 +317,7 @@ class ResidentLoader:
         self.fill_img_s = float("nan")
         self.mix, self.nb_class = mix, _mix_classes(mix, nb_class)
         self.augment = _no_mixed_warp(augment, mix)
-        self.generator = _device_generator(augment if mix is None else mix, generator, self.device)
+        self.generator = _device_generator(_first_policy(mix, augment, color), generator, self.device)
 
     @staticmethod
     def nbytes(dataset, n: int) -> int:
@@ -342,14 +377,16 @@ class ResidentLoader:
             if self.mix is not None:
                 xm, yp, q = _mixed(self.augment, self.mix, self.generator, self._x, rows,
                                    self._y.index_select(0, rows), self.nb_class)
-                yield _normalized(self.normalize, xm, None), yp, q
+                yield _finished(self.color, self.normalize, self.generator, xm, None), yp, q
             elif self.augment is None:
-                if self.normalize is not None:  # (straight from the resident set: no index_select)
-                    yield _normalized(self.normalize, self._x, rows), self._y.index_select(0, rows)
+                if self.normalize is not None or self.color is not None:  # (from the resident set: no index_select)
+                    yield (_finished(self.color, self.normalize, self.generator, self._x, rows),
+                           self._y.index_select(0, rows))
                 else:
                     yield self._x.index_select(0, rows), self._y.index_select(0, rows)
             else:
-                yield (_normalized(self.normalize, _augmented(self.augment, self.generator, self._x, rows), None),
+                yield (_finished(self.color, self.normalize, self.generator,
+                                 _augmented(self.augment, self.generator, self._x, rows), None),
                        self._y.index_select(0, rows))
 
     def __len__(self) -> int:

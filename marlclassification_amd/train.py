@@ -254,8 +254,18 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
         mix_policy = _mix.parse(train_config.mix)
         if aug_gen is None:
             aug_gen = th.Generator(device=device).manual_seed(base_seed + 104729 * (rank + 1))
+    # --color: likewise the training split only, drawn last from the same per-rank device generator
+    color_policy = None
+    if train_config.color is not None:
+        from . import color as _color
+
+        color_policy = _color.parse(train_config.color)
+        if aug_gen is None:
+            aug_gen = th.Generator(device=device).manual_seed(base_seed + 104729 * (rank + 1))
     for k, part in enumerate((idx[:cut].tolist(), idx[cut:].tolist())):
         aug = {"augment": policy, "generator": aug_gen} if policy is not None and k == 0 else {}
+        if color_policy is not None and k == 0:
+            aug.update(color=color_policy, generator=aug_gen)
         if mix_policy is not None and k == 0:
             aug.update(mix=mix_policy, nb_class=model_config.nb_class, generator=aug_gen)
         if normalize is not None:  # (both splits: the evaluation sees what the model was trained on)
@@ -328,6 +338,7 @@ def train_main(main_config: MainConfig, model_config: ModelConfig, train_config:
               (f", normalize {model_config.normalize}" if normalize is not None else "") +
               (f", augment {policy.spec}" if policy is not None else "") +
               (f", mix {mix_policy.spec}" if mix_policy is not None else "") +
+              (f", color {color_policy.spec}" if color_policy is not None else "") +
               (f", class weights {cw_spec if isinstance(cw_spec, str) else 'given'}" if cw_spec is not None else "") +
               (f", label_smoothing {train_config.label_smoothing}" if train_config.label_smoothing else "") +
               (f", error steps {train_config.error_steps}" if train_config.error_steps else "") +
