@@ -313,16 +313,11 @@ def apply(src: th.Tensor, rows: Optional[th.Tensor], params: th.Tensor, records:
     user, mode = None, 0
     if form == OUT_FORMS["norm"]:
         spec = _user_spec(normalize, src)
-        pairs = spec.user(c)
-        user = (C.c_double * (2 * c))(*[v for pair in pairs for v in pair])
+        user = _transforms._user_array(spec, c)
         mode = _transforms.MODES[spec.mode]
     elif normalize is not None:
         raise ValueError('color.apply: normalize goes with out_form="norm"')
-    shape, dtype = (nb, c, h, w), (th.float32 if form else src.dtype)
-    if out is None:
-        out = th.empty(shape, dtype=dtype, device=dev)
-    elif out.device != dev or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"color.apply: out must be a contiguous {dtype} {shape} tensor on {dev}")
+    out = _transforms._need_out(out, "color.apply", (nb, c, h, w), th.float32 if form else src.dtype, dev)
     coef = None
     if return_coef:
         coef = th.empty(nb, c, c + 1, dtype=th.int32 if src.dtype == th.uint8 else th.float32, device=dev)

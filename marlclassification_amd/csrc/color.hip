@@ -14,9 +14,9 @@
 // and sums of the pixels and the normalising pair of OUT_NORM round every operation, as their definition in color.py
 // does; the uint8 matrices equal color.reference_matrix integer for integer.
 #include "gather.h"
+#include "normrules.h"
 
 #include "../../include/marl_hip_color.h"
-#include "../../include/marl_hip_normalize.h"
 
 namespace marl {
 namespace {
@@ -93,18 +93,17 @@ __host__ __device__ __forceinline__ void compose(const ColorArgs& a, int b, doub
     }
     if (a.records != nullptr) {  // contrast pivots on the grey mean of the brightened image
         double m[C];
-        if constexpr (ELT == 1) {
-            const int64_t* __restrict__ rec = reinterpret_cast<const int64_t*>(a.records) + (int64_t)b * C * 4;
+        const Rec<typename RecOf<ELT>::T>* __restrict__ rec =
+            reinterpret_cast<const Rec<typename RecOf<ELT>::T>*>(a.records) + (int64_t)b * C;
 #pragma unroll
-            for (int ch = 0; ch < C; ++ch) {  // (S1 is not trusted either: clamped to what N bytes can sum to)
-                const int64_t top = 255 * (int64_t)a.plane, raw = rec[ch * 4];
+        for (int ch = 0; ch < C; ++ch) {
+            if constexpr (ELT == 1) {  // (S1 is not trusted either: clamped to what N bytes can sum to)
+                const int64_t top = 255 * (int64_t)a.plane, raw = rec[ch].s1;
                 const int64_t s1 = raw < 0 ? 0 : (raw > top ? top : raw);
                 m[ch] = (double)((256 * s1) / (int64_t)a.plane) * (1.0 / 256.0);
+            } else {
+                m[ch] = rec[ch].s1 / (double)a.plane;
             }
-        } else {
-            const double* __restrict__ rec = reinterpret_cast<const double*>(a.records) + (int64_t)b * C * 4;
-#pragma unroll
-            for (int ch = 0; ch < C; ++ch) m[ch] = rec[ch * 4] / (double)a.plane;
         }
         double v[C];
 #pragma unroll
@@ -143,27 +142,6 @@ __host__ __device__ __forceinline__ void compose(const ColorArgs& a, int b, doub
 __host__ __device__ __forceinline__ int quantise(double v, double bound) {
     const double r = rint(4096.0 * v);
     return (int)(r < -bound ? -bound : (r > bound ? bound : r));
-}
-
-// the (scale, offset) of channel ch under a user mode, as batch_normalize_kernel derives it for uint8 sources
-__device__ __forceinline__ void user_pair(const ColorArgs& a, int ch, float& scale, float& offset) {
-    double sc, of;
-    if (a.norm_mode == MARL_NORM_USER_NORMAL) {
-        const double m = a.user[ch][0], s = a.user[ch][1];
-        sc = 1.0 / (255.0 * s);
-        of = -m / s;
-    } else {
-        const double lo = a.user[ch][0], d = a.user[ch][1] - lo;
-        sc = 1.0 / (255.0 * d);
-        of = -lo / d;
-    }
-    scale = (float)sc;
-    offset = (float)of;
-}
-
-__device__ __forceinline__ float rounded(float v) {
-    asm volatile("" : "+v"(v));  // (a sum sees a rounded product whatever the contraction setting)
-    return v;
 }
 
 // LB bytes from an LB-aligned address into dwords (LB == 1: the byte)
@@ -234,7 +212,11 @@ __global__ void __launch_bounds__(kColorThreads) batch_color_kernel(const ColorA
     float scale[C], offset[C];
     if constexpr (NORM) {
 #pragma unroll
-        for (int i = 0; i < C; ++i) user_pair(a, i, scale[i], offset[i]);
+        for (int i = 0; i < C; ++i) {  // (the pair of the user normalisation, uint8 source: normrules.h)
+            double sc, of;
+            user_coef<1>(a, a.norm_mode, i, sc, of);
+            scale[i] = (float)sc, offset[i] = (float)of;
+        }
     }
 #pragma unroll
     for (int v = 0; v < kColorVectors; ++v) {
@@ -296,8 +278,6 @@ struct ColorPlan {
     int px, load_bytes, store_bytes, nvp, bpi;
 };
 
-bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-
 // The checks of gather_plan on the source (element, sizes, alignment, the 2^31 limit) behind the two of this family
 // (the form, c), the destination's own alignment and limit, then the vector width.
 int color_plan(const char* who, int c, int h, int w, int elt, int out_form, const void* src, const void* dst,
@@ -332,10 +312,7 @@ int color_plan(const char* who, int c, int h, int w, int elt, int out_form, cons
         p->px = (plane % 4 == 0 && (s & 3) == 0 && (d & 15) == 0) ? 4 : 1;
         p->load_bytes = p->px, p->store_bytes = 4 * p->px;
     } else {
-        const int64_t plane_bytes = plane * elt;
-        int v = 16;
-        while (v > elt && ((plane_bytes % v) != 0 || ((s | d) % v) != 0)) v >>= 1;
-        if (v < 4) v = elt;  // (uint8 planes that are no multiple of 4 bytes: bytes)
+        const int v = store_width(plane * elt, s | d, elt);  // (uint8 planes that are no multiple of 4 bytes: bytes)
         p->px = v / elt;
         p->load_bytes = p->store_bytes = v;
     }
@@ -392,10 +369,7 @@ extern "C" int marl_batch_color(const void* src, int64_t n_src, const int64_t* r
         set_error("%s: null src / dst / params", who);
         return MARL_EINVAL;
     }
-    if (batch <= 0 || n_src <= 0) {
-        set_error("%s: sizes must be positive (batch %d, n_src %lld)", who, batch, (long long)n_src);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_batch(who, batch, n_src));
     ColorPlan p{};
     MARL_TRY(color_plan(who, c, h, w, elt_bytes, out_form, src, dst, &p));
     const bool norm = out_form == MARL_COLOR_OUT_NORM;
@@ -410,46 +384,17 @@ extern "C" int marl_batch_color(const void* src, int64_t n_src, const int64_t* r
             set_error("%s: norm_mode %d needs user", who, norm_mode);
             return MARL_EINVAL;
         }
-        for (int ch = 0; ch < c; ++ch) {
-            const double u0 = user[2 * ch], u1 = user[2 * ch + 1];
-            const double width = norm_mode == MARL_NORM_USER_NORMAL ? u1 : u1 - u0;
-            if (!(u0 - u0 == 0.0) || !(u1 - u1 == 0.0) || !(width - width == 0.0) || width == 0.0) {  // (NaN, inf, 0)
-                set_error("%s: user[%d] = (%g, %g): %s", who, ch, u0, u1,
-                          norm_mode == MARL_NORM_USER_NORMAL ? "s must be finite and not 0"
-                                                             : "hi - lo must be finite and not 0");
-                return MARL_EINVAL;
-            }
-            a.user[ch][0] = u0, a.user[ch][1] = u1;
-        }
+        MARL_TRY(user_pairs(who, norm_mode, user, c, a.user));
     }
-    if (rows == nullptr && n_src < batch) {
-        set_error("%s: rows == NULL takes row b for image b, but n_src %lld < batch %d", who, (long long)n_src, batch);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_rows_cover(who, rows, n_src, batch));
     const int64_t pixels = (int64_t)c * h * w, img_bytes = pixels * elt_bytes, out_bytes = pixels * (norm ? 4 : elt_bytes);
-    if (n_src > (INT64_MAX / 2) / img_bytes) {
-        set_error("%s: n_src %lld images of %lld bytes overflow", who, (long long)n_src, (long long)img_bytes);
-        return MARL_ELIMIT;
-    }
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
-    const uintptr_t s1 = s0 + (uintptr_t)(n_src * img_bytes), d1 = d0 + (uintptr_t)((int64_t)batch * out_bytes);
-    if (d0 < s1 && s0 < d1) {
-        set_error("%s: dst overlaps src (a thread reads all planes of its pixels, other threads write them)", who);
-        return MARL_EINVAL;
-    }
-    if (misaligned(records, 8) || misaligned(rows, 8)) {
-        set_error("%s: records and rows must be 8-byte aligned", who);
-        return MARL_EINVAL;
-    }
-    if (misaligned(coef, 4) || misaligned(params, 4)) {
-        set_error("%s: coef and params must be 4-byte aligned", who);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_extent(who, n_src, img_bytes));
+    MARL_TRY(need_apart(who, src, n_src * img_bytes, dst, (int64_t)batch * out_bytes,
+                        "a thread reads all planes of its pixels, other threads write them"));
+    MARL_TRY(need_aligned(who, "records and rows", 8, records, rows));
+    MARL_TRY(need_aligned(who, "coef and params", 4, coef, params));
     const int64_t blocks = (int64_t)batch * p.bpi;
-    if (blocks > 0x7fffffffLL) {
-        set_error("%s: %lld workgroups (batch %d) are more than a grid holds", who, (long long)blocks, batch);
-        return MARL_ELIMIT;
-    }
+    MARL_TRY(need_grid(who, blocks, batch));
     a.src = static_cast<const uint8_t*>(src);
     a.dst = static_cast<uint8_t*>(dst);
     a.rows = rows;

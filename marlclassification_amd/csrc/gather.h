@@ -1,7 +1,8 @@
 // What the batch gathers share (augment.hip, mix.hip, warp.hip; internal).  Device side: the address rules that
 // include/marl_hip_augment.h documents - one sanitiser of rows[i] / ops[i] into a View, one fold, one per-pixel rule,
 // one family of store vectors.  Host side: the checks of the three plan queries, the guards of the three entries in their
-// one order, the fields every argument struct has, the switch over the store widths.  What differs per kernel
+// one order, the fields every argument struct has, the switch over the store widths; the guards are one function a rule
+// (need_*), and the store-width rule is store_width, which normalize.hip and color.hip use too.  What differs per kernel
 // (total_vec against plane_vec, the band size, the transposing tiles, the mix rule, the matrices) stays in its file.
 //
 // The device functions are templated on the kernel's argument struct (AugArgs, MixArgs, WarpArgs), which keeps its own
@@ -172,8 +173,15 @@ struct GatherPlan {
     int store_bytes, nv;  // V, and stores per output row
 };
 
-// The checks of the three plan queries, and the store width: the widest of 16 / 8 / 4 bytes that divides a row and
-// dst's address, the element for uint8 rows that are no multiple of 4 bytes.
+// The store width: the widest of 16 / 8 / 4 bytes that divides `bytes` (a row, a plane) and `addrs` (the OR of every
+// address a vector touches), the element for uint8 lengths that are no multiple of 4 bytes.
+inline int store_width(int64_t bytes, uintptr_t addrs, int elt) {
+    int v = 16;
+    while (v > elt && ((bytes % v) != 0 || (addrs % v) != 0)) v >>= 1;
+    return v < 4 ? elt : v;  // (uint8 rows that are no multiple of 4 bytes: byte stores)
+}
+
+// The checks of the three plan queries, and the store width of a row at dst's address.
 inline int gather_plan(const char* who, int c, int h, int w, int elt, const void* src, const void* dst, GatherPlan* p) {
     if (elt != 1 && elt != 4) {
         set_error("%s: elt_bytes %d is neither 1 nor 4", who, elt);
@@ -194,16 +202,70 @@ inline int gather_plan(const char* who, int c, int h, int w, int elt, const void
         return MARL_ELIMIT;
     }
     const int64_t row_bytes = (int64_t)w * elt;
-    int v = 16;
-    while (v > elt && ((row_bytes % v) != 0 || (d % v) != 0)) v >>= 1;
-    if (v < 4) v = elt;  // (uint8 rows that are no multiple of 4 bytes: byte stores)
-    p->store_bytes = v;
-    p->nv = (int)(row_bytes / v);
+    p->store_bytes = store_width(row_bytes, d, elt);
+    p->nv = (int)(row_bytes / p->store_bytes);
     return MARL_OK;
 }
 
-// The guards of an entry up to the grid size (gather_launch's), in the order the entries have always answered;
-// `in_place` is why that entry refuses dst inside src.  Host arithmetic: nothing is dereferenced.
+// The guards every batch entry has (the gathers here; normalize.hip, color.hip), one rule each: an entry is a sequence
+// of them in its own order, which is part of its contract (tools/gather_identity.py).  Host arithmetic: nothing is
+// dereferenced.
+inline int need_batch(const char* who, int batch, int64_t n_src) {
+    if (batch <= 0 || n_src <= 0) {
+        set_error("%s: sizes must be positive (batch %d, n_src %lld)", who, batch, (long long)n_src);
+        return MARL_EINVAL;
+    }
+    return MARL_OK;
+}
+
+inline int need_rows_cover(const char* who, const int64_t* rows, int64_t n_src, int batch) {
+    if (rows == nullptr && n_src < batch) {
+        set_error("%s: rows == NULL takes row b for image b, but n_src %lld < batch %d", who, (long long)n_src, batch);
+        return MARL_EINVAL;
+    }
+    return MARL_OK;
+}
+
+// n_src * img_bytes stays a byte count the overlap test can add to an address
+inline int need_extent(const char* who, int64_t n_src, int64_t img_bytes) {
+    if (n_src > (INT64_MAX / 2) / img_bytes) {
+        set_error("%s: n_src %lld images of %lld bytes overflow", who, (long long)n_src, (long long)img_bytes);
+        return MARL_ELIMIT;
+    }
+    return MARL_OK;
+}
+
+// [src, src + src_bytes) and [dst, dst + dst_bytes) share no byte (adjacent is apart); `in_place` is why that entry
+// refuses dst inside src
+inline int need_apart(const char* who, const void* src, int64_t src_bytes, const void* dst, int64_t dst_bytes,
+                      const char* in_place) {
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t s1 = s0 + (uintptr_t)src_bytes, d1 = d0 + (uintptr_t)dst_bytes;
+    if (d0 < s1 && s0 < d1) {
+        set_error("%s: dst overlaps src (%s)", who, in_place);
+        return MARL_EINVAL;
+    }
+    return MARL_OK;
+}
+
+inline int need_grid(const char* who, int64_t blocks, int batch) {
+    if (blocks > 0x7fffffffLL) {
+        set_error("%s: %lld workgroups (batch %d) are more than a grid holds", who, (long long)blocks, batch);
+        return MARL_ELIMIT;
+    }
+    return MARL_OK;
+}
+
+// `what` (one or two pointers, null allowed) on a multiple of `to` bytes
+inline int need_aligned(const char* who, const char* what, int to, const void* p, const void* q = nullptr) {
+    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & (uintptr_t)(to - 1)) {
+        set_error("%s: %s must be %d-byte aligned", who, what, to);
+        return MARL_EINVAL;
+    }
+    return MARL_OK;
+}
+
+// The guards of a gather entry up to the grid size (gather_launch's), in the order the entries have always answered.
 inline int gather_guard(const char* who, const char* in_place, const GatherCall& g, GatherPlan* p) {
     if (g.src == nullptr || g.dst == nullptr) {
         set_error("%s: null src / dst", who);
@@ -213,28 +275,12 @@ inline int gather_guard(const char* who, const char* in_place, const GatherCall&
         set_error("%s: unknown pad_mode %d", who, g.pad_mode);
         return MARL_EINVAL;
     }
-    if (g.batch <= 0 || g.n_src <= 0) {
-        set_error("%s: sizes must be positive (batch %d, n_src %lld)", who, g.batch, (long long)g.n_src);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_batch(who, g.batch, g.n_src));
     MARL_TRY(gather_plan(who, g.c, g.h, g.w, g.elt, g.src, g.dst, p));
-    if (g.rows == nullptr && g.n_src < g.batch) {
-        set_error("%s: rows == NULL takes row b for image b, but n_src %lld < batch %d", who, (long long)g.n_src,
-                  g.batch);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_rows_cover(who, g.rows, g.n_src, g.batch));
     const int64_t img_bytes = (int64_t)g.c * g.h * g.w * g.elt;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(g.src), d0 = reinterpret_cast<uintptr_t>(g.dst);
-    if (g.n_src > (INT64_MAX / 2) / img_bytes) {
-        set_error("%s: n_src %lld images of %lld bytes overflow", who, (long long)g.n_src, (long long)img_bytes);
-        return MARL_ELIMIT;
-    }
-    const uintptr_t s1 = s0 + (uintptr_t)(g.n_src * img_bytes), d1 = d0 + (uintptr_t)((int64_t)g.batch * img_bytes);
-    if (d0 < s1 && s0 < d1) {
-        set_error("%s: dst overlaps src (%s)", who, in_place);
-        return MARL_EINVAL;
-    }
-    return MARL_OK;
+    MARL_TRY(need_extent(who, g.n_src, img_bytes));
+    return need_apart(who, g.src, g.n_src * img_bytes, g.dst, (int64_t)g.batch * img_bytes, in_place);
 }
 
 // the fields every argument struct has
@@ -259,10 +305,7 @@ Args gather_args(const GatherCall& g, const GatherPlan& p) {
 template <class Launch>
 int gather_launch(const char* who, const GatherCall& g, const GatherPlan& p, int blocks_per_image, Launch&& launch) {
     const int64_t blocks = (int64_t)g.batch * blocks_per_image;
-    if (blocks > 0x7fffffffLL) {
-        set_error("%s: %lld workgroups (batch %d) are more than a grid holds", who, (long long)blocks, g.batch);
-        return MARL_ELIMIT;
-    }
+    MARL_TRY(need_grid(who, blocks, g.batch));
     const dim3 grid((unsigned)blocks);
     using E1 = std::integral_constant<int, 1>;
     using E4 = std::integral_constant<int, 4>;

@@ -19,8 +19,7 @@
 // The translation unit is built with -ffp-contract=off (Makefile): neither that pair nor the fp64 chain may be fused,
 // the definition (transforms.reference_coef / reference_apply) rounds every operation.
 #include "gather.h"
-
-#include "../../include/marl_hip_normalize.h"
+#include "normrules.h"
 
 namespace marl {
 namespace {
@@ -44,23 +43,6 @@ struct StatsArgs {
     uint8_t* records;
     int64_t planes;  // batch * c
 };
-
-template <int ELT>
-struct RecOf;
-template <>
-struct RecOf<1> {
-    using T = int64_t;
-};
-template <>
-struct RecOf<4> {
-    using T = double;
-};
-template <class T>
-struct Rec {
-    T s1, s2, mn, mx;
-};
-static_assert(sizeof(Rec<int64_t>) == MARL_NORM_RECORD_BYTES && sizeof(Rec<double>) == MARL_NORM_RECORD_BYTES,
-              "record layout");
 
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
@@ -206,16 +188,11 @@ struct NormArgs {
 template <int ELT>
 __device__ __forceinline__ void derive_coef(const NormArgs& a, int b, int ch, float& scale, float& offset) {
     using T = typename RecOf<ELT>::T;
-    constexpr double k255 = ELT == 1 ? 255.0 : 1.0;
     double sc = 0.0, of = 0.0;
-    if (a.mode == MARL_NORM_USER_NORMAL) {
-        const double m = a.user[ch][0], s = a.user[ch][1];
-        sc = 1.0 / (k255 * s);
-        of = -m / s;
+    if (a.mode == MARL_NORM_USER_NORMAL) {  // (one call per mode: a call under `normal || minmax` moves the kernel)
+        user_coef<ELT>(a, MARL_NORM_USER_NORMAL, ch, sc, of);
     } else if (a.mode == MARL_NORM_USER_MINMAX) {
-        const double lo = a.user[ch][0], d = a.user[ch][1] - lo;
-        sc = 1.0 / (k255 * d);
-        of = -lo / d;
+        user_coef<ELT>(a, MARL_NORM_USER_MINMAX, ch, sc, of);
     } else {
         const bool whole = a.mode == MARL_NORM_NORMAL || a.mode == MARL_NORM_MINMAX;
         const Rec<T>* __restrict__ rec = reinterpret_cast<const Rec<T>*>(a.records) + (int64_t)b * a.c;
@@ -293,9 +270,7 @@ __global__ void __launch_bounds__(kNormThreads) batch_normalize_kernel(const Nor
 #pragma unroll
         for (int e = 0; e < N; ++e) {
             const float xf = ELT == 1 ? (float)x[i][e] : __uint_as_float(x[i][e]);
-            float pr = __fmul_rn(xf, scale);
-            asm volatile("" : "+v"(pr));  // (the sum sees a rounded product whatever the contraction setting)
-            q[e] = __float_as_uint(__fadd_rn(pr, offset));
+            q[e] = __float_as_uint(__fadd_rn(rounded(__fmul_rn(xf, scale)), offset));
         }
         store_vec<V>(dp + (size_t)idx * V, q);
     }
@@ -325,49 +300,26 @@ int normalize_plan(const char* who, int c, int h, int w, int elt, const void* sr
     return MARL_OK;
 }
 
-// The guards both entries share, in the order of gather_guard; need_dst = false: the statistics, which write no image.
-// stat_limit: the entry takes (or consumes) statistics of the image, so a uint8 image is bounded by 2^23 pixels.
+// The guards both entries share: the rules of gather.h in the order of gather_guard, around this family's plan and its
+// one rule of its own (kept here, not folded into the entries, so that rule stands once); need_dst = false: the
+// statistics, which write no image.  stat_limit: the entry takes (or consumes) statistics of the image, so a uint8 image is bounded by 2^23 pixels.
 int normalize_guard(const char* who, const void* src, int64_t n_src, const int64_t* rows, int batch, int c, int h, int w,
                     int elt, const void* dst, bool need_dst, bool stat_limit, NormPlan* p) {
-    if (batch <= 0 || n_src <= 0) {
-        set_error("%s: sizes must be positive (batch %d, n_src %lld)", who, batch, (long long)n_src);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_batch(who, batch, n_src));
     MARL_TRY(normalize_plan(who, c, h, w, elt, src, dst, need_dst, p));
-    if (rows == nullptr && n_src < batch) {
-        set_error("%s: rows == NULL takes row b for image b, but n_src %lld < batch %d", who, (long long)n_src, batch);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_rows_cover(who, rows, n_src, batch));
     const int64_t pixels = (int64_t)c * h * w, img_bytes = pixels * elt;
-    if (n_src > (INT64_MAX / 2) / img_bytes) {
-        set_error("%s: n_src %lld images of %lld bytes overflow", who, (long long)n_src, (long long)img_bytes);
-        return MARL_ELIMIT;
-    }
+    MARL_TRY(need_extent(who, n_src, img_bytes));
     if (stat_limit && elt == 1 && pixels > MARL_NORM_MAX_STAT_PIXELS) {
         set_error("%s: the statistics of a uint8 image of %lld pixels (c %d, h %d, w %d) are beyond 2^23", who,
                   (long long)pixels, c, h, w);
         return MARL_ELIMIT;
     }
-    if (need_dst) {
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
-        const uintptr_t s1 = s0 + (uintptr_t)(n_src * img_bytes), d1 = d0 + (uintptr_t)((int64_t)batch * pixels * 4);
-        if (d0 < s1 && s0 < d1) {
-            set_error("%s: dst overlaps src (the output is fp32 whatever the source is)", who);
-            return MARL_EINVAL;
-        }
-    }
+    if (need_dst)
+        MARL_TRY(need_apart(who, src, n_src * img_bytes, dst, (int64_t)batch * pixels * 4,
+                            "the output is fp32 whatever the source is"));
     return MARL_OK;
 }
-
-int check_grid(const char* who, int64_t blocks, int batch) {
-    if (blocks > 0x7fffffffLL) {
-        set_error("%s: %lld workgroups (batch %d) are more than a grid holds", who, (long long)blocks, batch);
-        return MARL_ELIMIT;
-    }
-    return MARL_OK;
-}
-
-bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
 
 }  // namespace
 }  // namespace marl
@@ -410,10 +362,7 @@ extern "C" int marl_batch_stats(const void* src, int64_t n_src, const int64_t* r
     }
     NormPlan p{};
     MARL_TRY(normalize_guard(who, src, n_src, rows, batch, c, h, w, elt_bytes, nullptr, false, true, &p));
-    if (misaligned(scratch, 8) || misaligned(records, 8)) {
-        set_error("%s: scratch and records must be 8-byte aligned", who);
-        return MARL_EINVAL;
-    }
+    MARL_TRY(need_aligned(who, "scratch and records", 8, scratch, records));
     StatsArgs a{};
     a.src = static_cast<const uint8_t*>(src);
     a.rows = rows;
@@ -424,7 +373,7 @@ extern "C" int marl_batch_stats(const void* src, int64_t n_src, const int64_t* r
     a.records = static_cast<uint8_t*>(records);
     a.planes = (int64_t)batch * c;
     const int64_t blocks = a.planes * p.ppp;
-    MARL_TRY(check_grid(who, blocks, batch));
+    MARL_TRY(need_grid(who, blocks, batch));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks), fold((unsigned)cdiv(a.planes, kNormThreads));
     if (elt_bytes == 1) {
@@ -461,27 +410,12 @@ extern "C" int marl_batch_normalize(const void* src, int64_t n_src, const int64_
             set_error("%s: user modes take at most %d channels, got %d", who, MARL_NORM_MAX_USER_CHANNELS, c);
             return MARL_EINVAL;
         }
-        for (int ch = 0; ch < c; ++ch) {
-            const double u0 = user[2 * ch], u1 = user[2 * ch + 1];
-            const double width = mode == MARL_NORM_USER_NORMAL ? u1 : u1 - u0;
-            if (!(u0 - u0 == 0.0) || !(u1 - u1 == 0.0) || !(width - width == 0.0) || width == 0.0) {  // (NaN, inf, 0)
-                set_error("%s: user[%d] = (%g, %g): %s", who, ch, u0, u1,
-                          mode == MARL_NORM_USER_NORMAL ? "s must be finite and not 0" : "hi - lo must be finite and not 0");
-                return MARL_EINVAL;
-            }
-            a.user[ch][0] = u0, a.user[ch][1] = u1;
-        }
+        MARL_TRY(user_pairs(who, mode, user, c, a.user));
     }
     NormPlan p{};
     MARL_TRY(normalize_guard(who, src, n_src, rows, batch, c, h, w, elt_bytes, dst, true, !by_user, &p));
-    if (!by_user && misaligned(records, 8)) {
-        set_error("%s: records must be 8-byte aligned", who);
-        return MARL_EINVAL;
-    }
-    if (misaligned(coef, 4)) {
-        set_error("%s: coef must be 4-byte aligned", who);
-        return MARL_EINVAL;
-    }
+    if (!by_user) MARL_TRY(need_aligned(who, "records", 8, records));
+    MARL_TRY(need_aligned(who, "coef", 4, coef));
     a.src = static_cast<const uint8_t*>(src);
     a.dst = reinterpret_cast<uint8_t*>(dst);
     a.rows = rows;

@@ -68,20 +68,9 @@ class DevicePrefetcher:
     ToTensor runs in the gather kernel) from pinned staging memory on a COPY stream while batch
     i trains, and the compute stream only waits for the copy's event.
 
-    ``augment`` (an ``augment.Policy``): the uploaded batch goes through ``augment.apply`` into a fresh tensor on the
-    compute stream, behind the wait on the copy's event, under ops drawn from ``generator`` (a generator of
-    ``device``).  None: exactly the code above.
-
-    ``mix`` (a ``mix.Policy``, with ``nb_class``): the batch is mixed with a permutation of itself (CutMix / Mixup,
-    ``mix.apply``: the views are the augmented ones, still one launch) and the loader yields ``(x, y_primary, Q)`` with
-    the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes.
-
-    ``normalize`` (a ``transforms.Spec`` or its spelling): the batch - the uploaded one, or what the augment / mix
-    policy made of it - is standardised per image by ``transforms.apply`` and yielded as fp32.  None: nothing changes.
-
-    ``color`` (a ``color.Policy``): the batch - the uploaded one, or what the augment / mix policy made of it - is
-    jittered by ``color.apply`` (one launch; with a ``user-*`` ``normalize`` the same launch writes the normalised fp32
-    batch) under parameters drawn last from ``generator``, before any normalisation.  None: nothing changes."""
+    ``augment``, ``mix`` (with ``nb_class``), ``color``, ``normalize`` and ``generator`` (a generator of ``device``):
+    the policies of ``_batch``, which makes every yielded batch of the uploaded one (``rows`` None) on the compute
+    stream, behind the wait on the copy's event.  All None: exactly the code above."""
 
     def __init__(self, loader, device: th.device, augment=None, generator=None, mix=None,
                  nb_class: Optional[int] = None, normalize=None, color=None) -> None:
@@ -119,13 +108,7 @@ class DevicePrefetcher:
             cur.wait_event(ev)
             xd.record_stream(cur)
             yd.record_stream(cur)
-            if self.mix is not None:
-                xm, yp, q = _mixed(self.augment, self.mix, self.generator, xd, None, yd, self.nb_class)
-                yield _finished(self.color, self.normalize, self.generator, xm, None), yp, q
-                continue
-            if self.augment is not None:
-                xd = _augmented(self.augment, self.generator, xd, None)
-            yield _finished(self.color, self.normalize, self.generator, xd, None), yd
+            yield _batch(self.augment, self.mix, self.nb_class, self.color, self.normalize, self.generator, xd, None, yd)
 
     def __len__(self) -> int:
         return len(self.loader)
@@ -225,6 +208,42 @@ def _mixed(augment, policy, generator, x: th.Tensor, rows, y: th.Tensor, nb_clas
     return out, _mix.primary_labels(y, m, h, w), _mix.soft_targets(y, m, h, w, nb_class)
 
 
+def _batch(augment, mix, nb_class, color, normalize, generator, x: th.Tensor, rows, y: th.Tensor):
+    """What a loader yields for one batch: ``x[rows]`` / ``y[rows]`` (``rows`` int64 ``[B]`` into a resident set; None:
+    ``x`` and ``y`` are the batch, an uploaded one) under the loader's policies.  Every draw comes from ``generator``
+    without a host synchronisation, in the order augment, mix, colour.
+
+    ``augment`` (an ``augment.Policy``): the batch is ``augment.apply(x, rows, ops)`` - the gather with flips, quarter
+    turns, shifts and erasing fused in, one launch that moves the bytes ``index_select`` moves - into a fresh tensor.  A
+    policy with ``rotate`` / ``scale`` / ``stretch`` (``Policy.has_warp``) goes through ``warp.apply`` under
+    ``Policy.draw_warp`` instead: the gather with the bilinear resampling fused in, still one launch.
+
+    ``mix`` (a ``mix.Policy``, with ``nb_class``): the batch is mixed with a permutation of itself (CutMix / Mixup,
+    ``mix.apply``: the views are the augmented ones, still one launch) and the result is ``(x, y_primary, Q)`` with the
+    target distributions ``Q`` fp32 ``[B, nb_class]``, not ``(x, y)``.
+
+    ``color`` (a ``color.Policy``): the batch is jittered by ``color.apply`` - brightness, contrast, saturation, hue as
+    one colour matrix per image, one launch - after whatever gather made it and before the normalisation, under
+    parameters drawn last.  Without an augment / mix policy it reads ``x`` through ``rows`` (no ``index_select``; the
+    statistics contrast needs go through ``rows`` too); with a ``user-*`` ``normalize`` the same launch writes the
+    normalised fp32 batch.
+
+    ``normalize`` (a ``transforms.Spec``): the batch is standardised per image by ``transforms.apply`` and is fp32.
+    Without an augment / mix policy it reads ``x`` through ``rows`` - the ``index_select`` disappears; with one, the
+    batch the policy produced is normalised.
+
+    All None: ``x`` itself, or ``x.index_select(0, rows)``."""
+    labels = y if rows is None else y.index_select(0, rows)
+    if mix is not None:
+        xm, yp, q = _mixed(augment, mix, generator, x, rows, labels, nb_class)
+        return _finished(color, normalize, generator, xm, None), yp, q
+    if augment is not None:
+        return _finished(color, normalize, generator, _augmented(augment, generator, x, rows), None), labels
+    if color is not None or normalize is not None:  # (through rows: no index_select)
+        return _finished(color, normalize, generator, x, rows), labels
+    return (x if rows is None else x.index_select(0, rows)), labels
+
+
 class _Stripe:
     """every k-th batch of a batch sampler (same order: the base sampler is re-iterated per stripe)"""
 
@@ -283,26 +302,9 @@ class ResidentLoader:
     ``batch_sampler`` yields lists of dataset indices (this rank's slice of every global
     batch, train.ShardedBatchSampler); ``indices`` is the set it draws from.
 
-    ``augment`` (an ``augment.Policy``): every batch is ``augment.apply(resident set, rows, ops)`` - the gather with
-    flips, quarter turns, shifts and erasing fused in, one launch that moves the bytes ``index_select`` moves - under
-    ops drawn from ``generator`` (a generator of ``device``) without a host synchronisation.  Labels are gathered as
-    before.  None: exactly the ``index_select`` above.  A policy with ``rotate`` / ``scale`` / ``stretch``
-    (``Policy.has_warp``) goes through ``warp.apply`` under ``Policy.draw_warp`` instead: the gather with the bilinear
-    resampling fused in, still one launch and no host synchronisation.
-
-    ``mix`` (a ``mix.Policy``, with ``nb_class``): every batch is mixed with a permutation of itself (CutMix / Mixup,
-    ``mix.apply`` from the resident set: the views are the augmented ones, still one launch) and the loader yields
-    ``(x, y_primary, Q)`` with the target distributions ``Q`` fp32 ``[B, nb_class]``.  None: nothing changes.
-
-    ``normalize`` (a ``transforms.Spec`` or its spelling): every batch is standardised per image and yielded as fp32.
-    Without an augment / mix policy ``transforms.apply`` reads the resident set through ``rows`` - the ``index_select``
-    disappears; with one, the batch the policy produced is normalised.  None: exactly the code above.
-
-    ``color`` (a ``color.Policy``): every batch is jittered by ``color.apply`` - brightness, contrast, saturation, hue
-    as one colour matrix per image, one launch - after whatever gather made it and before the normalisation, under
-    parameters drawn last from ``generator``.  Without an augment / mix policy it reads the resident set through
-    ``rows`` (no ``index_select``; the statistics contrast needs go through ``rows`` too); with a ``user-*``
-    ``normalize`` the same launch writes the normalised fp32 batch.  None: exactly the code above."""
+    ``augment``, ``mix`` (with ``nb_class``), ``color``, ``normalize`` (a ``transforms.Spec`` or its spelling) and
+    ``generator`` (a generator of ``device``): the policies of ``_batch``, which makes every batch from the resident
+    set and the batch's ``rows``; labels are gathered as before.  All None: exactly the ``index_select`` above."""
 
     def __init__(self, dataset, indices, batch_sampler, device, workers: int = 0,
                  rank: int = 0, world: int = 1, group=None, chunk: int = 16, augment=None, generator=None,
@@ -374,20 +376,8 @@ class ResidentLoader:
             self._fill()
         for batch in self.batch_sampler:
             rows = self._row_of[th.tensor(batch, dtype=th.long).to(self.device, non_blocking=True)]
-            if self.mix is not None:
-                xm, yp, q = _mixed(self.augment, self.mix, self.generator, self._x, rows,
-                                   self._y.index_select(0, rows), self.nb_class)
-                yield _finished(self.color, self.normalize, self.generator, xm, None), yp, q
-            elif self.augment is None:
-                if self.normalize is not None or self.color is not None:  # (from the resident set: no index_select)
-                    yield (_finished(self.color, self.normalize, self.generator, self._x, rows),
-                           self._y.index_select(0, rows))
-                else:
-                    yield self._x.index_select(0, rows), self._y.index_select(0, rows)
-            else:
-                yield (_finished(self.color, self.normalize, self.generator,
-                                 _augmented(self.augment, self.generator, self._x, rows), None),
-                       self._y.index_select(0, rows))
+            yield _batch(self.augment, self.mix, self.nb_class, self.color, self.normalize, self.generator, self._x,
+                         rows, self._y)
 
     def __len__(self) -> int:
         return len(self.batch_sampler)

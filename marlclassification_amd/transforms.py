@@ -325,6 +325,21 @@ def _need_source(src: th.Tensor, rows: Optional[th.Tensor], who: str) -> int:
     return nb
 
 
+def _need_out(out: Optional[th.Tensor], who: str, shape, dtype, dev, called: Optional[str] = None) -> th.Tensor:
+    """the tensor a launch writes: a fresh one, or the caller's ``out`` if it is what a fresh one would be (``called``:
+    how the message names the dtype, ``dtype`` itself if None)"""
+    if out is None:
+        return th.empty(shape, dtype=dtype, device=dev)
+    if out.device != dev or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous {called or dtype} {shape} tensor on {dev}")
+    return out
+
+
+def _user_array(spec: Spec, c: int):
+    """the pairs of a user Spec, checked against ``c`` channels, as the ``double[2 c]`` the C entries take"""
+    return (C.c_double * (2 * c))(*[v for pair in spec.user(c) for v in pair])
+
+
 def plan(src: th.Tensor, out: Optional[th.Tensor] = None) -> dict:
     """What ``stats`` / ``apply`` launch for images like ``src`` (``marl_batch_normalize_plan``): the chunk a workgroup
     reduces, the partial records per plane, load and store widths, LDS bytes.  ``src`` may live anywhere (only its shape,
@@ -372,17 +387,12 @@ def apply(src: th.Tensor, rows: Optional[th.Tensor], spec, return_coef: bool = F
     nb = _need_source(src, rows, "transforms.apply")
     _, c, h, w = src.shape
     dev = src.device
-    shape = (nb, c, h, w)
-    if out is None:
-        out = th.empty(shape, dtype=th.float32, device=dev)
-    elif out.device != dev or out.dtype != th.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"transforms.apply: out must be a contiguous float32 {shape} tensor on {dev}")
+    out = _need_out(out, "transforms.apply", (nb, c, h, w), th.float32, dev, called="float32")
     coef = th.empty(nb, c, 2, dtype=th.float32, device=dev) if return_coef else None
     if nb > 0:
         user = None
         if spec.is_user:
-            pairs = spec.user(c)
-            user = (C.c_double * (2 * c))(*[v for pair in pairs for v in pair])
+            user = _user_array(spec, c)
             records = None
         elif records is None:
             records = stats(src, rows)
