@@ -83,7 +83,8 @@ EXPORTS = (
 ).split()
 
 # kernel-level test hooks that include/marl_hip_rowops.h declares (outside the versioned ABI above)
-ROWOP_HOOKS = ("marl_ln_silu_bwd", "marl_gn_silu_bwd")
+ROWOP_HOOKS = ("marl_ln_silu_bwd", "marl_gn_silu_bwd", "marl_gn_silu_fwd", "marl_ln_silu_dot_fwd", "marl_pos_embed_fwd",
+               "marl_lstm_cell_bwd", "marl_policy_dlogits", "marl_rowdot", "marl_agg_msg")
 # ... and those of the conv kernels that include/marl_hip_cnnops.h declares
 CNNOP_HOOKS = ("marl_cnn_dgrad", "marl_cnn_dgrad_scratch", "marl_cnn_bwd_plan", "marl_cnn_fwd", "marl_cnn_fwd_plan")
 # ... and the exploration controls that include/marl_hip_explore.h declares (beside the versioned ABI, not in it)
@@ -340,6 +341,14 @@ def _declare(lib: C.CDLL) -> None:
     lib.marl_episode_report.argtypes = [_vp, _vp] + [_i] * 6 + [C.POINTER(_f), _i, _i, _vp, _sz, _vp, _sz, _vp]
     lib.marl_ln_silu_bwd.argtypes = [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _vp, _sz, _i, _i, _vp]
     lib.marl_gn_silu_bwd.argtypes = [_vp, _i64, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _vp]
+    lib.marl_gn_silu_fwd.argtypes = [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i, _i, _i, _vp, _i, _i, _vp]
+    lib.marl_ln_silu_dot_fwd.argtypes = [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]
+    lib.marl_pos_embed_fwd.argtypes = [_vp, _vp, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _i, _i64, _i, _vp]
+    lib.marl_lstm_cell_bwd.argtypes = ([_i] + [C.POINTER(_vp)] * 5 + [C.POINTER(_i)] * 5 +
+                                       [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i64, _vp])
+    lib.marl_policy_dlogits.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _f, _f, _vp]
+    lib.marl_rowdot.argtypes = [_vp, _i, _vp, _vp, _vp, _i64, _i, _vp]
+    lib.marl_agg_msg.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
     lib.marl_cnn_dgrad.argtypes = [_vp, _vp, _i] + [_vp] * 8 + [_sz, _i64, _i, _i, _i, _i, _vp]
     lib.marl_cnn_dgrad_scratch.restype = _sz
     lib.marl_cnn_dgrad_scratch.argtypes = [_i64, _i, _i, _i, _i]

@@ -740,6 +740,19 @@ struct LstmBwdBatch {
 inline bool lstm_bwd_vec4_ok(const LstmBwdArgs& a) {
     return (a.n & 3) == 0 && (a.lddh & 3) == 0 && (a.lddc & 3) == 0 && (a.ldg & 3) == 0 && (a.ldc & 3) == 0;
 }
+// one unit's arithmetic, shared by both forms: o = d(pre-activations i, f, g, o), dL/dc_prev.  Every multiply-add
+// is spelled out: left to the compiler's contraction, the one-unit and the four-unit form rounded 1 - tc * tc
+// differently (one fused, one not) and their gate gradients differed in the last place.
+__device__ __forceinline__ void lstm_cell_bwd_math(float dhv, float gi, float gf, float gg, float go, float cp, float cn,
+                                                   float dcin, float (&o)[5]) {
+    const float tc = tanh_fast(cn);
+    const float dcv = fmaf(dhv * go, fmaf(-tc, tc, 1.0f), dcin);
+    o[0] = dcv * gg * gi * (1.0f - gi);
+    o[1] = dcv * cp * gf * (1.0f - gf);
+    o[2] = dcv * gi * fmaf(-gg, gg, 1.0f);
+    o[3] = dhv * tc * go * (1.0f - go);
+    o[4] = dcv * gf;
+}
 // element (r, u) with dL/dh given
 __device__ __forceinline__ void lstm_cell_bwd_at(const LstmBwdArgs& A, int64_t r, int u, float dhv);
 __device__ __forceinline__ void lstm_cell_bwd_elem(const LstmBwdArgs& A, int64_t rows, int64_t idx) {
@@ -753,13 +766,13 @@ __device__ __forceinline__ void lstm_cell_bwd_at(const LstmBwdArgs& A, int64_t r
     const int n = A.n;
     float* g = A.gates + r * A.ldg + u;
     const float gi = g[0], gf = g[n], gg = g[2 * n], go = g[3 * n];
-    const float tc = tanh_fast(A.c_new[r * A.ldc + u]);
-    const float dcv = dhv * go * (1.0f - tc * tc) + A.dc[r * A.lddc + u];
-    g[0] = dcv * gg * gi * (1.0f - gi);
-    g[n] = dcv * A.c_prev[r * A.ldc + u] * gf * (1.0f - gf);
-    g[2 * n] = dcv * gi * (1.0f - gg * gg);
-    g[3 * n] = dhv * tc * go * (1.0f - go);
-    A.dc[r * A.lddc + u] = dcv * gf;
+    float o[5];
+    lstm_cell_bwd_math(dhv, gi, gf, gg, go, A.c_prev[r * A.ldc + u], A.c_new[r * A.ldc + u], A.dc[r * A.lddc + u], o);
+    g[0] = o[0];
+    g[n] = o[1];
+    g[2 * n] = o[2];
+    g[3 * n] = o[3];
+    A.dc[r * A.lddc + u] = o[4];
 }
 
 // four consecutive units (row r, units u .. u + 3, u % 4 == 0) given their dL/dh; same arithmetic
@@ -778,13 +791,10 @@ __device__ __forceinline__ void lstm_cell_bwd_at4(const LstmBwdArgs& A, int64_t 
     float o[5][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const float tc = tanh_fast(cn[q]);
-        const float dcv = dhv[q] * go[q] * (1.0f - tc * tc) + dcin[q];
-        o[0][q] = dcv * gg[q] * gi[q] * (1.0f - gi[q]);
-        o[1][q] = dcv * cp[q] * gf[q] * (1.0f - gf[q]);
-        o[2][q] = dcv * gi[q] * (1.0f - gg[q] * gg[q]);
-        o[3][q] = dhv[q] * tc * go[q] * (1.0f - go[q]);
-        o[4][q] = dcv * gf[q];
+        float e[5];
+        lstm_cell_bwd_math(dhv[q], gi[q], gf[q], gg[q], go[q], cp[q], cn[q], dcin[q], e);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) o[k][q] = e[k];
     }
     if (!(A.g3 && A.skip_f32)) {
 #pragma unroll

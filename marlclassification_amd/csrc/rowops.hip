@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/marl_hip_rowops.h"
 #include "common.h"
 #include "sample.h"
 
@@ -1925,6 +1926,12 @@ int launch_policy_dlogits(const float* dlogp, const float* probs, const int32_t*
     return MARL_OK;
 }
 
+// one logit's gradient p (g - s) + gl (ind - p), ind = 1[j == a], shared by the scalar and the 16-byte kernel below.
+// The multiply-add is spelled out: left to the compiler's contraction, the two kernels fused opposite products (and
+// the scalar one's remainder loop none), so their rows differed in the last place.
+__device__ __forceinline__ float dlogit_probs(float p, float g, float s, float gl, float ind) {
+    return fmaf(p, g - s, gl * (ind - p));
+}
 // softmax backward from a general dL/dprobs plus the log-prob term of the sampled action, one row
 // per thread (nA <= MARL_MAX_ACTIONS): dz_j = p_j (g_j - sum_k p_k g_k) + gl (1[j == a] - p_j)
 __global__ void policy_dlogits_probs_kernel(const float* __restrict__ dlogp,
@@ -1941,7 +1948,7 @@ __global__ void policy_dlogits_probs_kernel(const float* __restrict__ dlogp,
     const float gl = dlogp ? dlogp[r] : 0.f;
     const int a = dlogp ? actions[r] : -1;
     for (int j = 0; j < nA; ++j)
-        out[r * ld + j] = p[j] * (g[j] - s) + gl * ((j == a ? 1.0f : 0.0f) - p[j]);
+        out[r * ld + j] = dlogit_probs(p[j], g[j], s, gl, j == a ? 1.0f : 0.0f);
 }
 // the same with nA = 4 * NV: a row's probabilities and upstream gradients arrive as NV 16-byte loads each and its
 // logit gradients leave as NV 16-byte stores (the fused episode runs this over Ns * R rows: three streams of
@@ -1975,7 +1982,7 @@ __global__ __launch_bounds__(256) void policy_dlogits_probs_v4_kernel(const floa
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int j = 4 * k + q;
-            o[q] = p[j] * (g[j] - s) + gl * ((j == a ? 1.0f : 0.0f) - p[j]);
+            o[q] = dlogit_probs(p[j], g[j], s, gl, j == a ? 1.0f : 0.0f);
         }
         ov[k] = make_float4(o[0], o[1], o[2], o[3]);
     }
@@ -2029,6 +2036,10 @@ __global__ __launch_bounds__(256) void policy_dlogits_explore_kernel(const float
                                                                      const int32_t* __restrict__ actions,
                                                                      float* __restrict__ out, int ld, int64_t rows,
                                                                      int nA_rt, float inv_tau, float keep, float floor) {
+    // every operation below rounds as written (the sum's fmaf stays one operation): left to the compiler's contraction,
+    // the 16-byte instantiations folded keep * (..) into G_j - dot and the scalar one did not, so their rows differed in
+    // the last places - and only the unfused form makes G_j - dot exactly 0 where s is one-hot (one action: always)
+#pragma clang fp contract(off)
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     constexpr int CAP = NV > 0 ? 4 * NV : MARL_MAX_ACTIONS;
@@ -2149,3 +2160,142 @@ int launch_rowdot(const float* a, int lda, const float* w, const float* b, float
 }  // namespace marl
 
 extern "C" const char* marl_last_error(void) { return marl::last_error(); }
+
+// ---- kernel-level hooks of the step loop's row kernels (include/marl_hip_rowops.h; not part of the versioned ABI):
+// thin wrappers of the launchers above.  A refused call launches nothing. ----
+extern "C" {
+using namespace marl;
+
+int marl_gn_silu_fwd(const float* z, const float* gamma, const float* beta, float* out, int64_t ldo, int out_chw,
+                     float* stats, int64_t rows, int p, int c, int groups, float* cols, int ldk, int hin,
+                     void* stream) {
+    if (!z || !gamma || !beta || (!out && !cols) || rows < 0 || p < 1 || c < 1 || groups < 1 || c % groups ||
+        (out && ldo < (int64_t)p * c) || (cols && (hin < 1 || hin * hin != p || ldk < 9 * c))) {
+        set_error("marl_gn_silu_fwd: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    if (cols && !gn_fwd_im2col_supported(p, c)) {
+        set_error("fused GroupNorm + im2col needs a power-of-two channel count <= 64");
+        return MARL_ELIMIT;
+    }
+    if (rows == 0) return MARL_OK;  // (a null out reaches the flat kernels only: cols is given and supported)
+    return launch_gn_silu_fwd(z, gamma, beta, out, ldo, out_chw, stats, rows, p, c, groups,
+                              static_cast<hipStream_t>(stream), cols, ldk, hin);
+}
+
+int marl_ln_silu_dot_fwd(const float* z, int ldz, const float* gamma, const float* beta, float* out, int ldo,
+                         float* stats, int m, int n, const float* wdot, const float* bdot, float* dot_out,
+                         void* stream) {
+    if (!z || !gamma || !beta || !out || m < 0 || n < 1 || ldz < n || ldo < n || (wdot && (!bdot || !dot_out))) {
+        set_error("marl_ln_silu_dot_fwd: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    if (wdot && n > 384) {
+        set_error("fused row dot needs a LayerNorm width <= 384");
+        return MARL_ELIMIT;
+    }
+    if (m == 0) return MARL_OK;
+    return launch_ln_silu_fwd(z, ldz, gamma, beta, out, ldo, stats, m, n, static_cast<hipStream_t>(stream), wdot,
+                              bdot, dot_out);
+}
+
+int marl_pos_embed_fwd(const int32_t* pos, const float* npos_in, int h, int w, const float* weight,
+                       const float* bias, const float* gamma, const float* beta, float* npos4, float* z, int ldz,
+                       float* stats, float* out, int ldo, int64_t rows, int nd, void* stream) {
+    if ((!pos && !npos_in) || (!npos_in && (h < 1 || w < 1)) || !weight || !bias || !gamma || !beta || !z || !out ||
+        rows < 0 || nd < 1 || ldz < nd || ldo < nd) {
+        set_error("marl_pos_embed_fwd: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    if (rows == 0) return MARL_OK;
+    return launch_pos_embed_fwd(pos, npos_in, h, w, weight, bias, gamma, beta, npos4, z, ldz, stats, out, ldo, rows,
+                                nd, static_cast<hipStream_t>(stream));
+}
+
+int marl_lstm_cell_bwd(int count, const float* const* dh, float* const* dc, float* const* gates,
+                       const float* const* c_prev, const float* const* c_new, const int* lddh, const int* lddc,
+                       const int* ldg, const int* ldc, const int* n, void* const* g3, const int* g3_row0,
+                       const int* g3_steps, const int* skip_f32, int64_t rows, void* stream) {
+    if (count < 1 || count > 2 || !dh || !dc || !gates || !c_prev || !c_new || !lddh || !lddc || !ldg || !ldc || !n ||
+        rows < 0 || (g3 && (!g3_row0 || !g3_steps))) {
+        set_error("marl_lstm_cell_bwd: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    LstmBwdBatch b{};
+    bool vec4 = true;
+    for (int i = 0; i < count; ++i) {
+        char* img = g3 ? static_cast<char*>(g3[i]) : nullptr;
+        const int skip = skip_f32 ? skip_f32[i] : 0;
+        if (!dh[i] || !dc[i] || !gates[i] || !c_prev[i] || !c_new[i] || n[i] < 1 || lddh[i] < n[i] || lddc[i] < n[i] ||
+            ldc[i] < n[i] || ldg[i] / 4 < n[i] || (skip && !img) ||
+            (img && (g3_row0[i] < 0 || g3_steps[i] < (4 * n[i] + kImgStep - 1) / kImgStep ||
+                     (reinterpret_cast<uintptr_t>(img) & 15)))) {
+            set_error("marl_lstm_cell_bwd: cell %d: null pointer or bad size", i);
+            return MARL_EINVAL;
+        }
+        b.a[i] = LstmBwdArgs{dh[i], dc[i], gates[i], c_prev[i], c_new[i], lddh[i], lddc[i], ldg[i], ldc[i], n[i],
+                             img, img ? g3_row0[i] : 0, img ? g3_steps[i] : 0, skip};
+        vec4 = vec4 && lstm_bwd_vec4_ok(b.a[i]);
+    }
+    if (vec4)  // the four-wide form moves 16 bytes at a time
+        for (int i = 0; i < count; ++i)
+            if ((reinterpret_cast<uintptr_t>(dh[i]) | reinterpret_cast<uintptr_t>(dc[i]) |
+                 reinterpret_cast<uintptr_t>(gates[i]) | reinterpret_cast<uintptr_t>(c_prev[i]) |
+                 reinterpret_cast<uintptr_t>(c_new[i])) & 15) {
+                set_error("marl_lstm_cell_bwd: cell %d: the four-wide form needs 16-byte aligned pointers", i);
+                return MARL_EINVAL;
+            }
+    b.rows = rows;
+    if (rows == 0) {
+        if (!vec4 && g3)
+            for (int i = 0; i < count; ++i)
+                if (g3[i]) {
+                    set_error("lstm_cell_bwd: the gate-gradient image needs the 4-wide form");
+                    return MARL_EINVAL;
+                }
+        return MARL_OK;
+    }
+    return launch_lstm_cell_bwd_batch(b, count, static_cast<hipStream_t>(stream));
+}
+
+int marl_policy_dlogits(int form, const float* dlogp, const float* dprobs, const float* probs,
+                        const int32_t* actions, float* out, int ld, int64_t rows, int n_actions, float inv_tau,
+                        float keep, float floor, void* stream) {
+    if (form < 0 || form > 2 || !probs || !out || rows < 0 || n_actions < 1 || ld < n_actions ||
+        (form == 1 && !dprobs) || ((form == 0 || dlogp) && !actions) ||
+        (form == 2 && !(inv_tau > 0.f && keep > 0.f && keep <= 1.f && floor >= 0.f && floor < 1.f))) {
+        set_error("marl_policy_dlogits: null pointer, unknown form or bad size");
+        return MARL_EINVAL;
+    }
+    if (n_actions > MARL_MAX_ACTIONS) {
+        set_error("marl_policy_dlogits: %d actions > %d unsupported", n_actions, MARL_MAX_ACTIONS);
+        return MARL_ELIMIT;
+    }
+    if (rows == 0) return MARL_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (form == 0) return launch_policy_dlogits(dlogp, probs, actions, out, ld, rows, n_actions, st);
+    if (form == 1) return launch_policy_dlogits_probs(dlogp, dprobs, probs, actions, out, ld, rows, n_actions, st);
+    return launch_policy_dlogits_explore(dlogp, dprobs, probs, actions, out, ld, rows, n_actions, inv_tau, keep, floor,
+                                         st);
+}
+
+int marl_rowdot(const float* a, int lda, const float* w, const float* b, float* out, int64_t rows, int n,
+                void* stream) {
+    if (!a || !w || !b || !out || rows < 0 || n < 1 || lda < n) {
+        set_error("marl_rowdot: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    if (rows == 0) return MARL_OK;
+    return launch_rowdot(a, lda, w, b, out, rows, n, static_cast<hipStream_t>(stream));
+}
+
+int marl_agg_msg(const float* m, float* out, int ld, int na, int nb, int n, void* stream) {
+    if (!m || !out || na < 1 || nb < 0 || n < 1 || ld < n) {
+        set_error("marl_agg_msg: null pointer or bad size");
+        return MARL_EINVAL;
+    }
+    if (nb == 0) return MARL_OK;
+    return launch_agg_msg(m, out, ld, na, nb, n, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

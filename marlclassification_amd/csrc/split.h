@@ -1,5 +1,11 @@
-// fp32 -> three bf16 terms (x0 + x1 + x2 == x exactly, round to nearest each) and the "k16 image"
-// of an fp32 matrix that the image GEMMs of gemm3.hip consume:
+// fp32 -> three bf16 terms (x0 + x1 + x2 == x exactly, round to nearest even each, the residuals taken in fp32) and
+// the "k16 image" of an fp32 matrix that the image GEMMs of gemm3.hip consume.
+// Range of the exact-split claim: x == +-0, or 2^-103 <= |x| <= 0x7f7f7fff (the largest fp32 that still rounds to a
+// finite bf16, just under (2 - 2^-8) 2^127).  Below 2^-103 the last residual reaches under 2^-126 and is a subnormal
+// (a flushed or rounded one loses bits); from 0x7f7f8000 up the first term is an infinity and the residuals are NaN.
+// Inside the range every term is a normal bf16 or zero.  tests/image_model.py is the host model of both the split and
+// the layout; tests/test_gpu_row_fwd.py holds marl_image_build to it bit for bit inside the range and records what
+// the device returns outside it (profiles/row_fwd_errors.json).  The image:
 //     image[row / 32][k / 16][row % 32][plane 0..2][k % 16]  bf16
 // i.e. 96 bytes per row and 16-deep K step, the 32 rows of a block next to each other: one (row block,
 // K step) chunk = 3072 contiguous bytes = what three LDS-DMA instructions move, and consecutive K steps
